@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput bench of the JMID predictor hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -12,20 +12,30 @@ independent and shard across ranks (weak scaling: E episodes per GPU).  Metric: 
 N_gpus * E * N * K / time.
 
 Default workload = BASELINE.json configs[2] ("256 parallel episodes x N=5 x K=20, 1 MI355X"), the configuration the
-throughput target and the roofline are quoted on; the single-scene case (configs[1], E=1) is measured in the same run
-and reported under "single_scene".
+throughput target and the roofline are quoted on; with --full the single-scene case (configs[1], E=1) is measured in the
+same run and reported under "single_scene".
+
+Plain run and --full.  A plain run does what the headline needs and nothing else: set-up, W warm-up steps and K timed steps
+of the --precision mode, the result line.  --full adds everything else the bench measures or checks: the other precision
+modes, the untimed per-kernel profiling step and the roofline, the in-run PMC counters and the sustained-MFMA probe, the
+single-scene latency, forecaster_e2e, cpu_baseline and parity against the oracle.
+
+--dump-outputs DIR writes what the last timed step of the --precision mode returned - `positions` [E, K, N, H, 2] and
+`episode_metrics` [E, 4] - as float32 DIR/<name>.npy (<name>_rank<r>.npy on rank r of a multi-rank run; a fixed, seeded
+sample of rows past 64 MB).  Inputs and weights are seeded: the same arguments give the same inputs on every run.
 
 Precision modes.  `value` is the mode named by --precision (default f16mx: fp16 activation x split-fp16 weight with the
 weight-lo correction term as one bf8 x bf8 MFMA per k64; >= the bf16 BASELINE.json names; an OPT-IN of the drop-in predictor
 class `HumanTrajectoryForecasterSim`, whose own default is the fp32-class mode f16x3 - the line carries both:
-`config.precision` and `config.class_default_precision`, and `modes.f16x3` is the class default's number).  Every mode listed in --modes (default "f16mx,f16x2,f16x3": f16x2 = the
+`config.precision` and `config.class_default_precision`, and `modes.f16x3` is the class default's number).  Every mode listed in --modes (default with --full "f16mx,f16x2,f16x3": f16x2 = the
 same products with the correction term in fp16, f16x3 = fp32-class three-term products) gets THE SAME measurement - W warm-up steps, one untimed profiling step, K timed steps between
 barriers, parity against the oracle on the same episodes - and is reported under `modes[<name>]` with the same keys;
 the top-level keys are a copy of modes[--precision].
 
 Output.  Rank 0 prints ONE COMPACT JSON line (< 4 KB: the contract keys, `roofline`, `cpu_baseline`, `parity`, one short row per
 mode) as the last line of stdout; everything else (notes, sources, per-kernel tables, forecaster_e2e, worker scaling, the full
-per-mode blocks) goes to the file named by `detail` in that line (--detail, default bench_detail.json next to this script).
+per-mode blocks) goes to the file named by `detail` in that line (--detail, default bench_detail.json next to this script; a
+fresh file in the temporary directory when that cannot be written, as in a read-only checkout).
 """
 import argparse
 import hashlib
@@ -95,6 +105,40 @@ def git_blob_sha1(path):
     """`git hash-object` of a file: lets a reader check which committed profile a bench field was taken from."""
     data = open(path, "rb").read()
     return hashlib.sha1(b"blob %d\0" % len(data) + data).hexdigest()
+
+
+def write_detail(full, path):
+    """The long result as JSON at `path`; where that cannot be written (a read-only checkout), at a fresh file in the temporary
+    directory instead.  Returns the path written."""
+    text = json.dumps(full, indent=1)
+    try:
+        with open(path, "w") as fh:
+            fh.write(text)
+        return path
+    except OSError as ex:
+        import tempfile
+        fd, tmp = tempfile.mkstemp(prefix="bench_detail_", suffix=".json")
+        with os.fdopen(fd, "w") as fh:
+            fh.write(text)
+        log(f"cannot write {path} ({ex.strerror}): full result goes to {tmp}")
+        return tmp
+
+
+DUMP_LIMIT = 64 << 20           # bytes, all files of one --dump-outputs call together
+
+
+def dump_outputs(out_dir, arrays, rank=None):
+    """`arrays` (name -> device tensor) as float32 `out_dir/<name>.npy` (`<name>_rank<r>.npy` for rank r of a multi-rank run).
+    An array that would take the files past DUMP_LIMIT keeps a fixed, seeded sample of its rows (first axis), in row order."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget and a.shape[0] > 1:
+            keep = max(1, budget * a.shape[0] // a.nbytes)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank is not None else "") + ".npy"), np.ascontiguousarray(a))
 
 
 def pmc_summary(mode):
@@ -448,8 +492,9 @@ def main():
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
     ap.add_argument("--episodes-per-gpu", type=int, default=0)
     ap.add_argument("--precision", default="f16mx", choices=["f32", "f16x3", "f16x2", "f16mx"], help="the mode `value` is quoted on")
-    ap.add_argument("--modes", default="f16mx,f16x2,f16x3",
-                    help="comma list of modes measured identically in this run (the --precision mode is always included)")
+    ap.add_argument("--modes", default=None,
+                    help="comma list of modes measured identically in this run (the --precision mode is always included; "
+                         "default: the --precision mode alone, with --full f16mx,f16x2,f16x3)")
     ap.add_argument("--net", default="jmid", choices=["jmid", "imid"])
     ap.add_argument("--chunk", type=int, default=0, help="episodes per pass of the denoise loop (0 = auto)")
     ap.add_argument("--cpu-episodes", type=int, default=-1,
@@ -479,11 +524,26 @@ def main():
                     help="do not re-run one 51-episode call under rocprofv3 --pmc after the timed region (roofline.traffic / mfma_busy "
                          "then come from the committed profiles/ summary, labelled as such) and do not run the sustained-MFMA probe")
     ap.add_argument("--detail", default=os.path.join(REPO, "bench_detail.json"),
-                    help="file the full (long) result goes to; the stdout line stays compact and names this path")
+                    help="file the full (long) result goes to (a file in the temporary directory when it cannot be written); "
+                         "the stdout line stays compact and names the file written")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group and run every collective even with one rank (exercises the RCCL calls "
                          "of the N > 1 path on a one-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the other precision modes, the per-kernel profiling "
+                         "step and roofline, in-run PMC counters and the sustained-MFMA probe, single-scene latency, forecaster_e2e, "
+                         "cpu_baseline and parity against the oracle (each still subject to its own --no-* / --cpu-episodes switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (positions, per-episode metrics) "
+                         "as float32 .npy files into DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.modes is None:
+        args.modes = "f16mx,f16x2,f16x3" if args.full else args.precision
+    if not args.full:
+        # a plain run measures the headline alone: no profiling step, no counters, no extra legs after the timed steps
+        args.no_profile, args.no_pmc, args.no_e2e, args.cpu_episodes = True, True, True, 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched plainly (`python bench.py --gpus N`): spawn the N ranks ourselves, one process per GPU, with the
@@ -644,6 +704,7 @@ def main():
             every = [torch.zeros_like(mine) for _ in range(world)]
             dist.all_gather(every, mine)
             rank_ms = [1e3 * float(v.item()) / args.steps for v in every]
+        step_out = {"positions": pos, "episode_metrics": met}     # what the last timed step returned (--dump-outputs)
         # the sweep's ONE collective: the per-episode metric rows of the last step, gathered to rank 0 after the timed steps
         #  and timed on its own - it is off the data path and says nothing about the kernels
         # (a fifth column, added outside the timed steps: the GLOBAL index of the episode a row belongs to, so that rank 0 can see that
@@ -712,12 +773,16 @@ def main():
                                     "mean_minADE_m": float(np.nanmean(allm[:, 1])),
                                     "mean_FDE_m": float(np.nanmean(allm[:, 2])),
                                     "rows_in_episode_order": bool(np.array_equal(allm[:, -1], np.arange(allm.shape[0], dtype=allm.dtype)))}
-        return res, pos
+        return res, step_out
 
     log(f"inputs resident: E={E} A={A} K={K} H={H} modes={modes} world={world} backend={args.dist_backend}")
-    results, last_pos = {}, {}
+    results, last_out = {}, {}
     for m in modes:
-        results[m], last_pos[m] = measure(m)
+        results[m], last_out[m] = measure(m)
+    last_pos = {m: o["positions"] for m, o in last_out.items()}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out[args.precision], rank if world > 1 else None)
+        log(f"outputs of the last timed step -> {args.dump_outputs}")
 
     if rank != 0:
         if use_dist:
@@ -727,8 +792,8 @@ def main():
 
     # ---- PMC counters of THIS run's build on THIS box (headline mode): one whole 51-episode call re-run under rocprofv3,
     # one counter group per pass (kernel-trace + pmc only), after the timed region; the other modes - and this one if
-    # rocprofv3 is missing or a pass fails - fall back to the committed profiles/ summary of the mode
-    for m in modes:
+    # rocprofv3 is missing or a pass fails - fall back to the committed profiles/ summary of the mode (--full only)
+    for m in (modes if args.full else ()):
         pmc, src = None, None
         if m == args.precision and world == 1 and not args.no_pmc and joint and (N, K, H, steps50) == (5, 20, 12, 50):
             try:
@@ -803,7 +868,7 @@ def main():
     # ONE synchronisation (PCIe both ways included: 9.6 KB per trajectory set).  `staged_ms_per_call`: the same work as two entries on
     # device tensors (jmid_encode + jmid_denoise, each ordered against the caller's stream, a range-flag round trip per call) - what
     # rounds 2-5 quoted here.
-    if world == 1:
+    if world == 1 and args.full:
         ctx1 = eng.encode(x_st[:A], nbr[:A], emask[:A]).view(1, A, -1)
         hx, hn, he = (t[:A].cpu().numpy() for t in (x_st, nbr, emask))
         hxT, hp0 = x_T[:1].cpu().numpy(), p0[:1].cpu().numpy()
@@ -835,7 +900,7 @@ def main():
             ss[m].update({"ms_per_call": round(1e3 * dt1, 3), "traj_per_s": round(A * K / dt1, 1)})
         out["single_scene"] = dict(ss[args.precision], workload=f"cfg2: 1 scene x N={N} x K={K} x H={H}, {steps50} steps",
                                    modes=ss)
-    log("single-scene done")
+        log("single-scene done")
     if world == 1 and not args.no_e2e and joint:
         out["forecaster_e2e"] = forecaster_e2e(weights, dev_id, modes)
         log("forecaster end-to-end done")
@@ -933,8 +998,7 @@ def main():
             results[m]["parity"] = {"mean_ADE_vs_oracle_m": ade, "gate_m": 1e-4, "episodes": ne, "pass": ade <= 1e-4,
                                     "episode_ids": pick, "precision": m}
         out["parity"] = results[args.precision]["parity"]
-    with open(args.detail, "w") as fh:
-        json.dump(out, fh, indent=1)
+    args.detail = write_detail(out, args.detail)
     log(f"full result -> {args.detail} ({os.path.getsize(args.detail)} bytes)")
     for m in modes:
         rr = results[m].get("roofline") or {}

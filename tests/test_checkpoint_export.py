@@ -1,57 +1,96 @@
 """export_checkpoint on a checkpoint in the REFERENCE'S OWN pickled format.
 
-The trained blobs are absent (/root/reference/.MISSING_LARGE_BLOBS), so every parity number in this repo is on
-random-init weights - but the container format can still be exercised for real: the reference's own module tree builds
-the predictor (tests/golden/make_golden.py::make_forecaster, seeded weights), MID._save_model's dict
+The trained blobs are absent, so every parity number in this repo is on random-init weights - but the container format can
+still be exercised for real: tests/golden/make_golden_checkpoint.py had the reference's own module tree build the predictor
+(tests/golden/make_golden.py::make_forecaster, seeded weights) and wrote MID._save_model's dict
 ({"encoder": registrar.model_dict - a pickled nn.ModuleDict of the reference's classes -, "ddpm": model.state_dict()},
-sicnav_diffusion/JMID/MID/mid.py:1501-1509) is written with torch.save, and the exporter has to unpickle it the way
-mid.py:1230-1232 does, pick the live tensors out of it (the state dict also carries the never-executed template
-`layer.*` and the var_sched buffers; the ModuleDict every encoder module the registrar created) and reproduce them
-bit for bit.  Needs the reference tree importable: runs in the build container, skipped on the GPU box."""
-import importlib.util
+sicnav_diffusion/JMID/MID/mid.py:1501-1509) with torch.save to tests/golden/ckpt_ref_*_w32.pt.xz, together with one net
+evaluation of the reference on it.  The exporter has to unpickle it the way mid.py:1230-1232 does - with the reference's
+module tree on sys.path, here a stand-in tree of empty nn.Module classes under the names the pickle refers to - pick the live
+tensors out of it (the state dict also carries the never-executed template `layer.*` and the var_sched buffers; the
+ModuleDict every encoder module the registrar created) and reproduce them bit for bit."""
+import importlib
+import lzma
 import os
+import pickletools
 import sys
+import zipfile
 
 import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "sicnav_diffusion")),
-                                reason="needs the reference tree (build container only)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.fixture(scope="module")
-def golden_tools():
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden.py")
-    argv = sys.argv
-    sys.argv = [path]                    # the module reads sys.argv[1] as a fixture-name filter at import
+def _pickled_globals(pt):
+    """(module, name) of every class / function the checkpoint's pickle refers to (torch.save writes protocol 2: GLOBAL)."""
+    with zipfile.ZipFile(pt) as z:
+        data = z.read(next(n for n in z.namelist() if n.endswith("/data.pkl")))
+    return {tuple(arg.split(" ", 1)) for op, arg, _ in pickletools.genops(data) if op.name == "GLOBAL"}
+
+
+def _importable(mod):
     try:
-        spec = importlib.util.spec_from_file_location("make_golden_for_export_test", path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)     # installs the import shims and imports the reference; generates nothing
-    finally:
-        sys.argv = argv
-    return mod
+        importlib.import_module(mod)
+        return True
+    except ImportError:
+        return False
+
+
+@pytest.fixture
+def stand_in_root(tmp_path):
+    """A directory to pass as reference_root; the test writes the stand-in module tree into it.  Afterwards the modules it
+    imported and the sys.path entries the exporter added are removed again."""
+    root = tmp_path / "reference"
+    root.mkdir()
+    mods, path = set(sys.modules), list(sys.path)
+    yield root
+    for m in set(sys.modules) - mods:
+        del sys.modules[m]
+    sys.path[:] = path
+
+
+def _write_stand_ins(root, pt):
+    """Empty nn.Module subclasses under every module path of the pickle that is not importable here (the reference's classes):
+    unpickling an nn.Module restores its __dict__ (parameters, buffers, submodules) and needs nothing of the class but its name."""
+    by_mod = {}
+    for mod, name in _pickled_globals(pt):
+        if not _importable(mod):
+            by_mod.setdefault(mod, set()).add(name)
+    assert by_mod, "the checkpoint refers to no class of the reference"
+    for mod, names in by_mod.items():
+        parts, d = mod.split("."), root
+        for p in parts[:-1]:
+            d = d / p
+            d.mkdir(exist_ok=True)
+            (d / "__init__.py").touch()
+        (d / (parts[-1] + ".py")).write_text("import torch\n" + "".join(f"\n\nclass {n}(torch.nn.Module):\n    pass\n"
+                                                                         for n in sorted(names)))
 
 
 @pytest.mark.parametrize("joint", [True, False])
-def test_exporter_reads_a_checkpoint_pickled_by_the_reference_classes(joint, golden_tools, tmp_path):
+def test_exporter_reads_a_checkpoint_pickled_by_the_reference_classes(joint, stand_in_root, tmp_path):
     from safe_interactive_crowdnav_amd import export_checkpoint, forecaster
     from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims
 
     dims = NetDims(ctx_dim=32)
-    f, weights = golden_tools.make_forecaster(joint, 32, N=3, K=4, k_ret=4, H=8, step=2, wseed=61)
-    mid = f.mid_model
-    ckpt = {"encoder": mid.registrar.model_dict, "ddpm": mid.model.state_dict()}       # MID._save_model, mid.py:1501-1509
+    tag = f"ckpt_ref_{'jmid' if joint else 'imid'}_w32"
+    ev = np.load(os.path.join(GOLDEN, tag + "_eval.npz"))
+    weights = JMIDWeights.from_seed(dims, int(ev["wseed"]))
+    assert weights.checksum() == str(ev["wsum"])                                       # the weights the reference was filled with
     pt = str(tmp_path / "sim_epoch1.pt")
-    torch.save(ckpt, pt)
+    with lzma.open(os.path.join(GOLDEN, tag + ".pt.xz")) as src, open(pt, "wb") as dst:
+        dst.write(src.read())
+    REF = str(stand_in_root)
+    _write_stand_ins(stand_in_root, pt)
+
+    out = export_checkpoint.export(pt, str(tmp_path / "sim_epoch1.npz"), dims, reference_root=REF)
+    ckpt = torch.load(pt, map_location="cpu", weights_only=False)          # (the exporter put the module tree on sys.path)
     sd = ckpt["ddpm"]
     assert any(k.startswith("vel_predictor.net.layer.") for k in sd) or not joint      # template copy rides along (JMID)
     assert any(k.startswith("vel_predictor.var_sched.") for k in sd)
-    assert len(mid.registrar.model_dict) >= 5                                           # more modules than the 5 live ones
-
-    out = export_checkpoint.export(pt, str(tmp_path / "sim_epoch1.npz"), dims, reference_root=REF)
+    assert len(ckpt["encoder"]) >= 5                                                    # more modules than the 5 live ones
     w = JMIDWeights.load(out)
     assert w.dims == dims and w.checksum() == weights.checksum()                        # every live tensor, bit for bit
     # the predictor's loader finds the export next to the .pt path the yaml names (forecaster.load_weights)
@@ -61,13 +100,9 @@ def test_exporter_reads_a_checkpoint_pickled_by_the_reference_classes(joint, gol
     out2 = str(tmp_path / "cli.npz")
     export_checkpoint.main([pt, "-o", out2, "--encoder-dim", "32", "--tf-layer", "3", "--reference-root", REF])
     assert JMIDWeights.load(out2).checksum() == weights.checksum()
-    # sanity: what was exported is what the reference itself computes with (one net evaluation)
-    net = mid.model.vel_predictor.net.eval()       # dropout off, as in inference
-    g = torch.Generator().manual_seed(1)
-    x, ctx = torch.randn([4, 8, 2], generator=g), torch.randn([4, 32], generator=g)
-    beta = mid.model.vel_predictor.var_sched.betas[[100] * 4]
+    # sanity: what was exported is what the reference itself computes with (one net evaluation, stored by the generator)
+    x, ctx, beta = (torch.from_numpy(ev[k]) for k in ("x", "ctx", "beta"))
     from oracle import jmid_oracle as O
     with torch.no_grad():
-        e_ref = net([x, ctx], beta=beta)
         e_ours = O.net_forward(w.tensors, x, ctx, beta, joint=joint)
-    np.testing.assert_allclose(e_ours.numpy(), e_ref.numpy(), rtol=0, atol=1e-6)
+    np.testing.assert_allclose(e_ours.numpy(), ev["e_ref"], rtol=0, atol=1e-6)

@@ -25,9 +25,11 @@ def test_schedule_matches_reference_buffers():
     z = np.load(os.path.join(GOLDEN, "schedule.npz"))
     s = VarianceSchedule.linear()
     np.testing.assert_array_equal(s.betas, z["betas"])
-    np.testing.assert_array_equal(s.alpha_bars, z["alpha_bars"])
-    np.testing.assert_array_equal(s.sigmas_inflex, z["sigmas_inflex"])
-    np.testing.assert_array_equal(s.sigmas_flex, z["sigmas_flex"])
+    # exp / log / sqrt of a torch CPU tensor go through MKL, whose vector code path depends on the CPU: the buffers derived
+    # from them are bit-equal on the CPU the fixture was made on and within a few ulp on others (2 / 1 / 4 seen)
+    np.testing.assert_array_max_ulp(s.alpha_bars, z["alpha_bars"], maxulp=4)
+    np.testing.assert_array_max_ulp(s.sigmas_inflex, z["sigmas_inflex"], maxulp=4)
+    np.testing.assert_array_max_ulp(s.sigmas_flex, z["sigmas_flex"], maxulp=4)
 
 
 def test_ddpm_table_flexibility():

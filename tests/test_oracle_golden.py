@@ -22,8 +22,12 @@ def _weights(z):
 def test_schedule_matches_reference():
     z = np.load(os.path.join(GOLDEN, "schedule.npz"))
     s = O.variance_schedule()
-    for k in ("betas", "alphas", "alpha_bars", "sigmas_flex", "sigmas_inflex"):
+    for k in ("betas", "alphas"):
         np.testing.assert_array_equal(s[k].numpy(), z[k], err_msg=k)
+    # exp / log / sqrt of a torch CPU tensor go through MKL, whose vector code path depends on the CPU: the buffers derived
+    # from them are bit-equal on the CPU the fixture was made on and within a few ulp on others (2 / 1 / 4 seen)
+    for k in ("alpha_bars", "sigmas_flex", "sigmas_inflex"):
+        np.testing.assert_array_max_ulp(s[k].numpy(), z[k], maxulp=4)
     # spot values recorded in SURVEY.md 8(a6)
     assert s["betas"][1].item() == pytest.approx(9.9999997e-05, rel=1e-7)
     assert s["alpha_bars"][100].item() == pytest.approx(0.078234285, rel=1e-6)

@@ -39,7 +39,7 @@ def collect(mode="f16mx", episodes=51, timeout_s=240, keep_dir=None):
             cmd = [rp, "--kernel-trace", "--pmc", c, "--output-format", "csv", "-d", d, "--", sys.executable,
                    os.path.join(REPO, "tools", "step_only.py"), str(episodes)]
             try:
-                p = subprocess.run(cmd, cwd=REPO, env=env, timeout=timeout_s, capture_output=True, text=True, start_new_session=True)
+                p = subprocess.run(cmd, cwd=work, env=env, timeout=timeout_s, capture_output=True, text=True, start_new_session=True)
             except subprocess.TimeoutExpired:
                 return None
             if p.returncode != 0:

@@ -11,5 +11,5 @@ O=gpurun_out/${R:-r06a}; mkdir -p $O
  echo "== one workgroup per CU"; ONE_WG=1 timeout 120 build/attn_check 51 1200 20 0
 ) 2>&1 | grep -v amdgpu.ids > $O/attn_check.log
 timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_baseline_sizes.py -x -q -m gpu > $O/parity.log 2>&1; echo "parity rc $?" >> $O/parity.log
-timeout 600 python bench.py --steps 5 --warmup 2 --no-pmc --no-e2e --detail $O/bench_cfg3.json > $O/bench_cfg3.line.json 2> $O/bench_cfg3.stderr.log
+timeout 600 python bench.py --full --steps 5 --warmup 2 --no-pmc --no-e2e --detail $O/bench_cfg3.json > $O/bench_cfg3.line.json 2> $O/bench_cfg3.stderr.log
 tail -3 $O/parity.log; cat $O/attn_check.log; cat $O/bench_cfg3.line.json

@@ -11,11 +11,11 @@ for n in names:
         shutil.copy(f"{src}/{n}", f"{dst}/{R}_{n}")
 if os.path.exists(f"{src}/bench_cfg3.err"):
     shutil.copy(f"{src}/bench_cfg3.err", f"{dst}/{R}_bench_cfg3.stderr.log")
-hdr = {"f16mx": "python bench.py --precision f16mx --modes f16mx --lanes 1 --steps 1 --warmup 0 --cpu-episodes 0 --episodes-per-gpu 51",
-       "cfg2_f16mx": "python bench.py --workload cfg2 --modes f16mx --steps 20 --warmup 3 --cpu-episodes 0 --no-profile",
-       "f16x2": "python bench.py --precision f16x2 --modes f16x2 --lanes 1 --steps 1 --warmup 0 --cpu-episodes 0 --episodes-per-gpu 51",
-       "f16x3": "python bench.py --precision f16x3 --modes f16x3 --lanes 1 --steps 1 --warmup 0 --cpu-episodes 0 --episodes-per-gpu 51",
-       "cfg2_f16x2": "python bench.py --workload cfg2 --modes f16x2 --steps 20 --warmup 3 --cpu-episodes 0 --no-profile"}
+hdr = {"f16mx": "python bench.py --full --precision f16mx --modes f16mx --lanes 1 --steps 1 --warmup 0 --cpu-episodes 0 --episodes-per-gpu 51",
+       "cfg2_f16mx": "python bench.py --full --workload cfg2 --modes f16mx --steps 20 --warmup 3 --cpu-episodes 0 --no-profile",
+       "f16x2": "python bench.py --full --precision f16x2 --modes f16x2 --lanes 1 --steps 1 --warmup 0 --cpu-episodes 0 --episodes-per-gpu 51",
+       "f16x3": "python bench.py --full --precision f16x3 --modes f16x3 --lanes 1 --steps 1 --warmup 0 --cpu-episodes 0 --episodes-per-gpu 51",
+       "cfg2_f16x2": "python bench.py --full --workload cfg2 --modes f16x2 --steps 20 --warmup 3 --cpu-episodes 0 --no-profile"}
 for tag, cmd in hdr.items():
     f = f"{src}/{tag}_kernel_stats.csv"
     if os.path.exists(f):
