@@ -153,9 +153,6 @@ struct Tuning {
     int lnx_withhold = 0;    // diagnostics: 1 = one workgroup of an OUT_LNX launch never publishes its statistics (the give-up path under test)
     int small_lnx2 = 0;      // ... for launches of 33 ... 64 row tiles (two scenes' worth of tokens; the reference's shipped K = 100) with TWO workgroups per CU: 0 on, 2 off (GEMM + add_ln2 [+ attn_combine])
     int gemm_pn = 0;         // F16MX large-tile GEMMs: column groups of the XCD tile order (0 / 1 = N fastest over all N-tiles)
-    int one_chunk = 1;       // set per call by run_network: the call is ONE chunk (OUT_LNX of gemm_small.hpp only then, whatever the lanes: a call's bits do not depend on its chunk plan)
-    int small_now = 1;       // set per call by run_network: the small-launch kernels only while ONE chunk is in flight (with two lanes their
-                             // one-workgroup-per-CU launches collide: 4 episodes as 2 x 2 measured 4 % slower with them)
     int small_lanes = 0;     // experiment: the small-launch kernels with several chunks in flight too: 1 = all of them, 2 = only the two-workgroups-per-CU shape
     int small_qk = 0;        // Q / K tiles of a small in_proj launch out through LDS in full rows: 0 / 1 on, 2 = the generic element-wise epilogue
     int small_pn = 0;        // its column groups per launch (two-dimensional XCD tile order): 0 = fewest Infinity-Cache bytes, 1 / 2 / 4 / 8 forced

@@ -1620,12 +1620,13 @@ inline hipError_t launch_gemm_h_mode(const GemmHArgs& g, hipStream_t st) {
 // launches of at most one workgroup per CU: gemm_small.hpp (defined after the LayerNorm headers it builds on)
 template <int EPI, int OUT>
 inline hipError_t launch_gemm_small(const GemmHArgs& g, int wc, hipStream_t st);
-inline int small_gemm_shape(const GemmHArgs& g);
+inline int small_gemm_shape(const GemmHArgs& g, int small_now);
 
 // the arithmetic mode is a template parameter of every kernel (a run-time flag in the K loops cost F16X3 4 %)
+// small_now: may the small-launch kernels run (gemm_small.hpp::small_gemm_shape; a fact of the call, not a knob)
 template <int EPI, int OUT>
-inline hipError_t launch_gemm_h(const GemmHArgs& g, hipStream_t st) {
-    if (const int wc = small_gemm_shape(g)) return launch_gemm_small<EPI, OUT>(g, wc, st);      // at most one workgroup per CU
+inline hipError_t launch_gemm_h(const GemmHArgs& g, hipStream_t st, int small_now = 1) {
+    if (const int wc = small_gemm_shape(g, small_now)) return launch_gemm_small<EPI, OUT>(g, wc, st);      // at most one workgroup per CU
     return g.x2 ? launch_gemm_h_mode<EPI, OUT, true>(g, st) : launch_gemm_h_mode<EPI, OUT, false>(g, st);
 }
 

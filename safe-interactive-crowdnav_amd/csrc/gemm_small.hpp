@@ -710,11 +710,13 @@ inline hipError_t launch_gemm_small_cfg(const GemmHArgs& g, hipStream_t st) {
 
 // Does this GEMM run on the small-launch kernel, and in which shape?  One workgroup per CU: at most 256 tiles.
 //   -> 0 no, 2 / 4 = WC, 8 = WC 4 with two workgroups per CU.  "gemm_small" knob: 0 auto, 1 never.
-inline int small_gemm_shape(const GemmHArgs& g) {
-    if (tune().gemm_small == 1 || tune().gemm_h_variant != 0 || !tune().small_now) return 0;
+// small_now (a fact of the call: the planner's CallFacts): 1 = one chunk in flight, 0 = several - with two lanes the
+// one-workgroup-per-CU launches collide: 4 episodes as 2 x 2 measured 4 % slower with them -, 2 = experiment "small_lanes" = 2
+inline int small_gemm_shape(const GemmHArgs& g, int small_now) {
+    if (tune().gemm_small == 1 || tune().gemm_h_variant != 0 || !small_now) return 0;
     if (g.K % 128 != 0 || g.N % 128 != 0) return 0;       // (k128 ring stages)
     const long ntm = (g.M + 63) / 64;
-    if (tune().small_now == 2) return g.x2 && ntm * (g.N / 128) <= 512 ? 8 : 0;      // (experiment "small_lanes" = 2)
+    if (small_now == 2) return g.x2 && ntm * (g.N / 128) <= 512 ? 8 : 0;      // (experiment "small_lanes" = 2)
     if (ntm * (g.N / 64) <= 256) return 2;
     if (ntm * (g.N / 128) <= 256) return 4;
     // 257 ... 512 tiles of 64 x 128 (two scenes; the reference's shipped K = 100): the same kernel, two workgroups per CU
@@ -747,14 +749,14 @@ inline bool small_cmb_fits(int nsplit, int head_dim, int x2) {
 
 
 // does out_proj / linear2 + residual + LayerNorm run as ONE small launch with the statistics exchange (OUT_LNX)?  F16MX at d_model 512,
-// nothing else in flight on the handle, calls of ONE chunk (a call's bits must not depend on its chunk plan or its lanes), and EVERY
-// workgroup of the launch resident at once - the waiting workgroups need their partners: 8 workgroups per 64-row tile against the
+// nothing else in flight on the handle (small_now == 1), calls of ONE chunk (one_chunk: whatever the lanes, a call's bits must not
+// depend on its chunk plan), and EVERY workgroup of the launch resident at once - the waiting workgroups need their partners: 8 workgroups per 64-row tile against the
 // device's compute units (Tuning::cus, from hipDeviceProp_t::multiProcessorCount at jmid_create - a partitioned or smaller device
 // takes the unfused pair), one per CU, or two per CU on half the LDS each, and at most SM_LNX_MAX_TILES row tiles (the exchange
 // buffer).  "small_lnx" = 2: off (GEMM + add_ln2, the same bits).
-inline int small_lnx_fits(int M, int K) {       // 0 no; 2: one workgroup per CU; 9: two per CU ("small_lnx2" = 2 off)
+inline int small_lnx_fits(int M, int K, int small_now, int one_chunk) {       // 0 no; 2: one workgroup per CU; 9: two per CU ("small_lnx2" = 2 off)
     const long ntm = (M + 63) / 64;
-    if (!(tune().gemm_small != 1 && tune().small_now == 1 && tune().one_chunk == 1 && tune().gemm_h_variant == 0 && tune().small_lnx != 2 && K % 128 == 0)) return 0;
+    if (!(tune().gemm_small != 1 && small_now == 1 && one_chunk == 1 && tune().gemm_h_variant == 0 && tune().small_lnx != 2 && K % 128 == 0)) return 0;
     if (ntm * 8 <= tune().cus && ntm <= SM_LNX_MAX_TILES) return 2;
     return ntm * 8 <= 2L * tune().cus && ntm <= SM_LNX_MAX_TILES && tune().small_lnx2 != 2 ? 9 : 0;
 }

@@ -126,13 +126,8 @@ int jmid_destroy(jmid_handle_t h) {
     hipSetDevice(h->device);
     sync_lanes(h);
     drop_graphs(h);
+    free_planes(h);
     for (auto& kv : h->w) hipFree(kv.second.p);
-    for (auto* m : {&h->wsplit, &h->w16})
-        for (auto& kv : *m) {
-            hipFree(kv.second.hi);
-            hipFree(kv.second.lo);
-        }
-    for (auto& kv : h->w8) hipFree(kv.second.p);
     if (h->range_flag) hipFree(h->range_flag);
     if (h->ev_in) hipEventDestroy(h->ev_in);
     if (h->ev_out) hipEventDestroy(h->ev_out);
@@ -203,7 +198,7 @@ int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* n
         ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
         ea.edge[0] = LstmW{h->lstmT[1][0], h->lstmT[1][1], h->lstmT[1][2]};
         ea.edge[1] = LstmW{h->lstmT[2][0], h->lstmT[2][1], h->lstmT[2][2]};
-        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = W(h, "PEDESTRIAN/edge_influence_encoder.v.weight");
+        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = h->wt.edge_v;
         ea.ctx = co; ea.n = n_agents; ea.Th = Th; ea.H = H;
         HIPCHK(h, launch_encoder(ea, h->stream));
     }
@@ -377,7 +372,7 @@ int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float
         ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
         ea.edge[0] = LstmW{h->lstmT[1][0], h->lstmT[1][1], h->lstmT[1][2]};
         ea.edge[1] = LstmW{h->lstmT[2][0], h->lstmT[2][1], h->lstmT[2][2]};
-        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = W(h, "PEDESTRIAN/edge_influence_encoder.v.weight");
+        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = h->wt.edge_v;
         ea.ctx = dev + o_ctx; ea.n = (int)n; ea.Th = (int)Th; ea.H = h->H;
         if (launch_encoder(ea, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, "jmid_predict: encoder launch failed");
     }

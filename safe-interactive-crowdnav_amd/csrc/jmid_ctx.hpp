@@ -66,6 +66,26 @@ struct HalfPair {
     half_t* lo = nullptr;
 };
 
+// The weights one net evaluation reads, resolved to plain pointers once (by jmid_finalize_weights, as it makes the operand planes;
+// emptied wherever the buffers they point into go away).  The name-keyed maps of the handle stay the owners of the memory.
+struct LinearW {
+    const float *W = nullptr, *bias = nullptr;   // fp32 [N, K] and [N]
+    HalfPair split;                              // blocked hi / lo fp16 planes (the split-fp16 GEMMs)
+    HalfPair k16;                                // k16 panels: out_proj / linear2 at d_model 512 (the row-tile GEMM + LayerNorm), null elsewhere
+    const unsigned char* w8 = nullptr;           // bf8 image of W_lo (JMID_PREC_F16MX), null where the shape has none
+};
+struct NormW {
+    const float *gamma = nullptr, *beta = nullptr;
+};
+struct LayerW {
+    LinearW in_proj, out_proj, linear1, linear2;
+    NormW norm1, norm2;
+};
+struct WeightTable {
+    std::vector<LayerW> layers;
+    LinearW concat1, concat3, concat4, linear;   // (concat1 and linear: fp32 only)
+    const float* edge_v = nullptr;               // PEDESTRIAN/edge_influence_encoder.v.weight (the encoder kernel)
+};
 
 struct jmid_ctx {
     int device = 0;
@@ -79,7 +99,7 @@ struct jmid_ctx {
     // attention workgroups of the other lane computed a few wrong values per run - packed-fp32 instructions with crossed
     // operand selects, which the library is no longer built with; build.py, docs/NOTEBOOK.md section 3.)
     int lanes = 2;
-    Tuning tune;         // jmid_set_tuning knobs of THIS handle (installed per call by TuneScope)
+    Tuning tune;         // jmid_set_tuning knobs of THIS handle (installed per call by TuneScope; `cus` is set by jmid_create)
     hipStream_t caller_stream = nullptr;   // stream device-mode buffers are ordered on (jmid_set_caller_stream)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     // captured denoise loops of small calls (one chunk): key = (E, A, K, T, precision) -> executable graph
@@ -117,6 +137,7 @@ struct jmid_ctx {
     std::map<std::string, W8Image> w8;       // JMID_PREC_F16MX: fp8 images of W_lo (w8_image_kernel), keyed like wsplit
     int mx = 0;          // the running call is JMID_PREC_F16MX (x2 is set as well: everything not on the fp8 path runs as F16X2)
     std::map<std::string, HalfPair> w16;     // k16-panel copies of out_proj / linear2 for the fused GEMM + LayerNorm
+    WeightTable wt;                          // what the launches read: pointers into the five maps above, valid while `finalized`
     int* range_flag = nullptr;               // device word: an fp16 operand left the fp16 range
     bool weights_in_half_range = true;
     bool finalized = false;
@@ -204,14 +225,13 @@ inline size_t numel(const std::vector<size_t>& s) {
     return n;
 }
 
-inline const float* W(jmid_ctx* h, const std::string& name) { return h->w[name].p; }
-
 // jmid_weights.hip
 void register_shapes(jmid_ctx* h);
 int dev_alloc_copy(jmid_ctx* h, float** out, const std::vector<float>& host);
 int fetch_host(jmid_ctx* h, const std::string& name, std::vector<float>& out);
 int upload_time_table(jmid_ctx* h);
 int make_w8(jmid_ctx* h, const float* dW, int N, int K, jmid_ctx::W8Image* out);
+void free_planes(jmid_ctx* h);
 // jmid_planner.hip
 void drop_graphs(jmid_ctx* h);
 void sync_lanes(jmid_ctx* h);

@@ -220,10 +220,11 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
         g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.W8 = img.p; g.bias = dB; g.C = dY; g.ldc = N; g.M = M; g.N = N; g.K = K;
         if (fused == 3) {        // the small-launch kernel with the statistics exchange (gemm_small.hpp, OUT_LNX)
             unsigned long long* xs = (unsigned long long*)dalloc(kLnxWords * sizeof(unsigned), nullptr);
-            if (!xs || !small_lnx_fits(M, K)) return fail(h, JMID_EINVAL, "jmid_dbg_gemm_ln_mx: shape does not take the small kernel with the statistics exchange");
+            const int shape = small_lnx_fits(M, K, 1, 1);      // (an idle handle: nothing else in flight, one launch)
+            if (!xs || !shape) return fail(h, JMID_EINVAL, "jmid_dbg_gemm_ln_mx: shape does not take the small kernel with the statistics exchange");
             g.ln_gamma = dG; g.ln_beta = dT; g.ln_xh = xh; g.ln_xl = nullptr; g.ln_xl8 = xl8; g.ln_xchg = xs; g.ln_eps = 1e-5f; g.ln_no_lo = 0;
             (void)hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream);
-            rc = run_gemm_lnx_small(h, KC_GEMM_OUT, g);
+            rc = run_gemm_lnx_small(h, KC_GEMM_OUT, g, shape);
             if (!rc) {
                 int flag = 0;
                 (void)hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream);

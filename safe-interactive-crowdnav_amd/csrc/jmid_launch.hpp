@@ -6,25 +6,27 @@
 namespace jmid_host {
 
 template <int EPI>
-int run_gemm(jmid_ctx* h, int cls, GemmArgs& g) {
+int run_gemm(jmid_ctx* h, int cls, const GemmArgs& g) {
     if (g.K % GEMM_BK != 0) return fail(h, JMID_EINVAL, "GEMM K must be a multiple of 32");
     ProfScope ps(h, cls);
     HIPCHK(h, launch_gemm_f32<EPI>(g, h->stream));
     return 0;
 }
 
+// small_now: gemm_small.hpp::small_gemm_shape (the planner's CallFacts; a single launch on an idle handle: 1)
 template <int EPI, int OUT>
-int run_gemm_h(jmid_ctx* h, int cls, GemmHArgs& g) {
+int run_gemm_h(jmid_ctx* h, int cls, GemmHArgs& g, int small_now = 1) {
     if (g.K % GEMMH_BK != 0) return fail(h, JMID_EINVAL, "GEMM K must be a multiple of 32");
     g.range_flag = h->range_flag;
     g.x2 = h->x2;
     ProfScope ps(h, cls);
-    HIPCHK(h, (launch_gemm_h<EPI, OUT>(g, h->stream)));
+    HIPCHK(h, (launch_gemm_h<EPI, OUT>(g, h->stream, small_now)));
     return 0;
 }
 
 // out_proj / linear2 + residual + LayerNorm as ONE small launch, the row statistics exchanged between the workgroups of a row tile (gemm_small.hpp, OUT_LNX; F16MX at d_model 512)
-inline int run_gemm_lnx_small(jmid_ctx* h, int cls, GemmHArgs& g) {
+// shape: what small_lnx_fits answered for this launch (2: one workgroup per CU, 9: two)
+inline int run_gemm_lnx_small(jmid_ctx* h, int cls, GemmHArgs& g, int shape) {
     g.range_flag = h->range_flag;
     g.x2 = h->x2;
     if (++h->lnx_epoch == 0) h->lnx_epoch = 1;        // (0 is what the zeroed granules hold)
@@ -34,18 +36,27 @@ inline int run_gemm_lnx_small(jmid_ctx* h, int cls, GemmHArgs& g) {
     // the kernel is written for the F16MX operand set (byte lo plane of the residual stream, bf8 image of W_lo) only
     if (!(g.x2 && g.W8 && g.ln_xl8)) return fail(h, JMID_EINVAL, "one-launch GEMM + LayerNorm without the F16MX operand set");
     ProfScope ps(h, cls);
-    HIPCHK(h, (launch_gemm_small<EPI_BIAS, OUT_LNX>(g, small_lnx_fits(g.M, g.K), h->stream)));      // (2: one workgroup per CU, 9: two)
+    HIPCHK(h, (launch_gemm_small<EPI_BIAS, OUT_LNX>(g, shape, h->stream)));
     return 0;
 }
 
 
-// JMID_PREC_F16MX: hand the GEMM the fp8 image of this weight's lo plane (the kernels that have no fp8 path ignore it)
-inline void set_w8(jmid_ctx* h, GemmHArgs& g, const std::string& name) {
-    g.W8 = nullptr;
-    if (!h->mx) return;
-    auto it = h->w8.find(name);
-    if (it == h->w8.end()) return;
-    g.W8 = it->second.p;
+// The operands of one fp32 GEMM: A [M, K] x a linear of the weight table [N, K] -> C [M, N].  The epilogue fields are the caller's.
+inline GemmArgs gemm_args(const RowMap& rm, int M, const float* A, const LinearW& w, float* C, int N, int K) {
+    GemmArgs g{};
+    g.rmap = rm; g.M = M; g.N = N; g.K = K;
+    g.A = A; g.lda = K; g.W = w.W; g.ldw = K; g.bias = w.bias; g.C = C; g.ldc = N;
+    return g;
+}
+
+// The operands of one split-fp16 GEMM: A planes [M, K] x a linear of the weight table [N, K] - in JMID_PREC_F16MX with the fp8 image
+// of the weight's lo plane (the kernels that have no fp8 path ignore it).  The output and epilogue fields are the caller's.
+inline GemmHArgs gemm_h_args(const jmid_ctx* h, const RowMap& rm, int M, const half_t* Ahi, const half_t* Alo, const LinearW& w, int N, int K) {
+    GemmHArgs g{};
+    g.rmap = rm; g.M = M; g.N = N; g.K = K;
+    g.Ahi = Ahi; g.Alo = Alo; g.Whi = w.split.hi; g.Wlo = w.split.lo; g.bias = w.bias;
+    g.W8 = h->mx ? w.w8 : nullptr;
+    return g;
 }
 
 inline int run_add_ln(jmid_ctx* h, float* X, const float* Y, const float* gm, const float* bt, int M, int d,

@@ -38,7 +38,6 @@ struct StepBuffers {
     // F16X3 path: hi/lo planes
     half_t *Xh, *Xl, *Qh, *Ql, *Kh, *Kl, *Vh, *Vl, *Vth, *Vtl, *Ah, *Al, *H1h, *H1l, *Y3h, *Y3l;
     size_t vt_elems;
-    int attn_nsplit;          // split-KV factor of the attention launch (1 = off)
     float *Opart, *MLpart;
     unsigned long long* ln_xchg;   // exchange granules of the small-launch GEMM + LayerNorm (gemm_small.hpp, OUT_LNX): kLnxWords words, zeroed once per call
 };
@@ -83,10 +82,9 @@ size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom
             s.vt_elems = (size_t)sg.nseq * h->d * sg.Spad;
             s.Vth = take_half(c, s.vt_elems);
             s.Vtl = take_half(c, s.vt_elems);
-            s.attn_nsplit = nsplit;
-            if (s.attn_nsplit > 1) {
-                s.Opart = c.take((size_t)s.attn_nsplit * Mc * h->d);
-                s.MLpart = c.take((size_t)s.attn_nsplit * Mc * h->nhead * 2);
+            if (nsplit > 1) {      // split-KV factor of the attention launch (1 = off)
+                s.Opart = c.take((size_t)nsplit * Mc * h->d);
+                s.MLpart = c.take((size_t)nsplit * Mc * h->nhead * 2);
             }
         } else {
             s.QKV = c.take(Mc * 3 * h->d);  // iMID: sequences of T tokens, exact-fp32 attention kernel
@@ -102,25 +100,163 @@ size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom
     return c.off;
 }
 
-// one evaluation of the net on a chunk of whole episodes + (optionally) the DDIM update
-int net_step(jmid_ctx* h, const StepBuffers& sb, int Ec, int A, int K, int T, int step_idx, float* x_chunk,
-             const float* hyp_chunk, float* e_out, int precision, const float* z_chunk = nullptr,
-             bool embed_done = false, int next_step = -1) {
+// What a call knows before its first launch and no chunk of it changes (run_network).  Facts, not knobs: jmid_set_tuning has no say.
+struct CallFacts {
+    // the small-launch GEMMs (gemm_small.hpp: one workgroup per CU, most of its LDS): 1 = one chunk in flight, 0 = several (their
+    // launches would collide), 2 = experiment "small_lanes" = 2: only the two-workgroups-per-CU shape
+    int small_now = 1;
+    // the call is ONE chunk, run eagerly (OUT_LNX of gemm_small.hpp only then, whatever the lanes: a call's bits do not depend on
+    // its chunk plan; a captured loop would replay that kernel's launch tags)
+    int one_chunk = 1;
+    int attn_nsplit = 1;      // split-KV factor of the attention launches: per call, never per chunk (run_network)
+};
+
+// JMID_PREC_F16MX at d_model 512: second-generation LayerNorm kernels (gemm_ln2_mx.hpp) - the lo plane of the residual stream
+// is a byte plane (it lives in the memory of the fp16 one), the row statistics are summed in that file's order
+bool byte_lo_plane(const jmid_ctx* h) { return h->mx && h->d == GLN_BN && tune().mx_ln != 2; }
+
+// A residual block of a layer in the split-fp16 modes - X <- LayerNorm(X + A . W^T + bias): out_proj + norm1 (K = d_model) and
+// linear2 + norm2 (K = d_ff) - runs in one of four ways.  All four give bit-identical rows.
+enum ResidualPath {
+    RB_GEMM_LN2,        // row-tile GEMM with the LayerNorm inside, second generation (gemm_ln2_mx.hpp)
+    RB_GEMM_LN,         // ... first generation (gemm_ln_f16x3.hpp)
+    RB_LNX_SMALL,       // ONE small launch whose workgroups exchange the row statistics (gemm_small.hpp, OUT_LNX)
+    RB_GEMM_ADD_LN,     // GEMM -> fp32 Y, then add_ln
+};
+struct ResidualPlan {
+    ResidualPath path;
+    int lnx_shape;      // RB_LNX_SMALL: 2 = one workgroup per CU, 9 = two
+    bool merge;         // RB_LNX_SMALL of out_proj: the split-KV merge of the attention launch rides in front of its K loop (plan_step)
+};
+
+// THE function that picks the path of a residual block of M rows; everything else (the step plan, the chunk plan) asks it.
+ResidualPlan residual_path(const jmid_ctx* h, int M, int K, const CallFacts& cf) {
+    // row-complete GEMM with residual + LayerNorm fused in from 7168 tokens (6 episodes
+    // per launch: 36.8 vs 39.1 ms per 12-episode call; 5: 33.8 vs 33.5, 4: 29.6 vs 28.8)
+    // (enough row tiles to occupy the chip); otherwise GEMM -> fp32 Y -> add_ln
+    if (h->d == GLN_BN && tune().ln_fuse != 2 && (tune().ln_fuse == 1 || M >= 7168))
+        return {byte_lo_plane(h) ? RB_GEMM_LN2 : RB_GEMM_LN, 0, false};
+    // one scene in F16MX (one chunk of <= 2048 rows, or two scenes' worth with two workgroups per CU; byte lo plane): GEMM + residual +
+    // LayerNorm in ONE small launch (two launches per layer fewer); a handle on which such a kernel ever gave up waiting (lnx_off)
+    // stays on the pair
+    const int shape = byte_lo_plane(h) && !h->lnx_off ? small_lnx_fits(M, K, cf.small_now, cf.one_chunk) : 0;
+    return {shape ? RB_LNX_SMALL : RB_GEMM_ADD_LN, shape, false};
+}
+
+// Is a batch of `tokens` tokens ONE launch by default (plan_chunks keeps it one chunk)?  Shape and mode only.  There are two
+// predicates on purpose: this one sizes the split-KV factor, which decides the order in which a sequence's keys are summed, so it
+// must not see a knob or lnx_off (the bits of a call must not depend on one); residual_path may, its paths give the same bits.
+bool one_launch_shape(const jmid_ctx* h, long tokens) { return h->mx && h->d == GLN_BN && tokens <= 2560; }
+
+// Everything one net evaluation on a chunk of Ec episodes decides, decided once per call and chunk size (run_network): the knobs
+// and lnx_off cannot change while a call runs.  net_step executes it.
+struct StepPlan {
+    int Ec, M, T;                // episodes and tokens (Ec * K * A * T) of the chunk, tokens per trajectory
+    bool split, mxv2, joint;     // split-fp16 mode; byte lo plane of the residual stream (byte_lo_plane); JMID (joint attention over an episode)
+    RowMap rm;
+    SeqGeom sg;
+    int hd;
+    float att_scale;
+    bool vt_direct;              // the QKV epilogue writes V^T itself; otherwise V row-major + v_transpose_kernel
+    bool k8, q8l;                // bf8 images of K_hi / K_lo, and of Q_lo, written by the QKV epilogue for the attention kernel
+    CallFacts cf;                // (small_now: for the launches that pick their own tile shape, small_gemm_shape; the split-KV factor)
+    ResidualPlan out_proj, linear2;
+    int out_tpw;                 // output kernel: tokens per wave of the per-trajectory form, 0 = one wave per token
+};
+
+StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision, const CallFacts& cf) {
+    StepPlan p{};
+    const int d = h->d;
+    p.Ec = Ec;
+    p.M = Ec * K * A * T;
+    p.T = T;
+    p.split = precision != JMID_PREC_F32;
+    p.mxv2 = p.split && byte_lo_plane(h);
+    p.joint = h->net_kind == JMID_NET_JMID;
+    p.rm = make_rowmap(T, A, K * A, (unsigned long long)p.M);
+    p.sg = seq_geom(h, Ec, A, K, T);
+    p.hd = d / h->nhead;
+    p.att_scale = 1.0f / sqrtf((float)p.hd);
+    p.cf = cf;
+    if (p.split) {
+        p.out_proj = residual_path(h, p.M, d, cf);
+        p.linear2 = residual_path(h, p.M, h->ff, cf);
+    }
+    if (p.split && p.joint) {
+        // S % 4 == 0: the QKV epilogue writes V^T itself; otherwise V row-major + v_transpose_kernel
+        p.vt_direct = (p.sg.S % 4 == 0) && !tune().no_vt_direct;
+        // JMID_PREC_F16MX, head_dim 128 (the LDS-DMA attention kernel): bf8 images of K_hi / K_lo in the K_lo plane's memory, for
+        // the logits' correction terms as bf8 MFMAs (attention 7 % faster; "attn_mx" = 2: fp16 terms as in F16X2)
+        // (the register-staged GEMM variants a knob can force are F16X2's kernels: no image stores)
+        p.k8 = h->mx && p.hd == 128 && tune().attn_h_variant == 0 && tune().attn_mx != 2 && tune().gemm_h_variant != 1 &&
+               tune().gemm_h_variant != 2;
+        p.q8l = p.k8 && tune().attn_mx != 3;      // 3: Q_lo as fp16 (A/B)
+        // one scene: the partial outputs of a split-KV attention launch are merged in front of the out-projection's K loop
+        // (gemm_small.hpp, lnx_combine) when that launch is the one with the LayerNorm inside
+        p.out_proj.merge = p.out_proj.path == RB_LNX_SMALL && small_cmb_fits(p.cf.attn_nsplit, p.hd, h->x2);
+    }
+    if (d <= 512 && p.M % T == 0 && tune().out_traj != 2 && (tune().out_traj == 1 || p.M >= 4096 * 4)) {
+        // one wave per trajectory (T tokens) - or per piece of one, the largest divisor of T that still leaves >= 4096 waves -
+        // once there are enough tokens to fill the chip that way: one scene (100 trajectories) takes 14.0 instead of
+        // 12.7 ms per call with whole trajectories, a 51-episode chunk 150.3 instead of 151.2
+        p.out_tpw = T;
+        while (p.out_tpw > 1 && (p.M / p.out_tpw < 4096 || T % p.out_tpw != 0)) --p.out_tpw;
+        if (tune().out_traj == 1) p.out_tpw = T;
+    }
+    return p;
+}
+
+// One residual block on the path the plan holds for it.  A planes [M, K]: the attention output (out_proj) or linear1's (linear2).
+// no_lo_out: the residual stream ends here (norm2 of the last layer: concat3 reads X_hi only), its lo plane is not written
+// where it is the byte plane or the mode is F16X2.
+int residual_block(jmid_ctx* h, const StepPlan& p, const ResidualPlan& rp, const StepBuffers& sb, const half_t* Ahi, const half_t* Alo,
+                   int K, const LinearW& lin, const NormW& nrm, int cls, bool no_lo_out) {
+    const int M = p.M, d = h->d;
+    unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
+    if (rp.path == RB_GEMM_LN2) {
+        GemmLn2Args g2{Ahi, lin.k16.hi, lin.w8, lin.bias, nrm.gamma, nrm.beta, sb.Xh, Xl8, M, K, 1e-5f, h->range_flag, no_lo_out};
+        ProfScope ps(h, cls);
+        HIPCHK(h, launch_gemm_ln2_mx(g2, h->stream));
+        return 0;
+    }
+    if (rp.path == RB_GEMM_LN) {
+        GemmLnArgs gl{Ahi, Alo, lin.k16.hi, lin.k16.lo, lin.bias, nrm.gamma, nrm.beta, sb.Xh, sb.Xl, M, K, 1e-5f, h->range_flag, h->x2};
+        gl.W8 = h->mx ? lin.w8 : nullptr;
+        gl.no_lo_out = h->x2 && no_lo_out;
+        ProfScope ps(h, cls);
+        HIPCHK(h, launch_gemm_ln(gl, h->stream));
+        return 0;
+    }
+    GemmHArgs g = gemm_h_args(h, p.rm, M, Ahi, Alo, lin, d, K);
+    g.C = sb.Y; g.ldc = d;
+    if (rp.path == RB_LNX_SMALL) {
+        if (rp.merge) {
+            g.cmb_O = sb.Opart; g.cmb_ML = sb.MLpart; g.cmb_ns = p.cf.attn_nsplit; g.cmb_nhead = h->nhead;
+            g.cmb_Mtot = (unsigned)((size_t)p.sg.nseq * p.sg.S);
+        }
+        g.ln_gamma = nrm.gamma; g.ln_beta = nrm.beta; g.ln_xh = sb.Xh; g.ln_xl = nullptr;
+        g.ln_xl8 = Xl8; g.ln_xchg = sb.ln_xchg; g.ln_eps = 1e-5f; g.ln_no_lo = no_lo_out;
+        return run_gemm_lnx_small(h, cls, g, rp.lnx_shape);
+    }
+    if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, cls, g, p.cf.small_now))) return rc;
+    return run_add_ln(h, sb.X, sb.Y, nrm.gamma, nrm.beta, M, d, sb.Xh, sb.Xl, p.mxv2, no_lo_out);
+}
+
+// one evaluation of the net on a chunk of whole episodes + (optionally) the DDIM update, as its plan says
+int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+             float* e_out, const float* z_chunk = nullptr, bool embed_done = false, int next_step = -1) {
     // embed_done: the previous step's output kernel already embedded x for this step; next_step >= 0: this step's
     // output kernel does the same for step `next_step` (same chunk, same buffers)
-    const bool split = precision != JMID_PREC_F32;
-    const int R = Ec * K * A, M = R * T;
-    const int d = h->d, ff = h->ff;
+    const bool split = p.split;
+    const int M = p.M, d = h->d, ff = h->ff;
+    const WeightTable& wt = h->wt;
     const float* thyp = h->thyp + (size_t)step_idx * h->hl.total;
-    const RowMap rm = make_rowmap(T, A, K * A, (unsigned long long)M);
-    // JMID_PREC_F16MX at d_model 512: second-generation LayerNorm kernels (gemm_ln2_mx.hpp) - the lo plane of the residual stream
-    // is a byte plane (it lives in the memory of the fp16 one), the row statistics are summed in that file's order
-    const bool mxv2 = split && h->mx && d == GLN_BN && tune().mx_ln != 2;
-    unsigned char* Xl8 = mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
+    const RowMap& rm = p.rm;
+    unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
     const auto embed_args = [&](const float* th) {
-        return EmbedArgs{x_chunk, W(h, "concat1._layer.weight"), W(h, "concat1._layer.bias"), h->pe, hyp_chunk, th,
+        return EmbedArgs{x_chunk, wt.concat1.W, wt.concat1.bias, h->pe, hyp_chunk, th,
                          split ? nullptr : sb.X, M, d, h->hl.total, h->hl.g1, h->hl.b1, rm, split ? sb.Xh : nullptr,
-                         split && !mxv2 ? sb.Xl : nullptr, Xl8};
+                         split && !p.mxv2 ? sb.Xl : nullptr, Xl8};
     };
     if (!embed_done) {
         ProfScope ps(h, KC_EMBED);
@@ -130,209 +266,83 @@ int net_step(jmid_ctx* h, const StepBuffers& sb, int Ec, int A, int K, int T, in
         hipLaunchKernelGGL(embed_kernel, dim3(blocks), dim3(256), bystander_lds(embed_kernel), h->stream, ea);
         HIPCHK(h, hipGetLastError());
     }
-    const SeqGeom sg = seq_geom(h, Ec, A, K, T);
-    const int nseq = sg.nseq, S = sg.S;
-    const int hd = d / h->nhead;
-    const float att_scale = 1.0f / sqrtf((float)hd);
+    const SeqGeom& sg = p.sg;
+    const int nseq = sg.nseq, S = sg.S, hd = p.hd;
     if (!split) {
-        for (int l = 0; l < h->tf_layer; ++l) {
-            const std::string p = "transformer_encoder.layers." + std::to_string(l);
-            GemmArgs g{};
-            g.rmap = rm;
-            // QKV projection
-            g.A = sb.X; g.lda = d; g.W = W(h, p + ".self_attn.in_proj_weight"); g.ldw = d;
-            g.bias = W(h, p + ".self_attn.in_proj_bias"); g.C = sb.QKV; g.ldc = 3 * d; g.M = M; g.N = 3 * d; g.K = d;
-            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_QKV, g)) return rc;
+        for (const LayerW& w : wt.layers) {
+            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_QKV, gemm_args(rm, M, sb.X, w.in_proj, sb.QKV, 3 * d, d))) return rc;
             {
                 ProfScope ps(h, KC_ATTN);
-                AttnArgs aa{sb.QKV, sb.ATT, S, d, h->nhead, att_scale, nullptr, nullptr};
+                AttnArgs aa{sb.QKV, sb.ATT, S, d, h->nhead, p.att_scale, nullptr, nullptr};
                 HIPCHK(h, launch_attn_f32(aa, nseq, hd, h->stream));
             }
             // attention output projection + residual + LN1
-            g.A = sb.ATT; g.lda = d; g.W = W(h, p + ".self_attn.out_proj.weight"); g.ldw = d;
-            g.bias = W(h, p + ".self_attn.out_proj.bias"); g.C = sb.Y; g.ldc = d; g.N = d; g.K = d;
-            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_OUT, g)) return rc;
-            if (int rc = run_add_ln(h, sb.X, sb.Y, W(h, p + ".norm1.weight"), W(h, p + ".norm1.bias"), M, d)) return rc;
+            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_OUT, gemm_args(rm, M, sb.ATT, w.out_proj, sb.Y, d, d))) return rc;
+            if (int rc = run_add_ln(h, sb.X, sb.Y, w.norm1.gamma, w.norm1.beta, M, d)) return rc;
             // feed-forward
-            g.A = sb.X; g.lda = d; g.W = W(h, p + ".linear1.weight"); g.ldw = d; g.bias = W(h, p + ".linear1.bias");
-            g.C = sb.H1; g.ldc = ff; g.N = ff; g.K = d;
-            if (int rc = run_gemm<EPI_BIAS_RELU>(h, KC_GEMM_FF1, g)) return rc;
-            g.A = sb.H1; g.lda = ff; g.W = W(h, p + ".linear2.weight"); g.ldw = ff; g.bias = W(h, p + ".linear2.bias");
-            g.C = sb.Y; g.ldc = d; g.N = d; g.K = ff;
-            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_FF2, g)) return rc;
-            if (int rc = run_add_ln(h, sb.X, sb.Y, W(h, p + ".norm2.weight"), W(h, p + ".norm2.bias"), M, d)) return rc;
+            if (int rc = run_gemm<EPI_BIAS_RELU>(h, KC_GEMM_FF1, gemm_args(rm, M, sb.X, w.linear1, sb.H1, ff, d))) return rc;
+            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_FF2, gemm_args(rm, M, sb.H1, w.linear2, sb.Y, d, ff))) return rc;
+            if (int rc = run_add_ln(h, sb.X, sb.Y, w.norm2.gamma, w.norm2.beta, M, d)) return rc;
         }
         // tail: concat3, concat4 (ConcatSquash epilogues)
-        GemmArgs g{};
-        g.rmap = rm; g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.M = M;
-        g.A = sb.X; g.lda = d; g.W = W(h, "concat3._layer.weight"); g.ldw = d; g.bias = W(h, "concat3._layer.bias");
-        g.C = sb.Y3; g.ldc = h->dmid; g.N = h->dmid; g.K = d; g.goff = h->hl.g3; g.boff = h->hl.b3;
+        GemmArgs g = gemm_args(rm, M, sb.X, wt.concat3, sb.Y3, h->dmid, d);
+        g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.goff = h->hl.g3; g.boff = h->hl.b3;
         if (int rc = run_gemm<EPI_CSL>(h, KC_GEMM_TAIL, g)) return rc;
-        g.A = sb.Y3; g.lda = h->dmid; g.W = W(h, "concat4._layer.weight"); g.ldw = h->dmid;
-        g.bias = W(h, "concat4._layer.bias"); g.C = sb.Y4; g.ldc = h->dlow; g.N = h->dlow; g.K = h->dmid;
-        g.goff = h->hl.g4; g.boff = h->hl.b4;
+        g = gemm_args(rm, M, sb.Y3, wt.concat4, sb.Y4, h->dlow, h->dmid);
+        g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.goff = h->hl.g4; g.boff = h->hl.b4;
         if (int rc = run_gemm<EPI_CSL>(h, KC_GEMM_TAIL, g)) return rc;
     } else {
-        const bool joint = h->net_kind == JMID_NET_JMID;
         for (int l = 0; l < h->tf_layer; ++l) {
-            const std::string p = "transformer_encoder.layers." + std::to_string(l);
-            GemmHArgs g{};
-            g.rmap = rm; g.M = M;
-            bool cmb_in_gemm = false;
-            int cmb_ns = 0;
-            size_t cmb_Mtot = 0;
-            const HalfPair& win = h->wsplit[p + ".self_attn.in_proj_weight"];
-            g.Ahi = sb.Xh; g.Alo = sb.Xl; g.Whi = win.hi; g.Wlo = win.lo;
-            set_w8(h, g, p + ".self_attn.in_proj_weight");
-            g.bias = W(h, p + ".self_attn.in_proj_bias"); g.N = 3 * d; g.K = d;
-            if (joint) {
-                // S % 4 == 0: the QKV epilogue writes V^T itself; otherwise V row-major + v_transpose_kernel
-                const bool vt_direct = (S % 4 == 0) && !tune().no_vt_direct;
+            const LayerW& w = wt.layers[l];
+            GemmHArgs g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, w.in_proj, 3 * d, d);
+            if (p.joint) {
                 g.Chi = sb.Qh; g.Clo = sb.Ql; g.Khi = sb.Kh; g.Klo = sb.Kl;
-                g.Vthi = vt_direct ? sb.Vth : sb.Vh; g.Vtlo = vt_direct ? sb.Vtl : sb.Vl; g.vt_direct = vt_direct;
-                g.d = d; g.hd = hd; g.S = S; g.Spad = sg.Spad; g.qscale = att_scale * 1.4426950408889634f;
-                // JMID_PREC_F16MX, head_dim 128 (the LDS-DMA attention kernel): bf8 images of K_hi / K_lo in the K_lo plane's memory, for
-                // the logits' correction terms as bf8 MFMAs (attention 7 % faster; "attn_mx" = 2: fp16 terms as in F16X2)
-                // (the register-staged GEMM variants a knob can force are F16X2's kernels: no image stores)
-                const bool k8 = h->mx && hd == 128 && tune().attn_h_variant == 0 && tune().attn_mx != 2 &&
-                                tune().gemm_h_variant != 1 && tune().gemm_h_variant != 2;
-                unsigned char* k8h = k8 ? reinterpret_cast<unsigned char*>(sb.Kl) : nullptr;
-                unsigned char* k8l = k8 ? k8h + (size_t)M * d : nullptr;
-                unsigned char* q8l = k8 && tune().attn_mx != 3 ? reinterpret_cast<unsigned char*>(sb.Ql) : nullptr;   // 3: Q_lo as fp16 (A/B)
+                g.Vthi = p.vt_direct ? sb.Vth : sb.Vh; g.Vtlo = p.vt_direct ? sb.Vtl : sb.Vl; g.vt_direct = p.vt_direct;
+                g.d = d; g.hd = hd; g.S = S; g.Spad = sg.Spad; g.qscale = p.att_scale * 1.4426950408889634f;
+                unsigned char* k8h = p.k8 ? reinterpret_cast<unsigned char*>(sb.Kl) : nullptr;
+                unsigned char* k8l = p.k8 ? k8h + (size_t)M * d : nullptr;
+                unsigned char* q8l = p.q8l ? reinterpret_cast<unsigned char*>(sb.Ql) : nullptr;
                 g.K8h = k8h; g.K8l = k8l; g.Q8l = q8l;
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, KC_GEMM_QKV, g))) return rc;
-                if (!vt_direct) {
+                if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, KC_GEMM_QKV, g, p.cf.small_now))) return rc;
+                if (!p.vt_direct) {
                     ProfScope ps(h, KC_VTRANS);
                     hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, nseq), dim3(256), 0, h->stream,
                                        sb.Vh, sb.Vl, sb.Vth, sb.Vtl, S, sg.Spad, d, hd);
                     HIPCHK(h, hipGetLastError());
                 }
                 ProfScope ps(h, KC_ATTN);
-                const int ns = sb.attn_nsplit;   // per call, not per chunk (run_network)
                 AttnHArgs aa{sb.Qh, sb.Ql, sb.Kh, sb.Kl, sb.Vth, sb.Vtl, sb.Ah, sb.Al, S, sg.Spad, d, h->nhead,
-                             att_scale, h->range_flag, ns, sb.Opart, sb.MLpart, h->x2, k8h, k8l, q8l};
-                // one scene: the partial outputs are merged in front of the out-projection's K loop (gemm_small.hpp, lnx_combine) when
-                // that launch is the one with the LayerNorm inside (the same conditions as below)
-                cmb_in_gemm = mxv2 && !h->lnx_off && !(tune().ln_fuse != 2 && (tune().ln_fuse == 1 || M >= 7168)) && small_lnx_fits(M, d) &&
-                              small_cmb_fits(ns, hd, h->x2);
-                aa.skip_combine = cmb_in_gemm;
-                cmb_ns = ns;
-                cmb_Mtot = (size_t)nseq * S;
+                             p.att_scale, h->range_flag, p.cf.attn_nsplit, sb.Opart, sb.MLpart, h->x2, k8h, k8l, q8l};
+                aa.skip_combine = p.out_proj.merge;
                 HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, h->stream));
-                g.K8h = nullptr; g.K8l = nullptr; g.Q8l = nullptr;
             } else {
                 g.C = sb.QKV; g.ldc = 3 * d;
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g))) return rc;
+                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g, p.cf.small_now))) return rc;
                 ProfScope ps(h, KC_ATTN);
-                AttnArgs aa{sb.QKV, nullptr, S, d, h->nhead, att_scale, sb.Ah, sb.Al};
+                AttnArgs aa{sb.QKV, nullptr, S, d, h->nhead, p.att_scale, sb.Ah, sb.Al};
                 HIPCHK(h, launch_attn_f32(aa, nseq, hd, h->stream));
             }
-            // row-complete GEMM with residual + LayerNorm fused in (gemm_ln_f16x3.hpp) from 7168 tokens (6 episodes
-            // per launch: 36.8 vs 39.1 ms per 12-episode call; 5: 33.8 vs 33.5, 4: 29.6 vs 28.8)
-            // (enough row tiles to occupy the chip); otherwise GEMM -> fp32 Y -> add_ln.  Both give bit-identical rows.
-            const bool ln_fused = d == GLN_BN && tune().ln_fuse != 2 && (tune().ln_fuse == 1 || M >= 7168);
-            // one scene in F16MX (one chunk of <= 2048 rows, byte lo plane of the second-generation LayerNorm: mxv2): GEMM + residual +
-            // LayerNorm in ONE small launch whose workgroups exchange the row statistics (gemm_small.hpp, OUT_LNX; two launches per
-            // layer fewer); a handle on which such a kernel ever gave up waiting (lnx_off) stays on the pair
-            if (ln_fused && mxv2) {
-                GemmLn2Args g2{sb.Ah, h->w16[p + ".self_attn.out_proj.weight"].hi, h->w8[p + ".self_attn.out_proj.weight"].p,
-                               W(h, p + ".self_attn.out_proj.bias"), W(h, p + ".norm1.weight"), W(h, p + ".norm1.bias"), sb.Xh, Xl8,
-                               M, d, 1e-5f, h->range_flag, 0};
-                ProfScope ps(h, KC_GEMM_OUT);
-                HIPCHK(h, launch_gemm_ln2_mx(g2, h->stream));
-            } else if (ln_fused) {
-                const HalfPair& w16 = h->w16[p + ".self_attn.out_proj.weight"];
-                GemmLnArgs gl{sb.Ah, sb.Al, w16.hi, w16.lo, W(h, p + ".self_attn.out_proj.bias"), W(h, p + ".norm1.weight"),
-                              W(h, p + ".norm1.bias"), sb.Xh, sb.Xl, M, d, 1e-5f, h->range_flag, h->x2};
-                if (h->mx) {
-                    auto it8 = h->w8.find(p + ".self_attn.out_proj.weight");
-                    if (it8 != h->w8.end()) gl.W8 = it8->second.p;
-                }
-                ProfScope ps(h, KC_GEMM_OUT);
-                HIPCHK(h, launch_gemm_ln(gl, h->stream));
-            } else {
-                const HalfPair& wout = h->wsplit[p + ".self_attn.out_proj.weight"];
-                g.Ahi = sb.Ah; g.Alo = sb.Al; g.Whi = wout.hi; g.Wlo = wout.lo;
-                set_w8(h, g, p + ".self_attn.out_proj.weight");
-                g.bias = W(h, p + ".self_attn.out_proj.bias"); g.C = sb.Y; g.ldc = d; g.N = d; g.K = d;
-                if (cmb_in_gemm && !(mxv2 && !h->lnx_off && small_lnx_fits(M, g.K))) return fail(h, JMID_EINVAL, "split-KV merge left to a launch that does not exist");
-                if (mxv2 && !h->lnx_off && small_lnx_fits(M, g.K)) {
-                    g.cmb_O = cmb_in_gemm ? sb.Opart : nullptr; g.cmb_ML = sb.MLpart; g.cmb_ns = cmb_ns; g.cmb_nhead = h->nhead; g.cmb_Mtot = (unsigned)cmb_Mtot;
-                    g.ln_gamma = W(h, p + ".norm1.weight"); g.ln_beta = W(h, p + ".norm1.bias"); g.ln_xh = sb.Xh; g.ln_xl = nullptr;
-                    g.ln_xl8 = Xl8; g.ln_xchg = sb.ln_xchg; g.ln_eps = 1e-5f; g.ln_no_lo = 0;
-                    if (int rc = run_gemm_lnx_small(h, KC_GEMM_OUT, g)) return rc;
-                } else
-                {
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_OUT, g))) return rc;
-                if (int rc = run_add_ln(h, sb.X, sb.Y, W(h, p + ".norm1.weight"), W(h, p + ".norm1.bias"), M, d, sb.Xh,
-                                        sb.Xl, mxv2, 0))
-                    return rc;
-                }
-            }
-            const HalfPair& w1 = h->wsplit[p + ".linear1.weight"];
-            g.Ahi = sb.Xh; g.Alo = sb.Xl; g.Whi = w1.hi; g.Wlo = w1.lo;
-            set_w8(h, g, p + ".linear1.weight");
-            g.bias = W(h, p + ".linear1.bias"); g.Chi = sb.H1h; g.Clo = sb.H1l; g.ldc = ff; g.N = ff; g.K = d;
-            if (int rc = (run_gemm_h<EPI_BIAS_RELU, OUT_SPLIT>(h, KC_GEMM_FF1, g))) return rc;
-            if (ln_fused && mxv2) {
-                GemmLn2Args g2{sb.H1h, h->w16[p + ".linear2.weight"].hi, h->w8[p + ".linear2.weight"].p, W(h, p + ".linear2.bias"),
-                               W(h, p + ".norm2.weight"), W(h, p + ".norm2.bias"), sb.Xh, Xl8, M, ff, 1e-5f, h->range_flag,
-                               l + 1 == h->tf_layer};       // the residual stream ends here: concat3 reads X_hi only
-                ProfScope ps(h, KC_GEMM_FF2);
-                HIPCHK(h, launch_gemm_ln2_mx(g2, h->stream));
-            } else if (ln_fused) {
-                const HalfPair& w16 = h->w16[p + ".linear2.weight"];
-                GemmLnArgs gl{sb.H1h, sb.H1l, w16.hi, w16.lo, W(h, p + ".linear2.bias"), W(h, p + ".norm2.weight"),
-                              W(h, p + ".norm2.bias"), sb.Xh, sb.Xl, M, ff, 1e-5f, h->range_flag, h->x2};
-                gl.no_lo_out = h->x2 && l + 1 == h->tf_layer;     // the residual stream ends here: concat3 reads X_hi only
-                if (h->mx) {
-                    auto it8 = h->w8.find(p + ".linear2.weight");
-                    if (it8 != h->w8.end()) gl.W8 = it8->second.p;
-                }
-                ProfScope ps(h, KC_GEMM_FF2);
-                HIPCHK(h, launch_gemm_ln(gl, h->stream));
-            } else {
-                const HalfPair& w2 = h->wsplit[p + ".linear2.weight"];
-                g.Ahi = sb.H1h; g.Alo = sb.H1l; g.Whi = w2.hi; g.Wlo = w2.lo;
-                set_w8(h, g, p + ".linear2.weight");
-                g.bias = W(h, p + ".linear2.bias"); g.C = sb.Y; g.ldc = d; g.N = d; g.K = ff;
-                if (mxv2 && !h->lnx_off && small_lnx_fits(M, g.K)) {
-                    g.cmb_O = nullptr;
-                    g.ln_gamma = W(h, p + ".norm2.weight"); g.ln_beta = W(h, p + ".norm2.bias"); g.ln_xh = sb.Xh; g.ln_xl = nullptr;
-                    g.ln_xl8 = Xl8; g.ln_xchg = sb.ln_xchg; g.ln_eps = 1e-5f; g.ln_no_lo = mxv2 && l + 1 == h->tf_layer;
-                    if (int rc = run_gemm_lnx_small(h, KC_GEMM_FF2, g)) return rc;
-                } else
-                {
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_FF2, g))) return rc;
-                if (int rc = run_add_ln(h, sb.X, sb.Y, W(h, p + ".norm2.weight"), W(h, p + ".norm2.bias"), M, d, sb.Xh,
-                                        sb.Xl, mxv2, l + 1 == h->tf_layer))
-                    return rc;
-                }
-            }
+            if (int rc = residual_block(h, p, p.out_proj, sb, sb.Ah, sb.Al, d, w.out_proj, w.norm1, KC_GEMM_OUT, false)) return rc;
+            g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, w.linear1, ff, d);
+            g.Chi = sb.H1h; g.Clo = sb.H1l; g.ldc = ff;
+            if (int rc = (run_gemm_h<EPI_BIAS_RELU, OUT_SPLIT>(h, KC_GEMM_FF1, g, p.cf.small_now))) return rc;
+            // (the residual stream ends with the last layer: concat3 reads X_hi only)
+            if (int rc = residual_block(h, p, p.linear2, sb, sb.H1h, sb.H1l, ff, w.linear2, w.norm2, KC_GEMM_FF2, l + 1 == h->tf_layer)) return rc;
         }
         // concat3 -> concat4 as two launches, the output layer + sampler update + next embedding as a third (one fused kernel for all
         // three was built in round 3 and measured slower at every batch size: docs/NOTEBOOK.md)
-        {
-        GemmHArgs g{};
-        g.rmap = rm; g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.M = M;
-        const HalfPair& w3 = h->wsplit["concat3._layer.weight"];
-        g.Ahi = sb.Xh; g.Alo = sb.Xl; g.Whi = w3.hi; g.Wlo = w3.lo;
-        set_w8(h, g, "concat3._layer.weight");
-        g.bias = W(h, "concat3._layer.bias"); g.Chi = sb.Y3h; g.Clo = sb.Y3l; g.ldc = h->dmid; g.N = h->dmid; g.K = d;
-        g.goff = h->hl.g3; g.boff = h->hl.b3;
-        if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, KC_GEMM_TAIL, g))) return rc;
-        const HalfPair& w4 = h->wsplit["concat4._layer.weight"];
-        g.Ahi = sb.Y3h; g.Alo = sb.Y3l; g.Whi = w4.hi; g.Wlo = w4.lo;
-        set_w8(h, g, "concat4._layer.weight");
-        g.bias = W(h, "concat4._layer.bias"); g.C = sb.Y4; g.ldc = h->dlow; g.N = h->dlow; g.K = h->dmid;
-        g.goff = h->hl.g4; g.boff = h->hl.b4;
-        g.x2 = h->x2; g.range_flag = h->range_flag;
-        if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, KC_GEMM_TAIL, g))) return rc;
-        }
+        GemmHArgs g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, wt.concat3, h->dmid, d);
+        g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
+        g.Chi = sb.Y3h; g.Clo = sb.Y3l; g.ldc = h->dmid; g.goff = h->hl.g3; g.boff = h->hl.b3;
+        if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, KC_GEMM_TAIL, g, p.cf.small_now))) return rc;
+        g = gemm_h_args(h, rm, M, sb.Y3h, sb.Y3l, wt.concat4, h->dlow, h->dmid);
+        g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
+        g.C = sb.Y4; g.ldc = h->dlow; g.goff = h->hl.g4; g.boff = h->hl.b4;
+        if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, KC_GEMM_TAIL, g, p.cf.small_now))) return rc;
     }
     {
         ProfScope ps(h, KC_OUT_DDIM);
-        OutArgs oa{sb.Y4, W(h, "linear._layer.weight"), W(h, "linear._layer.bias"), hyp_chunk, thyp, x_chunk, e_out,
+        OutArgs oa{sb.Y4, wt.linear.W, wt.linear.bias, hyp_chunk, thyp, x_chunk, e_out,
                    M, h->dlow, h->hl.total, h->hl.go, h->hl.bo,
                    h->c_e[step_idx], h->c_x[step_idx], h->n_x[step_idx], h->n_e[step_idx], rm,
                    nullptr, 0, 0.f, 0.f, 0.f};
@@ -343,26 +353,16 @@ int net_step(jmid_ctx* h, const StepBuffers& sb, int Ec, int A, int K, int T, in
             oa.c1 = h->p_c1[step_idx];
             oa.sigma = h->p_sigma[step_idx];
         }
-        if (d <= 512 && M % T == 0 && tune().out_traj != 2 && (tune().out_traj == 1 || M >= 4096 * 4)) {
-            // one wave per trajectory (T tokens) - or per piece of one, the largest divisor of T that still leaves >= 4096 waves -
-            // once there are enough tokens to fill the chip that way: one scene (100 trajectories) takes 14.0 instead of
-            // 12.7 ms per call with whole trajectories, a 51-episode chunk 150.3 instead of 151.2
-            int tpw = T;
-            while (tpw > 1 && (M / tpw < 4096 || T % tpw != 0)) --tpw;
-            if (tune().out_traj == 1) tpw = T;
-            const int nw = M / tpw;
-            if (next_step >= 0 && !e_out)
-                hipLaunchKernelGGL(out_ddim_traj_kernel<true>, dim3((nw + 3) / 4), dim3(256), bystander_lds(out_ddim_traj_kernel<true>),
-                                   h->stream, oa, embed_args(h->thyp + (size_t)next_step * h->hl.total), tpw);
-            else
-                hipLaunchKernelGGL(out_ddim_traj_kernel<false>, dim3((nw + 3) / 4), dim3(256), bystander_lds(out_ddim_traj_kernel<false>),
-                                   h->stream, oa, EmbedArgs{}, tpw);
-        } else if (next_step >= 0 && !e_out)
-            hipLaunchKernelGGL(out_ddim_kernel<true>, dim3((M + 3) / 4), dim3(256), bystander_lds(out_ddim_kernel<true>),
-                               h->stream, oa, embed_args(h->thyp + (size_t)next_step * h->hl.total));
-        else
-            hipLaunchKernelGGL(out_ddim_kernel<false>, dim3((M + 3) / 4), dim3(256), bystander_lds(out_ddim_kernel<false>),
-                               h->stream, oa, EmbedArgs{});
+        const bool embed_next = next_step >= 0 && !e_out;
+        const EmbedArgs en = embed_next ? embed_args(h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+        // four waves per workgroup: one wave per piece of a trajectory (out_tpw tokens), or one per token
+        const auto launch = [&](auto* kernel, int waves, auto... tpw) {
+            hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(kernel), h->stream, oa, en, tpw...);
+        };
+        if (p.out_tpw && embed_next) launch(out_ddim_traj_kernel<true>, M / p.out_tpw, p.out_tpw);
+        else if (p.out_tpw) launch(out_ddim_traj_kernel<false>, M / p.out_tpw, p.out_tpw);
+        else if (embed_next) launch(out_ddim_kernel<true>, M);
+        else launch(out_ddim_kernel<false>, M);
         HIPCHK(h, hipGetLastError());
     }
     return 0;
@@ -405,9 +405,8 @@ std::vector<int> plan_chunks(const jmid_ctx* h, int E, int tokens_per_episode) {
             // carry the LayerNorm and the split-KV merge (gemm_small.hpp, OUT_LNX - only while nothing else of the handle is in flight),
             // nine launches less per denoise step: two cfg2 scenes (2 400 tokens) 14.45 -> 13.90 ms per call, 12.63 with the split-KV factor chosen for that launch (run_network).  Three (3 600 tokens, 456
             // workgroups of that kernel) are better off as 2 + 1 side by side: 16.42 against 16.90 (profiles/r05s_lnx_two_per_cu.log)
-            const bool lnx_call = h->mx && h->d == jmid::GLN_BN && !h->lnx_off && (long)E * tokens_per_episode <= 2560 &&
-                                  ((long)E * tokens_per_episode + 63) / 64 * 8 <= 2L * tune().cus &&
-                                  tune().small_lnx != 2 && tune().small_lnx2 != 2 && tune().gemm_small != 1 && tune().gemm_h_variant == 0;
+            const long tokens = (long)E * tokens_per_episode;
+            const bool lnx_call = one_launch_shape(h, tokens) && residual_path(h, (int)tokens, h->d, CallFacts{}).path == RB_LNX_SMALL;
             c = lnx_call ? E : (E + 1) / 2;
         } else {
             int n = (E + c - 1) / c;
@@ -490,8 +489,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         // (a batch of at most 2 560 tokens in F16MX is ONE launch by default - plan_chunks: two cfg2 scenes take 3 key ranges x 80 blocks,
         //  13.43 ms per call, where the 6 x 80 of the halves' choice take 14.14-14.37; shape and mode only, no knob: the bits of a call
         //  must not depend on one)
-        const bool one_launch = h->mx && h->d == jmid::GLN_BN && (long)E * S <= 2560;
-        ns_call = attn_pick_nsplit(((S + 127) / 128) * h->nhead * (E >= 2 ? (one_launch ? E : (c_auto + 1) / 2) : 1), S);
+        ns_call = attn_pick_nsplit(((S + 127) / 128) * h->nhead * (E >= 2 ? (one_launch_shape(h, (long)E * S) ? E : (c_auto + 1) / 2) : 1), S);
         if (tune().attn_nsplit > 0) ns_call = std::min(tune().attn_nsplit, (S + 31) / 32);
     }
     // ---- workspace
@@ -512,12 +510,20 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     // workspace; results do not depend on the number of lanes.
     const int nchunks = (int)chunk_sizes.size();
     const int lanes = single_step < 0 ? std::max(1, std::min(h->lanes, nchunks)) : 1;
-    // the small-launch GEMMs (gemm_small.hpp: one workgroup per CU, most of its LDS) only while one chunk is in flight
-    struct SmallNow {
-        Tuning& t;
-        SmallNow(Tuning& t_, int v, int one) : t(t_) { t.small_now = v; t.one_chunk = one; }
-        ~SmallNow() { t.small_now = 1; t.one_chunk = 1; }
-    } small_now_scope(h->tune, lanes == 1 || h->tune.small_lanes == 1 ? 1 : h->tune.small_lanes == 2 ? 2 : 0, nchunks == 1 && tune().graph != 1);      // (a captured loop would replay the launch tags of OUT_LNX)
+    // one plan per distinct chunk size of the call (the knobs and lnx_off cannot change while it runs): net_step only executes it.
+    // The small-launch GEMMs (gemm_small.hpp: one workgroup per CU, most of its LDS) only while one chunk is in flight
+    CallFacts facts;
+    facts.small_now = lanes == 1 || tune().small_lanes == 1 ? 1 : tune().small_lanes == 2 ? 2 : 0;
+    facts.one_chunk = nchunks == 1 && tune().graph != 1;      // (a captured loop would replay the launch tags of OUT_LNX)
+    facts.attn_nsplit = ns_call;
+    std::vector<StepPlan> plans;            // a handful at most
+    std::vector<int> chunk_plan;            // chunk -> its plan
+    for (int ec : chunk_sizes) {
+        size_t j = 0;
+        while (j < plans.size() && plans[j].Ec != ec) ++j;
+        if (j == plans.size()) plans.push_back(plan_step(h, ec, A, K, T, precision, facts));
+        chunk_plan.push_back((int)j);
+    }
     const size_t lane_floats = step_ws_floats(h, Mc, precision, sg_full, ns_call, nullptr, nullptr);
     const size_t need = io_off + lanes * lane_floats;
     if (int rc = ensure_arena(h, need)) return rc;
@@ -599,10 +605,10 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     }
     for (int c0 = 0; c0 < nchunks && !(lg && lg->exec); c0 += lanes) {
         if (single_step >= 0) {
-            const int e0 = chunk_start[c0], ec = chunk_sizes[c0];
+            const int e0 = chunk_start[c0];
             float* eo = stage + (size_t)e0 * K * A * T * 2;
-            if (int rc = net_step(h, sb, ec, A, K, T, single_step, x_cur + (size_t)e0 * K * A * T * 2,
-                                  hyp + (size_t)e0 * A * h->hl.total, eo, precision))
+            if (int rc = net_step(h, plans[chunk_plan[c0]], sb, single_step, x_cur + (size_t)e0 * K * A * T * 2,
+                                  hyp + (size_t)e0 * A * h->hl.total, eo))
                 return rc;
             continue;
         }
@@ -610,12 +616,12 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         for (int i = 0; i < n_steps; ++i) {
             for (int l = 0; l < lanes; ++l) {
                 if (c0 + l >= nchunks) break;
-                const int el = chunk_start[c0 + l], ec = chunk_sizes[c0 + l];
+                const int el = chunk_start[c0 + l];
                 float* xc = x_cur + (size_t)el * K * A * T * 2;
                 const float* hc = hyp + (size_t)el * A * h->hl.total;
                 const float* zc = z_use ? z_use + ((size_t)i * M + (size_t)el * K * A * T) * 2 : nullptr;
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);   // net_step launches on h->stream
-                const int rc = net_step(h, sbs[l], ec, A, K, T, i, xc, hc, nullptr, precision, zc, tune().fuse_embed && i > 0,
+                const int rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, tune().fuse_embed && i > 0,
                                         tune().fuse_embed && i + 1 < n_steps ? i + 1 : -1);
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);
                 if (rc) {

@@ -91,6 +91,19 @@ int make_w8(jmid_ctx* h, const float* dW, int N, int K, jmid_ctx::W8Image* out) 
     return 0;
 }
 
+// The operand planes of the GEMM weights go away: so does the table that points into them.
+void free_planes(jmid_ctx* h) {
+    h->wt = WeightTable{};
+    for (auto* m : {&h->wsplit, &h->w16}) {
+        for (auto& kv : *m) {
+            hipFree(kv.second.hi);
+            hipFree(kv.second.lo);
+        }
+        m->clear();
+    }
+    for (auto& kv : h->w8) hipFree(kv.second.p);
+    h->w8.clear();
+}
 
 }  // namespace jmid_host
 
@@ -110,6 +123,7 @@ int jmid_load_weight(jmid_handle_t h, const char* name, const float* host_data, 
     drop_graphs(h);
     HIPCHK(h, hipMemcpy(b.p, host_data, n_elems * sizeof(float), hipMemcpyHostToDevice));
     h->finalized = false;
+    h->wt = WeightTable{};
     return JMID_OK;
 }
 
@@ -119,6 +133,7 @@ int jmid_finalize_weights(jmid_handle_t h) {
         if (!h->w.count(kv.first)) return fail(h, JMID_ENOWEIGHT, "missing weight " + kv.first);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->finalized = false;       // from here on the derived buffers and the operand planes are freed and rebuilt
     for (float** p : {&h->pe, &h->Whyp, &h->bhyp, &h->attW1T, &h->attW2T})
         if (*p) {
             hipFree(*p);
@@ -209,72 +224,75 @@ int jmid_finalize_weights(jmid_handle_t h) {
         if (int rc = dev_alloc_copy(h, &h->attW1T, w1T)) return rc;
         if (int rc = dev_alloc_copy(h, &h->attW2T, w2T)) return rc;
     }
-    // hi/lo fp16 planes of every GEMM weight (split once; activations are split by the producing kernels)
+    // The table the launches read (jmid_ctx.hpp, WeightTable), and with it the hi/lo fp16 planes of every GEMM weight (split once;
+    // activations are split by the producing kernels).  Every name is looked up here, once, without inserting: a name that is not
+    // there is an error of this call, never a null pointer in front of a kernel.
     {
-        for (auto& kv : h->wsplit) {
-            hipFree(kv.second.hi);
-            hipFree(kv.second.lo);
-        }
-        h->wsplit.clear();
-        for (auto& kv : h->w8) hipFree(kv.second.p);
-        h->w8.clear();
-        for (auto& kv : h->w16) {
-            hipFree(kv.second.hi);
-            hipFree(kv.second.lo);
-        }
-        h->w16.clear();
+        free_planes(h);
         if (!h->range_flag) {
             HIPCHK(h, hipMalloc((void**)&h->range_flag, sizeof(int)));
         }
         HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
-        std::vector<std::string> names = {"concat3._layer.weight", "concat4._layer.weight"};
-        for (int l = 0; l < h->tf_layer; ++l) {
-            const std::string p = "transformer_encoder.layers." + std::to_string(l);
-            names.push_back(p + ".self_attn.in_proj_weight");
-            names.push_back(p + ".self_attn.out_proj.weight");
-            names.push_back(p + ".linear1.weight");
-            names.push_back(p + ".linear2.weight");
-        }
-        for (const auto& nm : names) {
-            const DevBuf& b = h->w[nm];
-            const std::vector<size_t>& shp = h->expected[nm];   // [N, K]
-            const size_t pe = blk_plane_elems(shp[0], (int)shp[1]);
-            HalfPair hp;
+        std::string missing;
+        const auto f32 = [&](const std::string& name) -> const float* {
+            const auto it = h->w.find(name);
+            if (it != h->w.end() && it->second.p) return it->second.p;
+            missing = name;
+            return nullptr;
+        };
+        // planes: a linear of the split-fp16 GEMMs - its blocked hi / lo planes and, where the shape takes it, the bf8 image of W_lo;
+        // k16: also the k16-panel copy for gemm_ln_f16x3_kernel and gemm_ln2_mx_kernel (row-complete tiles need N == 512)
+        const auto linear = [&](const std::string& p, const char* w, const char* b, bool planes, bool k16, LinearW* lw) -> int {
+            const std::string nm = p + w;
+            lw->W = f32(nm);
+            lw->bias = f32(p + b);
+            if (!lw->W || !planes) return 0;
+            const std::vector<size_t>& shp = h->expected.at(nm);   // [N, K]
+            const int N = (int)shp[0], K = (int)shp[1];
+            const size_t pe = blk_plane_elems(N, K);
+            HalfPair& hp = h->wsplit[nm];
             HIPCHK(h, hipMalloc((void**)&hp.hi, pe * sizeof(half_t)));
             HIPCHK(h, hipMalloc((void**)&hp.lo, pe * sizeof(half_t)));
             HIPCHK(h, hipMemsetAsync(hp.hi, 0, pe * sizeof(half_t), h->stream));
             HIPCHK(h, hipMemsetAsync(hp.lo, 0, pe * sizeof(half_t), h->stream));
-            hipLaunchKernelGGL(split_planes_blocked_kernel, dim3(256), dim3(256), 0, h->stream, b.p, hp.hi, hp.lo,
-                               (int)shp[0], (int)shp[1], h->range_flag, kWScale);
+            hipLaunchKernelGGL(split_planes_blocked_kernel, dim3(256), dim3(256), 0, h->stream, lw->W, hp.hi, hp.lo, N, K,
+                               h->range_flag, kWScale);
             HIPCHK(h, hipGetLastError());
-            h->wsplit[nm] = hp;
-            if (shp[0] % 32 == 0 && shp[1] % 64 == 0) {
-                jmid_ctx::W8Image img;
-                if (int rc = make_w8(h, b.p, (int)shp[0], (int)shp[1], &img)) return rc;
-                h->w8[nm] = img;
+            lw->split = hp;
+            if (N % 32 == 0 && K % 64 == 0) {
+                jmid_ctx::W8Image& img = h->w8[nm];
+                if (int rc = make_w8(h, lw->W, N, K, &img)) return rc;
+                lw->w8 = img.p;
             }
+            if (!k16) return 0;
+            HalfPair& kp = h->w16[nm];
+            HIPCHK(h, hipMalloc((void**)&kp.hi, (size_t)N * K * sizeof(half_t)));
+            HIPCHK(h, hipMalloc((void**)&kp.lo, (size_t)N * K * sizeof(half_t)));
+            hipLaunchKernelGGL(split_planes_k16_kernel, dim3(256), dim3(256), 0, h->stream, lw->W, kp.hi, kp.lo, N, K);
+            HIPCHK(h, hipGetLastError());
+            lw->k16 = kp;
+            return 0;
+        };
+        WeightTable t;
+        t.layers.resize(h->tf_layer);
+        const bool k16 = h->d == GLN_BN;
+        for (int l = 0; l < h->tf_layer; ++l) {
+            const std::string p = "transformer_encoder.layers." + std::to_string(l);
+            LayerW& lw = t.layers[l];
+            if (int rc = linear(p + ".self_attn", ".in_proj_weight", ".in_proj_bias", true, false, &lw.in_proj)) return rc;
+            if (int rc = linear(p + ".self_attn.out_proj", ".weight", ".bias", true, k16, &lw.out_proj)) return rc;
+            if (int rc = linear(p + ".linear1", ".weight", ".bias", true, false, &lw.linear1)) return rc;
+            if (int rc = linear(p + ".linear2", ".weight", ".bias", true, k16, &lw.linear2)) return rc;
+            lw.norm1 = {f32(p + ".norm1.weight"), f32(p + ".norm1.bias")};
+            lw.norm2 = {f32(p + ".norm2.weight"), f32(p + ".norm2.bias")};
         }
-        if (h->d == GLN_BN) {   // k16-panel copies for gemm_ln_f16x3_kernel (row-complete tiles need N == 512) and tail_f16x3_kernel
-            std::vector<std::string> k16names;
-            for (int l = 0; l < h->tf_layer; ++l) {
-                const std::string p = "transformer_encoder.layers." + std::to_string(l);
-                k16names.push_back(p + ".self_attn.out_proj.weight");
-                k16names.push_back(p + ".linear2.weight");
-            }
-            {
-                for (const std::string& nm : k16names) {
-                    const DevBuf& b = h->w[nm];
-                    const std::vector<size_t>& shp = h->expected[nm];   // [512, K]
-                    HalfPair hp;
-                    HIPCHK(h, hipMalloc((void**)&hp.hi, shp[0] * shp[1] * sizeof(half_t)));
-                    HIPCHK(h, hipMalloc((void**)&hp.lo, shp[0] * shp[1] * sizeof(half_t)));
-                    hipLaunchKernelGGL(split_planes_k16_kernel, dim3(256), dim3(256), 0, h->stream, b.p, hp.hi, hp.lo,
-                                       (int)shp[0], (int)shp[1]);
-                    HIPCHK(h, hipGetLastError());
-                    h->w16[nm] = hp;
-                }
-            }
-        }
+        if (int rc = linear("concat1._layer", ".weight", ".bias", false, false, &t.concat1)) return rc;
+        if (int rc = linear("concat3._layer", ".weight", ".bias", true, false, &t.concat3)) return rc;
+        if (int rc = linear("concat4._layer", ".weight", ".bias", true, false, &t.concat4)) return rc;
+        if (int rc = linear("linear._layer", ".weight", ".bias", false, false, &t.linear)) return rc;
+        t.edge_v = f32("PEDESTRIAN/edge_influence_encoder.v.weight");
+        if (!missing.empty()) return fail(h, JMID_ENOWEIGHT, "missing weight " + missing);
+        h->wt = std::move(t);
         HIPCHK(h, hipStreamSynchronize(h->stream));
         int flag = 0;
         HIPCHK(h, hipMemcpy(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost));
