@@ -230,7 +230,7 @@ int jmid_set_chunk_episodes(jmid_handle_t h, int episodes);
  * The diagnostics flavour of the library (built with -DJMID_DIAGNOSTICS as csrc/libjmid_hip_diag.so; what tests/ and tools/
  * load) additionally takes the implementation knobs the experiments of docs/NOTEBOOK.md are made with - kernel-variant
  * selectors such as "gemm_h_variant", "ln_fuse", "ln_rows", "mx_ln", "attn_mx", "attn_nsplit", "vt_stage", "graph",
- * "tail_fuse", "out_traj", "csl_swap", "attn_pf" (listed with their value ranges in csrc/jmid_abi.hip::jmid_set_tuning and
+ * "out_traj", "csl_swap", "attn_pf" (listed with their value ranges in csrc/jmid_abi.hip::jmid_set_tuning and
  * csrc/common.hpp::Tuning; every variant of a key computes the same values, most of them bit-identically) - and, with
  * -DJMID_ABLATIONS on top, the timing ablations "gemm_abl" / "attn_abl" (WRONG results).  Every switch belongs to the handle it
  * is set on.  Unknown keys return JMID_EINVAL. */
@@ -270,6 +270,15 @@ int jmid_dbg_plan_chunks(int net_kind, int nhead, int lanes, int chunk_episodes,
 /* ... of a call in arithmetic mode `precision` (a JMID_PREC_F16MX batch of at most 2 560 tokens stays ONE chunk: its out-projection /
  * linear2 launches then carry the LayerNorm and the split-KV merge; every other mode runs such a batch as two halves side by side). */
 int jmid_dbg_plan_chunks_mode(int net_kind, int nhead, int lanes, int chunk_episodes, int E, int tokens_per_episode, int precision, int* sizes, int cap);
+/* The launch plan of ONE split-fp16 GEMM (csrc/launch_plan.hpp::plan_gemm; host logic only, no device): what the planner decides
+ * for a launch of mode (0 F16X3, 1 F16X2, 2 F16MX), epilogue class epi (0 bias, 1 bias + ReLU, 2 ConcatSquash) and out (0 fp32,
+ * 1 split planes, 2 Q / K / V^T, 4 + residual + LayerNorm in one small launch) on [M, K] x [N, K], with `small_now` / `one_chunk` as the
+ * call's facts and knobs[JMID_DBG_GEMM_PLAN_KNOBS] = the jmid_set_tuning values of "gemm_h_variant", "gemm_small", "ln_rows",
+ * "small_lnx", "small_lnx2", "cus", "vt_stage", "csl_swap", "h1_stage", "gemm_pn", "small_qk", "small_pn", "gemm_ng" in that order.
+ * plan[8] <- kernel family (a mode), tile shape (GemmShape; 0 = the launch does not fit, out = 4 only), flag word, N-tiles per column
+ * group, the shape's tile rows and columns, and the row tile of the first- / second-generation GEMM + LayerNorm kernel for M rows. */
+#define JMID_DBG_GEMM_PLAN_KNOBS 13
+int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int small_now, int one_chunk, const int* knobs, int* plan);
 #endif /* JMID_DIAGNOSTICS */
 
 #pragma GCC visibility pop

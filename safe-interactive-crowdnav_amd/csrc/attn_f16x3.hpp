@@ -987,26 +987,24 @@ inline int attn_pick_nsplit(int base_blocks, int S) {
 }
 
 
-// one instantiation of the LDS-DMA kernel: its dynamic-LDS attribute once per device, then the launch
+// one instantiation of the LDS-DMA kernel (its dynamic-LDS attribute allows the CU's whole 160 KB: AttnPlan::one_wg)
 template <bool X2, bool MX, bool PIPE, bool P1, bool PF = false, int SM = 1>
-inline void launch_attn_dma(const AttnHArgs& a, dim3 grid, int nqt, hipStream_t st) {
+inline hipError_t launch_attn_dma(const AttnHArgs& a, const AttnPlan& p, dim3 grid, int nqt, hipStream_t st) {
 #ifdef JMID_DIAGNOSTICS
-    if (SM == 1 && tune().attn_sm == 2) return launch_attn_dma<X2, MX, PIPE, P1, PF, 0>(a, grid, nqt, st);      // A/B: the round 2-5 softmax
+    if (SM == 1 && p.old_softmax) return launch_attn_dma<X2, MX, PIPE, P1, PF, 0>(a, p, grid, nqt, st);      // A/B: the round 2-5 softmax
 #endif
-    static DevSeen seen;
-    const auto kern = &attn_f16x3_dma_kernel<false, X2, MX, PIPE, P1, PF, SM>;
-    if (auto once_ = first_use_on_device(seen))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), tune().attn_one_wg ? 160 * 1024 : ATT_DMA_LDS, st, a, nqt, PIPE ? 0 : attn_abl_bits(), (unsigned long long*)nullptr);
+    return launch_with_lds<&attn_f16x3_dma_kernel<false, X2, MX, PIPE, P1, PF, SM>, 160 * 1024>(
+        grid, dim3(256), p.one_wg ? 160 * 1024 : ATT_DMA_LDS, st, a, nqt, PIPE ? 0 : p.abl, (unsigned long long*)nullptr);
 }
 
 // (An 8-wave ping-pong form of this kernel - two wave groups per SIMD alternating between a matrix-instruction segment and the softmax across
 //  s_barrier - was built three times: rounds 4-5 with the ~100-instruction softmax, round 6 with the SM = 1 softmax, whose ~38 vector
 //  instructions fit inside the partner's matrix segment.  Bit-identical every time, and 7 % SLOWER than two free-running 4-wave workgroups
 //  per CU even then: profiles/r06_attn_pp_check.log, docs/NOTEBOOK.md section 11.  The kernel is not in the tree.)
-inline hipError_t launch_attn_f16x3(const AttnHArgs& a_in, int nseq, int head_dim, hipStream_t st) {
+// p: launch_plan.hpp::plan_attn(head_dim, ...)
+inline hipError_t launch_attn_f16x3(const AttnHArgs& a_in, int nseq, int head_dim, const AttnPlan& p, hipStream_t st) {
     AttnHArgs a = a_in;
-    if (head_dim == 128 && tune().attn_h_variant != 1) {
+    if (p.dma) {
         const int nqt = (a.S + 127) / 128;
         const dim3 grid1(nqt * a.nhead * nseq * a.nsplit);
         const unsigned long long x_max = std::max<unsigned long long>(grid1.x, (unsigned long long)a.nsplit * ((a.S + 31) / 32));
@@ -1014,27 +1012,27 @@ inline hipError_t launch_attn_f16x3(const AttnHArgs& a_in, int nseq, int head_di
         a.ms = fast_div_magic(a.nsplit, x_max);
         a.mh = fast_div_magic(a.nhead, x_max);
         a.nseq = nseq;
-        a.prio = tune().attn_prio;
+        a.prio = p.prio;
         // the mode is a template parameter (a run-time flag in the key-tile loop costs F16X3 ~4 %).  F16X2 / F16MX: one fp16 plane
         // of P unless "attn_mx" = 1; F16MX with bf8 K images: the logits' correction terms as bf8 MFMAs
-        const bool p1 = tune().attn_mx != 1;
+        hipError_t e;
         if (a.x2 && a.K8h) {
-            if (p1 && tune().attn_pf != 2) launch_attn_dma<true, true, false, true, true>(a, grid1, nqt, st);
-            else if (p1) launch_attn_dma<true, true, false, true>(a, grid1, nqt, st);
-            else launch_attn_dma<true, true, false, false>(a, grid1, nqt, st);
+            if (p.p1 && p.pf) e = launch_attn_dma<true, true, false, true, true>(a, p, grid1, nqt, st);
+            else if (p.p1) e = launch_attn_dma<true, true, false, true>(a, p, grid1, nqt, st);
+            else e = launch_attn_dma<true, true, false, false>(a, p, grid1, nqt, st);
         } else if (a.x2) {
-            if (p1 && tune().attn_pf != 2) launch_attn_dma<true, false, false, true, true>(a, grid1, nqt, st);
-            else if (p1) launch_attn_dma<true, false, false, true>(a, grid1, nqt, st);
-            else launch_attn_dma<true, false, false, false>(a, grid1, nqt, st);
+            if (p.p1 && p.pf) e = launch_attn_dma<true, false, false, true, true>(a, p, grid1, nqt, st);
+            else if (p.p1) e = launch_attn_dma<true, false, false, true>(a, p, grid1, nqt, st);
+            else e = launch_attn_dma<true, false, false, false>(a, p, grid1, nqt, st);
         } else {
-            launch_attn_dma<false, false, false, false>(a, grid1, nqt, st);
+            e = launch_attn_dma<false, false, false, false>(a, p, grid1, nqt, st);
         }
         if (a.nsplit > 1 && !a.skip_combine) {
             const size_t Mtot = (size_t)nseq * a.S;
             const int blocks = (int)std::min<size_t>((Mtot * (a.d / 4) + 255) / 256, 2048);
-            hipLaunchKernelGGL(attn_combine_kernel, dim3(blocks), dim3(256), bystander_lds(attn_combine_kernel), st, a, Mtot, 128);
+            hipLaunchKernelGGL(attn_combine_kernel, dim3(blocks), dim3(256), bystander_lds(p.bystander_lds, attn_combine_kernel), st, a, Mtot, 128);
         }
-        return hipGetLastError();
+        return e != hipSuccess ? e : hipGetLastError();
     }
     dim3 grid((a.S + 127) / 128, a.nhead, nseq);
     switch (head_dim) {

@@ -321,19 +321,13 @@ __global__ __launch_bounds__(256, 2) void attn_f32_packed_kernel(AttnArgs a, int
 
 
 template <int HD>
-inline hipError_t launch_attn_f32_hd(const AttnArgs& a, int nseq, hipStream_t st) {
-    if (a.S <= 16 && tune().attn_pack) {
+inline hipError_t launch_attn_f32_hd(const AttnArgs& a, int nseq, bool pack, hipStream_t st) {
+    if (a.S <= 16 && pack) {
         const int J = (a.S + 1) / 2;
         const int G = std::min(32 / a.S, 16 / J);
         const size_t lds = size_t(4) * 32 * (HD + 4) * sizeof(float);
-        static DevSeen attr_seen;
-        if (auto once_ = first_use_on_device(attr_seen)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_packed_kernel<HD>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }
         dim3 grid((nseq + G - 1) / G, (a.nhead + 3) / 4);
-        hipLaunchKernelGGL((attn_f32_packed_kernel<HD>), grid, dim3(256), lds, st, a, nseq, G, J);
-        return hipGetLastError();
+        return launch_with_lds<&attn_f32_packed_kernel<HD>>(grid, dim3(256), lds, st, a, nseq, G, J);
     }
     if (a.S > 32) {
         dim3 grid((a.S + 127) / 128, a.nhead, nseq);
@@ -345,12 +339,13 @@ inline hipError_t launch_attn_f32_hd(const AttnArgs& a, int nseq, hipStream_t st
     return hipGetLastError();
 }
 
-inline hipError_t launch_attn_f32(const AttnArgs& a, int nseq, int head_dim, hipStream_t st) {
+// pack: AttnPlan::pack (launch_plan.hpp)
+inline hipError_t launch_attn_f32(const AttnArgs& a, int nseq, int head_dim, bool pack, hipStream_t st) {
     switch (head_dim) {
-        case 16: return launch_attn_f32_hd<16>(a, nseq, st);
-        case 32: return launch_attn_f32_hd<32>(a, nseq, st);
-        case 64: return launch_attn_f32_hd<64>(a, nseq, st);
-        case 128: return launch_attn_f32_hd<128>(a, nseq, st);
+        case 16: return launch_attn_f32_hd<16>(a, nseq, pack, st);
+        case 32: return launch_attn_f32_hd<32>(a, nseq, pack, st);
+        case 64: return launch_attn_f32_hd<64>(a, nseq, pack, st);
+        case 128: return launch_attn_f32_hd<128>(a, nseq, pack, st);
         default: return hipErrorInvalidValue;
     }
 }

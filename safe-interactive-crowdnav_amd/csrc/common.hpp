@@ -121,8 +121,8 @@ __device__ __forceinline__ unsigned long long pin_uniform_rfl(unsigned long long
     return u;
 }
 
-// Tuning knobs (jmid_set_tuning).  They belong to a handle: every entry point of the C ABI installs its handle's
-// set for the duration of the call (TuneScope, thread-local), the launch helpers read it through tune().
+// Tuning knobs (jmid_set_tuning).  They belong to a handle (jmid_ctx::tune) and reach the code that reads them as an explicit
+// const Tuning& - the rules of launch_plan.hpp, which turn them into launch plans before anything is launched.
 struct Tuning {
     int fuse_embed = 1;      // the output kernel of step i embeds x for step i + 1
     int ln_fuse = 0;         // 0 auto, 1 always, 2 never: fused GEMM + residual + LayerNorm
@@ -159,26 +159,12 @@ struct Tuning {
     int attn_abl = 0;        // timing ablations (results are WRONG): only in builds with -DJMID_ABLATIONS
     int gemm_abl = 0;
 };
-inline const Tuning*& tuning_slot() {
-    static thread_local const Tuning* p = nullptr;
-    return p;
-}
-inline const Tuning& tune() {
-    static const Tuning dflt;
-    const Tuning* p = tuning_slot();
-    return p ? *p : dflt;
-}
-struct TuneScope {
-    const Tuning* prev;
-    explicit TuneScope(const Tuning* t) : prev(tuning_slot()) { tuning_slot() = t; }
-    ~TuneScope() { tuning_slot() = prev; }
-};
 #ifdef JMID_ABLATIONS
-inline int attn_abl_bits() { return tune().attn_abl; }
-inline int gemm_abl_bits() { return tune().gemm_abl; }
+inline int attn_abl_bits(const Tuning& t) { return t.attn_abl; }
+inline int gemm_abl_bits(const Tuning& t) { return t.gemm_abl; }
 #else
-inline int attn_abl_bits() { return 0; }
-inline int gemm_abl_bits() { return 0; }
+inline int attn_abl_bits(const Tuning&) { return 0; }
+inline int gemm_abl_bits(const Tuning&) { return 0; }
 #endif
 
 // One-time per-device setup (function attributes are per device).  `if (auto once = first_use_on_device(seen)) { set attributes }`:
@@ -215,11 +201,22 @@ inline DeviceOnce first_use_on_device(DevSeen& seen) {
     return o;
 }
 
-// Dynamic LDS the small row-wise kernels request although they use none (tuning knob "bystander_lds").  With a
+// Launch of a kernel that needs more dynamic LDS than the default limit: its attribute is set once per device - to MaxLds where
+// the launches of one kernel differ in their request, otherwise to the request itself -, then the launch.
+template <auto Kernel, size_t MaxLds = 0, typename... Args>
+inline hipError_t launch_with_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, Args... args) {
+    static DevSeen seen;
+    if (auto once_ = first_use_on_device(seen))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(MaxLds ? MaxLds : lds_bytes));
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+    return hipGetLastError();
+}
+
+// Dynamic LDS the small row-wise kernels request although they use none (tuning knob "bystander_lds": n).  With a
 // request above 96 KB such a workgroup cannot share a CU with an attention or GEMM workgroup of another chunk lane.
 template <typename F>
-static inline int bystander_lds(F* fn) {
-    const int n = tune().bystander_lds;
+static inline int bystander_lds(int n, F* fn) {
     if (n > 0) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, n);
     return n;
 }

@@ -89,9 +89,6 @@ __device__ __forceinline__ void store_stream(T* p, const T& v) {
 #endif
 }
 
-enum GemmOut { OUT_F32 = 0, OUT_SPLIT = 1, OUT_QKV = 2, OUT_LNX = 4 };     // OUT_LNX (gemm_small.hpp only): + residual + LayerNorm, every workgroup normalising its own
-                                                                        // 64 columns after exchanging the row statistics with the seven others of its row tile
-
 
 struct GemmHArgs {
     const half_t *Ahi, *Alo;  // [M, K] in the blocked panel layout (common.hpp::blk_index), rows padded to 128
@@ -470,14 +467,7 @@ template <int WM, int WN, int EPI, int OUT, bool X2 = false>
 inline hipError_t launch_gemm_h_cfg(const GemmHArgs& g, hipStream_t st) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM);
-    size_t lds = gemm_h_lds_bytes<WM, WN>();
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_kernel<WM, WN, EPI, OUT, X2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    hipLaunchKernelGGL((gemm_f16x3_kernel<WM, WN, EPI, OUT, X2>), grid, dim3(256), lds, st, g);
-    return hipGetLastError();
+    return launch_with_lds<&gemm_f16x3_kernel<WM, WN, EPI, OUT, X2>>(grid, dim3(256), gemm_h_lds_bytes<WM, WN>(), st, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -595,13 +585,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f16x3_dma_kernel(GemmHArgs g, int
 template <int EPI, int OUT, bool X2 = false>
 inline hipError_t launch_gemm_h_dma(const GemmHArgs& g, hipStream_t st) {
     const int ntm = (g.M + 127) / 128, ntn = (g.N + 127) / 128;
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_dma_kernel<EPI, OUT, X2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)DMA_LDS_BYTES);
-    }
-    hipLaunchKernelGGL((gemm_f16x3_dma_kernel<EPI, OUT, X2>), dim3(ntm * ntn), dim3(256), DMA_LDS_BYTES, st, g, ntm, ntn);
-    return hipGetLastError();
+    return launch_with_lds<&gemm_f16x3_dma_kernel<EPI, OUT, X2>>(dim3(ntm * ntn), dim3(256), DMA_LDS_BYTES, st, g, ntm, ntn);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -720,16 +704,9 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x3_dma256_kernel(GemmHArgs g, 
 }
 
 template <int EPI, int OUT, bool X2 = false>
-inline hipError_t launch_gemm_h_dma256(const GemmHArgs& g, hipStream_t st) {
+inline hipError_t launch_gemm_h_dma256(const GemmHArgs& g, hipStream_t st, int ng = 0, int abl = 0) {      // ng: GemmPlan::group_tiles
     const int ntm = (g.M + 255) / 256, ntn = (g.N + 127) / 128;
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_dma256_kernel<EPI, OUT, X2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)DMA2_LDS_BYTES);
-    }
-    hipLaunchKernelGGL((gemm_f16x3_dma256_kernel<EPI, OUT, X2>), dim3(ntm * ntn), dim3(512), DMA2_LDS_BYTES, st, g, ntm, ntn,
-                       tune().gemm_ng, gemm_abl_bits());
-    return hipGetLastError();
+    return launch_with_lds<&gemm_f16x3_dma256_kernel<EPI, OUT, X2>>(dim3(ntm * ntn), dim3(512), DMA2_LDS_BYTES, st, g, ntm, ntn, ng, abl);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1158,17 +1135,10 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x3_dma256x256_kernel(GemmHArgs
 }
 
 template <int EPI, int OUT, bool X2 = false>
-inline hipError_t launch_gemm_h_dma256x256(const GemmHArgs& g, hipStream_t st) {
+inline hipError_t launch_gemm_h_dma256x256(const GemmHArgs& g, hipStream_t st, int flags = 3, int abl = 0) {      // flags: GemmPlan::flags (launch_plan.hpp)
     const int ntm = (g.M + 255) / 256, ntn = g.N / 256;
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_dma256x256_kernel<EPI, OUT, X2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)DMA3_LDS_BYTES);
-    }
-    const int vs = tune().vt_stage;     // 0 / 1: V^T and Q / K through LDS, 2: neither, 3: V^T only
-    hipLaunchKernelGGL((gemm_f16x3_dma256x256_kernel<EPI, OUT, X2>), dim3(ntm * ntn), dim3(512), DMA3_LDS_BYTES, st, g, ntm, ntn, (gemm_abl_bits() & 8) ? 0 : 1,
-                       vs == 2 ? 0 : (vs == 3 ? 1 : 3));
-    return hipGetLastError();
+    return launch_with_lds<&gemm_f16x3_dma256x256_kernel<EPI, OUT, X2>>(dim3(ntm * ntn), dim3(512), DMA3_LDS_BYTES, st, g, ntm, ntn,
+                                                                         (abl & 8) ? 0 : 1, flags);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1434,67 +1404,15 @@ __global__ __launch_bounds__(64 * WR * WC, (WR * WC == 4 && WM == 2 && NS > 2) ?
     gemm_h_epilogue<WM, WN, EPI, OUT, true, OUT == OUT_QKV && !(WM == 2 && WN == 4)>(g, acc, m0, n0, wr, wc, l31, hi, BM, BN);
 }
 
+// flags, group_tiles: GemmPlan's (launch_plan.hpp)
 template <int EPI, int OUT, int WR, int WC, int WM, int WN, int NS, bool K8IMG = false>
-inline hipError_t launch_gemm_mx_cfg(const GemmHArgs& g, hipStream_t st) {
+inline hipError_t launch_gemm_mx_cfg(const GemmHArgs& g, hipStream_t st, int flags, int group_tiles) {
     using C = MxCfg<WR, WC, WM, WN, NS>;
     if constexpr (OUT == OUT_QKV && WM == 2 && WN == 4 && !K8IMG)      // bf8 K images wanted (attn_mx = 1): the variant that can write them
-        if (g.K8h) return launch_gemm_mx_cfg<EPI, OUT, WR, WC, WM, WN, NS, true>(g, st);
+        if (g.K8h) return launch_gemm_mx_cfg<EPI, OUT, WR, WC, WM, WN, NS, true>(g, st, flags, group_tiles);
     const int ntm = (g.M + C::BM - 1) / C::BM, ntn = g.N / C::BN;
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mx_kernel<EPI, OUT, WR, WC, WM, WN, NS, K8IMG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-    }
-    const int vs = tune().vt_stage;     // 0 / 1: V^T and Q / K through LDS, 2: neither, 3: V^T only; bit 2: row-wise ConcatSquash epilogue
-    hipLaunchKernelGGL((gemm_mx_kernel<EPI, OUT, WR, WC, WM, WN, NS, K8IMG>), dim3(ntm * ntn), dim3(C::NT), C::LDS_BYTES, st, g, ntm, ntn,
-                       (vs == 2 ? 0 : (vs == 3 ? 1 : 3)) | (tune().csl_swap == 2 ? 0 : 4) | (tune().csl_swap == 3 ? 8 : 0) | (tune().h1_stage == 2 ? 0 : 16) |
-                           ((tune().gemm_pn > 1 && ntn % tune().gemm_pn == 0 ? ntn / tune().gemm_pn : 0) << 8));
-    return hipGetLastError();
-}
-template <int EPI, int OUT> inline hipError_t launch_gemm_mx_64(const GemmHArgs& g, hipStream_t st) { return launch_gemm_mx_cfg<EPI, OUT, 2, 2, 1, 1, 4>(g, st); }
-template <int EPI, int OUT> inline hipError_t launch_gemm_mx_128(const GemmHArgs& g, hipStream_t st) { return launch_gemm_mx_cfg<EPI, OUT, 2, 2, 2, 2, 4>(g, st); }
-template <int EPI, int OUT> inline hipError_t launch_gemm_mx_256x128(const GemmHArgs& g, hipStream_t st) { return launch_gemm_mx_cfg<EPI, OUT, 4, 2, 2, 2, 3>(g, st); }
-// 256 x 256: a TWO-stage ring - the K loop's body is two tiles, so every tile's stage is a constant and its fragment reads are lane offset +
-// immediate (29 vector address instructions per k64 block less than with three stages, whose extra tile of look-ahead measured neutral in
-// round 2); a 51-episode call 113.4 -> 112.8 ms, 256 episodes 573 -> 560 ms.  Diagnostics variant 8: the three-stage ring, for the A/B.
-template <int EPI, int OUT> inline hipError_t launch_gemm_mx_256x256(const GemmHArgs& g, hipStream_t st) { return launch_gemm_mx_cfg<EPI, OUT, 4, 2, 2, 4, 2>(g, st); }
-template <int EPI, int OUT> inline hipError_t launch_gemm_mx_256x256_ns3(const GemmHArgs& g, hipStream_t st) { return launch_gemm_mx_cfg<EPI, OUT, 4, 2, 2, 4, 3>(g, st); }
-// 128 x 256 with four waves (the 256 x 256 shape's wave tile), a two-stage ring: 80 KB of LDS and <= 256 registers, so TWO workgroups
-// share a CU - one's epilogue (stores through LDS, no MFMA) under the other's K loop
-template <int EPI, int OUT> inline hipError_t launch_gemm_mx_128x256(const GemmHArgs& g, hipStream_t st) { return launch_gemm_mx_cfg<EPI, OUT, 2, 2, 2, 4, 2>(g, st); }
-
-// the F16X2 shape rules (launch_gemm_h_mode below) for the fp8-correction kernels
-template <int EPI, int OUT>
-inline hipError_t launch_gemm_mx(const GemmHArgs& g, hipStream_t st) {
-    const long big = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-    const int v = tune().gemm_h_variant;
-    // the 256 x 128 shape with the ConcatSquash epilogue into fp32 (concat4: N = 128, never enough tiles for it) spills: not instantiated
-    constexpr bool has_256x128 = !(EPI == EPI_CSL && OUT == OUT_F32);
-    if (v == 3) return launch_gemm_mx_128<EPI, OUT>(g, st);
-    if constexpr (has_256x128)
-        if (v == 4) return launch_gemm_mx_256x128<EPI, OUT>(g, st);
-    if (v == 5) return launch_gemm_mx_64<EPI, OUT>(g, st);
-    if constexpr (EPI != EPI_CSL) {
-        if (v == 6 && g.N % 256 == 0) return launch_gemm_mx_256x256<EPI, OUT>(g, st);
-#ifdef JMID_DIAGNOSTICS      // measured: 51 episodes in ONE chunk 119.95 -> 117.82 ms, as two chunks in flight (the default plan) 114.62 -> 115.63
-        if (v == 7 && g.N % 256 == 0) return launch_gemm_mx_128x256<EPI, OUT>(g, st);
-        if (v == 8 && g.N % 256 == 0) return launch_gemm_mx_256x256_ns3<EPI, OUT>(g, st);
-#endif
-    }
-    if (big < 256) return launch_gemm_mx_64<EPI, OUT>(g, st);
-    const long nb256 = (long)((g.M + 255) / 256) * ((g.N + 127) / 128);
-    auto eff = [](long nb) { return (double)nb / (double)(((nb + 255) / 256) * 256); };
-    if constexpr (EPI != EPI_CSL)
-        if (g.N % 256 == 0) {
-            // also below one workgroup per CU, from 7168 rows: two chunks are in flight, and the larger tile moves a third
-            // fewer operand bytes per FLOP (2 x 12 episodes per call 60.6 vs 67.6 ms, 2 x 8: 45.1 vs 47.4, 2 x 6 equal,
-            // 2 x 5: 35.8 vs 33.4; tools/single_scene_sweep.py gemm_h_variant=0,6 f16mx E)
-            const long nbq = (long)((g.M + 255) / 256) * (g.N / 256);
-            if ((nbq >= 256 && 1.2 * eff(nbq) >= eff(nb256)) || (nbq < 256 && g.M >= 7168)) return launch_gemm_mx_256x256<EPI, OUT>(g, st);
-        }
-    if constexpr (has_256x128)
-        if (nb256 >= 256 && 1.2 * eff(nb256) >= eff(big)) return launch_gemm_mx_256x128<EPI, OUT>(g, st);
-    return launch_gemm_mx_128<EPI, OUT>(g, st);
+    return launch_with_lds<&gemm_mx_kernel<EPI, OUT, WR, WC, WM, WN, NS, K8IMG>>(dim3(ntm * ntn), dim3(C::NT), C::LDS_BYTES, st, g, ntm, ntn,
+                                                                                  flags | (group_tiles << 8));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1575,59 +1493,66 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_dma64_kernel(GemmHArgs g, i
 template <int EPI, int OUT, bool X2 = false>
 inline hipError_t launch_gemm_h_dma64(const GemmHArgs& g, hipStream_t st) {
     const int ntm = (g.M + 63) / 64, ntn = (g.N + 63) / 64;
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_dma64_kernel<EPI, OUT, X2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)DMA64_LDS_BYTES);
-    }
-    hipLaunchKernelGGL((gemm_f16x3_dma64_kernel<EPI, OUT, X2>), dim3(ntm * ntn), dim3(256), DMA64_LDS_BYTES, st, g, ntm, ntn);
-    return hipGetLastError();
+    return launch_with_lds<&gemm_f16x3_dma64_kernel<EPI, OUT, X2>>(dim3(ntm * ntn), dim3(256), DMA64_LDS_BYTES, st, g, ntm, ntn);
 }
 
+// The large-tile kernels of F16X3 / F16X2, by the plan's shape (launch_plan.hpp)
 template <int EPI, int OUT, bool X2>
-inline hipError_t launch_gemm_h_mode(const GemmHArgs& g, hipStream_t st) {
-    if constexpr (X2)      // JMID_PREC_F16MX: every shape has its fp8-correction kernel (N a multiple of 128, K of 64: all of the net's GEMMs)
-        if (g.W8 && g.K % 64 == 0 && g.N % 128 == 0 && tune().gemm_h_variant != 1 && tune().gemm_h_variant != 2)
-            return launch_gemm_mx<EPI, OUT>(g, st);
-    const long big = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-    // 0 auto, 1 = 64x64 register-staged, 2 = 128x128 register-staged, 3 = 128x128 LDS-DMA, 4 = 256x128 LDS-DMA,
-    // 5 = 64x64 LDS-DMA, 6 = 256x256 LDS-DMA (N % 256 == 0)
-    const int v = tune().gemm_h_variant;
-    if (v == 1) return launch_gemm_h_cfg<1, 1, EPI, OUT, X2>(g, st);
-    if (v == 2) return launch_gemm_h_cfg<2, 2, EPI, OUT, X2>(g, st);
-    if (v == 3) return launch_gemm_h_dma<EPI, OUT, X2>(g, st);
-    if (v == 4) return launch_gemm_h_dma256<EPI, OUT, X2>(g, st);
-    if (v == 5) return launch_gemm_h_dma64<EPI, OUT, X2>(g, st);
-    // (the ConcatSquash epilogue next to 128 accumulators spills: that shape is not instantiated for it)
-    if constexpr (EPI != EPI_CSL)
-        if (v == 6 && g.N % 256 == 0) return launch_gemm_h_dma256x256<EPI, OUT, X2>(g, st);
-    if (big < 256) return launch_gemm_h_dma64<EPI, OUT, X2>(g, st);
-    // auto: 256x128 unless the coarser grid quantises badly onto the 256 CUs (one workgroup per CU)
-    const long nb256 = (long)((g.M + 255) / 256) * ((g.N + 127) / 128);
-    auto eff = [](long nb) { return (double)nb / (double)(((nb + 255) / 256) * 256); };
-    // 256x256 when N allows it (in_proj, linear1) and the grid still fills the chip; the ConcatSquash epilogue needs
-    // too many registers next to the 128 accumulators
-    if constexpr (EPI != EPI_CSL) if (g.N % 256 == 0) {
-        // (below one workgroup per CU too from 12288 rows - two chunks are in flight: 2 x 12 episodes per call 76.0 vs 79.7 ms
-        // in F16X2, 102.2 vs 107.5 in F16X3; 2 x 8: within 1 %)
-        const long nbq = (long)((g.M + 255) / 256) * (g.N / 256);
-        if ((nbq >= 256 && 1.2 * eff(nbq) >= eff(nb256)) || (nbq < 256 && g.M >= 12288)) return launch_gemm_h_dma256x256<EPI, OUT, X2>(g, st);
+inline hipError_t launch_gemm_h_mode(const GemmHArgs& g, const GemmPlan& p, hipStream_t st) {
+    switch (p.shape) {
+        case GS_REG_64: return launch_gemm_h_cfg<1, 1, EPI, OUT, X2>(g, st);
+        case GS_REG_128: return launch_gemm_h_cfg<2, 2, EPI, OUT, X2>(g, st);
+        case GS_64: return launch_gemm_h_dma64<EPI, OUT, X2>(g, st);
+        case GS_128: return launch_gemm_h_dma<EPI, OUT, X2>(g, st);
+        case GS_256x128: return launch_gemm_h_dma256<EPI, OUT, X2>(g, st, p.group_tiles, p.abl);
+        case GS_256x256:
+            if constexpr (gemm_shape_built(GM_X2, EPI, OUT, GS_256x256)) return launch_gemm_h_dma256x256<EPI, OUT, X2>(g, st, p.flags, p.abl);
+            return hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;
     }
-    if (nb256 >= 256 && 1.2 * eff(nb256) >= eff(big)) return launch_gemm_h_dma256<EPI, OUT, X2>(g, st);
-    return launch_gemm_h_dma<EPI, OUT, X2>(g, st);
+}
+
+// ... and of F16MX: MxCfg<waves along M, along N, wave tile / 32 along M, along N, ring stages>
+//   256 x 256: a TWO-stage ring - the K loop's body is two tiles, so every tile's stage is a constant and its fragment reads are lane
+//   offset + immediate (29 vector address instructions per k64 block less than with three stages, whose extra tile of look-ahead
+//   measured neutral in round 2); a 51-episode call 113.4 -> 112.8 ms, 256 episodes 573 -> 560 ms.  GS_256x256_NS3: the three-stage
+//   ring, for the A/B.
+//   128 x 256 with four waves (the 256 x 256 shape's wave tile), a two-stage ring: 80 KB of LDS and <= 256 registers, so TWO
+//   workgroups share a CU - one's epilogue (stores through LDS, no MFMA) under the other's K loop (measured: 51 episodes in ONE
+//   chunk 119.95 -> 117.82 ms, as two chunks in flight (the default plan) 114.62 -> 115.63)
+template <int EPI, int OUT>
+inline hipError_t launch_gemm_mx(const GemmHArgs& g, const GemmPlan& p, hipStream_t st) {
+    switch (p.shape) {
+        case GS_64: return launch_gemm_mx_cfg<EPI, OUT, 2, 2, 1, 1, 4>(g, st, p.flags, p.group_tiles);
+        case GS_128: return launch_gemm_mx_cfg<EPI, OUT, 2, 2, 2, 2, 4>(g, st, p.flags, p.group_tiles);
+        case GS_256x128:
+            if constexpr (gemm_shape_built(GM_MX, EPI, OUT, GS_256x128)) return launch_gemm_mx_cfg<EPI, OUT, 4, 2, 2, 2, 3>(g, st, p.flags, p.group_tiles);
+            return hipErrorInvalidValue;
+        case GS_256x256:
+            if constexpr (gemm_shape_built(GM_MX, EPI, OUT, GS_256x256)) return launch_gemm_mx_cfg<EPI, OUT, 4, 2, 2, 4, 2>(g, st, p.flags, p.group_tiles);
+            return hipErrorInvalidValue;
+#ifdef JMID_DIAGNOSTICS
+        case GS_128x256:
+            if constexpr (gemm_shape_built(GM_MX, EPI, OUT, GS_128x256)) return launch_gemm_mx_cfg<EPI, OUT, 2, 2, 2, 4, 2>(g, st, p.flags, p.group_tiles);
+            return hipErrorInvalidValue;
+        case GS_256x256_NS3:
+            if constexpr (gemm_shape_built(GM_MX, EPI, OUT, GS_256x256_NS3)) return launch_gemm_mx_cfg<EPI, OUT, 4, 2, 2, 4, 3>(g, st, p.flags, p.group_tiles);
+            return hipErrorInvalidValue;
+#endif
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // launches of at most one workgroup per CU: gemm_small.hpp (defined after the LayerNorm headers it builds on)
 template <int EPI, int OUT>
-inline hipError_t launch_gemm_small(const GemmHArgs& g, int wc, hipStream_t st);
-inline int small_gemm_shape(const GemmHArgs& g, int small_now);
+inline hipError_t launch_gemm_small(const GemmHArgs& g, const GemmPlan& p, hipStream_t st);
 
-// the arithmetic mode is a template parameter of every kernel (a run-time flag in the K loops cost F16X3 4 %)
-// small_now: may the small-launch kernels run (gemm_small.hpp::small_gemm_shape; a fact of the call, not a knob)
+// One split-fp16 GEMM as its plan says (launch_plan.hpp::plan_gemm, made for this g's M, N, K and operand set)
 template <int EPI, int OUT>
-inline hipError_t launch_gemm_h(const GemmHArgs& g, hipStream_t st, int small_now = 1) {
-    if (const int wc = small_gemm_shape(g, small_now)) return launch_gemm_small<EPI, OUT>(g, wc, st);      // at most one workgroup per CU
-    return g.x2 ? launch_gemm_h_mode<EPI, OUT, true>(g, st) : launch_gemm_h_mode<EPI, OUT, false>(g, st);
+inline hipError_t launch_gemm_h(const GemmHArgs& g, const GemmPlan& p, hipStream_t st) {
+    if (gemm_shape_small(p.shape)) return launch_gemm_small<EPI, OUT>(g, p, st);
+    if (p.mode == GM_MX) return launch_gemm_mx<EPI, OUT>(g, p, st);
+    return p.mode == GM_X2 ? launch_gemm_h_mode<EPI, OUT, true>(g, p, st) : launch_gemm_h_mode<EPI, OUT, false>(g, p, st);
 }
 
 // fp32 -> hi/lo planes (weights at load time, activations produced by fp32-only kernels)

@@ -10,10 +10,9 @@
 // LDS buffer afterwards (one barrier per K-tile).
 #pragma once
 #include "common.hpp"
+#include "launch_plan.hpp"
 
 namespace jmid {
-
-enum GemmEpi { EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_CSL = 2 };
 
 struct GemmArgs {
     const float* A;      // [M, K], row stride lda
@@ -175,14 +174,7 @@ template <int WM, int WN, int EPI>
 inline hipError_t launch_gemm_f32_cfg(const GemmArgs& g, hipStream_t st) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM);
-    size_t lds = gemm_f32_lds_bytes<WM, WN>();
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<WM, WN, EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, EPI>), grid, dim3(256), lds, st, g);
-    return hipGetLastError();
+    return launch_with_lds<&gemm_f32_kernel<WM, WN, EPI>>(grid, dim3(256), gemm_f32_lds_bytes<WM, WN>(), st, g);
 }
 
 template <int EPI>

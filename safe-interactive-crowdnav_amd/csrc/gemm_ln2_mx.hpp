@@ -432,25 +432,17 @@ __global__ __launch_bounds__(64 * (16 / WN), 2) void gemm_ln2_mx_kernel(GemmLn2A
 }
 
 template <int WM, int WN>
-inline void launch_gemm_ln2_cfg(const GemmLn2Args& g, hipStream_t st) {
+inline hipError_t launch_gemm_ln2_cfg(const GemmLn2Args& g, hipStream_t st) {
     using C = Gl2Cfg<WM, WN>;
-    static DevSeen seen;
-    if (auto once_ = first_use_on_device(seen))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ln2_mx_kernel<WM, WN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)C::LDS_BYTES);
-    hipLaunchKernelGGL((gemm_ln2_mx_kernel<WM, WN>), dim3((g.M + C::BM - 1) / C::BM), dim3(C::NT), C::LDS_BYTES, st, g);
+    return launch_with_lds<&gemm_ln2_mx_kernel<WM, WN>>(dim3((g.M + C::BM - 1) / C::BM), dim3(C::NT), C::LDS_BYTES, st, g);
 }
-inline hipError_t launch_gemm_ln2_mx(const GemmLn2Args& g, hipStream_t st) {
+// rows: launch_plan.hpp::plan_ln_rows (second generation; the 64-row shape is built in the diagnostics flavour only)
+inline hipError_t launch_gemm_ln2_mx(const GemmLn2Args& g, int rows, hipStream_t st) {
 #ifdef JMID_DIAGNOSTICS
-    // the 64-row shape (two workgroups per CU; measured 10 % slower on full launches, and hipcc spills 48 registers in it) exists
-    // in the diagnostics flavour only, behind the "ln_rows" knob: the production library always runs the 128-row shape
-    if (tune().ln_rows == 64) {
-        launch_gemm_ln2_cfg<2, 4>(g, st);
-        return hipGetLastError();
-    }
+    if (rows == 64) return launch_gemm_ln2_cfg<2, 4>(g, st);
 #endif
-    launch_gemm_ln2_cfg<4, 2>(g, st);
-    return hipGetLastError();
+    (void)rows;
+    return launch_gemm_ln2_cfg<4, 2>(g, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -582,52 +582,29 @@ __global__ __launch_bounds__(512, 2) void gemm_ln_mx_kernel(GemmLnArgs g, int nt
     else gln64_epilogue(g, acc, lds_raw, m0, wid, wc, lane, l31, hi);
 }
 
+// rows: launch_plan.hpp::plan_ln_rows (first generation)
 template <bool X2>
-inline hipError_t launch_gemm_ln_mode(const GemmLnArgs& g, hipStream_t st) {
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ln_f16x3_kernel<X2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)GLN_LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ln128_f16x3_kernel<X2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)GLN2_LDS_BYTES);
-    }
-    // row tile by how well the grid fills whole rounds of the 256 CUs (one workgroup per CU); at equal fill the
-    // 128-row kernel is ~4 % faster (W streams through L2 -> LDS half as often)
-    auto fill = [](long n) { return (double)n / (double)(((n + 255) / 256) * 256); };
-    const long n128 = (g.M + GLN2_BM - 1) / GLN2_BM, n64 = (g.M + GLN_BM - 1) / GLN_BM;
-    const bool rows128 = tune().ln_rows == 128 || (tune().ln_rows == 0 && 1.04 * fill(n128) >= fill(n64));
-    if (rows128) {
+inline hipError_t launch_gemm_ln_mode(const GemmLnArgs& g, int rows, hipStream_t st) {
+    if (rows == GLN2_BM) {
         const int ntm = (g.M + GLN2_BM - 1) / GLN2_BM;
-        hipLaunchKernelGGL(gemm_ln128_f16x3_kernel<X2>, dim3(ntm), dim3(512), GLN2_LDS_BYTES, st, g, ntm);
-        return hipGetLastError();
+        return launch_with_lds<&gemm_ln128_f16x3_kernel<X2>>(dim3(ntm), dim3(512), GLN2_LDS_BYTES, st, g, ntm);
     }
     const int ntm = (g.M + GLN_BM - 1) / GLN_BM;
-    hipLaunchKernelGGL(gemm_ln_f16x3_kernel<X2>, dim3(ntm), dim3(512), GLN_LDS_BYTES, st, g, ntm);
-    return hipGetLastError();
+    return launch_with_lds<&gemm_ln_f16x3_kernel<X2>>(dim3(ntm), dim3(512), GLN_LDS_BYTES, st, g, ntm);
 }
 
-inline hipError_t launch_gemm_ln_mx(const GemmLnArgs& g, hipStream_t st) {
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ln_mx_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)GLNX_LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ln_mx_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)GLNX_LDS_BYTES);
+inline hipError_t launch_gemm_ln_mx(const GemmLnArgs& g, int rows, hipStream_t st) {
+    if (rows == GLN2_BM) {
+        const int ntm = (g.M + GLN2_BM - 1) / GLN2_BM;
+        return launch_with_lds<&gemm_ln_mx_kernel<4>>(dim3(ntm), dim3(512), GLNX_LDS_BYTES, st, g, ntm);
     }
-    // the row tile by grid fill, as launch_gemm_ln_mode
-    auto fill = [](long n) { return (double)n / (double)(((n + 255) / 256) * 256); };
-    const long n128 = (g.M + GLN2_BM - 1) / GLN2_BM, n64 = (g.M + GLN_BM - 1) / GLN_BM;
-    if (tune().ln_rows == 128 || (tune().ln_rows == 0 && 1.04 * fill(n128) >= fill(n64))) {
-        hipLaunchKernelGGL(gemm_ln_mx_kernel<4>, dim3((int)n128), dim3(512), GLNX_LDS_BYTES, st, g, (int)n128);
-    } else {
-        hipLaunchKernelGGL(gemm_ln_mx_kernel<2>, dim3((int)n64), dim3(512), GLNX_LDS_BYTES, st, g, (int)n64);
-    }
-    return hipGetLastError();
+    const int ntm = (g.M + GLN_BM - 1) / GLN_BM;
+    return launch_with_lds<&gemm_ln_mx_kernel<2>>(dim3(ntm), dim3(512), GLNX_LDS_BYTES, st, g, ntm);
 }
 
-inline hipError_t launch_gemm_ln(const GemmLnArgs& g, hipStream_t st) {
-    if (g.x2 && g.W8 && g.K % 64 == 0) return launch_gemm_ln_mx(g, st);
-    return g.x2 ? launch_gemm_ln_mode<true>(g, st) : launch_gemm_ln_mode<false>(g, st);
+inline hipError_t launch_gemm_ln(const GemmLnArgs& g, int rows, hipStream_t st) {
+    if (g.x2 && g.W8 && g.K % 64 == 0) return launch_gemm_ln_mx(g, rows, st);
+    return g.x2 ? launch_gemm_ln_mode<true>(g, rows, st) : launch_gemm_ln_mode<false>(g, rows, st);
 }
 
 }  // namespace jmid

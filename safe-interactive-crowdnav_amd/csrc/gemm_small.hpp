@@ -93,7 +93,7 @@ constexpr int SM_STG_LD = 68;                              // floats per row of 
 // front of an incomplete one is complete and finishes).  The polls are BOUNDED all the same - a workgroup that does not see a
 // partner within ~10^5 polls sets bit 1 of the range flag and leaves, and the host drops the fused path for the handle.
 constexpr int SM_LNX_POLLS = 1 << 17;
-constexpr int SM_LNX_MAX_TILES = 64;                            // row tiles of a launch: 32 with one workgroup per CU, 33 ... 64 with two
+constexpr int SM_LNX_MAX_TILES = kLnxMaxTiles;                           // row tiles of a launch: 32 with one workgroup per CU, 33 ... 64 with two
 constexpr size_t SM_LNX_STATS = size_t(2) * SM_LNX_MAX_TILES * 8 * 64;        // per step workspace: two statistics x row tiles x 8 blocks x 64 rows ...
 constexpr size_t SM_LNX_GRANULES = SM_LNX_STATS + SM_LNX_MAX_TILES * 8;       // ... + one flag per block of the A operand (lnx_combine)
 
@@ -674,98 +674,40 @@ __global__ __launch_bounds__(128 * WC, TWO ? WC : 1) void gemm_small_kernel(Gemm
 }
 
 
-// bytes all eight XCDs pull from the Infinity Cache with pn column groups: every XCD its column group's share of W and the A rows
-// of its part of the M range
-inline int small_pick_groups(const GemmHArgs& g, int ntn, double w_bytes_per_el, double a_bytes_per_el) {
-    const double wb = (double)g.N * g.K * w_bytes_per_el, ab = (double)g.M * g.K * a_bytes_per_el;
-    int best = 1;
-    double best_bytes = 8.0 * wb + ab;
-    for (int pn = 2; pn <= 8; pn *= 2) {
-        if (ntn % pn != 0) break;
-        const double bytes = 8.0 * wb / pn + pn * ab;
-        if (bytes < best_bytes) {
-            best = pn;
-            best_bytes = bytes;
-        }
-    }
-    return best;
-}
-
+// flags, gw: GemmPlan's flags and group_tiles (launch_plan.hpp)
 template <int EPI, int OUT, int MODE, int WC, bool TWO = false>
-inline hipError_t launch_gemm_small_cfg(const GemmHArgs& g, hipStream_t st) {
+inline hipError_t launch_gemm_small_cfg(const GemmHArgs& g, hipStream_t st, int flags, int gw) {
     using C = SmCfg<MODE, WC, TWO>;
     const int ntm = (g.M + C::BM - 1) / C::BM, ntn = g.N / C::BN;
-    static DevSeen attr_seen;
-    if (auto once_ = first_use_on_device(attr_seen))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_small_kernel<EPI, OUT, MODE, WC, TWO>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-    const int pn = tune().small_pn > 0 ? (ntn % tune().small_pn == 0 ? tune().small_pn : 1)
-                                       : small_pick_groups(g, ntn, MODE == SM_MX ? 3.0 : 4.0, MODE == SM_X3 ? 4.0 : 2.0);
-    const int flags = (tune().csl_swap == 2 ? 0 : 4) | (tune().csl_swap == 3 ? 8 : 0) | (tune().small_qk == 2 ? 16 : 0);
-    const int gw = ntn / pn;
-    hipLaunchKernelGGL((gemm_small_kernel<EPI, OUT, MODE, WC, TWO>), dim3(ntm * ntn), dim3(C::NT), C::LDS_BYTES, st, g, ntm, ntn,
-                       gw, flags, fast_div_magic(ntm * gw, (unsigned long long)ntm * ntn), fast_div_magic(gw, (unsigned long long)ntm * ntn));
-    return hipGetLastError();
-}
-
-// Does this GEMM run on the small-launch kernel, and in which shape?  One workgroup per CU: at most 256 tiles.
-//   -> 0 no, 2 / 4 = WC, 8 = WC 4 with two workgroups per CU.  "gemm_small" knob: 0 auto, 1 never.
-// small_now (a fact of the call: the planner's CallFacts): 1 = one chunk in flight, 0 = several - with two lanes the
-// one-workgroup-per-CU launches collide: 4 episodes as 2 x 2 measured 4 % slower with them -, 2 = experiment "small_lanes" = 2
-inline int small_gemm_shape(const GemmHArgs& g, int small_now) {
-    if (tune().gemm_small == 1 || tune().gemm_h_variant != 0 || !small_now) return 0;
-    if (g.K % 128 != 0 || g.N % 128 != 0) return 0;       // (k128 ring stages)
-    const long ntm = (g.M + 63) / 64;
-    if (small_now == 2) return g.x2 && ntm * (g.N / 128) <= 512 ? 8 : 0;      // (experiment "small_lanes" = 2)
-    if (ntm * (g.N / 64) <= 256) return 2;
-    if (ntm * (g.N / 128) <= 256) return 4;
-    // 257 ... 512 tiles of 64 x 128 (two scenes; the reference's shipped K = 100): the same kernel, two workgroups per CU
-    // (not F16X3: two k64 stages of its four operand planes do not fit half a CU's LDS)
-    if (g.x2 && tune().gemm_small != 2 && ntm * (g.N / 128) <= 512) return 8;
-    // (F16X3 at 257 ... 512 tiles in two rounds of one workgroup per CU measured slower than the round-3 kernels: 0.996 vs 0.977 ms
-    //  per shipped-point call)
-    return 0;
+    return launch_with_lds<&gemm_small_kernel<EPI, OUT, MODE, WC, TWO>>(dim3(ntm * ntn), dim3(C::NT), C::LDS_BYTES, st, g, ntm, ntn, gw, flags,
+                                                                         fast_div_magic(ntm * gw, (unsigned long long)ntm * ntn),
+                                                                         fast_div_magic(gw, (unsigned long long)ntm * ntn));
 }
 
 template <int EPI, int OUT, int MODE>
-inline hipError_t launch_gemm_small_mode(const GemmHArgs& g, int wc, hipStream_t st) {
-    if (wc == 2) return launch_gemm_small_cfg<EPI, OUT, MODE, 2>(g, st);
-    if constexpr (OUT == OUT_LNX) {                                  // (N = 512: always the 64-column shape; 9 = two workgroups per CU)
-        if constexpr (MODE == SM_MX)
-            if (wc == 9) return launch_gemm_small_cfg<EPI, OUT, MODE, 2, true>(g, st);
-        return hipErrorInvalidValue;
+inline hipError_t launch_gemm_small_mode(const GemmHArgs& g, const GemmPlan& p, hipStream_t st) {
+    constexpr GemmMode GM = (GemmMode)MODE;
+    static_assert(SM_X3 == (int)GM_X3 && SM_X2 == (int)GM_X2 && SM_MX == (int)GM_MX, "SmallMode is GemmMode");
+    switch (p.shape) {
+        case GS_SMALL_64x64: return launch_gemm_small_cfg<EPI, OUT, MODE, 2>(g, st, p.flags, p.group_tiles);
+        case GS_SMALL_64x64_TWO:
+            if constexpr (gemm_shape_built(GM, EPI, OUT, GS_SMALL_64x64_TWO)) return launch_gemm_small_cfg<EPI, OUT, MODE, 2, true>(g, st, p.flags, p.group_tiles);
+            return hipErrorInvalidValue;
+        case GS_SMALL_64x128:
+            if constexpr (gemm_shape_built(GM, EPI, OUT, GS_SMALL_64x128)) return launch_gemm_small_cfg<EPI, OUT, MODE, 4>(g, st, p.flags, p.group_tiles);
+            return hipErrorInvalidValue;
+        case GS_SMALL_64x128_TWO:
+            if constexpr (gemm_shape_built(GM, EPI, OUT, GS_SMALL_64x128_TWO)) return launch_gemm_small_cfg<EPI, OUT, MODE, 4, true>(g, st, p.flags, p.group_tiles);
+            return hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;
     }
-    else {
-        if constexpr (MODE != SM_X3)
-            if (wc == 8) return launch_gemm_small_cfg<EPI, OUT, MODE, 4, true>(g, st);
-        return launch_gemm_small_cfg<EPI, OUT, MODE, 4>(g, st);
-    }
-}
-
-// does the out-projection's OUT_LNX launch also merge the partial outputs of a split-KV attention launch (lnx_combine)?  "small_cmb": 0 on, 2 off
-inline bool small_cmb_fits(int nsplit, int head_dim, int x2) {
-    return tune().small_cmb != 2 && tune().attn_h_variant != 1 && nsplit > 1 && nsplit <= 8 && head_dim == 128 && x2;      // (attn_h_variant 1: the register-staged kernel, which does not split)
-}
-
-
-// does out_proj / linear2 + residual + LayerNorm run as ONE small launch with the statistics exchange (OUT_LNX)?  F16MX at d_model 512,
-// nothing else in flight on the handle (small_now == 1), calls of ONE chunk (one_chunk: whatever the lanes, a call's bits must not
-// depend on its chunk plan), and EVERY workgroup of the launch resident at once - the waiting workgroups need their partners: 8 workgroups per 64-row tile against the
-// device's compute units (Tuning::cus, from hipDeviceProp_t::multiProcessorCount at jmid_create - a partitioned or smaller device
-// takes the unfused pair), one per CU, or two per CU on half the LDS each, and at most SM_LNX_MAX_TILES row tiles (the exchange
-// buffer).  "small_lnx" = 2: off (GEMM + add_ln2, the same bits).
-inline int small_lnx_fits(int M, int K, int small_now, int one_chunk) {       // 0 no; 2: one workgroup per CU; 9: two per CU ("small_lnx2" = 2 off)
-    const long ntm = (M + 63) / 64;
-    if (!(tune().gemm_small != 1 && small_now == 1 && one_chunk == 1 && tune().gemm_h_variant == 0 && tune().small_lnx != 2 && K % 128 == 0)) return 0;
-    if (ntm * 8 <= tune().cus && ntm <= SM_LNX_MAX_TILES) return 2;
-    return ntm * 8 <= 2L * tune().cus && ntm <= SM_LNX_MAX_TILES && tune().small_lnx2 != 2 ? 9 : 0;
 }
 
 template <int EPI, int OUT>
-inline hipError_t launch_gemm_small(const GemmHArgs& g, int wc, hipStream_t st) {
-    if (g.x2 && g.W8) return launch_gemm_small_mode<EPI, OUT, SM_MX>(g, wc, st);
-    if (g.x2) return launch_gemm_small_mode<EPI, OUT, SM_X2>(g, wc, st);
-    return launch_gemm_small_mode<EPI, OUT, SM_X3>(g, wc, st);
+inline hipError_t launch_gemm_small(const GemmHArgs& g, const GemmPlan& p, hipStream_t st) {
+    if (p.mode == GM_MX) return launch_gemm_small_mode<EPI, OUT, SM_MX>(g, p, st);
+    if (p.mode == GM_X2) return launch_gemm_small_mode<EPI, OUT, SM_X2>(g, p, st);
+    return launch_gemm_small_mode<EPI, OUT, SM_X3>(g, p, st);
 }
 
 }  // namespace jmid

@@ -170,7 +170,6 @@ int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* n
     if (!h->finalized) return fail(h, JMID_ENOWEIGHT, "jmid_finalize_weights has not been called");
     if (n_agents <= 0 || !x_st || !nbr_sum || !edge_mask || !ctx_out) return fail(h, JMID_EINVAL, "bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     if (int rc = order_in(h, mem)) return rc;
     const int Th = h->hist_len, H = h->H;
     const size_t n = n_agents;
@@ -228,7 +227,6 @@ int jmid_episode_metrics(jmid_handle_t h, int E, int A, int K, int T, const floa
                          float* out, int mem) {
     if (!h || !pos || !gt || !out || E <= 0 || A <= 0 || K <= 0 || T <= 0) return fail(h, JMID_EINVAL, "bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     if (int rc = order_in(h, mem)) return rc;
     const size_t np_ = (size_t)E * K * A * T * 2, ng = (size_t)E * A * T * 2;
     const float *dp = pos, *dg = gt;
@@ -260,7 +258,6 @@ int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* p
     if (k < 1 || k > K) return fail(h, JMID_EINVAL, "k must be in 1..K");
     if (A > 32 || K > 1024 || T > 24) return fail(h, JMID_EINVAL, "jmid_topk supports A <= 32, K <= 1024, T <= 24");
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     if (!pos) {
         if (!h->last_pos || h->last_pos_dims[0] != E || h->last_pos_dims[1] != A || h->last_pos_dims[2] != K || h->last_pos_dims[3] != T)
             return fail(h, JMID_EINVAL, "pos = NULL needs a preceding jmid_denoise with p0 and the same E, A, K, T on this handle");
@@ -365,7 +362,6 @@ int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float
     int rc = 0;
     h->chained = true;
     {
-        TuneScope tune_scope(&h->tune);
         ProfScope ps(h, KC_ENCODER);
         EncArgs ea{};
         ea.x_st = dev + o_xs; ea.nbr_sum = dev + o_nb; ea.edge_mask = dev + o_em;
@@ -378,10 +374,7 @@ int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float
     }
     if (!rc) rc = run_network(h, E, A, K, T, dev + o_xT, dev + o_ctx, dev + o_p0, dt, precision, -1, nullptr, pos_out ? dev + o_pos : nullptr,
                               nullptr, JMID_MEM_DEVICE);
-    if (!rc && rank) {
-        TuneScope tune_scope(&h->tune);
-        rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw);
-    }
+    if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw);
     h->chained = false;
     if (rc) return rc;
     const bool flagged = precision != JMID_PREC_F32;

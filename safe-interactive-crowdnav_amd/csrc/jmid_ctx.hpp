@@ -29,6 +29,7 @@
 #include "gemm_small.hpp"
 #include "gemm_f32.hpp"
 #include "kde.hpp"
+#include "launch_plan.hpp"
 
 using namespace jmid;
 
@@ -99,7 +100,7 @@ struct jmid_ctx {
     // attention workgroups of the other lane computed a few wrong values per run - packed-fp32 instructions with crossed
     // operand selects, which the library is no longer built with; build.py, docs/NOTEBOOK.md section 3.)
     int lanes = 2;
-    Tuning tune;         // jmid_set_tuning knobs of THIS handle (installed per call by TuneScope; `cus` is set by jmid_create)
+    Tuning tune;         // jmid_set_tuning knobs of THIS handle (read as h->tune; `cus` is set by jmid_create)
     hipStream_t caller_stream = nullptr;   // stream device-mode buffers are ordered on (jmid_set_caller_stream)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     // captured denoise loops of small calls (one chunk): key = (E, A, K, T, precision) -> executable graph

@@ -13,7 +13,6 @@ int jmid_dbg_plan_chunks(int net_kind, int nhead, int lanes, int chunk_episodes,
     if (E <= 0 || tokens_per_episode <= 0 || nhead <= 0 || !sizes || cap <= 0) return JMID_EINVAL;
     jmid_ctx ctx;                      // host fields only: the planner reads net_kind, nhead, lanes, chunk_eps and the tuning
     ctx.net_kind = net_kind; ctx.nhead = nhead; ctx.lanes = lanes; ctx.chunk_eps = chunk_episodes;
-    TuneScope tune_scope(&ctx.tune);
     const std::vector<int> plan = plan_chunks(&ctx, E, tokens_per_episode);
     for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) sizes[i] = plan[i];
     return (int)plan.size();
@@ -27,10 +26,28 @@ int jmid_dbg_plan_chunks_mode(int net_kind, int nhead, int lanes, int chunk_epis
     ctx.net_kind = net_kind; ctx.nhead = nhead; ctx.lanes = lanes; ctx.chunk_eps = chunk_episodes;
     ctx.mx = precision == JMID_PREC_F16MX;
     ctx.x2 = precision == JMID_PREC_F16X2 || ctx.mx;
-    TuneScope tune_scope(&ctx.tune);
     const std::vector<int> plan = plan_chunks(&ctx, E, tokens_per_episode);
     for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) sizes[i] = plan[i];
     return (int)plan.size();
+}
+
+int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int small_now, int one_chunk, const int* knobs, int* plan) {
+    if (mode < GM_X3 || mode > GM_MX || epi < EPI_BIAS || epi > EPI_CSL || (out != OUT_F32 && out != OUT_SPLIT && out != OUT_QKV && out != OUT_LNX) ||
+        M <= 0 || N <= 0 || K <= 0 || !knobs || !plan || knobs[0] < 0 || knobs[0] > 8)
+        return JMID_EINVAL;
+    Tuning t;
+    int Tuning::*const fields[JMID_DBG_GEMM_PLAN_KNOBS] = {&Tuning::gemm_h_variant, &Tuning::gemm_small, &Tuning::ln_rows, &Tuning::small_lnx, &Tuning::small_lnx2,
+                                                           &Tuning::cus, &Tuning::vt_stage, &Tuning::csl_swap, &Tuning::h1_stage, &Tuning::gemm_pn,
+                                                           &Tuning::small_qk, &Tuning::small_pn, &Tuning::gemm_ng};
+    for (int i = 0; i < JMID_DBG_GEMM_PLAN_KNOBS; ++i) t.*fields[i] = knobs[i];
+    CallFacts cf;
+    cf.small_now = small_now;
+    cf.one_chunk = one_chunk;
+    const GemmPlan p = plan_gemm((GemmMode)mode, epi, out, M, N, K, cf, t);
+    plan[0] = p.mode; plan[1] = p.shape; plan[2] = p.flags; plan[3] = p.group_tiles;
+    plan[4] = gemm_shape_bm(p.shape); plan[5] = gemm_shape_bn(p.shape);
+    plan[6] = plan_ln_rows(false, M, t); plan[7] = plan_ln_rows(true, M, t);
+    return JMID_OK;
 }
 
 int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const float* Wt, const float* bias, int relu,
@@ -41,7 +58,6 @@ int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const fl
     h->mx = precision == JMID_PREC_F16MX;
     h->x2 = precision == JMID_PREC_F16X2 || h->mx;
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     if (!h->range_flag) {
         HIPCHK(h, hipMalloc((void**)&h->range_flag, sizeof(int)));
         HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
@@ -82,7 +98,9 @@ int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const fl
             if (int rc8 = make_w8(h, dW, N, K, &w8img)) return rc8;
             g.W8 = w8img.p;
         }
-        rc = relu ? run_gemm_h<EPI_BIAS_RELU, OUT_F32>(h, KC_GEMM_QKV, g) : run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g);
+        // (an idle handle: nothing else in flight, one launch)
+        const GemmPlan plan = plan_gemm(gemm_mode(h), relu ? EPI_BIAS_RELU : EPI_BIAS, OUT_F32, M, N, K, CallFacts{}, h->tune);
+        rc = relu ? run_gemm_h<EPI_BIAS_RELU, OUT_F32>(h, KC_GEMM_QKV, g, plan) : run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g, plan);
     }
     if (!rc) {
         hipError_t e = hipStreamSynchronize(h->stream);
@@ -104,7 +122,6 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
     h->mx = precision == JMID_PREC_F16MX;
     h->x2 = precision == JMID_PREC_F16X2 || h->mx;
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     if (!h->range_flag) {
         HIPCHK(h, hipMalloc((void**)&h->range_flag, sizeof(int)));
         HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
@@ -120,7 +137,7 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
     if (precision == JMID_PREC_F32) {
         AttnArgs aa{dQ, dO, S, d, h->nhead, 1.0f / sqrtf((float)hd), nullptr, nullptr};
         ProfScope ps(h, KC_ATTN);
-        hipError_t e = launch_attn_f32(aa, nseq, hd, h->stream);
+        hipError_t e = launch_attn_f32(aa, nseq, hd, plan_attn(hd, h->tune).pack, h->stream);
         if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
     } else {
         const int Spad = vt_spad(S);
@@ -147,7 +164,7 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
                      h->range_flag, ns, opart, mlpart, h->x2};
         {
             ProfScope ps(h, KC_ATTN);
-            hipError_t e = launch_attn_f16x3(aa, nseq, hd, h->stream);
+            hipError_t e = launch_attn_f16x3(aa, nseq, hd, plan_attn(hd, h->tune), h->stream);
             if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
         }
         hipLaunchKernelGGL(merge_planes_kernel, dim3(512), dim3(256), 0, h->stream, b[6], b[7], dO, (int)Mt, d);
@@ -169,7 +186,6 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
     if (!h || !A || !Wt || !bias || !gamma || !beta || !X || M <= 0 || K % 64 != 0) return JMID_EINVAL;
     constexpr int N = GLN_BN;
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     h->mx = 1;
     h->x2 = 1;
     if (!h->range_flag) {
@@ -213,18 +229,18 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
     int rc = 0;
     if (fused == 1) {
         GemmLn2Args g2{ah, w16h, img.p, dB, dG, dT, xh, xl8, M, K, 1e-5f, h->range_flag, 0};
-        hipError_t e = launch_gemm_ln2_mx(g2, h->stream);
+        hipError_t e = launch_gemm_ln2_mx(g2, plan_ln_rows(true, M, h->tune), h->stream);
         if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
     } else {
         GemmHArgs g{};
         g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.W8 = img.p; g.bias = dB; g.C = dY; g.ldc = N; g.M = M; g.N = N; g.K = K;
         if (fused == 3) {        // the small-launch kernel with the statistics exchange (gemm_small.hpp, OUT_LNX)
             unsigned long long* xs = (unsigned long long*)dalloc(kLnxWords * sizeof(unsigned), nullptr);
-            const int shape = small_lnx_fits(M, K, 1, 1);      // (an idle handle: nothing else in flight, one launch)
-            if (!xs || !shape) return fail(h, JMID_EINVAL, "jmid_dbg_gemm_ln_mx: shape does not take the small kernel with the statistics exchange");
+            const GemmPlan lnx = plan_gemm(GM_MX, EPI_BIAS, OUT_LNX, M, N, K, CallFacts{}, h->tune);      // (an idle handle: nothing else in flight, one launch)
+            if (!xs || lnx.shape == GS_NONE) return fail(h, JMID_EINVAL, "jmid_dbg_gemm_ln_mx: shape does not take the small kernel with the statistics exchange");
             g.ln_gamma = dG; g.ln_beta = dT; g.ln_xh = xh; g.ln_xl = nullptr; g.ln_xl8 = xl8; g.ln_xchg = xs; g.ln_eps = 1e-5f; g.ln_no_lo = 0;
             (void)hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream);
-            rc = run_gemm_lnx_small(h, KC_GEMM_OUT, g, shape);
+            rc = run_gemm_lnx_small(h, KC_GEMM_OUT, g, lnx);
             if (!rc) {
                 int flag = 0;
                 (void)hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream);
@@ -233,7 +249,7 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
             }
         } else
         {
-        rc = run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_OUT, g);
+        rc = run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_OUT, g, plan_gemm(GM_MX, EPI_BIAS, OUT_F32, M, N, K, CallFacts{}, h->tune));
         if (!rc) rc = run_add_ln(h, nullptr, dY, dG, dT, M, N, xh, reinterpret_cast<half_t*>(xl8), true, 0);
         }
     }
@@ -251,7 +267,6 @@ int jmid_dbg_add_layernorm(jmid_handle_t h, int M, int d, float* X, const float*
                            const float* beta) {
     if (!h || !X || !Y || !gamma || !beta) return JMID_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     float *dX, *dY, *dG, *dB;
     HIPCHK(h, hipMalloc((void**)&dX, (size_t)M * d * 4));
     HIPCHK(h, hipMalloc((void**)&dY, (size_t)M * d * 4));

@@ -100,20 +100,9 @@ size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom
     return c.off;
 }
 
-// What a call knows before its first launch and no chunk of it changes (run_network).  Facts, not knobs: jmid_set_tuning has no say.
-struct CallFacts {
-    // the small-launch GEMMs (gemm_small.hpp: one workgroup per CU, most of its LDS): 1 = one chunk in flight, 0 = several (their
-    // launches would collide), 2 = experiment "small_lanes" = 2: only the two-workgroups-per-CU shape
-    int small_now = 1;
-    // the call is ONE chunk, run eagerly (OUT_LNX of gemm_small.hpp only then, whatever the lanes: a call's bits do not depend on
-    // its chunk plan; a captured loop would replay that kernel's launch tags)
-    int one_chunk = 1;
-    int attn_nsplit = 1;      // split-KV factor of the attention launches: per call, never per chunk (run_network)
-};
-
 // JMID_PREC_F16MX at d_model 512: second-generation LayerNorm kernels (gemm_ln2_mx.hpp) - the lo plane of the residual stream
 // is a byte plane (it lives in the memory of the fp16 one), the row statistics are summed in that file's order
-bool byte_lo_plane(const jmid_ctx* h) { return h->mx && h->d == GLN_BN && tune().mx_ln != 2; }
+bool byte_lo_plane(const jmid_ctx* h) { return h->mx && h->d == GLN_BN && h->tune.mx_ln != 2; }
 
 // A residual block of a layer in the split-fp16 modes - X <- LayerNorm(X + A . W^T + bias): out_proj + norm1 (K = d_model) and
 // linear2 + norm2 (K = d_ff) - runs in one of four ways.  All four give bit-identical rows.
@@ -125,7 +114,8 @@ enum ResidualPath {
 };
 struct ResidualPlan {
     ResidualPath path;
-    int lnx_shape;      // RB_LNX_SMALL: 2 = one workgroup per CU, 9 = two
+    int ln_rows;        // RB_GEMM_LN2 / RB_GEMM_LN: the row tile (launch_plan.hpp::plan_ln_rows)
+    GemmPlan gemm;      // RB_LNX_SMALL / RB_GEMM_ADD_LN: the GEMM launch
     bool merge;         // RB_LNX_SMALL of out_proj: the split-KV merge of the attention launch rides in front of its K loop (plan_step)
 };
 
@@ -134,13 +124,17 @@ ResidualPlan residual_path(const jmid_ctx* h, int M, int K, const CallFacts& cf)
     // row-complete GEMM with residual + LayerNorm fused in from 7168 tokens (6 episodes
     // per launch: 36.8 vs 39.1 ms per 12-episode call; 5: 33.8 vs 33.5, 4: 29.6 vs 28.8)
     // (enough row tiles to occupy the chip); otherwise GEMM -> fp32 Y -> add_ln
-    if (h->d == GLN_BN && tune().ln_fuse != 2 && (tune().ln_fuse == 1 || M >= 7168))
-        return {byte_lo_plane(h) ? RB_GEMM_LN2 : RB_GEMM_LN, 0, false};
+    const Tuning& t = h->tune;
+    if (h->d == GLN_BN && t.ln_fuse != 2 && (t.ln_fuse == 1 || M >= 7168))
+        return {byte_lo_plane(h) ? RB_GEMM_LN2 : RB_GEMM_LN, plan_ln_rows(byte_lo_plane(h), M, t), {}, false};
     // one scene in F16MX (one chunk of <= 2048 rows, or two scenes' worth with two workgroups per CU; byte lo plane): GEMM + residual +
     // LayerNorm in ONE small launch (two launches per layer fewer); a handle on which such a kernel ever gave up waiting (lnx_off)
     // stays on the pair
-    const int shape = byte_lo_plane(h) && !h->lnx_off ? small_lnx_fits(M, K, cf.small_now, cf.one_chunk) : 0;
-    return {shape ? RB_LNX_SMALL : RB_GEMM_ADD_LN, shape, false};
+    if (byte_lo_plane(h) && !h->lnx_off) {
+        const GemmPlan lnx = plan_gemm(GM_MX, EPI_BIAS, OUT_LNX, M, h->d, K, cf, t);
+        if (lnx.shape != GS_NONE) return {RB_LNX_SMALL, 0, lnx, false};
+    }
+    return {RB_GEMM_ADD_LN, 0, plan_gemm(gemm_mode(h), EPI_BIAS, OUT_F32, M, h->d, K, cf, t), false};
 }
 
 // Is a batch of `tokens` tokens ONE launch by default (plan_chunks keeps it one chunk)?  Shape and mode only.  There are two
@@ -159,8 +153,10 @@ struct StepPlan {
     float att_scale;
     bool vt_direct;              // the QKV epilogue writes V^T itself; otherwise V row-major + v_transpose_kernel
     bool k8, q8l;                // bf8 images of K_hi / K_lo, and of Q_lo, written by the QKV epilogue for the attention kernel
-    CallFacts cf;                // (small_now: for the launches that pick their own tile shape, small_gemm_shape; the split-KV factor)
+    CallFacts cf;                // (the split-KV factor)
+    GemmPlan in_proj, linear1, concat3, concat4;      // the GEMM launches of a step in the split-fp16 modes (launch_plan.hpp)
     ResidualPlan out_proj, linear2;
+    AttnPlan attn;
     int out_tpw;                 // output kernel: tokens per wave of the per-trajectory form, 0 = one wave per token
 };
 
@@ -178,30 +174,36 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision
     p.hd = d / h->nhead;
     p.att_scale = 1.0f / sqrtf((float)p.hd);
     p.cf = cf;
+    const Tuning& t = h->tune;
+    p.attn = plan_attn(p.hd, t);
     if (p.split) {
+        const auto gemm = [&](int epi, int out, int N, int K) { return plan_gemm(gemm_mode(h), epi, out, p.M, N, K, cf, t); };
+        p.in_proj = gemm(EPI_BIAS, p.joint ? OUT_QKV : OUT_F32, 3 * d, d);
+        p.linear1 = gemm(EPI_BIAS_RELU, OUT_SPLIT, h->ff, d);
+        p.concat3 = gemm(EPI_CSL, OUT_SPLIT, h->dmid, d);
+        p.concat4 = gemm(EPI_CSL, OUT_F32, h->dlow, h->dmid);
         p.out_proj = residual_path(h, p.M, d, cf);
         p.linear2 = residual_path(h, p.M, h->ff, cf);
     }
     if (p.split && p.joint) {
         // S % 4 == 0: the QKV epilogue writes V^T itself; otherwise V row-major + v_transpose_kernel
-        p.vt_direct = (p.sg.S % 4 == 0) && !tune().no_vt_direct;
+        p.vt_direct = (p.sg.S % 4 == 0) && !t.no_vt_direct;
         // JMID_PREC_F16MX, head_dim 128 (the LDS-DMA attention kernel): bf8 images of K_hi / K_lo in the K_lo plane's memory, for
         // the logits' correction terms as bf8 MFMAs (attention 7 % faster; "attn_mx" = 2: fp16 terms as in F16X2)
-        // (the register-staged GEMM variants a knob can force are F16X2's kernels: no image stores)
-        p.k8 = h->mx && p.hd == 128 && tune().attn_h_variant == 0 && tune().attn_mx != 2 && tune().gemm_h_variant != 1 &&
-               tune().gemm_h_variant != 2;
-        p.q8l = p.k8 && tune().attn_mx != 3;      // 3: Q_lo as fp16 (A/B)
+        // (in_proj planned for F16X2's kernels - the register-staged variants a knob can force -: no image stores)
+        p.k8 = p.in_proj.mode == GM_MX && p.hd == 128 && t.attn_h_variant == 0 && t.attn_mx != 2;
+        p.q8l = p.k8 && t.attn_mx != 3;      // 3: Q_lo as fp16 (A/B)
         // one scene: the partial outputs of a split-KV attention launch are merged in front of the out-projection's K loop
         // (gemm_small.hpp, lnx_combine) when that launch is the one with the LayerNorm inside
-        p.out_proj.merge = p.out_proj.path == RB_LNX_SMALL && small_cmb_fits(p.cf.attn_nsplit, p.hd, h->x2);
+        p.out_proj.merge = p.out_proj.path == RB_LNX_SMALL && small_cmb_fits(p.attn, p.cf.attn_nsplit, h->x2, t);
     }
-    if (d <= 512 && p.M % T == 0 && tune().out_traj != 2 && (tune().out_traj == 1 || p.M >= 4096 * 4)) {
+    if (d <= 512 && p.M % T == 0 && t.out_traj != 2 && (t.out_traj == 1 || p.M >= 4096 * 4)) {
         // one wave per trajectory (T tokens) - or per piece of one, the largest divisor of T that still leaves >= 4096 waves -
         // once there are enough tokens to fill the chip that way: one scene (100 trajectories) takes 14.0 instead of
         // 12.7 ms per call with whole trajectories, a 51-episode chunk 150.3 instead of 151.2
         p.out_tpw = T;
         while (p.out_tpw > 1 && (p.M / p.out_tpw < 4096 || T % p.out_tpw != 0)) --p.out_tpw;
-        if (tune().out_traj == 1) p.out_tpw = T;
+        if (t.out_traj == 1) p.out_tpw = T;
     }
     return p;
 }
@@ -216,7 +218,7 @@ int residual_block(jmid_ctx* h, const StepPlan& p, const ResidualPlan& rp, const
     if (rp.path == RB_GEMM_LN2) {
         GemmLn2Args g2{Ahi, lin.k16.hi, lin.w8, lin.bias, nrm.gamma, nrm.beta, sb.Xh, Xl8, M, K, 1e-5f, h->range_flag, no_lo_out};
         ProfScope ps(h, cls);
-        HIPCHK(h, launch_gemm_ln2_mx(g2, h->stream));
+        HIPCHK(h, launch_gemm_ln2_mx(g2, rp.ln_rows, h->stream));
         return 0;
     }
     if (rp.path == RB_GEMM_LN) {
@@ -224,7 +226,7 @@ int residual_block(jmid_ctx* h, const StepPlan& p, const ResidualPlan& rp, const
         gl.W8 = h->mx ? lin.w8 : nullptr;
         gl.no_lo_out = h->x2 && no_lo_out;
         ProfScope ps(h, cls);
-        HIPCHK(h, launch_gemm_ln(gl, h->stream));
+        HIPCHK(h, launch_gemm_ln(gl, rp.ln_rows, h->stream));
         return 0;
     }
     GemmHArgs g = gemm_h_args(h, p.rm, M, Ahi, Alo, lin, d, K);
@@ -236,9 +238,9 @@ int residual_block(jmid_ctx* h, const StepPlan& p, const ResidualPlan& rp, const
         }
         g.ln_gamma = nrm.gamma; g.ln_beta = nrm.beta; g.ln_xh = sb.Xh; g.ln_xl = nullptr;
         g.ln_xl8 = Xl8; g.ln_xchg = sb.ln_xchg; g.ln_eps = 1e-5f; g.ln_no_lo = no_lo_out;
-        return run_gemm_lnx_small(h, cls, g, rp.lnx_shape);
+        return run_gemm_lnx_small(h, cls, g, rp.gemm);
     }
-    if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, cls, g, p.cf.small_now))) return rc;
+    if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, cls, g, rp.gemm))) return rc;
     return run_add_ln(h, sb.X, sb.Y, nrm.gamma, nrm.beta, M, d, sb.Xh, sb.Xl, p.mxv2, no_lo_out);
 }
 
@@ -263,7 +265,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
         EmbedArgs ea = embed_args(thyp);
         const long total = (long)M * (d / 4);
         int blocks = (int)std::min<long>((total + 255) / 256, 256L * 16);
-        hipLaunchKernelGGL(embed_kernel, dim3(blocks), dim3(256), bystander_lds(embed_kernel), h->stream, ea);
+        hipLaunchKernelGGL(embed_kernel, dim3(blocks), dim3(256), bystander_lds(h->tune.bystander_lds, embed_kernel), h->stream, ea);
         HIPCHK(h, hipGetLastError());
     }
     const SeqGeom& sg = p.sg;
@@ -274,7 +276,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
             {
                 ProfScope ps(h, KC_ATTN);
                 AttnArgs aa{sb.QKV, sb.ATT, S, d, h->nhead, p.att_scale, nullptr, nullptr};
-                HIPCHK(h, launch_attn_f32(aa, nseq, hd, h->stream));
+                HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, h->stream));
             }
             // attention output projection + residual + LN1
             if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_OUT, gemm_args(rm, M, sb.ATT, w.out_proj, sb.Y, d, d))) return rc;
@@ -303,7 +305,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
                 unsigned char* k8l = p.k8 ? k8h + (size_t)M * d : nullptr;
                 unsigned char* q8l = p.q8l ? reinterpret_cast<unsigned char*>(sb.Ql) : nullptr;
                 g.K8h = k8h; g.K8l = k8l; g.Q8l = q8l;
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, KC_GEMM_QKV, g, p.cf.small_now))) return rc;
+                if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, KC_GEMM_QKV, g, p.in_proj))) return rc;
                 if (!p.vt_direct) {
                     ProfScope ps(h, KC_VTRANS);
                     hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, nseq), dim3(256), 0, h->stream,
@@ -314,18 +316,18 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
                 AttnHArgs aa{sb.Qh, sb.Ql, sb.Kh, sb.Kl, sb.Vth, sb.Vtl, sb.Ah, sb.Al, S, sg.Spad, d, h->nhead,
                              p.att_scale, h->range_flag, p.cf.attn_nsplit, sb.Opart, sb.MLpart, h->x2, k8h, k8l, q8l};
                 aa.skip_combine = p.out_proj.merge;
-                HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, h->stream));
+                HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, p.attn, h->stream));
             } else {
                 g.C = sb.QKV; g.ldc = 3 * d;
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g, p.cf.small_now))) return rc;
+                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g, p.in_proj))) return rc;
                 ProfScope ps(h, KC_ATTN);
                 AttnArgs aa{sb.QKV, nullptr, S, d, h->nhead, p.att_scale, sb.Ah, sb.Al};
-                HIPCHK(h, launch_attn_f32(aa, nseq, hd, h->stream));
+                HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, h->stream));
             }
             if (int rc = residual_block(h, p, p.out_proj, sb, sb.Ah, sb.Al, d, w.out_proj, w.norm1, KC_GEMM_OUT, false)) return rc;
             g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, w.linear1, ff, d);
             g.Chi = sb.H1h; g.Clo = sb.H1l; g.ldc = ff;
-            if (int rc = (run_gemm_h<EPI_BIAS_RELU, OUT_SPLIT>(h, KC_GEMM_FF1, g, p.cf.small_now))) return rc;
+            if (int rc = (run_gemm_h<EPI_BIAS_RELU, OUT_SPLIT>(h, KC_GEMM_FF1, g, p.linear1))) return rc;
             // (the residual stream ends with the last layer: concat3 reads X_hi only)
             if (int rc = residual_block(h, p, p.linear2, sb, sb.H1h, sb.H1l, ff, w.linear2, w.norm2, KC_GEMM_FF2, l + 1 == h->tf_layer)) return rc;
         }
@@ -334,11 +336,11 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
         GemmHArgs g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, wt.concat3, h->dmid, d);
         g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
         g.Chi = sb.Y3h; g.Clo = sb.Y3l; g.ldc = h->dmid; g.goff = h->hl.g3; g.boff = h->hl.b3;
-        if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, KC_GEMM_TAIL, g, p.cf.small_now))) return rc;
+        if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, KC_GEMM_TAIL, g, p.concat3))) return rc;
         g = gemm_h_args(h, rm, M, sb.Y3h, sb.Y3l, wt.concat4, h->dlow, h->dmid);
         g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
         g.C = sb.Y4; g.ldc = h->dlow; g.goff = h->hl.g4; g.boff = h->hl.b4;
-        if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, KC_GEMM_TAIL, g, p.cf.small_now))) return rc;
+        if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, KC_GEMM_TAIL, g, p.concat4))) return rc;
     }
     {
         ProfScope ps(h, KC_OUT_DDIM);
@@ -357,7 +359,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
         const EmbedArgs en = embed_next ? embed_args(h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
         // four waves per workgroup: one wave per piece of a trajectory (out_tpw tokens), or one per token
         const auto launch = [&](auto* kernel, int waves, auto... tpw) {
-            hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(kernel), h->stream, oa, en, tpw...);
+            hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), h->stream, oa, en, tpw...);
         };
         if (p.out_tpw && embed_next) launch(out_ddim_traj_kernel<true>, M / p.out_tpw, p.out_tpw);
         else if (p.out_tpw) launch(out_ddim_traj_kernel<false>, M / p.out_tpw, p.out_tpw);
@@ -391,7 +393,7 @@ int auto_chunk(const jmid_ctx* h, int E, int tokens_per_episode) {
 // full chunks instead (52 + 4 x 51) - only with the automatic size: a forced size is taken literally.
 std::vector<int> plan_chunks(const jmid_ctx* h, int E, int tokens_per_episode) {
     int c = h->chunk_eps > 0 ? std::min(E, h->chunk_eps) : auto_chunk(h, E, tokens_per_episode);
-    if (h->chunk_eps <= 0 && h->lanes >= 2 && E >= 2 && tune().graph != 1) {     // (a captured loop is a one-chunk call)
+    if (h->chunk_eps <= 0 && h->lanes >= 2 && E >= 2 && h->tune.graph != 1) {     // (a captured loop is a one-chunk call)
         // Two chunks in flight want an EVEN number of chunks of equal size.  A batch that fits one chunk is split in two halves: its
         // kernels do not fill the chip, and two half-size launches side by side finish 5-13 % sooner than one (4 / 8 / 16 / 32 / 48
         // episodes: 23.3 -> 22.2, 36.0 -> 31.8, 60.9 -> 58.0, 111.3 -> 97.2, 140.5 -> 132.5 ms per call; tools/small_batch_lanes.py).
@@ -469,7 +471,6 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     if (single_step < 0 && h->ddpm && !z_in) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
     if (single_step < 0 && !h->ddpm && z_in) return fail(h, JMID_EINVAL, "jmid_denoise_ddpm needs jmid_set_ddpm_table");
     HIPCHK(h, hipSetDevice(h->device));
-    TuneScope tune_scope(&h->tune);
     if (int rc = order_in(h, mem)) return rc;
     const size_t R = (size_t)E * K * A, M = R * T, EA = (size_t)E * A;
     const std::vector<int> chunk_sizes = plan_chunks(h, E, K * A * T);
@@ -490,7 +491,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         //  13.43 ms per call, where the 6 x 80 of the halves' choice take 14.14-14.37; shape and mode only, no knob: the bits of a call
         //  must not depend on one)
         ns_call = attn_pick_nsplit(((S + 127) / 128) * h->nhead * (E >= 2 ? (one_launch_shape(h, (long)E * S) ? E : (c_auto + 1) / 2) : 1), S);
-        if (tune().attn_nsplit > 0) ns_call = std::min(tune().attn_nsplit, (S + 31) / 32);
+        if (h->tune.attn_nsplit > 0) ns_call = std::min(h->tune.attn_nsplit, (S + 31) / 32);
     }
     // ---- workspace
     size_t io_off;
@@ -513,8 +514,8 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     // one plan per distinct chunk size of the call (the knobs and lnx_off cannot change while it runs): net_step only executes it.
     // The small-launch GEMMs (gemm_small.hpp: one workgroup per CU, most of its LDS) only while one chunk is in flight
     CallFacts facts;
-    facts.small_now = lanes == 1 || tune().small_lanes == 1 ? 1 : tune().small_lanes == 2 ? 2 : 0;
-    facts.one_chunk = nchunks == 1 && tune().graph != 1;      // (a captured loop would replay the launch tags of OUT_LNX)
+    facts.small_now = lanes == 1 || h->tune.small_lanes == 1 ? 1 : h->tune.small_lanes == 2 ? 2 : 0;
+    facts.one_chunk = nchunks == 1 && h->tune.graph != 1;      // (a captured loop would replay the launch tags of OUT_LNX)
     facts.attn_nsplit = ns_call;
     std::vector<StepPlan> plans;            // a handful at most
     std::vector<int> chunk_plan;            // chunk -> its plan
@@ -586,8 +587,8 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     // Inputs / outputs (copies, hyper-net GEMM, integrator) stay outside the graph.
     jmid_ctx::LoopGraph* lg = nullptr;
     bool capturing = false;
-    if (single_step < 0 && lanes == 1 && nchunks == 1 && !h->prof_mask && !z_use && !h->ddpm && tune().graph == 1 &&
-        tune().bystander_lds == 0) {
+    if (single_step < 0 && lanes == 1 && nchunks == 1 && !h->prof_mask && !z_use && !h->ddpm && h->tune.graph == 1 &&
+        h->tune.bystander_lds == 0) {
         const std::string key = std::to_string(E) + "," + std::to_string(A) + "," + std::to_string(K) + "," + std::to_string(T) +
                                 "," + std::to_string(precision);
         lg = &h->graphs[key];
@@ -621,8 +622,8 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
                 const float* hc = hyp + (size_t)el * A * h->hl.total;
                 const float* zc = z_use ? z_use + ((size_t)i * M + (size_t)el * K * A * T) * 2 : nullptr;
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);   // net_step launches on h->stream
-                const int rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, tune().fuse_embed && i > 0,
-                                        tune().fuse_embed && i + 1 < n_steps ? i + 1 : -1);
+                const int rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, h->tune.fuse_embed && i > 0,
+                                        h->tune.fuse_embed && i + 1 < n_steps ? i + 1 : -1);
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);
                 if (rc) {
                     if (capturing) {

@@ -250,13 +250,10 @@ inline hipError_t launch_kde(const KdeArgs& g0, hipStream_t st) {
     g.y_in_lds = kde_y_in_lds(g.A, g.K);
     g.p_in_lds = kde_lds_bytes(d, g.K, g.y_in_lds != 0, true) <= 150 * 1024;
     const size_t lds = kde_lds_bytes(d, g.K, g.y_in_lds != 0, g.p_in_lds != 0);
-    static DevSeen seen;
-    if (auto once_ = first_use_on_device(seen))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&kde_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(kde_step_kernel, dim3(g.E * g.T), dim3(KDE_THREADS), lds, st, g);
+    const hipError_t e = launch_with_lds<&kde_step_kernel, 160 * 1024>(dim3(g.E * g.T), dim3(KDE_THREADS), lds, st, g);
     const size_t lds2 = sizeof(double) * (g.K + KDE_THREADS) + sizeof(int) * g.k;
     hipLaunchKernelGGL(kde_select_kernel, dim3(g.E), dim3(KDE_THREADS), lds2, st, g);
-    return hipGetLastError();
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 }  // namespace jmid

@@ -256,6 +256,138 @@ def test_chunk_plan_never_holds_an_empty_chunk():
         assert plan(E, 1200) == plan_mode(E, 1200, _lib.PREC_F16X3)
 
 
+# ---- the launch plan of a split-fp16 GEMM (csrc/launch_plan.hpp::plan_gemm through jmid_dbg_gemm_plan; host logic only) ----
+GEMM_PLAN_TABLE = os.path.join(GOLDEN, "gemm_plan_table.txt")
+GEMM_PLAN_KNOBS = ("gemm_h_variant", "gemm_small", "ln_rows", "small_lnx", "small_lnx2", "cus", "vt_stage", "csl_swap", "h1_stage", "gemm_pn",
+                   "small_qk", "small_pn", "gemm_ng")
+GEMM_PLAN_DEFAULTS = {**dict.fromkeys(GEMM_PLAN_KNOBS, 0), "cus": 256}
+EPI_BIAS, EPI_BIAS_RELU, EPI_CSL = 0, 1, 2
+OUT_F32, OUT_SPLIT, OUT_QKV, OUT_LNX = 0, 1, 2, 4
+GS_NONE, GS_SMALL_64x64, GS_SMALL_64x128, GS_SMALL_64x128_TWO, GS_SMALL_64x64_TWO, GS_64, GS_128, GS_256x128, GS_256x256, GS_128x256, \
+    GS_256x256_NS3, GS_REG_64, GS_REG_128 = range(13)
+GS_SMALL = (GS_SMALL_64x64, GS_SMALL_64x128, GS_SMALL_64x128_TWO, GS_SMALL_64x64_TWO)
+
+
+def gemm_plan_grid():
+    """(mode, epi, out, N, K, small_now, one_chunk, knobs) x the token counts: modes x3 / x2 / mx; the (epilogue, output) pairs of the
+    net, each on the layers that use it, at d_model 512 and at width 32 (d_ff = 2 d, d_mid = d / 2, d_low = d / 4); the default knobs
+    and every forced gemm_h_variant, gemm_small, ln_rows; small_now 0 / 1 / 2.  Token counts from 64 to 262 144, with the points around
+    every threshold of the rules, for every N of the net: 256 and 512 small tiles of 64 x 64 / 64 x 128 (N = 1536: 640, 1344, 2688
+    rows; 1024: 1024, 2048, 4096; 512: 2048; 256: 4096, 8192, 16384; 128: 8192, 16384, 32768), 256 tiles of 128 x 128 (2688, 3968, 8064,
+    16256, 32640), of 256 x 128 (5376, 7936, 16128, 32512, 65280) and of 256 x 256 (10752, 16128), the 7168 / 12288 rows of the 256 x 256
+    rule, 2048 / 2560 / 4096 tokens (32, 40 and 64 row tiles of the one-launch GEMM + LayerNorm)."""
+    Ms = {64, 100, 1200, 2400, 3600, 4800, 100000, 131072, 262144}
+    for base in (640, 1024, 1344, 2048, 2560, 2688, 3968, 4096, 5376, 7168, 7936, 8064, 8192, 10752, 12288, 16128, 16256, 16384, 32512, 32640,
+                 32768, 65280, 65536):
+        Ms |= {base - 64, base - 1, base, base + 1, base + 64}
+    Ms = sorted(Ms)
+    cases = []
+    for d in (512, 32):
+        layers = [(EPI_BIAS, OUT_QKV, 3 * d, d), (EPI_BIAS, OUT_F32, 3 * d, d), (EPI_BIAS, OUT_F32, d, d), (EPI_BIAS, OUT_F32, d, 2 * d),
+                  (EPI_BIAS_RELU, OUT_SPLIT, 2 * d, d), (EPI_CSL, OUT_SPLIT, d // 2, d), (EPI_CSL, OUT_F32, d // 4, d // 2)]
+        if d == 512:
+            layers += [(EPI_BIAS, OUT_LNX, d, d), (EPI_BIAS, OUT_LNX, d, 2 * d)]
+        knob_sets = [{}] + [{"gemm_h_variant": v} for v in range(1, 9)] + [{"gemm_small": v} for v in (1, 2)] + [{"ln_rows": v} for v in (64, 128)]
+        for mode in (0, 1, 2):
+            for epi, out, N, K in layers:
+                if out == OUT_LNX and mode != 2:        # (asked for in F16MX only: residual_path)
+                    continue
+                for small_now in (0, 1, 2):
+                    for one_chunk in ((0, 1) if out == OUT_LNX else (1,)):
+                        for ks in knob_sets:
+                            cases.append((mode, epi, out, N, K, small_now, one_chunk, GEMM_PLAN_DEFAULTS | ks))
+    return Ms, cases
+
+
+def gemm_plan_rows(lib):
+    """The plans of the whole grid as the lines of the table.  A plan row is one cell 'shape family . flags . group_tiles'
+    (hexadecimal) per token count, equal neighbours folded as cell*count; every distinct row is written once, followed by the
+    cases that have it: 'mode epi out N K | ... : small_now.one_chunk:forced knobs ...' (v = gemm_h_variant, s = gemm_small, r = ln_rows,
+    - = defaults, * = all thirteen knob sets).  The row tiles of the two GEMM + LayerNorm generations depend on the token count and
+    "ln_rows" only: three rows of their own."""
+    import ctypes as C
+    Ms, cases = gemm_plan_grid()
+    out8 = (C.c_int * 8)()
+
+    def fold(cells):
+        runs = []
+        for c in cells:
+            if runs and runs[-1][0] == c:
+                runs[-1][1] += 1
+            else:
+                runs.append([c, 1])
+        return " ".join(f"{c}*{n}" for c, n in runs)
+
+    short = {"gemm_h_variant": "v", "gemm_small": "s", "ln_rows": "r"}
+    plans, groups, ln_rows, knob_codes = [], {}, {}, []
+    for mode, epi, out, N, K, small_now, one_chunk, knobs in cases:
+        kv = (C.c_int * len(GEMM_PLAN_KNOBS))(*[knobs[k] for k in GEMM_PLAN_KNOBS])
+        cells = []
+        for M in Ms:
+            assert lib.jmid_dbg_gemm_plan(mode, epi, out, M, N, K, small_now, one_chunk, kv, out8) == 0
+            family, shape, flags, gt, bm, bn, rows1, rows2 = out8[:8]
+            plans.append(((mode, epi, out, M, N, K, small_now, one_chunk, knobs), (family, shape, flags, gt, bm, bn)))
+            fam = family if shape != GS_NONE else "-"        # (no launch, no kernel family)
+            cells.append(f"{shape:x}{fam}.{flags:x}.{gt:x}")
+            assert ln_rows.setdefault((knobs["ln_rows"], M), (rows1, rows2)) == (rows1, rows2)
+        code = "".join(f"{short[k]}{v}" for k, v in knobs.items() if v != GEMM_PLAN_DEFAULTS[k]) or "-"
+        if code not in knob_codes:
+            knob_codes.append(code)
+        groups.setdefault(fold(cells), {}).setdefault((mode, epi, out, N, K), {}).setdefault((small_now, one_chunk), []).append(code)
+    lines = ["# M: " + " ".join(str(m) for m in Ms)]
+    for r in (0, 64, 128):
+        lines.append(f"ln_rows={r} : " + fold([f"{ln_rows[(r, M)][0] // 64}{ln_rows[(r, M)][1] // 64}" for M in Ms]))
+    for row, layers in groups.items():
+        lines.append("row " + row)
+        by_facts = {}
+        for layer, facts in layers.items():
+            text = " ".join(f"{s}.{c}:" + ("*" if codes == knob_codes else ",".join(codes)) for (s, c), codes in facts.items())
+            by_facts.setdefault(text, []).append(" ".join(map(str, layer)))
+        for text, same in by_facts.items():
+            lines.append("  " + " | ".join(same) + " : " + text)
+    return lines, plans
+
+
+def test_gemm_launch_plans_are_the_ones_the_launchers_used_to_pick():
+    """csrc/launch_plan.hpp::plan_gemm reproduces, on the whole grid, what the per-launch rules it replaced decided (tests/golden/
+    gemm_plan_table.txt: dumped from those rules, cut unchanged out of the launchers into functions that return the shape, before
+    they were unified) - and never returns a shape that is not built for the mode and epilogue, or a small shape whose tiles do not
+    fit the chip."""
+    import __graft_entry__ as graft
+    from safe_interactive_crowdnav_amd import _lib
+    from safe_interactive_crowdnav_amd.build import LIB_DIAG
+    graft.build()
+    lines, plans = gemm_plan_rows(_lib.load_library(LIB_DIAG))
+    want = open(GEMM_PLAN_TABLE).read().splitlines()
+    assert len(lines) == len(want) > 50 and len(plans) > 200000
+    for got, exp in zip(lines, want):
+        assert got == exp
+    seen = set()
+    for (mode, epi, out, M, N, K, small_now, one_chunk, knobs), (family, shape, flags, gt, bm, bn) in plans:
+        seen.add(shape)
+        tiles = -(-M // bm) * -(-N // bn)
+        assert family in (0, 1, 2) and (family == mode or (mode == 2 and family == 1))
+        if family == 2:
+            assert K % 64 == 0 and N % 128 == 0 and shape not in (GS_REG_64, GS_REG_128)
+        else:
+            assert shape not in (GS_128x256, GS_256x256_NS3)
+        assert (shape == GS_NONE) <= (out == OUT_LNX)
+        if out == OUT_LNX:
+            assert shape in (GS_NONE, GS_SMALL_64x64, GS_SMALL_64x64_TWO)
+        if epi == EPI_CSL:
+            assert shape not in (GS_256x256, GS_128x256, GS_256x256_NS3) and not (family == 2 and out == OUT_F32 and shape == GS_256x128)
+        if shape in (GS_256x256, GS_128x256, GS_256x256_NS3):
+            assert N % 256 == 0
+        if shape in GS_SMALL:
+            assert small_now and knobs["gemm_small"] != 1 and knobs["gemm_h_variant"] == 0 and K % 128 == 0 and N % bn == 0 and bm == 64
+            two = shape in (GS_SMALL_64x128_TWO, GS_SMALL_64x64_TWO)
+            assert tiles <= (512 if two else 256) and (not two or family != 0)      # one workgroup per CU, or two (not F16X3)
+            assert gt >= 1 and (N // bn) % gt == 0
+            if out == OUT_LNX:
+                assert small_now == 1 and one_chunk == 1 and family == 2 and -(-M // 64) <= 64
+    assert seen == set(range(13))        # every shape of the enum is reached on the grid
+
+
 def test_module_level_get_most_likely_samples_has_the_reference_signature():
     """mid_sim_wrapper.get_most_likely_samples(forecasts, mid_model, num_ret_samples) -> torch tensors [A, k, H, 2], [A, k]."""
     from safe_interactive_crowdnav_amd.forecaster import get_most_likely_samples, topk_fits_device

@@ -79,11 +79,11 @@ int main(int argc, char** argv) {
                     dK8h, dK8l, dQ8};
         if (mode >= 1) { a.Qlo = dQl; a.Klo = dKl; a.K8h = a.K8l = a.Q8l = nullptr; }
         if (mode == 2) { a.Vtlo = dVl; a.Olo = dOl[v]; a.x2 = 0; }
-        TuneScope ts(&tn[v]);
-        CK(launch_attn_f16x3(a, nseq, hd, st));
+        const AttnPlan plan = plan_attn(hd, tn[v]);
+        CK(launch_attn_f16x3(a, nseq, hd, plan, st));
         CK(hipStreamSynchronize(st));
         CK(hipEventRecord(e0, st));
-        for (int r = 0; r < reps; ++r) CK(launch_attn_f16x3(a, nseq, hd, st));
+        for (int r = 0; r < reps; ++r) CK(launch_attn_f16x3(a, nseq, hd, plan, st));
         CK(hipEventRecord(e1, st));
         CK(hipStreamSynchronize(st));
         float ms = 0;

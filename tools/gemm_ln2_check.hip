@@ -47,11 +47,11 @@ int main(int argc, char** argv) {
     for (int round = 0; round < 3; ++round)
         for (size_t v = 0; v < nv; ++v) {
             Tuning tn; tn.ln_rows = variants[v];
-            TuneScope ts(&tn);
+            const int rows = plan_ln_rows(true, M, tn);
             GemmLn2Args g{dA, dW, dW8, db, dg, dt, dXh[v], dXl[v], M, K, 1e-5f, flag, 0};
             // the result of ONE application to the pristine residual planes (kept for the comparison) ...
             CK(hipMemcpyAsync(dXh[v], dXh0, Xh.size() * 2, hipMemcpyDeviceToDevice, st)); CK(hipMemcpyAsync(dXl[v], dXl0, Xl.size(), hipMemcpyDeviceToDevice, st));
-            CK(launch_gemm_ln2_mx(g, st));
+            CK(launch_gemm_ln2_mx(g, rows, st));
             CK(hipStreamSynchronize(st));
             if (round == 0) {
                 rh[v].resize(Xh.size()); rl[v].resize(Xl.size());
@@ -59,7 +59,7 @@ int main(int argc, char** argv) {
             }
             // ... then the timing (the planes are rewritten in place: LayerNorm output stays O(1), the time does not depend on the values)
             CK(hipEventRecord(e0, st));
-            for (int r = 0; r < reps; ++r) CK(launch_gemm_ln2_mx(g, st));
+            for (int r = 0; r < reps; ++r) CK(launch_gemm_ln2_mx(g, rows, st));
             CK(hipEventRecord(e1, st));
             CK(hipStreamSynchronize(st));
             float ms = 0; CK(hipEventElapsedTime(&ms, e0, e1));
