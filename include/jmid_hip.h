@@ -172,6 +172,31 @@ int jmid_net_eval(jmid_handle_t h, int E, int A, int K, int T, int step_idx, con
 int jmid_episode_metrics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt,
                          float* out, int mem);
 
+/* The statistics the reference's evaluation reports per agent and per scene, for a batch of episodes:
+ * compute_batch_statistics (MID/evaluation/evaluation.py:456-739, the branch without is_eval_hst; summarised at MID/mid.py:965-1003
+ * and logged as "Best Of 20: ADE / FDE / KDE", "SADE / SFDE").
+ *   pos        [E, K, A, T, 2]  sampled futures (jmid_denoise's pos_out layout), or NULL: the positions of the most recent
+ *                               jmid_denoise on this handle, under exactly the rules of jmid_topk's pos = NULL below
+ *   gt         [E, A, T, 2]     ground-truth futures
+ *   agent_out  [E, A, 10] = {ade_min, ade_mean, ade_std, ade_ml, fde_min, fde_mean, fde_std, fde_ml, kde_nll, ml_idx}
+ *                - ade[s] = mean_t ||pos - gt||, fde[s] = the last step's distance (compute_ade / compute_fde, :11-36); min, mean and
+ *                  np.std (population) over the K samples (:590-602)
+ *                - kde_nll (compute_kde_nll, :191-232): per horizon step a 2-D scipy.stats.gaussian_kde of the K points with its defaults
+ *                  (covariance with divisor K - 1, Scott's factor K^(-1/6)), its log-pdf at the ground truth clipped below at -20,
+ *                  averaged over the steps, negated
+ *                - ml_idx (get_most_likely_trajectory_idx -> _calc_kde_nll_for_each_traj, :259-285, 445-453): the sample with the highest
+ *                  step-mean clipped log-pdf under the same KDEs (the lowest index on an exact tie), stored as a float;
+ *                  ade_ml / fde_ml are that sample's ade / fde (:573-582)
+ *                - a step whose covariance has no Cholesky factor (scipy raises LinAlgError, which compute_kde_nll turns into nan,
+ *                  :229-230; e.g. K identical samples): kde_nll = NaN, ml_idx = -1, ade_ml = fde_ml = NaN, the other columns as usual
+ *   scene_out  [E, 6] = {sade_min, sade_mean, sade_std, sfde_min, sfde_mean, sfde_std}, sade[s] = mean_a ade[s, a], sfde[s] =
+ *                mean_a fde[s, a] (:717-737); may be NULL
+ * fp64 inside on the fp32 inputs, so the outputs are the fp32 roundings of the reference's float64 values; every reduction runs in
+ * a fixed order without atomics: an episode's rows are bit-identical whatever batch it is part of and in both memory modes.
+ * 2 <= K <= 1024, T <= 24, any A (JMID_EINVAL beyond).  jmid_episode_metrics above is unchanged by this entry point. */
+int jmid_eval_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt, float* agent_out,
+                         float* scene_out, int mem);
+
 /* Joint-KDE ranking of the K sampled futures of every episode and selection of the k most likely ones:
  * get_most_likely_samples (sicnav_diffusion/JMID/mid_sim_wrapper.py:14-169, the joint branch :20-21 the predictor always takes;
  * called from predict_ret_best when num_ret_samples < K, :487-492), which the reference runs on its GPU when it has one (:26-30).

@@ -14,22 +14,37 @@ int fail(jmid_ctx* h, int code, const std::string& msg) {
     return code;
 }
 
+// the handle's second workspace (jmid_topk, jmid_eval_statistics: it must not move the arena last_pos points into), grown on demand
+int ensure_kde_ws(jmid_ctx* h, size_t need, const char* who) {
+    if (need <= h->kde_ws_bytes) return 0;
+    if (h->kde_ws) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipFree(h->kde_ws));
+        h->kde_ws = nullptr;
+        h->kde_ws_bytes = 0;
+    }
+    if (hipMalloc((void**)&h->kde_ws, need) != hipSuccess) return fail(h, JMID_ENOMEM, std::string(who) + " workspace allocation failed");
+    h->kde_ws_bytes = need;
+    return 0;
+}
+
+// pos = NULL of jmid_topk / jmid_eval_statistics: the positions the most recent jmid_denoise left in the workspace, or null (with the
+// error set) when there are none of this shape - the rules include/jmid_hip.h documents at jmid_topk
+const float* resident_positions(jmid_ctx* h, int E, int A, int K, int T) {
+    if (!h->last_pos || h->last_pos_dims[0] != E || h->last_pos_dims[1] != A || h->last_pos_dims[2] != K || h->last_pos_dims[3] != T) {
+        fail(h, JMID_EINVAL, "pos = NULL needs a preceding jmid_denoise with p0 and the same E, A, K, T on this handle");
+        return nullptr;
+    }
+    return h->last_pos;
+}
+
 // the two KDE launches on device buffers (pos [E, K, A, T, 2], bw [T] or null -> sel, logw); the ll / Y workspace is the handle's
 int topk_on_device(jmid_ctx* h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw) {
     const int d = 2 * A;
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t y_bytes = kde_y_in_lds(A, K) ? 0 : up((size_t)E * T * K * d * 8);
     const size_t o_Y = up((size_t)E * T * K * 8), need = o_Y + y_bytes;
-    if (need > h->kde_ws_bytes) {
-        if (h->kde_ws) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            HIPCHK(h, hipFree(h->kde_ws));
-            h->kde_ws = nullptr;
-            h->kde_ws_bytes = 0;
-        }
-        if (hipMalloc((void**)&h->kde_ws, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_topk workspace allocation failed");
-        h->kde_ws_bytes = need;
-    }
+    if (int rc = ensure_kde_ws(h, need, "jmid_topk")) return rc;
     KdeArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T; g.k = k;
     g.ll = reinterpret_cast<double*>(h->kde_ws);
@@ -252,16 +267,55 @@ int jmid_episode_metrics(jmid_handle_t h, int E, int A, int K, int T, const floa
     return order_out(h, mem);
 }
 
+int jmid_eval_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt, float* agent_out,
+                         float* scene_out, int mem) {
+    if (!h || !gt || !agent_out || E <= 0 || A <= 0 || T <= 0) return fail(h, JMID_EINVAL, "bad argument");
+    if (K < 2 || K > 1024 || T > 24) return fail(h, JMID_EINVAL, "jmid_eval_statistics supports 2 <= K <= 1024, T <= 24");
+    if ((size_t)E * A > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, "jmid_eval_statistics: E * A exceeds the launch grid");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
+    if (int rc = order_in(h, mem)) return rc;
+    const size_t n_pos = (size_t)E * K * A * T * 2, n_gt = (size_t)E * A * T * 2, n_ag = (size_t)E * A * EVS_AGENT_COLS,
+                 n_sc = scene_out ? (size_t)E * EVS_SCENE_COLS : 0;
+    EvalStatsArgs g{};
+    g.E = E; g.A = A; g.K = K; g.T = T;
+    g.pos = pos ? pos : h->last_pos;
+    g.gt = gt; g.agent_out = agent_out; g.scene_out = scene_out;
+    if (mem == JMID_MEM_HOST) {
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        const size_t o_gt = 0, o_ag = o_gt + up(n_gt * 4), o_sc = o_ag + up(n_ag * 4), o_pos = o_sc + up(n_sc * 4),
+                     need = o_pos + (pos ? up(n_pos * 4) : 0);
+        if (int rc = ensure_kde_ws(h, need, "jmid_eval_statistics")) return rc;
+        float* dg = reinterpret_cast<float*>(h->kde_ws + o_gt);
+        HIPCHK(h, hipMemcpyAsync(dg, gt, n_gt * 4, hipMemcpyHostToDevice, h->stream));
+        g.gt = dg;
+        if (pos) {
+            float* dp = reinterpret_cast<float*>(h->kde_ws + o_pos);
+            HIPCHK(h, hipMemcpyAsync(dp, pos, n_pos * 4, hipMemcpyHostToDevice, h->stream));
+            g.pos = dp;
+        }
+        g.agent_out = reinterpret_cast<float*>(h->kde_ws + o_ag);
+        if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
+    }
+    {
+        ProfScope ps(h, KC_EVAL_STATS);
+        HIPCHK(h, launch_eval_stats(g, h->stream));
+    }
+    if (mem == JMID_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(agent_out, g.agent_out, n_ag * 4, hipMemcpyDeviceToHost, h->stream));
+        if (scene_out) HIPCHK(h, hipMemcpyAsync(scene_out, g.scene_out, n_sc * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return order_out(h, mem);
+}
+
 int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
               int mem) {
     if (!h || !sel || !logw || E <= 0 || A <= 0 || K <= 1 || T <= 0) return fail(h, JMID_EINVAL, "bad argument");
     if (k < 1 || k > K) return fail(h, JMID_EINVAL, "k must be in 1..K");
     if (A > 32 || K > 1024 || T > 24) return fail(h, JMID_EINVAL, "jmid_topk supports A <= 32, K <= 1024, T <= 24");
     HIPCHK(h, hipSetDevice(h->device));
-    if (!pos) {
-        if (!h->last_pos || h->last_pos_dims[0] != E || h->last_pos_dims[1] != A || h->last_pos_dims[2] != K || h->last_pos_dims[3] != T)
-            return fail(h, JMID_EINVAL, "pos = NULL needs a preceding jmid_denoise with p0 and the same E, A, K, T on this handle");
-    }
+    if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
     if (int rc = order_in(h, mem)) return rc;
     const int d = 2 * A;
     const size_t n_pos = (size_t)E * K * A * T * 2, n_sel = (size_t)E * A * k * T * 2, n_lw = (size_t)E * A * k;
@@ -271,16 +325,7 @@ int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* p
     const size_t o_ll = 0, o_Y = up((size_t)E * T * K * 8), o_bw = o_Y + y_bytes, o_pos = o_bw + up(T * 4),
                  o_sel = o_pos + (pos && mem == JMID_MEM_HOST ? up(n_pos * 4) : 0), o_lw = o_sel + (mem == JMID_MEM_HOST ? up(n_sel * 4) : 0),
                  need = o_lw + (mem == JMID_MEM_HOST ? up(n_lw * 4) : 0);
-    if (need > h->kde_ws_bytes) {
-        if (h->kde_ws) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            HIPCHK(h, hipFree(h->kde_ws));
-            h->kde_ws = nullptr;
-            h->kde_ws_bytes = 0;
-        }
-        if (hipMalloc((void**)&h->kde_ws, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_topk workspace allocation failed");
-        h->kde_ws_bytes = need;
-    }
+    if (int rc = ensure_kde_ws(h, need, "jmid_topk")) return rc;
     KdeArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T; g.k = k;
     g.ll = reinterpret_cast<double*>(h->kde_ws + o_ll);

@@ -1,6 +1,6 @@
 // libjmid_hip.so -- what every translation unit of the host side shares: the handle, error / profiling helpers and the
 // internal entry points between the units.  gfx950 only.  No CPU fallback: every entry point that computes needs a HIP device.
-//   jmid_abi.hip      the C ABI proper (include/jmid_hip.h): handle lifetime, encode / denoise / topk / predict, knobs, stream
+//   jmid_abi.hip      the C ABI proper (include/jmid_hip.h): handle lifetime, encode / denoise / topk / predict / statistics, knobs, stream
 //   jmid_weights.hip  weight registry, operand planes (fp16 hi / lo, bf8 images, k16 panels), sampler step tables
 //   jmid_planner.hip  chunk plan, step workspace, one net evaluation (net_step), the denoise loop (run_network)
 //   jmid_profile.hip  per-kernel-class HIP-event profiling
@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "elementwise.hpp"
 #include "encoder.hpp"
+#include "eval_stats.hpp"
 #include "gemm_f16x3.hpp"
 #include "gemm_ln_f16x3.hpp"
 #include "gemm_ln2_mx.hpp"
@@ -49,6 +50,7 @@ enum KClass {
     KC_METRICS,
     KC_VTRANS,
     KC_TOPK,
+    KC_EVAL_STATS,
     KC_COUNT
 };
 extern const char* const kClassNames[KC_COUNT];
@@ -112,10 +114,10 @@ struct jmid_ctx {
     std::map<std::string, LoopGraph> graphs;
     int64_t graph_replays = 0;
     // the positions of the most recent jmid_denoise (integrated into the workspace whether or not they were copied out): what
-    // jmid_topk ranks when it is given no pos pointer
+    // jmid_topk ranks and jmid_eval_statistics scores when they are given no pos pointer
     const float* last_pos = nullptr;
     int last_pos_dims[4] = {0, 0, 0, 0};     // E, A, K, T
-    char* kde_ws = nullptr;                  // jmid_topk's own workspace (it must not move the arena last_pos points into)
+    char* kde_ws = nullptr;                  // jmid_topk's and jmid_eval_statistics' own workspace (it must not move the arena last_pos points into)
     size_t kde_ws_bytes = 0;
     // jmid_predict: pinned host staging + device I/O buffers of the chained call, grown on demand
     char* pin = nullptr;

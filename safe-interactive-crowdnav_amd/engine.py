@@ -303,6 +303,39 @@ class JmidEngine:
                                                    self._mem(dev)))
         return out
 
+    def eval_statistics(self, pos: Optional[ArrayLike], gt: ArrayLike, dims: Optional[Tuple[int, int, int, int]] = None):
+        """The reference's evaluation statistics on the device (``jmid_eval_statistics``; compute_batch_statistics,
+        MID/evaluation/evaluation.py:456-739).  pos [E, K, A, T, 2], gt [E, A, T, 2] -> (agent [E, A, 10], scene [E, 6]) with the
+        columns ``metrics.STAT_AGENT_COLUMNS`` / ``metrics.STAT_SCENE_COLUMNS``; NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors
+        out.  ``pos=None`` with ``dims=(E, A, K, T)`` scores the positions of the preceding ``denoise`` call, which are still in the
+        engine's workspace (``gt`` then decides where the outputs live).  2 <= K <= 1024, T <= 24: ``metrics.eval_statistics_host``
+        beyond."""
+        dev = _is_cuda(gt)
+        if pos is None:
+            if dims is None:
+                raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
+            E, A, K, T = (int(v) for v in dims)
+            bp = None
+        else:
+            if _is_cuda(pos) != dev:
+                raise TypeError("pos and gt must both be CUDA/HIP tensors or both host arrays")
+            E, K, A, T, _ = (int(v) for v in pos.shape)
+            bp = _Buf(pos, dev)
+        if tuple(gt.shape) != (E, A, T, 2):
+            raise ValueError("gt must be [E, A, T, 2]")
+        bg = _Buf(gt, dev)
+        if dev:
+            agent = torch.empty((E, A, 10), dtype=torch.float32, device=gt.device)
+            scene = torch.empty((E, 6), dtype=torch.float32, device=gt.device)
+            ptrs = (C.c_void_p(agent.data_ptr()), C.c_void_p(scene.data_ptr()))
+        else:
+            agent = np.empty((E, A, 10), dtype=np.float32)
+            scene = np.empty((E, 6), dtype=np.float32)
+            ptrs = (C.c_void_p(agent.ctypes.data), C.c_void_p(scene.ctypes.data))
+        self._check(self._lib.jmid_eval_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, bg.ptr, *ptrs,
+                                                   self._mem(dev)))
+        return agent, scene
+
     # ------------------------------------------------------------------ measurement
     def kernel_classes(self):
         return [self._lib.jmid_kernel_class_name(i).decode() for i in range(self._lib.jmid_kernel_class_count())]

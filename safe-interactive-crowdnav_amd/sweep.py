@@ -42,3 +42,21 @@ def gather_metrics(local: torch.Tensor, total: int, dst: int = 0, force: bool = 
         lo, hi = shard_range(total, r, world)
         rows.append(gl[r][: hi - lo].cpu().numpy())
     return np.concatenate(rows, axis=0)
+
+
+def statistics_rows(agent, scene):
+    """One shard's evaluation statistics (``JmidEngine.eval_statistics``: agent [E, A, 10], scene [E, 6]; tensors or arrays) as
+    per-episode rows [E, A * 10 + 6], the form ``gather_metrics`` carries."""
+    if isinstance(agent, torch.Tensor):
+        return torch.cat([agent.reshape(agent.shape[0], -1), scene.reshape(scene.shape[0], -1)], dim=1)
+    return np.concatenate([agent.reshape(agent.shape[0], -1), scene.reshape(scene.shape[0], -1)], axis=1)
+
+
+def split_statistics_rows(rows, n_agents: int):
+    """Undo ``statistics_rows`` (on the destination rank, after ``gather_metrics``): [E, A * 10 + 6] -> (agent [E, A, 10],
+    scene [E, 6])."""
+    from .metrics import STAT_AGENT_COLUMNS, STAT_SCENE_COLUMNS
+    na, ns = len(STAT_AGENT_COLUMNS), len(STAT_SCENE_COLUMNS)
+    if rows.ndim != 2 or rows.shape[1] != n_agents * na + ns:
+        raise ValueError(f"expected rows [E, {n_agents} * {na} + {ns}]")
+    return rows[:, : n_agents * na].reshape(rows.shape[0], n_agents, na), rows[:, n_agents * na:]
