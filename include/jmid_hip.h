@@ -197,6 +197,42 @@ int jmid_episode_metrics(jmid_handle_t h, int E, int A, int K, int T, const floa
 int jmid_eval_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt, float* agent_out,
                          float* scene_out, int mem);
 
+/* The masked form of jmid_eval_statistics: the is_eval_hst branch of compute_batch_statistics (MID/evaluation/evaluation.py:540-545,
+ * 556-558, 566-568, 573-577, 624-715; its fixed-horizon columns are printed at MID/mid.py:978-1000, 1051-1075), for episodes whose
+ * ground-truth future is only partly real (an episode that ended, a human that arrived).
+ *   pos, gt        as jmid_eval_statistics (pos = NULL under the same rules)
+ *   interp_future  [E, A, T] bytes, 1 = the step's ground truth is interpolated or absent: not scored (interpolated_future)
+ *   skip           [E, A] bytes or NULL, 1 = the agent is left out (the reference: its history is all interpolated, :542-545); an agent
+ *                  without any scored step is left out as well
+ *   n_cut, cutoffs host ints: the fixed-horizon steps, each in [0, T), n_cut <= 4, may be 0 (the reference hard-codes 2, 5, 8 for
+ *                  T = 12: "one / two / three fourth")
+ *   agent_out  [E, A, 12] = the ten columns of jmid_eval_statistics, n_valid, fde_valid
+ *                - ade[s] = the mean of the distances over the scored steps (compute_ade, :20-22); fde[s] = the last step's distance,
+ *                  absent when that step is not scored (compute_fde, :32-34): fde_valid = 0 and fde_min / fde_mean / fde_std / fde_ml NaN
+ *                - kde_nll and ml_idx over the scored steps only (np.compress, :212-214, :262-266); one scored step is enough
+ *                - n_valid = the number of scored steps; 0 = the agent is left out: every float column NaN, ml_idx = -1
+ *   cut_out    [E, A, n_cut, 5] = {ade_min, ade_mean, ade_ml, kde, valid} per cut-off step c; may be NULL when n_cut = 0
+ *                - the distance at step c alone per sample (compute_ade with cutoff_idx, :13-18): its min and mean over the samples
+ *                  (:634-646) and its value at the most likely sample of the whole masked horizon (:647-653)
+ *                - kde: QUIRK OF THE REFERENCE, reproduced.  compute_kde_nll(cutoff_idx = c) slices the ground truth to shape [2] and
+ *                  then loops "time steps" over its two entries (:209-222), so it returns the mean of two 1-D gaussian_kde negative
+ *                  log-pdfs, each floored at -20 - the K x-coordinates at the ground truth's x and the K y-coordinates at its y, with
+ *                  scipy's 1-D defaults (variance with divisor K - 1, Scott's factor K^(-1/5)) - not a 2-D single-step density
+ *                - step c not scored (or the agent left out): the four values NaN, valid = 0
+ *   scene_out  [E, 6] as jmid_eval_statistics over the agents that are kept (:717-737); may be NULL
+ * A factorisation that fails follows jmid_eval_statistics: a scored step without a 2 x 2 Cholesky factor makes kde_nll NaN, ml_idx -1
+ * and every *_ml column (the cut-offs' too) NaN; a cut-off step whose x or y coordinates have no variance makes that cut-off's kde NaN.
+ * n_valid, fde_valid and valid tell "absent" from "NaN because scipy would have raised".
+ * THIS PROJECT'S CONVENTIONS, where the reference raises instead of computing: its scene block fails with TypeError when a kept
+ * agent has no fde and with IndexError when no agent is kept (and appends a stale min_fde_errors for an agent without fde, :592-612).
+ * Here sfde runs over the kept agents whose last step is scored, sade over all kept agents, and a block without any qualifying agent
+ * is NaN (three columns).
+ * fp64 inside, fixed-order reductions, no atomics, as jmid_eval_statistics; with nothing masked and skip = NULL the first ten agent
+ * columns and the scene row are bit-identical to that entry point's.  2 <= K <= 1024, T <= 24, any A (JMID_EINVAL beyond). */
+int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt,
+                                const uint8_t* interp_future, const uint8_t* skip, int n_cut, const int* cutoffs, float* agent_out,
+                                float* cut_out, float* scene_out, int mem);
+
 /* Joint-KDE ranking of the K sampled futures of every episode and selection of the k most likely ones:
  * get_most_likely_samples (sicnav_diffusion/JMID/mid_sim_wrapper.py:14-169, the joint branch :20-21 the predictor always takes;
  * called from predict_ret_best when num_ret_samples < K, :487-492), which the reference runs on its GPU when it has one (:26-30).

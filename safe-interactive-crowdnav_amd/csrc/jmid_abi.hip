@@ -309,6 +309,66 @@ int jmid_eval_statistics(jmid_handle_t h, int E, int A, int K, int T, const floa
     return order_out(h, mem);
 }
 
+int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt,
+                                const uint8_t* interp_future, const uint8_t* skip, int n_cut, const int* cutoffs, float* agent_out,
+                                float* cut_out, float* scene_out, int mem) {
+    if (!h || !gt || !interp_future || !agent_out || E <= 0 || A <= 0 || T <= 0) return fail(h, JMID_EINVAL, "bad argument");
+    if (K < 2 || K > 1024 || T > 24) return fail(h, JMID_EINVAL, "jmid_eval_statistics_masked supports 2 <= K <= 1024, T <= 24");
+    if ((size_t)E * A > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, "jmid_eval_statistics_masked: E * A exceeds the launch grid");
+    if (n_cut < 0 || n_cut > EVS_MAX_CUTS || (n_cut > 0 && (!cutoffs || !cut_out)))
+        return fail(h, JMID_EINVAL, "jmid_eval_statistics_masked takes 0 <= n_cut <= 4 cut-offs (with cutoffs and cut_out)");
+    EvalStatsMaskedArgs g{};
+    for (int j = 0; j < n_cut; ++j) {
+        if (cutoffs[j] < 0 || cutoffs[j] >= T) return fail(h, JMID_EINVAL, "jmid_eval_statistics_masked: a cut-off step is not in [0, T)");
+        g.cutoffs[j] = cutoffs[j];
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
+    if (int rc = order_in(h, mem)) return rc;
+    const size_t n_pos = (size_t)E * K * A * T * 2, n_gt = (size_t)E * A * T * 2, n_ag = (size_t)E * A * EVS_MASKED_AGENT_COLS,
+                 n_ct = (size_t)E * A * n_cut * EVS_CUT_COLS, n_sc = scene_out ? (size_t)E * EVS_SCENE_COLS : 0,
+                 n_if = (size_t)E * A * T, n_sk = skip ? (size_t)E * A : 0;
+    g.E = E; g.A = A; g.K = K; g.T = T; g.n_cut = n_cut;
+    g.pos = pos ? pos : h->last_pos;
+    g.gt = gt; g.interp = interp_future; g.skip = skip;
+    g.agent_out = agent_out; g.cut_out = n_cut ? cut_out : nullptr; g.scene_out = scene_out;
+    if (mem == JMID_MEM_HOST) {
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        const size_t o_gt = 0, o_ag = o_gt + up(n_gt * 4), o_ct = o_ag + up(n_ag * 4), o_sc = o_ct + up(n_ct * 4), o_if = o_sc + up(n_sc * 4),
+                     o_sk = o_if + up(n_if), o_pos = o_sk + up(n_sk), need = o_pos + (pos ? up(n_pos * 4) : 0);
+        if (int rc = ensure_kde_ws(h, need, "jmid_eval_statistics_masked")) return rc;
+        float* dg = reinterpret_cast<float*>(h->kde_ws + o_gt);
+        unsigned char* di = reinterpret_cast<unsigned char*>(h->kde_ws + o_if);
+        HIPCHK(h, hipMemcpyAsync(dg, gt, n_gt * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(di, interp_future, n_if, hipMemcpyHostToDevice, h->stream));
+        g.gt = dg; g.interp = di;
+        if (skip) {
+            unsigned char* ds = reinterpret_cast<unsigned char*>(h->kde_ws + o_sk);
+            HIPCHK(h, hipMemcpyAsync(ds, skip, n_sk, hipMemcpyHostToDevice, h->stream));
+            g.skip = ds;
+        }
+        if (pos) {
+            float* dp = reinterpret_cast<float*>(h->kde_ws + o_pos);
+            HIPCHK(h, hipMemcpyAsync(dp, pos, n_pos * 4, hipMemcpyHostToDevice, h->stream));
+            g.pos = dp;
+        }
+        g.agent_out = reinterpret_cast<float*>(h->kde_ws + o_ag);
+        if (n_cut) g.cut_out = reinterpret_cast<float*>(h->kde_ws + o_ct);
+        if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
+    }
+    {
+        ProfScope ps(h, KC_EVAL_STATS);
+        HIPCHK(h, launch_eval_stats_masked(g, h->stream));
+    }
+    if (mem == JMID_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(agent_out, g.agent_out, n_ag * 4, hipMemcpyDeviceToHost, h->stream));
+        if (n_cut) HIPCHK(h, hipMemcpyAsync(cut_out, g.cut_out, n_ct * 4, hipMemcpyDeviceToHost, h->stream));
+        if (scene_out) HIPCHK(h, hipMemcpyAsync(scene_out, g.scene_out, n_sc * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return order_out(h, mem);
+}
+
 int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
               int mem) {
     if (!h || !sel || !logw || E <= 0 || A <= 0 || K <= 1 || T <= 0) return fail(h, JMID_EINVAL, "bad argument");

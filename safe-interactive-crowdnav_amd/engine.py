@@ -336,6 +336,58 @@ class JmidEngine:
                                                    self._mem(dev)))
         return agent, scene
 
+    def eval_statistics_masked(self, pos: Optional[ArrayLike], gt: ArrayLike, interp_future: ArrayLike,
+                               interp_history: Optional[ArrayLike] = None, cutoffs=(2, 5, 8),
+                               dims: Optional[Tuple[int, int, int, int]] = None):
+        """The masked form of ``eval_statistics`` (``jmid_eval_statistics_masked``; the ``is_eval_hst`` branch of
+        compute_batch_statistics, MID/evaluation/evaluation.py:540-715): pos [E, K, A, T, 2] (or None with ``dims``, as there),
+        gt [E, A, T, 2], interp_future [E, A, T] bool (True = the step's ground truth is not real: not scored), interp_history
+        [E, A, F] bool or None (an agent whose history is all True is left out) -> (agent [E, A, 12], cut [E, A, len(cutoffs), 5],
+        scene [E, 6]) with the columns ``metrics.STAT_MASKED_AGENT_COLUMNS`` / ``STAT_CUTOFF_COLUMNS`` / ``STAT_SCENE_COLUMNS``.
+        NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out (the masks follow ``gt``).  At most 4 cut-off steps, each in
+        [0, T); 2 <= K <= 1024, T <= 24: ``metrics.eval_statistics_masked_host`` beyond."""
+        dev = _is_cuda(gt)
+        if pos is None:
+            if dims is None:
+                raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
+            E, A, K, T = (int(v) for v in dims)
+            bp = None
+        else:
+            if _is_cuda(pos) != dev:
+                raise TypeError("pos and gt must both be CUDA/HIP tensors or both host arrays")
+            E, K, A, T, _ = (int(v) for v in pos.shape)
+            bp = _Buf(pos, dev)
+        if tuple(gt.shape) != (E, A, T, 2):
+            raise ValueError("gt must be [E, A, T, 2]")
+        if tuple(interp_future.shape) != (E, A, T):
+            raise ValueError("interp_future must be [E, A, T]")
+        if interp_history is not None and tuple(interp_history.shape[:2]) != (E, A):
+            raise ValueError("interp_history must be [E, A, F]")
+        if _is_cuda(interp_future) != dev or (interp_history is not None and _is_cuda(interp_history) != dev):
+            raise TypeError("the masks must live where gt lives")
+        cuts = (C.c_int * max(len(cutoffs), 1))(*[int(c) for c in cutoffs])
+        n_cut = len(cutoffs)
+        bg = _Buf(gt, dev)
+        if dev:
+            fut = (interp_future != 0).to(torch.uint8).contiguous()
+            skip = (interp_history != 0).reshape(E, A, -1).all(dim=-1).to(torch.uint8).contiguous() if interp_history is not None else None
+            agent = torch.empty((E, A, 12), dtype=torch.float32, device=gt.device)
+            cut = torch.empty((E, A, n_cut, 5), dtype=torch.float32, device=gt.device)
+            scene = torch.empty((E, 6), dtype=torch.float32, device=gt.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        else:
+            to_np = lambda m: m.detach().cpu().numpy() if torch is not None and isinstance(m, torch.Tensor) else np.asarray(m)
+            fut = np.ascontiguousarray(to_np(interp_future) != 0, dtype=np.uint8)
+            skip = (np.ascontiguousarray((to_np(interp_history) != 0).reshape(E, A, -1).all(axis=-1), dtype=np.uint8)
+                    if interp_history is not None else None)
+            agent = np.empty((E, A, 12), dtype=np.float32)
+            cut = np.empty((E, A, n_cut, 5), dtype=np.float32)
+            scene = np.empty((E, 6), dtype=np.float32)
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None and t.size else None
+        self._check(self._lib.jmid_eval_statistics_masked(self._h, E, A, K, T, bp.ptr if bp is not None else None, bg.ptr, ptr(fut),
+                                                          ptr(skip), n_cut, cuts, ptr(agent), ptr(cut), ptr(scene), self._mem(dev)))
+        return agent, cut, scene
+
     # ------------------------------------------------------------------ measurement
     def kernel_classes(self):
         return [self._lib.jmid_kernel_class_name(i).decode() for i in range(self._lib.jmid_kernel_class_count())]

@@ -382,3 +382,28 @@ def history_windows(sim: Dict[str, np.ndarray], frame: int, num_hist_frames: int
     if lo < 0:
         raise ValueError("not enough simulated frames for a full history window")
     return sim["human_xy"][:, lo:frame + 1], sim["robot_xy"][:, lo:frame + 1]
+
+
+def future_windows(sim: Dict[str, np.ndarray], frame: int, horizon: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The ground-truth future of every human after simulator step ``frame``: (gt [E, N, horizon, 2], interpolated
+    [E, N, horizon] bool) - the ``gt`` and ``interp_future`` of ``JmidEngine.eval_statistics_masked``, so that every frame of a
+    closed-loop run can be scored and not only those with a complete future.  A step is flagged when it lies beyond the simulated
+    range and, for ``crowd_env.simulate_hallway`` output, when it was produced by a simulator step after the one that ended the
+    episode (``end_step``, -1 = still running; step k takes frame k to frame k + 1, so frame ``end_step`` + 1 is the last real one):
+    what the simulator wrote after it is not a future anybody walked.  Flagged steps hold the last real position (values that are
+    never scored)."""
+    xy = sim["human_xy"]
+    E, n_frames, N, _ = xy.shape
+    if frame < 0 or frame >= n_frames:
+        raise ValueError("frame is outside the simulated range")
+    if horizon < 1:
+        raise ValueError("horizon must be at least 1")
+    last = np.full(E, n_frames - 1)
+    if "end_step" in sim:
+        end = np.asarray(sim["end_step"])
+        last = np.where(end >= 0, np.minimum(end + 1, last), last)
+    steps = frame + 1 + np.arange(horizon)                             # [H] frames of the window
+    interpolated = steps[None, :] > last[:, None]                      # [E, H]
+    take = np.minimum(steps[None, :], np.maximum(last, frame)[:, None])
+    gt = np.take_along_axis(xy, take[:, :, None, None], axis=1).transpose(0, 2, 1, 3)
+    return np.ascontiguousarray(gt), np.ascontiguousarray(np.broadcast_to(interpolated[:, None, :], (E, N, horizon)))

@@ -5,6 +5,10 @@ Reference: ``compute_batch_statistics`` (MID/evaluation/evaluation.py:456-739, t
 ``compute_ade`` / ``compute_fde`` (:11-36), ``compute_kde_nll`` (:191-232), ``get_most_likely_trajectory_idx`` (:445-453) and the
 summary of ``MID.eval`` (MID/mid.py:965-1003).  The reference fits its per-step densities with ``scipy.stats.gaussian_kde``; the
 package does not import scipy - the two routines are restated here in closed form for the 2-D case.
+
+The masked form (``eval_statistics_masked_host``, ``summarise_masked``; ``jmid_eval_statistics_masked``) is the ``is_eval_hst`` branch
+of the same function (:540-545, :556-577, :624-715; summarised at MID/mid.py:978-1000, 1051-1075): only the horizon steps whose ground
+truth is real are scored, agents without any are left out, and the fixed-horizon ("one / two / three fourth") columns are added.
 """
 from __future__ import annotations
 
@@ -14,6 +18,9 @@ import numpy as np
 
 STAT_AGENT_COLUMNS = ("ade_min", "ade_mean", "ade_std", "ade_ml", "fde_min", "fde_mean", "fde_std", "fde_ml", "kde_nll", "ml_idx")
 STAT_SCENE_COLUMNS = ("sade_min", "sade_mean", "sade_std", "sfde_min", "sfde_mean", "sfde_std")
+STAT_MASKED_AGENT_COLUMNS = STAT_AGENT_COLUMNS + ("n_valid", "fde_valid")
+STAT_CUTOFF_COLUMNS = ("ade_min", "ade_mean", "ade_ml", "kde", "valid")
+CUTOFF_NAMES = ("one_fourth", "two_fourth", "three_fourth")      # the reference's names of cut-off positions 0, 1, 2
 LOG_PDF_LOWER_BOUND = -20.0      # evaluation.py:203, :271
 
 # the reference's summary keys (mid.py:965-1003) -> the column each one averages
@@ -48,6 +55,24 @@ def step_logpdf(points: np.ndarray, gt: np.ndarray):
         lse = np.where(np.isneginf(m), m, m + np.log(np.exp(en - m[:, None]).sum(axis=1)))
     lp = lse - np.log(K) - np.log(2.0 * np.pi) - np.log(l11 * l22)     # ln K + 1/2 ln det(2 pi C)
     return lp[:K], lp[K]
+
+
+def step_logpdf_1d(points: np.ndarray, x: float):
+    """``gaussian_kde(points)`` with scipy's defaults for one coordinate: points [K] float64 -> its log-pdf at ``x``, unclipped, or
+    None when the data have no variance (the 1 x 1 Cholesky factorisation fails: scipy raises LinAlgError).  Variance with divisor
+    K - 1, Scott's factor K^(-1/5) (d = 1)."""
+    K = points.shape[0]
+    c = points - points.mean()
+    var = (c * c).sum() / (K - 1)
+    if not var > 0.0:
+        return None
+    l = np.sqrt(var) * float(K) ** (-1.0 / 5.0)
+    y0 = (x - points) / l
+    en = -0.5 * (y0 * y0)
+    m = en.max()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lse = m if np.isneginf(m) else m + np.log(np.exp(en - m).sum())
+    return lse - np.log(K) - 0.5 * np.log(2.0 * np.pi) - np.log(l)
 
 
 def _min_mean_std(v: np.ndarray) -> np.ndarray:
@@ -103,6 +128,122 @@ def eval_statistics_host(pos: np.ndarray, gt: np.ndarray, return_details: bool =
     if return_details:
         return agent, scene, {"gt_logpdf": gt_lp, "ml_gap": gap}
     return agent, scene
+
+
+def eval_statistics_masked_host(pos: np.ndarray, gt: np.ndarray, interp_future: np.ndarray, interp_history=None,
+                                cutoffs=(2, 5, 8), return_details: bool = False):
+    """The ``is_eval_hst`` branch: pos [E, K, A, T, 2], gt [E, A, T, 2], interp_future [E, A, T] bool (True = the step is not scored),
+    interp_history [E, A, F] bool or None (an agent whose history is all True is left out, like one without a scored step, :544-545)
+    -> (agent [E, A, 12], cut [E, A, len(cutoffs), 5], scene [E, 6]) float64 with the columns ``STAT_MASKED_AGENT_COLUMNS``,
+    ``STAT_CUTOFF_COLUMNS``, ``STAT_SCENE_COLUMNS``: what ``JmidEngine.eval_statistics_masked`` computes on the device, without its
+    size limits.  Absent values are NaN with their flag column 0 (``n_valid`` = 0: the agent is left out; ``fde_valid``; a
+    cut-off's ``valid``).  The cut-offs' ``kde`` reproduces the reference's quirk: the mean of two 1-D negative log-pdfs (x and y),
+    not a 2-D single-step density (``compute_kde_nll`` with ``cutoff_idx``, :209-222).  This project's conventions where the
+    reference raises: sfde runs over the kept agents whose last step is scored, and a scene block without a qualifying agent is NaN.
+    ``return_details``: additionally ``ml_gap`` [E, A] as in ``eval_statistics_host``."""
+    pos = np.asarray(pos, dtype=np.float64)
+    gt = np.asarray(gt, dtype=np.float64)
+    E, K, A, T, _ = pos.shape
+    if gt.shape != (E, A, T, 2):
+        raise ValueError("gt must be [E, A, T, 2]")
+    masked = np.asarray(interp_future).astype(bool)
+    if masked.shape != (E, A, T):
+        raise ValueError("interp_future must be [E, A, T]")
+    if K < 2:
+        raise ValueError("the statistics need at least two samples")
+    cutoffs = tuple(int(c) for c in cutoffs)
+    if any(c < 0 or c >= T for c in cutoffs):
+        raise ValueError("every cut-off step must be in [0, T)")
+    valid = ~masked
+    if interp_history is not None:
+        hist = np.asarray(interp_history).astype(bool)
+        if hist.shape[:2] != (E, A):
+            raise ValueError("interp_history must be [E, A, F]")
+        valid = valid & ~hist.reshape(E, A, -1).all(axis=-1)[..., None]
+    n_valid = valid.sum(axis=-1)                                       # [E, A]
+    kept, fde_ok = n_valid > 0, valid[..., -1]
+    d = np.linalg.norm(pos - gt[:, None], axis=-1)                     # [E, K, A, T]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ade = np.where(valid[:, None], d, 0.0).sum(axis=-1) / n_valid[:, None]        # [E, K, A]; NaN for an agent left out
+    fde = np.where(fde_ok[:, None], d[..., -1], np.nan)
+    agent = np.full((E, A, len(STAT_MASKED_AGENT_COLUMNS)), np.nan)
+    cut = np.full((E, A, len(cutoffs), len(STAT_CUTOFF_COLUMNS)), np.nan)
+    agent[..., 0:3] = _min_mean_std(ade)
+    agent[..., 4:7] = _min_mean_std(fde)
+    agent[..., 9], agent[..., 10], agent[..., 11] = -1, n_valid, fde_ok
+    cut[..., 4] = 0
+    gap = np.full((E, A), np.nan)
+    for e in range(E):
+        for a in range(A):
+            if not kept[e, a]:
+                continue
+            steps = np.flatnonzero(valid[e, a])
+            self_ll, gt_lp, ok = np.zeros(K), np.full(T, np.nan), True
+            for t in steps:
+                r = step_logpdf(pos[e, :, a, t], gt[e, a, t])
+                if r is None:
+                    ok = False
+                    continue
+                self_ll += np.maximum(r[0], LOG_PDF_LOWER_BOUND)
+                gt_lp[t] = r[1]
+            ml = -1
+            if ok:
+                self_ll /= len(steps)
+                ml = int(np.argmax(self_ll))
+                agent[e, a, 3], agent[e, a, 7] = ade[e, ml, a], fde[e, ml, a]
+                agent[e, a, 8] = -np.mean(np.maximum(gt_lp[steps], LOG_PDF_LOWER_BOUND))
+                agent[e, a, 9] = ml
+                top2 = np.sort(self_ll)[-2:]
+                gap[e, a] = top2[1] - top2[0]
+            for j, c in enumerate(cutoffs):
+                if not valid[e, a, c]:
+                    continue
+                dc = d[e, :, a, c]
+                lps = [step_logpdf_1d(pos[e, :, a, c, k], gt[e, a, c, k]) for k in range(2)]
+                kde = np.nan if None in lps else -(max(lps[0], LOG_PDF_LOWER_BOUND) / 2 + max(lps[1], LOG_PDF_LOWER_BOUND) / 2)
+                cut[e, a, j] = [dc.min(), dc.mean(), dc[ml] if ml >= 0 else np.nan, kde, 1]
+    n_kept, n_last = kept.sum(axis=1), (kept & fde_ok).sum(axis=1)     # [E]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sade = np.where(kept[:, None], ade, 0.0).sum(axis=2) / n_kept[:, None]            # [E, K]
+        sfde = np.where((kept & fde_ok)[:, None], fde, 0.0).sum(axis=2) / n_last[:, None]
+    scene = np.concatenate([_min_mean_std(sade), _min_mean_std(sfde)], axis=1)
+    if return_details:
+        return agent, cut, scene, {"ml_gap": gap}
+    return agent, cut, scene
+
+
+def summarise_masked(agent: np.ndarray, cut: np.ndarray, scene: np.ndarray) -> Dict[str, float]:
+    """The reference's table of means for the ``is_eval_hst`` branch (mid.py:978-1000, 1051-1075) from the rows of all episodes:
+    agent [..., 12], cut [..., n_cut, 5], scene [..., 6].  Each key is a plain ``np.mean`` over the rows that are present - the
+    reference appends nothing for the others: ``n_valid`` > 0 for the ADE / KDE columns, ``fde_valid`` for the FDE columns, the
+    cut-off's ``valid`` for its columns (named ``*_one_fourth``, ``*_two_fourth``, ``*_three_fourth`` for cut-off positions 0, 1,
+    2); the scene keys average the episodes whose block exists.  A key without any row is NaN.  NaN rows from degenerate samples
+    propagate as in ``summarise``; their number comes back as ``nan_rows``."""
+    na, nc = len(STAT_MASKED_AGENT_COLUMNS), len(STAT_CUTOFF_COLUMNS)
+    cut = np.asarray(cut, dtype=np.float64)
+    n_cut = cut.shape[-2]
+    if n_cut > len(CUTOFF_NAMES):
+        raise ValueError("the reference names three cut-offs")
+    agent = np.asarray(agent, dtype=np.float64).reshape(-1, na)
+    cut = cut.reshape(-1, n_cut, nc)
+    scene = np.asarray(scene, dtype=np.float64).reshape(-1, len(STAT_SCENE_COLUMNS))
+    mean = lambda v: float(np.mean(v)) if v.size else float("nan")
+    kept = agent[:, STAT_MASKED_AGENT_COLUMNS.index("n_valid")] > 0
+    with_fde = kept & (agent[:, STAT_MASKED_AGENT_COLUMNS.index("fde_valid")] > 0)
+    out = {}
+    for k, c in _SUMMARY_AGENT.items():
+        out[k] = mean(agent[with_fde if c.startswith("fde") else kept, STAT_AGENT_COLUMNS.index(c)])
+    for j in range(n_cut):
+        rows = cut[cut[:, j, STAT_CUTOFF_COLUMNS.index("valid")] > 0, j]
+        for key, c in (("ade", "ade_min"), ("ade_most_likely", "ade_ml"), ("ade_mean", "ade_mean"), ("kde", "kde")):
+            out[f"{key}_{CUTOFF_NAMES[j]}"] = mean(rows[:, STAT_CUTOFF_COLUMNS.index(c)])
+    for k, c in _SUMMARY_SCENE.items():
+        col = scene[:, STAT_SCENE_COLUMNS.index(c)]
+        # an absent block (no qualifying agent) is NaN in all three of its columns; its minimum is NaN for no other reason
+        present = ~np.isnan(scene[:, STAT_SCENE_COLUMNS.index("sade_min" if c.startswith("sade") else "sfde_min")])
+        out[k] = mean(col[present])
+    out["nan_rows"] = int(np.isnan(agent[kept, STAT_AGENT_COLUMNS.index("kde_nll")]).sum())
+    return out
 
 
 def summarise(agent: np.ndarray, scene: np.ndarray) -> Dict[str, float]:

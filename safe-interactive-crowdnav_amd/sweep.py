@@ -60,3 +60,25 @@ def split_statistics_rows(rows, n_agents: int):
     if rows.ndim != 2 or rows.shape[1] != n_agents * na + ns:
         raise ValueError(f"expected rows [E, {n_agents} * {na} + {ns}]")
     return rows[:, : n_agents * na].reshape(rows.shape[0], n_agents, na), rows[:, n_agents * na:]
+
+
+def masked_statistics_rows(agent, cut, scene):
+    """One shard's masked evaluation statistics (``JmidEngine.eval_statistics_masked``: agent [E, A, 12], cut [E, A, C, 5],
+    scene [E, 6]; tensors or arrays) as per-episode rows [E, A * (12 + 5 C) + 6] - every agent's columns followed by its cut-offs',
+    then the scene's - the form ``gather_metrics`` carries."""
+    E, A = agent.shape[0], agent.shape[1]
+    if isinstance(agent, torch.Tensor):
+        return torch.cat([torch.cat([agent, cut.reshape(E, A, -1)], dim=2).reshape(E, -1), scene.reshape(E, -1)], dim=1)
+    return np.concatenate([np.concatenate([agent, cut.reshape(E, A, -1)], axis=2).reshape(E, -1), scene.reshape(E, -1)], axis=1)
+
+
+def split_masked_statistics_rows(rows, n_agents: int, n_cut: int):
+    """Undo ``masked_statistics_rows`` (on the destination rank, after ``gather_metrics``): [E, A * (12 + 5 C) + 6] ->
+    (agent [E, A, 12], cut [E, A, C, 5], scene [E, 6])."""
+    from .metrics import STAT_CUTOFF_COLUMNS, STAT_MASKED_AGENT_COLUMNS, STAT_SCENE_COLUMNS
+    na, nc, ns = len(STAT_MASKED_AGENT_COLUMNS), len(STAT_CUTOFF_COLUMNS), len(STAT_SCENE_COLUMNS)
+    w = na + nc * n_cut
+    if rows.ndim != 2 or rows.shape[1] != n_agents * w + ns:
+        raise ValueError(f"expected rows [E, {n_agents} * ({na} + {nc} * {n_cut}) + {ns}]")
+    per_agent = rows[:, : n_agents * w].reshape(rows.shape[0], n_agents, w)
+    return per_agent[..., :na], per_agent[..., na:].reshape(rows.shape[0], n_agents, n_cut, nc), rows[:, n_agents * w:]
