@@ -233,6 +233,37 @@ int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, con
                                 const uint8_t* interp_future, const uint8_t* skip, int n_cut, const int* cutoffs, float* agent_out,
                                 float* cut_out, float* scene_out, int mem);
 
+/* Collision statistics of joint samples: how close the agents of one sampled future come to each other and which of them collide -
+ * sicnav_diffusion/JMID/MID/models/collision_check_utils.py, whose counts DiffusionTraj.sample still returns as placeholders
+ * (MID/models/diffusion.py:606-613).
+ *   pos         [E, K, A, T, 2]  sampled futures (jmid_denoise's pos_out layout), or NULL: the positions of the most recent
+ *                                jmid_denoise on this handle, under exactly the rules of jmid_topk's pos = NULL below.  Ground-truth
+ *                                futures [E, A, T, 2] go through the same call as K = 1
+ *   threshold   metres; a pair collides when its distance is < threshold in fp64 (the reference hard-codes 0.2, :88).  NaN never
+ *               collides
+ *   pair_out    [E, K, P], P = A (A - 1) / 2; may be NULL.  calc_min_dists (:58-80): every agent's path between consecutive horizon
+ *               steps is a line segment, and a pair's value is the minimum over the T - 1 segments of the distance from the origin to
+ *               the segment of the relative position pos_i - pos_j (lineseg_dist, :20-55: |a| when the relative position stands still,
+ *               hypot(max(a.d, -b.d, 0), |(-a) x d|) with d the unit tangent otherwise).  Pairs in pdist order (get_diffs_pred, :5-17):
+ *               p(i, j) = i A - i (i + 1) / 2 + (j - i - 1), i < j
+ *   agent_out   [E, K, A] bytes; may be NULL.  1 = the agent belongs to a colliding pair (get_agents_in_collision, :83-97)
+ *   sample_out  [E, K, 4] = {min_dist, closest_pair, n_pairs_colliding, n_agents_colliding}; may be NULL.  min_dist = the smallest pair
+ *               value, closest_pair = its pair index as a float (the lowest index on an exact tie).  n_agents_colliding > 0 is
+ *               check_collision_velocity (:100-108) of the sample
+ *   scene_out   [E, 5] = {collision_rate, agent_collision_rate, min_dist_min, min_dist_mean, min_dist_std}; may be NULL.
+ *               collision_rate = the share of the K samples with a collision, agent_collision_rate = the mean of the K A flags; min,
+ *               mean and np.std (population) of min_dist over the samples
+ * A = 1 has no pairs: min_dist = +inf, closest_pair = -1, counts and rates 0, min_dist_min = min_dist_mean = +inf, min_dist_std = NaN
+ * (inf - inf, as np.std).  A non-finite position makes the pairs it belongs to NaN (torch.min / torch.max propagate it) and with them
+ * the sample's min_dist (closest_pair = -1) and the episode's three min_dist columns; the counts and rates leave NaN pairs out.
+ * T = 1 IS REFUSED: with a single step the reference collapses to one scalar over all pairs instead of one value per pair (:69-79),
+ * which is not a per-pair quantity; duplicate the step (T = 2) for the static distance.
+ * fp64 inside on the fp32 inputs, so the fp32 outputs are the roundings of the fp64 values; fixed-order reductions, no atomics: a row
+ * is bit-identical whatever batch it is part of and in both memory modes.  1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64, threshold
+ * finite and >= 0, at least one output (JMID_EINVAL otherwise). */
+int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, double threshold,
+                              float* pair_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem);
+
 /* Joint-KDE ranking of the K sampled futures of every episode and selection of the k most likely ones:
  * get_most_likely_samples (sicnav_diffusion/JMID/mid_sim_wrapper.py:14-169, the joint branch :20-21 the predictor always takes;
  * called from predict_ret_best when num_ret_samples < K, :487-492), which the reference runs on its GPU when it has one (:26-30).

@@ -1,5 +1,6 @@
 // libjmid_hip.so -- the C ABI proper (include/jmid_hip.h): handle lifetime, the compute entry points, knobs, streams.
 #include "jmid_ctx.hpp"
+#include "collision_stats.hpp"
 
 namespace jmid_host {
 
@@ -364,6 +365,59 @@ int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, con
         HIPCHK(h, hipMemcpyAsync(agent_out, g.agent_out, n_ag * 4, hipMemcpyDeviceToHost, h->stream));
         if (n_cut) HIPCHK(h, hipMemcpyAsync(cut_out, g.cut_out, n_ct * 4, hipMemcpyDeviceToHost, h->stream));
         if (scene_out) HIPCHK(h, hipMemcpyAsync(scene_out, g.scene_out, n_sc * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return order_out(h, mem);
+}
+
+int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, double threshold, float* pair_out,
+                              uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
+    if (!h || E <= 0) return fail(h, JMID_EINVAL, "bad argument");
+    if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
+        return fail(h, JMID_EINVAL, "jmid_collision_statistics supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold))
+        return fail(h, JMID_EINVAL, "jmid_collision_statistics: the threshold must be finite and >= 0");
+    if (!pair_out && !agent_out && !sample_out && !scene_out) return fail(h, JMID_EINVAL, "jmid_collision_statistics: every output is NULL");
+    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, "jmid_collision_statistics: E * K exceeds the launch grid");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
+    if (int rc = order_in(h, mem)) return rc;
+    const size_t P = (size_t)A * (A - 1) / 2, n_pos = (size_t)E * K * A * T * 2, n_pr = pair_out ? (size_t)E * K * P : 0,
+                 n_ag = agent_out ? (size_t)E * K * A : 0, n_sm = sample_out ? (size_t)E * K * CLS_SAMPLE_COLS : 0,
+                 n_sc = scene_out ? (size_t)E * CLS_SCENE_COLS : 0;
+    const bool host = mem == JMID_MEM_HOST;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // the per-sample fp64 values the scene kernel reduces, then (host mode) the staging copies of the outputs and of pos
+    const size_t o_ws = 0, o_pr = o_ws + up((size_t)E * K * CLS_WS_COLS * 8), o_ag = o_pr + (host ? up(n_pr * 4) : 0),
+                 o_sm = o_ag + (host ? up(n_ag) : 0), o_sc = o_sm + (host ? up(n_sm * 4) : 0), o_pos = o_sc + (host ? up(n_sc * 4) : 0),
+                 need = o_pos + (host && pos ? up(n_pos * 4) : 0);
+    if (int rc = ensure_kde_ws(h, need, "jmid_collision_statistics")) return rc;
+    CollisionStatsArgs g{};
+    g.E = E; g.A = A; g.K = K; g.T = T;
+    g.threshold = threshold;
+    g.pos = pos ? pos : h->last_pos;
+    g.ws = reinterpret_cast<double*>(h->kde_ws + o_ws);
+    g.pair_out = pair_out; g.agent_out = agent_out; g.sample_out = sample_out; g.scene_out = scene_out;
+    if (host) {
+        if (pos) {
+            float* dp = reinterpret_cast<float*>(h->kde_ws + o_pos);
+            HIPCHK(h, hipMemcpyAsync(dp, pos, n_pos * 4, hipMemcpyHostToDevice, h->stream));
+            g.pos = dp;
+        }
+        if (pair_out) g.pair_out = reinterpret_cast<float*>(h->kde_ws + o_pr);
+        if (agent_out) g.agent_out = reinterpret_cast<unsigned char*>(h->kde_ws + o_ag);
+        if (sample_out) g.sample_out = reinterpret_cast<float*>(h->kde_ws + o_sm);
+        if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
+    }
+    {
+        ProfScope ps(h, KC_EVAL_STATS);
+        HIPCHK(h, launch_collision_stats(g, h->stream));
+    }
+    if (host) {
+        if (n_pr) HIPCHK(h, hipMemcpyAsync(pair_out, g.pair_out, n_pr * 4, hipMemcpyDeviceToHost, h->stream));
+        if (n_ag) HIPCHK(h, hipMemcpyAsync(agent_out, g.agent_out, n_ag, hipMemcpyDeviceToHost, h->stream));
+        if (n_sm) HIPCHK(h, hipMemcpyAsync(sample_out, g.sample_out, n_sm * 4, hipMemcpyDeviceToHost, h->stream));
+        if (n_sc) HIPCHK(h, hipMemcpyAsync(scene_out, g.scene_out, n_sc * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return order_out(h, mem);

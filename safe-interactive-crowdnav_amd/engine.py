@@ -388,6 +388,37 @@ class JmidEngine:
                                                           ptr(skip), n_cut, cuts, ptr(agent), ptr(cut), ptr(scene), self._mem(dev)))
         return agent, cut, scene
 
+    def collision_statistics(self, pos: Optional[ArrayLike], threshold: float = 0.2,
+                             dims: Optional[Tuple[int, int, int, int]] = None, pairs: bool = False, agents: bool = True):
+        """Collision statistics of joint samples on the device (``jmid_collision_statistics``; calc_min_dists and
+        get_agents_in_collision, MID/models/collision_check_utils.py:58-97).  pos [E, K, A, T, 2] -> (pair [E, K, P] or None,
+        agent [E, K, A] uint8 or None, sample [E, K, 4], scene [E, 5]) with the columns ``metrics.COLLISION_SAMPLE_COLUMNS`` /
+        ``metrics.COLLISION_SCENE_COLUMNS``; ``pairs`` / ``agents`` choose whether the first two are computed.  NumPy in -> NumPy out,
+        CUDA tensors in -> CUDA tensors out.  ``pos=None`` with ``dims=(E, A, K, T)`` takes the positions of the preceding ``denoise``
+        call, which are still in the engine's workspace (host arrays out).  Ground-truth futures: ``gt[:, None]`` (K = 1).
+        K <= 1024, 2 <= T <= 24, A <= 64: ``metrics.collision_statistics_host`` beyond."""
+        if pos is None:
+            if dims is None:
+                raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
+            E, A, K, T = (int(v) for v in dims)
+            dev, bp = False, None
+        else:
+            dev = _is_cuda(pos)
+            E, K, A, T, _ = (int(v) for v in pos.shape)
+            bp = _Buf(pos, dev)
+        shapes = (((E, K, A * (A - 1) // 2), np.float32) if pairs else None, ((E, K, A), np.uint8) if agents else None,
+                  ((E, K, 4), np.float32), ((E, 5), np.float32))
+        if dev:
+            outs = [torch.empty(s[0], dtype=torch.uint8 if s[1] is np.uint8 else torch.float32, device=pos.device) if s else None
+                    for s in shapes]
+            ptrs = [C.c_void_p(o.data_ptr()) if o is not None else None for o in outs]
+        else:
+            outs = [np.empty(s[0], dtype=s[1]) if s else None for s in shapes]
+            ptrs = [C.c_void_p(o.ctypes.data) if o is not None else None for o in outs]
+        self._check(self._lib.jmid_collision_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, float(threshold),
+                                                        *ptrs, self._mem(dev)))
+        return tuple(outs)
+
     # ------------------------------------------------------------------ measurement
     def kernel_classes(self):
         return [self._lib.jmid_kernel_class_name(i).decode() for i in range(self._lib.jmid_kernel_class_count())]

@@ -9,6 +9,10 @@ package does not import scipy - the two routines are restated here in closed for
 The masked form (``eval_statistics_masked_host``, ``summarise_masked``; ``jmid_eval_statistics_masked``) is the ``is_eval_hst`` branch
 of the same function (:540-545, :556-577, :624-715; summarised at MID/mid.py:978-1000, 1051-1075): only the horizon steps whose ground
 truth is real are scored, agents without any are left out, and the fixed-horizon ("one / two / three fourth") columns are added.
+
+The collision statistics (``collision_statistics_host``, ``summarise_collisions``; ``csrc/collision_stats.hpp``,
+``jmid_collision_statistics``) follow MID/models/collision_check_utils.py: ``calc_min_dists`` (:58-80) with ``lineseg_dist`` (:20-55)
+for the clearance of every agent pair of one joint sample, ``get_agents_in_collision`` (:83-97) for the agents that collide.
 """
 from __future__ import annotations
 
@@ -22,6 +26,9 @@ STAT_MASKED_AGENT_COLUMNS = STAT_AGENT_COLUMNS + ("n_valid", "fde_valid")
 STAT_CUTOFF_COLUMNS = ("ade_min", "ade_mean", "ade_ml", "kde", "valid")
 CUTOFF_NAMES = ("one_fourth", "two_fourth", "three_fourth")      # the reference's names of cut-off positions 0, 1, 2
 LOG_PDF_LOWER_BOUND = -20.0      # evaluation.py:203, :271
+COLLISION_SAMPLE_COLUMNS = ("min_dist", "closest_pair", "n_pairs_colliding", "n_agents_colliding")
+COLLISION_SCENE_COLUMNS = ("collision_rate", "agent_collision_rate", "min_dist_min", "min_dist_mean", "min_dist_std")
+COLLISION_THRESHOLD = 0.2        # metres; collision_check_utils.py:88
 
 # the reference's summary keys (mid.py:965-1003) -> the column each one averages
 _SUMMARY_AGENT = {"ade": "ade_min", "fde": "fde_min", "kde": "kde_nll", "ade_most_likely": "ade_ml", "fde_most_likely": "fde_ml",
@@ -256,3 +263,60 @@ def summarise(agent: np.ndarray, scene: np.ndarray) -> Dict[str, float]:
     out.update({k: float(np.mean(scene[:, STAT_SCENE_COLUMNS.index(c)])) for k, c in _SUMMARY_SCENE.items()})
     out["nan_rows"] = int(np.isnan(agent[:, STAT_AGENT_COLUMNS.index("kde_nll")]).sum())
     return out
+
+
+def collision_statistics_host(pos: np.ndarray, threshold: float = COLLISION_THRESHOLD):
+    """pos [E, K, A, T, 2] -> (pair [E, K, P] float64, agent [E, K, A] uint8, sample [E, K, 4] float64, scene [E, 5] float64), the
+    columns ``COLLISION_SAMPLE_COLUMNS`` / ``COLLISION_SCENE_COLUMNS``: what ``JmidEngine.collision_statistics`` computes on the
+    device, without its size limits.  Pairs in ``pdist`` order, P = A (A - 1) / 2; a pair's value is the minimum over the T - 1
+    segments of the distance from the origin to the segment of the relative position (``calc_min_dists`` / ``lineseg_dist``); an
+    agent is flagged when one of its pairs is closer than ``threshold`` (``get_agents_in_collision``).  A = 1: no pairs, ``min_dist``
+    +inf, ``closest_pair`` -1, ``min_dist_std`` NaN.  A non-finite position makes its pairs and the sample's ``min_dist`` NaN
+    (``closest_pair`` -1); NaN pairs never collide.  T >= 2 (with one step the reference collapses to a scalar over all pairs)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    E, K, A, T, _ = pos.shape
+    if T < 2:
+        raise ValueError("the collision statistics need at least two horizon steps")
+    if not (np.isfinite(threshold) and threshold >= 0.0):
+        raise ValueError("the threshold must be finite and >= 0")
+    i, j = np.triu_indices(A, 1)                                       # pdist order
+    P = i.size
+    rel = pos[:, :, i] - pos[:, :, j]                                  # [E, K, P, T, 2]
+    a, b = rel[..., :-1, :], rel[..., 1:, :]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        still = (a == b).all(axis=-1)
+        u = b - a
+        d = u / np.sqrt(u[..., 0] * u[..., 0] + u[..., 1] * u[..., 1])[..., None]
+        s = a[..., 0] * d[..., 0] + a[..., 1] * d[..., 1]
+        t = (-b[..., 0]) * d[..., 0] + (-b[..., 1]) * d[..., 1]
+        h = np.maximum(np.maximum(s, t), 0.0)
+        c = (-a[..., 0]) * d[..., 1] - (-a[..., 1]) * d[..., 0]
+        seg = np.where(still, np.sqrt(a[..., 0] * a[..., 0] + a[..., 1] * a[..., 1]), np.hypot(h, np.abs(c)))
+        seg = np.where(np.isfinite(a).all(axis=-1) & np.isfinite(b).all(axis=-1), seg, np.nan)
+        pair = seg.min(axis=-1)                                        # [E, K, P]; np.min keeps a NaN
+        hit = pair < threshold
+    agent = np.zeros((E, K, A), dtype=np.uint8)
+    for p in range(P):
+        agent[:, :, i[p]] |= hit[:, :, p]
+        agent[:, :, j[p]] |= hit[:, :, p]
+    sample = np.empty((E, K, len(COLLISION_SAMPLE_COLUMNS)))
+    if P:
+        sample[..., 0] = pair.min(axis=-1)
+        sample[..., 1] = np.where(np.isnan(sample[..., 0]), -1, np.argmin(pair, axis=-1))      # the first minimum
+    else:
+        sample[..., 0], sample[..., 1] = np.inf, -1
+    sample[..., 2] = hit.sum(axis=-1)
+    sample[..., 3] = agent.sum(axis=-1)
+    md = sample[..., 0]
+    with np.errstate(invalid="ignore"):
+        scene = np.stack([(sample[..., 2] > 0).mean(axis=1), agent.reshape(E, -1).mean(axis=1), md.min(axis=1), md.mean(axis=1),
+                          md.std(axis=1)], axis=-1)
+    return pair, agent, sample, scene
+
+
+def summarise_collisions(scene: np.ndarray) -> Dict[str, float]:
+    """The means of the scene columns over all episodes: scene [..., 5] -> {column name: mean}.  Plain ``np.mean``: an episode with a
+    NaN column (a non-finite position, or ``min_dist_std`` with A = 1) makes that key NaN."""
+    scene = np.asarray(scene, dtype=np.float64).reshape(-1, len(COLLISION_SCENE_COLUMNS))
+    with np.errstate(invalid="ignore"):
+        return {c: float(np.mean(scene[:, k])) for k, c in enumerate(COLLISION_SCENE_COLUMNS)}
