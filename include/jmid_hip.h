@@ -294,6 +294,47 @@ int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* p
 int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask,
                  const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out);
 
+/* The scene batch on the device: track positions on the time_step grid in, the encoder's inputs left resident on the handle - what the
+ * reference does between update_state_hists and Trajectron.get_latent (mid_sim_wrapper.py:313-437, MID/dataset/preprocessing.py:428-620,
+ * MID/environment/scene_graph.py:111-250, the neighbour reductions of MID/models/encoders/mgcvae.py:726-768) for E independent episodes.
+ * With this entry a C caller goes from positions to forecasts: build -> draw x_T [E, K * n_in, T, 2] -> jmid_predict_scene.
+ *   human_xy  [E, F, N, 2] doubles  pedestrian positions, oldest frame first; F = the handle's hist_len (>= 3), 1 <= N <= 63
+ *   robot_xy  [E, F, 2] doubles     robot positions on the same frames
+ *   time_step the grid spacing in seconds (velocities and accelerations are first differences divided by it)
+ *   force_all_in_cluster  0: the reference's choice - the pedestrians within 3 m (at the last frame) of the pedestrian whose cluster mean
+ *             lies nearest the robot go through the network; non-zero: every pedestrian (and the robot) does
+ *   in_cluster_out        [E, N] bytes, 1 = the pedestrian is in the chosen cluster
+ *   robot_in_cluster_out  [E] bytes
+ *   n_in_out  [E] ints    pedestrians in the cluster: the A of the jmid_predict_scene call, and what sizes its x_T
+ *   cv_out    [E, N, horizon, 2] doubles or NULL: the constant-velocity forecasts of EVERY pedestrian - what the reference returns for the
+ *             ones outside the cluster (mid_sim_wrapper.py:413-429); 1 <= horizon <= 24 (horizon is ignored when cv_out is NULL)
+ * Left on the handle, in the padded layout that gives every pedestrian a row (jmid_scene_get copies them out): x and x_st [E, N, F, 6],
+ * nbr_sum [E, N, 2, F, 6], edge_mask [E, N, 2], p0 [E, N, 2], all fp32.  A row outside the cluster is computed as a node without neighbours.
+ * The edge mask of a row is min(sum of its edge scaling values, 1) for BOTH edge types: the reference does not filter the edge values by
+ * type (scene_graph.py:293-299), reproduced.
+ * fp64 wherever the reference computes in float64, fp32 exactly where it casts, the neighbour sums in node order, no FMA contraction: the
+ * rows are bit-identical to the reference's batch tensors.  The one freedom is the cluster means: the members are summed in ascending
+ * track id here and by a BLAS product there, so a scene whose two best clusters of DIFFERENT membership lie within rounding of the same
+ * distance from the robot may choose the other one.
+ * The call synchronises (the caller needs n_in to draw x_T).  The scene stays resident until the next jmid_build_scene on the handle; no
+ * other entry point touches it.  JMID_EINVAL (the resident scene, if any, is kept): F != hist_len, F < 3, N < 1, N > 63, horizon outside
+ * 1..24 with cv_out, time_step not finite and positive. */
+int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, double time_step, int horizon,
+                     int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem);
+
+/* Copies of the arrays jmid_build_scene left on the handle, in its padded layout: x, x_st [E, N, F, 6], nbr_sum [E, N, 2, F, 6],
+ * edge_mask [E, N, 2], p0 [E, N, 2].  NULL arguments are skipped.  JMID_EINVAL without a preceding jmid_build_scene. */
+int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float* edge_mask, float* p0, int mem);
+
+/* jmid_predict on the resident scene: the in-cluster rows are gathered on the device in ascending track id, then encoder -> denoise loop ->
+ * integrator -> top-k run chained on the stream exactly as in jmid_predict (the same kernels on the same values: the outputs are
+ * bit-identical to jmid_predict fed those rows).  Host buffers: x_T [E, K*A, T, 2], bw / sel / logw / pos_out as jmid_predict.
+ * JMID_EINVAL when no scene is resident, when E differs from the build's, or when any episode's in-cluster count is not A (group the
+ * episodes of a batch by their count, one jmid_build_scene + jmid_predict_scene per group); otherwise the limits and status codes of
+ * jmid_predict, JMID_ERANGE and JMID_ETIMEOUT included (the scene stays resident: jmid_scene_get feeds the staged repeat). */
+int jmid_predict_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
+                       float* sel, float* logw, float* pos_out);
+
 /* The stream (a hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream; NULL = the legacy default
  * stream) that produces the inputs and consumes the outputs of this handle's JMID_MEM_DEVICE calls - see Conventions. */
 int jmid_set_caller_stream(jmid_handle_t h, void* stream);

@@ -56,6 +56,98 @@ int topk_on_device(jmid_ctx* h, int E, int A, int K, int T, int k, const float* 
     return 0;
 }
 
+// the pinned host staging buffer of the chained calls (jmid_predict, jmid_predict_scene, jmid_build_scene), grown on demand
+int ensure_pin(jmid_ctx* h, size_t need, const char* who) {
+    if (need <= h->pin_bytes) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->pin) HIPCHK(h, hipHostFree(h->pin));
+    h->pin = nullptr;
+    h->pin_bytes = 0;
+    if (hipHostMalloc((void**)&h->pin, need, hipHostMallocDefault) != hipSuccess) return fail(h, JMID_ENOMEM, std::string(who) + ": pinned staging allocation failed");
+    h->pin_bytes = need;
+    return 0;
+}
+
+// jmid_predict and jmid_predict_scene after their argument checks: one upload, encoder -> denoise loop -> integrator -> top-k chained on
+// the stream, one download.  scene = false: the five inputs are host arrays.  scene = true: x_st, nbr_sum, edge_mask and p0 are null and
+// the in-cluster rows of the resident scene are gathered on the device instead (x_T and bw are the whole upload).
+int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask, const float* x_T,
+                  const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out, bool scene, const char* who) {
+    const bool rank = k < K;
+    const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
+    const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
+    const size_t n_sel = rank ? n * k * T * 2 : 0, n_lw = rank ? n * k : 0, n_pos = pos_out ? n_xT : 0;
+    auto up = [](size_t floats) { return (floats + 63) / 64 * 64; };
+    // upload block | ctx | download block (flag, sel, logw, pos)
+    const size_t o_xs = 0, o_nb = o_xs + up(n_xs), o_em = o_nb + up(n_nb), o_xT = o_em + up(n_em), o_p0 = o_xT + up(n_xT), o_bw = o_p0 + up(n_p0),
+                 in_floats = o_bw + up(n_bw), o_ctx = in_floats, o_out = o_ctx + up(n * H2), o_flag = o_out, o_sel = o_flag + 64, o_lw = o_sel + up(n_sel),
+                 o_pos = o_lw + up(n_lw), total = o_pos + up(n_pos), out_floats = total - o_out;
+    if (total * 4 > h->io_dev_bytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->io_dev) HIPCHK(h, hipFree(h->io_dev));
+        h->io_dev = nullptr;
+        h->io_dev_bytes = 0;
+        if (hipMalloc((void**)&h->io_dev, total * 4) != hipSuccess) return fail(h, JMID_ENOMEM, std::string(who) + ": device staging allocation failed");
+        h->io_dev_bytes = total * 4;
+    }
+    if (int rc = ensure_pin(h, (in_floats + out_floats) * 4, who)) return rc;
+    float* pin = reinterpret_cast<float*>(h->pin);
+    float* dev = reinterpret_cast<float*>(h->io_dev);
+    std::memcpy(pin + o_xT, x_T, n_xT * 4);
+    if (n_bw) std::memcpy(pin + o_bw, bw, n_bw * 4);
+    if (!scene) {
+        std::memcpy(pin + o_xs, x_st, n_xs * 4);
+        std::memcpy(pin + o_nb, nbr_sum, n_nb * 4);
+        std::memcpy(pin + o_em, edge_mask, n_em * 4);
+        std::memcpy(pin + o_p0, p0, n_p0 * 4);
+        HIPCHK(h, hipMemcpyAsync(dev, pin, in_floats * 4, hipMemcpyHostToDevice, h->stream));
+    } else {
+        // x_T ... bw in one copy (the p0 slot between them is written by the gather below, after the copy on the stream)
+        HIPCHK(h, hipMemcpyAsync(dev + o_xT, pin + o_xT, (in_floats - o_xT) * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    int rc = 0;
+    h->chained = true;
+    {
+        ProfScope ps(h, KC_ENCODER);
+        if (scene) {
+            const jmid_ctx::SceneWs& sc = h->scene;
+            SceneGatherArgs ga{};
+            ga.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev + sc.o_inc);
+            ga.x_st = reinterpret_cast<const float*>(sc.dev + sc.o_xst); ga.nbr_sum = reinterpret_cast<const float*>(sc.dev + sc.o_nbr);
+            ga.edge_mask = reinterpret_cast<const float*>(sc.dev + sc.o_em); ga.p0 = reinterpret_cast<const float*>(sc.dev + sc.o_p0);
+            ga.o_x_st = dev + o_xs; ga.o_nbr_sum = dev + o_nb; ga.o_edge_mask = dev + o_em; ga.o_p0 = dev + o_p0;
+            ga.E = E; ga.N = sc.N; ga.A = A; ga.F = (int)Th;
+            if (launch_scene_gather(ga, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": scene gather launch failed");
+        }
+        EncArgs ea{};
+        ea.x_st = dev + o_xs; ea.nbr_sum = dev + o_nb; ea.edge_mask = dev + o_em;
+        ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
+        ea.edge[0] = LstmW{h->lstmT[1][0], h->lstmT[1][1], h->lstmT[1][2]};
+        ea.edge[1] = LstmW{h->lstmT[2][0], h->lstmT[2][1], h->lstmT[2][2]};
+        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = h->wt.edge_v;
+        ea.ctx = dev + o_ctx; ea.n = (int)n; ea.Th = (int)Th; ea.H = h->H;
+        if (!rc && launch_encoder(ea, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": encoder launch failed");
+    }
+    if (!rc) rc = run_network(h, E, A, K, T, dev + o_xT, dev + o_ctx, dev + o_p0, dt, precision, -1, nullptr, pos_out ? dev + o_pos : nullptr,
+                              nullptr, JMID_MEM_DEVICE);
+    if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw);
+    h->chained = false;
+    if (rc) return rc;
+    const bool flagged = precision != JMID_PREC_F32;
+    if (flagged) HIPCHK(h, hipMemcpyAsync(dev + o_flag, h->range_flag, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    float* pout = pin + in_floats;
+    HIPCHK(h, hipMemcpyAsync(pout, dev + o_out, out_floats * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (flagged && *reinterpret_cast<const int*>(pout + (o_flag - o_out)))
+        return jmid_host::flagged_call(h, *reinterpret_cast<const int*>(pout + (o_flag - o_out)));
+    if (rank) {
+        std::memcpy(sel, pout + (o_sel - o_out), n_sel * 4);
+        std::memcpy(logw, pout + (o_lw - o_out), n_lw * 4);
+    }
+    if (pos_out) std::memcpy(pos_out, pout + (o_pos - o_out), n_pos * 4);
+    return JMID_OK;
+}
+
 }  // namespace jmid_host
 
 // ================================================================================================ C ABI
@@ -154,6 +246,7 @@ int jmid_destroy(jmid_handle_t h) {
             if (p) hipFree(p);
     if (h->arena) hipFree(h->arena);
     if (h->kde_ws) hipFree(h->kde_ws);
+    if (h->scene.dev) hipFree(h->scene.dev);
     for (int c = 0; c < KC_COUNT; ++c)
         for (auto& ev : h->prof_ev[c]) {
             hipEventDestroy(ev.a);
@@ -484,71 +577,117 @@ int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float
     if (rank && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, "jmid_predict: the device top-k supports A <= 32, K <= 1024, T <= 24");
     if (h->ddpm) return fail(h, JMID_EINVAL, "jmid_predict samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
-    const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
-    const size_t n_sel = rank ? n * k * T * 2 : 0, n_lw = rank ? n * k : 0, n_pos = pos_out ? n_xT : 0;
-    auto up = [](size_t floats) { return (floats + 63) / 64 * 64; };
-    // upload block | ctx | download block (flag, sel, logw, pos)
-    const size_t o_xs = 0, o_nb = o_xs + up(n_xs), o_em = o_nb + up(n_nb), o_xT = o_em + up(n_em), o_p0 = o_xT + up(n_xT), o_bw = o_p0 + up(n_p0),
-                 in_floats = o_bw + up(n_bw), o_ctx = in_floats, o_out = o_ctx + up(n * H2), o_flag = o_out, o_sel = o_flag + 64, o_lw = o_sel + up(n_sel),
-                 o_pos = o_lw + up(n_lw), total = o_pos + up(n_pos), out_floats = total - o_out;
-    if (total * 4 > h->io_dev_bytes) {
+    return predict_chain(h, E, A, K, T, k, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out, false, "jmid_predict");
+}
+
+int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, double time_step, int horizon,
+                     int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (E <= 0 || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out) return fail(h, JMID_EINVAL, "jmid_build_scene: bad argument");
+    if (F != h->hist_len || F < 3 || F > SCN_MAX_F) return fail(h, JMID_EINVAL, "jmid_build_scene: F must be the handle's hist_len, and at least 3");
+    if (N < 1 || N > SCN_LANES - 1) return fail(h, JMID_EINVAL, "jmid_build_scene supports 1 <= N <= 63 pedestrians");
+    if (cv_out && (horizon < 1 || horizon > SCN_MAX_H)) return fail(h, JMID_EINVAL, "jmid_build_scene: the horizon of cv_out must be in 1..24");
+    if (!(time_step > 0.0) || !std::isfinite(time_step)) return fail(h, JMID_EINVAL, "jmid_build_scene: time_step must be finite and > 0");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = order_in(h, mem)) return rc;
+    const bool host = mem == JMID_MEM_HOST;
+    const size_t rows = (size_t)E * N, b_hum = rows * F * 2 * 8, b_rob = (size_t)E * F * 2 * 8, b_cv = cv_out ? rows * horizon * 2 * 8 : 0;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // staged inputs (host mode) | the resident arrays | the download block: n_in, in_cluster, robot_in_cluster, cv
+    const size_t o_hum = 0, o_rob = o_hum + (host ? up(b_hum) : 0), o_x = o_rob + (host ? up(b_rob) : 0), o_xst = o_x + up(rows * F * 6 * 4),
+                 o_nbr = o_xst + up(rows * F * 6 * 4), o_em = o_nbr + up(rows * 2 * F * 6 * 4), o_p0 = o_em + up(rows * 2 * 4), o_nin = o_p0 + up(rows * 2 * 4),
+                 o_inc = o_nin + up((size_t)E * 4), o_rin = o_inc + up(rows), o_cv = o_rin + up((size_t)E), need = o_cv + up(b_cv), b_out = need - o_nin;
+    jmid_ctx::SceneWs& sc = h->scene;
+    sc.E = 0;                     // no scene is resident until this call has succeeded
+    if (need > sc.bytes) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->io_dev) HIPCHK(h, hipFree(h->io_dev));
-        h->io_dev = nullptr;
-        h->io_dev_bytes = 0;
-        if (hipMalloc((void**)&h->io_dev, total * 4) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_predict: device staging allocation failed");
-        h->io_dev_bytes = total * 4;
+        if (sc.dev) HIPCHK(h, hipFree(sc.dev));
+        sc.dev = nullptr;
+        sc.bytes = 0;
+        if (hipMalloc((void**)&sc.dev, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_build_scene: workspace allocation failed");
+        sc.bytes = need;
     }
-    const size_t pin_need = (in_floats + out_floats) * 4;
-    if (pin_need > h->pin_bytes) {
+    SceneArgs g{};
+    g.E = E; g.N = N; g.F = F; g.horizon = horizon; g.force_all = force_all_in_cluster ? 1 : 0;
+    g.dt = time_step;
+    g.human_xy = human_xy; g.robot_xy = robot_xy;
+    g.x = reinterpret_cast<float*>(sc.dev + o_x); g.x_st = reinterpret_cast<float*>(sc.dev + o_xst);
+    g.nbr_sum = reinterpret_cast<float*>(sc.dev + o_nbr); g.edge_mask = reinterpret_cast<float*>(sc.dev + o_em);
+    g.p0 = reinterpret_cast<float*>(sc.dev + o_p0);
+    g.n_in = reinterpret_cast<int*>(sc.dev + o_nin);
+    g.in_cluster = reinterpret_cast<unsigned char*>(sc.dev + o_inc);
+    g.robot_in = reinterpret_cast<unsigned char*>(sc.dev + o_rin);
+    g.cv = cv_out ? reinterpret_cast<double*>(sc.dev + o_cv) : nullptr;
+    if (int rc = ensure_pin(h, host ? o_x + b_out : (size_t)E * 4, "jmid_build_scene")) return rc;
+    if (host) {
+        std::memcpy(h->pin + o_hum, human_xy, b_hum);
+        std::memcpy(h->pin + o_rob, robot_xy, b_rob);
+        HIPCHK(h, hipMemcpyAsync(sc.dev, h->pin, o_x, hipMemcpyHostToDevice, h->stream));
+        g.human_xy = reinterpret_cast<const double*>(sc.dev + o_hum);
+        g.robot_xy = reinterpret_cast<const double*>(sc.dev + o_rob);
+    }
+    HIPCHK(h, launch_scene(g, h->stream));
+    sc.n_in.resize(E);
+    if (host) {
+        char* pout = h->pin + o_x;
+        HIPCHK(h, hipMemcpyAsync(pout, sc.dev + o_nin, b_out, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->pin) HIPCHK(h, hipHostFree(h->pin));
-        h->pin = nullptr;
-        h->pin_bytes = 0;
-        if (hipHostMalloc((void**)&h->pin, pin_need, hipHostMallocDefault) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_predict: pinned staging allocation failed");
-        h->pin_bytes = pin_need;
+        std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
+        std::memcpy(n_in_out, pout, (size_t)E * 4);
+        std::memcpy(in_cluster_out, pout + (o_inc - o_nin), rows);
+        std::memcpy(robot_in_cluster_out, pout + (o_rin - o_nin), (size_t)E);
+        if (cv_out) std::memcpy(cv_out, pout + (o_cv - o_nin), b_cv);
+    } else {
+        HIPCHK(h, hipMemcpyAsync(h->pin, g.n_in, (size_t)E * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(n_in_out, g.n_in, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(in_cluster_out, g.in_cluster, rows, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(robot_in_cluster_out, g.robot_in, (size_t)E, hipMemcpyDeviceToDevice, h->stream));
+        if (cv_out) HIPCHK(h, hipMemcpyAsync(cv_out, g.cv, b_cv, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::memcpy(sc.n_in.data(), h->pin, (size_t)E * 4);
     }
-    float* pin = reinterpret_cast<float*>(h->pin);
-    float* dev = reinterpret_cast<float*>(h->io_dev);
-    std::memcpy(pin + o_xs, x_st, n_xs * 4);
-    std::memcpy(pin + o_nb, nbr_sum, n_nb * 4);
-    std::memcpy(pin + o_em, edge_mask, n_em * 4);
-    std::memcpy(pin + o_xT, x_T, n_xT * 4);
-    std::memcpy(pin + o_p0, p0, n_p0 * 4);
-    if (n_bw) std::memcpy(pin + o_bw, bw, n_bw * 4);
-    HIPCHK(h, hipMemcpyAsync(dev, pin, in_floats * 4, hipMemcpyHostToDevice, h->stream));
-    int rc = 0;
-    h->chained = true;
-    {
-        ProfScope ps(h, KC_ENCODER);
-        EncArgs ea{};
-        ea.x_st = dev + o_xs; ea.nbr_sum = dev + o_nb; ea.edge_mask = dev + o_em;
-        ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
-        ea.edge[0] = LstmW{h->lstmT[1][0], h->lstmT[1][1], h->lstmT[1][2]};
-        ea.edge[1] = LstmW{h->lstmT[2][0], h->lstmT[2][1], h->lstmT[2][2]};
-        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = h->wt.edge_v;
-        ea.ctx = dev + o_ctx; ea.n = (int)n; ea.Th = (int)Th; ea.H = h->H;
-        if (launch_encoder(ea, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, "jmid_predict: encoder launch failed");
-    }
-    if (!rc) rc = run_network(h, E, A, K, T, dev + o_xT, dev + o_ctx, dev + o_p0, dt, precision, -1, nullptr, pos_out ? dev + o_pos : nullptr,
-                              nullptr, JMID_MEM_DEVICE);
-    if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw);
-    h->chained = false;
-    if (rc) return rc;
-    const bool flagged = precision != JMID_PREC_F32;
-    if (flagged) HIPCHK(h, hipMemcpyAsync(dev + o_flag, h->range_flag, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-    float* pout = pin + in_floats;
-    HIPCHK(h, hipMemcpyAsync(pout, dev + o_out, out_floats * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (flagged && *reinterpret_cast<const int*>(pout + (o_flag - o_out)))
-        return jmid_host::flagged_call(h, *reinterpret_cast<const int*>(pout + (o_flag - o_out)));
-    if (rank) {
-        std::memcpy(sel, pout + (o_sel - o_out), n_sel * 4);
-        std::memcpy(logw, pout + (o_lw - o_out), n_lw * 4);
-    }
-    if (pos_out) std::memcpy(pos_out, pout + (o_pos - o_out), n_pos * 4);
-    return JMID_OK;
+    sc.o_x = o_x; sc.o_xst = o_xst; sc.o_nbr = o_nbr; sc.o_em = o_em; sc.o_p0 = o_p0; sc.o_inc = o_inc;
+    sc.E = E; sc.N = N;
+    return order_out(h, mem);
+}
+
+int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float* edge_mask, float* p0, int mem) {
+    if (!h) return JMID_EINVAL;
+    const jmid_ctx::SceneWs& sc = h->scene;
+    if (!sc.E) return fail(h, JMID_EINVAL, "jmid_scene_get needs a preceding jmid_build_scene on this handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = order_in(h, mem)) return rc;
+    const size_t rows = (size_t)sc.E * sc.N, F = h->hist_len;
+    const hipMemcpyKind kind = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (x) HIPCHK(h, hipMemcpyAsync(x, sc.dev + sc.o_x, rows * F * 6 * 4, kind, h->stream));
+    if (x_st) HIPCHK(h, hipMemcpyAsync(x_st, sc.dev + sc.o_xst, rows * F * 6 * 4, kind, h->stream));
+    if (nbr_sum) HIPCHK(h, hipMemcpyAsync(nbr_sum, sc.dev + sc.o_nbr, rows * 2 * F * 6 * 4, kind, h->stream));
+    if (edge_mask) HIPCHK(h, hipMemcpyAsync(edge_mask, sc.dev + sc.o_em, rows * 2 * 4, kind, h->stream));
+    if (p0) HIPCHK(h, hipMemcpyAsync(p0, sc.dev + sc.o_p0, rows * 2 * 4, kind, h->stream));
+    if (mem == JMID_MEM_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return order_out(h, mem);
+}
+
+int jmid_predict_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw, float* sel,
+                       float* logw, float* pos_out) {
+    if (!h) return JMID_EINVAL;
+    if (int rc = check_ready(h)) return rc;
+    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, "jmid_predict_scene: bad dimensions");
+    if (!x_T) return fail(h, JMID_EINVAL, "jmid_predict_scene: null input");
+    const jmid_ctx::SceneWs& sc = h->scene;
+    if (!sc.E) return fail(h, JMID_EINVAL, "jmid_predict_scene needs a preceding jmid_build_scene on this handle");
+    if (E != sc.E) return fail(h, JMID_EINVAL, "jmid_predict_scene: E differs from the resident scene's");
+    for (int e = 0; e < E; ++e)
+        if (sc.n_in[e] != A)
+            return fail(h, JMID_EINVAL, "jmid_predict_scene: episode " + std::to_string(e) + " has " + std::to_string(sc.n_in[e]) +
+                                            " in-cluster pedestrians, not A = " + std::to_string(A) + " (group the episodes by their count)");
+    const bool rank = k < K;
+    if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, "jmid_predict_scene: k < K needs sel and logw");
+    if (!rank && !pos_out) return fail(h, JMID_EINVAL, "jmid_predict_scene: k == K needs pos_out");
+    if (rank && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, "jmid_predict_scene: the device top-k supports A <= 32, K <= 1024, T <= 24");
+    if (h->ddpm) return fail(h, JMID_EINVAL, "jmid_predict_scene samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, true, "jmid_predict_scene");
 }
 
 int jmid_set_chunk_episodes(jmid_handle_t h, int episodes) {

@@ -31,6 +31,7 @@
 #include "gemm_f32.hpp"
 #include "kde.hpp"
 #include "launch_plan.hpp"
+#include "scene.hpp"
 
 using namespace jmid;
 
@@ -124,6 +125,15 @@ struct jmid_ctx {
     size_t pin_bytes = 0;
     char* io_dev = nullptr;
     size_t io_dev_bytes = 0;
+    // jmid_build_scene: the scene batch it left on the device (padded [E, N, ...] rows; jmid_scene_get copies them out, jmid_predict_scene
+    // gathers the in-cluster rows), in a workspace of its own - no other entry point touches it
+    struct SceneWs {
+        char* dev = nullptr;
+        size_t bytes = 0;
+        int E = 0, N = 0;            // E = 0: no scene is resident
+        size_t o_x = 0, o_xst = 0, o_nbr = 0, o_em = 0, o_p0 = 0, o_inc = 0;   // byte offsets of the resident arrays
+        std::vector<int> n_in;       // [E] in-cluster pedestrians per episode (host copy)
+    } scene;
     bool chained = false;       // the running run_network is a stage of jmid_predict: no caller-stream ordering, no flag round trip
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)

@@ -270,6 +270,74 @@ class JmidEngine:
                                            None, None, None, C.c_void_p(pos.ctypes.data))
         return pos, None
 
+    def build_scene(self, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: Optional[int] = None,
+                    force_all_in_cluster: bool = False) -> Dict[str, np.ndarray]:
+        """The scene batch on the device (``jmid_build_scene``; the device twin of ``scene.build_scenes_batched``): human_xy [E, F, N, 2]
+        and robot_xy [E, F, 2] float64 on the ``time_step`` grid, oldest first - or [F, N, 2] and [F, 2] for one scene, whose results
+        then come without the episode axis.  The encoder inputs stay on the device (``scene_arrays`` copies them out, ``predict_scene``
+        runs the predictor on them); returned are ``in_cluster`` [E, N] bool, ``robot_in_cluster`` [E] bool, ``n_in`` [E] int32 and
+        ``cv`` [E, N, horizon, 2] float64 (None without ``horizon``)."""
+        hum = np.ascontiguousarray(human_xy, dtype=np.float64)
+        rob = np.ascontiguousarray(robot_xy, dtype=np.float64)
+        single = hum.ndim == 3
+        if single:
+            hum, rob = hum[None], rob[None]
+        if hum.ndim != 4 or hum.shape[-1] != 2 or rob.shape != (hum.shape[0], hum.shape[1], 2):
+            raise ValueError("expected human_xy [E, F, N, 2] and robot_xy [E, F, 2] (or one scene without the episode axis)")
+        E, F, N, _ = (int(v) for v in hum.shape)
+        inc = np.empty((E, N), dtype=np.uint8)
+        rin = np.empty(E, dtype=np.uint8)
+        n_in = np.empty(E, dtype=np.int32)
+        cv = np.empty((E, N, int(horizon), 2), dtype=np.float64) if horizon is not None else None
+        self._check(self._lib.jmid_build_scene(self._h, E, N, F, C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data), float(time_step),
+                                               int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
+                                               C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
+                                               C.c_void_p(cv.ctypes.data) if cv is not None else None, _lib.MEM_HOST))
+        self._scene_shape, self._scene_n_in = (E, N, F, single), n_in
+        out = {"in_cluster": inc.astype(bool), "robot_in_cluster": rin.astype(bool), "n_in": n_in, "cv": cv}
+        return {k: (v[0] if single and v is not None else v) for k, v in out.items()}
+
+    def scene_arrays(self) -> Dict[str, np.ndarray]:
+        """The arrays the preceding ``build_scene`` left on the device, under the keys of ``scene.build_scenes_batched``: x, x_st
+        [E, N, F, 6], nbr_sum [E, N, 2, F, 6], edge_mask [E, N, 2], p0 [E, N, 2] float32 (``jmid_scene_get``; every pedestrian has a row).
+        After a one-scene ``build_scene`` the episode axis is absent."""
+        shape = getattr(self, "_scene_shape", None)
+        E, N, F, single = shape if shape is not None else (0, 0, self.hist_len, False)      # (no build: the library says so)
+        out = {"x": np.empty((E, N, F, 6), np.float32), "x_st": np.empty((E, N, F, 6), np.float32),
+               "nbr_sum": np.empty((E, N, 2, F, 6), np.float32), "edge_mask": np.empty((E, N, 2), np.float32),
+               "p0": np.empty((E, N, 2), np.float32)}
+        self._check(self._lib.jmid_scene_get(self._h, *[C.c_void_p(a.ctypes.data) for a in out.values()], _lib.MEM_HOST))
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def predict_scene(self, x_T: np.ndarray, k: int, dt: float = 0.25, precision: str = "f32"):
+        """``predict`` on the scene the preceding ``build_scene`` left on the device (``jmid_predict_scene``): x_T [E, K*A, T, 2] with A the
+        in-cluster count of EVERY episode (``n_in``) and ``k`` kept futures of the K.  k < K -> (kept [E, A, k, T, 2], log-weights
+        [E, A, k]); k == K -> (pos [E, K, A, T, 2], None).  The same bits as ``predict`` fed the in-cluster rows of ``scene_arrays``."""
+        import math
+        x_T = np.asarray(x_T)
+        if x_T.ndim != 4 or x_T.shape[-1] != 2:
+            raise ValueError("expected x_T [E, K*A, T, 2]")
+        E, KA, T, _ = (int(v) for v in x_T.shape)
+        k = int(k)
+        # A = the first episode's count (the library refuses the call when another episode's differs, or when nothing is resident)
+        n_in = getattr(self, "_scene_n_in", None)
+        A = int(n_in[0]) if n_in is not None and len(n_in) and n_in[0] > 0 else 1
+        if KA % A != 0:
+            raise ValueError(f"x_T has {KA} rows per episode: not a multiple of the scene's {A} in-cluster pedestrians")
+        K = KA // A
+        bx = _Buf(x_T, False)
+        if k < K:
+            bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
+            sel = np.empty((E, A, k, T, 2), dtype=np.float32)
+            lw = np.empty((E, A, k), dtype=np.float32)
+            self._compute(self._lib.jmid_predict_scene, self._h, E, A, K, T, k, bx.ptr, float(dt), _lib.PRECISIONS[precision],
+                          C.c_void_p(bw.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data), None)
+            return sel, lw
+        pos = np.empty((E, K, A, T, 2), dtype=np.float32)
+        self._compute(self._lib.jmid_predict_scene, self._h, E, A, K, T, k, bx.ptr, float(dt), _lib.PRECISIONS[precision], None, None, None,
+                      C.c_void_p(pos.ctypes.data))
+        return pos, None
+
     def net_eval(self, x: ArrayLike, ctx: ArrayLike, step_idx: int = 0, precision: str = "f32"):
         """One evaluation of e_theta for DDIM table entry ``step_idx``; x [E, K*A, T, 2] -> e same shape."""
         dev = _is_cuda(x)

@@ -65,7 +65,8 @@ _CACHE_LOCK = Lock()            # guards the three caches above (forecasters may
 ERANGE_FALLBACKS = 0            # calls of this process that were repeated in "f32" after JMID_ERANGE
 SELF_CHECK_DOWNGRADES = 0       # instances whose opt-in precision was replaced by "f16x3" by the first-call self check
 # what HumanTrajectoryForecasterSim's keyword arguments default to (safe_interactive_crowdnav_amd.install(**defaults) edits it)
-DEFAULTS = {"device_id": 0, "precision": "f16mx", "rng_compat": "auto", "self_check": True, "device_topk": True}
+DEFAULTS = {"device_id": 0, "precision": "f16mx", "rng_compat": "auto", "self_check": True, "device_topk": True,
+            "device_scene": False}
 
 
 _PHILOX_STEP: Dict[Tuple[int, Tuple[int, ...]], int] = {}     # (device, shape) -> what one randn_like of that shape adds to the Philox offset
@@ -165,7 +166,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
     def __init__(self, env_config=None, mid_config_file=None, *, weights: Optional[JMIDWeights] = None,
                  device_id: Optional[int] = None, precision: Optional[str] = None, rng_compat: Optional[str] = None,
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
-                 lib_path: Optional[str] = None):
+                 lib_path: Optional[str] = None, device_scene: Optional[bool] = None):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -174,12 +175,16 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         rng_compat = DEFAULTS["rng_compat"] if rng_compat is None else rng_compat
         self_check = DEFAULTS["self_check"] if self_check is None else self_check
         device_topk = DEFAULTS["device_topk"] if device_topk is None else device_topk
+        device_scene = DEFAULTS["device_scene"] if device_scene is None else device_scene
         self.init_super(env_config)
         self.precision = precision
         self.self_check = bool(self_check) and precision in ("f16mx", "f16x2")
         self.self_check_tol = float(self_check_tol)
         self._checked_shapes = set()
         self.device_topk = bool(device_topk)
+        # True: the scene batch (cluster choice, states, scene graph, neighbour sums) is built on the device (jmid_build_scene) and the
+        # predictor runs on it where it lies (jmid_predict_scene); the history table stays on the host either way
+        self.device_scene = bool(device_scene)
         self.erange_fallbacks = 0
         self.timings: Dict[str, float] = {}     # ms of the last predict_ret_best(): scene, device, topk, assemble
         if rng_compat not in ("auto", "cpu", "cuda"):
@@ -272,11 +277,25 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
 
     def predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
         """mid_sim_wrapper.py:482-510 -> (forecasts [N, k, H+1, 2] float64, log-weights [N, k] float64)."""
+        if not self.device_scene:
+            return self._predict_ret_best()
+        with self._engine_lock:     # the engine holds ONE resident scene: nobody else builds between this call's build and its predict
+            return self._predict_ret_best()
+
+    def _predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
         t0 = time.perf_counter()
         prev, rob = self._snapshot()
         hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, self.num_hist_frames)
-        sb = SC.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon, self.num_hist_frames)
-        A, K, H, k = len(sb.ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
+        if self.device_scene:
+            if hum_xy.shape[0] < self.num_hist_frames:
+                raise SC.HistoryTooShortError(f"{hum_xy.shape[0]} history frames available, {self.num_hist_frames} needed")
+            ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon)
+            sb = None
+            ids_in, ids_out = np.nonzero(ds["in_cluster"])[0], np.nonzero(~ds["in_cluster"])[0]
+        else:
+            sb = SC.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon, self.num_hist_frames)
+            ids_in, ids_out = sb.ids_in, sb.ids_out
+        A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
         # RNG contract (module docstring): x_T is the first draw of the CPU default generator; the per-step z of the
         # reference (unused by DDIM) comes from the generator of the device the reference would run on
         x_T = torch.randn([K * A, H, 2])
@@ -301,8 +320,11 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 # the whole call in ONE library entry (jmid_predict: encoder -> denoise -> integrator -> top-k chained on the
                 # stream, one upload, one download); JMID_ERANGE -> the staged path below in exact fp32
                 try:
-                    out, lw = self.engine.predict(sb.x_st, sb.nbr_sum, sb.edge_mask, x_np, sb.p0[None], k, dt=self.time_step,
-                                                  precision=self.precision)
+                    if sb is None:
+                        out, lw = self.engine.predict_scene(x_np, k, dt=self.time_step, precision=self.precision)
+                    else:
+                        out, lw = self.engine.predict(sb.x_st, sb.nbr_sum, sb.edge_mask, x_np, sb.p0[None], k, dt=self.time_step,
+                                                      precision=self.precision)
                     if on_dev:
                         in_cluster, logw_in = out[0], lw[0].astype(np.float64)
                     else:
@@ -313,10 +335,15 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                     if e.code != -5 or self.precision == "f32":                   # JMID_ERANGE
                         raise
             if in_cluster is None:
-                ctx = self.engine.encode(sb.x_st, sb.nbr_sum, sb.edge_mask)
-                pos = self._denoise(x_np, ctx[None], sb.p0[None], want_pos=not on_dev or check)
+                if sb is None:   # the self-check call and the JMID_ERANGE repeat take their inputs from the resident scene
+                    sa = self.engine.scene_arrays()
+                    sx_st, snbr, sem, sp0 = (np.ascontiguousarray(sa[key][ids_in]) for key in ("x_st", "nbr_sum", "edge_mask", "p0"))
+                else:
+                    sx_st, snbr, sem, sp0 = sb.x_st, sb.nbr_sum, sb.edge_mask, sb.p0
+                ctx = self.engine.encode(sx_st, snbr, sem)
+                pos = self._denoise(x_np, ctx[None], sp0[None], want_pos=not on_dev or check)
                 if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
-                    pos = self._self_check(x_np, ctx[None], sb.p0[None], pos)
+                    pos = self._self_check(x_np, ctx[None], sp0[None], pos)
                 t2 = time.perf_counter()
                 if on_dev:
                     # joint-KDE top-k on the device (jmid_topk) over the positions the denoise call left in the workspace
@@ -331,10 +358,10 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         t3 = time.perf_counter()
         forecasts = np.zeros((self.num_hums, k, H, 2), dtype=np.float64)
         logw = np.zeros((self.num_hums, k), dtype=np.float64)
-        forecasts[sb.ids_in] = in_cluster
-        logw[sb.ids_in] = logw_in
-        for i in sb.ids_out:
-            forecasts[i] = sb.cv_forecasts[int(i)][np.newaxis]
+        forecasts[ids_in] = in_cluster
+        logw[ids_in] = logw_in
+        for i in ids_out:
+            forecasts[i] = (ds["cv"][int(i)] if sb is None else sb.cv_forecasts[int(i)])[np.newaxis]
             logw[i] = logw_in[0]
         # prepend the current pose estimate (mid_sim_wrapper.py:444-454)
         pose = np.repeat(pose_now[:, None, None, :], k, axis=1)
@@ -384,13 +411,14 @@ def _engine_lock_of(engine: JmidEngine) -> RLock:
 
 def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray, seeds, *, num_samples: int,
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
-                  device_topk: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  device_topk: bool = True, device_scene: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
     human_xy [E, F, N, 2], robot_xy [E, F, 2] on the ``time_step`` grid (oldest first); ``seeds[e]`` seeds the torch
     generator episode e draws its x_T from (== ``torch.manual_seed(seeds[e])`` before the per-episode call).
-    The host batch comes from ``scene.build_scenes_batched`` with the reference's own clustering (the pedestrians
+    The host batch comes from ``scene.build_scenes_batched`` (``device_scene=True``: from ``engine.build_scene`` +
+    ``engine.scene_arrays()``, the device twin) with the reference's own clustering (the pedestrians
     within 3 m of the cluster nearest the robot go through the network, mid_sim_wrapper.py:335-355; the others get
     constant-velocity forecasts, :413-429); episodes with the same number A of in-cluster pedestrians share one
     ``encode`` + ``denoise`` call (the C ABI takes one A per call).  Returns (forecasts [E, N, k, H+1, 2] float64,
@@ -399,7 +427,12 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     E, F, N, _ = human_xy.shape
     K, k, H = int(num_samples), int(num_ret_samples), int(horizon)
     precision = DEFAULTS["precision"] if precision is None else precision      # (no self check here: an engine-level call)
-    b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H)
+    if device_scene:           # the same batch from the device kernel (jmid_build_scene); grouping and everything after it as below
+        with _engine_lock_of(engine):
+            b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H)
+            b.update(engine.scene_arrays())
+    else:
+        b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H)
     inc = b["in_cluster"]
     forecasts = np.zeros((E, N, k, H, 2), dtype=np.float64)
     logw = np.zeros((E, N, k), dtype=np.float64)
