@@ -78,10 +78,12 @@ enum {
     JMID_EHIP = -3,       /* HIP runtime error */
     JMID_ENOMEM = -4,
     JMID_ERANGE = -5,     /* F16X3/F16X2/F16MX: an operand left the fp16 range; rerun with JMID_PREC_F32 */
-    JMID_ETIMEOUT = -6    /* a workgroup of a one-launch GEMM + LayerNorm (small F16MX calls) gave up waiting for its partner workgroups -
+    JMID_ETIMEOUT = -6,   /* a workgroup of a one-launch GEMM + LayerNorm (small F16MX calls) gave up waiting for its partner workgroups -
                              not all of the launch was resident on the GPU (another process or stream held compute units).  Nothing to do
                              with the arithmetic: the outputs are undefined, the handle runs the unfused kernels from now on (same bits,
                              ~0.6 ms more per 50-step one-scene call); repeat the call in the SAME precision.  Counted: jmid_timeout_count */
+    JMID_EHISTORY = -7    /* jmid_build_scene_stamped: an episode has fewer than hist_len frames on the time_step grid - where the reference
+                             fails with TypeError (get_timesteps_data returns None, MID/mid.py:326); scene.HistoryTooShortError in Python */
 };
 
 /* Library / build identification (also the cheap "does it load" probe). */
@@ -334,6 +336,45 @@ int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float
  * jmid_predict, JMID_ERANGE and JMID_ETIMEOUT included (the scene stays resident: jmid_scene_get feeds the staged repeat). */
 int jmid_predict_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
                        float* sel, float* logw, float* pos_out);
+
+/* jmid_build_scene from raw stamped frames: the history frame table of predict_ret_best (mid_sim_wrapper.py:244-298: dropna, the stable sort
+ * by stamp, subsample_df's trunc(stamp * 100) bins of round(time_step * 100) anchored at the LAST stamp, the last row per bin, linear
+ * interpolation of empty bins, the cut to past_num_frames) on the device, then exactly what jmid_build_scene does with the resulting grid.
+ * For histories in which every human and the robot share the stamps of a frame - what update_state_hists (:198-204) produces.
+ *   stamps    [E, R] doubles          the stamp of each raw frame, oldest-PUSHED first (they need not be sorted); 1 <= R <= 64
+ *   human_xy  [E, R, N, 2] doubles    pedestrian positions per raw frame, 1 <= N <= 63
+ *   robot_xy  [E, R, 2] doubles
+ *   n_frames  [E] ints or NULL        the first n_frames[e] (1..R) raw frames of episode e are valid; NULL: all R of every episode
+ *   n_grid_out [E] ints               frames on the grid per episode, min(hist_len, bins between the oldest kept and the newest stamp)
+ *   everything else as jmid_build_scene (F is the handle's hist_len)
+ * A frame with a NaN stamp or coordinate is dropped; equal stamps keep push order and the later one wins its bin; an empty bin is
+ * interpolated in fp64 as np.interp does (slope = (y1 - y0) / (x1 - x0); y = slope * (x - x0) + y0, no FMA) between the last frames of the
+ * nearest filled bins on either side - the older one may lie any number of bins back: only the hist_len newest bins are ever produced.
+ * pose_now (what predict_ret_best prepends, :444-454) is the LAST PUSHED valid frame, before anything is dropped (agent_df.tail(1)).
+ * The grid is bit-identical to the reference's frame table, so the resident arrays are jmid_build_scene's on that grid.
+ * Synchronises like jmid_build_scene.  JMID_EHISTORY when an episode has fewer than hist_len grid frames: n_grid_out is filled and the
+ * previously resident scene, if any, is kept.  JMID_EINVAL (the resident scene is kept): R outside 1..64, an n_frames[e] outside 1..R,
+ * time_step not finite or round(time_step * 100) < 1, and every refusal of jmid_build_scene. */
+int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
+                             const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
+                             uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int mem);
+
+/* The grid the resident scene was built from and its pose_now, as doubles: human_xy [E, F, N, 2], robot_xy [E, F, 2] (the frame table of
+ * mid_sim_wrapper.py:244-298 after jmid_build_scene_stamped; the caller's own input after a plain jmid_build_scene) and pose_now [E, N, 2]
+ * (:444-454; after a plain jmid_build_scene the last frame of the grid).  NULL arguments are skipped.  JMID_EINVAL without a resident scene. */
+int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_xy_out, double* pose_now_out, int mem);
+
+/* jmid_predict_scene followed by the result assembly of predict_ret_best (mid_sim_wrapper.py:493-510, :444-454) on the stream, with one
+ * download: exactly the two arrays HumanTrajectoryForecasterSim.predict_ret_best returns, for E episodes.
+ *   forecasts_out [E, N, k, T+1, 2] doubles   step 0 = pose_now; an in-cluster pedestrian (rank by ascending track id) gets its k kept
+ *                 futures (k == K: all K samples in sample order), fp32 widened exactly; a pedestrian outside the cluster its
+ *                 constant-velocity row (:413-429) for every sample
+ *   logw_out      [E, N, k] doubles           k < K: the renormalised log-weights of the kept samples (the same row for everybody, :139-151);
+ *                 k == K: log(1 / K) (:498)
+ * Host buffers.  All limits and status codes of jmid_predict_scene (one A per call: group the episodes by their count); JMID_EINVAL also
+ * when the resident scene was built without cv_out, or with a horizon other than T. */
+int jmid_forecast_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
+                        double* forecasts_out, double* logw_out);
 
 /* The stream (a hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream; NULL = the legacy default
  * stream) that produces the inputs and consumes the outputs of this handle's JMID_MEM_DEVICE calls - see Conventions. */

@@ -15,7 +15,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 PREC_F32, PREC_F16X3, PREC_F16, PREC_F16X2, PREC_F16MX = 0, 1, 2, 3, 4
 PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3, "f16": PREC_F16, "f16x2": PREC_F16X2, "f16mx": PREC_F16MX}
 
-ERR_NAMES = {-1: "JMID_EINVAL", -2: "JMID_ENOWEIGHT", -3: "JMID_EHIP", -4: "JMID_ENOMEM", -5: "JMID_ERANGE", -6: "JMID_ETIMEOUT"}
+ERR_NAMES = {-1: "JMID_EINVAL", -2: "JMID_ENOWEIGHT", -3: "JMID_EHIP", -4: "JMID_ENOMEM", -5: "JMID_ERANGE", -6: "JMID_ETIMEOUT",
+             -7: "JMID_EHISTORY"}
 
 # name -> (restype, argtypes): every symbol declared in include/jmid_hip.h
 SIGNATURES = {
@@ -52,6 +53,11 @@ SIGNATURES = {
     "jmid_scene_get": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "jmid_predict_scene": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jmid_build_scene_stamped": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_scene_get_frames": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_forecast_scene": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "jmid_set_chunk_episodes": (C.c_int, [Handle, C.c_int]),
     "jmid_set_tuning": (C.c_int, [Handle, C.c_char_p, C.c_int]),
     "jmid_set_caller_stream": (C.c_int, [Handle, C.c_void_p]),

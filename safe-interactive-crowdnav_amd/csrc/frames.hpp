@@ -1,0 +1,207 @@
+// Stamped frames in, predict_ret_best arrays out: the two ends of the predictor call that surround the scene batch (scene.hpp).
+//
+// frames_kernel: the device twin of scene.py::frame_table_frames (mid_sim_wrapper.py:244-298) for E independent episodes whose R raw
+// frames carry one stamp each, shared by every human and the robot (what update_state_hists produces), in the same operation order:
+//   1. pose_now = the human positions of the last PUSHED valid frame, before anything is dropped or sorted (agent_df.tail(1))
+//   2. a frame with a NaN stamp or a NaN coordinate is dropped (dropna)
+//   3. stable sort by stamp (equal stamps keep push order): never materialised - "later in sorted order" is the comparison
+//      (stamp, push index) wherever the order matters
+//   4. ns = (int64) trunc(stamp * 100), w = round(time_step * 100), bin b = floor((ns_last - ns) / w) counted back from the newest stamp
+//   5. only the bins 0 .. F-1 are produced (nb = max(b) + 1 rows are never materialised: one stale frame makes nb huge).  A bin holds the
+//      LAST sorted frame that falls into it; an empty bin is interpolated between the nearest filled older bin (which may lie beyond F-1)
+//      and the nearest filled newer bin, each by its last frame, in index space x = nb-1-b:
+//          slope = (y1 - y0) / (x1 - x0);  y = slope * (x - x0) + y0           fp64, no FMA contraction, this association
+//      which is what np.interp computes.  Bin 0 and the bin of the oldest kept frame are always filled.
+//   6. n_grid = min(F, nb) grid frames, oldest first in rows 0 .. n_grid-1 of the outputs; the rows behind them are zero
+// One workgroup of one wavefront per episode, as scene_kernel; a lane per raw frame (R <= 64) or per bin (F <= 16) where the work is
+// per frame or per bin, all lanes striding over (row, column) where it is per value.  LDS holds the per-frame stamps and bins and the
+// per-bin sources ([R] and [F] entries: frames_lds); the coordinates themselves (R x (2N + 2) doubles, N <= 63) are read where they lie.
+// Latency-bound and tiny: clarity before cleverness.
+//
+// assemble_kernel: the device twin of scene.py::assemble_forecasts (mid_sim_wrapper.py:493-510, :444-454): one thread per
+// (episode, pedestrian, kept sample) writes its (T + 1) x 2 doubles of forecasts [E, N, k, T+1, 2] and its double of logw [E, N, k].
+// Copies and exact fp32 -> fp64 widenings only; plain vector stores, no atomics, a fixed order: bit-reproducible.
+#pragma once
+#include "common.hpp"
+#include "scene.hpp"
+
+namespace jmid {
+
+constexpr int FRM_MAX_R = 64;         // raw frames per episode: one lane each
+
+struct FramesArgs {
+    const double* stamps;         // [E, R]
+    const double* human_xy;       // [E, R, N, 2]
+    const double* robot_xy;       // [E, R, 2]
+    const int* n_frames;          // [E] valid frames per episode (the first n_frames[e] of the R, oldest-pushed first), or null: all R
+    double* o_human;              // [E, F, N, 2]
+    double* o_robot;              // [E, F, 2]
+    double* o_pose;               // [E, N, 2]
+    int* o_n_grid;                // [E]   (-1: n_frames[e] outside 1..R, nothing else written for that episode)
+    long long w;                  // round(time_step * 100) >= 1
+    int E, N, R, F;
+};
+
+// t [R] fp64 | bin [R] int64 | x0, x1, x [F] fp64 | lo, hi [F] int
+inline size_t frames_lds(int R, int F) { return (size_t)R * 16 + (size_t)F * (24 + 8); }
+
+static __global__ __launch_bounds__(SCN_LANES) void frames_kernel(FramesArgs g) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char frm_lds_raw[];
+    const int i = threadIdx.x, e = blockIdx.x;
+    const int N = g.N, R = g.R, F = g.F, C = 2 * N + 2;
+    double* t = reinterpret_cast<double*>(frm_lds_raw);       // [R] stamps
+    long long* bin = reinterpret_cast<long long*>(t + R);     // [R] bin counted back from the newest stamp, -1 = dropped
+    double* bx = reinterpret_cast<double*>(bin + R);          // [F, 3] x0, x1, x of an interpolated bin
+    int* lo = reinterpret_cast<int*>(bx + 3 * F);             // [F] the frame a filled bin holds / the older end of an empty one
+    int* hi = lo + F;                                         // [F] -1 for a filled bin / the newer end of an empty one
+    const int n = g.n_frames ? g.n_frames[e] : R;
+    if (n < 1 || n > R) {                                     // (uniform: the whole wavefront leaves)
+        if (i == 0) g.o_n_grid[e] = -1;
+        return;
+    }
+    const double* st = g.stamps + (size_t)e * R;
+    const double* hum = g.human_xy + (size_t)e * R * N * 2;
+    const double* rob = g.robot_xy + (size_t)e * R * 2;
+    double* oh = g.o_human + (size_t)e * F * N * 2;
+    double* orb = g.o_robot + (size_t)e * F * 2;
+    // column c of raw frame r: the 2N human coordinates, then the robot's two (the frame table's column order)
+    auto val = [&](int r, int c) -> double { return c < 2 * N ? hum[(size_t)r * 2 * N + c] : rob[r * 2 + (c - 2 * N)]; };
+    // step 1
+    for (int q = i; q < 2 * N; q += SCN_LANES) g.o_pose[(size_t)e * 2 * N + q] = hum[(size_t)(n - 1) * 2 * N + q];
+    // step 2: frame by frame, the lanes over its columns; the mask is the same in every lane
+    unsigned long long keep = 0;
+    for (int r = 0; r < n; ++r) {
+        bool bad = false;
+        for (int c = i; c < C; c += SCN_LANES) {
+            const double v = val(r, c);
+            bad = bad || v != v;
+        }
+        if (i == 0) {
+            const double s = st[r];
+            bad = bad || s != s;
+        }
+        if (!__ballot(bad)) keep |= 1ull << r;
+    }
+    if (i < n) t[i] = st[i];
+    __syncthreads();
+    int n_grid = 0;
+    long long nb = 0;
+    if (keep) {
+        // steps 3-4: the newest frame = the last one in (stamp, push index) order
+        int last = -1;
+        for (int j = 0; j < n; ++j)
+            if (((keep >> j) & 1ull) && (last < 0 || t[j] >= t[last])) last = j;
+        const long long ns_last = (long long)trunc(t[last] * 100.0);
+        if (i < n) {
+            long long b = -1;
+            if ((keep >> i) & 1ull) {
+                const long long a = ns_last - (long long)trunc(t[i] * 100.0);
+                b = a / g.w;
+                if (a % g.w != 0 && a < 0) --b;               // floor division (a >= 0 for sorted stamps; w >= 1)
+            }
+            bin[i] = b;
+        }
+        __syncthreads();
+        for (int j = 0; j < n; ++j)
+            if (bin[j] + 1 > nb) nb = bin[j] + 1;
+        n_grid = nb < (long long)F ? (int)nb : F;
+        // step 5: one lane per needed bin finds its source frames
+        if (i < n_grid) {
+            const long long b = i;
+            int hit = -1;
+            long long bo = -1, bn = -1;                       // the nearest filled older / newer bin
+            for (int j = 0; j < n; ++j) {
+                const long long bj = bin[j];
+                if (bj < 0) continue;
+                if (bj == b && (hit < 0 || t[j] >= t[hit])) hit = j;
+                if (bj > b && (bo < 0 || bj < bo)) bo = bj;
+                if (bj < b && bj > bn) bn = bj;
+            }
+            if (hit >= 0) {
+                lo[i] = hit;
+                hi[i] = -1;
+            } else {
+                int jo = -1, jn = -1;                          // their last frames
+                for (int j = 0; j < n; ++j) {
+                    if (bin[j] == bo && (jo < 0 || t[j] >= t[jo])) jo = j;
+                    if (bin[j] == bn && (jn < 0 || t[j] >= t[jn])) jn = j;
+                }
+                lo[i] = jo;
+                hi[i] = jn;
+                bx[i * 3] = (double)(nb - 1 - bo);
+                bx[i * 3 + 1] = (double)(nb - 1 - bn);
+                bx[i * 3 + 2] = (double)(nb - 1 - b);
+            }
+        }
+    }
+    __syncthreads();
+    // step 6: grid row p holds bin n_grid-1-p; the rows behind the grid are zero
+    for (int q = i; q < F * C; q += SCN_LANES) {
+        const int p = q / C, c = q % C;
+        double y = 0.0;
+        if (p < n_grid) {
+            const int b = n_grid - 1 - p;
+            y = val(lo[b], c);
+            if (hi[b] >= 0) {
+                const double y1 = val(hi[b], c), x0 = bx[b * 3], x1 = bx[b * 3 + 1], x = bx[b * 3 + 2];
+                const double slope = (y1 - y) / (x1 - x0);
+                y = slope * (x - x0) + y;
+            }
+        }
+        if (c < 2 * N) oh[(size_t)p * 2 * N + c] = y;
+        else orb[p * 2 + (c - 2 * N)] = y;
+    }
+    if (i == 0) g.o_n_grid[e] = n_grid;
+}
+
+inline hipError_t launch_frames(const FramesArgs& g, hipStream_t st) {
+    hipLaunchKernelGGL(frames_kernel, dim3(g.E), dim3(SCN_LANES), frames_lds(g.R, g.F), st, g);
+    return hipGetLastError();
+}
+
+struct AssembleArgs {
+    const unsigned char* in_cluster;      // [E, N]
+    const float* src;                     // k < K: sel [E, A, k, T, 2]; k == K: pos [E, K, A, T, 2]
+    const float* logw_in;                 // k < K: [E, A, k]; k == K: unused
+    const double* cv;                     // [E, N, T, 2]
+    const double* pose;                   // pose_now of episode e at pose + e * pose_stride: [N, 2]
+    double* forecasts;                    // [E, N, k, T+1, 2]
+    double* logw;                         // [E, N, k]
+    double logw_full;                     // k == K: log(1 / K), computed on the host
+    size_t pose_stride;
+    int E, N, A, k, T, full;
+};
+
+constexpr int ASM_THREADS = 256;
+
+static __global__ __launch_bounds__(ASM_THREADS) void assemble_kernel(AssembleArgs g) {
+    const size_t idx = (size_t)blockIdx.x * ASM_THREADS + threadIdx.x;
+    const int N = g.N, A = g.A, k = g.k, T = g.T;
+    if (idx >= (size_t)g.E * N * k) return;
+    const int j = (int)(idx % k), n = (int)((idx / k) % N), e = (int)(idx / ((size_t)k * N));
+    const unsigned char* inc = g.in_cluster + (size_t)e * N;
+    double* o = g.forecasts + idx * (size_t)(T + 1) * 2;
+    const double* pose = g.pose + (size_t)e * g.pose_stride + (size_t)n * 2;
+    o[0] = pose[0];
+    o[1] = pose[1];
+    int a = 0;                                                // rank by ascending track id
+    for (int m = 0; m < n; ++m) a += inc[m] ? 1 : 0;
+    if (inc[n] && a < A) {
+        // (k == K: sample j is row j of pos; the host tail's transpose)
+        const float* s = g.src + (g.full ? ((size_t)e * k + j) * A + a : ((size_t)e * A + a) * k + j) * (size_t)T * 2;
+        for (int q = 0; q < T * 2; ++q) o[2 + q] = (double)s[q];
+    } else {
+        const double* s = g.cv + ((size_t)e * N + n) * (size_t)T * 2;
+        for (int q = 0; q < T * 2; ++q) o[2 + q] = s[q];
+    }
+    g.logw[idx] = g.full ? g.logw_full : (double)g.logw_in[(size_t)e * A * k + j];      // the row of in-cluster rank 0: all rows are equal
+}
+
+inline hipError_t launch_assemble(const AssembleArgs& g, hipStream_t st) {
+    const size_t total = (size_t)g.E * g.N * g.k;
+    hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((total + ASM_THREADS - 1) / ASM_THREADS)), dim3(ASM_THREADS), 0, st, g);
+    return hipGetLastError();
+}
+
+}  // namespace jmid

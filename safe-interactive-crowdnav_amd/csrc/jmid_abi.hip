@@ -71,17 +71,23 @@ int ensure_pin(jmid_ctx* h, size_t need, const char* who) {
 // jmid_predict and jmid_predict_scene after their argument checks: one upload, encoder -> denoise loop -> integrator -> top-k chained on
 // the stream, one download.  scene = false: the five inputs are host arrays.  scene = true: x_st, nbr_sum, edge_mask and p0 are null and
 // the in-cluster rows of the resident scene are gathered on the device instead (x_T and bw are the whole upload).
+// fc_out (scene mode only; jmid_forecast_scene): assemble_kernel follows on the stream and the download is forecasts [E, N, k, T+1, 2] and
+// logw [E, N, k] doubles instead of sel / logw / pos, which then never leave the device.
 int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask, const float* x_T,
-                  const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out, bool scene, const char* who) {
+                  const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out, bool scene, const char* who,
+                  double* fc_out = nullptr, double* lwd_out = nullptr) {
     const bool rank = k < K;
     const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
     const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
     const size_t n_sel = rank ? n * k * T * 2 : 0, n_lw = rank ? n * k : 0, n_pos = pos_out ? n_xT : 0;
     auto up = [](size_t floats) { return (floats + 63) / 64 * 64; };
-    // upload block | ctx | download block (flag, sel, logw, pos)
+    // the assembled arrays are doubles: two float slots each (every offset is a multiple of 256 bytes)
+    const size_t Np = fc_out ? (size_t)h->scene.N : 0, n_fc = 2 * ((size_t)E * Np * k * (T + 1) * 2), n_lwd = 2 * ((size_t)E * Np * k);
+    // upload block | ctx | download block (flag, forecasts, their logw, sel, logw, pos; with fc_out the download ends behind the first three)
     const size_t o_xs = 0, o_nb = o_xs + up(n_xs), o_em = o_nb + up(n_nb), o_xT = o_em + up(n_em), o_p0 = o_xT + up(n_xT), o_bw = o_p0 + up(n_p0),
-                 in_floats = o_bw + up(n_bw), o_ctx = in_floats, o_out = o_ctx + up(n * H2), o_flag = o_out, o_sel = o_flag + 64, o_lw = o_sel + up(n_sel),
-                 o_pos = o_lw + up(n_lw), total = o_pos + up(n_pos), out_floats = total - o_out;
+                 in_floats = o_bw + up(n_bw), o_ctx = in_floats, o_out = o_ctx + up(n * H2), o_flag = o_out, o_fc = o_flag + 64, o_lwd = o_fc + up(n_fc),
+                 o_sel = o_lwd + up(n_lwd), o_lw = o_sel + up(n_sel), o_pos = o_lw + up(n_lw), total = o_pos + up(n_pos),
+                 out_floats = (fc_out ? o_sel : total) - o_out;
     if (total * 4 > h->io_dev_bytes) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (h->io_dev) HIPCHK(h, hipFree(h->io_dev));
@@ -131,6 +137,23 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
     if (!rc) rc = run_network(h, E, A, K, T, dev + o_xT, dev + o_ctx, dev + o_p0, dt, precision, -1, nullptr, pos_out ? dev + o_pos : nullptr,
                               nullptr, JMID_MEM_DEVICE);
     if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw);
+    if (!rc && fc_out) {
+        const jmid_ctx::SceneWs& sc = h->scene;
+        AssembleArgs aa{};
+        aa.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev + sc.o_inc);
+        aa.src = rank ? dev + o_sel : h->last_pos;
+        aa.logw_in = rank ? dev + o_lw : nullptr;
+        aa.cv = reinterpret_cast<const double*>(sc.dev + sc.o_cv);
+        // pose_now: its own slot after a stamped build, the last frame of the grid otherwise (what predict_batch prepends)
+        aa.pose = sc.stamped ? reinterpret_cast<const double*>(sc.dev + sc.o_pose)
+                             : reinterpret_cast<const double*>(sc.dev + sc.o_hum) + (Th - 1) * (size_t)sc.N * 2;
+        aa.pose_stride = sc.stamped ? (size_t)sc.N * 2 : Th * (size_t)sc.N * 2;
+        aa.forecasts = reinterpret_cast<double*>(dev + o_fc);
+        aa.logw = reinterpret_cast<double*>(dev + o_lwd);
+        aa.logw_full = std::log(1.0 / (double)K);
+        aa.E = E; aa.N = sc.N; aa.A = A; aa.k = k; aa.T = T; aa.full = rank ? 0 : 1;
+        if (launch_assemble(aa, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": assemble launch failed");
+    }
     h->chained = false;
     if (rc) return rc;
     const bool flagged = precision != JMID_PREC_F32;
@@ -140,12 +163,134 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (flagged && *reinterpret_cast<const int*>(pout + (o_flag - o_out)))
         return jmid_host::flagged_call(h, *reinterpret_cast<const int*>(pout + (o_flag - o_out)));
+    if (fc_out) {
+        std::memcpy(fc_out, pout + (o_fc - o_out), n_fc * 4);
+        std::memcpy(lwd_out, pout + (o_lwd - o_out), n_lwd * 4);
+        return JMID_OK;
+    }
     if (rank) {
         std::memcpy(sel, pout + (o_sel - o_out), n_sel * 4);
         std::memcpy(logw, pout + (o_lw - o_out), n_lw * 4);
     }
     if (pos_out) std::memcpy(pos_out, pout + (o_pos - o_out), n_pos * 4);
     return JMID_OK;
+}
+
+// where the grid of a scene lies in a workspace: human_xy [E, F, N, 2] | robot_xy [E, F, 2] | pose_now [E, N, 2] doubles, each padded to
+// 256 bytes - the same block in the scene workspace and in the one frames_kernel writes, so that one copy moves it
+struct GridBlock {
+    size_t o_hum, o_rob, o_pose, end;
+};
+GridBlock grid_block(int E, int N, int F) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    GridBlock gb{};
+    gb.o_hum = 0;
+    gb.o_rob = up((size_t)E * F * N * 2 * 8);
+    gb.o_pose = gb.o_rob + up((size_t)E * F * 2 * 8);
+    gb.end = gb.o_pose + up((size_t)E * N * 2 * 8);
+    return gb;
+}
+
+// the refusals jmid_build_scene and jmid_build_scene_stamped share (F is the handle's hist_len by then)
+int check_scene_dims(jmid_ctx* h, const char* who, int N, int F, const double* cv_out, int horizon, double time_step) {
+    const std::string w(who);
+    if (F != h->hist_len || F < 3 || F > SCN_MAX_F) return fail(h, JMID_EINVAL, w + ": F must be the handle's hist_len, and at least 3");
+    if (N < 1 || N > SCN_LANES - 1) return fail(h, JMID_EINVAL, w + " supports 1 <= N <= 63 pedestrians");
+    if (cv_out && (horizon < 1 || horizon > SCN_MAX_H)) return fail(h, JMID_EINVAL, w + ": the horizon of cv_out must be in 1..24");
+    if (!(time_step > 0.0) || !std::isfinite(time_step)) return fail(h, JMID_EINVAL, w + ": time_step must be finite and > 0");
+    return 0;
+}
+
+// jmid_build_scene and jmid_build_scene_stamped after their argument checks and order_in: the grid into the scene workspace, scene_kernel, the
+// small outputs to the caller (`mem` says where they live), one synchronisation.  src 0: human_xy / robot_xy are host arrays; 1: device
+// arrays; 2: human_xy is a device GridBlock (grid + pose_now, as frames_kernel left it) and robot_xy is unused.
+int build_scene_resident(jmid_ctx* h, int E, int N, int F, const double* human_xy, const double* robot_xy, int src, double time_step, int horizon,
+                         int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem) {
+    const bool host = mem == JMID_MEM_HOST;
+    const size_t rows = (size_t)E * N, b_hum = rows * F * 2 * 8, b_rob = (size_t)E * F * 2 * 8, b_cv = cv_out ? rows * horizon * 2 * 8 : 0;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const GridBlock gb = grid_block(E, N, F);
+    // the grid | the resident arrays | the download block: n_in, in_cluster, robot_in_cluster, cv
+    const size_t o_x = gb.end, o_xst = o_x + up(rows * F * 6 * 4),
+                 o_nbr = o_xst + up(rows * F * 6 * 4), o_em = o_nbr + up(rows * 2 * F * 6 * 4), o_p0 = o_em + up(rows * 2 * 4), o_nin = o_p0 + up(rows * 2 * 4),
+                 o_inc = o_nin + up((size_t)E * 4), o_rin = o_inc + up(rows), o_cv = o_rin + up((size_t)E), need = o_cv + up(b_cv), b_out = need - o_nin;
+    jmid_ctx::SceneWs& sc = h->scene;
+    sc.E = 0;                     // no scene is resident until this call has succeeded
+    if (need > sc.bytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (sc.dev) HIPCHK(h, hipFree(sc.dev));
+        sc.dev = nullptr;
+        sc.bytes = 0;
+        if (hipMalloc((void**)&sc.dev, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_build_scene: workspace allocation failed");
+        sc.bytes = need;
+    }
+    SceneArgs g{};
+    g.E = E; g.N = N; g.F = F; g.horizon = horizon; g.force_all = force_all_in_cluster ? 1 : 0;
+    g.dt = time_step;
+    g.human_xy = reinterpret_cast<const double*>(sc.dev + gb.o_hum);
+    g.robot_xy = reinterpret_cast<const double*>(sc.dev + gb.o_rob);
+    g.x = reinterpret_cast<float*>(sc.dev + o_x); g.x_st = reinterpret_cast<float*>(sc.dev + o_xst);
+    g.nbr_sum = reinterpret_cast<float*>(sc.dev + o_nbr); g.edge_mask = reinterpret_cast<float*>(sc.dev + o_em);
+    g.p0 = reinterpret_cast<float*>(sc.dev + o_p0);
+    g.n_in = reinterpret_cast<int*>(sc.dev + o_nin);
+    g.in_cluster = reinterpret_cast<unsigned char*>(sc.dev + o_inc);
+    g.robot_in = reinterpret_cast<unsigned char*>(sc.dev + o_rin);
+    g.cv = cv_out ? reinterpret_cast<double*>(sc.dev + o_cv) : nullptr;
+    const size_t pin_in = src == 0 ? gb.o_pose : 0;       // host arrays are staged: human_xy | robot_xy
+    if (int rc = ensure_pin(h, pin_in + (host ? b_out : (size_t)E * 4), "jmid_build_scene")) return rc;
+    if (src == 0) {
+        std::memcpy(h->pin + gb.o_hum, human_xy, b_hum);
+        std::memcpy(h->pin + gb.o_rob, robot_xy, b_rob);
+        HIPCHK(h, hipMemcpyAsync(sc.dev, h->pin, pin_in, hipMemcpyHostToDevice, h->stream));
+    } else if (src == 1) {
+        HIPCHK(h, hipMemcpyAsync(sc.dev + gb.o_hum, human_xy, b_hum, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sc.dev + gb.o_rob, robot_xy, b_rob, hipMemcpyDeviceToDevice, h->stream));
+    } else {
+        HIPCHK(h, hipMemcpyAsync(sc.dev, human_xy, gb.end, hipMemcpyDeviceToDevice, h->stream));
+    }
+    HIPCHK(h, launch_scene(g, h->stream));
+    sc.n_in.resize(E);
+    char* pout = h->pin + pin_in;
+    if (host) {
+        HIPCHK(h, hipMemcpyAsync(pout, sc.dev + o_nin, b_out, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
+        std::memcpy(n_in_out, pout, (size_t)E * 4);
+        std::memcpy(in_cluster_out, pout + (o_inc - o_nin), rows);
+        std::memcpy(robot_in_cluster_out, pout + (o_rin - o_nin), (size_t)E);
+        if (cv_out) std::memcpy(cv_out, pout + (o_cv - o_nin), b_cv);
+    } else {
+        HIPCHK(h, hipMemcpyAsync(pout, g.n_in, (size_t)E * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(n_in_out, g.n_in, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(in_cluster_out, g.in_cluster, rows, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(robot_in_cluster_out, g.robot_in, (size_t)E, hipMemcpyDeviceToDevice, h->stream));
+        if (cv_out) HIPCHK(h, hipMemcpyAsync(cv_out, g.cv, b_cv, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
+    }
+    sc.o_x = o_x; sc.o_xst = o_xst; sc.o_nbr = o_nbr; sc.o_em = o_em; sc.o_p0 = o_p0; sc.o_inc = o_inc;
+    sc.o_hum = gb.o_hum; sc.o_rob = gb.o_rob; sc.o_pose = gb.o_pose; sc.o_cv = o_cv;
+    sc.stamped = src == 2;
+    sc.horizon = cv_out ? horizon : 0;
+    sc.E = E; sc.N = N;
+    return 0;
+}
+
+// the refusals jmid_predict_scene and jmid_forecast_scene share
+int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K, int T, int k, const float* x_T) {
+    if (int rc = check_ready(h)) return rc;
+    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, who + ": bad dimensions");
+    if (!x_T) return fail(h, JMID_EINVAL, who + ": null input");
+    const jmid_ctx::SceneWs& sc = h->scene;
+    if (!sc.E) return fail(h, JMID_EINVAL, who + " needs a preceding jmid_build_scene on this handle");
+    if (E != sc.E) return fail(h, JMID_EINVAL, who + ": E differs from the resident scene's");
+    for (int e = 0; e < E; ++e)
+        if (sc.n_in[e] != A)
+            return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(e) + " has " + std::to_string(sc.n_in[e]) +
+                                            " in-cluster pedestrians, not A = " + std::to_string(A) + " (group the episodes by their count)");
+    if (k < K && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, who + ": the device top-k supports A <= 32, K <= 1024, T <= 24");
+    if (h->ddpm) return fail(h, JMID_EINVAL, who + " samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
+    return 0;
 }
 
 }  // namespace jmid_host
@@ -247,6 +392,7 @@ int jmid_destroy(jmid_handle_t h) {
     if (h->arena) hipFree(h->arena);
     if (h->kde_ws) hipFree(h->kde_ws);
     if (h->scene.dev) hipFree(h->scene.dev);
+    if (h->frames_dev) hipFree(h->frames_dev);
     for (int c = 0; c < KC_COUNT; ++c)
         for (auto& ev : h->prof_ev[c]) {
             hipEventDestroy(ev.a);
@@ -584,70 +730,106 @@ int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_x
                      int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem) {
     if (!h) return JMID_EINVAL;
     if (E <= 0 || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out) return fail(h, JMID_EINVAL, "jmid_build_scene: bad argument");
-    if (F != h->hist_len || F < 3 || F > SCN_MAX_F) return fail(h, JMID_EINVAL, "jmid_build_scene: F must be the handle's hist_len, and at least 3");
-    if (N < 1 || N > SCN_LANES - 1) return fail(h, JMID_EINVAL, "jmid_build_scene supports 1 <= N <= 63 pedestrians");
-    if (cv_out && (horizon < 1 || horizon > SCN_MAX_H)) return fail(h, JMID_EINVAL, "jmid_build_scene: the horizon of cv_out must be in 1..24");
-    if (!(time_step > 0.0) || !std::isfinite(time_step)) return fail(h, JMID_EINVAL, "jmid_build_scene: time_step must be finite and > 0");
+    if (int rc = check_scene_dims(h, "jmid_build_scene", N, F, cv_out, horizon, time_step)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
+    if (int rc = build_scene_resident(h, E, N, F, human_xy, robot_xy, mem == JMID_MEM_HOST ? 0 : 1, time_step, horizon, force_all_in_cluster,
+                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem))
+        return rc;
+    return order_out(h, mem);
+}
+
+int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
+                             const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
+                             uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (E <= 0 || !stamps || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out || !n_grid_out)
+        return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: bad argument");
+    if (R < 1 || R > FRM_MAX_R) return fail(h, JMID_EINVAL, "jmid_build_scene_stamped supports 1 <= R <= 64 raw frames");
+    const int F = h->hist_len;
+    if (int rc = check_scene_dims(h, "jmid_build_scene_stamped", N, F, cv_out, horizon, time_step)) return rc;
+    // w = round(time_step * 100) as Python rounds it (to nearest, ties to even)
+    const double wd = std::nearbyint(time_step * 100.0);
+    if (!(wd >= 1.0) || wd > 9.0e15) return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: round(time_step * 100) must be at least 1");
     const bool host = mem == JMID_MEM_HOST;
-    const size_t rows = (size_t)E * N, b_hum = rows * F * 2 * 8, b_rob = (size_t)E * F * 2 * 8, b_cv = cv_out ? rows * horizon * 2 * 8 : 0;
+    if (host && n_frames)
+        for (int e = 0; e < E; ++e)
+            if (n_frames[e] < 1 || n_frames[e] > R)
+                return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: n_frames[" + std::to_string(e) + "] = " + std::to_string(n_frames[e]) + " is outside 1..R");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = order_in(h, mem)) return rc;
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    // staged inputs (host mode) | the resident arrays | the download block: n_in, in_cluster, robot_in_cluster, cv
-    const size_t o_hum = 0, o_rob = o_hum + (host ? up(b_hum) : 0), o_x = o_rob + (host ? up(b_rob) : 0), o_xst = o_x + up(rows * F * 6 * 4),
-                 o_nbr = o_xst + up(rows * F * 6 * 4), o_em = o_nbr + up(rows * 2 * F * 6 * 4), o_p0 = o_em + up(rows * 2 * 4), o_nin = o_p0 + up(rows * 2 * 4),
-                 o_inc = o_nin + up((size_t)E * 4), o_rin = o_inc + up(rows), o_cv = o_rin + up((size_t)E), need = o_cv + up(b_cv), b_out = need - o_nin;
-    jmid_ctx::SceneWs& sc = h->scene;
-    sc.E = 0;                     // no scene is resident until this call has succeeded
-    if (need > sc.bytes) {
+    const size_t b_st = (size_t)E * R * 8, b_hum = (size_t)E * R * N * 2 * 8, b_rob = (size_t)E * R * 2 * 8, b_nf = n_frames ? (size_t)E * 4 : 0;
+    const GridBlock gb = grid_block(E, N, F);
+    // the grid block frames_kernel writes | n_grid | the staged raw frames (host mode): stamps, human_xy, robot_xy, n_frames
+    const size_t o_ng = gb.end, o_st = o_ng + up((size_t)E * 4), o_rh = o_st + (host ? up(b_st) : 0), o_rr = o_rh + (host ? up(b_hum) : 0),
+                 o_nf = o_rr + (host ? up(b_rob) : 0), need = o_nf + (host ? up(b_nf) : 0), raw = need - o_st;
+    if (need > h->frames_bytes) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (sc.dev) HIPCHK(h, hipFree(sc.dev));
-        sc.dev = nullptr;
-        sc.bytes = 0;
-        if (hipMalloc((void**)&sc.dev, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_build_scene: workspace allocation failed");
-        sc.bytes = need;
+        if (h->frames_dev) HIPCHK(h, hipFree(h->frames_dev));
+        h->frames_dev = nullptr;
+        h->frames_bytes = 0;
+        if (hipMalloc((void**)&h->frames_dev, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_build_scene_stamped: workspace allocation failed");
+        h->frames_bytes = need;
     }
-    SceneArgs g{};
-    g.E = E; g.N = N; g.F = F; g.horizon = horizon; g.force_all = force_all_in_cluster ? 1 : 0;
-    g.dt = time_step;
-    g.human_xy = human_xy; g.robot_xy = robot_xy;
-    g.x = reinterpret_cast<float*>(sc.dev + o_x); g.x_st = reinterpret_cast<float*>(sc.dev + o_xst);
-    g.nbr_sum = reinterpret_cast<float*>(sc.dev + o_nbr); g.edge_mask = reinterpret_cast<float*>(sc.dev + o_em);
-    g.p0 = reinterpret_cast<float*>(sc.dev + o_p0);
-    g.n_in = reinterpret_cast<int*>(sc.dev + o_nin);
-    g.in_cluster = reinterpret_cast<unsigned char*>(sc.dev + o_inc);
-    g.robot_in = reinterpret_cast<unsigned char*>(sc.dev + o_rin);
-    g.cv = cv_out ? reinterpret_cast<double*>(sc.dev + o_cv) : nullptr;
-    if (int rc = ensure_pin(h, host ? o_x + b_out : (size_t)E * 4, "jmid_build_scene")) return rc;
+    if (int rc = ensure_pin(h, raw + (size_t)E * 4, "jmid_build_scene_stamped")) return rc;
+    char* fd = h->frames_dev;
+    FramesArgs f{};
+    f.E = E; f.N = N; f.R = R; f.F = F;
+    f.w = (long long)wd;
+    f.stamps = stamps; f.human_xy = human_xy; f.robot_xy = robot_xy; f.n_frames = n_frames;
+    f.o_human = reinterpret_cast<double*>(fd + gb.o_hum); f.o_robot = reinterpret_cast<double*>(fd + gb.o_rob);
+    f.o_pose = reinterpret_cast<double*>(fd + gb.o_pose); f.o_n_grid = reinterpret_cast<int*>(fd + o_ng);
     if (host) {
-        std::memcpy(h->pin + o_hum, human_xy, b_hum);
-        std::memcpy(h->pin + o_rob, robot_xy, b_rob);
-        HIPCHK(h, hipMemcpyAsync(sc.dev, h->pin, o_x, hipMemcpyHostToDevice, h->stream));
-        g.human_xy = reinterpret_cast<const double*>(sc.dev + o_hum);
-        g.robot_xy = reinterpret_cast<const double*>(sc.dev + o_rob);
+        std::memcpy(h->pin, stamps, b_st);
+        std::memcpy(h->pin + (o_rh - o_st), human_xy, b_hum);
+        std::memcpy(h->pin + (o_rr - o_st), robot_xy, b_rob);
+        if (n_frames) std::memcpy(h->pin + (o_nf - o_st), n_frames, b_nf);
+        HIPCHK(h, hipMemcpyAsync(fd + o_st, h->pin, raw, hipMemcpyHostToDevice, h->stream));
+        f.stamps = reinterpret_cast<const double*>(fd + o_st); f.human_xy = reinterpret_cast<const double*>(fd + o_rh);
+        f.robot_xy = reinterpret_cast<const double*>(fd + o_rr);
+        f.n_frames = n_frames ? reinterpret_cast<const int*>(fd + o_nf) : nullptr;
     }
-    HIPCHK(h, launch_scene(g, h->stream));
-    sc.n_in.resize(E);
-    if (host) {
-        char* pout = h->pin + o_x;
-        HIPCHK(h, hipMemcpyAsync(pout, sc.dev + o_nin, b_out, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
-        std::memcpy(n_in_out, pout, (size_t)E * 4);
-        std::memcpy(in_cluster_out, pout + (o_inc - o_nin), rows);
-        std::memcpy(robot_in_cluster_out, pout + (o_rin - o_nin), (size_t)E);
-        if (cv_out) std::memcpy(cv_out, pout + (o_cv - o_nin), b_cv);
-    } else {
-        HIPCHK(h, hipMemcpyAsync(h->pin, g.n_in, (size_t)E * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(n_in_out, g.n_in, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(in_cluster_out, g.in_cluster, rows, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(robot_in_cluster_out, g.robot_in, (size_t)E, hipMemcpyDeviceToDevice, h->stream));
-        if (cv_out) HIPCHK(h, hipMemcpyAsync(cv_out, g.cv, b_cv, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::memcpy(sc.n_in.data(), h->pin, (size_t)E * 4);
+    HIPCHK(h, launch_frames(f, h->stream));
+    int* ng = reinterpret_cast<int*>(h->pin + raw);
+    HIPCHK(h, hipMemcpyAsync(ng, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToHost, h->stream));
+    if (!host) HIPCHK(h, hipMemcpyAsync(n_grid_out, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (host) std::memcpy(n_grid_out, ng, (size_t)E * 4);
+    for (int e = 0; e < E; ++e)
+        if (ng[e] < 0) {
+            (void)order_out(h, mem);
+            return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: n_frames[" + std::to_string(e) + "] is outside 1..R");
+        }
+    for (int e = 0; e < E; ++e)
+        if (ng[e] < F) {
+            const int got = ng[e];
+            (void)order_out(h, mem);
+            return fail(h, JMID_EHISTORY, "jmid_build_scene_stamped: episode " + std::to_string(e) + " has " + std::to_string(got) +
+                                              " history frames on the time_step grid, " + std::to_string(F) + " needed");
+        }
+    if (int rc = build_scene_resident(h, E, N, F, reinterpret_cast<const double*>(fd), nullptr, 2, time_step, horizon, force_all_in_cluster,
+                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem))
+        return rc;
+    return order_out(h, mem);
+}
+
+int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_xy_out, double* pose_now_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    const jmid_ctx::SceneWs& sc = h->scene;
+    if (!sc.E) return fail(h, JMID_EINVAL, "jmid_scene_get_frames needs a preceding jmid_build_scene on this handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = order_in(h, mem)) return rc;
+    const size_t F = h->hist_len, row = (size_t)sc.N * 2 * 8;
+    const hipMemcpyKind kind = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (human_xy_out) HIPCHK(h, hipMemcpyAsync(human_xy_out, sc.dev + sc.o_hum, (size_t)sc.E * F * row, kind, h->stream));
+    if (robot_xy_out) HIPCHK(h, hipMemcpyAsync(robot_xy_out, sc.dev + sc.o_rob, (size_t)sc.E * F * 2 * 8, kind, h->stream));
+    if (pose_now_out) {
+        if (sc.stamped) HIPCHK(h, hipMemcpyAsync(pose_now_out, sc.dev + sc.o_pose, (size_t)sc.E * row, kind, h->stream));
+        else            // the last frame of every episode's grid
+            HIPCHK(h, hipMemcpy2DAsync(pose_now_out, row, sc.dev + sc.o_hum + (F - 1) * row, F * row, row, sc.E, kind, h->stream));
     }
-    sc.o_x = o_x; sc.o_xst = o_xst; sc.o_nbr = o_nbr; sc.o_em = o_em; sc.o_p0 = o_p0; sc.o_inc = o_inc;
-    sc.E = E; sc.N = N;
+    if (mem == JMID_MEM_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
     return order_out(h, mem);
 }
 
@@ -671,23 +853,26 @@ int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float
 int jmid_predict_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw, float* sel,
                        float* logw, float* pos_out) {
     if (!h) return JMID_EINVAL;
-    if (int rc = check_ready(h)) return rc;
-    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, "jmid_predict_scene: bad dimensions");
-    if (!x_T) return fail(h, JMID_EINVAL, "jmid_predict_scene: null input");
-    const jmid_ctx::SceneWs& sc = h->scene;
-    if (!sc.E) return fail(h, JMID_EINVAL, "jmid_predict_scene needs a preceding jmid_build_scene on this handle");
-    if (E != sc.E) return fail(h, JMID_EINVAL, "jmid_predict_scene: E differs from the resident scene's");
-    for (int e = 0; e < E; ++e)
-        if (sc.n_in[e] != A)
-            return fail(h, JMID_EINVAL, "jmid_predict_scene: episode " + std::to_string(e) + " has " + std::to_string(sc.n_in[e]) +
-                                            " in-cluster pedestrians, not A = " + std::to_string(A) + " (group the episodes by their count)");
+    if (int rc = check_predict_scene(h, "jmid_predict_scene", E, A, K, T, k, x_T)) return rc;
     const bool rank = k < K;
     if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, "jmid_predict_scene: k < K needs sel and logw");
     if (!rank && !pos_out) return fail(h, JMID_EINVAL, "jmid_predict_scene: k == K needs pos_out");
-    if (rank && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, "jmid_predict_scene: the device top-k supports A <= 32, K <= 1024, T <= 24");
-    if (h->ddpm) return fail(h, JMID_EINVAL, "jmid_predict_scene samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
     HIPCHK(h, hipSetDevice(h->device));
     return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, true, "jmid_predict_scene");
+}
+
+int jmid_forecast_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
+                        double* forecasts_out, double* logw_out) {
+    if (!h) return JMID_EINVAL;
+    if (int rc = check_predict_scene(h, "jmid_forecast_scene", E, A, K, T, k, x_T)) return rc;
+    if (!forecasts_out || !logw_out) return fail(h, JMID_EINVAL, "jmid_forecast_scene: null output");
+    if (!h->scene.horizon) return fail(h, JMID_EINVAL, "jmid_forecast_scene: the resident scene was built without cv_out (the rows outside the cluster need it)");
+    if (h->scene.horizon != T)
+        return fail(h, JMID_EINVAL, "jmid_forecast_scene: T = " + std::to_string(T) + " differs from the horizon " + std::to_string(h->scene.horizon) +
+                                        " the resident scene was built with");
+    HIPCHK(h, hipSetDevice(h->device));
+    return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, nullptr, nullptr, nullptr, true,
+                         "jmid_forecast_scene", forecasts_out, logw_out);
 }
 
 int jmid_set_chunk_episodes(jmid_handle_t h, int episodes) {

@@ -1,6 +1,6 @@
 // libjmid_hip.so -- what every translation unit of the host side shares: the handle, error / profiling helpers and the
 // internal entry points between the units.  gfx950 only.  No CPU fallback: every entry point that computes needs a HIP device.
-//   jmid_abi.hip      the C ABI proper (include/jmid_hip.h): handle lifetime, encode / denoise / topk / predict / statistics, knobs, stream
+//   jmid_abi.hip      the C ABI proper (include/jmid_hip.h): handle lifetime, encode / denoise / topk / predict / scene / statistics, knobs, stream
 //   jmid_weights.hip  weight registry, operand planes (fp16 hi / lo, bf8 images, k16 panels), sampler step tables
 //   jmid_planner.hip  chunk plan, step workspace, one net evaluation (net_step), the denoise loop (run_network)
 //   jmid_profile.hip  per-kernel-class HIP-event profiling
@@ -32,6 +32,7 @@
 #include "kde.hpp"
 #include "launch_plan.hpp"
 #include "scene.hpp"
+#include "frames.hpp"
 
 using namespace jmid;
 
@@ -133,7 +134,17 @@ struct jmid_ctx {
         int E = 0, N = 0;            // E = 0: no scene is resident
         size_t o_x = 0, o_xst = 0, o_nbr = 0, o_em = 0, o_p0 = 0, o_inc = 0;   // byte offsets of the resident arrays
         std::vector<int> n_in;       // [E] in-cluster pedestrians per episode (host copy)
+        // the grid the scene was built from (human_xy [E, F, N, 2], robot_xy [E, F, 2] fp64) and pose_now [E, N, 2]: what
+        // jmid_scene_get_frames copies out and jmid_forecast_scene prepends.  stamped: pose_now has a slot of its own (frames_kernel wrote
+        // it); otherwise it is the last frame of the grid
+        size_t o_hum = 0, o_rob = 0, o_pose = 0, o_cv = 0;
+        bool stamped = false;
+        int horizon = 0;             // of the resident cv; 0: built without cv
     } scene;
+    // jmid_build_scene_stamped: the raw frames and what frames_kernel made of them (grid, pose_now, n_grid), in a workspace of its own:
+    // a build that ends with JMID_EHISTORY must not touch the resident scene
+    char* frames_dev = nullptr;
+    size_t frames_bytes = 0;
     bool chained = false;       // the running run_network is a stage of jmid_predict: no caller-stream ordering, no flag round trip
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)

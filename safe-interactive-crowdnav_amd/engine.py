@@ -338,6 +338,87 @@ class JmidEngine:
                       C.c_void_p(pos.ctypes.data))
         return pos, None
 
+    def build_scene_stamped(self, stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
+                            horizon: Optional[int] = None, force_all_in_cluster: bool = False,
+                            n_frames: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
+        """``build_scene`` from raw stamped frames (``jmid_build_scene_stamped``; the frame table is the device twin of
+        ``scene.frame_table_frames_batched``): stamps [E, R], human_xy [E, R, N, 2], robot_xy [E, R, 2] float64, oldest-pushed first, the
+        first ``n_frames[e]`` of each episode valid (None: all R) - or [R], [R, N, 2], [R, 2] for one scene, whose results then come without
+        the episode axis.  Returns what ``build_scene`` returns plus ``n_grid`` [E] int32.  Raises ``scene.HistoryTooShortError`` when an
+        episode has fewer than ``hist_len`` frames on the grid (JMID_EHISTORY; a scene built before stays resident)."""
+        from .scene import HistoryTooShortError
+        st = np.ascontiguousarray(stamps, dtype=np.float64)
+        hum = np.ascontiguousarray(human_xy, dtype=np.float64)
+        rob = np.ascontiguousarray(robot_xy, dtype=np.float64)
+        single = hum.ndim == 3
+        if single:
+            st, hum, rob = st[None], hum[None], rob[None]
+        if hum.ndim != 4 or hum.shape[-1] != 2 or rob.shape != (hum.shape[0], hum.shape[1], 2) or st.shape != hum.shape[:2]:
+            raise ValueError("expected stamps [E, R], human_xy [E, R, N, 2] and robot_xy [E, R, 2] (or one scene without the episode axis)")
+        E, R, N, _ = (int(v) for v in hum.shape)
+        nf = None
+        if n_frames is not None:
+            nf = np.ascontiguousarray(np.atleast_1d(n_frames), dtype=np.int32)
+            if nf.shape != (E,):
+                raise ValueError("n_frames must hold one count per episode")
+        inc = np.empty((E, N), dtype=np.uint8)
+        rin = np.empty(E, dtype=np.uint8)
+        n_in = np.empty(E, dtype=np.int32)
+        n_grid = np.empty(E, dtype=np.int32)
+        cv = np.empty((E, N, int(horizon), 2), dtype=np.float64) if horizon is not None else None
+        rc = self._lib.jmid_build_scene_stamped(self._h, E, N, R, C.c_void_p(st.ctypes.data), C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data),
+                                                C.c_void_p(nf.ctypes.data) if nf is not None else None, float(time_step),
+                                                int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
+                                                C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
+                                                C.c_void_p(n_grid.ctypes.data), C.c_void_p(cv.ctypes.data) if cv is not None else None, _lib.MEM_HOST)
+        if rc == -7:                                 # JMID_EHISTORY
+            err = HistoryTooShortError(self._lib.jmid_last_error(self._h).decode())
+            err.n_grid = n_grid[0] if single else n_grid
+            raise err
+        self._check(rc)
+        self._scene_shape, self._scene_n_in = (E, N, self.hist_len, single), n_in
+        out = {"in_cluster": inc.astype(bool), "robot_in_cluster": rin.astype(bool), "n_in": n_in, "n_grid": n_grid, "cv": cv}
+        return {k: (v[0] if single and v is not None else v) for k, v in out.items()}
+
+    def scene_frames(self) -> Dict[str, np.ndarray]:
+        """The grid the resident scene was built from and its current pose (``jmid_scene_get_frames``): ``human_xy`` [E, F, N, 2],
+        ``robot_xy`` [E, F, 2], ``pose_now`` [E, N, 2] float64 - after ``build_scene_stamped`` the frame table of ``scene.frame_table``,
+        after ``build_scene`` its own input and the last frame.  After a one-scene build the episode axis is absent."""
+        shape = getattr(self, "_scene_shape", None)
+        E, N, F, single = shape if shape is not None else (0, 0, self.hist_len, False)      # (no build: the library says so)
+        out = {"human_xy": np.empty((E, F, N, 2), np.float64), "robot_xy": np.empty((E, F, 2), np.float64),
+               "pose_now": np.empty((E, N, 2), np.float64)}
+        self._check(self._lib.jmid_scene_get_frames(self._h, *[C.c_void_p(a.ctypes.data) for a in out.values()], _lib.MEM_HOST))
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def forecast_scene(self, x_T: np.ndarray, k: int, dt: float = 0.25, precision: str = "f32"):
+        """``predict_scene`` followed by the result assembly on the device (``jmid_forecast_scene``; the twin of
+        ``scene.assemble_forecasts``): x_T [E, K*A, T, 2] -> (forecasts [E, N, k, T+1, 2], log-weights [E, N, k]) float64, per episode
+        exactly what ``predict_ret_best()`` returns.  The resident scene must have been built with ``horizon`` = T.  After a one-scene
+        build the episode axis of the results is absent."""
+        import math
+        x_T = np.asarray(x_T)
+        if x_T.ndim != 4 or x_T.shape[-1] != 2:
+            raise ValueError("expected x_T [E, K*A, T, 2]")
+        E, KA, T, _ = (int(v) for v in x_T.shape)
+        k = int(k)
+        n_in = getattr(self, "_scene_n_in", None)
+        A = int(n_in[0]) if n_in is not None and len(n_in) and n_in[0] > 0 else 1
+        if KA % A != 0:
+            raise ValueError(f"x_T has {KA} rows per episode: not a multiple of the scene's {A} in-cluster pedestrians")
+        K = KA // A
+        shape = getattr(self, "_scene_shape", None)
+        N, single = (shape[1], shape[3]) if shape is not None else (1, False)
+        bx = _Buf(x_T, False)
+        bw = None
+        if k < K:
+            bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
+        fc = np.empty((E, N, max(k, 0), T + 1, 2), dtype=np.float64)
+        lw = np.empty((E, N, max(k, 0)), dtype=np.float64)
+        self._compute(self._lib.jmid_forecast_scene, self._h, E, A, K, T, k, bx.ptr, float(dt), _lib.PRECISIONS[precision],
+                      C.c_void_p(bw.ctypes.data) if bw is not None else None, C.c_void_p(fc.ctypes.data), C.c_void_p(lw.ctypes.data))
+        return (fc[0], lw[0]) if single else (fc, lw)
+
     def net_eval(self, x: ArrayLike, ctx: ArrayLike, step_idx: int = 0, precision: str = "f32"):
         """One evaluation of e_theta for DDIM table entry ``step_idx``; x [E, K*A, T, 2] -> e same shape."""
         dev = _is_cuda(x)

@@ -66,7 +66,7 @@ ERANGE_FALLBACKS = 0            # calls of this process that were repeated in "f
 SELF_CHECK_DOWNGRADES = 0       # instances whose opt-in precision was replaced by "f16x3" by the first-call self check
 # what HumanTrajectoryForecasterSim's keyword arguments default to (safe_interactive_crowdnav_amd.install(**defaults) edits it)
 DEFAULTS = {"device_id": 0, "precision": "f16mx", "rng_compat": "auto", "self_check": True, "device_topk": True,
-            "device_scene": False}
+            "device_scene": False, "device_frames": False}
 
 
 _PHILOX_STEP: Dict[Tuple[int, Tuple[int, ...]], int] = {}     # (device, shape) -> what one randn_like of that shape adds to the Philox offset
@@ -166,7 +166,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
     def __init__(self, env_config=None, mid_config_file=None, *, weights: Optional[JMIDWeights] = None,
                  device_id: Optional[int] = None, precision: Optional[str] = None, rng_compat: Optional[str] = None,
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
-                 lib_path: Optional[str] = None, device_scene: Optional[bool] = None):
+                 lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -176,6 +176,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         self_check = DEFAULTS["self_check"] if self_check is None else self_check
         device_topk = DEFAULTS["device_topk"] if device_topk is None else device_topk
         device_scene = DEFAULTS["device_scene"] if device_scene is None else device_scene
+        device_frames = DEFAULTS["device_frames"] if device_frames is None else device_frames
         self.init_super(env_config)
         self.precision = precision
         self.self_check = bool(self_check) and precision in ("f16mx", "f16x2")
@@ -185,6 +186,11 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # True: the scene batch (cluster choice, states, scene graph, neighbour sums) is built on the device (jmid_build_scene) and the
         # predictor runs on it where it lies (jmid_predict_scene); the history table stays on the host either way
         self.device_scene = bool(device_scene)
+        # True: the raw stamped frames go to the device as they are (jmid_build_scene_stamped: frame table + scene batch) and the two
+        # returned arrays come back assembled (jmid_forecast_scene); the staged path (self check, JMID_ERANGE repeat, k < K beyond the
+        # top-k limits) reads its inputs back and assembles on the host.  Histories that are not frames (the per-human lists do not share
+        # one stamp sequence with the robot's last entries) take the host frame table as before
+        self.device_frames = bool(device_frames)
         self.erange_fallbacks = 0
         self.timings: Dict[str, float] = {}     # ms of the last predict_ret_best(): scene, device, topk, assemble
         if rng_compat not in ("auto", "cpu", "cuda"):
@@ -277,7 +283,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
 
     def predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
         """mid_sim_wrapper.py:482-510 -> (forecasts [N, k, H+1, 2] float64, log-weights [N, k] float64)."""
-        if not self.device_scene:
+        if not (self.device_scene or self.device_frames):
             return self._predict_ret_best()
         with self._engine_lock:     # the engine holds ONE resident scene: nobody else builds between this call's build and its predict
             return self._predict_ret_best()
@@ -285,8 +291,15 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
     def _predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
         t0 = time.perf_counter()
         prev, rob = self._snapshot()
-        hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, self.num_hist_frames)
-        if self.device_scene:
+        frames = SC.histories_as_frames(prev, rob) if self.device_frames else None
+        if frames is None:
+            hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, self.num_hist_frames)
+        if frames is not None:
+            # the frame table on the device too (JMID_EHISTORY -> HistoryTooShortError, where build_scene raises it on the host path)
+            ds = self.engine.build_scene_stamped(*frames, self.time_step, self.predict_horizon)
+            sb = pose_now = None
+            ids_in, ids_out = np.nonzero(ds["in_cluster"])[0], np.nonzero(~ds["in_cluster"])[0]
+        elif self.device_scene:
             if hum_xy.shape[0] < self.num_hist_frames:
                 raise SC.HistoryTooShortError(f"{hum_xy.shape[0]} history frames available, {self.num_hist_frames} needed")
             ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon)
@@ -320,6 +333,13 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 # the whole call in ONE library entry (jmid_predict: encoder -> denoise -> integrator -> top-k chained on the
                 # stream, one upload, one download); JMID_ERANGE -> the staged path below in exact fp32
                 try:
+                    if frames is not None:
+                        # ... and, from raw frames, the assembled result itself (jmid_forecast_scene): nothing left to do on the host
+                        result = self.engine.forecast_scene(x_np, k, dt=self.time_step, precision=self.precision)
+                        t2 = time.perf_counter()
+                        self.timings = {"scene_ms": 1e3 * (t1 - t0), "device_ms": 1e3 * (t2 - t1), "topk_ms": 0.0,
+                                        "assemble_ms": 1e3 * (time.perf_counter() - t2), "total_ms": 1e3 * (time.perf_counter() - t0)}
+                        return result
                     if sb is None:
                         out, lw = self.engine.predict_scene(x_np, k, dt=self.time_step, precision=self.precision)
                     else:
@@ -338,6 +358,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 if sb is None:   # the self-check call and the JMID_ERANGE repeat take their inputs from the resident scene
                     sa = self.engine.scene_arrays()
                     sx_st, snbr, sem, sp0 = (np.ascontiguousarray(sa[key][ids_in]) for key in ("x_st", "nbr_sum", "edge_mask", "p0"))
+                    if frames is not None:
+                        pose_now = self.engine.scene_frames()["pose_now"]
                 else:
                     sx_st, snbr, sem, sp0 = sb.x_st, sb.nbr_sum, sb.edge_mask, sb.p0
                 ctx = self.engine.encode(sx_st, snbr, sem)
@@ -411,7 +433,8 @@ def _engine_lock_of(engine: JmidEngine) -> RLock:
 
 def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray, seeds, *, num_samples: int,
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
-                  device_topk: bool = True, device_scene: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  device_topk: bool = True, device_scene: bool = False,
+                  device_frames: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -423,14 +446,19 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     constant-velocity forecasts, :413-429); episodes with the same number A of in-cluster pedestrians share one
     ``encode`` + ``denoise`` call (the C ABI takes one A per call).  Returns (forecasts [E, N, k, H+1, 2] float64,
     log-weights [E, N, k] float64, in_cluster [E, N] bool), each episode as ``predict_ret_best`` would return it.
+    ``device_frames=True``: the inputs are on the grid already, so only the assembly moves - every count group is built on the device
+    and comes back as its assembled arrays (``engine.forecast_scene``: one call per group instead of encode + denoise + top-k + the
+    host scatter); a group whose ranking does not fit the device top-k takes the staged path.
     """
     E, F, N, _ = human_xy.shape
     K, k, H = int(num_samples), int(num_ret_samples), int(horizon)
     precision = DEFAULTS["precision"] if precision is None else precision      # (no self check here: an engine-level call)
-    if device_scene:           # the same batch from the device kernel (jmid_build_scene); grouping and everything after it as below
+    global ERANGE_FALLBACKS
+    if device_scene or device_frames:           # the same batch from the device kernel (jmid_build_scene); grouping and everything after it as below
         with _engine_lock_of(engine):
             b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H)
-            b.update(engine.scene_arrays())
+            if not device_frames:
+                b.update(engine.scene_arrays())
     else:
         b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H)
     inc = b["in_cluster"]
@@ -444,6 +472,23 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         ei = eps[:, None]
         x_T = torch.stack([torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
                            for e in eps]).numpy()
+        if device_frames and (k == K or (device_topk and topk_fits_device(A, K, H))):
+            with _engine_lock_of(engine):      # the group's scenes resident, then predictor + assembly in one entry
+                engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H)
+                try:
+                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision=precision)
+                except JmidError as err:
+                    if err.code != -5 or precision == "f32":     # JMID_ERANGE: the same call in exact fp32, counted
+                        raise
+                    ERANGE_FALLBACKS += 1
+                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision="f32")
+            forecasts[eps] = fc[:, :, :, 1:]
+            logw[eps] = lw
+            continue
+        if "p0" not in b:
+            with _engine_lock_of(engine):
+                engine.build_scene(human_xy, robot_xy, time_step, horizon=H)
+                b.update(engine.scene_arrays())
         p0 = np.ascontiguousarray(b["p0"][ei, rows])
         with _engine_lock_of(engine):          # an engine may be shared with forecaster instances; it is not re-entrant
             ctx = engine.encode(b["x_st"][ei, rows].reshape(len(eps) * A, F, 6),

@@ -101,6 +101,136 @@ def frame_table(prev_states: Sequence[Sequence[Sequence[float]]], prev_robot_sta
     return human_xy, robot_xy, pose_now
 
 
+def frame_table_frames(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
+                       num_hist_frames: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``frame_table`` for histories given as raw FRAMES - stamps [R], human_xy [R, N, 2], robot_xy [R, 2], oldest-pushed first, every
+    human and the robot sharing the stamp of a frame (what ``update_state_hists`` produces) - and the host twin of the device
+    ``frames_kernel`` (csrc/frames.hpp), in its operation order.  Same returns, bit for bit.
+
+    Only the ``num_hist_frames`` newest bins are produced: the ``nb = max(bin) + 1`` rows of the full table are never materialised (a
+    stale frame makes ``nb`` huge).  An empty bin is interpolated between the last frames of the nearest filled bin on either side - the
+    older one may lie beyond the cut - as ``np.interp`` does it: ``slope = (y1 - y0) / (x1 - x0); y = slope * (x - x0) + y0``."""
+    stamps = np.asarray(stamps, dtype=np.float64).reshape(-1)
+    R = len(stamps)
+    human_xy = np.asarray(human_xy, dtype=np.float64).reshape(R, -1, 2)
+    N = human_xy.shape[1]
+    tab = np.concatenate([human_xy.reshape(R, 2 * N), np.asarray(robot_xy, dtype=np.float64).reshape(R, 2)], axis=1)
+    if R == 0:
+        raise HistoryTooShortError("no complete history frame")
+    pose_now = human_xy[-1].copy()                       # agent_df.tail(1): before anything is dropped or sorted
+    keep = ~(np.isnan(tab).any(axis=1) | np.isnan(stamps))
+    tab, t = tab[keep], stamps[keep]
+    if len(t) == 0:
+        raise HistoryTooShortError("no complete history frame")
+    order = np.argsort(t, kind="stable")
+    tab, t = tab[order], t[order]
+    ns = np.trunc(t * 100.0).astype(np.int64)
+    w = int(round(time_step * 100))
+    k = (ns[-1] - ns) // w                               # bin counted backwards from the newest stamp (ascending in time: non-increasing)
+    nb = int(k.max()) + 1
+    n_grid = min(int(num_hist_frames), nb)
+    out = np.empty((n_grid, tab.shape[1]))
+    for b in range(n_grid):
+        hit = np.nonzero(k == b)[0]
+        if len(hit):
+            out[n_grid - 1 - b] = tab[hit[-1]]           # the LAST sorted frame of the bin
+            continue
+        bo = int(k[k > b].min())                         # the nearest filled older bin (the oldest kept frame's bin is filled)
+        bn = int(k[k < b].max())                         # the nearest filled newer bin (bin 0 is filled)
+        y0, y1 = tab[np.nonzero(k == bo)[0][-1]], tab[np.nonzero(k == bn)[0][-1]]
+        x0, x1, x = float(nb - 1 - bo), float(nb - 1 - bn), float(nb - 1 - b)
+        slope = (y1 - y0) / (x1 - x0)
+        out[n_grid - 1 - b] = slope * (x - x0) + y0
+    return out[:, :2 * N].reshape(n_grid, N, 2), out[:, 2 * N:2 * N + 2], pose_now
+
+
+def frame_table_frames_batched(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, n_frames: Optional[np.ndarray],
+                               time_step: float, num_hist_frames: int) -> Dict[str, np.ndarray]:
+    """``frame_table_frames`` for E episodes: stamps [E, R], human_xy [E, R, N, 2], robot_xy [E, R, 2]; the first ``n_frames[e]`` (1..R;
+    None: all R) raw frames of episode e are valid.  Returns ``human_xy`` [E, F, N, 2], ``robot_xy`` [E, F, 2], ``pose_now`` [E, N, 2]
+    float64 and ``n_grid`` [E] int32 with F = ``num_hist_frames``: episode e has ``n_grid[e]`` grid frames, oldest first in its rows
+    0 .. n_grid[e]-1, zeros behind them (``n_grid[e]`` = 0: no complete frame) - the layout ``jmid_build_scene_stamped`` leaves."""
+    stamps = np.asarray(stamps, dtype=np.float64)
+    human_xy = np.asarray(human_xy, dtype=np.float64)
+    robot_xy = np.asarray(robot_xy, dtype=np.float64)
+    E, R, N, _ = human_xy.shape
+    F = int(num_hist_frames)
+    n_frames = np.full(E, R, dtype=np.int64) if n_frames is None else np.asarray(n_frames)
+    if n_frames.shape != (E,) or (n_frames < 1).any() or (n_frames > R).any():
+        raise ValueError("n_frames must hold E values in 1..R")
+    out = {"human_xy": np.zeros((E, F, N, 2)), "robot_xy": np.zeros((E, F, 2)), "pose_now": np.empty((E, N, 2)),
+           "n_grid": np.zeros(E, dtype=np.int32)}
+    for e in range(E):
+        n = int(n_frames[e])
+        out["pose_now"][e] = human_xy[e, n - 1]
+        try:
+            h, r, _ = frame_table_frames(stamps[e, :n], human_xy[e, :n], robot_xy[e, :n], time_step, F)
+        except HistoryTooShortError:
+            continue
+        out["n_grid"][e] = len(h)
+        out["human_xy"][e, :len(h)] = h
+        out["robot_xy"][e, :len(h)] = r
+    return out
+
+
+def histories_as_frames(prev_states, prev_robot_states):
+    """The per-human lists of ``update_state_hists`` as raw frames (stamps [R], human_xy [R, N, 2], robot_xy [R, 2]) when they ARE frames:
+    every human's list has the same stamps, entry by entry, as the robot's last R entries, and a stamp that occurs twice comes with
+    NaN-free data (``frame_table`` joins on stamp VALUES, so a duplicated stamp next to a dropped frame is not a frame-wise table).
+    None otherwise (somebody edited the lists by hand): ``frame_table`` handles those."""
+    R = len(prev_states[0]) if len(prev_states) else 0
+    if R == 0 or len(prev_robot_states) < R or any(len(h) != R for h in prev_states):
+        return None
+    try:
+        hum = np.asarray(prev_states, dtype=np.float64)                     # [N, R, 3]
+        rob = np.asarray(prev_robot_states[-R:], dtype=np.float64)          # [R, 3]
+    except ValueError:
+        return None
+    if hum.ndim != 3 or hum.shape[2] != 3 or rob.shape != (R, 3):
+        return None
+    stamps = rob[:, 2]
+    if not (hum[:, :, 2] == stamps[None]).all():                            # (a NaN stamp fails this too)
+        return None
+    if len(np.unique(stamps)) != R and (np.isnan(hum).any() or np.isnan(rob).any()):
+        return None
+    # (the robot's list is unbounded, but frame_table's join takes the LAST entry with a stamp: always one of these R)
+    return stamps.copy(), np.ascontiguousarray(hum[:, :, 0:2].transpose(1, 0, 2)), np.ascontiguousarray(rob[:, 0:2])
+
+
+def assemble_forecasts(in_cluster: np.ndarray, sel_or_pos: np.ndarray, logw_in: Optional[np.ndarray], cv: np.ndarray,
+                       pose_now: np.ndarray, k: int, K: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The result assembly of ``predict_ret_best`` (mid_sim_wrapper.py:493-510, :444-454) and the host twin of the device
+    ``assemble_kernel`` (csrc/frames.hpp), for one scene or, with a leading episode axis on every array, for E of them.
+
+    in_cluster [N] bool; k < K: sel_or_pos = the kept samples [A, k, H, 2] and logw_in [A, k] (float32, as ``predict_scene`` returns
+    them); k == K: sel_or_pos = all samples [K, A, H, 2] (``pos``) and logw_in is ignored; cv [N, H, 2] float64 (every pedestrian's
+    constant-velocity row); pose_now [N, 2].  Returns (forecasts [N, k, H+1, 2], log-weights [N, k]) float64: the in-cluster rows
+    scattered by ascending track id, the others their ``cv`` row under the cluster's weight row, the current pose prepended."""
+    in_cluster = np.asarray(in_cluster, dtype=bool)
+    if in_cluster.ndim == 2:
+        parts = [assemble_forecasts(in_cluster[e], sel_or_pos[e], None if logw_in is None else logw_in[e], cv[e], pose_now[e], k, K)
+                 for e in range(in_cluster.shape[0])]
+        return np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts])
+    N = in_cluster.shape[0]
+    ids_in, ids_out = np.nonzero(in_cluster)[0], np.nonzero(~in_cluster)[0]
+    A = len(ids_in)
+    if k < K:
+        rows, lw = np.asarray(sel_or_pos), np.asarray(logw_in).astype(np.float64)
+    else:
+        rows = np.asarray(sel_or_pos).transpose(1, 0, 2, 3)                  # [K, A, H, 2] -> agents by ascending id
+        lw = np.log(np.ones((A, K), dtype=np.float64) / K)
+    H = rows.shape[2]
+    forecasts = np.zeros((N, k, H, 2), dtype=np.float64)
+    logw = np.zeros((N, k), dtype=np.float64)
+    forecasts[ids_in] = rows
+    logw[ids_in] = lw
+    for i in ids_out:
+        forecasts[i] = np.asarray(cv)[int(i)][np.newaxis]
+        logw[i] = lw[0]
+    pose = np.repeat(np.asarray(pose_now, dtype=np.float64)[:, None, None, :], k, axis=1)
+    return np.concatenate((pose, forecasts), axis=2), logw
+
+
 # --------------------------------------------------------------------------------------------- scene batch
 @dataclass
 class SceneBatch:

@@ -1,0 +1,250 @@
+"""The host twins of the device frame table and result assembly (scene.frame_table_frames, frame_table_frames_batched,
+assemble_forecasts; csrc/frames.hpp) against scene.frame_table and the forecaster's own tail, and the inputs of
+tests/test_gpu_frames_device.py, pinned on the host (the cluster margin of tests/test_scene_device_inputs.py)."""
+import inspect
+import os
+
+import numpy as np
+import pytest
+
+from safe_interactive_crowdnav_amd import scene as SC
+from tests.test_scene_device_inputs import DT, F, MARGIN, WRAPPER_CASES, cluster_margin, random_positions
+from tests.test_scene_golden import replay_histories
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def bits_equal(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def as_lists(stamps, hum, rob):
+    """Raw frames as the per-human lists update_state_hists keeps."""
+    R, N = hum.shape[0], hum.shape[1]
+    prev = [[[hum[r, i, 0], hum[r, i, 1], stamps[r]] for r in range(R)] for i in range(N)]
+    return prev, [[rob[r, 0], rob[r, 1], stamps[r]] for r in range(R)]
+
+
+def random_patterns(n=3000, seed=0):
+    """The issue's recipe: R in 1..6, N in 1..5, time_step in {0.25, 0.1, 0.01, 0.4}; by turns exact stamps, stamps early by up to
+    0.04 s, plus one dropped interior frame, plus one stale oldest frame up to 40 steps back, plus one duplicated stamp."""
+    rng = np.random.default_rng(seed)
+    for it in range(n):
+        N = int(rng.integers(1, 6)); R = int(rng.integers(1, 7)); dt = float(rng.choice([0.25, 0.1, 0.01, 0.4]))
+        base = rng.uniform(-50, 50)
+        t = base + np.arange(R) * dt
+        mode = it % 5
+        if mode >= 1:
+            t = t - rng.uniform(0, 0.04, R) * (rng.random(R) < 0.6)
+        if mode >= 2 and R > 2:
+            t = np.delete(t, rng.integers(1, R - 1))
+        if mode == 3 and len(t) > 1:
+            t[0] -= rng.integers(1, 40) * dt
+        if mode == 4 and len(t) > 2:
+            i = rng.integers(0, len(t) - 1)
+            t[i + 1] = t[i]
+        R = len(t)
+        yield t, rng.uniform(-6, 6, (R, N, 2)), rng.uniform(-3, 3, (R, 2)), dt
+
+
+def capture_frames(case):
+    """(fixture, stamps [R], human_xy [R, N, 2], robot_xy [R, 2]) of a reference capture: the last `past` frames, as the FIFO keeps."""
+    z = np.load(os.path.join(GOLDEN, case))
+    past = int(z["past"])
+    return z, z["stamps"][-past:].astype(np.float64), z["human_xy"][-past:].astype(np.float64), z["robot_xy"][-past:].astype(np.float64)
+
+
+def raw_batch(E, R, N, seed, past=F):
+    """Batched raw frames for the device tests: random_positions trajectories sampled at jittered stamps (early by up to 0.04 s on about
+    half the frames), R - past extra old frames in front of which one interior frame per third episode is missing (an interpolated bin),
+    ragged n_frames (past .. R valid frames; the tail of the arrays behind them is NaN and must not be read as data).  The pedestrians
+    stand where random_positions puts them at the last `past` grid times, so the grid inherits its cluster margin (checked below)."""
+    hum6, rob6 = random_positions(E, N, seed)                                # [E, F, N, 2] on the grid
+    rng = np.random.default_rng(seed + 1000)
+    stamps = np.full((E, R), np.nan)
+    hum = np.full((E, R, N, 2), np.nan)
+    rob = np.full((E, R, 2), np.nan)
+    n_frames = np.zeros(E, dtype=np.int32)
+    for e in range(E):
+        extra = int(rng.integers(0, R - past + 1))                           # older frames in front of the grid's six
+        steps = np.arange(-extra, past)                                      # grid step of every pushed frame; >= 0: the last `past`
+        t = 100.0 + e + steps * DT
+        jitter = rng.uniform(0.0, 0.04, len(t)) * (rng.random(len(t)) < 0.5)
+        if extra == 0:
+            jitter[-1] = 0.0             # (an early LAST stamp can pull the oldest of exactly six frames one bin in: a short history)
+        t = t - jitter
+        # positions: the grid's own for steps >= 0, a linear run-in before them
+        h = np.where((steps >= 0)[:, None, None], hum6[e][np.clip(steps, 0, past - 1)],
+                     hum6[e][0][None] + steps[:, None, None] * 0.05)
+        r = np.where((steps >= 0)[:, None], rob6[e][np.clip(steps, 0, past - 1)], rob6[e][0][None] + steps[:, None] * 0.05)
+        if e % 3 == 1:                                                       # a gap: one interior frame of the window never arrived
+            drop = extra + int(rng.integers(1, past - 1))
+            t, h, r = np.delete(t, drop), np.delete(h, drop, axis=0), np.delete(r, drop, axis=0)
+        if e % 5 == 2 and extra >= 2:                                        # ... or one arrived as NaN (dropna)
+            h[0, 0, 0] = np.nan
+        n = len(t)
+        stamps[e, :n], hum[e, :n], rob[e, :n], n_frames[e] = t, h, r, n
+    return stamps, hum, rob, n_frames
+
+
+RAW_SETS = {"spread": (33, 9, 12, 23), "all_lanes": (2, 6, 63, 41)}           # name -> E, R, N, seed
+
+
+# ------------------------------------------------------------------------------------------------ frame_table_frames
+@pytest.mark.parametrize("case", WRAPPER_CASES)
+def test_frames_twin_equals_frame_table_on_the_captures(case):
+    z = np.load(os.path.join(GOLDEN, case))
+    prev, rob = replay_histories(z)
+    want = SC.frame_table(prev, rob, float(z["time_step"]), int(z["past"]))
+    _, st, hum, rb = capture_frames(case)
+    got = SC.frame_table_frames(st, hum, rb, float(z["time_step"]), int(z["past"]))
+    assert all(bits_equal(a, b) for a, b in zip(got, want))
+    fr = SC.histories_as_frames(prev, rob)               # ... and the lists are recognised as frames
+    assert fr is not None and all(bits_equal(a, b) for a, b in zip(fr, (st, hum, rb)))
+
+
+def test_frames_twin_equals_frame_table_on_random_patterns():
+    n = full = bad = 0
+    for t, hum, rob, dt in random_patterns(3000):
+        prev, robs = as_lists(t, hum, rob)
+        want = SC.frame_table(prev, robs, dt, 6)
+        got = SC.frame_table_frames(t, hum, rob, dt, 6)
+        n += 1
+        full += want[0].shape[0] == 6
+        bad += not all(bits_equal(a, b) for a, b in zip(got, want))
+    assert n >= 3000 and bad == 0, f"{bad} of {n} patterns differ"
+    assert full * 4 >= n, f"only {full} of {n} patterns have a full-length history"
+
+
+def test_nan_frames_are_dropped_and_pushes_are_sorted_stably():
+    rng = np.random.default_rng(5)
+    R, N, dt = 8, 3, 0.25
+    t = 3.0 + np.arange(R) * dt
+    hum, rob = rng.uniform(-4, 4, (R, N, 2)), rng.uniform(-2, 2, (R, 2))
+    hum[2, 1, 0] = np.nan                                # a NaN coordinate, a NaN robot coordinate, a NaN stamp
+    rob[4, 1] = np.nan
+    t[5] = np.nan
+    prev, robs = as_lists(t, hum, rob)
+    want = SC.frame_table(prev, robs, dt, 6)
+    got = SC.frame_table_frames(t, hum, rob, dt, 6)
+    assert want[0].shape[0] == 6 and all(bits_equal(a, b) for a, b in zip(got, want))
+    # the last pushed frame as NaN: pose_now is taken before the drop
+    hum[-1, 0, 1] = np.nan
+    got = SC.frame_table_frames(t, hum, rob, dt, 6)
+    want = SC.frame_table(*as_lists(t, hum, rob), dt, 6)
+    assert np.isnan(got[2][0, 1]) and all(bits_equal(a, b) for a, b in zip(got, want))
+    # out-of-order pushes with an equal pair: sorted by stamp, push order among equals (the later push wins the bin)
+    t = np.array([1.0, 0.5, 1.5, 0.75, 1.5, 1.25, 0.25])
+    hum, rob = rng.uniform(-4, 4, (7, N, 2)), rng.uniform(-2, 2, (7, 2))
+    got = SC.frame_table_frames(t, hum, rob, dt, 6)
+    want = SC.frame_table(*as_lists(t, hum, rob), dt, 6)
+    assert all(bits_equal(a, b) for a, b in zip(got, want))
+    assert bits_equal(got[0][-1], hum[4]) and bits_equal(got[0][0], hum[0 + 6]) and bits_equal(got[2], hum[-1])
+    with pytest.raises(SC.HistoryTooShortError):
+        SC.frame_table_frames(np.array([np.nan]), hum[:1], rob[:1], dt, 6)
+
+
+def test_a_stale_frame_does_not_materialise_its_bins():
+    """One frame a year old: frame_table would allocate 1e8 rows; the twin only ever makes the six it returns."""
+    t = np.array([0.0, 3.15e7, 3.15e7 + 0.25, 3.15e7 + 0.5])
+    hum = np.arange(8, dtype=np.float64).reshape(4, 1, 2)
+    rob = np.zeros((4, 2))
+    h, r, pose = SC.frame_table_frames(t, hum, rob, 0.25, 6)
+    assert h.shape == (6, 1, 2) and bits_equal(h[-3:], hum[1:]) and bits_equal(pose, hum[-1])
+    nb = int(3.15e7 * 4) + 3
+    x0, x1, x = 0.0, float(nb - 3), float(nb - 4)
+    assert bits_equal(h[2, 0], (hum[1, 0] - hum[0, 0]) / (x1 - x0) * (x - x0) + hum[0, 0])
+
+
+@pytest.mark.parametrize("name", sorted(RAW_SETS))
+def test_batched_twin_equals_the_per_episode_twin_and_holds_the_margin(name):
+    E, R, N, seed = RAW_SETS[name]
+    stamps, hum, rob, n_frames = raw_batch(E, R, N, seed)
+    assert len(np.unique(n_frames)) > 1 and n_frames.min() >= 5 and n_frames.max() <= R       # ragged
+    b = SC.frame_table_frames_batched(stamps, hum, rob, n_frames, DT, F)
+    assert b["human_xy"].shape == (E, F, N, 2) and b["n_grid"].dtype == np.int32
+    interpolated = 0
+    for e in range(E):
+        n = int(n_frames[e])
+        h, r, pose = SC.frame_table_frames(stamps[e, :n], hum[e, :n], rob[e, :n], DT, F)
+        want = SC.frame_table(*as_lists(stamps[e, :n], hum[e, :n], rob[e, :n]), DT, F)
+        assert all(bits_equal(a, c) for a, c in zip((h, r, pose), want))
+        g = int(b["n_grid"][e])
+        assert g == len(h) and bits_equal(b["human_xy"][e, :g], h) and bits_equal(b["robot_xy"][e, :g], r) and bits_equal(b["pose_now"][e], pose)
+        assert not b["human_xy"][e, g:].any() and not b["robot_xy"][e, g:].any()
+        interpolated += any(not any(bits_equal(h[p], hum[e, j]) for j in range(n)) for p in range(g))     # a row that is no raw frame
+    assert (b["n_grid"] == F).all()                      # every episode of the device sets builds
+    assert interpolated >= 1                             # ... and some of them through an interpolated bin
+    m = cluster_margin(b["human_xy"], b["robot_xy"])
+    assert m.min() > MARGIN, f"{name}: episode {int(m.argmin())} leads by {m.min():.3e} m only"
+    with pytest.raises(ValueError):
+        SC.frame_table_frames_batched(stamps, hum, rob, np.zeros(E, dtype=np.int32), DT, F)
+
+
+def test_histories_that_are_not_frames_are_left_to_the_host_table():
+    t = np.arange(6) * 0.25
+    hum, rob = np.zeros((6, 2, 2)), np.zeros((6, 2))
+    prev, robs = as_lists(t, hum, rob)
+    assert SC.histories_as_frames(prev, robs) is not None
+    assert SC.histories_as_frames(prev, [[9.0, 9.0, -1.0]] + robs) is not None            # the robot's list is unbounded
+    shifted = [list(map(list, h)) for h in prev]
+    shifted[1][2][2] += 0.01
+    assert SC.histories_as_frames(shifted, robs) is None                                  # one human's stamp differs
+    assert SC.histories_as_frames([prev[0], prev[1][1:]], robs) is None                   # ... or its list is shorter
+    assert SC.histories_as_frames(prev, robs[:3]) is None
+    nan_stamp = [list(map(list, h)) for h in prev]
+    for h in nan_stamp:
+        h[1][2] = float("nan")
+    assert SC.histories_as_frames(nan_stamp, robs[:1] + [[0.0, 0.0, float("nan")]] + robs[2:]) is None
+
+
+# ------------------------------------------------------------------------------------------------ assemble_forecasts
+def existing_tail(num_hums, ids_in, ids_out, in_cluster, logw_in, cv, pose_now, k, H):
+    """forecaster._predict_ret_best after its device calls, as it stands."""
+    forecasts = np.zeros((num_hums, k, H, 2), dtype=np.float64)
+    logw = np.zeros((num_hums, k), dtype=np.float64)
+    forecasts[ids_in] = in_cluster
+    logw[ids_in] = logw_in
+    for i in ids_out:
+        forecasts[i] = cv[int(i)][np.newaxis]
+        logw[i] = logw_in[0]
+    pose = np.repeat(pose_now[:, None, None, :], k, axis=1)
+    return np.concatenate((pose, forecasts), axis=2), logw
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_assemble_forecasts_equals_the_existing_tail(full):
+    rng = np.random.default_rng(11)
+    N, K, H = 7, 9, 5
+    k = K if full else 4
+    inc = np.array([1, 0, 1, 1, 0, 0, 1], dtype=bool)
+    ids_in, ids_out = np.nonzero(inc)[0], np.nonzero(~inc)[0]
+    A = len(ids_in)
+    cv, pose_now = rng.standard_normal((N, H, 2)), rng.standard_normal((N, 2))
+    if full:
+        pos = rng.standard_normal((K, A, H, 2)).astype(np.float32)
+        want = existing_tail(N, ids_in, ids_out, pos.transpose(1, 0, 2, 3), np.log(np.ones((A, K), dtype=np.float64) / K), cv, pose_now, k, H)
+        got = SC.assemble_forecasts(inc, pos, None, cv, pose_now, k, K)
+    else:
+        sel = rng.standard_normal((A, k, H, 2)).astype(np.float32)
+        lw = np.repeat(rng.standard_normal((1, k)).astype(np.float32), A, axis=0)
+        want = existing_tail(N, ids_in, ids_out, sel, lw.astype(np.float64), cv, pose_now, k, H)
+        got = SC.assemble_forecasts(inc, sel, lw, cv, pose_now, k, K)
+    assert got[0].shape == (N, k, H + 1, 2) and got[1].shape == (N, k) and got[0].dtype == got[1].dtype == np.float64
+    assert bits_equal(got[0], want[0]) and bits_equal(got[1], want[1])
+    assert bits_equal(got[0][1, :, 1:], np.repeat(cv[1][None], k, axis=0)) and bits_equal(got[0][:, 0, 0], pose_now)
+    # with an episode axis: the per-episode results stacked
+    both = SC.assemble_forecasts(np.stack([inc, inc]), np.stack([pos if full else sel] * 2), None if full else np.stack([lw, lw]),
+                                 np.stack([cv, cv]), np.stack([pose_now, pose_now]), k, K)
+    assert bits_equal(both[0][1], got[0]) and bits_equal(both[1][0], got[1])
+
+
+# ------------------------------------------------------------------------------------------------ opt-in
+def test_device_frames_is_opt_in():
+    from safe_interactive_crowdnav_amd import forecaster as FC
+    assert FC.DEFAULTS["device_frames"] is False
+    p = inspect.signature(FC.HumanTrajectoryForecasterSim.__init__).parameters["device_frames"]
+    assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default is None          # None -> DEFAULTS
+    q = inspect.signature(FC.predict_batch).parameters["device_frames"]
+    assert q.kind is inspect.Parameter.KEYWORD_ONLY and q.default is False

@@ -1,10 +1,11 @@
 """End-to-end latency of HumanTrajectoryForecasterSim.predict_ret_best() (what one MPC step pays), split into
 host preprocessing / encoder / denoise loop / selection + assembly.  Run on the GPU box.
 
-    forecaster_latency.py [--device-scene] [--reps R] [--warmup W] [cfg2 | shipped [R]]
+    forecaster_latency.py [--device-scene | --device-frames] [--reps R] [--warmup W] [cfg2 | shipped [R]]
 
---device-scene builds the scene batch on the device (HumanTrajectoryForecasterSim(device_scene=True)); with a configuration name only
-that one runs and a "RESULT" line with the medians of scene_ms, device_ms and total_ms over the R calls after W warm-ups is printed."""
+--device-scene builds the scene batch on the device (HumanTrajectoryForecasterSim(device_scene=True)), --device-frames the frame table
+too and assembles the result there (device_frames=True); with a configuration name only that one runs and a "RESULT" line with the
+medians of scene_ms, device_ms, assemble_ms and total_ms over the R calls after W warm-ups is printed."""
 import os, sys, tempfile, time
 import numpy as np
 import torch
@@ -20,12 +21,15 @@ class State:
 
 PREC = os.environ.get("JMID_PREC", "f16x3")
 DEVICE_SCENE = False
+DEVICE_FRAMES = False
 
 
 def run(tag, N, K, k_ret, H, step, reps=20, warmup=1):
     d = tempfile.mkdtemp()
     env, ypath = F.write_configs(d, joint=True, ctx_dim=256, N=N, K=K, k_ret=k_ret, H=H, step=step)
     kw = {"device_scene": True} if DEVICE_SCENE else {}
+    if DEVICE_FRAMES:
+        kw["device_frames"] = True
     f = F.HumanTrajectoryForecasterSim(env, ypath, weights=JMIDWeights.from_seed(NetDims(ctx_dim=256), 0), precision=PREC, **kw)
     rng = np.random.default_rng(0)
     p = rng.uniform(-1.5, 1.5, (N, 2)); v = rng.uniform(-0.5, 0.5, (N, 2))
@@ -38,8 +42,8 @@ def run(tag, N, K, k_ret, H, step, reps=20, warmup=1):
         t0 = time.perf_counter(); f.predict_ret_best(); ts.append(time.perf_counter() - t0)
         parts.append(dict(f.timings))
     ts = np.array(ts) * 1e3
-    med = {k: float(np.median([p[k] for p in parts])) for k in ("scene_ms", "device_ms", "total_ms")}
-    print(f"RESULT {tag.split()[0]} device_scene={int(DEVICE_SCENE)} [{PREC}] reps={reps} warmup={warmup}: "
+    med = {k: float(np.median([p[k] for p in parts])) for k in ("scene_ms", "device_ms", "assemble_ms", "total_ms")}
+    print(f"RESULT {tag.split()[0]} device_scene={int(DEVICE_SCENE)} device_frames={int(DEVICE_FRAMES)} [{PREC}] reps={reps} warmup={warmup}: "
           + "  ".join(f"{k} {v:.4f}" for k, v in med.items()) + f"  total_ms p10 {np.percentile(ts, 10):.4f} p90 {np.percentile(ts, 90):.4f}", flush=True)
     print(f"{tag} [{PREC}]: predict_ret_best() median {np.median(ts):.3f} ms  min {ts.min():.3f}  max {ts.max():.3f}   last call: "
           + ", ".join(f"{k} {v:.3f}" for k, v in f.timings.items()), flush=True)
@@ -50,6 +54,9 @@ if __name__ == "__main__":
     if "--device-scene" in sys.argv:
         sys.argv.remove("--device-scene")
         DEVICE_SCENE = True
+    if "--device-frames" in sys.argv:
+        sys.argv.remove("--device-frames")
+        DEVICE_FRAMES = True
     opts = {}
     for name in ("--reps", "--warmup"):
         if name in sys.argv:
