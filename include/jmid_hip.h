@@ -299,7 +299,8 @@ int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float
 /* The scene batch on the device: track positions on the time_step grid in, the encoder's inputs left resident on the handle - what the
  * reference does between update_state_hists and Trajectron.get_latent (mid_sim_wrapper.py:313-437, MID/dataset/preprocessing.py:428-620,
  * MID/environment/scene_graph.py:111-250, the neighbour reductions of MID/models/encoders/mgcvae.py:726-768) for E independent episodes.
- * With this entry a C caller goes from positions to forecasts: build -> draw x_T [E, K * n_in, T, 2] -> jmid_predict_scene.
+ * With this entry a C caller goes from positions to forecasts: build -> draw x_T [E, K * n_in, T, 2] -> jmid_predict_scene, or without a
+ * generator of its own: build -> jmid_predict_scene_seeded (the library draws x_T from its counter generator, "Seeded noise" below).
  *   human_xy  [E, F, N, 2] doubles  pedestrian positions, oldest frame first; F = the handle's hist_len (>= 3), 1 <= N <= 63
  *   robot_xy  [E, F, 2] doubles     robot positions on the same frames
  *   time_step the grid spacing in seconds (velocities and accelerations are first differences divided by it)
@@ -375,6 +376,60 @@ int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_x
  * when the resident scene was built without cv_out, or with a horizon other than T. */
 int jmid_forecast_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
                         double* forecasts_out, double* logw_out);
+
+/* ---- Seeded noise: x_T and the DDPM z from a counter generator on the device ----------------------------------------------------
+ * OPT-IN, and statistically - NOT seed- - compatible with the reference: the reference draws x_T from torch's CPU generator and its
+ * per-step z from the generator of the device it runs on (MID/models/diffusion.py:499, 509), and the explicit-noise entries above keep
+ * that contract (the host draws, the library consumes).  The ADE gate of this project stays defined on identical x_T through those
+ * entries.  The entries below draw from the library's own generator instead, so that a C caller needs no Gaussian generator, a DDPM
+ * call uploads no [n_steps, ...] tensor, and an episode's noise is a pure function of its address - identical for every batch size,
+ * count group, chunk plan, lane and rank.  No generator state lives on the handle.
+ *
+ * Generator: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ * 0xBB67AE85, ten rounds.  Known answer: counter (0, 0, 0, 0), key (0, 0) -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ * Addressing:
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (q, episode_id, draw, 0)
+ *     episode_id  the caller's GLOBAL episode number (uint32): in a sharded sweep the number of the episode in the whole sweep, not
+ *                 its position in the call
+ *     draw        0 = x_T; i + 1 = the z of step-table entry i (entries whose use_noise is 0 keep their number: nothing is drawn
+ *                 for them, and the numbers of the others do not move)
+ *     q           idx / 4, idx = (r * T + t) * 2 + c the row-major element index inside the episode's [rows, T, 2] tensor (rows = K * A
+ *                 in the row order of this header); q must fit 32 bits
+ *     the fourth counter word is reserved and always 0
+ *   The four output words of block q belong to the elements 4q .. 4q + 3; the last block of an episode may be partly used.
+ * Normals: Box-Muller per word pair - (w0, w1) gives the elements 4q and 4q + 1, (w2, w3) the elements 4q + 2 and 4q + 3 - evaluated
+ * in fp64 and rounded once to fp32: for a pair (a, b)
+ *   u1 = (a + 1) * 2^-32,  u2 = b * 2^-32,  r = sqrt(-2 ln u1),  values (r cos(2 pi u2), r sin(2 pi u2))
+ * with 2 pi the fp64 constant 6.283185307179586 multiplied in one rounding, no fast-math and no FMA contraction.  |z| <= 6.67 by
+ * construction.  noise.py restates all of it in NumPy; the two agree to the bit except where the fp64 value lies within the math
+ * libraries' last-place difference of an fp32 rounding boundary (about 1e-8 of the values, one fp32 ulp there).
+ * episode_ids [E] is a HOST array in both memory modes (like the cut-offs of jmid_eval_statistics_masked); the library keeps a
+ * device copy for the duration of the call.
+ *
+ * jmid_noise_fill: one draw for E episodes, out [E, rows, T, 2] (where `mem` says).  JMID_EINVAL: E < 1, rows < 1, T < 1, draw < 0,
+ * NULL episode_ids, NULL out. */
+int jmid_noise_fill(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out, int mem);
+
+/* jmid_denoise or jmid_denoise_ddpm - whichever step table is installed - with the noise drawn by the library: x_T is draw 0, filled
+ * straight into the workspace; under DDPM the z of step-table entry i is draw i + 1, filled on the chunk's own stream just before that
+ * step's update into a one-step buffer per lane - no [n_steps, ...] buffer exists anywhere.  The update kernels are the ones of the
+ * explicit entries (they receive a pointer): the outputs are bit-identical to jmid_denoise / jmid_denoise_ddpm fed the same draws from
+ * jmid_noise_fill.  Same limits and status codes as those entries, JMID_ERANGE and JMID_ETIMEOUT included; the positions stay in the
+ * workspace for jmid_topk(pos = NULL) and the statistics entries exactly as after jmid_denoise.  JMID_EINVAL for NULL episode_ids.
+ * Captured loop ("graph" knob): the x_T fill is an input stage and lies outside the captured loop like the copies of the explicit
+ * entry, and a DDPM loop is never captured - a seeded call gives the same bits with and without capture, and a replay needs no
+ * re-instantiation for a new seed or new ids. */
+int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, const float* ctx,
+                        const float* p0, float dt, int precision, float* vel_out, float* pos_out, int mem);
+
+/* jmid_predict_scene and jmid_forecast_scene with (seed, episode_ids [E]) in place of x_T: x_T is draw 0 with rows = K * A, filled on the
+ * device (nothing but bw is uploaded).  Everything else as their namesakes, whose chain they share: bit-identical to them fed
+ * jmid_noise_fill's draw 0. */
+int jmid_predict_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
+                              int precision, const float* bw, float* sel, float* logw, float* pos_out);
+int jmid_forecast_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
+                               int precision, const float* bw, double* forecasts_out, double* logw_out);
 
 /* The stream (a hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream; NULL = the legacy default
  * stream) that produces the inputs and consumes the outputs of this handle's JMID_MEM_DEVICE calls - see Conventions. */
@@ -453,6 +508,8 @@ int jmid_dbg_plan_chunks_mode(int net_kind, int nhead, int lanes, int chunk_epis
  * group, the shape's tile rows and columns, and the row tile of the first- / second-generation GEMM + LayerNorm kernel for M rows. */
 #define JMID_DBG_GEMM_PLAN_KNOBS 13
 int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int small_now, int one_chunk, const int* knobs, int* plan);
+/* The raw Philox words behind jmid_noise_fill, same addressing: out [E, rows, T, 2] uint32 (where `mem` says). */
+int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem);
 #endif /* JMID_DIAGNOSTICS */
 
 #pragma GCC visibility pop

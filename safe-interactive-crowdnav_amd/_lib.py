@@ -58,6 +58,13 @@ SIGNATURES = {
     "jmid_scene_get_frames": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "jmid_forecast_scene": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "jmid_noise_fill": (C.c_int, [Handle, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "jmid_denoise_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_predict_scene_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jmid_forecast_scene_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_set_chunk_episodes": (C.c_int, [Handle, C.c_int]),
     "jmid_set_tuning": (C.c_int, [Handle, C.c_char_p, C.c_int]),
     "jmid_set_caller_stream": (C.c_int, [Handle, C.c_void_p]),
@@ -83,6 +90,7 @@ DIAG_SIGNATURES = {
     "jmid_dbg_plan_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "jmid_dbg_plan_chunks_mode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "jmid_dbg_gemm_plan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "jmid_dbg_noise_words": (C.c_int, [Handle, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
 }
 
 

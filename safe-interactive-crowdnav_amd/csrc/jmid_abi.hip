@@ -73,9 +73,10 @@ int ensure_pin(jmid_ctx* h, size_t need, const char* who) {
 // the in-cluster rows of the resident scene are gathered on the device instead (x_T and bw are the whole upload).
 // fc_out (scene mode only; jmid_forecast_scene): assemble_kernel follows on the stream and the download is forecasts [E, N, k, T+1, 2] and
 // logw [E, N, k] doubles instead of sel / logw / pos, which then never leave the device.
+// seeded (scene mode only; the *_seeded entries): x_T is null and its slot of the device block is filled there, draw 0 of noise.hpp.
 int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask, const float* x_T,
                   const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out, bool scene, const char* who,
-                  double* fc_out = nullptr, double* lwd_out = nullptr) {
+                  double* fc_out = nullptr, double* lwd_out = nullptr, const SeedArgs* seeded = nullptr) {
     const bool rank = k < K;
     const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
     const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
@@ -99,7 +100,7 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
     if (int rc = ensure_pin(h, (in_floats + out_floats) * 4, who)) return rc;
     float* pin = reinterpret_cast<float*>(h->pin);
     float* dev = reinterpret_cast<float*>(h->io_dev);
-    std::memcpy(pin + o_xT, x_T, n_xT * 4);
+    if (!seeded) std::memcpy(pin + o_xT, x_T, n_xT * 4);
     if (n_bw) std::memcpy(pin + o_bw, bw, n_bw * 4);
     if (!scene) {
         std::memcpy(pin + o_xs, x_st, n_xs * 4);
@@ -109,7 +110,12 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
         HIPCHK(h, hipMemcpyAsync(dev, pin, in_floats * 4, hipMemcpyHostToDevice, h->stream));
     } else {
         // x_T ... bw in one copy (the p0 slot between them is written by the gather below, after the copy on the stream)
-        HIPCHK(h, hipMemcpyAsync(dev + o_xT, pin + o_xT, (in_floats - o_xT) * 4, hipMemcpyHostToDevice, h->stream));
+        if (!seeded) HIPCHK(h, hipMemcpyAsync(dev + o_xT, pin + o_xT, (in_floats - o_xT) * 4, hipMemcpyHostToDevice, h->stream));
+        else if (n_bw) HIPCHK(h, hipMemcpyAsync(dev + o_bw, pin + o_bw, n_bw * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (seeded) {
+        if (int rc = upload_noise_ids(h, seeded->ids, E)) return rc;
+        if (int rc = fill_noise(h, seeded->seed, h->noise_ids, E, (size_t)K * A * T * 2, 0, dev + o_xT, nullptr, h->stream)) return rc;
     }
     int rc = 0;
     h->chained = true;
@@ -277,10 +283,10 @@ int build_scene_resident(jmid_ctx* h, int E, int N, int F, const double* human_x
 }
 
 // the refusals jmid_predict_scene and jmid_forecast_scene share
-int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K, int T, int k, const float* x_T) {
+int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K, int T, int k, const void* noise) {
     if (int rc = check_ready(h)) return rc;
     if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, who + ": bad dimensions");
-    if (!x_T) return fail(h, JMID_EINVAL, who + ": null input");
+    if (!noise) return fail(h, JMID_EINVAL, who + ": null input");            // x_T, or the episode ids of a seeded call
     const jmid_ctx::SceneWs& sc = h->scene;
     if (!sc.E) return fail(h, JMID_EINVAL, who + " needs a preceding jmid_build_scene on this handle");
     if (E != sc.E) return fail(h, JMID_EINVAL, who + ": E differs from the resident scene's");
@@ -291,6 +297,55 @@ int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K
     if (k < K && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, who + ": the device top-k supports A <= 32, K <= 1024, T <= 24");
     if (h->ddpm) return fail(h, JMID_EINVAL, who + " samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
     return 0;
+}
+
+// jmid_predict_scene / jmid_forecast_scene and their seeded forms: one chain, the noise either the caller's x_T or (seed, ids)
+int predict_scene_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, int k, const float* x_T, const SeedArgs* seeded, float dt,
+                               int precision, const float* bw, float* sel, float* logw, float* pos_out, double* forecasts_out, double* logw_out,
+                               bool forecast) {
+    if (!h) return JMID_EINVAL;
+    const std::string w(who);
+    if (int rc = check_predict_scene(h, w, E, A, K, T, k, seeded ? (const void*)seeded->ids : (const void*)x_T)) return rc;
+    if (seeded && !noise_fits((unsigned long long)K * A * T * 2)) return fail(h, JMID_EINVAL, w + ": K * A * T exceeds the noise addressing");
+    if (forecast) {
+        if (!forecasts_out || !logw_out) return fail(h, JMID_EINVAL, w + ": null output");
+        if (!h->scene.horizon) return fail(h, JMID_EINVAL, w + ": the resident scene was built without cv_out (the rows outside the cluster need it)");
+        if (h->scene.horizon != T)
+            return fail(h, JMID_EINVAL, w + ": T = " + std::to_string(T) + " differs from the horizon " + std::to_string(h->scene.horizon) +
+                                            " the resident scene was built with");
+    } else {
+        const bool rank = k < K;
+        if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, w + ": k < K needs sel and logw");
+        if (!rank && !pos_out) return fail(h, JMID_EINVAL, w + ": k == K needs pos_out");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, true, who, forecasts_out, logw_out,
+                         seeded);
+}
+
+// jmid_noise_fill and jmid_dbg_noise_words: one draw to the caller's buffer (normals or raw words; 4 bytes per element either way)
+int noise_entry(jmid_handle_t h, const char* who, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out,
+                unsigned* words, int mem) {
+    if (!h) return JMID_EINVAL;
+    const std::string w(who);
+    if (E < 1 || rows < 1 || T < 1 || draw < 0) return fail(h, JMID_EINVAL, w + ": E, rows, T must be at least 1 and draw at least 0");
+    if (!episode_ids || (!out && !words)) return fail(h, JMID_EINVAL, w + ": null argument");
+    const size_t n = (size_t)rows * T * 2;
+    if (!noise_fits(n)) return fail(h, JMID_EINVAL, w + ": rows * T exceeds the noise addressing");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = order_in(h, mem)) return rc;
+    if (int rc = upload_noise_ids(h, episode_ids, E)) return rc;
+    void* dst = out ? (void*)out : (void*)words;
+    if (mem == JMID_MEM_HOST) {      // staged in the handle's second workspace (the arena may hold the last call's positions)
+        if (int rc = ensure_kde_ws(h, (size_t)E * n * 4, who)) return rc;
+        dst = h->kde_ws;
+    }
+    if (int rc = fill_noise(h, seed, h->noise_ids, E, n, draw, out ? (float*)dst : nullptr, words ? (unsigned*)dst : nullptr, h->stream)) return rc;
+    if (mem == JMID_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(out ? (void*)out : (void*)words, dst, (size_t)E * n * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return order_out(h, mem);
 }
 
 }  // namespace jmid_host
@@ -392,6 +447,9 @@ int jmid_destroy(jmid_handle_t h) {
     if (h->arena) hipFree(h->arena);
     if (h->kde_ws) hipFree(h->kde_ws);
     if (h->scene.dev) hipFree(h->scene.dev);
+    if (h->noise_ids) hipFree(h->noise_ids);
+    if (h->noise_ids_pin) (void)hipHostFree(h->noise_ids_pin);
+    if (h->ev_ids) hipEventDestroy(h->ev_ids);
     if (h->frames_dev) hipFree(h->frames_dev);
     for (int c = 0; c < KC_COUNT; ++c)
         for (auto& ev : h->prof_ev[c]) {
@@ -852,27 +910,38 @@ int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float
 
 int jmid_predict_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw, float* sel,
                        float* logw, float* pos_out) {
-    if (!h) return JMID_EINVAL;
-    if (int rc = check_predict_scene(h, "jmid_predict_scene", E, A, K, T, k, x_T)) return rc;
-    const bool rank = k < K;
-    if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, "jmid_predict_scene: k < K needs sel and logw");
-    if (!rank && !pos_out) return fail(h, JMID_EINVAL, "jmid_predict_scene: k == K needs pos_out");
-    HIPCHK(h, hipSetDevice(h->device));
-    return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, true, "jmid_predict_scene");
+    return predict_scene_entry(h, "jmid_predict_scene", E, A, K, T, k, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr, false);
 }
 
 int jmid_forecast_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
                         double* forecasts_out, double* logw_out) {
+    return predict_scene_entry(h, "jmid_forecast_scene", E, A, K, T, k, x_T, nullptr, dt, precision, bw, nullptr, nullptr, nullptr, forecasts_out,
+                               logw_out, true);
+}
+
+int jmid_predict_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt, int precision,
+                              const float* bw, float* sel, float* logw, float* pos_out) {
+    const SeedArgs sa{seed, episode_ids};
+    return predict_scene_entry(h, "jmid_predict_scene_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr, false);
+}
+
+int jmid_forecast_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt, int precision,
+                               const float* bw, double* forecasts_out, double* logw_out) {
+    const SeedArgs sa{seed, episode_ids};
+    return predict_scene_entry(h, "jmid_forecast_scene_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, nullptr, nullptr, nullptr, forecasts_out,
+                               logw_out, true);
+}
+
+int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, const float* ctx, const float* p0,
+                        float dt, int precision, float* vel_out, float* pos_out, int mem) {
     if (!h) return JMID_EINVAL;
-    if (int rc = check_predict_scene(h, "jmid_forecast_scene", E, A, K, T, k, x_T)) return rc;
-    if (!forecasts_out || !logw_out) return fail(h, JMID_EINVAL, "jmid_forecast_scene: null output");
-    if (!h->scene.horizon) return fail(h, JMID_EINVAL, "jmid_forecast_scene: the resident scene was built without cv_out (the rows outside the cluster need it)");
-    if (h->scene.horizon != T)
-        return fail(h, JMID_EINVAL, "jmid_forecast_scene: T = " + std::to_string(T) + " differs from the horizon " + std::to_string(h->scene.horizon) +
-                                        " the resident scene was built with");
-    HIPCHK(h, hipSetDevice(h->device));
-    return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, nullptr, nullptr, nullptr, true,
-                         "jmid_forecast_scene", forecasts_out, logw_out);
+    if (!episode_ids) return fail(h, JMID_EINVAL, "jmid_denoise_seeded: null episode_ids");
+    const SeedArgs sa{seed, episode_ids};
+    return run_network(h, E, A, K, T, nullptr, ctx, p0, dt, precision, -1, vel_out, pos_out, nullptr, mem, nullptr, &sa);
+}
+
+int jmid_noise_fill(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out, int mem) {
+    return noise_entry(h, "jmid_noise_fill", seed, E, rows, T, episode_ids, draw, out, nullptr, mem);
 }
 
 int jmid_set_chunk_episodes(jmid_handle_t h, int episodes) {

@@ -31,6 +31,7 @@
 #include "gemm_f32.hpp"
 #include "kde.hpp"
 #include "launch_plan.hpp"
+#include "noise.hpp"
 #include "scene.hpp"
 #include "frames.hpp"
 
@@ -145,6 +146,11 @@ struct jmid_ctx {
     // a build that ends with JMID_EHISTORY must not touch the resident scene
     char* frames_dev = nullptr;
     size_t frames_bytes = 0;
+    // the seeded entry points: the call's episode ids on the device (the fill kernel reads them there), grown on demand
+    unsigned* noise_ids = nullptr;
+    int noise_ids_cap = 0;
+    unsigned* noise_ids_pin = nullptr;       // pinned staging of the ids: a device-mode call may return before its copies have run, and the
+    hipEvent_t ev_ids = nullptr;             // caller's array need not outlive the call; ev_ids = the last upload has left the staging
     bool chained = false;       // the running run_network is a stage of jmid_predict: no caller-stream ordering, no flag round trip
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)
@@ -264,11 +270,21 @@ std::vector<int> plan_chunks(const jmid_ctx* h, int E, int tokens_per_episode);
 int check_ready(jmid_ctx* h);
 int order_in(jmid_ctx* h, int mem);
 int order_out(jmid_ctx* h, int mem);
+// seeded noise of a call (noise.hpp): x_T is draw 0 and the z of step-table entry i draw i + 1, filled on the device; `ids` [E] is a HOST array
+struct SeedArgs {
+    uint64_t seed;
+    const uint32_t* ids;
+};
+int upload_noise_ids(jmid_ctx* h, const uint32_t* ids, int E);      // -> h->noise_ids, on h->stream
+int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream);
 int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, const float* ctx, const float* p0, float dt,
                 int precision, int single_step, float* vel_out, float* pos_out, float* e_out, int mem,
-                const float* z_in = nullptr);
+                const float* z_in = nullptr, const SeedArgs* seeded = nullptr);
 int flagged_call(jmid_ctx* h, int flag);      // the status of a call whose range flag came back set (JMID_ETIMEOUT / JMID_ERANGE)
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T);
+// jmid_abi.hip
+int noise_entry(jmid_ctx* h, const char* who, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out,
+                unsigned* words, int mem);
 // jmid_profile.hip
 int prof_collect(jmid_ctx* h);
 

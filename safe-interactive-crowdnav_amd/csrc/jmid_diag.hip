@@ -286,6 +286,10 @@ int jmid_dbg_add_layernorm(jmid_handle_t h, int M, int d, float* X, const float*
     return rc;
 }
 
+int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem) {
+    return noise_entry(h, "jmid_dbg_noise_words", seed, E, rows, T, episode_ids, draw, nullptr, out, mem);
+}
+
 }  // extern "C"
 #endif  // JMID_DIAGNOSTICS
 

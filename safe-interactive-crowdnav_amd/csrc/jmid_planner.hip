@@ -453,9 +453,44 @@ int check_ready(jmid_ctx* h) {
     return 0;
 }
 
+// The episode ids of a seeded call, from the caller's HOST array into the handle's device buffer, on h->stream (every fill of the call
+// is ordered behind it: the lanes fork from h->stream afterwards).
+int upload_noise_ids(jmid_ctx* h, const uint32_t* ids, int E) {
+    if (!h->ev_ids) HIPCHK(h, hipEventCreateWithFlags(&h->ev_ids, hipEventDisableTiming));
+    if (E > h->noise_ids_cap) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->noise_ids) HIPCHK(h, hipFree(h->noise_ids));
+        if (h->noise_ids_pin) HIPCHK(h, hipHostFree(h->noise_ids_pin));
+        h->noise_ids = h->noise_ids_pin = nullptr;
+        h->noise_ids_cap = 0;
+        const int cap = std::max(E, 64);
+        if (hipMalloc((void**)&h->noise_ids, (size_t)cap * sizeof(unsigned)) != hipSuccess ||
+            hipHostMalloc((void**)&h->noise_ids_pin, (size_t)cap * sizeof(unsigned), hipHostMallocDefault) != hipSuccess)
+            return fail(h, JMID_ENOMEM, "episode id buffer allocation failed");
+        h->noise_ids_cap = cap;
+    } else {
+        HIPCHK(h, hipEventSynchronize(h->ev_ids));       // the previous upload has read the staging (an event never recorded is complete)
+    }
+    std::memcpy(h->noise_ids_pin, ids, (size_t)E * sizeof(unsigned));
+    HIPCHK(h, hipMemcpyAsync(h->noise_ids, h->noise_ids_pin, (size_t)E * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev_ids, h->stream));
+    return 0;
+}
+
+// One draw for E episodes of n elements each (noise.hpp): normals to `out` and / or the raw words to `words`, device buffers.
+int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream) {
+    NoiseArgs g{};
+    g.ids = ids_dev; g.out = out; g.words = words;
+    g.n = n; g.E = E;
+    g.key0 = (unsigned)(seed & 0xffffffffull); g.key1 = (unsigned)(seed >> 32);
+    g.draw = (unsigned)draw;
+    HIPCHK(h, launch_noise(g, stream));
+    return 0;
+}
+
 int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, const float* ctx, const float* p0, float dt,
                 int precision, int single_step, float* vel_out, float* pos_out, float* e_out, int mem,
-                const float* z_in) {
+                const float* z_in, const SeedArgs* seeded) {
     if (int rc = check_ready(h)) return rc;
     if (E <= 0 || A <= 0 || K <= 0 || T <= 0) return fail(h, JMID_EINVAL, "E, A, K, T must be positive");
     if (T > 24) return fail(h, JMID_EINVAL, "T exceeds the positional-encoding table (max_len=24, diffusion.py:116-118)");
@@ -465,10 +500,12 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     h->x2 = precision == JMID_PREC_F16X2 || h->mx;
     if (precision != JMID_PREC_F32 && !h->weights_in_half_range && ++h->erange_calls)
         return fail(h, JMID_ERANGE, "a weight exceeds the fp16 range: use JMID_PREC_F32");
-    if (!x_in || !ctx) return fail(h, JMID_EINVAL, "null input");
+    if ((!x_in && !seeded) || !ctx) return fail(h, JMID_EINVAL, "null input");
+    if (seeded && !seeded->ids) return fail(h, JMID_EINVAL, "null episode_ids");
+    if (seeded && !noise_fits((unsigned long long)K * A * T * 2)) return fail(h, JMID_EINVAL, "K * A * T exceeds the noise addressing");
     if (pos_out && !p0) return fail(h, JMID_EINVAL, "pos_out requested without p0");
     h->last_pos = nullptr;     // (the staging buffer is about to be reused)
-    if (single_step < 0 && h->ddpm && !z_in) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
+    if (single_step < 0 && h->ddpm && !z_in && !seeded) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
     if (single_step < 0 && !h->ddpm && z_in) return fail(h, JMID_EINVAL, "jmid_denoise_ddpm needs jmid_set_ddpm_table");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
@@ -493,6 +530,10 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         ns_call = attn_pick_nsplit(((S + 127) / 128) * h->nhead * (E >= 2 ? (one_launch_shape(h, (long)E * S) ? E : (c_auto + 1) / 2) : 1), S);
         if (h->tune.attn_nsplit > 0) ns_call = std::min(h->tune.attn_nsplit, (S + 31) / 32);
     }
+    const int nchunks = (int)chunk_sizes.size();
+    const int lanes = single_step < 0 ? std::max(1, std::min(h->lanes, nchunks)) : 1;
+    // seeded DDPM: the z of ONE step per lane, filled on that lane's stream just before the step's update (no [n_steps, ...] buffer)
+    const bool z_fill = seeded && h->ddpm && single_step < 0;
     // ---- workspace
     size_t io_off;
     {
@@ -503,14 +544,13 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         c.take(EA * 2);                // p0
         c.take(M * 2);                 // e / pos staging
         if (z_in && mem == JMID_MEM_HOST) c.take(M * 2 * h->beta.size());   // DDPM noise
+        if (z_fill) c.take((size_t)lanes * Mc * 2);
         io_off = c.off;
     }
     const SeqGeom sg_full = seq_geom(h, Ec, A, K, T);
     // Independent chunks run `lanes` at a time on separate streams: the partially filled last round of one chunk's
     // kernels and its bandwidth-bound kernels overlap with another chunk's MFMA kernels.  Each lane has its own step
     // workspace; results do not depend on the number of lanes.
-    const int nchunks = (int)chunk_sizes.size();
-    const int lanes = single_step < 0 ? std::max(1, std::min(h->lanes, nchunks)) : 1;
     // one plan per distinct chunk size of the call (the knobs and lnx_off cannot change while it runs): net_step only executes it.
     // The small-launch GEMMs (gemm_small.hpp: one workgroup per CU, most of its LDS) only while one chunk is in flight
     CallFacts facts;
@@ -540,6 +580,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         HIPCHK(h, hipMemcpyAsync(zd, z_in, M * 2 * h->beta.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
         z_use = zd;
     }
+    float* z_lane = z_fill ? c.take((size_t)lanes * Mc * 2) : nullptr;
     StepBuffers sbs[jmid_ctx::kMaxLanes];
     for (int l = 0; l < lanes; ++l) step_ws_floats(h, Mc, precision, sg_full, ns_call, &sbs[l], h->arena + io_off + l * lane_floats);
     const StepBuffers& sb = sbs[0];
@@ -555,7 +596,12 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
 
     const hipMemcpyKind kin = mem == JMID_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     const hipMemcpyKind kout = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIPCHK(h, hipMemcpyAsync(x_cur, x_in, M * 2 * sizeof(float), kin, h->stream));
+    if (seeded) {
+        if (int rc = upload_noise_ids(h, seeded->ids, E)) return rc;
+        if (int rc = fill_noise(h, seeded->seed, h->noise_ids, E, (size_t)K * A * T * 2, 0, x_cur, nullptr, h->stream)) return rc;
+    } else {
+        HIPCHK(h, hipMemcpyAsync(x_cur, x_in, M * 2 * sizeof(float), kin, h->stream));
+    }
     const float* ctx_use = ctx;
     if (mem == JMID_MEM_HOST) {
         HIPCHK(h, hipMemcpyAsync(ctx_d, ctx, EA * h->ctx_dim * sizeof(float), kin, h->stream));
@@ -622,7 +668,13 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
                 const float* hc = hyp + (size_t)el * A * h->hl.total;
                 const float* zc = z_use ? z_use + ((size_t)i * M + (size_t)el * K * A * T) * 2 : nullptr;
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);   // net_step launches on h->stream
-                const int rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, h->tune.fuse_embed && i > 0,
+                int rc = 0;
+                if (z_fill && h->p_noise[i]) {      // this step's draw for the chunk's episodes, on the chunk's own stream
+                    float* zl = z_lane + (size_t)l * Mc * 2;
+                    rc = fill_noise(h, seeded->seed, h->noise_ids + el, chunk_sizes[c0 + l], (size_t)K * A * T * 2, i + 1, zl, nullptr, h->stream);
+                    zc = zl;
+                }
+                if (!rc) rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, h->tune.fuse_embed && i > 0,
                                         h->tune.fuse_embed && i + 1 < n_steps ? i + 1 : -1);
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);
                 if (rc) {

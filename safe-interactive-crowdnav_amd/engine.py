@@ -35,6 +35,30 @@ def _is_cuda(t) -> bool:
     return torch is not None and isinstance(t, torch.Tensor) and t.is_cuda
 
 
+def seeded_noise_args(x_T, seed, episode_ids, E: Optional[int] = None):
+    """The noise source of a call: either the caller's ``x_T`` or ``seed`` + ``episode_ids`` (the library's counter generator,
+    ``noise.py``), never both.  -> None for an explicit call, else (seed, ids uint32 [E])."""
+    if seed is None:
+        if episode_ids is not None:
+            raise ValueError("episode_ids needs seed")
+        if x_T is None:
+            raise ValueError("either x_T or seed + episode_ids")
+        return None
+    if x_T is not None:
+        raise ValueError("x_T and seed are mutually exclusive: a seeded call draws x_T itself")
+    if episode_ids is None:
+        raise ValueError("seed needs episode_ids (the global number of every episode of the call)")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must fit 64 bits")
+    ids = np.atleast_1d(np.asarray(episode_ids))
+    if ids.ndim != 1 or (E is not None and ids.size != E) or ids.size < 1:
+        raise ValueError("episode_ids must hold one id per episode")
+    if np.any(ids.astype(np.int64) < 0) or np.any(ids.astype(np.int64) > 0xFFFFFFFF):
+        raise ValueError("episode ids are uint32")
+    return seed, np.ascontiguousarray(ids, dtype=np.uint32)
+
+
 class _Buf:
     """fp32 contiguous view of an input + its raw pointer."""
 
@@ -180,28 +204,64 @@ class JmidEngine:
             raise ValueError("ctx width / row count mismatch")
         return E, A, KA // A, T
 
-    def denoise(self, x_T: ArrayLike, ctx: ArrayLike, p0: Optional[ArrayLike] = None, dt: float = 0.25,
-                precision: str = "f32", want_vel: bool = True, want_pos: bool = True, z: Optional[ArrayLike] = None):
+    def noise(self, seed: int, episode_ids, rows: int, T: int, draw: int = 0, device: bool = False, words: bool = False):
+        """One draw of the library's counter generator (``jmid_noise_fill``; host twin ``noise.normal``): standard normals float32
+        [E, rows, T, 2] for the episodes ``episode_ids`` - draw 0 is the x_T of a seeded call with rows = K * A, draw i + 1 the z of
+        step-table entry i.  ``device=True``: a CUDA tensor.  ``words=True`` (diagnostics flavour): the raw Philox words, uint32."""
+        seed, ids = seeded_noise_args(None, seed, episode_ids)
+        E = int(ids.size)
+        shape = (E, int(rows), int(T), 2)
+        if device:
+            out = torch.empty(shape, dtype=torch.int32 if words else torch.float32, device=f"cuda:{self.device_id}")
+            optr = C.c_void_p(out.data_ptr())
+        else:
+            out = np.empty(shape, dtype=np.uint32 if words else np.float32)
+            optr = C.c_void_p(out.ctypes.data)
+        fn = self._lib.jmid_dbg_noise_words if words else self._lib.jmid_noise_fill
+        self._check(fn(self._h, seed, E, int(rows), int(T), C.c_void_p(ids.ctypes.data), int(draw), optr, self._mem(bool(device))))
+        return out
+
+    def denoise(self, x_T: Optional[ArrayLike], ctx: ArrayLike, p0: Optional[ArrayLike] = None, dt: float = 0.25,
+                precision: str = "f32", want_vel: bool = True, want_pos: bool = True, z: Optional[ArrayLike] = None,
+                seed: Optional[int] = None, episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
         """Batched reverse-denoising loop.  x_T [E, K*A, T, 2], ctx [E, A, ctx_dim], p0 [E, A, 2].
         ``z`` [n_steps, E, K*A, T, 2]: per-step normal draws, required when the DDPM table is installed.
+        ``seed`` + ``episode_ids`` [E] (with ``x_T=None`` and the sample count ``K`` and horizon ``T``): the library draws x_T - and,
+        under the DDPM table, every step's z - from its counter generator (``jmid_denoise_seeded``; ``noise.py``): the same bits as the
+        explicit call fed ``noise(seed, episode_ids, K * A, T, draw)``, for every batch the episodes are part of.
         Returns (vel [E,K,A,T,2] or None, pos [E,K,A,T,2] or None)."""
-        dev = _is_cuda(x_T)
-        E, A, K, T = self._shapes(x_T, ctx)
+        seeded = seeded_noise_args(x_T, seed, episode_ids)
+        if seeded is not None:
+            if z is not None:
+                raise ValueError("z and seed are mutually exclusive: a seeded call draws z itself")
+            if K is None or T is None or ctx.ndim != 3 or int(ctx.shape[2]) != self.dims.ctx_dim:
+                raise ValueError("a seeded call needs K, T and ctx [E, A, ctx_dim]")
+            dev = _is_cuda(ctx)
+            E, A, K, T = int(ctx.shape[0]), int(ctx.shape[1]), int(K), int(T)
+            seeded = seeded_noise_args(None, seed, episode_ids, E)
+            x_like = ctx
+        else:
+            dev = _is_cuda(x_T)
+            E, A, K, T = self._shapes(x_T, ctx)
+            x_like = x_T
         want_pos = want_pos and p0 is not None
-        bx, bc = _Buf(x_T, dev), _Buf(ctx, dev)
+        bx, bc = (_Buf(x_T, dev) if seeded is None else None), _Buf(ctx, dev)
         bp = _Buf(p0, dev) if p0 is not None else None
         shape = (E, K, A, T, 2)
 
         def alloc():
             if dev:
-                t = torch.empty(shape, dtype=torch.float32, device=x_T.device)
+                t = torch.empty(shape, dtype=torch.float32, device=x_like.device)
                 return t, C.c_void_p(t.data_ptr())
             t = np.empty(shape, dtype=np.float32)
             return t, C.c_void_p(t.ctypes.data)
 
         vel, vptr = alloc() if want_vel else (None, None)
         pos, pptr = alloc() if want_pos else (None, None)
-        if z is not None:
+        if seeded is not None:
+            self._compute(self._lib.jmid_denoise_seeded, self._h, E, A, K, T, seeded[0], C.c_void_p(seeded[1].ctypes.data), bc.ptr,
+                          bp.ptr if bp else None, float(dt), _lib.PRECISIONS[precision], vptr, pptr, self._mem(dev))
+        elif z is not None:
             if tuple(z.shape) != (self.n_steps, E, K * A, T, 2):
                 raise ValueError("z must be [n_steps, E, K*A, T, 2]")
             bz = _Buf(z, dev)
@@ -309,32 +369,45 @@ class JmidEngine:
         self._check(self._lib.jmid_scene_get(self._h, *[C.c_void_p(a.ctypes.data) for a in out.values()], _lib.MEM_HOST))
         return {k: v[0] for k, v in out.items()} if single else out
 
-    def predict_scene(self, x_T: np.ndarray, k: int, dt: float = 0.25, precision: str = "f32"):
-        """``predict`` on the scene the preceding ``build_scene`` left on the device (``jmid_predict_scene``): x_T [E, K*A, T, 2] with A the
-        in-cluster count of EVERY episode (``n_in``) and ``k`` kept futures of the K.  k < K -> (kept [E, A, k, T, 2], log-weights
-        [E, A, k]); k == K -> (pos [E, K, A, T, 2], None).  The same bits as ``predict`` fed the in-cluster rows of ``scene_arrays``."""
-        import math
+    def _scene_noise(self, x_T, seed, episode_ids, K, T):
+        """What predict_scene / forecast_scene share: (E, A, K, T, the library entry's name suffix, its noise arguments, and the
+        array those point into - the caller keeps it alive over the call)."""
+        # A = the first episode's count (the library refuses the call when another episode's differs, or when nothing is resident)
+        n_in = getattr(self, "_scene_n_in", None)
+        A = int(n_in[0]) if n_in is not None and len(n_in) and n_in[0] > 0 else 1
+        seeded = seeded_noise_args(x_T, seed, episode_ids)
+        if seeded is not None:
+            if K is None or T is None:
+                raise ValueError("a seeded call needs K and T")
+            return int(seeded[1].size), A, int(K), int(T), "_seeded", (seeded[0], C.c_void_p(seeded[1].ctypes.data)), seeded[1]
         x_T = np.asarray(x_T)
         if x_T.ndim != 4 or x_T.shape[-1] != 2:
             raise ValueError("expected x_T [E, K*A, T, 2]")
         E, KA, T, _ = (int(v) for v in x_T.shape)
-        k = int(k)
-        # A = the first episode's count (the library refuses the call when another episode's differs, or when nothing is resident)
-        n_in = getattr(self, "_scene_n_in", None)
-        A = int(n_in[0]) if n_in is not None and len(n_in) and n_in[0] > 0 else 1
         if KA % A != 0:
             raise ValueError(f"x_T has {KA} rows per episode: not a multiple of the scene's {A} in-cluster pedestrians")
-        K = KA // A
         bx = _Buf(x_T, False)
+        return E, A, KA // A, T, "", (bx.ptr,), bx
+
+    def predict_scene(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
+                      episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+        """``predict`` on the scene the preceding ``build_scene`` left on the device (``jmid_predict_scene``): x_T [E, K*A, T, 2] with A the
+        in-cluster count of EVERY episode (``n_in``) and ``k`` kept futures of the K.  k < K -> (kept [E, A, k, T, 2], log-weights
+        [E, A, k]); k == K -> (pos [E, K, A, T, 2], None).  The same bits as ``predict`` fed the in-cluster rows of ``scene_arrays``.
+        ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is drawn on the device (``jmid_predict_scene_seeded``)."""
+        import math
+        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T)
+        k = int(k)
+        fn = getattr(self._lib, "jmid_predict_scene" + sfx)
         if k < K:
             bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
             sel = np.empty((E, A, k, T, 2), dtype=np.float32)
             lw = np.empty((E, A, k), dtype=np.float32)
-            self._compute(self._lib.jmid_predict_scene, self._h, E, A, K, T, k, bx.ptr, float(dt), _lib.PRECISIONS[precision],
+            self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision],
                           C.c_void_p(bw.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data), None)
             return sel, lw
         pos = np.empty((E, K, A, T, 2), dtype=np.float32)
-        self._compute(self._lib.jmid_predict_scene, self._h, E, A, K, T, k, bx.ptr, float(dt), _lib.PRECISIONS[precision], None, None, None,
+        self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision], None, None, None,
                       C.c_void_p(pos.ctypes.data))
         return pos, None
 
@@ -391,31 +464,25 @@ class JmidEngine:
         self._check(self._lib.jmid_scene_get_frames(self._h, *[C.c_void_p(a.ctypes.data) for a in out.values()], _lib.MEM_HOST))
         return {k: v[0] for k, v in out.items()} if single else out
 
-    def forecast_scene(self, x_T: np.ndarray, k: int, dt: float = 0.25, precision: str = "f32"):
+    def forecast_scene(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
+                       episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
         """``predict_scene`` followed by the result assembly on the device (``jmid_forecast_scene``; the twin of
         ``scene.assemble_forecasts``): x_T [E, K*A, T, 2] -> (forecasts [E, N, k, T+1, 2], log-weights [E, N, k]) float64, per episode
         exactly what ``predict_ret_best()`` returns.  The resident scene must have been built with ``horizon`` = T.  After a one-scene
-        build the episode axis of the results is absent."""
+        build the episode axis of the results is absent.  ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is
+        drawn on the device (``jmid_forecast_scene_seeded``)."""
         import math
-        x_T = np.asarray(x_T)
-        if x_T.ndim != 4 or x_T.shape[-1] != 2:
-            raise ValueError("expected x_T [E, K*A, T, 2]")
-        E, KA, T, _ = (int(v) for v in x_T.shape)
+        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T)
         k = int(k)
-        n_in = getattr(self, "_scene_n_in", None)
-        A = int(n_in[0]) if n_in is not None and len(n_in) and n_in[0] > 0 else 1
-        if KA % A != 0:
-            raise ValueError(f"x_T has {KA} rows per episode: not a multiple of the scene's {A} in-cluster pedestrians")
-        K = KA // A
+        fn = getattr(self._lib, "jmid_forecast_scene" + sfx)
         shape = getattr(self, "_scene_shape", None)
         N, single = (shape[1], shape[3]) if shape is not None else (1, False)
-        bx = _Buf(x_T, False)
         bw = None
         if k < K:
             bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
         fc = np.empty((E, N, max(k, 0), T + 1, 2), dtype=np.float64)
         lw = np.empty((E, N, max(k, 0)), dtype=np.float64)
-        self._compute(self._lib.jmid_forecast_scene, self._h, E, A, K, T, k, bx.ptr, float(dt), _lib.PRECISIONS[precision],
+        self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision],
                       C.c_void_p(bw.ctypes.data) if bw is not None else None, C.c_void_p(fc.ctypes.data), C.c_void_p(lw.ctypes.data))
         return (fc[0], lw[0]) if single else (fc, lw)
 

@@ -30,6 +30,10 @@ the CUDA generator on a GPU host (``MID/mid.py:91``).  ``rng_compat="cpu"`` cons
 generator, ``"cuda"`` from the device generator (the CPU generator then advances by ``x_T`` only; the device generator is
 moved by what the draws would consume without launching them, ``advance_cuda_generator``), and the default
 ``"auto"`` does what the reference itself would do on this host (``"cuda"`` iff ``torch.cuda.is_available()``).
+``rng_compat="device"`` (opt-in) leaves that contract: ``x_T`` comes from the library's counter generator (``noise.py``,
+``jmid_noise_fill``) as a pure function of (``seed``, ``episode_id``, draw number), the draw number advancing by one block of
+``n_steps + 1`` per ``predict_ret_best()``, and the torch generators are not touched.  Statistically, not seed-, compatible with
+the reference.
 
 Differences from the reference that a caller can observe:
   * the engine (weights on the GPU) is cached across instances: the reference rebuilds the model and reloads the
@@ -166,7 +170,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
     def __init__(self, env_config=None, mid_config_file=None, *, weights: Optional[JMIDWeights] = None,
                  device_id: Optional[int] = None, precision: Optional[str] = None, rng_compat: Optional[str] = None,
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
-                 lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None):
+                 lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
+                 seed: int = 0, episode_id: int = 0):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -193,8 +198,10 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         self.device_frames = bool(device_frames)
         self.erange_fallbacks = 0
         self.timings: Dict[str, float] = {}     # ms of the last predict_ret_best(): scene, device, topk, assemble
-        if rng_compat not in ("auto", "cpu", "cuda"):
-            raise ValueError("rng_compat must be 'auto', 'cpu' or 'cuda'")
+        if rng_compat not in ("auto", "cpu", "cuda", "device"):
+            raise ValueError("rng_compat must be 'auto', 'cpu', 'cuda' or 'device'")
+        # rng_compat="device": the address of this instance's noise (seed, episode id) and the draw number its next call starts at
+        self.noise_seed, self.episode_id, self._noise_draw = int(seed), int(episode_id), 0
         self.rng_compat = rng_compat if rng_compat != "auto" else ("cuda" if torch.cuda.is_available() else "cpu")
         self._init_MID(mid_config_file, weights, device_id, lib_path)
 
@@ -311,19 +318,26 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
         # RNG contract (module docstring): x_T is the first draw of the CPU default generator; the per-step z of the
         # reference (unused by DDIM) comes from the generator of the device the reference would run on
-        x_T = torch.randn([K * A, H, 2])
         stride = int(100 / self.step_size)
-        n_z = sum(1 for t in range(100, 0, -stride) if t > 1)
-        if self.rng_compat == "cpu":
-            for _ in range(n_z):
-                torch.randn_like(x_T)
+        if self.rng_compat == "device":
+            # the library's counter generator: this call's block of n_steps + 1 draw numbers (x_T is its first; a DDPM sampler would take
+            # the others), drawn ONCE - the self check and the JMID_ERANGE repeat below reuse the array
+            with self._engine_lock:
+                x_np = self.engine.noise(self.noise_seed, [self.episode_id], K * A, H, draw=self._noise_draw)
+            self._noise_draw += len(range(100, 0, -stride)) + 1
         else:
-            advance_cuda_generator(self.engine.device_id, tuple(x_T.shape), n_z)
+            x_T = torch.randn([K * A, H, 2])
+            n_z = sum(1 for t in range(100, 0, -stride) if t > 1)
+            if self.rng_compat == "cpu":
+                for _ in range(n_z):
+                    torch.randn_like(x_T)
+            else:
+                advance_cuda_generator(self.engine.device_id, tuple(x_T.shape), n_z)
+            x_np = x_T.numpy()[None]
         t1 = time.perf_counter()
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
                 self.engine.set_step(self.step_size, "ddim")   # eval_sicnav hard-codes sampling="ddim" (MID/mid.py:333)
-            x_np = x_T.numpy()[None]
             # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits
             # - the reference has none - the host twin ranks them
             on_dev = k < K and self.device_topk and topk_fits_device(A, K, H)
@@ -411,18 +425,19 @@ def topk_fits_device(A: int, K: int, H: int) -> bool:
     return A <= TOPK_MAX_AGENTS and K <= TOPK_MAX_SAMPLES and H <= TOPK_MAX_HORIZON
 
 
-def denoise_with_fallback(engine: JmidEngine, x_T, ctx, p0, dt: float, precision: str, want_pos: bool = True):
+def denoise_with_fallback(engine: JmidEngine, x_T, ctx, p0, dt: float, precision: str, want_pos: bool = True, **seeded):
     """``engine.denoise`` -> positions; on JMID_ERANGE (an fp16 operand left the fp16 range) the call is repeated in the
-    exact-fp32 mode - what the reference computes in throughout (diffusion.py:478-541) - and counted.  -> (pos, fell_back)."""
+    exact-fp32 mode - what the reference computes in throughout (diffusion.py:478-541) - and counted.  -> (pos, fell_back).
+    ``seeded``: the seed / episode_ids / K / T keywords of a seeded call (x_T None): the repeat draws the same noise."""
     global ERANGE_FALLBACKS
     try:
-        _, pos = engine.denoise(x_T, ctx, p0, dt=dt, precision=precision, want_vel=False, want_pos=want_pos)
+        _, pos = engine.denoise(x_T, ctx, p0, dt=dt, precision=precision, want_vel=False, want_pos=want_pos, **seeded)
         return pos, False
     except JmidError as e:
         if e.code != -5 or precision == "f32":     # JMID_ERANGE
             raise
     ERANGE_FALLBACKS += 1
-    _, pos = engine.denoise(x_T, ctx, p0, dt=dt, precision="f32", want_vel=False, want_pos=want_pos)
+    _, pos = engine.denoise(x_T, ctx, p0, dt=dt, precision="f32", want_vel=False, want_pos=want_pos, **seeded)
     return pos, True
 
 
@@ -434,7 +449,7 @@ def _engine_lock_of(engine: JmidEngine) -> RLock:
 def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray, seeds, *, num_samples: int,
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
                   device_topk: bool = True, device_scene: bool = False,
-                  device_frames: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  device_frames: bool = False, noise: str = "torch", seed: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -449,7 +464,14 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     ``device_frames=True``: the inputs are on the grid already, so only the assembly moves - every count group is built on the device
     and comes back as its assembled arrays (``engine.forecast_scene``: one call per group instead of encode + denoise + top-k + the
     host scatter); a group whose ranking does not fit the device top-k takes the staged path.
+    ``noise="device"`` (opt-in; ``"torch"`` is the reference's contract above): x_T is drawn on the device by the library's counter
+    generator (``noise.py``) with ``seed`` as its key and ``seeds[e]`` as episode e's GLOBAL id, so an episode's forecasts are the same
+    bits whichever batch, count group or shard it is part of (in JMID_PREC_F32 at any width and in every mode below head_dim 128; at
+    head_dim 128 the split modes agree to rounding across batch sizes, include/jmid_hip.h at jmid_set_chunk_episodes) - statistically,
+    not seed-, compatible with the reference.
     """
+    if noise not in ("torch", "device"):
+        raise ValueError("noise must be 'torch' or 'device'")
     E, F, N, _ = human_xy.shape
     K, k, H = int(num_samples), int(num_ret_samples), int(horizon)
     precision = DEFAULTS["precision"] if precision is None else precision      # (no self check here: an engine-level call)
@@ -470,18 +492,21 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         A = int(A)
         rows = np.stack([np.nonzero(inc[e])[0] for e in eps])                       # [Eg, A] ascending track ids
         ei = eps[:, None]
-        x_T = torch.stack([torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
-                           for e in eps]).numpy()
+        if noise == "device":       # (seed, global episode id) is the whole address: nothing to draw here
+            x_T, nz = None, dict(seed=int(seed), episode_ids=np.asarray(seeds)[eps], K=K, T=H)
+        else:
+            x_T, nz = torch.stack([torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
+                                   for e in eps]).numpy(), {}
         if device_frames and (k == K or (device_topk and topk_fits_device(A, K, H))):
             with _engine_lock_of(engine):      # the group's scenes resident, then predictor + assembly in one entry
                 engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H)
                 try:
-                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision=precision)
+                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision=precision, **nz)
                 except JmidError as err:
                     if err.code != -5 or precision == "f32":     # JMID_ERANGE: the same call in exact fp32, counted
                         raise
                     ERANGE_FALLBACKS += 1
-                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision="f32")
+                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision="f32", **nz)
             forecasts[eps] = fc[:, :, :, 1:]
             logw[eps] = lw
             continue
@@ -496,7 +521,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                                 b["edge_mask"][ei, rows].reshape(len(eps) * A, 2)).reshape(len(eps), A, -1)
             # the samples stay on the GPU; every episode of the group in ONE jmid_topk call (host twin beyond its size limits)
             on_dev = k < K and device_topk and topk_fits_device(A, K, H)
-            pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=not on_dev)
+            pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=not on_dev, **nz)
             if on_dev:
                 sel_all, lw_all = engine.topk(None, k, dims=(len(eps), A, K, H))   # [Eg, A, k, H, 2], [Eg, A, k]
         for g, e in enumerate(eps):                                                # pos [Eg, K, A, H, 2]
