@@ -508,6 +508,16 @@ int jmid_dbg_plan_chunks_mode(int net_kind, int nhead, int lanes, int chunk_epis
  * group, the shape's tile rows and columns, and the row tile of the first- / second-generation GEMM + LayerNorm kernel for M rows. */
 #define JMID_DBG_GEMM_PLAN_KNOBS 13
 int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int small_now, int one_chunk, const int* knobs, int* plan);
+/* Layer 0's Q, K, V of one denoise step of a JMID net in a split-fp16 mode, as the step's kernels leave them for the attention
+ * kernel: x [M, 2] (M = E K A T tokens) is embedded at step-table entry `step` with the hyper rows hyp [E A, hyper width] (the ctx
+ * part of the hyper nets: gate1 | bias1 | ... as the handle lays them out), layer 0's operand planes are made - expanded from the
+ * per-(row, step) coefficient tables, or by the in_proj GEMM with jmid_set_tuning "qkv0" = 1 - and read back as fp32
+ * qkv [M, 3 d_model] (hi + lo plane, or the bf8 image where it replaces a lo plane; Q without its softmax scale).  thyp_row (or
+ * NULL) receives the time part of the hyper nets at that step, [hyper width].  hyp_width is the caller's row length: a value other
+ * than the handle's hyper width (2 d_model + 2 d_mid + 2 d_low + 4) is JMID_EINVAL.  "qkv0" = 2 (A/B): expanded, with the table's
+ * GEMM as one running fp32 sum instead of per-tile sums. */
+int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision,
+                  float* qkv, float* thyp_row);
 /* The raw Philox words behind jmid_noise_fill, same addressing: out [E, rows, T, 2] uint32 (where `mem` says). */
 int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem);
 #endif /* JMID_DIAGNOSTICS */

@@ -16,6 +16,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kWave = 64;
+constexpr int kPeMaxLen = 24;      // rows of the positional-encoding table and of its image under layer 0's in_proj (max_len, diffusion.py:116-118): T <= kPeMaxLen
 
 // Layout of the per-(episode,agent) ConcatSquash "hyper" vector and of the per-step time table:
 // [gate1 | bias1 | gate3 | bias3 | gate4 | bias4 | gateO | biasO]   (MID/models/common.py:58-72)
@@ -156,6 +157,7 @@ struct Tuning {
     int small_lanes = 0;     // experiment: the small-launch kernels with several chunks in flight too: 1 = all of them, 2 = only the two-workgroups-per-CU shape
     int small_qk = 0;        // Q / K tiles of a small in_proj launch out through LDS in full rows: 0 / 1 on, 2 = the generic element-wise epilogue
     int small_pn = 0;        // its column groups per launch (two-dimensional XCD tile order): 0 = fewest Infinity-Cache bytes, 1 / 2 / 4 / 8 forced
+    int qkv0 = 0;            // layer 0's Q / K / V^T planes in the split-fp16 modes of JMID: 0 = expanded from per-(row, step) coefficient tables (qkv0.hpp), 1 = the in_proj GEMM as on every other layer (A/B), 2 = as 0 with the table's GEMM as one running fp32 sum (A/B of its per-tile sums: other bits)
     int attn_abl = 0;        // timing ablations (results are WRONG): only in builds with -DJMID_ABLATIONS
     int gemm_abl = 0;
 };

@@ -78,7 +78,10 @@ __device__ __forceinline__ void gemm_f32_epilogue(const GemmArgs& g, f32x16 (&ac
     }
 }
 
-template <int WM, int WN, int EPI>
+// TSUM: every k32 tile is summed into accumulators of its own, which are then added to the running ones - the rounding error of a
+// long product grows with the number of tiles instead of the number of terms (the coefficient tables of qkv0.hpp: one row stands
+// for hundreds of tokens).  Per element still one fixed order of operations, whatever the tile shape.
+template <int WM, int WN, int EPI, bool TSUM = false>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     constexpr int LD = GEMM_LDS_LD;
@@ -145,6 +148,15 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
         if (kt + 1 < nk) gload(kt + 1);
         const float* Ab = As + (buf * BM + wr * WM * 32 + l31) * LD + 4 * hi;
         const float* Bb = Bs + (buf * BN + wc * WN * 32 + l31) * LD + 4 * hi;
+        f32x16 part[TSUM ? WM : 1][TSUM ? WN : 1];
+        if constexpr (TSUM) {
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int j = 0; j < WN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) part[i][j][r] = 0.f;
+        }
 #pragma unroll
         for (int kk = 0; kk < GEMM_BK / 8; ++kk) {
             f32x4 a[WM], b[WN];
@@ -157,8 +169,18 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
 #pragma unroll
                 for (int i = 0; i < WM; ++i)
 #pragma unroll
-                    for (int j = 0; j < WN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < WN; ++j) {
+                        if constexpr (TSUM) part[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[j][e], part[i][j], 0, 0, 0);
+                        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+                    }
+        }
+        if constexpr (TSUM) {
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int j = 0; j < WN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] += part[i][j][r];
         }
         if (kt + 1 < nk) lstore(buf ^ 1);
         __syncthreads();
@@ -170,19 +192,19 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
         gemm_f32_epilogue<WM, WN, EPI, false>(g, acc, m0, n0, wr, wc, l31, hi);
 }
 
-template <int WM, int WN, int EPI>
+template <int WM, int WN, int EPI, bool TSUM = false>
 inline hipError_t launch_gemm_f32_cfg(const GemmArgs& g, hipStream_t st) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM);
-    return launch_with_lds<&gemm_f32_kernel<WM, WN, EPI>>(grid, dim3(256), gemm_f32_lds_bytes<WM, WN>(), st, g);
+    return launch_with_lds<&gemm_f32_kernel<WM, WN, EPI, TSUM>>(grid, dim3(256), gemm_f32_lds_bytes<WM, WN>(), st, g);
 }
 
-template <int EPI>
+template <int EPI, bool TSUM = false>
 inline hipError_t launch_gemm_f32(const GemmArgs& g, hipStream_t st) {
     // 128x128 tiles when they still give >= ~2 blocks per CU, else 64x64 (small single-scene batches)
     const long big = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-    if (big >= 512) return launch_gemm_f32_cfg<2, 2, EPI>(g, st);
-    return launch_gemm_f32_cfg<1, 1, EPI>(g, st);
+    if (big >= 512) return launch_gemm_f32_cfg<2, 2, EPI, TSUM>(g, st);
+    return launch_gemm_f32_cfg<1, 1, EPI, TSUM>(g, st);
 }
 
 }  // namespace jmid

@@ -439,7 +439,7 @@ int jmid_destroy(jmid_handle_t h) {
     if (h->range_flag) hipFree(h->range_flag);
     if (h->ev_in) hipEventDestroy(h->ev_in);
     if (h->ev_out) hipEventDestroy(h->ev_out);
-    for (float* p : {h->pe, h->Whyp, h->bhyp, h->thyp, h->attW1T, h->attW2T})
+    for (float* p : {h->pe, h->ppe, h->Whyp, h->bhyp, h->thyp, h->attW1T, h->attW2T})
         if (p) hipFree(p);
     for (auto& l : h->lstmT)
         for (float* p : l)
@@ -994,6 +994,7 @@ int jmid_set_tuning(jmid_handle_t h, const char* key, int value) {
         {"small_lnx2", &Tuning::small_lnx2, 0, 2},             // the same at 33 ... 64 row tiles, two workgroups per CU: 0 on, 2 off
         {"small_qk", &Tuning::small_qk, 0, 2},
         {"small_pn", &Tuning::small_pn, 0, 8},                 // column groups of its XCD tile order: 0 auto
+        {"qkv0", &Tuning::qkv0, 0, 2},                         // layer 0's Q / K / V^T: 0 expanded from coefficient tables (qkv0.hpp), 1 the in_proj GEMM, 2 expanded with the table GEMM as one running sum (A/B of the per-tile sums)
 #ifdef JMID_ABLATIONS
         {"attn_abl", &Tuning::attn_abl, 0, 1 << 30},           // timing ablations: results are WRONG (tools/attn_abl.py)
         {"gemm_abl", &Tuning::gemm_abl, 0, 1 << 30},

@@ -32,6 +32,7 @@
 #include "kde.hpp"
 #include "launch_plan.hpp"
 #include "noise.hpp"
+#include "qkv0.hpp"
 #include "scene.hpp"
 #include "frames.hpp"
 
@@ -173,6 +174,7 @@ struct jmid_ctx {
     bool finalized = false;
     // derived device buffers
     float* pe = nullptr;
+    float* ppe = nullptr;   // [kPeMaxLen, 3 d] image of the positional table under layer 0's in_proj, bias included (qkv0.hpp)
     float* Whyp = nullptr;
     float* bhyp = nullptr;
     float* thyp = nullptr;  // [n_steps, hl.total]
@@ -282,6 +284,9 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
                 const float* z_in = nullptr, const SeedArgs* seeded = nullptr);
 int flagged_call(jmid_ctx* h, int flag);      // the status of a call whose range flag came back set (JMID_ETIMEOUT / JMID_ERANGE)
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T);
+#ifdef JMID_DIAGNOSTICS
+int dbg_qkv0(jmid_ctx* h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision, float* qkv, float* thyp_row);
+#endif
 // jmid_abi.hip
 int noise_entry(jmid_ctx* h, const char* who, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out,
                 unsigned* words, int mem);

@@ -39,6 +39,7 @@ struct StepBuffers {
     half_t *Xh, *Xl, *Qh, *Ql, *Kh, *Kl, *Vh, *Vl, *Vth, *Vtl, *Ah, *Al, *H1h, *H1l, *Y3h, *Y3l;
     size_t vt_elems;
     float *Opart, *MLpart;
+    float *coef, *uvc;             // layer 0's coefficient rows [steps, Ec A, 3, d] and their image under in_proj [steps, Ec A, 3, 3 d] (qkv0.hpp), or null
     unsigned long long* ln_xchg;   // exchange granules of the small-launch GEMM + LayerNorm (gemm_small.hpp, OUT_LNX): kLnxWords words, zeroed once per call
 };
 
@@ -56,8 +57,9 @@ SeqGeom seq_geom(const jmid_ctx* h, int Ec, int A, int K, int T) {
     return g;
 }
 
+// qkv0_rows: coefficient rows of layer 0's table (steps x Ec A x 3), 0 = that layer runs its in_proj GEMM
 size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom& sg, int nsplit, StepBuffers* sb,
-                      char* base) {
+                      char* base, size_t qkv0_rows) {
     Carver c(base);
     StepBuffers s{};
     s.X = c.take(Mc * h->d);
@@ -85,6 +87,10 @@ size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom
             if (nsplit > 1) {      // split-KV factor of the attention launch (1 = off)
                 s.Opart = c.take((size_t)nsplit * Mc * h->d);
                 s.MLpart = c.take((size_t)nsplit * Mc * h->nhead * 2);
+            }
+            if (qkv0_rows) {
+                s.coef = c.take(qkv0_rows * h->d);
+                s.uvc = c.take(qkv0_rows * 3 * h->d);
             }
         } else {
             s.QKV = c.take(Mc * 3 * h->d);  // iMID: sequences of T tokens, exact-fp32 attention kernel
@@ -146,6 +152,9 @@ bool one_launch_shape(const jmid_ctx* h, long tokens) { return h->mx && h->d == 
 // and lnx_off cannot change while a call runs.  net_step executes it.
 struct StepPlan {
     int Ec, M, T;                // episodes and tokens (Ec * K * A * T) of the chunk, tokens per trajectory
+    int R;                       // (episode, agent) rows of the chunk: Ec * A
+    bool qkv0;                   // layer 0's Q / K / V^T planes are expanded from coefficient tables (qkv0.hpp) instead of its in_proj GEMM:
+    int qkv0_steps;              // mode and net only, never the token count; the steps a table holds (CallFacts)
     bool split, mxv2, joint;     // split-fp16 mode; byte lo plane of the residual stream (byte_lo_plane); JMID (joint attention over an episode)
     RowMap rm;
     SeqGeom sg;
@@ -166,6 +175,7 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision
     p.Ec = Ec;
     p.M = Ec * K * A * T;
     p.T = T;
+    p.R = Ec * A;
     p.split = precision != JMID_PREC_F32;
     p.mxv2 = p.split && byte_lo_plane(h);
     p.joint = h->net_kind == JMID_NET_JMID;
@@ -176,6 +186,8 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision
     p.cf = cf;
     const Tuning& t = h->tune;
     p.attn = plan_attn(p.hd, t);
+    p.qkv0 = p.split && p.joint && t.qkv0 != 1 && d % 32 == 0;      // (d % 32: the K tiles of the table's GEMM - as every GEMM of the net)
+    p.qkv0_steps = cf.qkv0_steps;
     if (p.split) {
         const auto gemm = [&](int epi, int out, int N, int K) { return plan_gemm(gemm_mode(h), epi, out, p.M, N, K, cf, t); };
         p.in_proj = gemm(EPI_BIAS, p.joint ? OUT_QKV : OUT_F32, 3 * d, d);
@@ -244,6 +256,102 @@ int residual_block(jmid_ctx* h, const StepPlan& p, const ResidualPlan& rp, const
     return run_add_ln(h, sb.X, sb.Y, nrm.gamma, nrm.beta, M, d, sb.Xh, sb.Xl, p.mxv2, no_lo_out);
 }
 
+// Steps one coefficient table of a chunk holds: all of the call's - built once per chunk - or one, rebuilt at the head of every step.
+// From (steps, Ec, A, d) only.  The table is DEVICE MEMORY the handle's arena grows by, per chunk lane: 48 d bytes per (step, episode,
+// agent) - the rows [.., 3, d] and their image [.., 3, 3 d] in fp32.  256 episodes of 5 agents at 50 steps and d_model 512 run as
+// 43-episode chunks: 264 MB per lane, 528 MB with two chunks in flight, next to ~1.5 GB of step workspace.  kQkv0TableMaxBytes per lane
+// caps it: a call beyond (a 100-step DDPM schedule on the same batch) keeps one step's table, 48 d Ec A bytes, and pays the small
+// GEMM every step.
+constexpr size_t kQkv0TableMaxBytes = size_t(512) << 20;
+int qkv0_table_steps(int steps, int Ec, int A, int d) {
+    const size_t bytes = (size_t)steps * Ec * A * 3 * 4 * d * sizeof(float);
+    return bytes <= kQkv0TableMaxBytes ? steps : 1;
+}
+
+// The table of `nsteps` steps from step `step0` on for the chunk whose hyper rows are hyp_chunk: the coefficient rows, then in_proj
+// of layer 0 on them in exact fp32 with per-tile sums (a row stands for every token of its (episode, agent) pair).
+int qkv0_build_table(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* hyp_chunk, int step0, int nsteps) {
+    const int d = h->d;
+    ProfScope ps(h, KC_HYPER);
+    Qkv0CoefArgs ca{h->wt.concat1.W, h->wt.concat1.bias, hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, sb.coef,
+                    nsteps, p.R, d, h->hl.total, h->hl.g1, h->hl.b1, h->range_flag};
+    const long total = (long)nsteps * p.R * (d / 4);
+    hipLaunchKernelGGL(qkv0_coef_kernel, dim3((int)std::min<long>((total + 255) / 256, 256L * 16)), dim3(256), 0, h->stream, ca);
+    HIPCHK(h, hipGetLastError());
+    GemmArgs g{};
+    g.A = sb.coef; g.lda = d; g.W = h->wt.layers[0].in_proj.W; g.ldw = d; g.C = sb.uvc; g.ldc = 3 * d;
+    g.M = nsteps * p.R * 3; g.N = 3 * d; g.K = d;
+    if (h->tune.qkv0 == 2) HIPCHK(h, (launch_gemm_f32<EPI_BIAS, false>(g, h->stream)));      // (A/B: what the per-tile sums buy)
+    else HIPCHK(h, (launch_gemm_f32<EPI_BIAS, true>(g, h->stream)));
+    return 0;
+}
+
+EmbedArgs embed_args(const jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* x_chunk, const float* hyp_chunk, const float* th) {
+    unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
+    return EmbedArgs{x_chunk, h->wt.concat1.W, h->wt.concat1.bias, h->pe, hyp_chunk, th,
+                     p.split ? nullptr : sb.X, p.M, h->d, h->hl.total, h->hl.g1, h->hl.b1, p.rm, p.split ? sb.Xh : nullptr,
+                     p.split && !p.mxv2 ? sb.Xl : nullptr, Xl8};
+}
+
+int run_embed(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* x_chunk, const float* hyp_chunk, const float* thyp) {
+    ProfScope ps(h, KC_EMBED);
+    EmbedArgs ea = embed_args(h, p, sb, x_chunk, hyp_chunk, thyp);
+    const long total = (long)p.M * (h->d / 4);
+    int blocks = (int)std::min<long>((total + 255) / 256, 256L * 16);
+    hipLaunchKernelGGL(embed_kernel, dim3(blocks), dim3(256), bystander_lds(h->tune.bystander_lds, embed_kernel), h->stream, ea);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// The bf8 images that replace the fp16 K_lo / Q_lo planes (plan_step: k8, q8l), in those planes' memory
+struct LoImages {
+    unsigned char *k8h, *k8l, *q8l;
+};
+LoImages lo_images(const StepPlan& p, const StepBuffers& sb, int d) {
+    LoImages im{};
+    im.k8h = p.k8 ? reinterpret_cast<unsigned char*>(sb.Kl) : nullptr;
+    im.k8l = p.k8 ? im.k8h + (size_t)p.M * d : nullptr;
+    im.q8l = p.q8l ? reinterpret_cast<unsigned char*>(sb.Ql) : nullptr;
+    return im;
+}
+
+// The Q / K / V^T operand planes of layer l of a JMID step in the split-fp16 modes: the in_proj GEMM on the residual stream's planes
+// (+ the transpose where its epilogue does not write V^T itself), or for layer 0 the expansion of the coefficient table (qkv0.hpp).
+int qkv_planes(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int l, int step_idx, const float* x_chunk, const float* hyp_chunk) {
+    const int M = p.M, d = h->d, hd = p.hd, S = p.sg.S;
+    const LoImages im = lo_images(p, sb, d);
+    const float qscale = p.att_scale * 1.4426950408889634f;
+    if (l == 0 && p.qkv0) {
+        if (p.qkv0_steps <= 1)
+            if (int rc = qkv0_build_table(h, p, sb, hyp_chunk, step_idx, 1)) return rc;
+        Qkv0Args qa{};
+        qa.x = x_chunk;
+        qa.uvc = sb.uvc + (p.qkv0_steps <= 1 ? 0 : (size_t)step_idx * p.R * 9 * d);
+        qa.ppe = h->ppe;
+        qa.Qh = sb.Qh; qa.Ql = sb.Ql; qa.Kh = sb.Kh; qa.Kl = sb.Kl; qa.Vth = sb.Vth; qa.Vtl = sb.Vtl;
+        qa.Q8l = im.q8l; qa.K8h = im.k8h; qa.K8l = im.k8l;
+        qa.M = M; qa.d = d; qa.hd = hd; qa.S = S; qa.Spad = p.sg.Spad; qa.nseq = p.sg.nseq;
+        qa.qscale = qscale; qa.rmap = p.rm; qa.range_flag = h->range_flag; qa.x2 = h->x2;
+        qkv0_plan(qa, p.T);
+        ProfScope ps(h, KC_GEMM_QKV);
+        HIPCHK(h, launch_qkv0_expand(qa, h->stream));
+        return 0;
+    }
+    GemmHArgs g = gemm_h_args(h, p.rm, M, sb.Xh, sb.Xl, h->wt.layers[l].in_proj, 3 * d, d);
+    g.Chi = sb.Qh; g.Clo = sb.Ql; g.Khi = sb.Kh; g.Klo = sb.Kl;
+    g.Vthi = p.vt_direct ? sb.Vth : sb.Vh; g.Vtlo = p.vt_direct ? sb.Vtl : sb.Vl; g.vt_direct = p.vt_direct;
+    g.d = d; g.hd = hd; g.S = S; g.Spad = p.sg.Spad; g.qscale = qscale;
+    g.K8h = im.k8h; g.K8l = im.k8l; g.Q8l = im.q8l;
+    if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, KC_GEMM_QKV, g, p.in_proj))) return rc;
+    if (!p.vt_direct) {
+        ProfScope ps(h, KC_VTRANS);
+        hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, p.sg.nseq), dim3(256), 0, h->stream,
+                           sb.Vh, sb.Vl, sb.Vth, sb.Vtl, S, p.sg.Spad, d, hd);
+        HIPCHK(h, hipGetLastError());
+    }
+    return 0;
+}
+
 // one evaluation of the net on a chunk of whole episodes + (optionally) the DDIM update, as its plan says
 int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
              float* e_out, const float* z_chunk = nullptr, bool embed_done = false, int next_step = -1) {
@@ -254,20 +362,8 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
     const WeightTable& wt = h->wt;
     const float* thyp = h->thyp + (size_t)step_idx * h->hl.total;
     const RowMap& rm = p.rm;
-    unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
-    const auto embed_args = [&](const float* th) {
-        return EmbedArgs{x_chunk, wt.concat1.W, wt.concat1.bias, h->pe, hyp_chunk, th,
-                         split ? nullptr : sb.X, M, d, h->hl.total, h->hl.g1, h->hl.b1, rm, split ? sb.Xh : nullptr,
-                         split && !p.mxv2 ? sb.Xl : nullptr, Xl8};
-    };
-    if (!embed_done) {
-        ProfScope ps(h, KC_EMBED);
-        EmbedArgs ea = embed_args(thyp);
-        const long total = (long)M * (d / 4);
-        int blocks = (int)std::min<long>((total + 255) / 256, 256L * 16);
-        hipLaunchKernelGGL(embed_kernel, dim3(blocks), dim3(256), bystander_lds(h->tune.bystander_lds, embed_kernel), h->stream, ea);
-        HIPCHK(h, hipGetLastError());
-    }
+    if (!embed_done)
+        if (int rc = run_embed(h, p, sb, x_chunk, hyp_chunk, thyp)) return rc;
     const SeqGeom& sg = p.sg;
     const int nseq = sg.nseq, S = sg.S, hd = p.hd;
     if (!split) {
@@ -296,28 +392,17 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
     } else {
         for (int l = 0; l < h->tf_layer; ++l) {
             const LayerW& w = wt.layers[l];
-            GemmHArgs g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, w.in_proj, 3 * d, d);
+            GemmHArgs g{};
             if (p.joint) {
-                g.Chi = sb.Qh; g.Clo = sb.Ql; g.Khi = sb.Kh; g.Klo = sb.Kl;
-                g.Vthi = p.vt_direct ? sb.Vth : sb.Vh; g.Vtlo = p.vt_direct ? sb.Vtl : sb.Vl; g.vt_direct = p.vt_direct;
-                g.d = d; g.hd = hd; g.S = S; g.Spad = sg.Spad; g.qscale = p.att_scale * 1.4426950408889634f;
-                unsigned char* k8h = p.k8 ? reinterpret_cast<unsigned char*>(sb.Kl) : nullptr;
-                unsigned char* k8l = p.k8 ? k8h + (size_t)M * d : nullptr;
-                unsigned char* q8l = p.q8l ? reinterpret_cast<unsigned char*>(sb.Ql) : nullptr;
-                g.K8h = k8h; g.K8l = k8l; g.Q8l = q8l;
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, KC_GEMM_QKV, g, p.in_proj))) return rc;
-                if (!p.vt_direct) {
-                    ProfScope ps(h, KC_VTRANS);
-                    hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, nseq), dim3(256), 0, h->stream,
-                                       sb.Vh, sb.Vl, sb.Vth, sb.Vtl, S, sg.Spad, d, hd);
-                    HIPCHK(h, hipGetLastError());
-                }
+                if (int rc = qkv_planes(h, p, sb, l, step_idx, x_chunk, hyp_chunk)) return rc;
+                const LoImages im = lo_images(p, sb, d);
                 ProfScope ps(h, KC_ATTN);
                 AttnHArgs aa{sb.Qh, sb.Ql, sb.Kh, sb.Kl, sb.Vth, sb.Vtl, sb.Ah, sb.Al, S, sg.Spad, d, h->nhead,
-                             p.att_scale, h->range_flag, p.cf.attn_nsplit, sb.Opart, sb.MLpart, h->x2, k8h, k8l, q8l};
+                             p.att_scale, h->range_flag, p.cf.attn_nsplit, sb.Opart, sb.MLpart, h->x2, im.k8h, im.k8l, im.q8l};
                 aa.skip_combine = p.out_proj.merge;
                 HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, p.attn, h->stream));
             } else {
+                g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, w.in_proj, 3 * d, d);
                 g.C = sb.QKV; g.ldc = 3 * d;
                 if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g, p.in_proj))) return rc;
                 ProfScope ps(h, KC_ATTN);
@@ -356,7 +441,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
             oa.sigma = h->p_sigma[step_idx];
         }
         const bool embed_next = next_step >= 0 && !e_out;
-        const EmbedArgs en = embed_next ? embed_args(h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+        const EmbedArgs en = embed_next ? embed_args(h, p, sb, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
         // four waves per workgroup: one wave per piece of a trajectory (out_tpw tokens), or one per token
         const auto launch = [&](auto* kernel, int waves, auto... tpw) {
             hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), h->stream, oa, en, tpw...);
@@ -493,7 +578,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
                 const float* z_in, const SeedArgs* seeded) {
     if (int rc = check_ready(h)) return rc;
     if (E <= 0 || A <= 0 || K <= 0 || T <= 0) return fail(h, JMID_EINVAL, "E, A, K, T must be positive");
-    if (T > 24) return fail(h, JMID_EINVAL, "T exceeds the positional-encoding table (max_len=24, diffusion.py:116-118)");
+    if (T > kPeMaxLen) return fail(h, JMID_EINVAL, "T exceeds the positional-encoding table (max_len=24, diffusion.py:116-118)");
     if (precision != JMID_PREC_F32 && precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX)
         return fail(h, JMID_EINVAL, "precision must be JMID_PREC_F32, JMID_PREC_F16X3, JMID_PREC_F16X2 or JMID_PREC_F16MX (JMID_PREC_F16 is not built)");
     h->mx = precision == JMID_PREC_F16MX;
@@ -557,6 +642,8 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     facts.small_now = lanes == 1 || h->tune.small_lanes == 1 ? 1 : h->tune.small_lanes == 2 ? 2 : 0;
     facts.one_chunk = nchunks == 1 && h->tune.graph != 1;      // (a captured loop would replay the launch tags of OUT_LNX)
     facts.attn_nsplit = ns_call;
+    const int n_steps = (int)h->beta.size();
+    facts.qkv0_steps = single_step < 0 ? qkv0_table_steps(n_steps, Ec, A, h->d) : 1;
     std::vector<StepPlan> plans;            // a handful at most
     std::vector<int> chunk_plan;            // chunk -> its plan
     for (int ec : chunk_sizes) {
@@ -565,7 +652,8 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         if (j == plans.size()) plans.push_back(plan_step(h, ec, A, K, T, precision, facts));
         chunk_plan.push_back((int)j);
     }
-    const size_t lane_floats = step_ws_floats(h, Mc, precision, sg_full, ns_call, nullptr, nullptr);
+    const size_t qkv0_rows = plans[0].qkv0 ? (size_t)facts.qkv0_steps * Ec * A * 3 : 0;
+    const size_t lane_floats = step_ws_floats(h, Mc, precision, sg_full, ns_call, nullptr, nullptr, qkv0_rows);
     const size_t need = io_off + lanes * lane_floats;
     if (int rc = ensure_arena(h, need)) return rc;
     Carver c(h->arena);
@@ -582,7 +670,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     }
     float* z_lane = z_fill ? c.take((size_t)lanes * Mc * 2) : nullptr;
     StepBuffers sbs[jmid_ctx::kMaxLanes];
-    for (int l = 0; l < lanes; ++l) step_ws_floats(h, Mc, precision, sg_full, ns_call, &sbs[l], h->arena + io_off + l * lane_floats);
+    for (int l = 0; l < lanes; ++l) step_ws_floats(h, Mc, precision, sg_full, ns_call, &sbs[l], h->arena + io_off + l * lane_floats, qkv0_rows);
     const StepBuffers& sb = sbs[0];
     if (precision != JMID_PREC_F32) {
         HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
@@ -619,7 +707,6 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         g.ldc = h->hl.total; g.M = (int)EA; g.N = h->hl.total; g.K = h->ctx_dim;
         if (int rc = run_gemm<EPI_BIAS>(h, KC_HYPER, g)) return rc;
     }
-    const int n_steps = (int)h->beta.size();
     if (lanes > 1) {   // everything enqueued so far (inputs, hyper nets, memsets) precedes the extra lanes as well
         HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
         for (int l = 1; l < lanes; ++l) HIPCHK(h, hipStreamWaitEvent(h->lane_stream[l - 1], h->ev_fork, 0));
@@ -674,6 +761,9 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
                     rc = fill_noise(h, seeded->seed, h->noise_ids + el, chunk_sizes[c0 + l], (size_t)K * A * T * 2, i + 1, zl, nullptr, h->stream);
                     zc = zl;
                 }
+                // layer 0's coefficient table of this chunk for all steps, ahead of its first step, on the chunk's own stream
+                const StepPlan& pl = plans[chunk_plan[c0 + l]];
+                if (!rc && i == 0 && pl.qkv0 && pl.qkv0_steps > 1) rc = qkv0_build_table(h, pl, sbs[l], hc, 0, n_steps);
                 if (!rc) rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, h->tune.fuse_embed && i > 0,
                                         h->tune.fuse_embed && i + 1 < n_steps ? i + 1 : -1);
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);
@@ -756,6 +846,63 @@ int flagged_call(jmid_ctx* h, int flag) {
     ++h->erange_calls;
     return fail(h, JMID_ERANGE, "an activation left the fp16 range in JMID_PREC_F16X3 / F16X2 / F16MX: rerun with JMID_PREC_F32");
 }
+
+#ifdef JMID_DIAGNOSTICS
+// jmid_dbg_qkv0: the embedding of x at step `step` and layer 0's Q / K / V^T planes as a step of a one-chunk call makes them (the
+// "qkv0" knob decides how), read back as fp32 [M, 3 d].  Host buffers.
+int dbg_qkv0(jmid_ctx* h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision, float* qkv, float* thyp_row) {
+    if (int rc = check_ready(h)) return rc;
+    if (!x || !hyp || !qkv || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen) return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: bad arguments");
+    if (hyp_width != h->hl.total) return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: hyp rows must be " + std::to_string(h->hl.total) + " wide");
+    if (h->net_kind != JMID_NET_JMID || (precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX))
+        return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: JMID in a split-fp16 mode only");
+    if (step < 0 || step >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: step outside the step table");
+    h->mx = precision == JMID_PREC_F16MX;
+    h->x2 = precision == JMID_PREC_F16X2 || h->mx;
+    HIPCHK(h, hipSetDevice(h->device));
+    h->last_pos = nullptr;
+    const size_t M = (size_t)E * K * A * T, EA = (size_t)E * A;
+    const int d = h->d;
+    CallFacts facts;          // (an idle handle: nothing else in flight, one launch, the table of one step)
+    const StepPlan p = plan_step(h, E, A, K, T, precision, facts);
+    const size_t rows = p.qkv0 ? EA * 3 : 0;
+    size_t io_off;
+    {
+        Carver c(nullptr);
+        c.take(M * 2);
+        c.take(EA * h->hl.total);
+        c.take(M * 3 * d);
+        io_off = c.off;
+    }
+    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, precision, p.sg, 1, nullptr, nullptr, rows))) return rc;
+    Carver c(h->arena);
+    float* x_d = c.take(M * 2);
+    float* hyp_d = c.take(EA * h->hl.total);
+    float* out_d = c.take(M * 3 * d);
+    StepBuffers sb;
+    step_ws_floats(h, M, precision, p.sg, 1, &sb, h->arena + io_off, rows);
+    HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(sb.Vth, 0, sb.vt_elems * sizeof(half_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(sb.Vtl, 0, sb.vt_elems * sizeof(half_t), h->stream));
+    HIPCHK(h, hipMemcpyAsync(x_d, x, M * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hyp_d, hyp, EA * h->hl.total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (int rc = run_embed(h, p, sb, x_d, hyp_d, h->thyp + (size_t)step * h->hl.total)) return rc;
+    if (int rc = qkv_planes(h, p, sb, 0, step, x_d, hyp_d)) return rc;
+    const LoImages im = lo_images(p, sb, d);
+    QkvReadArgs ra{sb.Qh, sb.Ql, sb.Kh, sb.Kl, sb.Vth, sb.Vtl, im.q8l, im.k8l, out_d, M, d, p.hd, p.sg.S, p.sg.Spad, h->x2,
+                   p.att_scale * 1.4426950408889634f};
+    hipLaunchKernelGGL(qkv_planes_read_kernel, dim3(512), dim3(256), 0, h->stream, ra);
+    HIPCHK(h, hipGetLastError());
+    int flag = 0;
+    HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(qkv, out_d, M * 3 * d * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (thyp_row)
+        HIPCHK(h, hipMemcpyAsync(thyp_row, h->thyp + (size_t)step * h->hl.total, h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (flag) return flagged_call(h, flag);
+    return 0;
+}
+#endif
 
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T) {
     ProfScope ps(h, KC_METRICS);

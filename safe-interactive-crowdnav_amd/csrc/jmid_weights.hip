@@ -134,7 +134,7 @@ int jmid_finalize_weights(jmid_handle_t h) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->finalized = false;       // from here on the derived buffers and the operand planes are freed and rebuilt
-    for (float** p : {&h->pe, &h->Whyp, &h->bhyp, &h->attW1T, &h->attW2T})
+    for (float** p : {&h->pe, &h->ppe, &h->Whyp, &h->bhyp, &h->attW1T, &h->attW2T})
         if (*p) {
             hipFree(*p);
             *p = nullptr;
@@ -146,11 +146,11 @@ int jmid_finalize_weights(jmid_handle_t h) {
                 p = nullptr;
             }
     const int d = h->d, C = h->ctx_dim, CC = C + 3;
-    // positional encoding table, max_len = 24 (MID/models/common.py:37-51; diffusion.py:116-118)
+    // positional encoding table, max_len = kPeMaxLen (MID/models/common.py:37-51; diffusion.py:116-118)
     {
-        std::vector<float> pe((size_t)24 * d);
+        std::vector<float> pe((size_t)kPeMaxLen * d);
         const float coef = (float)(-std::log(10000.0) / (double)d);  // python scalar -> fp32, as torch does
-        for (int pos = 0; pos < 24; ++pos)
+        for (int pos = 0; pos < kPeMaxLen; ++pos)
             for (int i = 0; i < d; i += 2) {
                 const float div = (float)std::exp((double)((float)i * coef));
                 const float arg = (float)pos * div;
@@ -158,6 +158,19 @@ int jmid_finalize_weights(jmid_handle_t h) {
                 if (i + 1 < d) pe[(size_t)pos * d + i + 1] = (float)std::cos((double)arg);
             }
         if (int rc = dev_alloc_copy(h, &h->pe, pe)) return rc;
+        // its image under layer 0's in_proj, bias included (qkv0.hpp): fp64 sums rounded once, made once per handle
+        std::vector<float> win, bin;
+        const std::string p0 = "transformer_encoder.layers.0.self_attn.in_proj_";
+        if (int rc = fetch_host(h, p0 + "weight", win)) return rc;
+        if (int rc = fetch_host(h, p0 + "bias", bin)) return rc;
+        std::vector<float> ppe((size_t)kPeMaxLen * 3 * d);
+        for (int pos = 0; pos < kPeMaxLen; ++pos)
+            for (int n = 0; n < 3 * d; ++n) {
+                double acc = 0.0;
+                for (int k = 0; k < d; ++k) acc += (double)win[(size_t)n * d + k] * (double)pe[(size_t)pos * d + k];
+                ppe[(size_t)pos * 3 * d + n] = (float)(acc + (double)bin[n]);
+            }
+        if (int rc = dev_alloc_copy(h, &h->ppe, ppe)) return rc;
     }
     // packed ctx-part of the hyper nets [hl.total, C], their biases, and the 3 time columns (host)
     {

@@ -709,3 +709,25 @@ class JmidEngine:
                                                      C.c_void_p(Y.ctypes.data), C.c_void_p(g.ctypes.data),
                                                      C.c_void_p(b.ctypes.data)))
         return X
+
+    def dbg_qkv0(self, x: np.ndarray, hyp: np.ndarray, step: int, dims: Tuple[int, int, int, int], precision: str = "f16mx"):
+        """Layer 0's Q, K, V of one denoise step as the step's kernels leave them for the attention kernel (``jmid_dbg_qkv0``; the
+        "qkv0" knob decides how they are made): x [M, 2], hyp [E * A, hyper width] -> (qkv [M, 3 d] float32, the time part of the
+        hyper nets at step-table entry ``step`` [hyper width])."""
+        E, A, K, T = (int(v) for v in dims)
+        x = np.ascontiguousarray(x, np.float32)
+        hyp = np.ascontiguousarray(hyp, np.float32)
+        M, d = E * K * A * T, 2 * self.dims.ctx_dim
+        width = self.hyper_width()
+        if x.shape != (M, 2) or hyp.shape != (E * A, width):
+            raise ValueError(f"expected x [{M}, 2] and hyp [{E * A}, {width}]")
+        out = np.empty((M, 3 * d), np.float32)
+        thyp = np.empty((width,), np.float32)
+        self._check(self._lib.jmid_dbg_qkv0(self._h, E, A, K, T, C.c_void_p(x.ctypes.data), C.c_void_p(hyp.ctypes.data), width, int(step),
+                                            _lib.PRECISIONS[precision], C.c_void_p(out.ctypes.data), C.c_void_p(thyp.ctypes.data)))
+        return out, thyp
+
+    def hyper_width(self) -> int:
+        """Row length of the ConcatSquash hyper vectors, gate1 | bias1 | gate3 | bias3 | gate4 | bias4 | gateO | biasO (the library
+        checks it: ``jmid_dbg_qkv0`` refuses any other)."""
+        return 2 * self.dims.d_model + 2 * self.dims.d_mid + 2 * self.dims.d_low + 4
