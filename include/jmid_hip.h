@@ -518,6 +518,12 @@ int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int smal
  * GEMM as one running fp32 sum instead of per-tile sums. */
 int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision,
                   float* qkv, float* thyp_row);
+/* The tail of one denoise step alone (concat3 -> concat4 -> output layer) in a split-fp16 mode: X [M, d_model] fp32 stands for the
+ * last LayerNorm's output and is split into the planes the mode's concat3 reads (X_hi; X_hi + X_lo in JMID_PREC_F16X3), hyp and step
+ * as for jmid_dbg_qkv0; e [M, 2] receives e_theta.  The tail runs as a step of a one-chunk call runs it: as one 2 x d_model map per
+ * (episode, agent) row from a one-step table, or as the two GEMMs + the output kernel with jmid_set_tuning "tail_fold" = 1. */
+int jmid_dbg_tail(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision,
+                  float* e, float* thyp_row);
 /* The raw Philox words behind jmid_noise_fill, same addressing: out [E, rows, T, 2] uint32 (where `mem` says). */
 int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem);
 #endif /* JMID_DIAGNOSTICS */

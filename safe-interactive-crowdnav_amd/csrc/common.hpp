@@ -158,6 +158,7 @@ struct Tuning {
     int small_qk = 0;        // Q / K tiles of a small in_proj launch out through LDS in full rows: 0 / 1 on, 2 = the generic element-wise epilogue
     int small_pn = 0;        // its column groups per launch (two-dimensional XCD tile order): 0 = fewest Infinity-Cache bytes, 1 / 2 / 4 / 8 forced
     int qkv0 = 0;            // layer 0's Q / K / V^T planes in the split-fp16 modes of JMID: 0 = expanded from per-(row, step) coefficient tables (qkv0.hpp), 1 = the in_proj GEMM as on every other layer (A/B), 2 = as 0 with the table's GEMM as one running fp32 sum (A/B of its per-tile sums: other bits)
+    int tail_fold = 0;       // concat3 -> concat4 -> output layer in the split-fp16 modes: 0 = one 2 x d map per (row, step) from a per-chunk table (tail_fold.hpp), 1 = the two GEMMs + out_ddim*_kernel (A/B), 2 = as 0 with a one-step table rebuilt at the head of every step (the over-cap form; the same bits)
     int attn_abl = 0;        // timing ablations (results are WRONG): only in builds with -DJMID_ABLATIONS
     int gemm_abl = 0;
 };

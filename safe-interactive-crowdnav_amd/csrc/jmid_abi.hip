@@ -995,6 +995,7 @@ int jmid_set_tuning(jmid_handle_t h, const char* key, int value) {
         {"small_qk", &Tuning::small_qk, 0, 2},
         {"small_pn", &Tuning::small_pn, 0, 8},                 // column groups of its XCD tile order: 0 auto
         {"qkv0", &Tuning::qkv0, 0, 2},                         // layer 0's Q / K / V^T: 0 expanded from coefficient tables (qkv0.hpp), 1 the in_proj GEMM, 2 expanded with the table GEMM as one running sum (A/B of the per-tile sums)
+        {"tail_fold", &Tuning::tail_fold, 0, 2},               // the step's tail: 0 one 2 x d map per (row, step) (tail_fold.hpp), 1 concat3 / concat4 GEMMs + out_ddim, 2 folded with the one-step table rebuilt every step
 #ifdef JMID_ABLATIONS
         {"attn_abl", &Tuning::attn_abl, 0, 1 << 30},           // timing ablations: results are WRONG (tools/attn_abl.py)
         {"gemm_abl", &Tuning::gemm_abl, 0, 1 << 30},

@@ -33,6 +33,7 @@
 #include "launch_plan.hpp"
 #include "noise.hpp"
 #include "qkv0.hpp"
+#include "tail_fold.hpp"
 #include "scene.hpp"
 #include "frames.hpp"
 
@@ -286,6 +287,7 @@ int flagged_call(jmid_ctx* h, int flag);      // the status of a call whose rang
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T);
 #ifdef JMID_DIAGNOSTICS
 int dbg_qkv0(jmid_ctx* h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision, float* qkv, float* thyp_row);
+int dbg_tail(jmid_ctx* h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision, float* e, float* thyp_row);
 #endif
 // jmid_abi.hip
 int noise_entry(jmid_ctx* h, const char* who, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out,

@@ -292,6 +292,12 @@ int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, c
     return dbg_qkv0(h, E, A, K, T, x, hyp, hyp_width, step, precision, qkv, thyp_row);
 }
 
+int jmid_dbg_tail(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision,
+                  float* e, float* thyp_row) {
+    if (!h) return JMID_EINVAL;
+    return dbg_tail(h, E, A, K, T, X, hyp, hyp_width, step, precision, e, thyp_row);
+}
+
 int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem) {
     return noise_entry(h, "jmid_dbg_noise_words", seed, E, rows, T, episode_ids, draw, nullptr, out, mem);
 }

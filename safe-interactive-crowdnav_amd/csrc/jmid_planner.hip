@@ -40,6 +40,7 @@ struct StepBuffers {
     size_t vt_elems;
     float *Opart, *MLpart;
     float *coef, *uvc;             // layer 0's coefficient rows [steps, Ec A, 3, d] and their image under in_proj [steps, Ec A, 3, 3 d] (qkv0.hpp), or null
+    float *weff, *beff;            // the folded tail's maps [steps, Ec A, 2, d] and [steps, Ec A, 2] (tail_fold.hpp), or null
     unsigned long long* ln_xchg;   // exchange granules of the small-launch GEMM + LayerNorm (gemm_small.hpp, OUT_LNX): kLnxWords words, zeroed once per call
 };
 
@@ -58,14 +59,15 @@ SeqGeom seq_geom(const jmid_ctx* h, int Ec, int A, int K, int T) {
 }
 
 // qkv0_rows: coefficient rows of layer 0's table (steps x Ec A x 3), 0 = that layer runs its in_proj GEMM
+// tail_rows: maps of the folded tail's table (steps x Ec A), 0 = the tail runs its GEMMs: only then are Y3 / Y4 reserved
 size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom& sg, int nsplit, StepBuffers* sb,
-                      char* base, size_t qkv0_rows) {
+                      char* base, size_t qkv0_rows, size_t tail_rows) {
     Carver c(base);
     StepBuffers s{};
     s.X = c.take(Mc * h->d);
     s.Y = c.take((Mc + 63) / 64 * 64 * h->d);     // (whole 64-row tiles)
     s.ln_xchg = reinterpret_cast<unsigned long long*>(c.take(kLnxWords));
-    s.Y4 = c.take(Mc * h->dlow);
+    if (!tail_rows) s.Y4 = c.take(Mc * h->dlow);
     if (precision == JMID_PREC_F32) {
         s.QKV = c.take(Mc * 3 * h->d);
         s.ATT = c.take(Mc * h->d);
@@ -99,8 +101,13 @@ size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom
         s.Al = take_half(c, blk_plane_elems(Mc, h->d));
         s.H1h = take_half(c, blk_plane_elems(Mc, h->ff));
         s.H1l = take_half(c, blk_plane_elems(Mc, h->ff));
-        s.Y3h = take_half(c, blk_plane_elems(Mc, h->dmid));
-        s.Y3l = take_half(c, blk_plane_elems(Mc, h->dmid));
+        if (tail_rows) {
+            s.weff = c.take(tail_rows * 2 * h->d);
+            s.beff = c.take(tail_rows * 2);
+        } else {
+            s.Y3h = take_half(c, blk_plane_elems(Mc, h->dmid));
+            s.Y3l = take_half(c, blk_plane_elems(Mc, h->dmid));
+        }
     }
     if (sb) *sb = s;
     return c.off;
@@ -155,6 +162,8 @@ struct StepPlan {
     int R;                       // (episode, agent) rows of the chunk: Ec * A
     bool qkv0;                   // layer 0's Q / K / V^T planes are expanded from coefficient tables (qkv0.hpp) instead of its in_proj GEMM:
     int qkv0_steps;              // mode and net only, never the token count; the steps a table holds (CallFacts)
+    bool tail_fold;              // concat3 -> concat4 -> output layer as one 2 x d map per (row, step) (tail_fold.hpp): mode and net only
+    int tail_steps;              // the steps its table holds (CallFacts)
     bool split, mxv2, joint;     // split-fp16 mode; byte lo plane of the residual stream (byte_lo_plane); JMID (joint attention over an episode)
     RowMap rm;
     SeqGeom sg;
@@ -188,6 +197,8 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision
     p.attn = plan_attn(p.hd, t);
     p.qkv0 = p.split && p.joint && t.qkv0 != 1 && d % 32 == 0;      // (d % 32: the K tiles of the table's GEMM - as every GEMM of the net)
     p.qkv0_steps = cf.qkv0_steps;
+    p.tail_fold = p.split && t.tail_fold != 1 && d % 8 == 0 && d <= kTailMaxD && h->dmid <= kTailMaxMid && h->dlow <= kTailMaxLow;
+    p.tail_steps = cf.tail_steps;
     if (p.split) {
         const auto gemm = [&](int epi, int out, int N, int K) { return plan_gemm(gemm_mode(h), epi, out, p.M, N, K, cf, t); };
         p.in_proj = gemm(EPI_BIAS, p.joint ? OUT_QKV : OUT_F32, 3 * d, d);
@@ -286,6 +297,26 @@ int qkv0_build_table(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, cons
     return 0;
 }
 
+// The folded tail's table is capped the same way, per chunk lane: (2 d + 2) floats per (step, episode, agent) - 44 MB for a 43-episode
+// chunk of 5 agents at 50 steps and d_model 512.  Beyond the cap, and wherever a single step runs (jmid_net_eval), the table holds
+// one step and is rebuilt at the head of each.  An entry is the same bits either way (tail_fold_table_kernel).
+constexpr size_t kTailTableMaxBytes = size_t(128) << 20;
+int tail_table_steps(int steps, int Ec, int A, int d) {
+    const size_t bytes = (size_t)steps * Ec * A * (2 * d + 2) * sizeof(float);
+    return bytes <= kTailTableMaxBytes ? steps : 1;
+}
+
+int tail_build_table(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* hyp_chunk, int step0, int nsteps) {
+    const WeightTable& wt = h->wt;
+    ProfScope ps(h, KC_HYPER);
+    TailTableArgs ta{wt.concat3.W, wt.concat3.bias, wt.concat4.W, wt.concat4.bias, wt.linear.W, wt.linear.bias,
+                     hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, sb.weff, sb.beff,
+                     nsteps, p.R, h->d, h->dmid, h->dlow, h->hl.total,
+                     h->hl.g3, h->hl.b3, h->hl.g4, h->hl.b4, h->hl.go, h->hl.bo, h->range_flag};
+    HIPCHK(h, launch_tail_fold_table(ta, h->stream));
+    return 0;
+}
+
 EmbedArgs embed_args(const jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* x_chunk, const float* hyp_chunk, const float* th) {
     unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
     return EmbedArgs{x_chunk, h->wt.concat1.W, h->wt.concat1.bias, h->pe, hyp_chunk, th,
@@ -352,6 +383,94 @@ int qkv_planes(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int l, int
     return 0;
 }
 
+// The sampler's part of the output stage of step `step_idx`: what out_ddim*_kernel and tail_fold*_kernel share
+OutArgs sampler_args(const jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+                     float* e_out, const float* z_chunk) {
+    OutArgs oa{sb.Y4, h->wt.linear.W, h->wt.linear.bias, hyp_chunk, h->thyp + (size_t)step_idx * h->hl.total, x_chunk, e_out,
+               p.M, h->dlow, h->hl.total, h->hl.go, h->hl.bo,
+               h->c_e[step_idx], h->c_x[step_idx], h->n_x[step_idx], h->n_e[step_idx], p.rm,
+               nullptr, 0, 0.f, 0.f, 0.f};
+    if (h->ddpm && !e_out) {
+        oa.ddpm = 1;
+        oa.z = h->p_noise[step_idx] ? z_chunk : nullptr;
+        oa.c0 = h->p_c0[step_idx];
+        oa.c1 = h->p_c1[step_idx];
+        oa.sigma = h->p_sigma[step_idx];
+    }
+    return oa;
+}
+
+// The tail of a step in the split-fp16 modes without its GEMMs (tail_fold.hpp): two dot products per token with the (row, step)'s
+// 2 x d map, then the sampler update and the next step's embedding - one launch, one wave per trajectory piece or per token
+// (StepPlan::out_tpw, as out_ddim*_kernel).  F16X3 reads X_hi + X_lo as its concat3 does, the other modes X_hi.
+int folded_tail(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+                float* e_out, const float* z_chunk, int next_step) {
+    const int M = p.M, d = h->d;
+    if (p.tail_steps <= 1)
+        if (int rc = tail_build_table(h, p, sb, hyp_chunk, step_idx, 1)) return rc;
+    const size_t at = p.tail_steps <= 1 ? 0 : (size_t)step_idx * p.R;
+    const TailFoldArgs fa{sb.Xh, sb.Xl, sb.weff + at * 2 * d, sb.beff + at * 2, d};
+    const OutArgs oa = sampler_args(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
+    const bool embed_next = next_step >= 0 && !e_out;
+    const EmbedArgs en = embed_next ? embed_args(h, p, sb, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+    const bool lo = !h->x2;
+    ProfScope ps(h, KC_OUT_DDIM);
+    const auto launch = [&](auto* kernel, int waves, auto... tpw) {
+        hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), h->stream, fa, oa, en, tpw...);
+    };
+    const auto pick = [&](auto embed, auto with_lo) {
+        constexpr bool EN = decltype(embed)::value, LO = decltype(with_lo)::value;
+        if (p.out_tpw) launch(tail_fold_traj_kernel<EN, LO>, M / p.out_tpw, p.out_tpw);
+        else launch(tail_fold_kernel<EN, LO>, M);
+    };
+    if (embed_next && lo) pick(std::true_type{}, std::true_type{});
+    else if (embed_next) pick(std::true_type{}, std::false_type{});
+    else if (lo) pick(std::false_type{}, std::true_type{});
+    else pick(std::false_type{}, std::false_type{});
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// output layer + sampler update (or e_theta out) + the next step's embedding on the Y4 rows the tail GEMMs left
+int output_stage(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+                 float* e_out, const float* z_chunk, int next_step) {
+    const int M = p.M;
+    ProfScope ps(h, KC_OUT_DDIM);
+    const OutArgs oa = sampler_args(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
+    const bool embed_next = next_step >= 0 && !e_out;
+    const EmbedArgs en = embed_next ? embed_args(h, p, sb, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+    // four waves per workgroup: one wave per piece of a trajectory (out_tpw tokens), or one per token
+    const auto launch = [&](auto* kernel, int waves, auto... tpw) {
+        hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), h->stream, oa, en, tpw...);
+    };
+    if (p.out_tpw && embed_next) launch(out_ddim_traj_kernel<true>, M / p.out_tpw, p.out_tpw);
+    else if (p.out_tpw) launch(out_ddim_traj_kernel<false>, M / p.out_tpw, p.out_tpw);
+    else if (embed_next) launch(out_ddim_kernel<true>, M);
+    else launch(out_ddim_kernel<false>, M);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// The tail of a step in the split-fp16 modes on the residual stream's planes: folded (tail_fold.hpp), or
+// concat3 -> concat4 as two launches, the output layer + sampler update + next embedding as a third (one fused kernel for all
+// three was built in round 3 and measured slower at every batch size: docs/NOTEBOOK.md)
+int net_tail(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+             float* e_out, const float* z_chunk, int next_step) {
+    if (p.tail_fold) return folded_tail(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
+    const int M = p.M, d = h->d;
+    const WeightTable& wt = h->wt;
+    const float* thyp = h->thyp + (size_t)step_idx * h->hl.total;
+    GemmHArgs g = gemm_h_args(h, p.rm, M, sb.Xh, sb.Xl, wt.concat3, h->dmid, d);
+    g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
+    g.Chi = sb.Y3h; g.Clo = sb.Y3l; g.ldc = h->dmid; g.goff = h->hl.g3; g.boff = h->hl.b3;
+    if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, KC_GEMM_TAIL, g, p.concat3))) return rc;
+    g = gemm_h_args(h, p.rm, M, sb.Y3h, sb.Y3l, wt.concat4, h->dlow, h->dmid);
+    g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
+    g.C = sb.Y4; g.ldc = h->dlow; g.goff = h->hl.g4; g.boff = h->hl.b4;
+    if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, KC_GEMM_TAIL, g, p.concat4))) return rc;
+    return output_stage(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
+}
+
 // one evaluation of the net on a chunk of whole episodes + (optionally) the DDIM update, as its plan says
 int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
              float* e_out, const float* z_chunk = nullptr, bool embed_done = false, int next_step = -1) {
@@ -416,43 +535,9 @@ int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx
             // (the residual stream ends with the last layer: concat3 reads X_hi only)
             if (int rc = residual_block(h, p, p.linear2, sb, sb.H1h, sb.H1l, ff, w.linear2, w.norm2, KC_GEMM_FF2, l + 1 == h->tf_layer)) return rc;
         }
-        // concat3 -> concat4 as two launches, the output layer + sampler update + next embedding as a third (one fused kernel for all
-        // three was built in round 3 and measured slower at every batch size: docs/NOTEBOOK.md)
-        GemmHArgs g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, wt.concat3, h->dmid, d);
-        g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
-        g.Chi = sb.Y3h; g.Clo = sb.Y3l; g.ldc = h->dmid; g.goff = h->hl.g3; g.boff = h->hl.b3;
-        if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, KC_GEMM_TAIL, g, p.concat3))) return rc;
-        g = gemm_h_args(h, rm, M, sb.Y3h, sb.Y3l, wt.concat4, h->dlow, h->dmid);
-        g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
-        g.C = sb.Y4; g.ldc = h->dlow; g.goff = h->hl.g4; g.boff = h->hl.b4;
-        if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, KC_GEMM_TAIL, g, p.concat4))) return rc;
+        return net_tail(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
     }
-    {
-        ProfScope ps(h, KC_OUT_DDIM);
-        OutArgs oa{sb.Y4, wt.linear.W, wt.linear.bias, hyp_chunk, thyp, x_chunk, e_out,
-                   M, h->dlow, h->hl.total, h->hl.go, h->hl.bo,
-                   h->c_e[step_idx], h->c_x[step_idx], h->n_x[step_idx], h->n_e[step_idx], rm,
-                   nullptr, 0, 0.f, 0.f, 0.f};
-        if (h->ddpm && !e_out) {
-            oa.ddpm = 1;
-            oa.z = h->p_noise[step_idx] ? z_chunk : nullptr;
-            oa.c0 = h->p_c0[step_idx];
-            oa.c1 = h->p_c1[step_idx];
-            oa.sigma = h->p_sigma[step_idx];
-        }
-        const bool embed_next = next_step >= 0 && !e_out;
-        const EmbedArgs en = embed_next ? embed_args(h, p, sb, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
-        // four waves per workgroup: one wave per piece of a trajectory (out_tpw tokens), or one per token
-        const auto launch = [&](auto* kernel, int waves, auto... tpw) {
-            hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), h->stream, oa, en, tpw...);
-        };
-        if (p.out_tpw && embed_next) launch(out_ddim_traj_kernel<true>, M / p.out_tpw, p.out_tpw);
-        else if (p.out_tpw) launch(out_ddim_traj_kernel<false>, M / p.out_tpw, p.out_tpw);
-        else if (embed_next) launch(out_ddim_kernel<true>, M);
-        else launch(out_ddim_kernel<false>, M);
-        HIPCHK(h, hipGetLastError());
-    }
-    return 0;
+    return output_stage(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
 }
 
 // Episodes per pass of the 50-step loop when nothing is forced: large enough to fill the chip several times over per
@@ -644,6 +729,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     facts.attn_nsplit = ns_call;
     const int n_steps = (int)h->beta.size();
     facts.qkv0_steps = single_step < 0 ? qkv0_table_steps(n_steps, Ec, A, h->d) : 1;
+    facts.tail_steps = single_step < 0 && h->tune.tail_fold != 2 ? tail_table_steps(n_steps, Ec, A, h->d) : 1;
     std::vector<StepPlan> plans;            // a handful at most
     std::vector<int> chunk_plan;            // chunk -> its plan
     for (int ec : chunk_sizes) {
@@ -653,7 +739,8 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         chunk_plan.push_back((int)j);
     }
     const size_t qkv0_rows = plans[0].qkv0 ? (size_t)facts.qkv0_steps * Ec * A * 3 : 0;
-    const size_t lane_floats = step_ws_floats(h, Mc, precision, sg_full, ns_call, nullptr, nullptr, qkv0_rows);
+    const size_t tail_rows = plans[0].tail_fold ? (size_t)facts.tail_steps * Ec * A : 0;
+    const size_t lane_floats = step_ws_floats(h, Mc, precision, sg_full, ns_call, nullptr, nullptr, qkv0_rows, tail_rows);
     const size_t need = io_off + lanes * lane_floats;
     if (int rc = ensure_arena(h, need)) return rc;
     Carver c(h->arena);
@@ -670,7 +757,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     }
     float* z_lane = z_fill ? c.take((size_t)lanes * Mc * 2) : nullptr;
     StepBuffers sbs[jmid_ctx::kMaxLanes];
-    for (int l = 0; l < lanes; ++l) step_ws_floats(h, Mc, precision, sg_full, ns_call, &sbs[l], h->arena + io_off + l * lane_floats, qkv0_rows);
+    for (int l = 0; l < lanes; ++l) step_ws_floats(h, Mc, precision, sg_full, ns_call, &sbs[l], h->arena + io_off + l * lane_floats, qkv0_rows, tail_rows);
     const StepBuffers& sb = sbs[0];
     if (precision != JMID_PREC_F32) {
         HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
@@ -764,6 +851,7 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
                 // layer 0's coefficient table of this chunk for all steps, ahead of its first step, on the chunk's own stream
                 const StepPlan& pl = plans[chunk_plan[c0 + l]];
                 if (!rc && i == 0 && pl.qkv0 && pl.qkv0_steps > 1) rc = qkv0_build_table(h, pl, sbs[l], hc, 0, n_steps);
+                if (!rc && i == 0 && pl.tail_fold && pl.tail_steps > 1) rc = tail_build_table(h, pl, sbs[l], hc, 0, n_steps);
                 if (!rc) rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, h->tune.fuse_embed && i > 0,
                                         h->tune.fuse_embed && i + 1 < n_steps ? i + 1 : -1);
                 if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);
@@ -874,13 +962,13 @@ int dbg_qkv0(jmid_ctx* h, int E, int A, int K, int T, const float* x, const floa
         c.take(M * 3 * d);
         io_off = c.off;
     }
-    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, precision, p.sg, 1, nullptr, nullptr, rows))) return rc;
+    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, precision, p.sg, 1, nullptr, nullptr, rows, 0))) return rc;
     Carver c(h->arena);
     float* x_d = c.take(M * 2);
     float* hyp_d = c.take(EA * h->hl.total);
     float* out_d = c.take(M * 3 * d);
     StepBuffers sb;
-    step_ws_floats(h, M, precision, p.sg, 1, &sb, h->arena + io_off, rows);
+    step_ws_floats(h, M, precision, p.sg, 1, &sb, h->arena + io_off, rows, 0);
     HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
     HIPCHK(h, hipMemsetAsync(sb.Vth, 0, sb.vt_elems * sizeof(half_t), h->stream));
     HIPCHK(h, hipMemsetAsync(sb.Vtl, 0, sb.vt_elems * sizeof(half_t), h->stream));
@@ -896,6 +984,58 @@ int dbg_qkv0(jmid_ctx* h, int E, int A, int K, int T, const float* x, const floa
     int flag = 0;
     HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(qkv, out_d, M * 3 * d * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (thyp_row)
+        HIPCHK(h, hipMemcpyAsync(thyp_row, h->thyp + (size_t)step * h->hl.total, h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (flag) return flagged_call(h, flag);
+    return 0;
+}
+
+// jmid_dbg_tail: the tail of step `step` alone on X [M, d] (fp32, split here into the planes the mode's concat3 reads: X_hi, and X_lo
+// in F16X3), as a step of a one-chunk call runs it - folded, or the two GEMMs + the output kernel with "tail_fold" = 1 -> e [M, 2].
+int dbg_tail(jmid_ctx* h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision, float* e, float* thyp_row) {
+    if (int rc = check_ready(h)) return rc;
+    if (!X || !hyp || !e || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen) return fail(h, JMID_EINVAL, "jmid_dbg_tail: bad arguments");
+    if (hyp_width != h->hl.total) return fail(h, JMID_EINVAL, "jmid_dbg_tail: hyp rows must be " + std::to_string(h->hl.total) + " wide");
+    if (precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX)
+        return fail(h, JMID_EINVAL, "jmid_dbg_tail: a split-fp16 mode only");
+    if (step < 0 || step >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "jmid_dbg_tail: step outside the step table");
+    h->mx = precision == JMID_PREC_F16MX;
+    h->x2 = precision == JMID_PREC_F16X2 || h->mx;
+    HIPCHK(h, hipSetDevice(h->device));
+    h->last_pos = nullptr;
+    const size_t M = (size_t)E * K * A * T, EA = (size_t)E * A;
+    const int d = h->d;
+    CallFacts facts;          // (an idle handle: nothing else in flight, one launch, the table of one step)
+    const StepPlan p = plan_step(h, E, A, K, T, precision, facts);
+    const size_t rows = p.tail_fold ? EA : 0;
+    size_t io_off;
+    {
+        Carver c(nullptr);
+        c.take(M * d);
+        c.take(EA * h->hl.total);
+        c.take(M * 2);
+        io_off = c.off;
+    }
+    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, precision, p.sg, 1, nullptr, nullptr, 0, rows))) return rc;
+    Carver c(h->arena);
+    float* X_d = c.take(M * d);
+    float* hyp_d = c.take(EA * h->hl.total);
+    float* e_d = c.take(M * 2);
+    StepBuffers sb;
+    step_ws_floats(h, M, precision, p.sg, 1, &sb, h->arena + io_off, 0, rows);
+    HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemcpyAsync(X_d, X, M * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hyp_d, hyp, EA * h->hl.total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    // (the planes' padding rows up to the next multiple of 128 only ever feed discarded output rows of the GEMM path, but must be finite)
+    HIPCHK(h, hipMemsetAsync(sb.Xh, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(sb.Xl, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
+    hipLaunchKernelGGL(tail_split_rows_kernel, dim3(512), dim3(256), 0, h->stream, X_d, sb.Xh, h->x2 ? nullptr : sb.Xl, (int)M, d);
+    HIPCHK(h, hipGetLastError());
+    if (int rc = net_tail(h, p, sb, step, nullptr, hyp_d, e_d, nullptr, -1)) return rc;
+    int flag = 0;
+    HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(e, e_d, M * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (thyp_row)
         HIPCHK(h, hipMemcpyAsync(thyp_row, h->thyp + (size_t)step * h->hl.total, h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -22,6 +22,7 @@ struct CallFacts {
     int one_chunk = 1;
     int attn_nsplit = 1;      // split-KV factor of the attention launches: per call, never per chunk (run_network)
     int qkv0_steps = 1;       // steps a chunk's coefficient table of layer 0 holds (qkv0.hpp): all of the call's, or 1 = rebuilt at the head of every step
+    int tail_steps = 1;       // the same for the folded tail's table of 2 x d maps (tail_fold.hpp)
 };
 
 // the arithmetic of a split-fp16 GEMM: a template parameter of every kernel (a run-time flag in the K loops cost F16X3 4 %)

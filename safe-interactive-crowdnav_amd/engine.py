@@ -727,6 +727,23 @@ class JmidEngine:
                                             _lib.PRECISIONS[precision], C.c_void_p(out.ctypes.data), C.c_void_p(thyp.ctypes.data)))
         return out, thyp
 
+    def dbg_tail(self, X: np.ndarray, hyp: np.ndarray, step: int, dims: Tuple[int, int, int, int], precision: str = "f16mx"):
+        """The tail of one denoise step alone (``jmid_dbg_tail``; the "tail_fold" knob decides how it runs): X [M, d] stands for the
+        last LayerNorm's output, hyp [E * A, hyper width] -> (e [M, 2] float32, the time part of the hyper nets at step-table entry
+        ``step`` [hyper width])."""
+        E, A, K, T = (int(v) for v in dims)
+        X = np.ascontiguousarray(X, np.float32)
+        hyp = np.ascontiguousarray(hyp, np.float32)
+        M, d = E * K * A * T, 2 * self.dims.ctx_dim
+        width = self.hyper_width()
+        if X.shape != (M, d) or hyp.shape != (E * A, width):
+            raise ValueError(f"expected X [{M}, {d}] and hyp [{E * A}, {width}]")
+        out = np.empty((M, 2), np.float32)
+        thyp = np.empty((width,), np.float32)
+        self._check(self._lib.jmid_dbg_tail(self._h, E, A, K, T, C.c_void_p(X.ctypes.data), C.c_void_p(hyp.ctypes.data), width, int(step),
+                                            _lib.PRECISIONS[precision], C.c_void_p(out.ctypes.data), C.c_void_p(thyp.ctypes.data)))
+        return out, thyp
+
     def hyper_width(self) -> int:
         """Row length of the ConcatSquash hyper vectors, gate1 | bias1 | gate3 | bias3 | gate4 | bias4 | gateO | biasO (the library
         checks it: ``jmid_dbg_qkv0`` refuses any other)."""

@@ -9,7 +9,7 @@ for m in ("f16mx", "f16x2", "f16x3"):
           r["frac_of_split_peak"], "timed", r["timed_region"]["avg_launch_ms"], "path", r["path_achieved"], r["path_frac"], "busy",
           r["mfma_busy"]["dominant_kernel"], r["mfma_busy"]["whole_call"])
     print("  ", {a: (b["avg_ms"], b["tflops"]) for a, b in k.items()})
-    s = 3 * sum(k[c]["avg_ms"] for c in ("gemm_qkv", "gemm_attn_out", "gemm_ff1", "gemm_ff2", "attention")) + 2 * k["gemm_tail"]["avg_ms"]
+    s = 3 * sum(k[c]["avg_ms"] for c in ("gemm_qkv", "gemm_attn_out", "gemm_ff1", "gemm_ff2", "attention")) + 2 * k.get("gemm_tail", {"avg_ms": 0.0})["avg_ms"]      # (no tail GEMMs on the folded path: csrc/tail_fold.hpp)
     print("   sum/step", round(s, 3), "attention share", round(3 * k["attention"]["avg_ms"] / s, 3))
 print(j["mean_ADE_between_modes_m"], "cpu", j["cpu_baseline"]["value"])
 print("hbm", j["hbm"]["bytes_per_trajectory"], j["hbm"]["GBps"], j["hbm"]["frac"])
