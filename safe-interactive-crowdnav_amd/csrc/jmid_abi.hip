@@ -51,7 +51,7 @@ int topk_on_device(jmid_ctx* h, int E, int A, int K, int T, int k, const float* 
     g.ll = reinterpret_cast<double*>(h->kde_ws);
     g.Y = reinterpret_cast<double*>(h->kde_ws + o_Y);
     g.pos = pos; g.bw = bw; g.sel = sel; g.logw = logw;
-    ProfScope ps(h, KC_TOPK);
+    ProfScope ps(h, KC_TOPK, h->stream);
     HIPCHK(h, launch_kde(g, h->stream));
     return 0;
 }
@@ -118,9 +118,8 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
         if (int rc = fill_noise(h, seeded->seed, h->noise_ids, E, (size_t)K * A * T * 2, 0, dev + o_xT, nullptr, h->stream)) return rc;
     }
     int rc = 0;
-    h->chained = true;
     {
-        ProfScope ps(h, KC_ENCODER);
+        ProfScope ps(h, KC_ENCODER, h->stream);
         if (scene) {
             const jmid_ctx::SceneWs& sc = h->scene;
             SceneGatherArgs ga{};
@@ -140,8 +139,9 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
         ea.ctx = dev + o_ctx; ea.n = (int)n; ea.Th = (int)Th; ea.H = h->H;
         if (!rc && launch_encoder(ea, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": encoder launch failed");
     }
-    if (!rc) rc = run_network(h, E, A, K, T, dev + o_xT, dev + o_ctx, dev + o_p0, dt, precision, -1, nullptr, pos_out ? dev + o_pos : nullptr,
-                              nullptr, JMID_MEM_DEVICE);
+    DenoiseCall c{E, A, K, T, precision, JMID_MEM_DEVICE};       // a stage of the chain: no caller-stream ordering, the flag comes with the one download
+    c.x_in = dev + o_xT; c.ctx = dev + o_ctx; c.p0 = dev + o_p0; c.dt = dt; c.pos_out = pos_out ? dev + o_pos : nullptr; c.chained = true;
+    if (!rc) rc = run_network(h, c);
     if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw);
     if (!rc && fc_out) {
         const jmid_ctx::SceneWs& sc = h->scene;
@@ -160,7 +160,6 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
         aa.E = E; aa.N = sc.N; aa.A = A; aa.k = k; aa.T = T; aa.full = rank ? 0 : 1;
         if (launch_assemble(aa, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": assemble launch failed");
     }
-    h->chained = false;
     if (rc) return rc;
     const bool flagged = precision != JMID_PREC_F32;
     if (flagged) HIPCHK(h, hipMemcpyAsync(dev + o_flag, h->range_flag, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
@@ -474,7 +473,9 @@ int jmid_denoise_ddpm(jmid_handle_t h, int E, int A, int K, int T, const float* 
                       const float* p0, float dt, int precision, float* vel_out, float* pos_out, int mem) {
     if (!h) return JMID_EINVAL;
     if (!z) return fail(h, JMID_EINVAL, "null z");
-    return run_network(h, E, A, K, T, x_T, ctx, p0, dt, precision, -1, vel_out, pos_out, nullptr, mem, z);
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.x_in = x_T; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.z = z;
+    return run_network(h, c);
 }
 
 int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* nbr_sum, const float* edge_mask,
@@ -504,7 +505,7 @@ int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* n
         xs = dx; ns = dn; em = de;
     }
     {
-        ProfScope ps(h, KC_ENCODER);
+        ProfScope ps(h, KC_ENCODER, h->stream);
         EncArgs ea{};
         ea.x_st = xs; ea.nbr_sum = ns; ea.edge_mask = em;
         ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
@@ -524,7 +525,9 @@ int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* n
 int jmid_denoise(jmid_handle_t h, int E, int A, int K, int T, const float* x_T, const float* ctx, const float* p0,
                  float dt, int precision, float* vel_out, float* pos_out, int mem) {
     if (!h) return JMID_EINVAL;
-    return run_network(h, E, A, K, T, x_T, ctx, p0, dt, precision, -1, vel_out, pos_out, nullptr, mem);
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.x_in = x_T; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out;
+    return run_network(h, c);
 }
 
 int jmid_net_eval(jmid_handle_t h, int E, int A, int K, int T, int step_idx, const float* x, const float* ctx,
@@ -533,7 +536,9 @@ int jmid_net_eval(jmid_handle_t h, int E, int A, int K, int T, int step_idx, con
     if (!e_out) return fail(h, JMID_EINVAL, "null e_out");
     if (int rc = check_ready(h)) return rc;
     if (step_idx < 0 || step_idx >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "step_idx out of range");
-    return run_network(h, E, A, K, T, x, ctx, nullptr, 0.f, precision, step_idx, nullptr, nullptr, e_out, mem);
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.x_in = x; c.ctx = ctx; c.e_out = e_out; c.single_step = step_idx;
+    return run_network(h, c);
 }
 
 int jmid_episode_metrics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt,
@@ -596,7 +601,7 @@ int jmid_eval_statistics(jmid_handle_t h, int E, int A, int K, int T, const floa
         if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
     }
     {
-        ProfScope ps(h, KC_EVAL_STATS);
+        ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_eval_stats(g, h->stream));
     }
     if (mem == JMID_MEM_HOST) {
@@ -655,7 +660,7 @@ int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, con
         if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
     }
     {
-        ProfScope ps(h, KC_EVAL_STATS);
+        ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_eval_stats_masked(g, h->stream));
     }
     if (mem == JMID_MEM_HOST) {
@@ -707,7 +712,7 @@ int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const
         if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
     }
     {
-        ProfScope ps(h, KC_EVAL_STATS);
+        ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_collision_stats(g, h->stream));
     }
     if (host) {
@@ -758,7 +763,7 @@ int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* p
         g.logw = reinterpret_cast<float*>(h->kde_ws + o_lw);
     }
     {
-        ProfScope ps(h, KC_TOPK);
+        ProfScope ps(h, KC_TOPK, h->stream);
         HIPCHK(h, launch_kde(g, h->stream));
     }
     if (mem == JMID_MEM_HOST) {
@@ -937,7 +942,9 @@ int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t se
     if (!h) return JMID_EINVAL;
     if (!episode_ids) return fail(h, JMID_EINVAL, "jmid_denoise_seeded: null episode_ids");
     const SeedArgs sa{seed, episode_ids};
-    return run_network(h, E, A, K, T, nullptr, ctx, p0, dt, precision, -1, vel_out, pos_out, nullptr, mem, nullptr, &sa);
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.seeded = &sa;
+    return run_network(h, c);
 }
 
 int jmid_noise_fill(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out, int mem) {

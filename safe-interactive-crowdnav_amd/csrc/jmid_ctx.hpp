@@ -1,8 +1,9 @@
 // libjmid_hip.so -- what every translation unit of the host side shares: the handle, error / profiling helpers and the
 // internal entry points between the units.  gfx950 only.  No CPU fallback: every entry point that computes needs a HIP device.
+// The handle holds what outlives a call; the mode (CallMode), arguments (DenoiseCall) and lanes of the RUNNING call are values passed down.
 //   jmid_abi.hip      the C ABI proper (include/jmid_hip.h): handle lifetime, encode / denoise / topk / predict / scene / statistics, knobs, stream
 //   jmid_weights.hip  weight registry, operand planes (fp16 hi / lo, bf8 images, k16 panels), sampler step tables
-//   jmid_planner.hip  chunk plan, step workspace, one net evaluation (net_step), the denoise loop (run_network)
+//   jmid_planner.hip  chunk plan, step workspace, one net evaluation (net_step), the call plan and the phases of a denoise call (run_network)
 //   jmid_profile.hip  per-kernel-class HIP-event profiling
 //   jmid_diag.hip     jmid_dbg_* single-kernel entry points (-DJMID_DIAGNOSTICS only)
 #pragma once
@@ -153,12 +154,10 @@ struct jmid_ctx {
     int noise_ids_cap = 0;
     unsigned* noise_ids_pin = nullptr;       // pinned staging of the ids: a device-mode call may return before its copies have run, and the
     hipEvent_t ev_ids = nullptr;             // caller's array need not outlive the call; ev_ids = the last upload has left the staging
-    bool chained = false;       // the running run_network is a stage of jmid_predict: no caller-stream ordering, no flag round trip
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)
     bool lnx_off = false;       // a workgroup of that kernel once gave up waiting for a partner (range flag bit 1): the handle stays on GEMM + add_ln2
     int64_t lnx_timeouts = 0;   // calls on this handle that ended with JMID_ETIMEOUT for that reason (jmid_timeout_count)
-    int x2 = 0;          // the running call is JMID_PREC_F16X2 (set by the entry points, read by the launch helpers)
     int net_kind = 1, ctx_dim = 256, tf_layer = 3, nhead = 4, hist_len = 6;
     int d = 512, ff = 1024, dmid = 256, dlow = 128, H = 128;
     HyperLayout hl;
@@ -167,7 +166,6 @@ struct jmid_ctx {
     std::map<std::string, HalfPair> wsplit;  // hi/lo fp16 planes of the GEMM weights (F16X3 path)
     struct W8Image { unsigned char* p = nullptr; };
     std::map<std::string, W8Image> w8;       // JMID_PREC_F16MX: fp8 images of W_lo (w8_image_kernel), keyed like wsplit
-    int mx = 0;          // the running call is JMID_PREC_F16MX (x2 is set as well: everything not on the fp8 path runs as F16X2)
     std::map<std::string, HalfPair> w16;     // k16-panel copies of out_proj / linear2 for the fused GEMM + LayerNorm
     WeightTable wt;                          // what the launches read: pointers into the five maps above, valid while `finalized`
     int* range_flag = nullptr;               // device word: an fp16 operand left the fp16 range
@@ -206,6 +204,24 @@ constexpr size_t kLnxWords = 2 * jmid::SM_LNX_GRANULES;      // 32-bit words of 
 
 namespace jmid_host {
 
+// The arithmetic mode of one call, made from its `precision` argument by call_mode - the one place that says which precisions exist -
+// and passed down by value: the step plan holds it, the rules that run before a step plan take it as a parameter.
+struct CallMode {
+    int precision = JMID_PREC_F32;
+    bool split = false;     // a split-fp16 mode: the residual stream lives in hi / lo planes
+    int x2 = 0;             // F16X2 or F16MX: two MFMA terms (everything of F16MX that is not on the fp8 path runs as F16X2)
+    int mx = 0;             // F16MX
+    // what the GEMMs are planned for (plan_gemm keeps F16MX exactly where a weight has its bf8 image: N a multiple of 128, K of 64 -
+    // jmid_weights.hip makes one from N % 32 == 0 and K % 64 == 0)
+    GemmMode gemm = GM_X3;
+};
+inline bool call_mode(int precision, CallMode* m) {
+    if (precision != JMID_PREC_F32 && precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX) return false;
+    const int mx = precision == JMID_PREC_F16MX, x2 = precision == JMID_PREC_F16X2 || mx;
+    *m = CallMode{precision, precision != JMID_PREC_F32, x2, mx, !x2 ? GM_X3 : mx ? GM_MX : GM_X2};
+    return true;
+}
+
 std::string& thread_error();      // the last error of this thread (jmid_last_error(NULL))
 int fail(jmid_ctx* h, int code, const std::string& msg);
 
@@ -219,9 +235,10 @@ int fail(jmid_ctx* h, int code, const std::string& msg);
 struct ProfScope {
     jmid_ctx* h;
     int cls;
+    hipStream_t stream;
     bool on;
     EvPair ev;
-    ProfScope(jmid_ctx* h_, int cls_) : h(h_), cls(cls_), on((h_->prof_mask >> cls_) & 1u) {
+    ProfScope(jmid_ctx* h_, int cls_, hipStream_t s) : h(h_), cls(cls_), stream(s), on((h_->prof_mask >> cls_) & 1u) {
         if (on) {
             if (!h->ev_pool.empty()) {
                 ev = h->ev_pool.back();
@@ -230,12 +247,12 @@ struct ProfScope {
                 hipEventCreate(&ev.a);
                 hipEventCreate(&ev.b);
             }
-            hipEventRecord(ev.a, h->stream);
+            hipEventRecord(ev.a, stream);
         }
     }
     ~ProfScope() {
         if (on) {
-            hipEventRecord(ev.b, h->stream);
+            hipEventRecord(ev.b, stream);
             h->prof_ev[cls].push_back(ev);
         }
     }
@@ -269,7 +286,7 @@ void free_planes(jmid_ctx* h);
 void drop_graphs(jmid_ctx* h);
 void sync_lanes(jmid_ctx* h);
 int ensure_arena(jmid_ctx* h, size_t bytes);
-std::vector<int> plan_chunks(const jmid_ctx* h, int E, int tokens_per_episode);
+std::vector<int> plan_chunks(const jmid_ctx* h, const CallMode& m, int E, int tokens_per_episode);
 int check_ready(jmid_ctx* h);
 int order_in(jmid_ctx* h, int mem);
 int order_out(jmid_ctx* h, int mem);
@@ -280,15 +297,22 @@ struct SeedArgs {
 };
 int upload_noise_ids(jmid_ctx* h, const uint32_t* ids, int E);      // -> h->noise_ids, on h->stream
 int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream);
-int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, const float* ctx, const float* p0, float dt,
-                int precision, int single_step, float* vel_out, float* pos_out, float* e_out, int mem,
-                const float* z_in = nullptr, const SeedArgs* seeded = nullptr);
+// One denoise call (or, with single_step >= 0, one net evaluation -> e_out) as its entry point states it
+struct DenoiseCall {
+    int E, A, K, T, precision, mem;
+    const float *x_in = nullptr, *ctx = nullptr, *p0 = nullptr;     // x_in null: seeded
+    float dt = 0.f;
+    float *vel_out = nullptr, *pos_out = nullptr, *e_out = nullptr;
+    int single_step = -1;
+    const float* z = nullptr;             // DDPM noise [n_steps, M, 2] of the caller
+    const SeedArgs* seeded = nullptr;     // ... or x_T and the DDPM z drawn on the device
+    bool chained = false;                 // a stage of jmid_predict: no caller-stream ordering, no flag round trip
+};
+int run_network(jmid_ctx* h, DenoiseCall a);      // (by value: its host inputs become their uploads)
+int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in, const float* hyp, int hyp_width, int step, int precision,
+             float* out, float* thyp_row);      // jmid_dbg_qkv0 (tail = false) / jmid_dbg_tail: -DJMID_DIAGNOSTICS only
 int flagged_call(jmid_ctx* h, int flag);      // the status of a call whose range flag came back set (JMID_ETIMEOUT / JMID_ERANGE)
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T);
-#ifdef JMID_DIAGNOSTICS
-int dbg_qkv0(jmid_ctx* h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision, float* qkv, float* thyp_row);
-int dbg_tail(jmid_ctx* h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision, float* e, float* thyp_row);
-#endif
 // jmid_abi.hip
 int noise_entry(jmid_ctx* h, const char* who, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out,
                 unsigned* words, int mem);

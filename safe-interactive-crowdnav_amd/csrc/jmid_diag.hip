@@ -5,28 +5,32 @@
 #ifdef JMID_DIAGNOSTICS
 // ---------------------------------------------------------------------------------------------- diagnostics
 // Single-op entry points used by the unit tests (host buffers only).
+
+// What the entry points that launch start with: the mode of their `precision`, the device, the handle's range flag
+static int dbg_open(jmid_ctx* h, int precision, CallMode* mode) {
+    if (!call_mode(precision, mode)) return fail(h, JMID_EINVAL, "bad precision");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->range_flag) {
+        HIPCHK(h, hipMalloc((void**)&h->range_flag, sizeof(int)));
+        HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
+    }
+    return 0;
+}
+
 extern "C" {
 
-// ---------------------------------------------------------------------------------------------- diagnostics
-// Single-op entry points used by the unit tests (host buffers only).
+// The chunk plan of a mode without the one-launch rule (JMID_PREC_F16X3)
 int jmid_dbg_plan_chunks(int net_kind, int nhead, int lanes, int chunk_episodes, int E, int tokens_per_episode, int* sizes, int cap) {
-    if (E <= 0 || tokens_per_episode <= 0 || nhead <= 0 || !sizes || cap <= 0) return JMID_EINVAL;
-    jmid_ctx ctx;                      // host fields only: the planner reads net_kind, nhead, lanes, chunk_eps and the tuning
-    ctx.net_kind = net_kind; ctx.nhead = nhead; ctx.lanes = lanes; ctx.chunk_eps = chunk_episodes;
-    const std::vector<int> plan = plan_chunks(&ctx, E, tokens_per_episode);
-    for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) sizes[i] = plan[i];
-    return (int)plan.size();
+    return jmid_dbg_plan_chunks_mode(net_kind, nhead, lanes, chunk_episodes, E, tokens_per_episode, JMID_PREC_F16X3, sizes, cap);
 }
 
 // ... in arithmetic mode `precision` (the plan of a small batch depends on it: at most 2 560 tokens stay ONE chunk in JMID_PREC_F16MX)
 int jmid_dbg_plan_chunks_mode(int net_kind, int nhead, int lanes, int chunk_episodes, int E, int tokens_per_episode, int precision, int* sizes, int cap) {
-    if (E <= 0 || tokens_per_episode <= 0 || nhead <= 0 || !sizes || cap <= 0) return JMID_EINVAL;
-    if (precision != JMID_PREC_F32 && precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX) return JMID_EINVAL;
-    jmid_ctx ctx;                      // (model dimensions at their defaults: d_model 512)
+    CallMode mode;
+    if (E <= 0 || tokens_per_episode <= 0 || nhead <= 0 || !sizes || cap <= 0 || !call_mode(precision, &mode)) return JMID_EINVAL;
+    jmid_ctx ctx;                      // host fields only: the planner reads net_kind, nhead, lanes, chunk_eps and the tuning (model dimensions at their defaults: d_model 512)
     ctx.net_kind = net_kind; ctx.nhead = nhead; ctx.lanes = lanes; ctx.chunk_eps = chunk_episodes;
-    ctx.mx = precision == JMID_PREC_F16MX;
-    ctx.x2 = precision == JMID_PREC_F16X2 || ctx.mx;
-    const std::vector<int> plan = plan_chunks(&ctx, E, tokens_per_episode);
+    const std::vector<int> plan = plan_chunks(&ctx, mode, E, tokens_per_episode);
     for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) sizes[i] = plan[i];
     return (int)plan.size();
 }
@@ -53,15 +57,8 @@ int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int smal
 int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const float* Wt, const float* bias, int relu,
                   int precision, float* C) {
     if (!h || !A || !Wt || !C) return JMID_EINVAL;
-    if (precision != JMID_PREC_F32 && precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX)
-        return fail(h, JMID_EINVAL, "bad precision");
-    h->mx = precision == JMID_PREC_F16MX;
-    h->x2 = precision == JMID_PREC_F16X2 || h->mx;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->range_flag) {
-        HIPCHK(h, hipMalloc((void**)&h->range_flag, sizeof(int)));
-        HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
-    }
+    CallMode mode;
+    if (int rc = dbg_open(h, precision, &mode)) return rc;
     float *dA, *dW, *dB = nullptr, *dC;
     HIPCHK(h, hipMalloc((void**)&dA, (size_t)M * K * 4));
     HIPCHK(h, hipMalloc((void**)&dW, (size_t)N * K * 4));
@@ -78,7 +75,7 @@ int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const fl
     if (precision == JMID_PREC_F32) {
         GemmArgs g{};
         g.A = dA; g.lda = K; g.W = dW; g.ldw = K; g.bias = dB; g.C = dC; g.ldc = N; g.M = M; g.N = N; g.K = K;
-        rc = relu ? run_gemm<EPI_BIAS_RELU>(h, KC_GEMM_QKV, g) : run_gemm<EPI_BIAS>(h, KC_GEMM_QKV, g);
+        rc = relu ? run_gemm<EPI_BIAS_RELU>(h, h->stream, KC_GEMM_QKV, g) : run_gemm<EPI_BIAS>(h, h->stream, KC_GEMM_QKV, g);
     } else {
         const size_t pa = blk_plane_elems(M, K) * 2, pw = blk_plane_elems(N, K) * 2;
         HIPCHK(h, hipMalloc((void**)&ah, pa));
@@ -93,14 +90,14 @@ int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const fl
                            h->range_flag, kWScale);
         GemmHArgs g{};
         g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.bias = dB; g.C = dC; g.ldc = N;
-        g.M = M; g.N = N; g.K = K;
-        if (h->mx && N % 32 == 0 && K % 64 == 0) {
+        g.M = M; g.N = N; g.K = K; g.x2 = mode.x2;
+        if (mode.mx && N % 32 == 0 && K % 64 == 0) {
             if (int rc8 = make_w8(h, dW, N, K, &w8img)) return rc8;
             g.W8 = w8img.p;
         }
         // (an idle handle: nothing else in flight, one launch)
-        const GemmPlan plan = plan_gemm(gemm_mode(h), relu ? EPI_BIAS_RELU : EPI_BIAS, OUT_F32, M, N, K, CallFacts{}, h->tune);
-        rc = relu ? run_gemm_h<EPI_BIAS_RELU, OUT_F32>(h, KC_GEMM_QKV, g, plan) : run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g, plan);
+        const GemmPlan plan = plan_gemm(mode.gemm, relu ? EPI_BIAS_RELU : EPI_BIAS, OUT_F32, M, N, K, CallFacts{}, h->tune);
+        rc = relu ? run_gemm_h<EPI_BIAS_RELU, OUT_F32>(h, h->stream, KC_GEMM_QKV, g, plan) : run_gemm_h<EPI_BIAS, OUT_F32>(h, h->stream, KC_GEMM_QKV, g, plan);
     }
     if (!rc) {
         hipError_t e = hipStreamSynchronize(h->stream);
@@ -117,15 +114,8 @@ int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const fl
 
 int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int precision, float* OUT) {
     if (!h || !QKV || !OUT) return JMID_EINVAL;
-    if (precision != JMID_PREC_F32 && precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX)
-        return fail(h, JMID_EINVAL, "bad precision");
-    h->mx = precision == JMID_PREC_F16MX;
-    h->x2 = precision == JMID_PREC_F16X2 || h->mx;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->range_flag) {
-        HIPCHK(h, hipMalloc((void**)&h->range_flag, sizeof(int)));
-        HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
-    }
+    CallMode mode;
+    if (int rc = dbg_open(h, precision, &mode)) return rc;
     const size_t Mt = (size_t)nseq * S;
     const int d = h->d, hd = h->d / h->nhead;
     float *dQ, *dO;
@@ -136,7 +126,7 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
     std::vector<half_t*> tmp;
     if (precision == JMID_PREC_F32) {
         AttnArgs aa{dQ, dO, S, d, h->nhead, 1.0f / sqrtf((float)hd), nullptr, nullptr};
-        ProfScope ps(h, KC_ATTN);
+        ProfScope ps(h, KC_ATTN, h->stream);
         hipError_t e = launch_attn_f32(aa, nseq, hd, plan_attn(hd, h->tune).pack, h->stream);
         if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
     } else {
@@ -161,9 +151,9 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
             tmp.push_back(reinterpret_cast<half_t*>(mlpart));
         }
         AttnHArgs aa{b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], S, Spad, d, h->nhead, 1.0f / sqrtf((float)hd),
-                     h->range_flag, ns, opart, mlpart, h->x2};
+                     h->range_flag, ns, opart, mlpart, mode.x2};
         {
-            ProfScope ps(h, KC_ATTN);
+            ProfScope ps(h, KC_ATTN, h->stream);
             hipError_t e = launch_attn_f16x3(aa, nseq, hd, plan_attn(hd, h->tune), h->stream);
             if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
         }
@@ -185,13 +175,8 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
     // (gemm_ln2_mx.hpp): fused = 1 the row-complete kernel, 0 the GEMM + add_ln2 pair.  X comes back as hi + bf8(lo).
     if (!h || !A || !Wt || !bias || !gamma || !beta || !X || M <= 0 || K % 64 != 0) return JMID_EINVAL;
     constexpr int N = GLN_BN;
-    HIPCHK(h, hipSetDevice(h->device));
-    h->mx = 1;
-    h->x2 = 1;
-    if (!h->range_flag) {
-        HIPCHK(h, hipMalloc((void**)&h->range_flag, sizeof(int)));
-        HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
-    }
+    CallMode mode;
+    if (int rc = dbg_open(h, JMID_PREC_F16MX, &mode)) return rc;
     std::vector<void*> tmp;
     auto dalloc = [&](size_t bytes, const void* host) -> void* {
         void* p = nullptr;
@@ -233,24 +218,23 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
         if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
     } else {
         GemmHArgs g{};
-        g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.W8 = img.p; g.bias = dB; g.C = dY; g.ldc = N; g.M = M; g.N = N; g.K = K;
+        g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.W8 = img.p; g.bias = dB; g.C = dY; g.ldc = N; g.M = M; g.N = N; g.K = K; g.x2 = mode.x2;
         if (fused == 3) {        // the small-launch kernel with the statistics exchange (gemm_small.hpp, OUT_LNX)
             unsigned long long* xs = (unsigned long long*)dalloc(kLnxWords * sizeof(unsigned), nullptr);
             const GemmPlan lnx = plan_gemm(GM_MX, EPI_BIAS, OUT_LNX, M, N, K, CallFacts{}, h->tune);      // (an idle handle: nothing else in flight, one launch)
             if (!xs || lnx.shape == GS_NONE) return fail(h, JMID_EINVAL, "jmid_dbg_gemm_ln_mx: shape does not take the small kernel with the statistics exchange");
             g.ln_gamma = dG; g.ln_beta = dT; g.ln_xh = xh; g.ln_xl = nullptr; g.ln_xl8 = xl8; g.ln_xchg = xs; g.ln_eps = 1e-5f; g.ln_no_lo = 0;
             (void)hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream);
-            rc = run_gemm_lnx_small(h, KC_GEMM_OUT, g, lnx);
+            rc = run_gemm_lnx_small(h, h->stream, KC_GEMM_OUT, g, lnx);
             if (!rc) {
                 int flag = 0;
                 (void)hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream);
                 (void)hipStreamSynchronize(h->stream);
                 if (flag & 2) rc = fail(h, JMID_EHIP, "jmid_dbg_gemm_ln_mx: a workgroup gave up waiting for its row tile's statistics");
             }
-        } else
-        {
-        rc = run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_OUT, g, plan_gemm(GM_MX, EPI_BIAS, OUT_F32, M, N, K, CallFacts{}, h->tune));
-        if (!rc) rc = run_add_ln(h, nullptr, dY, dG, dT, M, N, xh, reinterpret_cast<half_t*>(xl8), true, 0);
+        } else {
+            rc = run_gemm_h<EPI_BIAS, OUT_F32>(h, h->stream, KC_GEMM_OUT, g, plan_gemm(GM_MX, EPI_BIAS, OUT_F32, M, N, K, CallFacts{}, h->tune));
+            if (!rc) rc = run_add_ln(h, h->stream, nullptr, dY, dG, dT, M, N, xh, reinterpret_cast<half_t*>(xl8), true, 0);
         }
     }
     if (!rc) {
@@ -276,7 +260,7 @@ int jmid_dbg_add_layernorm(jmid_handle_t h, int M, int d, float* X, const float*
     HIPCHK(h, hipMemcpy(dY, Y, (size_t)M * d * 4, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(dG, gamma, (size_t)d * 4, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(dB, beta, (size_t)d * 4, hipMemcpyHostToDevice));
-    int rc = run_add_ln(h, dX, dY, dG, dB, M, d);
+    int rc = run_add_ln(h, h->stream, dX, dY, dG, dB, M, d);
     if (!rc) {
         hipError_t e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
@@ -288,14 +272,12 @@ int jmid_dbg_add_layernorm(jmid_handle_t h, int M, int d, float* X, const float*
 
 int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision,
                   float* qkv, float* thyp_row) {
-    if (!h) return JMID_EINVAL;
-    return dbg_qkv0(h, E, A, K, T, x, hyp, hyp_width, step, precision, qkv, thyp_row);
+    return h ? dbg_step(h, false, E, A, K, T, x, hyp, hyp_width, step, precision, qkv, thyp_row) : JMID_EINVAL;
 }
 
 int jmid_dbg_tail(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision,
                   float* e, float* thyp_row) {
-    if (!h) return JMID_EINVAL;
-    return dbg_tail(h, E, A, K, T, X, hyp, hyp_width, step, precision, e, thyp_row);
+    return h ? dbg_step(h, true, E, A, K, T, X, hyp, hyp_width, step, precision, e, thyp_row) : JMID_EINVAL;
 }
 
 int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem) {

@@ -44,6 +44,13 @@ struct StepBuffers {
     unsigned long long* ln_xchg;   // exchange granules of the small-launch GEMM + LayerNorm (gemm_small.hpp, OUT_LNX): kLnxWords words, zeroed once per call
 };
 
+// One chunk in flight: its step workspace, the stream its steps are enqueued on (lane 0: the handle's own) and, in a seeded DDPM call,
+// the z of its one current step.  A value of the call (CallPlan): the handle's stream is never reassigned.
+struct Lane : StepBuffers {
+    hipStream_t stream;
+    float* z;
+};
+
 half_t* take_half(Carver& c, size_t n) { return reinterpret_cast<half_t*>(c.take((n + 1) / 2)); }
 
 // attention geometry of a chunk
@@ -60,7 +67,7 @@ SeqGeom seq_geom(const jmid_ctx* h, int Ec, int A, int K, int T) {
 
 // qkv0_rows: coefficient rows of layer 0's table (steps x Ec A x 3), 0 = that layer runs its in_proj GEMM
 // tail_rows: maps of the folded tail's table (steps x Ec A), 0 = the tail runs its GEMMs: only then are Y3 / Y4 reserved
-size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom& sg, int nsplit, StepBuffers* sb,
+size_t step_ws_floats(const jmid_ctx* h, size_t Mc, const CallMode& m, const SeqGeom& sg, int nsplit, StepBuffers* sb,
                       char* base, size_t qkv0_rows, size_t tail_rows) {
     Carver c(base);
     StepBuffers s{};
@@ -68,7 +75,7 @@ size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom
     s.Y = c.take((Mc + 63) / 64 * 64 * h->d);     // (whole 64-row tiles)
     s.ln_xchg = reinterpret_cast<unsigned long long*>(c.take(kLnxWords));
     if (!tail_rows) s.Y4 = c.take(Mc * h->dlow);
-    if (precision == JMID_PREC_F32) {
+    if (!m.split) {
         s.QKV = c.take(Mc * 3 * h->d);
         s.ATT = c.take(Mc * h->d);
         s.H1 = c.take(Mc * h->ff);
@@ -115,7 +122,7 @@ size_t step_ws_floats(const jmid_ctx* h, size_t Mc, int precision, const SeqGeom
 
 // JMID_PREC_F16MX at d_model 512: second-generation LayerNorm kernels (gemm_ln2_mx.hpp) - the lo plane of the residual stream
 // is a byte plane (it lives in the memory of the fp16 one), the row statistics are summed in that file's order
-bool byte_lo_plane(const jmid_ctx* h) { return h->mx && h->d == GLN_BN && h->tune.mx_ln != 2; }
+bool byte_lo_plane(const jmid_ctx* h, const CallMode& m) { return m.mx && h->d == GLN_BN && h->tune.mx_ln != 2; }
 
 // A residual block of a layer in the split-fp16 modes - X <- LayerNorm(X + A . W^T + bias): out_proj + norm1 (K = d_model) and
 // linear2 + norm2 (K = d_ff) - runs in one of four ways.  All four give bit-identical rows.
@@ -133,27 +140,27 @@ struct ResidualPlan {
 };
 
 // THE function that picks the path of a residual block of M rows; everything else (the step plan, the chunk plan) asks it.
-ResidualPlan residual_path(const jmid_ctx* h, int M, int K, const CallFacts& cf) {
+ResidualPlan residual_path(const jmid_ctx* h, const CallMode& m, int M, int K, const CallFacts& cf) {
     // row-complete GEMM with residual + LayerNorm fused in from 7168 tokens (6 episodes
     // per launch: 36.8 vs 39.1 ms per 12-episode call; 5: 33.8 vs 33.5, 4: 29.6 vs 28.8)
     // (enough row tiles to occupy the chip); otherwise GEMM -> fp32 Y -> add_ln
     const Tuning& t = h->tune;
     if (h->d == GLN_BN && t.ln_fuse != 2 && (t.ln_fuse == 1 || M >= 7168))
-        return {byte_lo_plane(h) ? RB_GEMM_LN2 : RB_GEMM_LN, plan_ln_rows(byte_lo_plane(h), M, t), {}, false};
+        return {byte_lo_plane(h, m) ? RB_GEMM_LN2 : RB_GEMM_LN, plan_ln_rows(byte_lo_plane(h, m), M, t), {}, false};
     // one scene in F16MX (one chunk of <= 2048 rows, or two scenes' worth with two workgroups per CU; byte lo plane): GEMM + residual +
     // LayerNorm in ONE small launch (two launches per layer fewer); a handle on which such a kernel ever gave up waiting (lnx_off)
     // stays on the pair
-    if (byte_lo_plane(h) && !h->lnx_off) {
+    if (byte_lo_plane(h, m) && !h->lnx_off) {
         const GemmPlan lnx = plan_gemm(GM_MX, EPI_BIAS, OUT_LNX, M, h->d, K, cf, t);
         if (lnx.shape != GS_NONE) return {RB_LNX_SMALL, 0, lnx, false};
     }
-    return {RB_GEMM_ADD_LN, 0, plan_gemm(gemm_mode(h), EPI_BIAS, OUT_F32, M, h->d, K, cf, t), false};
+    return {RB_GEMM_ADD_LN, 0, plan_gemm(m.gemm, EPI_BIAS, OUT_F32, M, h->d, K, cf, t), false};
 }
 
-// Is a batch of `tokens` tokens ONE launch by default (plan_chunks keeps it one chunk)?  Shape and mode only.  There are two
+// Is a batch of `tokens` tokens ONE launch by default (plan_chunks keeps it one chunk)?  Shape and mode (its argument) only.  There are two
 // predicates on purpose: this one sizes the split-KV factor, which decides the order in which a sequence's keys are summed, so it
 // must not see a knob or lnx_off (the bits of a call must not depend on one); residual_path may, its paths give the same bits.
-bool one_launch_shape(const jmid_ctx* h, long tokens) { return h->mx && h->d == GLN_BN && tokens <= 2560; }
+bool one_launch_shape(const jmid_ctx* h, const CallMode& m, long tokens) { return m.mx && h->d == GLN_BN && tokens <= 2560; }
 
 // Everything one net evaluation on a chunk of Ec episodes decides, decided once per call and chunk size (run_network): the knobs
 // and lnx_off cannot change while a call runs.  net_step executes it.
@@ -161,10 +168,10 @@ struct StepPlan {
     int Ec, M, T;                // episodes and tokens (Ec * K * A * T) of the chunk, tokens per trajectory
     int R;                       // (episode, agent) rows of the chunk: Ec * A
     bool qkv0;                   // layer 0's Q / K / V^T planes are expanded from coefficient tables (qkv0.hpp) instead of its in_proj GEMM:
-    int qkv0_steps;              // mode and net only, never the token count; the steps a table holds (CallFacts)
-    bool tail_fold;              // concat3 -> concat4 -> output layer as one 2 x d map per (row, step) (tail_fold.hpp): mode and net only
-    int tail_steps;              // the steps its table holds (CallFacts)
-    bool split, mxv2, joint;     // split-fp16 mode; byte lo plane of the residual stream (byte_lo_plane); JMID (joint attention over an episode)
+                                 // mode and net only, never the token count; the steps a table holds: cf.qkv0_steps
+    bool tail_fold;              // concat3 -> concat4 -> output layer as one 2 x d map per (row, step) (tail_fold.hpp): mode and net only (cf.tail_steps)
+    CallMode mode;               // of the call: split-fp16 or not, x2, mx, the GEMM mode
+    bool mxv2, joint;            // from it: byte lo plane of the residual stream (byte_lo_plane); JMID (joint attention over an episode)
     RowMap rm;
     SeqGeom sg;
     int hd;
@@ -178,15 +185,16 @@ struct StepPlan {
     int out_tpw;                 // output kernel: tokens per wave of the per-trajectory form, 0 = one wave per token
 };
 
-StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision, const CallFacts& cf) {
+StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, const CallMode& mode, const CallFacts& cf) {
     StepPlan p{};
     const int d = h->d;
     p.Ec = Ec;
     p.M = Ec * K * A * T;
     p.T = T;
     p.R = Ec * A;
-    p.split = precision != JMID_PREC_F32;
-    p.mxv2 = p.split && byte_lo_plane(h);
+    p.mode = mode;
+    const bool split = mode.split;
+    p.mxv2 = split && byte_lo_plane(h, mode);
     p.joint = h->net_kind == JMID_NET_JMID;
     p.rm = make_rowmap(T, A, K * A, (unsigned long long)p.M);
     p.sg = seq_geom(h, Ec, A, K, T);
@@ -195,20 +203,18 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision
     p.cf = cf;
     const Tuning& t = h->tune;
     p.attn = plan_attn(p.hd, t);
-    p.qkv0 = p.split && p.joint && t.qkv0 != 1 && d % 32 == 0;      // (d % 32: the K tiles of the table's GEMM - as every GEMM of the net)
-    p.qkv0_steps = cf.qkv0_steps;
-    p.tail_fold = p.split && t.tail_fold != 1 && d % 8 == 0 && d <= kTailMaxD && h->dmid <= kTailMaxMid && h->dlow <= kTailMaxLow;
-    p.tail_steps = cf.tail_steps;
-    if (p.split) {
-        const auto gemm = [&](int epi, int out, int N, int K) { return plan_gemm(gemm_mode(h), epi, out, p.M, N, K, cf, t); };
+    p.qkv0 = split && p.joint && t.qkv0 != 1 && d % 32 == 0;      // (d % 32: the K tiles of the table's GEMM - as every GEMM of the net)
+    p.tail_fold = split && t.tail_fold != 1 && d % 8 == 0 && d <= kTailMaxD && h->dmid <= kTailMaxMid && h->dlow <= kTailMaxLow;
+    if (split) {
+        const auto gemm = [&](int epi, int out, int N, int K) { return plan_gemm(mode.gemm, epi, out, p.M, N, K, cf, t); };
         p.in_proj = gemm(EPI_BIAS, p.joint ? OUT_QKV : OUT_F32, 3 * d, d);
         p.linear1 = gemm(EPI_BIAS_RELU, OUT_SPLIT, h->ff, d);
         p.concat3 = gemm(EPI_CSL, OUT_SPLIT, h->dmid, d);
         p.concat4 = gemm(EPI_CSL, OUT_F32, h->dlow, h->dmid);
-        p.out_proj = residual_path(h, p.M, d, cf);
-        p.linear2 = residual_path(h, p.M, h->ff, cf);
+        p.out_proj = residual_path(h, mode, p.M, d, cf);
+        p.linear2 = residual_path(h, mode, p.M, h->ff, cf);
     }
-    if (p.split && p.joint) {
+    if (split && p.joint) {
         // S % 4 == 0: the QKV epilogue writes V^T itself; otherwise V row-major + v_transpose_kernel
         p.vt_direct = (p.sg.S % 4 == 0) && !t.no_vt_direct;
         // JMID_PREC_F16MX, head_dim 128 (the LDS-DMA attention kernel): bf8 images of K_hi / K_lo in the K_lo plane's memory, for
@@ -218,7 +224,7 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision
         p.q8l = p.k8 && t.attn_mx != 3;      // 3: Q_lo as fp16 (A/B)
         // one scene: the partial outputs of a split-KV attention launch are merged in front of the out-projection's K loop
         // (gemm_small.hpp, lnx_combine) when that launch is the one with the LayerNorm inside
-        p.out_proj.merge = p.out_proj.path == RB_LNX_SMALL && small_cmb_fits(p.attn, p.cf.attn_nsplit, h->x2, t);
+        p.out_proj.merge = p.out_proj.path == RB_LNX_SMALL && small_cmb_fits(p.attn, p.cf.attn_nsplit, mode.x2, t);
     }
     if (d <= 512 && p.M % T == 0 && t.out_traj != 2 && (t.out_traj == 1 || p.M >= 4096 * 4)) {
         // one wave per trajectory (T tokens) - or per piece of one, the largest divisor of T that still leaves >= 4096 waves -
@@ -234,37 +240,37 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, int precision
 // One residual block on the path the plan holds for it.  A planes [M, K]: the attention output (out_proj) or linear1's (linear2).
 // no_lo_out: the residual stream ends here (norm2 of the last layer: concat3 reads X_hi only), its lo plane is not written
 // where it is the byte plane or the mode is F16X2.
-int residual_block(jmid_ctx* h, const StepPlan& p, const ResidualPlan& rp, const StepBuffers& sb, const half_t* Ahi, const half_t* Alo,
+int residual_block(jmid_ctx* h, const StepPlan& p, const ResidualPlan& rp, const Lane& ln, const half_t* Ahi, const half_t* Alo,
                    int K, const LinearW& lin, const NormW& nrm, int cls, bool no_lo_out) {
     const int M = p.M, d = h->d;
-    unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
+    unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(ln.Xl) : nullptr;
     if (rp.path == RB_GEMM_LN2) {
-        GemmLn2Args g2{Ahi, lin.k16.hi, lin.w8, lin.bias, nrm.gamma, nrm.beta, sb.Xh, Xl8, M, K, 1e-5f, h->range_flag, no_lo_out};
-        ProfScope ps(h, cls);
-        HIPCHK(h, launch_gemm_ln2_mx(g2, rp.ln_rows, h->stream));
+        GemmLn2Args g2{Ahi, lin.k16.hi, lin.w8, lin.bias, nrm.gamma, nrm.beta, ln.Xh, Xl8, M, K, 1e-5f, h->range_flag, no_lo_out};
+        ProfScope ps(h, cls, ln.stream);
+        HIPCHK(h, launch_gemm_ln2_mx(g2, rp.ln_rows, ln.stream));
         return 0;
     }
     if (rp.path == RB_GEMM_LN) {
-        GemmLnArgs gl{Ahi, Alo, lin.k16.hi, lin.k16.lo, lin.bias, nrm.gamma, nrm.beta, sb.Xh, sb.Xl, M, K, 1e-5f, h->range_flag, h->x2};
-        gl.W8 = h->mx ? lin.w8 : nullptr;
-        gl.no_lo_out = h->x2 && no_lo_out;
-        ProfScope ps(h, cls);
-        HIPCHK(h, launch_gemm_ln(gl, rp.ln_rows, h->stream));
+        GemmLnArgs gl{Ahi, Alo, lin.k16.hi, lin.k16.lo, lin.bias, nrm.gamma, nrm.beta, ln.Xh, ln.Xl, M, K, 1e-5f, h->range_flag, p.mode.x2};
+        gl.W8 = p.mode.mx ? lin.w8 : nullptr;
+        gl.no_lo_out = p.mode.x2 && no_lo_out;
+        ProfScope ps(h, cls, ln.stream);
+        HIPCHK(h, launch_gemm_ln(gl, rp.ln_rows, ln.stream));
         return 0;
     }
-    GemmHArgs g = gemm_h_args(h, p.rm, M, Ahi, Alo, lin, d, K);
-    g.C = sb.Y; g.ldc = d;
+    GemmHArgs g = gemm_h_args(p.mode, p.rm, M, Ahi, Alo, lin, d, K);
+    g.C = ln.Y; g.ldc = d;
     if (rp.path == RB_LNX_SMALL) {
         if (rp.merge) {
-            g.cmb_O = sb.Opart; g.cmb_ML = sb.MLpart; g.cmb_ns = p.cf.attn_nsplit; g.cmb_nhead = h->nhead;
+            g.cmb_O = ln.Opart; g.cmb_ML = ln.MLpart; g.cmb_ns = p.cf.attn_nsplit; g.cmb_nhead = h->nhead;
             g.cmb_Mtot = (unsigned)((size_t)p.sg.nseq * p.sg.S);
         }
-        g.ln_gamma = nrm.gamma; g.ln_beta = nrm.beta; g.ln_xh = sb.Xh; g.ln_xl = nullptr;
-        g.ln_xl8 = Xl8; g.ln_xchg = sb.ln_xchg; g.ln_eps = 1e-5f; g.ln_no_lo = no_lo_out;
-        return run_gemm_lnx_small(h, cls, g, rp.gemm);
+        g.ln_gamma = nrm.gamma; g.ln_beta = nrm.beta; g.ln_xh = ln.Xh; g.ln_xl = nullptr;
+        g.ln_xl8 = Xl8; g.ln_xchg = ln.ln_xchg; g.ln_eps = 1e-5f; g.ln_no_lo = no_lo_out;
+        return run_gemm_lnx_small(h, ln.stream, cls, g, rp.gemm);
     }
-    if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, cls, g, rp.gemm))) return rc;
-    return run_add_ln(h, sb.X, sb.Y, nrm.gamma, nrm.beta, M, d, sb.Xh, sb.Xl, p.mxv2, no_lo_out);
+    if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, ln.stream, cls, g, rp.gemm))) return rc;
+    return run_add_ln(h, ln.stream, ln.X, ln.Y, nrm.gamma, nrm.beta, M, d, ln.Xh, ln.Xl, p.mxv2, no_lo_out);
 }
 
 // Steps one coefficient table of a chunk holds: all of the call's - built once per chunk - or one, rebuilt at the head of every step.
@@ -281,19 +287,19 @@ int qkv0_table_steps(int steps, int Ec, int A, int d) {
 
 // The table of `nsteps` steps from step `step0` on for the chunk whose hyper rows are hyp_chunk: the coefficient rows, then in_proj
 // of layer 0 on them in exact fp32 with per-tile sums (a row stands for every token of its (episode, agent) pair).
-int qkv0_build_table(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* hyp_chunk, int step0, int nsteps) {
+int qkv0_build_table(jmid_ctx* h, const StepPlan& p, const Lane& ln, const float* hyp_chunk, int step0, int nsteps) {
     const int d = h->d;
-    ProfScope ps(h, KC_HYPER);
-    Qkv0CoefArgs ca{h->wt.concat1.W, h->wt.concat1.bias, hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, sb.coef,
+    ProfScope ps(h, KC_HYPER, ln.stream);
+    Qkv0CoefArgs ca{h->wt.concat1.W, h->wt.concat1.bias, hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, ln.coef,
                     nsteps, p.R, d, h->hl.total, h->hl.g1, h->hl.b1, h->range_flag};
     const long total = (long)nsteps * p.R * (d / 4);
-    hipLaunchKernelGGL(qkv0_coef_kernel, dim3((int)std::min<long>((total + 255) / 256, 256L * 16)), dim3(256), 0, h->stream, ca);
+    hipLaunchKernelGGL(qkv0_coef_kernel, dim3((int)std::min<long>((total + 255) / 256, 256L * 16)), dim3(256), 0, ln.stream, ca);
     HIPCHK(h, hipGetLastError());
     GemmArgs g{};
-    g.A = sb.coef; g.lda = d; g.W = h->wt.layers[0].in_proj.W; g.ldw = d; g.C = sb.uvc; g.ldc = 3 * d;
+    g.A = ln.coef; g.lda = d; g.W = h->wt.layers[0].in_proj.W; g.ldw = d; g.C = ln.uvc; g.ldc = 3 * d;
     g.M = nsteps * p.R * 3; g.N = 3 * d; g.K = d;
-    if (h->tune.qkv0 == 2) HIPCHK(h, (launch_gemm_f32<EPI_BIAS, false>(g, h->stream)));      // (A/B: what the per-tile sums buy)
-    else HIPCHK(h, (launch_gemm_f32<EPI_BIAS, true>(g, h->stream)));
+    if (h->tune.qkv0 == 2) HIPCHK(h, (launch_gemm_f32<EPI_BIAS, false>(g, ln.stream)));      // (A/B: what the per-tile sums buy)
+    else HIPCHK(h, (launch_gemm_f32<EPI_BIAS, true>(g, ln.stream)));
     return 0;
 }
 
@@ -306,30 +312,30 @@ int tail_table_steps(int steps, int Ec, int A, int d) {
     return bytes <= kTailTableMaxBytes ? steps : 1;
 }
 
-int tail_build_table(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* hyp_chunk, int step0, int nsteps) {
+int tail_build_table(jmid_ctx* h, const StepPlan& p, const Lane& ln, const float* hyp_chunk, int step0, int nsteps) {
     const WeightTable& wt = h->wt;
-    ProfScope ps(h, KC_HYPER);
+    ProfScope ps(h, KC_HYPER, ln.stream);
     TailTableArgs ta{wt.concat3.W, wt.concat3.bias, wt.concat4.W, wt.concat4.bias, wt.linear.W, wt.linear.bias,
-                     hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, sb.weff, sb.beff,
+                     hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, ln.weff, ln.beff,
                      nsteps, p.R, h->d, h->dmid, h->dlow, h->hl.total,
                      h->hl.g3, h->hl.b3, h->hl.g4, h->hl.b4, h->hl.go, h->hl.bo, h->range_flag};
-    HIPCHK(h, launch_tail_fold_table(ta, h->stream));
+    HIPCHK(h, launch_tail_fold_table(ta, ln.stream));
     return 0;
 }
 
 EmbedArgs embed_args(const jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* x_chunk, const float* hyp_chunk, const float* th) {
     unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(sb.Xl) : nullptr;
     return EmbedArgs{x_chunk, h->wt.concat1.W, h->wt.concat1.bias, h->pe, hyp_chunk, th,
-                     p.split ? nullptr : sb.X, p.M, h->d, h->hl.total, h->hl.g1, h->hl.b1, p.rm, p.split ? sb.Xh : nullptr,
-                     p.split && !p.mxv2 ? sb.Xl : nullptr, Xl8};
+                     p.mode.split ? nullptr : sb.X, p.M, h->d, h->hl.total, h->hl.g1, h->hl.b1, p.rm, p.mode.split ? sb.Xh : nullptr,
+                     p.mode.split && !p.mxv2 ? sb.Xl : nullptr, Xl8};
 }
 
-int run_embed(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, const float* x_chunk, const float* hyp_chunk, const float* thyp) {
-    ProfScope ps(h, KC_EMBED);
-    EmbedArgs ea = embed_args(h, p, sb, x_chunk, hyp_chunk, thyp);
+int run_embed(jmid_ctx* h, const StepPlan& p, const Lane& ln, const float* x_chunk, const float* hyp_chunk, const float* thyp) {
+    ProfScope ps(h, KC_EMBED, ln.stream);
+    EmbedArgs ea = embed_args(h, p, ln, x_chunk, hyp_chunk, thyp);
     const long total = (long)p.M * (h->d / 4);
     int blocks = (int)std::min<long>((total + 255) / 256, 256L * 16);
-    hipLaunchKernelGGL(embed_kernel, dim3(blocks), dim3(256), bystander_lds(h->tune.bystander_lds, embed_kernel), h->stream, ea);
+    hipLaunchKernelGGL(embed_kernel, dim3(blocks), dim3(256), bystander_lds(h->tune.bystander_lds, embed_kernel), ln.stream, ea);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -348,36 +354,36 @@ LoImages lo_images(const StepPlan& p, const StepBuffers& sb, int d) {
 
 // The Q / K / V^T operand planes of layer l of a JMID step in the split-fp16 modes: the in_proj GEMM on the residual stream's planes
 // (+ the transpose where its epilogue does not write V^T itself), or for layer 0 the expansion of the coefficient table (qkv0.hpp).
-int qkv_planes(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int l, int step_idx, const float* x_chunk, const float* hyp_chunk) {
+int qkv_planes(jmid_ctx* h, const StepPlan& p, const Lane& ln, int l, int step_idx, const float* x_chunk, const float* hyp_chunk) {
     const int M = p.M, d = h->d, hd = p.hd, S = p.sg.S;
-    const LoImages im = lo_images(p, sb, d);
+    const LoImages im = lo_images(p, ln, d);
     const float qscale = p.att_scale * 1.4426950408889634f;
     if (l == 0 && p.qkv0) {
-        if (p.qkv0_steps <= 1)
-            if (int rc = qkv0_build_table(h, p, sb, hyp_chunk, step_idx, 1)) return rc;
+        if (p.cf.qkv0_steps <= 1)
+            if (int rc = qkv0_build_table(h, p, ln, hyp_chunk, step_idx, 1)) return rc;
         Qkv0Args qa{};
         qa.x = x_chunk;
-        qa.uvc = sb.uvc + (p.qkv0_steps <= 1 ? 0 : (size_t)step_idx * p.R * 9 * d);
+        qa.uvc = ln.uvc + (p.cf.qkv0_steps <= 1 ? 0 : (size_t)step_idx * p.R * 9 * d);
         qa.ppe = h->ppe;
-        qa.Qh = sb.Qh; qa.Ql = sb.Ql; qa.Kh = sb.Kh; qa.Kl = sb.Kl; qa.Vth = sb.Vth; qa.Vtl = sb.Vtl;
+        qa.Qh = ln.Qh; qa.Ql = ln.Ql; qa.Kh = ln.Kh; qa.Kl = ln.Kl; qa.Vth = ln.Vth; qa.Vtl = ln.Vtl;
         qa.Q8l = im.q8l; qa.K8h = im.k8h; qa.K8l = im.k8l;
         qa.M = M; qa.d = d; qa.hd = hd; qa.S = S; qa.Spad = p.sg.Spad; qa.nseq = p.sg.nseq;
-        qa.qscale = qscale; qa.rmap = p.rm; qa.range_flag = h->range_flag; qa.x2 = h->x2;
+        qa.qscale = qscale; qa.rmap = p.rm; qa.range_flag = h->range_flag; qa.x2 = p.mode.x2;
         qkv0_plan(qa, p.T);
-        ProfScope ps(h, KC_GEMM_QKV);
-        HIPCHK(h, launch_qkv0_expand(qa, h->stream));
+        ProfScope ps(h, KC_GEMM_QKV, ln.stream);
+        HIPCHK(h, launch_qkv0_expand(qa, ln.stream));
         return 0;
     }
-    GemmHArgs g = gemm_h_args(h, p.rm, M, sb.Xh, sb.Xl, h->wt.layers[l].in_proj, 3 * d, d);
-    g.Chi = sb.Qh; g.Clo = sb.Ql; g.Khi = sb.Kh; g.Klo = sb.Kl;
-    g.Vthi = p.vt_direct ? sb.Vth : sb.Vh; g.Vtlo = p.vt_direct ? sb.Vtl : sb.Vl; g.vt_direct = p.vt_direct;
+    GemmHArgs g = gemm_h_args(p.mode, p.rm, M, ln.Xh, ln.Xl, h->wt.layers[l].in_proj, 3 * d, d);
+    g.Chi = ln.Qh; g.Clo = ln.Ql; g.Khi = ln.Kh; g.Klo = ln.Kl;
+    g.Vthi = p.vt_direct ? ln.Vth : ln.Vh; g.Vtlo = p.vt_direct ? ln.Vtl : ln.Vl; g.vt_direct = p.vt_direct;
     g.d = d; g.hd = hd; g.S = S; g.Spad = p.sg.Spad; g.qscale = qscale;
     g.K8h = im.k8h; g.K8l = im.k8l; g.Q8l = im.q8l;
-    if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, KC_GEMM_QKV, g, p.in_proj))) return rc;
+    if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, ln.stream, KC_GEMM_QKV, g, p.in_proj))) return rc;
     if (!p.vt_direct) {
-        ProfScope ps(h, KC_VTRANS);
-        hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, p.sg.nseq), dim3(256), 0, h->stream,
-                           sb.Vh, sb.Vl, sb.Vth, sb.Vtl, S, p.sg.Spad, d, hd);
+        ProfScope ps(h, KC_VTRANS, ln.stream);
+        hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, p.sg.nseq), dim3(256), 0, ln.stream,
+                           ln.Vh, ln.Vl, ln.Vth, ln.Vtl, S, p.sg.Spad, d, hd);
         HIPCHK(h, hipGetLastError());
     }
     return 0;
@@ -403,20 +409,20 @@ OutArgs sampler_args(const jmid_ctx* h, const StepPlan& p, const StepBuffers& sb
 // The tail of a step in the split-fp16 modes without its GEMMs (tail_fold.hpp): two dot products per token with the (row, step)'s
 // 2 x d map, then the sampler update and the next step's embedding - one launch, one wave per trajectory piece or per token
 // (StepPlan::out_tpw, as out_ddim*_kernel).  F16X3 reads X_hi + X_lo as its concat3 does, the other modes X_hi.
-int folded_tail(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+int folded_tail(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float* x_chunk, const float* hyp_chunk,
                 float* e_out, const float* z_chunk, int next_step) {
     const int M = p.M, d = h->d;
-    if (p.tail_steps <= 1)
-        if (int rc = tail_build_table(h, p, sb, hyp_chunk, step_idx, 1)) return rc;
-    const size_t at = p.tail_steps <= 1 ? 0 : (size_t)step_idx * p.R;
-    const TailFoldArgs fa{sb.Xh, sb.Xl, sb.weff + at * 2 * d, sb.beff + at * 2, d};
-    const OutArgs oa = sampler_args(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
+    if (p.cf.tail_steps <= 1)
+        if (int rc = tail_build_table(h, p, ln, hyp_chunk, step_idx, 1)) return rc;
+    const size_t at = p.cf.tail_steps <= 1 ? 0 : (size_t)step_idx * p.R;
+    const TailFoldArgs fa{ln.Xh, ln.Xl, ln.weff + at * 2 * d, ln.beff + at * 2, d};
+    const OutArgs oa = sampler_args(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
     const bool embed_next = next_step >= 0 && !e_out;
-    const EmbedArgs en = embed_next ? embed_args(h, p, sb, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
-    const bool lo = !h->x2;
-    ProfScope ps(h, KC_OUT_DDIM);
+    const EmbedArgs en = embed_next ? embed_args(h, p, ln, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+    const bool lo = !p.mode.x2;
+    ProfScope ps(h, KC_OUT_DDIM, ln.stream);
     const auto launch = [&](auto* kernel, int waves, auto... tpw) {
-        hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), h->stream, fa, oa, en, tpw...);
+        hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), ln.stream, fa, oa, en, tpw...);
     };
     const auto pick = [&](auto embed, auto with_lo) {
         constexpr bool EN = decltype(embed)::value, LO = decltype(with_lo)::value;
@@ -432,16 +438,16 @@ int folded_tail(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_
 }
 
 // output layer + sampler update (or e_theta out) + the next step's embedding on the Y4 rows the tail GEMMs left
-int output_stage(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+int output_stage(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float* x_chunk, const float* hyp_chunk,
                  float* e_out, const float* z_chunk, int next_step) {
     const int M = p.M;
-    ProfScope ps(h, KC_OUT_DDIM);
-    const OutArgs oa = sampler_args(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
+    ProfScope ps(h, KC_OUT_DDIM, ln.stream);
+    const OutArgs oa = sampler_args(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
     const bool embed_next = next_step >= 0 && !e_out;
-    const EmbedArgs en = embed_next ? embed_args(h, p, sb, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+    const EmbedArgs en = embed_next ? embed_args(h, p, ln, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
     // four waves per workgroup: one wave per piece of a trajectory (out_tpw tokens), or one per token
     const auto launch = [&](auto* kernel, int waves, auto... tpw) {
-        hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), h->stream, oa, en, tpw...);
+        hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), ln.stream, oa, en, tpw...);
     };
     if (p.out_tpw && embed_next) launch(out_ddim_traj_kernel<true>, M / p.out_tpw, p.out_tpw);
     else if (p.out_tpw) launch(out_ddim_traj_kernel<false>, M / p.out_tpw, p.out_tpw);
@@ -454,90 +460,90 @@ int output_stage(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step
 // The tail of a step in the split-fp16 modes on the residual stream's planes: folded (tail_fold.hpp), or
 // concat3 -> concat4 as two launches, the output layer + sampler update + next embedding as a third (one fused kernel for all
 // three was built in round 3 and measured slower at every batch size: docs/NOTEBOOK.md)
-int net_tail(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+int net_tail(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float* x_chunk, const float* hyp_chunk,
              float* e_out, const float* z_chunk, int next_step) {
-    if (p.tail_fold) return folded_tail(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
+    if (p.tail_fold) return folded_tail(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
     const int M = p.M, d = h->d;
     const WeightTable& wt = h->wt;
     const float* thyp = h->thyp + (size_t)step_idx * h->hl.total;
-    GemmHArgs g = gemm_h_args(h, p.rm, M, sb.Xh, sb.Xl, wt.concat3, h->dmid, d);
+    GemmHArgs g = gemm_h_args(p.mode, p.rm, M, ln.Xh, ln.Xl, wt.concat3, h->dmid, d);
     g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
-    g.Chi = sb.Y3h; g.Clo = sb.Y3l; g.ldc = h->dmid; g.goff = h->hl.g3; g.boff = h->hl.b3;
-    if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, KC_GEMM_TAIL, g, p.concat3))) return rc;
-    g = gemm_h_args(h, p.rm, M, sb.Y3h, sb.Y3l, wt.concat4, h->dlow, h->dmid);
+    g.Chi = ln.Y3h; g.Clo = ln.Y3l; g.ldc = h->dmid; g.goff = h->hl.g3; g.boff = h->hl.b3;
+    if (int rc = (run_gemm_h<EPI_CSL, OUT_SPLIT>(h, ln.stream, KC_GEMM_TAIL, g, p.concat3))) return rc;
+    g = gemm_h_args(p.mode, p.rm, M, ln.Y3h, ln.Y3l, wt.concat4, h->dlow, h->dmid);
     g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
-    g.C = sb.Y4; g.ldc = h->dlow; g.goff = h->hl.g4; g.boff = h->hl.b4;
-    if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, KC_GEMM_TAIL, g, p.concat4))) return rc;
-    return output_stage(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
+    g.C = ln.Y4; g.ldc = h->dlow; g.goff = h->hl.g4; g.boff = h->hl.b4;
+    if (int rc = (run_gemm_h<EPI_CSL, OUT_F32>(h, ln.stream, KC_GEMM_TAIL, g, p.concat4))) return rc;
+    return output_stage(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
 }
 
 // one evaluation of the net on a chunk of whole episodes + (optionally) the DDIM update, as its plan says
-int net_step(jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
+int net_step(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float* x_chunk, const float* hyp_chunk,
              float* e_out, const float* z_chunk = nullptr, bool embed_done = false, int next_step = -1) {
     // embed_done: the previous step's output kernel already embedded x for this step; next_step >= 0: this step's
     // output kernel does the same for step `next_step` (same chunk, same buffers)
-    const bool split = p.split;
+    const bool split = p.mode.split;
     const int M = p.M, d = h->d, ff = h->ff;
     const WeightTable& wt = h->wt;
     const float* thyp = h->thyp + (size_t)step_idx * h->hl.total;
     const RowMap& rm = p.rm;
     if (!embed_done)
-        if (int rc = run_embed(h, p, sb, x_chunk, hyp_chunk, thyp)) return rc;
+        if (int rc = run_embed(h, p, ln, x_chunk, hyp_chunk, thyp)) return rc;
     const SeqGeom& sg = p.sg;
     const int nseq = sg.nseq, S = sg.S, hd = p.hd;
     if (!split) {
         for (const LayerW& w : wt.layers) {
-            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_QKV, gemm_args(rm, M, sb.X, w.in_proj, sb.QKV, 3 * d, d))) return rc;
+            if (int rc = run_gemm<EPI_BIAS>(h, ln.stream, KC_GEMM_QKV, gemm_args(rm, M, ln.X, w.in_proj, ln.QKV, 3 * d, d))) return rc;
             {
-                ProfScope ps(h, KC_ATTN);
-                AttnArgs aa{sb.QKV, sb.ATT, S, d, h->nhead, p.att_scale, nullptr, nullptr};
-                HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, h->stream));
+                ProfScope ps(h, KC_ATTN, ln.stream);
+                AttnArgs aa{ln.QKV, ln.ATT, S, d, h->nhead, p.att_scale, nullptr, nullptr};
+                HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, ln.stream));
             }
             // attention output projection + residual + LN1
-            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_OUT, gemm_args(rm, M, sb.ATT, w.out_proj, sb.Y, d, d))) return rc;
-            if (int rc = run_add_ln(h, sb.X, sb.Y, w.norm1.gamma, w.norm1.beta, M, d)) return rc;
+            if (int rc = run_gemm<EPI_BIAS>(h, ln.stream, KC_GEMM_OUT, gemm_args(rm, M, ln.ATT, w.out_proj, ln.Y, d, d))) return rc;
+            if (int rc = run_add_ln(h, ln.stream, ln.X, ln.Y, w.norm1.gamma, w.norm1.beta, M, d)) return rc;
             // feed-forward
-            if (int rc = run_gemm<EPI_BIAS_RELU>(h, KC_GEMM_FF1, gemm_args(rm, M, sb.X, w.linear1, sb.H1, ff, d))) return rc;
-            if (int rc = run_gemm<EPI_BIAS>(h, KC_GEMM_FF2, gemm_args(rm, M, sb.H1, w.linear2, sb.Y, d, ff))) return rc;
-            if (int rc = run_add_ln(h, sb.X, sb.Y, w.norm2.gamma, w.norm2.beta, M, d)) return rc;
+            if (int rc = run_gemm<EPI_BIAS_RELU>(h, ln.stream, KC_GEMM_FF1, gemm_args(rm, M, ln.X, w.linear1, ln.H1, ff, d))) return rc;
+            if (int rc = run_gemm<EPI_BIAS>(h, ln.stream, KC_GEMM_FF2, gemm_args(rm, M, ln.H1, w.linear2, ln.Y, d, ff))) return rc;
+            if (int rc = run_add_ln(h, ln.stream, ln.X, ln.Y, w.norm2.gamma, w.norm2.beta, M, d)) return rc;
         }
         // tail: concat3, concat4 (ConcatSquash epilogues)
-        GemmArgs g = gemm_args(rm, M, sb.X, wt.concat3, sb.Y3, h->dmid, d);
+        GemmArgs g = gemm_args(rm, M, ln.X, wt.concat3, ln.Y3, h->dmid, d);
         g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.goff = h->hl.g3; g.boff = h->hl.b3;
-        if (int rc = run_gemm<EPI_CSL>(h, KC_GEMM_TAIL, g)) return rc;
-        g = gemm_args(rm, M, sb.Y3, wt.concat4, sb.Y4, h->dlow, h->dmid);
+        if (int rc = run_gemm<EPI_CSL>(h, ln.stream, KC_GEMM_TAIL, g)) return rc;
+        g = gemm_args(rm, M, ln.Y3, wt.concat4, ln.Y4, h->dlow, h->dmid);
         g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.goff = h->hl.g4; g.boff = h->hl.b4;
-        if (int rc = run_gemm<EPI_CSL>(h, KC_GEMM_TAIL, g)) return rc;
+        if (int rc = run_gemm<EPI_CSL>(h, ln.stream, KC_GEMM_TAIL, g)) return rc;
     } else {
         for (int l = 0; l < h->tf_layer; ++l) {
             const LayerW& w = wt.layers[l];
             GemmHArgs g{};
             if (p.joint) {
-                if (int rc = qkv_planes(h, p, sb, l, step_idx, x_chunk, hyp_chunk)) return rc;
-                const LoImages im = lo_images(p, sb, d);
-                ProfScope ps(h, KC_ATTN);
-                AttnHArgs aa{sb.Qh, sb.Ql, sb.Kh, sb.Kl, sb.Vth, sb.Vtl, sb.Ah, sb.Al, S, sg.Spad, d, h->nhead,
-                             p.att_scale, h->range_flag, p.cf.attn_nsplit, sb.Opart, sb.MLpart, h->x2, im.k8h, im.k8l, im.q8l};
+                if (int rc = qkv_planes(h, p, ln, l, step_idx, x_chunk, hyp_chunk)) return rc;
+                const LoImages im = lo_images(p, ln, d);
+                ProfScope ps(h, KC_ATTN, ln.stream);
+                AttnHArgs aa{ln.Qh, ln.Ql, ln.Kh, ln.Kl, ln.Vth, ln.Vtl, ln.Ah, ln.Al, S, sg.Spad, d, h->nhead,
+                             p.att_scale, h->range_flag, p.cf.attn_nsplit, ln.Opart, ln.MLpart, p.mode.x2, im.k8h, im.k8l, im.q8l};
                 aa.skip_combine = p.out_proj.merge;
-                HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, p.attn, h->stream));
+                HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, p.attn, ln.stream));
             } else {
-                g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, w.in_proj, 3 * d, d);
-                g.C = sb.QKV; g.ldc = 3 * d;
-                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, KC_GEMM_QKV, g, p.in_proj))) return rc;
-                ProfScope ps(h, KC_ATTN);
-                AttnArgs aa{sb.QKV, nullptr, S, d, h->nhead, p.att_scale, sb.Ah, sb.Al};
-                HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, h->stream));
+                g = gemm_h_args(p.mode, rm, M, ln.Xh, ln.Xl, w.in_proj, 3 * d, d);
+                g.C = ln.QKV; g.ldc = 3 * d;
+                if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, ln.stream, KC_GEMM_QKV, g, p.in_proj))) return rc;
+                ProfScope ps(h, KC_ATTN, ln.stream);
+                AttnArgs aa{ln.QKV, nullptr, S, d, h->nhead, p.att_scale, ln.Ah, ln.Al};
+                HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, ln.stream));
             }
-            if (int rc = residual_block(h, p, p.out_proj, sb, sb.Ah, sb.Al, d, w.out_proj, w.norm1, KC_GEMM_OUT, false)) return rc;
-            g = gemm_h_args(h, rm, M, sb.Xh, sb.Xl, w.linear1, ff, d);
-            g.Chi = sb.H1h; g.Clo = sb.H1l; g.ldc = ff;
-            if (int rc = (run_gemm_h<EPI_BIAS_RELU, OUT_SPLIT>(h, KC_GEMM_FF1, g, p.linear1))) return rc;
+            if (int rc = residual_block(h, p, p.out_proj, ln, ln.Ah, ln.Al, d, w.out_proj, w.norm1, KC_GEMM_OUT, false)) return rc;
+            g = gemm_h_args(p.mode, rm, M, ln.Xh, ln.Xl, w.linear1, ff, d);
+            g.Chi = ln.H1h; g.Clo = ln.H1l; g.ldc = ff;
+            if (int rc = (run_gemm_h<EPI_BIAS_RELU, OUT_SPLIT>(h, ln.stream, KC_GEMM_FF1, g, p.linear1))) return rc;
             // (the residual stream ends with the last layer: concat3 reads X_hi only)
-            if (int rc = residual_block(h, p, p.linear2, sb, sb.H1h, sb.H1l, ff, w.linear2, w.norm2, KC_GEMM_FF2, l + 1 == h->tf_layer)) return rc;
+            if (int rc = residual_block(h, p, p.linear2, ln, ln.H1h, ln.H1l, ff, w.linear2, w.norm2, KC_GEMM_FF2, l + 1 == h->tf_layer)) return rc;
         }
-        return net_tail(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
+        return net_tail(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
     }
-    return output_stage(h, p, sb, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
+    return output_stage(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
 }
 
 // Episodes per pass of the 50-step loop when nothing is forced: large enough to fill the chip several times over per
@@ -561,7 +567,7 @@ int auto_chunk(const jmid_ctx* h, int E, int tokens_per_episode) {
 // The chunks of a call: `c` episodes each (jmid_set_chunk_episodes, or auto_chunk).  A short ragged tail (less than a
 // quarter of a chunk, e.g. 256 = 5 x 51 + 1) would run all 50 steps at single-scene latency, so it is spread over the
 // full chunks instead (52 + 4 x 51) - only with the automatic size: a forced size is taken literally.
-std::vector<int> plan_chunks(const jmid_ctx* h, int E, int tokens_per_episode) {
+std::vector<int> plan_chunks(const jmid_ctx* h, const CallMode& m, int E, int tokens_per_episode) {
     int c = h->chunk_eps > 0 ? std::min(E, h->chunk_eps) : auto_chunk(h, E, tokens_per_episode);
     if (h->chunk_eps <= 0 && h->lanes >= 2 && E >= 2 && h->tune.graph != 1) {     // (a captured loop is a one-chunk call)
         // Two chunks in flight want an EVEN number of chunks of equal size.  A batch that fits one chunk is split in two halves: its
@@ -578,7 +584,7 @@ std::vector<int> plan_chunks(const jmid_ctx* h, int E, int tokens_per_episode) {
             // nine launches less per denoise step: two cfg2 scenes (2 400 tokens) 14.45 -> 13.90 ms per call, 12.63 with the split-KV factor chosen for that launch (run_network).  Three (3 600 tokens, 456
             // workgroups of that kernel) are better off as 2 + 1 side by side: 16.42 against 16.90 (profiles/r05s_lnx_two_per_cu.log)
             const long tokens = (long)E * tokens_per_episode;
-            const bool lnx_call = one_launch_shape(h, tokens) && residual_path(h, (int)tokens, h->d, CallFacts{}).path == RB_LNX_SMALL;
+            const bool lnx_call = one_launch_shape(h, m, tokens) && residual_path(h, m, (int)tokens, h->d, CallFacts{}).path == RB_LNX_SMALL;
             c = lnx_call ? E : (E + 1) / 2;
         } else {
             int n = (E + c - 1) / c;
@@ -604,13 +610,13 @@ std::vector<int> plan_chunks(const jmid_ctx* h, int E, int tokens_per_episode) {
 // for everything the caller enqueued before the call, and the caller's stream waits for the call's last kernel, so
 // neither a producer kernel of an input nor a consumer (or the allocator's reuse) of an output can race with it.
 int order_in(jmid_ctx* h, int mem) {
-    if (mem != JMID_MEM_DEVICE || h->chained) return 0;
+    if (mem != JMID_MEM_DEVICE) return 0;
     HIPCHK(h, hipEventRecord(h->ev_in, h->caller_stream));
     HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_in, 0));
     return 0;
 }
 int order_out(jmid_ctx* h, int mem) {
-    if (mem != JMID_MEM_DEVICE || h->chained) return 0;
+    if (mem != JMID_MEM_DEVICE) return 0;
     HIPCHK(h, hipEventRecord(h->ev_out, h->stream));
     HIPCHK(h, hipStreamWaitEvent(h->caller_stream, h->ev_out, 0));
     return 0;
@@ -658,38 +664,41 @@ int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_
     return 0;
 }
 
-int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, const float* ctx, const float* p0, float dt,
-                int precision, int single_step, float* vel_out, float* pos_out, float* e_out, int mem,
-                const float* z_in, const SeedArgs* seeded) {
-    if (int rc = check_ready(h)) return rc;
-    if (E <= 0 || A <= 0 || K <= 0 || T <= 0) return fail(h, JMID_EINVAL, "E, A, K, T must be positive");
-    if (T > kPeMaxLen) return fail(h, JMID_EINVAL, "T exceeds the positional-encoding table (max_len=24, diffusion.py:116-118)");
-    if (precision != JMID_PREC_F32 && precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX)
-        return fail(h, JMID_EINVAL, "precision must be JMID_PREC_F32, JMID_PREC_F16X3, JMID_PREC_F16X2 or JMID_PREC_F16MX (JMID_PREC_F16 is not built)");
-    h->mx = precision == JMID_PREC_F16MX;
-    h->x2 = precision == JMID_PREC_F16X2 || h->mx;
-    if (precision != JMID_PREC_F32 && !h->weights_in_half_range && ++h->erange_calls)
-        return fail(h, JMID_ERANGE, "a weight exceeds the fp16 range: use JMID_PREC_F32");
-    if ((!x_in && !seeded) || !ctx) return fail(h, JMID_EINVAL, "null input");
-    if (seeded && !seeded->ids) return fail(h, JMID_EINVAL, "null episode_ids");
-    if (seeded && !noise_fits((unsigned long long)K * A * T * 2)) return fail(h, JMID_EINVAL, "K * A * T exceeds the noise addressing");
-    if (pos_out && !p0) return fail(h, JMID_EINVAL, "pos_out requested without p0");
-    h->last_pos = nullptr;     // (the staging buffer is about to be reused)
-    if (single_step < 0 && h->ddpm && !z_in && !seeded) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
-    if (single_step < 0 && !h->ddpm && z_in) return fail(h, JMID_EINVAL, "jmid_denoise_ddpm needs jmid_set_ddpm_table");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = order_in(h, mem)) return rc;
-    const size_t R = (size_t)E * K * A, M = R * T, EA = (size_t)E * A;
-    const std::vector<int> chunk_sizes = plan_chunks(h, E, K * A * T);
-    std::vector<int> chunk_start(chunk_sizes.size(), 0);
-    for (size_t i = 1; i < chunk_sizes.size(); ++i) chunk_start[i] = chunk_start[i - 1] + chunk_sizes[i - 1];
-    const int Ec = *std::max_element(chunk_sizes.begin(), chunk_sizes.end());
-    const size_t Mc = (size_t)Ec * K * A * T;
+// Everything a denoise call decides, decided before it enqueues anything: host values only.  The phases of run_network read it;
+// net_step executes its step plans.
+struct CallPlan {
+    CallMode mode;
+    std::vector<int> chunk_sizes, chunk_start;      // episodes of each chunk (plan_chunks) and its first episode
+    size_t Mc;                                      // tokens of the largest chunk: what a lane's step workspace holds
+    SeqGeom sg;                                     // ... and its attention geometry
+    // Independent chunks run `nlanes` at a time on separate streams: the partially filled last round of one chunk's
+    // kernels and its bandwidth-bound kernels overlap with another chunk's MFMA kernels.  Each lane has its own step
+    // workspace; results do not depend on the number of lanes.
+    int nlanes;
+    Lane lanes[jmid_ctx::kMaxLanes];                // (their buffers: fill_workspace)
+    CallFacts facts;
+    // one plan per distinct chunk size of the call (the knobs and lnx_off cannot change while it runs): a handful at most
+    std::vector<StepPlan> plans;
+    std::vector<int> chunk_plan;                    // chunk -> its plan
+    size_t qkv0_rows, tail_rows;                    // rows of a lane's two tables (step_ws_floats)
+    bool z_fill;                                    // seeded DDPM: the z of ONE step per lane, filled on that lane's stream just before the step's update (no [n_steps, ...] buffer)
+};
+
+CallPlan plan_call(const jmid_ctx* h, const DenoiseCall& a, const CallMode& mode) {
+    const int E = a.E, A = a.A, K = a.K, T = a.T;
+    CallPlan cp{};
+    cp.mode = mode;
+    cp.chunk_sizes = plan_chunks(h, mode, E, K * A * T);
+    cp.chunk_start.assign(cp.chunk_sizes.size(), 0);
+    for (size_t i = 1; i < cp.chunk_sizes.size(); ++i) cp.chunk_start[i] = cp.chunk_start[i - 1] + cp.chunk_sizes[i - 1];
+    const int Ec = *std::max_element(cp.chunk_sizes.begin(), cp.chunk_sizes.end());
+    cp.Mc = (size_t)Ec * K * A * T;
+    cp.sg = seq_geom(h, Ec, A, K, T);
     // Split-KV factor of the attention launches: chosen ONCE per call from the automatic chunk size, never from the
     // chunk at hand - a ragged last chunk or a forced chunk size must not change the order in which a sequence's keys
     // are summed (results are bit-identical for every chunking of the same call).
     int ns_call = 1;
-    if (h->net_kind == JMID_NET_JMID && precision != JMID_PREC_F32 && h->d / h->nhead == 128) {
+    if (h->net_kind == JMID_NET_JMID && mode.split && h->d / h->nhead == 128) {
         const int S = K * A * T;
         // sized for ONE launch of the default plan (two chunks in flight: a batch that fits one chunk runs as two halves) - a
         // function of the call's shape only, whatever the chunk size or number of lanes actually set
@@ -697,107 +706,128 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         // (a batch of at most 2 560 tokens in F16MX is ONE launch by default - plan_chunks: two cfg2 scenes take 3 key ranges x 80 blocks,
         //  13.43 ms per call, where the 6 x 80 of the halves' choice take 14.14-14.37; shape and mode only, no knob: the bits of a call
         //  must not depend on one)
-        ns_call = attn_pick_nsplit(((S + 127) / 128) * h->nhead * (E >= 2 ? (one_launch_shape(h, (long)E * S) ? E : (c_auto + 1) / 2) : 1), S);
+        ns_call = attn_pick_nsplit(((S + 127) / 128) * h->nhead * (E >= 2 ? (one_launch_shape(h, mode, (long)E * S) ? E : (c_auto + 1) / 2) : 1), S);
         if (h->tune.attn_nsplit > 0) ns_call = std::min(h->tune.attn_nsplit, (S + 31) / 32);
     }
-    const int nchunks = (int)chunk_sizes.size();
-    const int lanes = single_step < 0 ? std::max(1, std::min(h->lanes, nchunks)) : 1;
-    // seeded DDPM: the z of ONE step per lane, filled on that lane's stream just before the step's update (no [n_steps, ...] buffer)
-    const bool z_fill = seeded && h->ddpm && single_step < 0;
-    // ---- workspace
-    size_t io_off;
-    {
-        Carver c(nullptr);
-        c.take(M * 2);                 // x_cur
-        c.take(EA * h->ctx_dim);       // ctx
-        c.take(EA * h->hl.total);      // hyp
-        c.take(EA * 2);                // p0
-        c.take(M * 2);                 // e / pos staging
-        if (z_in && mem == JMID_MEM_HOST) c.take(M * 2 * h->beta.size());   // DDPM noise
-        if (z_fill) c.take((size_t)lanes * Mc * 2);
-        io_off = c.off;
-    }
-    const SeqGeom sg_full = seq_geom(h, Ec, A, K, T);
-    // Independent chunks run `lanes` at a time on separate streams: the partially filled last round of one chunk's
-    // kernels and its bandwidth-bound kernels overlap with another chunk's MFMA kernels.  Each lane has its own step
-    // workspace; results do not depend on the number of lanes.
-    // one plan per distinct chunk size of the call (the knobs and lnx_off cannot change while it runs): net_step only executes it.
+    cp.nlanes = a.single_step < 0 ? std::max(1, std::min(h->lanes, (int)cp.chunk_sizes.size())) : 1;
+    for (int l = 0; l < cp.nlanes; ++l) cp.lanes[l].stream = l ? h->lane_stream[l - 1] : h->stream;
+    cp.z_fill = a.seeded && h->ddpm && a.single_step < 0;
     // The small-launch GEMMs (gemm_small.hpp: one workgroup per CU, most of its LDS) only while one chunk is in flight
-    CallFacts facts;
-    facts.small_now = lanes == 1 || h->tune.small_lanes == 1 ? 1 : h->tune.small_lanes == 2 ? 2 : 0;
-    facts.one_chunk = nchunks == 1 && h->tune.graph != 1;      // (a captured loop would replay the launch tags of OUT_LNX)
-    facts.attn_nsplit = ns_call;
+    cp.facts.small_now = cp.nlanes == 1 || h->tune.small_lanes == 1 ? 1 : h->tune.small_lanes == 2 ? 2 : 0;
+    cp.facts.one_chunk = cp.chunk_sizes.size() == 1 && h->tune.graph != 1;      // (a captured loop would replay the launch tags of OUT_LNX)
+    cp.facts.attn_nsplit = ns_call;
     const int n_steps = (int)h->beta.size();
-    facts.qkv0_steps = single_step < 0 ? qkv0_table_steps(n_steps, Ec, A, h->d) : 1;
-    facts.tail_steps = single_step < 0 && h->tune.tail_fold != 2 ? tail_table_steps(n_steps, Ec, A, h->d) : 1;
-    std::vector<StepPlan> plans;            // a handful at most
-    std::vector<int> chunk_plan;            // chunk -> its plan
-    for (int ec : chunk_sizes) {
+    cp.facts.qkv0_steps = a.single_step < 0 ? qkv0_table_steps(n_steps, Ec, A, h->d) : 1;
+    cp.facts.tail_steps = a.single_step < 0 && h->tune.tail_fold != 2 ? tail_table_steps(n_steps, Ec, A, h->d) : 1;
+    for (int ec : cp.chunk_sizes) {
         size_t j = 0;
-        while (j < plans.size() && plans[j].Ec != ec) ++j;
-        if (j == plans.size()) plans.push_back(plan_step(h, ec, A, K, T, precision, facts));
-        chunk_plan.push_back((int)j);
+        while (j < cp.plans.size() && cp.plans[j].Ec != ec) ++j;
+        if (j == cp.plans.size()) cp.plans.push_back(plan_step(h, ec, A, K, T, mode, cp.facts));
+        cp.chunk_plan.push_back((int)j);
     }
-    const size_t qkv0_rows = plans[0].qkv0 ? (size_t)facts.qkv0_steps * Ec * A * 3 : 0;
-    const size_t tail_rows = plans[0].tail_fold ? (size_t)facts.tail_steps * Ec * A : 0;
-    const size_t lane_floats = step_ws_floats(h, Mc, precision, sg_full, ns_call, nullptr, nullptr, qkv0_rows, tail_rows);
-    const size_t need = io_off + lanes * lane_floats;
-    if (int rc = ensure_arena(h, need)) return rc;
-    Carver c(h->arena);
-    float* x_cur = c.take(M * 2);
-    float* ctx_d = c.take(EA * h->ctx_dim);
-    float* hyp = c.take(EA * h->hl.total);
-    float* p0_d = c.take(EA * 2);
-    float* stage = c.take(M * 2);
-    const float* z_use = z_in;
-    if (z_in && mem == JMID_MEM_HOST) {
-        float* zd = c.take(M * 2 * h->beta.size());
-        HIPCHK(h, hipMemcpyAsync(zd, z_in, M * 2 * h->beta.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        z_use = zd;
-    }
-    float* z_lane = z_fill ? c.take((size_t)lanes * Mc * 2) : nullptr;
-    StepBuffers sbs[jmid_ctx::kMaxLanes];
-    for (int l = 0; l < lanes; ++l) step_ws_floats(h, Mc, precision, sg_full, ns_call, &sbs[l], h->arena + io_off + l * lane_floats, qkv0_rows, tail_rows);
-    const StepBuffers& sb = sbs[0];
-    if (precision != JMID_PREC_F32) {
-        HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
-        for (int l = 0; l < lanes; ++l) HIPCHK(h, hipMemsetAsync(sbs[l].ln_xchg, 0, kLnxWords * sizeof(unsigned), h->stream));
-        for (int l = 0; l < lanes; ++l)
-            if (sbs[l].Vth && sg_full.Spad != sg_full.S) {  // padding keys of V^T must be finite (they meet P = 0)
-                HIPCHK(h, hipMemsetAsync(sbs[l].Vth, 0, sbs[l].vt_elems * sizeof(half_t), h->stream));
-                HIPCHK(h, hipMemsetAsync(sbs[l].Vtl, 0, sbs[l].vt_elems * sizeof(half_t), h->stream));
-            }
-    }
+    cp.qkv0_rows = cp.plans[0].qkv0 ? (size_t)cp.facts.qkv0_steps * Ec * A * 3 : 0;
+    cp.tail_rows = cp.plans[0].tail_fold ? (size_t)cp.facts.tail_steps * Ec * A : 0;
+    return cp;
+}
 
-    const hipMemcpyKind kin = mem == JMID_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    const hipMemcpyKind kout = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (seeded) {
-        if (int rc = upload_noise_ids(h, seeded->ids, E)) return rc;
-        if (int rc = fill_noise(h, seeded->seed, h->noise_ids, E, (size_t)K * A * T * 2, 0, x_cur, nullptr, h->stream)) return rc;
+// The I/O block of a call's workspace, in front of the lanes' step workspaces.  base null: its size only (as step_ws_floats).
+struct CallIo {
+    float *x_cur, *ctx, *hyp, *p0, *stage, *z_up, *z_lane;      // stage: e / pos; z_up: the caller's DDPM noise; z_lane: z_fill
+};
+size_t call_io(const jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, char* base, CallIo* out) {
+    const size_t M = (size_t)a.E * a.K * a.A * a.T, EA = (size_t)a.E * a.A;
+    Carver c(base);
+    CallIo io{};
+    io.x_cur = c.take(M * 2);
+    io.ctx = c.take(EA * h->ctx_dim);
+    io.hyp = c.take(EA * h->hl.total);
+    io.p0 = c.take(EA * 2);
+    io.stage = c.take(M * 2);
+    if (a.z && a.mem == JMID_MEM_HOST) io.z_up = c.take(M * 2 * h->beta.size());
+    if (cp.z_fill) io.z_lane = c.take((size_t)cp.nlanes * cp.Mc * 2);
+    if (out) *out = io;
+    return c.off;
+}
+
+int check_call(jmid_ctx* h, const DenoiseCall& a, CallMode* mode) {
+    if (int rc = check_ready(h)) return rc;
+    if (a.E <= 0 || a.A <= 0 || a.K <= 0 || a.T <= 0) return fail(h, JMID_EINVAL, "E, A, K, T must be positive");
+    if (a.T > kPeMaxLen) return fail(h, JMID_EINVAL, "T exceeds the positional-encoding table (max_len=24, diffusion.py:116-118)");
+    if (!call_mode(a.precision, mode))
+        return fail(h, JMID_EINVAL, "precision must be JMID_PREC_F32, JMID_PREC_F16X3, JMID_PREC_F16X2 or JMID_PREC_F16MX (JMID_PREC_F16 is not built)");
+    if (mode->split && !h->weights_in_half_range && ++h->erange_calls)
+        return fail(h, JMID_ERANGE, "a weight exceeds the fp16 range: use JMID_PREC_F32");
+    if ((!a.x_in && !a.seeded) || !a.ctx) return fail(h, JMID_EINVAL, "null input");
+    if (a.seeded && !a.seeded->ids) return fail(h, JMID_EINVAL, "null episode_ids");
+    if (a.seeded && !noise_fits((unsigned long long)a.K * a.A * a.T * 2)) return fail(h, JMID_EINVAL, "K * A * T exceeds the noise addressing");
+    if (a.pos_out && !a.p0) return fail(h, JMID_EINVAL, "pos_out requested without p0");
+    h->last_pos = nullptr;     // (the staging buffer is about to be reused)
+    if (a.single_step < 0 && h->ddpm && !a.z && !a.seeded) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
+    if (a.single_step < 0 && !h->ddpm && a.z) return fail(h, JMID_EINVAL, "jmid_denoise_ddpm needs jmid_set_ddpm_table");
+    return 0;
+}
+
+// Lay the workspace out (I/O block, then one step workspace per lane) and fill it on h->stream: uploads, memsets, the hyper nets'
+// ctx part; the extra lanes fork behind all of it.  From here on a.z, a.ctx and a.p0 are device pointers: the caller's, or their uploads.
+int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
+    const size_t M = (size_t)a.E * a.K * a.A * a.T, EA = (size_t)a.E * a.A;
+    const size_t io_off = call_io(h, a, cp, nullptr, nullptr);
+    const size_t lane_floats = step_ws_floats(h, cp.Mc, cp.mode, cp.sg, cp.facts.attn_nsplit, nullptr, nullptr, cp.qkv0_rows, cp.tail_rows);
+    if (int rc = ensure_arena(h, io_off + cp.nlanes * lane_floats)) return rc;
+    call_io(h, a, cp, h->arena, &io);
+    for (int l = 0; l < cp.nlanes; ++l) {
+        step_ws_floats(h, cp.Mc, cp.mode, cp.sg, cp.facts.attn_nsplit, &cp.lanes[l], h->arena + io_off + l * lane_floats, cp.qkv0_rows, cp.tail_rows);
+        cp.lanes[l].z = cp.z_fill ? io.z_lane + (size_t)l * cp.Mc * 2 : nullptr;
+    }
+    if (io.z_up) {
+        HIPCHK(h, hipMemcpyAsync(io.z_up, a.z, M * 2 * h->beta.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        a.z = io.z_up;
+    }
+    if (cp.mode.split) {
+        HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
+        for (int l = 0; l < cp.nlanes; ++l) HIPCHK(h, hipMemsetAsync(cp.lanes[l].ln_xchg, 0, kLnxWords * sizeof(unsigned), h->stream));
+        for (int l = 0; l < cp.nlanes; ++l) {
+            const StepBuffers& sb = cp.lanes[l];
+            if (sb.Vth && cp.sg.Spad != cp.sg.S) {  // padding keys of V^T must be finite (they meet P = 0)
+                HIPCHK(h, hipMemsetAsync(sb.Vth, 0, sb.vt_elems * sizeof(half_t), h->stream));
+                HIPCHK(h, hipMemsetAsync(sb.Vtl, 0, sb.vt_elems * sizeof(half_t), h->stream));
+            }
+        }
+    }
+    const hipMemcpyKind kin = a.mem == JMID_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    if (a.seeded) {
+        if (int rc = upload_noise_ids(h, a.seeded->ids, a.E)) return rc;
+        if (int rc = fill_noise(h, a.seeded->seed, h->noise_ids, a.E, (size_t)a.K * a.A * a.T * 2, 0, io.x_cur, nullptr, h->stream)) return rc;
     } else {
-        HIPCHK(h, hipMemcpyAsync(x_cur, x_in, M * 2 * sizeof(float), kin, h->stream));
+        HIPCHK(h, hipMemcpyAsync(io.x_cur, a.x_in, M * 2 * sizeof(float), kin, h->stream));
     }
-    const float* ctx_use = ctx;
-    if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(ctx_d, ctx, EA * h->ctx_dim * sizeof(float), kin, h->stream));
-        ctx_use = ctx_d;
+    if (a.mem == JMID_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(io.ctx, a.ctx, EA * h->ctx_dim * sizeof(float), kin, h->stream));
+        a.ctx = io.ctx;
     }
-    const float* p0_use = p0;
-    if (p0 && mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(p0_d, p0, EA * 2 * sizeof(float), kin, h->stream));
-        p0_use = p0_d;
+    if (a.p0 && a.mem == JMID_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(io.p0, a.p0, EA * 2 * sizeof(float), kin, h->stream));
+        a.p0 = io.p0;
     }
     // ---- ctx part of the four hyper nets, once per call (ctx is constant over the denoise steps)
-    {
-        GemmArgs g{};
-        g.A = ctx_use; g.lda = h->ctx_dim; g.W = h->Whyp; g.ldw = h->ctx_dim; g.bias = h->bhyp; g.C = hyp;
-        g.ldc = h->hl.total; g.M = (int)EA; g.N = h->hl.total; g.K = h->ctx_dim;
-        if (int rc = run_gemm<EPI_BIAS>(h, KC_HYPER, g)) return rc;
-    }
-    if (lanes > 1) {   // everything enqueued so far (inputs, hyper nets, memsets) precedes the extra lanes as well
+    GemmArgs g{};
+    g.A = a.ctx; g.lda = h->ctx_dim; g.W = h->Whyp; g.ldw = h->ctx_dim; g.bias = h->bhyp; g.C = io.hyp;
+    g.ldc = h->hl.total; g.M = (int)EA; g.N = h->hl.total; g.K = h->ctx_dim;
+    if (int rc = run_gemm<EPI_BIAS>(h, h->stream, KC_HYPER, g)) return rc;
+    if (cp.nlanes > 1) {   // everything enqueued so far (inputs, hyper nets, memsets) precedes the extra lanes as well
         HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-        for (int l = 1; l < lanes; ++l) HIPCHK(h, hipStreamWaitEvent(h->lane_stream[l - 1], h->ev_fork, 0));
+        for (int l = 1; l < cp.nlanes; ++l) HIPCHK(h, hipStreamWaitEvent(cp.lanes[l].stream, h->ev_fork, 0));
     }
+    return 0;
+}
+
+// The step loop: every chunk through all steps, `nlanes` chunks at a time, each on its lane's stream - or, for jmid_net_eval, through
+// that one step alone, e_theta to the chunk's staging rows.
+int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallIo& io) {
+    const int E = a.E, A = a.A, K = a.K, T = a.T, lanes = cp.nlanes, nchunks = (int)cp.chunk_sizes.size(), n_steps = (int)h->beta.size();
+    const size_t M = (size_t)E * K * A * T, tok = (size_t)K * A * T;       // tok: tokens per episode
+    const bool one = a.single_step >= 0;
+    const int i0 = one ? a.single_step : 0, i1 = one ? i0 + 1 : n_steps;
     // Opt-in (jmid_set_tuning "graph" = 1) for one-chunk calls: the whole denoise loop - n_steps x ~28 dependent launches on
     // workspace buffers only - is captured into a hipGraph the second time a shape is seen and replayed afterwards: one
     // graph launch instead of ~1400 kernel launches per call, bit-identical.  Measured on MI355X / ROCm 7.2
@@ -807,10 +837,10 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     // Inputs / outputs (copies, hyper-net GEMM, integrator) stay outside the graph.
     jmid_ctx::LoopGraph* lg = nullptr;
     bool capturing = false;
-    if (single_step < 0 && lanes == 1 && nchunks == 1 && !h->prof_mask && !z_use && !h->ddpm && h->tune.graph == 1 &&
+    if (a.single_step < 0 && lanes == 1 && nchunks == 1 && !h->prof_mask && !a.z && !h->ddpm && h->tune.graph == 1 &&
         h->tune.bystander_lds == 0) {
         const std::string key = std::to_string(E) + "," + std::to_string(A) + "," + std::to_string(K) + "," + std::to_string(T) +
-                                "," + std::to_string(precision);
+                                "," + std::to_string(a.precision);
         lg = &h->graphs[key];
         if (lg->exec && lg->arena != h->arena) {        // never true today (ensure_arena drops the graphs); cheap to keep
             hipGraphExecDestroy(lg->exec);
@@ -825,36 +855,26 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
         }
     }
     for (int c0 = 0; c0 < nchunks && !(lg && lg->exec); c0 += lanes) {
-        if (single_step >= 0) {
-            const int e0 = chunk_start[c0];
-            float* eo = stage + (size_t)e0 * K * A * T * 2;
-            if (int rc = net_step(h, plans[chunk_plan[c0]], sb, single_step, x_cur + (size_t)e0 * K * A * T * 2,
-                                  hyp + (size_t)e0 * A * h->hl.total, eo))
-                return rc;
-            continue;
-        }
         // the steps of the chunks of this round are enqueued alternately so that all queues stay fed
-        for (int i = 0; i < n_steps; ++i) {
+        for (int i = i0; i < i1; ++i) {
             for (int l = 0; l < lanes; ++l) {
                 if (c0 + l >= nchunks) break;
-                const int el = chunk_start[c0 + l];
-                float* xc = x_cur + (size_t)el * K * A * T * 2;
-                const float* hc = hyp + (size_t)el * A * h->hl.total;
-                const float* zc = z_use ? z_use + ((size_t)i * M + (size_t)el * K * A * T) * 2 : nullptr;
-                if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);   // net_step launches on h->stream
+                const Lane& ln = cp.lanes[l];
+                const size_t el = cp.chunk_start[c0 + l];
+                float* xc = io.x_cur + el * tok * 2;
+                const float* hc = io.hyp + el * A * h->hl.total;
+                const float* zc = a.z ? a.z + ((size_t)i * M + el * tok) * 2 : nullptr;
                 int rc = 0;
-                if (z_fill && h->p_noise[i]) {      // this step's draw for the chunk's episodes, on the chunk's own stream
-                    float* zl = z_lane + (size_t)l * Mc * 2;
-                    rc = fill_noise(h, seeded->seed, h->noise_ids + el, chunk_sizes[c0 + l], (size_t)K * A * T * 2, i + 1, zl, nullptr, h->stream);
-                    zc = zl;
+                if (cp.z_fill && h->p_noise[i]) {      // this step's draw for the chunk's episodes, on the chunk's own stream
+                    rc = fill_noise(h, a.seeded->seed, h->noise_ids + el, cp.chunk_sizes[c0 + l], tok * 2, i + 1, ln.z, nullptr, ln.stream);
+                    zc = ln.z;
                 }
                 // layer 0's coefficient table of this chunk for all steps, ahead of its first step, on the chunk's own stream
-                const StepPlan& pl = plans[chunk_plan[c0 + l]];
-                if (!rc && i == 0 && pl.qkv0 && pl.qkv0_steps > 1) rc = qkv0_build_table(h, pl, sbs[l], hc, 0, n_steps);
-                if (!rc && i == 0 && pl.tail_fold && pl.tail_steps > 1) rc = tail_build_table(h, pl, sbs[l], hc, 0, n_steps);
-                if (!rc) rc = net_step(h, plans[chunk_plan[c0 + l]], sbs[l], i, xc, hc, nullptr, zc, h->tune.fuse_embed && i > 0,
-                                        h->tune.fuse_embed && i + 1 < n_steps ? i + 1 : -1);
-                if (l > 0) std::swap(h->stream, h->lane_stream[l - 1]);
+                const StepPlan& pl = cp.plans[cp.chunk_plan[c0 + l]];
+                if (!rc && i == 0 && pl.qkv0 && pl.cf.qkv0_steps > 1) rc = qkv0_build_table(h, pl, ln, hc, 0, n_steps);
+                if (!rc && i == 0 && pl.tail_fold && pl.cf.tail_steps > 1) rc = tail_build_table(h, pl, ln, hc, 0, n_steps);
+                if (!rc) rc = net_step(h, pl, ln, i, xc, hc, one ? io.stage + el * tok * 2 : nullptr, zc, h->tune.fuse_embed && i > i0,
+                                        h->tune.fuse_embed && i + 1 < i1 ? i + 1 : -1);
                 if (rc) {
                     if (capturing) {
                         hipGraph_t dead = nullptr;
@@ -884,41 +904,55 @@ int run_network(jmid_ctx* h, int E, int A, int K, int T, const float* x_in, cons
     } else if (lg && !lg->exec) {
         lg->warm = true;
     }
-    for (int l = 1; l < lanes; ++l) {
-        HIPCHK(h, hipEventRecord(h->ev_join[l - 1], h->lane_stream[l - 1]));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[l - 1], 0));
-    }
-    if (single_step >= 0) {
-        HIPCHK(h, hipMemcpyAsync(e_out, stage, M * 2 * sizeof(float), kout, h->stream));
-    } else {
-        if (vel_out) HIPCHK(h, hipMemcpyAsync(vel_out, x_cur, M * 2 * sizeof(float), kout, h->stream));
-        if (p0_use) {      // integrated whenever p0 is given: the positions stay in the workspace for jmid_topk(pos = NULL)
-            {
-                ProfScope ps(h, KC_INTEGRATE);
-                const int n = (int)R * 2;
-                hipLaunchKernelGGL(integrate_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, x_cur, p0_use,
-                                   stage, (int)R, T, A, K * A, dt);
-                HIPCHK(h, hipGetLastError());
-            }
-            h->last_pos = stage;
-            h->last_pos_dims[0] = E; h->last_pos_dims[1] = A; h->last_pos_dims[2] = K; h->last_pos_dims[3] = T;
-            if (pos_out) HIPCHK(h, hipMemcpyAsync(pos_out, stage, M * 2 * sizeof(float), kout, h->stream));
-        }
-    }
-    if (int rc = order_out(h, mem)) return rc;
-    if (h->chained) return 0;          // (jmid_predict reads the range flag with its one download)
-    if (precision != JMID_PREC_F32) {
-        // an activation outside the fp16 range poisons the split operands: report it instead of returning garbage
-        int flag = 0;
-        HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (flag) return flagged_call(h, flag);
-    } else if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
     return 0;
 }
 
+// Join the lanes, integrate, hand the outputs over, and - unless the call is a stage of jmid_predict, which reads the range flag with
+// its one download - bring the flag back.
+int finish_call(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallIo& io) {
+    const size_t R = (size_t)a.E * a.K * a.A, M = R * a.T;
+    const hipMemcpyKind kout = a.mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    for (int l = 1; l < cp.nlanes; ++l) {
+        HIPCHK(h, hipEventRecord(h->ev_join[l - 1], cp.lanes[l].stream));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[l - 1], 0));
+    }
+    if (a.single_step >= 0) {
+        HIPCHK(h, hipMemcpyAsync(a.e_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
+    } else {
+        if (a.vel_out) HIPCHK(h, hipMemcpyAsync(a.vel_out, io.x_cur, M * 2 * sizeof(float), kout, h->stream));
+        if (a.p0) {      // integrated whenever p0 is given: the positions stay in the workspace for jmid_topk(pos = NULL)
+            {
+                ProfScope ps(h, KC_INTEGRATE, h->stream);
+                const int n = (int)R * 2;
+                hipLaunchKernelGGL(integrate_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, io.x_cur, a.p0,
+                                   io.stage, (int)R, a.T, a.A, a.K * a.A, a.dt);
+                HIPCHK(h, hipGetLastError());
+            }
+            h->last_pos = io.stage;
+            h->last_pos_dims[0] = a.E; h->last_pos_dims[1] = a.A; h->last_pos_dims[2] = a.K; h->last_pos_dims[3] = a.T;
+            if (a.pos_out) HIPCHK(h, hipMemcpyAsync(a.pos_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
+        }
+    }
+    if (a.chained) return 0;       // (no caller-stream ordering either)
+    if (int rc = order_out(h, a.mem)) return rc;
+    int flag = 0;      // an activation outside the fp16 range poisons the split operands: report it instead of returning garbage
+    if (cp.mode.split) HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (cp.mode.split || a.mem == JMID_MEM_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return flag ? flagged_call(h, flag) : 0;
+}
+
+int run_network(jmid_ctx* h, DenoiseCall a) {
+    CallMode mode;
+    if (int rc = check_call(h, a, &mode)) return rc;
+    CallPlan cp = plan_call(h, a, mode);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!a.chained)
+        if (int rc = order_in(h, a.mem)) return rc;
+    CallIo io;
+    if (int rc = fill_workspace(h, a, cp, io)) return rc;
+    if (int rc = run_steps(h, a, cp, io)) return rc;
+    return finish_call(h, a, cp, io);
+}
 
 // A call whose range flag came back set.  Bit 1 (gemm_small.hpp, OUT_LNX): a workgroup gave up waiting for a partner - nothing to do with
 // the arithmetic: the handle drops that kernel for good and the caller repeats the call in the SAME precision (JMID_ETIMEOUT).  Otherwise
@@ -936,116 +970,75 @@ int flagged_call(jmid_ctx* h, int flag) {
 }
 
 #ifdef JMID_DIAGNOSTICS
-// jmid_dbg_qkv0: the embedding of x at step `step` and layer 0's Q / K / V^T planes as a step of a one-chunk call makes them (the
-// "qkv0" knob decides how), read back as fp32 [M, 3 d].  Host buffers.
-int dbg_qkv0(jmid_ctx* h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision, float* qkv, float* thyp_row) {
+// jmid_dbg_qkv0 and jmid_dbg_tail: one piece of step `step` as a step of a one-chunk call on an idle handle runs it, on host buffers.
+// tail = false: the embedding of x [M, 2] and layer 0's Q / K / V^T planes (the "qkv0" knob decides how), read back as fp32 [M, 3 d].
+// tail = true: the tail alone on X [M, d] (fp32, split here into the planes the mode's concat3 reads: X_hi, and X_lo in F16X3) - folded,
+// or the two GEMMs + the output kernel with "tail_fold" = 1 -> e [M, 2].
+int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in, const float* hyp, int hyp_width, int step, int precision,
+             float* out, float* thyp_row) {
+    const std::string who = tail ? "jmid_dbg_tail" : "jmid_dbg_qkv0";
+    CallMode mode;
     if (int rc = check_ready(h)) return rc;
-    if (!x || !hyp || !qkv || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen) return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: bad arguments");
-    if (hyp_width != h->hl.total) return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: hyp rows must be " + std::to_string(h->hl.total) + " wide");
-    if (h->net_kind != JMID_NET_JMID || (precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX))
-        return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: JMID in a split-fp16 mode only");
-    if (step < 0 || step >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "jmid_dbg_qkv0: step outside the step table");
-    h->mx = precision == JMID_PREC_F16MX;
-    h->x2 = precision == JMID_PREC_F16X2 || h->mx;
+    if (!in || !hyp || !out || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen) return fail(h, JMID_EINVAL, who + ": bad arguments");
+    if (hyp_width != h->hl.total) return fail(h, JMID_EINVAL, who + ": hyp rows must be " + std::to_string(h->hl.total) + " wide");
+    if (!call_mode(precision, &mode) || !mode.split || (!tail && h->net_kind != JMID_NET_JMID))
+        return fail(h, JMID_EINVAL, who + (tail ? ": a split-fp16 mode only" : ": JMID in a split-fp16 mode only"));
+    if (step < 0 || step >= (int)h->beta.size()) return fail(h, JMID_EINVAL, who + ": step outside the step table");
     HIPCHK(h, hipSetDevice(h->device));
     h->last_pos = nullptr;
     const size_t M = (size_t)E * K * A * T, EA = (size_t)E * A;
-    const int d = h->d;
-    CallFacts facts;          // (an idle handle: nothing else in flight, one launch, the table of one step)
-    const StepPlan p = plan_step(h, E, A, K, T, precision, facts);
-    const size_t rows = p.qkv0 ? EA * 3 : 0;
-    size_t io_off;
-    {
-        Carver c(nullptr);
-        c.take(M * 2);
-        c.take(EA * h->hl.total);
-        c.take(M * 3 * d);
-        io_off = c.off;
-    }
-    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, precision, p.sg, 1, nullptr, nullptr, rows, 0))) return rc;
-    Carver c(h->arena);
-    float* x_d = c.take(M * 2);
-    float* hyp_d = c.take(EA * h->hl.total);
-    float* out_d = c.take(M * 3 * d);
-    StepBuffers sb;
-    step_ws_floats(h, M, precision, p.sg, 1, &sb, h->arena + io_off, rows, 0);
+    const int d = h->d, in_w = tail ? d : 2, out_w = tail ? 2 : 3 * d;
+    const StepPlan p = plan_step(h, E, A, K, T, mode, CallFacts{});      // (an idle handle: nothing else in flight, one launch, the table of one step)
+    const size_t qkv0_rows = !tail && p.qkv0 ? EA * 3 : 0, tail_rows = tail && p.tail_fold ? EA : 0;
+    float *in_d, *hyp_d, *out_d;
+    const auto io = [&](char* base) {      // base null: the size only
+        Carver c(base);
+        in_d = c.take(M * in_w);
+        hyp_d = c.take(EA * h->hl.total);
+        out_d = c.take(M * out_w);
+        return c.off;
+    };
+    const size_t io_off = io(nullptr);
+    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, mode, p.sg, 1, nullptr, nullptr, qkv0_rows, tail_rows))) return rc;
+    io(h->arena);
+    Lane ln{};
+    ln.stream = h->stream;
+    step_ws_floats(h, M, mode, p.sg, 1, &ln, h->arena + io_off, qkv0_rows, tail_rows);
     HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemsetAsync(sb.Vth, 0, sb.vt_elems * sizeof(half_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(sb.Vtl, 0, sb.vt_elems * sizeof(half_t), h->stream));
-    HIPCHK(h, hipMemcpyAsync(x_d, x, M * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (!tail) {
+        HIPCHK(h, hipMemsetAsync(ln.Vth, 0, ln.vt_elems * sizeof(half_t), h->stream));
+        HIPCHK(h, hipMemsetAsync(ln.Vtl, 0, ln.vt_elems * sizeof(half_t), h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(in_d, in, M * in_w * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(hyp_d, hyp, EA * h->hl.total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (int rc = run_embed(h, p, sb, x_d, hyp_d, h->thyp + (size_t)step * h->hl.total)) return rc;
-    if (int rc = qkv_planes(h, p, sb, 0, step, x_d, hyp_d)) return rc;
-    const LoImages im = lo_images(p, sb, d);
-    QkvReadArgs ra{sb.Qh, sb.Ql, sb.Kh, sb.Kl, sb.Vth, sb.Vtl, im.q8l, im.k8l, out_d, M, d, p.hd, p.sg.S, p.sg.Spad, h->x2,
-                   p.att_scale * 1.4426950408889634f};
-    hipLaunchKernelGGL(qkv_planes_read_kernel, dim3(512), dim3(256), 0, h->stream, ra);
-    HIPCHK(h, hipGetLastError());
+    if (tail) {
+        // (the planes' padding rows up to the next multiple of 128 only ever feed discarded output rows of the GEMM path, but must be finite)
+        HIPCHK(h, hipMemsetAsync(ln.Xh, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
+        HIPCHK(h, hipMemsetAsync(ln.Xl, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
+        hipLaunchKernelGGL(tail_split_rows_kernel, dim3(512), dim3(256), 0, h->stream, in_d, ln.Xh, mode.x2 ? nullptr : ln.Xl, (int)M, d);
+        HIPCHK(h, hipGetLastError());
+        if (int rc = net_tail(h, p, ln, step, nullptr, hyp_d, out_d, nullptr, -1)) return rc;
+    } else {
+        if (int rc = run_embed(h, p, ln, in_d, hyp_d, h->thyp + (size_t)step * h->hl.total)) return rc;
+        if (int rc = qkv_planes(h, p, ln, 0, step, in_d, hyp_d)) return rc;
+        const LoImages im = lo_images(p, ln, d);
+        QkvReadArgs ra{ln.Qh, ln.Ql, ln.Kh, ln.Kl, ln.Vth, ln.Vtl, im.q8l, im.k8l, out_d, M, d, p.hd, p.sg.S, p.sg.Spad, mode.x2,
+                       p.att_scale * 1.4426950408889634f};
+        hipLaunchKernelGGL(qkv_planes_read_kernel, dim3(512), dim3(256), 0, h->stream, ra);
+        HIPCHK(h, hipGetLastError());
+    }
     int flag = 0;
     HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(qkv, out_d, M * 3 * d * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, out_d, M * out_w * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (thyp_row)
         HIPCHK(h, hipMemcpyAsync(thyp_row, h->thyp + (size_t)step * h->hl.total, h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (flag) return flagged_call(h, flag);
-    return 0;
-}
-
-// jmid_dbg_tail: the tail of step `step` alone on X [M, d] (fp32, split here into the planes the mode's concat3 reads: X_hi, and X_lo
-// in F16X3), as a step of a one-chunk call runs it - folded, or the two GEMMs + the output kernel with "tail_fold" = 1 -> e [M, 2].
-int dbg_tail(jmid_ctx* h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision, float* e, float* thyp_row) {
-    if (int rc = check_ready(h)) return rc;
-    if (!X || !hyp || !e || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen) return fail(h, JMID_EINVAL, "jmid_dbg_tail: bad arguments");
-    if (hyp_width != h->hl.total) return fail(h, JMID_EINVAL, "jmid_dbg_tail: hyp rows must be " + std::to_string(h->hl.total) + " wide");
-    if (precision != JMID_PREC_F16X3 && precision != JMID_PREC_F16X2 && precision != JMID_PREC_F16MX)
-        return fail(h, JMID_EINVAL, "jmid_dbg_tail: a split-fp16 mode only");
-    if (step < 0 || step >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "jmid_dbg_tail: step outside the step table");
-    h->mx = precision == JMID_PREC_F16MX;
-    h->x2 = precision == JMID_PREC_F16X2 || h->mx;
-    HIPCHK(h, hipSetDevice(h->device));
-    h->last_pos = nullptr;
-    const size_t M = (size_t)E * K * A * T, EA = (size_t)E * A;
-    const int d = h->d;
-    CallFacts facts;          // (an idle handle: nothing else in flight, one launch, the table of one step)
-    const StepPlan p = plan_step(h, E, A, K, T, precision, facts);
-    const size_t rows = p.tail_fold ? EA : 0;
-    size_t io_off;
-    {
-        Carver c(nullptr);
-        c.take(M * d);
-        c.take(EA * h->hl.total);
-        c.take(M * 2);
-        io_off = c.off;
-    }
-    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, precision, p.sg, 1, nullptr, nullptr, 0, rows))) return rc;
-    Carver c(h->arena);
-    float* X_d = c.take(M * d);
-    float* hyp_d = c.take(EA * h->hl.total);
-    float* e_d = c.take(M * 2);
-    StepBuffers sb;
-    step_ws_floats(h, M, precision, p.sg, 1, &sb, h->arena + io_off, 0, rows);
-    HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemcpyAsync(X_d, X, M * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(hyp_d, hyp, EA * h->hl.total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    // (the planes' padding rows up to the next multiple of 128 only ever feed discarded output rows of the GEMM path, but must be finite)
-    HIPCHK(h, hipMemsetAsync(sb.Xh, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(sb.Xl, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
-    hipLaunchKernelGGL(tail_split_rows_kernel, dim3(512), dim3(256), 0, h->stream, X_d, sb.Xh, h->x2 ? nullptr : sb.Xl, (int)M, d);
-    HIPCHK(h, hipGetLastError());
-    if (int rc = net_tail(h, p, sb, step, nullptr, hyp_d, e_d, nullptr, -1)) return rc;
-    int flag = 0;
-    HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(e, e_d, M * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (thyp_row)
-        HIPCHK(h, hipMemcpyAsync(thyp_row, h->thyp + (size_t)step * h->hl.total, h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (flag) return flagged_call(h, flag);
-    return 0;
+    return flag ? flagged_call(h, flag) : 0;
 }
 #endif
 
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T) {
-    ProfScope ps(h, KC_METRICS);
+    ProfScope ps(h, KC_METRICS, h->stream);
     hipLaunchKernelGGL(episode_metrics_kernel, dim3(E), dim3(256), 0, h->stream, pos, gt, out, K, A, T);
     HIPCHK(h, hipGetLastError());
     return 0;
