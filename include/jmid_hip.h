@@ -296,6 +296,38 @@ int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* p
 int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask,
                  const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out);
 
+/* Padded scene batches: ONE call for episodes of different agent counts.  Every array keeps the uniform layout of the plain entry with
+ * A - the largest count of the batch - as the row stride, plus
+ *   n_agents  [E] int32, HOST array in both memory modes, 1 <= n_agents[e] <= A: episode e has n_agents[e] real agents, a < n_agents[e]
+ * Row s*A + a of an episode is real iff a < n_agents[e]; the other rows are padding.  The semantics are the reference's attn_mask
+ * (JointPredictionTransformerConcatLinear.forward(..., mask), MID/models/diffusion.py:186-195, built in
+ * MID/dataset/preprocessing.py:36-89): joint attention is block-diagonal over episodes and the tokens of padded agents are excluded as
+ * keys, so the real rows of episode e are what the plain entry computes for that episode alone at A = n_agents[e] (up to the rounding
+ * of a sum taken in another order; an episode with n_agents[e] == A keeps the plain call's bits under the rule of
+ * jmid_set_chunk_episodes).  Attention is the only operation that couples rows: an iMID handle accepts the same calls and needs no mask.
+ *   - what the caller leaves in the padded rows of x / x_T, ctx and p0 is never read (the library works on zeroed copies), NaN included,
+ *     and cannot raise JMID_ERANGE;
+ *   - the padded rows of every returned array are quiet NaN - e_out, vel_out, pos_out, sel, logw, and the positions left resident for
+ *     pos = NULL: a consumer that forgets n_agents sees it at once;
+ *   - jmid_topk_padded ranks episode e in 2 * n_agents[e] dimensions over its real agents (pos = NULL: as jmid_topk, after
+ *     jmid_denoise_padded of the same shape);
+ *   - chunking, chunk lanes and the split-KV factor follow E, A, K, T exactly as for the plain call; the padded share of the rows
+ *     is computed and thrown away.
+ * DDIM with the caller's x_T only: there is no padded form of jmid_denoise_ddpm, of the *_seeded entries (the generator addresses an
+ * element by its offset in [K*A, T, 2], which depends on A: which A a padded episode draws with is a decision of its own), nor of
+ * jmid_predict_scene / jmid_forecast_scene, where mixed counts stay JMID_EINVAL.  JMID_EINVAL for NULL n_agents, a count outside 1..A,
+ * a DDPM table on the handle, and (diagnostics flavour) for the attention A/B knobs that have no masked kernel: "attn_sm" = 2 in every
+ * split mode, "attn_mx" = 1 and "attn_pf" = 2 in JMID_PREC_F16X2 / F16MX.  Everything else as the plain entry of the same name. */
+int jmid_net_eval_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, int step_idx, const float* x, const float* ctx,
+                         int precision, float* e_out, int mem);
+int jmid_denoise_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* x_T, const float* ctx, const float* p0,
+                        float dt, int precision, float* vel_out, float* pos_out, int mem);
+int jmid_topk_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* pos, const float* bw, float* sel,
+                     float* logw, int mem);
+int jmid_predict_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
+                        const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
+                        float* logw, float* pos_out);
+
 /* The scene batch on the device: track positions on the time_step grid in, the encoder's inputs left resident on the handle - what the
  * reference does between update_state_hists and Trajectron.get_latent (mid_sim_wrapper.py:313-437, MID/dataset/preprocessing.py:428-620,
  * MID/environment/scene_graph.py:111-250, the neighbour reductions of MID/models/encoders/mgcvae.py:726-768) for E independent episodes.

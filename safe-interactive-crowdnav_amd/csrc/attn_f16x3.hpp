@@ -15,6 +15,7 @@
 #pragma once
 #include "common.hpp"
 #include <algorithm>
+#include <type_traits>
 
 #include "gemm_f16x3.hpp"
 
@@ -82,10 +83,21 @@ struct AttnHArgs {
     int prio = 0;                // static s_setprio 1 for half of the workgroups (two share a CU, one wave of each per SIMD): 0 none, 1 = odd
                                  // workgroups of an XCD's sequence, 2 = every second group of 32 of that sequence (the second to land on each CU)
 };
+// The argument block of the MASK instantiations (a padded call, padded.hpp): + the key-mask words [nseq][ceil(S/32)].  A type of its
+// own, so that the plain kernels keep their argument block - args_now pins every dword of it in a scalar register - as it was.
+struct AttnHArgsM : AttnHArgs {
+    const unsigned* mask;
+};
+template <bool MASK>
+using AttnHArgsOf = std::conditional_t<MASK, AttnHArgsM, AttnHArgs>;
+__device__ __forceinline__ const unsigned* mask_words_of(const AttnHArgs&) { return nullptr; }
+__device__ __forceinline__ const unsigned* mask_words_of(const AttnHArgsM& a) { return a.mask; }
 
 
-template <int HD>
-__global__ __launch_bounds__(256, 1) void attn_f16x3_kernel(AttnHArgs a) {
+// MASK (a padded call): as in attn_f32.hpp - a zero word skips the tile whole (the lazy maximum of an all -inf tile on a running
+// maximum of -inf would be exp2(-inf + inf)), any other word replaces `key < S` (its bits at or past S are 0).
+template <int HD, bool MASK = false>
+__global__ __launch_bounds__(256, 1) void attn_f16x3_kernel(AttnHArgsOf<MASK> a) {
     constexpr int KT = 32;                    // keys per tile
     constexpr int KLD = HD + 8;               // halfs per K row in LDS (row = 2*HD + 16 bytes)
     constexpr int VLD = KT + 4;               // halfs per V^T row in LDS (72 bytes)
@@ -134,7 +146,10 @@ __global__ __launch_bounds__(256, 1) void attn_f16x3_kernel(AttnHArgs a) {
     constexpr int KCH = HD / 8;               // 16-byte chunks per K row
     const int ntiles = (S + KT - 1) / KT;
 
+    const unsigned* mwords = MASK ? mask_words_of(a) + (size_t)seq * ntiles : nullptr;
     for (int kt = 0; kt < ntiles; ++kt) {
+        const unsigned mw = MASK ? mwords[kt] : ~0u;       // (uniform over the workgroup: one sequence)
+        if (MASK && mw == 0u) continue;
         __syncthreads();                      // previous tile fully consumed (also orders the padding zero-fill)
         // ---- stage K tile [KT][HD] (rows past S zero-filled)
         for (int idx = tid; idx < KT * KCH; idx += 256) {
@@ -180,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void attn_f16x3_kernel(AttnHArgs a) {
         for (int r = 0; r < 16; ++r) {
             float s = sm[r];
             const int key = kt * KT + frag_row(r, hi);
-            s = key < S ? s : -INFINITY;
+            s = (MASK ? ((mw >> frag_row(r, hi)) & 1u) != 0u : key < S) ? s : -INFINITY;
             sm[r] = s;
             tmax = fmaxf(tmax, s);
         }
@@ -306,8 +321,18 @@ constexpr size_t ATT_DMA_LDS = size_t(2) * ATT_STAGE * sizeof(half_t);
 //     instructions instead of sixteen, and l normalises exactly the P that was used).
 // SM = 0: the round 2-5 form (tile maximum, lazy reference maximum, subtraction, fp32 row sum); diagnostics A/B ("attn_sm" = 2).
 constexpr float ATT_SM_THR = 16384.0f;      // the largest P stays below 2^14 (fp16 holds 2^16); every P keeps fp16's relative precision whatever its size
-template <bool TRACE, bool X2 = false, bool MX = false, bool PIPE = false, bool P1 = false, bool PF = false, int SM = 1>
-__global__ __launch_bounds__(256, 2) void attn_f16x3_dma_kernel(AttnHArgs a, int nqt, int abl, unsigned long long* trace) {
+// MASK (a padded call, padded.hpp; SM = 1 only) - per key tile the wave reads the tile's word, uniform over the workgroup, and branches:
+//   * all ones: the instruction sequence of the plain kernel;
+//   * zero: no arithmetic, but the tile keeps its place in the ring - its wait, its barrier and the copies of tile kt + 1 (the path
+//     of a wave without queries): the ring stage and the counted waits assume every tile is issued;
+//   * otherwise: the logits of invalid keys become -inf where keys past S do (the word's bits at or past S are 0).
+//   The "first tile" of the softmax (reference maximum still the placeholder 0, no rescale) is the first tile the wave COMPUTES, not
+//   tile kt_begin: only key 0 of a sequence is guaranteed valid, so a split may start on zero words.  A wave that computed no tile
+//   at all (its whole key range masked, or empty) hands (m, l) = (-inf, 0) with O = 0 to the merge: its weight there is
+//   exp2(-inf - M) = 0 whatever M, where the placeholder 0 would weigh 2^-M and overflow to inf x 0 for M < -128.
+template <bool TRACE, bool X2 = false, bool MX = false, bool PIPE = false, bool P1 = false, bool PF = false, int SM = 1, bool MASK = false>
+__global__ __launch_bounds__(256, 2) void attn_f16x3_dma_kernel(AttnHArgsOf<MASK> a, int nqt, int abl, unsigned long long* trace) {
+    static_assert(!MASK || SM == 1, "the masked kernels have the SM = 1 softmax only");
     constexpr int HD = 128, KT = 32, NT = 4, NKS = 8;
     args_now_each(a, nqt, abl, trace);
 #ifndef JMID_ABLATIONS
@@ -494,6 +519,8 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_dma_kernel(AttnHArgs a, int
     for (int mf = 0; mf < 2; ++mf) vbase[mf] = l31 * 32 + (((2 * mf + hi) ^ ((l31 >> 2) & 3)) * 8);
 
     const int ntiles_all = (S + KT - 1) / KT;
+    const unsigned* mwords = MASK ? mask_words_of(a) + (size_t)seq * ntiles_all : nullptr;
+    bool seen = false;       // MASK: (uniform) this wave has computed a key tile
     const bool fd = a.ms != 0 || a.nsplit == 1;
     const int kt_begin = fd ? fast_div(split * ntiles_all, a.nsplit, a.ms) : (int)((long)split * ntiles_all / a.nsplit);
     const int ntiles = fd ? fast_div((split + 1) * ntiles_all, a.nsplit, a.ms)
@@ -521,7 +548,8 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_dma_kernel(AttnHArgs a, int
         const bool more = MORE && !(abl & 1);    // abl: timing ablations (diagnostics only; zero otherwise, see the top of the kernel)
         if (more && (abl & 16)) issue(kt + 1, 1 - STG);
         ATT_STAMP(3)
-        if (wave_idle) {       // S = 1200: 2 of the 40 waves of a (sequence, head) - 5 % of the kernel's MFMA work
+        const unsigned mw = MASK ? __builtin_amdgcn_readfirstlane(mwords[kt]) : ~0u;
+        if (wave_idle || (MASK && mw == 0u)) {       // S = 1200: 2 of the 40 waves of a (sequence, head) - 5 % of the kernel's MFMA work
             if (more && !(abl & 16)) issue(kt + 1, 1 - STG);
             return;
         }
@@ -652,7 +680,13 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_dma_kernel(AttnHArgs a, int
         ATT_STAMP(4)
         f16x8 ph[2], pl[2];
         if (SM) {
-            if (kt == ntiles_all - 1) {              // only the last tile can hold keys past S
+            if (MASK) {
+                if (mw != ~0u) {                     // (uniform) a partial word: padded agents' keys, and in the last tile keys past S
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (!((mw >> frag_row(r, hi)) & 1u)) sm[r] = -INFINITY;
+                }
+            } else if (kt == ntiles_all - 1) {       // only the last tile can hold keys past S
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if (kt * KT + frag_row(r, hi) >= S) sm[r] = -INFINITY;
@@ -686,7 +720,8 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_dma_kernel(AttnHArgs a, int
                 half_swap(ps, x0, x1);
                 psum = x0 + x1;
             };
-            const bool first = kt == kt_begin;       // (uniform) a wave's first tile: m_run is still the placeholder 0
+            const bool first = MASK ? !seen : kt == kt_begin;       // (uniform) a wave's first tile: m_run is still the placeholder 0
+            if (MASK) seen = true;
             if (!first) soft(0.f, std::false_type{});      // (a first tile goes straight to the slow path: with a key split a wave has ~6 tiles)
             if (first || __any(!(psum <= ATT_SM_THR))) {
                 // slow path (a wave's first tile; afterwards only when a row's logits outgrow its reference maximum by 9 ... 14 in log2 units):
@@ -855,7 +890,7 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_dma_kernel(AttnHArgs a, int
                 }
             if (hi == 0) {
                 float* ml = a.MLpart + (((size_t)split * Mtot + tok) * a.nhead + h) * 2;
-                ml[0] = m_run;
+                ml[0] = MASK && !seen ? -INFINITY : m_run;
                 ml[1] = l_run;
             }
         }
@@ -996,14 +1031,26 @@ inline hipError_t launch_attn_dma(const AttnHArgs& a, const AttnPlan& p, dim3 gr
     return launch_with_lds<&attn_f16x3_dma_kernel<false, X2, MX, PIPE, P1, PF, SM>, 160 * 1024>(
         grid, dim3(256), p.one_wg ? 160 * 1024 : ATT_DMA_LDS, st, a, nqt, PIPE ? 0 : p.abl, (unsigned long long*)nullptr);
 }
+// the MASK instantiation of a padded call: the one the default plan picks for each mode (attn_masked_built)
+template <bool X2, bool MX, bool P1, bool PF>
+inline hipError_t launch_attn_dma_masked(const AttnHArgsM& a, const AttnPlan& p, dim3 grid, int nqt, hipStream_t st) {
+    return launch_with_lds<&attn_f16x3_dma_kernel<false, X2, MX, false, P1, PF, 1, true>, 160 * 1024>(
+        grid, dim3(256), p.one_wg ? 160 * 1024 : ATT_DMA_LDS, st, a, nqt, 0, (unsigned long long*)nullptr);
+}
 
 // (An 8-wave ping-pong form of this kernel - two wave groups per SIMD alternating between a matrix-instruction segment and the softmax across
 //  s_barrier - was built three times: rounds 4-5 with the ~100-instruction softmax, round 6 with the SM = 1 softmax, whose ~38 vector
 //  instructions fit inside the partner's matrix segment.  Bit-identical every time, and 7 % SLOWER than two free-running 4-wave workgroups
 //  per CU even then: profiles/r06_attn_pp_check.log, docs/NOTEBOOK.md section 11.  The kernel is not in the tree.)
-// p: launch_plan.hpp::plan_attn(head_dim, ...)
-inline hipError_t launch_attn_f16x3(const AttnHArgs& a_in, int nseq, int head_dim, const AttnPlan& p, hipStream_t st) {
+// p: launch_plan.hpp::plan_attn(head_dim, ...); mask: the key-mask words of the launch's sequences (p.masked), else null
+inline hipError_t launch_attn_f16x3(const AttnHArgs& a_in, int nseq, int head_dim, const AttnPlan& p, hipStream_t st, const unsigned* mask = nullptr) {
     AttnHArgs a = a_in;
+    const auto masked = [&]() {
+        AttnHArgsM m{};
+        static_cast<AttnHArgs&>(m) = a;
+        m.mask = mask;
+        return m;
+    };
     if (p.dma) {
         const int nqt = (a.S + 127) / 128;
         const dim3 grid1(nqt * a.nhead * nseq * a.nsplit);
@@ -1016,7 +1063,12 @@ inline hipError_t launch_attn_f16x3(const AttnHArgs& a_in, int nseq, int head_di
         // the mode is a template parameter (a run-time flag in the key-tile loop costs F16X3 ~4 %).  F16X2 / F16MX: one fp16 plane
         // of P unless "attn_mx" = 1; F16MX with bf8 K images: the logits' correction terms as bf8 MFMAs
         hipError_t e;
-        if (a.x2 && a.K8h) {
+        if (mask) {
+            if (!attn_masked_built(p, a.x2 != 0)) return hipErrorInvalidValue;      // (the planner refuses such a call before anything is launched)
+            if (a.x2 && a.K8h) e = launch_attn_dma_masked<true, true, true, true>(masked(), p, grid1, nqt, st);
+            else if (a.x2) e = launch_attn_dma_masked<true, false, true, true>(masked(), p, grid1, nqt, st);
+            else e = launch_attn_dma_masked<false, false, false, false>(masked(), p, grid1, nqt, st);
+        } else if (a.x2 && a.K8h) {
             if (p.p1 && p.pf) e = launch_attn_dma<true, true, false, true, true>(a, p, grid1, nqt, st);
             else if (p.p1) e = launch_attn_dma<true, true, false, true>(a, p, grid1, nqt, st);
             else e = launch_attn_dma<true, true, false, false>(a, p, grid1, nqt, st);
@@ -1035,6 +1087,17 @@ inline hipError_t launch_attn_f16x3(const AttnHArgs& a_in, int nseq, int head_di
         return e != hipSuccess ? e : hipGetLastError();
     }
     dim3 grid((a.S + 127) / 128, a.nhead, nseq);
+    if (mask) {
+        const AttnHArgsM m = masked();
+        switch (head_dim) {
+            case 16: hipLaunchKernelGGL((attn_f16x3_kernel<16, true>), grid, dim3(256), 0, st, m); break;
+            case 32: hipLaunchKernelGGL((attn_f16x3_kernel<32, true>), grid, dim3(256), 0, st, m); break;
+            case 64: hipLaunchKernelGGL((attn_f16x3_kernel<64, true>), grid, dim3(256), 0, st, m); break;
+            case 128: hipLaunchKernelGGL((attn_f16x3_kernel<128, true>), grid, dim3(256), 0, st, m); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (head_dim) {
         case 16: hipLaunchKernelGGL((attn_f16x3_kernel<16>), grid, dim3(256), 0, st, a); break;
         case 32: hipLaunchKernelGGL((attn_f16x3_kernel<32>), grid, dim3(256), 0, st, a); break;

@@ -26,9 +26,14 @@ struct AttnArgs {
     float scale;       // 1/sqrt(head_dim)
     half_t* Ohi;       // optional: write hi/lo planes [nseq*S, d] (blocked panel layout) instead of OUT
     half_t* Olo;
+    const unsigned* mask = nullptr;   // padded call (padded.hpp): key-mask words [nseq][ceil(S/32)], read by the MASK instantiations only
 };
 
-template <int HD, int NWAVES>
+// MASK (a padded call): the word of a key tile says which of its keys exist for EVERY query of the sequence, padded queries included
+// (they stay finite and are thrown away).  A zero word: the tile is skipped whole - with the running maximum still at -inf its
+// all -inf logits would give exp(-inf + inf); a full word: the arithmetic of the plain kernel (bits at or past S are 0 in the
+// words, so the word also does the plain kernel's `key < S`).  Key 0 of a sequence is always valid: l_run > 0 at the end.
+template <int HD, int NWAVES, bool MASK = false>
 __global__ __launch_bounds__(NWAVES * 64) void attn_f32_kernel(AttnArgs a) {
     constexpr int KT = 32;                 // keys per tile
     constexpr int KLD = HD + 4;            // padded K row (floats)
@@ -70,7 +75,10 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_f32_kernel(AttnArgs a) {
     constexpr int F4_PER_ROW = HD / 4;
     constexpr int NF4 = KT * F4_PER_ROW;
 
+    const unsigned* mwords = MASK ? a.mask + (size_t)seq * ntiles : nullptr;
     for (int kt = 0; kt < ntiles; ++kt) {
+        const unsigned mw = MASK ? mwords[kt] : ~0u;       // (uniform over the workgroup: one sequence)
+        if (MASK && mw == 0u) continue;
         // ---- cooperative K/V tile load (rows past S are zero-filled)
         for (int idx = tid; idx < NF4; idx += NWAVES * 64) {
             const int row = idx / F4_PER_ROW, c4 = idx % F4_PER_ROW;
@@ -104,7 +112,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_f32_kernel(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int key = kt * KT + frag_row(r, hi);
-            if (key >= S) st[r] = -INFINITY;
+            if (MASK ? !((mw >> frag_row(r, hi)) & 1u) : key >= S) st[r] = -INFINITY;
             tmax = fmaxf(tmax, st[r]);
         }
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
@@ -178,7 +186,8 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_f32_kernel(AttnArgs a) {
 // The result of a sequence must not depend on which slot of the tile it lands in (chunking-invariance is tested
 // bit for bit), so slot s puts its local key k on accumulator register j = s*J + k/2 of lane-half hi = k%2
 // (J = ceil(S/2)): every slot then adds its keys in the same order, and the masked positions contribute exact zeros.
-template <int HD>
+// MASK (a padded call; S <= 16: one mask word per sequence): a key must also be valid in the word of its own sequence.
+template <int HD, bool MASK = false>
 __global__ __launch_bounds__(256, 2) void attn_f32_packed_kernel(AttnArgs a, int nseq, int G, int J) {
     constexpr int KLD = HD + 4;            // padded K / V row (floats)
     constexpr int NT = (HD + 31) / 32;
@@ -248,10 +257,11 @@ __global__ __launch_bounds__(256, 2) void attn_f32_packed_kernel(AttnArgs a, int
     // ---- block-diagonal mask + softmax (single tile: no running state)
     float tmax = -INFINITY;
     {
+        const unsigned mw = MASK && qvalid ? a.mask[seq0 + sq] : ~0u;      // the word of this query's sequence
         int sl = 0, jj = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const bool ok = qvalid && sl == sq && (jj * 2 + hi) < S;
+            const bool ok = qvalid && sl == sq && (jj * 2 + hi) < S && (!MASK || ((mw >> (jj * 2 + hi)) & 1u));
             if (!ok) st[r] = -INFINITY;
             tmax = fmaxf(tmax, st[r]);
             if (++jj == J) {
@@ -320,23 +330,28 @@ __global__ __launch_bounds__(256, 2) void attn_f32_packed_kernel(AttnArgs a, int
 }
 
 
-template <int HD>
-inline hipError_t launch_attn_f32_hd(const AttnArgs& a, int nseq, bool pack, hipStream_t st) {
+template <int HD, bool MASK>
+inline hipError_t launch_attn_f32_hd_m(const AttnArgs& a, int nseq, bool pack, hipStream_t st) {
     if (a.S <= 16 && pack) {
         const int J = (a.S + 1) / 2;
         const int G = std::min(32 / a.S, 16 / J);
         const size_t lds = size_t(4) * 32 * (HD + 4) * sizeof(float);
         dim3 grid((nseq + G - 1) / G, (a.nhead + 3) / 4);
-        return launch_with_lds<&attn_f32_packed_kernel<HD>>(grid, dim3(256), lds, st, a, nseq, G, J);
+        return launch_with_lds<&attn_f32_packed_kernel<HD, MASK>>(grid, dim3(256), lds, st, a, nseq, G, J);
     }
     if (a.S > 32) {
         dim3 grid((a.S + 127) / 128, a.nhead, nseq);
-        hipLaunchKernelGGL((attn_f32_kernel<HD, 4>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((attn_f32_kernel<HD, 4, MASK>), grid, dim3(256), 0, st, a);
     } else {
         dim3 grid(1, a.nhead, nseq);
-        hipLaunchKernelGGL((attn_f32_kernel<HD, 1>), grid, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((attn_f32_kernel<HD, 1, MASK>), grid, dim3(64), 0, st, a);
     }
     return hipGetLastError();
+}
+// a.mask set (a padded call): the MASK instantiations
+template <int HD>
+inline hipError_t launch_attn_f32_hd(const AttnArgs& a, int nseq, bool pack, hipStream_t st) {
+    return a.mask ? launch_attn_f32_hd_m<HD, true>(a, nseq, pack, st) : launch_attn_f32_hd_m<HD, false>(a, nseq, pack, st);
 }
 
 // pack: AttnPlan::pack (launch_plan.hpp)

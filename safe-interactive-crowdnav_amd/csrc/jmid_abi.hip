@@ -40,7 +40,8 @@ const float* resident_positions(jmid_ctx* h, int E, int A, int K, int T) {
 }
 
 // the two KDE launches on device buffers (pos [E, K, A, T, 2], bw [T] or null -> sel, logw); the ll / Y workspace is the handle's
-int topk_on_device(jmid_ctx* h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw) {
+int topk_on_device(jmid_ctx* h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
+                   const int* n_agents_dev = nullptr) {
     const int d = 2 * A;
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t y_bytes = kde_y_in_lds(A, K) ? 0 : up((size_t)E * T * K * d * 8);
@@ -50,7 +51,7 @@ int topk_on_device(jmid_ctx* h, int E, int A, int K, int T, int k, const float* 
     g.E = E; g.A = A; g.K = K; g.T = T; g.k = k;
     g.ll = reinterpret_cast<double*>(h->kde_ws);
     g.Y = reinterpret_cast<double*>(h->kde_ws + o_Y);
-    g.pos = pos; g.bw = bw; g.sel = sel; g.logw = logw;
+    g.pos = pos; g.bw = bw; g.sel = sel; g.logw = logw; g.n_agents = n_agents_dev;
     ProfScope ps(h, KC_TOPK, h->stream);
     HIPCHK(h, launch_kde(g, h->stream));
     return 0;
@@ -76,7 +77,9 @@ int ensure_pin(jmid_ctx* h, size_t need, const char* who) {
 // seeded (scene mode only; the *_seeded entries): x_T is null and its slot of the device block is filled there, draw 0 of noise.hpp.
 int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask, const float* x_T,
                   const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out, bool scene, const char* who,
-                  double* fc_out = nullptr, double* lwd_out = nullptr, const SeedArgs* seeded = nullptr) {
+                  double* fc_out = nullptr, double* lwd_out = nullptr, const SeedArgs* seeded = nullptr, const int32_t* n_agents = nullptr) {
+    // n_agents (jmid_predict_padded; host arrays only): the padded agents' rows go through the encoder as the caller left them - its rows are
+    // independent - and the denoise stage zeroes their ctx, x_T and p0
     const bool rank = k < K;
     const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
     const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
@@ -141,8 +144,9 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
     }
     DenoiseCall c{E, A, K, T, precision, JMID_MEM_DEVICE};       // a stage of the chain: no caller-stream ordering, the flag comes with the one download
     c.x_in = dev + o_xT; c.ctx = dev + o_ctx; c.p0 = dev + o_p0; c.dt = dt; c.pos_out = pos_out ? dev + o_pos : nullptr; c.chained = true;
+    c.n_agents = n_agents;
     if (!rc) rc = run_network(h, c);
-    if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw);
+    if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw, n_agents ? h->nag_dev : nullptr);
     if (!rc && fc_out) {
         const jmid_ctx::SceneWs& sc = h->scene;
         AssembleArgs aa{};
@@ -449,6 +453,9 @@ int jmid_destroy(jmid_handle_t h) {
     if (h->noise_ids) hipFree(h->noise_ids);
     if (h->noise_ids_pin) (void)hipHostFree(h->noise_ids_pin);
     if (h->ev_ids) hipEventDestroy(h->ev_ids);
+    if (h->nag_dev) hipFree(h->nag_dev);
+    if (h->nag_pin) (void)hipHostFree(h->nag_pin);
+    if (h->ev_nag) hipEventDestroy(h->ev_nag);
     if (h->frames_dev) hipFree(h->frames_dev);
     for (int c = 0; c < KC_COUNT; ++c)
         for (auto& ev : h->prof_ev[c]) {
@@ -538,6 +545,27 @@ int jmid_net_eval(jmid_handle_t h, int E, int A, int K, int T, int step_idx, con
     if (step_idx < 0 || step_idx >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "step_idx out of range");
     DenoiseCall c{E, A, K, T, precision, mem};
     c.x_in = x; c.ctx = ctx; c.e_out = e_out; c.single_step = step_idx;
+    return run_network(h, c);
+}
+
+int jmid_net_eval_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, int step_idx, const float* x, const float* ctx,
+                         int precision, float* e_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (!n_agents) return fail(h, JMID_EINVAL, "jmid_net_eval_padded: null n_agents");
+    if (!e_out) return fail(h, JMID_EINVAL, "null e_out");
+    if (int rc = check_ready(h)) return rc;
+    if (step_idx < 0 || step_idx >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "step_idx out of range");
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.x_in = x; c.ctx = ctx; c.e_out = e_out; c.single_step = step_idx; c.n_agents = n_agents;
+    return run_network(h, c);
+}
+
+int jmid_denoise_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* x_T, const float* ctx, const float* p0,
+                        float dt, int precision, float* vel_out, float* pos_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (!n_agents) return fail(h, JMID_EINVAL, "jmid_denoise_padded: null n_agents");
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.x_in = x_T; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.n_agents = n_agents;
     return run_network(h, c);
 }
 
@@ -725,8 +753,9 @@ int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const
     return order_out(h, mem);
 }
 
-int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
-              int mem) {
+// jmid_topk (n_agents null) and jmid_topk_padded
+static int topk_entry(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* pos, const float* bw, float* sel,
+                      float* logw, int mem) {
     if (!h || !sel || !logw || E <= 0 || A <= 0 || K <= 1 || T <= 0) return fail(h, JMID_EINVAL, "bad argument");
     if (k < 1 || k > K) return fail(h, JMID_EINVAL, "k must be in 1..K");
     if (A > 32 || K > 1024 || T > 24) return fail(h, JMID_EINVAL, "jmid_topk supports A <= 32, K <= 1024, T <= 24");
@@ -744,6 +773,10 @@ int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* p
     if (int rc = ensure_kde_ws(h, need, "jmid_topk")) return rc;
     KdeArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T; g.k = k;
+    if (n_agents) {
+        if (int rc = upload_n_agents(h, n_agents, E)) return rc;
+        g.n_agents = h->nag_dev;
+    }
     g.ll = reinterpret_cast<double*>(h->kde_ws + o_ll);
     g.Y = reinterpret_cast<double*>(h->kde_ws + o_Y);
     g.pos = pos ? pos : h->last_pos;
@@ -774,8 +807,39 @@ int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* p
     return order_out(h, mem);
 }
 
+int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
+              int mem) {
+    return topk_entry(h, E, A, K, T, k, nullptr, pos, bw, sel, logw, mem);
+}
+
+int jmid_topk_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* pos, const float* bw, float* sel,
+                     float* logw, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (int rc = check_n_agents(h, "jmid_topk_padded", n_agents, E, A)) return rc;
+    return topk_entry(h, E, A, K, T, k, n_agents, pos, bw, sel, logw, mem);
+}
+
+static int predict_entry(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
+                         const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
+                         float* logw, float* pos_out);
+
+int jmid_predict_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
+                        const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
+                        float* logw, float* pos_out) {
+    if (!h) return JMID_EINVAL;
+    if (int rc = check_n_agents(h, "jmid_predict_padded", n_agents, E, A)) return rc;
+    return predict_entry(h, E, A, K, T, k, n_agents, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out);
+}
+
 int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask,
                  const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out) {
+    return predict_entry(h, E, A, K, T, k, nullptr, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out);
+}
+
+// jmid_predict (n_agents null) and jmid_predict_padded
+static int predict_entry(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
+                         const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
+                         float* logw, float* pos_out) {
     if (!h) return JMID_EINVAL;
     if (int rc = check_ready(h)) return rc;
     if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, "jmid_predict: bad dimensions");
@@ -786,7 +850,8 @@ int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float
     if (rank && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, "jmid_predict: the device top-k supports A <= 32, K <= 1024, T <= 24");
     if (h->ddpm) return fail(h, JMID_EINVAL, "jmid_predict samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
     HIPCHK(h, hipSetDevice(h->device));
-    return predict_chain(h, E, A, K, T, k, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out, false, "jmid_predict");
+    return predict_chain(h, E, A, K, T, k, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out, false, "jmid_predict", nullptr, nullptr,
+                         nullptr, n_agents);
 }
 
 int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, double time_step, int horizon,

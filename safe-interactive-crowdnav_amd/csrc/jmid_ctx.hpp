@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <vector>
@@ -33,6 +34,7 @@
 #include "kde.hpp"
 #include "launch_plan.hpp"
 #include "noise.hpp"
+#include "padded.hpp"
 #include "qkv0.hpp"
 #include "tail_fold.hpp"
 #include "scene.hpp"
@@ -154,6 +156,11 @@ struct jmid_ctx {
     int noise_ids_cap = 0;
     unsigned* noise_ids_pin = nullptr;       // pinned staging of the ids: a device-mode call may return before its copies have run, and the
     hipEvent_t ev_ids = nullptr;             // caller's array need not outlive the call; ev_ids = the last upload has left the staging
+    // the padded entry points: the call's agent counts on the device, with their pinned staging (as the episode ids above)
+    int* nag_dev = nullptr;
+    int nag_cap = 0;
+    int* nag_pin = nullptr;
+    hipEvent_t ev_nag = nullptr;
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)
     bool lnx_off = false;       // a workgroup of that kernel once gave up waiting for a partner (range flag bit 1): the handle stays on GEMM + add_ln2
@@ -307,7 +314,14 @@ struct DenoiseCall {
     const float* z = nullptr;             // DDPM noise [n_steps, M, 2] of the caller
     const SeedArgs* seeded = nullptr;     // ... or x_T and the DDPM z drawn on the device
     bool chained = false;                 // a stage of jmid_predict: no caller-stream ordering, no flag round trip
+    // a padded call (padded.hpp): HOST array [E], 1 <= n_agents[e] <= A - episode e has n_agents[e] real agents, the rows of the others
+    // are zeroed on entry and NaN in every output; JMID attention takes the key-mask words.  DDIM with the caller's x_T only.
+    const int32_t* n_agents = nullptr;
 };
+// the counts of a padded call: checked by its entry before anything is enqueued (JMID_EINVAL: null, or a count outside 1..A), then
+// uploaded to h->nag_dev on h->stream
+int check_n_agents(jmid_ctx* h, const char* who, const int32_t* n_agents, int E, int A);
+int upload_n_agents(jmid_ctx* h, const int32_t* n_agents, int E);
 int run_network(jmid_ctx* h, DenoiseCall a);      // (by value: its host inputs become their uploads)
 int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in, const float* hyp, int hyp_width, int step, int precision,
              float* out, float* thyp_row);      // jmid_dbg_qkv0 (tail = false) / jmid_dbg_tail: -DJMID_DIAGNOSTICS only

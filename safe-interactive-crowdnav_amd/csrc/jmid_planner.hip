@@ -185,7 +185,7 @@ struct StepPlan {
     int out_tpw;                 // output kernel: tokens per wave of the per-trajectory form, 0 = one wave per token
 };
 
-StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, const CallMode& mode, const CallFacts& cf) {
+StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, const CallMode& mode, const CallFacts& cf, bool masked = false) {
     StepPlan p{};
     const int d = h->d;
     p.Ec = Ec;
@@ -203,6 +203,7 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, const CallMod
     p.cf = cf;
     const Tuning& t = h->tune;
     p.attn = plan_attn(p.hd, t);
+    p.attn.masked = masked && p.joint;      // (iMID: its rows are independent sequences, nothing to mask)
     p.qkv0 = split && p.joint && t.qkv0 != 1 && d % 32 == 0;      // (d % 32: the K tiles of the table's GEMM - as every GEMM of the net)
     p.tail_fold = split && t.tail_fold != 1 && d % 8 == 0 && d <= kTailMaxD && h->dmid <= kTailMaxMid && h->dlow <= kTailMaxLow;
     if (split) {
@@ -479,7 +480,8 @@ int net_tail(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float
 
 // one evaluation of the net on a chunk of whole episodes + (optionally) the DDIM update, as its plan says
 int net_step(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float* x_chunk, const float* hyp_chunk,
-             float* e_out, const float* z_chunk = nullptr, bool embed_done = false, int next_step = -1) {
+             float* e_out, const float* z_chunk = nullptr, bool embed_done = false, int next_step = -1, const unsigned* mask_chunk = nullptr) {
+    // mask_chunk: the key-mask words of the chunk's episodes in a padded call (p.attn.masked), else null
     // embed_done: the previous step's output kernel already embedded x for this step; next_step >= 0: this step's
     // output kernel does the same for step `next_step` (same chunk, same buffers)
     const bool split = p.mode.split;
@@ -497,6 +499,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float
             {
                 ProfScope ps(h, KC_ATTN, ln.stream);
                 AttnArgs aa{ln.QKV, ln.ATT, S, d, h->nhead, p.att_scale, nullptr, nullptr};
+                aa.mask = p.attn.masked ? mask_chunk : nullptr;
                 HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, ln.stream));
             }
             // attention output projection + residual + LN1
@@ -525,7 +528,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float
                 AttnHArgs aa{ln.Qh, ln.Ql, ln.Kh, ln.Kl, ln.Vth, ln.Vtl, ln.Ah, ln.Al, S, sg.Spad, d, h->nhead,
                              p.att_scale, h->range_flag, p.cf.attn_nsplit, ln.Opart, ln.MLpart, p.mode.x2, im.k8h, im.k8l, im.q8l};
                 aa.skip_combine = p.out_proj.merge;
-                HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, p.attn, ln.stream));
+                HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, p.attn, ln.stream, p.attn.masked ? mask_chunk : nullptr));
             } else {
                 g = gemm_h_args(p.mode, rm, M, ln.Xh, ln.Xl, w.in_proj, 3 * d, d);
                 g.C = ln.QKV; g.ldc = 3 * d;
@@ -653,6 +656,36 @@ int upload_noise_ids(jmid_ctx* h, const uint32_t* ids, int E) {
     return 0;
 }
 
+int check_n_agents(jmid_ctx* h, const char* who, const int32_t* n_agents, int E, int A) {
+    if (!n_agents) return fail(h, JMID_EINVAL, std::string(who) + ": null n_agents");
+    for (int e = 0; e < E; ++e)
+        if (n_agents[e] < 1 || n_agents[e] > A)
+            return fail(h, JMID_EINVAL, std::string(who) + ": n_agents[" + std::to_string(e) + "] = " + std::to_string(n_agents[e]) + " is outside 1..A");
+    return 0;
+}
+
+int upload_n_agents(jmid_ctx* h, const int32_t* n_agents, int E) {
+    if (!h->ev_nag) HIPCHK(h, hipEventCreateWithFlags(&h->ev_nag, hipEventDisableTiming));
+    if (E > h->nag_cap) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->nag_dev) HIPCHK(h, hipFree(h->nag_dev));
+        if (h->nag_pin) HIPCHK(h, hipHostFree(h->nag_pin));
+        h->nag_dev = h->nag_pin = nullptr;
+        h->nag_cap = 0;
+        const int cap = std::max(E, 64);
+        if (hipMalloc((void**)&h->nag_dev, (size_t)cap * sizeof(int)) != hipSuccess ||
+            hipHostMalloc((void**)&h->nag_pin, (size_t)cap * sizeof(int), hipHostMallocDefault) != hipSuccess)
+            return fail(h, JMID_ENOMEM, "agent count buffer allocation failed");
+        h->nag_cap = cap;
+    } else {
+        HIPCHK(h, hipEventSynchronize(h->ev_nag));       // the previous upload has read the staging
+    }
+    std::memcpy(h->nag_pin, n_agents, (size_t)E * sizeof(int));
+    HIPCHK(h, hipMemcpyAsync(h->nag_dev, h->nag_pin, (size_t)E * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev_nag, h->stream));
+    return 0;
+}
+
 // One draw for E episodes of n elements each (noise.hpp): normals to `out` and / or the raw words to `words`, device buffers.
 int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream) {
     NoiseArgs g{};
@@ -681,6 +714,7 @@ struct CallPlan {
     std::vector<StepPlan> plans;
     std::vector<int> chunk_plan;                    // chunk -> its plan
     size_t qkv0_rows, tail_rows;                    // rows of a lane's two tables (step_ws_floats)
+    bool masked;                                    // a padded call (DenoiseCall::n_agents)
     bool z_fill;                                    // seeded DDPM: the z of ONE step per lane, filled on that lane's stream just before the step's update (no [n_steps, ...] buffer)
 };
 
@@ -688,6 +722,7 @@ CallPlan plan_call(const jmid_ctx* h, const DenoiseCall& a, const CallMode& mode
     const int E = a.E, A = a.A, K = a.K, T = a.T;
     CallPlan cp{};
     cp.mode = mode;
+    cp.masked = a.n_agents != nullptr;
     cp.chunk_sizes = plan_chunks(h, mode, E, K * A * T);
     cp.chunk_start.assign(cp.chunk_sizes.size(), 0);
     for (size_t i = 1; i < cp.chunk_sizes.size(); ++i) cp.chunk_start[i] = cp.chunk_start[i - 1] + cp.chunk_sizes[i - 1];
@@ -722,7 +757,7 @@ CallPlan plan_call(const jmid_ctx* h, const DenoiseCall& a, const CallMode& mode
     for (int ec : cp.chunk_sizes) {
         size_t j = 0;
         while (j < cp.plans.size() && cp.plans[j].Ec != ec) ++j;
-        if (j == cp.plans.size()) cp.plans.push_back(plan_step(h, ec, A, K, T, mode, cp.facts));
+        if (j == cp.plans.size()) cp.plans.push_back(plan_step(h, ec, A, K, T, mode, cp.facts, cp.masked));
         cp.chunk_plan.push_back((int)j);
     }
     cp.qkv0_rows = cp.plans[0].qkv0 ? (size_t)cp.facts.qkv0_steps * Ec * A * 3 : 0;
@@ -733,6 +768,7 @@ CallPlan plan_call(const jmid_ctx* h, const DenoiseCall& a, const CallMode& mode
 // The I/O block of a call's workspace, in front of the lanes' step workspaces.  base null: its size only (as step_ws_floats).
 struct CallIo {
     float *x_cur, *ctx, *hyp, *p0, *stage, *z_up, *z_lane;      // stage: e / pos; z_up: the caller's DDPM noise; z_lane: z_fill
+    unsigned* mask;      // a padded JMID call: key-mask words [E][ceil(S / 32)] (padded.hpp) - a chunk's words are its episodes' slice
 };
 size_t call_io(const jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, char* base, CallIo* out) {
     const size_t M = (size_t)a.E * a.K * a.A * a.T, EA = (size_t)a.E * a.A;
@@ -745,6 +781,7 @@ size_t call_io(const jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, char
     io.stage = c.take(M * 2);
     if (a.z && a.mem == JMID_MEM_HOST) io.z_up = c.take(M * 2 * h->beta.size());
     if (cp.z_fill) io.z_lane = c.take((size_t)cp.nlanes * cp.Mc * 2);
+    if (cp.masked && h->net_kind == JMID_NET_JMID) io.mask = reinterpret_cast<unsigned*>(c.take((size_t)a.E * mask_words_per_seq(a.K * a.A * a.T)));
     if (out) *out = io;
     return c.off;
 }
@@ -761,6 +798,12 @@ int check_call(jmid_ctx* h, const DenoiseCall& a, CallMode* mode) {
     if (a.seeded && !a.seeded->ids) return fail(h, JMID_EINVAL, "null episode_ids");
     if (a.seeded && !noise_fits((unsigned long long)a.K * a.A * a.T * 2)) return fail(h, JMID_EINVAL, "K * A * T exceeds the noise addressing");
     if (a.pos_out && !a.p0) return fail(h, JMID_EINVAL, "pos_out requested without p0");
+    if (a.n_agents) {
+        if (a.seeded || a.z || (a.single_step < 0 && h->ddpm)) return fail(h, JMID_EINVAL, "a padded call samples with DDIM from the caller's x_T only");
+        if (int rc = check_n_agents(h, "padded call", a.n_agents, a.E, a.A)) return rc;
+        if (h->net_kind == JMID_NET_JMID && mode->split && !attn_masked_built(plan_attn(h->d / h->nhead, h->tune), mode->x2 != 0))
+            return fail(h, JMID_EINVAL, "a padded call needs the default attention kernel: \"attn_sm\" = 2 and the ablations (every split mode), \"attn_mx\" = 1 and \"attn_pf\" = 2 (F16X2 / F16MX) have no masked form");
+    }
     h->last_pos = nullptr;     // (the staging buffer is about to be reused)
     if (a.single_step < 0 && h->ddpm && !a.z && !a.seeded) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
     if (a.single_step < 0 && !h->ddpm && a.z) return fail(h, JMID_EINVAL, "jmid_denoise_ddpm needs jmid_set_ddpm_table");
@@ -801,13 +844,22 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
     } else {
         HIPCHK(h, hipMemcpyAsync(io.x_cur, a.x_in, M * 2 * sizeof(float), kin, h->stream));
     }
-    if (a.mem == JMID_MEM_HOST) {
+    if (a.mem == JMID_MEM_HOST || cp.masked) {      // (a padded call zeroes rows of ctx and p0: never in the caller's arrays)
         HIPCHK(h, hipMemcpyAsync(io.ctx, a.ctx, EA * h->ctx_dim * sizeof(float), kin, h->stream));
         a.ctx = io.ctx;
     }
-    if (a.p0 && a.mem == JMID_MEM_HOST) {
+    if (a.p0 && (a.mem == JMID_MEM_HOST || cp.masked)) {
         HIPCHK(h, hipMemcpyAsync(io.p0, a.p0, EA * 2 * sizeof(float), kin, h->stream));
         a.p0 = io.p0;
+    }
+    if (cp.masked) {
+        // the counts, the key-mask words from them, and zeros in the padded agents' rows of x_T, ctx and p0: whatever the caller left
+        // there is never read.  All of it outside a captured loop, on memory the loop reads: a replay sees this call's counts.
+        if (int rc = upload_n_agents(h, a.n_agents, a.E)) return rc;
+        if (io.mask) HIPCHK(h, launch_mask_words(h->nag_dev, io.mask, a.E, a.A, a.T, a.K * a.A * a.T, h->stream));
+        HIPCHK(h, launch_pad_fill(io.x_cur, h->nag_dev, a.E, a.K, a.A, a.T * 2, 0.f, h->stream));
+        HIPCHK(h, launch_pad_fill(io.ctx, h->nag_dev, a.E, 1, a.A, h->ctx_dim, 0.f, h->stream));
+        if (a.p0) HIPCHK(h, launch_pad_fill(io.p0, h->nag_dev, a.E, 1, a.A, 2, 0.f, h->stream));
     }
     // ---- ctx part of the four hyper nets, once per call (ctx is constant over the denoise steps)
     GemmArgs g{};
@@ -840,7 +892,7 @@ int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallI
     if (a.single_step < 0 && lanes == 1 && nchunks == 1 && !h->prof_mask && !a.z && !h->ddpm && h->tune.graph == 1 &&
         h->tune.bystander_lds == 0) {
         const std::string key = std::to_string(E) + "," + std::to_string(A) + "," + std::to_string(K) + "," + std::to_string(T) +
-                                "," + std::to_string(a.precision);
+                                "," + std::to_string(a.precision) + (cp.masked ? ",padded" : "");
         lg = &h->graphs[key];
         if (lg->exec && lg->arena != h->arena) {        // never true today (ensure_arena drops the graphs); cheap to keep
             hipGraphExecDestroy(lg->exec);
@@ -874,7 +926,8 @@ int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallI
                 if (!rc && i == 0 && pl.qkv0 && pl.cf.qkv0_steps > 1) rc = qkv0_build_table(h, pl, ln, hc, 0, n_steps);
                 if (!rc && i == 0 && pl.tail_fold && pl.cf.tail_steps > 1) rc = tail_build_table(h, pl, ln, hc, 0, n_steps);
                 if (!rc) rc = net_step(h, pl, ln, i, xc, hc, one ? io.stage + el * tok * 2 : nullptr, zc, h->tune.fuse_embed && i > i0,
-                                        h->tune.fuse_embed && i + 1 < i1 ? i + 1 : -1);
+                                        h->tune.fuse_embed && i + 1 < i1 ? i + 1 : -1,
+                                        io.mask ? io.mask + el * mask_words_per_seq((int)tok) : nullptr);
                 if (rc) {
                     if (capturing) {
                         hipGraph_t dead = nullptr;
@@ -916,6 +969,9 @@ int finish_call(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const Cal
         HIPCHK(h, hipEventRecord(h->ev_join[l - 1], cp.lanes[l].stream));
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[l - 1], 0));
     }
+    // a padded call: quiet NaN in the padded agents' rows of what it returns - and, through the integrator, of the resident positions
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    if (cp.masked) HIPCHK(h, launch_pad_fill(a.single_step >= 0 ? io.stage : io.x_cur, h->nag_dev, a.E, a.K, a.A, a.T * 2, qnan, h->stream));
     if (a.single_step >= 0) {
         HIPCHK(h, hipMemcpyAsync(a.e_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
     } else {

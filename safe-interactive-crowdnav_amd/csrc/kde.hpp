@@ -28,6 +28,9 @@ struct KdeArgs {
     int E, A, K, T, k;
     int y_in_lds;
     int p_in_lds;         // the K x d points of the (episode, horizon step) staged in LDS as doubles (they are read ~2 d + 3 times each)
+    // padded batches (jmid_topk_padded; null: every episode has A agents - the same kernels on the same values, bit for bit): episode e
+    // is ranked in d = 2 n_agents[e] dimensions over its first n_agents[e] agents of the A-strided rows; sel and logw of the others are NaN
+    const int* n_agents;
 };
 
 constexpr int KDE_THREADS = 256;
@@ -69,13 +72,13 @@ static __global__ __launch_bounds__(KDE_THREADS) void kde_step_kernel(KdeArgs g)
     extern __shared__ __attribute__((aligned(16))) unsigned char kde_lds_raw[];
     const int tid = threadIdx.x, blk = blockIdx.x;
     const int e = blk / g.T, h = blk - e * g.T;
-    const int A = g.A, K = g.K, T = g.T, d = 2 * A;
+    const int A = g.A, K = g.K, T = g.T, d = 2 * (g.n_agents ? g.n_agents[e] : A);      // (d: the episode's; A stays the row stride of pos)
     double* Pm = reinterpret_cast<double*>(kde_lds_raw);     // P, then inverse(P), then L
     double* Im = Pm + d * d;                                 // triangular inverses
     double* mean = Im + d * d;
     double* red = mean + d;
     double* llv = red + KDE_THREADS;
-    double* Yp = g.y_in_lds ? llv + K : g.Y + (size_t)blk * K * d;
+    double* Yp = g.y_in_lds ? llv + K : g.Y + (size_t)blk * K * 2 * A;      // (the slice of a block by the stride 2 A, whatever the episode's d)
     double* Pp = g.p_in_lds ? llv + K + (g.y_in_lds ? K * d : 0) : nullptr;
     const float* pe = g.pos + (size_t)e * K * A * T * 2;
     // the points of this (episode, horizon step): staged once (one pass over global memory instead of a dependent load per use -
@@ -232,12 +235,14 @@ static __global__ __launch_bounds__(KDE_THREADS) void kde_select_kernel(KdeArgs 
         __syncthreads();
     }
     const double lse = m + log(red[0]);
-    for (int idx = tid; idx < A * k; idx += KDE_THREADS) g.logw[(size_t)e * A * k + idx] = (float)(tot[keep[idx % k]] - lse);
+    const int An = g.n_agents ? g.n_agents[e] : A;      // real agents of the episode
+    const float qnan = __builtin_nanf("");
+    for (int idx = tid; idx < A * k; idx += KDE_THREADS) g.logw[(size_t)e * A * k + idx] = idx / k < An ? (float)(tot[keep[idx % k]] - lse) : qnan;
     const float* pe = g.pos + (size_t)e * K * A * T * 2;
     float* se = g.sel + (size_t)e * A * k * T * 2;
     for (int idx = tid; idx < A * k * T * 2; idx += KDE_THREADS) {
         const int r = idx % (T * 2), q = (idx / (T * 2)) % k, a = idx / (T * 2 * k);
-        se[idx] = pe[((size_t)keep[q] * A + a) * T * 2 + r];
+        se[idx] = a < An ? pe[((size_t)keep[q] * A + a) * T * 2 + r] : qnan;
     }
 }
 

@@ -211,6 +211,7 @@ struct AttnPlan {
     int abl;             // timing ablations (-DJMID_ABLATIONS only)
     int bystander_lds;   // dynamic LDS of the split-KV merge kernel (common.hpp::bystander_lds)
     bool pack;           // exact-fp32 kernel: several short sequences (S <= 16) per wave
+    bool masked;         // a padded call (padded.hpp): the MASK instantiations, key-mask words in AttnArgs::mask / AttnHArgsM::mask
 };
 inline AttnPlan plan_attn(int head_dim, const Tuning& t) {
     AttnPlan p{};
@@ -225,6 +226,12 @@ inline AttnPlan plan_attn(int head_dim, const Tuning& t) {
     p.pack = t.attn_pack != 0;
     return p;
 }
+
+// The masked LDS-DMA kernel exists as the instantiation the default plan picks for each of F16X3, F16X2 and F16MX (with or without the
+// bf8 K images): in no mode with the round 2-5 softmax ("attn_sm" = 2) or the timing ablations, and in the two-term modes (x2: F16X2 /
+// F16MX) neither with P_hi + P_lo ("attn_mx" = 1) nor with the one-step fragment reads ("attn_pf" = 2) - F16X3 has one instantiation,
+// which those two knobs do not select.  A padded call under such a knob is JMID_EINVAL.
+inline bool attn_masked_built(const AttnPlan& p, bool x2) { return !p.dma || (!p.old_softmax && !p.abl && (!x2 || (p.p1 && p.pf))); }
 
 // does the out-projection's OUT_LNX launch also merge the partial outputs of a split-KV attention launch (lnx_combine)?  "small_cmb": 0 on, 2 off
 inline bool small_cmb_fits(const AttnPlan& ap, int nsplit, int x2, const Tuning& t) {

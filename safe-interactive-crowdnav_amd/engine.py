@@ -35,6 +35,15 @@ def _is_cuda(t) -> bool:
     return torch is not None and isinstance(t, torch.Tensor) and t.is_cuda
 
 
+def agent_counts(n_agents, E: int) -> np.ndarray:
+    """The ``n_agents`` argument of a padded call as the library takes it: a contiguous HOST int32 array [E] (the library checks the
+    range 1..A and answers JMID_EINVAL)."""
+    n = np.ascontiguousarray(np.asarray(n_agents.cpu() if torch is not None and torch.is_tensor(n_agents) else n_agents), dtype=np.int32).reshape(-1)
+    if n.size != E:
+        raise ValueError(f"n_agents must hold one count per episode ({E}), got {n.size}")
+    return n
+
+
 def seeded_noise_args(x_T, seed, episode_ids, E: Optional[int] = None):
     """The noise source of a call: either the caller's ``x_T`` or ``seed`` + ``episode_ids`` (the library's counter generator,
     ``noise.py``), never both.  -> None for an explicit call, else (seed, ids uint32 [E])."""
@@ -223,14 +232,18 @@ class JmidEngine:
 
     def denoise(self, x_T: Optional[ArrayLike], ctx: ArrayLike, p0: Optional[ArrayLike] = None, dt: float = 0.25,
                 precision: str = "f32", want_vel: bool = True, want_pos: bool = True, z: Optional[ArrayLike] = None,
-                seed: Optional[int] = None, episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+                seed: Optional[int] = None, episode_ids=None, K: Optional[int] = None, T: Optional[int] = None, n_agents=None):
         """Batched reverse-denoising loop.  x_T [E, K*A, T, 2], ctx [E, A, ctx_dim], p0 [E, A, 2].
+        ``n_agents`` [E] (``jmid_denoise_padded``, DDIM with an explicit x_T only): episode e has n_agents[e] <= A real agents, rows
+        s*A + a with a >= n_agents[e] are padding - never read on the way in, NaN in vel and pos.
         ``z`` [n_steps, E, K*A, T, 2]: per-step normal draws, required when the DDPM table is installed.
         ``seed`` + ``episode_ids`` [E] (with ``x_T=None`` and the sample count ``K`` and horizon ``T``): the library draws x_T - and,
         under the DDPM table, every step's z - from its counter generator (``jmid_denoise_seeded``; ``noise.py``): the same bits as the
         explicit call fed ``noise(seed, episode_ids, K * A, T, draw)``, for every batch the episodes are part of.
         Returns (vel [E,K,A,T,2] or None, pos [E,K,A,T,2] or None)."""
         seeded = seeded_noise_args(x_T, seed, episode_ids)
+        if n_agents is not None and (seeded is not None or z is not None):
+            raise ValueError("a padded call (n_agents) is DDIM with an explicit x_T: no seed, no z")
         if seeded is not None:
             if z is not None:
                 raise ValueError("z and seed are mutually exclusive: a seeded call draws z itself")
@@ -268,17 +281,23 @@ class JmidEngine:
             self._compute(self._lib.jmid_denoise_ddpm, self._h, E, A, K, T, bx.ptr, bz.ptr, bc.ptr, bp.ptr if bp else None,
                                                     float(dt), _lib.PRECISIONS[precision], vptr, pptr,
                                                     self._mem(dev))
+        elif n_agents is not None:
+            na = agent_counts(n_agents, E)
+            self._compute(self._lib.jmid_denoise_padded, self._h, E, A, K, T, C.c_void_p(na.ctypes.data), bx.ptr, bc.ptr, bp.ptr if bp else None,
+                          float(dt), _lib.PRECISIONS[precision], vptr, pptr, self._mem(dev))
         else:
             self._compute(self._lib.jmid_denoise, self._h, E, A, K, T, bx.ptr, bc.ptr, bp.ptr if bp else None, float(dt),
                                                _lib.PRECISIONS[precision], vptr, pptr,
                                                self._mem(dev))
         return vel, pos
 
-    def topk(self, pos: Optional[ArrayLike], k: int, dims: Optional[Tuple[int, int, int, int]] = None):
+    def topk(self, pos: Optional[ArrayLike], k: int, dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None):
         """Joint-KDE top-k on the device (``jmid_topk``; get_most_likely_samples, mid_sim_wrapper.py:14-169), batched over
         episodes.  pos [E, K, A, T, 2] -> (kept [E, A, k, T, 2], log-weights [E, A, k]) in ascending likelihood.
         ``pos=None`` with ``dims=(E, A, K, T)`` ranks the positions of the preceding ``denoise`` call, which are still in the
-        engine's workspace (nothing but the k kept samples comes back to the host)."""
+        engine's workspace (nothing but the k kept samples comes back to the host).
+        ``n_agents`` [E] (``jmid_topk_padded``): episode e is ranked in 2 n_agents[e] dimensions over its real agents; kept samples
+        and log-weights of the padded agents are NaN."""
         import math
         if pos is None:
             if dims is None:
@@ -301,15 +320,30 @@ class JmidEngine:
             sel = np.empty((E, A, k, T, 2), dtype=np.float32)
             lw = np.empty((E, A, k), dtype=np.float32)
             ptrs = (C.c_void_p(bwb.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data))
+        if n_agents is not None:
+            na = agent_counts(n_agents, E)
+            self._check(self._lib.jmid_topk_padded(self._h, E, A, K, T, int(k), C.c_void_p(na.ctypes.data), bp.ptr if bp is not None else None,
+                                                   *ptrs, self._mem(dev)))
+            return sel, lw
         self._check(self._lib.jmid_topk(self._h, E, A, K, T, int(k), bp.ptr if bp is not None else None, *ptrs,
                                         self._mem(dev)))
         return sel, lw
+
+    def predict_padded(self, x_st: np.ndarray, nbr_sum: np.ndarray, edge_mask: np.ndarray, x_T: np.ndarray, p0: np.ndarray, k: int,
+                       n_agents, dt: float = 0.25, precision: str = "f32"):
+        """``predict`` for episodes of different agent counts in one call (``jmid_predict_padded``): the same arrays with A = the
+        largest count as the row stride (``scene.pad_rows`` / ``scene.pad_samples`` make them) and ``n_agents`` [E].  The padded
+        agents' rows of every output are NaN."""
+        return self._predict(n_agents, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision)
 
     def predict(self, x_st: np.ndarray, nbr_sum: np.ndarray, edge_mask: np.ndarray, x_T: np.ndarray, p0: np.ndarray, k: int,
                 dt: float = 0.25, precision: str = "f32"):
         """One predictor call end to end (``jmid_predict``): encoder -> denoise loop -> integrator -> joint-KDE top-k, host arrays in
         and out, one upload, one download, nothing in between.  x_st [E*A, hist, 6], nbr_sum [E*A, 2, hist, 6], edge_mask [E*A, 2],
         x_T [E, K*A, T, 2], p0 [E, A, 2].  k < K -> (kept [E, A, k, T, 2], log-weights [E, A, k]); k == K -> (pos [E, K, A, T, 2], None)."""
+        return self._predict(None, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision)
+
+    def _predict(self, n_agents, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision):
         import math
         E, KA, T, _ = (int(v) for v in x_T.shape)
         A = int(p0.shape[1])
@@ -318,16 +352,20 @@ class JmidEngine:
                 or tuple(edge_mask.shape) != (E * A, 2) or KA != K * A or tuple(p0.shape) != (E, A, 2):
             raise ValueError("bad predict() input shapes")
         b = [_Buf(a, False) for a in (x_st, nbr_sum, edge_mask, x_T, p0)]
+        if n_agents is not None:
+            na = agent_counts(n_agents, E)
+            fn, head = self._lib.jmid_predict_padded, (self._h, E, A, K, T, int(k), C.c_void_p(na.ctypes.data))
+        else:
+            fn, head = self._lib.jmid_predict, (self._h, E, A, K, T, int(k))
         if k < K:
             bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
             sel = np.empty((E, A, k, T, 2), dtype=np.float32)
             lw = np.empty((E, A, k), dtype=np.float32)
-            self._compute(self._lib.jmid_predict, self._h, E, A, K, T, int(k), *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision],
-                                               C.c_void_p(bw.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data), None)
+            self._compute(fn, *head, *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision],
+                          C.c_void_p(bw.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data), None)
             return sel, lw
         pos = np.empty((E, K, A, T, 2), dtype=np.float32)
-        self._compute(self._lib.jmid_predict, self._h, E, A, K, T, int(k), *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision],
-                                           None, None, None, C.c_void_p(pos.ctypes.data))
+        self._compute(fn, *head, *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision], None, None, None, C.c_void_p(pos.ctypes.data))
         return pos, None
 
     def build_scene(self, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: Optional[int] = None,
@@ -486,8 +524,9 @@ class JmidEngine:
                       C.c_void_p(bw.ctypes.data) if bw is not None else None, C.c_void_p(fc.ctypes.data), C.c_void_p(lw.ctypes.data))
         return (fc[0], lw[0]) if single else (fc, lw)
 
-    def net_eval(self, x: ArrayLike, ctx: ArrayLike, step_idx: int = 0, precision: str = "f32"):
-        """One evaluation of e_theta for DDIM table entry ``step_idx``; x [E, K*A, T, 2] -> e same shape."""
+    def net_eval(self, x: ArrayLike, ctx: ArrayLike, step_idx: int = 0, precision: str = "f32", n_agents=None):
+        """One evaluation of e_theta for DDIM table entry ``step_idx``; x [E, K*A, T, 2] -> e same shape.  ``n_agents`` [E]
+        (``jmid_net_eval_padded``): rows of agents a >= n_agents[e] are padding, NaN in e."""
         dev = _is_cuda(x)
         E, A, K, T = self._shapes(x, ctx)
         bx, bc = _Buf(x, dev), _Buf(ctx, dev)
@@ -497,6 +536,11 @@ class JmidEngine:
         else:
             out = np.empty(tuple(x.shape), dtype=np.float32)
             optr = C.c_void_p(out.ctypes.data)
+        if n_agents is not None:
+            na = agent_counts(n_agents, E)
+            self._compute(self._lib.jmid_net_eval_padded, self._h, E, A, K, T, C.c_void_p(na.ctypes.data), int(step_idx), bx.ptr, bc.ptr,
+                          _lib.PRECISIONS[precision], optr, self._mem(dev))
+            return out
         self._compute(self._lib.jmid_net_eval, self._h, E, A, K, T, int(step_idx), bx.ptr, bc.ptr,
                                             _lib.PRECISIONS[precision], optr,
                                             self._mem(dev))

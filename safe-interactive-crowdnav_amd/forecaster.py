@@ -449,7 +449,8 @@ def _engine_lock_of(engine: JmidEngine) -> RLock:
 def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray, seeds, *, num_samples: int,
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
                   device_topk: bool = True, device_scene: bool = False,
-                  device_frames: bool = False, noise: str = "torch", seed: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  device_frames: bool = False, noise: str = "torch", seed: int = 0,
+                  padded: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -469,9 +470,19 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     bits whichever batch, count group or shard it is part of (in JMID_PREC_F32 at any width and in every mode below head_dim 128; at
     head_dim 128 the split modes agree to rounding across batch sizes, include/jmid_hip.h at jmid_set_chunk_episodes) - statistically,
     not seed-, compatible with the reference.
+    ``padded=True`` (opt-in): instead of one call per count, EVERY episode goes through one ``engine.predict_padded`` call with
+    A = the largest count; episodes with fewer in-cluster pedestrians carry padding rows, which the attention kernels mask as keys
+    (the reference's attn_mask, diffusion.py:186-195) - the forecasts equal the grouped path's up to rounding, the torch draws are the
+    same (episode e draws [K * n_e, H, 2] from ``seeds[e]``, scattered to the padded rows).  One loop at the batch's launch rate against
+    one per count at a group's; the padded share of the rows is wasted work.  Host arrays and torch noise only:
+    not with ``device_scene``, ``device_frames`` or ``noise="device"``; a batch whose ranking does not fit the device top-k, or
+    with an empty cluster, takes the grouped path.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
+    if padded and (device_scene or device_frames or noise == "device"):
+        raise ValueError("padded=True takes host scene arrays and torch noise only: not with device_scene, device_frames or noise='device' "
+                         "(the padded entries have no scene-resident or seeded form)")
     E, F, N, _ = human_xy.shape
     K, k, H = int(num_samples), int(num_ret_samples), int(horizon)
     precision = DEFAULTS["precision"] if precision is None else precision      # (no self check here: an engine-level call)
@@ -487,6 +498,34 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     forecasts = np.zeros((E, N, k, H, 2), dtype=np.float64)
     logw = np.zeros((E, N, k), dtype=np.float64)
     n_in = inc.sum(axis=1)
+    pose = np.repeat(human_xy[:, -1][:, :, None, None, :], k, axis=2)              # [E, N, k, 1, 2]
+    if padded and n_in.min() >= 1 and (k == K or (device_topk and topk_fits_device(int(n_in.max()), K, H))):
+        A = int(n_in.max())
+        x_T = SC.pad_samples([torch.randn([K * int(n_in[e]), H, 2], generator=torch.Generator().manual_seed(int(seeds[e]))).numpy()
+                              for e in range(E)], n_in, A, K)
+        args = (SC.pad_agents(b["x_st"], inc, A).reshape(E * A, F, 6), SC.pad_agents(b["nbr_sum"], inc, A).reshape(E * A, 2, F, 6),
+                SC.pad_agents(b["edge_mask"], inc, A).reshape(E * A, 2), x_T, SC.pad_agents(b["p0"], inc, A), k, n_in)
+        with _engine_lock_of(engine):
+            try:
+                sel_all, lw_all = engine.predict_padded(*args, dt=time_step, precision=precision)
+            except JmidError as err:
+                if err.code != -5 or precision == "f32":     # JMID_ERANGE: the same call in exact fp32, counted
+                    raise
+                ERANGE_FALLBACKS += 1
+                sel_all, lw_all = engine.predict_padded(*args, dt=time_step, precision="f32")
+        for e in range(E):
+            n, rows = int(n_in[e]), np.nonzero(inc[e])[0]
+            if k < K:
+                sel, lw = sel_all[e, :n], lw_all[e, :n].astype(np.float64)        # [n, k, H, 2], [n, k]
+            else:
+                sel = SC.unpad_samples(sel_all, n_in, e).transpose(1, 0, 2, 3)    # pos [K, n, H, 2] -> agents first
+                lw = np.log(np.ones((n, K), dtype=np.float64) / K)
+            forecasts[e, rows] = sel
+            logw[e, rows] = lw
+            out_rows = np.nonzero(~inc[e])[0]
+            forecasts[e, out_rows] = b["cv"][e, out_rows][:, None]
+            logw[e, out_rows] = lw[0]
+        return np.concatenate((pose, forecasts), axis=3), logw, inc
     for A in np.unique(n_in):
         eps = np.nonzero(n_in == A)[0]
         A = int(A)
@@ -538,7 +577,6 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             out_rows = np.nonzero(~inc[e])[0]
             forecasts[e, out_rows] = b["cv"][e, out_rows][:, None]
             logw[e, out_rows] = lw[0]
-    pose = np.repeat(human_xy[:, -1][:, :, None, None, :], k, axis=2)              # [E, N, k, 1, 2]
     return np.concatenate((pose, forecasts), axis=3), logw, inc
 
 

@@ -426,6 +426,47 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
 
 
 # --------------------------------------------------------------------------------------------- synthetic feeds
+# ---------------------------------------------------------------------------------------------- padded scene batches
+# Episodes of different in-cluster counts n[e] in ONE device call of the uniform shape [E, K * A, ...], A = max(n) (the *_padded
+# entries of include/jmid_hip.h): agent a of episode e is real iff a < n[e]; sample s of agent a is row s * A + a.
+
+def pad_agents(arr: np.ndarray, in_cluster: np.ndarray, A: int) -> np.ndarray:
+    """Per-track arrays [E, N, ...] -> [E, A, ...]: episode e's in-cluster rows in ascending track id, then zero rows."""
+    E = arr.shape[0]
+    out = np.zeros((E, A) + arr.shape[2:], dtype=arr.dtype)
+    for e in range(E):
+        rows = np.nonzero(in_cluster[e])[0]
+        out[e, :rows.size] = arr[e, rows]
+    return out
+
+
+def pad_samples(per_episode: Sequence[np.ndarray], n_agents: np.ndarray, A: int, K: int) -> np.ndarray:
+    """Per-episode sample rows [K * n[e], ...] (row s * n[e] + a, as the plain call takes them) -> [E, K * A, ...] with the row of
+    (s, a) at s * A + a and zeros in the padded agents' rows."""
+    first = np.asarray(per_episode[0])
+    out = np.zeros((len(per_episode), K * A) + first.shape[1:], dtype=first.dtype)
+    for e, x in enumerate(per_episode):
+        n = int(n_agents[e])
+        out[e].reshape((K, A) + first.shape[1:])[:, :n] = np.asarray(x).reshape((K, n) + first.shape[1:])
+    return out
+
+
+def unpad_samples(arr: np.ndarray, n_agents: np.ndarray, e: int) -> np.ndarray:
+    """The inverse for one episode of an output [E, K, A, ...]: its real agents [K, n[e], ...]."""
+    return arr[e][:, :int(n_agents[e])]
+
+
+def key_mask_words(n_agents: np.ndarray, A: int, K: int, T: int) -> np.ndarray:
+    """NumPy twin of the device's key-mask words (csrc/padded.hpp): uint32 [E, ceil(S / 32)], S = K * A * T; bit i of word w of
+    episode e is set iff key 32 w + i < S belongs to a real agent - token j = (s * A + a) * T + t is a valid key iff a < n[e]."""
+    S = K * A * T
+    nw = (S + 31) // 32
+    key = np.arange(nw * 32)
+    valid = (key[None, :] < S) & (((key // T) % A)[None, :] < np.asarray(n_agents).reshape(-1, 1))
+    bits = valid.reshape(len(valid), nw, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
+    return bits.sum(axis=2).astype(np.uint32)
+
+
 def synthetic_episodes(E: int, N: int, seed: int, time_step: float = 0.25, num_hist_frames: int = 6,
                        horizon: int = 12) -> Dict[str, np.ndarray]:
     """Synthetic scene batches for measurement: per episode pos0 ~ U(-2,2)^2,
