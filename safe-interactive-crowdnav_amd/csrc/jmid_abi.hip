@@ -15,20 +15,6 @@ int fail(jmid_ctx* h, int code, const std::string& msg) {
     return code;
 }
 
-// the handle's second workspace (jmid_topk, jmid_eval_statistics: it must not move the arena last_pos points into), grown on demand
-int ensure_kde_ws(jmid_ctx* h, size_t need, const char* who) {
-    if (need <= h->kde_ws_bytes) return 0;
-    if (h->kde_ws) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipFree(h->kde_ws));
-        h->kde_ws = nullptr;
-        h->kde_ws_bytes = 0;
-    }
-    if (hipMalloc((void**)&h->kde_ws, need) != hipSuccess) return fail(h, JMID_ENOMEM, std::string(who) + " workspace allocation failed");
-    h->kde_ws_bytes = need;
-    return 0;
-}
-
 // pos = NULL of jmid_topk / jmid_eval_statistics: the positions the most recent jmid_denoise left in the workspace, or null (with the
 // error set) when there are none of this shape - the rules include/jmid_hip.h documents at jmid_topk
 const float* resident_positions(jmid_ctx* h, int E, int A, int K, int T) {
@@ -39,34 +25,43 @@ const float* resident_positions(jmid_ctx* h, int E, int A, int K, int T) {
     return h->last_pos;
 }
 
-// the two KDE launches on device buffers (pos [E, K, A, T, 2], bw [T] or null -> sel, logw); the ll / Y workspace is the handle's
-int topk_on_device(jmid_ctx* h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
-                   const int* n_agents_dev = nullptr) {
-    const int d = 2 * A;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t y_bytes = kde_y_in_lds(A, K) ? 0 : up((size_t)E * T * K * d * 8);
-    const size_t o_Y = up((size_t)E * T * K * 8), need = o_Y + y_bytes;
-    if (int rc = ensure_kde_ws(h, need, "jmid_topk")) return rc;
+// The KDE's workspace, laid out here only: ll [E, T, K] doubles | Y, the whitened points [E, T, K, 2 A], only when they do not fit in
+// LDS (E = 64, T = 12, K = 1024, A = 32 would be 400 MB).  base null: the size only
+size_t kde_workspace(int E, int A, int K, int T, char* base, KdeArgs* g) {
+    Carver c(base);
+    double* ll = c.take<double>((size_t)E * T * K);
+    double* Y = c.take<double>(kde_y_in_lds(A, K) ? 0 : (size_t)E * T * K * 2 * A);
+    if (g) g->ll = ll, g->Y = Y;
+    return c.off;
+}
+
+// the two KDE launches on device buffers (pos [E, K, A, T, 2], bw [T] or null -> sel, logw).  ws: kde_workspace bytes the caller staged,
+// or null: the handle's second workspace
+int topk_on_device(jmid_ctx* h, const char* who, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
+                   const int* n_agents_dev, char* ws = nullptr) {
+    if (!ws) {
+        if (int rc = h->kde_ws.reserve(h, kde_workspace(E, A, K, T, nullptr, nullptr), who)) return rc;
+        ws = h->kde_ws.p;
+    }
     KdeArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T; g.k = k;
-    g.ll = reinterpret_cast<double*>(h->kde_ws);
-    g.Y = reinterpret_cast<double*>(h->kde_ws + o_Y);
+    kde_workspace(E, A, K, T, ws, &g);
     g.pos = pos; g.bw = bw; g.sel = sel; g.logw = logw; g.n_agents = n_agents_dev;
     ProfScope ps(h, KC_TOPK, h->stream);
     HIPCHK(h, launch_kde(g, h->stream));
     return 0;
 }
 
-// the pinned host staging buffer of the chained calls (jmid_predict, jmid_predict_scene, jmid_build_scene), grown on demand
-int ensure_pin(jmid_ctx* h, size_t need, const char* who) {
-    if (need <= h->pin_bytes) return 0;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->pin) HIPCHK(h, hipHostFree(h->pin));
-    h->pin = nullptr;
-    h->pin_bytes = 0;
-    if (hipHostMalloc((void**)&h->pin, need, hipHostMallocDefault) != hipSuccess) return fail(h, JMID_ENOMEM, std::string(who) + ": pinned staging allocation failed");
-    h->pin_bytes = need;
-    return 0;
+// the encoder's launch arguments: the handle's transposed LSTM / attention weights, the caller's n rows
+EncArgs encoder_args(const jmid_ctx* h, const float* x_st, const float* nbr_sum, const float* edge_mask, float* ctx, int n) {
+    EncArgs ea{};
+    ea.x_st = x_st; ea.nbr_sum = nbr_sum; ea.edge_mask = edge_mask;
+    ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
+    ea.edge[0] = LstmW{h->lstmT[1][0], h->lstmT[1][1], h->lstmT[1][2]};
+    ea.edge[1] = LstmW{h->lstmT[2][0], h->lstmT[2][1], h->lstmT[2][2]};
+    ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = h->wt.edge_v;
+    ea.ctx = ctx; ea.n = n; ea.Th = h->hist_len; ea.H = h->H;
+    return ea;
 }
 
 // jmid_predict and jmid_predict_scene after their argument checks: one upload, encoder -> denoise loop -> integrator -> top-k chained on
@@ -84,25 +79,17 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
     const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
     const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
     const size_t n_sel = rank ? n * k * T * 2 : 0, n_lw = rank ? n * k : 0, n_pos = pos_out ? n_xT : 0;
-    auto up = [](size_t floats) { return (floats + 63) / 64 * 64; };
     // the assembled arrays are doubles: two float slots each (every offset is a multiple of 256 bytes)
     const size_t Np = fc_out ? (size_t)h->scene.N : 0, n_fc = 2 * ((size_t)E * Np * k * (T + 1) * 2), n_lwd = 2 * ((size_t)E * Np * k);
     // upload block | ctx | download block (flag, forecasts, their logw, sel, logw, pos; with fc_out the download ends behind the first three)
-    const size_t o_xs = 0, o_nb = o_xs + up(n_xs), o_em = o_nb + up(n_nb), o_xT = o_em + up(n_em), o_p0 = o_xT + up(n_xT), o_bw = o_p0 + up(n_p0),
-                 in_floats = o_bw + up(n_bw), o_ctx = in_floats, o_out = o_ctx + up(n * H2), o_flag = o_out, o_fc = o_flag + 64, o_lwd = o_fc + up(n_fc),
-                 o_sel = o_lwd + up(n_lwd), o_lw = o_sel + up(n_sel), o_pos = o_lw + up(n_lw), total = o_pos + up(n_pos),
+    const size_t o_xs = 0, o_nb = o_xs + align_up_floats(n_xs), o_em = o_nb + align_up_floats(n_nb), o_xT = o_em + align_up_floats(n_em), o_p0 = o_xT + align_up_floats(n_xT), o_bw = o_p0 + align_up_floats(n_p0),
+                 in_floats = o_bw + align_up_floats(n_bw), o_ctx = in_floats, o_out = o_ctx + align_up_floats(n * H2), o_flag = o_out, o_fc = o_flag + align_up_floats(1), o_lwd = o_fc + align_up_floats(n_fc),
+                 o_sel = o_lwd + align_up_floats(n_lwd), o_lw = o_sel + align_up_floats(n_sel), o_pos = o_lw + align_up_floats(n_lw), total = o_pos + align_up_floats(n_pos),
                  out_floats = (fc_out ? o_sel : total) - o_out;
-    if (total * 4 > h->io_dev_bytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->io_dev) HIPCHK(h, hipFree(h->io_dev));
-        h->io_dev = nullptr;
-        h->io_dev_bytes = 0;
-        if (hipMalloc((void**)&h->io_dev, total * 4) != hipSuccess) return fail(h, JMID_ENOMEM, std::string(who) + ": device staging allocation failed");
-        h->io_dev_bytes = total * 4;
-    }
-    if (int rc = ensure_pin(h, (in_floats + out_floats) * 4, who)) return rc;
-    float* pin = reinterpret_cast<float*>(h->pin);
-    float* dev = reinterpret_cast<float*>(h->io_dev);
+    if (int rc = h->io_dev.reserve(h, total * 4, who)) return rc;
+    if (int rc = h->pin.reserve(h, (in_floats + out_floats) * 4, who)) return rc;
+    float* pin = h->pin.as<float>();
+    float* dev = h->io_dev.as<float>();
     if (!seeded) std::memcpy(pin + o_xT, x_T, n_xT * 4);
     if (n_bw) std::memcpy(pin + o_bw, bw, n_bw * 4);
     if (!scene) {
@@ -117,8 +104,8 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
         else if (n_bw) HIPCHK(h, hipMemcpyAsync(dev + o_bw, pin + o_bw, n_bw * 4, hipMemcpyHostToDevice, h->stream));
     }
     if (seeded) {
-        if (int rc = upload_noise_ids(h, seeded->ids, E)) return rc;
-        if (int rc = fill_noise(h, seeded->seed, h->noise_ids, E, (size_t)K * A * T * 2, 0, dev + o_xT, nullptr, h->stream)) return rc;
+        if (int rc = h->noise_ids.upload(h, seeded->ids, E, who)) return rc;
+        if (int rc = fill_noise(h, seeded->seed, h->noise_ids.get<unsigned>(), E, (size_t)K * A * T * 2, 0, dev + o_xT, nullptr, h->stream)) return rc;
     }
     int rc = 0;
     {
@@ -126,37 +113,31 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
         if (scene) {
             const jmid_ctx::SceneWs& sc = h->scene;
             SceneGatherArgs ga{};
-            ga.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev + sc.o_inc);
-            ga.x_st = reinterpret_cast<const float*>(sc.dev + sc.o_xst); ga.nbr_sum = reinterpret_cast<const float*>(sc.dev + sc.o_nbr);
-            ga.edge_mask = reinterpret_cast<const float*>(sc.dev + sc.o_em); ga.p0 = reinterpret_cast<const float*>(sc.dev + sc.o_p0);
+            ga.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev.p + sc.o_inc);
+            ga.x_st = reinterpret_cast<const float*>(sc.dev.p + sc.o_xst); ga.nbr_sum = reinterpret_cast<const float*>(sc.dev.p + sc.o_nbr);
+            ga.edge_mask = reinterpret_cast<const float*>(sc.dev.p + sc.o_em); ga.p0 = reinterpret_cast<const float*>(sc.dev.p + sc.o_p0);
             ga.o_x_st = dev + o_xs; ga.o_nbr_sum = dev + o_nb; ga.o_edge_mask = dev + o_em; ga.o_p0 = dev + o_p0;
             ga.E = E; ga.N = sc.N; ga.A = A; ga.F = (int)Th;
             if (launch_scene_gather(ga, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": scene gather launch failed");
         }
-        EncArgs ea{};
-        ea.x_st = dev + o_xs; ea.nbr_sum = dev + o_nb; ea.edge_mask = dev + o_em;
-        ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
-        ea.edge[0] = LstmW{h->lstmT[1][0], h->lstmT[1][1], h->lstmT[1][2]};
-        ea.edge[1] = LstmW{h->lstmT[2][0], h->lstmT[2][1], h->lstmT[2][2]};
-        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = h->wt.edge_v;
-        ea.ctx = dev + o_ctx; ea.n = (int)n; ea.Th = (int)Th; ea.H = h->H;
+        const EncArgs ea = encoder_args(h, dev + o_xs, dev + o_nb, dev + o_em, dev + o_ctx, (int)n);
         if (!rc && launch_encoder(ea, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": encoder launch failed");
     }
     DenoiseCall c{E, A, K, T, precision, JMID_MEM_DEVICE};       // a stage of the chain: no caller-stream ordering, the flag comes with the one download
     c.x_in = dev + o_xT; c.ctx = dev + o_ctx; c.p0 = dev + o_p0; c.dt = dt; c.pos_out = pos_out ? dev + o_pos : nullptr; c.chained = true;
-    c.n_agents = n_agents;
+    c.n_agents = n_agents; c.who = who;
     if (!rc) rc = run_network(h, c);
-    if (!rc && rank) rc = topk_on_device(h, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw, n_agents ? h->nag_dev : nullptr);
+    if (!rc && rank) rc = topk_on_device(h, who, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw, n_agents ? h->nag.get<int>() : nullptr);
     if (!rc && fc_out) {
         const jmid_ctx::SceneWs& sc = h->scene;
         AssembleArgs aa{};
-        aa.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev + sc.o_inc);
+        aa.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev.p + sc.o_inc);
         aa.src = rank ? dev + o_sel : h->last_pos;
         aa.logw_in = rank ? dev + o_lw : nullptr;
-        aa.cv = reinterpret_cast<const double*>(sc.dev + sc.o_cv);
+        aa.cv = reinterpret_cast<const double*>(sc.dev.p + sc.o_cv);
         // pose_now: its own slot after a stamped build, the last frame of the grid otherwise (what predict_batch prepends)
-        aa.pose = sc.stamped ? reinterpret_cast<const double*>(sc.dev + sc.o_pose)
-                             : reinterpret_cast<const double*>(sc.dev + sc.o_hum) + (Th - 1) * (size_t)sc.N * 2;
+        aa.pose = sc.stamped ? reinterpret_cast<const double*>(sc.dev.p + sc.o_pose)
+                             : reinterpret_cast<const double*>(sc.dev.p + sc.o_hum) + (Th - 1) * (size_t)sc.N * 2;
         aa.pose_stride = sc.stamped ? (size_t)sc.N * 2 : Th * (size_t)sc.N * 2;
         aa.forecasts = reinterpret_cast<double*>(dev + o_fc);
         aa.logw = reinterpret_cast<double*>(dev + o_lwd);
@@ -191,12 +172,11 @@ struct GridBlock {
     size_t o_hum, o_rob, o_pose, end;
 };
 GridBlock grid_block(int E, int N, int F) {
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     GridBlock gb{};
     gb.o_hum = 0;
-    gb.o_rob = up((size_t)E * F * N * 2 * 8);
-    gb.o_pose = gb.o_rob + up((size_t)E * F * 2 * 8);
-    gb.end = gb.o_pose + up((size_t)E * N * 2 * 8);
+    gb.o_rob = align_up((size_t)E * F * N * 2 * 8);
+    gb.o_pose = gb.o_rob + align_up((size_t)E * F * 2 * 8);
+    gb.end = gb.o_pose + align_up((size_t)E * N * 2 * 8);
     return gb;
 }
 
@@ -213,55 +193,49 @@ int check_scene_dims(jmid_ctx* h, const char* who, int N, int F, const double* c
 // jmid_build_scene and jmid_build_scene_stamped after their argument checks and order_in: the grid into the scene workspace, scene_kernel, the
 // small outputs to the caller (`mem` says where they live), one synchronisation.  src 0: human_xy / robot_xy are host arrays; 1: device
 // arrays; 2: human_xy is a device GridBlock (grid + pose_now, as frames_kernel left it) and robot_xy is unused.
-int build_scene_resident(jmid_ctx* h, int E, int N, int F, const double* human_xy, const double* robot_xy, int src, double time_step, int horizon,
+int build_scene_resident(jmid_ctx* h, const char* who, int E, int N, int F, const double* human_xy, const double* robot_xy, int src, double time_step, int horizon,
                          int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem) {
     const bool host = mem == JMID_MEM_HOST;
     const size_t rows = (size_t)E * N, b_hum = rows * F * 2 * 8, b_rob = (size_t)E * F * 2 * 8, b_cv = cv_out ? rows * horizon * 2 * 8 : 0;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const GridBlock gb = grid_block(E, N, F);
     // the grid | the resident arrays | the download block: n_in, in_cluster, robot_in_cluster, cv
-    const size_t o_x = gb.end, o_xst = o_x + up(rows * F * 6 * 4),
-                 o_nbr = o_xst + up(rows * F * 6 * 4), o_em = o_nbr + up(rows * 2 * F * 6 * 4), o_p0 = o_em + up(rows * 2 * 4), o_nin = o_p0 + up(rows * 2 * 4),
-                 o_inc = o_nin + up((size_t)E * 4), o_rin = o_inc + up(rows), o_cv = o_rin + up((size_t)E), need = o_cv + up(b_cv), b_out = need - o_nin;
+    const size_t o_x = gb.end, o_xst = o_x + align_up(rows * F * 6 * 4),
+                 o_nbr = o_xst + align_up(rows * F * 6 * 4), o_em = o_nbr + align_up(rows * 2 * F * 6 * 4), o_p0 = o_em + align_up(rows * 2 * 4), o_nin = o_p0 + align_up(rows * 2 * 4),
+                 o_inc = o_nin + align_up((size_t)E * 4), o_rin = o_inc + align_up(rows), o_cv = o_rin + align_up((size_t)E), need = o_cv + align_up(b_cv), b_out = need - o_nin;
     jmid_ctx::SceneWs& sc = h->scene;
     sc.E = 0;                     // no scene is resident until this call has succeeded
-    if (need > sc.bytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (sc.dev) HIPCHK(h, hipFree(sc.dev));
-        sc.dev = nullptr;
-        sc.bytes = 0;
-        if (hipMalloc((void**)&sc.dev, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_build_scene: workspace allocation failed");
-        sc.bytes = need;
-    }
+    if (int rc = sc.dev.reserve(h, need, who)) return rc;
+    char* const dev = sc.dev.p;
     SceneArgs g{};
     g.E = E; g.N = N; g.F = F; g.horizon = horizon; g.force_all = force_all_in_cluster ? 1 : 0;
     g.dt = time_step;
-    g.human_xy = reinterpret_cast<const double*>(sc.dev + gb.o_hum);
-    g.robot_xy = reinterpret_cast<const double*>(sc.dev + gb.o_rob);
-    g.x = reinterpret_cast<float*>(sc.dev + o_x); g.x_st = reinterpret_cast<float*>(sc.dev + o_xst);
-    g.nbr_sum = reinterpret_cast<float*>(sc.dev + o_nbr); g.edge_mask = reinterpret_cast<float*>(sc.dev + o_em);
-    g.p0 = reinterpret_cast<float*>(sc.dev + o_p0);
-    g.n_in = reinterpret_cast<int*>(sc.dev + o_nin);
-    g.in_cluster = reinterpret_cast<unsigned char*>(sc.dev + o_inc);
-    g.robot_in = reinterpret_cast<unsigned char*>(sc.dev + o_rin);
-    g.cv = cv_out ? reinterpret_cast<double*>(sc.dev + o_cv) : nullptr;
+    g.human_xy = reinterpret_cast<const double*>(dev + gb.o_hum);
+    g.robot_xy = reinterpret_cast<const double*>(dev + gb.o_rob);
+    g.x = reinterpret_cast<float*>(dev + o_x); g.x_st = reinterpret_cast<float*>(dev + o_xst);
+    g.nbr_sum = reinterpret_cast<float*>(dev + o_nbr); g.edge_mask = reinterpret_cast<float*>(dev + o_em);
+    g.p0 = reinterpret_cast<float*>(dev + o_p0);
+    g.n_in = reinterpret_cast<int*>(dev + o_nin);
+    g.in_cluster = reinterpret_cast<unsigned char*>(dev + o_inc);
+    g.robot_in = reinterpret_cast<unsigned char*>(dev + o_rin);
+    g.cv = cv_out ? reinterpret_cast<double*>(dev + o_cv) : nullptr;
     const size_t pin_in = src == 0 ? gb.o_pose : 0;       // host arrays are staged: human_xy | robot_xy
-    if (int rc = ensure_pin(h, pin_in + (host ? b_out : (size_t)E * 4), "jmid_build_scene")) return rc;
+    if (int rc = h->pin.reserve(h, pin_in + (host ? b_out : (size_t)E * 4), who)) return rc;
+    char* const pin = h->pin.p;
     if (src == 0) {
-        std::memcpy(h->pin + gb.o_hum, human_xy, b_hum);
-        std::memcpy(h->pin + gb.o_rob, robot_xy, b_rob);
-        HIPCHK(h, hipMemcpyAsync(sc.dev, h->pin, pin_in, hipMemcpyHostToDevice, h->stream));
+        std::memcpy(pin + gb.o_hum, human_xy, b_hum);
+        std::memcpy(pin + gb.o_rob, robot_xy, b_rob);
+        HIPCHK(h, hipMemcpyAsync(dev, pin, pin_in, hipMemcpyHostToDevice, h->stream));
     } else if (src == 1) {
-        HIPCHK(h, hipMemcpyAsync(sc.dev + gb.o_hum, human_xy, b_hum, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(sc.dev + gb.o_rob, robot_xy, b_rob, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dev + gb.o_hum, human_xy, b_hum, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dev + gb.o_rob, robot_xy, b_rob, hipMemcpyDeviceToDevice, h->stream));
     } else {
-        HIPCHK(h, hipMemcpyAsync(sc.dev, human_xy, gb.end, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dev, human_xy, gb.end, hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCHK(h, launch_scene(g, h->stream));
     sc.n_in.resize(E);
-    char* pout = h->pin + pin_in;
+    char* pout = pin + pin_in;
     if (host) {
-        HIPCHK(h, hipMemcpyAsync(pout, sc.dev + o_nin, b_out, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pout, dev + o_nin, b_out, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
         std::memcpy(n_in_out, pout, (size_t)E * 4);
@@ -336,22 +310,35 @@ int noise_entry(jmid_handle_t h, const char* who, uint64_t seed, int E, int rows
     const size_t n = (size_t)rows * T * 2;
     if (!noise_fits(n)) return fail(h, JMID_EINVAL, w + ": rows * T exceeds the noise addressing");
     HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = order_in(h, mem)) return rc;
-    if (int rc = upload_noise_ids(h, episode_ids, E)) return rc;
-    void* dst = out ? (void*)out : (void*)words;
-    if (mem == JMID_MEM_HOST) {      // staged in the handle's second workspace (the arena may hold the last call's positions)
-        if (int rc = ensure_kde_ws(h, (size_t)E * n * 4, who)) return rc;
-        dst = h->kde_ws;
-    }
-    if (int rc = fill_noise(h, seed, h->noise_ids, E, n, draw, out ? (float*)dst : nullptr, words ? (unsigned*)dst : nullptr, h->stream)) return rc;
-    if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(out ? (void*)out : (void*)words, dst, (size_t)E * n * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return order_out(h, mem);
+    char* dst = nullptr;             // host mode: staged in the handle's second workspace (the arena may hold the last call's positions)
+    Staging st(h, mem, h->kde_ws, who);
+    st.out(&dst, out ? (char*)out : (char*)words, (size_t)E * n * 4);
+    if (int rc = st.begin()) return rc;
+    if (int rc = h->noise_ids.upload(h, episode_ids, E, who)) return rc;
+    if (int rc = fill_noise(h, seed, h->noise_ids.get<unsigned>(), E, n, draw, out ? (float*)dst : nullptr, words ? (unsigned*)dst : nullptr, h->stream)) return rc;
+    return st.end();
 }
 
 }  // namespace jmid_host
+
+// What the handle created, and only that: a handle that never created anything (jmid_dbg_plan_chunks_mode builds one on the stack) makes
+// no HIP call here.  The member owners (the workspaces, the id / count arrays) free themselves after this body.
+jmid_ctx::~jmid_ctx() {
+    drop_graphs(this);
+    free_weights(this);
+    for (int c = 0; c < KC_COUNT; ++c) ev_pool.insert(ev_pool.end(), prof_ev[c].begin(), prof_ev[c].end());
+    for (auto& ev : ev_pool) {
+        hipEventDestroy(ev.a);
+        hipEventDestroy(ev.b);
+    }
+    for (int l = 0; l < kMaxLanes - 1; ++l) {
+        if (lane_stream[l]) hipStreamDestroy(lane_stream[l]);
+        if (ev_join[l]) hipEventDestroy(ev_join[l]);
+    }
+    if (stream) hipStreamDestroy(stream);
+    for (hipEvent_t e : {ev_in, ev_out, ev_fork})
+        if (e) hipEventDestroy(e);
+}
 
 // ================================================================================================ C ABI
 extern "C" {
@@ -416,7 +403,7 @@ int jmid_create(jmid_handle_t* out, int device_id, int net_kind, int ctx_dim, in
         ok = hipStreamCreateWithFlags(&h->lane_stream[l], hipStreamNonBlocking) == hipSuccess &&
              hipEventCreateWithFlags(&h->ev_join[l], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
-        delete h;
+        delete h;       // (~jmid_ctx: the streams and events that do exist)
         return fail(nullptr, JMID_EHIP, "cannot create a HIP stream");
     }
     // compute units of this device (or of its partition): the kernels whose workgroups wait for each other launch only when all of
@@ -428,50 +415,10 @@ int jmid_create(jmid_handle_t* out, int device_id, int net_kind, int ctx_dim, in
 }
 
 int jmid_destroy(jmid_handle_t h) {
-    if (h) {
-        if (h->pin) (void)hipHostFree(h->pin);
-        if (h->io_dev) (void)hipFree(h->io_dev);
-        h->pin = h->io_dev = nullptr;
-    }
     if (!h) return JMID_OK;
     hipSetDevice(h->device);
     sync_lanes(h);
     drop_graphs(h);
-    free_planes(h);
-    for (auto& kv : h->w) hipFree(kv.second.p);
-    if (h->range_flag) hipFree(h->range_flag);
-    if (h->ev_in) hipEventDestroy(h->ev_in);
-    if (h->ev_out) hipEventDestroy(h->ev_out);
-    for (float* p : {h->pe, h->ppe, h->Whyp, h->bhyp, h->thyp, h->attW1T, h->attW2T})
-        if (p) hipFree(p);
-    for (auto& l : h->lstmT)
-        for (float* p : l)
-            if (p) hipFree(p);
-    if (h->arena) hipFree(h->arena);
-    if (h->kde_ws) hipFree(h->kde_ws);
-    if (h->scene.dev) hipFree(h->scene.dev);
-    if (h->noise_ids) hipFree(h->noise_ids);
-    if (h->noise_ids_pin) (void)hipHostFree(h->noise_ids_pin);
-    if (h->ev_ids) hipEventDestroy(h->ev_ids);
-    if (h->nag_dev) hipFree(h->nag_dev);
-    if (h->nag_pin) (void)hipHostFree(h->nag_pin);
-    if (h->ev_nag) hipEventDestroy(h->ev_nag);
-    if (h->frames_dev) hipFree(h->frames_dev);
-    for (int c = 0; c < KC_COUNT; ++c)
-        for (auto& ev : h->prof_ev[c]) {
-            hipEventDestroy(ev.a);
-            hipEventDestroy(ev.b);
-        }
-    for (auto& ev : h->ev_pool) {
-        hipEventDestroy(ev.a);
-        hipEventDestroy(ev.b);
-    }
-    hipStreamDestroy(h->stream);
-    for (int l = 0; l < jmid_ctx::kMaxLanes - 1; ++l) {
-        hipStreamDestroy(h->lane_stream[l]);
-        hipEventDestroy(h->ev_join[l]);
-    }
-    hipEventDestroy(h->ev_fork);
     delete h;
     return JMID_OK;
 }
@@ -481,7 +428,7 @@ int jmid_denoise_ddpm(jmid_handle_t h, int E, int A, int K, int T, const float* 
     if (!h) return JMID_EINVAL;
     if (!z) return fail(h, JMID_EINVAL, "null z");
     DenoiseCall c{E, A, K, T, precision, mem};
-    c.x_in = x_T; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.z = z;
+    c.x_in = x_T; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.z = z; c.who = "jmid_denoise_ddpm";
     return run_network(h, c);
 }
 
@@ -491,42 +438,20 @@ int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* n
     if (!h->finalized) return fail(h, JMID_ENOWEIGHT, "jmid_finalize_weights has not been called");
     if (n_agents <= 0 || !x_st || !nbr_sum || !edge_mask || !ctx_out) return fail(h, JMID_EINVAL, "bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = order_in(h, mem)) return rc;
-    const int Th = h->hist_len, H = h->H;
-    const size_t n = n_agents;
-    const float *xs = x_st, *ns = nbr_sum, *em = edge_mask;
-    float* co = ctx_out;
-    if (mem == JMID_MEM_HOST) {
-        Carver c0(nullptr);
-        c0.take(n * Th * 6); c0.take(n * 2 * Th * 6); c0.take(n * 2); c0.take(n * 2 * H);
-        if (int rc = ensure_arena(h, c0.off)) return rc;
-        h->last_pos = nullptr;        // the staging buffers below overwrite the workspace the last positions live in
-        Carver c(h->arena);
-        float* dx = c.take(n * Th * 6);
-        float* dn = c.take(n * 2 * Th * 6);
-        float* de = c.take(n * 2);
-        co = c.take(n * 2 * H);
-        HIPCHK(h, hipMemcpyAsync(dx, x_st, n * Th * 6 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(dn, nbr_sum, n * 2 * Th * 6 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(de, edge_mask, n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        xs = dx; ns = dn; em = de;
-    }
+    const size_t n = n_agents, Th = h->hist_len;
+    EncArgs ea = encoder_args(h, nullptr, nullptr, nullptr, nullptr, n_agents);
+    if (mem == JMID_MEM_HOST) h->last_pos = nullptr;      // the staging below overwrites the workspace the last positions live in
+    Staging st(h, mem, h->arena, "jmid_encode");
+    st.in(&ea.x_st, x_st, n * Th * 6);
+    st.in(&ea.nbr_sum, nbr_sum, n * 2 * Th * 6);
+    st.in(&ea.edge_mask, edge_mask, n * 2);
+    st.out(&ea.ctx, ctx_out, n * 2 * h->H);
+    if (int rc = st.begin()) return rc;
     {
         ProfScope ps(h, KC_ENCODER, h->stream);
-        EncArgs ea{};
-        ea.x_st = xs; ea.nbr_sum = ns; ea.edge_mask = em;
-        ea.hist = LstmW{h->lstmT[0][0], h->lstmT[0][1], h->lstmT[0][2]};
-        ea.edge[0] = LstmW{h->lstmT[1][0], h->lstmT[1][1], h->lstmT[1][2]};
-        ea.edge[1] = LstmW{h->lstmT[2][0], h->lstmT[2][1], h->lstmT[2][2]};
-        ea.W1T = h->attW1T; ea.W2T = h->attW2T; ea.v = h->wt.edge_v;
-        ea.ctx = co; ea.n = n_agents; ea.Th = Th; ea.H = H;
         HIPCHK(h, launch_encoder(ea, h->stream));
     }
-    if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(ctx_out, co, n * 2 * H * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return order_out(h, mem);
+    return st.end();
 }
 
 int jmid_denoise(jmid_handle_t h, int E, int A, int K, int T, const float* x_T, const float* ctx, const float* p0,
@@ -544,7 +469,7 @@ int jmid_net_eval(jmid_handle_t h, int E, int A, int K, int T, int step_idx, con
     if (int rc = check_ready(h)) return rc;
     if (step_idx < 0 || step_idx >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "step_idx out of range");
     DenoiseCall c{E, A, K, T, precision, mem};
-    c.x_in = x; c.ctx = ctx; c.e_out = e_out; c.single_step = step_idx;
+    c.x_in = x; c.ctx = ctx; c.e_out = e_out; c.single_step = step_idx; c.who = "jmid_net_eval";
     return run_network(h, c);
 }
 
@@ -556,7 +481,7 @@ int jmid_net_eval_padded(jmid_handle_t h, int E, int A, int K, int T, const int3
     if (int rc = check_ready(h)) return rc;
     if (step_idx < 0 || step_idx >= (int)h->beta.size()) return fail(h, JMID_EINVAL, "step_idx out of range");
     DenoiseCall c{E, A, K, T, precision, mem};
-    c.x_in = x; c.ctx = ctx; c.e_out = e_out; c.single_step = step_idx; c.n_agents = n_agents;
+    c.x_in = x; c.ctx = ctx; c.e_out = e_out; c.single_step = step_idx; c.n_agents = n_agents; c.who = "jmid_net_eval_padded";
     return run_network(h, c);
 }
 
@@ -565,7 +490,7 @@ int jmid_denoise_padded(jmid_handle_t h, int E, int A, int K, int T, const int32
     if (!h) return JMID_EINVAL;
     if (!n_agents) return fail(h, JMID_EINVAL, "jmid_denoise_padded: null n_agents");
     DenoiseCall c{E, A, K, T, precision, mem};
-    c.x_in = x_T; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.n_agents = n_agents;
+    c.x_in = x_T; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.n_agents = n_agents; c.who = "jmid_denoise_padded";
     return run_network(h, c);
 }
 
@@ -573,29 +498,16 @@ int jmid_episode_metrics(jmid_handle_t h, int E, int A, int K, int T, const floa
                          float* out, int mem) {
     if (!h || !pos || !gt || !out || E <= 0 || A <= 0 || K <= 0 || T <= 0) return fail(h, JMID_EINVAL, "bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = order_in(h, mem)) return rc;
-    const size_t np_ = (size_t)E * K * A * T * 2, ng = (size_t)E * A * T * 2;
-    const float *dp = pos, *dg = gt;
-    float* dout = out;
-    if (mem == JMID_MEM_HOST) {
-        Carver c0(nullptr);
-        c0.take(np_); c0.take(ng); c0.take((size_t)E * 4);
-        if (int rc = ensure_arena(h, c0.off)) return rc;
-        h->last_pos = nullptr;        // (as in jmid_encode)
-        Carver c(h->arena);
-        float* a = c.take(np_);
-        float* b = c.take(ng);
-        dout = c.take((size_t)E * 4);
-        HIPCHK(h, hipMemcpyAsync(a, pos, np_ * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(b, gt, ng * 4, hipMemcpyHostToDevice, h->stream));
-        dp = a; dg = b;
-    }
+    const float *dp, *dg;
+    float* dout;
+    if (mem == JMID_MEM_HOST) h->last_pos = nullptr;      // (as in jmid_encode)
+    Staging st(h, mem, h->arena, "jmid_episode_metrics");
+    st.in(&dp, pos, (size_t)E * K * A * T * 2);
+    st.in(&dg, gt, (size_t)E * A * T * 2);
+    st.out(&dout, out, (size_t)E * 4);
+    if (int rc = st.begin()) return rc;
     if (int rc = launch_episode_metrics(h, dp, dg, dout, E, K, A, T)) return rc;
-    if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)E * 4 * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return order_out(h, mem);
+    return st.end();
 }
 
 int jmid_eval_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt, float* agent_out,
@@ -605,39 +517,20 @@ int jmid_eval_statistics(jmid_handle_t h, int E, int A, int K, int T, const floa
     if ((size_t)E * A > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, "jmid_eval_statistics: E * A exceeds the launch grid");
     HIPCHK(h, hipSetDevice(h->device));
     if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
-    if (int rc = order_in(h, mem)) return rc;
-    const size_t n_pos = (size_t)E * K * A * T * 2, n_gt = (size_t)E * A * T * 2, n_ag = (size_t)E * A * EVS_AGENT_COLS,
-                 n_sc = scene_out ? (size_t)E * EVS_SCENE_COLS : 0;
     EvalStatsArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T;
-    g.pos = pos ? pos : h->last_pos;
-    g.gt = gt; g.agent_out = agent_out; g.scene_out = scene_out;
-    if (mem == JMID_MEM_HOST) {
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t o_gt = 0, o_ag = o_gt + up(n_gt * 4), o_sc = o_ag + up(n_ag * 4), o_pos = o_sc + up(n_sc * 4),
-                     need = o_pos + (pos ? up(n_pos * 4) : 0);
-        if (int rc = ensure_kde_ws(h, need, "jmid_eval_statistics")) return rc;
-        float* dg = reinterpret_cast<float*>(h->kde_ws + o_gt);
-        HIPCHK(h, hipMemcpyAsync(dg, gt, n_gt * 4, hipMemcpyHostToDevice, h->stream));
-        g.gt = dg;
-        if (pos) {
-            float* dp = reinterpret_cast<float*>(h->kde_ws + o_pos);
-            HIPCHK(h, hipMemcpyAsync(dp, pos, n_pos * 4, hipMemcpyHostToDevice, h->stream));
-            g.pos = dp;
-        }
-        g.agent_out = reinterpret_cast<float*>(h->kde_ws + o_ag);
-        if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
-    }
+    Staging st(h, mem, h->kde_ws, "jmid_eval_statistics");
+    st.in(&g.gt, gt, (size_t)E * A * T * 2);
+    if (pos) st.in(&g.pos, pos, (size_t)E * K * A * T * 2);
+    else g.pos = h->last_pos;
+    st.out(&g.agent_out, agent_out, (size_t)E * A * EVS_AGENT_COLS);
+    if (scene_out) st.out(&g.scene_out, scene_out, (size_t)E * EVS_SCENE_COLS);
+    if (int rc = st.begin()) return rc;
     {
         ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_eval_stats(g, h->stream));
     }
-    if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(agent_out, g.agent_out, n_ag * 4, hipMemcpyDeviceToHost, h->stream));
-        if (scene_out) HIPCHK(h, hipMemcpyAsync(scene_out, g.scene_out, n_sc * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return order_out(h, mem);
+    return st.end();
 }
 
 int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* gt,
@@ -655,49 +548,22 @@ int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, con
     }
     HIPCHK(h, hipSetDevice(h->device));
     if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
-    if (int rc = order_in(h, mem)) return rc;
-    const size_t n_pos = (size_t)E * K * A * T * 2, n_gt = (size_t)E * A * T * 2, n_ag = (size_t)E * A * EVS_MASKED_AGENT_COLS,
-                 n_ct = (size_t)E * A * n_cut * EVS_CUT_COLS, n_sc = scene_out ? (size_t)E * EVS_SCENE_COLS : 0,
-                 n_if = (size_t)E * A * T, n_sk = skip ? (size_t)E * A : 0;
     g.E = E; g.A = A; g.K = K; g.T = T; g.n_cut = n_cut;
-    g.pos = pos ? pos : h->last_pos;
-    g.gt = gt; g.interp = interp_future; g.skip = skip;
-    g.agent_out = agent_out; g.cut_out = n_cut ? cut_out : nullptr; g.scene_out = scene_out;
-    if (mem == JMID_MEM_HOST) {
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t o_gt = 0, o_ag = o_gt + up(n_gt * 4), o_ct = o_ag + up(n_ag * 4), o_sc = o_ct + up(n_ct * 4), o_if = o_sc + up(n_sc * 4),
-                     o_sk = o_if + up(n_if), o_pos = o_sk + up(n_sk), need = o_pos + (pos ? up(n_pos * 4) : 0);
-        if (int rc = ensure_kde_ws(h, need, "jmid_eval_statistics_masked")) return rc;
-        float* dg = reinterpret_cast<float*>(h->kde_ws + o_gt);
-        unsigned char* di = reinterpret_cast<unsigned char*>(h->kde_ws + o_if);
-        HIPCHK(h, hipMemcpyAsync(dg, gt, n_gt * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(di, interp_future, n_if, hipMemcpyHostToDevice, h->stream));
-        g.gt = dg; g.interp = di;
-        if (skip) {
-            unsigned char* ds = reinterpret_cast<unsigned char*>(h->kde_ws + o_sk);
-            HIPCHK(h, hipMemcpyAsync(ds, skip, n_sk, hipMemcpyHostToDevice, h->stream));
-            g.skip = ds;
-        }
-        if (pos) {
-            float* dp = reinterpret_cast<float*>(h->kde_ws + o_pos);
-            HIPCHK(h, hipMemcpyAsync(dp, pos, n_pos * 4, hipMemcpyHostToDevice, h->stream));
-            g.pos = dp;
-        }
-        g.agent_out = reinterpret_cast<float*>(h->kde_ws + o_ag);
-        if (n_cut) g.cut_out = reinterpret_cast<float*>(h->kde_ws + o_ct);
-        if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
-    }
+    Staging st(h, mem, h->kde_ws, "jmid_eval_statistics_masked");
+    st.in(&g.gt, gt, (size_t)E * A * T * 2);
+    st.in(&g.interp, interp_future, (size_t)E * A * T);
+    if (skip) st.in(&g.skip, skip, (size_t)E * A);
+    if (pos) st.in(&g.pos, pos, (size_t)E * K * A * T * 2);
+    else g.pos = h->last_pos;
+    st.out(&g.agent_out, agent_out, (size_t)E * A * EVS_MASKED_AGENT_COLS);
+    if (n_cut) st.out(&g.cut_out, cut_out, (size_t)E * A * n_cut * EVS_CUT_COLS);
+    if (scene_out) st.out(&g.scene_out, scene_out, (size_t)E * EVS_SCENE_COLS);
+    if (int rc = st.begin()) return rc;
     {
         ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_eval_stats_masked(g, h->stream));
     }
-    if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(agent_out, g.agent_out, n_ag * 4, hipMemcpyDeviceToHost, h->stream));
-        if (n_cut) HIPCHK(h, hipMemcpyAsync(cut_out, g.cut_out, n_ct * 4, hipMemcpyDeviceToHost, h->stream));
-        if (scene_out) HIPCHK(h, hipMemcpyAsync(scene_out, g.scene_out, n_sc * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return order_out(h, mem);
+    return st.end();
 }
 
 int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, double threshold, float* pair_out,
@@ -711,46 +577,24 @@ int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const
     if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, "jmid_collision_statistics: E * K exceeds the launch grid");
     HIPCHK(h, hipSetDevice(h->device));
     if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
-    if (int rc = order_in(h, mem)) return rc;
-    const size_t P = (size_t)A * (A - 1) / 2, n_pos = (size_t)E * K * A * T * 2, n_pr = pair_out ? (size_t)E * K * P : 0,
-                 n_ag = agent_out ? (size_t)E * K * A : 0, n_sm = sample_out ? (size_t)E * K * CLS_SAMPLE_COLS : 0,
-                 n_sc = scene_out ? (size_t)E * CLS_SCENE_COLS : 0;
-    const bool host = mem == JMID_MEM_HOST;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    // the per-sample fp64 values the scene kernel reduces, then (host mode) the staging copies of the outputs and of pos
-    const size_t o_ws = 0, o_pr = o_ws + up((size_t)E * K * CLS_WS_COLS * 8), o_ag = o_pr + (host ? up(n_pr * 4) : 0),
-                 o_sm = o_ag + (host ? up(n_ag) : 0), o_sc = o_sm + (host ? up(n_sm * 4) : 0), o_pos = o_sc + (host ? up(n_sc * 4) : 0),
-                 need = o_pos + (host && pos ? up(n_pos * 4) : 0);
-    if (int rc = ensure_kde_ws(h, need, "jmid_collision_statistics")) return rc;
+    const size_t P = (size_t)A * (A - 1) / 2;
     CollisionStatsArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T;
     g.threshold = threshold;
-    g.pos = pos ? pos : h->last_pos;
-    g.ws = reinterpret_cast<double*>(h->kde_ws + o_ws);
-    g.pair_out = pair_out; g.agent_out = agent_out; g.sample_out = sample_out; g.scene_out = scene_out;
-    if (host) {
-        if (pos) {
-            float* dp = reinterpret_cast<float*>(h->kde_ws + o_pos);
-            HIPCHK(h, hipMemcpyAsync(dp, pos, n_pos * 4, hipMemcpyHostToDevice, h->stream));
-            g.pos = dp;
-        }
-        if (pair_out) g.pair_out = reinterpret_cast<float*>(h->kde_ws + o_pr);
-        if (agent_out) g.agent_out = reinterpret_cast<unsigned char*>(h->kde_ws + o_ag);
-        if (sample_out) g.sample_out = reinterpret_cast<float*>(h->kde_ws + o_sm);
-        if (scene_out) g.scene_out = reinterpret_cast<float*>(h->kde_ws + o_sc);
-    }
+    Staging st(h, mem, h->kde_ws, "jmid_collision_statistics");
+    st.scratch(&g.ws, (size_t)E * K * CLS_WS_COLS * 8);      // the per-sample fp64 values the scene kernel reduces
+    if (pos) st.in(&g.pos, pos, (size_t)E * K * A * T * 2);
+    else g.pos = h->last_pos;
+    if (pair_out) st.out(&g.pair_out, pair_out, (size_t)E * K * P);
+    if (agent_out) st.out(&g.agent_out, agent_out, (size_t)E * K * A);
+    if (sample_out) st.out(&g.sample_out, sample_out, (size_t)E * K * CLS_SAMPLE_COLS);
+    if (scene_out) st.out(&g.scene_out, scene_out, (size_t)E * CLS_SCENE_COLS);
+    if (int rc = st.begin()) return rc;
     {
         ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_collision_stats(g, h->stream));
     }
-    if (host) {
-        if (n_pr) HIPCHK(h, hipMemcpyAsync(pair_out, g.pair_out, n_pr * 4, hipMemcpyDeviceToHost, h->stream));
-        if (n_ag) HIPCHK(h, hipMemcpyAsync(agent_out, g.agent_out, n_ag, hipMemcpyDeviceToHost, h->stream));
-        if (n_sm) HIPCHK(h, hipMemcpyAsync(sample_out, g.sample_out, n_sm * 4, hipMemcpyDeviceToHost, h->stream));
-        if (n_sc) HIPCHK(h, hipMemcpyAsync(scene_out, g.scene_out, n_sc * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return order_out(h, mem);
+    return st.end();
 }
 
 // jmid_topk (n_agents null) and jmid_topk_padded
@@ -761,50 +605,21 @@ static int topk_entry(jmid_handle_t h, int E, int A, int K, int T, int k, const 
     if (A > 32 || K > 1024 || T > 24) return fail(h, JMID_EINVAL, "jmid_topk supports A <= 32, K <= 1024, T <= 24");
     HIPCHK(h, hipSetDevice(h->device));
     if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
-    if (int rc = order_in(h, mem)) return rc;
-    const int d = 2 * A;
-    const size_t n_pos = (size_t)E * K * A * T * 2, n_sel = (size_t)E * A * k * T * 2, n_lw = (size_t)E * A * k;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    // the global buffer of whitened points only when they do not fit in LDS (E = 64, T = 12, K = 1024, A = 32 would be 400 MB)
-    const size_t y_bytes = kde_y_in_lds(A, K) ? 0 : up((size_t)E * T * K * d * 8);
-    const size_t o_ll = 0, o_Y = up((size_t)E * T * K * 8), o_bw = o_Y + y_bytes, o_pos = o_bw + up(T * 4),
-                 o_sel = o_pos + (pos && mem == JMID_MEM_HOST ? up(n_pos * 4) : 0), o_lw = o_sel + (mem == JMID_MEM_HOST ? up(n_sel * 4) : 0),
-                 need = o_lw + (mem == JMID_MEM_HOST ? up(n_lw * 4) : 0);
-    if (int rc = ensure_kde_ws(h, need, "jmid_topk")) return rc;
-    KdeArgs g{};
-    g.E = E; g.A = A; g.K = K; g.T = T; g.k = k;
-    if (n_agents) {
-        if (int rc = upload_n_agents(h, n_agents, E)) return rc;
-        g.n_agents = h->nag_dev;
-    }
-    g.ll = reinterpret_cast<double*>(h->kde_ws + o_ll);
-    g.Y = reinterpret_cast<double*>(h->kde_ws + o_Y);
-    g.pos = pos ? pos : h->last_pos;
-    g.sel = sel; g.logw = logw;
-    if (bw) {
-        float* dbw = reinterpret_cast<float*>(h->kde_ws + o_bw);
-        HIPCHK(h, hipMemcpyAsync(dbw, bw, T * sizeof(float), mem == JMID_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-        g.bw = dbw;
-    }
-    if (mem == JMID_MEM_HOST) {
-        if (pos) {
-            float* dp = reinterpret_cast<float*>(h->kde_ws + o_pos);
-            HIPCHK(h, hipMemcpyAsync(dp, pos, n_pos * 4, hipMemcpyHostToDevice, h->stream));
-            g.pos = dp;
-        }
-        g.sel = reinterpret_cast<float*>(h->kde_ws + o_sel);
-        g.logw = reinterpret_cast<float*>(h->kde_ws + o_lw);
-    }
-    {
-        ProfScope ps(h, KC_TOPK, h->stream);
-        HIPCHK(h, launch_kde(g, h->stream));
-    }
-    if (mem == JMID_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(sel, g.sel, n_sel * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(logw, g.logw, n_lw * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return order_out(h, mem);
+    const char* who = n_agents ? "jmid_topk_padded" : "jmid_topk";
+    const float *dpos = h->last_pos, *dbw = nullptr;
+    float *dsel, *dlw;
+    char* ws;
+    Staging st(h, mem, h->kde_ws, who);
+    st.scratch(&ws, kde_workspace(E, A, K, T, nullptr, nullptr));
+    if (bw) st.in(&dbw, bw, (size_t)T, true);      // (bw has always gone through the workspace, in device mode too: the entry enqueues what it did)
+    if (pos) st.in(&dpos, pos, (size_t)E * K * A * T * 2);
+    st.out(&dsel, sel, (size_t)E * A * k * T * 2);
+    st.out(&dlw, logw, (size_t)E * A * k);
+    if (int rc = st.begin()) return rc;
+    if (n_agents)
+        if (int rc = h->nag.upload(h, n_agents, E, who)) return rc;
+    if (int rc = topk_on_device(h, who, E, A, K, T, k, dpos, dbw, dsel, dlw, n_agents ? h->nag.get<int>() : nullptr, ws)) return rc;
+    return st.end();
 }
 
 int jmid_topk(jmid_handle_t h, int E, int A, int K, int T, int k, const float* pos, const float* bw, float* sel, float* logw,
@@ -842,15 +657,17 @@ static int predict_entry(jmid_handle_t h, int E, int A, int K, int T, int k, con
                          float* logw, float* pos_out) {
     if (!h) return JMID_EINVAL;
     if (int rc = check_ready(h)) return rc;
-    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, "jmid_predict: bad dimensions");
-    if (!x_st || !nbr_sum || !edge_mask || !x_T || !p0) return fail(h, JMID_EINVAL, "jmid_predict: null input");
+    const char* who = n_agents ? "jmid_predict_padded" : "jmid_predict";
+    const std::string w(who);
+    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, w + ": bad dimensions");
+    if (!x_st || !nbr_sum || !edge_mask || !x_T || !p0) return fail(h, JMID_EINVAL, w + ": null input");
     const bool rank = k < K;
-    if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, "jmid_predict: k < K needs sel and logw");
-    if (!rank && !pos_out) return fail(h, JMID_EINVAL, "jmid_predict: k == K needs pos_out");
-    if (rank && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, "jmid_predict: the device top-k supports A <= 32, K <= 1024, T <= 24");
-    if (h->ddpm) return fail(h, JMID_EINVAL, "jmid_predict samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
+    if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, w + ": k < K needs sel and logw");
+    if (!rank && !pos_out) return fail(h, JMID_EINVAL, w + ": k == K needs pos_out");
+    if (rank && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, w + ": the device top-k supports A <= 32, K <= 1024, T <= 24");
+    if (h->ddpm) return fail(h, JMID_EINVAL, w + " samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
     HIPCHK(h, hipSetDevice(h->device));
-    return predict_chain(h, E, A, K, T, k, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out, false, "jmid_predict", nullptr, nullptr,
+    return predict_chain(h, E, A, K, T, k, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out, false, who, nullptr, nullptr,
                          nullptr, n_agents);
 }
 
@@ -861,7 +678,7 @@ int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_x
     if (int rc = check_scene_dims(h, "jmid_build_scene", N, F, cv_out, horizon, time_step)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
-    if (int rc = build_scene_resident(h, E, N, F, human_xy, robot_xy, mem == JMID_MEM_HOST ? 0 : 1, time_step, horizon, force_all_in_cluster,
+    if (int rc = build_scene_resident(h, "jmid_build_scene", E, N, F, human_xy, robot_xy, mem == JMID_MEM_HOST ? 0 : 1, time_step, horizon, force_all_in_cluster,
                                       in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem))
         return rc;
     return order_out(h, mem);
@@ -886,22 +703,14 @@ int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double*
                 return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: n_frames[" + std::to_string(e) + "] = " + std::to_string(n_frames[e]) + " is outside 1..R");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t b_st = (size_t)E * R * 8, b_hum = (size_t)E * R * N * 2 * 8, b_rob = (size_t)E * R * 2 * 8, b_nf = n_frames ? (size_t)E * 4 : 0;
     const GridBlock gb = grid_block(E, N, F);
     // the grid block frames_kernel writes | n_grid | the staged raw frames (host mode): stamps, human_xy, robot_xy, n_frames
-    const size_t o_ng = gb.end, o_st = o_ng + up((size_t)E * 4), o_rh = o_st + (host ? up(b_st) : 0), o_rr = o_rh + (host ? up(b_hum) : 0),
-                 o_nf = o_rr + (host ? up(b_rob) : 0), need = o_nf + (host ? up(b_nf) : 0), raw = need - o_st;
-    if (need > h->frames_bytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->frames_dev) HIPCHK(h, hipFree(h->frames_dev));
-        h->frames_dev = nullptr;
-        h->frames_bytes = 0;
-        if (hipMalloc((void**)&h->frames_dev, need) != hipSuccess) return fail(h, JMID_ENOMEM, "jmid_build_scene_stamped: workspace allocation failed");
-        h->frames_bytes = need;
-    }
-    if (int rc = ensure_pin(h, raw + (size_t)E * 4, "jmid_build_scene_stamped")) return rc;
-    char* fd = h->frames_dev;
+    const size_t o_ng = gb.end, o_st = o_ng + align_up((size_t)E * 4), o_rh = o_st + (host ? align_up(b_st) : 0), o_rr = o_rh + (host ? align_up(b_hum) : 0),
+                 o_nf = o_rr + (host ? align_up(b_rob) : 0), need = o_nf + (host ? align_up(b_nf) : 0), raw = need - o_st;
+    if (int rc = h->frames_dev.reserve(h, need, "jmid_build_scene_stamped")) return rc;
+    if (int rc = h->pin.reserve(h, raw + (size_t)E * 4, "jmid_build_scene_stamped")) return rc;
+    char *const fd = h->frames_dev.p, *const pin = h->pin.p;
     FramesArgs f{};
     f.E = E; f.N = N; f.R = R; f.F = F;
     f.w = (long long)wd;
@@ -909,17 +718,17 @@ int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double*
     f.o_human = reinterpret_cast<double*>(fd + gb.o_hum); f.o_robot = reinterpret_cast<double*>(fd + gb.o_rob);
     f.o_pose = reinterpret_cast<double*>(fd + gb.o_pose); f.o_n_grid = reinterpret_cast<int*>(fd + o_ng);
     if (host) {
-        std::memcpy(h->pin, stamps, b_st);
-        std::memcpy(h->pin + (o_rh - o_st), human_xy, b_hum);
-        std::memcpy(h->pin + (o_rr - o_st), robot_xy, b_rob);
-        if (n_frames) std::memcpy(h->pin + (o_nf - o_st), n_frames, b_nf);
-        HIPCHK(h, hipMemcpyAsync(fd + o_st, h->pin, raw, hipMemcpyHostToDevice, h->stream));
+        std::memcpy(pin, stamps, b_st);
+        std::memcpy(pin + (o_rh - o_st), human_xy, b_hum);
+        std::memcpy(pin + (o_rr - o_st), robot_xy, b_rob);
+        if (n_frames) std::memcpy(pin + (o_nf - o_st), n_frames, b_nf);
+        HIPCHK(h, hipMemcpyAsync(fd + o_st, pin, raw, hipMemcpyHostToDevice, h->stream));
         f.stamps = reinterpret_cast<const double*>(fd + o_st); f.human_xy = reinterpret_cast<const double*>(fd + o_rh);
         f.robot_xy = reinterpret_cast<const double*>(fd + o_rr);
         f.n_frames = n_frames ? reinterpret_cast<const int*>(fd + o_nf) : nullptr;
     }
     HIPCHK(h, launch_frames(f, h->stream));
-    int* ng = reinterpret_cast<int*>(h->pin + raw);
+    int* ng = reinterpret_cast<int*>(pin + raw);
     HIPCHK(h, hipMemcpyAsync(ng, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToHost, h->stream));
     if (!host) HIPCHK(h, hipMemcpyAsync(n_grid_out, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -936,7 +745,7 @@ int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double*
             return fail(h, JMID_EHISTORY, "jmid_build_scene_stamped: episode " + std::to_string(e) + " has " + std::to_string(got) +
                                               " history frames on the time_step grid, " + std::to_string(F) + " needed");
         }
-    if (int rc = build_scene_resident(h, E, N, F, reinterpret_cast<const double*>(fd), nullptr, 2, time_step, horizon, force_all_in_cluster,
+    if (int rc = build_scene_resident(h, "jmid_build_scene_stamped", E, N, F, reinterpret_cast<const double*>(fd), nullptr, 2, time_step, horizon, force_all_in_cluster,
                                       in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem))
         return rc;
     return order_out(h, mem);
@@ -950,12 +759,12 @@ int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_x
     if (int rc = order_in(h, mem)) return rc;
     const size_t F = h->hist_len, row = (size_t)sc.N * 2 * 8;
     const hipMemcpyKind kind = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (human_xy_out) HIPCHK(h, hipMemcpyAsync(human_xy_out, sc.dev + sc.o_hum, (size_t)sc.E * F * row, kind, h->stream));
-    if (robot_xy_out) HIPCHK(h, hipMemcpyAsync(robot_xy_out, sc.dev + sc.o_rob, (size_t)sc.E * F * 2 * 8, kind, h->stream));
+    if (human_xy_out) HIPCHK(h, hipMemcpyAsync(human_xy_out, sc.dev.p + sc.o_hum, (size_t)sc.E * F * row, kind, h->stream));
+    if (robot_xy_out) HIPCHK(h, hipMemcpyAsync(robot_xy_out, sc.dev.p + sc.o_rob, (size_t)sc.E * F * 2 * 8, kind, h->stream));
     if (pose_now_out) {
-        if (sc.stamped) HIPCHK(h, hipMemcpyAsync(pose_now_out, sc.dev + sc.o_pose, (size_t)sc.E * row, kind, h->stream));
+        if (sc.stamped) HIPCHK(h, hipMemcpyAsync(pose_now_out, sc.dev.p + sc.o_pose, (size_t)sc.E * row, kind, h->stream));
         else            // the last frame of every episode's grid
-            HIPCHK(h, hipMemcpy2DAsync(pose_now_out, row, sc.dev + sc.o_hum + (F - 1) * row, F * row, row, sc.E, kind, h->stream));
+            HIPCHK(h, hipMemcpy2DAsync(pose_now_out, row, sc.dev.p + sc.o_hum + (F - 1) * row, F * row, row, sc.E, kind, h->stream));
     }
     if (mem == JMID_MEM_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
     return order_out(h, mem);
@@ -969,11 +778,11 @@ int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float
     if (int rc = order_in(h, mem)) return rc;
     const size_t rows = (size_t)sc.E * sc.N, F = h->hist_len;
     const hipMemcpyKind kind = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (x) HIPCHK(h, hipMemcpyAsync(x, sc.dev + sc.o_x, rows * F * 6 * 4, kind, h->stream));
-    if (x_st) HIPCHK(h, hipMemcpyAsync(x_st, sc.dev + sc.o_xst, rows * F * 6 * 4, kind, h->stream));
-    if (nbr_sum) HIPCHK(h, hipMemcpyAsync(nbr_sum, sc.dev + sc.o_nbr, rows * 2 * F * 6 * 4, kind, h->stream));
-    if (edge_mask) HIPCHK(h, hipMemcpyAsync(edge_mask, sc.dev + sc.o_em, rows * 2 * 4, kind, h->stream));
-    if (p0) HIPCHK(h, hipMemcpyAsync(p0, sc.dev + sc.o_p0, rows * 2 * 4, kind, h->stream));
+    if (x) HIPCHK(h, hipMemcpyAsync(x, sc.dev.p + sc.o_x, rows * F * 6 * 4, kind, h->stream));
+    if (x_st) HIPCHK(h, hipMemcpyAsync(x_st, sc.dev.p + sc.o_xst, rows * F * 6 * 4, kind, h->stream));
+    if (nbr_sum) HIPCHK(h, hipMemcpyAsync(nbr_sum, sc.dev.p + sc.o_nbr, rows * 2 * F * 6 * 4, kind, h->stream));
+    if (edge_mask) HIPCHK(h, hipMemcpyAsync(edge_mask, sc.dev.p + sc.o_em, rows * 2 * 4, kind, h->stream));
+    if (p0) HIPCHK(h, hipMemcpyAsync(p0, sc.dev.p + sc.o_p0, rows * 2 * 4, kind, h->stream));
     if (mem == JMID_MEM_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
     return order_out(h, mem);
 }
@@ -1008,7 +817,7 @@ int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t se
     if (!episode_ids) return fail(h, JMID_EINVAL, "jmid_denoise_seeded: null episode_ids");
     const SeedArgs sa{seed, episode_ids};
     DenoiseCall c{E, A, K, T, precision, mem};
-    c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.seeded = &sa;
+    c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.seeded = &sa; c.who = "jmid_denoise_seeded";
     return run_network(h, c);
 }
 

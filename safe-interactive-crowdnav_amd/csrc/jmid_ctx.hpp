@@ -6,6 +6,8 @@
 //   jmid_planner.hip  chunk plan, step workspace, one net evaluation (net_step), the call plan and the phases of a denoise call (run_network)
 //   jmid_profile.hip  per-kernel-class HIP-event profiling
 //   jmid_diag.hip     jmid_dbg_* single-kernel entry points (-DJMID_DIAGNOSTICS only)
+//   host_mem.hpp      align_up / Carver, the owning Block (device or pinned) every workspace of the handle is, HostArray, Staging
+// Whatever the handle owns is released by ~jmid_ctx: jmid_destroy and a jmid_create that fails half way both end in `delete h`.
 #pragma once
 #include "../../include/jmid_hip.h"
 
@@ -98,6 +100,26 @@ struct WeightTable {
     const float* edge_v = nullptr;               // PEDESTRIAN/edge_influence_encoder.v.weight (the encoder kernel)
 };
 
+struct jmid_ctx;
+namespace jmid_host {
+
+std::string& thread_error();      // the last error of this thread (jmid_last_error(NULL))
+int fail(jmid_ctx* h, int code, const std::string& msg);
+
+#define HIPCHK(h, expr)                                                                               \
+    do {                                                                                              \
+        hipError_t e__ = (expr);                                                                      \
+        if (e__ != hipSuccess)                                                                        \
+            return fail(h, JMID_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));            \
+    } while (0)
+
+int ensure_arena(jmid_ctx* h, size_t bytes, const char* who);      // jmid_planner.hip
+int order_in(jmid_ctx* h, int mem);
+int order_out(jmid_ctx* h, int mem);
+
+}  // namespace jmid_host
+#include "host_mem.hpp"
+
 struct jmid_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -125,18 +147,14 @@ struct jmid_ctx {
     // jmid_topk ranks and jmid_eval_statistics scores when they are given no pos pointer
     const float* last_pos = nullptr;
     int last_pos_dims[4] = {0, 0, 0, 0};     // E, A, K, T
-    char* kde_ws = nullptr;                  // jmid_topk's and jmid_eval_statistics' own workspace (it must not move the arena last_pos points into)
-    size_t kde_ws_bytes = 0;
+    jmid_host::Block kde_ws;                 // jmid_topk's and the statistics entries' own workspace (it must not move the arena last_pos points into)
     // jmid_predict: pinned host staging + device I/O buffers of the chained call, grown on demand
-    char* pin = nullptr;
-    size_t pin_bytes = 0;
-    char* io_dev = nullptr;
-    size_t io_dev_bytes = 0;
+    jmid_host::Block pin{jmid_host::MEM_PINNED};
+    jmid_host::Block io_dev;
     // jmid_build_scene: the scene batch it left on the device (padded [E, N, ...] rows; jmid_scene_get copies them out, jmid_predict_scene
     // gathers the in-cluster rows), in a workspace of its own - no other entry point touches it
     struct SceneWs {
-        char* dev = nullptr;
-        size_t bytes = 0;
+        jmid_host::Block dev;
         int E = 0, N = 0;            // E = 0: no scene is resident
         size_t o_x = 0, o_xst = 0, o_nbr = 0, o_em = 0, o_p0 = 0, o_inc = 0;   // byte offsets of the resident arrays
         std::vector<int> n_in;       // [E] in-cluster pedestrians per episode (host copy)
@@ -149,18 +167,9 @@ struct jmid_ctx {
     } scene;
     // jmid_build_scene_stamped: the raw frames and what frames_kernel made of them (grid, pose_now, n_grid), in a workspace of its own:
     // a build that ends with JMID_EHISTORY must not touch the resident scene
-    char* frames_dev = nullptr;
-    size_t frames_bytes = 0;
-    // the seeded entry points: the call's episode ids on the device (the fill kernel reads them there), grown on demand
-    unsigned* noise_ids = nullptr;
-    int noise_ids_cap = 0;
-    unsigned* noise_ids_pin = nullptr;       // pinned staging of the ids: a device-mode call may return before its copies have run, and the
-    hipEvent_t ev_ids = nullptr;             // caller's array need not outlive the call; ev_ids = the last upload has left the staging
-    // the padded entry points: the call's agent counts on the device, with their pinned staging (as the episode ids above)
-    int* nag_dev = nullptr;
-    int nag_cap = 0;
-    int* nag_pin = nullptr;
-    hipEvent_t ev_nag = nullptr;
+    jmid_host::Block frames_dev;
+    // the seeded entry points: the call's episode ids on the device (the fill kernel reads them there); the padded ones: its agent counts
+    jmid_host::HostArray noise_ids, nag;
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)
     bool lnx_off = false;       // a workgroup of that kernel once gave up waiting for a partner (range flag bit 1): the handle stays on GEMM + add_ln2
@@ -193,9 +202,7 @@ struct jmid_ctx {
     bool ddpm = false;
     std::vector<float> p_c0, p_c1, p_sigma;
     std::vector<int> p_noise;
-    // workspace arena
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
+    jmid_host::Block arena;     // the workspace of the denoise call (grown by ensure_arena only)
     // I/O staging
     int chunk_eps = 0;
     // profiling
@@ -205,11 +212,19 @@ struct jmid_ctx {
     double prof_ms[KC_COUNT] = {0};
     int64_t prof_n[KC_COUNT] = {0};
     std::string err;
+    jmid_ctx() = default;
+    jmid_ctx(const jmid_ctx&) = delete;
+    ~jmid_ctx();                // everything above that was created; nothing for a handle that never created anything (jmid_abi.hip)
 };
 
 constexpr size_t kLnxWords = 2 * jmid::SM_LNX_GRANULES;      // 32-bit words of the exchange granules (8 bytes each) of the small-launch GEMM + LayerNorm per step workspace (gemm_small.hpp, OUT_LNX)
 
 namespace jmid_host {
+
+inline hipStream_t stream_of(jmid_ctx* h) { return h->stream; }
+inline int reserve_block(jmid_ctx* h, Block& b, size_t need, const char* who) {
+    return &b == &h->arena ? ensure_arena(h, need, who) : b.reserve(h, need, who);
+}
 
 // The arithmetic mode of one call, made from its `precision` argument by call_mode - the one place that says which precisions exist -
 // and passed down by value: the step plan holds it, the rules that run before a step plan take it as a parameter.
@@ -228,16 +243,6 @@ inline bool call_mode(int precision, CallMode* m) {
     *m = CallMode{precision, precision != JMID_PREC_F32, x2, mx, !x2 ? GM_X3 : mx ? GM_MX : GM_X2};
     return true;
 }
-
-std::string& thread_error();      // the last error of this thread (jmid_last_error(NULL))
-int fail(jmid_ctx* h, int code, const std::string& msg);
-
-#define HIPCHK(h, expr)                                                                               \
-    do {                                                                                              \
-        hipError_t e__ = (expr);                                                                      \
-        if (e__ != hipSuccess)                                                                        \
-            return fail(h, JMID_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));            \
-    } while (0)
 
 struct ProfScope {
     jmid_ctx* h;
@@ -265,17 +270,6 @@ struct ProfScope {
     }
 };
 
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(char* b) : base(b) {}
-    float* take(size_t nfloats) {
-        float* p = reinterpret_cast<float*>(base ? base + off : nullptr);
-        off += ((nfloats * sizeof(float) + 255) / 256) * 256;
-        return p;
-    }
-};
-
 inline size_t numel(const std::vector<size_t>& s) {
     size_t n = 1;
     for (size_t v : s) n *= v;
@@ -288,21 +282,20 @@ int dev_alloc_copy(jmid_ctx* h, float** out, const std::vector<float>& host);
 int fetch_host(jmid_ctx* h, const std::string& name, std::vector<float>& out);
 int upload_time_table(jmid_ctx* h);
 int make_w8(jmid_ctx* h, const float* dW, int N, int K, jmid_ctx::W8Image* out);
+int w8_image(jmid_ctx* h, const float* dW, int N, int K, unsigned char* out);      // ... into a buffer of the caller's (N K bytes)
 void free_planes(jmid_ctx* h);
+void free_derived(jmid_ctx* h);     // the buffers jmid_finalize_weights derives from the weights
+void free_weights(jmid_ctx* h);     // the planes, the derived buffers, the weights themselves, the step table and the range flag
 // jmid_planner.hip
 void drop_graphs(jmid_ctx* h);
 void sync_lanes(jmid_ctx* h);
-int ensure_arena(jmid_ctx* h, size_t bytes);
 std::vector<int> plan_chunks(const jmid_ctx* h, const CallMode& m, int E, int tokens_per_episode);
 int check_ready(jmid_ctx* h);
-int order_in(jmid_ctx* h, int mem);
-int order_out(jmid_ctx* h, int mem);
 // seeded noise of a call (noise.hpp): x_T is draw 0 and the z of step-table entry i draw i + 1, filled on the device; `ids` [E] is a HOST array
 struct SeedArgs {
     uint64_t seed;
     const uint32_t* ids;
 };
-int upload_noise_ids(jmid_ctx* h, const uint32_t* ids, int E);      // -> h->noise_ids, on h->stream
 int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream);
 // One denoise call (or, with single_step >= 0, one net evaluation -> e_out) as its entry point states it
 struct DenoiseCall {
@@ -317,11 +310,11 @@ struct DenoiseCall {
     // a padded call (padded.hpp): HOST array [E], 1 <= n_agents[e] <= A - episode e has n_agents[e] real agents, the rows of the others
     // are zeroed on entry and NaN in every output; JMID attention takes the key-mask words.  DDIM with the caller's x_T only.
     const int32_t* n_agents = nullptr;
+    const char* who = "jmid_denoise";     // the entry point that was called (error texts)
 };
 // the counts of a padded call: checked by its entry before anything is enqueued (JMID_EINVAL: null, or a count outside 1..A), then
-// uploaded to h->nag_dev on h->stream
+// uploaded through h->nag on h->stream
 int check_n_agents(jmid_ctx* h, const char* who, const int32_t* n_agents, int E, int A);
-int upload_n_agents(jmid_ctx* h, const int32_t* n_agents, int E);
 int run_network(jmid_ctx* h, DenoiseCall a);      // (by value: its host inputs become their uploads)
 int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in, const float* hyp, int hyp_width, int step, int precision,
              float* out, float* thyp_row);      // jmid_dbg_qkv0 (tail = false) / jmid_dbg_tail: -DJMID_DIAGNOSTICS only

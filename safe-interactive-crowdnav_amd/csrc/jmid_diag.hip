@@ -2,6 +2,8 @@
 #include "jmid_ctx.hpp"
 #include "jmid_launch.hpp"
 
+#include <deque>
+
 #ifdef JMID_DIAGNOSTICS
 // ---------------------------------------------------------------------------------------------- diagnostics
 // Single-op entry points used by the unit tests (host buffers only).
@@ -15,6 +17,37 @@ static int dbg_open(jmid_ctx* h, int precision, CallMode* mode) {
         HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
     }
     return 0;
+}
+
+// The device temporaries of one jmid_dbg_* call: local owners, so every exit frees them.  take(): `bytes` of device memory holding
+// `host`'s bytes (host null: uninitialised), or null with the error set
+struct DbgTemps {
+    jmid_ctx* h;
+    const char* who;
+    std::deque<Block> blocks;
+    int rc = 0;                    // the first failure: the caller looks once, after its takes
+    template <class T>
+    T* take(size_t bytes, const void* host = nullptr) {
+        if (rc) return nullptr;
+        blocks.emplace_back();
+        Block& b = blocks.back();
+        if ((rc = b.reserve(h, bytes, who))) return nullptr;
+        const hipError_t e = host ? hipMemcpy(b.p, host, bytes, hipMemcpyHostToDevice) : hipSuccess;
+        if (e != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+        return rc ? nullptr : b.as<T>();
+    }
+    template <class T>
+    T* zeros(size_t bytes) {       // ... zero-filled, on the handle's stream
+        T* p = take<T>(bytes);
+        if (p && hipMemsetAsync(p, 0, bytes, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": memset failed");
+        return rc ? nullptr : p;
+    }
+};
+// the bf8 image of W_lo (what make_w8 gives the weight registry), as a temporary
+static unsigned char* dbg_w8(DbgTemps& t, const float* dW, int N, int K) {
+    unsigned char* p = t.take<unsigned char>((size_t)N * K);
+    if (p) t.rc = w8_image(t.h, dW, N, K, p);
+    return t.rc ? nullptr : p;
 }
 
 extern "C" {
@@ -59,31 +92,21 @@ int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const fl
     if (!h || !A || !Wt || !C) return JMID_EINVAL;
     CallMode mode;
     if (int rc = dbg_open(h, precision, &mode)) return rc;
-    float *dA, *dW, *dB = nullptr, *dC;
-    HIPCHK(h, hipMalloc((void**)&dA, (size_t)M * K * 4));
-    HIPCHK(h, hipMalloc((void**)&dW, (size_t)N * K * 4));
-    HIPCHK(h, hipMalloc((void**)&dC, (size_t)M * N * 4));
-    HIPCHK(h, hipMemcpy(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dW, Wt, (size_t)N * K * 4, hipMemcpyHostToDevice));
-    if (bias) {
-        HIPCHK(h, hipMalloc((void**)&dB, (size_t)N * 4));
-        HIPCHK(h, hipMemcpy(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice));
-    }
+    DbgTemps t{h, "jmid_dbg_gemm"};
+    float* dA = t.take<float>((size_t)M * K * 4, A);
+    float* dW = t.take<float>((size_t)N * K * 4, Wt);
+    float* dC = t.take<float>((size_t)M * N * 4);
+    float* dB = bias ? t.take<float>((size_t)N * 4, bias) : nullptr;
+    if (t.rc) return t.rc;
     int rc = 0;
-    half_t *ah = nullptr, *al = nullptr, *wh = nullptr, *wl = nullptr;
-    jmid_ctx::W8Image w8img;
     if (precision == JMID_PREC_F32) {
         GemmArgs g{};
         g.A = dA; g.lda = K; g.W = dW; g.ldw = K; g.bias = dB; g.C = dC; g.ldc = N; g.M = M; g.N = N; g.K = K;
         rc = relu ? run_gemm<EPI_BIAS_RELU>(h, h->stream, KC_GEMM_QKV, g) : run_gemm<EPI_BIAS>(h, h->stream, KC_GEMM_QKV, g);
     } else {
         const size_t pa = blk_plane_elems(M, K) * 2, pw = blk_plane_elems(N, K) * 2;
-        HIPCHK(h, hipMalloc((void**)&ah, pa));
-        HIPCHK(h, hipMalloc((void**)&al, pa));
-        HIPCHK(h, hipMalloc((void**)&wh, pw));
-        HIPCHK(h, hipMalloc((void**)&wl, pw));
-        for (auto pr : {std::make_pair(ah, pa), std::make_pair(al, pa), std::make_pair(wh, pw), std::make_pair(wl, pw)})
-            HIPCHK(h, hipMemsetAsync(pr.first, 0, pr.second, h->stream));
+        half_t *ah = t.zeros<half_t>(pa), *al = t.zeros<half_t>(pa), *wh = t.zeros<half_t>(pw), *wl = t.zeros<half_t>(pw);
+        if (t.rc) return t.rc;
         hipLaunchKernelGGL(split_planes_blocked_kernel, dim3(512), dim3(256), 0, h->stream, dA, ah, al, M, K,
                            h->range_flag, 1.0f);
         hipLaunchKernelGGL(split_planes_blocked_kernel, dim3(512), dim3(256), 0, h->stream, dW, wh, wl, N, K,
@@ -91,25 +114,16 @@ int jmid_dbg_gemm(jmid_handle_t h, int M, int N, int K, const float* A, const fl
         GemmHArgs g{};
         g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.bias = dB; g.C = dC; g.ldc = N;
         g.M = M; g.N = N; g.K = K; g.x2 = mode.x2;
-        if (mode.mx && N % 32 == 0 && K % 64 == 0) {
-            if (int rc8 = make_w8(h, dW, N, K, &w8img)) return rc8;
-            g.W8 = w8img.p;
-        }
+        if (mode.mx && N % 32 == 0 && K % 64 == 0)
+            if (!(g.W8 = dbg_w8(t, dW, N, K))) return t.rc;
         // (an idle handle: nothing else in flight, one launch)
         const GemmPlan plan = plan_gemm(mode.gemm, relu ? EPI_BIAS_RELU : EPI_BIAS, OUT_F32, M, N, K, CallFacts{}, h->tune);
         rc = relu ? run_gemm_h<EPI_BIAS_RELU, OUT_F32>(h, h->stream, KC_GEMM_QKV, g, plan) : run_gemm_h<EPI_BIAS, OUT_F32>(h, h->stream, KC_GEMM_QKV, g, plan);
     }
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
-    }
-    if (!rc) HIPCHK(h, hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dW); hipFree(dC);
-    if (dB) hipFree(dB);
-    for (half_t* p : {ah, al, wh, wl})
-        if (p) hipFree(p);
-    if (w8img.p) hipFree(w8img.p);
-    return rc;
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int precision, float* OUT) {
@@ -118,12 +132,11 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
     if (int rc = dbg_open(h, precision, &mode)) return rc;
     const size_t Mt = (size_t)nseq * S;
     const int d = h->d, hd = h->d / h->nhead;
-    float *dQ, *dO;
-    HIPCHK(h, hipMalloc((void**)&dQ, Mt * 3 * d * 4));
-    HIPCHK(h, hipMalloc((void**)&dO, Mt * d * 4));
-    HIPCHK(h, hipMemcpy(dQ, QKV, Mt * 3 * d * 4, hipMemcpyHostToDevice));
+    DbgTemps t{h, "jmid_dbg_attention"};
+    float* dQ = t.take<float>(Mt * 3 * d * 4, QKV);
+    float* dO = t.take<float>(Mt * d * 4);
+    if (t.rc) return t.rc;
     int rc = 0;
-    std::vector<half_t*> tmp;
     if (precision == JMID_PREC_F32) {
         AttnArgs aa{dQ, dO, S, d, h->nhead, 1.0f / sqrtf((float)hd), nullptr, nullptr};
         ProfScope ps(h, KC_ATTN, h->stream);
@@ -134,21 +147,17 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
         const size_t vt = (size_t)nseq * d * Spad;
         half_t* b[8];
         const size_t sz[8] = {Mt * d, Mt * d, Mt * d, Mt * d, vt, vt, blk_plane_elems(Mt, d), blk_plane_elems(Mt, d)};
-        for (int i = 0; i < 8; ++i) {
-            HIPCHK(h, hipMalloc((void**)&b[i], sz[i] * sizeof(half_t)));
-            HIPCHK(h, hipMemsetAsync(b[i], 0, sz[i] * sizeof(half_t), h->stream));
-            tmp.push_back(b[i]);
-        }
+        for (int i = 0; i < 8; ++i) b[i] = t.zeros<half_t>(sz[i] * sizeof(half_t));
+        if (t.rc) return t.rc;
         hipLaunchKernelGGL(qkv_to_planes_kernel, dim3(512), dim3(256), 0, h->stream, dQ, b[0], b[1], b[2], b[3], b[4],
                            b[5], Mt, d, hd, S, Spad, 1.4426950408889634f / sqrtf((float)hd));
         int ns = 1;
         float *opart = nullptr, *mlpart = nullptr;
         if (hd == 128) ns = attn_pick_nsplit(((S + 127) / 128) * h->nhead * nseq, S);
         if (ns > 1) {
-            HIPCHK(h, hipMalloc((void**)&opart, (size_t)ns * Mt * d * 4));
-            HIPCHK(h, hipMalloc((void**)&mlpart, (size_t)ns * Mt * h->nhead * 2 * 4));
-            tmp.push_back(reinterpret_cast<half_t*>(opart));
-            tmp.push_back(reinterpret_cast<half_t*>(mlpart));
+            opart = t.take<float>((size_t)ns * Mt * d * 4);
+            mlpart = t.take<float>((size_t)ns * Mt * h->nhead * 2 * 4);
+            if (t.rc) return t.rc;
         }
         AttnHArgs aa{b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], S, Spad, d, h->nhead, 1.0f / sqrtf((float)hd),
                      h->range_flag, ns, opart, mlpart, mode.x2};
@@ -159,14 +168,10 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
         }
         hipLaunchKernelGGL(merge_planes_kernel, dim3(512), dim3(256), 0, h->stream, b[6], b[7], dO, (int)Mt, d);
     }
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
-    }
-    if (!rc) HIPCHK(h, hipMemcpy(OUT, dO, Mt * d * 4, hipMemcpyDeviceToHost));
-    hipFree(dQ); hipFree(dO);
-    for (half_t* p : tmp) hipFree(p);
-    return rc;
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(OUT, dO, Mt * d * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const float* Wt, const float* bias, const float* gamma,
@@ -177,50 +182,36 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
     constexpr int N = GLN_BN;
     CallMode mode;
     if (int rc = dbg_open(h, JMID_PREC_F16MX, &mode)) return rc;
-    std::vector<void*> tmp;
-    auto dalloc = [&](size_t bytes, const void* host) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        tmp.push_back(p);
-        if (host) (void)hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
-        else (void)hipMemsetAsync(p, 0, bytes, h->stream);
-        return p;
-    };
-    float* dA = (float*)dalloc((size_t)M * K * 4, A);
-    float* dW = (float*)dalloc((size_t)N * K * 4, Wt);
-    float* dB = (float*)dalloc(N * 4, bias);
-    float* dG = (float*)dalloc(N * 4, gamma);
-    float* dT = (float*)dalloc(N * 4, beta);
-    float* dX = (float*)dalloc((size_t)M * N * 4, X);
-    float* dY = (float*)dalloc((size_t)(M + 63) / 64 * 64 * N * 4, nullptr);
+    DbgTemps t{h, "jmid_dbg_gemm_ln_mx"};
+    float* dA = t.take<float>((size_t)M * K * 4, A);
+    float* dW = t.take<float>((size_t)N * K * 4, Wt);
+    float* dB = t.take<float>(N * 4, bias);
+    float* dG = t.take<float>(N * 4, gamma);
+    float* dT = t.take<float>(N * 4, beta);
+    float* dX = t.take<float>((size_t)M * N * 4, X);
+    float* dY = t.zeros<float>((size_t)(M + 63) / 64 * 64 * N * 4);
     const size_t pa = blk_plane_elems(M, K) * 2, pw = blk_plane_elems(N, K) * 2, px = blk_plane_elems(M, N) * 2;
-    half_t* ah = (half_t*)dalloc(pa, nullptr);
-    half_t* al = (half_t*)dalloc(pa, nullptr);
-    half_t* wh = (half_t*)dalloc(pw, nullptr);
-    half_t* wl = (half_t*)dalloc(pw, nullptr);
-    half_t* w16h = (half_t*)dalloc((size_t)N * K * 2, nullptr);
-    half_t* w16l = (half_t*)dalloc((size_t)N * K * 2, nullptr);
-    half_t* xh = (half_t*)dalloc(px, nullptr);
-    unsigned char* xl8 = (unsigned char*)dalloc(px, nullptr);
-    for (void* p : tmp)
-        if (!p) return fail(h, JMID_ENOMEM, "jmid_dbg_gemm_ln_mx: allocation failed");
+    half_t *ah = t.zeros<half_t>(pa), *al = t.zeros<half_t>(pa), *wh = t.zeros<half_t>(pw), *wl = t.zeros<half_t>(pw);
+    half_t *w16h = t.zeros<half_t>((size_t)N * K * 2), *w16l = t.zeros<half_t>((size_t)N * K * 2);
+    half_t* xh = t.zeros<half_t>(px);
+    unsigned char* xl8 = t.zeros<unsigned char>(px);
+    if (t.rc) return t.rc;
     hipLaunchKernelGGL(split_planes_blocked_kernel, dim3(512), dim3(256), 0, h->stream, dA, ah, al, M, K, h->range_flag, 1.0f);
     hipLaunchKernelGGL(split_planes_blocked_kernel, dim3(512), dim3(256), 0, h->stream, dW, wh, wl, N, K, h->range_flag, kWScale);
     hipLaunchKernelGGL(split_planes_k16_kernel, dim3(256), dim3(256), 0, h->stream, dW, w16h, w16l, N, K);
     hipLaunchKernelGGL(split_planes_lo8_kernel, dim3(512), dim3(256), 0, h->stream, dX, xh, xl8, M);
-    jmid_ctx::W8Image img;
-    if (int rc = make_w8(h, dW, N, K, &img)) return rc;
-    tmp.push_back(img.p);
+    unsigned char* w8 = dbg_w8(t, dW, N, K);
+    if (!w8) return t.rc;
     int rc = 0;
     if (fused == 1) {
-        GemmLn2Args g2{ah, w16h, img.p, dB, dG, dT, xh, xl8, M, K, 1e-5f, h->range_flag, 0};
+        GemmLn2Args g2{ah, w16h, w8, dB, dG, dT, xh, xl8, M, K, 1e-5f, h->range_flag, 0};
         hipError_t e = launch_gemm_ln2_mx(g2, plan_ln_rows(true, M, h->tune), h->stream);
         if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
     } else {
         GemmHArgs g{};
-        g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.W8 = img.p; g.bias = dB; g.C = dY; g.ldc = N; g.M = M; g.N = N; g.K = K; g.x2 = mode.x2;
+        g.Ahi = ah; g.Alo = al; g.Whi = wh; g.Wlo = wl; g.W8 = w8; g.bias = dB; g.C = dY; g.ldc = N; g.M = M; g.N = N; g.K = K; g.x2 = mode.x2;
         if (fused == 3) {        // the small-launch kernel with the statistics exchange (gemm_small.hpp, OUT_LNX)
-            unsigned long long* xs = (unsigned long long*)dalloc(kLnxWords * sizeof(unsigned), nullptr);
+            unsigned long long* xs = t.zeros<unsigned long long>(kLnxWords * sizeof(unsigned));
             const GemmPlan lnx = plan_gemm(GM_MX, EPI_BIAS, OUT_LNX, M, N, K, CallFacts{}, h->tune);      // (an idle handle: nothing else in flight, one launch)
             if (!xs || lnx.shape == GS_NONE) return fail(h, JMID_EINVAL, "jmid_dbg_gemm_ln_mx: shape does not take the small kernel with the statistics exchange");
             g.ln_gamma = dG; g.ln_beta = dT; g.ln_xh = xh; g.ln_xl = nullptr; g.ln_xl8 = xl8; g.ln_xchg = xs; g.ln_eps = 1e-5f; g.ln_no_lo = 0;
@@ -237,37 +228,27 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
             if (!rc) rc = run_add_ln(h, h->stream, nullptr, dY, dG, dT, M, N, xh, reinterpret_cast<half_t*>(xl8), true, 0);
         }
     }
-    if (!rc) {
-        hipLaunchKernelGGL(merge_planes_lo8_kernel, dim3(512), dim3(256), 0, h->stream, xh, xl8, dX, M);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
-    }
-    if (!rc) HIPCHK(h, hipMemcpy(X, dX, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    for (void* p : tmp) hipFree(p);
-    return rc;
+    if (rc) return rc;
+    hipLaunchKernelGGL(merge_planes_lo8_kernel, dim3(512), dim3(256), 0, h->stream, xh, xl8, dX, M);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(X, dX, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int jmid_dbg_add_layernorm(jmid_handle_t h, int M, int d, float* X, const float* Y, const float* gamma,
                            const float* beta) {
     if (!h || !X || !Y || !gamma || !beta) return JMID_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
-    float *dX, *dY, *dG, *dB;
-    HIPCHK(h, hipMalloc((void**)&dX, (size_t)M * d * 4));
-    HIPCHK(h, hipMalloc((void**)&dY, (size_t)M * d * 4));
-    HIPCHK(h, hipMalloc((void**)&dG, (size_t)d * 4));
-    HIPCHK(h, hipMalloc((void**)&dB, (size_t)d * 4));
-    HIPCHK(h, hipMemcpy(dX, X, (size_t)M * d * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dY, Y, (size_t)M * d * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dG, gamma, (size_t)d * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dB, beta, (size_t)d * 4, hipMemcpyHostToDevice));
-    int rc = run_add_ln(h, h->stream, dX, dY, dG, dB, M, d);
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
-    }
-    if (!rc) HIPCHK(h, hipMemcpy(X, dX, (size_t)M * d * 4, hipMemcpyDeviceToHost));
-    hipFree(dX); hipFree(dY); hipFree(dG); hipFree(dB);
-    return rc;
+    DbgTemps t{h, "jmid_dbg_add_layernorm"};
+    float* dX = t.take<float>((size_t)M * d * 4, X);
+    float* dY = t.take<float>((size_t)M * d * 4, Y);
+    float* dG = t.take<float>((size_t)d * 4, gamma);
+    float* dB = t.take<float>((size_t)d * 4, beta);
+    if (t.rc) return t.rc;
+    if (int rc = run_add_ln(h, h->stream, dX, dY, dG, dB, M, d)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(X, dX, (size_t)M * d * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, const float* hyp, int hyp_width, int step, int precision,

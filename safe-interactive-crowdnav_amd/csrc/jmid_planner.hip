@@ -17,20 +17,12 @@ void sync_lanes(jmid_ctx* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
 }
 
-int ensure_arena(jmid_ctx* h, size_t bytes) {
-    if (bytes <= h->arena_bytes) return 0;
+int ensure_arena(jmid_ctx* h, size_t bytes, const char* who) {
+    if (bytes <= h->arena.bytes) return 0;
     drop_graphs(h);
     h->last_pos = nullptr;
-    if (h->arena) {
-        sync_lanes(h);
-        HIPCHK(h, hipFree(h->arena));
-        h->arena = nullptr;
-        h->arena_bytes = 0;
-    }
-    hipError_t e = hipMalloc((void**)&h->arena, bytes);
-    if (e != hipSuccess) return fail(h, JMID_ENOMEM, "workspace allocation of " + std::to_string(bytes) + " bytes failed");
-    h->arena_bytes = bytes;
-    return 0;
+    sync_lanes(h);
+    return h->arena.reserve(h, bytes, who);
 }
 
 struct StepBuffers {
@@ -632,57 +624,11 @@ int check_ready(jmid_ctx* h) {
     return 0;
 }
 
-// The episode ids of a seeded call, from the caller's HOST array into the handle's device buffer, on h->stream (every fill of the call
-// is ordered behind it: the lanes fork from h->stream afterwards).
-int upload_noise_ids(jmid_ctx* h, const uint32_t* ids, int E) {
-    if (!h->ev_ids) HIPCHK(h, hipEventCreateWithFlags(&h->ev_ids, hipEventDisableTiming));
-    if (E > h->noise_ids_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->noise_ids) HIPCHK(h, hipFree(h->noise_ids));
-        if (h->noise_ids_pin) HIPCHK(h, hipHostFree(h->noise_ids_pin));
-        h->noise_ids = h->noise_ids_pin = nullptr;
-        h->noise_ids_cap = 0;
-        const int cap = std::max(E, 64);
-        if (hipMalloc((void**)&h->noise_ids, (size_t)cap * sizeof(unsigned)) != hipSuccess ||
-            hipHostMalloc((void**)&h->noise_ids_pin, (size_t)cap * sizeof(unsigned), hipHostMallocDefault) != hipSuccess)
-            return fail(h, JMID_ENOMEM, "episode id buffer allocation failed");
-        h->noise_ids_cap = cap;
-    } else {
-        HIPCHK(h, hipEventSynchronize(h->ev_ids));       // the previous upload has read the staging (an event never recorded is complete)
-    }
-    std::memcpy(h->noise_ids_pin, ids, (size_t)E * sizeof(unsigned));
-    HIPCHK(h, hipMemcpyAsync(h->noise_ids, h->noise_ids_pin, (size_t)E * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev_ids, h->stream));
-    return 0;
-}
-
 int check_n_agents(jmid_ctx* h, const char* who, const int32_t* n_agents, int E, int A) {
     if (!n_agents) return fail(h, JMID_EINVAL, std::string(who) + ": null n_agents");
     for (int e = 0; e < E; ++e)
         if (n_agents[e] < 1 || n_agents[e] > A)
             return fail(h, JMID_EINVAL, std::string(who) + ": n_agents[" + std::to_string(e) + "] = " + std::to_string(n_agents[e]) + " is outside 1..A");
-    return 0;
-}
-
-int upload_n_agents(jmid_ctx* h, const int32_t* n_agents, int E) {
-    if (!h->ev_nag) HIPCHK(h, hipEventCreateWithFlags(&h->ev_nag, hipEventDisableTiming));
-    if (E > h->nag_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->nag_dev) HIPCHK(h, hipFree(h->nag_dev));
-        if (h->nag_pin) HIPCHK(h, hipHostFree(h->nag_pin));
-        h->nag_dev = h->nag_pin = nullptr;
-        h->nag_cap = 0;
-        const int cap = std::max(E, 64);
-        if (hipMalloc((void**)&h->nag_dev, (size_t)cap * sizeof(int)) != hipSuccess ||
-            hipHostMalloc((void**)&h->nag_pin, (size_t)cap * sizeof(int), hipHostMallocDefault) != hipSuccess)
-            return fail(h, JMID_ENOMEM, "agent count buffer allocation failed");
-        h->nag_cap = cap;
-    } else {
-        HIPCHK(h, hipEventSynchronize(h->ev_nag));       // the previous upload has read the staging
-    }
-    std::memcpy(h->nag_pin, n_agents, (size_t)E * sizeof(int));
-    HIPCHK(h, hipMemcpyAsync(h->nag_dev, h->nag_pin, (size_t)E * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev_nag, h->stream));
     return 0;
 }
 
@@ -816,10 +762,10 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
     const size_t M = (size_t)a.E * a.K * a.A * a.T, EA = (size_t)a.E * a.A;
     const size_t io_off = call_io(h, a, cp, nullptr, nullptr);
     const size_t lane_floats = step_ws_floats(h, cp.Mc, cp.mode, cp.sg, cp.facts.attn_nsplit, nullptr, nullptr, cp.qkv0_rows, cp.tail_rows);
-    if (int rc = ensure_arena(h, io_off + cp.nlanes * lane_floats)) return rc;
-    call_io(h, a, cp, h->arena, &io);
+    if (int rc = ensure_arena(h, io_off + cp.nlanes * lane_floats, a.who)) return rc;
+    call_io(h, a, cp, h->arena.p, &io);
     for (int l = 0; l < cp.nlanes; ++l) {
-        step_ws_floats(h, cp.Mc, cp.mode, cp.sg, cp.facts.attn_nsplit, &cp.lanes[l], h->arena + io_off + l * lane_floats, cp.qkv0_rows, cp.tail_rows);
+        step_ws_floats(h, cp.Mc, cp.mode, cp.sg, cp.facts.attn_nsplit, &cp.lanes[l], h->arena.p + io_off + l * lane_floats, cp.qkv0_rows, cp.tail_rows);
         cp.lanes[l].z = cp.z_fill ? io.z_lane + (size_t)l * cp.Mc * 2 : nullptr;
     }
     if (io.z_up) {
@@ -839,8 +785,8 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
     }
     const hipMemcpyKind kin = a.mem == JMID_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (a.seeded) {
-        if (int rc = upload_noise_ids(h, a.seeded->ids, a.E)) return rc;
-        if (int rc = fill_noise(h, a.seeded->seed, h->noise_ids, a.E, (size_t)a.K * a.A * a.T * 2, 0, io.x_cur, nullptr, h->stream)) return rc;
+        if (int rc = h->noise_ids.upload(h, a.seeded->ids, a.E, a.who)) return rc;
+        if (int rc = fill_noise(h, a.seeded->seed, h->noise_ids.get<unsigned>(), a.E, (size_t)a.K * a.A * a.T * 2, 0, io.x_cur, nullptr, h->stream)) return rc;
     } else {
         HIPCHK(h, hipMemcpyAsync(io.x_cur, a.x_in, M * 2 * sizeof(float), kin, h->stream));
     }
@@ -855,11 +801,11 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
     if (cp.masked) {
         // the counts, the key-mask words from them, and zeros in the padded agents' rows of x_T, ctx and p0: whatever the caller left
         // there is never read.  All of it outside a captured loop, on memory the loop reads: a replay sees this call's counts.
-        if (int rc = upload_n_agents(h, a.n_agents, a.E)) return rc;
-        if (io.mask) HIPCHK(h, launch_mask_words(h->nag_dev, io.mask, a.E, a.A, a.T, a.K * a.A * a.T, h->stream));
-        HIPCHK(h, launch_pad_fill(io.x_cur, h->nag_dev, a.E, a.K, a.A, a.T * 2, 0.f, h->stream));
-        HIPCHK(h, launch_pad_fill(io.ctx, h->nag_dev, a.E, 1, a.A, h->ctx_dim, 0.f, h->stream));
-        if (a.p0) HIPCHK(h, launch_pad_fill(io.p0, h->nag_dev, a.E, 1, a.A, 2, 0.f, h->stream));
+        if (int rc = h->nag.upload(h, a.n_agents, a.E, a.who)) return rc;
+        if (io.mask) HIPCHK(h, launch_mask_words(h->nag.get<int>(), io.mask, a.E, a.A, a.T, a.K * a.A * a.T, h->stream));
+        HIPCHK(h, launch_pad_fill(io.x_cur, h->nag.get<int>(), a.E, a.K, a.A, a.T * 2, 0.f, h->stream));
+        HIPCHK(h, launch_pad_fill(io.ctx, h->nag.get<int>(), a.E, 1, a.A, h->ctx_dim, 0.f, h->stream));
+        if (a.p0) HIPCHK(h, launch_pad_fill(io.p0, h->nag.get<int>(), a.E, 1, a.A, 2, 0.f, h->stream));
     }
     // ---- ctx part of the four hyper nets, once per call (ctx is constant over the denoise steps)
     GemmArgs g{};
@@ -894,7 +840,7 @@ int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallI
         const std::string key = std::to_string(E) + "," + std::to_string(A) + "," + std::to_string(K) + "," + std::to_string(T) +
                                 "," + std::to_string(a.precision) + (cp.masked ? ",padded" : "");
         lg = &h->graphs[key];
-        if (lg->exec && lg->arena != h->arena) {        // never true today (ensure_arena drops the graphs); cheap to keep
+        if (lg->exec && lg->arena != h->arena.p) {        // never true today (ensure_arena drops the graphs); cheap to keep
             hipGraphExecDestroy(lg->exec);
             lg->exec = nullptr;
         }
@@ -918,7 +864,7 @@ int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallI
                 const float* zc = a.z ? a.z + ((size_t)i * M + el * tok) * 2 : nullptr;
                 int rc = 0;
                 if (cp.z_fill && h->p_noise[i]) {      // this step's draw for the chunk's episodes, on the chunk's own stream
-                    rc = fill_noise(h, a.seeded->seed, h->noise_ids + el, cp.chunk_sizes[c0 + l], tok * 2, i + 1, ln.z, nullptr, ln.stream);
+                    rc = fill_noise(h, a.seeded->seed, h->noise_ids.get<unsigned>() + el, cp.chunk_sizes[c0 + l], tok * 2, i + 1, ln.z, nullptr, ln.stream);
                     zc = ln.z;
                 }
                 // layer 0's coefficient table of this chunk for all steps, ahead of its first step, on the chunk's own stream
@@ -951,7 +897,7 @@ int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallI
             lg->exec = nullptr;
             return fail(h, JMID_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ge));
         }
-        lg->arena = h->arena;
+        lg->arena = h->arena.p;
         HIPCHK(h, hipGraphLaunch(lg->exec, h->stream));
         ++h->graph_replays;
     } else if (lg && !lg->exec) {
@@ -971,7 +917,7 @@ int finish_call(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const Cal
     }
     // a padded call: quiet NaN in the padded agents' rows of what it returns - and, through the integrator, of the resident positions
     const float qnan = std::numeric_limits<float>::quiet_NaN();
-    if (cp.masked) HIPCHK(h, launch_pad_fill(a.single_step >= 0 ? io.stage : io.x_cur, h->nag_dev, a.E, a.K, a.A, a.T * 2, qnan, h->stream));
+    if (cp.masked) HIPCHK(h, launch_pad_fill(a.single_step >= 0 ? io.stage : io.x_cur, h->nag.get<int>(), a.E, a.K, a.A, a.T * 2, qnan, h->stream));
     if (a.single_step >= 0) {
         HIPCHK(h, hipMemcpyAsync(a.e_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
     } else {
@@ -1055,11 +1001,11 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
         return c.off;
     };
     const size_t io_off = io(nullptr);
-    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, mode, p.sg, 1, nullptr, nullptr, qkv0_rows, tail_rows))) return rc;
-    io(h->arena);
+    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, mode, p.sg, 1, nullptr, nullptr, qkv0_rows, tail_rows), who.c_str())) return rc;
+    io(h->arena.p);
     Lane ln{};
     ln.stream = h->stream;
-    step_ws_floats(h, M, mode, p.sg, 1, &ln, h->arena + io_off, qkv0_rows, tail_rows);
+    step_ws_floats(h, M, mode, p.sg, 1, &ln, h->arena.p + io_off, qkv0_rows, tail_rows);
     HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
     if (!tail) {
         HIPCHK(h, hipMemsetAsync(ln.Vth, 0, ln.vt_elems * sizeof(half_t), h->stream));

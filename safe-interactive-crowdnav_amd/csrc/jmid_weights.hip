@@ -86,7 +86,10 @@ int upload_time_table(jmid_ctx* h) {
 // bf8 image of W_lo for a device-resident fp32 weight [N, K] (N % 32 == 0, K % 64 == 0)
 int make_w8(jmid_ctx* h, const float* dW, int N, int K, jmid_ctx::W8Image* out) {
     HIPCHK(h, hipMalloc((void**)&out->p, (size_t)N * K));
-    hipLaunchKernelGGL(w8_image_kernel, dim3(256), dim3(256), 0, h->stream, dW, out->p, N, K, kWScale);
+    return w8_image(h, dW, N, K, out->p);
+}
+int w8_image(jmid_ctx* h, const float* dW, int N, int K, unsigned char* out) {
+    hipLaunchKernelGGL(w8_image_kernel, dim3(256), dim3(256), 0, h->stream, dW, out, N, K, kWScale);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -103,6 +106,31 @@ void free_planes(jmid_ctx* h) {
     }
     for (auto& kv : h->w8) hipFree(kv.second.p);
     h->w8.clear();
+}
+
+void free_derived(jmid_ctx* h) {
+    for (float** p : {&h->pe, &h->ppe, &h->Whyp, &h->bhyp, &h->attW1T, &h->attW2T})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    for (auto& l : h->lstmT)
+        for (float*& p : l)
+            if (p) {
+                hipFree(p);
+                p = nullptr;
+            }
+}
+
+void free_weights(jmid_ctx* h) {
+    free_planes(h);
+    free_derived(h);
+    for (auto& kv : h->w) hipFree(kv.second.p);
+    h->w.clear();
+    for (void* p : {(void*)h->thyp, (void*)h->range_flag})
+        if (p) hipFree(p);
+    h->thyp = nullptr;
+    h->range_flag = nullptr;
 }
 
 }  // namespace jmid_host
@@ -134,17 +162,7 @@ int jmid_finalize_weights(jmid_handle_t h) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->finalized = false;       // from here on the derived buffers and the operand planes are freed and rebuilt
-    for (float** p : {&h->pe, &h->ppe, &h->Whyp, &h->bhyp, &h->attW1T, &h->attW2T})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    for (auto& l : h->lstmT)
-        for (float*& p : l)
-            if (p) {
-                hipFree(p);
-                p = nullptr;
-            }
+    free_derived(h);
     const int d = h->d, C = h->ctx_dim, CC = C + 3;
     // positional encoding table, max_len = kPeMaxLen (MID/models/common.py:37-51; diffusion.py:116-118)
     {
