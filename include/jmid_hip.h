@@ -463,6 +463,38 @@ int jmid_predict_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k
 int jmid_forecast_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
                                int precision, const float* bw, double* forecasts_out, double* logw_out);
 
+/* ---- the denoising loss on data with known futures: DiffusionTraj.get_loss (MID/models/diffusion.py:448-476), reached through
+ * AutoEncoder.get_loss (MID/models/autoencoder.py:105-122) from MID.validation() (MID/mid.py:252-296, its "Avg. Val Loss") - the
+ * noise-prediction MSE of ONE net evaluation per scene, every agent row at a timestep of its own.
+ *
+ * jmid_set_loss_schedule: the forward process per TIMESTEP: beta, c0 = sqrt(alpha_bar), c1 = sqrt(1 - alpha_bar) [n_t], index = timestep,
+ * entry 0 the reference's padding entry (n_t = num_steps + 1 = 101), c0 / c1 computed by the host in fp32 as diffusion.py:456-457 does.
+ * Builds the device time table [n_t, hyper width] with the expression of the sampler's step table: a timestep that is also a step of the
+ * installed DDIM table has identical bits.  Independent of jmid_set_ddim_table / jmid_set_ddpm_table (either order, any number of times);
+ * captured loops stay.
+ *
+ * jmid_loss: x0, e [E, A, T, 2] and ctx [E, A, ctx_dim] where `mem` says; t int32 [E, A] is always a HOST array, like n_agents, values
+ * 1 .. n_t - 1.  x_t = c0[t_r] x0 + c1[t_r] e (two rounded products, one rounded sum), e_theta = net(x_t, beta[t_r], ctx) with K = 1 - the
+ * row's timestep is folded into its hyper-net row once, the net's kernels are those of jmid_net_eval -, then per element (e_theta - e)^2
+ * in fp32 (F.mse_loss(reduction="none")) and fp64 sums in a fixed order (no atomics: the same bits for every chunk plan).
+ *   n_agents    int32 [E] HOST, or NULL when every row is real: a padded batch as jmid_net_eval_padded (generate_mask,
+ *               MID/dataset/preprocessing.py:35-89: padded agents are no attention keys and are dropped from the loss)
+ *   loss_out    double [2]: the mean squared error over the real rows' T * 2 components, the number of components
+ *   row_out     double [E, A] sum of squared errors per row, or NULL; NaN for padded rows
+ *   e_theta_out [E, A, T, 2] or NULL; NaN for padded rows
+ * (the three outputs where `mem` says).  JMID_NET_JMID and JMID_NET_IMID, every precision.  JMID_EINVAL before anything is enqueued: no
+ * loss schedule, a t outside 1 .. n_t - 1 (the message names the row), a count outside 1..A, a padded call on a non-default attention
+ * variant, T > 24, NULL t / x0 / e / ctx / loss_out.  JMID_ERANGE and JMID_ETIMEOUT as from jmid_net_eval.  Leaves no state on the handle
+ * (but, like jmid_net_eval, reuses the workspace of the resident positions).
+ *
+ * jmid_loss_seeded: the same with e drawn by the library - draw 0 of the counter generator with rows = A, the bits
+ * jmid_noise_fill(seed, E, A, T, episode_ids, 0) returns; t stays the caller's. */
+int jmid_set_loss_schedule(jmid_handle_t h, int n_t, const float* beta, const float* c0, const float* c1);
+int jmid_loss(jmid_handle_t h, int E, int A, int T, const int32_t* n_agents, const int32_t* t, const float* x0, const float* e, const float* ctx,
+              int precision, double* loss_out, double* row_out, float* e_theta_out, int mem);
+int jmid_loss_seeded(jmid_handle_t h, int E, int A, int T, const int32_t* n_agents, const int32_t* t, const float* x0, uint64_t seed,
+                     const uint32_t* episode_ids, const float* ctx, int precision, double* loss_out, double* row_out, float* e_theta_out, int mem);
+
 /* The stream (a hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream; NULL = the legacy default
  * stream) that produces the inputs and consumes the outputs of this handle's JMID_MEM_DEVICE calls - see Conventions. */
 int jmid_set_caller_stream(jmid_handle_t h, void* stream);

@@ -191,6 +191,10 @@ struct OutArgs {
     const float* z;      // [M, 2] normal draws of this step (nullptr for t == 1: zeros)
     int ddpm;
     float c0, c1, sigma;
+    // a loss call (loss.hpp): the time part of the output layer's bias per ROW [EA, 2], in place of thyp[boff ..] - the one place that
+    // adds the ctx and time parts to a running sum one after the other, where a timestep folded into hyp would round differently.  Null
+    // everywhere else
+    const float* tbo;
 };
 
 // The three pieces of the output stage of one token, shared by out_ddim_kernel (one wave per token, lane 0 updates) and
@@ -210,10 +214,11 @@ __device__ __forceinline__ void out_dot(const OutArgs& a, const float* y, int la
     s1 = wave_sum(s1);
 }
 __device__ __forceinline__ void out_update(const OutArgs& a, int m, float s0, float s1, float& xn0, float& xn1) {
-    const float* hrow = a.hyp + (size_t)a.rmap.ea(m) * a.hyp_ld;
-    const float e0 = (s0 + a.bo[0]) * sigmoidf_(hrow[a.goff] + a.thyp[a.goff]) + hrow[a.boff] + a.thyp[a.boff];
-    const float e1 = (s1 + a.bo[1]) * sigmoidf_(hrow[a.goff + 1] + a.thyp[a.goff + 1]) + hrow[a.boff + 1] +
-                     a.thyp[a.boff + 1];
+    const size_t ea = a.rmap.ea(m);
+    const float* hrow = a.hyp + ea * a.hyp_ld;
+    const float* tb = a.tbo ? a.tbo + 2 * ea : a.thyp + a.boff;
+    const float e0 = (s0 + a.bo[0]) * sigmoidf_(hrow[a.goff] + a.thyp[a.goff]) + hrow[a.boff] + tb[0];
+    const float e1 = (s1 + a.bo[1]) * sigmoidf_(hrow[a.goff + 1] + a.thyp[a.goff + 1]) + hrow[a.boff + 1] + tb[1];
     if (a.e_out) {
         a.e_out[2 * (size_t)m] = e0;
         a.e_out[2 * (size_t)m + 1] = e1;
@@ -285,7 +290,8 @@ __device__ __forceinline__ void out_ddim_piece(const OutArgs& a, const EmbedArgs
     const float wo01 = c1 < a.dl ? a.Wo[c1] : 0.f, wo11 = c1 < a.dl ? a.Wo[a.dl + c1] : 0.f;
     const float* hrow_o = a.hyp + (size_t)a.rmap.ea(m0) * a.hyp_ld;
     const float g0 = sigmoidf_(hrow_o[a.goff] + a.thyp[a.goff]), g1 = sigmoidf_(hrow_o[a.goff + 1] + a.thyp[a.goff + 1]);
-    const float hb0 = hrow_o[a.boff], hb1 = hrow_o[a.boff + 1], tb0 = a.thyp[a.boff], tb1 = a.thyp[a.boff + 1];
+    const float* tbp = a.tbo ? a.tbo + 2 * (size_t)a.rmap.ea(m0) : a.thyp + a.boff;
+    const float hb0 = hrow_o[a.boff], hb1 = hrow_o[a.boff + 1], tb0 = tbp[0], tb1 = tbp[1];
     const float bo0 = a.bo[0], bo1 = a.bo[1];
     for (int tb = 0; tb < tpw; tb += 12) {
         const int nb = tpw - tb < 12 ? tpw - tb : 12;

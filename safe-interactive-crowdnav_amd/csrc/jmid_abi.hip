@@ -485,6 +485,30 @@ int jmid_net_eval_padded(jmid_handle_t h, int E, int A, int K, int T, const int3
     return run_network(h, c);
 }
 
+// jmid_loss (seeded null) and jmid_loss_seeded: one net evaluation with K = 1 at per-row timesteps, the squared error against e reduced on
+// the device (loss.hpp).  Every argument error surfaces in check_call, before anything is enqueued.
+static int loss_entry(jmid_handle_t h, const char* who, int E, int A, int T, const int32_t* n_agents, const int32_t* t, const float* x0, const float* e,
+                      const SeedArgs* seeded, const float* ctx, int precision, double* loss_out, double* row_out, float* e_theta_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    LossCall lc;
+    lc.t = t; lc.e = e; lc.seeded = seeded; lc.loss_out = loss_out; lc.row_out = row_out;
+    DenoiseCall c{E, A, 1, T, precision, mem};
+    c.x_in = x0; c.ctx = ctx; c.e_out = e_theta_out; c.single_step = 0; c.n_agents = n_agents; c.loss = &lc; c.who = who;
+    return run_network(h, c);
+}
+
+int jmid_loss(jmid_handle_t h, int E, int A, int T, const int32_t* n_agents, const int32_t* t, const float* x0, const float* e, const float* ctx,
+              int precision, double* loss_out, double* row_out, float* e_theta_out, int mem) {
+    if (h && !e) return fail(h, JMID_EINVAL, "jmid_loss: null e");
+    return loss_entry(h, "jmid_loss", E, A, T, n_agents, t, x0, e, nullptr, ctx, precision, loss_out, row_out, e_theta_out, mem);
+}
+
+int jmid_loss_seeded(jmid_handle_t h, int E, int A, int T, const int32_t* n_agents, const int32_t* t, const float* x0, uint64_t seed,
+                     const uint32_t* episode_ids, const float* ctx, int precision, double* loss_out, double* row_out, float* e_theta_out, int mem) {
+    const SeedArgs sa{seed, episode_ids};
+    return loss_entry(h, "jmid_loss_seeded", E, A, T, n_agents, t, x0, nullptr, &sa, ctx, precision, loss_out, row_out, e_theta_out, mem);
+}
+
 int jmid_denoise_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* x_T, const float* ctx, const float* p0,
                         float dt, int precision, float* vel_out, float* pos_out, int mem) {
     if (!h) return JMID_EINVAL;

@@ -35,6 +35,7 @@
 #include "gemm_f32.hpp"
 #include "kde.hpp"
 #include "launch_plan.hpp"
+#include "loss.hpp"
 #include "noise.hpp"
 #include "padded.hpp"
 #include "qkv0.hpp"
@@ -59,6 +60,8 @@ enum KClass {
     KC_INTEGRATE,
     KC_METRICS,
     KC_VTRANS,
+    KC_LOSS_PREPARE,
+    KC_LOSS_REDUCE,
     KC_TOPK,
     KC_EVAL_STATS,
     KC_COUNT
@@ -170,6 +173,8 @@ struct jmid_ctx {
     jmid_host::Block frames_dev;
     // the seeded entry points: the call's episode ids on the device (the fill kernel reads them there); the padded ones: its agent counts
     jmid_host::HostArray noise_ids, nag;
+    // jmid_loss: the per-row timesteps of the call on the device (uploaded once per call, as the counts)
+    jmid_host::HostArray loss_t;
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)
     bool lnx_off = false;       // a workgroup of that kernel once gave up waiting for a partner (range flag bit 1): the handle stays on GEMM + add_ln2
@@ -194,6 +199,13 @@ struct jmid_ctx {
     float* bhyp = nullptr;
     float* thyp = nullptr;  // [n_steps, hl.total]
     std::vector<float> time_w;  // host [hl.total][3] time columns of the hyper nets
+    // jmid_set_loss_schedule: the forward process per TIMESTEP (index 0 is the reference's padding entry), independent of the sampler's
+    // step table - host copies, and on the device the time table [n_t, hl.total] (the expression of thyp), c0 | c1 [2 n_t] and the
+    // zeroed row of hl.total floats a loss call hands the kernels as their thyp
+    std::vector<float> loss_beta, loss_c0, loss_c1;
+    float* loss_tt = nullptr;
+    float* loss_c = nullptr;
+    float* zero_thyp = nullptr;
     float* lstmT[3][3] = {{nullptr}};  // [hist, edge_ped, edge_robot] x [WihT, WhhT, b]
     float* attW1T = nullptr;
     float* attW2T = nullptr;
@@ -280,7 +292,9 @@ inline size_t numel(const std::vector<size_t>& s) {
 void register_shapes(jmid_ctx* h);
 int dev_alloc_copy(jmid_ctx* h, float** out, const std::vector<float>& host);
 int fetch_host(jmid_ctx* h, const std::string& name, std::vector<float>& out);
+std::vector<float> time_table(const jmid_ctx* h, const std::vector<float>& beta);      // [beta.size(), hl.total]: thyp's and the loss schedule's
 int upload_time_table(jmid_ctx* h);
+int upload_loss_schedule(jmid_ctx* h);
 int make_w8(jmid_ctx* h, const float* dW, int N, int K, jmid_ctx::W8Image* out);
 int w8_image(jmid_ctx* h, const float* dW, int N, int K, unsigned char* out);      // ... into a buffer of the caller's (N K bytes)
 void free_planes(jmid_ctx* h);
@@ -297,6 +311,13 @@ struct SeedArgs {
     const uint32_t* ids;
 };
 int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream);
+// What a loss call (jmid_loss / jmid_loss_seeded; loss.hpp) adds to a single-step call with K = 1: x_in is x0
+struct LossCall {
+    const int32_t* t = nullptr;           // HOST [E, A] timesteps, 1 .. n_t - 1
+    const float* e = nullptr;             // [E, A, T, 2], or null: draw 0 of the counter generator with rows = A
+    const SeedArgs* seeded = nullptr;
+    double *loss_out = nullptr, *row_out = nullptr;      // [2]; [E, A] or null
+};
 // One denoise call (or, with single_step >= 0, one net evaluation -> e_out) as its entry point states it
 struct DenoiseCall {
     int E, A, K, T, precision, mem;
@@ -310,6 +331,7 @@ struct DenoiseCall {
     // a padded call (padded.hpp): HOST array [E], 1 <= n_agents[e] <= A - episode e has n_agents[e] real agents, the rows of the others
     // are zeroed on entry and NaN in every output; JMID attention takes the key-mask words.  DDIM with the caller's x_T only.
     const int32_t* n_agents = nullptr;
+    const LossCall* loss = nullptr;       // a loss call: per-row timesteps folded into hyp, a zero row as thyp, e_out may be null
     const char* who = "jmid_denoise";     // the entry point that was called (error texts)
 };
 // the counts of a padded call: checked by its entry before anything is enqueued (JMID_EINVAL: null, or a count outside 1..A), then

@@ -175,6 +175,16 @@ struct StepPlan {
     ResidualPlan out_proj, linear2;
     AttnPlan attn;
     int out_tpw;                 // output kernel: tokens per wave of the per-trajectory form, 0 = one wave per token
+    // The time part of the hyper nets the kernels of step i add to every row's hyp: row i of the handle's step table - or, in a loss call,
+    // whose rows carry their own timestep inside hyp (loss.hpp), the handle's zeroed row for every step (stride 0).  A value of the call.
+    const float* thyp_base;
+    size_t thyp_stride;
+    const float* thyp(int step) const { return thyp_base + (size_t)step * thyp_stride; }
+    // ... and, where such a call's tail is not the folded one, the time part of the output layer's bias per row (OutArgs::tbo) for the
+    // chunk whose hyper rows are hyp_chunk: loss_tbo [E A, 2] runs parallel to the call's hyper rows loss_hyp [E A, hl.total]
+    const float *loss_hyp, *loss_tbo;
+    const float* tbo(const float* hyp_chunk) const { return loss_tbo ? loss_tbo + (size_t)(hyp_chunk - loss_hyp) / thyp_ld * 2 : nullptr; }
+    size_t thyp_ld;              // hl.total
 };
 
 StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, const CallMode& mode, const CallFacts& cf, bool masked = false) {
@@ -193,6 +203,8 @@ StepPlan plan_step(const jmid_ctx* h, int Ec, int A, int K, int T, const CallMod
     p.hd = d / h->nhead;
     p.att_scale = 1.0f / sqrtf((float)p.hd);
     p.cf = cf;
+    p.thyp_base = h->thyp;
+    p.thyp_stride = p.thyp_ld = (size_t)h->hl.total;
     const Tuning& t = h->tune;
     p.attn = plan_attn(p.hd, t);
     p.attn.masked = masked && p.joint;      // (iMID: its rows are independent sequences, nothing to mask)
@@ -283,7 +295,7 @@ int qkv0_table_steps(int steps, int Ec, int A, int d) {
 int qkv0_build_table(jmid_ctx* h, const StepPlan& p, const Lane& ln, const float* hyp_chunk, int step0, int nsteps) {
     const int d = h->d;
     ProfScope ps(h, KC_HYPER, ln.stream);
-    Qkv0CoefArgs ca{h->wt.concat1.W, h->wt.concat1.bias, hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, ln.coef,
+    Qkv0CoefArgs ca{h->wt.concat1.W, h->wt.concat1.bias, hyp_chunk, p.thyp(step0), ln.coef,
                     nsteps, p.R, d, h->hl.total, h->hl.g1, h->hl.b1, h->range_flag};
     const long total = (long)nsteps * p.R * (d / 4);
     hipLaunchKernelGGL(qkv0_coef_kernel, dim3((int)std::min<long>((total + 255) / 256, 256L * 16)), dim3(256), 0, ln.stream, ca);
@@ -309,7 +321,7 @@ int tail_build_table(jmid_ctx* h, const StepPlan& p, const Lane& ln, const float
     const WeightTable& wt = h->wt;
     ProfScope ps(h, KC_HYPER, ln.stream);
     TailTableArgs ta{wt.concat3.W, wt.concat3.bias, wt.concat4.W, wt.concat4.bias, wt.linear.W, wt.linear.bias,
-                     hyp_chunk, h->thyp + (size_t)step0 * h->hl.total, ln.weff, ln.beff,
+                     hyp_chunk, p.thyp(step0), ln.weff, ln.beff,
                      nsteps, p.R, h->d, h->dmid, h->dlow, h->hl.total,
                      h->hl.g3, h->hl.b3, h->hl.g4, h->hl.b4, h->hl.go, h->hl.bo, h->range_flag};
     HIPCHK(h, launch_tail_fold_table(ta, ln.stream));
@@ -385,10 +397,10 @@ int qkv_planes(jmid_ctx* h, const StepPlan& p, const Lane& ln, int l, int step_i
 // The sampler's part of the output stage of step `step_idx`: what out_ddim*_kernel and tail_fold*_kernel share
 OutArgs sampler_args(const jmid_ctx* h, const StepPlan& p, const StepBuffers& sb, int step_idx, float* x_chunk, const float* hyp_chunk,
                      float* e_out, const float* z_chunk) {
-    OutArgs oa{sb.Y4, h->wt.linear.W, h->wt.linear.bias, hyp_chunk, h->thyp + (size_t)step_idx * h->hl.total, x_chunk, e_out,
+    OutArgs oa{sb.Y4, h->wt.linear.W, h->wt.linear.bias, hyp_chunk, p.thyp(step_idx), x_chunk, e_out,
                p.M, h->dlow, h->hl.total, h->hl.go, h->hl.bo,
                h->c_e[step_idx], h->c_x[step_idx], h->n_x[step_idx], h->n_e[step_idx], p.rm,
-               nullptr, 0, 0.f, 0.f, 0.f};
+               nullptr, 0, 0.f, 0.f, 0.f, p.tbo(hyp_chunk)};
     if (h->ddpm && !e_out) {
         oa.ddpm = 1;
         oa.z = h->p_noise[step_idx] ? z_chunk : nullptr;
@@ -411,7 +423,7 @@ int folded_tail(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, fl
     const TailFoldArgs fa{ln.Xh, ln.Xl, ln.weff + at * 2 * d, ln.beff + at * 2, d};
     const OutArgs oa = sampler_args(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
     const bool embed_next = next_step >= 0 && !e_out;
-    const EmbedArgs en = embed_next ? embed_args(h, p, ln, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+    const EmbedArgs en = embed_next ? embed_args(h, p, ln, x_chunk, hyp_chunk, p.thyp(next_step)) : EmbedArgs{};
     const bool lo = !p.mode.x2;
     ProfScope ps(h, KC_OUT_DDIM, ln.stream);
     const auto launch = [&](auto* kernel, int waves, auto... tpw) {
@@ -437,7 +449,7 @@ int output_stage(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, f
     ProfScope ps(h, KC_OUT_DDIM, ln.stream);
     const OutArgs oa = sampler_args(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk);
     const bool embed_next = next_step >= 0 && !e_out;
-    const EmbedArgs en = embed_next ? embed_args(h, p, ln, x_chunk, hyp_chunk, h->thyp + (size_t)next_step * h->hl.total) : EmbedArgs{};
+    const EmbedArgs en = embed_next ? embed_args(h, p, ln, x_chunk, hyp_chunk, p.thyp(next_step)) : EmbedArgs{};
     // four waves per workgroup: one wave per piece of a trajectory (out_tpw tokens), or one per token
     const auto launch = [&](auto* kernel, int waves, auto... tpw) {
         hipLaunchKernelGGL(kernel, dim3((waves + 3) / 4), dim3(256), bystander_lds(h->tune.bystander_lds, kernel), ln.stream, oa, en, tpw...);
@@ -458,7 +470,7 @@ int net_tail(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float
     if (p.tail_fold) return folded_tail(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
     const int M = p.M, d = h->d;
     const WeightTable& wt = h->wt;
-    const float* thyp = h->thyp + (size_t)step_idx * h->hl.total;
+    const float* thyp = p.thyp(step_idx);
     GemmHArgs g = gemm_h_args(p.mode, p.rm, M, ln.Xh, ln.Xl, wt.concat3, h->dmid, d);
     g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total;
     g.Chi = ln.Y3h; g.Clo = ln.Y3l; g.ldc = h->dmid; g.goff = h->hl.g3; g.boff = h->hl.b3;
@@ -479,7 +491,7 @@ int net_step(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float
     const bool split = p.mode.split;
     const int M = p.M, d = h->d, ff = h->ff;
     const WeightTable& wt = h->wt;
-    const float* thyp = h->thyp + (size_t)step_idx * h->hl.total;
+    const float* thyp = p.thyp(step_idx);
     const RowMap& rm = p.rm;
     if (!embed_done)
         if (int rc = run_embed(h, p, ln, x_chunk, hyp_chunk, thyp)) return rc;
@@ -706,6 +718,8 @@ CallPlan plan_call(const jmid_ctx* h, const DenoiseCall& a, const CallMode& mode
         if (j == cp.plans.size()) cp.plans.push_back(plan_step(h, ec, A, K, T, mode, cp.facts, cp.masked));
         cp.chunk_plan.push_back((int)j);
     }
+    if (a.loss)      // the rows' timesteps are inside hyp (loss_prepare_kernel): a zero row for the one "step"
+        for (StepPlan& p : cp.plans) p.thyp_base = h->zero_thyp, p.thyp_stride = 0;
     cp.qkv0_rows = cp.plans[0].qkv0 ? (size_t)cp.facts.qkv0_steps * Ec * A * 3 : 0;
     cp.tail_rows = cp.plans[0].tail_fold ? (size_t)cp.facts.tail_steps * Ec * A : 0;
     return cp;
@@ -715,6 +729,11 @@ CallPlan plan_call(const jmid_ctx* h, const DenoiseCall& a, const CallMode& mode
 struct CallIo {
     float *x_cur, *ctx, *hyp, *p0, *stage, *z_up, *z_lane;      // stage: e / pos; z_up: the caller's DDPM noise; z_lane: z_fill
     unsigned* mask;      // a padded JMID call: key-mask words [E][ceil(S / 32)] (padded.hpp) - a chunk's words are its episodes' slice
+    // a loss call (loss.hpp): e where it is not the caller's device array (its upload, or the seeded draw), the per-row sums, {loss, count}
+    float* e_up;
+    float* tbo;          // (StepPlan::loss_tbo; only off the folded tail)
+    double *loss_rows, *loss;
+    const float* e_dev;  // ... and the e the two loss kernels read (fill_workspace)
 };
 size_t call_io(const jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, char* base, CallIo* out) {
     const size_t M = (size_t)a.E * a.K * a.A * a.T, EA = (size_t)a.E * a.A;
@@ -728,6 +747,12 @@ size_t call_io(const jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, char
     if (a.z && a.mem == JMID_MEM_HOST) io.z_up = c.take(M * 2 * h->beta.size());
     if (cp.z_fill) io.z_lane = c.take((size_t)cp.nlanes * cp.Mc * 2);
     if (cp.masked && h->net_kind == JMID_NET_JMID) io.mask = reinterpret_cast<unsigned*>(c.take((size_t)a.E * mask_words_per_seq(a.K * a.A * a.T)));
+    if (a.loss) {
+        if (!a.loss->e || a.mem == JMID_MEM_HOST) io.e_up = c.take(M * 2);
+        if (!cp.plans[0].tail_fold) io.tbo = c.take(EA * 2);
+        io.loss_rows = c.take<double>(EA);
+        io.loss = c.take<double>(2);
+    }
     if (out) *out = io;
     return c.off;
 }
@@ -749,6 +774,19 @@ int check_call(jmid_ctx* h, const DenoiseCall& a, CallMode* mode) {
         if (int rc = check_n_agents(h, "padded call", a.n_agents, a.E, a.A)) return rc;
         if (h->net_kind == JMID_NET_JMID && mode->split && !attn_masked_built(plan_attn(h->d / h->nhead, h->tune), mode->x2 != 0))
             return fail(h, JMID_EINVAL, "a padded call needs the default attention kernel: \"attn_sm\" = 2 and the ablations (every split mode), \"attn_mx\" = 1 and \"attn_pf\" = 2 (F16X2 / F16MX) have no masked form");
+    }
+    if (const LossCall* lc = a.loss) {
+        const std::string w(a.who);
+        if (a.K != 1 || a.single_step < 0) return fail(h, JMID_EINVAL, w + ": a loss call is one net evaluation with K = 1");
+        if (!h->loss_tt) return fail(h, JMID_EINVAL, w + ": jmid_set_loss_schedule has not been called");
+        if (!lc->t || !lc->loss_out || (!lc->e && !lc->seeded)) return fail(h, JMID_EINVAL, w + ": null argument");
+        if (lc->seeded && !lc->seeded->ids) return fail(h, JMID_EINVAL, w + ": null episode_ids");
+        if (lc->seeded && !noise_fits((unsigned long long)a.A * a.T * 2)) return fail(h, JMID_EINVAL, w + ": A * T exceeds the noise addressing");
+        const int n_t = (int)h->loss_beta.size();
+        for (size_t r = 0; r < (size_t)a.E * a.A; ++r)
+            if (lc->t[r] < 1 || lc->t[r] >= n_t)
+                return fail(h, JMID_EINVAL, w + ": t[" + std::to_string(r / a.A) + ", " + std::to_string(r % a.A) + "] = " + std::to_string(lc->t[r]) +
+                                                " (row " + std::to_string(r) + ") is outside 1.." + std::to_string(n_t - 1));
     }
     h->last_pos = nullptr;     // (the staging buffer is about to be reused)
     if (a.single_step < 0 && h->ddpm && !a.z && !a.seeded) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
@@ -812,6 +850,23 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
     g.A = a.ctx; g.lda = h->ctx_dim; g.W = h->Whyp; g.ldw = h->ctx_dim; g.bias = h->bhyp; g.C = io.hyp;
     g.ldc = h->hl.total; g.M = (int)EA; g.N = h->hl.total; g.K = h->ctx_dim;
     if (int rc = run_gemm<EPI_BIAS>(h, h->stream, KC_HYPER, g)) return rc;
+    if (const LossCall* lc = a.loss) {
+        // x_cur holds x0 (zeros in the padded rows): e to the device, then x_t in place and every row's timestep into its hyp row
+        if (int rc = h->loss_t.upload(h, lc->t, (int)EA, a.who)) return rc;
+        io.e_dev = io.e_up ? io.e_up : lc->e;
+        if (!lc->e) {
+            if (int rc = h->noise_ids.upload(h, lc->seeded->ids, a.E, a.who)) return rc;
+            if (int rc = fill_noise(h, lc->seeded->seed, h->noise_ids.get<unsigned>(), a.E, (size_t)a.A * a.T * 2, 0, io.e_up, nullptr, h->stream)) return rc;
+        } else if (io.e_up) {
+            HIPCHK(h, hipMemcpyAsync(io.e_up, lc->e, M * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        }
+        const int n_t = (int)h->loss_beta.size();
+        const LossPrepareArgs pa{io.x_cur, io.e_dev, h->loss_t.get<int>(), h->loss_c, h->loss_c + n_t, io.hyp, h->loss_tt,
+                                 cp.masked ? h->nag.get<int>() : nullptr, io.tbo, (int)EA, a.A, a.T * 2, h->hl.total, h->hl.bo};
+        for (StepPlan& p : cp.plans) p.loss_hyp = io.hyp, p.loss_tbo = io.tbo;
+        ProfScope ps(h, KC_LOSS_PREPARE, h->stream);
+        HIPCHK(h, launch_loss_prepare(pa, h->stream));
+    }
     if (cp.nlanes > 1) {   // everything enqueued so far (inputs, hyper nets, memsets) precedes the extra lanes as well
         HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
         for (int l = 1; l < cp.nlanes; ++l) HIPCHK(h, hipStreamWaitEvent(cp.lanes[l].stream, h->ev_fork, 0));
@@ -917,9 +972,18 @@ int finish_call(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const Cal
     }
     // a padded call: quiet NaN in the padded agents' rows of what it returns - and, through the integrator, of the resident positions
     const float qnan = std::numeric_limits<float>::quiet_NaN();
+    if (const LossCall* lc = a.loss) {      // the staged e_theta against e, before the pad fill below touches the stage
+        const LossReduceArgs ra{io.stage, io.e_dev, cp.masked ? h->nag.get<int>() : nullptr, io.loss_rows, io.loss, (int)R, a.A, a.T * 2};
+        {
+            ProfScope ps(h, KC_LOSS_REDUCE, h->stream);
+            HIPCHK(h, launch_loss_reduce(ra, h->stream));
+        }
+        HIPCHK(h, hipMemcpyAsync(lc->loss_out, io.loss, 2 * sizeof(double), kout, h->stream));
+        if (lc->row_out) HIPCHK(h, hipMemcpyAsync(lc->row_out, io.loss_rows, R * sizeof(double), kout, h->stream));
+    }
     if (cp.masked) HIPCHK(h, launch_pad_fill(a.single_step >= 0 ? io.stage : io.x_cur, h->nag.get<int>(), a.E, a.K, a.A, a.T * 2, qnan, h->stream));
     if (a.single_step >= 0) {
-        HIPCHK(h, hipMemcpyAsync(a.e_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
+        if (a.e_out) HIPCHK(h, hipMemcpyAsync(a.e_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
     } else {
         if (a.vel_out) HIPCHK(h, hipMemcpyAsync(a.vel_out, io.x_cur, M * 2 * sizeof(float), kout, h->stream));
         if (a.p0) {      // integrated whenever p0 is given: the positions stay in the workspace for jmid_topk(pos = NULL)
@@ -1021,7 +1085,7 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
         HIPCHK(h, hipGetLastError());
         if (int rc = net_tail(h, p, ln, step, nullptr, hyp_d, out_d, nullptr, -1)) return rc;
     } else {
-        if (int rc = run_embed(h, p, ln, in_d, hyp_d, h->thyp + (size_t)step * h->hl.total)) return rc;
+        if (int rc = run_embed(h, p, ln, in_d, hyp_d, p.thyp(step))) return rc;
         if (int rc = qkv_planes(h, p, ln, 0, step, in_d, hyp_d)) return rc;
         const LoImages im = lo_images(p, ln, d);
         QkvReadArgs ra{ln.Qh, ln.Ql, ln.Kh, ln.Kl, ln.Vth, ln.Vtl, im.q8l, im.k8l, out_d, M, d, p.hd, p.sg.S, p.sg.Spad, mode.x2,
@@ -1033,7 +1097,7 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
     HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(out, out_d, M * out_w * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (thyp_row)
-        HIPCHK(h, hipMemcpyAsync(thyp_row, h->thyp + (size_t)step * h->hl.total, h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(thyp_row, p.thyp(step), h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return flag ? flagged_call(h, flag) : 0;
 }

@@ -61,25 +61,49 @@ int fetch_host(jmid_ctx* h, const std::string& name, std::vector<float>& out) {
     return 0;
 }
 
-// upload the per-step time part of the four hyper nets: thyp[i][j] = w0*beta + w1*sin(beta) + w2*cos(beta)
-int upload_time_table(jmid_ctx* h) {
-    drop_graphs(h);        // the captured loops hold the old table's pointer and the old step coefficients
-    if (!h->finalized || h->beta.empty()) return 0;
-    const int n = (int)h->beta.size(), tot = h->hl.total;
+// the time part of the four hyper nets for every entry of `beta`: t[i][j] = w0*beta + w1*sin(beta) + w2*cos(beta)
+std::vector<float> time_table(const jmid_ctx* h, const std::vector<float>& beta) {
+    const int n = (int)beta.size(), tot = h->hl.total;
     std::vector<float> t((size_t)n * tot);
     for (int i = 0; i < n; ++i) {
-        const float b = h->beta[i], sb = sinf(b), cb = cosf(b);
+        const float b = beta[i], sb = sinf(b), cb = cosf(b);
         for (int j = 0; j < tot; ++j) {
             const float* w3 = &h->time_w[(size_t)j * 3];
             t[(size_t)i * tot + j] = w3[0] * b + w3[1] * sb + w3[2] * cb;
         }
     }
+    return t;
+}
+
+// upload the per-step time part of the four hyper nets (thyp)
+int upload_time_table(jmid_ctx* h) {
+    drop_graphs(h);        // the captured loops hold the old table's pointer and the old step coefficients
+    if (!h->finalized || h->beta.empty()) return 0;
+    const std::vector<float> t = time_table(h, h->beta);
     if (h->thyp) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         HIPCHK(h, hipFree(h->thyp));
         h->thyp = nullptr;
     }
     return dev_alloc_copy(h, &h->thyp, t);
+}
+
+// the loss schedule's device side (jmid_set_loss_schedule, and again whenever the weights are finalized: the time columns are theirs).
+// No captured loop reads any of it: the graphs stay.
+int upload_loss_schedule(jmid_ctx* h) {
+    if (!h->finalized || h->loss_beta.empty()) return 0;
+    if (h->loss_tt || h->loss_c) HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (float** p : {&h->loss_tt, &h->loss_c})
+        if (*p) {
+            HIPCHK(h, hipFree(*p));
+            *p = nullptr;
+        }
+    std::vector<float> c(h->loss_c0);
+    c.insert(c.end(), h->loss_c1.begin(), h->loss_c1.end());
+    if (int rc = dev_alloc_copy(h, &h->loss_tt, time_table(h, h->loss_beta))) return rc;
+    if (int rc = dev_alloc_copy(h, &h->loss_c, c)) return rc;
+    if (!h->zero_thyp) return dev_alloc_copy(h, &h->zero_thyp, std::vector<float>((size_t)h->hl.total, 0.f));
+    return 0;
 }
 
 
@@ -127,9 +151,9 @@ void free_weights(jmid_ctx* h) {
     free_derived(h);
     for (auto& kv : h->w) hipFree(kv.second.p);
     h->w.clear();
-    for (void* p : {(void*)h->thyp, (void*)h->range_flag})
+    for (void* p : {(void*)h->thyp, (void*)h->range_flag, (void*)h->loss_tt, (void*)h->loss_c, (void*)h->zero_thyp})
         if (p) hipFree(p);
-    h->thyp = nullptr;
+    h->thyp = h->loss_tt = h->loss_c = h->zero_thyp = nullptr;
     h->range_flag = nullptr;
 }
 
@@ -331,7 +355,8 @@ int jmid_finalize_weights(jmid_handle_t h) {
         HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), h->stream));
     }
     h->finalized = true;
-    return upload_time_table(h);
+    if (int rc = upload_time_table(h)) return rc;
+    return upload_loss_schedule(h);
 }
 
 int jmid_set_ddim_table(jmid_handle_t h, int n_steps, const float* beta, const float* c_e, const float* c_x,
@@ -362,6 +387,15 @@ int jmid_set_ddpm_table(jmid_handle_t h, int n_steps, const float* beta, const f
     h->ddpm = true;
     HIPCHK(h, hipSetDevice(h->device));
     return upload_time_table(h);
+}
+
+int jmid_set_loss_schedule(jmid_handle_t h, int n_t, const float* beta, const float* c0, const float* c1) {
+    if (!h || n_t < 2 || !beta || !c0 || !c1) return fail(h, JMID_EINVAL, "bad loss schedule");
+    h->loss_beta.assign(beta, beta + n_t);
+    h->loss_c0.assign(c0, c0 + n_t);
+    h->loss_c1.assign(c1, c1 + n_t);
+    HIPCHK(h, hipSetDevice(h->device));
+    return upload_loss_schedule(h);
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import JmidError
-from .schedule import VarianceSchedule, ddim_steps, ddpm_steps
+from .schedule import VarianceSchedule, ddim_steps, ddpm_steps, loss_tables
 from .weights import JMIDWeights
 
 try:  # torch is optional plumbing here (device tensors in / out)
@@ -66,6 +66,17 @@ def seeded_noise_args(x_T, seed, episode_ids, E: Optional[int] = None):
     if np.any(ids.astype(np.int64) < 0) or np.any(ids.astype(np.int64) > 0xFFFFFFFF):
         raise ValueError("episode ids are uint32")
     return seed, np.ascontiguousarray(ids, dtype=np.uint32)
+
+
+class LossResult:
+    """What ``JmidEngine.loss`` returns: ``loss``, ``count``, and ``rows`` / ``e_theta`` where they were asked for (else None)."""
+    __slots__ = ("loss", "count", "rows", "e_theta")
+
+    def __init__(self, loss, count, rows=None, e_theta=None):
+        self.loss, self.count, self.rows, self.e_theta = loss, count, rows, e_theta
+
+    def __repr__(self):
+        return f"LossResult(loss={float(self.loss):.6g}, count={int(self.count)})"
 
 
 class _Buf:
@@ -545,6 +556,63 @@ class JmidEngine:
                                             _lib.PRECISIONS[precision], optr,
                                             self._mem(dev))
         return out
+
+    def set_loss_schedule(self, schedule: Optional[VarianceSchedule] = None) -> None:
+        """Install the forward process per timestep (``jmid_set_loss_schedule``; ``schedule.loss_tables``) - ``loss`` does it from
+        ``self.schedule`` on first use.  Independent of ``set_step``."""
+        tabs = loss_tables(schedule or self.schedule)
+        self._check(self._lib.jmid_set_loss_schedule(self._h, len(tabs[0]), *[C.c_void_p(c.ctypes.data) for c in tabs]))
+        self._loss_schedule = True
+
+    def loss(self, x0: ArrayLike, ctx: ArrayLike, t, e: Optional[ArrayLike] = None, seed: Optional[int] = None, episode_ids=None,
+             n_agents=None, precision: str = "f32", want_rows: bool = False, want_e_theta: bool = False) -> "LossResult":
+        """The reference's denoising loss (``jmid_loss``; ``DiffusionTraj.get_loss``, MID/models/diffusion.py:448-476): one net
+        evaluation with every agent row at its own timestep.  x0 [E, A, T, 2] (the recorded futures), ctx [E, A, ctx_dim], t int [E, A]
+        in 1..num_steps (always a host array), and exactly one of ``e`` [E, A, T, 2] (the noise) or ``seed`` + ``episode_ids`` [E]
+        (``jmid_loss_seeded``: e is ``noise(seed, episode_ids, A, T, 0)``).  ``n_agents`` [E]: a padded batch - the rows of agents
+        a >= n_agents[e] are masked as attention keys and dropped from the loss (NaN in ``rows`` and ``e_theta``).
+        -> ``LossResult``: ``loss`` (mean squared error over the real rows' T * 2 components), ``count`` (their number), ``rows`` [E, A]
+        float64 sum of squared errors per row (``want_rows``), ``e_theta`` [E, A, T, 2] (``want_e_theta``).  NumPy in -> NumPy out (and
+        ``loss`` a float, ``count`` an int); CUDA tensors in -> CUDA tensors out (``loss`` and ``count`` 0-d float64 tensors)."""
+        if (e is None) == (seed is None):
+            raise ValueError("exactly one of e and seed must be given")
+        dev = _is_cuda(x0)
+        if x0.ndim != 4 or ctx.ndim != 3:
+            raise ValueError("expected x0 [E, A, T, 2] and ctx [E, A, ctx_dim]")
+        E, A, K, T = self._shapes(x0, ctx)
+        if K != 1:
+            raise ValueError("x0 must hold one row per agent: [E, A, T, 2]")
+        tt = np.ascontiguousarray(np.asarray(t.cpu() if torch is not None and torch.is_tensor(t) else t), dtype=np.int32)
+        if tt.size != E * A:
+            raise ValueError(f"t must hold one timestep per agent row ({E * A}), got {tt.size}")
+        seeded = seeded_noise_args(None, seed, episode_ids, E) if seed is not None else None
+        if e is not None and (_is_cuda(e) != dev or tuple(e.shape) != tuple(x0.shape)):
+            raise ValueError("e must have x0's shape and live where x0 lives")
+        if not getattr(self, "_loss_schedule", False):
+            self.set_loss_schedule()
+        bx, bc = _Buf(x0, dev), _Buf(ctx, dev)
+        be = _Buf(e, dev) if e is not None else None
+        na = agent_counts(n_agents, E) if n_agents is not None else None
+
+        def alloc(shape, dtype):
+            if dev:
+                a = torch.empty(shape, dtype=getattr(torch, dtype), device=x0.device)
+                return a, C.c_void_p(a.data_ptr())
+            a = np.empty(shape, dtype=dtype)
+            return a, C.c_void_p(a.ctypes.data)
+
+        out, optr = alloc((2,), "float64")
+        rows, rptr = alloc((E, A), "float64") if want_rows else (None, None)
+        eth, eptr = alloc((E, A, T, 2), "float32") if want_e_theta else (None, None)
+        head = (self._h, E, A, T, C.c_void_p(na.ctypes.data) if na is not None else None, C.c_void_p(tt.ctypes.data), bx.ptr)
+        tail = (bc.ptr, _lib.PRECISIONS[precision], optr, rptr, eptr, self._mem(dev))
+        if seeded is not None:
+            self._compute(self._lib.jmid_loss_seeded, *head, seeded[0], C.c_void_p(seeded[1].ctypes.data), *tail)
+        else:
+            self._compute(self._lib.jmid_loss, *head, be.ptr, *tail)
+        if dev:
+            return LossResult(out[0], out[1], rows, eth)
+        return LossResult(float(out[0]), int(out[1]), rows, eth)
 
     def episode_metrics(self, pos: ArrayLike, gt: ArrayLike) -> ArrayLike:
         """pos [E,K,A,T,2], gt [E,A,T,2] -> [E,4] = (mean ADE, joint min ADE, mean FDE, joint min FDE)."""

@@ -13,6 +13,9 @@ truth is real are scored, agents without any are left out, and the fixed-horizon
 The collision statistics (``collision_statistics_host``, ``summarise_collisions``; ``csrc/collision_stats.hpp``,
 ``jmid_collision_statistics``) follow MID/models/collision_check_utils.py: ``calc_min_dists`` (:58-80) with ``lineseg_dist`` (:20-55)
 for the clearance of every agent pair of one joint sample, ``get_agents_in_collision`` (:83-97) for the agents that collide.
+
+The denoising loss (``loss_host``, ``loss_by_timestep``; ``csrc/loss.hpp``, ``jmid_loss``) is the reduction of ``DiffusionTraj.get_loss``
+(MID/models/diffusion.py:465-475): ``F.mse_loss(reduction="none")`` in fp32, the mean over the rows the loss mask keeps in fp64.
 """
 from __future__ import annotations
 
@@ -320,3 +323,44 @@ def summarise_collisions(scene: np.ndarray) -> Dict[str, float]:
     scene = np.asarray(scene, dtype=np.float64).reshape(-1, len(COLLISION_SCENE_COLUMNS))
     with np.errstate(invalid="ignore"):
         return {c: float(np.mean(scene[:, k])) for k, c in enumerate(COLLISION_SCENE_COLUMNS)}
+
+
+def _real_rows(E: int, A: int, n_agents) -> np.ndarray:
+    """[E, A] bool: agent a of episode e is real (a < n_agents[e]); every row when ``n_agents`` is None."""
+    if n_agents is None:
+        return np.ones((E, A), dtype=bool)
+    n = np.asarray(n_agents, dtype=np.int64).reshape(-1)
+    if n.size != E or np.any(n < 1) or np.any(n > A):
+        raise ValueError("n_agents must hold one count in 1..A per episode")
+    return np.arange(A)[None, :] < n[:, None]
+
+
+def loss_host(e_theta: np.ndarray, e: np.ndarray, n_agents=None):
+    """The host twin of the device loss reduction (``csrc/loss.hpp``, ``jmid_loss``): ``DiffusionTraj.get_loss``'s
+    ``F.mse_loss(reduction="none")`` and masked mean (MID/models/diffusion.py:465-475).  e_theta, e [E, A, T, 2]: the difference and its
+    square in fp32, sums in fp64 -> (loss, count, rows): the mean over the real rows' T * 2 components, their number, and the sum of
+    squared errors per row [E, A] float64 (NaN for padded rows, whose values are never read)."""
+    e_theta, e = np.asarray(e_theta, dtype=np.float32), np.asarray(e, dtype=np.float32)
+    if e_theta.ndim != 4 or e_theta.shape != e.shape or e.shape[-1] != 2:
+        raise ValueError("expected e_theta and e [E, A, T, 2]")
+    E, A, T, _ = e.shape
+    real = _real_rows(E, A, n_agents)
+    with np.errstate(invalid="ignore"):
+        d = np.where(real[:, :, None, None], e_theta - e, np.float32(0))
+    sq = (d * d).astype(np.float32)
+    rows = sq.astype(np.float64).reshape(E, A, T * 2).sum(axis=-1)
+    count = int(real.sum()) * T * 2
+    loss = float(rows[real].sum() / count)
+    rows[~real] = np.nan
+    return loss, count, rows
+
+
+def loss_by_timestep(rows: np.ndarray, t: np.ndarray, T: int, n_agents=None) -> Dict[int, float]:
+    """The usual diagnostic of a denoising loss: the mean squared error per distinct timestep.  rows [E, A] (sum of squared errors per
+    row, as ``loss_host`` / ``JmidEngine.loss`` return them), t [E, A] the rows' timesteps, T the horizon -> {t: mean over the real rows at
+    that t of rows / (T * 2)}."""
+    rows, t = np.asarray(rows, dtype=np.float64), np.asarray(t)
+    if rows.ndim != 2 or t.shape != rows.shape:
+        raise ValueError("expected rows and t [E, A]")
+    real = _real_rows(rows.shape[0], rows.shape[1], n_agents)
+    return {int(v): float(rows[real & (t == v)].sum() / (int((real & (t == v)).sum()) * T * 2)) for v in np.unique(t[real])}

@@ -12,6 +12,10 @@ RNG contract: the global torch CPU generator is consumed exactly as the referenc
 where it is unused).  ``seed=`` (opt-in; None is the contract above) draws nothing on the host: x_T and every step's z come from the
 library's counter generator (``noise.py``, ``jmid_denoise_seeded``) with sample i as episode id i - no [n_steps, ...] tensor is drawn
 or uploaded.  Statistically, not seed-, compatible with the reference.
+
+``get_loss`` / ``validation`` mirror ``AutoEncoder.get_loss`` (``MID/models/autoencoder.py:105-122``) and ``MID.validation()``
+(``MID/mid.py:252-296``): the denoising loss of ``DiffusionTraj.get_loss`` (``diffusion.py:448-476``) on recorded futures, one device
+call per batch (``JmidEngine.loss``), with the reference's draws of t and e.
 """
 from __future__ import annotations
 
@@ -79,3 +83,74 @@ def generate(engine: JmidEngine, context, p0, dt: float, num_points: int, sample
     pos, nsteps, a, b, c = sample(engine, num_points, context, sample_n, bestof, flexibility=flexibility,
                                   sampling=sampling, step=step, precision=precision, _integrate=(p0, dt), seed=seed)
     return np.asarray(pos, dtype=np.float32), nsteps, a, b, c
+
+
+def agent_counts_from_futures(y_t, batch_size: int) -> np.ndarray:
+    """The real agents per scene of a NaN-padded batch of futures, by ``generate_mask``'s rule (MID/dataset/preprocessing.py:35-89).
+    y_t [batch_size * A, T, 2] -> n_agents int32 [batch_size].  The reference makes two masks from the NaNs: attention sees the agents in
+    front of the first row with ANY NaN (:63-73), the loss drops the rows that are ALL NaN (:85).  They describe one padded batch only
+    when the padding is trailing and whole rows; anything else raises ``ValueError``."""
+    y = np.asarray(y_t.detach().cpu() if torch.is_tensor(y_t) else y_t)
+    if y.ndim != 3 or batch_size < 1 or y.shape[0] % batch_size != 0:
+        raise ValueError("expected y_t [batch_size * A, T, 2]")
+    A = y.shape[0] // batch_size
+    nan = np.isnan(y).reshape(batch_size, A, -1)
+    any_nan, all_nan = nan.any(axis=-1), nan.all(axis=-1)
+    n = np.where(any_nan.any(axis=1), any_nan.argmax(axis=1), A).astype(np.int32)       # attention: agents before the first NaN row
+    for b in range(batch_size):
+        if (any_nan[b] != all_nan[b]).any():
+            raise ValueError(f"scene {b}: agent {int((any_nan[b] != all_nan[b]).argmax())} is partly NaN - the reference's two masks disagree there "
+                             "(attention drops the row and every later one, the loss keeps it)")
+        if not all_nan[b, n[b]:].all():
+            raise ValueError(f"scene {b}: a NaN agent (row {int(n[b])}) in front of a real one - the reference's two masks disagree there "
+                             "(attention stops at the first NaN row, the loss keeps the real rows behind it): padding must be trailing")
+        if n[b] < 1:
+            raise ValueError(f"scene {b} has no real agent")
+    return n
+
+
+def get_loss(engine: JmidEngine, x_st, nbr_sum, edge_mask, y_t, batch_size: Optional[int] = None, t=None, precision: str = "f32",
+             seed: Optional[int] = None, episode_ids=None, want_rows: bool = False, want_e_theta: bool = False):
+    """``AutoEncoder.get_loss`` (MID/models/autoencoder.py:105-122) on the engine: encode, then ``DiffusionTraj.get_loss``
+    (MID/models/diffusion.py:448-476) as one device call (``JmidEngine.loss``).  x_st [R, hist, 6], nbr_sum [R, 2, hist, 6], edge_mask
+    [R, 2] the encoder's inputs, y_t [R, T, 2] the futures.  ``batch_size`` (the joint predictor's validation, MID/mid.py:275-281): R =
+    batch_size * A rows, scenes padded to A agents with NaN rows in y_t - the counts come from ``agent_counts_from_futures``
+    (``generate_mask``), NaNs are zeroed as ``masked_fill`` does (preprocessing.py:29-33).  None: the unmasked branch, all R rows one scene.
+    RNG contract (the reference's): ``t`` from ``np.random.choice(np.arange(1, num_steps + 1), R)`` when not given
+    (``uniform_sample_t``, diffusion.py:55-57), then e from one global ``torch.randn`` of y_t's shape.  ``seed=`` draws e on the device
+    instead (scene b is episode id ``episode_ids[b]``, default b); t is still drawn on the host.  -> ``engine.LossResult``."""
+    y = torch.as_tensor(np.asarray(y_t.detach().cpu() if torch.is_tensor(y_t) else y_t, dtype=np.float32))
+    if y.ndim != 3 or y.shape[-1] != 2:
+        raise ValueError("expected y_t [R, T, 2]")
+    R, T = int(y.shape[0]), int(y.shape[1])
+    E = 1 if batch_size is None else int(batch_size)
+    n_agents = None if batch_size is None else agent_counts_from_futures(y, E)
+    A = R // E
+    clean = [np.nan_to_num(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float32), nan=0.0) for a in (x_st, nbr_sum, edge_mask)]
+    ctx = engine.encode(*clean).reshape(E, A, -1)
+    if t is None:
+        t = np.random.choice(np.arange(1, engine.schedule.num_steps + 1), R)
+    t = np.asarray(t, dtype=np.int32).reshape(E, A)
+    x0 = torch.nan_to_num(y, nan=0.0).numpy().reshape(E, A, T, 2)
+    if n_agents is not None and (n_agents == A).all():
+        n_agents = None if not engine.joint else n_agents       # (iMID rows are independent: nothing to mask)
+    kw = dict(n_agents=n_agents, precision=precision, want_rows=want_rows, want_e_theta=want_e_theta)
+    if seed is not None:
+        return engine.loss(x0, ctx, t, seed=seed, episode_ids=np.arange(E) if episode_ids is None else episode_ids, **kw)
+    e = torch.randn(y.shape).numpy().reshape(E, A, T, 2)
+    return engine.loss(x0, ctx, t, e=e, **kw)
+
+
+def validation(engine: JmidEngine, batches, precision: str = "f32", seed: Optional[int] = None) -> float:
+    """``MID.validation`` (MID/mid.py:252-296): the mean of the per-batch losses ("Avg. Val Loss").  ``batches``: an iterable of dicts
+    with the keyword arguments of ``get_loss`` (x_st, nbr_sum, edge_mask, y_t and optionally batch_size, t).  ``seed``: batch i draws its
+    e on the device with scene b as episode id (number of scenes before the batch) + b."""
+    losses, first = [], 0
+    for b in batches:
+        kw = dict(b)
+        if seed is not None:
+            E = 1 if kw.get("batch_size") is None else int(kw["batch_size"])
+            kw.update(seed=seed, episode_ids=np.arange(first, first + E))
+            first += E
+        losses.append(float(get_loss(engine, precision=precision, **kw).loss))
+    return sum(losses) / len(losses)

@@ -44,6 +44,14 @@ class VarianceSchedule:
                    sigmas_inflex.numpy().copy(), sigmas_flex.numpy().copy())
 
 
+def loss_tables(sched: VarianceSchedule):
+    """The forward process per timestep, as ``DiffusionTraj.get_loss`` reads it (``diffusion.py:453-457``): ``(beta, c0, c1)`` float32
+    [num_steps + 1] with ``c0 = sqrt(alpha_bar)``, ``c1 = sqrt(1 - alpha_bar)`` in torch fp32; index = timestep, entry 0 the padding
+    entry.  What ``jmid_set_loss_schedule`` takes."""
+    ab = torch.from_numpy(np.ascontiguousarray(sched.alpha_bars, dtype=np.float32))
+    return (np.ascontiguousarray(sched.betas, dtype=np.float32), torch.sqrt(ab).numpy().copy(), torch.sqrt(1 - ab).numpy().copy())
+
+
 @dataclass(frozen=True)
 class DDIMStep:
     t: int
