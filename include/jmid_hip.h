@@ -141,6 +141,15 @@ int jmid_set_ddpm_table(jmid_handle_t h, int n_steps, const float* beta, const f
 int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* nbr_sum, const float* edge_mask,
                 float* ctx_out, int mem);
 
+/* jmid_encode for rows seen for fewer than hist_len frames (the reference's first_history_index, MID/dataset/preprocessing.py:468,
+ * MID/models/encoders/model_utils.py:77-105): the history LSTM and both edge LSTMs of row r run over frames first_index[r] .. hist_len-1
+ * from a zero state and the last output is the encoding.  Frames in front of first_index[r] are not read - x_st AND nbr_sum may hold NaN
+ * there.  Row r equals row r of a handle created with hist_len - first_index[r] fed the slice, bit for bit; all zero: jmid_encode's bits.
+ *   first_index  [n_agents] int32, a HOST array in both memory modes (like the episode ids of the seeded entries)
+ * JMID_EINVAL, before anything is enqueued, for a value outside 0..hist_len-2 (a row needs two frames) or a NULL first_index. */
+int jmid_encode_var(jmid_handle_t h, int n_agents, const float* x_st, const float* nbr_sum, const float* edge_mask,
+                    const int32_t* first_index, float* ctx_out, int mem);
+
 /* The batched reverse-denoising loop + integrator:
  * DiffusionTraj.sample_sicnav_inference with sampling="ddim" (MID/models/diffusion.py:478-541),
  * the net forward (diffusion.py:133-150 / 173-209) and SingleIntegrator.integrate_samples
@@ -360,6 +369,32 @@ int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_x
 /* Copies of the arrays jmid_build_scene left on the handle, in its padded layout: x, x_st [E, N, F, 6], nbr_sum [E, N, 2, F, 6],
  * edge_mask [E, N, 2], p0 [E, N, 2].  NULL arguments are skipped.  JMID_EINVAL without a preceding jmid_build_scene. */
 int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float* edge_mask, float* p0, int mem);
+
+/* jmid_build_scene for tracks seen for fewer than F frames (an episode's first control steps, a pedestrian entering sensor range):
+ *   first_frame  [E, N + 1] int32, robot first then the pedestrians by id; a HOST array in both memory modes; NULL: all zero, and then
+ *                every resident array has the bits jmid_build_scene leaves
+ * Node j is present on frames first_frame[j] .. F-1, without gaps; its positions in front of that are never read and may be NaN.
+ *   - velocity and acceleration are first differences over the node's own span (MID/environment/data_utils.py:24-37; one frame: zero);
+ *     x and x_st are NaN in front of it
+ *   - the scene graph has no adjacency on a frame where either node is absent (MID/environment/scene.py:84-106)
+ *   - a connected neighbour is taken with padding 0.0 and THEN standardised relative to the ego (preprocessing.py:531-550): on a frame
+ *     where it is absent it adds (0 - ego_now) / std in all six columns, so nbr_sum is finite on all F frames.  The reference's quirk.
+ *   - a pedestrian with ONE frame is never an ego row: in_cluster_out 0 and not counted in n_in_out, its cv_out row its position repeated;
+ *     it still counts in the cluster choice and as a neighbour
+ * Additionally resident: first_index [E, N] int32 (jmid_scene_get_first_index); jmid_predict_scene, jmid_forecast_scene and their seeded
+ * forms gather it with the rows and run the encoder as jmid_encode_var does.  A scene built by jmid_build_scene or
+ * jmid_build_scene_stamped has none and runs the launches it always ran.
+ * JMID_EINVAL (the resident scene is kept): a first_frame outside 0..F-1, a robot with fewer than 2 frames while force_all_in_cluster is
+ * 0, and every refusal of jmid_build_scene.
+ * Not covered: raw-stamp input (jmid_build_scene_stamped still ends in JMID_EHISTORY below hist_len grid frames), gaps inside a track's
+ * span, and tracks that end before the last frame (leave those out of the scene). */
+int jmid_build_scene_var(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, const int32_t* first_frame,
+                         double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out,
+                         int* n_in_out, double* cv_out, int mem);
+
+/* first_index [E, N] int32 of the resident scene, in its padded layout (all zero after a build without first_frame).  JMID_EINVAL without
+ * a resident scene. */
+int jmid_scene_get_first_index(jmid_handle_t h, int32_t* out, int mem);
 
 /* jmid_predict on the resident scene: the in-cluster rows are gathered on the device in ascending track id, then encoder -> denoise loop ->
  * integrator -> top-k run chained on the stream exactly as in jmid_predict (the same kernels on the same values: the outputs are

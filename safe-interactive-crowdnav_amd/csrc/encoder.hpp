@@ -5,6 +5,10 @@
 // One workgroup per agent, one thread per LSTM gate row (4H threads).  The whole recurrent state and the
 // agent's history live in LDS; weights are stored transposed ([in, 4H]) so that the 4H threads read
 // consecutive addresses for each k.  The work is tiny (once per predictor call).
+//
+// Short histories (first_index, the reference's first_history_index: MID/models/encoders/model_utils.py:77-105 run_lstm_on_variable_length_seqs):
+// the three LSTMs of row r run over frames first_index[r] .. Th-1 from a zero state and the last output is the encoding.  The start frame is
+// uniform over the workgroup (one agent); frames in front of it are neither loaded into LDS nor read (they may hold NaN).
 #pragma once
 #include "common.hpp"
 
@@ -25,13 +29,14 @@ struct EncArgs {
     const float* W2T;        // [H, H]
     const float* v;          // [H]
     float* ctx;              // [n, 2H]
+    const int* first_index;  // [n] first history frame of every row (0 .. Th-2), or null: 0 for every row
     int n, Th, H;
 };
 
 constexpr int ENC_MAX_TH = 16;
 constexpr int ENC_MAX_H = 256;
 
-__device__ inline void lstm_run(const LstmW& w, const float* xin /*LDS [Th, in]*/, int in, int Th, int H, float* gates,
+__device__ inline void lstm_run(const LstmW& w, const float* xin /*LDS [Th, in]*/, int in, int first, int Th, int H, float* gates,
                                 float* hbuf, float* cbuf) {
     const int row = threadIdx.x;  // gate row, 0..4H-1
     const int H4 = 4 * H;
@@ -40,7 +45,7 @@ __device__ inline void lstm_run(const LstmW& w, const float* xin /*LDS [Th, in]*
         cbuf[row] = 0.f;
     }
     __syncthreads();
-    for (int t = 0; t < Th; ++t) {
+    for (int t = first; t < Th; ++t) {
         float acc = w.b[row];
         for (int k = 0; k < in; ++k) acc += w.WihT[k * H4 + row] * xin[t * in + k];
         for (int k = 0; k < H; ++k) acc += w.WhhT[k * H4 + row] * hbuf[k];
@@ -64,7 +69,7 @@ __device__ inline void lstm_run(const LstmW& w, const float* xin /*LDS [Th, in]*
 // encoder took at the shipped operating point, where it was 10 % of the device time).  Here a thread loads its row once per LSTM
 // (H + 12 registers) and the steps run from registers and LDS.  Same products, same order: bit-identical to lstm_run.
 template <int H>
-__device__ inline void lstm_run_reg(const LstmW& w, const float* xin /*LDS [Th, in]*/, int in, int Th, float* gates, float* hbuf,
+__device__ inline void lstm_run_reg(const LstmW& w, const float* xin /*LDS [Th, in]*/, int in, int first, int Th, float* gates, float* hbuf,
                                     float* cbuf) {
     constexpr int H4 = 4 * H;
     const int row = threadIdx.x;  // gate row, 0..4H-1
@@ -79,7 +84,7 @@ __device__ inline void lstm_run_reg(const LstmW& w, const float* xin /*LDS [Th, 
         cbuf[row] = 0.f;
     }
     __syncthreads();
-    for (int t = 0; t < Th; ++t) {
+    for (int t = first; t < Th; ++t) {
         float acc = bias;
 #pragma unroll
         for (int k = 0; k < 12; ++k)
@@ -115,25 +120,26 @@ __global__ __launch_bounds__(HT ? 4 * HT : 1024) void encoder_kernel(EncArgs a) 
     __shared__ float score[2];
     const int ag = blockIdx.x, tid = threadIdx.x;
     const int Th = a.Th, H = a.H;
+    const int first = a.first_index ? a.first_index[ag] : 0;      // (the host has checked 0 <= first <= Th - 2)
 
     // ---- history LSTM (input 6)
-    for (int i = tid; i < Th * 6; i += blockDim.x) xin[i] = a.x_st[(size_t)ag * Th * 6 + i];
+    for (int i = first * 6 + tid; i < Th * 6; i += blockDim.x) xin[i] = a.x_st[(size_t)ag * Th * 6 + i];
     __syncthreads();
-    if constexpr (HT > 0) lstm_run_reg<HT>(a.hist, xin, 6, Th, gates, hbuf, cbuf);
-    else lstm_run(a.hist, xin, 6, Th, H, gates, hbuf, cbuf);
+    if constexpr (HT > 0) lstm_run_reg<HT>(a.hist, xin, 6, first, Th, gates, hbuf, cbuf);
+    else lstm_run(a.hist, xin, 6, first, Th, H, gates, hbuf, cbuf);
     if (tid < H) h_hist[tid] = hbuf[tid];
     __syncthreads();
 
     // ---- edge LSTMs (input = [summed neighbour state(6), own state(6)])
     for (int e = 0; e < 2; ++e) {
-        for (int i = tid; i < Th * 12; i += blockDim.x) {
+        for (int i = first * 12 + tid; i < Th * 12; i += blockDim.x) {
             const int t = i / 12, k = i % 12;
             xin[i] = k < 6 ? a.nbr_sum[(((size_t)ag * 2 + e) * Th + t) * 6 + k]
                            : a.x_st[((size_t)ag * Th + t) * 6 + (k - 6)];
         }
         __syncthreads();
-        if constexpr (HT > 0) lstm_run_reg<HT>(a.edge[e], xin, 12, Th, gates, hbuf, cbuf);
-        else lstm_run(a.edge[e], xin, 12, Th, H, gates, hbuf, cbuf);
+        if constexpr (HT > 0) lstm_run_reg<HT>(a.edge[e], xin, 12, first, Th, gates, hbuf, cbuf);
+        else lstm_run(a.edge[e], xin, 12, first, Th, H, gates, hbuf, cbuf);
         if (tid < H) u[e][tid] = hbuf[tid] * a.edge_mask[(size_t)ag * 2 + e];
         __syncthreads();
     }

@@ -86,7 +86,10 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
                  in_floats = o_bw + align_up_floats(n_bw), o_ctx = in_floats, o_out = o_ctx + align_up_floats(n * H2), o_flag = o_out, o_fc = o_flag + align_up_floats(1), o_lwd = o_fc + align_up_floats(n_fc),
                  o_sel = o_lwd + align_up_floats(n_lwd), o_lw = o_sel + align_up_floats(n_sel), o_pos = o_lw + align_up_floats(n_lw), total = o_pos + align_up_floats(n_pos),
                  out_floats = (fc_out ? o_sel : total) - o_out;
-    if (int rc = h->io_dev.reserve(h, total * 4, who)) return rc;
+    // a scene with first_index: its dense [E * A] copy behind everything else (no other offset moves)
+    const bool var = scene && h->scene.has_first;
+    const size_t o_fi = total;
+    if (int rc = h->io_dev.reserve(h, (total + (var ? align_up_floats(n) : 0)) * 4, who)) return rc;
     if (int rc = h->pin.reserve(h, (in_floats + out_floats) * 4, who)) return rc;
     float* pin = h->pin.as<float>();
     float* dev = h->io_dev.as<float>();
@@ -118,9 +121,14 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
             ga.edge_mask = reinterpret_cast<const float*>(sc.dev.p + sc.o_em); ga.p0 = reinterpret_cast<const float*>(sc.dev.p + sc.o_p0);
             ga.o_x_st = dev + o_xs; ga.o_nbr_sum = dev + o_nb; ga.o_edge_mask = dev + o_em; ga.o_p0 = dev + o_p0;
             ga.E = E; ga.N = sc.N; ga.A = A; ga.F = (int)Th;
+            if (var) {
+                ga.first_index = reinterpret_cast<const int*>(sc.dev.p + sc.o_first);
+                ga.o_first_index = reinterpret_cast<int*>(dev + o_fi);
+            }
             if (launch_scene_gather(ga, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": scene gather launch failed");
         }
-        const EncArgs ea = encoder_args(h, dev + o_xs, dev + o_nb, dev + o_em, dev + o_ctx, (int)n);
+        EncArgs ea = encoder_args(h, dev + o_xs, dev + o_nb, dev + o_em, dev + o_ctx, (int)n);
+        if (var) ea.first_index = reinterpret_cast<const int*>(dev + o_fi);
         if (!rc && launch_encoder(ea, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": encoder launch failed");
     }
     DenoiseCall c{E, A, K, T, precision, JMID_MEM_DEVICE};       // a stage of the chain: no caller-stream ordering, the flag comes with the one download
@@ -193,15 +201,18 @@ int check_scene_dims(jmid_ctx* h, const char* who, int N, int F, const double* c
 // jmid_build_scene and jmid_build_scene_stamped after their argument checks and order_in: the grid into the scene workspace, scene_kernel, the
 // small outputs to the caller (`mem` says where they live), one synchronisation.  src 0: human_xy / robot_xy are host arrays; 1: device
 // arrays; 2: human_xy is a device GridBlock (grid + pose_now, as frames_kernel left it) and robot_xy is unused.
+// first_frame (jmid_build_scene_var; a HOST array [E, N + 1], checked by the caller, or null): uploaded ahead of the kernel, which then leaves
+// first_index [E, N] behind the download block.
 int build_scene_resident(jmid_ctx* h, const char* who, int E, int N, int F, const double* human_xy, const double* robot_xy, int src, double time_step, int horizon,
-                         int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem) {
+                         int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem,
+                         const int32_t* first_frame = nullptr) {
     const bool host = mem == JMID_MEM_HOST;
     const size_t rows = (size_t)E * N, b_hum = rows * F * 2 * 8, b_rob = (size_t)E * F * 2 * 8, b_cv = cv_out ? rows * horizon * 2 * 8 : 0;
     const GridBlock gb = grid_block(E, N, F);
     // the grid | the resident arrays | the download block: n_in, in_cluster, robot_in_cluster, cv
     const size_t o_x = gb.end, o_xst = o_x + align_up(rows * F * 6 * 4),
                  o_nbr = o_xst + align_up(rows * F * 6 * 4), o_em = o_nbr + align_up(rows * 2 * F * 6 * 4), o_p0 = o_em + align_up(rows * 2 * 4), o_nin = o_p0 + align_up(rows * 2 * 4),
-                 o_inc = o_nin + align_up((size_t)E * 4), o_rin = o_inc + align_up(rows), o_cv = o_rin + align_up((size_t)E), need = o_cv + align_up(b_cv), b_out = need - o_nin;
+                 o_inc = o_nin + align_up((size_t)E * 4), o_rin = o_inc + align_up(rows), o_cv = o_rin + align_up((size_t)E), o_first = o_cv + align_up(b_cv), need = o_first + (first_frame ? align_up(rows * 4) : 0), b_out = o_first - o_nin;
     jmid_ctx::SceneWs& sc = h->scene;
     sc.E = 0;                     // no scene is resident until this call has succeeded
     if (int rc = sc.dev.reserve(h, need, who)) return rc;
@@ -218,6 +229,11 @@ int build_scene_resident(jmid_ctx* h, const char* who, int E, int N, int F, cons
     g.in_cluster = reinterpret_cast<unsigned char*>(dev + o_inc);
     g.robot_in = reinterpret_cast<unsigned char*>(dev + o_rin);
     g.cv = cv_out ? reinterpret_cast<double*>(dev + o_cv) : nullptr;
+    if (first_frame) {
+        if (int rc = h->first_idx.upload(h, first_frame, E * (N + 1), who)) return rc;
+        g.first_frame = h->first_idx.get<int>();
+        g.first_index = reinterpret_cast<int*>(dev + o_first);
+    }
     const size_t pin_in = src == 0 ? gb.o_pose : 0;       // host arrays are staged: human_xy | robot_xy
     if (int rc = h->pin.reserve(h, pin_in + (host ? b_out : (size_t)E * 4), who)) return rc;
     char* const pin = h->pin.p;
@@ -254,6 +270,7 @@ int build_scene_resident(jmid_ctx* h, const char* who, int E, int N, int F, cons
     sc.o_x = o_x; sc.o_xst = o_xst; sc.o_nbr = o_nbr; sc.o_em = o_em; sc.o_p0 = o_p0; sc.o_inc = o_inc;
     sc.o_hum = gb.o_hum; sc.o_rob = gb.o_rob; sc.o_pose = gb.o_pose; sc.o_cv = o_cv;
     sc.stamped = src == 2;
+    sc.o_first = o_first; sc.has_first = first_frame != nullptr;
     sc.horizon = cv_out ? horizon : 0;
     sc.E = E; sc.N = N;
     return 0;
@@ -432,26 +449,47 @@ int jmid_denoise_ddpm(jmid_handle_t h, int E, int A, int K, int T, const float* 
     return run_network(h, c);
 }
 
-int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* nbr_sum, const float* edge_mask,
-                float* ctx_out, int mem) {
+// jmid_encode (first_index null: the launch it always made) and jmid_encode_var (a HOST array, refused here before anything is enqueued)
+static int encode_entry(jmid_handle_t h, const char* who, int n_agents, const float* x_st, const float* nbr_sum, const float* edge_mask,
+                        const int32_t* first_index, float* ctx_out, int mem) {
     if (!h) return JMID_EINVAL;
     if (!h->finalized) return fail(h, JMID_ENOWEIGHT, "jmid_finalize_weights has not been called");
     if (n_agents <= 0 || !x_st || !nbr_sum || !edge_mask || !ctx_out) return fail(h, JMID_EINVAL, "bad argument");
+    if (first_index)
+        for (int r = 0; r < n_agents; ++r)
+            if (first_index[r] < 0 || first_index[r] > h->hist_len - 2)
+                return fail(h, JMID_EINVAL, std::string(who) + ": first_index[" + std::to_string(r) + "] = " + std::to_string(first_index[r]) +
+                                                " is outside 0..hist_len-2 (a row needs two history frames)");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t n = n_agents, Th = h->hist_len;
     EncArgs ea = encoder_args(h, nullptr, nullptr, nullptr, nullptr, n_agents);
     if (mem == JMID_MEM_HOST) h->last_pos = nullptr;      // the staging below overwrites the workspace the last positions live in
-    Staging st(h, mem, h->arena, "jmid_encode");
+    Staging st(h, mem, h->arena, who);
     st.in(&ea.x_st, x_st, n * Th * 6);
     st.in(&ea.nbr_sum, nbr_sum, n * 2 * Th * 6);
     st.in(&ea.edge_mask, edge_mask, n * 2);
     st.out(&ea.ctx, ctx_out, n * 2 * h->H);
     if (int rc = st.begin()) return rc;
+    if (first_index) {
+        if (int rc = h->first_idx.upload(h, first_index, n_agents, who)) return rc;
+        ea.first_index = h->first_idx.get<int>();
+    }
     {
         ProfScope ps(h, KC_ENCODER, h->stream);
         HIPCHK(h, launch_encoder(ea, h->stream));
     }
     return st.end();
+}
+
+int jmid_encode(jmid_handle_t h, int n_agents, const float* x_st, const float* nbr_sum, const float* edge_mask,
+                float* ctx_out, int mem) {
+    return encode_entry(h, "jmid_encode", n_agents, x_st, nbr_sum, edge_mask, nullptr, ctx_out, mem);
+}
+
+int jmid_encode_var(jmid_handle_t h, int n_agents, const float* x_st, const float* nbr_sum, const float* edge_mask,
+                    const int32_t* first_index, float* ctx_out, int mem) {
+    if (h && !first_index) return fail(h, JMID_EINVAL, "jmid_encode_var: null first_index");
+    return encode_entry(h, "jmid_encode_var", n_agents, x_st, nbr_sum, edge_mask, first_index, ctx_out, mem);
 }
 
 int jmid_denoise(jmid_handle_t h, int E, int A, int K, int T, const float* x_T, const float* ctx, const float* p0,
@@ -705,6 +743,52 @@ int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_x
     if (int rc = build_scene_resident(h, "jmid_build_scene", E, N, F, human_xy, robot_xy, mem == JMID_MEM_HOST ? 0 : 1, time_step, horizon, force_all_in_cluster,
                                       in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem))
         return rc;
+    return order_out(h, mem);
+}
+
+int jmid_build_scene_var(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, const int32_t* first_frame,
+                         double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out,
+                         double* cv_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (E <= 0 || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out) return fail(h, JMID_EINVAL, "jmid_build_scene_var: bad argument");
+    if (int rc = check_scene_dims(h, "jmid_build_scene_var", N, F, cv_out, horizon, time_step)) return rc;
+    // every refusal comes before the resident scene is touched
+    if (first_frame)
+        for (int e = 0; e < E; ++e)
+            for (int j = 0; j <= N; ++j) {
+                const int f = first_frame[(size_t)e * (N + 1) + j];
+                if (f < 0 || f > F - 1)
+                    return fail(h, JMID_EINVAL, "jmid_build_scene_var: first_frame[" + std::to_string(e) + ", " + std::to_string(j) + "] = " + std::to_string(f) +
+                                                    " is outside 0..F-1");
+                if (j == 0 && f > F - 2 && !force_all_in_cluster)
+                    return fail(h, JMID_EINVAL, "jmid_build_scene_var: the robot of episode " + std::to_string(e) + " has fewer than 2 frames");
+            }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = order_in(h, mem)) return rc;
+    if (int rc = build_scene_resident(h, "jmid_build_scene_var", E, N, F, human_xy, robot_xy, mem == JMID_MEM_HOST ? 0 : 1, time_step, horizon, force_all_in_cluster,
+                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem, first_frame))
+        return rc;
+    return order_out(h, mem);
+}
+
+int jmid_scene_get_first_index(jmid_handle_t h, int32_t* out, int mem) {
+    if (!h) return JMID_EINVAL;
+    const jmid_ctx::SceneWs& sc = h->scene;
+    if (!sc.E) return fail(h, JMID_EINVAL, "jmid_scene_get_first_index needs a preceding jmid_build_scene on this handle");
+    if (!out) return fail(h, JMID_EINVAL, "jmid_scene_get_first_index: null output");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = order_in(h, mem)) return rc;
+    const size_t bytes = (size_t)sc.E * sc.N * 4;
+    const bool host = mem == JMID_MEM_HOST;
+    // a scene built without first_frame: every track starts at frame 0
+    if (sc.has_first) {
+        HIPCHK(h, hipMemcpyAsync(out, sc.dev.p + sc.o_first, bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+    } else if (host) {
+        std::memset(out, 0, bytes);
+    } else {
+        HIPCHK(h, hipMemsetAsync(out, 0, bytes, h->stream));
+    }
+    if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
     return order_out(h, mem);
 }
 

@@ -167,6 +167,10 @@ struct jmid_ctx {
         size_t o_hum = 0, o_rob = 0, o_pose = 0, o_cv = 0;
         bool stamped = false;
         int horizon = 0;             // of the resident cv; 0: built without cv
+        // jmid_build_scene_var: first_index [E, N] int32 (every pedestrian's first history frame); the other builds leave none and
+        // the chained entries then run the encoder without one
+        size_t o_first = 0;
+        bool has_first = false;
     } scene;
     // jmid_build_scene_stamped: the raw frames and what frames_kernel made of them (grid, pose_now, n_grid), in a workspace of its own:
     // a build that ends with JMID_EHISTORY must not touch the resident scene
@@ -175,6 +179,8 @@ struct jmid_ctx {
     jmid_host::HostArray noise_ids, nag;
     // jmid_loss: the per-row timesteps of the call on the device (uploaded once per call, as the counts)
     jmid_host::HostArray loss_t;
+    // jmid_encode_var: the rows' first history frames; jmid_build_scene_var: the nodes' first frames
+    jmid_host::HostArray first_idx;
     int64_t erange_calls = 0;   // calls on this handle that ended with JMID_ERANGE (jmid_erange_count)
     unsigned lnx_epoch = 0;     // launch tag of the small-launch GEMM + LayerNorm with the statistics exchange (gemm_small.hpp, OUT_LNX)
     bool lnx_off = false;       // a workgroup of that kernel once gave up waiting for a partner (range flag bit 1): the handle stays on GEMM + add_ln2

@@ -17,6 +17,16 @@
 // distance by an ulp, and tests/golden/wrapper_jmid_entering.npz has a pair 4.4e-16 from the radius): the outputs are bit-identical to
 // the host twin's whenever the chosen cluster does not hinge on the summation order of step 2.
 //
+// Short histories (first_frame [E, N + 1], robot first; null: every node has all F frames): node j is present on frames first_frame[j] .. F-1.
+//   * its velocity and acceleration are the first differences over ITS span (data_utils.py:24-37; a single frame: both zero); x and x_st
+//     are NaN in front of the span (node.get(..., padding=nan)), and a position in front of it is never read
+//   * the scene graph sees NaN there (environment/scene.py:84-106): a NaN distance is not <= radius, no adjacency on that frame
+//   * a connected neighbour's state is taken with padding 0.0 and THEN standardised relative to the ego (preprocessing.py:531-550): on a
+//     frame where it is absent it adds (0 - ego_now) / std in all six columns
+//   * a pedestrian with ONE frame is never an ego row (in_cluster 0, no graph row, its constant-velocity row its position repeated) but
+//     still counts in the cluster choice and as a neighbour (present_nodes: min_history_timesteps 1 for the egos, 0 for the graph)
+// With first_frame null every operation and its order are the ones above.
+//
 // One workgroup of one wavefront per episode, one lane per node (node 0 the robot, 1 .. N the pedestrians: N + 1 <= 64); the node states
 // are staged in LDS.  The kernel is latency-bound and tiny.  A second kernel gathers the in-cluster rows, in ascending track id, into the
 // dense [E * A, ...] layout the encoder and the integrator read (jmid_predict_scene).
@@ -32,6 +42,8 @@ constexpr int SCN_MAX_H = 24;         // horizon of the constant-velocity foreca
 struct SceneArgs {
     const double* human_xy;       // [E, F, N, 2]
     const double* robot_xy;       // [E, F, 2]
+    const int* first_frame;       // [E, N + 1] first present frame of every node (robot first), 0 .. F-1; null: 0
+    int* first_index;             // [E, N] the pedestrians' first_frame, as the encoder reads it (written only with first_frame)
     float* x;                     // [E, N, F, 6]
     float* x_st;                  // [E, N, F, 6]
     float* nbr_sum;               // [E, N, 2, F, 6]
@@ -52,6 +64,7 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char scn_lds_raw[];
     __shared__ double rdist[SCN_LANES];
     __shared__ unsigned long long nearm[SCN_LANES];
+    __shared__ int sfirst[SCN_LANES];
     double* S = reinterpret_cast<double*>(scn_lds_raw);       // [F, 64, 6] node states
     const int i = threadIdx.x, e = blockIdx.x;
     const int N = g.N, F = g.F, n = N + 1;
@@ -60,18 +73,29 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
     // positions: robot first, like the track ids (-1, 0, 1, ...)
     const double* hum = g.human_xy + (size_t)e * F * N * 2;
     const double* rob = g.robot_xy + (size_t)e * F * 2;
+    const int* ffe = g.first_frame ? g.first_frame + (size_t)e * n : nullptr;
+    const double nan64 = __builtin_nan("");
     for (int q = i; q < F * n * 2; q += SCN_LANES) {
         const int c = q & 1, node = (q >> 1) % n, t = (q >> 1) / n;
-        st(t, node, c) = node == 0 ? rob[t * 2 + c] : hum[((size_t)t * N + (node - 1)) * 2 + c];
+        const bool here = !ffe || t >= ffe[node];
+        st(t, node, c) = !here ? nan64 : node == 0 ? rob[t * 2 + c] : hum[((size_t)t * N + (node - 1)) * 2 + c];
     }
+    sfirst[i] = ffe && i < n ? ffe[i] : 0;
     __syncthreads();
-    // step 4 (every lane its own node) and steps 1-2
+    // step 4 (every lane its own node, over its own span) and steps 1-2
     if (i < n) {
+        const int f0 = sfirst[i];
         for (int c = 0; c < 2; ++c) {
-            for (int t = 1; t < F; ++t) st(t, i, 2 + c) = (st(t, i, c) - st(t - 1, i, c)) / dt;
-            st(0, i, 2 + c) = st(1, i, 2 + c);
-            for (int t = 1; t < F; ++t) st(t, i, 4 + c) = (st(t, i, 2 + c) - st(t - 1, i, 2 + c)) / dt;
-            st(0, i, 4 + c) = st(1, i, 4 + c);
+            if (f0 < F - 1) {
+                for (int t = f0 + 1; t < F; ++t) st(t, i, 2 + c) = (st(t, i, c) - st(t - 1, i, c)) / dt;
+                st(f0, i, 2 + c) = st(f0 + 1, i, 2 + c);
+                for (int t = f0 + 1; t < F; ++t) st(t, i, 4 + c) = (st(t, i, 2 + c) - st(t - 1, i, 2 + c)) / dt;
+                st(f0, i, 4 + c) = st(f0 + 1, i, 4 + c);
+            } else {
+                st(f0, i, 2 + c) = 0.0;
+                st(f0, i, 4 + c) = 0.0;
+            }
+            for (int t = 0; t < f0; ++t) st(t, i, 2 + c) = st(t, i, 4 + c) = nan64;
         }
         const double px = st(F - 1, i, 0), py = st(F - 1, i, 1);
         unsigned long long m = 0;
@@ -103,14 +127,20 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
         }
         inc = nearm[best];
     }
+    // the ego rows: the in-cluster pedestrians with at least two frames (all of them without first_frame)
+    unsigned long long ego = inc & ~1ull;
+    for (int j = 1; j < n; ++j)
+        if (sfirst[j] > F - 2) ego &= ~(1ull << j);
     if (i == 0) {
         g.robot_in[e] = (unsigned char)(inc & 1ull);
-        g.n_in[e] = __popcll(inc >> 1);
+        g.n_in[e] = __popcll(ego);
     }
     if (i < 1 || i >= n) return;
     const size_t row = (size_t)e * N + (i - 1);
-    const bool in_me = (inc >> i) & 1ull;
+    const bool in_me = (ego >> i) & 1ull;
+    const int f0 = sfirst[i];
     g.in_cluster[row] = in_me ? 1 : 0;
+    if (ffe) g.first_index[row] = f0;
     // step 5: this pedestrian's row of the edge scaling, as a mask of connected nodes and the fp32 sum of their values
     unsigned long long conn = 0;
     float ev = 0.0f;
@@ -144,15 +174,16 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
     for (int c = 0; c < 6; ++c) now[c] = st(F - 1, i, c);
     g.p0[row * 2] = (float)now[0];
     g.p0[row * 2 + 1] = (float)now[1];
+    const float nan32 = __builtin_nanf("");
     for (int t = 0; t < F; ++t)
         for (int c = 0; c < 6; ++c) {
             const double v = st(t, i, c);
-            xo[t * 6 + c] = (float)v;
-            xs[t * 6 + c] = (float)((v - (c < 2 ? now[c] : 0.0)) / std6[c]);
+            xo[t * 6 + c] = t < f0 ? nan32 : (float)v;
+            xs[t * 6 + c] = t < f0 ? nan32 : (float)((v - (c < 2 ? now[c] : 0.0)) / std6[c]);
             // every node is added, an unconnected one with weight 0, as the host twin does (the sums start at +0.0)
             float acc_ped = 0.0f, acc_rob = 0.0f;
             for (int j = 0; j < n; ++j) {
-                const float rel = (float)((st(t, j, c) - now[c]) / std6[c]);
+                const float rel = (float)(((t < sfirst[j] ? 0.0 : st(t, j, c)) - now[c]) / std6[c]);
                 const float w = (conn >> j) & 1ull ? 1.0f : 0.0f;
                 if (j == 0) acc_rob = acc_rob + rel * w;
                 else acc_ped = acc_ped + rel * w;
@@ -184,6 +215,8 @@ struct SceneGatherArgs {
     const unsigned char* in_cluster;      // [E, N]
     const float *x_st, *nbr_sum, *edge_mask, *p0;     // padded
     float *o_x_st, *o_nbr_sum, *o_edge_mask, *o_p0;   // dense
+    const int* first_index;               // [E, N] padded, or null (a scene built without first_frame)
+    int* o_first_index;                   // [E * A] dense (written only with first_index)
     int E, N, A, F;
 };
 
@@ -206,6 +239,7 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_gather_kernel(SceneGat
             g.o_edge_mask[d * 2 + i] = g.edge_mask[s * 2 + i];
             g.o_p0[d * 2 + i] = g.p0[s * 2 + i];
         }
+        if (g.first_index && i == 0) g.o_first_index[d] = g.first_index[s];
     }
 }
 

@@ -197,13 +197,27 @@ class JmidEngine:
         self._check(self._lib.jmid_synchronize(self._h))
 
     # ------------------------------------------------------------------ compute
-    def encode(self, x_st: ArrayLike, nbr_sum: ArrayLike, edge_mask: ArrayLike) -> ArrayLike:
-        """x_st [n, hist, 6], nbr_sum [n, 2, hist, 6], edge_mask [n, 2] -> ctx [n, ctx_dim]."""
+    def _first_index(self, first_index, n: int) -> np.ndarray:
+        """The argument check of ``encode(first_index=)``: n values in 0..hist_len-2 -> contiguous int32 (no device is touched)."""
+        if torch is not None and isinstance(first_index, torch.Tensor):
+            first_index = first_index.detach().cpu().numpy()
+        fi = np.asarray(first_index)
+        if fi.shape != (n,) or not np.issubdtype(fi.dtype, np.integer):
+            raise ValueError("first_index must hold one integer per row")
+        if (fi < 0).any() or (fi > self.hist_len - 2).any():
+            raise ValueError(f"first_index must lie in 0..hist_len-2 = 0..{self.hist_len - 2}: a row needs two history frames")
+        return np.ascontiguousarray(fi, dtype=np.int32)
+
+    def encode(self, x_st: ArrayLike, nbr_sum: ArrayLike, edge_mask: ArrayLike, first_index=None) -> ArrayLike:
+        """x_st [n, hist, 6], nbr_sum [n, 2, hist, 6], edge_mask [n, 2] -> ctx [n, ctx_dim].  ``first_index`` [n] integers (a host array;
+        ``jmid_encode_var``): row r was first seen at history frame first_index[r] and its LSTMs run over the frames from there on, from a
+        zero state - the frames in front of it are not read and may hold NaN.  None: every row has the full window (``jmid_encode``)."""
         dev = _is_cuda(x_st)
         n = int(x_st.shape[0])
         if tuple(x_st.shape) != (n, self.hist_len, 6) or tuple(nbr_sum.shape) != (n, 2, self.hist_len, 6) \
                 or tuple(edge_mask.shape) != (n, 2):
             raise ValueError("bad encoder input shapes")
+        fi = None if first_index is None else self._first_index(first_index, n)
         a, b, c = _Buf(x_st, dev), _Buf(nbr_sum, dev), _Buf(edge_mask, dev)
         if dev:
             out = torch.empty((n, self.dims.ctx_dim), dtype=torch.float32, device=x_st.device)
@@ -211,6 +225,9 @@ class JmidEngine:
         else:
             out = np.empty((n, self.dims.ctx_dim), dtype=np.float32)
             optr = C.c_void_p(out.ctypes.data)
+        if fi is not None:
+            self._check(self._lib.jmid_encode_var(self._h, n, a.ptr, b.ptr, c.ptr, C.c_void_p(fi.ctypes.data), optr, self._mem(dev)))
+            return out
         self._check(self._lib.jmid_encode(self._h, n, a.ptr, b.ptr, c.ptr, optr,
                                           self._mem(dev)))
         return out
@@ -380,12 +397,16 @@ class JmidEngine:
         return pos, None
 
     def build_scene(self, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: Optional[int] = None,
-                    force_all_in_cluster: bool = False) -> Dict[str, np.ndarray]:
+                    force_all_in_cluster: bool = False, first_frame=None) -> Dict[str, np.ndarray]:
         """The scene batch on the device (``jmid_build_scene``; the device twin of ``scene.build_scenes_batched``): human_xy [E, F, N, 2]
         and robot_xy [E, F, 2] float64 on the ``time_step`` grid, oldest first - or [F, N, 2] and [F, 2] for one scene, whose results
         then come without the episode axis.  The encoder inputs stay on the device (``scene_arrays`` copies them out, ``predict_scene``
         runs the predictor on them); returned are ``in_cluster`` [E, N] bool, ``robot_in_cluster`` [E] bool, ``n_in`` [E] int32 and
-        ``cv`` [E, N, horizon, 2] float64 (None without ``horizon``)."""
+        ``cv`` [E, N, horizon, 2] float64 (None without ``horizon``).
+        ``first_frame`` [E, N + 1] integers, robot first (``jmid_build_scene_var``; ``scene.build_scenes_batched(first_frame=)`` is the
+        host twin): node j is present on frames first_frame[j] .. F-1 and its earlier positions are never read.  A pedestrian with a single
+        frame is no ego row (``in_cluster`` False, not counted in ``n_in``).  ``scene_arrays`` then returns ``first_index`` as well and
+        ``predict_scene`` / ``forecast_scene`` encode every row from its own first frame."""
         hum = np.ascontiguousarray(human_xy, dtype=np.float64)
         rob = np.ascontiguousarray(robot_xy, dtype=np.float64)
         single = hum.ndim == 3
@@ -398,17 +419,26 @@ class JmidEngine:
         rin = np.empty(E, dtype=np.uint8)
         n_in = np.empty(E, dtype=np.int32)
         cv = np.empty((E, N, int(horizon), 2), dtype=np.float64) if horizon is not None else None
-        self._check(self._lib.jmid_build_scene(self._h, E, N, F, C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data), float(time_step),
-                                               int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
-                                               C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
-                                               C.c_void_p(cv.ctypes.data) if cv is not None else None, _lib.MEM_HOST))
+        tail = (float(time_step), int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
+                C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
+                C.c_void_p(cv.ctypes.data) if cv is not None else None, _lib.MEM_HOST)
+        if first_frame is not None:
+            ff = np.asarray(first_frame)
+            if not np.issubdtype(ff.dtype, np.integer) or ff.shape != ((N + 1,) if single else (E, N + 1)):
+                raise ValueError("first_frame must hold N + 1 integers per episode, robot first")
+            ff = np.ascontiguousarray(ff.reshape(E, N + 1), dtype=np.int32)
+            self._check(self._lib.jmid_build_scene_var(self._h, E, N, F, C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data),
+                                                       C.c_void_p(ff.ctypes.data), *tail))
+        else:
+            self._check(self._lib.jmid_build_scene(self._h, E, N, F, C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data), *tail))
         self._scene_shape, self._scene_n_in = (E, N, F, single), n_in
         out = {"in_cluster": inc.astype(bool), "robot_in_cluster": rin.astype(bool), "n_in": n_in, "cv": cv}
         return {k: (v[0] if single and v is not None else v) for k, v in out.items()}
 
     def scene_arrays(self) -> Dict[str, np.ndarray]:
         """The arrays the preceding ``build_scene`` left on the device, under the keys of ``scene.build_scenes_batched``: x, x_st
-        [E, N, F, 6], nbr_sum [E, N, 2, F, 6], edge_mask [E, N, 2], p0 [E, N, 2] float32 (``jmid_scene_get``; every pedestrian has a row).
+        [E, N, F, 6], nbr_sum [E, N, 2, F, 6], edge_mask [E, N, 2], p0 [E, N, 2] float32 (``jmid_scene_get``; every pedestrian has a row)
+        and first_index [E, N] int32 (``jmid_scene_get_first_index``; zeros unless the scene was built with ``first_frame``).
         After a one-scene ``build_scene`` the episode axis is absent."""
         shape = getattr(self, "_scene_shape", None)
         E, N, F, single = shape if shape is not None else (0, 0, self.hist_len, False)      # (no build: the library says so)
@@ -416,6 +446,8 @@ class JmidEngine:
                "nbr_sum": np.empty((E, N, 2, F, 6), np.float32), "edge_mask": np.empty((E, N, 2), np.float32),
                "p0": np.empty((E, N, 2), np.float32)}
         self._check(self._lib.jmid_scene_get(self._h, *[C.c_void_p(a.ctypes.data) for a in out.values()], _lib.MEM_HOST))
+        out["first_index"] = np.empty((E, N), np.int32)
+        self._check(self._lib.jmid_scene_get_first_index(self._h, C.c_void_p(out["first_index"].ctypes.data), _lib.MEM_HOST))
         return {k: v[0] for k, v in out.items()} if single else out
 
     def _scene_noise(self, x_T, seed, episode_ids, K, T):

@@ -42,7 +42,9 @@ Differences from the reference that a caller can observe:
     one per (weights, net, device, history length, step size) and calls on it are serialised by a lock;
   * ``model_path`` may point to the neutral ``.npz`` written by ``export_checkpoint`` instead of the pickled
     ``nn.ModuleDict`` container (which needs the reference tree on ``sys.path`` to unpickle);
-  * a too-short history raises ``HistoryTooShortError`` (a ``TypeError``, like the reference's failure mode).
+  * a too-short history raises ``HistoryTooShortError`` (a ``TypeError``, like the reference's failure mode) - unless the instance was
+    made with ``short_history=True`` (opt-in): then a call with 2 .. past_num_frames - 1 shared frames predicts, every track encoded from
+    its first frame on as the reference's MODEL does it (``first_history_index``, MID/dataset/preprocessing.py:468).
 """
 from __future__ import annotations
 
@@ -171,7 +173,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  device_id: Optional[int] = None, precision: Optional[str] = None, rng_compat: Optional[str] = None,
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
                  lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
-                 seed: int = 0, episode_id: int = 0):
+                 seed: int = 0, episode_id: int = 0, short_history: bool = False):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -196,6 +198,11 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # top-k limits) reads its inputs back and assembles on the host.  Histories that are not frames (the per-human lists do not share
         # one stamp sequence with the robot's last entries) take the host frame table as before
         self.device_frames = bool(device_frames)
+        # True (opt-in; False is the reference wrapper's refusal): a call with 2 <= L < past_num_frames shared grid frames predicts - the
+        # window is padded in front (scene.pad_short_window) and every row is encoded from its first frame (the reference model's
+        # first_history_index) - instead of raising HistoryTooShortError.  One frame still raises; from past_num_frames frames on
+        # nothing changes
+        self.short_history = bool(short_history)
         self.erange_fallbacks = 0
         self.timings: Dict[str, float] = {}     # ms of the last predict_ret_best(): scene, device, topk, assemble
         if rng_compat not in ("auto", "cpu", "cuda", "device"):
@@ -298,22 +305,27 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
     def _predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
         t0 = time.perf_counter()
         prev, rob = self._snapshot()
-        frames = SC.histories_as_frames(prev, rob) if self.device_frames else None
-        if frames is None:
+        ff = None                            # short_history: the padded window's first_frame [N + 1]
+        if self.short_history:
+            hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, self.num_hist_frames)
+            if 2 <= hum_xy.shape[0] < self.num_hist_frames:
+                hum_xy, rob_xy, ff = SC.pad_short_window(hum_xy, rob_xy, self.num_hist_frames)
+        frames = SC.histories_as_frames(prev, rob) if self.device_frames and ff is None else None
+        if frames is None and not self.short_history:       # (short_history has the table already)
             hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, self.num_hist_frames)
         if frames is not None:
             # the frame table on the device too (JMID_EHISTORY -> HistoryTooShortError, where build_scene raises it on the host path)
             ds = self.engine.build_scene_stamped(*frames, self.time_step, self.predict_horizon)
             sb = pose_now = None
             ids_in, ids_out = np.nonzero(ds["in_cluster"])[0], np.nonzero(~ds["in_cluster"])[0]
-        elif self.device_scene:
+        elif self.device_scene or (self.device_frames and ff is not None):
             if hum_xy.shape[0] < self.num_hist_frames:
                 raise SC.HistoryTooShortError(f"{hum_xy.shape[0]} history frames available, {self.num_hist_frames} needed")
-            ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon)
+            ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon, first_frame=ff)
             sb = None
             ids_in, ids_out = np.nonzero(ds["in_cluster"])[0], np.nonzero(~ds["in_cluster"])[0]
         else:
-            sb = SC.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon, self.num_hist_frames)
+            sb = SC.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon, self.num_hist_frames, first_frame=ff)
             ids_in, ids_out = sb.ids_in, sb.ids_out
         A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
         # RNG contract (module docstring): x_T is the first draw of the CPU default generator; the per-step z of the
@@ -343,7 +355,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
             on_dev = k < K and self.device_topk and topk_fits_device(A, K, H)
             check = self.self_check and tuple(x_np.shape) not in self._checked_shapes
             in_cluster = None
-            if (on_dev or k == K) and not check:
+            # (a short window built on the host takes the staged path: jmid_predict has no first_index; a resident one is predict_scene's)
+            if (on_dev or k == K) and not check and (ff is None or sb is None):
                 # the whole call in ONE library entry (jmid_predict: encoder -> denoise -> integrator -> top-k chained on the
                 # stream, one upload, one download); JMID_ERANGE -> the staged path below in exact fp32
                 try:
@@ -372,11 +385,13 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 if sb is None:   # the self-check call and the JMID_ERANGE repeat take their inputs from the resident scene
                     sa = self.engine.scene_arrays()
                     sx_st, snbr, sem, sp0 = (np.ascontiguousarray(sa[key][ids_in]) for key in ("x_st", "nbr_sum", "edge_mask", "p0"))
+                    fi = None if ff is None else np.ascontiguousarray(sa["first_index"][ids_in])
                     if frames is not None:
                         pose_now = self.engine.scene_frames()["pose_now"]
                 else:
                     sx_st, snbr, sem, sp0 = sb.x_st, sb.nbr_sum, sb.edge_mask, sb.p0
-                ctx = self.engine.encode(sx_st, snbr, sem)
+                    fi = None if ff is None else sb.first_index
+                ctx = self.engine.encode(sx_st, snbr, sem, first_index=fi)
                 pos = self._denoise(x_np, ctx[None], sp0[None], want_pos=not on_dev or check)
                 if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
                     pos = self._self_check(x_np, ctx[None], sp0[None], pos)
@@ -450,7 +465,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
                   device_topk: bool = True, device_scene: bool = False,
                   device_frames: bool = False, noise: str = "torch", seed: int = 0,
-                  padded: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  padded: bool = False, short_history: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -477,23 +492,31 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     one per count at a group's; the padded share of the rows is wasted work.  Host arrays and torch noise only:
     not with ``device_scene``, ``device_frames`` or ``noise="device"``; a batch whose ranking does not fit the device top-k, or
     with an empty cluster, takes the grouped path.
+    ``short_history=True`` (opt-in): human_xy / robot_xy may hold 2 <= L < hist_len frames (every episode the same L: the episode start);
+    the windows are padded in front (``scene.pad_short_window``) and every row is encoded from its first frame.  Not with ``padded``.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
     if padded and (device_scene or device_frames or noise == "device"):
         raise ValueError("padded=True takes host scene arrays and torch noise only: not with device_scene, device_frames or noise='device' "
                          "(the padded entries have no scene-resident or seeded form)")
+    ff = None                                    # short_history: first_frame [E, N + 1] of the padded windows
+    if short_history and 2 <= human_xy.shape[1] < engine.hist_len:
+        if padded:
+            raise ValueError("short_history has no padded form (jmid_predict_padded takes no first_index)")
+        parts = [SC.pad_short_window(human_xy[e], robot_xy[e], engine.hist_len) for e in range(human_xy.shape[0])]
+        human_xy, robot_xy, ff = (np.stack([p[i] for p in parts]) for i in range(3))
     E, F, N, _ = human_xy.shape
     K, k, H = int(num_samples), int(num_ret_samples), int(horizon)
     precision = DEFAULTS["precision"] if precision is None else precision      # (no self check here: an engine-level call)
     global ERANGE_FALLBACKS
     if device_scene or device_frames:           # the same batch from the device kernel (jmid_build_scene); grouping and everything after it as below
         with _engine_lock_of(engine):
-            b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H)
+            b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
             if not device_frames:
                 b.update(engine.scene_arrays())
     else:
-        b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H)
+        b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
     inc = b["in_cluster"]
     forecasts = np.zeros((E, N, k, H, 2), dtype=np.float64)
     logw = np.zeros((E, N, k), dtype=np.float64)
@@ -538,7 +561,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                                    for e in eps]).numpy(), {}
         if device_frames and (k == K or (device_topk and topk_fits_device(A, K, H))):
             with _engine_lock_of(engine):      # the group's scenes resident, then predictor + assembly in one entry
-                engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H)
+                engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H, first_frame=None if ff is None else ff[eps])
                 try:
                     fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision=precision, **nz)
                 except JmidError as err:
@@ -551,13 +574,14 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             continue
         if "p0" not in b:
             with _engine_lock_of(engine):
-                engine.build_scene(human_xy, robot_xy, time_step, horizon=H)
+                engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
                 b.update(engine.scene_arrays())
         p0 = np.ascontiguousarray(b["p0"][ei, rows])
         with _engine_lock_of(engine):          # an engine may be shared with forecaster instances; it is not re-entrant
             ctx = engine.encode(b["x_st"][ei, rows].reshape(len(eps) * A, F, 6),
                                 b["nbr_sum"][ei, rows].reshape(len(eps) * A, 2, F, 6),
-                                b["edge_mask"][ei, rows].reshape(len(eps) * A, 2)).reshape(len(eps), A, -1)
+                                b["edge_mask"][ei, rows].reshape(len(eps) * A, 2),
+                                first_index=None if ff is None else b["first_index"][ei, rows].reshape(-1)).reshape(len(eps), A, -1)
             # the samples stay on the GPU; every episode of the group in ONE jmid_topk call (host twin beyond its size limits)
             on_dev = k < K and device_topk and topk_fits_device(A, K, H)
             pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=not on_dev, **nz)

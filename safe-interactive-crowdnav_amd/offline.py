@@ -110,7 +110,8 @@ def agent_counts_from_futures(y_t, batch_size: int) -> np.ndarray:
 
 
 def get_loss(engine: JmidEngine, x_st, nbr_sum, edge_mask, y_t, batch_size: Optional[int] = None, t=None, precision: str = "f32",
-             seed: Optional[int] = None, episode_ids=None, want_rows: bool = False, want_e_theta: bool = False):
+             seed: Optional[int] = None, episode_ids=None, want_rows: bool = False, want_e_theta: bool = False,
+             first_history_index=None):
     """``AutoEncoder.get_loss`` (MID/models/autoencoder.py:105-122) on the engine: encode, then ``DiffusionTraj.get_loss``
     (MID/models/diffusion.py:448-476) as one device call (``JmidEngine.loss``).  x_st [R, hist, 6], nbr_sum [R, 2, hist, 6], edge_mask
     [R, 2] the encoder's inputs, y_t [R, T, 2] the futures.  ``batch_size`` (the joint predictor's validation, MID/mid.py:275-281): R =
@@ -118,7 +119,10 @@ def get_loss(engine: JmidEngine, x_st, nbr_sum, edge_mask, y_t, batch_size: Opti
     (``generate_mask``), NaNs are zeroed as ``masked_fill`` does (preprocessing.py:29-33).  None: the unmasked branch, all R rows one scene.
     RNG contract (the reference's): ``t`` from ``np.random.choice(np.arange(1, num_steps + 1), R)`` when not given
     (``uniform_sample_t``, diffusion.py:55-57), then e from one global ``torch.randn`` of y_t's shape.  ``seed=`` draws e on the device
-    instead (scene b is episode id ``episode_ids[b]``, default b); t is still drawn on the host.  -> ``engine.LossResult``."""
+    instead (scene b is episode id ``episode_ids[b]``, default b); t is still drawn on the host.
+    ``first_history_index`` [R] (the batch's own, MID/dataset/preprocessing.py:468; the loaders admit rows with two history frames,
+    MID/mid.py:1334, 1427): row r is encoded from that frame on (``JmidEngine.encode(first_index=)``); nothing else in the loss changes.
+    -> ``engine.LossResult``."""
     y = torch.as_tensor(np.asarray(y_t.detach().cpu() if torch.is_tensor(y_t) else y_t, dtype=np.float32))
     if y.ndim != 3 or y.shape[-1] != 2:
         raise ValueError("expected y_t [R, T, 2]")
@@ -127,7 +131,9 @@ def get_loss(engine: JmidEngine, x_st, nbr_sum, edge_mask, y_t, batch_size: Opti
     n_agents = None if batch_size is None else agent_counts_from_futures(y, E)
     A = R // E
     clean = [np.nan_to_num(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float32), nan=0.0) for a in (x_st, nbr_sum, edge_mask)]
-    ctx = engine.encode(*clean).reshape(E, A, -1)
+    if first_history_index is not None and torch.is_tensor(first_history_index):
+        first_history_index = first_history_index.detach().cpu().numpy()
+    ctx = engine.encode(*clean, first_index=first_history_index).reshape(E, A, -1)
     if t is None:
         t = np.random.choice(np.arange(1, engine.schedule.num_steps + 1), R)
     t = np.asarray(t, dtype=np.int32).reshape(E, A)
@@ -143,7 +149,7 @@ def get_loss(engine: JmidEngine, x_st, nbr_sum, edge_mask, y_t, batch_size: Opti
 
 def validation(engine: JmidEngine, batches, precision: str = "f32", seed: Optional[int] = None) -> float:
     """``MID.validation`` (MID/mid.py:252-296): the mean of the per-batch losses ("Avg. Val Loss").  ``batches``: an iterable of dicts
-    with the keyword arguments of ``get_loss`` (x_st, nbr_sum, edge_mask, y_t and optionally batch_size, t).  ``seed``: batch i draws its
+    with the keyword arguments of ``get_loss`` (x_st, nbr_sum, edge_mask, y_t and optionally batch_size, t, first_history_index).  ``seed``: batch i draws its
     e on the device with scene b as episode id (number of scenes before the batch) + b."""
     losses, first = [], 0
     for b in batches:

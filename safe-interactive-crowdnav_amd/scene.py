@@ -244,6 +244,7 @@ class SceneBatch:
     cv_forecasts: Dict[int, np.ndarray] = field(default_factory=dict)   # id -> [H, 2] f64
     pose_now: Optional[np.ndarray] = None                               # [N, 2] f64
     robot_in_cluster: bool = False
+    first_index: Optional[np.ndarray] = None   # [A] int32 first history frame of every row (the reference's first_history_index)
 
 
 def edge_scaling_last(adj3: np.ndarray) -> np.ndarray:
@@ -256,15 +257,51 @@ def edge_scaling_last(adj3: np.ndarray) -> np.ndarray:
     return np.minimum(s, 1.0)
 
 
+def pad_short_window(human_xy: np.ndarray, robot_xy: np.ndarray, F: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The episode-start case of ``first_frame``: L < F shared frames (human_xy [L, N, 2], robot_xy [L, 2], oldest first) as F-frame arrays
+    that are NaN in front, with ``first_frame`` = F - L for the robot and every pedestrian.  L >= F: the last F frames, first_frame 0."""
+    human_xy = np.asarray(human_xy, dtype=np.float64)
+    robot_xy = np.asarray(robot_xy, dtype=np.float64)
+    L, N, _ = human_xy.shape
+    if L < 1 or robot_xy.shape != (L, 2):
+        raise ValueError("expected human_xy [L, N, 2] and robot_xy [L, 2] with L >= 1")
+    pad = max(int(F) - L, 0)
+    hum = np.concatenate([np.full((pad, N, 2), np.nan), human_xy[-int(F):]], axis=0)
+    rob = np.concatenate([np.full((pad, 2), np.nan), robot_xy[-int(F):]], axis=0)
+    return hum, rob, np.full(N + 1, pad, dtype=np.int32)
+
+
+def _check_first_frame(first_frame, E: int, N: int, F: int, force_all_in_cluster: bool) -> np.ndarray:
+    ff = np.asarray(first_frame)
+    if ff.shape != (E, N + 1) or not np.issubdtype(ff.dtype, np.integer):
+        raise ValueError("first_frame must hold N + 1 integers per episode, robot first")
+    if (ff < 0).any() or (ff > F - 1).any():
+        raise ValueError("first_frame must lie in 0..F-1")
+    if not force_all_in_cluster and (ff[:, 0] > F - 2).any():
+        raise ValueError("the robot needs at least 2 frames unless force_all_in_cluster is set")
+    return ff.astype(np.int32)
+
+
 def build_scene(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: int,
-                num_hist_frames: int = 6, force_all_in_cluster: bool = False) -> SceneBatch:
+                num_hist_frames: int = 6, force_all_in_cluster: bool = False, first_frame=None) -> SceneBatch:
     """mid_sim_wrapper.py:313-437 + preprocessing.py:428-694 for one scene.
 
-    human_xy [F, N, 2], robot_xy [F, 2] on the ``time_step`` grid (oldest first).
+    human_xy [F, N, 2], robot_xy [F, 2] on the ``time_step`` grid (oldest first).  ``first_frame`` [N + 1] (robot first): see
+    ``build_scenes_batched``, whose episode this then is - the rows are the EGO rows (in-cluster pedestrians with at least two frames),
+    a one-frame pedestrian is listed in ``ids_out`` with its position repeated as its constant-velocity row.
     """
     F, N, _ = human_xy.shape
     if F < num_hist_frames:
         raise HistoryTooShortError(f"{F} history frames available, {num_hist_frames} needed")
+    if first_frame is not None:
+        b = build_scenes_batched(np.asarray(human_xy, dtype=np.float64)[None], np.asarray(robot_xy, dtype=np.float64)[None], time_step,
+                                 force_all_in_cluster=force_all_in_cluster, horizon=horizon, first_frame=np.asarray(first_frame)[None])
+        rows = np.nonzero(b["in_cluster"][0])[0]
+        out = np.nonzero(~b["in_cluster"][0])[0]
+        return SceneBatch(ids_in=rows.astype(np.int64), ids_out=out.astype(np.int64), x=b["x"][0, rows], x_st=b["x_st"][0, rows],
+                          nbr_sum=b["nbr_sum"][0, rows], edge_mask=b["edge_mask"][0, rows], p0=b["p0"][0, rows],
+                          cv_forecasts={int(i): b["cv"][0, i] for i in out}, robot_in_cluster=bool(b["robot_in_cluster"][0]),
+                          first_index=b["first_index"][0, rows])
     dt = time_step
     # positions at the last frame, sorted by track id: robot (-1) first
     pos_last = np.concatenate([robot_xy[-1:], human_xy[-1]], axis=0)           # [N+1, 2]
@@ -351,12 +388,12 @@ def build_scene(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, ho
     ids_out = np.array(out_peds, dtype=np.int64)
     return SceneBatch(ids_in=ids_in, ids_out=ids_out, x=x.astype(np.float32), x_st=x_st.astype(np.float32),
                       nbr_sum=nbr_sum, edge_mask=edge_mask, p0=x[:, -1, 0:2].astype(np.float32),
-                      cv_forecasts=cv, robot_in_cluster=bool(in_mask[0]))
+                      cv_forecasts=cv, robot_in_cluster=bool(in_mask[0]), first_index=np.zeros(A, dtype=np.int32))
 
 
 # --------------------------------------------------------------------------------------------- batched builder
 def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
-                         force_all_in_cluster: bool = False, horizon: Optional[int] = None) -> Dict[str, np.ndarray]:
+                         force_all_in_cluster: bool = False, horizon: Optional[int] = None, first_frame=None) -> Dict[str, np.ndarray]:
     """``build_scene`` for E independent episodes at once (no Python loop over episodes): the feed of the
     256-4096-episode evaluation sweeps.
 
@@ -367,10 +404,22 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
     neighbours in the graph (they are not graph nodes in the reference).  Bit-identical to ``build_scene`` per episode.
     With ``horizon`` the constant-velocity forecasts of EVERY pedestrian (what the reference returns for the ones
     outside the cluster, mid_sim_wrapper.py:413-429) come back as ``cv`` [E, N, horizon, 2] float64.
+
+    ``first_frame`` [E, N + 1] integers in 0..F-1, robot first (the host twin of ``jmid_build_scene_var``, csrc/scene.hpp): node j is
+    present on frames first_frame[j] .. F-1 and its earlier positions are never read.  Velocity and acceleration are first differences
+    over the node's own span (data_utils.py:24-37; one frame: zero), x and x_st are NaN in front of it (``node.get(padding=nan)``), the
+    scene graph has no adjacency on a frame where a node is absent (environment/scene.py:84-106), and a connected neighbour is taken
+    with padding 0.0 and THEN standardised (preprocessing.py:531-550): absent, it adds (0 - ego_now) / std.  A pedestrian with one frame
+    is no ego row (``in_cluster`` False) but counts in the cluster choice and as a neighbour.  ``first_index`` [E, N] int32 is returned
+    in every case (zeros without ``first_frame``); all-zero ``first_frame`` gives the bits of None.
     """
     E, F, N, _ = human_xy.shape
     dt = time_step
+    ff = None if first_frame is None else _check_first_frame(first_frame, E, N, F, force_all_in_cluster)
     pos = np.concatenate([robot_xy[:, :, None, :], human_xy], axis=2)              # [E, F, N+1, 2], robot first
+    if ff is not None:
+        present = np.arange(F)[None, None, :] >= ff[:, :, None]                    # [E, N+1, F]
+        pos = np.where(present.transpose(0, 2, 1)[..., None], pos, np.nan)
     last = pos[:, -1]                                                              # [E, N+1, 2]
     d_last = np.sqrt(np.square(last[:, :, None] - last[:, None, :]).sum(-1))
     near = d_last < ATTENTION_RADIUS
@@ -386,24 +435,40 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
 
     def deriv(a):
         dd = np.diff(a, axis=2) / dt
-        return np.concatenate([dd[:, :, :1], dd], axis=2)
+        d = np.concatenate([dd[:, :, :1], dd], axis=2)
+        if ff is None:
+            return d
+        # the node's own span: the first present element duplicates the second, a single element is zero, NaN in front
+        nxt = np.take_along_axis(d, np.minimum(ff + 1, F - 1)[:, :, None, None], axis=2)               # [E, N+1, 1, 2]
+        first_val = np.where((ff < F - 1)[:, :, None, None], nxt, 0.0)
+        d = np.where((np.arange(F)[None, None, :] == ff[:, :, None])[..., None], first_val, d)
+        return np.where(present[..., None], d, np.nan)
 
-    V = deriv(P)
-    A_ = deriv(V)
+    with np.errstate(invalid="ignore"):
+        V = deriv(P)
+        A_ = deriv(V)
     S = np.concatenate([P, V, A_], axis=3)                                         # [E, N+1, F, 6]
     # temporal scene graph over the last three frames, in-cluster nodes only
     P3 = P[:, :, F - 3:F].transpose(0, 2, 1, 3)                                    # [E, 3, N+1, 2]
-    d3 = np.sqrt(np.square(P3[:, :, :, None] - P3[:, :, None, :]).sum(-1))         # [E, 3, n, n]
+    with np.errstate(invalid="ignore"):
+        d3 = np.sqrt(np.square(P3[:, :, :, None] - P3[:, :, None, :]).sum(-1))     # [E, 3, n, n]; NaN where a node is absent: not <= radius
+        near3 = d3 <= ATTENTION_RADIUS
     types = np.full(N + 1, float(TYPE_VALUE_PED))
     types[0] = float(TYPE_VALUE_ROBOT)
     tmat = np.tile(types[None, :], (N + 1, 1))
     np.fill_diagonal(tmat, 0)
     pair_in = (inc[:, :, None] & inc[:, None, :]).astype(np.float64)               # [E, n, n]
-    adj3 = (d3 <= ATTENTION_RADIUS).astype(np.float64) * tmat[None, None] * pair_in[:, None]
+    adj3 = near3.astype(np.float64) * tmat[None, None] * pair_in[:, None]
     f = EDGE_ADDITION_FILTER
     scal = np.minimum(f[0] * adj3[:, 2] + f[1] * adj3[:, 1] + f[2] * adj3[:, 0], 1.0)
     scal = np.where(adj3[:, 2] == 0, 0.0, scal)                                    # [E, n, n]
     conn = scal > 1e-2
+    ego = inc[:, 1:]
+    Sn = S                                                                          # what a neighbour contributes
+    if ff is not None:
+        ego = ego & (ff[:, 1:] <= F - 2)                                            # an ego row needs two frames
+        conn = conn & np.concatenate([np.ones((E, 1), dtype=bool), ego], axis=1)[:, :, None]     # the others have no graph row
+        Sn = np.where(present[..., None], S, 0.0)                                   # padding 0.0, standardised below
     xs = S[:, 1:]                                                                   # pedestrians [E, N, F, 6]
     rel = np.zeros((E, N, 1, 6))
     rel[:, :, 0, 0:2] = xs[:, :, -1, 0:2]
@@ -413,12 +478,17 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
     nbr_sum = np.zeros((E, N, 2, F, 6), dtype=np.float32)
     ego_now = xs[:, :, -1:, :]                                                      # [E, N, 1, 6]
     for j in range(N + 1):                                                          # neighbours in node order
-        relj = ((S[:, j][:, None] - ego_now) / STATE_STD).astype(np.float32)        # [E, N, F, 6]
+        relj = ((Sn[:, j][:, None] - ego_now) / STATE_STD).astype(np.float32)       # [E, N, F, 6]
         w = conn[:, 1:, j].astype(np.float32)[:, :, None, None]
         e_idx = 1 if j == 0 else 0                                                  # robot -> edge type PED->ROBOT
         nbr_sum[:, :, e_idx] = nbr_sum[:, :, e_idx] + relj * w
     out = dict(x=xs.astype(np.float32), x_st=x_st.astype(np.float32), nbr_sum=nbr_sum, edge_mask=edge_mask,
-               p0=xs[:, :, -1, 0:2].astype(np.float32), in_cluster=inc[:, 1:], robot_in_cluster=inc[:, 0])
+               p0=xs[:, :, -1, 0:2].astype(np.float32), in_cluster=ego, robot_in_cluster=inc[:, 0],
+               first_index=np.zeros((E, N), dtype=np.int32) if ff is None else np.ascontiguousarray(ff[:, 1:]))
+    if ff is not None:                                                              # (one NaN, whatever the arithmetic made of its payload)
+        gone = ~present[:, 1:, :, None]
+        out["x"] = np.where(gone, np.float32(np.nan), out["x"])
+        out["x_st"] = np.where(gone, np.float32(np.nan), out["x_st"])
     if horizon is not None:      # same operations, in the same order, as build_scene's per-pedestrian loop
         step = np.repeat((xs[:, :, -1, 2:4] * dt)[:, :, None, :], horizon, axis=2)     # [E, N, H, 2]
         out["cv"] = xs[:, :, -1:, 0:2] + np.cumsum(step, axis=2)
