@@ -15,8 +15,9 @@ MEM_HOST, MEM_DEVICE = 0, 1
 PREC_F32, PREC_F16X3, PREC_F16, PREC_F16X2, PREC_F16MX = 0, 1, 2, 3, 4
 PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3, "f16": PREC_F16, "f16x2": PREC_F16X2, "f16mx": PREC_F16MX}
 
-ERR_NAMES = {-1: "JMID_EINVAL", -2: "JMID_ENOWEIGHT", -3: "JMID_EHIP", -4: "JMID_ENOMEM", -5: "JMID_ERANGE", -6: "JMID_ETIMEOUT",
-             -7: "JMID_EHISTORY"}
+EINVAL, ENOWEIGHT, EHIP, ENOMEM, ERANGE, ETIMEOUT, EHISTORY = -1, -2, -3, -4, -5, -6, -7        # JMID_E* of include/jmid_hip.h
+ERR_NAMES = {EINVAL: "JMID_EINVAL", ENOWEIGHT: "JMID_ENOWEIGHT", EHIP: "JMID_EHIP", ENOMEM: "JMID_ENOMEM", ERANGE: "JMID_ERANGE",
+             ETIMEOUT: "JMID_ETIMEOUT", EHISTORY: "JMID_EHISTORY"}
 
 # name -> (restype, argtypes): every symbol declared in include/jmid_hip.h
 SIGNATURES = {

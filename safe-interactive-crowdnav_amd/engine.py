@@ -8,6 +8,7 @@ batch of independent episodes.  No arithmetic happens in Python.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional, Tuple, Union
 
 import numpy as np
@@ -33,6 +34,27 @@ TIMEOUT_EVENTS: list = []
 
 def _is_cuda(t) -> bool:
     return torch is not None and isinstance(t, torch.Tensor) and t.is_cuda
+
+
+def _out(shape, dtype=np.float32, device=None):
+    """An uninitialised output array: a torch tensor on ``device`` (a device-mode call: the device its input lives on), or NumPy."""
+    if device is None:
+        return np.empty(shape, dtype=dtype)
+    name = np.dtype(dtype).name
+    return torch.empty(shape, dtype=getattr(torch, "int32" if name == "uint32" else name), device=device)     # (Philox words: the bits)
+
+
+def _ptr(a) -> Optional[C.c_void_p]:
+    """The raw pointer of a torch tensor or a NumPy array; None (an output that was not asked for) stays None."""
+    if a is None:
+        return None
+    return C.c_void_p(a.data_ptr() if torch is not None and isinstance(a, torch.Tensor) else a.ctypes.data)
+
+
+def kde_bandwidths(T: int):
+    """The per-step KDE bandwidths of the joint top-k exactly as the reference computes them (fp32 torch ops, mid_sim_wrapper.py:26-30):
+    a contiguous float32 CPU tensor [T]."""
+    return torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T))
 
 
 def agent_counts(n_agents, E: int) -> np.ndarray:
@@ -122,7 +144,7 @@ class JmidEngine:
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int) -> None:
-        if rc == -5:
+        if rc == _lib.ERANGE:
             ERANGE_EVENTS.append((id(self), self._lib.jmid_last_error(self._h).decode()))
         if rc != 0:
             raise JmidError(rc, self._lib.jmid_last_error(self._h).decode())
@@ -131,7 +153,7 @@ class JmidEngine:
         """A compute entry of the C ABI.  JMID_ETIMEOUT is not an arithmetic condition: the library has switched this handle to the
         unfused kernels (same bits), so the call is repeated once, as it is, and the event recorded."""
         rc = fn(*args)
-        if rc == -6:
+        if rc == _lib.ETIMEOUT:
             TIMEOUT_EVENTS.append((id(self), self._lib.jmid_last_error(self._h).decode()))
             rc = fn(*args)
         self._check(rc)
@@ -219,17 +241,11 @@ class JmidEngine:
             raise ValueError("bad encoder input shapes")
         fi = None if first_index is None else self._first_index(first_index, n)
         a, b, c = _Buf(x_st, dev), _Buf(nbr_sum, dev), _Buf(edge_mask, dev)
-        if dev:
-            out = torch.empty((n, self.dims.ctx_dim), dtype=torch.float32, device=x_st.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.empty((n, self.dims.ctx_dim), dtype=np.float32)
-            optr = C.c_void_p(out.ctypes.data)
+        out = _out((n, self.dims.ctx_dim), device=x_st.device if dev else None)
         if fi is not None:
-            self._check(self._lib.jmid_encode_var(self._h, n, a.ptr, b.ptr, c.ptr, C.c_void_p(fi.ctypes.data), optr, self._mem(dev)))
+            self._check(self._lib.jmid_encode_var(self._h, n, a.ptr, b.ptr, c.ptr, _ptr(fi), _ptr(out), self._mem(dev)))
             return out
-        self._check(self._lib.jmid_encode(self._h, n, a.ptr, b.ptr, c.ptr, optr,
-                                          self._mem(dev)))
+        self._check(self._lib.jmid_encode(self._h, n, a.ptr, b.ptr, c.ptr, _ptr(out), self._mem(dev)))
         return out
 
     def _shapes(self, x, ctx) -> Tuple[int, int, int, int]:
@@ -247,15 +263,9 @@ class JmidEngine:
         step-table entry i.  ``device=True``: a CUDA tensor.  ``words=True`` (diagnostics flavour): the raw Philox words, uint32."""
         seed, ids = seeded_noise_args(None, seed, episode_ids)
         E = int(ids.size)
-        shape = (E, int(rows), int(T), 2)
-        if device:
-            out = torch.empty(shape, dtype=torch.int32 if words else torch.float32, device=f"cuda:{self.device_id}")
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.empty(shape, dtype=np.uint32 if words else np.float32)
-            optr = C.c_void_p(out.ctypes.data)
+        out = _out((E, int(rows), int(T), 2), np.uint32 if words else np.float32, f"cuda:{self.device_id}" if device else None)
         fn = self._lib.jmid_dbg_noise_words if words else self._lib.jmid_noise_fill
-        self._check(fn(self._h, seed, E, int(rows), int(T), C.c_void_p(ids.ctypes.data), int(draw), optr, self._mem(bool(device))))
+        self._check(fn(self._h, seed, E, int(rows), int(T), _ptr(ids), int(draw), _ptr(out), self._mem(bool(device))))
         return out
 
     def denoise(self, x_T: Optional[ArrayLike], ctx: ArrayLike, p0: Optional[ArrayLike] = None, dt: float = 0.25,
@@ -288,35 +298,22 @@ class JmidEngine:
         want_pos = want_pos and p0 is not None
         bx, bc = (_Buf(x_T, dev) if seeded is None else None), _Buf(ctx, dev)
         bp = _Buf(p0, dev) if p0 is not None else None
-        shape = (E, K, A, T, 2)
-
-        def alloc():
-            if dev:
-                t = torch.empty(shape, dtype=torch.float32, device=x_like.device)
-                return t, C.c_void_p(t.data_ptr())
-            t = np.empty(shape, dtype=np.float32)
-            return t, C.c_void_p(t.ctypes.data)
-
-        vel, vptr = alloc() if want_vel else (None, None)
-        pos, pptr = alloc() if want_pos else (None, None)
+        if z is not None and tuple(z.shape) != (self.n_steps, E, K * A, T, 2):
+            raise ValueError("z must be [n_steps, E, K*A, T, 2]")
+        where = x_like.device if dev else None
+        vel = _out((E, K, A, T, 2), device=where) if want_vel else None
+        pos = _out((E, K, A, T, 2), device=where) if want_pos else None
+        tail = (bc.ptr, bp.ptr if bp else None, float(dt), _lib.PRECISIONS[precision], _ptr(vel), _ptr(pos), self._mem(dev))
         if seeded is not None:
-            self._compute(self._lib.jmid_denoise_seeded, self._h, E, A, K, T, seeded[0], C.c_void_p(seeded[1].ctypes.data), bc.ptr,
-                          bp.ptr if bp else None, float(dt), _lib.PRECISIONS[precision], vptr, pptr, self._mem(dev))
+            self._compute(self._lib.jmid_denoise_seeded, self._h, E, A, K, T, seeded[0], _ptr(seeded[1]), *tail)
         elif z is not None:
-            if tuple(z.shape) != (self.n_steps, E, K * A, T, 2):
-                raise ValueError("z must be [n_steps, E, K*A, T, 2]")
             bz = _Buf(z, dev)
-            self._compute(self._lib.jmid_denoise_ddpm, self._h, E, A, K, T, bx.ptr, bz.ptr, bc.ptr, bp.ptr if bp else None,
-                                                    float(dt), _lib.PRECISIONS[precision], vptr, pptr,
-                                                    self._mem(dev))
+            self._compute(self._lib.jmid_denoise_ddpm, self._h, E, A, K, T, bx.ptr, bz.ptr, *tail)
         elif n_agents is not None:
             na = agent_counts(n_agents, E)
-            self._compute(self._lib.jmid_denoise_padded, self._h, E, A, K, T, C.c_void_p(na.ctypes.data), bx.ptr, bc.ptr, bp.ptr if bp else None,
-                          float(dt), _lib.PRECISIONS[precision], vptr, pptr, self._mem(dev))
+            self._compute(self._lib.jmid_denoise_padded, self._h, E, A, K, T, _ptr(na), bx.ptr, *tail)
         else:
-            self._compute(self._lib.jmid_denoise, self._h, E, A, K, T, bx.ptr, bc.ptr, bp.ptr if bp else None, float(dt),
-                                               _lib.PRECISIONS[precision], vptr, pptr,
-                                               self._mem(dev))
+            self._compute(self._lib.jmid_denoise, self._h, E, A, K, T, bx.ptr, *tail)
         return vel, pos
 
     def topk(self, pos: Optional[ArrayLike], k: int, dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None):
@@ -326,7 +323,6 @@ class JmidEngine:
         engine's workspace (nothing but the k kept samples comes back to the host).
         ``n_agents`` [E] (``jmid_topk_padded``): episode e is ranked in 2 n_agents[e] dimensions over its real agents; kept samples
         and log-weights of the padded agents are NaN."""
-        import math
         if pos is None:
             if dims is None:
                 raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
@@ -336,25 +332,15 @@ class JmidEngine:
             dev = _is_cuda(pos)
             E, K, A, T, _ = (int(v) for v in pos.shape)
             bp = _Buf(pos, dev)
-        # the bandwidths exactly as the reference computes them (fp32 torch ops, mid_sim_wrapper.py:26-30)
-        bw = torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T))
-        if dev:
-            bwb = bw.to(pos.device)
-            sel = torch.empty((E, A, k, T, 2), dtype=torch.float32, device=pos.device)
-            lw = torch.empty((E, A, k), dtype=torch.float32, device=pos.device)
-            ptrs = (C.c_void_p(bwb.data_ptr()), C.c_void_p(sel.data_ptr()), C.c_void_p(lw.data_ptr()))
+        na = agent_counts(n_agents, E) if n_agents is not None else None
+        where = pos.device if dev else None
+        bw = kde_bandwidths(T).to(pos.device) if dev else kde_bandwidths(T)
+        sel, lw = _out((E, A, k, T, 2), device=where), _out((E, A, k), device=where)
+        tail = (bp.ptr if bp is not None else None, _ptr(bw), _ptr(sel), _ptr(lw), self._mem(dev))
+        if na is not None:
+            self._check(self._lib.jmid_topk_padded(self._h, E, A, K, T, int(k), _ptr(na), *tail))
         else:
-            bwb = np.ascontiguousarray(bw.numpy())
-            sel = np.empty((E, A, k, T, 2), dtype=np.float32)
-            lw = np.empty((E, A, k), dtype=np.float32)
-            ptrs = (C.c_void_p(bwb.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data))
-        if n_agents is not None:
-            na = agent_counts(n_agents, E)
-            self._check(self._lib.jmid_topk_padded(self._h, E, A, K, T, int(k), C.c_void_p(na.ctypes.data), bp.ptr if bp is not None else None,
-                                                   *ptrs, self._mem(dev)))
-            return sel, lw
-        self._check(self._lib.jmid_topk(self._h, E, A, K, T, int(k), bp.ptr if bp is not None else None, *ptrs,
-                                        self._mem(dev)))
+            self._check(self._lib.jmid_topk(self._h, E, A, K, T, int(k), *tail))
         return sel, lw
 
     def predict_padded(self, x_st: np.ndarray, nbr_sum: np.ndarray, edge_mask: np.ndarray, x_T: np.ndarray, p0: np.ndarray, k: int,
@@ -372,7 +358,6 @@ class JmidEngine:
         return self._predict(None, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision)
 
     def _predict(self, n_agents, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision):
-        import math
         E, KA, T, _ = (int(v) for v in x_T.shape)
         A = int(p0.shape[1])
         K = KA // A
@@ -382,18 +367,20 @@ class JmidEngine:
         b = [_Buf(a, False) for a in (x_st, nbr_sum, edge_mask, x_T, p0)]
         if n_agents is not None:
             na = agent_counts(n_agents, E)
-            fn, head = self._lib.jmid_predict_padded, (self._h, E, A, K, T, int(k), C.c_void_p(na.ctypes.data))
+            fn, head = self._lib.jmid_predict_padded, (self._h, E, A, K, T, int(k), _ptr(na))
         else:
             fn, head = self._lib.jmid_predict, (self._h, E, A, K, T, int(k))
+        return self._ranked_or_all(fn, (*head, *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k)
+
+    def _ranked_or_all(self, fn, args, E: int, A: int, K: int, T: int, k: int):
+        """The output half of a chained predictor entry (``args`` = everything in front of it): k < K -> the joint-KDE top-k, (kept
+        [E, A, k, T, 2], log-weights [E, A, k]); k == K -> every sample, (pos [E, K, A, T, 2], None)."""
         if k < K:
-            bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
-            sel = np.empty((E, A, k, T, 2), dtype=np.float32)
-            lw = np.empty((E, A, k), dtype=np.float32)
-            self._compute(fn, *head, *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision],
-                          C.c_void_p(bw.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data), None)
+            bw, sel, lw = kde_bandwidths(T), _out((E, A, k, T, 2)), _out((E, A, k))
+            self._compute(fn, *args, _ptr(bw), _ptr(sel), _ptr(lw), None)
             return sel, lw
-        pos = np.empty((E, K, A, T, 2), dtype=np.float32)
-        self._compute(fn, *head, *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision], None, None, None, C.c_void_p(pos.ctypes.data))
+        pos = _out((E, K, A, T, 2))
+        self._compute(fn, *args, None, None, None, _ptr(pos))
         return pos, None
 
     def build_scene(self, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: Optional[int] = None,
@@ -476,21 +463,10 @@ class JmidEngine:
         in-cluster count of EVERY episode (``n_in``) and ``k`` kept futures of the K.  k < K -> (kept [E, A, k, T, 2], log-weights
         [E, A, k]); k == K -> (pos [E, K, A, T, 2], None).  The same bits as ``predict`` fed the in-cluster rows of ``scene_arrays``.
         ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is drawn on the device (``jmid_predict_scene_seeded``)."""
-        import math
         E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T)
         k = int(k)
         fn = getattr(self._lib, "jmid_predict_scene" + sfx)
-        if k < K:
-            bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
-            sel = np.empty((E, A, k, T, 2), dtype=np.float32)
-            lw = np.empty((E, A, k), dtype=np.float32)
-            self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision],
-                          C.c_void_p(bw.ctypes.data), C.c_void_p(sel.ctypes.data), C.c_void_p(lw.ctypes.data), None)
-            return sel, lw
-        pos = np.empty((E, K, A, T, 2), dtype=np.float32)
-        self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision], None, None, None,
-                      C.c_void_p(pos.ctypes.data))
-        return pos, None
+        return self._ranked_or_all(fn, (self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k)
 
     def build_scene_stamped(self, stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
                             horizon: Optional[int] = None, force_all_in_cluster: bool = False,
@@ -525,7 +501,7 @@ class JmidEngine:
                                                 int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
                                                 C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
                                                 C.c_void_p(n_grid.ctypes.data), C.c_void_p(cv.ctypes.data) if cv is not None else None, _lib.MEM_HOST)
-        if rc == -7:                                 # JMID_EHISTORY
+        if rc == _lib.EHISTORY:
             err = HistoryTooShortError(self._lib.jmid_last_error(self._h).decode())
             err.n_grid = n_grid[0] if single else n_grid
             raise err
@@ -552,19 +528,14 @@ class JmidEngine:
         exactly what ``predict_ret_best()`` returns.  The resident scene must have been built with ``horizon`` = T.  After a one-scene
         build the episode axis of the results is absent.  ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is
         drawn on the device (``jmid_forecast_scene_seeded``)."""
-        import math
         E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T)
         k = int(k)
         fn = getattr(self._lib, "jmid_forecast_scene" + sfx)
         shape = getattr(self, "_scene_shape", None)
         N, single = (shape[1], shape[3]) if shape is not None else (1, False)
-        bw = None
-        if k < K:
-            bw = np.ascontiguousarray(torch.exp(torch.linspace(math.log(0.01), math.log(0.1), steps=T)).numpy())   # mid_sim_wrapper.py:26-30
-        fc = np.empty((E, N, max(k, 0), T + 1, 2), dtype=np.float64)
-        lw = np.empty((E, N, max(k, 0)), dtype=np.float64)
-        self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision],
-                      C.c_void_p(bw.ctypes.data) if bw is not None else None, C.c_void_p(fc.ctypes.data), C.c_void_p(lw.ctypes.data))
+        bw = kde_bandwidths(T) if k < K else None
+        fc, lw = _out((E, N, max(k, 0), T + 1, 2), np.float64), _out((E, N, max(k, 0)), np.float64)
+        self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision], _ptr(bw), _ptr(fc), _ptr(lw))
         return (fc[0], lw[0]) if single else (fc, lw)
 
     def net_eval(self, x: ArrayLike, ctx: ArrayLike, step_idx: int = 0, precision: str = "f32", n_agents=None):
@@ -573,20 +544,14 @@ class JmidEngine:
         dev = _is_cuda(x)
         E, A, K, T = self._shapes(x, ctx)
         bx, bc = _Buf(x, dev), _Buf(ctx, dev)
-        if dev:
-            out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.empty(tuple(x.shape), dtype=np.float32)
-            optr = C.c_void_p(out.ctypes.data)
+        out = _out(tuple(x.shape), device=x.device if dev else None)
         if n_agents is not None:
             na = agent_counts(n_agents, E)
-            self._compute(self._lib.jmid_net_eval_padded, self._h, E, A, K, T, C.c_void_p(na.ctypes.data), int(step_idx), bx.ptr, bc.ptr,
-                          _lib.PRECISIONS[precision], optr, self._mem(dev))
+            self._compute(self._lib.jmid_net_eval_padded, self._h, E, A, K, T, _ptr(na), int(step_idx), bx.ptr, bc.ptr,
+                          _lib.PRECISIONS[precision], _ptr(out), self._mem(dev))
             return out
-        self._compute(self._lib.jmid_net_eval, self._h, E, A, K, T, int(step_idx), bx.ptr, bc.ptr,
-                                            _lib.PRECISIONS[precision], optr,
-                                            self._mem(dev))
+        self._compute(self._lib.jmid_net_eval, self._h, E, A, K, T, int(step_idx), bx.ptr, bc.ptr, _lib.PRECISIONS[precision], _ptr(out),
+                      self._mem(dev))
         return out
 
     def set_loss_schedule(self, schedule: Optional[VarianceSchedule] = None) -> None:
@@ -625,21 +590,14 @@ class JmidEngine:
         bx, bc = _Buf(x0, dev), _Buf(ctx, dev)
         be = _Buf(e, dev) if e is not None else None
         na = agent_counts(n_agents, E) if n_agents is not None else None
-
-        def alloc(shape, dtype):
-            if dev:
-                a = torch.empty(shape, dtype=getattr(torch, dtype), device=x0.device)
-                return a, C.c_void_p(a.data_ptr())
-            a = np.empty(shape, dtype=dtype)
-            return a, C.c_void_p(a.ctypes.data)
-
-        out, optr = alloc((2,), "float64")
-        rows, rptr = alloc((E, A), "float64") if want_rows else (None, None)
-        eth, eptr = alloc((E, A, T, 2), "float32") if want_e_theta else (None, None)
-        head = (self._h, E, A, T, C.c_void_p(na.ctypes.data) if na is not None else None, C.c_void_p(tt.ctypes.data), bx.ptr)
-        tail = (bc.ptr, _lib.PRECISIONS[precision], optr, rptr, eptr, self._mem(dev))
+        where = x0.device if dev else None
+        out = _out((2,), np.float64, where)
+        rows = _out((E, A), np.float64, where) if want_rows else None
+        eth = _out((E, A, T, 2), device=where) if want_e_theta else None
+        head = (self._h, E, A, T, _ptr(na), _ptr(tt), bx.ptr)
+        tail = (bc.ptr, _lib.PRECISIONS[precision], _ptr(out), _ptr(rows), _ptr(eth), self._mem(dev))
         if seeded is not None:
-            self._compute(self._lib.jmid_loss_seeded, *head, seeded[0], C.c_void_p(seeded[1].ctypes.data), *tail)
+            self._compute(self._lib.jmid_loss_seeded, *head, seeded[0], _ptr(seeded[1]), *tail)
         else:
             self._compute(self._lib.jmid_loss, *head, be.ptr, *tail)
         if dev:
@@ -653,14 +611,8 @@ class JmidEngine:
         if tuple(gt.shape) != (E, A, T, 2):
             raise ValueError("gt must be [E, A, T, 2]")
         bp, bg = _Buf(pos, dev), _Buf(gt, dev)
-        if dev:
-            out = torch.empty((E, 4), dtype=torch.float32, device=pos.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.empty((E, 4), dtype=np.float32)
-            optr = C.c_void_p(out.ctypes.data)
-        self._check(self._lib.jmid_episode_metrics(self._h, E, A, K, T, bp.ptr, bg.ptr, optr,
-                                                   self._mem(dev)))
+        out = _out((E, 4), device=pos.device if dev else None)
+        self._check(self._lib.jmid_episode_metrics(self._h, E, A, K, T, bp.ptr, bg.ptr, _ptr(out), self._mem(dev)))
         return out
 
     def eval_statistics(self, pos: Optional[ArrayLike], gt: ArrayLike, dims: Optional[Tuple[int, int, int, int]] = None):
@@ -684,15 +636,9 @@ class JmidEngine:
         if tuple(gt.shape) != (E, A, T, 2):
             raise ValueError("gt must be [E, A, T, 2]")
         bg = _Buf(gt, dev)
-        if dev:
-            agent = torch.empty((E, A, 10), dtype=torch.float32, device=gt.device)
-            scene = torch.empty((E, 6), dtype=torch.float32, device=gt.device)
-            ptrs = (C.c_void_p(agent.data_ptr()), C.c_void_p(scene.data_ptr()))
-        else:
-            agent = np.empty((E, A, 10), dtype=np.float32)
-            scene = np.empty((E, 6), dtype=np.float32)
-            ptrs = (C.c_void_p(agent.ctypes.data), C.c_void_p(scene.ctypes.data))
-        self._check(self._lib.jmid_eval_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, bg.ptr, *ptrs,
+        where = gt.device if dev else None
+        agent, scene = _out((E, A, 10), device=where), _out((E, 6), device=where)
+        self._check(self._lib.jmid_eval_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, bg.ptr, _ptr(agent), _ptr(scene),
                                                    self._mem(dev)))
         return agent, scene
 
@@ -731,19 +677,14 @@ class JmidEngine:
         if dev:
             fut = (interp_future != 0).to(torch.uint8).contiguous()
             skip = (interp_history != 0).reshape(E, A, -1).all(dim=-1).to(torch.uint8).contiguous() if interp_history is not None else None
-            agent = torch.empty((E, A, 12), dtype=torch.float32, device=gt.device)
-            cut = torch.empty((E, A, n_cut, 5), dtype=torch.float32, device=gt.device)
-            scene = torch.empty((E, 6), dtype=torch.float32, device=gt.device)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
         else:
             to_np = lambda m: m.detach().cpu().numpy() if torch is not None and isinstance(m, torch.Tensor) else np.asarray(m)
             fut = np.ascontiguousarray(to_np(interp_future) != 0, dtype=np.uint8)
             skip = (np.ascontiguousarray((to_np(interp_history) != 0).reshape(E, A, -1).all(axis=-1), dtype=np.uint8)
                     if interp_history is not None else None)
-            agent = np.empty((E, A, 12), dtype=np.float32)
-            cut = np.empty((E, A, n_cut, 5), dtype=np.float32)
-            scene = np.empty((E, 6), dtype=np.float32)
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None and t.size else None
+        where = gt.device if dev else None
+        agent, cut, scene = _out((E, A, 12), device=where), _out((E, A, n_cut, 5), device=where), _out((E, 6), device=where)
+        ptr = lambda t: _ptr(t) if t is not None and (t.numel() if dev else t.size) else None      # (an empty array goes as NULL)
         self._check(self._lib.jmid_eval_statistics_masked(self._h, E, A, K, T, bp.ptr if bp is not None else None, bg.ptr, ptr(fut),
                                                           ptr(skip), n_cut, cuts, ptr(agent), ptr(cut), ptr(scene), self._mem(dev)))
         return agent, cut, scene
@@ -768,15 +709,9 @@ class JmidEngine:
             bp = _Buf(pos, dev)
         shapes = (((E, K, A * (A - 1) // 2), np.float32) if pairs else None, ((E, K, A), np.uint8) if agents else None,
                   ((E, K, 4), np.float32), ((E, 5), np.float32))
-        if dev:
-            outs = [torch.empty(s[0], dtype=torch.uint8 if s[1] is np.uint8 else torch.float32, device=pos.device) if s else None
-                    for s in shapes]
-            ptrs = [C.c_void_p(o.data_ptr()) if o is not None else None for o in outs]
-        else:
-            outs = [np.empty(s[0], dtype=s[1]) if s else None for s in shapes]
-            ptrs = [C.c_void_p(o.ctypes.data) if o is not None else None for o in outs]
+        outs = [_out(*s, pos.device if dev else None) if s else None for s in shapes]
         self._check(self._lib.jmid_collision_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, float(threshold),
-                                                        *ptrs, self._mem(dev)))
+                                                        *[_ptr(o) for o in outs], self._mem(dev)))
         return tuple(outs)
 
     # ------------------------------------------------------------------ measurement

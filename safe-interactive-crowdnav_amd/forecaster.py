@@ -53,13 +53,14 @@ import os
 import time
 import warnings
 from threading import Lock, RLock
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 import yaml
 
 from . import scene as SC
+from ._lib import ERANGE
 from .engine import JmidEngine, JmidError
 from .kde import most_likely_samples
 from .weights import JMIDWeights, NetDims
@@ -302,125 +303,108 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         with self._engine_lock:     # the engine holds ONE resident scene: nobody else builds between this call's build and its predict
             return self._predict_ret_best()
 
-    def _predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
-        t0 = time.perf_counter()
-        prev, rob = self._snapshot()
-        ff = None                            # short_history: the padded window's first_frame [N + 1]
+    def _scene(self, prev, rob):
+        """Scene stage: the histories -> (``Route.scene``, ids_in: the in-cluster track ids, ascending; cv: the constant-velocity rows as
+        ``scene.assemble_forecasts`` takes them; pose_now [N, 2] or None while it lies on the device; the host ``SceneBatch`` or None
+        when the scene is resident; the padded short window's first_frame [N + 1] or None).  Raises HistoryTooShortError before
+        anything is drawn."""
+        F, H, ff = self.num_hist_frames, self.predict_horizon, None
         if self.short_history:
-            hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, self.num_hist_frames)
-            if 2 <= hum_xy.shape[0] < self.num_hist_frames:
-                hum_xy, rob_xy, ff = SC.pad_short_window(hum_xy, rob_xy, self.num_hist_frames)
-        frames = SC.histories_as_frames(prev, rob) if self.device_frames and ff is None else None
-        if frames is None and not self.short_history:       # (short_history has the table already)
-            hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, self.num_hist_frames)
-        if frames is not None:
-            # the frame table on the device too (JMID_EHISTORY -> HistoryTooShortError, where build_scene raises it on the host path)
-            ds = self.engine.build_scene_stamped(*frames, self.time_step, self.predict_horizon)
-            sb = pose_now = None
-            ids_in, ids_out = np.nonzero(ds["in_cluster"])[0], np.nonzero(~ds["in_cluster"])[0]
-        elif self.device_scene or (self.device_frames and ff is not None):
-            if hum_xy.shape[0] < self.num_hist_frames:
-                raise SC.HistoryTooShortError(f"{hum_xy.shape[0]} history frames available, {self.num_hist_frames} needed")
-            ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon, first_frame=ff)
-            sb = None
-            ids_in, ids_out = np.nonzero(ds["in_cluster"])[0], np.nonzero(~ds["in_cluster"])[0]
-        else:
-            sb = SC.build_scene(hum_xy, rob_xy, self.time_step, self.predict_horizon, self.num_hist_frames, first_frame=ff)
-            ids_in, ids_out = sb.ids_in, sb.ids_out
-        A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
-        # RNG contract (module docstring): x_T is the first draw of the CPU default generator; the per-step z of the
-        # reference (unused by DDIM) comes from the generator of the device the reference would run on
-        stride = int(100 / self.step_size)
+            hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, F)
+            if 2 <= hum_xy.shape[0] < F:
+                hum_xy, rob_xy, ff = SC.pad_short_window(hum_xy, rob_xy, F)
+        frames = SC.histories_as_frames(prev, rob) if self.device_frames and ff is None else None     # (a short window is never stamped)
+        source = scene_source(self.device_scene, self.device_frames, short=ff is not None, frames=frames is not None)
+        if source == "stamped":
+            # the frame table on the device too (JMID_EHISTORY -> HistoryTooShortError, where build_scene raises it on the host path);
+            # the pose is read back only by the staged path (forecast_scene prepends it on the device)
+            ds = self.engine.build_scene_stamped(*frames, self.time_step, H)
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], None, None, None
+        if not self.short_history:                          # (short_history has the table already)
+            hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, F)
+        if source == "resident":
+            if hum_xy.shape[0] < F:
+                raise SC.HistoryTooShortError(f"{hum_xy.shape[0]} history frames available, {F} needed")
+            ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, H, first_frame=ff)
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], pose_now, None, ff
+        sb = SC.build_scene(hum_xy, rob_xy, self.time_step, H, F, first_frame=ff)
+        return source, sb.ids_in, sb.cv_forecasts, pose_now, sb, ff
+
+    def _draw_x_T(self, A: int) -> np.ndarray:
+        """Noise stage -> x_T [1, K * A, H, 2].  RNG contract (module docstring): x_T is the first draw of the CPU default generator; the
+        per-step z of the reference (unused by DDIM) comes from the generator of the device the reference would run on."""
+        K, H, stride = self.num_samples, self.predict_horizon, int(100 / self.step_size)
         if self.rng_compat == "device":
             # the library's counter generator: this call's block of n_steps + 1 draw numbers (x_T is its first; a DDPM sampler would take
-            # the others), drawn ONCE - the self check and the JMID_ERANGE repeat below reuse the array
+            # the others), drawn ONCE - the self check and the JMID_ERANGE repeat reuse the array
             with self._engine_lock:
                 x_np = self.engine.noise(self.noise_seed, [self.episode_id], K * A, H, draw=self._noise_draw)
             self._noise_draw += len(range(100, 0, -stride)) + 1
+            return x_np
+        x_T = torch.randn([K * A, H, 2])
+        n_z = sum(1 for t in range(100, 0, -stride) if t > 1)
+        if self.rng_compat == "cpu":
+            for _ in range(n_z):
+                torch.randn_like(x_T)
         else:
-            x_T = torch.randn([K * A, H, 2])
-            n_z = sum(1 for t in range(100, 0, -stride) if t > 1)
-            if self.rng_compat == "cpu":
-                for _ in range(n_z):
-                    torch.randn_like(x_T)
-            else:
-                advance_cuda_generator(self.engine.device_id, tuple(x_T.shape), n_z)
-            x_np = x_T.numpy()[None]
+            advance_cuda_generator(self.engine.device_id, tuple(x_T.shape), n_z)
+        return x_T.numpy()[None]
+
+    def _encoder_inputs(self, ids_in, sb, ff):
+        """The staged path's (x_st, nbr_sum, edge_mask, p0, first_index): the host batch, or the in-cluster rows of the resident scene read
+        back (the self-check call and the JMID_ERANGE repeat take their inputs from there)."""
+        if sb is not None:
+            return sb.x_st, sb.nbr_sum, sb.edge_mask, sb.p0, None if ff is None else sb.first_index
+        sa = self.engine.scene_arrays()
+        x_st, nbr_sum, edge_mask, p0 = (np.ascontiguousarray(sa[key][ids_in]) for key in ("x_st", "nbr_sum", "edge_mask", "p0"))
+        return x_st, nbr_sum, edge_mask, p0, None if ff is None else np.ascontiguousarray(sa["first_index"][ids_in])
+
+    def _predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Snapshot -> scene -> noise -> route -> run (ONE chained library entry, or encode / denoise / rank) -> assembly -> timings."""
+        t0 = time.perf_counter()
+        source, ids_in, cv, pose_now, sb, ff = self._scene(*self._snapshot())
+        A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
+        x_np = self._draw_x_T(A)             # after the scene: a call that raises HistoryTooShortError has drawn nothing
         t1 = time.perf_counter()
+        check = self.self_check and tuple(x_np.shape) not in self._checked_shapes
+        route = plan_route(k=k, K=K, A=A, H=H, device_topk=self.device_topk, device_scene=self.device_scene,
+                           device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped")
+        result, call = None, dict(dt=self.time_step, precision=self.precision)
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
                 self.engine.set_step(self.step_size, "ddim")   # eval_sicnav hard-codes sampling="ddim" (MID/mid.py:333)
-            # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits
-            # - the reference has none - the host twin ranks them
-            on_dev = k < K and self.device_topk and topk_fits_device(A, K, H)
-            check = self.self_check and tuple(x_np.shape) not in self._checked_shapes
-            in_cluster = None
-            # (a short window built on the host takes the staged path: jmid_predict has no first_index; a resident one is predict_scene's)
-            if (on_dev or k == K) and not check and (ff is None or sb is None):
-                # the whole call in ONE library entry (jmid_predict: encoder -> denoise -> integrator -> top-k chained on the
-                # stream, one upload, one download); JMID_ERANGE -> the staged path below in exact fp32
+            if route.run == "chain":
                 try:
-                    if frames is not None:
-                        # ... and, from raw frames, the assembled result itself (jmid_forecast_scene): nothing left to do on the host
-                        result = self.engine.forecast_scene(x_np, k, dt=self.time_step, precision=self.precision)
-                        t2 = time.perf_counter()
-                        self.timings = {"scene_ms": 1e3 * (t1 - t0), "device_ms": 1e3 * (t2 - t1), "topk_ms": 0.0,
-                                        "assemble_ms": 1e3 * (time.perf_counter() - t2), "total_ms": 1e3 * (time.perf_counter() - t0)}
-                        return result
-                    if sb is None:
-                        out, lw = self.engine.predict_scene(x_np, k, dt=self.time_step, precision=self.precision)
+                    if source == "stamped":      # from raw frames, the assembled result itself: nothing left to do on the host
+                        result = self.engine.forecast_scene(x_np, k, **call)
+                    elif sb is None:
+                        rows, logw = self.engine.predict_scene(x_np, k, **call)
                     else:
-                        out, lw = self.engine.predict(sb.x_st, sb.nbr_sum, sb.edge_mask, x_np, sb.p0[None], k, dt=self.time_step,
-                                                      precision=self.precision)
-                    if on_dev:
-                        in_cluster, logw_in = out[0], lw[0].astype(np.float64)
-                    else:
-                        in_cluster = out[0].transpose(1, 0, 2, 3)                 # [K, A, H, 2] -> agents by ascending id
-                        logw_in = np.log(np.ones((A, K), dtype=np.float64) / K)
-                    t2 = time.perf_counter()
+                        rows, logw = self.engine.predict(sb.x_st, sb.nbr_sum, sb.edge_mask, x_np, sb.p0[None], k, **call)
                 except JmidError as e:
-                    if e.code != -5 or self.precision == "f32":                   # JMID_ERANGE
+                    if not _repeats_in_fp32(e, self.precision):
                         raise
-            if in_cluster is None:
-                if sb is None:   # the self-check call and the JMID_ERANGE repeat take their inputs from the resident scene
-                    sa = self.engine.scene_arrays()
-                    sx_st, snbr, sem, sp0 = (np.ascontiguousarray(sa[key][ids_in]) for key in ("x_st", "nbr_sum", "edge_mask", "p0"))
-                    fi = None if ff is None else np.ascontiguousarray(sa["first_index"][ids_in])
-                    if frames is not None:
-                        pose_now = self.engine.scene_frames()["pose_now"]
-                else:
-                    sx_st, snbr, sem, sp0 = sb.x_st, sb.nbr_sum, sb.edge_mask, sb.p0
-                    fi = None if ff is None else sb.first_index
-                ctx = self.engine.encode(sx_st, snbr, sem, first_index=fi)
-                pos = self._denoise(x_np, ctx[None], sp0[None], want_pos=not on_dev or check)
+                    route = route._replace(run="staged")      # whose denoise call repeats in exact fp32, warns once and counts
+            t2 = time.perf_counter()
+            if route.run == "staged":
+                x_st, nbr_sum, edge_mask, p0, first_index = self._encoder_inputs(ids_in, sb, ff)
+                if pose_now is None:
+                    pose_now = self.engine.scene_frames()["pose_now"]
+                ctx = self.engine.encode(x_st, nbr_sum, edge_mask, first_index=first_index)
+                pos = self._denoise(x_np, ctx[None], p0[None], want_pos=route.rank != "device_resident")
                 if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
-                    pos = self._self_check(x_np, ctx[None], sp0[None], pos)
+                    pos = self._self_check(x_np, ctx[None], p0[None], pos)
                 t2 = time.perf_counter()
-                if on_dev:
-                    # joint-KDE top-k on the device (jmid_topk) over the positions the denoise call left in the workspace
-                    sel, lw = self.engine.topk(pos if check else None, k, dims=(1, A, K, H))
-                    in_cluster, logw_in = sel[0], lw[0].astype(np.float64)
-                elif k < K:
-                    in_cluster, logw_in = most_likely_samples(pos[0], k)          # [A, k, H, 2], [A, k]: host path
-                    logw_in = logw_in.astype(np.float64)
-                else:
-                    in_cluster = pos[0].transpose(1, 0, 2, 3)                     # [K, A, H, 2] -> agents by ascending id
-                    logw_in = np.log(np.ones((A, K), dtype=np.float64) / K)
+                rows, logw = rank_samples(self.engine, route.rank, pos, k, (1, A, K, H))
         t3 = time.perf_counter()
-        forecasts = np.zeros((self.num_hums, k, H, 2), dtype=np.float64)
-        logw = np.zeros((self.num_hums, k), dtype=np.float64)
-        forecasts[ids_in] = in_cluster
-        logw[ids_in] = logw_in
-        for i in ids_out:
-            forecasts[i] = (ds["cv"][int(i)] if sb is None else sb.cv_forecasts[int(i)])[np.newaxis]
-            logw[i] = logw_in[0]
-        # prepend the current pose estimate (mid_sim_wrapper.py:444-454)
-        pose = np.repeat(pose_now[:, None, None, :], k, axis=1)
-        out = np.concatenate((pose, forecasts), axis=2), logw
+        if result is None:
+            in_cluster = np.zeros(self.num_hums, dtype=bool)
+            in_cluster[ids_in] = True
+            result = SC.assemble_forecasts(in_cluster, rows[0], None if logw is None else logw[0], cv, pose_now, k, K)
         t4 = time.perf_counter()
         self.timings = {"scene_ms": 1e3 * (t1 - t0), "device_ms": 1e3 * (t2 - t1), "topk_ms": 1e3 * (t3 - t2),
                         "assemble_ms": 1e3 * (t4 - t3), "total_ms": 1e3 * (t4 - t0)}
-        return out
+        return result
 
 
 def get_most_likely_samples(forecasts, mid_model, num_ret_samples):
@@ -440,20 +424,75 @@ def topk_fits_device(A: int, K: int, H: int) -> bool:
     return A <= TOPK_MAX_AGENTS and K <= TOPK_MAX_SAMPLES and H <= TOPK_MAX_HORIZON
 
 
-def denoise_with_fallback(engine: JmidEngine, x_T, ctx, p0, dt: float, precision: str, want_pos: bool = True, **seeded):
-    """``engine.denoise`` -> positions; on JMID_ERANGE (an fp16 operand left the fp16 range) the call is repeated in the
-    exact-fp32 mode - what the reference computes in throughout (diffusion.py:478-541) - and counted.  -> (pos, fell_back).
-    ``seeded``: the seed / episode_ids / K / T keywords of a seeded call (x_T None): the repeat draws the same noise."""
+class Route(NamedTuple):
+    """The path of one ``predict_ret_best()`` - or of one count group, or the padded form, of ``predict_batch`` - as data."""
+    scene: str     # the scene batch: "host" (scene.py), "resident" (engine.build_scene) or "stamped" (engine.build_scene_stamped, raw frames)
+    run: str       # "chain": ONE library entry (predict / predict_scene / forecast_scene / predict_padded); "staged": encode -> denoise -> rank
+    rank: str      # the k of K samples: "device_resident" (jmid_topk on the positions the call left in the workspace; inside a chain), "device"
+    #                (jmid_topk on given positions), "host" (kde.py, beyond the device's size limits) or "none" (k == K: uniform weights)
+
+
+def scene_source(device_scene: bool, device_frames: bool, short: bool = False, frames: bool = True, batch: bool = False) -> str:
+    """``Route.scene``.  ``predict_batch`` takes grid inputs: nothing to stamp.  A single call's histories that are not frames take the
+    host frame table, and a short window has no stamped form (its padded table is built with ``first_frame``)."""
+    if batch:
+        return "resident" if device_scene or device_frames else "host"
+    if device_frames and frames and not short:
+        return "stamped"
+    return "resident" if device_scene or (device_frames and short) else "host"
+
+
+def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, device_scene: bool = False, device_frames: bool = False,
+               check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False) -> Route:
+    """Every decision of a call that does not need an array: the flags, k of K samples, A in-cluster pedestrians, horizon H, whether the
+    first-call self check is due (``check``), whether the window is short (``short``) and whether the histories are frames (``frames``).
+    ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count."""
+    scene = scene_source(device_scene, device_frames, short, frames, batch)
+    # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits - the reference
+    # has none - the host twin ranks them
+    on_dev = k < K and device_topk and topk_fits_device(A, K, H)
+    if batch:       # the chains predict_batch has: predict_padded on host arrays, forecast_scene on a group's resident scenes
+        chain = padded or device_frames
+    else:           # a short window built on the host is staged: jmid_predict has no first_index (a resident one is predict_scene's)
+        chain = not (short and scene == "host")
+    chain = chain and (on_dev or k == K) and not check        # (the self check compares the staged denoise call's positions)
+    rank = "none" if k >= K else "host" if not on_dev else "device" if check else "device_resident"
+    return Route(scene, "chain" if chain else "staged", rank)
+
+
+def _repeats_in_fp32(err: JmidError, precision: str) -> bool:
+    return err.code == ERANGE and precision != "f32"
+
+
+def repeat_in_fp32(call, precision: str):
+    """``call(precision)``; on JMID_ERANGE (an fp16 operand left the fp16 range) the same call in the exact-fp32 mode - what the
+    reference computes in throughout (diffusion.py:478-541) - and counted.  -> (result, fell_back)."""
     global ERANGE_FALLBACKS
     try:
-        _, pos = engine.denoise(x_T, ctx, p0, dt=dt, precision=precision, want_vel=False, want_pos=want_pos, **seeded)
-        return pos, False
+        return call(precision), False
     except JmidError as e:
-        if e.code != -5 or precision == "f32":     # JMID_ERANGE
+        if not _repeats_in_fp32(e, precision):
             raise
     ERANGE_FALLBACKS += 1
-    _, pos = engine.denoise(x_T, ctx, p0, dt=dt, precision="f32", want_vel=False, want_pos=want_pos, **seeded)
-    return pos, True
+    return call("f32"), True
+
+
+def denoise_with_fallback(engine: JmidEngine, x_T, ctx, p0, dt: float, precision: str, want_pos: bool = True, **seeded):
+    """``engine.denoise`` -> positions under ``repeat_in_fp32``.  -> (pos, fell_back).
+    ``seeded``: the seed / episode_ids / K / T keywords of a seeded call (x_T None): the repeat draws the same noise."""
+    return repeat_in_fp32(lambda p: engine.denoise(x_T, ctx, p0, dt=dt, precision=p, want_vel=False, want_pos=want_pos, **seeded)[1],
+                          precision)
+
+
+def rank_samples(engine: JmidEngine, rank: str, pos, k: int, dims: Tuple[int, int, int, int]):
+    """The ranking stage (``Route.rank``) after a denoise call of ``dims`` = (E, A, K, H), ``pos`` [E, K, A, H, 2] or None (left on the device)
+    -> what ``scene.assemble_forecasts`` takes: (kept [E, A, k, H, 2], log-weights [E, A, k]), or (pos, None) when all K are returned."""
+    if rank == "none":
+        return pos, None
+    if rank == "host":
+        parts = [most_likely_samples(p, k) for p in pos]
+        return np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts])
+    return engine.topk(pos if rank == "device" else None, k, dims=dims)
 
 
 def _engine_lock_of(engine: JmidEngine) -> RLock:
@@ -509,99 +548,63 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     E, F, N, _ = human_xy.shape
     K, k, H = int(num_samples), int(num_ret_samples), int(horizon)
     precision = DEFAULTS["precision"] if precision is None else precision      # (no self check here: an engine-level call)
-    global ERANGE_FALLBACKS
-    if device_scene or device_frames:           # the same batch from the device kernel (jmid_build_scene); grouping and everything after it as below
-        with _engine_lock_of(engine):
+    lock = _engine_lock_of(engine)               # an engine may be shared with forecaster instances; it is not re-entrant
+    if scene_source(device_scene, device_frames, batch=True) == "resident":
+        with lock:                               # the same batch from the device kernel (jmid_build_scene)
             b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
             if not device_frames:
                 b.update(engine.scene_arrays())
     else:
         b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
-    inc = b["in_cluster"]
-    forecasts = np.zeros((E, N, k, H, 2), dtype=np.float64)
-    logw = np.zeros((E, N, k), dtype=np.float64)
+    inc, pose_now = b["in_cluster"], human_xy[:, -1]
     n_in = inc.sum(axis=1)
-    pose = np.repeat(human_xy[:, -1][:, :, None, None, :], k, axis=2)              # [E, N, k, 1, 2]
-    if padded and n_in.min() >= 1 and (k == K or (device_topk and topk_fits_device(int(n_in.max()), K, H))):
+
+    def plan(A, padded=False):
+        return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
+                          short=ff is not None, batch=True, padded=padded)
+
+    def torch_x_T(e, A):
+        return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
+
+    if padded and n_in.min() >= 1 and plan(int(n_in.max()), padded=True).run == "chain":
         A = int(n_in.max())
-        x_T = SC.pad_samples([torch.randn([K * int(n_in[e]), H, 2], generator=torch.Generator().manual_seed(int(seeds[e]))).numpy()
-                              for e in range(E)], n_in, A, K)
+        x_T = SC.pad_samples([torch_x_T(e, int(n_in[e])).numpy() for e in range(E)], n_in, A, K)
         args = (SC.pad_agents(b["x_st"], inc, A).reshape(E * A, F, 6), SC.pad_agents(b["nbr_sum"], inc, A).reshape(E * A, 2, F, 6),
                 SC.pad_agents(b["edge_mask"], inc, A).reshape(E * A, 2), x_T, SC.pad_agents(b["p0"], inc, A), k, n_in)
-        with _engine_lock_of(engine):
-            try:
-                sel_all, lw_all = engine.predict_padded(*args, dt=time_step, precision=precision)
-            except JmidError as err:
-                if err.code != -5 or precision == "f32":     # JMID_ERANGE: the same call in exact fp32, counted
-                    raise
-                ERANGE_FALLBACKS += 1
-                sel_all, lw_all = engine.predict_padded(*args, dt=time_step, precision="f32")
-        for e in range(E):
-            n, rows = int(n_in[e]), np.nonzero(inc[e])[0]
-            if k < K:
-                sel, lw = sel_all[e, :n], lw_all[e, :n].astype(np.float64)        # [n, k, H, 2], [n, k]
-            else:
-                sel = SC.unpad_samples(sel_all, n_in, e).transpose(1, 0, 2, 3)    # pos [K, n, H, 2] -> agents first
-                lw = np.log(np.ones((n, K), dtype=np.float64) / K)
-            forecasts[e, rows] = sel
-            logw[e, rows] = lw
-            out_rows = np.nonzero(~inc[e])[0]
-            forecasts[e, out_rows] = b["cv"][e, out_rows][:, None]
-            logw[e, out_rows] = lw[0]
-        return np.concatenate((pose, forecasts), axis=3), logw, inc
-    for A in np.unique(n_in):
+        with lock:
+            (rows, lw), _ = repeat_in_fp32(lambda p: engine.predict_padded(*args, dt=time_step, precision=p), precision)
+        return (*SC.assemble_forecasts(inc, rows, lw, b["cv"], pose_now, k, K, n_agents=n_in), inc)
+    forecasts = np.empty((E, N, k, H + 1, 2), dtype=np.float64)
+    logw = np.empty((E, N, k), dtype=np.float64)
+    for A in np.unique(n_in):                   # episodes with the same count share their device calls
         eps = np.nonzero(n_in == A)[0]
         A = int(A)
-        rows = np.stack([np.nonzero(inc[e])[0] for e in eps])                       # [Eg, A] ascending track ids
-        ei = eps[:, None]
+        route = plan(A)
         if noise == "device":       # (seed, global episode id) is the whole address: nothing to draw here
             x_T, nz = None, dict(seed=int(seed), episode_ids=np.asarray(seeds)[eps], K=K, T=H)
         else:
-            x_T, nz = torch.stack([torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
-                                   for e in eps]).numpy(), {}
-        if device_frames and (k == K or (device_topk and topk_fits_device(A, K, H))):
-            with _engine_lock_of(engine):      # the group's scenes resident, then predictor + assembly in one entry
+            x_T, nz = torch.stack([torch_x_T(e, A) for e in eps]).numpy(), {}
+        if route.run == "chain":
+            with lock:              # the group's scenes resident, then predictor + assembly in one entry
                 engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H, first_frame=None if ff is None else ff[eps])
-                try:
-                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision=precision, **nz)
-                except JmidError as err:
-                    if err.code != -5 or precision == "f32":     # JMID_ERANGE: the same call in exact fp32, counted
-                        raise
-                    ERANGE_FALLBACKS += 1
-                    fc, lw = engine.forecast_scene(x_T, k, dt=time_step, precision="f32", **nz)
-            forecasts[eps] = fc[:, :, :, 1:]
-            logw[eps] = lw
+                (forecasts[eps], logw[eps]), _ = repeat_in_fp32(
+                    lambda p: engine.forecast_scene(x_T, k, dt=time_step, precision=p, **nz), precision)
             continue
-        if "p0" not in b:
-            with _engine_lock_of(engine):
+        if "p0" not in b:           # (device_frames built without reading the encoder inputs back)
+            with lock:
                 engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
                 b.update(engine.scene_arrays())
+        rows = np.stack([np.nonzero(inc[e])[0] for e in eps])                       # [Eg, A] ascending track ids
+        ei, n = eps[:, None], len(eps) * A
         p0 = np.ascontiguousarray(b["p0"][ei, rows])
-        with _engine_lock_of(engine):          # an engine may be shared with forecaster instances; it is not re-entrant
-            ctx = engine.encode(b["x_st"][ei, rows].reshape(len(eps) * A, F, 6),
-                                b["nbr_sum"][ei, rows].reshape(len(eps) * A, 2, F, 6),
-                                b["edge_mask"][ei, rows].reshape(len(eps) * A, 2),
+        with lock:                  # every episode of the group in ONE encode, denoise and jmid_topk call
+            ctx = engine.encode(b["x_st"][ei, rows].reshape(n, F, 6), b["nbr_sum"][ei, rows].reshape(n, 2, F, 6),
+                                b["edge_mask"][ei, rows].reshape(n, 2),
                                 first_index=None if ff is None else b["first_index"][ei, rows].reshape(-1)).reshape(len(eps), A, -1)
-            # the samples stay on the GPU; every episode of the group in ONE jmid_topk call (host twin beyond its size limits)
-            on_dev = k < K and device_topk and topk_fits_device(A, K, H)
-            pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=not on_dev, **nz)
-            if on_dev:
-                sel_all, lw_all = engine.topk(None, k, dims=(len(eps), A, K, H))   # [Eg, A, k, H, 2], [Eg, A, k]
-        for g, e in enumerate(eps):                                                # pos [Eg, K, A, H, 2]
-            if on_dev:
-                sel, lw = sel_all[g], lw_all[g].astype(np.float64)
-            elif k < K:
-                sel, lw = most_likely_samples(pos[g], k)                          # [A, k, H, 2], [A, k]
-                lw = lw.astype(np.float64)
-            else:
-                sel = pos[g].transpose(1, 0, 2, 3)
-                lw = np.log(np.ones((A, K), dtype=np.float64) / K)
-            forecasts[e, rows[g]] = sel
-            logw[e, rows[g]] = lw
-            out_rows = np.nonzero(~inc[e])[0]
-            forecasts[e, out_rows] = b["cv"][e, out_rows][:, None]
-            logw[e, out_rows] = lw[0]
-    return np.concatenate((pose, forecasts), axis=3), logw, inc
+            pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
+            sel, lw = rank_samples(engine, route.rank, pos, k, (len(eps), A, K, H))
+        forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], sel, lw, b["cv"][eps], pose_now[eps], k, K)
+    return forecasts, logw, inc
 
 
 def write_configs(directory: str, *, joint: bool, ctx_dim: int, N: int, K: int, k_ret: int, H: int, step: int,

@@ -18,6 +18,7 @@ All arithmetic is float64 until the final cast to float32, as in the reference
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -197,38 +198,50 @@ def histories_as_frames(prev_states, prev_robot_states):
     return stamps.copy(), np.ascontiguousarray(hum[:, :, 0:2].transpose(1, 0, 2)), np.ascontiguousarray(rob[:, 0:2])
 
 
-def assemble_forecasts(in_cluster: np.ndarray, sel_or_pos: np.ndarray, logw_in: Optional[np.ndarray], cv: np.ndarray,
-                       pose_now: np.ndarray, k: int, K: int) -> Tuple[np.ndarray, np.ndarray]:
+def assemble_forecasts(in_cluster: np.ndarray, sel_or_pos: np.ndarray, logw_in: Optional[np.ndarray], cv,
+                       pose_now: np.ndarray, k: int, K: int, n_agents: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
     """The result assembly of ``predict_ret_best`` (mid_sim_wrapper.py:493-510, :444-454) and the host twin of the device
     ``assemble_kernel`` (csrc/frames.hpp), for one scene or, with a leading episode axis on every array, for E of them.
 
     in_cluster [N] bool; k < K: sel_or_pos = the kept samples [A, k, H, 2] and logw_in [A, k] (float32, as ``predict_scene`` returns
     them); k == K: sel_or_pos = all samples [K, A, H, 2] (``pos``) and logw_in is ignored; cv [N, H, 2] float64 (every pedestrian's
-    constant-velocity row); pose_now [N, 2].  Returns (forecasts [N, k, H+1, 2], log-weights [N, k]) float64: the in-cluster rows
-    scattered by ascending track id, the others their ``cv`` row under the cluster's weight row, the current pose prepended."""
-    in_cluster = np.asarray(in_cluster, dtype=bool)
-    if in_cluster.ndim == 2:
-        parts = [assemble_forecasts(in_cluster[e], sel_or_pos[e], None if logw_in is None else logw_in[e], cv[e], pose_now[e], k, K)
-                 for e in range(in_cluster.shape[0])]
-        return np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts])
-    N = in_cluster.shape[0]
-    ids_in, ids_out = np.nonzero(in_cluster)[0], np.nonzero(~in_cluster)[0]
-    A = len(ids_in)
+    constant-velocity row) or, for one scene, ``SceneBatch.cv_forecasts`` (the rows of the pedestrians outside the cluster by track id:
+    nothing is made dense for the others); pose_now [N, 2].  Returns (forecasts [N, k, H+1, 2], log-weights [N, k]) float64: the in-cluster rows
+    scattered by ascending track id, the others their ``cv`` row under the cluster's weight row, the current pose prepended.
+    ``n_agents`` [E]: episodes of different counts, A = the largest and episode e's agents in its first n_agents[e] rows (``pad_agents``;
+    the others are not read).  None: every episode has A."""
+    in_cluster, rows, pose_now = np.asarray(in_cluster, dtype=bool), np.asarray(sel_or_pos), np.asarray(pose_now)
     if k < K:
-        rows, lw = np.asarray(sel_or_pos), np.asarray(logw_in).astype(np.float64)
+        lw = np.asarray(logw_in).astype(np.float64)
     else:
-        rows = np.asarray(sel_or_pos).transpose(1, 0, 2, 3)                  # [K, A, H, 2] -> agents by ascending id
-        lw = np.log(np.ones((A, K), dtype=np.float64) / K)
-    H = rows.shape[2]
-    forecasts = np.zeros((N, k, H, 2), dtype=np.float64)
-    logw = np.zeros((N, k), dtype=np.float64)
-    forecasts[ids_in] = rows
-    logw[ids_in] = lw
-    for i in ids_out:
-        forecasts[i] = np.asarray(cv)[int(i)][np.newaxis]
-        logw[i] = lw[0]
-    pose = np.repeat(np.asarray(pose_now, dtype=np.float64)[:, None, None, :], k, axis=1)
-    return np.concatenate((pose, forecasts), axis=2), logw
+        rows = np.swapaxes(rows, -4, -3)                                     # [K, A, H, 2] -> agents by ascending id
+        lw = _uniform_logw(rows.shape[-4], K)
+    H = rows.shape[-2]
+    forecasts = np.empty(in_cluster.shape + (k, H + 1, 2), dtype=np.float64)
+    logw = np.empty(in_cluster.shape + (k,), dtype=np.float64)
+    forecasts[..., 0, :] = pose_now[..., None, :]
+    # everybody the constant-velocity row under the cluster's first weight row, then the in-cluster rows over them (no loop over
+    # pedestrians): both masks take their (episode, row) pairs in row-major order, an episode's n tracks against its first n rows
+    future = forecasts[..., 1:, :]
+    if isinstance(cv, dict):
+        for i, row in cv.items():
+            future[i] = row
+    else:
+        future[...] = np.asarray(cv)[..., None, :, :]
+    logw[...] = lw[..., :1, :]
+    real = Ellipsis if n_agents is None else np.arange(rows.shape[-4]) < np.asarray(n_agents)[:, None]
+    future[in_cluster] = rows[real].reshape(-1, k, H, 2)
+    if k < K:                                                                # (k == K: every weight row is the one just written)
+        logw[in_cluster] = lw[real].reshape(-1, k)
+    return forecasts, logw
+
+
+@functools.lru_cache(maxsize=None)
+def _uniform_logw(A: int, K: int) -> np.ndarray:
+    """The weight rows of a call that returns all K samples (mid_sim_wrapper.py:507), [A, K]; read-only, computed once per shape."""
+    lw = np.log(np.ones((A, K), dtype=np.float64) / K)
+    lw.setflags(write=False)
+    return lw
 
 
 # --------------------------------------------------------------------------------------------- scene batch

@@ -45,6 +45,15 @@ def test_header_and_binding_agree(lib):
     assert lib.has_diagnostics          # the flavour this test session runs on
 
 
+def test_error_codes_are_named_as_in_the_header():
+    """The named codes of _lib.py (what engine.py and forecaster.py compare against) are the header's enum, value by value."""
+    src = open(os.path.join(REPO, "include", "jmid_hip.h")).read()
+    header = {name: int(value) for name, value in re.findall(r"\b(JMID_E[A-Z]+)\s*=\s*(-\d+)", src)}
+    assert len(header) == 7 and header == {name: code for code, name in _lib.ERR_NAMES.items()}
+    for short in ("EINVAL", "ENOWEIGHT", "EHIP", "ENOMEM", "ERANGE", "ETIMEOUT", "EHISTORY"):
+        assert _lib.ERR_NAMES[getattr(_lib, short)] == "JMID_" + short
+
+
 def test_libraries_export_the_c_abi_and_nothing_else():
     """-fvisibility=hidden + the header's visibility block: the dynamic symbol table of either flavour holds the declared
     jmid_* entry points only (no C++ template instances or their static guards that a second copy of the library - tests load

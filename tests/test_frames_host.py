@@ -248,3 +248,21 @@ def test_device_frames_is_opt_in():
     assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default is None          # None -> DEFAULTS
     q = inspect.signature(FC.predict_batch).parameters["device_frames"]
     assert q.kind is inspect.Parameter.KEYWORD_ONLY and q.default is False
+
+
+def test_assemble_forecasts_takes_the_host_scene_rows_by_track_id():
+    """One scene's constant-velocity rows as ``SceneBatch.cv_forecasts`` (a dict of the pedestrians outside the cluster): the dense form's bits."""
+    rng = np.random.default_rng(12)
+    N, K, k, H = 6, 8, 3, 4
+    inc = np.array([0, 1, 1, 0, 1, 0], dtype=bool)
+    cv, pose_now = rng.standard_normal((N, H, 2)), rng.standard_normal((N, 2))
+    sel, lw = rng.standard_normal((3, k, H, 2)).astype(np.float32), rng.standard_normal((3, k)).astype(np.float32)
+    pos = rng.standard_normal((K, 3, H, 2)).astype(np.float32)
+    rows = {int(i): cv[i] for i in np.nonzero(~inc)[0]}
+    for args, kk in (((sel, lw), k), ((pos, None), K)):
+        want, got = SC.assemble_forecasts(inc, *args, cv, pose_now, kk, K), SC.assemble_forecasts(inc, *args, rows, pose_now, kk, K)
+        assert bits_equal(got[0], want[0]) and bits_equal(got[1], want[1])
+    full = np.ones(N, dtype=bool)          # nobody outside: an empty dict
+    want = SC.assemble_forecasts(full, pos.repeat(2, axis=1), None, cv, pose_now, K, K)
+    got = SC.assemble_forecasts(full, pos.repeat(2, axis=1), None, {}, pose_now, K, K)
+    assert bits_equal(got[0], want[0]) and bits_equal(got[1], want[1])
