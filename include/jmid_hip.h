@@ -322,9 +322,10 @@ int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float
  *     jmid_denoise_padded of the same shape);
  *   - chunking, chunk lanes and the split-KV factor follow E, A, K, T exactly as for the plain call; the padded share of the rows
  *     is computed and thrown away.
- * DDIM with the caller's x_T only: there is no padded form of jmid_denoise_ddpm, of the *_seeded entries (the generator addresses an
- * element by its offset in [K*A, T, 2], which depends on A: which A a padded episode draws with is a decision of its own), nor of
- * jmid_predict_scene / jmid_forecast_scene, where mixed counts stay JMID_EINVAL.  JMID_EINVAL for NULL n_agents, a count outside 1..A,
+ * DDIM only: there is no padded form of jmid_denoise_ddpm.  The entries above take the caller's x_T; the seeded forms
+ * (jmid_noise_fill_padded, jmid_denoise_padded_seeded) and the padded chains on the resident scene (jmid_predict_scene_padded,
+ * jmid_forecast_scene_padded and their seeded forms) stand with "Seeded noise" and "Padded chains on the resident scene" below;
+ * jmid_predict_scene / jmid_forecast_scene themselves keep JMID_EINVAL on mixed counts.  JMID_EINVAL for NULL n_agents, a count outside 1..A,
  * a DDPM table on the handle, and (diagnostics flavour) for the attention A/B knobs that have no masked kernel: "attn_sm" = 2 in every
  * split mode, "attn_mx" = 1 and "attn_pf" = 2 in JMID_PREC_F16X2 / F16MX.  Everything else as the plain entry of the same name. */
 int jmid_net_eval_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, int step_idx, const float* x, const float* ctx,
@@ -497,6 +498,52 @@ int jmid_predict_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k
                               int precision, const float* bw, float* sel, float* logw, float* pos_out);
 int jmid_forecast_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
                                int precision, const float* bw, double* forecasts_out, double* logw_out);
+
+/* Seeded noise of a padded batch.  THE DECISION: episode e draws exactly what it draws alone, at ITS count - its tensor is the compact
+ * [K * n_e, T, 2], n_e = n_agents[e]:
+ *     idx = ((s * n_e + a) * T + t) * 2 + c,  counter = (idx / 4, episode_id, draw, 0),  the value lands in padded row s * A + a
+ * so an episode's noise stays a pure function of (seed, episode id, draw, element): the same bits in a padded batch, in its count group
+ * (jmid_*_seeded at A = n_e) and alone.  Drawing at the batch's A instead would make an episode's futures depend on its batch mates.
+ * One Philox block serves four consecutive COMPACT elements, which may lie in two padded rows.
+ *
+ * jmid_noise_fill_padded: out [E, K*A, T, 2] (where `mem` says); the real rows of episode e are bit-identical to
+ * jmid_noise_fill(E = 1, rows = K * n_agents[e]) of that episode, the padded rows quiet NaN.  n_agents and episode_ids are HOST arrays.
+ * JMID_EINVAL: a dimension < 1, draw < 0, a NULL argument, a count outside 1..A.
+ *
+ * jmid_denoise_padded_seeded: jmid_denoise_padded with (seed, episode_ids) in place of x_T - draw 0 of the rule above, filled straight
+ * into the workspace (whose padded rows are zeroed as jmid_denoise_padded zeroes them): bit-identical to jmid_denoise_padded fed
+ * jmid_noise_fill_padded's draw 0.  DDIM only: JMID_EINVAL with a DDPM table on the handle, exactly like jmid_denoise_padded. */
+int jmid_noise_fill_padded(jmid_handle_t h, uint64_t seed, int E, int A, int K, int T, const int32_t* n_agents, const uint32_t* episode_ids,
+                           int draw, float* out, int mem);
+int jmid_denoise_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,
+                               const float* ctx, const float* p0, float dt, int precision, float* vel_out, float* pos_out, int mem);
+
+/* Padded chains on the resident scene: jmid_predict_scene / jmid_forecast_scene (and their seeded forms) for a scene whose episodes have
+ * DIFFERENT in-cluster counts - what jmid_build_scene leaves whenever it chooses the clusters itself - in one call, in the layout and
+ * under the rules of "Padded scene batches" above.  The caller passes no n_agents: the counts are the resident scene's n_in, read on the
+ * device where the build kernel wrote them (the chain uploads nothing but x_T and bw; the seeded forms nothing but bw).
+ *   A     must equal the LARGEST in-cluster count of the resident scene, and every count must be >= 1: JMID_EINVAL otherwise (the scene
+ *         stays resident; an episode with an empty cluster has nothing to forecast - leave it out of the build)
+ *   x_T   [E, K*A, T, 2] in the padded layout, row s*A + a real iff a < n_in[e]; padded rows are never read, NaN included.  The seeded
+ *         forms draw by the padded rule above: episode e gets the bits jmid_predict_scene_seeded gives it in a batch of its own count
+ *   the gather writes zeros into the padded rows of the encoder's inputs (x_st, nbr_sum, edge_mask, p0, first_index), never what an earlier
+ *   call left there; the encoder runs on all E * A rows, and a padded row can neither raise JMID_ERANGE nor reach a real row
+ *   a scene from jmid_build_scene_var works (first_index is gathered and the encoder runs as jmid_encode_var): the padded form of short
+ *   histories, which jmid_predict_padded - it takes no first_index - does not have
+ *   sel, logw, pos_out and the resident positions: quiet NaN in the padded rows; the ranking is jmid_topk_padded's, in 2 * n_in[e] dimensions
+ *   forecasts_out / logw_out: as jmid_forecast_scene - an in-cluster pedestrian reads its own (real) row, everybody else the
+ *   constant-velocity row: no NaN in either array
+ * The real rows are bit-identical to jmid_predict_padded fed the gathered rows of jmid_scene_get and the same x_T; a scene whose counts
+ * are all equal gives the bits of jmid_predict_scene / jmid_forecast_scene.  Everything else - limits, JMID_ERANGE, JMID_ETIMEOUT, the
+ * forecast entries' refusals, DDIM only - as their namesakes. */
+int jmid_predict_scene_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
+                              float* sel, float* logw, float* pos_out);
+int jmid_forecast_scene_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
+                               double* forecasts_out, double* logw_out);
+int jmid_predict_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
+                                     int precision, const float* bw, float* sel, float* logw, float* pos_out);
+int jmid_forecast_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
+                                      int precision, const float* bw, double* forecasts_out, double* logw_out);
 
 /* ---- the denoising loss on data with known futures: DiffusionTraj.get_loss (MID/models/diffusion.py:448-476), reached through
  * AutoEncoder.get_loss (MID/models/autoencoder.py:105-122) from MID.validation() (MID/mid.py:252-296, its "Avg. Val Loss") - the

@@ -78,6 +78,18 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_forecast_scene_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jmid_noise_fill_padded": (C.c_int, [Handle, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_int]),
+    "jmid_denoise_padded_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_predict_scene_padded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jmid_forecast_scene_padded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "jmid_predict_scene_padded_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float,
+                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jmid_forecast_scene_padded_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float,
+                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_set_loss_schedule": (C.c_int, [Handle, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_loss": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

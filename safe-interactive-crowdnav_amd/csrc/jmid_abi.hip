@@ -75,6 +75,9 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
                   double* fc_out = nullptr, double* lwd_out = nullptr, const SeedArgs* seeded = nullptr, const int32_t* n_agents = nullptr) {
     // n_agents (jmid_predict_padded; host arrays only): the padded agents' rows go through the encoder as the caller left them - its rows are
     // independent - and the denoise stage zeroes their ctx, x_T and p0
+    // scene mode with n_agents (the *_scene_padded entries): n_agents is the host copy of the resident scene's counts; the stages read the
+    // device counts the build kernel wrote (nothing is uploaded for them), the gather zeroes the padded rows and a seeded x_T is the padded fill
+    const int* nag_dev = scene && n_agents ? reinterpret_cast<const int*>(h->scene.dev.p + h->scene.o_nin) : nullptr;
     const bool rank = k < K;
     const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
     const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
@@ -108,7 +111,9 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
     }
     if (seeded) {
         if (int rc = h->noise_ids.upload(h, seeded->ids, E, who)) return rc;
-        if (int rc = fill_noise(h, seeded->seed, h->noise_ids.get<unsigned>(), E, (size_t)K * A * T * 2, 0, dev + o_xT, nullptr, h->stream)) return rc;
+        if (nag_dev) {
+            if (int rc = fill_noise_padded(h, seeded->seed, h->noise_ids.get<unsigned>(), nag_dev, E, A, K, T, 0, dev + o_xT, h->stream)) return rc;
+        } else if (int rc = fill_noise(h, seeded->seed, h->noise_ids.get<unsigned>(), E, (size_t)K * A * T * 2, 0, dev + o_xT, nullptr, h->stream)) return rc;
     }
     int rc = 0;
     {
@@ -120,7 +125,7 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
             ga.x_st = reinterpret_cast<const float*>(sc.dev.p + sc.o_xst); ga.nbr_sum = reinterpret_cast<const float*>(sc.dev.p + sc.o_nbr);
             ga.edge_mask = reinterpret_cast<const float*>(sc.dev.p + sc.o_em); ga.p0 = reinterpret_cast<const float*>(sc.dev.p + sc.o_p0);
             ga.o_x_st = dev + o_xs; ga.o_nbr_sum = dev + o_nb; ga.o_edge_mask = dev + o_em; ga.o_p0 = dev + o_p0;
-            ga.E = E; ga.N = sc.N; ga.A = A; ga.F = (int)Th;
+            ga.E = E; ga.N = sc.N; ga.A = A; ga.F = (int)Th; ga.pad = nag_dev ? 1 : 0;
             if (var) {
                 ga.first_index = reinterpret_cast<const int*>(sc.dev.p + sc.o_first);
                 ga.o_first_index = reinterpret_cast<int*>(dev + o_fi);
@@ -133,9 +138,10 @@ int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x
     }
     DenoiseCall c{E, A, K, T, precision, JMID_MEM_DEVICE};       // a stage of the chain: no caller-stream ordering, the flag comes with the one download
     c.x_in = dev + o_xT; c.ctx = dev + o_ctx; c.p0 = dev + o_p0; c.dt = dt; c.pos_out = pos_out ? dev + o_pos : nullptr; c.chained = true;
-    c.n_agents = n_agents; c.who = who;
+    c.n_agents = n_agents; c.n_agents_dev = nag_dev; c.who = who;
     if (!rc) rc = run_network(h, c);
-    if (!rc && rank) rc = topk_on_device(h, who, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw, n_agents ? h->nag.get<int>() : nullptr);
+    if (!rc && rank)
+        rc = topk_on_device(h, who, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw, nag_dev ? nag_dev : n_agents ? h->nag.get<int>() : nullptr);
     if (!rc && fc_out) {
         const jmid_ctx::SceneWs& sc = h->scene;
         AssembleArgs aa{};
@@ -267,7 +273,7 @@ int build_scene_resident(jmid_ctx* h, const char* who, int E, int N, int F, cons
         HIPCHK(h, hipStreamSynchronize(h->stream));
         std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
     }
-    sc.o_x = o_x; sc.o_xst = o_xst; sc.o_nbr = o_nbr; sc.o_em = o_em; sc.o_p0 = o_p0; sc.o_inc = o_inc;
+    sc.o_x = o_x; sc.o_xst = o_xst; sc.o_nbr = o_nbr; sc.o_em = o_em; sc.o_p0 = o_p0; sc.o_inc = o_inc; sc.o_nin = o_nin;
     sc.o_hum = gb.o_hum; sc.o_rob = gb.o_rob; sc.o_pose = gb.o_pose; sc.o_cv = o_cv;
     sc.stamped = src == 2;
     sc.o_first = o_first; sc.has_first = first_frame != nullptr;
@@ -277,14 +283,23 @@ int build_scene_resident(jmid_ctx* h, const char* who, int E, int N, int F, cons
 }
 
 // the refusals jmid_predict_scene and jmid_forecast_scene share
-int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K, int T, int k, const void* noise) {
+int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K, int T, int k, const void* noise, bool padded) {
     if (int rc = check_ready(h)) return rc;
     if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, who + ": bad dimensions");
     if (!noise) return fail(h, JMID_EINVAL, who + ": null input");            // x_T, or the episode ids of a seeded call
     const jmid_ctx::SceneWs& sc = h->scene;
     if (!sc.E) return fail(h, JMID_EINVAL, who + " needs a preceding jmid_build_scene on this handle");
     if (E != sc.E) return fail(h, JMID_EINVAL, who + ": E differs from the resident scene's");
-    for (int e = 0; e < E; ++e)
+    if (padded) {      // A is the largest count of the scene, and nobody's cluster is empty
+        int most = 0;
+        for (int e = 0; e < E; ++e) {
+            if (sc.n_in[e] < 1) return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(e) + " has no in-cluster pedestrian");
+            most = std::max(most, sc.n_in[e]);
+        }
+        if (most != A)
+            return fail(h, JMID_EINVAL, who + ": A = " + std::to_string(A) + " is not the largest in-cluster count of the resident scene, " + std::to_string(most));
+    }
+    for (int e = 0; e < E && !padded; ++e)
         if (sc.n_in[e] != A)
             return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(e) + " has " + std::to_string(sc.n_in[e]) +
                                             " in-cluster pedestrians, not A = " + std::to_string(A) + " (group the episodes by their count)");
@@ -293,13 +308,14 @@ int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K
     return 0;
 }
 
-// jmid_predict_scene / jmid_forecast_scene and their seeded forms: one chain, the noise either the caller's x_T or (seed, ids)
+// jmid_predict_scene / jmid_forecast_scene, their seeded and their padded forms: one chain, the noise either the caller's x_T or (seed, ids);
+// padded: mixed in-cluster counts, A the largest, in the layout of jmid_predict_padded
 int predict_scene_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, int k, const float* x_T, const SeedArgs* seeded, float dt,
                                int precision, const float* bw, float* sel, float* logw, float* pos_out, double* forecasts_out, double* logw_out,
-                               bool forecast) {
+                               bool forecast, bool padded = false) {
     if (!h) return JMID_EINVAL;
     const std::string w(who);
-    if (int rc = check_predict_scene(h, w, E, A, K, T, k, seeded ? (const void*)seeded->ids : (const void*)x_T)) return rc;
+    if (int rc = check_predict_scene(h, w, E, A, K, T, k, seeded ? (const void*)seeded->ids : (const void*)x_T, padded)) return rc;
     if (seeded && !noise_fits((unsigned long long)K * A * T * 2)) return fail(h, JMID_EINVAL, w + ": K * A * T exceeds the noise addressing");
     if (forecast) {
         if (!forecasts_out || !logw_out) return fail(h, JMID_EINVAL, w + ": null output");
@@ -314,7 +330,30 @@ int predict_scene_entry(jmid_handle_t h, const char* who, int E, int A, int K, i
     }
     HIPCHK(h, hipSetDevice(h->device));
     return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, true, who, forecasts_out, logw_out,
-                         seeded);
+                         seeded, padded ? h->scene.n_in.data() : nullptr);
+}
+
+// jmid_noise_fill_padded: every episode's own compact draw in the padded layout, quiet NaN in the padded rows
+int noise_padded_entry(jmid_handle_t h, uint64_t seed, int E, int A, int K, int T, const int32_t* n_agents, const uint32_t* episode_ids, int draw,
+                       float* out, int mem) {
+    if (!h) return JMID_EINVAL;
+    const char* who = "jmid_noise_fill_padded";
+    const std::string w(who);
+    if (E < 1 || A < 1 || K < 1 || T < 1 || draw < 0) return fail(h, JMID_EINVAL, w + ": E, A, K, T must be at least 1 and draw at least 0");
+    if (!episode_ids || !out) return fail(h, JMID_EINVAL, w + ": null argument");
+    if (int rc = check_n_agents(h, who, n_agents, E, A)) return rc;
+    const size_t n = (size_t)K * A * T * 2;
+    if (!noise_fits(n)) return fail(h, JMID_EINVAL, w + ": K * A * T exceeds the noise addressing");
+    HIPCHK(h, hipSetDevice(h->device));
+    float* dst = nullptr;
+    Staging st(h, mem, h->kde_ws, who);
+    st.out(&dst, out, (size_t)E * n);
+    if (int rc = st.begin()) return rc;
+    if (int rc = h->noise_ids.upload(h, episode_ids, E, who)) return rc;
+    if (int rc = h->nag.upload(h, n_agents, E, who)) return rc;
+    if (int rc = fill_noise_padded(h, seed, h->noise_ids.get<unsigned>(), h->nag.get<int>(), E, A, K, T, draw, dst, h->stream)) return rc;
+    HIPCHK(h, launch_pad_fill(dst, h->nag.get<int>(), E, K, A, T * 2, std::numeric_limits<float>::quiet_NaN(), h->stream));
+    return st.end();
 }
 
 // jmid_noise_fill and jmid_dbg_noise_words: one draw to the caller's buffer (normals or raw words; 4 bytes per element either way)
@@ -917,6 +956,48 @@ int jmid_forecast_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int 
     const SeedArgs sa{seed, episode_ids};
     return predict_scene_entry(h, "jmid_forecast_scene_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, nullptr, nullptr, nullptr, forecasts_out,
                                logw_out, true);
+}
+
+int jmid_predict_scene_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
+                              float* sel, float* logw, float* pos_out) {
+    return predict_scene_entry(h, "jmid_predict_scene_padded", E, A, K, T, k, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr, false, true);
+}
+
+int jmid_forecast_scene_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
+                               double* forecasts_out, double* logw_out) {
+    return predict_scene_entry(h, "jmid_forecast_scene_padded", E, A, K, T, k, x_T, nullptr, dt, precision, bw, nullptr, nullptr, nullptr, forecasts_out,
+                               logw_out, true, true);
+}
+
+int jmid_predict_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
+                                     int precision, const float* bw, float* sel, float* logw, float* pos_out) {
+    const SeedArgs sa{seed, episode_ids};
+    return predict_scene_entry(h, "jmid_predict_scene_padded_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr,
+                               false, true);
+}
+
+int jmid_forecast_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
+                                      int precision, const float* bw, double* forecasts_out, double* logw_out) {
+    const SeedArgs sa{seed, episode_ids};
+    return predict_scene_entry(h, "jmid_forecast_scene_padded_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, nullptr, nullptr, nullptr,
+                               forecasts_out, logw_out, true, true);
+}
+
+int jmid_denoise_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,
+                               const float* ctx, const float* p0, float dt, int precision, float* vel_out, float* pos_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (!n_agents) return fail(h, JMID_EINVAL, "jmid_denoise_padded_seeded: null n_agents");
+    if (!episode_ids) return fail(h, JMID_EINVAL, "jmid_denoise_padded_seeded: null episode_ids");
+    const SeedArgs sa{seed, episode_ids};
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.n_agents = n_agents; c.seeded = &sa;
+    c.who = "jmid_denoise_padded_seeded";
+    return run_network(h, c);
+}
+
+int jmid_noise_fill_padded(jmid_handle_t h, uint64_t seed, int E, int A, int K, int T, const int32_t* n_agents, const uint32_t* episode_ids, int draw,
+                           float* out, int mem) {
+    return noise_padded_entry(h, seed, E, A, K, T, n_agents, episode_ids, draw, out, mem);
 }
 
 int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, const float* ctx, const float* p0,

@@ -161,6 +161,7 @@ struct jmid_ctx {
         int E = 0, N = 0;            // E = 0: no scene is resident
         size_t o_x = 0, o_xst = 0, o_nbr = 0, o_em = 0, o_p0 = 0, o_inc = 0;   // byte offsets of the resident arrays
         std::vector<int> n_in;       // [E] in-cluster pedestrians per episode (host copy)
+        size_t o_nin = 0;            // ... and where the build kernel wrote them: the device counts of the padded chains
         // the grid the scene was built from (human_xy [E, F, N, 2], robot_xy [E, F, 2] fp64) and pose_now [E, N, 2]: what
         // jmid_scene_get_frames copies out and jmid_forecast_scene prepends.  stamped: pose_now has a slot of its own (frames_kernel wrote
         // it); otherwise it is the last frame of the grid
@@ -317,6 +318,9 @@ struct SeedArgs {
     const uint32_t* ids;
 };
 int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream);
+// ... of a padded batch: the real rows of out [E, K * A, T, 2], every episode's own compact draw; the padded rows are left alone
+int fill_noise_padded(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, const int* n_agents_dev, int E, int A, int K, int T, int draw, float* out,
+                      hipStream_t stream);
 // What a loss call (jmid_loss / jmid_loss_seeded; loss.hpp) adds to a single-step call with K = 1: x_in is x0
 struct LossCall {
     const int32_t* t = nullptr;           // HOST [E, A] timesteps, 1 .. n_t - 1
@@ -335,8 +339,11 @@ struct DenoiseCall {
     const SeedArgs* seeded = nullptr;     // ... or x_T and the DDPM z drawn on the device
     bool chained = false;                 // a stage of jmid_predict: no caller-stream ordering, no flag round trip
     // a padded call (padded.hpp): HOST array [E], 1 <= n_agents[e] <= A - episode e has n_agents[e] real agents, the rows of the others
-    // are zeroed on entry and NaN in every output; JMID attention takes the key-mask words.  DDIM with the caller's x_T only.
+    // are zeroed on entry and NaN in every output; JMID attention takes the key-mask words.  DDIM only.
     const int32_t* n_agents = nullptr;
+    // ... whose counts already lie on the device (the padded scene chains: the n_in the build kernel wrote): n_agents is the host copy
+    // the checks read, and nothing is uploaded.  With `seeded`, x_T is the padded fill of noise.hpp (DDIM only).
+    const int* n_agents_dev = nullptr;
     const LossCall* loss = nullptr;       // a loss call: per-row timesteps folded into hyp, a zero row as thyp, e_out may be null
     const char* who = "jmid_denoise";     // the entry point that was called (error texts)
 };

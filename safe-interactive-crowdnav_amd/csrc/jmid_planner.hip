@@ -655,6 +655,17 @@ int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_
     return 0;
 }
 
+int fill_noise_padded(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, const int* n_agents_dev, int E, int A, int K, int T, int draw, float* out,
+                      hipStream_t stream) {
+    NoisePaddedArgs g{};
+    g.ids = ids_dev; g.n_agents = n_agents_dev; g.out = out;
+    g.key0 = (unsigned)(seed & 0xffffffffull); g.key1 = (unsigned)(seed >> 32);
+    g.draw = (unsigned)draw;
+    g.E = E; g.A = A; g.K = K; g.T = T;
+    HIPCHK(h, launch_noise_padded(g, stream));
+    return 0;
+}
+
 // Everything a denoise call decides, decided before it enqueues anything: host values only.  The phases of run_network read it;
 // net_step executes its step plans.
 struct CallPlan {
@@ -729,6 +740,7 @@ CallPlan plan_call(const jmid_ctx* h, const DenoiseCall& a, const CallMode& mode
 struct CallIo {
     float *x_cur, *ctx, *hyp, *p0, *stage, *z_up, *z_lane;      // stage: e / pos; z_up: the caller's DDPM noise; z_lane: z_fill
     unsigned* mask;      // a padded JMID call: key-mask words [E][ceil(S / 32)] (padded.hpp) - a chunk's words are its episodes' slice
+    const int* nag;      // ... and every padded call: its counts on the device (h->nag's upload, or DenoiseCall::n_agents_dev)
     // a loss call (loss.hpp): e where it is not the caller's device array (its upload, or the seeded draw), the per-row sums, {loss, count}
     float* e_up;
     float* tbo;          // (StepPlan::loss_tbo; only off the folded tail)
@@ -770,7 +782,7 @@ int check_call(jmid_ctx* h, const DenoiseCall& a, CallMode* mode) {
     if (a.seeded && !noise_fits((unsigned long long)a.K * a.A * a.T * 2)) return fail(h, JMID_EINVAL, "K * A * T exceeds the noise addressing");
     if (a.pos_out && !a.p0) return fail(h, JMID_EINVAL, "pos_out requested without p0");
     if (a.n_agents) {
-        if (a.seeded || a.z || (a.single_step < 0 && h->ddpm)) return fail(h, JMID_EINVAL, "a padded call samples with DDIM from the caller's x_T only");
+        if (a.z || (a.single_step < 0 && h->ddpm)) return fail(h, JMID_EINVAL, "a padded call samples with DDIM only");
         if (int rc = check_n_agents(h, "padded call", a.n_agents, a.E, a.A)) return rc;
         if (h->net_kind == JMID_NET_JMID && mode->split && !attn_masked_built(plan_attn(h->d / h->nhead, h->tune), mode->x2 != 0))
             return fail(h, JMID_EINVAL, "a padded call needs the default attention kernel: \"attn_sm\" = 2 and the ablations (every split mode), \"attn_mx\" = 1 and \"attn_pf\" = 2 (F16X2 / F16MX) have no masked form");
@@ -822,7 +834,17 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
         }
     }
     const hipMemcpyKind kin = a.mem == JMID_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    if (a.seeded) {
+    if (cp.masked) {      // the counts first: a seeded padded fill addresses with them
+        io.nag = a.n_agents_dev;
+        if (!io.nag) {
+            if (int rc = h->nag.upload(h, a.n_agents, a.E, a.who)) return rc;
+            io.nag = h->nag.get<int>();
+        }
+    }
+    if (a.seeded && cp.masked) {
+        if (int rc = h->noise_ids.upload(h, a.seeded->ids, a.E, a.who)) return rc;
+        if (int rc = fill_noise_padded(h, a.seeded->seed, h->noise_ids.get<unsigned>(), io.nag, a.E, a.A, a.K, a.T, 0, io.x_cur, h->stream)) return rc;
+    } else if (a.seeded) {
         if (int rc = h->noise_ids.upload(h, a.seeded->ids, a.E, a.who)) return rc;
         if (int rc = fill_noise(h, a.seeded->seed, h->noise_ids.get<unsigned>(), a.E, (size_t)a.K * a.A * a.T * 2, 0, io.x_cur, nullptr, h->stream)) return rc;
     } else {
@@ -839,11 +861,10 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
     if (cp.masked) {
         // the counts, the key-mask words from them, and zeros in the padded agents' rows of x_T, ctx and p0: whatever the caller left
         // there is never read.  All of it outside a captured loop, on memory the loop reads: a replay sees this call's counts.
-        if (int rc = h->nag.upload(h, a.n_agents, a.E, a.who)) return rc;
-        if (io.mask) HIPCHK(h, launch_mask_words(h->nag.get<int>(), io.mask, a.E, a.A, a.T, a.K * a.A * a.T, h->stream));
-        HIPCHK(h, launch_pad_fill(io.x_cur, h->nag.get<int>(), a.E, a.K, a.A, a.T * 2, 0.f, h->stream));
-        HIPCHK(h, launch_pad_fill(io.ctx, h->nag.get<int>(), a.E, 1, a.A, h->ctx_dim, 0.f, h->stream));
-        if (a.p0) HIPCHK(h, launch_pad_fill(io.p0, h->nag.get<int>(), a.E, 1, a.A, 2, 0.f, h->stream));
+        if (io.mask) HIPCHK(h, launch_mask_words(io.nag, io.mask, a.E, a.A, a.T, a.K * a.A * a.T, h->stream));
+        HIPCHK(h, launch_pad_fill(io.x_cur, io.nag, a.E, a.K, a.A, a.T * 2, 0.f, h->stream));
+        HIPCHK(h, launch_pad_fill(io.ctx, io.nag, a.E, 1, a.A, h->ctx_dim, 0.f, h->stream));
+        if (a.p0) HIPCHK(h, launch_pad_fill(io.p0, io.nag, a.E, 1, a.A, 2, 0.f, h->stream));
     }
     // ---- ctx part of the four hyper nets, once per call (ctx is constant over the denoise steps)
     GemmArgs g{};
@@ -862,7 +883,7 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
         }
         const int n_t = (int)h->loss_beta.size();
         const LossPrepareArgs pa{io.x_cur, io.e_dev, h->loss_t.get<int>(), h->loss_c, h->loss_c + n_t, io.hyp, h->loss_tt,
-                                 cp.masked ? h->nag.get<int>() : nullptr, io.tbo, (int)EA, a.A, a.T * 2, h->hl.total, h->hl.bo};
+                                 io.nag, io.tbo, (int)EA, a.A, a.T * 2, h->hl.total, h->hl.bo};
         for (StepPlan& p : cp.plans) p.loss_hyp = io.hyp, p.loss_tbo = io.tbo;
         ProfScope ps(h, KC_LOSS_PREPARE, h->stream);
         HIPCHK(h, launch_loss_prepare(pa, h->stream));
@@ -973,7 +994,7 @@ int finish_call(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const Cal
     // a padded call: quiet NaN in the padded agents' rows of what it returns - and, through the integrator, of the resident positions
     const float qnan = std::numeric_limits<float>::quiet_NaN();
     if (const LossCall* lc = a.loss) {      // the staged e_theta against e, before the pad fill below touches the stage
-        const LossReduceArgs ra{io.stage, io.e_dev, cp.masked ? h->nag.get<int>() : nullptr, io.loss_rows, io.loss, (int)R, a.A, a.T * 2};
+        const LossReduceArgs ra{io.stage, io.e_dev, io.nag, io.loss_rows, io.loss, (int)R, a.A, a.T * 2};
         {
             ProfScope ps(h, KC_LOSS_REDUCE, h->stream);
             HIPCHK(h, launch_loss_reduce(ra, h->stream));
@@ -981,7 +1002,7 @@ int finish_call(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const Cal
         HIPCHK(h, hipMemcpyAsync(lc->loss_out, io.loss, 2 * sizeof(double), kout, h->stream));
         if (lc->row_out) HIPCHK(h, hipMemcpyAsync(lc->row_out, io.loss_rows, R * sizeof(double), kout, h->stream));
     }
-    if (cp.masked) HIPCHK(h, launch_pad_fill(a.single_step >= 0 ? io.stage : io.x_cur, h->nag.get<int>(), a.E, a.K, a.A, a.T * 2, qnan, h->stream));
+    if (cp.masked) HIPCHK(h, launch_pad_fill(a.single_step >= 0 ? io.stage : io.x_cur, io.nag, a.E, a.K, a.A, a.T * 2, qnan, h->stream));
     if (a.single_step >= 0) {
         if (a.e_out) HIPCHK(h, hipMemcpyAsync(a.e_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
     } else {

@@ -80,6 +80,52 @@ static __global__ __launch_bounds__(256) void noise_fill_kernel(NoiseArgs g) {
     }
 }
 
+// The padded form (padded.hpp): episode e draws exactly what it draws alone - its COMPACT tensor [K * n_e, T, 2], n_e = n_agents[e], with
+// idx = ((s * n_e + a) * T + t) * 2 + c and the counter (idx / 4, id, draw, 0) - and the value lands in padded row s * A + a of
+// out [E, K * A, T, 2].  One thread per Philox block of the compact tensor, as above; the block's four elements may lie in two padded
+// rows, so each word pair goes to its own destination (T * 2 is even: a pair never straddles a row, and a compact tensor ends on a pair).
+// Padded rows are not written (the caller's pad_fill_kernel decides what they hold).
+struct NoisePaddedArgs {
+    const unsigned* ids;     // [E] episode ids (device)
+    const int* n_agents;     // [E] counts (device), 1 .. A
+    float* out;              // [E, K * A, T, 2]
+    unsigned key0, key1;
+    unsigned draw;
+    int E, A, K, T;
+    int vec;                 // 2: out is 8-byte aligned, float2 stores; 1: scalar stores
+};
+
+static __global__ __launch_bounds__(256) void noise_fill_padded_kernel(NoisePaddedArgs g) {
+    const unsigned long long q = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long L = (unsigned long long)g.T * 2;
+    for (int e = blockIdx.y; e < g.E; e += gridDim.y) {
+        const int ne = min(max(g.n_agents[e], 0), g.A);          // (the host has checked 1 .. A; a count outside could write out of bounds)
+        const unsigned long long n = (unsigned long long)g.K * ne * L;
+        if (4 * q >= n) continue;
+        unsigned w[4];
+        philox4x32_10((unsigned)q, g.ids[e], g.draw, 0u, g.key0, g.key1, w);
+        float* oe = g.out + (size_t)e * g.K * g.A * L;
+        for (int p = 0; p < 2; ++p) {
+            const unsigned long long idx = 4 * q + 2 * p;
+            if (idx >= n) break;
+            float z[2];
+            box_muller(w[2 * p], w[2 * p + 1], z);
+            const unsigned long long r = idx / L, rem = idx - r * L, s = r / ne, a = r - s * ne;
+            float* o = oe + (s * g.A + a) * L + rem;
+            if (g.vec == 2) *reinterpret_cast<float2*>(o) = make_float2(z[0], z[1]);
+            else o[0] = z[0], o[1] = z[1];
+        }
+    }
+}
+
+inline hipError_t launch_noise_padded(NoisePaddedArgs g, hipStream_t stream) {
+    const unsigned long long nq = ((unsigned long long)g.K * g.A * g.T * 2 + 3) / 4;       // of the largest count an episode can have
+    g.vec = reinterpret_cast<uintptr_t>(g.out) % 8 == 0 ? 2 : 1;
+    const dim3 grid((unsigned)((nq + 255) / 256), (unsigned)std::min(g.E, 65535));
+    hipLaunchKernelGGL(noise_fill_padded_kernel, grid, dim3(256), 0, stream, g);
+    return hipGetLastError();
+}
+
 // the limits of the addressing: the block index is one 32-bit counter word, the launch grid 2^31 - 1 workgroups
 inline bool noise_fits(unsigned long long n) { return (n + 3) / 4 <= 0x100000000ull && ((n + 3) / 4 + 255) / 256 <= 0x7fffffffull; }
 

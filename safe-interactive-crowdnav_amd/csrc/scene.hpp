@@ -218,6 +218,7 @@ struct SceneGatherArgs {
     const int* first_index;               // [E, N] padded, or null (a scene built without first_frame)
     int* o_first_index;                   // [E * A] dense (written only with first_index)
     int E, N, A, F;
+    int pad;                              // the padded chains: an episode with fewer than A rows gets zeros in the rest (0: they are left alone)
 };
 
 static __global__ __launch_bounds__(SCN_LANES) void scene_gather_kernel(SceneGatherArgs g) {
@@ -240,6 +241,17 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_gather_kernel(SceneGat
             g.o_p0[d * 2 + i] = g.p0[s * 2 + i];
         }
         if (g.first_index && i == 0) g.o_first_index[d] = g.first_index[s];
+    }
+    // padded rows: zeros, never what the previous call left there - a finite encoder row that starts at frame 0
+    for (int r = g.pad ? rows : A; r < A; ++r) {
+        const size_t d = (size_t)e * A + r;
+        for (int q = i; q < nx; q += SCN_LANES) g.o_x_st[d * nx + q] = 0.0f;
+        for (int q = i; q < nn; q += SCN_LANES) g.o_nbr_sum[d * nn + q] = 0.0f;
+        if (i < 2) {
+            g.o_edge_mask[d * 2 + i] = 0.0f;
+            g.o_p0[d * 2 + i] = 0.0f;
+        }
+        if (g.first_index && i == 0) g.o_first_index[d] = 0;
     }
 }
 

@@ -257,12 +257,27 @@ class JmidEngine:
             raise ValueError("ctx width / row count mismatch")
         return E, A, KA // A, T
 
-    def noise(self, seed: int, episode_ids, rows: int, T: int, draw: int = 0, device: bool = False, words: bool = False):
+    def noise(self, seed: int, episode_ids, rows: int, T: int, draw: int = 0, device: bool = False, words: bool = False, n_agents=None,
+              A: Optional[int] = None):
         """One draw of the library's counter generator (``jmid_noise_fill``; host twin ``noise.normal``): standard normals float32
         [E, rows, T, 2] for the episodes ``episode_ids`` - draw 0 is the x_T of a seeded call with rows = K * A, draw i + 1 the z of
-        step-table entry i.  ``device=True``: a CUDA tensor.  ``words=True`` (diagnostics flavour): the raw Philox words, uint32."""
+        step-table entry i.  ``device=True``: a CUDA tensor.  ``words=True`` (diagnostics flavour): the raw Philox words, uint32.
+        ``n_agents`` [E] (``jmid_noise_fill_padded``; host twin ``noise.fill_padded``): the draw of a padded batch, rows = K * A with A
+        the largest count (or ``A``): episode e draws what it draws alone at rows = K * n_agents[e], its row s * n_e + a lands in row
+        s * A + a, and the padded rows are NaN."""
         seed, ids = seeded_noise_args(None, seed, episode_ids)
         E = int(ids.size)
+        if n_agents is not None:
+            if words:
+                raise ValueError("the raw words have no padded form")
+            na = agent_counts(n_agents, E)
+            A = int(na.max()) if A is None else int(A)
+            if A < 1 or int(rows) % A != 0:
+                raise ValueError(f"rows = {rows} is not K * A for A = {A}")
+            out = _out((E, int(rows), int(T), 2), np.float32, f"cuda:{self.device_id}" if device else None)
+            self._check(self._lib.jmid_noise_fill_padded(self._h, seed, E, A, int(rows) // A, int(T), _ptr(na), _ptr(ids), int(draw), _ptr(out),
+                                                         self._mem(bool(device))))
+            return out
         out = _out((E, int(rows), int(T), 2), np.uint32 if words else np.float32, f"cuda:{self.device_id}" if device else None)
         fn = self._lib.jmid_dbg_noise_words if words else self._lib.jmid_noise_fill
         self._check(fn(self._h, seed, E, int(rows), int(T), _ptr(ids), int(draw), _ptr(out), self._mem(bool(device))))
@@ -314,6 +329,26 @@ class JmidEngine:
             self._compute(self._lib.jmid_denoise_padded, self._h, E, A, K, T, _ptr(na), bx.ptr, *tail)
         else:
             self._compute(self._lib.jmid_denoise, self._h, E, A, K, T, bx.ptr, *tail)
+        return vel, pos
+
+    def denoise_padded_seeded(self, ctx: ArrayLike, p0: Optional[ArrayLike], n_agents, seed: int, episode_ids, K: int, T: int, dt: float = 0.25,
+                              precision: str = "f32", want_vel: bool = True, want_pos: bool = True):
+        """``denoise(n_agents=)`` with x_T drawn by the library (``jmid_denoise_padded_seeded``, DDIM only): the same bits as the padded
+        call fed ``noise(seed, episode_ids, K * A, T, n_agents=n_agents)`` - every episode draws what it draws alone at its own count.
+        ctx [E, A, ctx_dim], p0 [E, A, 2] -> (vel [E, K, A, T, 2] or None, pos or None), NaN in the padded rows."""
+        if ctx.ndim != 3 or int(ctx.shape[2]) != self.dims.ctx_dim:
+            raise ValueError("expected ctx [E, A, ctx_dim]")
+        dev = _is_cuda(ctx)
+        E, A, K, T = int(ctx.shape[0]), int(ctx.shape[1]), int(K), int(T)
+        seed, ids = seeded_noise_args(None, seed, episode_ids, E)
+        na = agent_counts(n_agents, E)
+        want_pos = want_pos and p0 is not None
+        bc, bp = _Buf(ctx, dev), (_Buf(p0, dev) if p0 is not None else None)
+        where = ctx.device if dev else None
+        vel = _out((E, K, A, T, 2), device=where) if want_vel else None
+        pos = _out((E, K, A, T, 2), device=where) if want_pos else None
+        self._compute(self._lib.jmid_denoise_padded_seeded, self._h, E, A, K, T, _ptr(na), seed, _ptr(ids), bc.ptr, bp.ptr if bp else None,
+                      float(dt), _lib.PRECISIONS[precision], _ptr(vel), _ptr(pos), self._mem(dev))
         return vel, pos
 
     def topk(self, pos: Optional[ArrayLike], k: int, dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None):
@@ -437,12 +472,14 @@ class JmidEngine:
         self._check(self._lib.jmid_scene_get_first_index(self._h, C.c_void_p(out["first_index"].ctypes.data), _lib.MEM_HOST))
         return {k: v[0] for k, v in out.items()} if single else out
 
-    def _scene_noise(self, x_T, seed, episode_ids, K, T):
-        """What predict_scene / forecast_scene share: (E, A, K, T, the library entry's name suffix, its noise arguments, and the
-        array those point into - the caller keeps it alive over the call)."""
-        # A = the first episode's count (the library refuses the call when another episode's differs, or when nothing is resident)
+    def _scene_noise(self, x_T, seed, episode_ids, K, T, padded=False):
+        """What predict_scene / forecast_scene and their padded forms share: (E, A, K, T, the library entry's name suffix, its noise
+        arguments, and the array those point into - the caller keeps it alive over the call)."""
+        # A = the first episode's count (the library refuses the call when another episode's differs, or when nothing is resident);
+        # padded: the largest count
         n_in = getattr(self, "_scene_n_in", None)
-        A = int(n_in[0]) if n_in is not None and len(n_in) and n_in[0] > 0 else 1
+        A = int(n_in.max() if padded else n_in[0]) if n_in is not None and len(n_in) else 0
+        A = max(A, 1)
         seeded = seeded_noise_args(x_T, seed, episode_ids)
         if seeded is not None:
             if K is None or T is None:
@@ -467,6 +504,25 @@ class JmidEngine:
         k = int(k)
         fn = getattr(self._lib, "jmid_predict_scene" + sfx)
         return self._ranked_or_all(fn, (self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k)
+
+    def predict_scene_padded(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
+                             episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+        """``predict_scene`` for a resident scene of MIXED in-cluster counts, in one call (``jmid_predict_scene_padded``): A = the largest
+        ``n_in``, x_T [E, K*A, T, 2] in the padded layout (row s*A + a real iff a < n_in[e]; the others are never read), the results of
+        ``predict_padded`` fed the gathered rows of ``scene_arrays`` - NaN in the padded rows.  Every ``n_in`` must be at least 1.
+        ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T`` (``jmid_predict_scene_padded_seeded``): every episode draws what it
+        draws alone at its own count, ``noise(seed, episode_ids, K * A, T, n_agents=n_in)``."""
+        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T, padded=True)
+        k = int(k)
+        fn = getattr(self._lib, "jmid_predict_scene_padded" + sfx)
+        return self._ranked_or_all(fn, (self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k)
+
+    def forecast_scene_padded(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
+                              episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+        """``forecast_scene`` for a resident scene of mixed in-cluster counts (``jmid_forecast_scene_padded`` /
+        ``jmid_forecast_scene_padded_seeded``): the arguments of ``predict_scene_padded``, the results of ``forecast_scene`` - no NaN: an
+        in-cluster pedestrian reads its own row, everybody else the constant-velocity row."""
+        return self._forecast_scene("jmid_forecast_scene_padded", True, x_T, k, dt, precision, seed, episode_ids, K, T)
 
     def build_scene_stamped(self, stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
                             horizon: Optional[int] = None, force_all_in_cluster: bool = False,
@@ -528,9 +584,12 @@ class JmidEngine:
         exactly what ``predict_ret_best()`` returns.  The resident scene must have been built with ``horizon`` = T.  After a one-scene
         build the episode axis of the results is absent.  ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is
         drawn on the device (``jmid_forecast_scene_seeded``)."""
-        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T)
+        return self._forecast_scene("jmid_forecast_scene", False, x_T, k, dt, precision, seed, episode_ids, K, T)
+
+    def _forecast_scene(self, entry, padded, x_T, k, dt, precision, seed, episode_ids, K, T):
+        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T, padded)
         k = int(k)
-        fn = getattr(self._lib, "jmid_forecast_scene" + sfx)
+        fn = getattr(self._lib, entry + sfx)
         shape = getattr(self, "_scene_shape", None)
         N, single = (shape[1], shape[3]) if shape is not None else (1, False)
         bw = kde_bandwidths(T) if k < K else None

@@ -427,32 +427,37 @@ def topk_fits_device(A: int, K: int, H: int) -> bool:
 class Route(NamedTuple):
     """The path of one ``predict_ret_best()`` - or of one count group, or the padded form, of ``predict_batch`` - as data."""
     scene: str     # the scene batch: "host" (scene.py), "resident" (engine.build_scene) or "stamped" (engine.build_scene_stamped, raw frames)
-    run: str       # "chain": ONE library entry (predict / predict_scene / forecast_scene / predict_padded); "staged": encode -> denoise -> rank
+    run: str       # "chain": ONE library entry (predict / predict_scene / forecast_scene / predict_padded / forecast_scene_padded); "staged": encode -> denoise -> rank
     rank: str      # the k of K samples: "device_resident" (jmid_topk on the positions the call left in the workspace; inside a chain), "device"
     #                (jmid_topk on given positions), "host" (kde.py, beyond the device's size limits) or "none" (k == K: uniform weights)
 
 
-def scene_source(device_scene: bool, device_frames: bool, short: bool = False, frames: bool = True, batch: bool = False) -> str:
+def scene_source(device_scene: bool, device_frames: bool, short: bool = False, frames: bool = True, batch: bool = False,
+                 resident: bool = False) -> str:
     """``Route.scene``.  ``predict_batch`` takes grid inputs: nothing to stamp.  A single call's histories that are not frames take the
-    host frame table, and a short window has no stamped form (its padded table is built with ``first_frame``)."""
+    host frame table, and a short window has no stamped form (its padded table is built with ``first_frame``).  ``resident``
+    (``predict_batch(padded="resident")``): the whole batch is built on the device."""
     if batch:
-        return "resident" if device_scene or device_frames else "host"
+        return "resident" if device_scene or device_frames or resident else "host"
     if device_frames and frames and not short:
         return "stamped"
     return "resident" if device_scene or (device_frames and short) else "host"
 
 
 def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, device_scene: bool = False, device_frames: bool = False,
-               check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False) -> Route:
+               check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False,
+               resident: bool = False) -> Route:
     """Every decision of a call that does not need an array: the flags, k of K samples, A in-cluster pedestrians, horizon H, whether the
     first-call self check is due (``check``), whether the window is short (``short``) and whether the histories are frames (``frames``).
-    ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count."""
-    scene = scene_source(device_scene, device_frames, short, frames, batch)
+    ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count, ``resident``: that form on the
+    batch's resident scene (``padded="resident"``: forecast_scene_padded)."""
+    scene = scene_source(device_scene, device_frames, short, frames, batch, resident)
     # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits - the reference
     # has none - the host twin ranks them
     on_dev = k < K and device_topk and topk_fits_device(A, K, H)
-    if batch:       # the chains predict_batch has: predict_padded on host arrays, forecast_scene on a group's resident scenes
-        chain = padded or device_frames
+    if batch:       # the chains predict_batch has: predict_padded on host arrays, forecast_scene on a group's resident scenes,
+        #             forecast_scene_padded on the batch's
+        chain = padded or device_frames or resident
     else:           # a short window built on the host is staged: jmid_predict has no first_index (a resident one is predict_scene's)
         chain = not (short and scene == "host")
     chain = chain and (on_dev or k == K) and not check        # (the self check compares the staged denoise call's positions)
@@ -504,7 +509,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
                   device_topk: bool = True, device_scene: bool = False,
                   device_frames: bool = False, noise: str = "torch", seed: int = 0,
-                  padded: bool = False, short_history: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  padded=False, short_history: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -532,10 +537,20 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     not with ``device_scene``, ``device_frames`` or ``noise="device"``; a batch whose ranking does not fit the device top-k, or
     with an empty cluster, takes the grouped path.
     ``short_history=True`` (opt-in): human_xy / robot_xy may hold 2 <= L < hist_len frames (every episode the same L: the episode start);
-    the windows are padded in front (``scene.pad_short_window``) and every row is encoded from its first frame.  Not with ``padded``.
+    the windows are padded in front (``scene.pad_short_window``) and every row is encoded from its first frame.  Not with ``padded=True``.
+    ``padded="resident"`` (opt-in): the one-call form on the device scene - ONE ``engine.build_scene`` for all E episodes, then ONE
+    ``engine.forecast_scene_padded`` with A = the largest count (the counts are the resident scene's).  With ``noise="device"`` the call is
+    seeded and episode e draws what it draws alone and in its count group; otherwise the torch draws of ``padded=True``.  It combines with
+    ``short_history``.  A batch with an empty cluster, or whose ranking does not fit the device top-k, takes the grouped device path
+    (``device_frames=True``).
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
+    if padded not in (False, True, "resident"):
+        raise ValueError("padded must be False, True or 'resident'")
+    resident = isinstance(padded, str)
+    if resident:
+        padded, device_frames = False, True       # (what it falls back to: the grouped device path)
     if padded and (device_scene or device_frames or noise == "device"):
         raise ValueError("padded=True takes host scene arrays and torch noise only: not with device_scene, device_frames or noise='device' "
                          "(the padded entries have no scene-resident or seeded form)")
@@ -549,22 +564,32 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     K, k, H = int(num_samples), int(num_ret_samples), int(horizon)
     precision = DEFAULTS["precision"] if precision is None else precision      # (no self check here: an engine-level call)
     lock = _engine_lock_of(engine)               # an engine may be shared with forecaster instances; it is not re-entrant
-    if scene_source(device_scene, device_frames, batch=True) == "resident":
+
+    def plan(A, padded=False, resident=False):
+        return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
+                          short=ff is not None, batch=True, padded=padded, resident=resident)
+
+    def torch_x_T(e, A):
+        return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
+
+    if scene_source(device_scene, device_frames, batch=True, resident=resident) == "resident":
         with lock:                               # the same batch from the device kernel (jmid_build_scene)
             b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
+            n_in = b["in_cluster"].sum(axis=1)
+            if resident and n_in.min() >= 1 and plan(int(n_in.max()), resident=True).run == "chain":
+                # the scene stays where it is: predictor + assembly for every count in one entry
+                if noise == "device":
+                    x_T, nz = None, dict(seed=int(seed), episode_ids=np.asarray(seeds), K=K, T=H)
+                else:
+                    x_T, nz = SC.pad_samples([torch_x_T(e, int(n_in[e])).numpy() for e in range(E)], n_in, int(n_in.max()), K), {}
+                (forecasts, logw), _ = repeat_in_fp32(lambda p: engine.forecast_scene_padded(x_T, k, dt=time_step, precision=p, **nz), precision)
+                return forecasts, logw, b["in_cluster"]
             if not device_frames:
                 b.update(engine.scene_arrays())
     else:
         b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
     inc, pose_now = b["in_cluster"], human_xy[:, -1]
     n_in = inc.sum(axis=1)
-
-    def plan(A, padded=False):
-        return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
-                          short=ff is not None, batch=True, padded=padded)
-
-    def torch_x_T(e, A):
-        return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
 
     if padded and n_in.min() >= 1 and plan(int(n_in.max()), padded=True).run == "chain":
         A = int(n_in.max())

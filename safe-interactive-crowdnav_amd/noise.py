@@ -78,3 +78,20 @@ def normal(seed: int, episode_ids, rows: int, T: int, draw: int = 0) -> np.ndarr
     th = TWO_PI * u2
     z = np.stack([r * np.cos(th), r * np.sin(th)], axis=-1).astype(np.float32)
     return np.ascontiguousarray(z.reshape(ids.size, nq * 4)[:, :n]).reshape(ids.size, int(rows), int(T), 2)
+
+
+def fill_padded(seed: int, episode_ids, n_agents, A: int, K: int, T: int, draw: int = 0) -> np.ndarray:
+    """The draw of a padded batch, float32 [E, K * A, T, 2]: what ``jmid_noise_fill_padded`` writes for the same arguments.
+
+    Episode e draws exactly what it draws alone at its own count - ``normal(seed, [id_e], K * n_e, T, draw)``, n_e = n_agents[e] - and
+    row ``s * n_e + a`` of that compact tensor lands in padded row ``s * A + a``; the padded rows (a >= n_e) are NaN."""
+    ids = _ids(episode_ids)
+    n = np.atleast_1d(np.asarray(n_agents)).astype(np.int64)
+    A, K, T = int(A), int(K), int(T)
+    if n.shape != ids.shape or A < 1 or K < 1 or np.any(n < 1) or np.any(n > A):
+        raise ValueError("one count per episode, 1 <= n_agents[e] <= A, and K >= 1")
+    out = np.full((ids.size, K, A, T, 2), np.nan, dtype=np.float32)
+    for e in range(ids.size):
+        ne = int(n[e])
+        out[e, :, :ne] = normal(seed, ids[e:e + 1], K * ne, T, draw).reshape(K, ne, T, 2)
+    return out.reshape(ids.size, K * A, T, 2)
