@@ -670,6 +670,32 @@ int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, c
  * (episode, agent) row from a one-step table, or as the two GEMMs + the output kernel with jmid_set_tuning "tail_fold" = 1. */
 int jmid_dbg_tail(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision,
                   float* e, float* thyp_row);
+/* Encoder layer `layer` of one net evaluation, launch for launch as a step of a one-chunk call of that shape on an idle handle runs it
+ * (all four precisions, JMID and iMID; the split-KV factor and the launch plans are that call's), with every stage copied out in
+ * between.  X [M, d_model] fp32 (M = E K A T tokens) is split into the operand planes the mode's layer reads (fp16 hi + lo; hi + the
+ * bf8 image of lo where the residual stream's lo plane is the byte plane); n_agents [E] (or NULL: an unpadded call) makes it a padded
+ * call, its key-mask words made on the device as a denoise call makes them; last != 0: the layer is the encoder's last (norm2 does
+ * not write the lo plane where nothing reads it).  Layer 0 runs its in_proj GEMM here (its coefficient expansion: jmid_dbg_qkv0).
+ * hi and lo, each [M x JMID_DBG_LAYER_WIDTH(d_model, d_ff)] floats, receive the two planes of every stage as fp32 (one array and a zero
+ * lo plane in JMID_PREC_F32, and wherever a mode does not write a lo plane); stage s is the row-major [M, width] block at
+ * M x (the widths of the stages before it):
+ *   0  X as split                                        [M, d_model]
+ *   1  Q, K, V as the attention kernel reads them        [M, 3 d_model]  (Q's pre-scale undone, bf8 images decoded, V^T read back)
+ *   2  the attention output                              [M, d_model]
+ *   3  X after out_proj + residual + LayerNorm 1         [M, d_model]
+ *   4  linear1 + ReLU                                    [M, d_ff]
+ *   5  X after linear2 + residual + LayerNorm 2          [M, d_model]
+ * plan [JMID_DBG_LAYER_PLAN_WORDS] receives: bit mask of the stages present (stage 2 is absent when the out-projection's launch merges
+ * the split-KV partials itself); in_proj's GEMM family, tile shape (GemmShape) and flag word; linear1's; the path of the out_proj
+ * block (0 row-tile GEMM + LayerNorm second generation, 1 first generation, 2 one small launch with the statistics exchange, 3 GEMM +
+ * add_ln), its row tile and the tile shape of its GEMM; the same three for the linear2 block; V^T written by in_proj's epilogue;
+ * bf8 images of K; of Q_lo; the split-KV factor; masked; the out-projection merges the partials; byte lo plane; LDS-DMA attention
+ * kernel; the range flag; the GEMM family of the out_proj block's and of the linear2 block's arithmetic (-1 where a split-fp16 plan does
+ * not apply); the exact-fp32 attention kernel packs several short sequences into a wave ("attn_pack").  Returns as a denoise call does when the flag is set. */
+#define JMID_DBG_LAYER_WIDTH(d_model, d_ff) (7 * (d_model) + (d_ff))
+#define JMID_DBG_LAYER_PLAN_WORDS 25
+int jmid_dbg_layer(jmid_handle_t h, int E, int A, int K, int T, int layer, int precision, const float* X, const int32_t* n_agents, int last,
+                   float* hi, float* lo, int* plan);
 /* The raw Philox words behind jmid_noise_fill, same addressing: out [E, rows, T, 2] uint32 (where `mem` says). */
 int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem);
 #endif /* JMID_DIAGNOSTICS */

@@ -122,6 +122,8 @@ DIAG_SIGNATURES = {
     "jmid_dbg_gemm_plan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "jmid_dbg_qkv0": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "jmid_dbg_tail": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "jmid_dbg_layer": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "jmid_dbg_noise_words": (C.c_int, [Handle, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
 }
 

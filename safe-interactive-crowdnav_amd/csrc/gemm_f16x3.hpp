@@ -1620,12 +1620,19 @@ static __global__ __launch_bounds__(256) void v_transpose_kernel(const half_t* v
     }
 }
 
-// blocked hi/lo planes [rows, K] -> fp32 row-major (diagnostics)
-static __global__ void merge_planes_kernel(const half_t* hi, const half_t* lo, float* out, int rows, int K) {
+// blocked hi/lo planes [rows, K] -> fp32 row-major (diagnostics): their sum, or with out_lo the two planes apart (lo null: a plane
+// the mode does not write, read as zero)
+static __global__ void merge_planes_kernel(const half_t* hi, const half_t* lo, float* out, int rows, int K, float* out_lo) {
     const size_t n = (size_t)rows * K;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const size_t o = blk_index((int)(i / K), (int)(i % K), K);
-        out[i] = (float)hi[o] + (float)lo[o];
+        const float h = (float)hi[o], l = lo ? (float)lo[o] : 0.f;
+        if (out_lo) {
+            out[i] = h;
+            out_lo[i] = l;
+        } else {
+            out[i] = h + l;
+        }
     }
 }
 

@@ -543,12 +543,19 @@ static __global__ void split_planes_lo8_kernel(const float* in, half_t* hi, unsi
         lo8[blk8_index(r, k, GLN_BN)] = bf8_of_f16(l);
     }
 }
-static __global__ void merge_planes_lo8_kernel(const half_t* hi, const unsigned char* lo8, float* out, int rows) {
+// (with out_lo: the two planes apart; lo8 null: the byte plane was not written, read as zero)
+static __global__ void merge_planes_lo8_kernel(const half_t* hi, const unsigned char* lo8, float* out, int rows, float* out_lo) {
     const size_t n = (size_t)rows * GLN_BN;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int r = (int)(i / GLN_BN), k = (int)(i % GLN_BN);
-        const unsigned short lb = (unsigned short)(lo8[blk8_index(r, k, GLN_BN)]) << 8;
-        out[i] = (float)hi[blk_index(r, k, GLN_BN)] + (float)__builtin_bit_cast(half_t, lb);
+        const unsigned short lb = lo8 ? (unsigned short)((unsigned short)(lo8[blk8_index(r, k, GLN_BN)]) << 8) : (unsigned short)0;
+        const float h = (float)hi[blk_index(r, k, GLN_BN)], l = (float)__builtin_bit_cast(half_t, lb);
+        if (out_lo) {
+            out[i] = h;
+            out_lo[i] = l;
+        } else {
+            out[i] = h + l;
+        }
     }
 }
 

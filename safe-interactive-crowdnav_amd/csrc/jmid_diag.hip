@@ -166,7 +166,7 @@ int jmid_dbg_attention(jmid_handle_t h, int nseq, int S, const float* QKV, int p
             hipError_t e = launch_attn_f16x3(aa, nseq, hd, plan_attn(hd, h->tune), h->stream);
             if (e != hipSuccess) rc = fail(h, JMID_EHIP, hipGetErrorString(e));
         }
-        hipLaunchKernelGGL(merge_planes_kernel, dim3(512), dim3(256), 0, h->stream, b[6], b[7], dO, (int)Mt, d);
+        hipLaunchKernelGGL(merge_planes_kernel, dim3(512), dim3(256), 0, h->stream, b[6], b[7], dO, (int)Mt, d, (float*)nullptr);
     }
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -229,7 +229,7 @@ int jmid_dbg_gemm_ln_mx(jmid_handle_t h, int M, int K, const float* A, const flo
         }
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(merge_planes_lo8_kernel, dim3(512), dim3(256), 0, h->stream, xh, xl8, dX, M);
+    hipLaunchKernelGGL(merge_planes_lo8_kernel, dim3(512), dim3(256), 0, h->stream, xh, xl8, dX, M, (float*)nullptr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(X, dX, (size_t)M * N * 4, hipMemcpyDeviceToHost));
     return 0;
@@ -259,6 +259,11 @@ int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, c
 int jmid_dbg_tail(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision,
                   float* e, float* thyp_row) {
     return h ? dbg_step(h, true, E, A, K, T, X, hyp, hyp_width, step, precision, e, thyp_row) : JMID_EINVAL;
+}
+
+int jmid_dbg_layer(jmid_handle_t h, int E, int A, int K, int T, int layer, int precision, const float* X, const int32_t* n_agents, int last,
+                   float* hi, float* lo, int* plan) {
+    return h ? dbg_layer(h, E, A, K, T, layer, precision, X, n_agents, last, hi, lo, plan) : JMID_EINVAL;
 }
 
 int jmid_dbg_noise_words(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, uint32_t* out, int mem) {

@@ -357,8 +357,29 @@ LoImages lo_images(const StepPlan& p, const StepBuffers& sb, int d) {
     return im;
 }
 
-// The Q / K / V^T operand planes of layer l of a JMID step in the split-fp16 modes: the in_proj GEMM on the residual stream's planes
-// (+ the transpose where its epilogue does not write V^T itself), or for layer 0 the expansion of the coefficient table (qkv0.hpp).
+// The Q / K / V^T operand planes of layer l of a JMID step from the in_proj GEMM on the residual stream's planes (+ the transpose where
+// its epilogue does not write V^T itself)
+int in_proj_planes(jmid_ctx* h, const StepPlan& p, const Lane& ln, int l) {
+    const int M = p.M, d = h->d, hd = p.hd, S = p.sg.S;
+    const LoImages im = lo_images(p, ln, d);
+    const float qscale = p.att_scale * 1.4426950408889634f;
+    GemmHArgs g = gemm_h_args(p.mode, p.rm, M, ln.Xh, ln.Xl, h->wt.layers[l].in_proj, 3 * d, d);
+    g.Chi = ln.Qh; g.Clo = ln.Ql; g.Khi = ln.Kh; g.Klo = ln.Kl;
+    g.Vthi = p.vt_direct ? ln.Vth : ln.Vh; g.Vtlo = p.vt_direct ? ln.Vtl : ln.Vl; g.vt_direct = p.vt_direct;
+    g.d = d; g.hd = hd; g.S = S; g.Spad = p.sg.Spad; g.qscale = qscale;
+    g.K8h = im.k8h; g.K8l = im.k8l; g.Q8l = im.q8l;
+    if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, ln.stream, KC_GEMM_QKV, g, p.in_proj))) return rc;
+    if (!p.vt_direct) {
+        ProfScope ps(h, KC_VTRANS, ln.stream);
+        hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, p.sg.nseq), dim3(256), 0, ln.stream,
+                           ln.Vh, ln.Vl, ln.Vth, ln.Vtl, S, p.sg.Spad, d, hd);
+        HIPCHK(h, hipGetLastError());
+    }
+    return 0;
+}
+
+// The Q / K / V^T operand planes of layer l of a JMID step in the split-fp16 modes: the in_proj GEMM (in_proj_planes), or for layer 0
+// the expansion of the coefficient table (qkv0.hpp).
 int qkv_planes(jmid_ctx* h, const StepPlan& p, const Lane& ln, int l, int step_idx, const float* x_chunk, const float* hyp_chunk) {
     const int M = p.M, d = h->d, hd = p.hd, S = p.sg.S;
     const LoImages im = lo_images(p, ln, d);
@@ -379,19 +400,7 @@ int qkv_planes(jmid_ctx* h, const StepPlan& p, const Lane& ln, int l, int step_i
         HIPCHK(h, launch_qkv0_expand(qa, ln.stream));
         return 0;
     }
-    GemmHArgs g = gemm_h_args(p.mode, p.rm, M, ln.Xh, ln.Xl, h->wt.layers[l].in_proj, 3 * d, d);
-    g.Chi = ln.Qh; g.Clo = ln.Ql; g.Khi = ln.Kh; g.Klo = ln.Kl;
-    g.Vthi = p.vt_direct ? ln.Vth : ln.Vh; g.Vtlo = p.vt_direct ? ln.Vtl : ln.Vl; g.vt_direct = p.vt_direct;
-    g.d = d; g.hd = hd; g.S = S; g.Spad = p.sg.Spad; g.qscale = qscale;
-    g.K8h = im.k8h; g.K8l = im.k8l; g.Q8l = im.q8l;
-    if (int rc = (run_gemm_h<EPI_BIAS, OUT_QKV>(h, ln.stream, KC_GEMM_QKV, g, p.in_proj))) return rc;
-    if (!p.vt_direct) {
-        ProfScope ps(h, KC_VTRANS, ln.stream);
-        hipLaunchKernelGGL(v_transpose_kernel, dim3((S + 63) / 64, d / 64, p.sg.nseq), dim3(256), 0, ln.stream,
-                           ln.Vh, ln.Vl, ln.Vth, ln.Vtl, S, p.sg.Spad, d, hd);
-        HIPCHK(h, hipGetLastError());
-    }
-    return 0;
+    return in_proj_planes(h, p, ln, l);
 }
 
 // The sampler's part of the output stage of step `step_idx`: what out_ddim*_kernel and tail_fold*_kernel share
@@ -483,6 +492,7 @@ int net_tail(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float
 }
 
 // one evaluation of the net on a chunk of whole episodes + (optionally) the DDIM update, as its plan says
+// (dbg_layer below repeats the body of the layer loop launch for launch, with a read-back after every stage: a change here belongs there too)
 int net_step(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float* x_chunk, const float* hyp_chunk,
              float* e_out, const float* z_chunk = nullptr, bool embed_done = false, int next_step = -1, const unsigned* mask_chunk = nullptr) {
     // mask_chunk: the key-mask words of the chunk's episodes in a padded call (p.attn.masked), else null
@@ -1120,6 +1130,185 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
     if (thyp_row)
         HIPCHK(h, hipMemcpyAsync(thyp_row, p.thyp(step), h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return flag ? flagged_call(h, flag) : 0;
+}
+
+// jmid_dbg_layer: encoder layer `layer` of one step, launch for launch as net_step runs it in a one-chunk call on an idle handle (the
+// facts - the split-KV factor included - are plan_call's for that shape), on X [M, d] given in fp32 and split here into the planes the
+// mode's layer reads.  After every stage its planes are copied out on the same stream as two fp32 arrays: hi and lo, M x
+// JMID_DBG_LAYER_WIDTH(d, ff) floats each, hold stage s as the row-major [M, width of the stage] block at M x off[s].
+// The stages and plan [JMID_DBG_LAYER_PLAN_WORDS]: include/jmid_hip.h.
+int dbg_layer(jmid_ctx* h, int E, int A, int K, int T, int layer, int precision, const float* X, const int32_t* n_agents, int last,
+              float* hi, float* lo, int* plan) {
+    const std::string who = "jmid_dbg_layer";
+    CallMode mode;
+    if (int rc = check_ready(h)) return rc;
+    if (!X || !hi || !lo || !plan || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen) return fail(h, JMID_EINVAL, who + ": bad arguments");
+    if (!call_mode(precision, &mode)) return fail(h, JMID_EINVAL, who + ": bad precision");
+    if (layer < 0 || layer >= h->tf_layer) return fail(h, JMID_EINVAL, who + ": layer outside the encoder");
+    if (mode.split && !h->weights_in_half_range) return fail(h, JMID_ERANGE, who + ": a weight exceeds the fp16 range");
+    if (n_agents) {
+        if (int rc = check_n_agents(h, who.c_str(), n_agents, E, A)) return rc;
+        if (h->net_kind == JMID_NET_JMID && mode.split && !attn_masked_built(plan_attn(h->d / h->nhead, h->tune), mode.x2 != 0))
+            return fail(h, JMID_EINVAL, who + ": the attention kernel these knobs select has no masked form");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    h->last_pos = nullptr;
+    DenoiseCall call{};
+    call.E = E; call.A = A; call.K = K; call.T = T; call.precision = precision; call.mem = JMID_MEM_HOST;
+    call.single_step = 0; call.n_agents = n_agents; call.who = "jmid_dbg_layer";
+    CallFacts cf = plan_call(h, call, mode).facts;      // (the split-KV factor: the call's shape, mode and knob only)
+    cf.small_now = 1;                                   // one chunk on an idle handle
+    cf.one_chunk = h->tune.graph != 1;
+    const StepPlan p = plan_step(h, E, A, K, T, mode, cf, n_agents != nullptr);
+    const bool split = mode.split, joint = p.joint;
+    const int M = p.M, d = h->d, ff = h->ff, S = p.sg.S, nseq = p.sg.nseq, hd = p.hd;
+    const size_t Mz = (size_t)M, width = 7 * (size_t)d + ff;
+    const size_t off[6] = {0, (size_t)d, 4 * (size_t)d, 5 * (size_t)d, 6 * (size_t)d, 6 * (size_t)d + ff};
+    const bool mask_words = n_agents && joint;
+    float *in_d, *hi_d, *lo_d;
+    unsigned* mask_d;
+    const auto io = [&](char* base) {      // base null: the size only
+        Carver c(base);
+        in_d = c.take(Mz * d);
+        hi_d = c.take(Mz * width);
+        lo_d = c.take(Mz * width);
+        mask_d = mask_words ? reinterpret_cast<unsigned*>(c.take((size_t)E * mask_words_per_seq(S))) : nullptr;
+        return c.off;
+    };
+    const size_t io_off = io(nullptr);
+    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, Mz, mode, p.sg, cf.attn_nsplit, nullptr, nullptr, 0, 0), who.c_str())) return rc;
+    io(h->arena.p);
+    Lane ln{};
+    ln.stream = h->stream;
+    step_ws_floats(h, Mz, mode, p.sg, cf.attn_nsplit, &ln, h->arena.p + io_off, 0, 0);
+    hipStream_t st = h->stream;
+    HIPCHK(h, hipMemsetAsync(lo_d, 0, Mz * width * sizeof(float), st));
+    HIPCHK(h, hipMemcpyAsync(in_d, X, Mz * d * sizeof(float), hipMemcpyHostToDevice, st));
+    if (mask_words) {
+        if (int rc = h->nag.upload(h, n_agents, E, who.c_str())) return rc;
+        HIPCHK(h, launch_mask_words(h->nag.get<int>(), mask_d, E, A, T, S, st));
+    }
+    unsigned char* Xl8 = p.mxv2 ? reinterpret_cast<unsigned char*>(ln.Xl) : nullptr;
+    // a stage's planes -> hi_d / lo_d at its offset
+    const auto out_hi = [&](int s) { return hi_d + Mz * off[s]; };
+    const auto out_lo = [&](int s) { return lo_d + Mz * off[s]; };
+    const auto copy_f32 = [&](int s, const float* src, size_t w) {
+        return hipMemcpyAsync(out_hi(s), src, Mz * w * sizeof(float), hipMemcpyDeviceToDevice, st);
+    };
+    const auto read_x = [&](int s, bool lo_written) {      // the residual stream
+        if (!split) return copy_f32(s, ln.X, d);
+        if (p.mxv2) hipLaunchKernelGGL(merge_planes_lo8_kernel, dim3(512), dim3(256), 0, st, ln.Xh, lo_written ? Xl8 : nullptr, out_hi(s), M, out_lo(s));
+        else hipLaunchKernelGGL(merge_planes_kernel, dim3(512), dim3(256), 0, st, ln.Xh, lo_written ? ln.Xl : nullptr, out_hi(s), M, d, out_lo(s));
+        return hipGetLastError();
+    };
+    const auto read_planes = [&](int s, const half_t* ph, const half_t* pl, int w) {
+        hipLaunchKernelGGL(merge_planes_kernel, dim3(512), dim3(256), 0, st, ph, pl, out_hi(s), M, w, out_lo(s));
+        return hipGetLastError();
+    };
+    int stages = 0;
+    // ---- stage 0: X as the layer reads it
+    if (!split) {
+        HIPCHK(h, hipMemcpyAsync(ln.X, in_d, Mz * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+    } else {
+        HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), st));
+        HIPCHK(h, hipMemsetAsync(ln.ln_xchg, 0, kLnxWords * sizeof(unsigned), st));
+        // (the planes' padding rows up to the next multiple of 128 only ever feed discarded output rows, but must be finite)
+        half_t* const planes[6] = {ln.Xh, ln.Xl, ln.Ah, ln.Al, ln.H1h, ln.H1l};
+        const int plane_w[6] = {d, d, d, d, ff, ff};
+        for (int i = 0; i < 6; ++i) HIPCHK(h, hipMemsetAsync(planes[i], 0, blk_plane_elems(Mz, plane_w[i]) * sizeof(half_t), st));
+        if (ln.Vth) {
+            HIPCHK(h, hipMemsetAsync(ln.Vth, 0, ln.vt_elems * sizeof(half_t), st));
+            HIPCHK(h, hipMemsetAsync(ln.Vtl, 0, ln.vt_elems * sizeof(half_t), st));
+        }
+        if (p.mxv2) hipLaunchKernelGGL(split_planes_lo8_kernel, dim3(512), dim3(256), 0, st, in_d, ln.Xh, Xl8, M);
+        else hipLaunchKernelGGL(split_planes_blocked_kernel, dim3(512), dim3(256), 0, st, in_d, ln.Xh, ln.Xl, M, d, h->range_flag, 1.0f);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, read_x(0, true));
+    stages |= 1;
+    const LayerW& w = h->wt.layers[layer];
+    const RowMap& rm = p.rm;
+    // ---- stages 1 and 2: Q / K / V and the attention on them (net_step)
+    if (!split) {
+        if (int rc = run_gemm<EPI_BIAS>(h, st, KC_GEMM_QKV, gemm_args(rm, M, ln.X, w.in_proj, ln.QKV, 3 * d, d))) return rc;
+        HIPCHK(h, copy_f32(1, ln.QKV, 3 * (size_t)d));
+        AttnArgs aa{ln.QKV, ln.ATT, S, d, h->nhead, p.att_scale, nullptr, nullptr};
+        aa.mask = p.attn.masked ? mask_d : nullptr;
+        HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, st));
+        HIPCHK(h, copy_f32(2, ln.ATT, d));
+        stages |= 6;
+        if (int rc = run_gemm<EPI_BIAS>(h, st, KC_GEMM_OUT, gemm_args(rm, M, ln.ATT, w.out_proj, ln.Y, d, d))) return rc;
+        if (int rc = run_add_ln(h, st, ln.X, ln.Y, w.norm1.gamma, w.norm1.beta, M, d)) return rc;
+        HIPCHK(h, read_x(3, true));
+        if (int rc = run_gemm<EPI_BIAS_RELU>(h, st, KC_GEMM_FF1, gemm_args(rm, M, ln.X, w.linear1, ln.H1, ff, d))) return rc;
+        HIPCHK(h, copy_f32(4, ln.H1, ff));
+        if (int rc = run_gemm<EPI_BIAS>(h, st, KC_GEMM_FF2, gemm_args(rm, M, ln.H1, w.linear2, ln.Y, d, ff))) return rc;
+        if (int rc = run_add_ln(h, st, ln.X, ln.Y, w.norm2.gamma, w.norm2.beta, M, d)) return rc;
+        HIPCHK(h, read_x(5, true));
+        stages |= 56;
+    } else {
+        GemmHArgs g{};
+        if (joint) {
+            if (int rc = in_proj_planes(h, p, ln, layer)) return rc;
+            const LoImages im = lo_images(p, ln, d);
+            QkvReadArgs ra{ln.Qh, ln.Ql, ln.Kh, ln.Kl, ln.Vth, ln.Vtl, im.q8l, im.k8l, out_hi(1), Mz, d, hd, S, p.sg.Spad, mode.x2,
+                           p.att_scale * 1.4426950408889634f, out_lo(1)};
+            hipLaunchKernelGGL(qkv_planes_read_kernel, dim3(512), dim3(256), 0, st, ra);
+            HIPCHK(h, hipGetLastError());
+            AttnHArgs aa{ln.Qh, ln.Ql, ln.Kh, ln.Kl, ln.Vth, ln.Vtl, ln.Ah, ln.Al, S, p.sg.Spad, d, h->nhead,
+                         p.att_scale, h->range_flag, p.cf.attn_nsplit, ln.Opart, ln.MLpart, p.mode.x2, im.k8h, im.k8l, im.q8l};
+            aa.skip_combine = p.out_proj.merge;
+            HIPCHK(h, launch_attn_f16x3(aa, nseq, hd, p.attn, st, p.attn.masked ? mask_d : nullptr));
+            if (!p.out_proj.merge) {
+                HIPCHK(h, read_planes(2, ln.Ah, mode.x2 ? nullptr : ln.Al, d));      // (F16X2 / F16MX: O_lo is not written)
+                stages |= 4;
+            }
+        } else {
+            g = gemm_h_args(p.mode, rm, M, ln.Xh, ln.Xl, w.in_proj, 3 * d, d);
+            g.C = ln.QKV; g.ldc = 3 * d;
+            if (int rc = (run_gemm_h<EPI_BIAS, OUT_F32>(h, st, KC_GEMM_QKV, g, p.in_proj))) return rc;
+            HIPCHK(h, copy_f32(1, ln.QKV, 3 * (size_t)d));
+            AttnArgs aa{ln.QKV, nullptr, S, d, h->nhead, p.att_scale, ln.Ah, ln.Al};
+            HIPCHK(h, launch_attn_f32(aa, nseq, hd, p.attn.pack, st));
+            HIPCHK(h, read_planes(2, ln.Ah, ln.Al, d));
+            stages |= 4;
+        }
+        stages |= 2;
+        // ---- stage 3: out_proj + residual + norm1
+        if (int rc = residual_block(h, p, p.out_proj, ln, ln.Ah, ln.Al, d, w.out_proj, w.norm1, KC_GEMM_OUT, false)) return rc;
+        HIPCHK(h, read_x(3, true));
+        // ---- stage 4: linear1 + ReLU
+        g = gemm_h_args(p.mode, rm, M, ln.Xh, ln.Xl, w.linear1, ff, d);
+        g.Chi = ln.H1h; g.Clo = ln.H1l; g.ldc = ff;
+        if (int rc = (run_gemm_h<EPI_BIAS_RELU, OUT_SPLIT>(h, st, KC_GEMM_FF1, g, p.linear1))) return rc;
+        HIPCHK(h, read_planes(4, ln.H1h, mode.x2 ? nullptr : ln.H1l, ff));      // (F16X2 / F16MX: the consumer GEMM takes A_hi only)
+        // ---- stage 5: linear2 + residual + norm2
+        if (int rc = residual_block(h, p, p.linear2, ln, ln.H1h, ln.H1l, ff, w.linear2, w.norm2, KC_GEMM_FF2, last != 0)) return rc;
+        // (last in F16X2 / F16MX: nothing reads the lo plane and most paths do not write it - GEMM + add_ln in F16X2 still does -:
+        //  it is reported as zero, the plane concat3 reads is the hi plane alone)
+        HIPCHK(h, read_x(5, !(last && mode.x2)));
+        stages |= 56;
+    }
+    // the arithmetic of a residual block's GEMM (GemmMode): the row-tile kernels take the fp8 correction wherever the weight has its image
+    const auto block_mode = [&](const ResidualPlan& rp, const LinearW& lin) {
+        if (rp.path == RB_GEMM_LN2 || rp.path == RB_LNX_SMALL) return (int)GM_MX;
+        if (rp.path == RB_GEMM_LN) return (int)(mode.mx && lin.w8 ? GM_MX : mode.x2 ? GM_X2 : GM_X3);
+        return (int)rp.gemm.mode;
+    };
+    int flag = 0;
+    if (split) HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hi, hi_d, Mz * width * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(lo, lo_d, Mz * width * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    const int words[JMID_DBG_LAYER_PLAN_WORDS] = {
+        stages, split ? p.in_proj.mode : -1, split ? p.in_proj.shape : -1, split ? p.in_proj.flags : 0,
+        split ? p.linear1.mode : -1, split ? p.linear1.shape : -1, split ? p.linear1.flags : 0,
+        split ? p.out_proj.path : -1, split ? p.out_proj.ln_rows : 0, split ? (int)p.out_proj.gemm.shape : -1,
+        split ? p.linear2.path : -1, split ? p.linear2.ln_rows : 0, split ? (int)p.linear2.gemm.shape : -1,
+        p.vt_direct, p.k8, p.q8l, p.cf.attn_nsplit, p.attn.masked, p.out_proj.merge, p.mxv2, p.attn.dma, flag,
+        split ? block_mode(p.out_proj, w.out_proj) : -1, split ? block_mode(p.linear2, w.linear2) : -1, p.attn.pack};
+    for (int i = 0; i < JMID_DBG_LAYER_PLAN_WORDS; ++i) plan[i] = words[i];
     return flag ? flagged_call(h, flag) : 0;
 }
 #endif

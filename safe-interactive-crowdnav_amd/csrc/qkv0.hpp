@@ -221,6 +221,7 @@ struct QkvReadArgs {
     size_t M;
     int d, hd, S, Spad, x2;
     float qscale;
+    float* out_lo = nullptr;      // the two planes apart: out takes the hi planes, out_lo [M, 3d] the lo planes / their bf8 images (jmid_dbg_layer)
 };
 __device__ __forceinline__ float f32_of_bf8(unsigned char b) {
     return (float)__builtin_bit_cast(half_t, (unsigned short)((unsigned)b << 8));
@@ -230,13 +231,26 @@ static __global__ void qkv_planes_read_kernel(QkvReadArgs a) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const size_t m = i / a.d;
         const int c = (int)(i % a.d);
-        float* o = a.out + m * 3 * a.d;
-        o[c] = ((float)a.Qh[i] + (a.Q8l ? f32_of_bf8(a.Q8l[i]) : (float)a.Ql[i])) / a.qscale;
-        o[a.d + c] = (float)a.Kh[i] + (a.K8l ? f32_of_bf8(a.K8l[i]) : (float)a.Kl[i]);
         const size_t seq = m / a.S, key = m % a.S;
         const int head = c / a.hd, vc = c % a.hd;
         const size_t at = ((seq * (a.d / a.hd) + head) * a.hd + vc) * a.Spad + (size_t)vt_key_pos((int)key);
-        o[2 * a.d + c] = (float)a.Vth[at] + (a.x2 ? 0.f : (float)a.Vtl[at]);
+        const float qh = (float)a.Qh[i], ql = a.Q8l ? f32_of_bf8(a.Q8l[i]) : (float)a.Ql[i];
+        const float kh = (float)a.Kh[i], kl = a.K8l ? f32_of_bf8(a.K8l[i]) : (float)a.Kl[i];
+        const float vh = (float)a.Vth[at], vl = a.x2 ? 0.f : (float)a.Vtl[at];
+        float* o = a.out + m * 3 * a.d;
+        if (a.out_lo) {
+            float* ol = a.out_lo + m * 3 * a.d;
+            o[c] = qh / a.qscale;
+            ol[c] = ql / a.qscale;
+            o[a.d + c] = kh;
+            ol[a.d + c] = kl;
+            o[2 * a.d + c] = vh;
+            ol[2 * a.d + c] = vl;
+        } else {
+            o[c] = (qh + ql) / a.qscale;
+            o[a.d + c] = kh + kl;
+            o[2 * a.d + c] = vh + vl;
+        }
     }
 }
 #endif

@@ -882,6 +882,42 @@ class JmidEngine:
                                             _lib.PRECISIONS[precision], C.c_void_p(out.ctypes.data), C.c_void_p(thyp.ctypes.data)))
         return out, thyp
 
+    LAYER_PLAN_FIELDS = ("stages", "in_proj_mode", "in_proj_shape", "in_proj_flags", "linear1_mode", "linear1_shape", "linear1_flags",
+                         "out_proj_path", "out_proj_ln_rows", "out_proj_gemm_shape", "linear2_path", "linear2_ln_rows", "linear2_gemm_shape",
+                         "vt_direct", "k8", "q8l", "attn_nsplit", "masked", "merge", "byte_lo", "attn_dma", "range_flag", "out_proj_mode", "linear2_mode", "attn_pack")
+
+    def dbg_layer(self, X: np.ndarray, layer: int, dims: Tuple[int, int, int, int], precision: str = "f16mx", n_agents=None, last: bool = False):
+        """Encoder layer ``layer`` of one net evaluation as a step of a one-chunk call of shape ``dims`` = (E, A, K, T) runs it
+        (``jmid_dbg_layer``), every stage copied out in between: X [M, d_model] float32 -> (stages, plan).  ``stages[s]`` is the pair
+        (hi plane, lo plane) of stage s as float32 arrays - 0: X as split, 1: Q | K | V as the attention kernel reads them [M, 3 d],
+        2: the attention output, 3: X after norm1, 4: linear1 + ReLU [M, d_ff], 5: X after norm2 - or None where the stage does not
+        exist (stage 2 when the out-projection's launch merges the split-KV partials).  ``plan``: the launch plan it ran, by
+        ``LAYER_PLAN_FIELDS``.  ``n_agents`` [E]: a padded call; ``last``: the encoder's last layer."""
+        E, A, K, T = (int(v) for v in dims)
+        X = np.ascontiguousarray(X, np.float32)
+        M, d, ff = E * K * A * T, self.dims.d_model, self.dims.d_ff
+        if X.shape != (M, d):
+            raise ValueError(f"expected X [{M}, {d}]")
+        nag = None
+        if n_agents is not None:
+            nag = np.ascontiguousarray(n_agents, np.int32)
+            if nag.shape != (E,):
+                raise ValueError(f"expected n_agents [{E}]")
+        widths = (d, 3 * d, d, d, ff, d)
+        total = sum(widths)
+        hi, lo = np.empty((M * total,), np.float32), np.empty((M * total,), np.float32)
+        plan = (C.c_int * len(self.LAYER_PLAN_FIELDS))()
+        self._check(self._lib.jmid_dbg_layer(self._h, E, A, K, T, int(layer), _lib.PRECISIONS[precision], C.c_void_p(X.ctypes.data),
+                                             C.c_void_p(nag.ctypes.data) if nag is not None else None, int(bool(last)),
+                                             C.c_void_p(hi.ctypes.data), C.c_void_p(lo.ctypes.data), plan))
+        plan = dict(zip(self.LAYER_PLAN_FIELDS, (int(v) for v in plan)))
+        stages, at = [], 0
+        for s, w in enumerate(widths):
+            pair = (hi[M * at:M * (at + w)].reshape(M, w), lo[M * at:M * (at + w)].reshape(M, w))
+            stages.append(pair if plan["stages"] >> s & 1 else None)
+            at += w
+        return stages, plan
+
     def hyper_width(self) -> int:
         """Row length of the ConcatSquash hyper vectors, gate1 | bias1 | gate3 | bias3 | gate4 | bias4 | gateO | biasO (the library
         checks it: ``jmid_dbg_qkv0`` refuses any other)."""
