@@ -387,8 +387,8 @@ int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float
  * jmid_build_scene_stamped has none and runs the launches it always ran.
  * JMID_EINVAL (the resident scene is kept): a first_frame outside 0..F-1, a robot with fewer than 2 frames while force_all_in_cluster is
  * 0, and every refusal of jmid_build_scene.
- * Not covered: raw-stamp input (jmid_build_scene_stamped still ends in JMID_EHISTORY below hist_len grid frames), gaps inside a track's
- * span, and tracks that end before the last frame (leave those out of the scene). */
+ * Raw-stamp input, with gaps inside a track's span interpolated: jmid_build_scene_stamped_var (jmid_build_scene_stamped still ends in
+ * JMID_EHISTORY below hist_len grid frames).  Not covered: tracks that end before the last frame (leave those out of the scene). */
 int jmid_build_scene_var(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, const int32_t* first_frame,
                          double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out,
                          int* n_in_out, double* cv_out, int mem);
@@ -427,6 +427,35 @@ int jmid_predict_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const
 int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
                              const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
                              uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int mem);
+
+/* jmid_build_scene_stamped with a history window PER TRACK: a NaN coordinate of pedestrian j in a raw frame means "track j was not seen in
+ * this frame" and drops nothing, and a window shorter than hist_len is built, not refused.  The arguments of jmid_build_scene_stamped and
+ *   first_frame_out [E, N + 1] int32 or NULL   robot first, the first_frame of jmid_build_scene_var as derived from the raw frames
+ * One definition, shared with scene.py::frame_table_tracks (fp64, no FMA, the association of jmid_build_scene_stamped):
+ *   1. pose_now = the human positions of the last PUSHED valid frame (NaN for a track not seen there)
+ *   2. a frame is dropped iff its stamp or a robot coordinate is NaN
+ *   3. the kept frames, in stable sort order by stamp, share one grid: ns = trunc(stamp * 100), w = round(time_step * 100), bin
+ *      b = floor((ns_last - ns) / w) counted back from the newest kept frame (the ANCHOR), nb = max(b) + 1, n_grid = min(hist_len, nb).
+ *      The robot's column is jmid_build_scene_stamped's.
+ *   4. pedestrian j's frames are the kept ones where both its coordinates are non-NaN.  A bin holds the last sorted of them; an empty bin
+ *      between filled ones is interpolated between the nearest filled older and newer bin OF THAT TRACK in index space x = nb-1-b;
+ *      nothing is extrapolated in front of its oldest filled bin b_old(j), which may lie beyond the window.
+ *   5. the grid is right-aligned in hist_len rows, NaN in front, the newest frame in row hist_len-1 (jmid_scene_get_frames returns it so);
+ *      first_frame = hist_len - n_grid for the robot and hist_len-1 - min(b_old(j), n_grid-1) for pedestrian j - a pedestrian seen only in
+ *      the anchor frame is a graph node and no ego row, as jmid_build_scene_var has it.
+ * Then exactly jmid_build_scene_var on that grid and first_frame: first_index is resident, and jmid_predict_scene, jmid_forecast_scene, their
+ * _seeded and _padded forms, jmid_scene_get* and jmid_scene_get_frames work on the scene unchanged.  Without a human NaN and with
+ * n_grid = hist_len every resident array has the bits jmid_build_scene_stamped leaves.
+ * n_grid_out and first_frame_out are filled before either refusal below, and the previously resident scene, if any, is kept:
+ *   JMID_EHISTORY  an episode has n_grid < 2
+ *   JMID_EINVAL    a pedestrian is not seen in the anchor frame (first_frame_out -1; jmid_last_error names the episode and the track): the
+ *                  resident scene cannot hold a node that is absent now - leave the track out of the call, as for an empty cluster;
+ *                  and every refusal of jmid_build_scene_stamped.
+ * Not covered: absent-now nodes inside the scene, tracks that end early with an extrapolated forecast. */
+int jmid_build_scene_stamped_var(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
+                                 const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
+                                 uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int32_t* first_frame_out,
+                                 int mem);
 
 /* The grid the resident scene was built from and its pose_now, as doubles: human_xy [E, F, N, 2], robot_xy [E, F, 2] (the frame table of
  * mid_sim_wrapper.py:244-298 after jmid_build_scene_stamped; the caller's own input after a plain jmid_build_scene) and pose_now [E, N, 2]

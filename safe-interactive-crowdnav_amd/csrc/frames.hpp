@@ -18,6 +18,23 @@
 // per-bin sources ([R] and [F] entries: frames_lds); the coordinates themselves (R x (2N + 2) doubles, N <= 63) are read where they lie.
 // Latency-bound and tiny: clarity before cleverness.
 //
+// track_frames_kernel: the frame table PER TRACK (jmid_build_scene_stamped_var; the device twin of scene.py::frame_table_tracks, in its
+// operation order).  A NaN coordinate of pedestrian j means "track j was not seen in this frame" and drops nothing:
+//   1. pose_now as above (NaN for a track not seen in the last pushed frame)
+//   2. a frame is dropped iff its stamp or a robot coordinate is NaN
+//   3. the kept frames share ONE grid: the bins of step 4 above, counted back from the newest kept frame (the anchor), nb and n_grid as
+//      above; the robot's column is frames_kernel's
+//   4. pedestrian j's frames are the kept ones where both its coordinates are non-NaN.  A bin holds the last sorted of them; an empty bin
+//      between filled ones is interpolated between the nearest filled older and newer bin OF THAT TRACK by the formula of step 5 above
+//      (x = nb-1-b with the shared nb); nothing is extrapolated in front of its oldest filled bin b_old(j), which may lie beyond F-1
+//   5. the outputs are RIGHT-aligned in F rows: row p holds bin F-1-p, NaN in front (the layout of scene.py::pad_short_window, what
+//      scene_kernel takes with first_frame); first_frame [N + 1], robot first: F - n_grid for the robot, F-1 - min(b_old(j), n_grid-1) for
+//      pedestrian j, -1 for a pedestrian not seen in the anchor frame (absent now: its column NaN, the host refuses the build)
+// One wavefront per episode, a lane per raw frame for the stamps and bins (LDS, shared by all tracks); a track's seen set over the 64
+// lanes is one ballot word; then one lane per (track, row) finds the last sorted seen frame of its bin, or the two ends of its
+// interpolation, reads the coordinates where they lie and writes its two doubles - every output element once, plain vector stores, a
+// fixed order.  frames_kernel itself is untouched.
+//
 // assemble_kernel: the device twin of scene.py::assemble_forecasts (mid_sim_wrapper.py:493-510, :444-454): one thread per
 // (episode, pedestrian, kept sample) writes its (T + 1) x 2 doubles of forecasts [E, N, k, T+1, 2] and its double of logw [E, N, k].
 // Copies and exact fp32 -> fp64 widenings only; plain vector stores, no atomics, a fixed order: bit-reproducible.
@@ -157,6 +174,148 @@ static __global__ __launch_bounds__(SCN_LANES) void frames_kernel(FramesArgs g) 
 
 inline hipError_t launch_frames(const FramesArgs& g, hipStream_t st) {
     hipLaunchKernelGGL(frames_kernel, dim3(g.E), dim3(SCN_LANES), frames_lds(g.R, g.F), st, g);
+    return hipGetLastError();
+}
+
+struct TrackFramesArgs {
+    const double* stamps;         // [E, R]
+    const double* human_xy;       // [E, R, N, 2]
+    const double* robot_xy;       // [E, R, 2]
+    const int* n_frames;          // [E] or null, as FramesArgs
+    double* o_human;              // [E, F, N, 2]   right-aligned: NaN in front, the newest frame in row F-1
+    double* o_robot;              // [E, F, 2]
+    double* o_pose;               // [E, N, 2]
+    int* o_n_grid;                // [E]   (-1: n_frames[e] outside 1..R, nothing else written for that episode)
+    int* o_first;                 // [E, N + 1]   robot first; -1: a pedestrian not seen in the anchor frame
+    long long w;                  // round(time_step * 100) >= 1
+    int E, N, R, F;
+};
+
+// the shared bins of step 3 and the seen sets of step 4 (column group N = the robot: the kept frames)
+struct TrackFramesLds {
+    double t[FRM_MAX_R];
+    long long bin[FRM_MAX_R];
+    unsigned long long seen[SCN_LANES];
+};
+
+static __global__ __launch_bounds__(SCN_LANES) void track_frames_kernel(TrackFramesArgs g) {
+#pragma clang fp contract(off)
+    __shared__ TrackFramesLds s;
+    const int i = threadIdx.x, e = blockIdx.x;
+    const int N = g.N, R = g.R, F = g.F;
+    const int n = g.n_frames ? g.n_frames[e] : R;
+    if (n < 1 || n > R) {                                     // (uniform: the whole wavefront leaves)
+        if (i == 0) g.o_n_grid[e] = -1;
+        return;
+    }
+    const double* st = g.stamps + (size_t)e * R;
+    const double* hum = g.human_xy + (size_t)e * R * N * 2;
+    const double* rob = g.robot_xy + (size_t)e * R * 2;
+    double* oh = g.o_human + (size_t)e * F * N * 2;
+    double* orb = g.o_robot + (size_t)e * F * 2;
+    int* of = g.o_first + (size_t)e * (N + 1);
+    const double nan = __builtin_nan("");
+    // coordinate c (0, 1) of column group q in raw frame r: pedestrian q < N, the robot q == N
+    auto val = [&](int r, int q, int c) -> double { return q < N ? hum[((size_t)r * N + q) * 2 + c] : rob[r * 2 + c]; };
+    // step 1
+    for (int q = i; q < 2 * N; q += SCN_LANES) g.o_pose[(size_t)e * 2 * N + q] = hum[(size_t)(n - 1) * 2 * N + q];
+    // step 2: lane i holds raw frame i; one ballot word per column group says on which kept frames it is seen
+    bool kept = false;
+    if (i < n) {
+        const double ts = st[i], rx = rob[i * 2], ry = rob[i * 2 + 1];
+        kept = ts == ts && rx == rx && ry == ry;
+        s.t[i] = ts;
+    }
+    const unsigned long long keep = __ballot(kept);
+    for (int q = 0; q < N; ++q) {
+        bool here = false;
+        if (kept) {
+            const double x = val(i, q, 0), y = val(i, q, 1);
+            here = x == x && y == y;
+        }
+        const unsigned long long m = __ballot(here);
+        if (i == 0) s.seen[q] = m;
+    }
+    if (i == 0) s.seen[N] = keep;
+    __syncthreads();
+    int n_grid = 0, last = -1;
+    long long nb = 0;
+    if (keep) {
+        // step 3: the anchor = the last kept frame in (stamp, push index) order; every track shares its bins
+        for (int j = 0; j < n; ++j)
+            if (((keep >> j) & 1ull) && (last < 0 || s.t[j] >= s.t[last])) last = j;
+        const long long ns_last = (long long)trunc(s.t[last] * 100.0);
+        if (i < n) {
+            long long b = -1;
+            if (kept) {
+                const long long a = ns_last - (long long)trunc(s.t[i] * 100.0);
+                b = a / g.w;
+                if (a % g.w != 0 && a < 0) --b;               // floor division (a >= 0 for sorted stamps; w >= 1)
+            }
+            s.bin[i] = b;
+        }
+        __syncthreads();
+        for (int j = 0; j < n; ++j)
+            if (s.bin[j] + 1 > nb) nb = s.bin[j] + 1;
+        n_grid = nb < (long long)F ? (int)nb : F;
+    }
+    // steps 4-5: one (column group, row) per lane and pass; row p holds bin F-1-p.  NaN: a row in front of the grid, a bin older than
+    // the track's oldest filled one, a pedestrian not seen in the anchor frame
+    for (int u = i; u < (N + 1) * F; u += SCN_LANES) {
+        const int q = u / F, p = u % F;
+        const long long b = F - 1 - p;
+        const unsigned long long m = last < 0 ? 0ull : s.seen[q];
+        double y[2] = {nan, nan};
+        if (b < n_grid && ((m >> last) & 1ull)) {
+            int hit = -1;
+            long long bo = -1, bn = -1;                       // the track's nearest filled older / newer bin
+            for (int j = 0; j < n; ++j) {
+                if (!((m >> j) & 1ull)) continue;
+                const long long bj = s.bin[j];
+                if (bj == b && (hit < 0 || s.t[j] >= s.t[hit])) hit = j;
+                if (bj > b && (bo < 0 || bj < bo)) bo = bj;
+                if (bj < b && bj > bn) bn = bj;
+            }
+            if (hit >= 0) {
+                y[0] = val(hit, q, 0);
+                y[1] = val(hit, q, 1);
+            } else if (bo >= 0 && bn >= 0) {                  // (bn: bin 0 holds the anchor; no bo: older than the track - NaN)
+                int jo = -1, jn = -1;                         // their last frames
+                for (int j = 0; j < n; ++j) {
+                    if (!((m >> j) & 1ull)) continue;
+                    if (s.bin[j] == bo && (jo < 0 || s.t[j] >= s.t[jo])) jo = j;
+                    if (s.bin[j] == bn && (jn < 0 || s.t[j] >= s.t[jn])) jn = j;
+                }
+                const double x0 = (double)(nb - 1 - bo), x1 = (double)(nb - 1 - bn), x = (double)(nb - 1 - b);
+                for (int c = 0; c < 2; ++c) {
+                    const double y0 = val(jo, q, c), y1 = val(jn, q, c);
+                    const double slope = (y1 - y0) / (x1 - x0);
+                    y[c] = slope * (x - x0) + y0;
+                }
+            }
+        }
+        double* o = q < N ? oh + ((size_t)p * N + q) * 2 : orb + p * 2;
+        o[0] = y[0];
+        o[1] = y[1];
+    }
+    // first_frame: lane q for pedestrian q, lane N for the robot
+    if (i <= N) {
+        int f = -1;
+        if (i == N) {
+            f = F - n_grid;
+        } else if (last >= 0 && ((s.seen[i] >> last) & 1ull)) {
+            long long b_old = 0;
+            for (int j = 0; j < n; ++j)
+                if (((s.seen[i] >> j) & 1ull) && s.bin[j] > b_old) b_old = s.bin[j];
+            f = F - 1 - (int)(b_old < (long long)(n_grid - 1) ? b_old : (long long)(n_grid - 1));
+        }
+        of[i == N ? 0 : i + 1] = f;
+    }
+    if (i == 0) g.o_n_grid[e] = n_grid;
+}
+
+inline hipError_t launch_track_frames(const TrackFramesArgs& g, hipStream_t st) {
+    hipLaunchKernelGGL(track_frames_kernel, dim3(g.E), dim3(SCN_LANES), 0, st, g);
     return hipGetLastError();
 }
 

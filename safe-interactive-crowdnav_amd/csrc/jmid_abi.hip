@@ -831,32 +831,38 @@ int jmid_scene_get_first_index(jmid_handle_t h, int32_t* out, int mem) {
     return order_out(h, mem);
 }
 
-int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
-                             const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
-                             uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int mem) {
+// jmid_build_scene_stamped (tracks false: frames_kernel, a window shorter than hist_len refused) and jmid_build_scene_stamped_var (tracks true:
+// track_frames_kernel, first_frame [E, N + 1] read back with n_grid in the one synchronisation and handed to build_scene_resident)
+static int build_scene_stamped_entry(jmid_handle_t h, const char* who_c, bool tracks, int E, int N, int R, const double* stamps, const double* human_xy,
+                                     const double* robot_xy, const int* n_frames, double time_step, int horizon, int force_all_in_cluster,
+                                     uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out,
+                                     int32_t* first_frame_out, int mem) {
     if (!h) return JMID_EINVAL;
+    const std::string who(who_c);
     if (E <= 0 || !stamps || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out || !n_grid_out)
-        return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: bad argument");
-    if (R < 1 || R > FRM_MAX_R) return fail(h, JMID_EINVAL, "jmid_build_scene_stamped supports 1 <= R <= 64 raw frames");
+        return fail(h, JMID_EINVAL, who + ": bad argument");
+    if (R < 1 || R > FRM_MAX_R) return fail(h, JMID_EINVAL, who + " supports 1 <= R <= 64 raw frames");
     const int F = h->hist_len;
-    if (int rc = check_scene_dims(h, "jmid_build_scene_stamped", N, F, cv_out, horizon, time_step)) return rc;
+    if (int rc = check_scene_dims(h, who_c, N, F, cv_out, horizon, time_step)) return rc;
     // w = round(time_step * 100) as Python rounds it (to nearest, ties to even)
     const double wd = std::nearbyint(time_step * 100.0);
-    if (!(wd >= 1.0) || wd > 9.0e15) return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: round(time_step * 100) must be at least 1");
+    if (!(wd >= 1.0) || wd > 9.0e15) return fail(h, JMID_EINVAL, who + ": round(time_step * 100) must be at least 1");
     const bool host = mem == JMID_MEM_HOST;
     if (host && n_frames)
         for (int e = 0; e < E; ++e)
             if (n_frames[e] < 1 || n_frames[e] > R)
-                return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: n_frames[" + std::to_string(e) + "] = " + std::to_string(n_frames[e]) + " is outside 1..R");
+                return fail(h, JMID_EINVAL, who + ": n_frames[" + std::to_string(e) + "] = " + std::to_string(n_frames[e]) + " is outside 1..R");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
     const size_t b_st = (size_t)E * R * 8, b_hum = (size_t)E * R * N * 2 * 8, b_rob = (size_t)E * R * 2 * 8, b_nf = n_frames ? (size_t)E * 4 : 0;
     const GridBlock gb = grid_block(E, N, F);
-    // the grid block frames_kernel writes | n_grid | the staged raw frames (host mode): stamps, human_xy, robot_xy, n_frames
-    const size_t o_ng = gb.end, o_st = o_ng + align_up((size_t)E * 4), o_rh = o_st + (host ? align_up(b_st) : 0), o_rr = o_rh + (host ? align_up(b_hum) : 0),
+    // the grid block frames_kernel writes | n_grid (tracks: and first_frame [E, N + 1] behind it, one download) | the staged raw frames (host
+    // mode): stamps, human_xy, robot_xy, n_frames
+    const size_t n_first = tracks ? (size_t)E * (N + 1) : 0, b_back = ((size_t)E + n_first) * 4;
+    const size_t o_ng = gb.end, o_st = o_ng + align_up(b_back), o_rh = o_st + (host ? align_up(b_st) : 0), o_rr = o_rh + (host ? align_up(b_hum) : 0),
                  o_nf = o_rr + (host ? align_up(b_rob) : 0), need = o_nf + (host ? align_up(b_nf) : 0), raw = need - o_st;
-    if (int rc = h->frames_dev.reserve(h, need, "jmid_build_scene_stamped")) return rc;
-    if (int rc = h->pin.reserve(h, raw + (size_t)E * 4, "jmid_build_scene_stamped")) return rc;
+    if (int rc = h->frames_dev.reserve(h, need, who_c)) return rc;
+    if (int rc = h->pin.reserve(h, raw + b_back, who_c)) return rc;
     char *const fd = h->frames_dev.p, *const pin = h->pin.p;
     FramesArgs f{};
     f.E = E; f.N = N; f.R = R; f.F = F;
@@ -874,28 +880,67 @@ int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double*
         f.robot_xy = reinterpret_cast<const double*>(fd + o_rr);
         f.n_frames = n_frames ? reinterpret_cast<const int*>(fd + o_nf) : nullptr;
     }
-    HIPCHK(h, launch_frames(f, h->stream));
+    if (tracks) {
+        TrackFramesArgs t{};
+        t.E = E; t.N = N; t.R = R; t.F = F;
+        t.w = f.w;
+        t.stamps = f.stamps; t.human_xy = f.human_xy; t.robot_xy = f.robot_xy; t.n_frames = f.n_frames;
+        t.o_human = f.o_human; t.o_robot = f.o_robot; t.o_pose = f.o_pose; t.o_n_grid = f.o_n_grid;
+        t.o_first = f.o_n_grid + E;
+        HIPCHK(h, launch_track_frames(t, h->stream));
+    } else {
+        HIPCHK(h, launch_frames(f, h->stream));
+    }
     int* ng = reinterpret_cast<int*>(pin + raw);
-    HIPCHK(h, hipMemcpyAsync(ng, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToHost, h->stream));
-    if (!host) HIPCHK(h, hipMemcpyAsync(n_grid_out, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ng, f.o_n_grid, b_back, hipMemcpyDeviceToHost, h->stream));
+    if (!host) {
+        HIPCHK(h, hipMemcpyAsync(n_grid_out, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (first_frame_out) HIPCHK(h, hipMemcpyAsync(first_frame_out, f.o_n_grid + E, n_first * 4, hipMemcpyDeviceToDevice, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (host) std::memcpy(n_grid_out, ng, (size_t)E * 4);
+    if (host) {
+        std::memcpy(n_grid_out, ng, (size_t)E * 4);
+        if (first_frame_out) std::memcpy(first_frame_out, ng + E, n_first * 4);
+    }
     for (int e = 0; e < E; ++e)
         if (ng[e] < 0) {
             (void)order_out(h, mem);
-            return fail(h, JMID_EINVAL, "jmid_build_scene_stamped: n_frames[" + std::to_string(e) + "] is outside 1..R");
+            return fail(h, JMID_EINVAL, who + ": n_frames[" + std::to_string(e) + "] is outside 1..R");
         }
+    const int F_min = tracks ? 2 : F;                         // a per-track table starts every node where its own frames start
     for (int e = 0; e < E; ++e)
-        if (ng[e] < F) {
+        if (ng[e] < F_min) {
             const int got = ng[e];
             (void)order_out(h, mem);
-            return fail(h, JMID_EHISTORY, "jmid_build_scene_stamped: episode " + std::to_string(e) + " has " + std::to_string(got) +
-                                              " history frames on the time_step grid, " + std::to_string(F) + " needed");
+            return fail(h, JMID_EHISTORY, who + ": episode " + std::to_string(e) + " has " + std::to_string(got) +
+                                              " history frames on the time_step grid, " + std::to_string(F_min) + " needed");
         }
-    if (int rc = build_scene_resident(h, "jmid_build_scene_stamped", E, N, F, reinterpret_cast<const double*>(fd), nullptr, 2, time_step, horizon, force_all_in_cluster,
-                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem))
+    // (build_scene_resident stages through the pinned block again: first_frame leaves it first)
+    std::vector<int32_t> first(ng + E, ng + E + n_first);
+    for (size_t q = 0; q < n_first; ++q)
+        if (first[q] < 0) {
+            (void)order_out(h, mem);
+            return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(q / (N + 1)) + ", track " + std::to_string((int)(q % (N + 1)) - 1) +
+                                            " is not seen in the newest kept frame (leave the track out)");
+        }
+    if (int rc = build_scene_resident(h, who_c, E, N, F, reinterpret_cast<const double*>(fd), nullptr, 2, time_step, horizon, force_all_in_cluster,
+                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem, tracks ? first.data() : nullptr))
         return rc;
     return order_out(h, mem);
+}
+
+int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
+                             const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
+                             uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int mem) {
+    return build_scene_stamped_entry(h, "jmid_build_scene_stamped", false, E, N, R, stamps, human_xy, robot_xy, n_frames, time_step, horizon,
+                                     force_all_in_cluster, in_cluster_out, robot_in_cluster_out, n_in_out, n_grid_out, cv_out, nullptr, mem);
+}
+
+int jmid_build_scene_stamped_var(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
+                                 const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
+                                 uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int32_t* first_frame_out, int mem) {
+    return build_scene_stamped_entry(h, "jmid_build_scene_stamped_var", true, E, N, R, stamps, human_xy, robot_xy, n_frames, time_step, horizon,
+                                     force_all_in_cluster, in_cluster_out, robot_in_cluster_out, n_in_out, n_grid_out, cv_out, first_frame_out, mem);
 }
 
 int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_xy_out, double* pose_now_out, int mem) {

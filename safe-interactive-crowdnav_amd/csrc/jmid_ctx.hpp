@@ -173,8 +173,8 @@ struct jmid_ctx {
         size_t o_first = 0;
         bool has_first = false;
     } scene;
-    // jmid_build_scene_stamped: the raw frames and what frames_kernel made of them (grid, pose_now, n_grid), in a workspace of its own:
-    // a build that ends with JMID_EHISTORY must not touch the resident scene
+    // jmid_build_scene_stamped / _stamped_var: the raw frames and what frames_kernel / track_frames_kernel made of them (grid, pose_now,
+    // n_grid, first_frame), in a workspace of its own: a refused build (JMID_EHISTORY, an absent-now track) must not touch the resident scene
     jmid_host::Block frames_dev;
     // the seeded entry points: the call's episode ids on the device (the fill kernel reads them there); the padded ones: its agent counts
     jmid_host::HostArray noise_ids, nag;

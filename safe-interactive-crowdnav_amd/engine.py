@@ -526,13 +526,18 @@ class JmidEngine:
 
     def build_scene_stamped(self, stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
                             horizon: Optional[int] = None, force_all_in_cluster: bool = False,
-                            n_frames: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
+                            n_frames: Optional[np.ndarray] = None, tracks: bool = False) -> Dict[str, np.ndarray]:
         """``build_scene`` from raw stamped frames (``jmid_build_scene_stamped``; the frame table is the device twin of
         ``scene.frame_table_frames_batched``): stamps [E, R], human_xy [E, R, N, 2], robot_xy [E, R, 2] float64, oldest-pushed first, the
         first ``n_frames[e]`` of each episode valid (None: all R) - or [R], [R, N, 2], [R, 2] for one scene, whose results then come without
         the episode axis.  Returns what ``build_scene`` returns plus ``n_grid`` [E] int32.  Raises ``scene.HistoryTooShortError`` when an
-        episode has fewer than ``hist_len`` frames on the grid (JMID_EHISTORY; a scene built before stays resident)."""
-        from .scene import HistoryTooShortError
+        episode has fewer than ``hist_len`` frames on the grid (JMID_EHISTORY; a scene built before stays resident).
+        ``tracks=True`` (``jmid_build_scene_stamped_var``; the device twin of ``scene.frame_table_tracks_batched``): a history window per
+        track - a NaN human coordinate means "not seen in this frame" and drops nothing, a window of 2 .. hist_len-1 grid frames is built
+        like ``build_scene(first_frame=)`` - and ``first_frame`` [E, N + 1] int32 (robot first) is returned as well.
+        ``HistoryTooShortError`` then means fewer than 2 grid frames; a pedestrian who is not seen in the newest kept frame raises
+        ``scene.TrackAbsentError(episode, track)`` (leave the track out; a scene built before stays resident)."""
+        from .scene import HistoryTooShortError, TrackAbsentError
         st = np.ascontiguousarray(stamps, dtype=np.float64)
         hum = np.ascontiguousarray(human_xy, dtype=np.float64)
         rob = np.ascontiguousarray(robot_xy, dtype=np.float64)
@@ -550,20 +555,33 @@ class JmidEngine:
         inc = np.empty((E, N), dtype=np.uint8)
         rin = np.empty(E, dtype=np.uint8)
         n_in = np.empty(E, dtype=np.int32)
-        n_grid = np.empty(E, dtype=np.int32)
+        n_grid = np.zeros(E, dtype=np.int32)         # (zeros: a refusal in front of the kernel leaves them, and is then no absent-now one)
         cv = np.empty((E, N, int(horizon), 2), dtype=np.float64) if horizon is not None else None
-        rc = self._lib.jmid_build_scene_stamped(self._h, E, N, R, C.c_void_p(st.ctypes.data), C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data),
-                                                C.c_void_p(nf.ctypes.data) if nf is not None else None, float(time_step),
-                                                int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
-                                                C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
-                                                C.c_void_p(n_grid.ctypes.data), C.c_void_p(cv.ctypes.data) if cv is not None else None, _lib.MEM_HOST)
+        head = (self._h, E, N, R, C.c_void_p(st.ctypes.data), C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data),
+                C.c_void_p(nf.ctypes.data) if nf is not None else None, float(time_step),
+                int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
+                C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
+                C.c_void_p(n_grid.ctypes.data), C.c_void_p(cv.ctypes.data) if cv is not None else None)
+        first = None
+        if tracks:
+            first = np.zeros((E, N + 1), dtype=np.int32)
+            rc = self._lib.jmid_build_scene_stamped_var(*head, C.c_void_p(first.ctypes.data), _lib.MEM_HOST)
+        else:
+            rc = self._lib.jmid_build_scene_stamped(*head, _lib.MEM_HOST)
         if rc == _lib.EHISTORY:
             err = HistoryTooShortError(self._lib.jmid_last_error(self._h).decode())
             err.n_grid = n_grid[0] if single else n_grid
             raise err
+        if tracks and rc == _lib.EINVAL and (n_grid >= 2).all() and (first < 0).any():     # the absent-now refusal: both arrays were filled
+            e, j = (int(v[0]) for v in np.nonzero(first < 0))
+            err = TrackAbsentError(e, j - 1, f"JMID_EINVAL: {self._lib.jmid_last_error(self._h).decode()}")
+            err.first_frame = first[0] if single else first
+            raise err
         self._check(rc)
         self._scene_shape, self._scene_n_in = (E, N, self.hist_len, single), n_in
         out = {"in_cluster": inc.astype(bool), "robot_in_cluster": rin.astype(bool), "n_in": n_in, "n_grid": n_grid, "cv": cv}
+        if tracks:
+            out["first_frame"] = first
         return {k: (v[0] if single and v is not None else v) for k, v in out.items()}
 
     def scene_frames(self) -> Dict[str, np.ndarray]:

@@ -44,7 +44,10 @@ Differences from the reference that a caller can observe:
     ``nn.ModuleDict`` container (which needs the reference tree on ``sys.path`` to unpickle);
   * a too-short history raises ``HistoryTooShortError`` (a ``TypeError``, like the reference's failure mode) - unless the instance was
     made with ``short_history=True`` (opt-in): then a call with 2 .. past_num_frames - 1 shared frames predicts, every track encoded from
-    its first frame on as the reference's MODEL does it (``first_history_index``, MID/dataset/preprocessing.py:468).
+    its first frame on as the reference's MODEL does it (``first_history_index``, MID/dataset/preprocessing.py:468);
+  * ``track_presence=True`` (opt-in, with ``short_history=True``): ``update_state_hists`` may be fed NaN positions for a pedestrian who is not
+    seen.  The reference's table drops such a frame for everybody (``mid_sim_wrapper.py:266``); here every track keeps a window of its own
+    (``scene.frame_table_tracks``), and a pedestrian who is NaN in the newest frame is left out of the call - his rows come back NaN.
 """
 from __future__ import annotations
 
@@ -174,7 +177,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  device_id: Optional[int] = None, precision: Optional[str] = None, rng_compat: Optional[str] = None,
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
                  lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
-                 seed: int = 0, episode_id: int = 0, short_history: bool = False):
+                 seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -204,6 +207,15 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # first_history_index) - instead of raising HistoryTooShortError.  One frame still raises; from past_num_frames frames on
         # nothing changes
         self.short_history = bool(short_history)
+        # True (opt-in, needs short_history): a history window PER TRACK.  update_state_hists may be fed NaN positions for a pedestrian who
+        # is not seen; such a frame is not dropped (scene.frame_table_tracks), a track that appears mid-run is encoded from its own first
+        # frame and a hole inside a track is interpolated.  A pedestrian who is NaN in the anchor frame (the newest frame with a stamp
+        # and a robot position) is absent now: left out of the call, his rows NaN in both returned arrays; everybody absent raises
+        # HistoryTooShortError.  With device_frames the raw frames go to the device as they are (jmid_build_scene_stamped_var): ONE build
+        # and ONE chain, short windows included
+        self.track_presence = bool(track_presence)
+        if self.track_presence and not self.short_history:
+            raise ValueError("track_presence needs short_history=True (a track that appears mid-run has a short window)")
         self.erange_fallbacks = 0
         self.timings: Dict[str, float] = {}     # ms of the last predict_ret_best(): scene, device, topk, assemble
         if rng_compat not in ("auto", "cpu", "cuda", "device"):
@@ -309,6 +321,11 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         when the scene is resident; the padded short window's first_frame [N + 1] or None).  Raises HistoryTooShortError before
         anything is drawn."""
         F, H, ff = self.num_hist_frames, self.predict_horizon, None
+        if self.track_presence:
+            # (lists edited by hand are no frames: they take the table below, where a NaN position drops its frame)
+            frames = SC.histories_as_frames(prev, rob, joined=False)
+            if frames is not None:
+                return self._scene_tracks(*frames)
         if self.short_history:
             hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, F)
             if 2 <= hum_xy.shape[0] < F:
@@ -319,16 +336,41 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
             # the frame table on the device too (JMID_EHISTORY -> HistoryTooShortError, where build_scene raises it on the host path);
             # the pose is read back only by the staged path (forecast_scene prepends it on the device)
             ds = self.engine.build_scene_stamped(*frames, self.time_step, H)
-            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], None, None, None
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], None, None, None, None
         if not self.short_history:                          # (short_history has the table already)
             hum_xy, rob_xy, pose_now = SC.frame_table(prev, rob, self.time_step, F)
         if source == "resident":
             if hum_xy.shape[0] < F:
                 raise SC.HistoryTooShortError(f"{hum_xy.shape[0]} history frames available, {F} needed")
             ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, H, first_frame=ff)
-            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], pose_now, None, ff
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], pose_now, None, ff, None
         sb = SC.build_scene(hum_xy, rob_xy, self.time_step, H, F, first_frame=ff)
-        return source, sb.ids_in, sb.cv_forecasts, pose_now, sb, ff
+        return source, sb.ids_in, sb.cv_forecasts, pose_now, sb, ff, None
+
+    def _scene_tracks(self, stamps, hum, rob):
+        """``_scene`` with ``track_presence`` for histories that are frames: its returns for the pedestrians who are present now, and
+        ``present`` [N] bool - the pedestrians seen in the anchor frame (the others are left out; nobody left: HistoryTooShortError)."""
+        F, H = self.num_hist_frames, self.predict_horizon
+        kept = np.nonzero(~(np.isnan(stamps) | np.isnan(rob).any(axis=1)))[0]
+        if not len(kept):
+            raise SC.HistoryTooShortError("no history frame with a stamp and a robot position")
+        anchor = kept[np.argsort(stamps[kept], kind="stable")[-1]]
+        present = ~np.isnan(hum[anchor]).any(axis=1)
+        if not present.any():
+            raise SC.HistoryTooShortError("no pedestrian is seen in the newest history frame")
+        hum = np.ascontiguousarray(hum[:, present])
+        source = scene_source(self.device_scene, self.device_frames, short=True, tracks=True)
+        if source == "stamped":      # raw frames in, short windows included: one build (first_index resident), one chain
+            ds = self.engine.build_scene_stamped(stamps, hum, rob, self.time_step, H, tracks=True)
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], None, None, ds["first_frame"], present
+        hum_xy, rob_xy, pose_now, ff, _ = SC.frame_table_tracks(stamps, hum, rob, self.time_step, F)
+        if not ff.any():             # everybody on every frame: the bits of a build without first_frame, and its routes
+            ff = None
+        if source == "resident":
+            ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, H, first_frame=ff)
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], pose_now, None, ff, present
+        sb = SC.build_scene(hum_xy, rob_xy, self.time_step, H, F, first_frame=ff)
+        return source, sb.ids_in, sb.cv_forecasts, pose_now, sb, ff, present
 
     def _draw_x_T(self, A: int) -> np.ndarray:
         """Noise stage -> x_T [1, K * A, H, 2].  RNG contract (module docstring): x_T is the first draw of the CPU default generator; the
@@ -362,13 +404,14 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
     def _predict_ret_best(self) -> Tuple[np.ndarray, np.ndarray]:
         """Snapshot -> scene -> noise -> route -> run (ONE chained library entry, or encode / denoise / rank) -> assembly -> timings."""
         t0 = time.perf_counter()
-        source, ids_in, cv, pose_now, sb, ff = self._scene(*self._snapshot())
+        source, ids_in, cv, pose_now, sb, ff, present = self._scene(*self._snapshot())
         A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
         x_np = self._draw_x_T(A)             # after the scene: a call that raises HistoryTooShortError has drawn nothing
         t1 = time.perf_counter()
         check = self.self_check and tuple(x_np.shape) not in self._checked_shapes
         route = plan_route(k=k, K=K, A=A, H=H, device_topk=self.device_topk, device_scene=self.device_scene,
-                           device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped")
+                           device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped",
+                           tracks=present is not None)
         result, call = None, dict(dt=self.time_step, precision=self.precision)
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
@@ -398,9 +441,13 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 rows, logw = rank_samples(self.engine, route.rank, pos, k, (1, A, K, H))
         t3 = time.perf_counter()
         if result is None:
-            in_cluster = np.zeros(self.num_hums, dtype=bool)
+            in_cluster = np.zeros(self.num_hums if present is None else int(present.sum()), dtype=bool)
             in_cluster[ids_in] = True
             result = SC.assemble_forecasts(in_cluster, rows[0], None if logw is None else logw[0], cv, pose_now, k, K)
+        if present is not None and not present.all():     # the rows of the pedestrians who are absent now: NaN
+            full = np.full((self.num_hums,) + result[0].shape[1:], np.nan), np.full((self.num_hums,) + result[1].shape[1:], np.nan)
+            full[0][present], full[1][present] = result
+            result = full
         t4 = time.perf_counter()
         self.timings = {"scene_ms": 1e3 * (t1 - t0), "device_ms": 1e3 * (t2 - t1), "topk_ms": 1e3 * (t3 - t2),
                         "assemble_ms": 1e3 * (t4 - t3), "total_ms": 1e3 * (t4 - t0)}
@@ -433,12 +480,15 @@ class Route(NamedTuple):
 
 
 def scene_source(device_scene: bool, device_frames: bool, short: bool = False, frames: bool = True, batch: bool = False,
-                 resident: bool = False) -> str:
+                 resident: bool = False, tracks: bool = False) -> str:
     """``Route.scene``.  ``predict_batch`` takes grid inputs: nothing to stamp.  A single call's histories that are not frames take the
-    host frame table, and a short window has no stamped form (its padded table is built with ``first_frame``).  ``resident``
+    host frame table, and a short window has no stamped form (its padded table is built with ``first_frame``) - unless the windows are
+    per track (``tracks``: ``track_presence`` on histories that are frames), whose stamped form builds short windows too.  ``resident``
     (``predict_batch(padded="resident")``): the whole batch is built on the device."""
     if batch:
         return "resident" if device_scene or device_frames or resident else "host"
+    if tracks and device_frames and frames:
+        return "stamped"
     if device_frames and frames and not short:
         return "stamped"
     return "resident" if device_scene or (device_frames and short) else "host"
@@ -446,12 +496,12 @@ def scene_source(device_scene: bool, device_frames: bool, short: bool = False, f
 
 def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, device_scene: bool = False, device_frames: bool = False,
                check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False,
-               resident: bool = False) -> Route:
+               resident: bool = False, tracks: bool = False) -> Route:
     """Every decision of a call that does not need an array: the flags, k of K samples, A in-cluster pedestrians, horizon H, whether the
     first-call self check is due (``check``), whether the window is short (``short``) and whether the histories are frames (``frames``).
     ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count, ``resident``: that form on the
-    batch's resident scene (``padded="resident"``: forecast_scene_padded)."""
-    scene = scene_source(device_scene, device_frames, short, frames, batch, resident)
+    batch's resident scene (``padded="resident"``: forecast_scene_padded).  ``tracks``: per-track windows (``track_presence``)."""
+    scene = scene_source(device_scene, device_frames, short, frames, batch, resident, tracks)
     # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits - the reference
     # has none - the host twin ranks them
     on_dev = k < K and device_topk and topk_fits_device(A, K, H)

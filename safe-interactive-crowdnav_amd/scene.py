@@ -174,11 +174,125 @@ def frame_table_frames_batched(stamps: np.ndarray, human_xy: np.ndarray, robot_x
     return out
 
 
-def histories_as_frames(prev_states, prev_robot_states):
+class TrackAbsentError(ValueError):
+    """A pedestrian is not seen in the anchor frame (the newest frame with a finite stamp and robot position) of an episode handed to
+    ``engine.build_scene_stamped(tracks=True)``: the resident scene cannot hold a node that is absent now.  Leave the track out."""
+
+    def __init__(self, episode: int, track: int, message: Optional[str] = None):
+        super().__init__(message or f"episode {episode}: track {track} is not seen in the anchor frame")
+        self.episode, self.track = int(episode), int(track)
+
+
+def _track_table(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, F: int):
+    """``frame_table_tracks`` without its refusal: (human_xy [F, N, 2], robot_xy [F, 2], pose_now [N, 2], first_frame [N + 1], n_grid)
+    whatever ``n_grid`` is (0: no kept frame - everything NaN, the robot's first_frame F, every pedestrian's -1)."""
+    stamps = np.asarray(stamps, dtype=np.float64).reshape(-1)
+    R = len(stamps)
+    human_xy = np.asarray(human_xy, dtype=np.float64).reshape(R, -1, 2)
+    robot_xy = np.asarray(robot_xy, dtype=np.float64).reshape(R, 2)
+    N = human_xy.shape[1]
+    hum, rob = np.full((F, N, 2), np.nan), np.full((F, 2), np.nan)
+    first = np.full(N + 1, -1, dtype=np.int32)
+    first[0] = F
+    pose_now = human_xy[-1].copy() if R else np.full((N, 2), np.nan)      # before anything is dropped or sorted
+    keep = ~(np.isnan(stamps) | np.isnan(robot_xy).any(axis=1))          # a human NaN drops nothing
+    if not keep.any():
+        return hum, rob, pose_now, first, 0
+    order = np.argsort(stamps[keep], kind="stable")
+    t, H, Rb = stamps[keep][order], human_xy[keep][order], robot_xy[keep][order]
+    ns = np.trunc(t * 100.0).astype(np.int64)
+    w = int(round(time_step * 100))
+    k = (ns[-1] - ns) // w                               # the shared bins, counted back from the anchor (the last sorted kept frame)
+    nb = int(k.max()) + 1
+    n_grid = min(F, nb)
+    first[0] = F - n_grid
+
+    def column(seen, y):                                 # y [n, 2] of one track, seen [n] bool with the anchor seen -> its b_old
+        ks = np.where(seen, k, -1)
+        b_old = int(ks.max())
+        col = np.full((F, 2), np.nan)
+        for b in range(min(b_old, n_grid - 1) + 1):
+            hit = np.nonzero(ks == b)[0]
+            if len(hit):
+                col[F - 1 - b] = y[hit[-1]]              # the LAST sorted seen frame of the bin
+                continue
+            bo = int(ks[ks > b].min())                   # the nearest filled older bin of THIS track (b < b_old: there is one)
+            bn = int(ks[(ks < b) & seen].max())          # the nearest filled newer one (bin 0 holds the anchor)
+            y0, y1 = y[np.nonzero(ks == bo)[0][-1]], y[np.nonzero(ks == bn)[0][-1]]
+            x0, x1, x = float(nb - 1 - bo), float(nb - 1 - bn), float(nb - 1 - b)
+            slope = (y1 - y0) / (x1 - x0)
+            col[F - 1 - b] = slope * (x - x0) + y0
+        return col, b_old
+
+    rob, _ = column(np.ones(len(t), dtype=bool), Rb)
+    for j in range(N):
+        seen = ~np.isnan(H[:, j]).any(axis=1)
+        if not seen[-1]:                                 # absent now: first_frame -1, the column stays NaN
+            continue
+        hum[:, j], b_old = column(seen, H[:, j])
+        first[j + 1] = F - 1 - min(b_old, n_grid - 1)
+    return hum, rob, pose_now, first, n_grid
+
+
+def frame_table_tracks(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
+                       num_hist_frames: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
+    """The frame table PER TRACK from raw frames - stamps [R], human_xy [R, N, 2], robot_xy [R, 2], oldest-pushed first - and the host
+    twin of the device ``track_frames_kernel`` (csrc/frames.hpp), in its operation order.  A NaN coordinate of pedestrian j means "track
+    j was not seen in this frame" and drops nothing:
+
+      1. ``pose_now`` = the human positions of the last pushed frame, before anything is dropped or sorted (NaN where not seen)
+      2. a frame is dropped iff its stamp or a robot coordinate is NaN
+      3. the kept frames in stable sort order by stamp share one grid: ns = trunc(stamp * 100), w = round(time_step * 100), bin
+         b = (ns_last - ns) // w counted back from the newest kept frame (the ANCHOR), nb = max(b) + 1, n_grid = min(F, nb); the robot's
+         column is ``frame_table_frames``'s
+      4. pedestrian j's frames are the kept ones where both its coordinates are non-NaN; a bin holds the last sorted of them, an empty
+         bin between filled ones is interpolated between the nearest filled older and newer bin of THAT track in index space
+         x = nb-1-b (``slope = (y1 - y0) / (x1 - x0); y = slope * (x - x0) + y0``), nothing is extrapolated in front of its oldest filled
+         bin b_old(j), which may lie beyond the window
+
+    Returns (human_xy [F, N, 2], robot_xy [F, 2], pose_now [N, 2], first_frame [N + 1] int32, n_grid) with F = ``num_hist_frames``:
+    right-aligned, NaN in front, the newest frame in row F-1 (the layout of ``pad_short_window``); ``first_frame`` (robot first) is
+    F - n_grid for the robot, F-1 - min(b_old(j), n_grid-1) for pedestrian j and -1 for a pedestrian not seen in the anchor frame (absent
+    now: its column is NaN; leave it out of the scene).  Without human NaN the rows F-n_grid .. F-1 are the bytes of
+    ``frame_table_frames``.  Raises ``HistoryTooShortError`` (``.n_grid`` attached) when n_grid < 2."""
+    out = _track_table(stamps, human_xy, robot_xy, time_step, int(num_hist_frames))
+    if out[4] < 2:
+        err = HistoryTooShortError(f"{out[4]} history frames on the time_step grid, at least 2 needed")
+        err.n_grid = out[4]
+        raise err
+    return out
+
+
+def frame_table_tracks_batched(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, n_frames: Optional[np.ndarray],
+                               time_step: float, num_hist_frames: int) -> Dict[str, np.ndarray]:
+    """``frame_table_tracks`` for E episodes: stamps [E, R], human_xy [E, R, N, 2], robot_xy [E, R, 2]; the first ``n_frames[e]`` (1..R;
+    None: all R) raw frames of episode e are valid.  Returns ``human_xy`` [E, F, N, 2], ``robot_xy`` [E, F, 2], ``pose_now`` [E, N, 2]
+    float64, ``first_frame`` [E, N + 1] and ``n_grid`` [E] int32 - what ``jmid_build_scene_stamped_var`` leaves.  Nothing is raised for
+    an episode: ``n_grid[e]`` < 2 is the too-short one, ``first_frame[e, 1 + j]`` = -1 the pedestrian who is absent now."""
+    stamps = np.asarray(stamps, dtype=np.float64)
+    human_xy = np.asarray(human_xy, dtype=np.float64)
+    robot_xy = np.asarray(robot_xy, dtype=np.float64)
+    E, R, N, _ = human_xy.shape
+    F = int(num_hist_frames)
+    n_frames = np.full(E, R, dtype=np.int64) if n_frames is None else np.asarray(n_frames)
+    if n_frames.shape != (E,) or (n_frames < 1).any() or (n_frames > R).any():
+        raise ValueError("n_frames must hold E values in 1..R")
+    out = {"human_xy": np.empty((E, F, N, 2)), "robot_xy": np.empty((E, F, 2)), "pose_now": np.empty((E, N, 2)),
+           "first_frame": np.empty((E, N + 1), dtype=np.int32), "n_grid": np.empty(E, dtype=np.int32)}
+    for e in range(E):
+        n = int(n_frames[e])
+        parts = _track_table(stamps[e, :n], human_xy[e, :n], robot_xy[e, :n], time_step, F)
+        for key, v in zip(("human_xy", "robot_xy", "pose_now", "first_frame", "n_grid"), parts):
+            out[key][e] = v
+    return out
+
+
+def histories_as_frames(prev_states, prev_robot_states, joined: bool = True):
     """The per-human lists of ``update_state_hists`` as raw frames (stamps [R], human_xy [R, N, 2], robot_xy [R, 2]) when they ARE frames:
     every human's list has the same stamps, entry by entry, as the robot's last R entries, and a stamp that occurs twice comes with
     NaN-free data (``frame_table`` joins on stamp VALUES, so a duplicated stamp next to a dropped frame is not a frame-wise table).
-    None otherwise (somebody edited the lists by hand): ``frame_table`` handles those."""
+    None otherwise (somebody edited the lists by hand): ``frame_table`` handles those.  ``joined=False``: for ``frame_table_tracks``,
+    which never joins on stamp values - the last condition does not apply."""
     R = len(prev_states[0]) if len(prev_states) else 0
     if R == 0 or len(prev_robot_states) < R or any(len(h) != R for h in prev_states):
         return None
@@ -192,7 +306,7 @@ def histories_as_frames(prev_states, prev_robot_states):
     stamps = rob[:, 2]
     if not (hum[:, :, 2] == stamps[None]).all():                            # (a NaN stamp fails this too)
         return None
-    if len(np.unique(stamps)) != R and (np.isnan(hum).any() or np.isnan(rob).any()):
+    if joined and len(np.unique(stamps)) != R and (np.isnan(hum).any() or np.isnan(rob).any()):
         return None
     # (the robot's list is unbounded, but frame_table's join takes the LAST entry with a stamp: always one of these R)
     return stamps.copy(), np.ascontiguousarray(hum[:, :, 0:2].transpose(1, 0, 2)), np.ascontiguousarray(rob[:, 0:2])

@@ -1,11 +1,15 @@
 """Latency of HumanTrajectoryForecasterSim(short_history=True).predict_ret_best() with L = 2 .. 5 shared history frames against the full
 window (L = 6), in ONE process on one engine: what an MPC step pays during the first control steps of an episode.  Run on the GPU box.
 
-    short_history_latency.py [--device-scene] [--reps R] [--warmup W] [cfg2 | shipped]
+    short_history_latency.py [--device-scene | --routes] [--reps R] [--warmup W] [cfg2 | shipped]
 
 Per L a fresh forecaster is fed L frames (the engine is shared: forecaster.py caches it), called W times unmeasured and R times measured;
 printed are the median and the 10th / 90th percentile of the wall time of a call and the medians of its parts.  L < 6 on the host scene
-takes the staged path (encode(first_index) -> denoise -> topk: three library entries), L = 6 and --device-scene the one-entry chain."""
+takes the staged path (encode(first_index) -> denoise -> topk: three library entries), L = 6 and --device-scene the one-entry chain.
+--routes: per L, three forecasters side by side, their measured calls ALTERNATING (drift and the neighbours on the box hit them alike):
+  host    short_history=True                                        the host frame table and scene, staged below L = 6
+  frames  short_history=True, device_frames=True                    the host frame table, then engine.build_scene(first_frame=) + chain
+  tracks  short_history=True, device_frames=True, track_presence=True   raw frames in: jmid_build_scene_stamped_var + ONE chain"""
 import os, sys, tempfile, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,8 +47,37 @@ def run(tag, N, K, k_ret, H, step, reps=30, warmup=3, device_scene=False):
               f"p10 {np.percentile(ts, 10):.4f} p90 {np.percentile(ts, 90):.4f}  " + "  ".join(f"{k} {x:.4f}" for k, x in med.items()), flush=True)
 
 
+ROUTES = {"host": dict(), "frames": dict(device_frames=True), "tracks": dict(device_frames=True, track_presence=True)}
+
+
+def run_routes(tag, N, K, k_ret, H, step, reps=30, warmup=3):
+    d = tempfile.mkdtemp()
+    env, ypath = F.write_configs(d, joint=True, ctx_dim=256, N=N, K=K, k_ret=k_ret, H=H, step=step)
+    w = JMIDWeights.from_seed(NetDims(ctx_dim=256), 0)
+    rng = np.random.default_rng(0)
+    p = rng.uniform(-1.0, 1.0, (N, 2)); v = rng.uniform(-0.5, 0.5, (N, 2))
+    for L in (6, 5, 4, 3, 2, 6):
+        fs = {name: F.HumanTrajectoryForecasterSim(env, ypath, weights=w, precision=PREC, short_history=True, **kw) for name, kw in ROUTES.items()}
+        for f in fs.values():
+            for i in range(L):
+                f.update_state_hists(State((0.0, -2.0 + 0.2 * i)), [State(p[j] + v[j] * 0.25 * i) for j in range(N)], 0.25 * i)
+            for _ in range(max(warmup, 1)):
+                f.predict_ret_best()
+        ts = {name: [] for name in fs}
+        for _ in range(reps):
+            for name, f in fs.items():
+                t0 = time.perf_counter(); f.predict_ret_best(); ts[name].append(time.perf_counter() - t0)
+        for name in fs:
+            t = np.array(ts[name]) * 1e3
+            print(f"RESULT {tag} route={name} [{PREC}] L={L} reps={reps} warmup={warmup}: total_ms median {np.median(t):.4f} "
+                  f"p10 {np.percentile(t, 10):.4f} p90 {np.percentile(t, 90):.4f}", flush=True)
+
+
 if __name__ == "__main__":
     opts = {}
+    if "--routes" in sys.argv:
+        sys.argv.remove("--routes")
+        run = run_routes
     if "--device-scene" in sys.argv:
         sys.argv.remove("--device-scene")
         opts["device_scene"] = True
