@@ -683,6 +683,37 @@ int jmid_dbg_plan_chunks_mode(int net_kind, int nhead, int lanes, int chunk_epis
  * group, the shape's tile rows and columns, and the row tile of the first- / second-generation GEMM + LayerNorm kernel for M rows. */
 #define JMID_DBG_GEMM_PLAN_KNOBS 13
 int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int small_now, int one_chunk, const int* knobs, int* plan);
+/* The layouts of a chained call's I/O block and of the scene workspace (csrc/jmid_abi.hip::chain_io, scene_arrays; host logic only, no
+ * device): where every array of jmid_predict* / jmid_predict_scene* / jmid_forecast_scene* lies for a handle of this hist_len and ctx_dim, a
+ * call of E, A, K, T, k and a resident scene of N pedestrians.  flags: JMID_DBG_LAYOUT_SCENE the scene entries (clear: host arrays),
+ * _FORECAST jmid_forecast_scene*, _SEEDED the seeded entries, _PADDED the padded ones, _FIRST_INDEX a scene built with first_frame, _BW a
+ * bw is given, _POS pos_out is given, _CV the scene was built with cv_out (at horizon T).  JMID_EINVAL for a call no entry makes: forecast,
+ * seeded or first_index without scene; a forecast without cv or with pos_out; k == K without pos_out (outside a forecast).
+ * Every array is a pair (byte offset from the block's base, bytes); an array the call does not have is (-1, 0).
+ * chain_dev, chain_pin [JMID_DBG_CHAIN_WORDS]: the device block and the pinned block - 14 arrays, then the upload block's (offset, bytes),
+ * the download block's (offset, bytes) and the block's size.  With Th = hist_len and fp32 unless said:
+ *    0 x_st [E A, Th, 6]   1 nbr_sum [E A, 2, Th, 6]   2 edge_mask [E A, 2]   3 x_T [E, K A, T, 2]   4 p0 [E, A, 2]   5 bw [T] (k < K and _BW)
+ *    6 ctx [E A, ctx_dim] (device only)   7 the range flag, one int32   8 forecasts [E, N, k, T+1, 2] fp64   9 their logw [E, N, k] fp64 (8, 9: _FORECAST)
+ *   10 sel [E, A, k, T, 2]   11 logw [E, A, k] (10, 11: k < K)   12 pos [E, K, A, T, 2] (_POS)   13 first_index [E A] int32 (_FIRST_INDEX, device only)
+ * The upload block is arrays 0-5 (a scene call's copy starts at x_T), the download block 7-12, ending behind 9 in a forecast - whose pinned
+ * block has no 10-12.
+ * scene [JMID_DBG_SCENE_WORDS]: 13 arrays, then the grid block's bytes, the download block's (offset, bytes) and the workspace's size:
+ *    0 human_xy [E, Th, N, 2] fp64   1 robot_xy [E, Th, 2] fp64   2 pose_now [E, N, 2] fp64 (0-2: the grid block, the workspace's first bytes)
+ *    3 x [E, N, Th, 6]   4 x_st [E, N, Th, 6]   5 nbr_sum [E, N, 2, Th, 6]   6 edge_mask [E, N, 2]   7 p0 [E, N, 2]
+ *    8 n_in [E] int32   9 in_cluster [E, N] bytes   10 robot_in [E] bytes   11 cv [E, N, T, 2] fp64 (_CV)   (8-11: the download block)
+ *   12 first_index [E, N] int32 (_FIRST_INDEX) */
+#define JMID_DBG_LAYOUT_SCENE 1
+#define JMID_DBG_LAYOUT_FORECAST 2
+#define JMID_DBG_LAYOUT_SEEDED 4
+#define JMID_DBG_LAYOUT_PADDED 8
+#define JMID_DBG_LAYOUT_FIRST_INDEX 16
+#define JMID_DBG_LAYOUT_BW 32
+#define JMID_DBG_LAYOUT_POS 64
+#define JMID_DBG_LAYOUT_CV 128
+#define JMID_DBG_CHAIN_WORDS (2 * 14 + 5)
+#define JMID_DBG_SCENE_WORDS (2 * 13 + 4)
+int jmid_dbg_chain_layout(int hist_len, int ctx_dim, int E, int A, int K, int T, int k, int N, int flags, int64_t* chain_dev, int64_t* chain_pin,
+                          int64_t* scene);
 /* Layer 0's Q, K, V of one denoise step of a JMID net in a split-fp16 mode, as the step's kernels leave them for the attention
  * kernel: x [M, 2] (M = E K A T tokens) is embedded at step-table entry `step` with the hyper rows hyp [E A, hyper width] (the ctx
  * part of the hyper nets: gate1 | bias1 | ... as the handle lays them out), layer 0's operand planes are made - expanded from the

@@ -122,6 +122,7 @@ DIAG_SIGNATURES = {
     "jmid_dbg_plan_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "jmid_dbg_plan_chunks_mode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "jmid_dbg_gemm_plan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "jmid_dbg_chain_layout": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int64)] * 3),
     "jmid_dbg_qkv0": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "jmid_dbg_tail": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "jmid_dbg_layer": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -177,18 +177,9 @@ inline hipError_t launch_frames(const FramesArgs& g, hipStream_t st) {
     return hipGetLastError();
 }
 
-struct TrackFramesArgs {
-    const double* stamps;         // [E, R]
-    const double* human_xy;       // [E, R, N, 2]
-    const double* robot_xy;       // [E, R, 2]
-    const int* n_frames;          // [E] or null, as FramesArgs
-    double* o_human;              // [E, F, N, 2]   right-aligned: NaN in front, the newest frame in row F-1
-    double* o_robot;              // [E, F, 2]
-    double* o_pose;               // [E, N, 2]
-    int* o_n_grid;                // [E]   (-1: n_frames[e] outside 1..R, nothing else written for that episode)
+// FramesArgs (o_human right-aligned: NaN in front, the newest frame in row F-1) and
+struct TrackFramesArgs : FramesArgs {
     int* o_first;                 // [E, N + 1]   robot first; -1: a pedestrian not seen in the anchor frame
-    long long w;                  // round(time_step * 100) >= 1
-    int E, N, R, F;
 };
 
 // the shared bins of step 3 and the seen sets of step 4 (column group N = the robot: the kept frames)

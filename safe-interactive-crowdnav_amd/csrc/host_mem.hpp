@@ -15,6 +15,16 @@ constexpr size_t kAlign = 256;
 inline size_t align_up(size_t bytes) { return (bytes + kAlign - 1) / kAlign * kAlign; }
 inline size_t align_up_floats(size_t floats) { return align_up(floats * sizeof(float)) / sizeof(float); }      // (a block addressed in floats)
 
+// One array of a laid-out block: where it lies and how many elements it has, stated once by the layout function - the launches take
+// the pointer, the copies the bytes.  n = 0: the call has no such array, and it reads as a null pointer
+template <class T>
+struct Arr {
+    T* p = nullptr;
+    size_t n = 0;
+    size_t bytes() const { return n * sizeof(T); }
+    operator T*() const { return n ? p : nullptr; }
+};
+
 // Lays arrays out one behind the other.  base null: the size only (`off` after the same takes)
 struct Carver {
     char* base;
@@ -25,6 +35,10 @@ struct Carver {
         T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
         off += align_up(n * sizeof(T));
         return p;
+    }
+    template <class T = float>
+    Arr<T> arr(size_t n) {
+        return Arr<T>{take<T>(n), n};
     }
 };
 

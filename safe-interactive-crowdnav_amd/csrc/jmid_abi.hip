@@ -64,134 +64,178 @@ EncArgs encoder_args(const jmid_ctx* h, const float* x_st, const float* nbr_sum,
     return ea;
 }
 
-// jmid_predict and jmid_predict_scene after their argument checks: one upload, encoder -> denoise loop -> integrator -> top-k chained on
-// the stream, one download.  scene = false: the five inputs are host arrays.  scene = true: x_st, nbr_sum, edge_mask and p0 are null and
-// the in-cluster rows of the resident scene are gathered on the device instead (x_T and bw are the whole upload).
-// fc_out (scene mode only; jmid_forecast_scene): assemble_kernel follows on the stream and the download is forecasts [E, N, k, T+1, 2] and
-// logw [E, N, k] doubles instead of sel / logw / pos, which then never leave the device.
-// seeded (scene mode only; the *_seeded entries): x_T is null and its slot of the device block is filled there, draw 0 of noise.hpp.
-int predict_chain(jmid_ctx* h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask, const float* x_T,
-                  const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out, bool scene, const char* who,
-                  double* fc_out = nullptr, double* lwd_out = nullptr, const SeedArgs* seeded = nullptr, const int32_t* n_agents = nullptr) {
-    // n_agents (jmid_predict_padded; host arrays only): the padded agents' rows go through the encoder as the caller left them - its rows are
-    // independent - and the denoise stage zeroes their ctx, x_T and p0
-    // scene mode with n_agents (the *_scene_padded entries): n_agents is the host copy of the resident scene's counts; the stages read the
-    // device counts the build kernel wrote (nothing is uploaded for them), the gather zeroes the padded rows and a seeded x_T is the padded fill
-    const int* nag_dev = scene && n_agents ? reinterpret_cast<const int*>(h->scene.dev.p + h->scene.o_nin) : nullptr;
-    const bool rank = k < K;
-    const size_t Th = h->hist_len, n = (size_t)E * A, H2 = 2 * (size_t)h->H;
-    const size_t n_xs = n * Th * 6, n_nb = n * 2 * Th * 6, n_em = n * 2, n_xT = (size_t)E * K * A * T * 2, n_p0 = n * 2, n_bw = rank && bw ? T : 0;
-    const size_t n_sel = rank ? n * k * T * 2 : 0, n_lw = rank ? n * k : 0, n_pos = pos_out ? n_xT : 0;
-    // the assembled arrays are doubles: two float slots each (every offset is a multiple of 256 bytes)
-    const size_t Np = fc_out ? (size_t)h->scene.N : 0, n_fc = 2 * ((size_t)E * Np * k * (T + 1) * 2), n_lwd = 2 * ((size_t)E * Np * k);
-    // upload block | ctx | download block (flag, forecasts, their logw, sel, logw, pos; with fc_out the download ends behind the first three)
-    const size_t o_xs = 0, o_nb = o_xs + align_up_floats(n_xs), o_em = o_nb + align_up_floats(n_nb), o_xT = o_em + align_up_floats(n_em), o_p0 = o_xT + align_up_floats(n_xT), o_bw = o_p0 + align_up_floats(n_p0),
-                 in_floats = o_bw + align_up_floats(n_bw), o_ctx = in_floats, o_out = o_ctx + align_up_floats(n * H2), o_flag = o_out, o_fc = o_flag + align_up_floats(1), o_lwd = o_fc + align_up_floats(n_fc),
-                 o_sel = o_lwd + align_up_floats(n_lwd), o_lw = o_sel + align_up_floats(n_sel), o_pos = o_lw + align_up_floats(n_lw), total = o_pos + align_up_floats(n_pos),
-                 out_floats = (fc_out ? o_sel : total) - o_out;
-    // a scene with first_index: its dense [E * A] copy behind everything else (no other offset moves)
-    const bool var = scene && h->scene.has_first;
-    const size_t o_fi = total;
-    if (int rc = h->io_dev.reserve(h, (total + (var ? align_up_floats(n) : 0)) * 4, who)) return rc;
-    if (int rc = h->pin.reserve(h, (in_floats + out_floats) * 4, who)) return rc;
-    float* pin = h->pin.as<float>();
-    float* dev = h->io_dev.as<float>();
-    if (!seeded) std::memcpy(pin + o_xT, x_T, n_xT * 4);
-    if (n_bw) std::memcpy(pin + o_bw, bw, n_bw * 4);
-    if (!scene) {
-        std::memcpy(pin + o_xs, x_st, n_xs * 4);
-        std::memcpy(pin + o_nb, nbr_sum, n_nb * 4);
-        std::memcpy(pin + o_em, edge_mask, n_em * 4);
-        std::memcpy(pin + o_p0, p0, n_p0 * 4);
-        HIPCHK(h, hipMemcpyAsync(dev, pin, in_floats * 4, hipMemcpyHostToDevice, h->stream));
-    } else {
-        // x_T ... bw in one copy (the p0 slot between them is written by the gather below, after the copy on the stream)
-        if (!seeded) HIPCHK(h, hipMemcpyAsync(dev + o_xT, pin + o_xT, (in_floats - o_xT) * 4, hipMemcpyHostToDevice, h->stream));
-        else if (n_bw) HIPCHK(h, hipMemcpyAsync(dev + o_bw, pin + o_bw, n_bw * 4, hipMemcpyHostToDevice, h->stream));
+// The I/O block of a chained call, laid out here only: the upload block (x_st, nbr_sum, edge_mask, x_T, p0, bw: contiguous, one copy; in
+// scene mode the copy starts at x_T and the gather overwrites the p0 slot after it, on the stream) | ctx | the download block (flag,
+// forecasts, their logw, sel, logw, pos: contiguous, one copy, ending behind the assembled arrays of a forecast) | the dense [E * A] copy of
+// a resident scene's first_index.  pinned: the handle's pinned block instead - upload + download and nothing else, with the same inner
+// offsets.  base null: the size only
+size_t chain_io(const jmid_ctx* h, const ChainCall& c, char* base, ChainIo* out, bool pinned) {
+    const size_t n = (size_t)c.E * c.A, Th = h->hist_len, n_xT = (size_t)c.E * c.K * c.A * c.T * 2, Np = c.forecast ? h->scene.N : 0;
+    Carver cv(base);
+    ChainIo io{};
+    io.x_st = cv.arr(n * Th * 6); io.nbr_sum = cv.arr(n * 2 * Th * 6); io.edge_mask = cv.arr(n * 2);
+    io.x_T = cv.arr(n_xT); io.p0 = cv.arr(n * 2); io.bw = cv.arr(c.rank() && c.bw ? c.T : 0);
+    io.up_bytes = cv.off;
+    if (!pinned) io.ctx = cv.arr(n * 2 * h->H);
+    const size_t down = cv.off;
+    io.flag = cv.arr<int>(1); io.forecasts = cv.arr<double>((size_t)c.E * Np * c.k * (c.T + 1) * 2); io.logw_d = cv.arr<double>((size_t)c.E * Np * c.k);
+    if (c.forecast) io.down_bytes = cv.off - down;
+    if (!c.forecast || !pinned) io.sel = cv.arr(c.rank() ? n * c.k * c.T * 2 : 0), io.logw = cv.arr(c.rank() ? n * c.k : 0), io.pos = cv.arr(c.pos_out ? n_xT : 0);
+    if (!c.forecast) io.down_bytes = cv.off - down;
+    if (!pinned && c.scene && h->scene.has_first()) io.first_index = cv.arr<int>(n);
+    if (out) *out = io;
+    return cv.off;
+}
+
+// What the phases of one chained call share: its device and pinned blocks as chain_io laid them out, and the device counts of a padded
+// scene chain (the n_in the build kernel wrote), null otherwise
+struct ChainRun {
+    ChainIo dev, pin;
+    const int* nag_dev = nullptr;
+};
+
+int reserve_chain_io(jmid_ctx* h, const ChainCall& c, Block& b, bool pinned, ChainIo* io) {
+    if (int rc = b.reserve(h, chain_io(h, c, nullptr, nullptr, pinned), c.who)) return rc;
+    chain_io(h, c, b.p, io, pinned);
+    return 0;
+}
+
+// phase 1: the host inputs through the pinned block in one copy; a seeded x_T is filled in its slot on the device
+int stage_inputs(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
+    const ChainIo &dev = r.dev, &pin = r.pin;
+    if (!c.seeded) std::memcpy(pin.x_T.p, c.x_T, pin.x_T.bytes());
+    if (pin.bw.n) std::memcpy(pin.bw.p, c.bw, pin.bw.bytes());
+    if (!c.scene) {
+        std::memcpy(pin.x_st.p, c.x_st, pin.x_st.bytes()); std::memcpy(pin.nbr_sum.p, c.nbr_sum, pin.nbr_sum.bytes());
+        std::memcpy(pin.edge_mask.p, c.edge_mask, pin.edge_mask.bytes()); std::memcpy(pin.p0.p, c.p0, pin.p0.bytes());
+        HIPCHK(h, hipMemcpyAsync(dev.x_st.p, pin.x_st.p, dev.up_bytes, hipMemcpyHostToDevice, h->stream));
+    } else if (!c.seeded) {
+        // x_T ... bw in one copy (the p0 slot between them is written by the gather, after the copy on the stream)
+        HIPCHK(h, hipMemcpyAsync(dev.x_T.p, pin.x_T.p, dev.up_bytes_from(dev.x_T), hipMemcpyHostToDevice, h->stream));
+    } else if (dev.bw.n) {
+        HIPCHK(h, hipMemcpyAsync(dev.bw.p, pin.bw.p, dev.bw.bytes(), hipMemcpyHostToDevice, h->stream));
     }
-    if (seeded) {
-        if (int rc = h->noise_ids.upload(h, seeded->ids, E, who)) return rc;
-        if (nag_dev) {
-            if (int rc = fill_noise_padded(h, seeded->seed, h->noise_ids.get<unsigned>(), nag_dev, E, A, K, T, 0, dev + o_xT, h->stream)) return rc;
-        } else if (int rc = fill_noise(h, seeded->seed, h->noise_ids.get<unsigned>(), E, (size_t)K * A * T * 2, 0, dev + o_xT, nullptr, h->stream)) return rc;
+    if (c.seeded) {
+        if (int rc = h->noise_ids.upload(h, c.seeded->ids, c.E, c.who)) return rc;
+        if (r.nag_dev) return fill_noise_padded(h, c.seeded->seed, h->noise_ids.get<unsigned>(), r.nag_dev, c.E, c.A, c.K, c.T, 0, dev.x_T, h->stream);
+        return fill_noise(h, c.seeded->seed, h->noise_ids.get<unsigned>(), c.E, (size_t)c.K * c.A * c.T * 2, 0, dev.x_T, nullptr, h->stream);
     }
-    int rc = 0;
-    {
-        ProfScope ps(h, KC_ENCODER, h->stream);
-        if (scene) {
-            const jmid_ctx::SceneWs& sc = h->scene;
-            SceneGatherArgs ga{};
-            ga.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev.p + sc.o_inc);
-            ga.x_st = reinterpret_cast<const float*>(sc.dev.p + sc.o_xst); ga.nbr_sum = reinterpret_cast<const float*>(sc.dev.p + sc.o_nbr);
-            ga.edge_mask = reinterpret_cast<const float*>(sc.dev.p + sc.o_em); ga.p0 = reinterpret_cast<const float*>(sc.dev.p + sc.o_p0);
-            ga.o_x_st = dev + o_xs; ga.o_nbr_sum = dev + o_nb; ga.o_edge_mask = dev + o_em; ga.o_p0 = dev + o_p0;
-            ga.E = E; ga.N = sc.N; ga.A = A; ga.F = (int)Th; ga.pad = nag_dev ? 1 : 0;
-            if (var) {
-                ga.first_index = reinterpret_cast<const int*>(sc.dev.p + sc.o_first);
-                ga.o_first_index = reinterpret_cast<int*>(dev + o_fi);
-            }
-            if (launch_scene_gather(ga, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": scene gather launch failed");
-        }
-        EncArgs ea = encoder_args(h, dev + o_xs, dev + o_nb, dev + o_em, dev + o_ctx, (int)n);
-        if (var) ea.first_index = reinterpret_cast<const int*>(dev + o_fi);
-        if (!rc && launch_encoder(ea, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": encoder launch failed");
+    return 0;
+}
+
+// phase 2: (scene: the in-cluster rows of the resident scene into the upload block's slots, then) the encoder -> ctx
+int gather_encode(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
+    const ChainIo& dev = r.dev;
+    ProfScope ps(h, KC_ENCODER, h->stream);
+    if (c.scene) {
+        const SceneArrays& sa = h->scene.arr;
+        SceneGatherArgs ga{};
+        ga.in_cluster = sa.in_cluster;
+        ga.x_st = sa.x_st; ga.nbr_sum = sa.nbr_sum; ga.edge_mask = sa.edge_mask; ga.p0 = sa.p0;
+        ga.o_x_st = dev.x_st; ga.o_nbr_sum = dev.nbr_sum; ga.o_edge_mask = dev.edge_mask; ga.o_p0 = dev.p0;
+        ga.first_index = sa.first_index; ga.o_first_index = dev.first_index;      // (both null for a scene without one)
+        ga.E = c.E; ga.N = h->scene.N; ga.A = c.A; ga.F = h->hist_len; ga.pad = r.nag_dev ? 1 : 0;
+        if (launch_scene_gather(ga, h->stream) != hipSuccess) return fail(h, JMID_EHIP, std::string(c.who) + ": scene gather launch failed");
     }
-    DenoiseCall c{E, A, K, T, precision, JMID_MEM_DEVICE};       // a stage of the chain: no caller-stream ordering, the flag comes with the one download
-    c.x_in = dev + o_xT; c.ctx = dev + o_ctx; c.p0 = dev + o_p0; c.dt = dt; c.pos_out = pos_out ? dev + o_pos : nullptr; c.chained = true;
-    c.n_agents = n_agents; c.n_agents_dev = nag_dev; c.who = who;
-    if (!rc) rc = run_network(h, c);
-    if (!rc && rank)
-        rc = topk_on_device(h, who, E, A, K, T, k, h->last_pos, n_bw ? dev + o_bw : nullptr, dev + o_sel, dev + o_lw, nag_dev ? nag_dev : n_agents ? h->nag.get<int>() : nullptr);
-    if (!rc && fc_out) {
-        const jmid_ctx::SceneWs& sc = h->scene;
-        AssembleArgs aa{};
-        aa.in_cluster = reinterpret_cast<const unsigned char*>(sc.dev.p + sc.o_inc);
-        aa.src = rank ? dev + o_sel : h->last_pos;
-        aa.logw_in = rank ? dev + o_lw : nullptr;
-        aa.cv = reinterpret_cast<const double*>(sc.dev.p + sc.o_cv);
-        // pose_now: its own slot after a stamped build, the last frame of the grid otherwise (what predict_batch prepends)
-        aa.pose = sc.stamped ? reinterpret_cast<const double*>(sc.dev.p + sc.o_pose)
-                             : reinterpret_cast<const double*>(sc.dev.p + sc.o_hum) + (Th - 1) * (size_t)sc.N * 2;
-        aa.pose_stride = sc.stamped ? (size_t)sc.N * 2 : Th * (size_t)sc.N * 2;
-        aa.forecasts = reinterpret_cast<double*>(dev + o_fc);
-        aa.logw = reinterpret_cast<double*>(dev + o_lwd);
-        aa.logw_full = std::log(1.0 / (double)K);
-        aa.E = E; aa.N = sc.N; aa.A = A; aa.k = k; aa.T = T; aa.full = rank ? 0 : 1;
-        if (launch_assemble(aa, h->stream) != hipSuccess) rc = fail(h, JMID_EHIP, std::string(who) + ": assemble launch failed");
-    }
-    if (rc) return rc;
-    const bool flagged = precision != JMID_PREC_F32;
-    if (flagged) HIPCHK(h, hipMemcpyAsync(dev + o_flag, h->range_flag, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-    float* pout = pin + in_floats;
-    HIPCHK(h, hipMemcpyAsync(pout, dev + o_out, out_floats * 4, hipMemcpyDeviceToHost, h->stream));
+    EncArgs ea = encoder_args(h, dev.x_st, dev.nbr_sum, dev.edge_mask, dev.ctx, c.E * c.A);
+    ea.first_index = dev.first_index;
+    if (launch_encoder(ea, h->stream) != hipSuccess) return fail(h, JMID_EHIP, std::string(c.who) + ": encoder launch failed");
+    return 0;
+}
+
+// phase 3: the denoise loop and the integrator as a stage of the chain - no caller-stream ordering, the flag comes with the one download
+int denoise_stage(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
+    DenoiseCall d{c.E, c.A, c.K, c.T, c.precision, JMID_MEM_DEVICE};
+    d.x_in = r.dev.x_T; d.ctx = r.dev.ctx; d.p0 = r.dev.p0; d.dt = c.dt; d.pos_out = r.dev.pos; d.chained = true;
+    d.n_agents = c.n_agents; d.n_agents_dev = r.nag_dev; d.who = c.who;
+    return run_network(h, d);
+}
+
+// phase 4 (k < K): the KDE ranks the positions the denoise stage left in the workspace -> sel, logw
+int rank_samples(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
+    const int* nag = r.nag_dev ? r.nag_dev : c.padded ? h->nag.get<int>() : nullptr;      // (host arrays: the denoise stage's upload)
+    return topk_on_device(h, c.who, c.E, c.A, c.K, c.T, c.k, h->last_pos, r.dev.bw, r.dev.sel, r.dev.logw, nag);
+}
+
+// phase 5 (forecast): assemble_kernel -> forecasts [E, N, k, T+1, 2] and logw [E, N, k] doubles over every pedestrian of the scene
+int assemble_forecasts(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
+    const jmid_ctx::SceneWs& sc = h->scene;
+    const size_t Th = h->hist_len;
+    AssembleArgs aa{};
+    aa.in_cluster = sc.arr.in_cluster;
+    aa.src = c.rank() ? r.dev.sel.p : h->last_pos;
+    aa.logw_in = r.dev.logw;
+    aa.cv = sc.arr.cv;
+    // pose_now: its own slot after a stamped build, the last frame of the grid otherwise (what predict_batch prepends)
+    aa.pose = sc.stamped ? sc.arr.grid.pose_now.p : sc.arr.grid.human_xy.p + (Th - 1) * (size_t)sc.N * 2;
+    aa.pose_stride = sc.stamped ? (size_t)sc.N * 2 : Th * (size_t)sc.N * 2;
+    aa.forecasts = r.dev.forecasts;
+    aa.logw = r.dev.logw_d;
+    aa.logw_full = std::log(1.0 / (double)c.K);
+    aa.E = c.E; aa.N = sc.N; aa.A = c.A; aa.k = c.k; aa.T = c.T; aa.full = c.rank() ? 0 : 1;
+    if (launch_assemble(aa, h->stream) != hipSuccess) return fail(h, JMID_EHIP, std::string(c.who) + ": assemble launch failed");
+    return 0;
+}
+
+// phase 6: the range flag joins the download block, one copy, the one synchronisation, the caller's arrays
+int finish_chain(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
+    const ChainIo &dev = r.dev, &pin = r.pin;
+    const bool flagged = c.precision != JMID_PREC_F32;
+    if (flagged) HIPCHK(h, hipMemcpyAsync(dev.flag.p, h->range_flag, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(pin.flag.p, dev.flag.p, dev.down_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (flagged && *reinterpret_cast<const int*>(pout + (o_flag - o_out)))
-        return jmid_host::flagged_call(h, *reinterpret_cast<const int*>(pout + (o_flag - o_out)));
-    if (fc_out) {
-        std::memcpy(fc_out, pout + (o_fc - o_out), n_fc * 4);
-        std::memcpy(lwd_out, pout + (o_lwd - o_out), n_lwd * 4);
+    if (flagged && *pin.flag.p) return jmid_host::flagged_call(h, *pin.flag.p);
+    if (c.forecast) {
+        std::memcpy(c.forecasts_out, pin.forecasts.p, pin.forecasts.bytes());
+        std::memcpy(c.logw_out, pin.logw_d.p, pin.logw_d.bytes());
         return JMID_OK;
     }
-    if (rank) {
-        std::memcpy(sel, pout + (o_sel - o_out), n_sel * 4);
-        std::memcpy(logw, pout + (o_lw - o_out), n_lw * 4);
+    if (c.rank()) {
+        std::memcpy(c.sel, pin.sel.p, pin.sel.bytes());
+        std::memcpy(c.logw, pin.logw.p, pin.logw.bytes());
     }
-    if (pos_out) std::memcpy(pos_out, pout + (o_pos - o_out), n_pos * 4);
+    if (c.pos_out) std::memcpy(c.pos_out, pin.pos.p, pin.pos.bytes());
     return JMID_OK;
 }
 
-// where the grid of a scene lies in a workspace: human_xy [E, F, N, 2] | robot_xy [E, F, 2] | pose_now [E, N, 2] doubles, each padded to
-// 256 bytes - the same block in the scene workspace and in the one frames_kernel writes, so that one copy moves it
-struct GridBlock {
-    size_t o_hum, o_rob, o_pose, end;
-};
-GridBlock grid_block(int E, int N, int F) {
+// A chained call after its entry's argument checks (every refusal has come by then: nothing is enqueued for a call that is refused)
+int predict_chain(jmid_ctx* h, const ChainCall& c) {
+    ChainRun r;
+    if (c.scene && c.padded) r.nag_dev = h->scene.arr.n_in;
+    if (int rc = reserve_chain_io(h, c, h->io_dev, false, &r.dev)) return rc;
+    if (int rc = reserve_chain_io(h, c, h->pin, true, &r.pin)) return rc;
+    int rc = stage_inputs(h, c, r);
+    if (!rc) rc = gather_encode(h, c, r);
+    if (!rc) rc = denoise_stage(h, c, r);
+    if (!rc && c.rank()) rc = rank_samples(h, c, r);
+    if (!rc && c.forecast) rc = assemble_forecasts(h, c, r);
+    return rc ? rc : finish_chain(h, c, r);
+}
+
+// where the grid of a scene lies in a workspace: human_xy [E, F, N, 2] | robot_xy [E, F, 2] | pose_now [E, N, 2] doubles.  base null: the size only
+size_t grid_block(int E, int N, int F, char* base, GridBlock* out) {
+    Carver c(base);
     GridBlock gb{};
-    gb.o_hum = 0;
-    gb.o_rob = align_up((size_t)E * F * N * 2 * 8);
-    gb.o_pose = gb.o_rob + align_up((size_t)E * F * 2 * 8);
-    gb.end = gb.o_pose + align_up((size_t)E * N * 2 * 8);
-    return gb;
+    gb.human_xy = c.arr<double>((size_t)E * F * N * 2); gb.robot_xy = c.arr<double>((size_t)E * F * 2);
+    gb.xy_bytes = c.off;
+    gb.pose_now = c.arr<double>((size_t)E * N * 2);
+    if (out) *out = gb;
+    return c.off;
+}
+
+// The scene workspace, laid out here only (horizon 0: no cv), the grid block its prefix.  base null: the size only
+size_t scene_arrays(int E, int N, int F, int horizon, bool has_first, char* base, SceneArrays* out) {
+    const size_t rows = (size_t)E * N;
+    SceneArrays a{};
+    Carver c(base);
+    c.off = grid_block(E, N, F, base, &a.grid);
+    a.x = c.arr(rows * F * 6); a.x_st = c.arr(rows * F * 6); a.nbr_sum = c.arr(rows * 2 * F * 6); a.edge_mask = c.arr(rows * 2); a.p0 = c.arr(rows * 2);
+    const size_t down = c.off;
+    a.n_in = c.arr<int>(E); a.in_cluster = c.arr<unsigned char>(rows); a.robot_in = c.arr<unsigned char>(E); a.cv = c.arr<double>(rows * horizon * 2);
+    a.down_bytes = c.off - down;
+    if (has_first) a.first_index = c.arr<int>(rows);
+    if (out) *out = a;
+    return c.off;
 }
 
 // the refusals jmid_build_scene and jmid_build_scene_stamped share (F is the handle's hist_len by then)
@@ -204,93 +248,82 @@ int check_scene_dims(jmid_ctx* h, const char* who, int N, int F, const double* c
     return 0;
 }
 
-// jmid_build_scene and jmid_build_scene_stamped after their argument checks and order_in: the grid into the scene workspace, scene_kernel, the
-// small outputs to the caller (`mem` says where they live), one synchronisation.  src 0: human_xy / robot_xy are host arrays; 1: device
-// arrays; 2: human_xy is a device GridBlock (grid + pose_now, as frames_kernel left it) and robot_xy is unused.
-// first_frame (jmid_build_scene_var; a HOST array [E, N + 1], checked by the caller, or null): uploaded ahead of the kernel, which then leaves
-// first_index [E, N] behind the download block.
-int build_scene_resident(jmid_ctx* h, const char* who, int E, int N, int F, const double* human_xy, const double* robot_xy, int src, double time_step, int horizon,
-                         int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem,
-                         const int32_t* first_frame = nullptr) {
-    const bool host = mem == JMID_MEM_HOST;
-    const size_t rows = (size_t)E * N, b_hum = rows * F * 2 * 8, b_rob = (size_t)E * F * 2 * 8, b_cv = cv_out ? rows * horizon * 2 * 8 : 0;
-    const GridBlock gb = grid_block(E, N, F);
-    // the grid | the resident arrays | the download block: n_in, in_cluster, robot_in_cluster, cv
-    const size_t o_x = gb.end, o_xst = o_x + align_up(rows * F * 6 * 4),
-                 o_nbr = o_xst + align_up(rows * F * 6 * 4), o_em = o_nbr + align_up(rows * 2 * F * 6 * 4), o_p0 = o_em + align_up(rows * 2 * 4), o_nin = o_p0 + align_up(rows * 2 * 4),
-                 o_inc = o_nin + align_up((size_t)E * 4), o_rin = o_inc + align_up(rows), o_cv = o_rin + align_up((size_t)E), o_first = o_cv + align_up(b_cv), need = o_first + (first_frame ? align_up(rows * 4) : 0), b_out = o_first - o_nin;
+// A scene build after its entry's argument checks and order_in: the grid into the scene workspace, scene_kernel, the small outputs to the
+// caller (`mem` says where they live), one synchronisation
+int build_scene_resident(jmid_ctx* h, const SceneBuild& b) {
+    const bool host = b.mem == JMID_MEM_HOST;
+    const int E = b.E, N = b.N, F = b.F, horizon = b.cv_out ? b.horizon : 0;
     jmid_ctx::SceneWs& sc = h->scene;
     sc.E = 0;                     // no scene is resident until this call has succeeded
-    if (int rc = sc.dev.reserve(h, need, who)) return rc;
-    char* const dev = sc.dev.p;
+    if (int rc = sc.dev.reserve(h, scene_arrays(E, N, F, horizon, b.first_frame != nullptr, nullptr, nullptr), b.who)) return rc;
+    SceneArrays a;
+    scene_arrays(E, N, F, horizon, b.first_frame != nullptr, sc.dev.p, &a);
     SceneArgs g{};
-    g.E = E; g.N = N; g.F = F; g.horizon = horizon; g.force_all = force_all_in_cluster ? 1 : 0;
-    g.dt = time_step;
-    g.human_xy = reinterpret_cast<const double*>(dev + gb.o_hum);
-    g.robot_xy = reinterpret_cast<const double*>(dev + gb.o_rob);
-    g.x = reinterpret_cast<float*>(dev + o_x); g.x_st = reinterpret_cast<float*>(dev + o_xst);
-    g.nbr_sum = reinterpret_cast<float*>(dev + o_nbr); g.edge_mask = reinterpret_cast<float*>(dev + o_em);
-    g.p0 = reinterpret_cast<float*>(dev + o_p0);
-    g.n_in = reinterpret_cast<int*>(dev + o_nin);
-    g.in_cluster = reinterpret_cast<unsigned char*>(dev + o_inc);
-    g.robot_in = reinterpret_cast<unsigned char*>(dev + o_rin);
-    g.cv = cv_out ? reinterpret_cast<double*>(dev + o_cv) : nullptr;
-    if (first_frame) {
-        if (int rc = h->first_idx.upload(h, first_frame, E * (N + 1), who)) return rc;
+    g.E = E; g.N = N; g.F = F; g.horizon = b.horizon; g.force_all = b.force_all_in_cluster ? 1 : 0;
+    g.dt = b.time_step;
+    g.human_xy = a.grid.human_xy; g.robot_xy = a.grid.robot_xy;
+    g.x = a.x; g.x_st = a.x_st; g.nbr_sum = a.nbr_sum; g.edge_mask = a.edge_mask; g.p0 = a.p0;
+    g.n_in = a.n_in; g.in_cluster = a.in_cluster; g.robot_in = a.robot_in; g.cv = a.cv;
+    if (b.first_frame) {
+        if (int rc = h->first_idx.upload(h, b.first_frame, E * (N + 1), b.who)) return rc;
         g.first_frame = h->first_idx.get<int>();
-        g.first_index = reinterpret_cast<int*>(dev + o_first);
+        g.first_index = a.first_index;
     }
-    const size_t pin_in = src == 0 ? gb.o_pose : 0;       // host arrays are staged: human_xy | robot_xy
-    if (int rc = h->pin.reserve(h, pin_in + (host ? b_out : (size_t)E * 4), who)) return rc;
+    // the pinned block: human_xy | robot_xy of a host build, as the grid block has them | the download block (device mode: n_in alone)
+    const size_t pin_in = b.src == SCENE_HOST_ARRAYS ? a.grid.xy_bytes : 0, b_nin = a.n_in.bytes();
+    if (int rc = h->pin.reserve(h, pin_in + (host ? a.down_bytes : b_nin), b.who)) return rc;
     char* const pin = h->pin.p;
-    if (src == 0) {
-        std::memcpy(pin + gb.o_hum, human_xy, b_hum);
-        std::memcpy(pin + gb.o_rob, robot_xy, b_rob);
-        HIPCHK(h, hipMemcpyAsync(dev, pin, pin_in, hipMemcpyHostToDevice, h->stream));
-    } else if (src == 1) {
-        HIPCHK(h, hipMemcpyAsync(dev + gb.o_hum, human_xy, b_hum, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(dev + gb.o_rob, robot_xy, b_rob, hipMemcpyDeviceToDevice, h->stream));
+    if (b.src == SCENE_HOST_ARRAYS) {
+        GridBlock pg;
+        grid_block(E, N, F, pin, &pg);
+        std::memcpy(pg.human_xy.p, b.human_xy, pg.human_xy.bytes()); std::memcpy(pg.robot_xy.p, b.robot_xy, pg.robot_xy.bytes());
+        HIPCHK(h, hipMemcpyAsync(sc.dev.p, pin, pin_in, hipMemcpyHostToDevice, h->stream));
+    } else if (b.src == SCENE_DEVICE_ARRAYS) {
+        HIPCHK(h, hipMemcpyAsync(a.grid.human_xy.p, b.human_xy, a.grid.human_xy.bytes(), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(a.grid.robot_xy.p, b.robot_xy, a.grid.robot_xy.bytes(), hipMemcpyDeviceToDevice, h->stream));
     } else {
-        HIPCHK(h, hipMemcpyAsync(dev, human_xy, gb.end, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sc.dev.p, b.human_xy, grid_block(E, N, F, nullptr, nullptr), hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCHK(h, launch_scene(g, h->stream));
     sc.n_in.resize(E);
-    char* pout = pin + pin_in;
+    char* const pout = pin + pin_in;
     if (host) {
-        HIPCHK(h, hipMemcpyAsync(pout, dev + o_nin, b_out, hipMemcpyDeviceToHost, h->stream));
+        // the download block in one copy: every array sits in the pinned block where it sits behind n_in on the device
+        const auto back = [&](const auto& arr) { return pout + ((const char*)arr.p - (const char*)a.n_in.p); };
+        HIPCHK(h, hipMemcpyAsync(pout, a.n_in.p, a.down_bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
-        std::memcpy(n_in_out, pout, (size_t)E * 4);
-        std::memcpy(in_cluster_out, pout + (o_inc - o_nin), rows);
-        std::memcpy(robot_in_cluster_out, pout + (o_rin - o_nin), (size_t)E);
-        if (cv_out) std::memcpy(cv_out, pout + (o_cv - o_nin), b_cv);
+        std::memcpy(sc.n_in.data(), pout, b_nin);
+        std::memcpy(b.n_in_out, pout, b_nin);
+        std::memcpy(b.in_cluster_out, back(a.in_cluster), a.in_cluster.bytes());
+        std::memcpy(b.robot_in_cluster_out, back(a.robot_in), a.robot_in.bytes());
+        if (b.cv_out) std::memcpy(b.cv_out, back(a.cv), a.cv.bytes());
     } else {
-        HIPCHK(h, hipMemcpyAsync(pout, g.n_in, (size_t)E * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(n_in_out, g.n_in, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(in_cluster_out, g.in_cluster, rows, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(robot_in_cluster_out, g.robot_in, (size_t)E, hipMemcpyDeviceToDevice, h->stream));
-        if (cv_out) HIPCHK(h, hipMemcpyAsync(cv_out, g.cv, b_cv, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pout, a.n_in.p, b_nin, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.n_in_out, a.n_in.p, b_nin, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.in_cluster_out, a.in_cluster.p, a.in_cluster.bytes(), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.robot_in_cluster_out, a.robot_in.p, a.robot_in.bytes(), hipMemcpyDeviceToDevice, h->stream));
+        if (b.cv_out) HIPCHK(h, hipMemcpyAsync(b.cv_out, a.cv.p, a.cv.bytes(), hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::memcpy(sc.n_in.data(), pout, (size_t)E * 4);
+        std::memcpy(sc.n_in.data(), pout, b_nin);
     }
-    sc.o_x = o_x; sc.o_xst = o_xst; sc.o_nbr = o_nbr; sc.o_em = o_em; sc.o_p0 = o_p0; sc.o_inc = o_inc; sc.o_nin = o_nin;
-    sc.o_hum = gb.o_hum; sc.o_rob = gb.o_rob; sc.o_pose = gb.o_pose; sc.o_cv = o_cv;
-    sc.stamped = src == 2;
-    sc.o_first = o_first; sc.has_first = first_frame != nullptr;
-    sc.horizon = cv_out ? horizon : 0;
+    sc.arr = a;
+    sc.stamped = b.src == SCENE_DEVICE_GRID;
+    sc.horizon = horizon;
     sc.E = E; sc.N = N;
     return 0;
 }
 
 // the refusals jmid_predict_scene and jmid_forecast_scene share
-int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K, int T, int k, const void* noise, bool padded) {
+int check_predict_scene(jmid_ctx* h, const ChainCall& c) {
+    const std::string who(c.who);
+    const int E = c.E, A = c.A, K = c.K, T = c.T;
     if (int rc = check_ready(h)) return rc;
-    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, who + ": bad dimensions");
-    if (!noise) return fail(h, JMID_EINVAL, who + ": null input");            // x_T, or the episode ids of a seeded call
+    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || c.k < 1 || c.k > K) return fail(h, JMID_EINVAL, who + ": bad dimensions");
+    if (c.seeded ? !c.seeded->ids : !c.x_T) return fail(h, JMID_EINVAL, who + ": null input");            // x_T, or the episode ids of a seeded call
     const jmid_ctx::SceneWs& sc = h->scene;
     if (!sc.E) return fail(h, JMID_EINVAL, who + " needs a preceding jmid_build_scene on this handle");
     if (E != sc.E) return fail(h, JMID_EINVAL, who + ": E differs from the resident scene's");
-    if (padded) {      // A is the largest count of the scene, and nobody's cluster is empty
+    if (c.padded) {      // A is the largest count of the scene, and nobody's cluster is empty
         int most = 0;
         for (int e = 0; e < E; ++e) {
             if (sc.n_in[e] < 1) return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(e) + " has no in-cluster pedestrian");
@@ -299,38 +332,37 @@ int check_predict_scene(jmid_ctx* h, const std::string& who, int E, int A, int K
         if (most != A)
             return fail(h, JMID_EINVAL, who + ": A = " + std::to_string(A) + " is not the largest in-cluster count of the resident scene, " + std::to_string(most));
     }
-    for (int e = 0; e < E && !padded; ++e)
+    for (int e = 0; e < E && !c.padded; ++e)
         if (sc.n_in[e] != A)
             return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(e) + " has " + std::to_string(sc.n_in[e]) +
                                             " in-cluster pedestrians, not A = " + std::to_string(A) + " (group the episodes by their count)");
-    if (k < K && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, who + ": the device top-k supports A <= 32, K <= 1024, T <= 24");
+    if (c.rank() && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, who + ": the device top-k supports A <= 32, K <= 1024, T <= 24");
     if (h->ddpm) return fail(h, JMID_EINVAL, who + " samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
     return 0;
 }
 
 // jmid_predict_scene / jmid_forecast_scene, their seeded and their padded forms: one chain, the noise either the caller's x_T or (seed, ids);
-// padded: mixed in-cluster counts, A the largest, in the layout of jmid_predict_padded
-int predict_scene_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, int k, const float* x_T, const SeedArgs* seeded, float dt,
-                               int precision, const float* bw, float* sel, float* logw, float* pos_out, double* forecasts_out, double* logw_out,
-                               bool forecast, bool padded = false) {
+// padded: mixed in-cluster counts, A the largest, in the layout of jmid_predict_padded.  The entry states forecast, padded, the noise and
+// the outputs; scene mode and the resident scene's counts are filled in here
+int predict_scene_entry(jmid_handle_t h, ChainCall c) {
     if (!h) return JMID_EINVAL;
-    const std::string w(who);
-    if (int rc = check_predict_scene(h, w, E, A, K, T, k, seeded ? (const void*)seeded->ids : (const void*)x_T, padded)) return rc;
-    if (seeded && !noise_fits((unsigned long long)K * A * T * 2)) return fail(h, JMID_EINVAL, w + ": K * A * T exceeds the noise addressing");
-    if (forecast) {
-        if (!forecasts_out || !logw_out) return fail(h, JMID_EINVAL, w + ": null output");
+    const std::string w(c.who);
+    c.scene = true;
+    if (int rc = check_predict_scene(h, c)) return rc;
+    if (c.seeded && !noise_fits((unsigned long long)c.K * c.A * c.T * 2)) return fail(h, JMID_EINVAL, w + ": K * A * T exceeds the noise addressing");
+    if (c.forecast) {
+        if (!c.forecasts_out || !c.logw_out) return fail(h, JMID_EINVAL, w + ": null output");
         if (!h->scene.horizon) return fail(h, JMID_EINVAL, w + ": the resident scene was built without cv_out (the rows outside the cluster need it)");
-        if (h->scene.horizon != T)
-            return fail(h, JMID_EINVAL, w + ": T = " + std::to_string(T) + " differs from the horizon " + std::to_string(h->scene.horizon) +
+        if (h->scene.horizon != c.T)
+            return fail(h, JMID_EINVAL, w + ": T = " + std::to_string(c.T) + " differs from the horizon " + std::to_string(h->scene.horizon) +
                                             " the resident scene was built with");
     } else {
-        const bool rank = k < K;
-        if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, w + ": k < K needs sel and logw");
-        if (!rank && !pos_out) return fail(h, JMID_EINVAL, w + ": k == K needs pos_out");
+        if (c.rank() && (!c.sel || !c.logw)) return fail(h, JMID_EINVAL, w + ": k < K needs sel and logw");
+        if (!c.rank() && !c.pos_out) return fail(h, JMID_EINVAL, w + ": k == K needs pos_out");
     }
     HIPCHK(h, hipSetDevice(h->device));
-    return predict_chain(h, E, A, K, T, k, nullptr, nullptr, nullptr, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, true, who, forecasts_out, logw_out,
-                         seeded, padded ? h->scene.n_in.data() : nullptr);
+    if (c.padded) c.n_agents = h->scene.n_in.data();
+    return predict_chain(h, c);
 }
 
 // jmid_noise_fill_padded: every episode's own compact draw in the padded layout, quiet NaN in the padded rows
@@ -735,79 +767,92 @@ int jmid_topk_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const i
     return topk_entry(h, E, A, K, T, k, n_agents, pos, bw, sel, logw, mem);
 }
 
-static int predict_entry(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
-                         const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
-                         float* logw, float* pos_out);
+// what the chained entries' calls start from: the dimensions, dt, the precision and the entry's name
+static ChainCall chain_call(const char* who, int E, int A, int K, int T, int k, float dt, int precision) {
+    ChainCall c{E, A, K, T, k, precision};
+    c.dt = dt; c.who = who;
+    return c;
+}
+
+// jmid_predict and jmid_predict_padded: the five inputs are host arrays
+static int predict_entry(jmid_handle_t h, const ChainCall& c) {
+    if (!h) return JMID_EINVAL;
+    if (int rc = check_ready(h)) return rc;
+    const std::string w(c.who);
+    if (c.E <= 0 || c.A <= 0 || c.K <= 0 || c.T <= 0 || c.k < 1 || c.k > c.K) return fail(h, JMID_EINVAL, w + ": bad dimensions");
+    if (!c.x_st || !c.nbr_sum || !c.edge_mask || !c.x_T || !c.p0) return fail(h, JMID_EINVAL, w + ": null input");
+    if (c.rank() && (!c.sel || !c.logw)) return fail(h, JMID_EINVAL, w + ": k < K needs sel and logw");
+    if (!c.rank() && !c.pos_out) return fail(h, JMID_EINVAL, w + ": k == K needs pos_out");
+    if (c.rank() && (c.A > 32 || c.K > 1024 || c.T > 24)) return fail(h, JMID_EINVAL, w + ": the device top-k supports A <= 32, K <= 1024, T <= 24");
+    if (h->ddpm) return fail(h, JMID_EINVAL, w + " samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return predict_chain(h, c);
+}
 
 int jmid_predict_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
                         const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
                         float* logw, float* pos_out) {
     if (!h) return JMID_EINVAL;
     if (int rc = check_n_agents(h, "jmid_predict_padded", n_agents, E, A)) return rc;
-    return predict_entry(h, E, A, K, T, k, n_agents, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out);
+    ChainCall c = chain_call("jmid_predict_padded", E, A, K, T, k, dt, precision);
+    c.padded = true; c.n_agents = n_agents;
+    c.x_st = x_st; c.nbr_sum = nbr_sum; c.edge_mask = edge_mask; c.x_T = x_T; c.p0 = p0; c.bw = bw;
+    c.sel = sel; c.logw = logw; c.pos_out = pos_out;
+    return predict_entry(h, c);
 }
 
 int jmid_predict(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_st, const float* nbr_sum, const float* edge_mask,
                  const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel, float* logw, float* pos_out) {
-    return predict_entry(h, E, A, K, T, k, nullptr, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out);
+    ChainCall c = chain_call("jmid_predict", E, A, K, T, k, dt, precision);
+    c.x_st = x_st; c.nbr_sum = nbr_sum; c.edge_mask = edge_mask; c.x_T = x_T; c.p0 = p0; c.bw = bw;
+    c.sel = sel; c.logw = logw; c.pos_out = pos_out;
+    return predict_entry(h, c);
 }
 
-// jmid_predict (n_agents null) and jmid_predict_padded
-static int predict_entry(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
-                         const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
-                         float* logw, float* pos_out) {
+// what the scene builds' calls start from: everything the four entries share but the source
+static SceneBuild scene_build(const char* who, int E, int N, int F, double time_step, int horizon, int force_all_in_cluster, int mem) {
+    SceneBuild b{who, E, N, F};
+    b.time_step = time_step; b.horizon = horizon; b.force_all_in_cluster = force_all_in_cluster; b.mem = mem;
+    return b;
+}
+
+// jmid_build_scene and jmid_build_scene_var (first_frame given): every refusal comes before the resident scene is touched
+static int build_scene_entry(jmid_handle_t h, SceneBuild b) {
     if (!h) return JMID_EINVAL;
-    if (int rc = check_ready(h)) return rc;
-    const char* who = n_agents ? "jmid_predict_padded" : "jmid_predict";
-    const std::string w(who);
-    if (E <= 0 || A <= 0 || K <= 0 || T <= 0 || k < 1 || k > K) return fail(h, JMID_EINVAL, w + ": bad dimensions");
-    if (!x_st || !nbr_sum || !edge_mask || !x_T || !p0) return fail(h, JMID_EINVAL, w + ": null input");
-    const bool rank = k < K;
-    if (rank && (!sel || !logw)) return fail(h, JMID_EINVAL, w + ": k < K needs sel and logw");
-    if (!rank && !pos_out) return fail(h, JMID_EINVAL, w + ": k == K needs pos_out");
-    if (rank && (A > 32 || K > 1024 || T > 24)) return fail(h, JMID_EINVAL, w + ": the device top-k supports A <= 32, K <= 1024, T <= 24");
-    if (h->ddpm) return fail(h, JMID_EINVAL, w + " samples with DDIM (MID.eval_sicnav: sampling=\"ddim\", MID/mid.py:333)");
+    const std::string who(b.who);
+    if (b.E <= 0 || !b.human_xy || !b.robot_xy || !b.in_cluster_out || !b.robot_in_cluster_out || !b.n_in_out) return fail(h, JMID_EINVAL, who + ": bad argument");
+    if (int rc = check_scene_dims(h, b.who, b.N, b.F, b.cv_out, b.horizon, b.time_step)) return rc;
+    if (b.first_frame)
+        for (int e = 0; e < b.E; ++e)
+            for (int j = 0; j <= b.N; ++j) {
+                const int f = b.first_frame[(size_t)e * (b.N + 1) + j];
+                if (f < 0 || f > b.F - 1)
+                    return fail(h, JMID_EINVAL, who + ": first_frame[" + std::to_string(e) + ", " + std::to_string(j) + "] = " + std::to_string(f) + " is outside 0..F-1");
+                if (j == 0 && f > b.F - 2 && !b.force_all_in_cluster)
+                    return fail(h, JMID_EINVAL, who + ": the robot of episode " + std::to_string(e) + " has fewer than 2 frames");
+            }
     HIPCHK(h, hipSetDevice(h->device));
-    return predict_chain(h, E, A, K, T, k, x_st, nbr_sum, edge_mask, x_T, p0, dt, precision, bw, sel, logw, pos_out, false, who, nullptr, nullptr,
-                         nullptr, n_agents);
+    if (int rc = order_in(h, b.mem)) return rc;
+    b.src = b.mem == JMID_MEM_HOST ? SCENE_HOST_ARRAYS : SCENE_DEVICE_ARRAYS;
+    if (int rc = build_scene_resident(h, b)) return rc;
+    return order_out(h, b.mem);
 }
 
 int jmid_build_scene(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, double time_step, int horizon,
                      int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, double* cv_out, int mem) {
-    if (!h) return JMID_EINVAL;
-    if (E <= 0 || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out) return fail(h, JMID_EINVAL, "jmid_build_scene: bad argument");
-    if (int rc = check_scene_dims(h, "jmid_build_scene", N, F, cv_out, horizon, time_step)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = order_in(h, mem)) return rc;
-    if (int rc = build_scene_resident(h, "jmid_build_scene", E, N, F, human_xy, robot_xy, mem == JMID_MEM_HOST ? 0 : 1, time_step, horizon, force_all_in_cluster,
-                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem))
-        return rc;
-    return order_out(h, mem);
+    SceneBuild b = scene_build("jmid_build_scene", E, N, F, time_step, horizon, force_all_in_cluster, mem);
+    b.human_xy = human_xy; b.robot_xy = robot_xy;
+    b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
+    return build_scene_entry(h, b);
 }
 
 int jmid_build_scene_var(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, const int32_t* first_frame,
                          double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out,
                          double* cv_out, int mem) {
-    if (!h) return JMID_EINVAL;
-    if (E <= 0 || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out) return fail(h, JMID_EINVAL, "jmid_build_scene_var: bad argument");
-    if (int rc = check_scene_dims(h, "jmid_build_scene_var", N, F, cv_out, horizon, time_step)) return rc;
-    // every refusal comes before the resident scene is touched
-    if (first_frame)
-        for (int e = 0; e < E; ++e)
-            for (int j = 0; j <= N; ++j) {
-                const int f = first_frame[(size_t)e * (N + 1) + j];
-                if (f < 0 || f > F - 1)
-                    return fail(h, JMID_EINVAL, "jmid_build_scene_var: first_frame[" + std::to_string(e) + ", " + std::to_string(j) + "] = " + std::to_string(f) +
-                                                    " is outside 0..F-1");
-                if (j == 0 && f > F - 2 && !force_all_in_cluster)
-                    return fail(h, JMID_EINVAL, "jmid_build_scene_var: the robot of episode " + std::to_string(e) + " has fewer than 2 frames");
-            }
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = order_in(h, mem)) return rc;
-    if (int rc = build_scene_resident(h, "jmid_build_scene_var", E, N, F, human_xy, robot_xy, mem == JMID_MEM_HOST ? 0 : 1, time_step, horizon, force_all_in_cluster,
-                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem, first_frame))
-        return rc;
-    return order_out(h, mem);
+    SceneBuild b = scene_build("jmid_build_scene_var", E, N, F, time_step, horizon, force_all_in_cluster, mem);
+    b.human_xy = human_xy; b.robot_xy = robot_xy; b.first_frame = first_frame;
+    b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
+    return build_scene_entry(h, b);
 }
 
 int jmid_scene_get_first_index(jmid_handle_t h, int32_t* out, int mem) {
@@ -820,8 +865,8 @@ int jmid_scene_get_first_index(jmid_handle_t h, int32_t* out, int mem) {
     const size_t bytes = (size_t)sc.E * sc.N * 4;
     const bool host = mem == JMID_MEM_HOST;
     // a scene built without first_frame: every track starts at frame 0
-    if (sc.has_first) {
-        HIPCHK(h, hipMemcpyAsync(out, sc.dev.p + sc.o_first, bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+    if (sc.has_first()) {
+        HIPCHK(h, hipMemcpyAsync(out, sc.arr.first_index.p, bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
     } else if (host) {
         std::memset(out, 0, bytes);
     } else {
@@ -831,83 +876,84 @@ int jmid_scene_get_first_index(jmid_handle_t h, int32_t* out, int mem) {
     return order_out(h, mem);
 }
 
-// jmid_build_scene_stamped (tracks false: frames_kernel, a window shorter than hist_len refused) and jmid_build_scene_stamped_var (tracks true:
-// track_frames_kernel, first_frame [E, N + 1] read back with n_grid in the one synchronisation and handed to build_scene_resident)
-static int build_scene_stamped_entry(jmid_handle_t h, const char* who_c, bool tracks, int E, int N, int R, const double* stamps, const double* human_xy,
-                                     const double* robot_xy, const int* n_frames, double time_step, int horizon, int force_all_in_cluster,
-                                     uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out,
-                                     int32_t* first_frame_out, int mem) {
+// the raw frames of jmid_build_scene_stamped / _stamped_var (where the build's `mem` says), and what only those two return
+struct StampedFrames {
+    bool tracks;                   // false: frames_kernel, a window shorter than hist_len refused.  true: track_frames_kernel, first_frame
+                                   // [E, N + 1] read back with n_grid in the one synchronisation and handed to the build
+    int R;
+    const double *stamps, *human_xy, *robot_xy;
+    const int* n_frames;
+    int* n_grid_out;
+    int32_t* first_frame_out;      // tracks only, or null
+};
+
+// jmid_build_scene_stamped and jmid_build_scene_stamped_var: b states everything but the source, which is the grid block made here
+static int build_scene_stamped_entry(jmid_handle_t h, SceneBuild b, const StampedFrames& s) {
     if (!h) return JMID_EINVAL;
-    const std::string who(who_c);
-    if (E <= 0 || !stamps || !human_xy || !robot_xy || !in_cluster_out || !robot_in_cluster_out || !n_in_out || !n_grid_out)
+    const std::string who(b.who);
+    const int E = b.E, N = b.N, R = s.R, mem = b.mem;
+    if (E <= 0 || !s.stamps || !s.human_xy || !s.robot_xy || !b.in_cluster_out || !b.robot_in_cluster_out || !b.n_in_out || !s.n_grid_out)
         return fail(h, JMID_EINVAL, who + ": bad argument");
     if (R < 1 || R > FRM_MAX_R) return fail(h, JMID_EINVAL, who + " supports 1 <= R <= 64 raw frames");
-    const int F = h->hist_len;
-    if (int rc = check_scene_dims(h, who_c, N, F, cv_out, horizon, time_step)) return rc;
+    const int F = b.F = h->hist_len;
+    if (int rc = check_scene_dims(h, b.who, N, F, b.cv_out, b.horizon, b.time_step)) return rc;
     // w = round(time_step * 100) as Python rounds it (to nearest, ties to even)
-    const double wd = std::nearbyint(time_step * 100.0);
+    const double wd = std::nearbyint(b.time_step * 100.0);
     if (!(wd >= 1.0) || wd > 9.0e15) return fail(h, JMID_EINVAL, who + ": round(time_step * 100) must be at least 1");
     const bool host = mem == JMID_MEM_HOST;
-    if (host && n_frames)
+    if (host && s.n_frames)
         for (int e = 0; e < E; ++e)
-            if (n_frames[e] < 1 || n_frames[e] > R)
-                return fail(h, JMID_EINVAL, who + ": n_frames[" + std::to_string(e) + "] = " + std::to_string(n_frames[e]) + " is outside 1..R");
+            if (s.n_frames[e] < 1 || s.n_frames[e] > R)
+                return fail(h, JMID_EINVAL, who + ": n_frames[" + std::to_string(e) + "] = " + std::to_string(s.n_frames[e]) + " is outside 1..R");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
-    const size_t b_st = (size_t)E * R * 8, b_hum = (size_t)E * R * N * 2 * 8, b_rob = (size_t)E * R * 2 * 8, b_nf = n_frames ? (size_t)E * 4 : 0;
-    const GridBlock gb = grid_block(E, N, F);
+    const size_t b_st = (size_t)E * R * 8, b_hum = (size_t)E * R * N * 2 * 8, b_rob = (size_t)E * R * 2 * 8, b_nf = s.n_frames ? (size_t)E * 4 : 0;
     // the grid block frames_kernel writes | n_grid (tracks: and first_frame [E, N + 1] behind it, one download) | the staged raw frames (host
     // mode): stamps, human_xy, robot_xy, n_frames
-    const size_t n_first = tracks ? (size_t)E * (N + 1) : 0, b_back = ((size_t)E + n_first) * 4;
-    const size_t o_ng = gb.end, o_st = o_ng + align_up(b_back), o_rh = o_st + (host ? align_up(b_st) : 0), o_rr = o_rh + (host ? align_up(b_hum) : 0),
-                 o_nf = o_rr + (host ? align_up(b_rob) : 0), need = o_nf + (host ? align_up(b_nf) : 0), raw = need - o_st;
-    if (int rc = h->frames_dev.reserve(h, need, who_c)) return rc;
-    if (int rc = h->pin.reserve(h, raw + b_back, who_c)) return rc;
+    const size_t n_first = s.tracks ? (size_t)E * (N + 1) : 0, b_back = ((size_t)E + n_first) * 4;
+    const size_t o_ng = grid_block(E, N, F, nullptr, nullptr), o_st = o_ng + align_up(b_back), o_rh = o_st + (host ? align_up(b_st) : 0),
+                 o_rr = o_rh + (host ? align_up(b_hum) : 0), o_nf = o_rr + (host ? align_up(b_rob) : 0), need = o_nf + (host ? align_up(b_nf) : 0), raw = need - o_st;
+    if (int rc = h->frames_dev.reserve(h, need, b.who)) return rc;
+    if (int rc = h->pin.reserve(h, raw + b_back, b.who)) return rc;
     char *const fd = h->frames_dev.p, *const pin = h->pin.p;
-    FramesArgs f{};
+    GridBlock gb;
+    grid_block(E, N, F, fd, &gb);
+    TrackFramesArgs t{};
+    FramesArgs& f = t;
     f.E = E; f.N = N; f.R = R; f.F = F;
     f.w = (long long)wd;
-    f.stamps = stamps; f.human_xy = human_xy; f.robot_xy = robot_xy; f.n_frames = n_frames;
-    f.o_human = reinterpret_cast<double*>(fd + gb.o_hum); f.o_robot = reinterpret_cast<double*>(fd + gb.o_rob);
-    f.o_pose = reinterpret_cast<double*>(fd + gb.o_pose); f.o_n_grid = reinterpret_cast<int*>(fd + o_ng);
+    f.stamps = s.stamps; f.human_xy = s.human_xy; f.robot_xy = s.robot_xy; f.n_frames = s.n_frames;
+    f.o_human = gb.human_xy; f.o_robot = gb.robot_xy; f.o_pose = gb.pose_now; f.o_n_grid = reinterpret_cast<int*>(fd + o_ng);
+    t.o_first = f.o_n_grid + E;
     if (host) {
-        std::memcpy(pin, stamps, b_st);
-        std::memcpy(pin + (o_rh - o_st), human_xy, b_hum);
-        std::memcpy(pin + (o_rr - o_st), robot_xy, b_rob);
-        if (n_frames) std::memcpy(pin + (o_nf - o_st), n_frames, b_nf);
+        std::memcpy(pin, s.stamps, b_st);
+        std::memcpy(pin + (o_rh - o_st), s.human_xy, b_hum);
+        std::memcpy(pin + (o_rr - o_st), s.robot_xy, b_rob);
+        if (s.n_frames) std::memcpy(pin + (o_nf - o_st), s.n_frames, b_nf);
         HIPCHK(h, hipMemcpyAsync(fd + o_st, pin, raw, hipMemcpyHostToDevice, h->stream));
         f.stamps = reinterpret_cast<const double*>(fd + o_st); f.human_xy = reinterpret_cast<const double*>(fd + o_rh);
         f.robot_xy = reinterpret_cast<const double*>(fd + o_rr);
-        f.n_frames = n_frames ? reinterpret_cast<const int*>(fd + o_nf) : nullptr;
+        f.n_frames = s.n_frames ? reinterpret_cast<const int*>(fd + o_nf) : nullptr;
     }
-    if (tracks) {
-        TrackFramesArgs t{};
-        t.E = E; t.N = N; t.R = R; t.F = F;
-        t.w = f.w;
-        t.stamps = f.stamps; t.human_xy = f.human_xy; t.robot_xy = f.robot_xy; t.n_frames = f.n_frames;
-        t.o_human = f.o_human; t.o_robot = f.o_robot; t.o_pose = f.o_pose; t.o_n_grid = f.o_n_grid;
-        t.o_first = f.o_n_grid + E;
-        HIPCHK(h, launch_track_frames(t, h->stream));
-    } else {
-        HIPCHK(h, launch_frames(f, h->stream));
-    }
+    if (s.tracks) HIPCHK(h, launch_track_frames(t, h->stream));
+    else HIPCHK(h, launch_frames(f, h->stream));
     int* ng = reinterpret_cast<int*>(pin + raw);
     HIPCHK(h, hipMemcpyAsync(ng, f.o_n_grid, b_back, hipMemcpyDeviceToHost, h->stream));
     if (!host) {
-        HIPCHK(h, hipMemcpyAsync(n_grid_out, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
-        if (first_frame_out) HIPCHK(h, hipMemcpyAsync(first_frame_out, f.o_n_grid + E, n_first * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(s.n_grid_out, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (s.first_frame_out) HIPCHK(h, hipMemcpyAsync(s.first_frame_out, t.o_first, n_first * 4, hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (host) {
-        std::memcpy(n_grid_out, ng, (size_t)E * 4);
-        if (first_frame_out) std::memcpy(first_frame_out, ng + E, n_first * 4);
+        std::memcpy(s.n_grid_out, ng, (size_t)E * 4);
+        if (s.first_frame_out) std::memcpy(s.first_frame_out, ng + E, n_first * 4);
     }
     for (int e = 0; e < E; ++e)
         if (ng[e] < 0) {
             (void)order_out(h, mem);
             return fail(h, JMID_EINVAL, who + ": n_frames[" + std::to_string(e) + "] is outside 1..R");
         }
-    const int F_min = tracks ? 2 : F;                         // a per-track table starts every node where its own frames start
+    const int F_min = s.tracks ? 2 : F;                       // a per-track table starts every node where its own frames start
     for (int e = 0; e < E; ++e)
         if (ng[e] < F_min) {
             const int got = ng[e];
@@ -923,24 +969,27 @@ static int build_scene_stamped_entry(jmid_handle_t h, const char* who_c, bool tr
             return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(q / (N + 1)) + ", track " + std::to_string((int)(q % (N + 1)) - 1) +
                                             " is not seen in the newest kept frame (leave the track out)");
         }
-    if (int rc = build_scene_resident(h, who_c, E, N, F, reinterpret_cast<const double*>(fd), nullptr, 2, time_step, horizon, force_all_in_cluster,
-                                      in_cluster_out, robot_in_cluster_out, n_in_out, cv_out, mem, tracks ? first.data() : nullptr))
-        return rc;
+    b.src = SCENE_DEVICE_GRID;
+    b.human_xy = reinterpret_cast<const double*>(fd);
+    b.first_frame = s.tracks ? first.data() : nullptr;
+    if (int rc = build_scene_resident(h, b)) return rc;
     return order_out(h, mem);
 }
 
 int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
                              const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
                              uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int mem) {
-    return build_scene_stamped_entry(h, "jmid_build_scene_stamped", false, E, N, R, stamps, human_xy, robot_xy, n_frames, time_step, horizon,
-                                     force_all_in_cluster, in_cluster_out, robot_in_cluster_out, n_in_out, n_grid_out, cv_out, nullptr, mem);
+    SceneBuild b = scene_build("jmid_build_scene_stamped", E, N, 0, time_step, horizon, force_all_in_cluster, mem);
+    b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
+    return build_scene_stamped_entry(h, b, StampedFrames{false, R, stamps, human_xy, robot_xy, n_frames, n_grid_out, nullptr});
 }
 
 int jmid_build_scene_stamped_var(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
                                  const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
                                  uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int32_t* first_frame_out, int mem) {
-    return build_scene_stamped_entry(h, "jmid_build_scene_stamped_var", true, E, N, R, stamps, human_xy, robot_xy, n_frames, time_step, horizon,
-                                     force_all_in_cluster, in_cluster_out, robot_in_cluster_out, n_in_out, n_grid_out, cv_out, first_frame_out, mem);
+    SceneBuild b = scene_build("jmid_build_scene_stamped_var", E, N, 0, time_step, horizon, force_all_in_cluster, mem);
+    b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
+    return build_scene_stamped_entry(h, b, StampedFrames{true, R, stamps, human_xy, robot_xy, n_frames, n_grid_out, first_frame_out});
 }
 
 int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_xy_out, double* pose_now_out, int mem) {
@@ -949,14 +998,15 @@ int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_x
     if (!sc.E) return fail(h, JMID_EINVAL, "jmid_scene_get_frames needs a preceding jmid_build_scene on this handle");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
+    const GridBlock& gb = sc.arr.grid;
     const size_t F = h->hist_len, row = (size_t)sc.N * 2 * 8;
     const hipMemcpyKind kind = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (human_xy_out) HIPCHK(h, hipMemcpyAsync(human_xy_out, sc.dev.p + sc.o_hum, (size_t)sc.E * F * row, kind, h->stream));
-    if (robot_xy_out) HIPCHK(h, hipMemcpyAsync(robot_xy_out, sc.dev.p + sc.o_rob, (size_t)sc.E * F * 2 * 8, kind, h->stream));
+    if (human_xy_out) HIPCHK(h, hipMemcpyAsync(human_xy_out, gb.human_xy.p, gb.human_xy.bytes(), kind, h->stream));
+    if (robot_xy_out) HIPCHK(h, hipMemcpyAsync(robot_xy_out, gb.robot_xy.p, gb.robot_xy.bytes(), kind, h->stream));
     if (pose_now_out) {
-        if (sc.stamped) HIPCHK(h, hipMemcpyAsync(pose_now_out, sc.dev.p + sc.o_pose, (size_t)sc.E * row, kind, h->stream));
+        if (sc.stamped) HIPCHK(h, hipMemcpyAsync(pose_now_out, gb.pose_now.p, gb.pose_now.bytes(), kind, h->stream));
         else            // the last frame of every episode's grid
-            HIPCHK(h, hipMemcpy2DAsync(pose_now_out, row, sc.dev.p + sc.o_hum + (F - 1) * row, F * row, row, sc.E, kind, h->stream));
+            HIPCHK(h, hipMemcpy2DAsync(pose_now_out, row, gb.human_xy.p + (F - 1) * (size_t)sc.N * 2, F * row, row, sc.E, kind, h->stream));
     }
     if (mem == JMID_MEM_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
     return order_out(h, mem);
@@ -968,64 +1018,75 @@ int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float
     if (!sc.E) return fail(h, JMID_EINVAL, "jmid_scene_get needs a preceding jmid_build_scene on this handle");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
-    const size_t rows = (size_t)sc.E * sc.N, F = h->hist_len;
+    const SceneArrays& a = sc.arr;
     const hipMemcpyKind kind = mem == JMID_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (x) HIPCHK(h, hipMemcpyAsync(x, sc.dev.p + sc.o_x, rows * F * 6 * 4, kind, h->stream));
-    if (x_st) HIPCHK(h, hipMemcpyAsync(x_st, sc.dev.p + sc.o_xst, rows * F * 6 * 4, kind, h->stream));
-    if (nbr_sum) HIPCHK(h, hipMemcpyAsync(nbr_sum, sc.dev.p + sc.o_nbr, rows * 2 * F * 6 * 4, kind, h->stream));
-    if (edge_mask) HIPCHK(h, hipMemcpyAsync(edge_mask, sc.dev.p + sc.o_em, rows * 2 * 4, kind, h->stream));
-    if (p0) HIPCHK(h, hipMemcpyAsync(p0, sc.dev.p + sc.o_p0, rows * 2 * 4, kind, h->stream));
+    if (x) HIPCHK(h, hipMemcpyAsync(x, a.x.p, a.x.bytes(), kind, h->stream));
+    if (x_st) HIPCHK(h, hipMemcpyAsync(x_st, a.x_st.p, a.x_st.bytes(), kind, h->stream));
+    if (nbr_sum) HIPCHK(h, hipMemcpyAsync(nbr_sum, a.nbr_sum.p, a.nbr_sum.bytes(), kind, h->stream));
+    if (edge_mask) HIPCHK(h, hipMemcpyAsync(edge_mask, a.edge_mask.p, a.edge_mask.bytes(), kind, h->stream));
+    if (p0) HIPCHK(h, hipMemcpyAsync(p0, a.p0.p, a.p0.bytes(), kind, h->stream));
     if (mem == JMID_MEM_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
     return order_out(h, mem);
 }
 
 int jmid_predict_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw, float* sel,
                        float* logw, float* pos_out) {
-    return predict_scene_entry(h, "jmid_predict_scene", E, A, K, T, k, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr, false);
+    ChainCall c = chain_call("jmid_predict_scene", E, A, K, T, k, dt, precision);
+    c.x_T = x_T; c.bw = bw; c.sel = sel; c.logw = logw; c.pos_out = pos_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_forecast_scene(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
                         double* forecasts_out, double* logw_out) {
-    return predict_scene_entry(h, "jmid_forecast_scene", E, A, K, T, k, x_T, nullptr, dt, precision, bw, nullptr, nullptr, nullptr, forecasts_out,
-                               logw_out, true);
+    ChainCall c = chain_call("jmid_forecast_scene", E, A, K, T, k, dt, precision);
+    c.forecast = true; c.x_T = x_T; c.bw = bw; c.forecasts_out = forecasts_out; c.logw_out = logw_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_predict_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt, int precision,
                               const float* bw, float* sel, float* logw, float* pos_out) {
     const SeedArgs sa{seed, episode_ids};
-    return predict_scene_entry(h, "jmid_predict_scene_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr, false);
+    ChainCall c = chain_call("jmid_predict_scene_seeded", E, A, K, T, k, dt, precision);
+    c.seeded = &sa; c.bw = bw; c.sel = sel; c.logw = logw; c.pos_out = pos_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_forecast_scene_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt, int precision,
                                const float* bw, double* forecasts_out, double* logw_out) {
     const SeedArgs sa{seed, episode_ids};
-    return predict_scene_entry(h, "jmid_forecast_scene_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, nullptr, nullptr, nullptr, forecasts_out,
-                               logw_out, true);
+    ChainCall c = chain_call("jmid_forecast_scene_seeded", E, A, K, T, k, dt, precision);
+    c.forecast = true; c.seeded = &sa; c.bw = bw; c.forecasts_out = forecasts_out; c.logw_out = logw_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_predict_scene_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
                               float* sel, float* logw, float* pos_out) {
-    return predict_scene_entry(h, "jmid_predict_scene_padded", E, A, K, T, k, x_T, nullptr, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr, false, true);
+    ChainCall c = chain_call("jmid_predict_scene_padded", E, A, K, T, k, dt, precision);
+    c.padded = true; c.x_T = x_T; c.bw = bw; c.sel = sel; c.logw = logw; c.pos_out = pos_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_forecast_scene_padded(jmid_handle_t h, int E, int A, int K, int T, int k, const float* x_T, float dt, int precision, const float* bw,
                                double* forecasts_out, double* logw_out) {
-    return predict_scene_entry(h, "jmid_forecast_scene_padded", E, A, K, T, k, x_T, nullptr, dt, precision, bw, nullptr, nullptr, nullptr, forecasts_out,
-                               logw_out, true, true);
+    ChainCall c = chain_call("jmid_forecast_scene_padded", E, A, K, T, k, dt, precision);
+    c.forecast = c.padded = true; c.x_T = x_T; c.bw = bw; c.forecasts_out = forecasts_out; c.logw_out = logw_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_predict_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
                                      int precision, const float* bw, float* sel, float* logw, float* pos_out) {
     const SeedArgs sa{seed, episode_ids};
-    return predict_scene_entry(h, "jmid_predict_scene_padded_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, sel, logw, pos_out, nullptr, nullptr,
-                               false, true);
+    ChainCall c = chain_call("jmid_predict_scene_padded_seeded", E, A, K, T, k, dt, precision);
+    c.padded = true; c.seeded = &sa; c.bw = bw; c.sel = sel; c.logw = logw; c.pos_out = pos_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_forecast_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
                                       int precision, const float* bw, double* forecasts_out, double* logw_out) {
     const SeedArgs sa{seed, episode_ids};
-    return predict_scene_entry(h, "jmid_forecast_scene_padded_seeded", E, A, K, T, k, nullptr, &sa, dt, precision, bw, nullptr, nullptr, nullptr,
-                               forecasts_out, logw_out, true, true);
+    ChainCall c = chain_call("jmid_forecast_scene_padded_seeded", E, A, K, T, k, dt, precision);
+    c.forecast = c.padded = true; c.seeded = &sa; c.bw = bw; c.forecasts_out = forecasts_out; c.logw_out = logw_out;
+    return predict_scene_entry(h, c);
 }
 
 int jmid_denoise_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,

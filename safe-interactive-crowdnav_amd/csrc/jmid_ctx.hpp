@@ -1,12 +1,15 @@
 // libjmid_hip.so -- what every translation unit of the host side shares: the handle, error / profiling helpers and the
 // internal entry points between the units.  gfx950 only.  No CPU fallback: every entry point that computes needs a HIP device.
-// The handle holds what outlives a call; the mode (CallMode), arguments (DenoiseCall) and lanes of the RUNNING call are values passed down.
-//   jmid_abi.hip      the C ABI proper (include/jmid_hip.h): handle lifetime, encode / denoise / topk / predict / scene / statistics, knobs, stream
+// The handle holds what outlives a call; the mode (CallMode), arguments (DenoiseCall, ChainCall, SceneBuild) and lanes of the RUNNING call
+// are values passed down, and every block is laid out once by a Carver function that returns typed arrays (call_io, kde_workspace, chain_io,
+// grid_block, scene_arrays).
+//   jmid_abi.hip      the C ABI proper (include/jmid_hip.h): handle lifetime, encode / denoise / topk / statistics, knobs, stream; the chained
+//                     predictor (chain_io, the phases of predict_chain) and the scene build (scene_arrays, build_scene_resident)
 //   jmid_weights.hip  weight registry, operand planes (fp16 hi / lo, bf8 images, k16 panels), sampler step tables
 //   jmid_planner.hip  chunk plan, step workspace, one net evaluation (net_step), the call plan and the phases of a denoise call (run_network)
 //   jmid_profile.hip  per-kernel-class HIP-event profiling
-//   jmid_diag.hip     jmid_dbg_* single-kernel entry points (-DJMID_DIAGNOSTICS only)
-//   host_mem.hpp      align_up / Carver, the owning Block (device or pinned) every workspace of the handle is, HostArray, Staging
+//   jmid_diag.hip     jmid_dbg_* single-kernel, plan and layout entry points (-DJMID_DIAGNOSTICS only)
+//   host_mem.hpp      align_up / Carver / Arr, the owning Block (device or pinned) every workspace of the handle is, HostArray, Staging
 // Whatever the handle owns is released by ~jmid_ctx: jmid_destroy and a jmid_create that fails half way both end in `delete h`.
 #pragma once
 #include "../../include/jmid_hip.h"
@@ -123,6 +126,26 @@ int order_out(jmid_ctx* h, int mem);
 }  // namespace jmid_host
 #include "host_mem.hpp"
 
+namespace jmid_host {
+// where the grid of a scene lies in a workspace: the same block in the scene workspace and in the one frames_kernel writes, so that
+// one copy moves it (grid_block lays it out)
+struct GridBlock {
+    Arr<double> human_xy, robot_xy, pose_now;      // [E, F, N, 2] | [E, F, 2] | [E, N, 2]
+    size_t xy_bytes = 0;                           // human_xy | robot_xy: what a build from host arrays stages, one copy
+};
+// The scene workspace (scene_arrays lays it out): the grid block | the padded [E, N, ...] rows jmid_scene_get copies out and
+// jmid_predict_scene gathers from | the download block of a build: n_in, in_cluster, robot_in, cv | first_index
+struct SceneArrays {
+    GridBlock grid;
+    Arr<float> x, x_st, nbr_sum, edge_mask, p0;    // [E, N, F, 6] twice | [E, N, 2, F, 6] | [E, N, 2] twice
+    Arr<int> n_in;                                 // [E]
+    Arr<unsigned char> in_cluster, robot_in;       // [E, N] | [E]
+    Arr<double> cv;                                // [E, N, horizon, 2], or none
+    size_t down_bytes = 0;                         // n_in ... cv: one copy
+    Arr<int> first_index;                          // [E, N], or none
+};
+}  // namespace jmid_host
+
 struct jmid_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -159,19 +182,13 @@ struct jmid_ctx {
     struct SceneWs {
         jmid_host::Block dev;
         int E = 0, N = 0;            // E = 0: no scene is resident
-        size_t o_x = 0, o_xst = 0, o_nbr = 0, o_em = 0, o_p0 = 0, o_inc = 0;   // byte offsets of the resident arrays
-        std::vector<int> n_in;       // [E] in-cluster pedestrians per episode (host copy)
-        size_t o_nin = 0;            // ... and where the build kernel wrote them: the device counts of the padded chains
-        // the grid the scene was built from (human_xy [E, F, N, 2], robot_xy [E, F, 2] fp64) and pose_now [E, N, 2]: what
-        // jmid_scene_get_frames copies out and jmid_forecast_scene prepends.  stamped: pose_now has a slot of its own (frames_kernel wrote
-        // it); otherwise it is the last frame of the grid
-        size_t o_hum = 0, o_rob = 0, o_pose = 0, o_cv = 0;
+        jmid_host::SceneArrays arr;  // the resident arrays, typed pointers into dev (scene_arrays laid them out)
+        std::vector<int> n_in;       // [E] in-cluster pedestrians per episode (host copy of arr.n_in, the device counts of the padded chains)
+        // stamped: pose_now has the grid block's slot of its own (frames_kernel wrote it); otherwise it is the last frame of the grid
         bool stamped = false;
         int horizon = 0;             // of the resident cv; 0: built without cv
-        // jmid_build_scene_var: first_index [E, N] int32 (every pedestrian's first history frame); the other builds leave none and
-        // the chained entries then run the encoder without one
-        size_t o_first = 0;
-        bool has_first = false;
+        // jmid_build_scene_var leaves arr.first_index; the other builds leave none and the chained entries then run the encoder without one
+        bool has_first() const { return arr.first_index.n != 0; }
     } scene;
     // jmid_build_scene_stamped / _stamped_var: the raw frames and what frames_kernel / track_frames_kernel made of them (grid, pose_now,
     // n_grid, first_frame), in a workspace of its own: a refused build (JMID_EHISTORY, an absent-now track) must not touch the resident scene
@@ -347,6 +364,60 @@ struct DenoiseCall {
     const LossCall* loss = nullptr;       // a loss call: per-row timesteps folded into hyp, a zero row as thyp, e_out may be null
     const char* who = "jmid_denoise";     // the entry point that was called (error texts)
 };
+// One chained call (jmid_predict*, jmid_predict_scene*, jmid_forecast_scene*) as its entry point states it: upload, encoder -> denoise
+// loop -> integrator -> top-k (-> assembly) on the stream, one download.  The modes are members, not null pointers read at a distance.
+struct ChainCall {
+    int E, A, K, T, k, precision;
+    float dt = 0.f;
+    const char* who = "jmid_predict";     // the entry point that was called (error texts)
+    bool scene = false;                   // the in-cluster rows of the resident scene are gathered on the device: no host inputs but the noise and bw
+    bool forecast = false;                // scene only: assemble_kernel follows, forecasts_out / logw_out are the download and sel / logw / pos stay on the device
+    bool padded = false;                  // mixed agent counts, A the largest: n_agents says them
+    const float *x_st = nullptr, *nbr_sum = nullptr, *edge_mask = nullptr, *p0 = nullptr;      // HOST inputs (scene: none)
+    const float* x_T = nullptr;           // the noise: HOST [E, K A, T, 2], or
+    const SeedArgs* seeded = nullptr;     // ... (scene only) draw 0 of noise.hpp, filled into x_T's slot on the device
+    const float* bw = nullptr;            // HOST [T] or null; read when k < K
+    float *sel = nullptr, *logw = nullptr, *pos_out = nullptr;      // k < K: sel, logw; pos_out optional then
+    double *forecasts_out = nullptr, *logw_out = nullptr;           // forecast: [E, N, k, T+1, 2] and [E, N, k]
+    // padded: HOST [E].  Host arrays: the caller's counts, uploaded by the denoise stage - the padded agents' rows go through the
+    // encoder as the caller left them (its rows are independent) and the denoise stage zeroes their ctx, x_T and p0.  Scene: the host
+    // copy of the resident scene's counts; the stages read the device counts the build kernel wrote (nothing is uploaded for them),
+    // the gather zeroes the padded rows and a seeded x_T is the padded fill
+    const int32_t* n_agents = nullptr;
+    bool rank() const { return k < K; }
+};
+// The I/O block of a chained call as chain_io lays it out, in device memory or (ctx and first_index absent, and after the assembled
+// arrays of a forecast nothing) in the pinned block
+struct ChainIo {
+    Arr<float> x_st, nbr_sum, edge_mask, x_T, p0, bw;      // the upload block: [E A, Th, 6] | [E A, 2, Th, 6] | [E A, 2] | [E, K A, T, 2] | [E, A, 2] | [T] or none
+    size_t up_bytes = 0;
+    Arr<float> ctx;                                        // [E A, 2 H]
+    Arr<int> flag;                                         // the download block: the range flag's word |
+    Arr<double> forecasts, logw_d;                         // forecast: [E, N, k, T+1, 2] | [E, N, k] |
+    Arr<float> sel, logw, pos;                             // k < K: [E, A, k, T, 2] | [E, A, k] | pos_out given: [E, K, A, T, 2]
+    size_t down_bytes = 0;                                 // flag ... pos; forecast: flag ... logw_d
+    Arr<int> first_index;                                  // a scene with one: [E A]
+    size_t up_bytes_from(const Arr<float>& a) const { return up_bytes - (size_t)((const char*)a.p - (const char*)x_st.p); }      // the rest of the upload block from `a` on
+};
+// One scene build (jmid_build_scene*, and the second half of jmid_build_scene_stamped*) as its entry point states it
+enum SceneSource {
+    SCENE_HOST_ARRAYS,       // human_xy [E, F, N, 2], robot_xy [E, F, 2]: host arrays, staged
+    SCENE_DEVICE_ARRAYS,     // ... device arrays
+    SCENE_DEVICE_GRID,       // human_xy is a device GridBlock (grid + pose_now, as frames_kernel left it), robot_xy unused
+};
+struct SceneBuild {
+    const char* who;
+    int E, N, F;
+    SceneSource src;
+    const double *human_xy, *robot_xy;
+    const int32_t* first_frame = nullptr;      // a HOST array [E, N + 1], checked by the entry, or null: uploaded ahead of the kernel, which then leaves first_index
+    double time_step = 0.0;
+    int horizon = 0, force_all_in_cluster = 0;
+    uint8_t *in_cluster_out = nullptr, *robot_in_cluster_out = nullptr;
+    int* n_in_out = nullptr;
+    double* cv_out = nullptr;                  // null: no cv (and no jmid_forecast_scene on this scene)
+    int mem = JMID_MEM_HOST;                   // where the four outputs live
+};
 // the counts of a padded call: checked by its entry before anything is enqueued (JMID_EINVAL: null, or a count outside 1..A), then
 // uploaded through h->nag on h->stream
 int check_n_agents(jmid_ctx* h, const char* who, const int32_t* n_agents, int E, int A);
@@ -358,6 +429,8 @@ int dbg_layer(jmid_ctx* h, int E, int A, int K, int T, int layer, int precision,
 int flagged_call(jmid_ctx* h, int flag);      // the status of a call whose range flag came back set (JMID_ETIMEOUT / JMID_ERANGE)
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T);
 // jmid_abi.hip
+size_t chain_io(const jmid_ctx* h, const ChainCall& c, char* base, ChainIo* out, bool pinned);
+size_t scene_arrays(int E, int N, int F, int horizon, bool has_first, char* base, SceneArrays* out);
 int noise_entry(jmid_ctx* h, const char* who, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out,
                 unsigned* words, int mem);
 // jmid_profile.hip

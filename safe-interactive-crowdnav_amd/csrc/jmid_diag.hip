@@ -50,6 +50,13 @@ static unsigned char* dbg_w8(DbgTemps& t, const float* dW, int N, int K) {
     return t.rc ? nullptr : p;
 }
 
+// one array of a layout -> (byte offset from the block's base, bytes); an array the call does not have: (-1, 0)
+template <class T>
+static void put_arr(int64_t*& w, const Arr<T>& a, const char* base) {
+    *w++ = a.n ? (const char*)a.p - base : -1;
+    *w++ = (int64_t)a.bytes();
+}
+
 extern "C" {
 
 // The chunk plan of a mode without the one-launch rule (JMID_PREC_F16X3)
@@ -84,6 +91,55 @@ int jmid_dbg_gemm_plan(int mode, int epi, int out, int M, int N, int K, int smal
     plan[0] = p.mode; plan[1] = p.shape; plan[2] = p.flags; plan[3] = p.group_tiles;
     plan[4] = gemm_shape_bm(p.shape); plan[5] = gemm_shape_bn(p.shape);
     plan[6] = plan_ln_rows(false, M, t); plan[7] = plan_ln_rows(true, M, t);
+    return JMID_OK;
+}
+
+// chain_io and scene_arrays on a handle that lives on the stack (host fields only) and blocks of host memory: no HIP call
+int jmid_dbg_chain_layout(int hist_len, int ctx_dim, int E, int A, int K, int T, int k, int N, int flags, int64_t* chain_dev, int64_t* chain_pin,
+                          int64_t* scene) {
+    const bool in_scene = flags & JMID_DBG_LAYOUT_SCENE, forecast = flags & JMID_DBG_LAYOUT_FORECAST, seeded = flags & JMID_DBG_LAYOUT_SEEDED,
+               first = flags & JMID_DBG_LAYOUT_FIRST_INDEX, pos = flags & JMID_DBG_LAYOUT_POS, cv = flags & JMID_DBG_LAYOUT_CV;
+    if (!chain_dev || !chain_pin || !scene || hist_len < 1 || ctx_dim < 2 || E < 1 || A < 1 || K < 1 || T < 1 || k < 1 || k > K || N < 1) return JMID_EINVAL;
+    if (!in_scene && (forecast || seeded || first)) return JMID_EINVAL;      // what exists in scene mode only
+    if (forecast ? !cv || pos : k == K && !pos) return JMID_EINVAL;          // a forecast needs the scene's cv and downloads no pos; k == K needs pos_out
+    jmid_ctx ctx;
+    ctx.hist_len = hist_len; ctx.ctx_dim = ctx_dim; ctx.H = ctx_dim / 2;
+    jmid_ctx::SceneWs& sc = ctx.scene;
+    const int horizon = cv ? T : 0;
+    std::vector<char> sbuf(scene_arrays(E, N, hist_len, horizon, first, nullptr, nullptr));
+    const size_t s_total = scene_arrays(E, N, hist_len, horizon, first, sbuf.data(), &sc.arr);
+    sc.E = E; sc.N = N; sc.horizon = horizon;
+    const SceneArrays& a = sc.arr;
+    int64_t* w = scene;
+    put_arr(w, a.grid.human_xy, sbuf.data()); put_arr(w, a.grid.robot_xy, sbuf.data()); put_arr(w, a.grid.pose_now, sbuf.data());
+    put_arr(w, a.x, sbuf.data()); put_arr(w, a.x_st, sbuf.data()); put_arr(w, a.nbr_sum, sbuf.data()); put_arr(w, a.edge_mask, sbuf.data());
+    put_arr(w, a.p0, sbuf.data()); put_arr(w, a.n_in, sbuf.data()); put_arr(w, a.in_cluster, sbuf.data()); put_arr(w, a.robot_in, sbuf.data());
+    put_arr(w, a.cv, sbuf.data()); put_arr(w, a.first_index, sbuf.data());
+    *w++ = (const char*)a.x.p - sbuf.data();                  // the grid block: the bytes in front of x
+    *w++ = (const char*)a.n_in.p - sbuf.data(); *w++ = (int64_t)a.down_bytes; *w++ = (int64_t)s_total;
+    float some = 0.f;
+    double some_d = 0.0;
+    const uint32_t id = 0;
+    const SeedArgs sa{0, &id};
+    ChainCall c{E, A, K, T, k, JMID_PREC_F32};
+    c.scene = in_scene; c.forecast = forecast; c.padded = flags & JMID_DBG_LAYOUT_PADDED;
+    if (seeded) c.seeded = &sa;
+    else c.x_T = &some;
+    if (flags & JMID_DBG_LAYOUT_BW) c.bw = &some;
+    if (pos) c.pos_out = &some;
+    if (forecast) c.forecasts_out = c.logw_out = &some_d;
+    for (int pinned = 0; pinned < 2; ++pinned) {
+        std::vector<char> buf(chain_io(&ctx, c, nullptr, nullptr, pinned));
+        ChainIo io;
+        const size_t total = chain_io(&ctx, c, buf.data(), &io, pinned);
+        w = pinned ? chain_pin : chain_dev;
+        put_arr(w, io.x_st, buf.data()); put_arr(w, io.nbr_sum, buf.data()); put_arr(w, io.edge_mask, buf.data()); put_arr(w, io.x_T, buf.data());
+        put_arr(w, io.p0, buf.data()); put_arr(w, io.bw, buf.data()); put_arr(w, io.ctx, buf.data()); put_arr(w, io.flag, buf.data());
+        put_arr(w, io.forecasts, buf.data()); put_arr(w, io.logw_d, buf.data()); put_arr(w, io.sel, buf.data()); put_arr(w, io.logw, buf.data());
+        put_arr(w, io.pos, buf.data()); put_arr(w, io.first_index, buf.data());
+        *w++ = (const char*)io.x_st.p - buf.data(); *w++ = (int64_t)io.up_bytes;
+        *w++ = (const char*)io.flag.p - buf.data(); *w++ = (int64_t)io.down_bytes; *w++ = (int64_t)total;
+    }
     return JMID_OK;
 }
 

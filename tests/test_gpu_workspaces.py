@@ -189,6 +189,40 @@ def test_scene_chain_small_large_small(fresh, precision):
     assert all(same(a, b) for a, b in zip(*per_mode)), "host- and device-mode results differ"
 
 
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_chain_kinds_in_sequence_equal_fresh_handles(fresh, precision):
+    """predict on host arrays -> build_scene(first_frame=) + forecast_scene_padded(seed=) -> build_scene + predict_scene on the episodes
+    of equal count -> predict on host arrays again, on ONE handle: every kind of chain lays the same pinned and device block out its own
+    way (with and without the host inputs, the assembled arrays, sel / logw, first_index), and each result must be what the same call
+    gives on a handle that has run nothing else."""
+    E, N, K, T, k = 3, 4, 6, 3, 2
+    host_in = encoder_inputs(E, N, K, T, 61)
+    hum, rob = random_positions(E, N, 7, half_width=2.0)
+    # every pedestrian in the cluster but those seen on the last frame alone: counts 3, 2, 3
+    first = np.array([[0, 0, 2, 1, F - 1], [1, F - 1, 0, F - 1, 3], [0, 1, 0, F - 1, 0]], np.int32)
+    ids, pick = [9, 4, 70], [0, 2]
+    x_s = torch.randn([len(pick), K * N, T, 2], generator=torch.Generator().manual_seed(62)).numpy()
+
+    def host_chain(eng):
+        return eng.predict(*host_in, k, dt=DT, precision=precision)
+
+    def padded_forecast(eng):
+        out = eng.build_scene(hum, rob, DT, horizon=T, force_all_in_cluster=True, first_frame=first)
+        assert out["n_in"].tolist() == [3, 2, 3]
+        return eng.forecast_scene_padded(None, k, dt=DT, precision=precision, seed=5, episode_ids=ids, K=K, T=T)
+
+    def scene_chain(eng):
+        out = eng.build_scene(hum[pick], rob[pick], DT, force_all_in_cluster=True)
+        assert out["n_in"].tolist() == [N] * len(pick)
+        return eng.predict_scene(x_s, k, dt=DT, precision=precision)
+
+    steps = (host_chain, padded_forecast, scene_chain, host_chain)
+    one = fresh()
+    for i, step in enumerate(steps):
+        got, want = step(one), step(fresh())
+        assert all(same(a, b) for a, b in zip(got, want)), f"call {i + 1} ({step.__name__}) depends on what ran before it on the handle"
+
+
 # ------------------------------------------------------------------------------------------------ 3. the id and count buffers
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_episode_ids_pass_their_capacity(fresh, precision):

@@ -437,3 +437,131 @@ def test_compact_bench_line_always_fits_and_always_parses():
     j = json.loads(line)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline"):
         assert k in j, k
+
+
+# ---- the layouts of a chained call's I/O block and of the scene workspace (csrc/jmid_abi.hip::chain_io, scene_arrays through
+# jmid_dbg_chain_layout; host logic only) ----
+L_SCENE, L_FORECAST, L_SEEDED, L_PADDED, L_FIRST, L_BW, L_POS, L_CV = (1 << i for i in range(8))
+CHAIN_ARRAYS = ("x_st", "nbr_sum", "edge_mask", "x_T", "p0", "bw", "ctx", "flag", "forecasts", "logw_d", "sel", "logw", "pos", "first_index")
+SCENE_ARRAYS = ("human_xy", "robot_xy", "pose_now", "x", "x_st", "nbr_sum", "edge_mask", "p0", "n_in", "in_cluster", "robot_in", "cv", "first_index")
+LAYOUT_ALIGN = 256
+
+
+def _check_block(arrays, total):
+    """arrays {name: (offset, bytes)} of the arrays present: every offset on the rounding rule, no two overlap, the size is the last end"""
+    spans = sorted(arrays.values())
+    assert all(o % LAYOUT_ALIGN == 0 and b > 0 for o, b in spans), arrays
+    assert all(o0 + b0 <= o1 for (o0, b0), (o1, _) in zip(spans, spans[1:])), arrays
+    up = lambda v: -(-v // LAYOUT_ALIGN) * LAYOUT_ALIGN
+    assert total == up(spans[-1][0] + spans[-1][1]), (arrays, total)
+
+
+def _contiguous(arrays, names, start):
+    """the arrays `names` that are present lie one behind the other from `start`, each rounded up -> the end"""
+    for n in names:
+        if n in arrays:
+            assert arrays[n][0] == start, (n, arrays, start)
+            start += -(-arrays[n][1] // LAYOUT_ALIGN) * LAYOUT_ALIGN
+    return start
+
+
+@pytest.mark.parametrize("dims", [(1, 1, 2, 1, 1), (3, 5, 20, 12, 7)], ids=["e1a1k2t1n1", "e3a5k20t12n7"])
+def test_chain_and_scene_layouts(dims):
+    """Every mode combination of the chained entries at two shapes (hist_len 6, ctx_dim 32): 256-byte offsets, no overlap, the upload
+    arrays the contiguous prefix in their order, the download arrays one contiguous range (ending behind the assembled arrays of a
+    forecast), the bytes of include/jmid_hip.h's shapes, the size = the last end, the pinned block = upload + download at the same inner
+    offsets; the combinations no entry makes are refused.  The scene workspace likewise, the grid block its first bytes."""
+    import ctypes as C
+    import itertools
+    import __graft_entry__ as graft
+    from safe_interactive_crowdnav_amd import _lib
+    from safe_interactive_crowdnav_amd.build import LIB_DIAG
+    graft.build()
+    lib = _lib.load_library(LIB_DIAG)
+    E, A, K, T, N = dims
+    Th, ctx_dim = 6, 32
+    n_chain, n_scene = 2 * len(CHAIN_ARRAYS) + 5, 2 * len(SCENE_ARRAYS) + 4
+
+    def layout(k, flags):
+        dev, pin, scn = (C.c_int64 * n_chain)(), (C.c_int64 * n_chain)(), (C.c_int64 * n_scene)()
+        rc = lib.jmid_dbg_chain_layout(Th, ctx_dim, E, A, K, T, k, N, flags, dev, pin, scn)
+        if rc:
+            return None
+
+        def block(words, names):
+            arrays = {n: (words[2 * i], words[2 * i + 1]) for i, n in enumerate(names)}
+            assert all((o == -1) == (b == 0) for o, b in arrays.values()), arrays
+            return {n: v for n, v in arrays.items() if v[1]}, list(words[2 * len(names):])
+        return block(dev, CHAIN_ARRAYS), block(pin, CHAIN_ARRAYS), block(scn, SCENE_ARRAYS)
+
+    n_valid = 0
+    for scene, forecast, seeded, padded, first, (k, bw) in itertools.product(*[(False, True)] * 5, ((1, True), (1, False), (K, False))):
+        rank = k < K
+        for pos in ((False, True) if rank and not forecast else (not forecast,)):
+            flags = (scene * L_SCENE | forecast * L_FORECAST | seeded * L_SEEDED | padded * L_PADDED | first * L_FIRST | bw * L_BW | pos * L_POS
+                     | forecast * L_CV)
+            got = layout(k, flags)
+            if not scene and (forecast or seeded or first):
+                assert got is None, "forecast, seeded noise and first_index exist in scene mode only"
+                continue
+            assert got is not None, (dims, k, flags)
+            n_valid += 1
+            (dev, (up_off, up_bytes, down_off, down_bytes, total)), (pin, (p_up_off, p_up_bytes, p_down_off, p_down_bytes, p_total)), _ = got
+            EA, f4 = E * A, 4
+            want = {"x_st": EA * Th * 6 * f4, "nbr_sum": EA * 2 * Th * 6 * f4, "edge_mask": EA * 2 * f4, "x_T": E * K * A * T * 2 * f4, "p0": EA * 2 * f4,
+                    "ctx": EA * ctx_dim * f4, "flag": 4}
+            if rank and bw:
+                want["bw"] = T * f4
+            if forecast:
+                want.update(forecasts=E * N * k * (T + 1) * 2 * 8, logw_d=E * N * k * 8)
+            if rank:
+                want.update(sel=EA * k * T * 2 * f4, logw=EA * k * f4)
+            if pos:
+                want["pos"] = E * K * A * T * 2 * f4
+            if first:
+                want["first_index"] = EA * 4
+            assert {n: b for n, (_, b) in dev.items()} == want, (dims, k, flags)
+            _check_block(dev, total)
+            # the upload block: the prefix, in the stated order; ctx behind it; then the download block
+            upload, download = ("x_st", "nbr_sum", "edge_mask", "x_T", "p0", "bw"), ("flag", "forecasts", "logw_d", "sel", "logw", "pos")
+            assert up_off == 0 and _contiguous(dev, upload, 0) == up_bytes == dev["ctx"][0]
+            assert _contiguous(dev, ("ctx",), up_bytes) == down_off
+            end = _contiguous(dev, download, down_off)
+            if forecast:      # the one copy ends behind the assembled arrays; sel / logw stay on the device
+                assert down_off + down_bytes == _contiguous(dev, download[:3], down_off) <= end
+            else:
+                assert down_off + down_bytes == end
+            assert _contiguous(dev, ("first_index",), end) == total
+            # the pinned block: exactly upload + download, the same inner offsets
+            moved = [n for n in upload + (download[:3] if forecast else download) if n in dev]
+            assert sorted(pin) == sorted(moved) and all(pin[n][1] == dev[n][1] for n in moved)
+            _check_block(pin, p_total)
+            assert (p_up_off, p_up_bytes, p_down_off, p_down_bytes, p_total) == (0, up_bytes, up_bytes, down_bytes, up_bytes + down_bytes)
+            for n in moved:
+                inner = (dev[n][0] - up_off, pin[n][0] - p_up_off) if n in upload else (dev[n][0] - down_off, pin[n][0] - p_down_off)
+                assert inner[0] == inner[1], n
+    # per (k, bw, pos): 5 calls that rank or return pos, 3 forecasts.  Host arrays: {uniform, padded} x 5; scene: {x_T, seeded} x {uniform,
+    # padded} x {no first_index, first_index} x (5 + 3)
+    assert n_valid == 2 * 5 + 8 * (5 + 3)
+    # the calls no entry makes
+    assert layout(K, L_SCENE) is None and layout(K, 0) is None                      # k == K needs pos_out
+    assert layout(1, L_SCENE | L_FORECAST) is None                                  # a forecast needs the scene's cv
+    assert layout(1, L_SCENE | L_FORECAST | L_CV | L_POS) is None                   # ... and downloads no pos
+    assert layout(K + 1, L_POS) is None and layout(0, L_POS) is None
+
+    # the scene workspace, with and without cv and first_index
+    for cv, first in itertools.product((False, True), repeat=2):
+        _, _, (scn, (grid_bytes, down_off, down_bytes, total)) = layout(K, L_SCENE | L_POS | cv * L_CV | first * L_FIRST)
+        rows = E * N
+        want = {"human_xy": E * Th * N * 2 * 8, "robot_xy": E * Th * 2 * 8, "pose_now": rows * 2 * 8, "x": rows * Th * 6 * 4, "x_st": rows * Th * 6 * 4,
+                "nbr_sum": rows * 2 * Th * 6 * 4, "edge_mask": rows * 2 * 4, "p0": rows * 2 * 4, "n_in": E * 4, "in_cluster": rows, "robot_in": E}
+        if cv:
+            want["cv"] = rows * T * 2 * 8
+        if first:
+            want["first_index"] = rows * 4
+        assert {n: b for n, (_, b) in scn.items()} == want
+        _check_block(scn, total)
+        assert _contiguous(scn, SCENE_ARRAYS[:3], 0) == grid_bytes                  # its first bytes: the grid block's three arrays
+        assert _contiguous(scn, SCENE_ARRAYS[3:8], grid_bytes) == down_off
+        end = _contiguous(scn, SCENE_ARRAYS[8:12], down_off)
+        assert down_off + down_bytes == end and _contiguous(scn, SCENE_ARRAYS[12:], end) == total
