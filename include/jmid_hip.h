@@ -388,13 +388,29 @@ int jmid_scene_get(jmid_handle_t h, float* x, float* x_st, float* nbr_sum, float
  * JMID_EINVAL (the resident scene is kept): a first_frame outside 0..F-1, a robot with fewer than 2 frames while force_all_in_cluster is
  * 0, and every refusal of jmid_build_scene.
  * Raw-stamp input, with gaps inside a track's span interpolated: jmid_build_scene_stamped_var (jmid_build_scene_stamped still ends in
- * JMID_EHISTORY below hist_len grid frames).  Not covered: tracks that end before the last frame (leave those out of the scene). */
+ * JMID_EHISTORY below hist_len grid frames).  A track that ends before the last frame: jmid_build_scene_absent (left out), or coasted
+ * from raw frames by jmid_build_scene_stamped_coast.  This entry keeps refusing a negative first_frame. */
 int jmid_build_scene_var(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, const int32_t* first_frame,
                          double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out,
                          int* n_in_out, double* cv_out, int mem);
 
-/* first_index [E, N] int32 of the resident scene, in its padded layout (all zero after a build without first_frame).  JMID_EINVAL without
- * a resident scene. */
+/* jmid_build_scene_var for episodes in which some pedestrians are NOT IN THE SCENE: the same arguments, and first_frame[e, 1 + j] may be -1
+ * (never the robot's entry).  "Not there" is the reference's own treatment of a node without data at the current frame (edge scaling is
+ * zero where not adjacent now, a NaN distance is not <= radius, present_nodes does not list it), so pedestrian j of episode e
+ *   - is never read (his positions may be anything), is no candidate of the cluster choice and no member of a cluster mean,
+ *   - is no graph node, nobody's neighbour and no ego row: in_cluster_out 0, not counted in n_in_out,
+ *   - has NaN in every float row of his: x, x_st, nbr_sum, edge_mask, p0 (jmid_scene_get), cv_out; first_index -1,
+ *   - gets NaN forecast rows (the prepended pose included) and a NaN log-weight row from jmid_forecast_scene and its forms,
+ * and every output of every other track is bit for bit what jmid_build_scene_var leaves for the episode with his column removed - so a
+ * batch whose episodes see different pedestrians keeps ONE N.  Every chained entry works on the scene unchanged.  Without a -1 every
+ * byte is jmid_build_scene_var's.  JMID_EINVAL (the resident scene is kept): an episode in which every pedestrian is -1
+ * (jmid_last_error names it), a NULL first_frame, and every refusal of jmid_build_scene_var. */
+int jmid_build_scene_absent(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, const int32_t* first_frame,
+                            double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out,
+                            int* n_in_out, double* cv_out, int mem);
+
+/* first_index [E, N] int32 of the resident scene, in its padded layout (all zero after a build without first_frame; -1: a pedestrian
+ * who is not in the scene, jmid_build_scene_absent).  JMID_EINVAL without a resident scene. */
 int jmid_scene_get_first_index(jmid_handle_t h, int32_t* out, int mem);
 
 /* jmid_predict on the resident scene: the in-cluster rows are gathered on the device in ascending track id, then encoder -> denoise loop ->
@@ -451,11 +467,34 @@ int jmid_build_scene_stamped(jmid_handle_t h, int E, int N, int R, const double*
  *   JMID_EINVAL    a pedestrian is not seen in the anchor frame (first_frame_out -1; jmid_last_error names the episode and the track): the
  *                  resident scene cannot hold a node that is absent now - leave the track out of the call, as for an empty cluster;
  *                  and every refusal of jmid_build_scene_stamped.
- * Not covered: absent-now nodes inside the scene, tracks that end early with an extrapolated forecast. */
+ * A pedestrian who is not seen now, left out or coasted instead of refused: jmid_build_scene_stamped_coast. */
 int jmid_build_scene_stamped_var(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
                                  const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
                                  uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int32_t* first_frame_out,
                                  int mem);
+
+/* jmid_build_scene_stamped_var that never refuses a pedestrian who is not seen in the anchor frame: he is COASTED to it or LEFT OUT of the
+ * scene (jmid_build_scene_absent's -1).  The arguments of jmid_build_scene_stamped_var and
+ *   max_coast  0 .. hist_len-2   the bins a track may be extrapolated over; 0: leave out whoever is not seen in the anchor's bin
+ *   coast_out  [E, N] int32 or NULL   0: seen in the anchor frame; b_new > 0: coasted over b_new bins; -1: left out
+ * One definition, shared with scene.py::frame_table_tracks(max_coast=) (fp64, no FMA).  b_new(j) is pedestrian j's newest filled bin:
+ *   - seen in the anchor frame: everything as jmid_build_scene_stamped_var has it, coast 0
+ *   - no filled bin, b_new > max_coast or b_new > n_grid-1: left out - first_frame -1, his column and pose_now NaN, coast -1
+ *   - otherwise coasted: the bins b >= b_new of his column by rule 4 of jmid_build_scene_stamped_var; the bins b < b_new are
+ *     y(b) = y(b_new) + (double)(b_new - b) * step with step = y(b_new) - y(b_new + 1) when the grid row b_new + 1 exists in his window
+ *     (b_new + 1 <= min(b_old, n_grid-1); real or interpolated) and 0 otherwise (one observation: the position repeated);
+ *     first_frame by the formula of rule 5, pose_now = y(0), coast = b_new (0: seen in the anchor's bin, not in the anchor frame)
+ * Then exactly jmid_build_scene_absent on that grid and first_frame.  A coasted pedestrian is an ordinary node: a network forecast when
+ * he is in the cluster with two grid rows, his constant-velocity row otherwise, his coasted pose prepended.  When the anchor frame
+ * sees everybody every byte is jmid_build_scene_stamped_var's.
+ * n_grid_out, first_frame_out and coast_out are filled before the refusals that follow the kernel; the resident scene is kept by all:
+ *   JMID_EHISTORY  an episode has n_grid < 2
+ *   JMID_EINVAL    max_coast outside 0..hist_len-2 (nothing is filled); an episode with nobody left (jmid_last_error names it); and every
+ *                  refusal of jmid_build_scene_stamped. */
+int jmid_build_scene_stamped_coast(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
+                                   const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
+                                   uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int32_t* first_frame_out,
+                                   int max_coast, int32_t* coast_out, int mem);
 
 /* The grid the resident scene was built from and its pose_now, as doubles: human_xy [E, F, N, 2], robot_xy [E, F, 2] (the frame table of
  * mid_sim_wrapper.py:244-298 after jmid_build_scene_stamped; the caller's own input after a plain jmid_build_scene) and pose_now [E, N, 2]

@@ -35,9 +35,22 @@
 // interpolation, reads the coordinates where they lie and writes its two doubles - every output element once, plain vector stores, a
 // fixed order.  frames_kernel itself is untouched.
 //
+// track_frames_coast_kernel: track_frames_kernel for pedestrians who are not seen in the anchor frame (jmid_build_scene_stamped_coast;
+// the device twin of scene.py::frame_table_tracks(max_coast=), in its operation order).  One lane per track scans its ballot word for
+// its newest and oldest filled bin, b_new and b_old:
+//   * seen in the anchor frame: everything as in track_frames_kernel, coast 0
+//   * no filled bin, b_new > max_coast or b_new > n_grid-1: left out - first_frame -1, column and pose_now NaN, coast -1
+//   * otherwise COASTED: the bins b >= b_new by rule 4 above (bin b_new is filled, so an empty bin behind it has both ends); the bins
+//     b < b_new are y(b) = y(b_new) + (double)(b_new - b) * step, step = y(b_new) - y(b_new + 1) when the grid row b_new + 1 exists in
+//     the track's window (b_new + 1 <= min(b_old, n_grid-1); real or interpolated), 0 otherwise - fp64, no FMA contraction;
+//     first_frame by the same formula, pose_now = y(0), coast = b_new
+// The (track, row) lanes of the bins < b_new evaluate rule 4 at b_new and b_new + 1 themselves: every output element is still written
+// once, by one lane.  track_frames_kernel and frames_kernel are untouched.
+//
 // assemble_kernel: the device twin of scene.py::assemble_forecasts (mid_sim_wrapper.py:493-510, :444-454): one thread per
 // (episode, pedestrian, kept sample) writes its (T + 1) x 2 doubles of forecasts [E, N, k, T+1, 2] and its double of logw [E, N, k].
-// Copies and exact fp32 -> fp64 widenings only; plain vector stores, no atomics, a fixed order: bit-reproducible.
+// Copies and exact fp32 -> fp64 widenings only; plain vector stores, no atomics, a fixed order: bit-reproducible.  A track whose resident
+// first_index is -1 (not in the scene) gets NaN in its forecast rows, the prepended pose included, and in its log-weight row.
 #pragma once
 #include "common.hpp"
 #include "scene.hpp"
@@ -310,6 +323,183 @@ inline hipError_t launch_track_frames(const TrackFramesArgs& g, hipStream_t st) 
     return hipGetLastError();
 }
 
+struct TrackCoastArgs : TrackFramesArgs {
+    int* o_coast;                 // [E, N]   0: seen in the anchor frame; b_new: coasted over b_new bins; -1: left out
+    int max_coast;                // 0 .. F-2
+};
+
+// TrackFramesLds and every track's newest filled bin (-1: no column) and min(oldest filled bin, n_grid-1); entry N = the robot
+struct TrackCoastLds : TrackFramesLds {
+    int b_new[SCN_LANES];
+    int b_old[SCN_LANES];
+};
+
+// Rule 4 for one bin of one track (m: its seen set, q: its column group; tc: where the raw coordinates lie): the last sorted seen frame of
+// bin b, or the interpolation between the nearest filled older and newer bin, or NaN where one of the two is missing
+struct TrackCols {
+    const double *hum, *rob;
+    int N, n;
+    long long nb;
+};
+
+static __device__ inline void track_bin_value(const TrackFramesLds& s, const TrackCols& tc, unsigned long long m, int q, long long b, double* y) {
+#pragma clang fp contract(off)
+    const int N = tc.N, n = tc.n;
+    auto val = [&](int r, int c) -> double { return q < N ? tc.hum[((size_t)r * N + q) * 2 + c] : tc.rob[r * 2 + c]; };
+    int hit = -1;
+    long long bo = -1, bn = -1;                               // the track's nearest filled older / newer bin
+    for (int j = 0; j < n; ++j) {
+        if (!((m >> j) & 1ull)) continue;
+        const long long bj = s.bin[j];
+        if (bj == b && (hit < 0 || s.t[j] >= s.t[hit])) hit = j;
+        if (bj > b && (bo < 0 || bj < bo)) bo = bj;
+        if (bj < b && bj > bn) bn = bj;
+    }
+    y[0] = y[1] = __builtin_nan("");
+    if (hit >= 0) {
+        y[0] = val(hit, 0);
+        y[1] = val(hit, 1);
+    } else if (bo >= 0 && bn >= 0) {
+        int jo = -1, jn = -1;                                 // their last frames
+        for (int j = 0; j < n; ++j) {
+            if (!((m >> j) & 1ull)) continue;
+            if (s.bin[j] == bo && (jo < 0 || s.t[j] >= s.t[jo])) jo = j;
+            if (s.bin[j] == bn && (jn < 0 || s.t[j] >= s.t[jn])) jn = j;
+        }
+        const double x0 = (double)(tc.nb - 1 - bo), x1 = (double)(tc.nb - 1 - bn), x = (double)(tc.nb - 1 - b);
+        for (int c = 0; c < 2; ++c) {
+            const double y0 = val(jo, c), y1 = val(jn, c);
+            const double slope = (y1 - y0) / (x1 - x0);
+            y[c] = slope * (x - x0) + y0;
+        }
+    }
+}
+
+static __global__ __launch_bounds__(SCN_LANES) void track_frames_coast_kernel(TrackCoastArgs g) {
+#pragma clang fp contract(off)
+    __shared__ TrackCoastLds s;
+    const int i = threadIdx.x, e = blockIdx.x;
+    const int N = g.N, R = g.R, F = g.F;
+    const int n = g.n_frames ? g.n_frames[e] : R;
+    if (n < 1 || n > R) {                                     // (uniform: the whole wavefront leaves)
+        if (i == 0) g.o_n_grid[e] = -1;
+        return;
+    }
+    const double* st = g.stamps + (size_t)e * R;
+    const double* hum = g.human_xy + (size_t)e * R * N * 2;
+    const double* rob = g.robot_xy + (size_t)e * R * 2;
+    double* oh = g.o_human + (size_t)e * F * N * 2;
+    double* orb = g.o_robot + (size_t)e * F * 2;
+    // steps 2-3 of track_frames_kernel: lane i holds raw frame i; the kept frames, the seen sets, the anchor and the shared bins
+    bool kept = false;
+    if (i < n) {
+        const double ts = st[i], rx = rob[i * 2], ry = rob[i * 2 + 1];
+        kept = ts == ts && rx == rx && ry == ry;
+        s.t[i] = ts;
+    }
+    const unsigned long long keep = __ballot(kept);
+    for (int q = 0; q < N; ++q) {
+        bool here = false;
+        if (kept) {
+            const double x = hum[((size_t)i * N + q) * 2], y = hum[((size_t)i * N + q) * 2 + 1];
+            here = x == x && y == y;
+        }
+        const unsigned long long m = __ballot(here);
+        if (i == 0) s.seen[q] = m;
+    }
+    if (i == 0) s.seen[N] = keep;
+    __syncthreads();
+    int n_grid = 0, last = -1;
+    long long nb = 0;
+    if (keep) {
+        for (int j = 0; j < n; ++j)
+            if (((keep >> j) & 1ull) && (last < 0 || s.t[j] >= s.t[last])) last = j;
+        const long long ns_last = (long long)trunc(s.t[last] * 100.0);
+        if (i < n) {
+            long long b = -1;
+            if (kept) {
+                const long long a = ns_last - (long long)trunc(s.t[i] * 100.0);
+                b = a / g.w;
+                if (a % g.w != 0 && a < 0) --b;               // floor division (a >= 0 for sorted stamps; w >= 1)
+            }
+            s.bin[i] = b;
+        }
+        __syncthreads();
+        for (int j = 0; j < n; ++j)
+            if (s.bin[j] + 1 > nb) nb = s.bin[j] + 1;
+        n_grid = nb < (long long)F ? (int)nb : F;
+    }
+    // every track's newest and oldest filled bin, by the lane of its number: a column for a track seen in the anchor frame (b_new 0)
+    // and for one whose newest bin is at most max_coast bins back and inside the window
+    if (i <= N) {
+        int bw = -1, bl = -1;
+        if (last >= 0) {
+            const unsigned long long m = s.seen[i];
+            long long mn = -1, mx = -1;
+            for (int j = 0; j < n; ++j) {
+                if (!((m >> j) & 1ull)) continue;
+                const long long bj = s.bin[j];
+                if (mn < 0 || bj < mn) mn = bj;
+                if (bj > mx) mx = bj;
+            }
+            const bool anchor = (m >> last) & 1ull;
+            if (mn >= 0 && (anchor || (mn <= (long long)g.max_coast && mn <= (long long)(n_grid - 1)))) {
+                bw = (int)mn;
+                bl = (int)(mx < (long long)(n_grid - 1) ? mx : (long long)(n_grid - 1));
+            }
+        }
+        s.b_new[i] = bw;
+        s.b_old[i] = bl;
+    }
+    __syncthreads();
+    // one (column group, row) per lane and pass; row p holds bin F-1-p.  NaN: a track without a column, a bin older than its oldest
+    const TrackCols tc{hum, rob, N, n, nb};
+    const double nan = __builtin_nan("");
+    for (int u = i; u < (N + 1) * F; u += SCN_LANES) {
+        const int q = u / F, p = u % F;
+        const int b = F - 1 - p, bw = s.b_new[q], bl = s.b_old[q];
+        const unsigned long long m = last < 0 ? 0ull : s.seen[q];
+        double y[2] = {nan, nan};
+        if (bw >= 0 && b <= bl) {
+            if (b >= bw) {
+                track_bin_value(s, tc, m, q, b, y);
+            } else {
+                double y0[2], y1[2];
+                track_bin_value(s, tc, m, q, bw, y0);
+                const bool moving = bw + 1 <= bl;             // (uniform per track: its lanes agree)
+                if (moving) track_bin_value(s, tc, m, q, bw + 1, y1);
+                for (int c = 0; c < 2; ++c) {
+                    const double step = moving ? y0[c] - y1[c] : 0.0;
+                    y[c] = y0[c] + (double)(bw - b) * step;
+                }
+            }
+        }
+        double* o = q < N ? oh + ((size_t)p * N + q) * 2 : orb + p * 2;
+        o[0] = y[0];
+        o[1] = y[1];
+        // pose_now by the lane of the track's newest row: the last pushed frame for a track seen in the anchor frame, as track_frames_kernel
+        // has it; the coasted position, or NaN, for the others
+        if (q < N && p == F - 1) {
+            const bool anchor = last >= 0 && ((m >> last) & 1ull);
+            double* po = g.o_pose + ((size_t)e * N + q) * 2;
+            po[0] = anchor ? hum[((size_t)(n - 1) * N + q) * 2] : y[0];
+            po[1] = anchor ? hum[((size_t)(n - 1) * N + q) * 2 + 1] : y[1];
+        }
+    }
+    // first_frame and coast: lane q for pedestrian q, lane N for the robot
+    if (i <= N) {
+        const int f = i == N ? F - n_grid : s.b_new[i] < 0 ? -1 : F - 1 - s.b_old[i];
+        g.o_first[(size_t)e * (N + 1) + (i == N ? 0 : i + 1)] = f;
+        if (i < N) g.o_coast[(size_t)e * N + i] = s.b_new[i];
+    }
+    if (i == 0) g.o_n_grid[e] = n_grid;
+}
+
+inline hipError_t launch_track_frames_coast(const TrackCoastArgs& g, hipStream_t st) {
+    hipLaunchKernelGGL(track_frames_coast_kernel, dim3(g.E), dim3(SCN_LANES), 0, st, g);
+    return hipGetLastError();
+}
+
 struct AssembleArgs {
     const unsigned char* in_cluster;      // [E, N]
     const float* src;                     // k < K: sel [E, A, k, T, 2]; k == K: pos [E, K, A, T, 2]
@@ -321,6 +511,7 @@ struct AssembleArgs {
     double logw_full;                     // k == K: log(1 / K), computed on the host
     size_t pose_stride;
     int E, N, A, k, T, full;
+    const int* first_index;               // [E, N] the resident scene's, or null; -1: not in the scene, NaN rows
 };
 
 constexpr int ASM_THREADS = 256;
@@ -332,6 +523,12 @@ static __global__ __launch_bounds__(ASM_THREADS) void assemble_kernel(AssembleAr
     const int j = (int)(idx % k), n = (int)((idx / k) % N), e = (int)(idx / ((size_t)k * N));
     const unsigned char* inc = g.in_cluster + (size_t)e * N;
     double* o = g.forecasts + idx * (size_t)(T + 1) * 2;
+    if (g.first_index && g.first_index[(size_t)e * N + n] < 0) {
+        const double nan = __builtin_nan("");
+        for (int q = 0; q < (T + 1) * 2; ++q) o[q] = nan;
+        g.logw[idx] = nan;
+        return;
+    }
     const double* pose = g.pose + (size_t)e * g.pose_stride + (size_t)n * 2;
     o[0] = pose[0];
     o[1] = pose[1];

@@ -173,6 +173,7 @@ int assemble_forecasts(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
     aa.logw = r.dev.logw_d;
     aa.logw_full = std::log(1.0 / (double)c.K);
     aa.E = c.E; aa.N = sc.N; aa.A = c.A; aa.k = c.k; aa.T = c.T; aa.full = c.rank() ? 0 : 1;
+    aa.first_index = sc.arr.first_index;                      // (null for a scene without one) -1: the track's rows are NaN
     if (launch_assemble(aa, h->stream) != hipSuccess) return fail(h, JMID_EHIP, std::string(c.who) + ": assemble launch failed");
     return 0;
 }
@@ -816,7 +817,18 @@ static SceneBuild scene_build(const char* who, int E, int N, int F, double time_
     return b;
 }
 
-// jmid_build_scene and jmid_build_scene_var (first_frame given): every refusal comes before the resident scene is touched
+// the refusal jmid_build_scene_absent and jmid_build_scene_stamped_coast share: an episode whose pedestrians are all -1 (-1: none)
+static int episode_with_nobody(const int32_t* first_frame, int E, int N) {
+    for (int e = 0; e < E; ++e) {
+        int left = 0;
+        for (int j = 1; j <= N; ++j) left += first_frame[(size_t)e * (N + 1) + j] >= 0 ? 1 : 0;
+        if (!left) return e;
+    }
+    return -1;
+}
+
+// jmid_build_scene, jmid_build_scene_var (first_frame given) and jmid_build_scene_absent (-1 allowed for a pedestrian): every refusal
+// comes before the resident scene is touched
 static int build_scene_entry(jmid_handle_t h, SceneBuild b) {
     if (!h) return JMID_EINVAL;
     const std::string who(b.who);
@@ -826,11 +838,16 @@ static int build_scene_entry(jmid_handle_t h, SceneBuild b) {
         for (int e = 0; e < b.E; ++e)
             for (int j = 0; j <= b.N; ++j) {
                 const int f = b.first_frame[(size_t)e * (b.N + 1) + j];
-                if (f < 0 || f > b.F - 1)
+                if ((f < 0 && !(b.allow_absent && j > 0 && f == -1)) || f > b.F - 1)
                     return fail(h, JMID_EINVAL, who + ": first_frame[" + std::to_string(e) + ", " + std::to_string(j) + "] = " + std::to_string(f) + " is outside 0..F-1");
                 if (j == 0 && f > b.F - 2 && !b.force_all_in_cluster)
                     return fail(h, JMID_EINVAL, who + ": the robot of episode " + std::to_string(e) + " has fewer than 2 frames");
             }
+    if (b.allow_absent) {
+        if (!b.first_frame) return fail(h, JMID_EINVAL, who + ": null first_frame");
+        const int e = episode_with_nobody(b.first_frame, b.E, b.N);
+        if (e >= 0) return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(e) + " has no pedestrian left (every first_frame is -1)");
+    }
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, b.mem)) return rc;
     b.src = b.mem == JMID_MEM_HOST ? SCENE_HOST_ARRAYS : SCENE_DEVICE_ARRAYS;
@@ -851,6 +868,15 @@ int jmid_build_scene_var(jmid_handle_t h, int E, int N, int F, const double* hum
                          double* cv_out, int mem) {
     SceneBuild b = scene_build("jmid_build_scene_var", E, N, F, time_step, horizon, force_all_in_cluster, mem);
     b.human_xy = human_xy; b.robot_xy = robot_xy; b.first_frame = first_frame;
+    b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
+    return build_scene_entry(h, b);
+}
+
+int jmid_build_scene_absent(jmid_handle_t h, int E, int N, int F, const double* human_xy, const double* robot_xy, const int32_t* first_frame,
+                            double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out, uint8_t* robot_in_cluster_out,
+                            int* n_in_out, double* cv_out, int mem) {
+    SceneBuild b = scene_build("jmid_build_scene_absent", E, N, F, time_step, horizon, force_all_in_cluster, mem);
+    b.human_xy = human_xy; b.robot_xy = robot_xy; b.first_frame = first_frame; b.allow_absent = true;
     b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
     return build_scene_entry(h, b);
 }
@@ -885,9 +911,13 @@ struct StampedFrames {
     const int* n_frames;
     int* n_grid_out;
     int32_t* first_frame_out;      // tracks only, or null
+    bool coast = false;            // tracks only: track_frames_coast_kernel - a pedestrian who is not seen in the anchor frame is coasted over at
+    int max_coast = 0;             // most max_coast bins or left out (first_frame -1, which the build then takes), never refused; coast [E, N]
+    int32_t* coast_out = nullptr;  // joins the one download; or null
 };
 
-// jmid_build_scene_stamped and jmid_build_scene_stamped_var: b states everything but the source, which is the grid block made here
+// jmid_build_scene_stamped, jmid_build_scene_stamped_var and jmid_build_scene_stamped_coast: b states everything but the source, which is
+// the grid block made here
 static int build_scene_stamped_entry(jmid_handle_t h, SceneBuild b, const StampedFrames& s) {
     if (!h) return JMID_EINVAL;
     const std::string who(b.who);
@@ -897,6 +927,8 @@ static int build_scene_stamped_entry(jmid_handle_t h, SceneBuild b, const Stampe
     if (R < 1 || R > FRM_MAX_R) return fail(h, JMID_EINVAL, who + " supports 1 <= R <= 64 raw frames");
     const int F = b.F = h->hist_len;
     if (int rc = check_scene_dims(h, b.who, N, F, b.cv_out, b.horizon, b.time_step)) return rc;
+    if (s.coast && (s.max_coast < 0 || s.max_coast > F - 2))
+        return fail(h, JMID_EINVAL, who + ": max_coast = " + std::to_string(s.max_coast) + " is outside 0..F-2");
     // w = round(time_step * 100) as Python rounds it (to nearest, ties to even)
     const double wd = std::nearbyint(b.time_step * 100.0);
     if (!(wd >= 1.0) || wd > 9.0e15) return fail(h, JMID_EINVAL, who + ": round(time_step * 100) must be at least 1");
@@ -908,9 +940,9 @@ static int build_scene_stamped_entry(jmid_handle_t h, SceneBuild b, const Stampe
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = order_in(h, mem)) return rc;
     const size_t b_st = (size_t)E * R * 8, b_hum = (size_t)E * R * N * 2 * 8, b_rob = (size_t)E * R * 2 * 8, b_nf = s.n_frames ? (size_t)E * 4 : 0;
-    // the grid block frames_kernel writes | n_grid (tracks: and first_frame [E, N + 1] behind it, one download) | the staged raw frames (host
-    // mode): stamps, human_xy, robot_xy, n_frames
-    const size_t n_first = s.tracks ? (size_t)E * (N + 1) : 0, b_back = ((size_t)E + n_first) * 4;
+    // the grid block frames_kernel writes | n_grid (tracks: and first_frame [E, N + 1] behind it, coast: and coast [E, N] behind that, one
+    // download) | the staged raw frames (host mode): stamps, human_xy, robot_xy, n_frames
+    const size_t n_first = s.tracks ? (size_t)E * (N + 1) : 0, n_coast = s.coast ? (size_t)E * N : 0, b_back = ((size_t)E + n_first + n_coast) * 4;
     const size_t o_ng = grid_block(E, N, F, nullptr, nullptr), o_st = o_ng + align_up(b_back), o_rh = o_st + (host ? align_up(b_st) : 0),
                  o_rr = o_rh + (host ? align_up(b_hum) : 0), o_nf = o_rr + (host ? align_up(b_rob) : 0), need = o_nf + (host ? align_up(b_nf) : 0), raw = need - o_st;
     if (int rc = h->frames_dev.reserve(h, need, b.who)) return rc;
@@ -918,13 +950,14 @@ static int build_scene_stamped_entry(jmid_handle_t h, SceneBuild b, const Stampe
     char *const fd = h->frames_dev.p, *const pin = h->pin.p;
     GridBlock gb;
     grid_block(E, N, F, fd, &gb);
-    TrackFramesArgs t{};
+    TrackCoastArgs t{};
     FramesArgs& f = t;
     f.E = E; f.N = N; f.R = R; f.F = F;
     f.w = (long long)wd;
     f.stamps = s.stamps; f.human_xy = s.human_xy; f.robot_xy = s.robot_xy; f.n_frames = s.n_frames;
     f.o_human = gb.human_xy; f.o_robot = gb.robot_xy; f.o_pose = gb.pose_now; f.o_n_grid = reinterpret_cast<int*>(fd + o_ng);
     t.o_first = f.o_n_grid + E;
+    t.o_coast = t.o_first + n_first; t.max_coast = s.max_coast;
     if (host) {
         std::memcpy(pin, s.stamps, b_st);
         std::memcpy(pin + (o_rh - o_st), s.human_xy, b_hum);
@@ -935,18 +968,21 @@ static int build_scene_stamped_entry(jmid_handle_t h, SceneBuild b, const Stampe
         f.robot_xy = reinterpret_cast<const double*>(fd + o_rr);
         f.n_frames = s.n_frames ? reinterpret_cast<const int*>(fd + o_nf) : nullptr;
     }
-    if (s.tracks) HIPCHK(h, launch_track_frames(t, h->stream));
+    if (s.coast) HIPCHK(h, launch_track_frames_coast(t, h->stream));
+    else if (s.tracks) HIPCHK(h, launch_track_frames(t, h->stream));
     else HIPCHK(h, launch_frames(f, h->stream));
     int* ng = reinterpret_cast<int*>(pin + raw);
     HIPCHK(h, hipMemcpyAsync(ng, f.o_n_grid, b_back, hipMemcpyDeviceToHost, h->stream));
     if (!host) {
         HIPCHK(h, hipMemcpyAsync(s.n_grid_out, f.o_n_grid, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
         if (s.first_frame_out) HIPCHK(h, hipMemcpyAsync(s.first_frame_out, t.o_first, n_first * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (s.coast_out) HIPCHK(h, hipMemcpyAsync(s.coast_out, t.o_coast, n_coast * 4, hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (host) {
         std::memcpy(s.n_grid_out, ng, (size_t)E * 4);
         if (s.first_frame_out) std::memcpy(s.first_frame_out, ng + E, n_first * 4);
+        if (s.coast_out) std::memcpy(s.coast_out, ng + E + n_first, n_coast * 4);
     }
     for (int e = 0; e < E; ++e)
         if (ng[e] < 0) {
@@ -963,7 +999,14 @@ static int build_scene_stamped_entry(jmid_handle_t h, SceneBuild b, const Stampe
         }
     // (build_scene_resident stages through the pinned block again: first_frame leaves it first)
     std::vector<int32_t> first(ng + E, ng + E + n_first);
-    for (size_t q = 0; q < n_first; ++q)
+    if (s.coast) {                                            // a -1 is a pedestrian left out of the scene; somebody has to be left
+        const int e = episode_with_nobody(first.data(), E, N);
+        if (e >= 0) {
+            (void)order_out(h, mem);
+            return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(e) + " has no pedestrian left (nobody is seen within max_coast bins of the newest kept frame)");
+        }
+    }
+    for (size_t q = 0; q < n_first && !s.coast; ++q)
         if (first[q] < 0) {
             (void)order_out(h, mem);
             return fail(h, JMID_EINVAL, who + ": episode " + std::to_string(q / (N + 1)) + ", track " + std::to_string((int)(q % (N + 1)) - 1) +
@@ -990,6 +1033,18 @@ int jmid_build_scene_stamped_var(jmid_handle_t h, int E, int N, int R, const dou
     SceneBuild b = scene_build("jmid_build_scene_stamped_var", E, N, 0, time_step, horizon, force_all_in_cluster, mem);
     b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
     return build_scene_stamped_entry(h, b, StampedFrames{true, R, stamps, human_xy, robot_xy, n_frames, n_grid_out, first_frame_out});
+}
+
+int jmid_build_scene_stamped_coast(jmid_handle_t h, int E, int N, int R, const double* stamps, const double* human_xy, const double* robot_xy,
+                                   const int* n_frames, double time_step, int horizon, int force_all_in_cluster, uint8_t* in_cluster_out,
+                                   uint8_t* robot_in_cluster_out, int* n_in_out, int* n_grid_out, double* cv_out, int32_t* first_frame_out,
+                                   int max_coast, int32_t* coast_out, int mem) {
+    SceneBuild b = scene_build("jmid_build_scene_stamped_coast", E, N, 0, time_step, horizon, force_all_in_cluster, mem);
+    b.in_cluster_out = in_cluster_out; b.robot_in_cluster_out = robot_in_cluster_out; b.n_in_out = n_in_out; b.cv_out = cv_out;
+    b.allow_absent = true;
+    StampedFrames s{true, R, stamps, human_xy, robot_xy, n_frames, n_grid_out, first_frame_out};
+    s.coast = true; s.max_coast = max_coast; s.coast_out = coast_out;
+    return build_scene_stamped_entry(h, b, s);
 }
 
 int jmid_scene_get_frames(jmid_handle_t h, double* human_xy_out, double* robot_xy_out, double* pose_now_out, int mem) {

@@ -411,6 +411,7 @@ struct SceneBuild {
     SceneSource src;
     const double *human_xy, *robot_xy;
     const int32_t* first_frame = nullptr;      // a HOST array [E, N + 1], checked by the entry, or null: uploaded ahead of the kernel, which then leaves first_index
+    bool allow_absent = false;                 // first_frame may hold -1 for a pedestrian (not in the scene; jmid_build_scene_absent, _stamped_coast)
     double time_step = 0.0;
     int horizon = 0, force_all_in_cluster = 0;
     uint8_t *in_cluster_out = nullptr, *robot_in_cluster_out = nullptr;

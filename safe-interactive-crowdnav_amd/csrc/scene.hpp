@@ -27,6 +27,13 @@
 //     still counts in the cluster choice and as a neighbour (present_nodes: min_history_timesteps 1 for the egos, 0 for the graph)
 // With first_frame null every operation and its order are the ones above.
 //
+// A node with no frame (first_frame[1 + j] == -1, jmid_build_scene_absent; never the robot): pedestrian j is NOT IN THE SCENE.  His
+// positions are never read (`here` is false on every frame), he is no candidate of step 3 (his rdist would be 0 / 0, and a NaN is
+// the minimum), no member of a cluster mean (a NaN distance is not < 3), not in `inc` - so no graph node and nobody's neighbour -, no
+// ego row, and his output rows are in_cluster 0, first_index -1, NaN in every float.  Every other lane does what it does when his
+// column is removed: the members are summed in ascending node order and a non-member adds nothing (a neighbour outside `conn` adds
+// +-0 to a sum that started at +0: the bits stay).  A first_frame without -1 takes none of these branches.
+//
 // One workgroup of one wavefront per episode, one lane per node (node 0 the robot, 1 .. N the pedestrians: N + 1 <= 64); the node states
 // are staged in LDS.  The kernel is latency-bound and tiny.  A second kernel gathers the in-cluster rows, in ascending track id, into the
 // dense [E * A, ...] layout the encoder and the integrator read (jmid_predict_scene).
@@ -42,7 +49,8 @@ constexpr int SCN_MAX_H = 24;         // horizon of the constant-velocity foreca
 struct SceneArgs {
     const double* human_xy;       // [E, F, N, 2]
     const double* robot_xy;       // [E, F, 2]
-    const int* first_frame;       // [E, N + 1] first present frame of every node (robot first), 0 .. F-1; null: 0
+    const int* first_frame;       // [E, N + 1] first present frame of every node (robot first), 0 .. F-1; null: 0.  -1 (a pedestrian, the
+                                  // host has checked: not all of an episode's): not in the scene
     int* first_index;             // [E, N] the pedestrians' first_frame, as the encoder reads it (written only with first_frame)
     float* x;                     // [E, N, F, 6]
     float* x_st;                  // [E, N, F, 6]
@@ -77,13 +85,19 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
     const double nan64 = __builtin_nan("");
     for (int q = i; q < F * n * 2; q += SCN_LANES) {
         const int c = q & 1, node = (q >> 1) % n, t = (q >> 1) / n;
-        const bool here = !ffe || t >= ffe[node];
+        const bool here = !ffe || (ffe[node] >= 0 && t >= ffe[node]);
         st(t, node, c) = !here ? nan64 : node == 0 ? rob[t * 2 + c] : hum[((size_t)t * N + (node - 1)) * 2 + c];
     }
     sfirst[i] = ffe && i < n ? ffe[i] : 0;
     __syncthreads();
     // step 4 (every lane its own node, over its own span) and steps 1-2
-    if (i < n) {
+    if (i < n && sfirst[i] < 0) {
+        // no frame: NaN states (the positions are NaN already), near nobody
+        for (int t = 0; t < F; ++t)
+            for (int c = 2; c < 6; ++c) st(t, i, c) = nan64;
+        rdist[i] = nan64;
+        nearm[i] = 0;
+    } else if (i < n) {
         const int f0 = sfirst[i];
         for (int c = 0; c < 2; ++c) {
             if (f0 < F - 1) {
@@ -116,21 +130,25 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
         nearm[i] = m;
     }
     __syncthreads();
-    // step 3: the first minimum over the pedestrians (np.argmin: a NaN counts as the minimum)
+    // step 3: the first minimum over the pedestrians that are in the scene (np.argmin: a NaN counts as the minimum)
     unsigned long long inc = n == 64 ? ~0ull : (1ull << n) - 1;
     if (!g.force_all) {
-        int best = 1;
-        double bv = rdist[1];
-        for (int j = 2; j < n; ++j) {
+        int best = -1;
+        double bv = 0.0;
+        for (int j = 1; j < n; ++j) {
+            if (sfirst[j] < 0) continue;
             const double r = rdist[j];
-            if (bv == bv && (r < bv || r != r)) { bv = r; best = j; }
+            if (best < 0 || (bv == bv && (r < bv || r != r))) { bv = r; best = j; }
         }
-        inc = nearm[best];
+        inc = best < 0 ? 0ull : nearm[best];
+    } else {
+        for (int j = 1; j < n; ++j)
+            if (sfirst[j] < 0) inc &= ~(1ull << j);
     }
     // the ego rows: the in-cluster pedestrians with at least two frames (all of them without first_frame)
     unsigned long long ego = inc & ~1ull;
     for (int j = 1; j < n; ++j)
-        if (sfirst[j] > F - 2) ego &= ~(1ull << j);
+        if (sfirst[j] > F - 2 || sfirst[j] < 0) ego &= ~(1ull << j);
     if (i == 0) {
         g.robot_in[e] = (unsigned char)(inc & 1ull);
         g.n_in[e] = __popcll(ego);
@@ -141,6 +159,15 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
     const int f0 = sfirst[i];
     g.in_cluster[row] = in_me ? 1 : 0;
     if (ffe) g.first_index[row] = f0;
+    const float nan32 = __builtin_nanf("");
+    if (f0 < 0) {                                             // not in the scene: NaN rows
+        for (int q = 0; q < F * 6; ++q) g.x[row * F * 6 + q] = g.x_st[row * F * 6 + q] = nan32;
+        for (int q = 0; q < 2 * F * 6; ++q) g.nbr_sum[row * 2 * F * 6 + q] = nan32;
+        for (int q = 0; q < 2; ++q) g.edge_mask[row * 2 + q] = g.p0[row * 2 + q] = nan32;
+        if (g.cv)
+            for (int q = 0; q < g.horizon * 2; ++q) g.cv[row * g.horizon * 2 + q] = nan64;
+        return;
+    }
     // step 5: this pedestrian's row of the edge scaling, as a mask of connected nodes and the fp32 sum of their values
     unsigned long long conn = 0;
     float ev = 0.0f;
@@ -174,7 +201,6 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
     for (int c = 0; c < 6; ++c) now[c] = st(F - 1, i, c);
     g.p0[row * 2] = (float)now[0];
     g.p0[row * 2 + 1] = (float)now[1];
-    const float nan32 = __builtin_nanf("");
     for (int t = 0; t < F; ++t)
         for (int c = 0; c < 6; ++c) {
             const double v = st(t, i, c);
@@ -183,7 +209,7 @@ static __global__ __launch_bounds__(SCN_LANES) void scene_kernel(SceneArgs g) {
             // every node is added, an unconnected one with weight 0, as the host twin does (the sums start at +0.0)
             float acc_ped = 0.0f, acc_rob = 0.0f;
             for (int j = 0; j < n; ++j) {
-                const float rel = (float)(((t < sfirst[j] ? 0.0 : st(t, j, c)) - now[c]) / std6[c]);
+                const float rel = (float)(((t < sfirst[j] || sfirst[j] < 0 ? 0.0 : st(t, j, c)) - now[c]) / std6[c]);
                 const float w = (conn >> j) & 1ull ? 1.0f : 0.0f;
                 if (j == 0) acc_rob = acc_rob + rel * w;
                 else acc_ped = acc_ped + rel * w;

@@ -419,7 +419,7 @@ class JmidEngine:
         return pos, None
 
     def build_scene(self, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: Optional[int] = None,
-                    force_all_in_cluster: bool = False, first_frame=None) -> Dict[str, np.ndarray]:
+                    force_all_in_cluster: bool = False, first_frame=None, allow_absent: bool = False) -> Dict[str, np.ndarray]:
         """The scene batch on the device (``jmid_build_scene``; the device twin of ``scene.build_scenes_batched``): human_xy [E, F, N, 2]
         and robot_xy [E, F, 2] float64 on the ``time_step`` grid, oldest first - or [F, N, 2] and [F, 2] for one scene, whose results
         then come without the episode axis.  The encoder inputs stay on the device (``scene_arrays`` copies them out, ``predict_scene``
@@ -428,7 +428,10 @@ class JmidEngine:
         ``first_frame`` [E, N + 1] integers, robot first (``jmid_build_scene_var``; ``scene.build_scenes_batched(first_frame=)`` is the
         host twin): node j is present on frames first_frame[j] .. F-1 and its earlier positions are never read.  A pedestrian with a single
         frame is no ego row (``in_cluster`` False, not counted in ``n_in``).  ``scene_arrays`` then returns ``first_index`` as well and
-        ``predict_scene`` / ``forecast_scene`` encode every row from its own first frame."""
+        ``predict_scene`` / ``forecast_scene`` encode every row from its own first frame.
+        ``allow_absent=True`` (``jmid_build_scene_absent``; ``scene.build_scenes_batched(allow_absent=True)`` is the host twin): a
+        pedestrian's ``first_frame`` may be -1 - he is not in the scene of that episode: never read, ``in_cluster`` False, NaN rows in
+        ``scene_arrays``, ``cv`` and the forecasts, ``first_index`` -1, and everybody else as if his column were removed."""
         hum = np.ascontiguousarray(human_xy, dtype=np.float64)
         rob = np.ascontiguousarray(robot_xy, dtype=np.float64)
         single = hum.ndim == 3
@@ -449,8 +452,10 @@ class JmidEngine:
             if not np.issubdtype(ff.dtype, np.integer) or ff.shape != ((N + 1,) if single else (E, N + 1)):
                 raise ValueError("first_frame must hold N + 1 integers per episode, robot first")
             ff = np.ascontiguousarray(ff.reshape(E, N + 1), dtype=np.int32)
-            self._check(self._lib.jmid_build_scene_var(self._h, E, N, F, C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data),
-                                                       C.c_void_p(ff.ctypes.data), *tail))
+            entry = self._lib.jmid_build_scene_absent if allow_absent else self._lib.jmid_build_scene_var
+            self._check(entry(self._h, E, N, F, C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data), C.c_void_p(ff.ctypes.data), *tail))
+        elif allow_absent:
+            raise ValueError("allow_absent needs first_frame")
         else:
             self._check(self._lib.jmid_build_scene(self._h, E, N, F, C.c_void_p(hum.ctypes.data), C.c_void_p(rob.ctypes.data), *tail))
         self._scene_shape, self._scene_n_in = (E, N, F, single), n_in
@@ -526,7 +531,8 @@ class JmidEngine:
 
     def build_scene_stamped(self, stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
                             horizon: Optional[int] = None, force_all_in_cluster: bool = False,
-                            n_frames: Optional[np.ndarray] = None, tracks: bool = False) -> Dict[str, np.ndarray]:
+                            n_frames: Optional[np.ndarray] = None, tracks: bool = False,
+                            max_coast: Optional[int] = None) -> Dict[str, np.ndarray]:
         """``build_scene`` from raw stamped frames (``jmid_build_scene_stamped``; the frame table is the device twin of
         ``scene.frame_table_frames_batched``): stamps [E, R], human_xy [E, R, N, 2], robot_xy [E, R, 2] float64, oldest-pushed first, the
         first ``n_frames[e]`` of each episode valid (None: all R) - or [R], [R, N, 2], [R, 2] for one scene, whose results then come without
@@ -536,8 +542,14 @@ class JmidEngine:
         track - a NaN human coordinate means "not seen in this frame" and drops nothing, a window of 2 .. hist_len-1 grid frames is built
         like ``build_scene(first_frame=)`` - and ``first_frame`` [E, N + 1] int32 (robot first) is returned as well.
         ``HistoryTooShortError`` then means fewer than 2 grid frames; a pedestrian who is not seen in the newest kept frame raises
-        ``scene.TrackAbsentError(episode, track)`` (leave the track out; a scene built before stays resident)."""
+        ``scene.TrackAbsentError(episode, track)`` (leave the track out; a scene built before stays resident).
+        ``max_coast`` = 0 .. hist_len-2 (with ``tracks=True``; ``jmid_build_scene_stamped_coast``, the device twin of
+        ``scene.frame_table_tracks_batched(max_coast=)``): such a pedestrian is coasted to the anchor frame over at most ``max_coast`` bins,
+        or left out of the scene (``first_frame`` -1, NaN rows) - nothing is raised for him, and ``coast`` [E, N] int32 is returned as
+        well (0 seen, b > 0 coasted over b bins, -1 left out).  An episode with nobody left raises ``JmidError`` (JMID_EINVAL)."""
         from .scene import HistoryTooShortError, TrackAbsentError
+        if max_coast is not None and not tracks:
+            raise ValueError("max_coast needs tracks=True")
         st = np.ascontiguousarray(stamps, dtype=np.float64)
         hum = np.ascontiguousarray(human_xy, dtype=np.float64)
         rob = np.ascontiguousarray(robot_xy, dtype=np.float64)
@@ -562,8 +574,12 @@ class JmidEngine:
                 int(horizon) if horizon is not None else 0, int(bool(force_all_in_cluster)),
                 C.c_void_p(inc.ctypes.data), C.c_void_p(rin.ctypes.data), C.c_void_p(n_in.ctypes.data),
                 C.c_void_p(n_grid.ctypes.data), C.c_void_p(cv.ctypes.data) if cv is not None else None)
-        first = None
-        if tracks:
+        first = coast = None
+        if max_coast is not None:
+            first, coast = np.zeros((E, N + 1), dtype=np.int32), np.zeros((E, N), dtype=np.int32)
+            rc = self._lib.jmid_build_scene_stamped_coast(*head, C.c_void_p(first.ctypes.data), int(max_coast), C.c_void_p(coast.ctypes.data),
+                                                          _lib.MEM_HOST)
+        elif tracks:
             first = np.zeros((E, N + 1), dtype=np.int32)
             rc = self._lib.jmid_build_scene_stamped_var(*head, C.c_void_p(first.ctypes.data), _lib.MEM_HOST)
         else:
@@ -572,7 +588,7 @@ class JmidEngine:
             err = HistoryTooShortError(self._lib.jmid_last_error(self._h).decode())
             err.n_grid = n_grid[0] if single else n_grid
             raise err
-        if tracks and rc == _lib.EINVAL and (n_grid >= 2).all() and (first < 0).any():     # the absent-now refusal: both arrays were filled
+        if tracks and coast is None and rc == _lib.EINVAL and (n_grid >= 2).all() and (first < 0).any():     # the absent-now refusal: both arrays were filled
             e, j = (int(v[0]) for v in np.nonzero(first < 0))
             err = TrackAbsentError(e, j - 1, f"JMID_EINVAL: {self._lib.jmid_last_error(self._h).decode()}")
             err.first_frame = first[0] if single else first
@@ -582,6 +598,8 @@ class JmidEngine:
         out = {"in_cluster": inc.astype(bool), "robot_in_cluster": rin.astype(bool), "n_in": n_in, "n_grid": n_grid, "cv": cv}
         if tracks:
             out["first_frame"] = first
+        if coast is not None:
+            out["coast"] = coast
         return {k: (v[0] if single and v is not None else v) for k, v in out.items()}
 
     def scene_frames(self) -> Dict[str, np.ndarray]:

@@ -47,7 +47,10 @@ Differences from the reference that a caller can observe:
     its first frame on as the reference's MODEL does it (``first_history_index``, MID/dataset/preprocessing.py:468);
   * ``track_presence=True`` (opt-in, with ``short_history=True``): ``update_state_hists`` may be fed NaN positions for a pedestrian who is not
     seen.  The reference's table drops such a frame for everybody (``mid_sim_wrapper.py:266``); here every track keeps a window of its own
-    (``scene.frame_table_tracks``), and a pedestrian who is NaN in the newest frame is left out of the call - his rows come back NaN.
+    (``scene.frame_table_tracks``), and a pedestrian who is NaN in the newest frame is left out of the call - his rows come back NaN;
+  * ``coast_frames=c`` > 0 (opt-in, with ``track_presence=True``): such a pedestrian is instead COASTED to the newest frame when he was seen
+    at most c grid bins ago (``scene.frame_table_tracks(max_coast=c)``: his last step repeated, or his position when he was seen once)
+    and forecast like everybody else from there; seen longer ago, he is left out as above.
 """
 from __future__ import annotations
 
@@ -63,7 +66,7 @@ import torch
 import yaml
 
 from . import scene as SC
-from ._lib import ERANGE
+from ._lib import EINVAL, ERANGE
 from .engine import JmidEngine, JmidError
 from .kde import most_likely_samples
 from .weights import JMIDWeights, NetDims
@@ -177,7 +180,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  device_id: Optional[int] = None, precision: Optional[str] = None, rng_compat: Optional[str] = None,
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
                  lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
-                 seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False):
+                 seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False, coast_frames: int = 0):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -216,6 +219,16 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         self.track_presence = bool(track_presence)
         if self.track_presence and not self.short_history:
             raise ValueError("track_presence needs short_history=True (a track that appears mid-run has a short window)")
+        # > 0 (opt-in, needs track_presence): a pedestrian who is NaN in the anchor frame but was seen at most coast_frames grid bins ago is
+        # coasted to it (scene.frame_table_tracks(max_coast=)) - a node like any other: a network forecast in the cluster with two grid
+        # rows, his constant-velocity row otherwise, his coasted pose prepended.  Seen longer ago: left out of the SCENE, not of the
+        # arrays (first_frame -1, jmid_build_scene_absent) - with device_frames all num_hums tracks go to the device as they are
+        # (jmid_build_scene_stamped_coast), nothing is filtered on the host.  0: the host filter above, today's routes and bits
+        self.coast_frames = int(coast_frames)
+        if self.coast_frames and not self.track_presence:
+            raise ValueError("coast_frames needs track_presence=True")
+        if not 0 <= self.coast_frames <= self.num_hist_frames - 2:
+            raise ValueError("coast_frames must lie in 0..past_num_frames-2")
         self.erange_fallbacks = 0
         self.timings: Dict[str, float] = {}     # ms of the last predict_ret_best(): scene, device, topk, assemble
         if rng_compat not in ("auto", "cpu", "cuda", "device"):
@@ -351,6 +364,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         """``_scene`` with ``track_presence`` for histories that are frames: its returns for the pedestrians who are present now, and
         ``present`` [N] bool - the pedestrians seen in the anchor frame (the others are left out; nobody left: HistoryTooShortError)."""
         F, H = self.num_hist_frames, self.predict_horizon
+        if self.coast_frames:
+            return self._scene_coasted(stamps, hum, rob)
         kept = np.nonzero(~(np.isnan(stamps) | np.isnan(rob).any(axis=1)))[0]
         if not len(kept):
             raise SC.HistoryTooShortError("no history frame with a stamp and a robot position")
@@ -370,6 +385,31 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
             ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, H, first_frame=ff)
             return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], pose_now, None, ff, present
         sb = SC.build_scene(hum_xy, rob_xy, self.time_step, H, F, first_frame=ff)
+        return source, sb.ids_in, sb.cv_forecasts, pose_now, sb, ff, present
+
+    def _scene_coasted(self, stamps, hum, rob):
+        """``_scene_tracks`` with ``coast_frames``: every track stays in the arrays (``present`` all True); who is neither seen now nor
+        coasted has first_frame -1 - not in the scene, his rows NaN.  Nobody left: HistoryTooShortError on both routes."""
+        F, H, c = self.num_hist_frames, self.predict_horizon, self.coast_frames
+        present = np.ones(hum.shape[1], dtype=bool)
+        source = scene_source(self.device_scene, self.device_frames, short=True, tracks=True)
+        if source == "stamped":      # all N tracks as raw frames: one build (coasting and leaving out on the device), one chain
+            try:
+                ds = self.engine.build_scene_stamped(stamps, hum, rob, self.time_step, H, tracks=True, max_coast=c)
+            except JmidError as e:
+                if e.code == EINVAL and "no pedestrian left" in str(e):
+                    raise SC.HistoryTooShortError("no pedestrian is seen in, or coasted to, the newest history frame") from e
+                raise
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], None, None, ds["first_frame"], present
+        hum_xy, rob_xy, pose_now, ff, _, _ = SC.frame_table_tracks(stamps, hum, rob, self.time_step, F, max_coast=c)
+        if (ff[1:] < 0).all():
+            raise SC.HistoryTooShortError("no pedestrian is seen in, or coasted to, the newest history frame")
+        if not ff.any():             # everybody on every frame: the bits of a build without first_frame, and its routes
+            ff = None
+        if source == "resident":
+            ds = self.engine.build_scene(hum_xy, rob_xy, self.time_step, H, first_frame=ff, allow_absent=ff is not None)
+            return source, np.nonzero(ds["in_cluster"])[0], ds["cv"], pose_now, None, ff, present
+        sb = SC.build_scene(hum_xy, rob_xy, self.time_step, H, F, first_frame=ff, allow_absent=ff is not None)
         return source, sb.ids_in, sb.cv_forecasts, pose_now, sb, ff, present
 
     def _draw_x_T(self, A: int) -> np.ndarray:
@@ -448,6 +488,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
             full = np.full((self.num_hums,) + result[0].shape[1:], np.nan), np.full((self.num_hums,) + result[1].shape[1:], np.nan)
             full[0][present], full[1][present] = result
             result = full
+        if present is not None and ff is not None and (ff[1:] < 0).any():      # coast_frames: the rows of the pedestrians left out of the scene
+            result[0][ff[1:] < 0], result[1][ff[1:] < 0] = np.nan, np.nan
         t4 = time.perf_counter()
         self.timings = {"scene_ms": 1e3 * (t1 - t0), "device_ms": 1e3 * (t2 - t1), "topk_ms": 1e3 * (t3 - t2),
                         "assemble_ms": 1e3 * (t4 - t3), "total_ms": 1e3 * (t4 - t0)}
@@ -559,7 +601,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
                   device_topk: bool = True, device_scene: bool = False,
                   device_frames: bool = False, noise: str = "torch", seed: int = 0,
-                  padded=False, short_history: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  padded=False, short_history: bool = False, first_frame=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -593,6 +635,12 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     seeded and episode e draws what it draws alone and in its count group; otherwise the torch draws of ``padded=True``.  It combines with
     ``short_history``.  A batch with an empty cluster, or whose ranking does not fit the device top-k, takes the grouped device path
     (``device_frames=True``).
+    ``first_frame`` [E, N + 1] integers, robot first (opt-in; human_xy / robot_xy hold hist_len frames and are never read in front of a
+    node's first frame): every node of every episode with a window of its own, as ``engine.build_scene(first_frame=)`` takes it - it
+    supersedes the common-L padding of ``short_history``.  A pedestrian's entry may be -1: he is NOT IN THE SCENE of that episode
+    (``jmid_build_scene_absent``; not seen now) - the episodes of a batch keep one N, his rows come back NaN in both arrays with
+    ``in_cluster`` False, everybody else as if his column were removed.  On the host route, the grouped device route and
+    ``padded="resident"``; not with ``padded=True``.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
@@ -605,7 +653,15 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         raise ValueError("padded=True takes host scene arrays and torch noise only: not with device_scene, device_frames or noise='device' "
                          "(the padded entries have no scene-resident or seeded form)")
     ff = None                                    # short_history: first_frame [E, N + 1] of the padded windows
-    if short_history and 2 <= human_xy.shape[1] < engine.hist_len:
+    absent = first_frame is not None             # (the builds that take a -1; without one they leave the bits of the others)
+    ab = {"allow_absent": True} if absent else {}
+    if absent:
+        if padded:
+            raise ValueError("first_frame has no padded form (jmid_predict_padded takes no first_index)")
+        if human_xy.shape[1] != engine.hist_len:
+            raise ValueError("first_frame needs hist_len frames in human_xy / robot_xy")
+        ff = SC._check_first_frame(first_frame, human_xy.shape[0], human_xy.shape[2], engine.hist_len, False, allow_absent=True)
+    elif short_history and 2 <= human_xy.shape[1] < engine.hist_len:
         if padded:
             raise ValueError("short_history has no padded form (jmid_predict_padded takes no first_index)")
         parts = [SC.pad_short_window(human_xy[e], robot_xy[e], engine.hist_len) for e in range(human_xy.shape[0])]
@@ -624,7 +680,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
 
     if scene_source(device_scene, device_frames, batch=True, resident=resident) == "resident":
         with lock:                               # the same batch from the device kernel (jmid_build_scene)
-            b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
+            b = engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff, **ab)
             n_in = b["in_cluster"].sum(axis=1)
             if resident and n_in.min() >= 1 and plan(int(n_in.max()), resident=True).run == "chain":
                 # the scene stays where it is: predictor + assembly for every count in one entry
@@ -637,8 +693,11 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             if not device_frames:
                 b.update(engine.scene_arrays())
     else:
-        b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
+        b = SC.build_scenes_batched(human_xy, robot_xy, time_step, horizon=H, first_frame=ff, **ab)
     inc, pose_now = b["in_cluster"], human_xy[:, -1]
+    left_out = ff[:, 1:] < 0 if absent else None      # [E, N] not in the scene: NaN rows
+    if absent:
+        pose_now = np.where(left_out[..., None], np.nan, pose_now)
     n_in = inc.sum(axis=1)
 
     if padded and n_in.min() >= 1 and plan(int(n_in.max()), padded=True).run == "chain":
@@ -661,13 +720,13 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             x_T, nz = torch.stack([torch_x_T(e, A) for e in eps]).numpy(), {}
         if route.run == "chain":
             with lock:              # the group's scenes resident, then predictor + assembly in one entry
-                engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H, first_frame=None if ff is None else ff[eps])
+                engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H, first_frame=None if ff is None else ff[eps], **ab)
                 (forecasts[eps], logw[eps]), _ = repeat_in_fp32(
                     lambda p: engine.forecast_scene(x_T, k, dt=time_step, precision=p, **nz), precision)
             continue
         if "p0" not in b:           # (device_frames built without reading the encoder inputs back)
             with lock:
-                engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff)
+                engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff, **ab)
                 b.update(engine.scene_arrays())
         rows = np.stack([np.nonzero(inc[e])[0] for e in eps])                       # [Eg, A] ascending track ids
         ei, n = eps[:, None], len(eps) * A
@@ -679,6 +738,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
             sel, lw = rank_samples(engine, route.rank, pos, k, (len(eps), A, K, H))
         forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], sel, lw, b["cv"][eps], pose_now[eps], k, K)
+    if absent:
+        forecasts[left_out], logw[left_out] = np.nan, np.nan
     return forecasts, logw, inc
 
 

@@ -183,9 +183,83 @@ class TrackAbsentError(ValueError):
         self.episode, self.track = int(episode), int(track)
 
 
-def _track_table(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, F: int):
+def _track_column(k: np.ndarray, nb: int, n_grid: int, F: int, seen: np.ndarray, y: np.ndarray, b_new: int = 0):
+    """One track's column [F, 2] of the per-track frame table and its oldest filled bin b_old: k [n] the shared bins of the kept frames
+    in sorted order, seen [n] bool where the track is seen, y [n, 2] its positions; ``b_new`` its newest filled bin (0: the anchor's).
+    The bins b_new .. min(b_old, n_grid-1) are written, the rows of the others stay NaN."""
+    ks = np.where(seen, k, -1)
+    b_old = int(ks.max())
+    col = np.full((F, 2), np.nan)
+    for b in range(b_new, min(b_old, n_grid - 1) + 1):
+        hit = np.nonzero(ks == b)[0]
+        if len(hit):
+            col[F - 1 - b] = y[hit[-1]]              # the LAST sorted seen frame of the bin
+            continue
+        bo = int(ks[ks > b].min())                   # the nearest filled older bin of THIS track (b < b_old: there is one)
+        bn = int(ks[(ks < b) & seen].max())          # the nearest filled newer one (bin b_new is filled)
+        y0, y1 = y[np.nonzero(ks == bo)[0][-1]], y[np.nonzero(ks == bn)[0][-1]]
+        x0, x1, x = float(nb - 1 - bo), float(nb - 1 - bn), float(nb - 1 - b)
+        slope = (y1 - y0) / (x1 - x0)
+        col[F - 1 - b] = slope * (x - x0) + y0
+    return col, b_old
+
+
+def _coast_tracks(table, stamps, human_xy, robot_xy, time_step: float, F: int, max_coast: int):
+    """The ``max_coast`` half of ``_track_table``: ``table`` is its result without coasting, in which a pedestrian who is not seen in the
+    anchor frame has first_frame -1; every such column, first_frame and pose_now entry is decided again here.  Returns table + (coast,)."""
+    hum, rob, pose_now, first, n_grid = table
+    N = hum.shape[1]
+    coast = np.where(first[1:] >= 0, 0, -1).astype(np.int32)
+    if n_grid == 0:                                      # no kept frame: nobody is seen anywhere
+        pose_now[:] = np.nan
+    if n_grid == 0 or (coast == 0).all():
+        return hum, rob, pose_now, first, n_grid, coast
+    stamps = np.asarray(stamps, dtype=np.float64).reshape(-1)
+    R = len(stamps)
+    human_xy = np.asarray(human_xy, dtype=np.float64).reshape(R, N, 2)
+    robot_xy = np.asarray(robot_xy, dtype=np.float64).reshape(R, 2)
+    keep = ~(np.isnan(stamps) | np.isnan(robot_xy).any(axis=1))
+    order = np.argsort(stamps[keep], kind="stable")
+    t, H = stamps[keep][order], human_xy[keep][order]
+    ns = np.trunc(t * 100.0).astype(np.int64)
+    k = (ns[-1] - ns) // int(round(time_step * 100))
+    nb = int(k.max()) + 1
+    for j in np.nonzero(coast < 0)[0]:
+        pose_now[j] = np.nan                             # not seen in the anchor frame: the coasted position, or left out
+        seen = ~np.isnan(H[:, j]).any(axis=1)
+        if not seen.any():
+            continue
+        b_new = int(k[seen].min())
+        if b_new > max_coast or b_new > n_grid - 1:
+            continue
+        col, b_old = _track_column(k, nb, n_grid, F, seen, H[:, j], b_new)
+        y_new = col[F - 1 - b_new]
+        # (a grid row behind b_new, real or interpolated, gives the step; a single observation stands still)
+        step = y_new - col[F - 2 - b_new] if b_new + 1 <= min(b_old, n_grid - 1) else np.zeros(2)
+        for b in range(b_new):
+            col[F - 1 - b] = y_new + float(b_new - b) * step
+        hum[:, j] = col
+        first[j + 1] = F - 1 - min(b_old, n_grid - 1)
+        pose_now[j] = col[F - 1]
+        coast[j] = b_new
+    return hum, rob, pose_now, first, n_grid, coast
+
+
+def _check_max_coast(max_coast, F: int) -> Optional[int]:
+    if max_coast is None:
+        return None
+    if int(max_coast) != max_coast or not 0 <= int(max_coast) <= F - 2:
+        raise ValueError("max_coast must be an integer in 0..F-2")
+    return int(max_coast)
+
+
+def _track_table(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, F: int, max_coast: Optional[int] = None):
     """``frame_table_tracks`` without its refusal: (human_xy [F, N, 2], robot_xy [F, 2], pose_now [N, 2], first_frame [N + 1], n_grid)
-    whatever ``n_grid`` is (0: no kept frame - everything NaN, the robot's first_frame F, every pedestrian's -1)."""
+    whatever ``n_grid`` is (0: no kept frame - everything NaN, the robot's first_frame F, every pedestrian's -1).  With ``max_coast``
+    (see ``frame_table_tracks``) ``coast`` [N] int32 comes behind them."""
+    if max_coast is not None:
+        out = _track_table(stamps, human_xy, robot_xy, time_step, F)
+        return _coast_tracks(out, stamps, human_xy, robot_xy, time_step, F, max_coast)
     stamps = np.asarray(stamps, dtype=np.float64).reshape(-1)
     R = len(stamps)
     human_xy = np.asarray(human_xy, dtype=np.float64).reshape(R, -1, 2)
@@ -208,21 +282,7 @@ def _track_table(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray,
     first[0] = F - n_grid
 
     def column(seen, y):                                 # y [n, 2] of one track, seen [n] bool with the anchor seen -> its b_old
-        ks = np.where(seen, k, -1)
-        b_old = int(ks.max())
-        col = np.full((F, 2), np.nan)
-        for b in range(min(b_old, n_grid - 1) + 1):
-            hit = np.nonzero(ks == b)[0]
-            if len(hit):
-                col[F - 1 - b] = y[hit[-1]]              # the LAST sorted seen frame of the bin
-                continue
-            bo = int(ks[ks > b].min())                   # the nearest filled older bin of THIS track (b < b_old: there is one)
-            bn = int(ks[(ks < b) & seen].max())          # the nearest filled newer one (bin 0 holds the anchor)
-            y0, y1 = y[np.nonzero(ks == bo)[0][-1]], y[np.nonzero(ks == bn)[0][-1]]
-            x0, x1, x = float(nb - 1 - bo), float(nb - 1 - bn), float(nb - 1 - b)
-            slope = (y1 - y0) / (x1 - x0)
-            col[F - 1 - b] = slope * (x - x0) + y0
-        return col, b_old
+        return _track_column(k, nb, n_grid, F, seen, y)
 
     rob, _ = column(np.ones(len(t), dtype=bool), Rb)
     for j in range(N):
@@ -235,7 +295,7 @@ def _track_table(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray,
 
 
 def frame_table_tracks(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
-                       num_hist_frames: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
+                       num_hist_frames: int, max_coast: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
     """The frame table PER TRACK from raw frames - stamps [R], human_xy [R, N, 2], robot_xy [R, 2], oldest-pushed first - and the host
     twin of the device ``track_frames_kernel`` (csrc/frames.hpp), in its operation order.  A NaN coordinate of pedestrian j means "track
     j was not seen in this frame" and drops nothing:
@@ -254,8 +314,17 @@ def frame_table_tracks(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.nd
     right-aligned, NaN in front, the newest frame in row F-1 (the layout of ``pad_short_window``); ``first_frame`` (robot first) is
     F - n_grid for the robot, F-1 - min(b_old(j), n_grid-1) for pedestrian j and -1 for a pedestrian not seen in the anchor frame (absent
     now: its column is NaN; leave it out of the scene).  Without human NaN the rows F-n_grid .. F-1 are the bytes of
-    ``frame_table_frames``.  Raises ``HistoryTooShortError`` (``.n_grid`` attached) when n_grid < 2."""
-    out = _track_table(stamps, human_xy, robot_xy, time_step, int(num_hist_frames))
+    ``frame_table_frames``.  Raises ``HistoryTooShortError`` (``.n_grid`` attached) when n_grid < 2.
+
+    ``max_coast`` (0 .. F-2 bins; None: everything above, and the five returns): a pedestrian who is not seen in the anchor frame is
+    COASTED to it when his newest filled bin b_new is at most ``max_coast`` (and inside the window), and left out otherwise - the twin
+    of ``track_frames_coast_kernel``.  Coasted: the bins b >= b_new of his column follow rule 4; the bins b < b_new are
+    ``y(b) = y(b_new) + float(b_new - b) * step`` with ``step = y(b_new) - y(b_new + 1)`` when the grid row b_new + 1 exists in his window
+    (real or interpolated) and 0 otherwise; ``first_frame`` by the same formula; ``pose_now`` = y(0).  Left out: ``first_frame`` -1, the
+    column and ``pose_now`` NaN.  ``coast`` [N] int32 is returned as a sixth value: 0 seen in the anchor frame (everything as without
+    ``max_coast``), b_new coasted (0: seen in the anchor's bin but not in the anchor frame itself), -1 left out."""
+    F = int(num_hist_frames)
+    out = _track_table(stamps, human_xy, robot_xy, time_step, F, _check_max_coast(max_coast, F))
     if out[4] < 2:
         err = HistoryTooShortError(f"{out[4]} history frames on the time_step grid, at least 2 needed")
         err.n_grid = out[4]
@@ -264,25 +333,29 @@ def frame_table_tracks(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.nd
 
 
 def frame_table_tracks_batched(stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, n_frames: Optional[np.ndarray],
-                               time_step: float, num_hist_frames: int) -> Dict[str, np.ndarray]:
+                               time_step: float, num_hist_frames: int, max_coast: Optional[int] = None) -> Dict[str, np.ndarray]:
     """``frame_table_tracks`` for E episodes: stamps [E, R], human_xy [E, R, N, 2], robot_xy [E, R, 2]; the first ``n_frames[e]`` (1..R;
     None: all R) raw frames of episode e are valid.  Returns ``human_xy`` [E, F, N, 2], ``robot_xy`` [E, F, 2], ``pose_now`` [E, N, 2]
     float64, ``first_frame`` [E, N + 1] and ``n_grid`` [E] int32 - what ``jmid_build_scene_stamped_var`` leaves.  Nothing is raised for
-    an episode: ``n_grid[e]`` < 2 is the too-short one, ``first_frame[e, 1 + j]`` = -1 the pedestrian who is absent now."""
+    an episode: ``n_grid[e]`` < 2 is the too-short one, ``first_frame[e, 1 + j]`` = -1 the pedestrian who is absent now.
+    ``max_coast``: as in ``frame_table_tracks``, with ``coast`` [E, N] int32 - what ``jmid_build_scene_stamped_coast`` leaves."""
     stamps = np.asarray(stamps, dtype=np.float64)
     human_xy = np.asarray(human_xy, dtype=np.float64)
     robot_xy = np.asarray(robot_xy, dtype=np.float64)
     E, R, N, _ = human_xy.shape
     F = int(num_hist_frames)
+    max_coast = _check_max_coast(max_coast, F)
     n_frames = np.full(E, R, dtype=np.int64) if n_frames is None else np.asarray(n_frames)
     if n_frames.shape != (E,) or (n_frames < 1).any() or (n_frames > R).any():
         raise ValueError("n_frames must hold E values in 1..R")
     out = {"human_xy": np.empty((E, F, N, 2)), "robot_xy": np.empty((E, F, 2)), "pose_now": np.empty((E, N, 2)),
            "first_frame": np.empty((E, N + 1), dtype=np.int32), "n_grid": np.empty(E, dtype=np.int32)}
+    if max_coast is not None:
+        out["coast"] = np.empty((E, N), dtype=np.int32)
     for e in range(E):
         n = int(n_frames[e])
-        parts = _track_table(stamps[e, :n], human_xy[e, :n], robot_xy[e, :n], time_step, F)
-        for key, v in zip(("human_xy", "robot_xy", "pose_now", "first_frame", "n_grid"), parts):
+        parts = _track_table(stamps[e, :n], human_xy[e, :n], robot_xy[e, :n], time_step, F, max_coast)
+        for key, v in zip(("human_xy", "robot_xy", "pose_now", "first_frame", "n_grid", "coast"), parts):
             out[key][e] = v
     return out
 
@@ -398,11 +471,17 @@ def pad_short_window(human_xy: np.ndarray, robot_xy: np.ndarray, F: int) -> Tupl
     return hum, rob, np.full(N + 1, pad, dtype=np.int32)
 
 
-def _check_first_frame(first_frame, E: int, N: int, F: int, force_all_in_cluster: bool) -> np.ndarray:
+def _check_first_frame(first_frame, E: int, N: int, F: int, force_all_in_cluster: bool, allow_absent: bool = False) -> np.ndarray:
     ff = np.asarray(first_frame)
     if ff.shape != (E, N + 1) or not np.issubdtype(ff.dtype, np.integer):
         raise ValueError("first_frame must hold N + 1 integers per episode, robot first")
-    if (ff < 0).any() or (ff > F - 1).any():
+    if allow_absent:
+        if (ff[:, 0] < 0).any() or (ff[:, 1:] < -1).any() or (ff > F - 1).any():
+            raise ValueError("first_frame must lie in 0..F-1, or be -1 for a pedestrian who is not in the scene")
+        if (ff[:, 1:] == -1).all(axis=1).any():
+            e = int(np.nonzero((ff[:, 1:] == -1).all(axis=1))[0][0])
+            raise ValueError(f"episode {e}: every pedestrian is left out (first_frame -1)")
+    elif (ff < 0).any() or (ff > F - 1).any():
         raise ValueError("first_frame must lie in 0..F-1")
     if not force_all_in_cluster and (ff[:, 0] > F - 2).any():
         raise ValueError("the robot needs at least 2 frames unless force_all_in_cluster is set")
@@ -410,21 +489,23 @@ def _check_first_frame(first_frame, E: int, N: int, F: int, force_all_in_cluster
 
 
 def build_scene(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: int,
-                num_hist_frames: int = 6, force_all_in_cluster: bool = False, first_frame=None) -> SceneBatch:
+                num_hist_frames: int = 6, force_all_in_cluster: bool = False, first_frame=None, allow_absent: bool = False) -> SceneBatch:
     """mid_sim_wrapper.py:313-437 + preprocessing.py:428-694 for one scene.
 
     human_xy [F, N, 2], robot_xy [F, 2] on the ``time_step`` grid (oldest first).  ``first_frame`` [N + 1] (robot first): see
     ``build_scenes_batched``, whose episode this then is - the rows are the EGO rows (in-cluster pedestrians with at least two frames),
-    a one-frame pedestrian is listed in ``ids_out`` with its position repeated as its constant-velocity row.
+    a one-frame pedestrian is listed in ``ids_out`` with its position repeated as its constant-velocity row.  ``allow_absent``: a
+    pedestrian with first_frame -1 is not in the scene - neither in ``ids_in`` nor in ``ids_out``.
     """
     F, N, _ = human_xy.shape
     if F < num_hist_frames:
         raise HistoryTooShortError(f"{F} history frames available, {num_hist_frames} needed")
     if first_frame is not None:
         b = build_scenes_batched(np.asarray(human_xy, dtype=np.float64)[None], np.asarray(robot_xy, dtype=np.float64)[None], time_step,
-                                 force_all_in_cluster=force_all_in_cluster, horizon=horizon, first_frame=np.asarray(first_frame)[None])
+                                 force_all_in_cluster=force_all_in_cluster, horizon=horizon, first_frame=np.asarray(first_frame)[None],
+                                 allow_absent=allow_absent)
         rows = np.nonzero(b["in_cluster"][0])[0]
-        out = np.nonzero(~b["in_cluster"][0])[0]
+        out = np.nonzero(~b["in_cluster"][0] & (b["first_index"][0] >= 0))[0]
         return SceneBatch(ids_in=rows.astype(np.int64), ids_out=out.astype(np.int64), x=b["x"][0, rows], x_st=b["x_st"][0, rows],
                           nbr_sum=b["nbr_sum"][0, rows], edge_mask=b["edge_mask"][0, rows], p0=b["p0"][0, rows],
                           cv_forecasts={int(i): b["cv"][0, i] for i in out}, robot_in_cluster=bool(b["robot_in_cluster"][0]),
@@ -520,7 +601,8 @@ def build_scene(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, ho
 
 # --------------------------------------------------------------------------------------------- batched builder
 def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
-                         force_all_in_cluster: bool = False, horizon: Optional[int] = None, first_frame=None) -> Dict[str, np.ndarray]:
+                         force_all_in_cluster: bool = False, horizon: Optional[int] = None, first_frame=None,
+                         allow_absent: bool = False) -> Dict[str, np.ndarray]:
     """``build_scene`` for E independent episodes at once (no Python loop over episodes): the feed of the
     256-4096-episode evaluation sweeps.
 
@@ -539,10 +621,20 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
     with padding 0.0 and THEN standardised (preprocessing.py:531-550): absent, it adds (0 - ego_now) / std.  A pedestrian with one frame
     is no ego row (``in_cluster`` False) but counts in the cluster choice and as a neighbour.  ``first_index`` [E, N] int32 is returned
     in every case (zeros without ``first_frame``); all-zero ``first_frame`` gives the bits of None.
+
+    ``allow_absent`` (the host twin of ``jmid_build_scene_absent``): ``first_frame[e, 1 + j]`` may be -1 - pedestrian j is NOT IN THE SCENE
+    of episode e.  His positions are never read, he is no candidate of the cluster choice, no member of a cluster mean, no graph node,
+    no neighbour and no ego row; his rows come back NaN (x, x_st, nbr_sum, edge_mask, p0, cv), ``in_cluster`` False, ``first_index`` -1,
+    and every output of every other track is what the episode gives with his column removed.  The robot may not be -1; an episode in
+    which every pedestrian is -1 raises ValueError.  Without a -1 the bits of ``allow_absent=False``.
     """
     E, F, N, _ = human_xy.shape
     dt = time_step
-    ff = None if first_frame is None else _check_first_frame(first_frame, E, N, F, force_all_in_cluster)
+    ff = None if first_frame is None else _check_first_frame(first_frame, E, N, F, force_all_in_cluster, allow_absent)
+    absent = None                                                                  # [E, N+1] the nodes that are not in the scene
+    if ff is not None and (ff < 0).any():
+        absent, ff_in = ff < 0, ff
+        ff = np.where(absent, F, ff)                                               # present on no frame: NaN wherever a position is taken
     pos = np.concatenate([robot_xy[:, :, None, :], human_xy], axis=2)              # [E, F, N+1, 2], robot first
     if ff is not None:
         present = np.arange(F)[None, None, :] >= ff[:, :, None]                    # [E, N+1, F]
@@ -553,10 +645,16 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
     if force_all_in_cluster:
         inc = np.ones((E, N + 1), dtype=bool)
     else:
-        means = (near.astype(np.float64) @ last) / near.sum(axis=2, keepdims=True)
+        # (a node that is not in the scene is near nobody: a zero in its place keeps its NaN out of the others' sums)
+        with np.errstate(invalid="ignore"):                                        # (its own row: 0 / 0)
+            means = (near.astype(np.float64) @ (last if absent is None else np.where(absent[..., None], 0.0, last))) / near.sum(axis=2, keepdims=True)
         rdist = np.linalg.norm(means - last[:, :1], axis=2)
+        if absent is not None:                                                     # no candidate (its 0 / 0 would be the minimum)
+            rdist = np.where(absent, np.inf, rdist)
         chosen = np.argmin(rdist[:, 1:], axis=1) + 1
         inc = near[np.arange(E), chosen]                                           # [E, N+1]
+    if absent is not None:
+        inc = inc & ~absent
     # node states [E, N+1, F, 6] by first differences (first element duplicated)
     P = pos.transpose(0, 2, 1, 3)                                                  # [E, N+1, F, 2]
 
@@ -611,7 +709,7 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
         nbr_sum[:, :, e_idx] = nbr_sum[:, :, e_idx] + relj * w
     out = dict(x=xs.astype(np.float32), x_st=x_st.astype(np.float32), nbr_sum=nbr_sum, edge_mask=edge_mask,
                p0=xs[:, :, -1, 0:2].astype(np.float32), in_cluster=ego, robot_in_cluster=inc[:, 0],
-               first_index=np.zeros((E, N), dtype=np.int32) if ff is None else np.ascontiguousarray(ff[:, 1:]))
+               first_index=np.zeros((E, N), dtype=np.int32) if ff is None else np.ascontiguousarray((ff if absent is None else ff_in)[:, 1:]))
     if ff is not None:                                                              # (one NaN, whatever the arithmetic made of its payload)
         gone = ~present[:, 1:, :, None]
         out["x"] = np.where(gone, np.float32(np.nan), out["x"])
@@ -619,6 +717,11 @@ def build_scenes_batched(human_xy: np.ndarray, robot_xy: np.ndarray, time_step: 
     if horizon is not None:      # same operations, in the same order, as build_scene's per-pedestrian loop
         step = np.repeat((xs[:, :, -1, 2:4] * dt)[:, :, None, :], horizon, axis=2)     # [E, N, H, 2]
         out["cv"] = xs[:, :, -1:, 0:2] + np.cumsum(step, axis=2)
+    if absent is not None:                                                          # not in the scene: NaN rows
+        for key in ("x", "x_st", "nbr_sum", "edge_mask", "p0", "cv"):
+            if key in out:
+                g = absent[:, 1:].reshape(absent[:, 1:].shape + (1,) * (out[key].ndim - 2))
+                out[key] = np.where(g, out[key].dtype.type(np.nan), out[key])
     return out
 
 

@@ -9,7 +9,12 @@ takes the staged path (encode(first_index) -> denoise -> topk: three library ent
 --routes: per L, three forecasters side by side, their measured calls ALTERNATING (drift and the neighbours on the box hit them alike):
   host    short_history=True                                        the host frame table and scene, staged below L = 6
   frames  short_history=True, device_frames=True                    the host frame table, then engine.build_scene(first_frame=) + chain
-  tracks  short_history=True, device_frames=True, track_presence=True   raw frames in: jmid_build_scene_stamped_var + ONE chain"""
+  tracks  short_history=True, device_frames=True, track_presence=True   raw frames in: jmid_build_scene_stamped_var + ONE chain
+and behind the L rows one more case, "absent": a full window in which the last of the N pedestrians is not seen on the two newest frames,
+three forecasters with device_frames=True and track_presence=True, alternating as above:
+  filter    coast_frames=0   today's route: his column is cut out on the host, jmid_build_scene_stamped_var on N - 1 tracks
+  left_out  coast_frames=1   all N tracks to jmid_build_scene_stamped_coast; last seen 2 bins ago, he is left out on the device
+  coasted   coast_frames=2   the same entry; he is coasted over 2 bins and forecast like everybody else"""
 import os, sys, tempfile, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -71,6 +76,28 @@ def run_routes(tag, N, K, k_ret, H, step, reps=30, warmup=3):
             t = np.array(ts[name]) * 1e3
             print(f"RESULT {tag} route={name} [{PREC}] L={L} reps={reps} warmup={warmup}: total_ms median {np.median(t):.4f} "
                   f"p10 {np.percentile(t, 10):.4f} p90 {np.percentile(t, 90):.4f}", flush=True)
+    # one of N pedestrians not seen now
+    fs = {name: F.HumanTrajectoryForecasterSim(env, ypath, weights=w, precision=PREC, short_history=True, device_frames=True, track_presence=True,
+                                               coast_frames=c) for name, c in ABSENT.items()}
+    for f in fs.values():
+        for i in range(6):
+            hum = [State(p[j] + v[j] * 0.25 * i) for j in range(N)]
+            if i >= 4:
+                hum[N - 1] = State((np.nan, np.nan))
+            f.update_state_hists(State((0.0, -2.0 + 0.2 * i)), hum, 0.25 * i)
+        for _ in range(max(warmup, 1)):
+            f.predict_ret_best()
+    ts = {name: [] for name in fs}
+    for _ in range(reps):
+        for name, f in fs.items():
+            t0 = time.perf_counter(); f.predict_ret_best(); ts[name].append(time.perf_counter() - t0)
+    for name in fs:
+        t = np.array(ts[name]) * 1e3
+        print(f"RESULT {tag} absent={name} [{PREC}] L=6 reps={reps} warmup={warmup}: total_ms median {np.median(t):.4f} "
+              f"p10 {np.percentile(t, 10):.4f} p90 {np.percentile(t, 90):.4f}", flush=True)
+
+
+ABSENT = {"filter": 0, "left_out": 1, "coasted": 2}
 
 
 if __name__ == "__main__":
