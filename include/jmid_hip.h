@@ -559,6 +559,51 @@ int jmid_noise_fill(jmid_handle_t h, uint64_t seed, int E, int rows, int T, cons
 int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, const float* ctx,
                         const float* p0, float dt, int precision, float* vel_out, float* pos_out, int mem);
 
+/* Collision-free sampling: jmid_denoise_seeded that redraws joint samples in which two agents collide.  OFF unless this entry is called.
+ * DiffusionTraj.sample (MID/models/diffusion.py:544-613) takes with_constraints / constraint_type / dynamics and returns (samples,
+ * number_of_steps, num_iter, total_num_samples_with_collisions, total_num_samples_with_collisions_fixed); MID/mid.py:404-407, 492-498,
+ * 908-954, 1048 accumulate and print the counts ("Rejection sampling fixed X samples out of Y samples with collisions").  The reference's
+ * loop body is gone and its counts are hard-coded zeros; its predicate is check_collision_velocity (MID/models/collision_check_utils.py:
+ * 100-108).  THE RULE, decided here:
+ *   In JMID the K samples of an episode are ONE attention sequence (diffusion.py:196-204; jmid_denoise above), so a single sample cannot be
+ *   redrawn alone without changing what it attends to: a redraw is a whole episode, all K samples afresh.  With K = 1 this is the
+ *   reference's offline per-sample loop.
+ *   Predicate: a candidate joint sample [A, T, 2] is ACCEPTABLE iff its n_agents_colliding column of jmid_collision_statistics is 0 at
+ *   `threshold` AND its min_dist column is not NaN (A = 1: +inf, acceptable).  fp64, that entry's own kernel.  The reference's 0.2 is the
+ *   Python default.
+ *   Round 0: the candidates c_0[s] are the K samples of draw number draw0; slot s holds c_0[s]; bad = the slots whose candidate is not
+ *   acceptable.
+ *   Round j = 1 .. max_rounds: only the episodes with a non-empty bad set are rerun - their K samples are denoised again from the x_T of
+ *   draw number draw0 + j (episode id, seed and element addressing of "Seeded noise" above); good_j = the ascending list of the acceptable
+ *   candidate indices; the i-th smallest slot of bad receives the i-th smallest candidate of good_j, i < min(|bad|, |good_j|), positions
+ *   and velocities both; filled slots leave bad; unused candidates are discarded.
+ *   End: a slot that never got an acceptable candidate keeps its round-0 sample and stays flagged.  Slots acceptable at round 0 and slots
+ *   never fixed are bit for bit the plain seeded call's samples; max_rounds = 0 is the plain call plus the flags.
+ * Every output of an episode is a function of (weights, ctx, p0, seed, episode id, draw0, threshold, max_rounds) only - not of its batch
+ * mates, its shard or the chunk plan - on top of the rule for calls of different episode counts at jmid_set_chunk_episodes (bit-identical
+ * at head_dim 16, equal to rounding at head_dim 128).  Two equalities:
+ *   - draw0 = 0, max_rounds = 0 is bit-identical to jmid_denoise_seeded;
+ *   - round j's candidates are bit-identical to jmid_noise_fill(draw = draw0 + j) + jmid_denoise on the gathered ctx / p0 rows of exactly
+ *     the rerun episodes, in ascending order, as ONE call.
+ *   ctx [E, A, ctx_dim], p0 [E, A, 2] (required: the predicate is defined on positions), episode_ids [E] a HOST array
+ *   vel_out, pos_out  [E, K, A, T, 2]; may be NULL
+ *   slot_out    [E, K, 3] int32 = {round whose draw the slot holds (0 .. max_rounds), candidate index within that round, 1 if the slot's
+ *               sample is not acceptable}; may be NULL
+ *   episode_out [E, 3] int32 = {slots not acceptable at round 0, slots fixed, last round in which the episode was rerun (0 = never)};
+ *               may be NULL
+ * Every kernel of the loop runs in a fixed order without atomics.  The host reads ONE small download per round (how many episodes the next
+ * round reruns, which, and the round's range flag): the loop's inherent synchronisation, the rerun's launch dimensions depend on it.  A
+ * rerun is a seeded denoise call of E' episodes through the same planner, the denoise kernels are untouched, and the captured loop ("graph")
+ * gives the same bits on and off.
+ * After the call the ACCEPTED set is what pos = NULL means for jmid_topk, jmid_eval_statistics, jmid_eval_statistics_masked and
+ * jmid_collision_statistics, at (E, A, K, T), forgotten exactly as after jmid_denoise.
+ * DDIM only (JMID_EINVAL under a DDPM table: its draws 1.. are the steps' z); uniform agent count only (no padded form).  JMID_EINVAL:
+ * E < 1, K outside 1..1024, T outside 2..24, A outside 1..64, threshold not finite or < 0, max_rounds outside 0..64, draw0 < 0, NULL
+ * episode_ids / ctx / p0.  JMID_ERANGE or JMID_ETIMEOUT of any round is the status of the whole call and the outputs are then undefined. */
+int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0,
+                               const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds,
+                               float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out, int mem);
+
 /* jmid_predict_scene and jmid_forecast_scene with (seed, episode_ids [E]) in place of x_T: x_T is draw 0 with rows = K * A, filled on the
  * device (nothing but bw is uploaded).  Everything else as their namesakes, whose chain they share: bit-identical to them fed
  * jmid_noise_fill's draw 0. */

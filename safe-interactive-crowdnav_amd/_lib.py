@@ -81,6 +81,8 @@ SIGNATURES = {
     "jmid_noise_fill": (C.c_int, [Handle, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "jmid_denoise_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_denoise_reject_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_float, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "jmid_predict_scene_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_forecast_scene_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float, C.c_int,

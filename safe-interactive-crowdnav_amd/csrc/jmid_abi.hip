@@ -408,6 +408,107 @@ int noise_entry(jmid_handle_t h, const char* who, uint64_t seed, int E, int rows
     return st.end();
 }
 
+// The workspace of jmid_denoise_reject_seeded, laid out here only: the call's ctx and p0 (host mode: their uploads) | the accepted block |
+// the rerun's input and output blocks | the flags' per-sample values | the tables | the download block of a round (the rerun list with its
+// length in front, then the range flag).  base null: the size only
+struct RejectIo {
+    Arr<float> ctx, p0;                        // [E, A, ctx_dim] | [E, A, 2] (host mode)
+    Arr<float> acc_vel, acc_pos;               // [E, K, A, T, 2] twice (acc_vel: when velocities are asked for)
+    Arr<float> g_ctx, g_p0, cand_vel, cand_pos;      // a rerun of at most E episodes (none with max_rounds = 0)
+    Arr<double> ws;                            // [E, K, 2]
+    Arr<int> slots, episodes, remaining;       // [E, K, 3] | [E, 3] | [E]
+    Arr<int> list, flag;                       // [1 + E] | one word: the download block
+    size_t down_bytes = 0;
+};
+size_t reject_io(const jmid_ctx* h, int E, int A, int K, int T, bool host, bool vel, bool rerun, char* base, RejectIo* out) {
+    const size_t EA = (size_t)E * A, M2 = (size_t)E * K * A * T * 2, Er = rerun ? 1 : 0;
+    Carver c(base);
+    RejectIo io{};
+    io.ctx = c.arr(host ? EA * h->ctx_dim : 0); io.p0 = c.arr(host ? EA * 2 : 0);
+    io.acc_vel = c.arr(vel ? M2 : 0); io.acc_pos = c.arr(M2);
+    io.g_ctx = c.arr(Er * EA * h->ctx_dim); io.g_p0 = c.arr(Er * EA * 2); io.cand_vel = c.arr(vel ? Er * M2 : 0); io.cand_pos = c.arr(Er * M2);
+    io.ws = c.arr<double>((size_t)E * K * CLS_WS_COLS);
+    io.slots = c.arr<int>((size_t)E * K * REJ_SLOT_COLS); io.episodes = c.arr<int>((size_t)E * REJ_EPISODE_COLS); io.remaining = c.arr<int>(E);
+    const size_t down = c.off;
+    io.list = c.arr<int>((size_t)E + 1); io.flag = c.arr<int>(1);
+    io.down_bytes = c.off - down;
+    if (out) *out = io;
+    return c.off;
+}
+
+// jmid_denoise_reject_seeded after its argument checks.  Every round is one seeded denoise call through run_network (a stage: no
+// caller-stream ordering, the range flag comes with the round's one download), the flags of its candidates, the pairing, the compaction.
+int reject_loop(jmid_ctx* h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx, const float* p0,
+                float dt, int precision, double threshold, int max_rounds, float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out,
+                int mem) {
+    const char* who = "jmid_denoise_reject_seeded";
+    const bool host = mem == JMID_MEM_HOST, vel = vel_out != nullptr, split = precision != JMID_PREC_F32;
+    h->last_pos = nullptr;
+    if (int rc = order_in(h, mem)) return rc;
+    if (int rc = h->reject_ws.reserve(h, reject_io(h, E, A, K, T, host, vel, max_rounds > 0, nullptr, nullptr), who)) return rc;
+    RejectIo io;
+    reject_io(h, E, A, K, T, host, vel, max_rounds > 0, h->reject_ws.p, &io);
+    if (int rc = h->reject_pin.reserve(h, io.down_bytes, who)) return rc;
+    const int* pin = h->reject_pin.as<int>();
+    const size_t flag_word = (size_t)((const char*)io.flag.p - (const char*)io.list.p) / sizeof(int);
+    if (host) {
+        HIPCHK(h, hipMemcpyAsync(io.ctx.p, ctx, io.ctx.bytes(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(io.p0.p, p0, io.p0.bytes(), hipMemcpyHostToDevice, h->stream));
+        ctx = io.ctx.p; p0 = io.p0.p;
+    }
+    HIPCHK(h, hipMemsetAsync(io.flag.p, 0, sizeof(int), h->stream));
+    RejectArgs g{};
+    g.ws = io.ws; g.cand_pos = io.cand_pos; g.cand_vel = io.cand_vel; g.acc_pos = io.acc_pos; g.acc_vel = io.acc_vel;
+    g.slots = io.slots; g.episodes = io.episodes; g.remaining = io.remaining; g.list = io.list;
+    g.ctx = ctx; g.p0 = p0; g.g_ctx = io.g_ctx; g.g_p0 = io.g_p0;
+    g.E = E; g.K = K; g.n = A * T * 2; g.n_ctx = A * h->ctx_dim; g.n_p0 = A * 2;
+    std::vector<uint32_t> ids(episode_ids, episode_ids + E);
+    int n_run = E;
+    for (int j = 0; j <= max_rounds && n_run > 0; ++j) {
+        if (j > 0) {      // the listed episodes, ascending: their ids, their rows
+            for (int b = 0; b < n_run; ++b) ids[b] = episode_ids[pin[1 + b]];
+            HIPCHK(h, launch_reject_gather(g, n_run, h->stream));
+        }
+        const SeedArgs sa{seed, ids.data(), draw0 + j};
+        DenoiseCall d{n_run, A, K, T, precision, JMID_MEM_DEVICE};
+        d.ctx = j ? io.g_ctx.p : ctx; d.p0 = j ? io.g_p0.p : p0; d.dt = dt; d.seeded = &sa; d.chained = true; d.who = who;
+        d.vel_out = j ? io.cand_vel : io.acc_vel; d.pos_out = j ? io.cand_pos.p : io.acc_pos.p;      // round 0 IS the accepted block
+        if (int rc = run_network(h, d)) return rc;
+        h->last_pos = nullptr;       // (the arena's stage is not what pos = NULL means after this entry)
+        {
+            ProfScope ps(h, KC_EVAL_STATS, h->stream);
+            CollisionStatsArgs cs{};
+            cs.pos = d.pos_out; cs.ws = io.ws; cs.threshold = threshold;
+            cs.E = n_run; cs.A = A; cs.K = K; cs.T = T;
+            HIPCHK(h, launch_collision_stats(cs, h->stream));
+            g.round = j;
+            HIPCHK(h, j ? launch_reject_accept(g, n_run, h->stream) : launch_reject_init(g, h->stream));
+            HIPCHK(h, launch_reject_compact(g, h->stream));
+        }
+        // the round's one download: how many episodes the next round reruns and which, and the range flag of this round's denoise call
+        if (split) HIPCHK(h, hipMemcpyAsync(io.flag.p, h->range_flag, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->reject_pin.p, io.list.p, io.down_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (split && pin[flag_word]) {
+            (void)order_out(h, mem);
+            return flagged_call(h, pin[flag_word]);
+        }
+        n_run = pin[0];
+        if (n_run < 0 || n_run > E) return fail(h, JMID_EHIP, std::string(who) + ": the rerun list came back with an impossible length");
+    }
+    const hipMemcpyKind kout = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (vel_out) HIPCHK(h, hipMemcpyAsync(vel_out, io.acc_vel.p, io.acc_vel.bytes(), kout, h->stream));
+    if (pos_out) HIPCHK(h, hipMemcpyAsync(pos_out, io.acc_pos.p, io.acc_pos.bytes(), kout, h->stream));
+    if (slot_out) HIPCHK(h, hipMemcpyAsync(slot_out, io.slots.p, io.slots.bytes(), kout, h->stream));
+    if (episode_out) HIPCHK(h, hipMemcpyAsync(episode_out, io.episodes.p, io.episodes.bytes(), kout, h->stream));
+    if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the accepted set is what pos = NULL consumers see, under jmid_denoise's forgetting rules (every later denoise call and every
+    // host-mode entry that clears last_pos forgets it, although this block itself would survive them)
+    h->last_pos = io.acc_pos.p;
+    h->last_pos_dims[0] = E; h->last_pos_dims[1] = A; h->last_pos_dims[2] = K; h->last_pos_dims[3] = T;
+    return order_out(h, mem);
+}
+
 }  // namespace jmid_host
 
 // What the handle created, and only that: a handle that never created anything (jmid_dbg_plan_chunks_mode builds one on the stack) makes
@@ -1169,6 +1270,29 @@ int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t se
     DenoiseCall c{E, A, K, T, precision, mem};
     c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.seeded = &sa; c.who = "jmid_denoise_seeded";
     return run_network(h, c);
+}
+
+int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx,
+                               const float* p0, float dt, int precision, double threshold, int max_rounds, float* vel_out, float* pos_out,
+                               int32_t* slot_out, int32_t* episode_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    const std::string w("jmid_denoise_reject_seeded");
+    if (int rc = check_ready(h)) return rc;
+    if (h->ddpm) return fail(h, JMID_EINVAL, w + " samples with DDIM: under a DDPM table the draws 1.. are the steps' z");
+    if (E < 1 || K < 1 || K > REJ_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
+        return fail(h, JMID_EINVAL, w + " supports E >= 1, 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
+    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
+    if (!episode_ids || !ctx) return fail(h, JMID_EINVAL, w + ": null episode_ids or ctx");
+    if (!p0) return fail(h, JMID_EINVAL, w + ": null p0 (the predicate is defined on positions)");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(h, JMID_EINVAL, w + ": the threshold must be finite and >= 0");
+    if (max_rounds < 0 || max_rounds > 64) return fail(h, JMID_EINVAL, w + ": max_rounds must be in 0..64");
+    if (draw0 < 0 || draw0 > 0x7fffffff - 64) return fail(h, JMID_EINVAL, w + ": draw0 must be at least 0 (and draw0 + max_rounds must fit an int)");
+    CallMode mode;
+    if (!call_mode(precision, &mode)) return fail(h, JMID_EINVAL, w + ": precision must be JMID_PREC_F32, JMID_PREC_F16X3, JMID_PREC_F16X2 or JMID_PREC_F16MX");
+    if (mem != JMID_MEM_HOST && mem != JMID_MEM_DEVICE) return fail(h, JMID_EINVAL, w + ": bad mem");
+    HIPCHK(h, hipSetDevice(h->device));
+    return reject_loop(h, E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, vel_out, pos_out, slot_out,
+                       episode_out, mem);
 }
 
 int jmid_noise_fill(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out, int mem) {

@@ -42,6 +42,7 @@
 #include "noise.hpp"
 #include "padded.hpp"
 #include "qkv0.hpp"
+#include "reject.hpp"
 #include "tail_fold.hpp"
 #include "scene.hpp"
 #include "frames.hpp"
@@ -173,6 +174,10 @@ struct jmid_ctx {
     // jmid_topk ranks and jmid_eval_statistics scores when they are given no pos pointer
     const float* last_pos = nullptr;
     int last_pos_dims[4] = {0, 0, 0, 0};     // E, A, K, T
+    // jmid_denoise_reject_seeded: the accepted set and the loop's tables, in a workspace of its own (it survives the reruns, which reuse the
+    // arena; last_pos points into it after the call), and the pinned words of the loop's one download per round
+    jmid_host::Block reject_ws;
+    jmid_host::Block reject_pin{jmid_host::MEM_PINNED};
     jmid_host::Block kde_ws;                 // jmid_topk's and the statistics entries' own workspace (it must not move the arena last_pos points into)
     // jmid_predict: pinned host staging + device I/O buffers of the chained call, grown on demand
     jmid_host::Block pin{jmid_host::MEM_PINNED};
@@ -333,6 +338,7 @@ int check_ready(jmid_ctx* h);
 struct SeedArgs {
     uint64_t seed;
     const uint32_t* ids;
+    int draw = 0;                         // the draw number x_T is (jmid_denoise_reject_seeded: draw0 + the round); DDIM only when not 0
 };
 int fill_noise(jmid_ctx* h, uint64_t seed, const unsigned* ids_dev, int E, size_t n, int draw, float* out, unsigned* words, hipStream_t stream);
 // ... of a padded batch: the real rows of out [E, K * A, T, 2], every episode's own compact draw; the padded rows are left alone

@@ -351,6 +351,37 @@ class JmidEngine:
                       float(dt), _lib.PRECISIONS[precision], _ptr(vel), _ptr(pos), self._mem(dev))
         return vel, pos
 
+    def denoise_reject(self, ctx: ArrayLike, p0: ArrayLike, seed: int, episode_ids, K: int, T: int, dt: float = 0.25, precision: str = "f32",
+                       threshold: float = 0.2, max_rounds: int = 3, draw0: int = 0, want_vel: bool = True, want_pos: bool = True):
+        """Collision-free sampling (``jmid_denoise_reject_seeded``; the rule stands in include/jmid_hip.h, its host twin is
+        ``metrics.fill_slots``): the seeded ``denoise`` of draw number ``draw0``, then up to ``max_rounds`` reruns of the episodes that
+        still hold a joint sample in which two agents come closer than ``threshold`` (the predicate of ``collision_statistics``) - an
+        episode's K samples are redrawn together from draw ``draw0 + round`` and the acceptable candidates fill the bad slots in
+        ascending order.  ctx [E, A, ctx_dim], p0 [E, A, 2] -> (vel [E, K, A, T, 2] or None, pos [E, K, A, T, 2] or None, slots [E, K, 3] int32 =
+        (round, candidate, still colliding), episodes [E, 3] int32 = (colliding at round 0, fixed, last round rerun)).  DDIM only.
+        NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out.  The accepted set stays resident for ``topk(None, ...)`` and the
+        statistics entries."""
+        if ctx.ndim != 3 or int(ctx.shape[2]) != self.dims.ctx_dim:
+            raise ValueError("expected ctx [E, A, ctx_dim]")
+        if self.sampling != "ddim":
+            raise ValueError("collision-free sampling is DDIM only: under DDPM the draws 1.. are the steps' z")
+        if p0 is None:
+            raise ValueError("collision-free sampling needs p0: the predicate is defined on positions")
+        dev = _is_cuda(ctx)
+        E, A, K, T = int(ctx.shape[0]), int(ctx.shape[1]), int(K), int(T)
+        if tuple(p0.shape) != (E, A, 2):
+            raise ValueError("p0 must be [E, A, 2]")
+        seed, ids = seeded_noise_args(None, seed, episode_ids, E)
+        bc, bp = _Buf(ctx, dev), _Buf(p0, dev)
+        where = ctx.device if dev else None
+        vel = _out((E, K, A, T, 2), device=where) if want_vel else None
+        pos = _out((E, K, A, T, 2), device=where) if want_pos else None
+        slots, episodes = _out((E, K, 3), np.int32, where), _out((E, 3), np.int32, where)
+        self._compute(self._lib.jmid_denoise_reject_seeded, self._h, E, A, K, T, seed, _ptr(ids), int(draw0), bc.ptr, bp.ptr, float(dt),
+                      _lib.PRECISIONS[precision], float(threshold), int(max_rounds), _ptr(vel), _ptr(pos), _ptr(slots), _ptr(episodes),
+                      self._mem(dev))
+        return vel, pos, slots, episodes
+
     def topk(self, pos: Optional[ArrayLike], k: int, dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None):
         """Joint-KDE top-k on the device (``jmid_topk``; get_most_likely_samples, mid_sim_wrapper.py:14-169), batched over
         episodes.  pos [E, K, A, T, 2] -> (kept [E, A, k, T, 2], log-weights [E, A, k]) in ascending likelihood.

@@ -34,6 +34,11 @@ moved by what the draws would consume without launching them, ``advance_cuda_gen
 ``jmid_noise_fill``) as a pure function of (``seed``, ``episode_id``, draw number), the draw number advancing by one block of
 ``n_steps + 1`` per ``predict_ret_best()``, and the torch generators are not touched.  Statistically, not seed-, compatible with
 the reference.
+``collision_free_rounds=R`` > 0 (opt-in, with ``rng_compat="device"``; 0 is today's behaviour, draw numbering included): collision-free
+sampling (``JmidEngine.denoise_reject``; the rule stands in include/jmid_hip.h) - a joint sample in which two pedestrians come closer
+than ``collision_threshold`` is redrawn, the whole scene's K samples together, up to R times; the ranking then runs on the accepted
+set.  The route is staged, the draw number advances by ``max(n_steps + 1, R + 1)`` per call, and ``self.rejection`` holds the last
+call's (num_iter, samples with collisions, samples fixed).  A slot that no round could fix keeps its round-0 sample.
 
 Differences from the reference that a caller can observe:
   * the engine (weights on the GPU) is cached across instances: the reference rebuilds the model and reloads the
@@ -180,7 +185,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  device_id: Optional[int] = None, precision: Optional[str] = None, rng_compat: Optional[str] = None,
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
                  lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
-                 seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False, coast_frames: int = 0):
+                 seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False, coast_frames: int = 0,
+                 collision_free_rounds: int = 0, collision_threshold: float = 0.2):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -236,6 +242,16 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # rng_compat="device": the address of this instance's noise (seed, episode id) and the draw number its next call starts at
         self.noise_seed, self.episode_id, self._noise_draw = int(seed), int(episode_id), 0
         self.rng_compat = rng_compat if rng_compat != "auto" else ("cuda" if torch.cuda.is_available() else "cpu")
+        # > 0 (opt-in, needs rng_compat="device": a redraw is a draw number of the counter generator): collision-free sampling, up to that
+        # many reruns of a scene whose joint samples collide at collision_threshold metres; rejection: the last call's totals
+        self.collision_free_rounds, self.collision_threshold = int(collision_free_rounds), float(collision_threshold)
+        if not 0 <= self.collision_free_rounds <= 64:
+            raise ValueError("collision_free_rounds must lie in 0..64")
+        if self.collision_free_rounds and self.rng_compat != "device":
+            raise ValueError("collision_free_rounds needs rng_compat='device' (a redraw is a draw number of the library's counter generator)")
+        if not (np.isfinite(self.collision_threshold) and self.collision_threshold >= 0.0):
+            raise ValueError("collision_threshold must be finite and >= 0")
+        self.rejection: Optional[Tuple[int, int, int]] = None
         self._init_MID(mid_config_file, weights, device_id, lib_path)
 
     def _init_MID(self, mid_config_file, weights, device_id, lib_path=None):
@@ -303,6 +319,44 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
             SELF_CHECK_DOWNGRADES += 1
             return ref
         return pos
+
+    def _denoise_reject(self, ctx, p0, check, want_pos=True):
+        """The denoise stage with ``collision_free_rounds``: ``engine.denoise_reject`` from this call's draw0 in ``self.precision``
+        (JMID_ERANGE: the whole call again in exact fp32, counted and warned about like ``_denoise``); ``check``: the first-call self
+        check - the same call, the same draws, once more in "f16x3", and the downgrade when the two disagree.  ``self.rejection`` <- the
+        totals of the call whose positions are used.  -> pos [1, K, A, H, 2], or None when they stay on the device."""
+        from .metrics import rejection_totals
+        A, K, H = int(ctx.shape[1]), self.num_samples, self.predict_horizon
+
+        def run(precision, pos_back):
+            out, fell_back = repeat_in_fp32(lambda p: self.engine.denoise_reject(
+                ctx, p0, self.noise_seed, [self.episode_id], K, H, dt=self.time_step, precision=p, threshold=self.collision_threshold,
+                max_rounds=self.collision_free_rounds, draw0=self._draw0, want_vel=False, want_pos=pos_back), precision)
+            return out[1], out[3], fell_back
+
+        pos, episodes, fell_back = run(self.precision, want_pos or check)
+        if fell_back:
+            if not self.erange_fallbacks:
+                warnings.warn("JMID_ERANGE: an activation left the fp16 range; the call was repeated in the exact-fp32 mode "
+                              "(same result, ~5x the latency).  Construct the forecaster with precision='f32' if this "
+                              "checkpoint does it often.", RuntimeWarning, stacklevel=3)
+            self.erange_fallbacks += 1
+        if check:
+            global SELF_CHECK_DOWNGRADES
+            self._checked_shapes.add((1, K * A, H, 2))
+            ref, ref_episodes, _ = run("f16x3", True)      # (the accepted set now resident is this call's: route.rank is "device" under check)
+            with np.errstate(invalid="ignore"):
+                delta = float(np.linalg.norm(pos - ref, axis=-1).mean())
+            self.self_check_delta = delta
+            if not delta <= self.self_check_tol:
+                warnings.warn(f"precision={self.precision!r} differs from 'f16x3' by {delta:.2e} m mean displacement on this "
+                              f"checkpoint (> {self.self_check_tol:.1e}): this forecaster now runs 'f16x3'", RuntimeWarning,
+                              stacklevel=3)
+                self.precision, self.self_check = "f16x3", False
+                SELF_CHECK_DOWNGRADES += 1
+                pos, episodes = ref, ref_episodes
+        self.rejection = rejection_totals(episodes)
+        return pos if want_pos or check else None
 
     def get_most_likely_samples(self, forecasts):
         """mid_sim_wrapper.py:440-441: the ``num_ret_samples`` most likely of the sampled joint futures under the per-step
@@ -416,6 +470,12 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         """Noise stage -> x_T [1, K * A, H, 2].  RNG contract (module docstring): x_T is the first draw of the CPU default generator; the
         per-step z of the reference (unused by DDIM) comes from the generator of the device the reference would run on."""
         K, H, stride = self.num_samples, self.predict_horizon, int(100 / self.step_size)
+        if self.rng_compat == "device" and self.collision_free_rounds:
+            # collision-free sampling draws inside the entry: round j is draw number draw0 + j.  The block of this call is reserved here
+            # (the self check and the JMID_ERANGE repeat start from the same draw0); nothing is drawn
+            self._draw0 = self._noise_draw
+            self._noise_draw += max(len(range(100, 0, -stride)) + 1, self.collision_free_rounds + 1)
+            return None
         if self.rng_compat == "device":
             # the library's counter generator: this call's block of n_steps + 1 draw numbers (x_T is its first; a DDPM sampler would take
             # the others), drawn ONCE - the self check and the JMID_ERANGE repeat reuse the array
@@ -448,10 +508,10 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
         x_np = self._draw_x_T(A)             # after the scene: a call that raises HistoryTooShortError has drawn nothing
         t1 = time.perf_counter()
-        check = self.self_check and tuple(x_np.shape) not in self._checked_shapes
+        check = self.self_check and (1, K * A, H, 2) not in self._checked_shapes
         route = plan_route(k=k, K=K, A=A, H=H, device_topk=self.device_topk, device_scene=self.device_scene,
                            device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped",
-                           tracks=present is not None)
+                           tracks=present is not None, collision_free=self.collision_free_rounds > 0)
         result, call = None, dict(dt=self.time_step, precision=self.precision)
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
@@ -474,9 +534,12 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 if pose_now is None:
                     pose_now = self.engine.scene_frames()["pose_now"]
                 ctx = self.engine.encode(x_st, nbr_sum, edge_mask, first_index=first_index)
-                pos = self._denoise(x_np, ctx[None], p0[None], want_pos=route.rank != "device_resident")
-                if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
-                    pos = self._self_check(x_np, ctx[None], p0[None], pos)
+                if self.collision_free_rounds:
+                    pos = self._denoise_reject(ctx[None], p0[None], check, want_pos=route.rank != "device_resident")
+                else:
+                    pos = self._denoise(x_np, ctx[None], p0[None], want_pos=route.rank != "device_resident")
+                    if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
+                        pos = self._self_check(x_np, ctx[None], p0[None], pos)
                 t2 = time.perf_counter()
                 rows, logw = rank_samples(self.engine, route.rank, pos, k, (1, A, K, H))
         t3 = time.perf_counter()
@@ -538,11 +601,13 @@ def scene_source(device_scene: bool, device_frames: bool, short: bool = False, f
 
 def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, device_scene: bool = False, device_frames: bool = False,
                check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False,
-               resident: bool = False, tracks: bool = False) -> Route:
+               resident: bool = False, tracks: bool = False, collision_free: bool = False) -> Route:
     """Every decision of a call that does not need an array: the flags, k of K samples, A in-cluster pedestrians, horizon H, whether the
     first-call self check is due (``check``), whether the window is short (``short``) and whether the histories are frames (``frames``).
     ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count, ``resident``: that form on the
-    batch's resident scene (``padded="resident"``: forecast_scene_padded).  ``tracks``: per-track windows (``track_presence``)."""
+    batch's resident scene (``padded="resident"``: forecast_scene_padded).  ``tracks``: per-track windows (``track_presence``).
+    ``collision_free``: collision-free sampling (``collision_free_rounds`` > 0) - the rejection loop has no one-entry chain, so the run is
+    staged (encode -> ``denoise_reject`` -> rank) and the ranking reads the accepted set where the loop left it."""
     scene = scene_source(device_scene, device_frames, short, frames, batch, resident, tracks)
     # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits - the reference
     # has none - the host twin ranks them
@@ -553,6 +618,7 @@ def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, devi
     else:           # a short window built on the host is staged: jmid_predict has no first_index (a resident one is predict_scene's)
         chain = not (short and scene == "host")
     chain = chain and (on_dev or k == K) and not check        # (the self check compares the staged denoise call's positions)
+    chain = chain and not collision_free
     rank = "none" if k >= K else "host" if not on_dev else "device" if check else "device_resident"
     return Route(scene, "chain" if chain else "staged", rank)
 
@@ -601,7 +667,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   num_ret_samples: int, horizon: int, time_step: float, precision: Optional[str] = None,
                   device_topk: bool = True, device_scene: bool = False,
                   device_frames: bool = False, noise: str = "torch", seed: int = 0,
-                  padded=False, short_history: bool = False, first_frame=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  padded=False, short_history: bool = False, first_frame=None, collision_free_rounds: int = 0,
+                  collision_threshold: float = 0.2, stats: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -641,11 +708,23 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     (``jmid_build_scene_absent``; not seen now) - the episodes of a batch keep one N, his rows come back NaN in both arrays with
     ``in_cluster`` False, everybody else as if his column were removed.  On the host route, the grouped device route and
     ``padded="resident"``; not with ``padded=True``.
+    ``collision_free_rounds=R`` > 0 (opt-in, with ``noise="device"``): collision-free sampling per count group
+    (``engine.denoise_reject`` from draw 0: a joint sample in which two pedestrians come closer than ``collision_threshold`` is redrawn,
+    its episode's K samples together, up to R times) - every group is staged and ranked on its accepted set, and an episode's rows stay
+    the same bits whichever batch it is part of.  ``stats`` (a dict) is filled with ``episodes`` [E, 3] int32 = (samples colliding at
+    round 0, fixed, last round rerun) and ``slots`` [E, K, 3] int32, rows in input order (an episode with an empty cluster: zeros).
+    Not with ``padded=``.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
     if padded not in (False, True, "resident"):
         raise ValueError("padded must be False, True or 'resident'")
+    R = int(collision_free_rounds)
+    if R:
+        if padded:
+            raise ValueError("collision_free_rounds has no padded form (jmid_denoise_reject_seeded takes one agent count per call)")
+        if noise != "device":
+            raise ValueError("collision_free_rounds needs noise='device' (a redraw is a draw number of the library's counter generator)")
     resident = isinstance(padded, str)
     if resident:
         padded, device_frames = False, True       # (what it falls back to: the grouped device path)
@@ -673,7 +752,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
 
     def plan(A, padded=False, resident=False):
         return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
-                          short=ff is not None, batch=True, padded=padded, resident=resident)
+                          short=ff is not None, batch=True, padded=padded, resident=resident, collision_free=R > 0)
 
     def torch_x_T(e, A):
         return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
@@ -710,6 +789,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         return (*SC.assemble_forecasts(inc, rows, lw, b["cv"], pose_now, k, K, n_agents=n_in), inc)
     forecasts = np.empty((E, N, k, H + 1, 2), dtype=np.float64)
     logw = np.empty((E, N, k), dtype=np.float64)
+    if R and stats is not None:
+        stats["episodes"], stats["slots"] = np.zeros((E, 3), dtype=np.int32), np.zeros((E, K, 3), dtype=np.int32)
     for A in np.unique(n_in):                   # episodes with the same count share their device calls
         eps = np.nonzero(n_in == A)[0]
         A = int(A)
@@ -735,7 +816,14 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             ctx = engine.encode(b["x_st"][ei, rows].reshape(n, F, 6), b["nbr_sum"][ei, rows].reshape(n, 2, F, 6),
                                 b["edge_mask"][ei, rows].reshape(n, 2),
                                 first_index=None if ff is None else b["first_index"][ei, rows].reshape(-1)).reshape(len(eps), A, -1)
-            pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
+            if R and A:
+                (_, pos, slots, episodes), _ = repeat_in_fp32(lambda p: engine.denoise_reject(
+                    ctx, p0, dt=time_step, precision=p, threshold=collision_threshold, max_rounds=R, want_vel=False,
+                    want_pos=route.rank != "device_resident", **nz), precision)
+                if stats is not None:
+                    stats["episodes"][eps], stats["slots"][eps] = episodes, slots
+            else:
+                pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
             sel, lw = rank_samples(engine, route.rank, pos, k, (len(eps), A, K, H))
         forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], sel, lw, b["cv"][eps], pose_now[eps], k, K)
     if absent:

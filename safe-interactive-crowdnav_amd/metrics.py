@@ -256,16 +256,67 @@ def summarise_masked(agent: np.ndarray, cut: np.ndarray, scene: np.ndarray) -> D
     return out
 
 
-def summarise(agent: np.ndarray, scene: np.ndarray) -> Dict[str, float]:
+def summarise(agent: np.ndarray, scene: np.ndarray, rejection=None) -> Dict[str, float]:
     """The means the reference prints after an evaluation (mid.py:965-1003) from the rows of all episodes: agent [..., 10],
     scene [..., 6].  Plain ``np.mean`` as there: one agent without a KDE makes ``kde`` (and the most-likely columns) NaN; the
-    number of such rows comes back as ``nan_rows``."""
+    number of such rows comes back as ``nan_rows``.  ``rejection`` = the (num_iter, colliding, fixed) of ``rejection_totals``: the
+    reference's sentence about them (mid.py:1046-1049) is printed and the three come back under ``rejection_*``."""
     agent = np.asarray(agent, dtype=np.float64).reshape(-1, len(STAT_AGENT_COLUMNS))
     scene = np.asarray(scene, dtype=np.float64).reshape(-1, len(STAT_SCENE_COLUMNS))
     out = {k: float(np.mean(agent[:, STAT_AGENT_COLUMNS.index(c)])) for k, c in _SUMMARY_AGENT.items()}
     out.update({k: float(np.mean(scene[:, STAT_SCENE_COLUMNS.index(c)])) for k, c in _SUMMARY_SCENE.items()})
     out["nan_rows"] = int(np.isnan(agent[:, STAT_AGENT_COLUMNS.index("kde_nll")]).sum())
+    if rejection is not None:
+        num_iter, colliding, fixed = (int(v) for v in rejection)
+        print(rejection_sentence(colliding, fixed))
+        out.update(rejection_num_iter=num_iter, rejection_colliding=colliding, rejection_fixed=fixed)
     return out
+
+
+def rejection_totals(episodes) -> tuple:
+    """The three counts ``DiffusionTraj.sample`` returns behind its samples (MID/models/diffusion.py:606-613; placeholders there) from the
+    ``episodes`` [..., 3] rows of ``JmidEngine.denoise_reject`` = (colliding at round 0, fixed, last round rerun):
+    -> (num_iter = the largest round over the batch, samples with collisions, samples fixed)."""
+    ep = np.asarray(episodes.detach().cpu() if hasattr(episodes, "detach") else episodes).reshape(-1, 3).astype(np.int64)
+    if ep.shape[0] == 0:
+        return 0, 0, 0
+    return int(ep[:, 2].max()), int(ep[:, 0].sum()), int(ep[:, 1].sum())
+
+
+def rejection_sentence(colliding: int, fixed: int) -> str:
+    """The line the reference prints after an evaluation with constraints (MID/mid.py:1048)."""
+    return f"Rejection sampling fixed {int(fixed)} samples out of {int(colliding)} samples with collisions"
+
+
+def fill_slots(acceptable_by_round):
+    """The pairing rule of collision-free sampling (include/jmid_hip.h, ``jmid_denoise_reject_seeded``) for ONE episode, the host twin of
+    the device loop.  ``acceptable_by_round``: a callable j -> bool [K] (the acceptability of the K candidates of round j, asked for
+    round 0 and then only for the rounds in which the episode is rerun; None ends the loop: ``max_rounds`` is reached), or a sequence
+    of such rows, whose length is ``max_rounds`` + 1.
+    Round 0: slot s holds candidate s, bad = the unacceptable slots.  Round j >= 1, only while bad is not empty: the i-th smallest bad
+    slot takes the i-th smallest acceptable candidate, i < min(|bad|, |good|).
+    -> (slots int32 [K, 3] = (round, candidate, still not acceptable), episode int32 [3] = (bad at round 0, fixed, last round rerun))."""
+    if callable(acceptable_by_round):
+        ask = acceptable_by_round
+    else:
+        rows = [np.asarray(r, dtype=bool) for r in acceptable_by_round]
+        ask = lambda j: rows[j] if j < len(rows) else None
+    ok0 = np.asarray(ask(0), dtype=bool)
+    K = ok0.size
+    slots = np.stack([np.zeros(K, np.int32), np.arange(K, dtype=np.int32), (~ok0).astype(np.int32)], axis=1)
+    episode = np.array([int((~ok0).sum()), 0, 0], dtype=np.int32)
+    j = 1
+    while slots[:, 2].any():
+        ok = ask(j)
+        if ok is None:
+            break
+        bad, good = np.flatnonzero(slots[:, 2]), np.flatnonzero(np.asarray(ok, dtype=bool))
+        n = min(bad.size, good.size)
+        slots[bad[:n], 0], slots[bad[:n], 1], slots[bad[:n], 2] = j, good[:n], 0
+        episode[1] += n
+        episode[2] = j
+        j += 1
+    return slots, episode
 
 
 def collision_statistics_host(pos: np.ndarray, threshold: float = COLLISION_THRESHOLD):

@@ -29,10 +29,21 @@ from .engine import JmidEngine
 
 def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bool, point_dim: int = 2,
            flexibility: float = 0.0, ret_traj: bool = False, sampling: str = "ddpm", step: int = 100,
-           precision: str = "f32", _integrate=None, seed: Optional[int] = None) -> Tuple[np.ndarray, int, int, int, int]:
+           precision: str = "f32", _integrate=None, seed: Optional[int] = None, with_constraints: bool = False,
+           collision_threshold: float = 0.2, max_rounds: int = 3) -> Tuple[np.ndarray, int, int, int, int]:
     """-> (vel [sample, B, num_points, 2] float32, number_of_steps, 0, 0, 0)   (diffusion.py:603-613).
     ``_integrate`` = (p0 [B, 2], dt): used by ``generate`` - the same call also integrates on the device (integrate_kernel) and
-    the first element of the result is the positions instead."""
+    the first element of the result is the positions instead.
+    ``with_constraints=True`` (the reference's flag, whose loop body is gone there): collision-free sampling,
+    ``JmidEngine.denoise_reject`` - a sample in which two agents come closer than ``collision_threshold`` is redrawn up to
+    ``max_rounds`` times (sample i is episode i with K = 1, so a redraw is exactly the reference's per-sample loop), and the last three
+    values are the real (num_iter, samples with collisions, samples fixed) of ``metrics.rejection_totals``.  Needs ``seed=``,
+    ``bestof=True``, ``sampling="ddim"`` and positions (``_integrate``: ``generate`` passes it); ``ValueError`` otherwise."""
+    if with_constraints:
+        missing = [w for w, ok in (("seed=", seed is not None), ("bestof=True", bool(bestof)), ('sampling="ddim"', sampling == "ddim"),
+                                   ("positions (generate, or _integrate)", _integrate is not None)) if not ok]
+        if missing:
+            raise ValueError("with_constraints=True needs " + ", ".join(missing))
     if point_dim != 2:
         raise ValueError("point_dim must be 2")
     if ret_traj:
@@ -51,6 +62,11 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
         number_of_steps = sample * (engine.schedule.num_steps // stride + 1)
         if _integrate is not None:
             p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(_integrate[0], dtype=np.float32)[None], (sample, B, 2)))
+            if with_constraints:
+                from .metrics import rejection_totals
+                _, pos, _, episodes = engine.denoise_reject(ctx_e, p0, dt=float(_integrate[1]), precision=precision, threshold=collision_threshold,
+                                                            max_rounds=max_rounds, want_vel=False, **nz)
+                return (pos.reshape(sample, B, num_points, 2), number_of_steps, *rejection_totals(episodes))
             _, pos = engine.denoise(None, ctx_e, p0, dt=float(_integrate[1]), precision=precision, want_vel=False, **nz)
             return pos.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
         vel, _ = engine.denoise(None, ctx_e, None, precision=precision, want_pos=False, **nz)
@@ -76,12 +92,15 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
 
 
 def generate(engine: JmidEngine, context, p0, dt: float, num_points: int, sample_n: int, bestof: bool,
-             flexibility: float = 0.0, sampling: str = "ddpm", step: int = 100, precision: str = "f32", seed: Optional[int] = None):
+             flexibility: float = 0.0, sampling: str = "ddpm", step: int = 100, precision: str = "f32", seed: Optional[int] = None,
+             with_constraints: bool = False, collision_threshold: float = 0.2, max_rounds: int = 3):
     """Tail of ``AutoEncoder.generate``: ``sample`` + ``SingleIntegrator.integrate_samples``
     (``single_integrator.py:290-321``): pos = cumsum(vel, T) * dt + p0[b].  ``context`` [B, ctx] is the encoder
-    output (``JmidEngine.encode``), ``p0`` [B, 2] the current positions.  -> (pos [sample, B, T, 2], steps, 0, 0, 0)."""
+    output (``JmidEngine.encode``), ``p0`` [B, 2] the current positions.  -> (pos [sample, B, T, 2], steps, 0, 0, 0); with
+    ``with_constraints=True`` (see ``sample``) the zeros are (num_iter, samples with collisions, samples fixed)."""
     pos, nsteps, a, b, c = sample(engine, num_points, context, sample_n, bestof, flexibility=flexibility,
-                                  sampling=sampling, step=step, precision=precision, _integrate=(p0, dt), seed=seed)
+                                  sampling=sampling, step=step, precision=precision, _integrate=(p0, dt), seed=seed,
+                                  with_constraints=with_constraints, collision_threshold=collision_threshold, max_rounds=max_rounds)
     return np.asarray(pos, dtype=np.float32), nsteps, a, b, c
 
 

@@ -1,0 +1,110 @@
+"""What collision-free sampling costs per ``predict_ret_best()`` (docs/NOTEBOOK.md section 32), on ORCA circle-crossing scenes
+(episodes.py), at the shipped point (N = 3, K = 100 -> 15, H = 8, 2 steps) and cfg2 (N = 5, K = 20 -> 20, H = 12, 50 steps), seeded
+random-init weights at the shipped width.  Three forecasters in ONE process, called alternately on the same frames:
+  (a) rng_compat="device" on the staged route (precision given, self check off) - the route the flag takes, without the flag
+  (b) collision_free_rounds=3 at threshold 0: nothing collides - the cost of asking (one flags launch, the slot table, one small download)
+  (c) collision_free_rounds=3 at threshold 0.2: the reference's threshold - collision rate, rounds, fixed / colliding, latency
+(a) is held on the staged route (``plan_route`` alone would chain it into one entry) so that the three differ in the denoise stage only:
+all three encode, denoise and, at k < K, rank on the device from the resident positions.
+Every figure is the median over the measured calls after warm-up; the three variants see the same frames in the same order and are
+interleaved call by call, so clock and thermal drift hit them alike.  Run on the GPU box:
+    python tools/reject_timing.py [--precision f16mx] [--calls 40] [--episodes 4]"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from safe_interactive_crowdnav_amd import episodes as EP
+from safe_interactive_crowdnav_amd.forecaster import HumanTrajectoryForecasterSim, write_configs
+from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims
+
+POINTS = {"shipped": (3, 100, 15, 8, 2), "cfg2": (5, 20, 20, 12, 50)}      # N, K, k, H, steps
+
+
+class St:
+    def __init__(self, p):
+        self.position = (float(p[0]), float(p[1]))
+
+
+class Staged(HumanTrajectoryForecasterSim):
+    """Variant (a): today's seeded forecaster held on the staged route (``plan_route`` would chain it): encode, denoise, rank."""
+
+    def _predict_ret_best(self):
+        import safe_interactive_crowdnav_amd.forecaster as FC
+        keep = FC.plan_route
+        FC.plan_route = lambda **kw: keep(**kw)._replace(run="staged")
+        try:
+            return super()._predict_ret_best()
+        finally:
+            FC.plan_route = keep
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", default="f16mx")
+    ap.add_argument("--calls", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--episodes", type=int, default=4)
+    args = ap.parse_args()
+    weights = JMIDWeights.from_seed(NetDims(ctx_dim=256), 5)
+    out = {}
+    for point, (N, K, k, H, step) in POINTS.items():
+        sim = EP.simulate_circle_crossing(args.episodes, N, 6 + args.warmup + args.calls, seed=11)
+        with tempfile.TemporaryDirectory() as td:
+            env, yp = write_configs(td, joint=True, ctx_dim=256, N=N, K=K, k_ret=k, H=H, step=step, time_step=0.25)
+            common = dict(weights=weights, precision=args.precision, self_check=False, rng_compat="device", seed=7)
+            variants = {"a_staged": Staged(env, yp, **common),
+                        "b_threshold_0": HumanTrajectoryForecasterSim(env, yp, collision_free_rounds=3, collision_threshold=0.0, **common),
+                        "c_threshold_0.2": HumanTrajectoryForecasterSim(env, yp, collision_free_rounds=3, collision_threshold=0.2, **common)}
+        ms = {name: [] for name in variants}
+        totals = {name: np.zeros(3, dtype=np.int64) for name in variants}
+        rounds, calls_with_collision = [], 0
+        for e in range(args.episodes):
+            for f in variants.values():
+                f.prev_states, f.prev_robot_states = [[] for _ in range(N)], []
+            for i in range(6 + args.warmup + args.calls):
+                for f in variants.values():
+                    f.update_state_hists(St(sim["robot_xy"][e, i]), [St(p) for p in sim["human_xy"][e, i]], float(sim["stamps"][i]))
+                if i < 5:
+                    continue
+                order = list(variants.items())
+                order = order[i % 3:] + order[:i % 3]                       # alternate who goes first
+                for name, f in order:
+                    t0 = time.perf_counter()
+                    f.predict_ret_best()
+                    dt = 1e3 * (time.perf_counter() - t0)
+                    if i >= 5 + args.warmup:
+                        ms[name].append(dt)
+                        if f.rejection is not None:
+                            totals[name] += np.array([0, f.rejection[1], f.rejection[2]])
+                            if name.startswith("c"):
+                                rounds.append(f.rejection[0])
+                                calls_with_collision += f.rejection[1] > 0
+        n = len(ms["a_staged"])
+        res = {name: {"median_ms": round(float(np.median(v)), 3), "p10_ms": round(float(np.percentile(v, 10)), 3),
+                      "p90_ms": round(float(np.percentile(v, 90)), 3)} for name, v in ms.items()}
+        res["calls"] = n
+        res["b_minus_a_ms"] = round(res["b_threshold_0"]["median_ms"] - res["a_staged"]["median_ms"], 3)
+        res["c_minus_a_ms"] = round(res["c_threshold_0.2"]["median_ms"] - res["a_staged"]["median_ms"], 3)
+        res["c"] = {"samples": n * K, "samples_colliding": int(totals["c_threshold_0.2"][1]), "samples_fixed": int(totals["c_threshold_0.2"][2]),
+                    "collision_rate": round(float(totals["c_threshold_0.2"][1]) / (n * K), 5), "calls_with_a_collision": int(calls_with_collision),
+                    "rounds_mean": round(float(np.mean(rounds)), 3), "rounds_max": int(np.max(rounds))}
+        res["erange_fallbacks"] = sum(f.erange_fallbacks for f in variants.values())
+        res["workload"] = f"N={N}, K={K} -> {k}, H={H}, {step} steps, {args.precision}, ORCA circle crossing, {args.episodes} episodes"
+        out[point] = res
+        print(point, json.dumps(res), flush=True)
+    try:      # the matrix rate this box sustains at its power cap, next to the figures (tools/mfma_peak.hip, as bench.py reports it)
+        import bench
+        out["sustained_mfma"] = bench.sustained_mfma_tflops()
+    except Exception:
+        out["sustained_mfma"] = None
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
