@@ -275,6 +275,38 @@ int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, con
 int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, double threshold,
                               float* pair_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem);
 
+/* Wall statistics of joint samples: how close each agent's forecast path comes to every wall segment and which agents walk into one.
+ * The predicate is the reference simulator's own: constrain_agent_action_exact (crowd_sim_plus/envs/crowd_sim_plus.py:885-893) takes an
+ * agent's step as a line segment, and the step hits a wall when closest_distance_between_line_segments(wall, step) - radius < 0
+ * (crowd_sim_plus/envs/utils/utils_plus.py:205-338).
+ *   Walls     walls [L, 4] float64 {x1, y1, x2, y2}, 0 <= L <= 64: a HOST array in both memory modes, like episode_ids (the library
+ *             keeps a device copy for the call).  crowd_env.static_obstacles(rule)[0].reshape(-1, 4) as it is.  A non-finite
+ *             coordinate is JMID_EINVAL.  A zero-length wall is a point, handled as the reference handles it (:222-224: it goes through
+ *             the parallel branch and yields the distance to the END of the step)
+ *   Paths     agent a of sample (e, k) walks the segments pos[t-1] -> pos[t], t = 1 .. T-1.  With p0 [E, A, 2] (may be NULL) it walks
+ *             p0 -> pos[0] first: T segments, in step order.  The step from the present position into the forecast is where a wall
+ *             right next to a pedestrian is crossed
+ *   Distance  d(a, l) = the minimum over the agent's segments of the reference's closest distance between wall l and the segment, in
+ *             fp64 on the fp32 positions, with the reference's branches (segments shorter than 1e-8 are points; exactly parallel
+ *             segments with the three sub-cases of :242-291; crossing lines with both clamps) - no other formula, so the conditioning
+ *             near parallel segments is the reference's.  A segment with a non-finite end makes the agent's d(a, .) NaN (the minimum
+ *             keeps a NaN)
+ *   Hit       agent a hits wall l iff d(a, l) - radius < 0 in fp64; NaN never hits.  radius: a finite double >= 0
+ *   pos         [E, K, A, T, 2], or NULL: the resident positions, under exactly the rules of jmid_collision_statistics
+ *   dist_out    [E, K, A, L] d(a, l); may be NULL
+ *   agent_out   [E, K, A] bytes, 1 = the agent hits some wall; may be NULL
+ *   sample_out  [E, K, 3] = {min_clear, n_agents_hitting, n_hits}; may be NULL.  min_clear = the smallest d of the sample (a NaN decides
+ *               it), n_hits = the number of (agent, wall) pairs that hit
+ *   scene_out   [E, 5] = {wall_hit_rate, agent_wall_hit_rate, min_clear_min, min_clear_mean, min_clear_std}; may be NULL.  The
+ *               definitions of jmid_collision_statistics' scene row with "hits a wall" for "collides"
+ * L = 0: min_clear = +inf, counts and rates 0, min_clear_std NaN (what jmid_collision_statistics gives for A = 1).
+ * There is no "nearest wall" index: walls share corner points and a path may cross two walls (a crossing's distance is a cancellation of
+ * about 1e-17), so the index would be decided by rounding; take the argmin of dist_out where it is wanted.
+ * fp64 inside, fixed-order reductions, no atomics: a row is bit-identical whatever batch it is part of and in both memory modes.
+ * 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64, 0 <= L <= 64, at least one output (JMID_EINVAL otherwise). */
+int jmid_wall_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* p0, int L, const double* walls,
+                         double radius, float* dist_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem);
+
 /* Joint-KDE ranking of the K sampled futures of every episode and selection of the k most likely ones:
  * get_most_likely_samples (sicnav_diffusion/JMID/mid_sim_wrapper.py:14-169, the joint branch :20-21 the predictor always takes;
  * called from predict_ret_best when num_ret_samples < K, :487-492), which the reference runs on its GPU when it has one (:26-30).
@@ -603,6 +635,20 @@ int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t se
 int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0,
                                const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds,
                                float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out, int mem);
+
+/* jmid_denoise_reject_seeded with walls: a joint sample is ACCEPTABLE iff it is acceptable there AND jmid_wall_statistics at (walls,
+ * radius, the call's p0: T segments per agent) gives it n_agents_hitting == 0 AND a min_clear that is not NaN.  Everything else of the rule
+ * is that entry's: the rounds, the ascending fill, the slots that stay flagged, slot_out / episode_out (whose counts now speak of slots
+ * that are not acceptable for either cause), what pos = NULL means afterwards, the refusals, DDIM and a uniform agent count only.
+ *   walls [L, 4] float64, a HOST array, 0 <= L <= 64, finite; radius finite and >= 0 (JMID_EINVAL otherwise)
+ *   cause_out [E, 2] int32 = {slots whose round-0 sample fails the pedestrian predicate, slots whose round-0 sample fails the wall
+ *             predicate}; a slot may count in both; may be NULL
+ * The wall kernel runs next to the collision kernel on each round's candidates, and the one small download per round stays the only one.
+ * L = 0 is bit-identical to jmid_denoise_reject_seeded in every output, with cause_out[:, 1] = 0: that entry IS this one at L = 0. */
+int jmid_denoise_reject_walls_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0,
+                                     const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds, int L,
+                                     const double* walls, double radius, float* vel_out, float* pos_out, int32_t* slot_out,
+                                     int32_t* episode_out, int32_t* cause_out, int mem);
 
 /* jmid_predict_scene and jmid_forecast_scene with (seed, episode_ids [E]) in place of x_T: x_T is draw 0 with rows = K * A, filled on the
  * device (nothing but bw is uploaded).  Everything else as their namesakes, whose chain they share: bit-identical to them fed

@@ -1,8 +1,23 @@
 // libjmid_hip.so -- the C ABI proper (include/jmid_hip.h): handle lifetime, the compute entry points, knobs, streams.
 #include "jmid_ctx.hpp"
 #include "collision_stats.hpp"
+#include "wall_stats.hpp"
 
 namespace jmid_host {
+
+// The wall segments of a call: a HOST array [L, 4] fp64 in both memory modes.  Checked here (finite, 0 <= L <= 64) and sent ahead of the
+// kernels through the handle's own staging; *dev: where they lie on the device (null with L = 0)
+int upload_walls(jmid_ctx* h, int L, const double* walls, const double** dev, const std::string& who) {
+    *dev = nullptr;
+    if (L < 0 || L > WLS_MAX_L) return fail(h, JMID_EINVAL, who + " supports 0 <= L <= 64 walls");
+    if (L == 0) return 0;
+    if (!walls) return fail(h, JMID_EINVAL, who + ": null walls with L > 0");
+    for (int i = 0; i < L * 4; ++i)
+        if (!std::isfinite(walls[i])) return fail(h, JMID_EINVAL, who + ": a wall has a non-finite coordinate");
+    if (int rc = h->wall_seg.upload(h, walls, L * 8, who.c_str())) return rc;
+    *dev = h->wall_seg.get<double>();
+    return 0;
+}
 
 std::string& thread_error() {
     static thread_local std::string e;
@@ -415,39 +430,46 @@ struct RejectIo {
     Arr<float> ctx, p0;                        // [E, A, ctx_dim] | [E, A, 2] (host mode)
     Arr<float> acc_vel, acc_pos;               // [E, K, A, T, 2] twice (acc_vel: when velocities are asked for)
     Arr<float> g_ctx, g_p0, cand_vel, cand_pos;      // a rerun of at most E episodes (none with max_rounds = 0)
-    Arr<double> ws;                            // [E, K, 2]
+    Arr<double> ws, ws_wall;                   // [E, K, 2] each (ws_wall: with walls)
     Arr<int> slots, episodes, remaining;       // [E, K, 3] | [E, 3] | [E]
-    Arr<int> list, flag;                       // [1 + E] | one word: the download block
+    Arr<int> list, flag, cause;                // [1 + E] | one word | [E, 2]: the download block (the causes of round 0 ride along)
     size_t down_bytes = 0;
 };
-size_t reject_io(const jmid_ctx* h, int E, int A, int K, int T, bool host, bool vel, bool rerun, char* base, RejectIo* out) {
+size_t reject_io(const jmid_ctx* h, int E, int A, int K, int T, bool host, bool vel, bool rerun, bool with_walls, char* base, RejectIo* out) {
     const size_t EA = (size_t)E * A, M2 = (size_t)E * K * A * T * 2, Er = rerun ? 1 : 0;
     Carver c(base);
     RejectIo io{};
     io.ctx = c.arr(host ? EA * h->ctx_dim : 0); io.p0 = c.arr(host ? EA * 2 : 0);
     io.acc_vel = c.arr(vel ? M2 : 0); io.acc_pos = c.arr(M2);
     io.g_ctx = c.arr(Er * EA * h->ctx_dim); io.g_p0 = c.arr(Er * EA * 2); io.cand_vel = c.arr(vel ? Er * M2 : 0); io.cand_pos = c.arr(Er * M2);
-    io.ws = c.arr<double>((size_t)E * K * CLS_WS_COLS);
+    io.ws = c.arr<double>((size_t)E * K * CLS_WS_COLS); io.ws_wall = c.arr<double>(with_walls ? (size_t)E * K * WLS_WS_COLS : 0);
     io.slots = c.arr<int>((size_t)E * K * REJ_SLOT_COLS); io.episodes = c.arr<int>((size_t)E * REJ_EPISODE_COLS); io.remaining = c.arr<int>(E);
     const size_t down = c.off;
-    io.list = c.arr<int>((size_t)E + 1); io.flag = c.arr<int>(1);
+    io.list = c.arr<int>((size_t)E + 1); io.flag = c.arr<int>(1); io.cause = c.arr<int>((size_t)E * 2);
     io.down_bytes = c.off - down;
     if (out) *out = io;
     return c.off;
 }
 
-// jmid_denoise_reject_seeded after its argument checks.  Every round is one seeded denoise call through run_network (a stage: no
-// caller-stream ordering, the range flag comes with the round's one download), the flags of its candidates, the pairing, the compaction.
-int reject_loop(jmid_ctx* h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx, const float* p0,
-                float dt, int precision, double threshold, int max_rounds, float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out,
-                int mem) {
-    const char* who = "jmid_denoise_reject_seeded";
-    const bool host = mem == JMID_MEM_HOST, vel = vel_out != nullptr, split = precision != JMID_PREC_F32;
+// The walls of a rejection call: the segments on the device (upload_walls) and the radius; L = 0: no wall predicate
+struct RejectWalls {
+    int L = 0;
+    const double* dev = nullptr;
+    double radius = 0.0;
+};
+
+// jmid_denoise_reject_seeded (no walls) and jmid_denoise_reject_walls_seeded after their argument checks.  Every round is one seeded
+// denoise call through run_network (a stage: no caller-stream ordering, the range flag comes with the round's one download), the flags of
+// its candidates - the collision kernel and, with walls, the wall kernel next to it -, the pairing, the compaction.
+int reject_loop(jmid_ctx* h, const char* who, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx,
+                const float* p0, float dt, int precision, double threshold, int max_rounds, const RejectWalls& walls, float* vel_out,
+                float* pos_out, int32_t* slot_out, int32_t* episode_out, int32_t* cause_out, int mem) {
+    const bool host = mem == JMID_MEM_HOST, vel = vel_out != nullptr, split = precision != JMID_PREC_F32, with_walls = walls.L > 0;
     h->last_pos = nullptr;
     if (int rc = order_in(h, mem)) return rc;
-    if (int rc = h->reject_ws.reserve(h, reject_io(h, E, A, K, T, host, vel, max_rounds > 0, nullptr, nullptr), who)) return rc;
+    if (int rc = h->reject_ws.reserve(h, reject_io(h, E, A, K, T, host, vel, max_rounds > 0, with_walls, nullptr, nullptr), who)) return rc;
     RejectIo io;
-    reject_io(h, E, A, K, T, host, vel, max_rounds > 0, h->reject_ws.p, &io);
+    reject_io(h, E, A, K, T, host, vel, max_rounds > 0, with_walls, h->reject_ws.p, &io);
     if (int rc = h->reject_pin.reserve(h, io.down_bytes, who)) return rc;
     const int* pin = h->reject_pin.as<int>();
     const size_t flag_word = (size_t)((const char*)io.flag.p - (const char*)io.list.p) / sizeof(int);
@@ -458,8 +480,8 @@ int reject_loop(jmid_ctx* h, int E, int A, int K, int T, uint64_t seed, const ui
     }
     HIPCHK(h, hipMemsetAsync(io.flag.p, 0, sizeof(int), h->stream));
     RejectArgs g{};
-    g.ws = io.ws; g.cand_pos = io.cand_pos; g.cand_vel = io.cand_vel; g.acc_pos = io.acc_pos; g.acc_vel = io.acc_vel;
-    g.slots = io.slots; g.episodes = io.episodes; g.remaining = io.remaining; g.list = io.list;
+    g.ws = io.ws; g.ws_wall = io.ws_wall; g.cand_pos = io.cand_pos; g.cand_vel = io.cand_vel; g.acc_pos = io.acc_pos; g.acc_vel = io.acc_vel;
+    g.slots = io.slots; g.episodes = io.episodes; g.remaining = io.remaining; g.cause = io.cause; g.list = io.list;
     g.ctx = ctx; g.p0 = p0; g.g_ctx = io.g_ctx; g.g_p0 = io.g_p0;
     g.E = E; g.K = K; g.n = A * T * 2; g.n_ctx = A * h->ctx_dim; g.n_p0 = A * 2;
     std::vector<uint32_t> ids(episode_ids, episode_ids + E);
@@ -481,6 +503,12 @@ int reject_loop(jmid_ctx* h, int E, int A, int K, int T, uint64_t seed, const ui
             cs.pos = d.pos_out; cs.ws = io.ws; cs.threshold = threshold;
             cs.E = n_run; cs.A = A; cs.K = K; cs.T = T;
             HIPCHK(h, launch_collision_stats(cs, h->stream));
+            if (with_walls) {
+                WallStatsArgs ww{};
+                ww.pos = d.pos_out; ww.p0 = d.p0; ww.walls = walls.dev; ww.ws = io.ws_wall; ww.radius = walls.radius;
+                ww.E = n_run; ww.A = A; ww.K = K; ww.T = T; ww.L = walls.L;
+                HIPCHK(h, launch_wall_stats(ww, h->stream));
+            }
             g.round = j;
             HIPCHK(h, j ? launch_reject_accept(g, n_run, h->stream) : launch_reject_init(g, h->stream));
             HIPCHK(h, launch_reject_compact(g, h->stream));
@@ -501,6 +529,10 @@ int reject_loop(jmid_ctx* h, int E, int A, int K, int T, uint64_t seed, const ui
     if (pos_out) HIPCHK(h, hipMemcpyAsync(pos_out, io.acc_pos.p, io.acc_pos.bytes(), kout, h->stream));
     if (slot_out) HIPCHK(h, hipMemcpyAsync(slot_out, io.slots.p, io.slots.bytes(), kout, h->stream));
     if (episode_out) HIPCHK(h, hipMemcpyAsync(episode_out, io.episodes.p, io.episodes.bytes(), kout, h->stream));
+    if (cause_out) {      // host mode: the causes came with the rounds' download - no copy of their own
+        if (host) std::memcpy(cause_out, pin + ((const char*)io.cause.p - (const char*)io.list.p) / sizeof(int), io.cause.bytes());
+        else HIPCHK(h, hipMemcpyAsync(cause_out, io.cause.p, io.cause.bytes(), kout, h->stream));
+    }
     if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
     // the accepted set is what pos = NULL consumers see, under jmid_denoise's forgetting rules (every later denoise call and every
     // host-mode entry that clears last_pos forgets it, although this block itself would survive them)
@@ -828,6 +860,38 @@ int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const
     {
         ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_collision_stats(g, h->stream));
+    }
+    return st.end();
+}
+
+int jmid_wall_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* p0, int L, const double* walls,
+                         double radius, float* dist_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
+    if (!h || E <= 0) return fail(h, JMID_EINVAL, "bad argument");
+    const std::string w("jmid_wall_statistics");
+    if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
+        return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(h, JMID_EINVAL, w + ": the radius must be finite and >= 0");
+    if (!dist_out && !agent_out && !sample_out && !scene_out) return fail(h, JMID_EINVAL, w + ": every output is NULL");
+    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
+    HIPCHK(h, hipSetDevice(h->device));
+    WallStatsArgs g{};
+    if (int rc = upload_walls(h, L, walls, &g.walls, w)) return rc;
+    if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
+    g.E = E; g.A = A; g.K = K; g.T = T; g.L = L;
+    g.radius = radius;
+    Staging st(h, mem, h->kde_ws, "jmid_wall_statistics");
+    st.scratch(&g.ws, (size_t)E * K * WLS_WS_COLS * 8);      // the per-sample fp64 values the scene kernel reduces
+    if (pos) st.in(&g.pos, pos, (size_t)E * K * A * T * 2);
+    else g.pos = h->last_pos;
+    if (p0) st.in(&g.p0, p0, (size_t)E * A * 2);
+    if (dist_out && L > 0) st.out(&g.dist_out, dist_out, (size_t)E * K * A * L);
+    if (agent_out) st.out(&g.agent_out, agent_out, (size_t)E * K * A);
+    if (sample_out) st.out(&g.sample_out, sample_out, (size_t)E * K * WLS_SAMPLE_COLS);
+    if (scene_out) st.out(&g.scene_out, scene_out, (size_t)E * WLS_SCENE_COLS);
+    if (int rc = st.begin()) return rc;
+    {
+        ProfScope ps(h, KC_EVAL_STATS, h->stream);
+        HIPCHK(h, launch_wall_stats(g, h->stream));
     }
     return st.end();
 }
@@ -1272,11 +1336,12 @@ int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t se
     return run_network(h, c);
 }
 
-int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx,
-                               const float* p0, float dt, int precision, double threshold, int max_rounds, float* vel_out, float* pos_out,
-                               int32_t* slot_out, int32_t* episode_out, int mem) {
+// jmid_denoise_reject_seeded (L = 0, walls and cause_out null) and jmid_denoise_reject_walls_seeded: the argument checks, then the loop
+static int reject_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0,
+                        const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds, int L, const double* walls,
+                        double radius, float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out, int32_t* cause_out, int mem) {
     if (!h) return JMID_EINVAL;
-    const std::string w("jmid_denoise_reject_seeded");
+    const std::string w(who);
     if (int rc = check_ready(h)) return rc;
     if (h->ddpm) return fail(h, JMID_EINVAL, w + " samples with DDIM: under a DDPM table the draws 1.. are the steps' z");
     if (E < 1 || K < 1 || K > REJ_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
@@ -1290,9 +1355,28 @@ int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint
     CallMode mode;
     if (!call_mode(precision, &mode)) return fail(h, JMID_EINVAL, w + ": precision must be JMID_PREC_F32, JMID_PREC_F16X3, JMID_PREC_F16X2 or JMID_PREC_F16MX");
     if (mem != JMID_MEM_HOST && mem != JMID_MEM_DEVICE) return fail(h, JMID_EINVAL, w + ": bad mem");
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(h, JMID_EINVAL, w + ": the radius must be finite and >= 0");
     HIPCHK(h, hipSetDevice(h->device));
-    return reject_loop(h, E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, vel_out, pos_out, slot_out,
-                       episode_out, mem);
+    RejectWalls rw;
+    rw.L = L; rw.radius = radius;
+    if (int rc = upload_walls(h, L, walls, &rw.dev, w)) return rc;
+    return reject_loop(h, who, E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, rw, vel_out, pos_out, slot_out,
+                       episode_out, cause_out, mem);
+}
+
+int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx,
+                               const float* p0, float dt, int precision, double threshold, int max_rounds, float* vel_out, float* pos_out,
+                               int32_t* slot_out, int32_t* episode_out, int mem) {
+    return reject_entry(h, "jmid_denoise_reject_seeded", E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, 0,
+                        nullptr, 0.0, vel_out, pos_out, slot_out, episode_out, nullptr, mem);
+}
+
+int jmid_denoise_reject_walls_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0,
+                                     const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds, int L,
+                                     const double* walls, double radius, float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out,
+                                     int32_t* cause_out, int mem) {
+    return reject_entry(h, "jmid_denoise_reject_walls_seeded", E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds,
+                        L, walls, radius, vel_out, pos_out, slot_out, episode_out, cause_out, mem);
 }
 
 int jmid_noise_fill(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out, int mem) {

@@ -200,6 +200,8 @@ struct jmid_ctx {
     jmid_host::Block frames_dev;
     // the seeded entry points: the call's episode ids on the device (the fill kernel reads them there); the padded ones: its agent counts
     jmid_host::HostArray noise_ids, nag;
+    // jmid_wall_statistics / jmid_denoise_reject_walls_seeded: the call's wall segments [L, 4] fp64 on the device (two words per value)
+    jmid_host::HostArray wall_seg;
     // jmid_loss: the per-row timesteps of the call on the device (uploaded once per call, as the counts)
     jmid_host::HostArray loss_t;
     // jmid_encode_var: the rows' first history frames; jmid_build_scene_var: the nodes' first frames

@@ -4,6 +4,8 @@
 // loop whose body is gone; check_collision_velocity (MID/models/collision_check_utils.py:100-108) is its predicate.  Here a joint sample
 // is ACCEPTABLE iff collision_sample_kernel (collision_stats.hpp) gives it n_agents_colliding == 0 and a min_dist that is not NaN - read
 // from that kernel's own fp64 per-sample values (CollisionStatsArgs::ws), so the predicate is the one jmid_collision_statistics reports.
+// With walls (jmid_denoise_reject_walls_seeded) it must ALSO have n_agents_hitting == 0 and a min_clear that is not NaN in
+// wall_sample_kernel's per-sample values (WallStatsArgs::ws, wall_stats.hpp); without walls that workspace is null and nothing else is read.
 //
 // A redraw is a whole episode (its K samples are one attention sequence).  Per round:
 //   reject_init_kernel     round 0, one workgroup per episode: the slot table from the flags, the episode's counters
@@ -25,11 +27,13 @@ constexpr int REJ_EPISODE_COLS = 3;    // slots not acceptable at round 0, slots
 
 struct RejectArgs {
     const double* ws;                  // [Er, K, 2] min_dist, n_agents_colliding of the round's candidates (collision_sample_kernel)
+    const double* ws_wall;             // [Er, K, 2] min_clear, n_agents_hitting of the round's candidates (wall_sample_kernel); null: no walls
     const float *cand_pos, *cand_vel;  // [Er, K, n] the rerun's output block (cand_vel null: no velocities were asked for)
     float *acc_pos, *acc_vel;          // [E, K, n] the accepted block
     int* slots;                        // [E, K, 3]
     int* episodes;                     // [E, 3]
     int* remaining;                    // [E] bad slots left
+    int* cause;                        // [E, 2] slots whose round-0 sample fails the pedestrian predicate, the wall predicate
     int* list;                         // [1 + E] the number of episodes to rerun, then their indices, ascending
     const float *ctx, *p0;             // [E, A, ctx_dim], [E, A, 2]
     float *g_ctx, *g_p0;               // [Er, A, ctx_dim], [Er, A, 2] the rerun's input block
@@ -37,9 +41,14 @@ struct RejectArgs {
     int n_ctx, n_p0;                   // A * ctx_dim, A * 2
 };
 
-__device__ __forceinline__ bool rej_acceptable(const double* ws, size_t sample) {
-    const double min_dist = ws[sample * 2], n_agents = ws[sample * 2 + 1];
-    return n_agents == 0.0 && min_dist == min_dist;
+// one predicate on one workspace: no agent counted and a clearance that is not NaN (ws null: nothing to fail)
+__device__ __forceinline__ bool rej_clear(const double* ws, size_t sample) {
+    if (!ws) return true;
+    const double clearance = ws[sample * 2], n_agents = ws[sample * 2 + 1];
+    return n_agents == 0.0 && clearance == clearance;
+}
+__device__ __forceinline__ bool rej_acceptable(const RejectArgs& g, size_t sample) {
+    return rej_clear(g.ws, sample) && rej_clear(g.ws_wall, sample);
 }
 
 // exclusive scan of one count per thread over the thread index (sh [2 * REJ_THREADS]); *total: the sum, in every thread
@@ -64,18 +73,25 @@ static __global__ __launch_bounds__(REJ_THREADS) void reject_init_kernel(RejectA
     __shared__ int sh[2 * REJ_THREADS];
     const int tid = threadIdx.x, e = blockIdx.x, K = g.K;
     const int per = (K + REJ_THREADS - 1) / REJ_THREADS, s0 = min(tid * per, K), s1 = min(s0 + per, K);
-    int nbad = 0;
+    int nbad = 0, nped = 0, nwall = 0;
     for (int s = s0; s < s1; ++s) {
         const size_t q = (size_t)e * K + s;
-        const int bad = rej_acceptable(g.ws, q) ? 0 : 1;
+        const int ped = rej_clear(g.ws, q) ? 0 : 1, wall = rej_clear(g.ws_wall, q) ? 0 : 1;
+        const int bad = ped | wall;
+        nped += ped;
+        nwall += wall;
         g.slots[q * REJ_SLOT_COLS] = 0;
         g.slots[q * REJ_SLOT_COLS + 1] = s;
         g.slots[q * REJ_SLOT_COLS + 2] = bad;
         nbad += bad;
     }
-    int total;
+    int total, tped, twall;
     rej_excl_scan(nbad, sh, tid, &total);
+    rej_excl_scan(nped, sh, tid, &tped);
+    rej_excl_scan(nwall, sh, tid, &twall);
     if (tid == 0) {
+        g.cause[e * 2] = tped;
+        g.cause[e * 2 + 1] = twall;
         g.episodes[e * REJ_EPISODE_COLS] = total;
         g.episodes[e * REJ_EPISODE_COLS + 1] = 0;
         g.episodes[e * REJ_EPISODE_COLS + 2] = 0;
@@ -93,14 +109,14 @@ static __global__ __launch_bounds__(REJ_THREADS) void reject_accept_kernel(Rejec
     int nb = 0, ng = 0;
     for (int s = s0; s < s1; ++s) {
         nb += g.slots[((size_t)e * K + s) * REJ_SLOT_COLS + 2];
-        ng += rej_acceptable(g.ws, (size_t)b * K + s) ? 1 : 0;
+        ng += rej_acceptable(g, (size_t)b * K + s) ? 1 : 0;
     }
     int tb, tg;
     int rb = rej_excl_scan(nb, sh, tid, &tb);      // (every flag has been read behind the scan's first barrier)
     int rg = rej_excl_scan(ng, sh, tid, &tg);
     for (int s = s0; s < s1; ++s) {
         if (g.slots[((size_t)e * K + s) * REJ_SLOT_COLS + 2]) bslot[rb++] = s;
-        if (rej_acceptable(g.ws, (size_t)b * K + s)) good[rg++] = s;
+        if (rej_acceptable(g, (size_t)b * K + s)) good[rg++] = s;
     }
     __syncthreads();
     const int np = min(tb, tg);

@@ -66,6 +66,17 @@ def agent_counts(n_agents, E: int) -> np.ndarray:
     return n
 
 
+def wall_segments(walls) -> np.ndarray:
+    """The ``walls`` argument of the wall entries as the library takes it: a contiguous HOST float64 array [L, 4] = {x1, y1, x2, y2}
+    from [L, 4] or [L, 2, 2] (``crowd_env.static_obstacles(rule)[0]``); None or empty: L = 0.  The library checks the values."""
+    if walls is None:
+        return np.zeros((0, 4), dtype=np.float64)
+    w = np.asarray(walls.detach().cpu() if torch is not None and torch.is_tensor(walls) else walls, dtype=np.float64)
+    if w.size and (w.ndim < 2 or int(np.prod(w.shape[1:])) != 4):
+        raise ValueError("walls must be [L, 4] or [L, 2, 2]")
+    return np.ascontiguousarray(w.reshape(-1, 4))
+
+
 def seeded_noise_args(x_T, seed, episode_ids, E: Optional[int] = None):
     """The noise source of a call: either the caller's ``x_T`` or ``seed`` + ``episode_ids`` (the library's counter generator,
     ``noise.py``), never both.  -> None for an explicit call, else (seed, ids uint32 [E])."""
@@ -352,7 +363,8 @@ class JmidEngine:
         return vel, pos
 
     def denoise_reject(self, ctx: ArrayLike, p0: ArrayLike, seed: int, episode_ids, K: int, T: int, dt: float = 0.25, precision: str = "f32",
-                       threshold: float = 0.2, max_rounds: int = 3, draw0: int = 0, want_vel: bool = True, want_pos: bool = True):
+                       threshold: float = 0.2, max_rounds: int = 3, draw0: int = 0, want_vel: bool = True, want_pos: bool = True,
+                       walls=None, wall_radius: Optional[float] = None):
         """Collision-free sampling (``jmid_denoise_reject_seeded``; the rule stands in include/jmid_hip.h, its host twin is
         ``metrics.fill_slots``): the seeded ``denoise`` of draw number ``draw0``, then up to ``max_rounds`` reruns of the episodes that
         still hold a joint sample in which two agents come closer than ``threshold`` (the predicate of ``collision_statistics``) - an
@@ -360,9 +372,15 @@ class JmidEngine:
         ascending order.  ctx [E, A, ctx_dim], p0 [E, A, 2] -> (vel [E, K, A, T, 2] or None, pos [E, K, A, T, 2] or None, slots [E, K, 3] int32 =
         (round, candidate, still colliding), episodes [E, 3] int32 = (colliding at round 0, fixed, last round rerun)).  DDIM only.
         NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out.  The accepted set stays resident for ``topk(None, ...)`` and the
-        statistics entries."""
+        statistics entries.
+        ``walls`` [L, 4] or [L, 2, 2] with ``wall_radius`` (``jmid_denoise_reject_walls_seeded``): a sample must also keep every agent's
+        path, the step p0 -> pos[0] included, at least ``wall_radius`` away from every wall (the predicate of ``wall_statistics`` with
+        this call's p0); a fifth value comes back, cause [E, 2] int32 = (slots whose round-0 sample fails the pedestrian predicate,
+        the wall predicate).  Without ``walls`` the call, its route and its four values are what they were."""
         if ctx.ndim != 3 or int(ctx.shape[2]) != self.dims.ctx_dim:
             raise ValueError("expected ctx [E, A, ctx_dim]")
+        if (walls is None) != (wall_radius is None):
+            raise ValueError("walls and wall_radius go together (the sampler knows no agent radius)")
         if self.sampling != "ddim":
             raise ValueError("collision-free sampling is DDIM only: under DDPM the draws 1.. are the steps' z")
         if p0 is None:
@@ -377,6 +395,13 @@ class JmidEngine:
         vel = _out((E, K, A, T, 2), device=where) if want_vel else None
         pos = _out((E, K, A, T, 2), device=where) if want_pos else None
         slots, episodes = _out((E, K, 3), np.int32, where), _out((E, 3), np.int32, where)
+        if walls is not None:
+            w, cause = wall_segments(walls), _out((E, 2), np.int32, where)
+            L = int(w.shape[0])
+            self._compute(self._lib.jmid_denoise_reject_walls_seeded, self._h, E, A, K, T, seed, _ptr(ids), int(draw0), bc.ptr, bp.ptr, float(dt),
+                          _lib.PRECISIONS[precision], float(threshold), int(max_rounds), L, _ptr(w) if L else None, float(wall_radius),
+                          _ptr(vel), _ptr(pos), _ptr(slots), _ptr(episodes), _ptr(cause), self._mem(dev))
+            return vel, pos, slots, episodes, cause
         self._compute(self._lib.jmid_denoise_reject_seeded, self._h, E, A, K, T, seed, _ptr(ids), int(draw0), bc.ptr, bp.ptr, float(dt),
                       _lib.PRECISIONS[precision], float(threshold), int(max_rounds), _ptr(vel), _ptr(pos), _ptr(slots), _ptr(episodes),
                       self._mem(dev))
@@ -838,6 +863,37 @@ class JmidEngine:
         outs = [_out(*s, pos.device if dev else None) if s else None for s in shapes]
         self._check(self._lib.jmid_collision_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, float(threshold),
                                                         *[_ptr(o) for o in outs], self._mem(dev)))
+        return tuple(outs)
+
+    def wall_statistics(self, pos: Optional[ArrayLike], walls, radius: float, p0: Optional[ArrayLike] = None,
+                        dims: Optional[Tuple[int, int, int, int]] = None):
+        """Wall statistics of joint samples on the device (``jmid_wall_statistics``; the reference simulator's
+        closest_distance_between_line_segments(wall, step) - radius < 0, include/jmid_hip.h states the definitions).  pos [E, K, A, T, 2],
+        walls [L, 4] or [L, 2, 2] (a host array, ``crowd_env.static_obstacles(rule)[0]``), p0 [E, A, 2] or None (the step from the present
+        position into the forecast is then walked too) -> (dist [E, K, A, L], agent [E, K, A] uint8, sample [E, K, 3], scene [E, 5]) with
+        the columns ``metrics.WALL_SAMPLE_COLUMNS`` / ``metrics.WALL_SCENE_COLUMNS``.  NumPy in -> NumPy out, CUDA tensors in -> CUDA
+        tensors out.  ``pos=None`` with ``dims=(E, A, K, T)`` takes the positions of the preceding ``denoise`` / ``denoise_reject`` call,
+        which are still in the engine's workspace (``p0`` then decides where the outputs live; host arrays without it).
+        K <= 1024, 2 <= T <= 24, A <= 64, L <= 64: ``metrics.wall_statistics_host`` beyond."""
+        w = wall_segments(walls)
+        L = int(w.shape[0])
+        if pos is None:
+            if dims is None:
+                raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
+            E, A, K, T = (int(v) for v in dims)
+            dev, bp = p0 is not None and _is_cuda(p0), None
+        else:
+            dev = _is_cuda(pos)
+            E, K, A, T, _ = (int(v) for v in pos.shape)
+            bp = _Buf(pos, dev)
+        if p0 is not None and tuple(p0.shape) != (E, A, 2):
+            raise ValueError("p0 must be [E, A, 2]")
+        b0 = _Buf(p0, dev) if p0 is not None else None
+        where = (pos if pos is not None else p0).device if dev else None
+        outs = [_out((E, K, A, L), np.float32, where), _out((E, K, A), np.uint8, where), _out((E, K, 3), np.float32, where),
+                _out((E, 5), np.float32, where)]
+        self._check(self._lib.jmid_wall_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, b0.ptr if b0 is not None else None,
+                                                   L, _ptr(w) if L else None, float(radius), *[_ptr(o) for o in outs], self._mem(dev)))
         return tuple(outs)
 
     # ------------------------------------------------------------------ measurement

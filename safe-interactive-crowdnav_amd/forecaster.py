@@ -39,6 +39,11 @@ sampling (``JmidEngine.denoise_reject``; the rule stands in include/jmid_hip.h) 
 than ``collision_threshold`` is redrawn, the whole scene's K samples together, up to R times; the ranking then runs on the accepted
 set.  The route is staged, the draw number advances by ``max(n_steps + 1, R + 1)`` per call, and ``self.rejection`` holds the last
 call's (num_iter, samples with collisions, samples fixed).  A slot that no round could fix keeps its round-0 sample.
+``static_obstacles=`` [L, 2, 2] or [L, 4] with ``wall_radius=`` (opt-in, with ``collision_free_rounds`` > 0; the wall segments the MPC
+receives as ``static_obs``, in the forecasts' world frame): a joint sample in which a pedestrian's path - the step from his present
+position included - comes closer than ``wall_radius`` to a wall is redrawn too (``jmid_denoise_reject_walls_seeded``), and
+``self.rejection`` gains the two cause counts (samples that fail the pedestrian predicate, the wall predicate).  The forecaster knows
+no agent radius: ``wall_radius`` has no default.
 
 Differences from the reference that a caller can observe:
   * the engine (weights on the GPU) is cached across instances: the reference rebuilds the model and reloads the
@@ -72,7 +77,7 @@ import yaml
 
 from . import scene as SC
 from ._lib import EINVAL, ERANGE
-from .engine import JmidEngine, JmidError
+from .engine import JmidEngine, JmidError, wall_segments
 from .kde import most_likely_samples
 from .weights import JMIDWeights, NetDims
 
@@ -88,6 +93,29 @@ DEFAULTS = {"device_id": 0, "precision": "f16mx", "rng_compat": "auto", "self_ch
 
 
 _PHILOX_STEP: Dict[Tuple[int, Tuple[int, ...]], int] = {}     # (device, shape) -> what one randn_like of that shape adds to the Philox offset
+
+
+def wall_arguments(static_obstacles, wall_radius, rounds: int) -> dict:
+    """The ``static_obstacles`` / ``wall_radius`` keywords of the forecaster, ``predict_batch`` and ``offline.sample`` as the keywords of
+    ``JmidEngine.denoise_reject``: {} without walls (the call, its route and its bits are then what they were), else
+    {"walls": [L, 4] float64, "wall_radius": float}.  Walls need collision-free sampling (``rounds`` > 0) and a radius - the sampler
+    knows no agent radius, so there is no default."""
+    if static_obstacles is None:
+        if wall_radius is not None:
+            raise ValueError("wall_radius is given without static_obstacles")
+        return {}
+    if rounds <= 0:
+        raise ValueError("static_obstacles needs collision-free sampling (collision_free_rounds > 0 / with_constraints=True)")
+    if wall_radius is None:
+        raise ValueError("static_obstacles needs wall_radius (the sampler knows no agent radius)")
+    walls, radius = wall_segments(static_obstacles), float(wall_radius)
+    if not np.isfinite(walls).all():
+        raise ValueError("static_obstacles holds a non-finite coordinate")
+    if walls.shape[0] > 64:
+        raise ValueError("static_obstacles holds more than 64 segments")
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("wall_radius must be finite and >= 0")
+    return {"walls": walls, "wall_radius": radius}
 
 
 def advance_cuda_generator(device_id: int, shape: Tuple[int, ...], n: int) -> None:
@@ -186,7 +214,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  self_check: Optional[bool] = None, self_check_tol: float = 5e-5, device_topk: Optional[bool] = None,
                  lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
                  seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False, coast_frames: int = 0,
-                 collision_free_rounds: int = 0, collision_threshold: float = 0.2):
+                 collision_free_rounds: int = 0, collision_threshold: float = 0.2, static_obstacles=None,
+                 wall_radius: Optional[float] = None):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -251,7 +280,10 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
             raise ValueError("collision_free_rounds needs rng_compat='device' (a redraw is a draw number of the library's counter generator)")
         if not (np.isfinite(self.collision_threshold) and self.collision_threshold >= 0.0):
             raise ValueError("collision_threshold must be finite and >= 0")
-        self.rejection: Optional[Tuple[int, int, int]] = None
+        # static_obstacles + wall_radius (opt-in, with collision_free_rounds > 0): the wall predicate joins the pedestrian one, and
+        # rejection holds five counts (the three, then the samples that fail the pedestrian predicate, the wall predicate)
+        self._walls = wall_arguments(static_obstacles, wall_radius, self.collision_free_rounds)
+        self.rejection: Optional[Tuple[int, ...]] = None
         self._init_MID(mid_config_file, weights, device_id, lib_path)
 
     def _init_MID(self, mid_config_file, weights, device_id, lib_path=None):
@@ -331,8 +363,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         def run(precision, pos_back):
             out, fell_back = repeat_in_fp32(lambda p: self.engine.denoise_reject(
                 ctx, p0, self.noise_seed, [self.episode_id], K, H, dt=self.time_step, precision=p, threshold=self.collision_threshold,
-                max_rounds=self.collision_free_rounds, draw0=self._draw0, want_vel=False, want_pos=pos_back), precision)
-            return out[1], out[3], fell_back
+                max_rounds=self.collision_free_rounds, draw0=self._draw0, want_vel=False, want_pos=pos_back, **self._walls), precision)
+            return out[1], out[3:], fell_back            # (out[3:]: episodes, and with walls the causes)
 
         pos, episodes, fell_back = run(self.precision, want_pos or check)
         if fell_back:
@@ -355,7 +387,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 self.precision, self.self_check = "f16x3", False
                 SELF_CHECK_DOWNGRADES += 1
                 pos, episodes = ref, ref_episodes
-        self.rejection = rejection_totals(episodes)
+        self.rejection = rejection_totals(*episodes)
         return pos if want_pos or check else None
 
     def get_most_likely_samples(self, forecasts):
@@ -668,7 +700,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   device_topk: bool = True, device_scene: bool = False,
                   device_frames: bool = False, noise: str = "torch", seed: int = 0,
                   padded=False, short_history: bool = False, first_frame=None, collision_free_rounds: int = 0,
-                  collision_threshold: float = 0.2, stats: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  collision_threshold: float = 0.2, stats: Optional[dict] = None, static_obstacles=None,
+                  wall_radius: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -714,12 +747,17 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     the same bits whichever batch it is part of.  ``stats`` (a dict) is filled with ``episodes`` [E, 3] int32 = (samples colliding at
     round 0, fixed, last round rerun) and ``slots`` [E, K, 3] int32, rows in input order (an episode with an empty cluster: zeros).
     Not with ``padded=``.
+    ``static_obstacles=`` [L, 2, 2] or [L, 4] with ``wall_radius=`` (opt-in, with ``collision_free_rounds`` > 0): a joint sample in which
+    a pedestrian's path, the step from his present position included, comes closer than ``wall_radius`` to a wall is redrawn too
+    (``jmid_denoise_reject_walls_seeded``); ``stats`` also gets ``cause`` [E, 2] int32 = (samples that fail the pedestrian predicate,
+    the wall predicate, at round 0).  ``wall_radius`` has no default: the sampler knows no agent radius.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
     if padded not in (False, True, "resident"):
         raise ValueError("padded must be False, True or 'resident'")
     R = int(collision_free_rounds)
+    walls = wall_arguments(static_obstacles, wall_radius, R)
     if R:
         if padded:
             raise ValueError("collision_free_rounds has no padded form (jmid_denoise_reject_seeded takes one agent count per call)")
@@ -791,6 +829,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     logw = np.empty((E, N, k), dtype=np.float64)
     if R and stats is not None:
         stats["episodes"], stats["slots"] = np.zeros((E, 3), dtype=np.int32), np.zeros((E, K, 3), dtype=np.int32)
+        if walls:
+            stats["cause"] = np.zeros((E, 2), dtype=np.int32)
     for A in np.unique(n_in):                   # episodes with the same count share their device calls
         eps = np.nonzero(n_in == A)[0]
         A = int(A)
@@ -817,11 +857,13 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                                 b["edge_mask"][ei, rows].reshape(n, 2),
                                 first_index=None if ff is None else b["first_index"][ei, rows].reshape(-1)).reshape(len(eps), A, -1)
             if R and A:
-                (_, pos, slots, episodes), _ = repeat_in_fp32(lambda p: engine.denoise_reject(
+                (_, pos, slots, episodes, *cause), _ = repeat_in_fp32(lambda p: engine.denoise_reject(
                     ctx, p0, dt=time_step, precision=p, threshold=collision_threshold, max_rounds=R, want_vel=False,
-                    want_pos=route.rank != "device_resident", **nz), precision)
+                    want_pos=route.rank != "device_resident", **walls, **nz), precision)
                 if stats is not None:
                     stats["episodes"][eps], stats["slots"][eps] = episodes, slots
+                    if cause:
+                        stats["cause"][eps] = cause[0]
             else:
                 pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
             sel, lw = rank_samples(engine, route.rank, pos, k, (len(eps), A, K, H))

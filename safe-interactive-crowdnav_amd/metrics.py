@@ -14,12 +14,16 @@ The collision statistics (``collision_statistics_host``, ``summarise_collisions`
 ``jmid_collision_statistics``) follow MID/models/collision_check_utils.py: ``calc_min_dists`` (:58-80) with ``lineseg_dist`` (:20-55)
 for the clearance of every agent pair of one joint sample, ``get_agents_in_collision`` (:83-97) for the agents that collide.
 
+The wall statistics (``wall_statistics_host``, ``summarise_walls``; ``csrc/wall_stats.hpp``, ``jmid_wall_statistics``) take the
+reference simulator's predicate: a step hits a wall when ``closest_distance_between_line_segments(wall, step) - radius < 0``
+(crowd_sim_plus/envs/crowd_sim_plus.py:885-893, crowd_sim_plus/envs/utils/utils_plus.py:205-338).
+
 The denoising loss (``loss_host``, ``loss_by_timestep``; ``csrc/loss.hpp``, ``jmid_loss``) is the reduction of ``DiffusionTraj.get_loss``
 (MID/models/diffusion.py:465-475): ``F.mse_loss(reduction="none")`` in fp32, the mean over the rows the loss mask keeps in fp64.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -32,6 +36,8 @@ LOG_PDF_LOWER_BOUND = -20.0      # evaluation.py:203, :271
 COLLISION_SAMPLE_COLUMNS = ("min_dist", "closest_pair", "n_pairs_colliding", "n_agents_colliding")
 COLLISION_SCENE_COLUMNS = ("collision_rate", "agent_collision_rate", "min_dist_min", "min_dist_mean", "min_dist_std")
 COLLISION_THRESHOLD = 0.2        # metres; collision_check_utils.py:88
+WALL_SAMPLE_COLUMNS = ("min_clear", "n_agents_hitting", "n_hits")
+WALL_SCENE_COLUMNS = ("wall_hit_rate", "agent_wall_hit_rate", "min_clear_min", "min_clear_mean", "min_clear_std")
 
 # the reference's summary keys (mid.py:965-1003) -> the column each one averages
 _SUMMARY_AGENT = {"ade": "ade_min", "fde": "fde_min", "kde": "kde_nll", "ade_most_likely": "ade_ml", "fde_most_likely": "fde_ml",
@@ -267,25 +273,36 @@ def summarise(agent: np.ndarray, scene: np.ndarray, rejection=None) -> Dict[str,
     out.update({k: float(np.mean(scene[:, STAT_SCENE_COLUMNS.index(c)])) for k, c in _SUMMARY_SCENE.items()})
     out["nan_rows"] = int(np.isnan(agent[:, STAT_AGENT_COLUMNS.index("kde_nll")]).sum())
     if rejection is not None:
-        num_iter, colliding, fixed = (int(v) for v in rejection)
-        print(rejection_sentence(colliding, fixed))
+        num_iter, colliding, fixed, *causes = (int(v) for v in rejection)
+        print(rejection_sentence(colliding, fixed, causes or None))
         out.update(rejection_num_iter=num_iter, rejection_colliding=colliding, rejection_fixed=fixed)
+        if causes:
+            out.update(rejection_pedestrian=causes[0], rejection_wall=causes[1])
     return out
 
 
-def rejection_totals(episodes) -> tuple:
+def rejection_totals(episodes, cause=None) -> tuple:
     """The three counts ``DiffusionTraj.sample`` returns behind its samples (MID/models/diffusion.py:606-613; placeholders there) from the
     ``episodes`` [..., 3] rows of ``JmidEngine.denoise_reject`` = (colliding at round 0, fixed, last round rerun):
-    -> (num_iter = the largest round over the batch, samples with collisions, samples fixed)."""
+    -> (num_iter = the largest round over the batch, samples with collisions, samples fixed).  With walls ("collisions" then counts a
+    sample that fails either predicate) ``cause`` [..., 2] = (fails the pedestrian predicate, fails the wall predicate) at round 0 adds
+    its two sums: five counts."""
     ep = np.asarray(episodes.detach().cpu() if hasattr(episodes, "detach") else episodes).reshape(-1, 3).astype(np.int64)
-    if ep.shape[0] == 0:
-        return 0, 0, 0
-    return int(ep[:, 2].max()), int(ep[:, 0].sum()), int(ep[:, 1].sum())
+    totals = (int(ep[:, 2].max()), int(ep[:, 0].sum()), int(ep[:, 1].sum())) if ep.shape[0] else (0, 0, 0)
+    if cause is None:
+        return totals
+    ca = np.asarray(cause.detach().cpu() if hasattr(cause, "detach") else cause).reshape(-1, 2).astype(np.int64)
+    return totals + (int(ca[:, 0].sum()), int(ca[:, 1].sum()))
 
 
-def rejection_sentence(colliding: int, fixed: int) -> str:
-    """The line the reference prints after an evaluation with constraints (MID/mid.py:1048)."""
-    return f"Rejection sampling fixed {int(fixed)} samples out of {int(colliding)} samples with collisions"
+def rejection_sentence(colliding: int, fixed: int, causes=None) -> str:
+    """The line the reference prints after an evaluation with constraints (MID/mid.py:1048).  ``causes`` = (samples that fail the
+    pedestrian predicate, samples that fail the wall predicate), when walls were asked for: both are named (a sample may count in
+    both)."""
+    line = f"Rejection sampling fixed {int(fixed)} samples out of {int(colliding)} samples with collisions"
+    if causes is None:
+        return line
+    return line + f" ({int(causes[0])} between pedestrians, {int(causes[1])} with walls)"
 
 
 def fill_slots(acceptable_by_round):
@@ -374,6 +391,100 @@ def summarise_collisions(scene: np.ndarray) -> Dict[str, float]:
     scene = np.asarray(scene, dtype=np.float64).reshape(-1, len(COLLISION_SCENE_COLUMNS))
     with np.errstate(invalid="ignore"):
         return {c: float(np.mean(scene[:, k])) for k, c in enumerate(COLLISION_SCENE_COLUMNS)}
+
+
+def _wall_step_distance(a0, a1, b0, b1):
+    """``closest_distance_between_line_segments`` (crowd_sim_plus/envs/utils/utils_plus.py:205-338) on arrays: walls a0 -> a1 and steps
+    b0 -> b1, [..., 2] each and broadcast against each other -> the distance [...].  Every branch of the scalar
+    ``crowd_env._closest_between_segments`` (the yardstick this is pinned to) is evaluated and chosen with ``np.where``, in its
+    arithmetic and its order of operations; only the distance is kept.  Finite inputs."""
+    dot = lambda u, v: u[..., 0] * v[..., 0] + u[..., 1] * v[..., 1]
+    dist = lambda p, q: np.sqrt(dot(p - q, p - q))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        a0, a1, b0, b1 = np.broadcast_arrays(a0, a1, b0, b1)
+        A, B = a1 - a0, b1 - b0
+        magA, magB = np.sqrt(dot(A, A)), np.sqrt(dot(B, B))
+        degA, degB = magA < 1e-8, magB < 1e-8
+        a1, b1 = np.where(degA[..., None], a0, a1), np.where(degB[..., None], b0, b1)
+        uA, uB = np.where(degA[..., None], 0.0, A / magA[..., None]), np.where(degB[..., None], 0.0, B / magB[..., None])
+        cross = uA[..., 0] * uB[..., 1] - uA[..., 1] * uB[..., 0]
+        denom = cross * cross
+        # exactly parallel (or a degenerate segment): before the wall, behind it, or an overlap
+        d0, d1 = dot(uA, b0 - a0), dot(uA, b1 - a0)
+        first = np.abs(d0) < np.abs(d1)
+        before, behind = (d0 <= 0) & (0 >= d1), (d0 >= magA) & (magA <= d1)
+        same = (dist(uA, uB) < 1e-8) | degB
+        a0f, uAf = np.where(same[..., None], a0, a1), np.where(same[..., None], uA, -uA)
+        d0f = dot(uAf, b0 - a0f)
+        onto_wall = dist(a0f + uAf * d0f[..., None], b0)
+        onto_step = dist(a0f, b0 + uB * dot(uB, a0f - b0)[..., None])
+        parallel = np.where(before, np.where(first, dist(a0, b0), dist(a0, b1)),
+                            np.where(behind, np.where(first, dist(a1, b0), dist(a1, b1)), np.where(d0f >= 0, onto_wall, onto_step)))
+        # crossing lines: the two projections, each clamped, each clamp re-projecting the other point
+        t = b0 - a0
+        t0 = cross * (t[..., 0] * uB[..., 1] - t[..., 1] * uB[..., 0]) / denom
+        t1 = cross * (t[..., 0] * uA[..., 1] - t[..., 1] * uA[..., 0]) / denom
+        lowA, highA, lowB, highB = t0 < 0, t0 > magA, t1 < 0, t1 > magB
+        pA = np.where(lowA[..., None], a0, np.where(highA[..., None], a1, a0 + uA * t0[..., None]))
+        pB = np.where(lowB[..., None], b0, np.where(highB[..., None], b1, b0 + uB * t1[..., None]))
+        pB = np.where((lowA | highA)[..., None], b0 + uB * np.minimum(np.maximum(dot(uB, pA - b0), 0.0), magB)[..., None], pB)
+        pA = np.where((lowB | highB)[..., None], a0 + uA * np.minimum(np.maximum(dot(uA, pB - a0), 0.0), magA)[..., None], pA)
+        return np.where(denom == 0, parallel, dist(pA, pB))
+
+
+def wall_statistics_host(pos: np.ndarray, walls: np.ndarray, radius: float, p0: Optional[np.ndarray] = None):
+    """pos [E, K, A, T, 2], walls [L, 4] or [L, 2, 2], p0 [E, A, 2] or None -> (dist [E, K, A, L] float64, agent [E, K, A] uint8,
+    sample [E, K, 3] float64, scene [E, 5] float64), the columns ``WALL_SAMPLE_COLUMNS`` / ``WALL_SCENE_COLUMNS``: what
+    ``JmidEngine.wall_statistics`` computes on the device (include/jmid_hip.h, ``jmid_wall_statistics``), without its size limits.
+    Agent a walks pos[t-1] -> pos[t] (and p0 -> pos[0] first when ``p0`` is given); dist[a, l] is the minimum over its segments of the
+    reference's closest distance between wall l and the segment, the agent hits wall l iff dist - radius < 0.  A segment with a
+    non-finite end makes the agent's row NaN (NaN never hits, and decides ``min_clear``).  L = 0: ``min_clear`` +inf, counts and rates
+    0, ``min_clear_std`` NaN.  fp64 on the fp32 positions; vectorised over everything (the samples in blocks, for the memory)."""
+    pos = np.asarray(np.asarray(pos, dtype=np.float32), dtype=np.float64)
+    E, K, A, T, _ = pos.shape
+    if T < 2:
+        raise ValueError("the wall statistics need at least two horizon steps")
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("the radius must be finite and >= 0")
+    walls = np.asarray(walls, dtype=np.float64).reshape(-1, 4)
+    if not np.isfinite(walls).all():
+        raise ValueError("a wall has a non-finite coordinate")
+    L = walls.shape[0]
+    if p0 is not None:
+        p0 = np.asarray(np.asarray(p0, dtype=np.float32), dtype=np.float64)
+        if p0.shape != (E, A, 2):
+            raise ValueError("p0 must be [E, A, 2]")
+        pos = np.concatenate([np.broadcast_to(p0[:, None, :, None, :], (E, K, A, 1, 2)), pos], axis=3)
+    S = pos.shape[3] - 1
+    d = np.empty((E, K, A, L))
+    a0, a1 = walls[:, None, :2], walls[:, None, 2:]                    # [L, 1, 2] against the steps [..., 1, S, 2]
+    block = max(1, (1 << 21) // max(1, E * A * S * L))
+    for k0 in range(0, K, block):
+        b0, b1 = pos[:, k0:k0 + block, :, None, :-1, :], pos[:, k0:k0 + block, :, None, 1:, :]
+        ok = np.isfinite(b0).all(axis=-1) & np.isfinite(b1).all(axis=-1)
+        seg = np.where(ok, _wall_step_distance(a0, a1, np.where(ok[..., None], b0, 0.0), np.where(ok[..., None], b1, 0.0)), np.nan)
+        d[:, k0:k0 + block] = seg.min(axis=-1)                         # [E, block, A, L]; np.min keeps a NaN
+    with np.errstate(invalid="ignore"):
+        hit = d - float(radius) < 0
+    agent = hit.any(axis=-1).astype(np.uint8)
+    sample = np.empty((E, K, len(WALL_SAMPLE_COLUMNS)))
+    sample[..., 0] = d.reshape(E, K, -1).min(axis=-1) if L else np.inf
+    sample[..., 1] = agent.sum(axis=-1)
+    sample[..., 2] = hit.reshape(E, K, -1).sum(axis=-1)
+    mc = sample[..., 0]
+    with np.errstate(invalid="ignore"):
+        scene = np.stack([(sample[..., 1] > 0).mean(axis=1), agent.reshape(E, -1).mean(axis=1), mc.min(axis=1), mc.mean(axis=1),
+                          mc.std(axis=1)], axis=-1)
+    return d, agent, sample, scene
+
+
+def summarise_walls(scene: np.ndarray) -> Dict[str, float]:
+    """The means of the wall scene columns over all episodes: scene [..., 5] -> {column name: mean}.  Plain ``np.mean``, as
+    ``summarise_collisions``: an episode with a NaN column (a non-finite position, or ``min_clear_std`` without walls) makes that key
+    NaN."""
+    scene = np.asarray(scene, dtype=np.float64).reshape(-1, len(WALL_SCENE_COLUMNS))
+    with np.errstate(invalid="ignore"):
+        return {c: float(np.mean(scene[:, k])) for k, c in enumerate(WALL_SCENE_COLUMNS)}
 
 
 def _real_rows(E: int, A: int, n_agents) -> np.ndarray:

@@ -30,7 +30,8 @@ from .engine import JmidEngine
 def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bool, point_dim: int = 2,
            flexibility: float = 0.0, ret_traj: bool = False, sampling: str = "ddpm", step: int = 100,
            precision: str = "f32", _integrate=None, seed: Optional[int] = None, with_constraints: bool = False,
-           collision_threshold: float = 0.2, max_rounds: int = 3) -> Tuple[np.ndarray, int, int, int, int]:
+           collision_threshold: float = 0.2, max_rounds: int = 3, static_obstacles=None,
+           wall_radius: Optional[float] = None) -> Tuple[np.ndarray, int, int, int, int]:
     """-> (vel [sample, B, num_points, 2] float32, number_of_steps, 0, 0, 0)   (diffusion.py:603-613).
     ``_integrate`` = (p0 [B, 2], dt): used by ``generate`` - the same call also integrates on the device (integrate_kernel) and
     the first element of the result is the positions instead.
@@ -38,7 +39,12 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     ``JmidEngine.denoise_reject`` - a sample in which two agents come closer than ``collision_threshold`` is redrawn up to
     ``max_rounds`` times (sample i is episode i with K = 1, so a redraw is exactly the reference's per-sample loop), and the last three
     values are the real (num_iter, samples with collisions, samples fixed) of ``metrics.rejection_totals``.  Needs ``seed=``,
-    ``bestof=True``, ``sampling="ddim"`` and positions (``_integrate``: ``generate`` passes it); ``ValueError`` otherwise."""
+    ``bestof=True``, ``sampling="ddim"`` and positions (``_integrate``: ``generate`` passes it); ``ValueError`` otherwise.
+    ``static_obstacles=`` [L, 2, 2] or [L, 4] with ``wall_radius=`` (with ``with_constraints=True`` only; no default radius): a sample in
+    which an agent's path, the step from p0 included, comes closer than ``wall_radius`` to a wall is redrawn too; the five returned
+    values keep their meaning ("with collisions": not acceptable for either cause)."""
+    from .forecaster import wall_arguments
+    walls = wall_arguments(static_obstacles, wall_radius, 1 if with_constraints else 0)
     if with_constraints:
         missing = [w for w, ok in (("seed=", seed is not None), ("bestof=True", bool(bestof)), ('sampling="ddim"', sampling == "ddim"),
                                    ("positions (generate, or _integrate)", _integrate is not None)) if not ok]
@@ -64,8 +70,9 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
             p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(_integrate[0], dtype=np.float32)[None], (sample, B, 2)))
             if with_constraints:
                 from .metrics import rejection_totals
-                _, pos, _, episodes = engine.denoise_reject(ctx_e, p0, dt=float(_integrate[1]), precision=precision, threshold=collision_threshold,
-                                                            max_rounds=max_rounds, want_vel=False, **nz)
+                _, pos, _, episodes, *_ = engine.denoise_reject(ctx_e, p0, dt=float(_integrate[1]), precision=precision,
+                                                                threshold=collision_threshold, max_rounds=max_rounds, want_vel=False,
+                                                                **walls, **nz)
                 return (pos.reshape(sample, B, num_points, 2), number_of_steps, *rejection_totals(episodes))
             _, pos = engine.denoise(None, ctx_e, p0, dt=float(_integrate[1]), precision=precision, want_vel=False, **nz)
             return pos.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
@@ -93,14 +100,17 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
 
 def generate(engine: JmidEngine, context, p0, dt: float, num_points: int, sample_n: int, bestof: bool,
              flexibility: float = 0.0, sampling: str = "ddpm", step: int = 100, precision: str = "f32", seed: Optional[int] = None,
-             with_constraints: bool = False, collision_threshold: float = 0.2, max_rounds: int = 3):
+             with_constraints: bool = False, collision_threshold: float = 0.2, max_rounds: int = 3, static_obstacles=None,
+             wall_radius: Optional[float] = None):
     """Tail of ``AutoEncoder.generate``: ``sample`` + ``SingleIntegrator.integrate_samples``
     (``single_integrator.py:290-321``): pos = cumsum(vel, T) * dt + p0[b].  ``context`` [B, ctx] is the encoder
     output (``JmidEngine.encode``), ``p0`` [B, 2] the current positions.  -> (pos [sample, B, T, 2], steps, 0, 0, 0); with
-    ``with_constraints=True`` (see ``sample``) the zeros are (num_iter, samples with collisions, samples fixed)."""
+    ``with_constraints=True`` (see ``sample``) the zeros are (num_iter, samples with collisions, samples fixed); ``static_obstacles`` /
+    ``wall_radius`` as there."""
     pos, nsteps, a, b, c = sample(engine, num_points, context, sample_n, bestof, flexibility=flexibility,
                                   sampling=sampling, step=step, precision=precision, _integrate=(p0, dt), seed=seed,
-                                  with_constraints=with_constraints, collision_threshold=collision_threshold, max_rounds=max_rounds)
+                                  with_constraints=with_constraints, collision_threshold=collision_threshold, max_rounds=max_rounds,
+                                  static_obstacles=static_obstacles, wall_radius=wall_radius)
     return np.asarray(pos, dtype=np.float32), nsteps, a, b, c
 
 

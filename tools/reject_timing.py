@@ -44,14 +44,84 @@ class Staged(HumanTrajectoryForecasterSim):
             FC.plan_route = keep
 
 
+def walls_main(args, weights):
+    """--rule: what the wall predicate costs per ``engine.denoise_reject`` call (docs/NOTEBOOK.md section 33), one scene per call at the
+    two points, the pedestrians standing inside the rule's walls.  Four variants in ONE process, interleaved call by call on the same
+    inputs and draw numbers:
+      (a) jmid_denoise_reject_seeded at threshold 0.2                      (b) jmid_denoise_reject_walls_seeded with L = 0
+      (c) ... with the rule's walls moved 1 km away: nothing hits          (d) ... with the rule's walls in place
+    (b) must lie inside the spread of the repeated (a) calls (``b_inside_a_spread``): anything else means L = 0 is not the old path."""
+    import torch
+
+    from safe_interactive_crowdnav_amd import crowd_env
+    from safe_interactive_crowdnav_amd.engine import JmidEngine
+    walls = crowd_env.static_obstacles(args.rule)[0].reshape(-1, 4)
+    if not len(walls):
+        raise SystemExit(f"rule {args.rule!r} has no walls")
+    away = walls + np.array([1000.0, 0.0, 1000.0, 0.0])
+    geo, R = crowd_env.Geometry(), 3
+    half_x = 0.5 * geo.rect_width - args.radius - 0.05
+    out = {"rule": args.rule, "radius": args.radius, "walls": int(len(walls))}
+    for point, (N, K, k, H, step) in POINTS.items():
+        eng = JmidEngine(weights, joint=True, hist_len=6, step=step)
+        eng.set_step(step, "ddim")
+        g = torch.Generator().manual_seed(11)
+        ctx = torch.randn([1, N, 256], generator=g).numpy()
+        # the pedestrians stand in the room below the door band (y in -1.6 .. -1.0), clear of every wall of the straight-walled rules:
+        # what hits is the forecast, not the present position
+        p0 = ((torch.rand([1, N, 2], generator=g) * 2.0 - 1.0) * torch.tensor([max(half_x, 0.05), 0.3]) - torch.tensor([0.0, 1.3])).numpy()
+        common = dict(seed=7, episode_ids=[0], K=K, T=H, dt=0.25, precision=args.precision, threshold=0.2, max_rounds=R)
+        variants = {"a_no_walls_entry": {}, "b_L0": dict(walls=np.zeros((0, 4)), wall_radius=args.radius),
+                    "c_walls_away": dict(walls=away, wall_radius=args.radius), "d_walls": dict(walls=walls, wall_radius=args.radius)}
+        ms = {name: [] for name in variants}
+        hit, reruns = [], []
+        for i in range(args.warmup + args.calls):
+            order = list(variants.items())
+            order = order[i % 4:] + order[:i % 4]                           # alternate who goes first
+            for name, kw in order:
+                t0 = time.perf_counter()
+                res = eng.denoise_reject(ctx, p0, draw0=i * (R + 1), **common, **kw)
+                dt = 1e3 * (time.perf_counter() - t0)
+                if i >= args.warmup:
+                    ms[name].append(dt)
+                    if name == "d_walls":
+                        hit.append(int(res[4][0, 1]))
+                        reruns.append(int(res[3][0, 2]))
+        res = {name: {"median_ms": round(float(np.median(v)), 3), "p10_ms": round(float(np.percentile(v, 10)), 3),
+                      "p90_ms": round(float(np.percentile(v, 90)), 3)} for name, v in ms.items()}
+        a = res["a_no_walls_entry"]
+        res["calls"] = len(ms["a_no_walls_entry"])
+        res["b_minus_a_ms"] = round(res["b_L0"]["median_ms"] - a["median_ms"], 3)
+        res["b_inside_a_spread"] = bool(a["p10_ms"] <= res["b_L0"]["median_ms"] <= a["p90_ms"])
+        res["c_minus_a_ms"] = round(res["c_walls_away"]["median_ms"] - a["median_ms"], 3)
+        res["d"] = {"minus_a_ms": round(res["d_walls"]["median_ms"] - a["median_ms"], 3),
+                    "share_of_samples_hitting": round(float(np.sum(hit)) / (len(hit) * K), 5), "reruns_mean": round(float(np.mean(reruns)), 3)}
+        res["workload"] = f"N={N}, K={K}, H={H}, {step} steps, {args.precision}, {args.rule}, one scene per call"
+        out[point] = res
+        print(point, json.dumps(res), flush=True)
+        eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16mx")
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--episodes", type=int, default=4)
+    ap.add_argument("--rule", default=None, help="a hallway rule of crowd_env (hallway_static, rectangle, ...): measure the wall predicate instead")
+    ap.add_argument("--radius", type=float, default=0.3, help="with --rule: the wall radius in metres")
     args = ap.parse_args()
     weights = JMIDWeights.from_seed(NetDims(ctx_dim=256), 5)
+    if args.rule:
+        out = walls_main(args, weights)
+        try:
+            import bench
+            out["sustained_mfma"] = bench.sustained_mfma_tflops()
+        except Exception:
+            out["sustained_mfma"] = None
+        print(json.dumps(out))
+        return
     out = {}
     for point, (N, K, k, H, step) in POINTS.items():
         sim = EP.simulate_circle_crossing(args.episodes, N, 6 + args.warmup + args.calls, seed=11)
