@@ -370,6 +370,32 @@ int jmid_predict_padded(jmid_handle_t h, int E, int A, int K, int T, int k, cons
                         const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, float* sel,
                         float* logw, float* pos_out);
 
+/* Collision and wall statistics of a padded batch: jmid_collision_statistics / jmid_wall_statistics that know which agents are real.
+ * (The plain entries have no such notion: fed a padded call's positions, the NaN rows make every sample's min_dist / min_clear NaN.)
+ * n_agents as above; every output keeps the plain entry's shape at A.
+ *   pair_out    [E, K, P_A] in pdist order at A.  A pair with a padded agent is quiet NaN and takes part in NOTHING - not in min_dist,
+ *               closest_pair or the counts (in the plain entry a NaN pair decides the minimum).  A non-finite position of a REAL agent
+ *               propagates exactly as in the plain entry
+ *   dist_out    [E, K, A, L]: quiet NaN in a padded agent's row; that agent is left out of min_clear, n_agents_hitting and n_hits
+ *   agent_out   a padded agent's byte is 0 (a byte has no NaN: read it with n_agents at hand)
+ *   sample_out  closest_pair is the pair's index at A.  n_agents[e] = 1 behaves as A = 1 does in the plain entry: min_dist +inf,
+ *               closest_pair -1, counts 0
+ *   scene_out   agent_collision_rate / agent_wall_hit_rate divide by K * n_agents[e]; everything else as the plain row
+ *   pos, p0     padded rows are never read (NaN, 1e30, anything).  pos = NULL: the resident positions after a padded denoise call of
+ *               the same shape (jmid_denoise_padded, jmid_denoise_padded_seeded, jmid_denoise_reject_padded_seeded), under the rule of
+ *               jmid_topk_padded
+ * THE EQUALITY that defines them: every value of episode e is bit for bit what the plain entry gives for that episode's compacted
+ * [1, K, n_e, T, 2] block (and [1, n_e, 2] p0), with pair (i, j) at p_A(i, j) instead of p_{n_e}(i, j).  The index map is monotone, so
+ * "the lowest index on an exact tie" carries over.  It holds by construction, not by measurement: a workgroup is one (episode, sample)
+ * and walks the real pairs / (agent, wall) couples of the compacted episode in the plain kernel's order; the minimum is a total order;
+ * the counts are exact integer sums in fp64; the sums over the K samples keep their order.
+ * JMID_EINVAL: NULL n_agents, a count outside 1..A, and the plain entry's refusals. */
+int jmid_collision_statistics_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, double threshold,
+                                     float* pair_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem);
+int jmid_wall_statistics_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, int L,
+                                const double* walls, double radius, float* dist_out, uint8_t* agent_out, float* sample_out, float* scene_out,
+                                int mem);
+
 /* The scene batch on the device: track positions on the time_step grid in, the encoder's inputs left resident on the handle - what the
  * reference does between update_state_hists and Trajectron.get_latent (mid_sim_wrapper.py:313-437, MID/dataset/preprocessing.py:428-620,
  * MID/environment/scene_graph.py:111-250, the neighbour reductions of MID/models/encoders/mgcvae.py:726-768) for E independent episodes.
@@ -629,7 +655,8 @@ int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t se
  * gives the same bits on and off.
  * After the call the ACCEPTED set is what pos = NULL means for jmid_topk, jmid_eval_statistics, jmid_eval_statistics_masked and
  * jmid_collision_statistics, at (E, A, K, T), forgotten exactly as after jmid_denoise.
- * DDIM only (JMID_EINVAL under a DDPM table: its draws 1.. are the steps' z); uniform agent count only (no padded form).  JMID_EINVAL:
+ * DDIM only (JMID_EINVAL under a DDPM table: its draws 1.. are the steps' z); uniform agent count only (mixed counts:
+ * jmid_denoise_reject_padded_seeded below).  JMID_EINVAL:
  * E < 1, K outside 1..1024, T outside 2..24, A outside 1..64, threshold not finite or < 0, max_rounds outside 0..64, draw0 < 0, NULL
  * episode_ids / ctx / p0.  JMID_ERANGE or JMID_ETIMEOUT of any round is the status of the whole call and the outputs are then undefined. */
 int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0,
@@ -676,6 +703,34 @@ int jmid_noise_fill_padded(jmid_handle_t h, uint64_t seed, int E, int A, int K, 
                            int draw, float* out, int mem);
 int jmid_denoise_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,
                                const float* ctx, const float* p0, float dt, int precision, float* vel_out, float* pos_out, int mem);
+
+/* Collision-free sampling of a padded batch: ONE rejection loop for episodes of different agent counts, in the layout of "Padded scene
+ * batches".  The rule is jmid_denoise_reject_walls_seeded's, word for word (L = 0: no walls, as jmid_denoise_reject_seeded is that entry at
+ * L = 0), and three things change:
+ *   Predicate  a candidate is ACCEPTABLE iff jmid_collision_statistics_padded (and, with walls, jmid_wall_statistics_padded at the call's
+ *              p0) gives it no colliding / hitting agent and a clearance that is not NaN - those entries' own kernels on the round's
+ *              counts.  An episode with n_agents[e] = 1 can only fail on walls
+ *   Noise      round j draws by the padded rule above at draw number draw0 + j: episode e draws what it draws alone at its own count
+ *   Reruns     a rerun is ONE padded seeded denoise call with the listed episodes' rows and THEIR counts, gathered in ascending order, at
+ *              the CALL's A: the row stride does not shrink when the episodes left over are all smaller.  The padded share of the rows is
+ *              computed and thrown away, as in every padded call
+ * The candidates' padded rows are quiet NaN and are copied as they are: the accepted block is NaN in its padded rows in every round.
+ * Equalities:
+ *   - every count equal to A: bit-identical to jmid_denoise_reject_walls_seeded in all five outputs;
+ *   - max_rounds = 0, draw0 = 0: vel_out and pos_out are bit-identical to jmid_denoise_padded_seeded;
+ *   - round j's candidates are bit-identical to jmid_noise_fill_padded(draw = draw0 + j) + jmid_denoise_padded on the gathered rows and
+ *     counts of exactly the rerun episodes, ascending, as ONE call at the call's A;
+ *   - an episode's outputs are a function of (weights, its ctx, p0, n_agents[e], A, seed, id, draw0, threshold, walls, radius, max_rounds)
+ *     only, under the chunk rule of jmid_set_chunk_episodes - not of its batch mates.
+ * The host still reads ONE small download per round; the gathered counts of a rerun go up with the rerun's episode ids.
+ * Afterwards the accepted set is what pos = NULL means for jmid_topk_padded, jmid_collision_statistics_padded and
+ * jmid_wall_statistics_padded at (E, A, K, T), forgotten exactly as after jmid_denoise_padded.
+ * JMID_EINVAL: the refusals of jmid_denoise_reject_walls_seeded and of jmid_denoise_padded_seeded (NULL n_agents, a count outside 1..A, a
+ * DDPM table, the attention A/B knobs that have no masked kernel). */
+int jmid_denoise_reject_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed,
+                                      const uint32_t* episode_ids, int draw0, const float* ctx, const float* p0, float dt, int precision,
+                                      double threshold, int max_rounds, int L, const double* walls, double radius, float* vel_out,
+                                      float* pos_out, int32_t* slot_out, int32_t* episode_out, int32_t* cause_out, int mem);
 
 /* Padded chains on the resident scene: jmid_predict_scene / jmid_forecast_scene (and their seeded forms) for a scene whose episodes have
  * DIFFERENT in-cluster counts - what jmid_build_scene leaves whenever it chooses the clusters itself - in one call, in the layout and

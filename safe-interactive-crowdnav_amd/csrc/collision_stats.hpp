@@ -17,6 +17,13 @@
 // as a binary tree over the thread index; a second kernel, one workgroup per episode, reduces the K samples the same way.  No
 // atomics; agent flags are plain byte stores of 1 in LDS (every writer stores the same value).  A row depends on nothing but its own
 // sample (or episode).
+//
+// Padded batches (CollisionStatsArgs::n_agents, jmid_collision_statistics_padded): episode e has n_e <= A real agents, rows a < n_e of its
+// [A, T, 2] blocks.  A workgroup is one (episode, sample), so n_e is uniform over it: it loads the n_e real rows only, walks the
+// n_e (n_e - 1) / 2 real pairs in pdist order at n_e - the loop, the reductions and their order are those of the plain call on the
+// compacted episode - and writes pair (i, j) at its index at A, quiet NaN in the pairs of a padded agent, 0 in a padded agent's byte.
+// The map from the index at n_e to the index at A is monotone, so the closest pair's tie rule carries over.  n_agents null: the plain
+// call, bit for bit.
 #pragma once
 #include "common.hpp"
 #include "eval_stats.hpp"
@@ -38,7 +45,17 @@ struct CollisionStatsArgs {
     double* ws;                   // [E, K, 2]
     double threshold;
     int E, A, K, T;
+    const int* n_agents;          // [E] on the device: the real agents of a padded batch's episodes (1 <= n_e <= A), or null: A everywhere
 };
+
+// pdist order at n agents: p(i, j) = i n - i (i + 1) / 2 + (j - i - 1), i < j, and its inverse
+__device__ __forceinline__ int cls_pair_index(int i, int j, int n) { return i * n - i * (i + 1) / 2 + (j - i - 1); }
+__device__ __forceinline__ void cls_pair_agents(int pr, int n, int* i_out, int* j_out) {
+    int i = 0, rem = pr;
+    while (rem >= n - 1 - i) { rem -= n - 1 - i; ++i; }
+    *i_out = i;
+    *j_out = i + 1 + rem;
+}
 
 inline size_t collision_sample_lds(int A, int T) {
     const size_t P = (size_t)A * (A - 1) / 2;
@@ -74,17 +91,18 @@ static __global__ __launch_bounds__(CLS_THREADS) void collision_sample_kernel(Co
     extern __shared__ __attribute__((aligned(16))) unsigned char cls_lds_raw[];
     const int tid = threadIdx.x;
     const size_t blk = blockIdx.x;
-    const int A = g.A, T = g.T, G = T - 1;
-    const int P = A * (A - 1) / 2, n_in = A * T * 2;
-    double* p = reinterpret_cast<double*>(cls_lds_raw);       // [A, T, 2] the sample
-    double* pmin = p + n_in;                                  // [P] the pair minima
+    const int AA = g.A, T = g.T, G = T - 1;                   // AA: the row stride; A: the real agents of this episode (uniform over the workgroup)
+    const int A = g.n_agents ? g.n_agents[blk / (size_t)g.K] : AA;
+    const int P = A * (A - 1) / 2, n_in = A * T * 2, PA = AA * (AA - 1) / 2;
+    double* p = reinterpret_cast<double*>(cls_lds_raw);       // [A, T, 2] the sample's real rows
+    double* pmin = p + n_in;                                  // [P] the pair minima, in pdist order at A
     double* seg = pmin + P;                                   // [CLS_THREADS] the segment distances of one pass
     double* red = seg + CLS_THREADS;                          // [CLS_THREADS]
     int* redi = reinterpret_cast<int*>(red + CLS_THREADS);    // [CLS_THREADS]
     unsigned char* flag = reinterpret_cast<unsigned char*>(redi + CLS_THREADS);       // [A]
-    const float* src = g.pos + blk * n_in;
+    const float* src = g.pos + blk * ((size_t)AA * T * 2);    // (the real rows come first: padded rows are never read)
     for (int i = tid; i < n_in; i += CLS_THREADS) p[i] = (double)src[i];
-    for (int i = tid; i < A; i += CLS_THREADS) flag[i] = 0;
+    for (int i = tid; i < AA; i += CLS_THREADS) flag[i] = 0;
     __syncthreads();
     // G neighbouring threads per pair, per_pass pairs at a time
     const int per_pass = CLS_THREADS / G, lp = tid / G, s = tid - lp * G;
@@ -93,9 +111,7 @@ static __global__ __launch_bounds__(CLS_THREADS) void collision_sample_kernel(Co
         const bool on = lp < per_pass && pr < P;
         int i = 0, j = 0;
         if (on) {
-            int rem = pr;                                     // pdist order: p(i, j) = i A - i (i + 1) / 2 + (j - i - 1)
-            while (rem >= A - 1 - i) { rem -= A - 1 - i; ++i; }
-            j = i + 1 + rem;
+            cls_pair_agents(pr, A, &i, &j);
             const double* pi = p + ((size_t)i * T + s) * 2;
             const double* pj = p + ((size_t)j * T + s) * 2;
             seg[tid] = cls_segment_dist(pi[0] - pj[0], pi[1] - pj[1], pi[2] - pj[2], pi[3] - pj[3]);
@@ -109,13 +125,22 @@ static __global__ __launch_bounds__(CLS_THREADS) void collision_sample_kernel(Co
         }
         __syncthreads();
     }
-    if (g.pair_out) {
+    if (g.pair_out && A == AA) {
         float* o = g.pair_out + blk * P;
         for (int q = tid; q < P; q += CLS_THREADS) o[q] = (float)pmin[q];
+    } else if (g.pair_out) {      // a padded episode: NaN everywhere, then the real pairs at their index at AA (uniform branch)
+        float* o = g.pair_out + blk * PA;
+        for (int q = tid; q < PA; q += CLS_THREADS) o[q] = __builtin_nanf("");
+        __syncthreads();
+        for (int q = tid; q < P; q += CLS_THREADS) {
+            int i, j;
+            cls_pair_agents(q, A, &i, &j);
+            o[cls_pair_index(i, j, AA)] = (float)pmin[q];
+        }
     }
     if (g.agent_out) {
-        unsigned char* o = g.agent_out + blk * A;
-        for (int q = tid; q < A; q += CLS_THREADS) o[q] = flag[q];
+        unsigned char* o = g.agent_out + blk * AA;
+        for (int q = tid; q < AA; q += CLS_THREADS) o[q] = flag[q];      // (a padded agent's byte stays 0)
     }
     // the closest pair (the lowest index on an exact tie), the number of colliding pairs and of colliding agents
     double bv = INFINITY, n_pairs = 0.0, n_agents = 0.0;
@@ -134,7 +159,7 @@ static __global__ __launch_bounds__(CLS_THREADS) void collision_sample_kernel(Co
         __syncthreads();
     }
     const double min_dist = red[0];
-    const int closest = redi[0];
+    int closest = redi[0];
     n_pairs = evs_block_sum(n_pairs, red, tid);
     n_agents = evs_block_sum(n_agents, red, tid);
     if (tid == 0) {
@@ -142,8 +167,14 @@ static __global__ __launch_bounds__(CLS_THREADS) void collision_sample_kernel(Co
         g.ws[blk * CLS_WS_COLS + 1] = n_agents;
         if (g.sample_out) {
             float* o = g.sample_out + blk * CLS_SAMPLE_COLS;
+            const bool none = min_dist != min_dist || closest >= P;
+            if (!none && A != AA) {                           // the pair's index at the row stride
+                int i, j;
+                cls_pair_agents(closest, A, &i, &j);
+                closest = cls_pair_index(i, j, AA);
+            }
             o[0] = (float)min_dist;
-            o[1] = (min_dist != min_dist || closest >= P) ? -1.0f : (float)closest;
+            o[1] = none ? -1.0f : (float)closest;
             o[2] = (float)n_pairs;
             o[3] = (float)n_agents;
         }
@@ -154,7 +185,7 @@ static __global__ __launch_bounds__(CLS_THREADS) void collision_sample_kernel(Co
 static __global__ __launch_bounds__(CLS_THREADS) void collision_scene_kernel(CollisionStatsArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char cls_lds_raw[];
     const int tid = threadIdx.x, e = blockIdx.x;
-    const int A = g.A, K = g.K;
+    const int A = g.n_agents ? g.n_agents[e] : g.A, K = g.K;  // the rate of the agent flags is over the episode's real agents
     double* v = reinterpret_cast<double*>(cls_lds_raw);       // [K] min_dist of the samples
     double* red = v + K;                                      // [CLS_THREADS]
     const double* w = g.ws + (size_t)e * K * CLS_WS_COLS;

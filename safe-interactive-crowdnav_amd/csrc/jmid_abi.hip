@@ -461,8 +461,8 @@ struct RejectWalls {
 // jmid_denoise_reject_seeded (no walls) and jmid_denoise_reject_walls_seeded after their argument checks.  Every round is one seeded
 // denoise call through run_network (a stage: no caller-stream ordering, the range flag comes with the round's one download), the flags of
 // its candidates - the collision kernel and, with walls, the wall kernel next to it -, the pairing, the compaction.
-int reject_loop(jmid_ctx* h, const char* who, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx,
-                const float* p0, float dt, int precision, double threshold, int max_rounds, const RejectWalls& walls, float* vel_out,
+int reject_loop(jmid_ctx* h, const char* who, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids, int draw0,
+                const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds, const RejectWalls& walls, float* vel_out,
                 float* pos_out, int32_t* slot_out, int32_t* episode_out, int32_t* cause_out, int mem) {
     const bool host = mem == JMID_MEM_HOST, vel = vel_out != nullptr, split = precision != JMID_PREC_F32, with_walls = walls.L > 0;
     h->last_pos = nullptr;
@@ -485,28 +485,35 @@ int reject_loop(jmid_ctx* h, const char* who, int E, int A, int K, int T, uint64
     g.ctx = ctx; g.p0 = p0; g.g_ctx = io.g_ctx; g.g_p0 = io.g_p0;
     g.E = E; g.K = K; g.n = A * T * 2; g.n_ctx = A * h->ctx_dim; g.n_p0 = A * 2;
     std::vector<uint32_t> ids(episode_ids, episode_ids + E);
+    // a padded batch: the counts of the round's episodes, a host array the round's denoise call checks and uploads (h->nag); the flag
+    // kernels behind it on the stream read that upload
+    std::vector<int32_t> nag;
+    if (n_agents) nag.assign(n_agents, n_agents + E);
     int n_run = E;
     for (int j = 0; j <= max_rounds && n_run > 0; ++j) {
-        if (j > 0) {      // the listed episodes, ascending: their ids, their rows
+        if (j > 0) {      // the listed episodes, ascending: their ids, their counts, their rows
             for (int b = 0; b < n_run; ++b) ids[b] = episode_ids[pin[1 + b]];
+            for (int b = 0; b < n_run && n_agents; ++b) nag[b] = n_agents[pin[1 + b]];
             HIPCHK(h, launch_reject_gather(g, n_run, h->stream));
         }
         const SeedArgs sa{seed, ids.data(), draw0 + j};
         DenoiseCall d{n_run, A, K, T, precision, JMID_MEM_DEVICE};
         d.ctx = j ? io.g_ctx.p : ctx; d.p0 = j ? io.g_p0.p : p0; d.dt = dt; d.seeded = &sa; d.chained = true; d.who = who;
         d.vel_out = j ? io.cand_vel : io.acc_vel; d.pos_out = j ? io.cand_pos.p : io.acc_pos.p;      // round 0 IS the accepted block
+        if (n_agents) d.n_agents = nag.data();       // (the row stride stays the call's A whatever counts are left)
         if (int rc = run_network(h, d)) return rc;
         h->last_pos = nullptr;       // (the arena's stage is not what pos = NULL means after this entry)
+        const int* nag_dev = n_agents ? h->nag.get<int>() : nullptr;
         {
             ProfScope ps(h, KC_EVAL_STATS, h->stream);
             CollisionStatsArgs cs{};
             cs.pos = d.pos_out; cs.ws = io.ws; cs.threshold = threshold;
-            cs.E = n_run; cs.A = A; cs.K = K; cs.T = T;
+            cs.E = n_run; cs.A = A; cs.K = K; cs.T = T; cs.n_agents = nag_dev;
             HIPCHK(h, launch_collision_stats(cs, h->stream));
             if (with_walls) {
                 WallStatsArgs ww{};
                 ww.pos = d.pos_out; ww.p0 = d.p0; ww.walls = walls.dev; ww.ws = io.ws_wall; ww.radius = walls.radius;
-                ww.E = n_run; ww.A = A; ww.K = K; ww.T = T; ww.L = walls.L;
+                ww.E = n_run; ww.A = A; ww.K = K; ww.T = T; ww.L = walls.L; ww.n_agents = nag_dev;
                 HIPCHK(h, launch_wall_stats(ww, h->stream));
             }
             g.round = j;
@@ -833,22 +840,23 @@ int jmid_eval_statistics_masked(jmid_handle_t h, int E, int A, int K, int T, con
     return st.end();
 }
 
-int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, double threshold, float* pair_out,
-                              uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
+// jmid_collision_statistics (n_agents null) and jmid_collision_statistics_padded (a HOST array, checked by the entry)
+static int collision_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, double threshold,
+                           float* pair_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
     if (!h || E <= 0) return fail(h, JMID_EINVAL, "bad argument");
+    const std::string w(who);
     if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
-        return fail(h, JMID_EINVAL, "jmid_collision_statistics supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
-    if (!(threshold >= 0.0) || !std::isfinite(threshold))
-        return fail(h, JMID_EINVAL, "jmid_collision_statistics: the threshold must be finite and >= 0");
-    if (!pair_out && !agent_out && !sample_out && !scene_out) return fail(h, JMID_EINVAL, "jmid_collision_statistics: every output is NULL");
-    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, "jmid_collision_statistics: E * K exceeds the launch grid");
+        return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(h, JMID_EINVAL, w + ": the threshold must be finite and >= 0");
+    if (!pair_out && !agent_out && !sample_out && !scene_out) return fail(h, JMID_EINVAL, w + ": every output is NULL");
+    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
     HIPCHK(h, hipSetDevice(h->device));
     if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
     const size_t P = (size_t)A * (A - 1) / 2;
     CollisionStatsArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T;
     g.threshold = threshold;
-    Staging st(h, mem, h->kde_ws, "jmid_collision_statistics");
+    Staging st(h, mem, h->kde_ws, who);
     st.scratch(&g.ws, (size_t)E * K * CLS_WS_COLS * 8);      // the per-sample fp64 values the scene kernel reduces
     if (pos) st.in(&g.pos, pos, (size_t)E * K * A * T * 2);
     else g.pos = h->last_pos;
@@ -857,6 +865,10 @@ int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const
     if (sample_out) st.out(&g.sample_out, sample_out, (size_t)E * K * CLS_SAMPLE_COLS);
     if (scene_out) st.out(&g.scene_out, scene_out, (size_t)E * CLS_SCENE_COLS);
     if (int rc = st.begin()) return rc;
+    if (n_agents) {
+        if (int rc = h->nag.upload(h, n_agents, E, who)) return rc;
+        g.n_agents = h->nag.get<int>();
+    }
     {
         ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_collision_stats(g, h->stream));
@@ -864,10 +876,24 @@ int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const
     return st.end();
 }
 
-int jmid_wall_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* p0, int L, const double* walls,
-                         double radius, float* dist_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
+int jmid_collision_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, double threshold, float* pair_out,
+                              uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
+    return collision_entry(h, "jmid_collision_statistics", E, A, K, T, nullptr, pos, threshold, pair_out, agent_out, sample_out, scene_out, mem);
+}
+
+int jmid_collision_statistics_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, double threshold,
+                                     float* pair_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    if (E > 0 && A > 0)
+        if (int rc = check_n_agents(h, "jmid_collision_statistics_padded", n_agents, E, A)) return rc;
+    return collision_entry(h, "jmid_collision_statistics_padded", E, A, K, T, n_agents, pos, threshold, pair_out, agent_out, sample_out, scene_out, mem);
+}
+
+// jmid_wall_statistics (n_agents null) and jmid_wall_statistics_padded (a HOST array, checked by the entry)
+static int wall_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, int L,
+                      const double* walls, double radius, float* dist_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
     if (!h || E <= 0) return fail(h, JMID_EINVAL, "bad argument");
-    const std::string w("jmid_wall_statistics");
+    const std::string w(who);
     if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
         return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
     if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(h, JMID_EINVAL, w + ": the radius must be finite and >= 0");
@@ -879,7 +905,7 @@ int jmid_wall_statistics(jmid_handle_t h, int E, int A, int K, int T, const floa
     if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
     g.E = E; g.A = A; g.K = K; g.T = T; g.L = L;
     g.radius = radius;
-    Staging st(h, mem, h->kde_ws, "jmid_wall_statistics");
+    Staging st(h, mem, h->kde_ws, who);
     st.scratch(&g.ws, (size_t)E * K * WLS_WS_COLS * 8);      // the per-sample fp64 values the scene kernel reduces
     if (pos) st.in(&g.pos, pos, (size_t)E * K * A * T * 2);
     else g.pos = h->last_pos;
@@ -889,11 +915,29 @@ int jmid_wall_statistics(jmid_handle_t h, int E, int A, int K, int T, const floa
     if (sample_out) st.out(&g.sample_out, sample_out, (size_t)E * K * WLS_SAMPLE_COLS);
     if (scene_out) st.out(&g.scene_out, scene_out, (size_t)E * WLS_SCENE_COLS);
     if (int rc = st.begin()) return rc;
+    if (n_agents) {
+        if (int rc = h->nag.upload(h, n_agents, E, who)) return rc;
+        g.n_agents = h->nag.get<int>();
+    }
     {
         ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_wall_stats(g, h->stream));
     }
     return st.end();
+}
+
+int jmid_wall_statistics(jmid_handle_t h, int E, int A, int K, int T, const float* pos, const float* p0, int L, const double* walls,
+                         double radius, float* dist_out, uint8_t* agent_out, float* sample_out, float* scene_out, int mem) {
+    return wall_entry(h, "jmid_wall_statistics", E, A, K, T, nullptr, pos, p0, L, walls, radius, dist_out, agent_out, sample_out, scene_out, mem);
+}
+
+int jmid_wall_statistics_padded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, int L,
+                                const double* walls, double radius, float* dist_out, uint8_t* agent_out, float* sample_out, float* scene_out,
+                                int mem) {
+    if (!h) return JMID_EINVAL;
+    if (E > 0 && A > 0)
+        if (int rc = check_n_agents(h, "jmid_wall_statistics_padded", n_agents, E, A)) return rc;
+    return wall_entry(h, "jmid_wall_statistics_padded", E, A, K, T, n_agents, pos, p0, L, walls, radius, dist_out, agent_out, sample_out, scene_out, mem);
 }
 
 // jmid_topk (n_agents null) and jmid_topk_padded
@@ -1336,8 +1380,9 @@ int jmid_denoise_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t se
     return run_network(h, c);
 }
 
-// jmid_denoise_reject_seeded (L = 0, walls and cause_out null) and jmid_denoise_reject_walls_seeded: the argument checks, then the loop
-static int reject_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0,
+// jmid_denoise_reject_seeded (L = 0, walls and cause_out null), jmid_denoise_reject_walls_seeded and jmid_denoise_reject_padded_seeded
+// (padded: n_agents a HOST array [E]): the argument checks, then the loop
+static int reject_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, bool padded, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids, int draw0,
                         const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds, int L, const double* walls,
                         double radius, float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out, int32_t* cause_out, int mem) {
     if (!h) return JMID_EINVAL;
@@ -1356,18 +1401,23 @@ static int reject_entry(jmid_handle_t h, const char* who, int E, int A, int K, i
     if (!call_mode(precision, &mode)) return fail(h, JMID_EINVAL, w + ": precision must be JMID_PREC_F32, JMID_PREC_F16X3, JMID_PREC_F16X2 or JMID_PREC_F16MX");
     if (mem != JMID_MEM_HOST && mem != JMID_MEM_DEVICE) return fail(h, JMID_EINVAL, w + ": bad mem");
     if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(h, JMID_EINVAL, w + ": the radius must be finite and >= 0");
+    if (padded) {
+        if (int rc = check_n_agents(h, who, n_agents, E, A)) return rc;
+        if (h->net_kind == JMID_NET_JMID && mode.split && !attn_masked_built(plan_attn(h->d / h->nhead, h->tune), mode.x2 != 0))
+            return fail(h, JMID_EINVAL, w + ": a padded call needs the default attention kernel (the attention A/B knobs have no masked form)");
+    }
     HIPCHK(h, hipSetDevice(h->device));
     RejectWalls rw;
     rw.L = L; rw.radius = radius;
     if (int rc = upload_walls(h, L, walls, &rw.dev, w)) return rc;
-    return reject_loop(h, who, E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, rw, vel_out, pos_out, slot_out,
+    return reject_loop(h, who, E, A, K, T, n_agents, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, rw, vel_out, pos_out, slot_out,
                        episode_out, cause_out, mem);
 }
 
 int jmid_denoise_reject_seeded(jmid_handle_t h, int E, int A, int K, int T, uint64_t seed, const uint32_t* episode_ids, int draw0, const float* ctx,
                                const float* p0, float dt, int precision, double threshold, int max_rounds, float* vel_out, float* pos_out,
                                int32_t* slot_out, int32_t* episode_out, int mem) {
-    return reject_entry(h, "jmid_denoise_reject_seeded", E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, 0,
+    return reject_entry(h, "jmid_denoise_reject_seeded", E, A, K, T, false, nullptr, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds, 0,
                         nullptr, 0.0, vel_out, pos_out, slot_out, episode_out, nullptr, mem);
 }
 
@@ -1375,8 +1425,16 @@ int jmid_denoise_reject_walls_seeded(jmid_handle_t h, int E, int A, int K, int T
                                      const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds, int L,
                                      const double* walls, double radius, float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out,
                                      int32_t* cause_out, int mem) {
-    return reject_entry(h, "jmid_denoise_reject_walls_seeded", E, A, K, T, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold, max_rounds,
-                        L, walls, radius, vel_out, pos_out, slot_out, episode_out, cause_out, mem);
+    return reject_entry(h, "jmid_denoise_reject_walls_seeded", E, A, K, T, false, nullptr, seed, episode_ids, draw0, ctx, p0, dt, precision, threshold,
+                        max_rounds, L, walls, radius, vel_out, pos_out, slot_out, episode_out, cause_out, mem);
+}
+
+int jmid_denoise_reject_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,
+                                      int draw0, const float* ctx, const float* p0, float dt, int precision, double threshold, int max_rounds, int L,
+                                      const double* walls, double radius, float* vel_out, float* pos_out, int32_t* slot_out, int32_t* episode_out,
+                                      int32_t* cause_out, int mem) {
+    return reject_entry(h, "jmid_denoise_reject_padded_seeded", E, A, K, T, true, n_agents, seed, episode_ids, draw0, ctx, p0, dt, precision,
+                        threshold, max_rounds, L, walls, radius, vel_out, pos_out, slot_out, episode_out, cause_out, mem);
 }
 
 int jmid_noise_fill(jmid_handle_t h, uint64_t seed, int E, int rows, int T, const uint32_t* episode_ids, int draw, float* out, int mem) {

@@ -853,7 +853,7 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
     }
     if (a.seeded && cp.masked) {
         if (int rc = h->noise_ids.upload(h, a.seeded->ids, a.E, a.who)) return rc;
-        if (int rc = fill_noise_padded(h, a.seeded->seed, h->noise_ids.get<unsigned>(), io.nag, a.E, a.A, a.K, a.T, 0, io.x_cur, h->stream)) return rc;
+        if (int rc = fill_noise_padded(h, a.seeded->seed, h->noise_ids.get<unsigned>(), io.nag, a.E, a.A, a.K, a.T, a.seeded->draw, io.x_cur, h->stream)) return rc;
     } else if (a.seeded) {
         if (int rc = h->noise_ids.upload(h, a.seeded->ids, a.E, a.who)) return rc;
         if (int rc = fill_noise(h, a.seeded->seed, h->noise_ids.get<unsigned>(), a.E, (size_t)a.K * a.A * a.T * 2, a.seeded->draw, io.x_cur, nullptr, h->stream)) return rc;

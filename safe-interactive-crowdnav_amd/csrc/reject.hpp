@@ -15,6 +15,10 @@
 //   reject_gather_kernel   one workgroup per listed episode: its ctx [A, ctx_dim] and p0 [A, 2] rows into the rerun's input block
 // Ranks come from a block-wide exclusive scan over per-thread counts; a thread owns ceil(K / 256) CONSECUTIVE samples (episodes in the
 // compaction), so ranks ascend with the index.  Fixed order, no atomics: an episode's rows depend on nothing but the episode.
+//
+// A padded batch (jmid_denoise_reject_padded_seeded) needs no rule of its own here: the flags come from the same two kernels run with
+// the round's agent counts, the candidates' padded rows are quiet NaN and are copied as they are, and the gather moves whole [A, ...]
+// rows - the row stride is the call's A in every round.
 #pragma once
 #include "common.hpp"
 

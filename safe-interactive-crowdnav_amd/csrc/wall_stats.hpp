@@ -21,6 +21,11 @@
 // reductions run per thread in index order and then as a binary tree over the thread index.  The per-sample {min_clear,
 // n_agents_hitting} go to the fp64 workspace; the K samples of an episode are reduced by collision_scene_kernel, whose definitions the
 // scene row shares ("hits a wall" for "collides").  No atomics; agent flags are plain byte stores of 1 in LDS.
+//
+// Padded batches (WallStatsArgs::n_agents, jmid_wall_statistics_padded): the workgroup of (episode e, sample k) loads and walks the
+// n_e real agents only - the (agent, wall) order and the reductions are those of the plain call on the compacted episode -, writes quiet
+// NaN into the padded agents' rows of dist_out and leaves their bytes 0; padded rows of pos and p0 are never read.  n_agents null: the
+// plain call, bit for bit.
 #pragma once
 #include "collision_stats.hpp"
 
@@ -44,6 +49,7 @@ struct WallStatsArgs {
     double* ws;                   // [E, K, 2]
     double radius;
     int E, A, K, T, L;
+    const int* n_agents;          // [E] on the device: the real agents of a padded batch's episodes (1 <= n_e <= A), or null: A everywhere
 };
 
 // The [A, L] table of minima is NOT kept in LDS: every (agent, wall) value is consumed by the thread that computed it (its store, its
@@ -117,23 +123,24 @@ static __global__ __launch_bounds__(WLS_THREADS) void wall_sample_kernel(WallSta
     extern __shared__ __attribute__((aligned(16))) unsigned char wls_lds_raw[];
     const int tid = threadIdx.x;
     const size_t blk = blockIdx.x;
-    const int A = g.A, T = g.T, L = g.L;
+    const int AA = g.A, T = g.T, L = g.L;                     // AA: the row stride; A: the real agents of this episode (uniform over the workgroup)
+    const int A = g.n_agents ? g.n_agents[blk / (size_t)g.K] : AA;
     const int lead = g.p0 ? 1 : 0, NP = T + lead;             // points per agent; NP - 1 segments
     double* p = reinterpret_cast<double*>(wls_lds_raw);       // [A, NP, 2] the paths
     double* w = p + (size_t)A * NP * 2;                       // [L, 4] the walls
     double* red = w + (size_t)L * 4;                          // [WLS_THREADS]
     unsigned char* flag = reinterpret_cast<unsigned char*>(red + WLS_THREADS);        // [A]
-    const float* src = g.pos + blk * ((size_t)A * T * 2);
+    const float* src = g.pos + blk * ((size_t)AA * T * 2);    // (the real rows come first: padded rows are never read)
     for (int i = tid; i < A * T * 2; i += WLS_THREADS) {
         const int a = i / (T * 2), r = i - a * (T * 2);
         p[((size_t)a * NP + lead) * 2 + r] = (double)src[i];
     }
     if (lead) {
-        const float* s0 = g.p0 + (blk / (size_t)g.K) * ((size_t)A * 2);
+        const float* s0 = g.p0 + (blk / (size_t)g.K) * ((size_t)AA * 2);
         for (int i = tid; i < A * 2; i += WLS_THREADS) p[(size_t)(i >> 1) * NP * 2 + (i & 1)] = (double)s0[i];
     }
     for (int i = tid; i < L * 4; i += WLS_THREADS) w[i] = g.walls[i];
-    for (int i = tid; i < A; i += WLS_THREADS) flag[i] = 0;
+    for (int i = tid; i < AA; i += WLS_THREADS) flag[i] = 0;
     __syncthreads();
     double mn = INFINITY, n_hits = 0.0, n_agents = 0.0;
     for (int q = tid; q < A * L; q += WLS_THREADS) {
@@ -143,17 +150,19 @@ static __global__ __launch_bounds__(WLS_THREADS) void wall_sample_kernel(WallSta
         double m = wls_segment_dist(wl[0], wl[1], wl[2], wl[3], pa[0], pa[1], pa[2], pa[3]);
         for (int s = 1; s < NP - 1; ++s)                      // in step order
             m = cls_min(m, wls_segment_dist(wl[0], wl[1], wl[2], wl[3], pa[2 * s], pa[2 * s + 1], pa[2 * s + 2], pa[2 * s + 3]));
-        if (g.dist_out) g.dist_out[blk * ((size_t)A * L) + q] = (float)m;
+        if (g.dist_out) g.dist_out[blk * ((size_t)AA * L) + q] = (float)m;
         if (m - g.radius < 0.0) {
             flag[a] = 1;
             n_hits += 1.0;
         }
         mn = cls_min(m, mn);
     }
+    if (g.dist_out)      // the rows of the padded agents
+        for (int q = A * L + tid; q < AA * L; q += WLS_THREADS) g.dist_out[blk * ((size_t)AA * L) + q] = __builtin_nanf("");
     __syncthreads();
     if (g.agent_out) {
-        unsigned char* o = g.agent_out + blk * A;
-        for (int q = tid; q < A; q += WLS_THREADS) o[q] = flag[q];
+        unsigned char* o = g.agent_out + blk * AA;
+        for (int q = tid; q < AA; q += WLS_THREADS) o[q] = flag[q];      // (a padded agent's byte stays 0)
     }
     for (int q = tid; q < A; q += WLS_THREADS) n_agents += (double)flag[q];
     red[tid] = mn;
@@ -182,7 +191,7 @@ inline hipError_t launch_wall_stats(const WallStatsArgs& g, hipStream_t st) {
                        g);
     if (g.scene_out) {        // the scene row has collision_scene_kernel's definitions, on this entry's per-sample values
         CollisionStatsArgs c{};
-        c.ws = g.ws; c.scene_out = g.scene_out; c.E = g.E; c.A = g.A; c.K = g.K; c.T = g.T;
+        c.ws = g.ws; c.scene_out = g.scene_out; c.E = g.E; c.A = g.A; c.K = g.K; c.T = g.T; c.n_agents = g.n_agents;
         hipLaunchKernelGGL(collision_scene_kernel, dim3(g.E), dim3(CLS_THREADS), collision_scene_lds(g.K), st, c);
     }
     return hipGetLastError();

@@ -364,7 +364,7 @@ class JmidEngine:
 
     def denoise_reject(self, ctx: ArrayLike, p0: ArrayLike, seed: int, episode_ids, K: int, T: int, dt: float = 0.25, precision: str = "f32",
                        threshold: float = 0.2, max_rounds: int = 3, draw0: int = 0, want_vel: bool = True, want_pos: bool = True,
-                       walls=None, wall_radius: Optional[float] = None):
+                       walls=None, wall_radius: Optional[float] = None, n_agents=None):
         """Collision-free sampling (``jmid_denoise_reject_seeded``; the rule stands in include/jmid_hip.h, its host twin is
         ``metrics.fill_slots``): the seeded ``denoise`` of draw number ``draw0``, then up to ``max_rounds`` reruns of the episodes that
         still hold a joint sample in which two agents come closer than ``threshold`` (the predicate of ``collision_statistics``) - an
@@ -376,7 +376,11 @@ class JmidEngine:
         ``walls`` [L, 4] or [L, 2, 2] with ``wall_radius`` (``jmid_denoise_reject_walls_seeded``): a sample must also keep every agent's
         path, the step p0 -> pos[0] included, at least ``wall_radius`` away from every wall (the predicate of ``wall_statistics`` with
         this call's p0); a fifth value comes back, cause [E, 2] int32 = (slots whose round-0 sample fails the pedestrian predicate,
-        the wall predicate).  Without ``walls`` the call, its route and its four values are what they were."""
+        the wall predicate).  Without ``walls`` the call, its route and its four values are what they were.
+        ``n_agents`` [E] (``jmid_denoise_reject_padded_seeded``): ONE loop for a padded batch of mixed counts - episode e has n_agents[e] <= A
+        real agents, the predicate is that of ``collision_statistics(n_agents=)`` / ``wall_statistics(n_agents=)``, round j draws by the
+        padded rule at draw ``draw0 + j``, a rerun keeps the call's A as its row stride, and the padded rows of vel and pos are NaN.
+        Always five values (cause [:, 1] is 0 without walls).  Without ``n_agents`` nothing changes."""
         if ctx.ndim != 3 or int(ctx.shape[2]) != self.dims.ctx_dim:
             raise ValueError("expected ctx [E, A, ctx_dim]")
         if (walls is None) != (wall_radius is None):
@@ -395,6 +399,15 @@ class JmidEngine:
         vel = _out((E, K, A, T, 2), device=where) if want_vel else None
         pos = _out((E, K, A, T, 2), device=where) if want_pos else None
         slots, episodes = _out((E, K, 3), np.int32, where), _out((E, 3), np.int32, where)
+        if n_agents is not None:
+            na, cause = agent_counts(n_agents, E), _out((E, 2), np.int32, where)
+            w = wall_segments(walls) if walls is not None else None
+            L = int(w.shape[0]) if w is not None else 0
+            self._compute(self._lib.jmid_denoise_reject_padded_seeded, self._h, E, A, K, T, _ptr(na), seed, _ptr(ids), int(draw0), bc.ptr, bp.ptr,
+                          float(dt), _lib.PRECISIONS[precision], float(threshold), int(max_rounds), L, _ptr(w) if L else None,
+                          float(wall_radius) if wall_radius is not None else 0.0, _ptr(vel), _ptr(pos), _ptr(slots), _ptr(episodes), _ptr(cause),
+                          self._mem(dev))
+            return vel, pos, slots, episodes, cause
         if walls is not None:
             w, cause = wall_segments(walls), _out((E, 2), np.int32, where)
             L = int(w.shape[0])
@@ -841,14 +854,17 @@ class JmidEngine:
         return agent, cut, scene
 
     def collision_statistics(self, pos: Optional[ArrayLike], threshold: float = 0.2,
-                             dims: Optional[Tuple[int, int, int, int]] = None, pairs: bool = False, agents: bool = True):
+                             dims: Optional[Tuple[int, int, int, int]] = None, pairs: bool = False, agents: bool = True, n_agents=None):
         """Collision statistics of joint samples on the device (``jmid_collision_statistics``; calc_min_dists and
         get_agents_in_collision, MID/models/collision_check_utils.py:58-97).  pos [E, K, A, T, 2] -> (pair [E, K, P] or None,
         agent [E, K, A] uint8 or None, sample [E, K, 4], scene [E, 5]) with the columns ``metrics.COLLISION_SAMPLE_COLUMNS`` /
         ``metrics.COLLISION_SCENE_COLUMNS``; ``pairs`` / ``agents`` choose whether the first two are computed.  NumPy in -> NumPy out,
         CUDA tensors in -> CUDA tensors out.  ``pos=None`` with ``dims=(E, A, K, T)`` takes the positions of the preceding ``denoise``
         call, which are still in the engine's workspace (host arrays out).  Ground-truth futures: ``gt[:, None]`` (K = 1).
-        K <= 1024, 2 <= T <= 24, A <= 64: ``metrics.collision_statistics_host`` beyond."""
+        K <= 1024, 2 <= T <= 24, A <= 64: ``metrics.collision_statistics_host`` beyond.
+        ``n_agents`` [E] (``jmid_collision_statistics_padded``): episode e has n_agents[e] <= A real agents; every value of the episode is
+        what the plain call gives for its compacted block, a pair with a padded agent is NaN at its index at A and counts nowhere, a padded
+        agent's byte is 0, agent_collision_rate divides by K * n_agents[e].  Padded rows of pos are never read."""
         if pos is None:
             if dims is None:
                 raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
@@ -861,12 +877,17 @@ class JmidEngine:
         shapes = (((E, K, A * (A - 1) // 2), np.float32) if pairs else None, ((E, K, A), np.uint8) if agents else None,
                   ((E, K, 4), np.float32), ((E, 5), np.float32))
         outs = [_out(*s, pos.device if dev else None) if s else None for s in shapes]
+        if n_agents is not None:
+            na = agent_counts(n_agents, E)
+            self._check(self._lib.jmid_collision_statistics_padded(self._h, E, A, K, T, _ptr(na), bp.ptr if bp is not None else None,
+                                                                   float(threshold), *[_ptr(o) for o in outs], self._mem(dev)))
+            return tuple(outs)
         self._check(self._lib.jmid_collision_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, float(threshold),
                                                         *[_ptr(o) for o in outs], self._mem(dev)))
         return tuple(outs)
 
     def wall_statistics(self, pos: Optional[ArrayLike], walls, radius: float, p0: Optional[ArrayLike] = None,
-                        dims: Optional[Tuple[int, int, int, int]] = None):
+                        dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None):
         """Wall statistics of joint samples on the device (``jmid_wall_statistics``; the reference simulator's
         closest_distance_between_line_segments(wall, step) - radius < 0, include/jmid_hip.h states the definitions).  pos [E, K, A, T, 2],
         walls [L, 4] or [L, 2, 2] (a host array, ``crowd_env.static_obstacles(rule)[0]``), p0 [E, A, 2] or None (the step from the present
@@ -874,7 +895,9 @@ class JmidEngine:
         the columns ``metrics.WALL_SAMPLE_COLUMNS`` / ``metrics.WALL_SCENE_COLUMNS``.  NumPy in -> NumPy out, CUDA tensors in -> CUDA
         tensors out.  ``pos=None`` with ``dims=(E, A, K, T)`` takes the positions of the preceding ``denoise`` / ``denoise_reject`` call,
         which are still in the engine's workspace (``p0`` then decides where the outputs live; host arrays without it).
-        K <= 1024, 2 <= T <= 24, A <= 64, L <= 64: ``metrics.wall_statistics_host`` beyond."""
+        K <= 1024, 2 <= T <= 24, A <= 64, L <= 64: ``metrics.wall_statistics_host`` beyond.
+        ``n_agents`` [E] (``jmid_wall_statistics_padded``): the padded agents' rows of dist are NaN, their bytes 0, they count nowhere and
+        agent_wall_hit_rate divides by K * n_agents[e]; padded rows of pos and p0 are never read."""
         w = wall_segments(walls)
         L = int(w.shape[0])
         if pos is None:
@@ -892,6 +915,12 @@ class JmidEngine:
         where = (pos if pos is not None else p0).device if dev else None
         outs = [_out((E, K, A, L), np.float32, where), _out((E, K, A), np.uint8, where), _out((E, K, 3), np.float32, where),
                 _out((E, 5), np.float32, where)]
+        if n_agents is not None:
+            na = agent_counts(n_agents, E)
+            self._check(self._lib.jmid_wall_statistics_padded(self._h, E, A, K, T, _ptr(na), bp.ptr if bp is not None else None,
+                                                              b0.ptr if b0 is not None else None, L, _ptr(w) if L else None, float(radius),
+                                                              *[_ptr(o) for o in outs], self._mem(dev)))
+            return tuple(outs)
         self._check(self._lib.jmid_wall_statistics(self._h, E, A, K, T, bp.ptr if bp is not None else None, b0.ptr if b0 is not None else None,
                                                    L, _ptr(w) if L else None, float(radius), *[_ptr(o) for o in outs], self._mem(dev)))
         return tuple(outs)

@@ -701,7 +701,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   device_frames: bool = False, noise: str = "torch", seed: int = 0,
                   padded=False, short_history: bool = False, first_frame=None, collision_free_rounds: int = 0,
                   collision_threshold: float = 0.2, stats: Optional[dict] = None, static_obstacles=None,
-                  wall_radius: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  wall_radius: Optional[float] = None, collision_free_padded: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -751,6 +751,13 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     a pedestrian's path, the step from his present position included, comes closer than ``wall_radius`` to a wall is redrawn too
     (``jmid_denoise_reject_walls_seeded``); ``stats`` also gets ``cause`` [E, 2] int32 = (samples that fail the pedestrian predicate,
     the wall predicate, at round 0).  ``wall_radius`` has no default: the sampler knows no agent radius.
+    ``collision_free_padded=True`` (opt-in, with ``collision_free_rounds`` > 0 and ``noise="device"``; not with ``padded=``): ONE
+    rejection loop for the whole batch instead of one per count group (``jmid_denoise_reject_padded_seeded``) - the staged route on
+    padded inputs with A = the largest count: the scene as above, ONE ``engine.encode`` over E * A rows, ONE
+    ``engine.denoise_reject(n_agents=)`` from draw 0, the ranking by ``engine.topk(n_agents=)`` on the accepted set (the host twin beyond
+    its limits).  Episode e draws what it draws in its count group; its forecasts equal the grouped path's up to the rounding of a
+    padded call's attention (bit for bit when every count is the same).  ``stats`` gets ``episodes``, ``slots`` and ``cause`` in input
+    order.  A batch with an empty cluster takes the count groups.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
@@ -763,6 +770,11 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             raise ValueError("collision_free_rounds has no padded form (jmid_denoise_reject_seeded takes one agent count per call)")
         if noise != "device":
             raise ValueError("collision_free_rounds needs noise='device' (a redraw is a draw number of the library's counter generator)")
+    if collision_free_padded:
+        if padded:
+            raise ValueError("collision_free_padded is the padded form of collision_free_rounds: not with padded=")
+        if not R:
+            raise ValueError("collision_free_padded needs collision_free_rounds > 0")
     resident = isinstance(padded, str)
     if resident:
         padded, device_frames = False, True       # (what it falls back to: the grouped device path)
@@ -825,6 +837,37 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         with lock:
             (rows, lw), _ = repeat_in_fp32(lambda p: engine.predict_padded(*args, dt=time_step, precision=p), precision)
         return (*SC.assemble_forecasts(inc, rows, lw, b["cv"], pose_now, k, K, n_agents=n_in), inc)
+    if collision_free_padded and n_in.min() >= 1:
+        # the staged route on the whole batch: padded inputs, one encode, one rejection loop, one ranking of the accepted set
+        A = int(n_in.max())
+        route = plan(A)
+        if "p0" not in b:           # (device_frames built without reading the encoder inputs back)
+            with lock:
+                engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff, **ab)
+                b.update(engine.scene_arrays())
+        counts = n_in.astype(np.int32)
+        p0 = SC.pad_agents(b["p0"], inc, A)
+        with lock:
+            ctx = engine.encode(SC.pad_agents(b["x_st"], inc, A).reshape(E * A, F, 6), SC.pad_agents(b["nbr_sum"], inc, A).reshape(E * A, 2, F, 6),
+                                SC.pad_agents(b["edge_mask"], inc, A).reshape(E * A, 2),
+                                first_index=None if ff is None else SC.pad_agents(b["first_index"], inc, A).reshape(-1)).reshape(E, A, -1)
+            (_, pos, slots, episodes, cause), _ = repeat_in_fp32(lambda p: engine.denoise_reject(
+                ctx, p0, seed=int(seed), episode_ids=np.asarray(seeds), K=K, T=H, dt=time_step, precision=p, threshold=collision_threshold,
+                max_rounds=R, draw0=0, want_vel=False, want_pos=route.rank != "device_resident", n_agents=counts, **walls), precision)
+            if route.rank == "host":        # (beyond the device top-k's limits: the host twin on every episode's real agents)
+                sel, lw = np.full((E, A, k, H, 2), np.nan, dtype=np.float32), np.full((E, A, k), np.nan, dtype=np.float32)
+                for e in range(E):
+                    sel[e, :counts[e]], lw[e, :counts[e]] = most_likely_samples(np.ascontiguousarray(pos[e][:, :counts[e]]), k)
+            elif route.rank == "none":
+                sel, lw = pos, None
+            else:
+                sel, lw = engine.topk(pos if route.rank == "device" else None, k, dims=(E, A, K, H), n_agents=counts)
+        if stats is not None:
+            stats["episodes"], stats["slots"], stats["cause"] = episodes, slots, cause
+        forecasts, logw = SC.assemble_forecasts(inc, sel, lw, b["cv"], pose_now, k, K, n_agents=counts)
+        if absent:
+            forecasts[left_out], logw[left_out] = np.nan, np.nan
+        return forecasts, logw, inc
     forecasts = np.empty((E, N, k, H + 1, 2), dtype=np.float64)
     logw = np.empty((E, N, k), dtype=np.float64)
     if R and stats is not None:

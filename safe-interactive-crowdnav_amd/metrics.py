@@ -336,14 +336,54 @@ def fill_slots(acceptable_by_round):
     return slots, episode
 
 
-def collision_statistics_host(pos: np.ndarray, threshold: float = COLLISION_THRESHOLD):
+def pair_index(i, j, A: int):
+    """The ``pdist`` index of pair (i, j), i < j, among A agents: i A - i (i + 1) / 2 + (j - i - 1)."""
+    return i * A - i * (i + 1) // 2 + (j - i - 1)
+
+
+def _counts(n_agents, E: int, A: int) -> np.ndarray:
+    n = np.asarray(n_agents, dtype=np.int64).reshape(-1)
+    if n.size != E or np.any(n < 1) or np.any(n > A):
+        raise ValueError("n_agents must hold one count in 1..A per episode")
+    return n
+
+
+def _collision_statistics_padded(pos: np.ndarray, threshold: float, n_agents):
+    """The plain twin on every compacted episode, scattered to the layout at A (``jmid_collision_statistics_padded``)."""
+    pos = np.asarray(pos)
+    E, K, A, T, _ = pos.shape
+    n = _counts(n_agents, E, A)
+    pair = np.full((E, K, A * (A - 1) // 2), np.nan)
+    agent = np.zeros((E, K, A), dtype=np.uint8)
+    sample, scene = np.empty((E, K, len(COLLISION_SAMPLE_COLUMNS))), np.empty((E, len(COLLISION_SCENE_COLUMNS)))
+    for e in range(E):
+        ne = int(n[e])
+        pr, ag, sm, sc = collision_statistics_host(pos[e:e + 1, :, :ne], threshold)
+        i, j = np.triu_indices(ne, 1)
+        at_A = pair_index(i, j, A)                                     # monotone in the index at n_e
+        pair[e][:, at_A] = pr[0]
+        agent[e, :, :ne] = ag[0]
+        sample[e] = sm[0]
+        has = sm[0, :, 1] >= 0
+        sample[e, has, 1] = at_A[sm[0, has, 1].astype(np.int64)]
+        scene[e] = sc[0]
+    return pair, agent, sample, scene
+
+
+def collision_statistics_host(pos: np.ndarray, threshold: float = COLLISION_THRESHOLD, n_agents=None):
     """pos [E, K, A, T, 2] -> (pair [E, K, P] float64, agent [E, K, A] uint8, sample [E, K, 4] float64, scene [E, 5] float64), the
     columns ``COLLISION_SAMPLE_COLUMNS`` / ``COLLISION_SCENE_COLUMNS``: what ``JmidEngine.collision_statistics`` computes on the
     device, without its size limits.  Pairs in ``pdist`` order, P = A (A - 1) / 2; a pair's value is the minimum over the T - 1
     segments of the distance from the origin to the segment of the relative position (``calc_min_dists`` / ``lineseg_dist``); an
     agent is flagged when one of its pairs is closer than ``threshold`` (``get_agents_in_collision``).  A = 1: no pairs, ``min_dist``
     +inf, ``closest_pair`` -1, ``min_dist_std`` NaN.  A non-finite position makes its pairs and the sample's ``min_dist`` NaN
-    (``closest_pair`` -1); NaN pairs never collide.  T >= 2 (with one step the reference collapses to a scalar over all pairs)."""
+    (``closest_pair`` -1); NaN pairs never collide.  T >= 2 (with one step the reference collapses to a scalar over all pairs).
+    ``n_agents`` [E] (``jmid_collision_statistics_padded``): a padded batch, episode e has n_agents[e] <= A real agents.  Defined as
+    this function on each compacted episode ``pos[e, :, :n_e]``, scattered to the shapes at A: pair (i, j) at ``pair_index(i, j, A)``,
+    NaN in the pairs of a padded agent (they take part in nothing), 0 in a padded agent's byte, ``closest_pair`` the index at A,
+    ``agent_collision_rate`` over K * n_e.  Padded rows are never read."""
+    if n_agents is not None:
+        return _collision_statistics_padded(pos, threshold, n_agents)
     pos = np.asarray(pos, dtype=np.float64)
     E, K, A, T, _ = pos.shape
     if T < 2:
@@ -432,14 +472,37 @@ def _wall_step_distance(a0, a1, b0, b1):
         return np.where(denom == 0, parallel, dist(pA, pB))
 
 
-def wall_statistics_host(pos: np.ndarray, walls: np.ndarray, radius: float, p0: Optional[np.ndarray] = None):
+def _wall_statistics_padded(pos, walls, radius, p0, n_agents):
+    """The plain twin on every compacted episode, scattered to the layout at A (``jmid_wall_statistics_padded``)."""
+    pos = np.asarray(pos)
+    E, K, A, T, _ = pos.shape
+    n = _counts(n_agents, E, A)
+    L = np.asarray(walls, dtype=np.float64).reshape(-1, 4).shape[0]
+    if p0 is not None and np.asarray(p0).shape != (E, A, 2):
+        raise ValueError("p0 must be [E, A, 2]")
+    d = np.full((E, K, A, L), np.nan)
+    agent = np.zeros((E, K, A), dtype=np.uint8)
+    sample, scene = np.empty((E, K, len(WALL_SAMPLE_COLUMNS))), np.empty((E, len(WALL_SCENE_COLUMNS)))
+    for e in range(E):
+        ne = int(n[e])
+        de, ag, sm, sc = wall_statistics_host(pos[e:e + 1, :, :ne], walls, radius, None if p0 is None else np.asarray(p0)[e:e + 1, :ne])
+        d[e, :, :ne], agent[e, :, :ne], sample[e], scene[e] = de[0], ag[0], sm[0], sc[0]
+    return d, agent, sample, scene
+
+
+def wall_statistics_host(pos: np.ndarray, walls: np.ndarray, radius: float, p0: Optional[np.ndarray] = None, n_agents=None):
     """pos [E, K, A, T, 2], walls [L, 4] or [L, 2, 2], p0 [E, A, 2] or None -> (dist [E, K, A, L] float64, agent [E, K, A] uint8,
     sample [E, K, 3] float64, scene [E, 5] float64), the columns ``WALL_SAMPLE_COLUMNS`` / ``WALL_SCENE_COLUMNS``: what
     ``JmidEngine.wall_statistics`` computes on the device (include/jmid_hip.h, ``jmid_wall_statistics``), without its size limits.
     Agent a walks pos[t-1] -> pos[t] (and p0 -> pos[0] first when ``p0`` is given); dist[a, l] is the minimum over its segments of the
     reference's closest distance between wall l and the segment, the agent hits wall l iff dist - radius < 0.  A segment with a
     non-finite end makes the agent's row NaN (NaN never hits, and decides ``min_clear``).  L = 0: ``min_clear`` +inf, counts and rates
-    0, ``min_clear_std`` NaN.  fp64 on the fp32 positions; vectorised over everything (the samples in blocks, for the memory)."""
+    0, ``min_clear_std`` NaN.  fp64 on the fp32 positions; vectorised over everything (the samples in blocks, for the memory).
+    ``n_agents`` [E] (``jmid_wall_statistics_padded``): defined as this function on each compacted episode (``pos[e, :, :n_e]``,
+    ``p0[e, :n_e]``), scattered to the shapes at A: NaN in a padded agent's row of dist, 0 in its byte, it counts nowhere and
+    ``agent_wall_hit_rate`` is over K * n_e.  Padded rows of pos and p0 are never read."""
+    if n_agents is not None:
+        return _wall_statistics_padded(pos, walls, radius, p0, n_agents)
     pos = np.asarray(np.asarray(pos, dtype=np.float32), dtype=np.float64)
     E, K, A, T, _ = pos.shape
     if T < 2:

@@ -8,7 +8,8 @@ random-init weights at the shipped width.  Three forecasters in ONE process, cal
 all three encode, denoise and, at k < K, rank on the device from the resident positions.
 Every figure is the median over the measured calls after warm-up; the three variants see the same frames in the same order and are
 interleaved call by call, so clock and thermal drift hit them alike.  Run on the GPU box:
-    python tools/reject_timing.py [--precision f16mx] [--calls 40] [--episodes 4]"""
+    python tools/reject_timing.py [--precision f16mx] [--calls 40] [--episodes 4]
+--rule RULE measures the wall predicate instead (section 33), --padded the one-loop form on mixed-count batches (section 34)."""
 import argparse
 import json
 import os
@@ -103,6 +104,57 @@ def walls_main(args, weights):
     return out
 
 
+def padded_main(args, weights):
+    """--padded: ``predict_batch(collision_free_rounds=3)`` on the naturally clustered, mixed-count scenes of
+    tools/padded_batch_timing.py (docs/NOTEBOOK.md section 34): the grouped form - one rejection loop per in-cluster count - against
+    ``collision_free_padded=True`` - ONE loop for the batch at A = the largest count.  Both in ONE process on the same scenes, seeds and
+    draw numbers, alternating call by call; next to the medians the count histogram, the share of padded rows, what the loops did
+    (samples colliding, fixed, rounds) and the distance between the two forecasts (a padded call's attention sums in another order)."""
+    import torch
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from padded_batch_timing import scenes
+    from safe_interactive_crowdnav_amd.engine import JmidEngine
+    from safe_interactive_crowdnav_amd.forecaster import predict_batch
+    out = {"threshold": args.threshold, "rounds": 3}
+    E = args.episodes
+    for point, (N, K, k, H, step) in POINTS.items():
+        eng = JmidEngine(weights, joint=True, hist_len=6, step=step)
+        hum, rob = scenes(E, N)
+        kw = dict(num_samples=K, num_ret_samples=k, horizon=H, time_step=0.25, precision=args.precision, noise="device", seed=7,
+                  collision_free_rounds=3, collision_threshold=args.threshold)
+        paths = {"grouped": {}, "padded": dict(collision_free_padded=True)}
+        ms, res, stats = {name: [] for name in paths}, {}, {name: {} for name in paths}
+        for i in range(args.warmup + args.calls):
+            order = list(paths.items())
+            order = order[i % 2:] + order[:i % 2]                           # alternate who goes first
+            for name, how in order:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res[name] = predict_batch(eng, hum, rob, list(range(E)), stats=stats[name], **how, **kw)      # (host arrays out: the call has synchronised)
+                if i >= args.warmup:
+                    ms[name].append(1e3 * (time.perf_counter() - t0))
+        inc = res["grouped"][2]
+        n_in = inc.sum(axis=1)
+        r = {name: {"median_ms": round(float(np.median(v)), 3), "p10_ms": round(float(np.percentile(v, 10)), 3),
+                    "p90_ms": round(float(np.percentile(v, 90)), 3)} for name, v in ms.items()}
+        r["calls"] = len(ms["grouped"])
+        r["counts"] = {int(a): int((n_in == a).sum()) for a in np.unique(n_in)}
+        r["padded_rows"] = round(1.0 - float(n_in.sum()) / float(E * n_in.max()), 4)
+        r["speedup"] = round(r["grouped"]["median_ms"] / r["padded"]["median_ms"], 3)
+        for name in paths:
+            ep = stats[name]["episodes"]
+            r[name].update(samples_colliding=int(ep[:, 0].sum()), samples_fixed=int(ep[:, 1].sum()), rounds=int(ep[:, 2].max()),
+                           episodes_rerun=int((ep[:, 2] > 0).sum()))
+        d = np.linalg.norm(res["padded"][0][inc] - res["grouped"][0][inc], axis=-1)
+        r["forecast_distance_m"] = {"mean": float(d.mean()), "max": float(d.max())} if k == K else None      # (k < K: the kept sets may differ)
+        r["workload"] = f"E={E}, N={N}, K={K} -> {k}, H={H}, {step} steps, {args.precision}, naturally clustered scenes, threshold {args.threshold}"
+        out[point] = r
+        print(point, json.dumps(r), flush=True)
+        eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16mx")
@@ -111,10 +163,14 @@ def main():
     ap.add_argument("--episodes", type=int, default=4)
     ap.add_argument("--rule", default=None, help="a hallway rule of crowd_env (hallway_static, rectangle, ...): measure the wall predicate instead")
     ap.add_argument("--radius", type=float, default=0.3, help="with --rule: the wall radius in metres")
+    ap.add_argument("--padded", action="store_true", help="predict_batch on mixed-count scenes: one loop per count against collision_free_padded")
+    ap.add_argument("--threshold", type=float, default=0.2, help="with --padded: the collision threshold in metres")
     args = ap.parse_args()
     weights = JMIDWeights.from_seed(NetDims(ctx_dim=256), 5)
-    if args.rule:
-        out = walls_main(args, weights)
+    if args.rule or args.padded:
+        if args.padded and "--episodes" not in sys.argv:
+            args.episodes = 8
+        out = padded_main(args, weights) if args.padded else walls_main(args, weights)
         try:
             import bench
             out["sustained_mfma"] = bench.sustained_mfma_tflops()
