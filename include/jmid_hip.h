@@ -732,6 +732,54 @@ int jmid_denoise_reject_padded_seeded(jmid_handle_t h, int E, int A, int K, int 
                                       double threshold, int max_rounds, int L, const double* walls, double radius, float* vel_out,
                                       float* pos_out, int32_t* slot_out, int32_t* episode_out, int32_t* cause_out, int mem);
 
+/* Collision repair: the second mechanism DiffusionTraj.sample names - constraint_type, next to with_constraints (MID/models/diffusion.py:
+ * 544-613); every shipped config sets constraint_type: opt_softplus (test_time_configs/mid_jp.yaml:34).  The reference's stripped sampler
+ * has no body for it and nothing in the reference mentions softplus, so THE RULE is decided here, as the rejection rule was.  OFF unless
+ * this entry is called.  A small fp64 optimisation on FINISHED samples: only colliding samples are touched, no net evaluation, no redraw,
+ * no noise (it works behind every entry that leaves positions, whatever drew them), no download.
+ * Per joint sample x[a][t], a < n agents, t < T; inputs fp32, everything inside fp64, every sample independent of every other:
+ *   Candidates  a sample is repaired iff jmid_collision_statistics' own kernel gives it n_agents_colliding > 0 at `threshold`.  A sample
+ *               whose min_dist is NaN is untouched and reported as such (state 3); a sample with A = 1 or n_agents[e] = 1 is untouched.
+ *               Every untouched sample comes back bit for bit.
+ *   Objective   J(x) = sum over the pairs i < j (pdist order) and the segments s = 0 .. T - 2 of tau * softplus((m - d_ijs) / tau),
+ *               m = threshold + margin, d_ijs the distance from the origin to the segment of the relative position in closest-point form:
+ *                 a = x_i[s] - x_j[s], b = x_i[s+1] - x_j[s+1], ab = b - a, den = ab . ab,
+ *                 u = den > 0 ? clamp(-(a . ab) / den, 0, 1) : 0,  c = a + u ab,  d = sqrt(c . c),  n = d > 0 ? c / d : (1, 0)
+ *               The step from the present position is not part of it, as in the pedestrian predicate.
+ *   Iteration   at most max_iter times:
+ *                 1. dmin = the minimum of d over all pairs and segments; stop when dmin >= threshold + margin / 2;
+ *                 2. sigma = sigmoid(z), z = (m - d) / tau, in the overflow-free form: e = exp(-|z|), sigma = 1 / (1 + e) for z >= 0 and
+ *                    e / (1 + e) otherwise.  Pair (i, j, s) subtracts (sigma (1 - u)) n from g_i[s] and (sigma u) n from g_i[s+1] and
+ *                    adds the same amounts to g_j;
+ *                 3. x <- x - step g (Jacobi: every gradient comes from the same iterate).
+ *               The summation order of g[a][t] is fixed: partners b ascending, per partner the segment t - 1 first, then the segment t.
+ *               No atomics.
+ *   End         x is rounded to fp32 and the predicate is evaluated on the rounded values with the predicate's own device function.
+ *               Acceptable: state 1 (repaired).  Otherwise the sample reverts to its input bits, state 2: an output is always either the
+ *               model's sample or an acceptable one.  The velocities of a repaired sample are
+ *               float((double(x32[t]) - double(x32[t-1])) / dt), x32[-1] = p0.
+ * Defaults of the Python layer (arguments here, not constants): margin 0.02 m, tau 0.005 m, step 0.02 m, max_iter 32.
+ *   n_agents    int32 [E] HOST, or NULL: every agent is real.  Otherwise the layout and NaN conventions of "Padded scene batches": the
+ *               padded agents take part in nothing and their rows are copied as they are
+ *   pos         [E, K, A, T, 2], or NULL: the resident set (what jmid_denoise*, or the rejection entries, left; the rules of jmid_topk), which
+ *               is repaired IN PLACE - a following jmid_topk(pos = NULL) or statistics entry sees the repaired set; the accepted block's
+ *               velocities are rewritten too where the block holds them and p0 is given.  The forgetting rules are unchanged
+ *   p0          [E, A, 2] or NULL (no velocities); dt must then be finite and > 0
+ *   pos_out     [E, K, A, T, 2] or NULL; may be pos itself in JMID_MEM_DEVICE.  With pos = NULL: a copy of the repaired resident set
+ *   vel_out     [E, K, A, T, 2] or NULL, IN and OUT: the caller's velocities, of which only the real rows of REPAIRED samples are rewritten
+ *   sample_out  [E, K, 4] float = {min_dist before, min_dist after (of the sample that comes back), iterations used, state: 0 untouched,
+ *               1 repaired, 2 reverted, 3 NaN}; may be NULL
+ *   episode_out [E, 3] int32 = {samples colliding on entry (states 1 and 2), samples repaired, the largest iteration count}; may be NULL
+ * max_iter = 0 is the identity plus the flags (every colliding sample is state 2).  Three launches on the handle's stream - the collision
+ * kernel's lean form, one workgroup per (episode, sample) that holds the sample in LDS and does the iteration, the final predicate, the
+ * revert and the velocities, one workgroup per episode for episode_out - and nothing comes back to the host in between.
+ * Limits: those of jmid_collision_statistics.  JMID_EINVAL: those, a threshold or margin that is not finite or < 0, tau <= 0, step <= 0,
+ * max_iter outside 0..1024, a NULL p0 with a non-NULL vel_out, a count outside 1..A, pos with every output NULL, pos = NULL without a
+ * resident set of this shape. */
+int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, float dt,
+                           double threshold, double margin, double tau, double step, int max_iter, float* pos_out, float* vel_out,
+                           float* sample_out, int32_t* episode_out, int mem);
+
 /* Padded chains on the resident scene: jmid_predict_scene / jmid_forecast_scene (and their seeded forms) for a scene whose episodes have
  * DIFFERENT in-cluster counts - what jmid_build_scene leaves whenever it chooses the clusters itself - in one call, in the layout and
  * under the rules of "Padded scene batches" above.  The caller passes no n_agents: the counts are the resident scene's n_in, read on the

@@ -2,6 +2,7 @@
 #include "jmid_ctx.hpp"
 #include "collision_stats.hpp"
 #include "wall_stats.hpp"
+#include "repair.hpp"
 
 namespace jmid_host {
 
@@ -544,6 +545,7 @@ int reject_loop(jmid_ctx* h, const char* who, int E, int A, int K, int T, const 
     // the accepted set is what pos = NULL consumers see, under jmid_denoise's forgetting rules (every later denoise call and every
     // host-mode entry that clears last_pos forgets it, although this block itself would survive them)
     h->last_pos = io.acc_pos.p;
+    h->last_vel = io.acc_vel; h->last_vel_pos = io.acc_pos.p;
     h->last_pos_dims[0] = E; h->last_pos_dims[1] = A; h->last_pos_dims[2] = K; h->last_pos_dims[3] = T;
     return order_out(h, mem);
 }
@@ -938,6 +940,70 @@ int jmid_wall_statistics_padded(jmid_handle_t h, int E, int A, int K, int T, con
     if (E > 0 && A > 0)
         if (int rc = check_n_agents(h, "jmid_wall_statistics_padded", n_agents, E, A)) return rc;
     return wall_entry(h, "jmid_wall_statistics_padded", E, A, K, T, n_agents, pos, p0, L, walls, radius, dist_out, agent_out, sample_out, scene_out, mem);
+}
+
+// The repair of colliding samples (repair.hpp): the collision kernel's lean form for the flags, the repair kernel, the episode rows - three
+// launches on the handle's stream, nothing comes back to the host in between.  pos null: the resident set, in place
+int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, float dt,
+                           double threshold, double margin, double tau, double step, int max_iter, float* pos_out, float* vel_out,
+                           float* sample_out, int32_t* episode_out, int mem) {
+    if (!h || E <= 0) return fail(h, JMID_EINVAL, "bad argument");
+    const char* who = "jmid_repair_collisions";
+    const std::string w(who);
+    if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
+        return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(h, JMID_EINVAL, w + ": the threshold must be finite and >= 0");
+    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(h, JMID_EINVAL, w + ": the margin must be finite and >= 0");
+    if (!(tau > 0.0) || !std::isfinite(tau)) return fail(h, JMID_EINVAL, w + ": tau must be finite and > 0");
+    if (!(step > 0.0) || !std::isfinite(step)) return fail(h, JMID_EINVAL, w + ": the step must be finite and > 0");
+    if (max_iter < 0 || max_iter > RPR_MAX_ITER) return fail(h, JMID_EINVAL, w + ": max_iter must lie in 0..1024");
+    if (vel_out && !p0) return fail(h, JMID_EINVAL, w + ": vel_out needs p0 (a velocity's first step starts at the present position)");
+    if (p0 && !(dt > 0.0f && std::isfinite(dt))) return fail(h, JMID_EINVAL, w + ": p0 needs a finite dt > 0 (the velocities divide by it)");
+    if (pos && !pos_out && !vel_out && !sample_out && !episode_out) return fail(h, JMID_EINVAL, w + ": every output is NULL");
+    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
+    if (n_agents)
+        if (int rc = check_n_agents(h, who, n_agents, E, A)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
+    const bool host = mem == JMID_MEM_HOST;
+    const size_t M2 = (size_t)E * K * A * T * 2;
+    CollisionStatsArgs cs{};
+    cs.E = E; cs.A = A; cs.K = K; cs.T = T; cs.threshold = threshold;
+    RepairArgs g{};
+    g.E = E; g.A = A; g.K = K; g.T = T; g.max_iter = max_iter;
+    g.threshold = threshold; g.margin = margin; g.tau = tau; g.step = step; g.dt = (double)dt;
+    Staging st(h, mem, h->kde_ws, who);
+    st.scratch(&cs.ws, (size_t)E * K * CLS_WS_COLS * 8);
+    if (pos) {
+        st.in(&g.src, pos, M2);
+        if (pos_out) st.out(&g.dst, pos_out, M2);
+    } else {      // in place where the samples lie; pos_out is a copy of the block afterwards
+        g.src = h->last_pos;
+        g.dst = const_cast<float*>(h->last_pos);
+        if (p0 && h->last_vel && h->last_vel_pos == h->last_pos) g.vel2 = h->last_vel;
+    }
+    if (p0 && (vel_out || g.vel2)) st.in(&g.p0, p0, (size_t)E * A * 2);
+    if (vel_out) {      // in and out: only the rows of repaired samples are rewritten
+        g.vel = vel_out;
+        if (host) st.add(&g.vel, vel_out, vel_out, M2 * sizeof(float));
+    }
+    if (sample_out) st.out(&g.sample, sample_out, (size_t)E * K * RPR_SAMPLE_COLS);
+    else st.scratch(&g.sample, (size_t)E * K * RPR_SAMPLE_COLS * sizeof(float));
+    if (episode_out) st.out(&g.episode, episode_out, (size_t)E * RPR_EPISODE_COLS);
+    if (int rc = st.begin()) return rc;
+    if (n_agents) {
+        if (int rc = h->nag.upload(h, n_agents, E, who)) return rc;
+        cs.n_agents = g.n_agents = h->nag.get<int>();
+    }
+    cs.pos = g.src;
+    g.ws = cs.ws;
+    {
+        ProfScope ps(h, KC_EVAL_STATS, h->stream);
+        HIPCHK(h, launch_collision_stats(cs, h->stream));
+        HIPCHK(h, launch_repair(g, h->stream));
+    }
+    if (!pos && pos_out) HIPCHK(h, hipMemcpyAsync(pos_out, h->last_pos, M2 * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+    return st.end();
 }
 
 // jmid_topk (n_agents null) and jmid_topk_padded

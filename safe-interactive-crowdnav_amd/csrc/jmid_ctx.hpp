@@ -174,6 +174,10 @@ struct jmid_ctx {
     // jmid_topk ranks and jmid_eval_statistics scores when they are given no pos pointer
     const float* last_pos = nullptr;
     int last_pos_dims[4] = {0, 0, 0, 0};     // E, A, K, T
+    // the velocities that go with last_pos where a block holds them (the accepted block of the rejection entries, when they were asked
+    // for), valid only while last_pos == last_vel_pos: jmid_repair_collisions(pos = NULL) rewrites the rows of the samples it repairs
+    float* last_vel = nullptr;
+    const float* last_vel_pos = nullptr;
     // jmid_denoise_reject_seeded: the accepted set and the loop's tables, in a workspace of its own (it survives the reruns, which reuse the
     // arena; last_pos points into it after the call), and the pinned words of the loop's one download per round
     jmid_host::Block reject_ws;

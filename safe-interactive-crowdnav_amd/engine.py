@@ -886,6 +886,54 @@ class JmidEngine:
                                                         *[_ptr(o) for o in outs], self._mem(dev)))
         return tuple(outs)
 
+    def repair_collisions(self, pos: Optional[ArrayLike], threshold: float = 0.2, margin: float = 0.02, tau: float = 0.005, step: float = 0.02,
+                          max_iter: int = 32, p0: Optional[ArrayLike] = None, dt: float = 0.25, vel: Optional[ArrayLike] = None,
+                          dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None, want_pos: Optional[bool] = None):
+        """Collision repair on the device (``jmid_repair_collisions``; the rule stands in include/jmid_hip.h, its host twin is
+        ``metrics.repair_collisions_host``): every joint sample of pos [E, K, A, T, 2] in which ``collision_statistics`` counts a colliding
+        agent at ``threshold`` is pushed apart under a softplus penalty until the predicate holds - a small fp64 optimisation on the
+        finished samples, no net evaluation, no redraw, no download - and comes back either repaired (acceptable) or bit for bit as it
+        went in.  -> (pos_out [E, K, A, T, 2] or None, vel_out or None, sample [E, K, 4] = ``metrics.REPAIR_SAMPLE_COLUMNS``,
+        episode [E, 3] int32 = ``metrics.REPAIR_EPISODE_COLUMNS``).  NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out.
+        ``vel`` [E, K, A, T, 2] with ``p0`` [E, A, 2] and ``dt``: the samples' velocities; a copy comes back in which the rows of the
+        repaired samples are (x[t] - x[t - 1]) / dt, x[-1] = p0.
+        ``pos=None`` with ``dims=(E, A, K, T)``: the set the preceding ``denoise`` / ``denoise_reject`` call left in the engine's workspace is
+        repaired IN PLACE (with ``p0``, the accepted block's velocities too where it holds them): ``topk(None, ...)`` and the statistics
+        entries then see the repaired set; pos_out is None unless ``want_pos=True`` (``p0`` / ``vel`` decide where the outputs live; host
+        arrays without them).  ``n_agents`` [E]: a padded batch - padded agents take part in nothing and their rows pass through."""
+        if pos is None:
+            if dims is None:
+                raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
+            E, A, K, T = (int(v) for v in dims)
+            like = vel if vel is not None else p0
+            dev, bp = like is not None and _is_cuda(like), None
+            want_pos = bool(want_pos)
+        else:
+            dev, like = _is_cuda(pos), pos
+            E, K, A, T, _ = (int(v) for v in pos.shape)
+            bp = _Buf(pos, dev)
+            want_pos = True if want_pos is None else bool(want_pos)
+        if vel is not None and p0 is None:
+            raise ValueError("vel needs p0 (a velocity's first step starts at the present position)")
+        if p0 is not None and tuple(p0.shape) != (E, A, 2):
+            raise ValueError("p0 must be [E, A, 2]")
+        if vel is not None and tuple(vel.shape) != (E, K, A, T, 2):
+            raise ValueError("vel must be [E, K, A, T, 2]")
+        b0 = _Buf(p0, dev) if p0 is not None else None
+        where = like.device if dev else None
+        vel_out = None
+        if vel is not None:      # in and out: the library rewrites the rows of the repaired samples in this copy
+            bv = _Buf(vel, dev)
+            vel_out = bv.keep.clone() if dev else np.array(bv.keep, dtype=np.float32, copy=True)
+        pos_out = _out((E, K, A, T, 2), device=where) if want_pos else None
+        sample, episode = _out((E, K, 4), device=where), _out((E, 3), np.int32, where)
+        na = agent_counts(n_agents, E) if n_agents is not None else None
+        self._check(self._lib.jmid_repair_collisions(self._h, E, A, K, T, _ptr(na), bp.ptr if bp is not None else None,
+                                                     b0.ptr if b0 is not None else None, float(dt), float(threshold), float(margin), float(tau),
+                                                     float(step), int(max_iter), _ptr(pos_out), _ptr(vel_out), _ptr(sample), _ptr(episode),
+                                                     self._mem(dev)))
+        return pos_out, vel_out, sample, episode
+
     def wall_statistics(self, pos: Optional[ArrayLike], walls, radius: float, p0: Optional[ArrayLike] = None,
                         dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None):
         """Wall statistics of joint samples on the device (``jmid_wall_statistics``; the reference simulator's

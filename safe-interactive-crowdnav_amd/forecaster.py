@@ -44,6 +44,14 @@ receives as ``static_obs``, in the forecasts' world frame): a joint sample in wh
 position included - comes closer than ``wall_radius`` to a wall is redrawn too (``jmid_denoise_reject_walls_seeded``), and
 ``self.rejection`` gains the two cause counts (samples that fail the pedestrian predicate, the wall predicate).  The forecaster knows
 no agent radius: ``wall_radius`` has no default.
+``constraint_type="opt_softplus"`` (opt-in, under EVERY ``rng_compat``; the name is the reference's, ``DiffusionTraj.sample``'s second
+mechanism and what every shipped config sets): collision repair (``JmidEngine.repair_collisions``; the rule stands in include/jmid_hip.h) -
+a joint sample in which two pedestrians come closer than ``collision_threshold`` is pushed apart on the device under a softplus penalty
+until the predicate holds, or comes back as it was when ``max_iter`` steps do not get it there: no redraw, no second denoise loop, no
+download.  The route is staged (denoise -> repair -> ranking on the repaired set), ``self.repair`` holds the last call's (samples with
+collisions, repaired, reverted, largest iteration count), and ``repair_options`` = {margin, tau, step, max_iter} overrides the defaults.
+Together with ``collision_free_rounds=R`` the redraw loop runs first and the repair takes whatever is still flagged.  Not with
+``static_obstacles=``: walls are not in the objective.
 
 Differences from the reference that a caller can observe:
   * the engine (weights on the GPU) is cached across instances: the reference rebuilds the model and reloads the
@@ -116,6 +124,51 @@ def wall_arguments(static_obstacles, wall_radius, rounds: int) -> dict:
     if not (np.isfinite(radius) and radius >= 0.0):
         raise ValueError("wall_radius must be finite and >= 0")
     return {"walls": walls, "wall_radius": radius}
+
+
+REPAIR_OPTIONS = ("margin", "tau", "step", "max_iter")
+
+
+def repair_arguments(constraint_type, repair_options=None, static_obstacles=None) -> Optional[dict]:
+    """The ``constraint_type`` / ``repair_options`` keywords of the forecaster, ``predict_batch`` and ``offline.sample`` as the keywords of
+    ``JmidEngine.repair_collisions``: None without a constraint type (nothing changes), else the options that were given ({}: the
+    defaults).  The only type is the reference configs' ``"opt_softplus"``; walls are not in its objective, so ``static_obstacles`` is
+    refused with it."""
+    if constraint_type is None:
+        if repair_options:
+            raise ValueError("repair_options is given without constraint_type")
+        return None
+    if constraint_type != "opt_softplus":
+        raise ValueError(f"unknown constraint_type {constraint_type!r} (the one there is: 'opt_softplus')")
+    if static_obstacles is not None:
+        raise ValueError("static_obstacles cannot be combined with constraint_type='opt_softplus': walls are not in the repair's objective "
+                         "(a repaired sample could be pushed into one)")
+    opts = dict(repair_options or {})
+    unknown = sorted(set(opts) - set(REPAIR_OPTIONS))
+    if unknown:
+        raise ValueError(f"unknown repair_options {unknown} (known: {list(REPAIR_OPTIONS)})")
+    for key in ("margin", "tau", "step"):
+        if key in opts and not (np.isfinite(opts[key]) and (opts[key] >= 0.0 if key == "margin" else opts[key] > 0.0)):
+            raise ValueError(f"repair_options[{key!r}] must be finite and {'>= 0' if key == 'margin' else '> 0'}")
+    if "max_iter" in opts and not 0 <= int(opts["max_iter"]) <= 1024:
+        raise ValueError("repair_options['max_iter'] must lie in 0..1024")
+    return opts
+
+
+def repair_totals(episode) -> Tuple[int, int, int, int]:
+    """``episode`` [..., 3] of ``JmidEngine.repair_collisions`` -> (samples with collisions, repaired, reverted, largest iteration count)."""
+    ep = np.asarray(episode.detach().cpu() if hasattr(episode, "detach") else episode).reshape(-1, 3).astype(np.int64)
+    if not ep.shape[0]:
+        return 0, 0, 0, 0
+    return int(ep[:, 0].sum()), int(ep[:, 1].sum()), int(ep[:, 0].sum() - ep[:, 1].sum()), int(ep[:, 2].max())
+
+
+def repair_stage(engine: JmidEngine, pos, dims: Tuple[int, int, int, int], threshold: float, options: dict, n_agents=None):
+    """The repair stage of a staged route behind a denoise (or rejection) call of ``dims`` = (E, A, K, H): ``pos`` [E, K, A, H, 2], or None
+    when the samples stayed on the device - they are then repaired where they lie and the ranking reads them there.
+    -> (pos repaired, or None; episode [E, 3])."""
+    out, _, _, episode = engine.repair_collisions(pos, threshold=threshold, dims=dims if pos is None else None, n_agents=n_agents, **options)
+    return out, episode
 
 
 def advance_cuda_generator(device_id: int, shape: Tuple[int, ...], n: int) -> None:
@@ -215,7 +268,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
                  seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False, coast_frames: int = 0,
                  collision_free_rounds: int = 0, collision_threshold: float = 0.2, static_obstacles=None,
-                 wall_radius: Optional[float] = None):
+                 wall_radius: Optional[float] = None, constraint_type: Optional[str] = None, repair_options: Optional[dict] = None):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -282,6 +335,10 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
             raise ValueError("collision_threshold must be finite and >= 0")
         # static_obstacles + wall_radius (opt-in, with collision_free_rounds > 0): the wall predicate joins the pedestrian one, and
         # rejection holds five counts (the three, then the samples that fail the pedestrian predicate, the wall predicate)
+        # constraint_type="opt_softplus" (opt-in, every RNG contract): collision repair behind the denoise stage (and behind the redraw
+        # loop, when both are asked for); repair: the last call's (samples with collisions, repaired, reverted, largest iteration count)
+        self.constraint_type, self._repair_options = constraint_type, repair_arguments(constraint_type, repair_options, static_obstacles)
+        self.repair: Optional[Tuple[int, int, int, int]] = None
         self._walls = wall_arguments(static_obstacles, wall_radius, self.collision_free_rounds)
         self.rejection: Optional[Tuple[int, ...]] = None
         self._init_MID(mid_config_file, weights, device_id, lib_path)
@@ -543,7 +600,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         check = self.self_check and (1, K * A, H, 2) not in self._checked_shapes
         route = plan_route(k=k, K=K, A=A, H=H, device_topk=self.device_topk, device_scene=self.device_scene,
                            device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped",
-                           tracks=present is not None, collision_free=self.collision_free_rounds > 0)
+                           tracks=present is not None, collision_free=self.collision_free_rounds > 0,
+                           repair=self._repair_options is not None)
         result, call = None, dict(dt=self.time_step, precision=self.precision)
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
@@ -572,6 +630,9 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                     pos = self._denoise(x_np, ctx[None], p0[None], want_pos=route.rank != "device_resident")
                     if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
                         pos = self._self_check(x_np, ctx[None], p0[None], pos)
+                if self._repair_options is not None:      # on the set the stage above left: in place on the device, or on the host copy
+                    pos, episode = repair_stage(self.engine, pos, (1, A, K, H), self.collision_threshold, self._repair_options)
+                    self.repair = repair_totals(episode)
                 t2 = time.perf_counter()
                 rows, logw = rank_samples(self.engine, route.rank, pos, k, (1, A, K, H))
         t3 = time.perf_counter()
@@ -633,13 +694,15 @@ def scene_source(device_scene: bool, device_frames: bool, short: bool = False, f
 
 def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, device_scene: bool = False, device_frames: bool = False,
                check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False,
-               resident: bool = False, tracks: bool = False, collision_free: bool = False) -> Route:
+               resident: bool = False, tracks: bool = False, collision_free: bool = False, repair: bool = False) -> Route:
     """Every decision of a call that does not need an array: the flags, k of K samples, A in-cluster pedestrians, horizon H, whether the
     first-call self check is due (``check``), whether the window is short (``short``) and whether the histories are frames (``frames``).
     ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count, ``resident``: that form on the
     batch's resident scene (``padded="resident"``: forecast_scene_padded).  ``tracks``: per-track windows (``track_presence``).
     ``collision_free``: collision-free sampling (``collision_free_rounds`` > 0) - the rejection loop has no one-entry chain, so the run is
-    staged (encode -> ``denoise_reject`` -> rank) and the ranking reads the accepted set where the loop left it."""
+    staged (encode -> ``denoise_reject`` -> rank) and the ranking reads the accepted set where the loop left it.
+    ``repair``: collision repair (``constraint_type="opt_softplus"``) - a stage between the denoise call and the ranking, so the run is
+    staged too (encode -> denoise -> ``repair_collisions`` -> rank); with neither of the two nothing changes."""
     scene = scene_source(device_scene, device_frames, short, frames, batch, resident, tracks)
     # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits - the reference
     # has none - the host twin ranks them
@@ -650,7 +713,7 @@ def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, devi
     else:           # a short window built on the host is staged: jmid_predict has no first_index (a resident one is predict_scene's)
         chain = not (short and scene == "host")
     chain = chain and (on_dev or k == K) and not check        # (the self check compares the staged denoise call's positions)
-    chain = chain and not collision_free
+    chain = chain and not collision_free and not repair
     rank = "none" if k >= K else "host" if not on_dev else "device" if check else "device_resident"
     return Route(scene, "chain" if chain else "staged", rank)
 
@@ -701,7 +764,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   device_frames: bool = False, noise: str = "torch", seed: int = 0,
                   padded=False, short_history: bool = False, first_frame=None, collision_free_rounds: int = 0,
                   collision_threshold: float = 0.2, stats: Optional[dict] = None, static_obstacles=None,
-                  wall_radius: Optional[float] = None, collision_free_padded: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  wall_radius: Optional[float] = None, collision_free_padded: bool = False, constraint_type: Optional[str] = None,
+                  repair_options: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -758,12 +822,18 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     its limits).  Episode e draws what it draws in its count group; its forecasts equal the grouped path's up to the rounding of a
     padded call's attention (bit for bit when every count is the same).  ``stats`` gets ``episodes``, ``slots`` and ``cause`` in input
     order.  A batch with an empty cluster takes the count groups.
+    ``constraint_type="opt_softplus"`` (opt-in, with either ``noise``; ``repair_options`` = {margin, tau, step, max_iter}): collision repair
+    (``engine.repair_collisions``) behind every group's denoise call - or behind its rejection loop, ``collision_free_padded`` included,
+    when ``collision_free_rounds`` is given too - and the ranking on the repaired set; every group is staged.  ``stats`` gets ``repair``
+    [E, 3] int32 = (samples with collisions, repaired, largest iteration count), rows in input order (an empty cluster: zeros).  Not with
+    ``static_obstacles=`` (walls are not in the objective); with ``padded=`` the batch takes the count groups.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
     if padded not in (False, True, "resident"):
         raise ValueError("padded must be False, True or 'resident'")
     R = int(collision_free_rounds)
+    fix = repair_arguments(constraint_type, repair_options, static_obstacles)
     walls = wall_arguments(static_obstacles, wall_radius, R)
     if R:
         if padded:
@@ -802,7 +872,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
 
     def plan(A, padded=False, resident=False):
         return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
-                          short=ff is not None, batch=True, padded=padded, resident=resident, collision_free=R > 0)
+                          short=ff is not None, batch=True, padded=padded, resident=resident, collision_free=R > 0, repair=fix is not None)
 
     def torch_x_T(e, A):
         return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
@@ -854,6 +924,10 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             (_, pos, slots, episodes, cause), _ = repeat_in_fp32(lambda p: engine.denoise_reject(
                 ctx, p0, seed=int(seed), episode_ids=np.asarray(seeds), K=K, T=H, dt=time_step, precision=p, threshold=collision_threshold,
                 max_rounds=R, draw0=0, want_vel=False, want_pos=route.rank != "device_resident", n_agents=counts, **walls), precision)
+            if fix is not None:
+                pos, fixed = repair_stage(engine, pos, (E, A, K, H), collision_threshold, fix, n_agents=counts)
+                if stats is not None:
+                    stats["repair"] = fixed
             if route.rank == "host":        # (beyond the device top-k's limits: the host twin on every episode's real agents)
                 sel, lw = np.full((E, A, k, H, 2), np.nan, dtype=np.float32), np.full((E, A, k), np.nan, dtype=np.float32)
                 for e in range(E):
@@ -870,6 +944,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         return forecasts, logw, inc
     forecasts = np.empty((E, N, k, H + 1, 2), dtype=np.float64)
     logw = np.empty((E, N, k), dtype=np.float64)
+    if fix is not None and stats is not None:
+        stats["repair"] = np.zeros((E, 3), dtype=np.int32)
     if R and stats is not None:
         stats["episodes"], stats["slots"] = np.zeros((E, 3), dtype=np.int32), np.zeros((E, K, 3), dtype=np.int32)
         if walls:
@@ -909,6 +985,10 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                         stats["cause"][eps] = cause[0]
             else:
                 pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
+            if fix is not None and A:
+                pos, fixed = repair_stage(engine, pos, (len(eps), A, K, H), collision_threshold, fix)
+                if stats is not None:
+                    stats["repair"][eps] = fixed
             sel, lw = rank_samples(engine, route.rank, pos, k, (len(eps), A, K, H))
         forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], sel, lw, b["cv"][eps], pose_now[eps], k, K)
     if absent:

@@ -14,6 +14,10 @@ The collision statistics (``collision_statistics_host``, ``summarise_collisions`
 ``jmid_collision_statistics``) follow MID/models/collision_check_utils.py: ``calc_min_dists`` (:58-80) with ``lineseg_dist`` (:20-55)
 for the clearance of every agent pair of one joint sample, ``get_agents_in_collision`` (:83-97) for the agents that collide.
 
+Collision repair (``repair_collisions_host``; ``csrc/repair.hpp``, ``jmid_repair_collisions``) is the twin of the rule include/jmid_hip.h
+states for the reference's ``constraint_type: opt_softplus``: colliding samples are pushed apart under a softplus penalty on that
+clearance until the predicate holds, or come back as they were.
+
 The wall statistics (``wall_statistics_host``, ``summarise_walls``; ``csrc/wall_stats.hpp``, ``jmid_wall_statistics``) take the
 reference simulator's predicate: a step hits a wall when ``closest_distance_between_line_segments(wall, step) - radius < 0``
 (crowd_sim_plus/envs/crowd_sim_plus.py:885-893, crowd_sim_plus/envs/utils/utils_plus.py:205-338).
@@ -431,6 +435,119 @@ def summarise_collisions(scene: np.ndarray) -> Dict[str, float]:
     scene = np.asarray(scene, dtype=np.float64).reshape(-1, len(COLLISION_SCENE_COLUMNS))
     with np.errstate(invalid="ignore"):
         return {c: float(np.mean(scene[:, k])) for k, c in enumerate(COLLISION_SCENE_COLUMNS)}
+
+
+REPAIR_SAMPLE_COLUMNS = ("min_dist_before", "min_dist_after", "iterations", "state")
+REPAIR_EPISODE_COLUMNS = ("colliding", "repaired", "max_iterations")
+REPAIR_UNTOUCHED, REPAIR_REPAIRED, REPAIR_REVERTED, REPAIR_NAN = 0, 1, 2, 3
+# the defaults of collision repair (include/jmid_hip.h, ``jmid_repair_collisions``): arguments of the entry, not constants of the rule
+REPAIR_DEFAULTS = {"margin": 0.02, "tau": 0.005, "step": 0.02, "max_iter": 32}
+
+
+def _repair_segments(x: np.ndarray, lo: np.ndarray, hi: np.ndarray, m: float, tau: float, exp):
+    """The closest-point form of the rule for the pairs (lo[a], hi[a]) of x [S, n, T, 2], every segment: -> (d, u, nx, ny, sigma), each
+    [S, n, T - 1].  The operations and their order are the device function's (``csrc/repair.hpp::rpr_segment``)."""
+    rel = x[:, lo] - x[:, hi]
+    ax, ay, bx, by = rel[:, :, :-1, 0], rel[:, :, :-1, 1], rel[:, :, 1:, 0], rel[:, :, 1:, 1]
+    abx, aby = bx - ax, by - ay
+    den = abx * abx + aby * aby
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = np.where(den > 0.0, np.clip(-(ax * abx + ay * aby) / den, 0.0, 1.0), 0.0)
+        cx, cy = ax + u * abx, ay + u * aby
+        d = np.sqrt(cx * cx + cy * cy)
+        nx, ny = np.where(d > 0.0, cx / d, 1.0), np.where(d > 0.0, cy / d, 0.0)
+    z = (m - d) / tau
+    e = exp(-np.abs(z))
+    sigma = np.where(z >= 0.0, 1.0 / (1.0 + e), e / (1.0 + e))
+    return d, u, nx, ny, sigma
+
+
+def _repair_iterate(x: np.ndarray, threshold: float, margin: float, tau: float, step: float, max_iter: int, exp):
+    """The iteration of the rule on the candidates x [S, n, T, 2] float64 -> (x at the end, iterations used [S])."""
+    S, n, T, _ = x.shape
+    m, stop = threshold + margin, threshold + margin * 0.5
+    x, iters, active = x.copy(), np.zeros(S, dtype=np.int64), np.ones(S, dtype=bool)
+    agents = np.arange(n)
+    for _ in range(int(max_iter)):
+        idx = np.flatnonzero(active)
+        if not idx.size:
+            break
+        xa = x[idx]
+        g = np.zeros_like(xa)
+        dmin = np.full(idx.size, np.inf)
+        for b in range(n):                                   # partners ascending; a partner's segment t - 1 before its segment t
+            lo, hi = np.minimum(agents, b), np.maximum(agents, b)
+            d, u, nx, ny, sigma = _repair_segments(xa, lo, hi, m, tau, exp)
+            real = (agents != b)[None, :, None]
+            sign = np.where(agents < b, -1.0, 1.0)[None, :, None]      # the pair's i subtracts, its j adds
+            w1, w0 = sigma * u, sigma * (1.0 - u)
+            for c, nc in ((0, nx), (1, ny)):
+                far, near = w1 * nc, w0 * nc
+                g[:, :, 1:, c] = np.where(real, np.where(sign < 0, g[:, :, 1:, c] - far, g[:, :, 1:, c] + far), g[:, :, 1:, c])
+                g[:, :, :-1, c] = np.where(real, np.where(sign < 0, g[:, :, :-1, c] - near, g[:, :, :-1, c] + near), g[:, :, :-1, c])
+            dmin = np.minimum(dmin, np.where(real, d, np.inf).min(axis=(1, 2)))
+        go = dmin < stop
+        active[idx[~go]] = False
+        moved = idx[go]
+        x[moved] = xa[go] - step * g[go]
+        iters[moved] += 1
+    return x, iters
+
+
+def repair_collisions_host(pos: np.ndarray, threshold: float = COLLISION_THRESHOLD, margin: float = REPAIR_DEFAULTS["margin"],
+                           tau: float = REPAIR_DEFAULTS["tau"], step: float = REPAIR_DEFAULTS["step"],
+                           max_iter: int = REPAIR_DEFAULTS["max_iter"], p0: Optional[np.ndarray] = None, dt: Optional[float] = None,
+                           vel: Optional[np.ndarray] = None, n_agents=None, exp=np.exp):
+    """The NumPy twin of collision repair (``jmid_repair_collisions``; include/jmid_hip.h states the rule, ``csrc/repair.hpp`` is the
+    kernel): the same candidates, the same operations in the same order, the same outputs.  pos [E, K, A, T, 2] float32 ->
+    (pos_out float32 [E, K, A, T, 2], vel_out float32 or None, sample float64 [E, K, 4] = ``REPAIR_SAMPLE_COLUMNS``, episode int32 [E, 3] =
+    ``REPAIR_EPISODE_COLUMNS``).  A sample is a candidate iff ``collision_statistics_host`` counts a colliding agent in it at
+    ``threshold``; a NaN ``min_dist`` is state 3; everything that is not repaired comes back bit for bit.  ``vel`` [E, K, A, T, 2] with
+    ``p0`` [E, A, 2] and ``dt``: the velocities, of which the rows of repaired samples are rewritten as
+    float32((float64(x32[t]) - float64(x32[t - 1])) / dt), x32[-1] = p0.  ``n_agents`` [E]: a padded batch - the rule on every compacted
+    episode, the padded rows as they are.  ``exp``: the exponential (the tests perturb it)."""
+    pos = np.asarray(pos)
+    if pos.dtype != np.float32:
+        raise ValueError("pos must be float32 (the rule is defined on the fp32 samples)")
+    E, K, A, T, _ = pos.shape
+    for name, v, low in (("threshold", threshold, True), ("margin", margin, True), ("tau", tau, False), ("step", step, False)):
+        if not (np.isfinite(v) and (v >= 0.0 if low else v > 0.0)):
+            raise ValueError(f"{name} must be finite and {'>= 0' if low else '> 0'}")
+    if not 0 <= int(max_iter) <= 1024:
+        raise ValueError("max_iter must lie in 0..1024")
+    if vel is not None and (p0 is None or dt is None):
+        raise ValueError("vel needs p0 and dt")
+    counts = _counts(n_agents, E, A) if n_agents is not None else np.full(E, A, dtype=np.int64)
+    out = pos.copy()
+    vel_out = None if vel is None else np.array(vel, dtype=np.float32, copy=True)
+    sample, episode = np.zeros((E, K, 4)), np.zeros((E, 3), dtype=np.int32)
+    for e in range(E):
+        n = int(counts[e])
+        x32 = pos[e, :, :n]
+        _, _, cs, _ = collision_statistics_host(x32[None], threshold)
+        before, hit = cs[0, :, 0], cs[0, :, 3]
+        sample[e, :, 0] = sample[e, :, 1] = before
+        is_nan = np.isnan(before)
+        sample[e, is_nan, 3] = REPAIR_NAN
+        cand = np.flatnonzero(~is_nan & (hit > 0)) if n >= 2 else np.zeros(0, dtype=np.int64)
+        if not cand.size:
+            continue
+        x, iters = _repair_iterate(x32[cand].astype(np.float64), float(threshold), float(margin), float(tau), float(step), max_iter, exp)
+        r32 = x.astype(np.float32)
+        _, _, rs, _ = collision_statistics_host(r32[None], threshold)
+        after = rs[0, :, 0]
+        ok = ~np.isnan(after) & (rs[0, :, 3] == 0)
+        sample[e, cand, 2] = iters
+        sample[e, cand, 3] = np.where(ok, REPAIR_REPAIRED, REPAIR_REVERTED)
+        sample[e, cand[ok], 1] = after[ok]
+        out[e, cand[ok], :n] = r32[ok]
+        if vel_out is not None:
+            r = r32[ok].astype(np.float64)
+            prev = np.concatenate([np.broadcast_to(np.asarray(p0, dtype=np.float32)[e, :n].astype(np.float64)[None, :, None], r[:, :, :1].shape),
+                                   r[:, :, :-1]], axis=2)
+            vel_out[e, cand[ok], :n] = ((r - prev) / float(np.float32(dt))).astype(np.float32)
+        episode[e] = (cand.size, int(ok.sum()), int(iters.max()))
+    return out, vel_out, sample, episode
 
 
 def _wall_step_distance(a0, a1, b0, b1):

@@ -31,7 +31,8 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
            flexibility: float = 0.0, ret_traj: bool = False, sampling: str = "ddpm", step: int = 100,
            precision: str = "f32", _integrate=None, seed: Optional[int] = None, with_constraints: bool = False,
            collision_threshold: float = 0.2, max_rounds: int = 3, static_obstacles=None,
-           wall_radius: Optional[float] = None) -> Tuple[np.ndarray, int, int, int, int]:
+           wall_radius: Optional[float] = None, constraint_type: Optional[str] = None,
+           repair_options: Optional[dict] = None) -> Tuple[np.ndarray, int, int, int, int]:
     """-> (vel [sample, B, num_points, 2] float32, number_of_steps, 0, 0, 0)   (diffusion.py:603-613).
     ``_integrate`` = (p0 [B, 2], dt): used by ``generate`` - the same call also integrates on the device (integrate_kernel) and
     the first element of the result is the positions instead.
@@ -42,8 +43,27 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     ``bestof=True``, ``sampling="ddim"`` and positions (``_integrate``: ``generate`` passes it); ``ValueError`` otherwise.
     ``static_obstacles=`` [L, 2, 2] or [L, 4] with ``wall_radius=`` (with ``with_constraints=True`` only; no default radius): a sample in
     which an agent's path, the step from p0 included, comes closer than ``wall_radius`` to a wall is redrawn too; the five returned
-    values keep their meaning ("with collisions": not acceptable for either cause)."""
-    from .forecaster import wall_arguments
+    values keep their meaning ("with collisions": not acceptable for either cause).
+    ``constraint_type="opt_softplus"`` (with ``with_constraints=True``; the reference's name for its second mechanism): collision repair
+    INSTEAD of redraws (``JmidEngine.repair_collisions``, every sample an episode with K = 1) - the samples are drawn exactly as without
+    constraints, on either RNG contract and under either sampler, and a sample in which two agents come closer than
+    ``collision_threshold`` is pushed apart until the predicate holds or comes back as it was.  Needs positions only; the last three
+    values are (the largest iteration count, samples with collisions, samples repaired).  ``repair_options`` = {margin, tau, step,
+    max_iter}.  Not with ``static_obstacles=``: walls are not in the objective."""
+    from .forecaster import repair_arguments, wall_arguments
+    fix = repair_arguments(constraint_type, repair_options, static_obstacles)
+    if fix is not None:
+        if not with_constraints:
+            raise ValueError("constraint_type needs with_constraints=True")
+        if _integrate is None:
+            raise ValueError("with_constraints=True needs positions (generate, or _integrate)")
+        pos, number_of_steps, *_ = _sample(engine, num_points, context, sample, bestof, point_dim, flexibility, ret_traj, sampling, step,
+                                           precision, _integrate, seed)      # (this function: its own name is taken by an argument)
+        B = int(pos.shape[1])
+        out, _, _, episode = engine.repair_collisions(np.ascontiguousarray(pos, dtype=np.float32).reshape(sample, 1, B, num_points, 2),
+                                                      threshold=collision_threshold, **fix)
+        return (out.reshape(sample, B, num_points, 2), number_of_steps, int(episode[:, 2].max()), int(episode[:, 0].sum()),
+                int(episode[:, 1].sum()))
     walls = wall_arguments(static_obstacles, wall_radius, 1 if with_constraints else 0)
     if with_constraints:
         missing = [w for w, ok in (("seed=", seed is not None), ("bestof=True", bool(bestof)), ('sampling="ddim"', sampling == "ddim"),
@@ -98,19 +118,24 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     return vel.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
 
 
+_sample = sample
+
+
 def generate(engine: JmidEngine, context, p0, dt: float, num_points: int, sample_n: int, bestof: bool,
              flexibility: float = 0.0, sampling: str = "ddpm", step: int = 100, precision: str = "f32", seed: Optional[int] = None,
              with_constraints: bool = False, collision_threshold: float = 0.2, max_rounds: int = 3, static_obstacles=None,
-             wall_radius: Optional[float] = None):
+             wall_radius: Optional[float] = None, constraint_type: Optional[str] = None, repair_options: Optional[dict] = None):
     """Tail of ``AutoEncoder.generate``: ``sample`` + ``SingleIntegrator.integrate_samples``
     (``single_integrator.py:290-321``): pos = cumsum(vel, T) * dt + p0[b].  ``context`` [B, ctx] is the encoder
     output (``JmidEngine.encode``), ``p0`` [B, 2] the current positions.  -> (pos [sample, B, T, 2], steps, 0, 0, 0); with
     ``with_constraints=True`` (see ``sample``) the zeros are (num_iter, samples with collisions, samples fixed); ``static_obstacles`` /
-    ``wall_radius`` as there."""
+    ``wall_radius`` as there; with ``constraint_type="opt_softplus"`` they are (the largest iteration count, samples with collisions,
+    samples repaired) of the collision repair."""
     pos, nsteps, a, b, c = sample(engine, num_points, context, sample_n, bestof, flexibility=flexibility,
                                   sampling=sampling, step=step, precision=precision, _integrate=(p0, dt), seed=seed,
                                   with_constraints=with_constraints, collision_threshold=collision_threshold, max_rounds=max_rounds,
-                                  static_obstacles=static_obstacles, wall_radius=wall_radius)
+                                  static_obstacles=static_obstacles, wall_radius=wall_radius, constraint_type=constraint_type,
+                                  repair_options=repair_options)
     return np.asarray(pos, dtype=np.float32), nsteps, a, b, c
 
 

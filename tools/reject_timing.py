@@ -9,7 +9,8 @@ all three encode, denoise and, at k < K, rank on the device from the resident po
 Every figure is the median over the measured calls after warm-up; the three variants see the same frames in the same order and are
 interleaved call by call, so clock and thermal drift hit them alike.  Run on the GPU box:
     python tools/reject_timing.py [--precision f16mx] [--calls 40] [--episodes 4]
---rule RULE measures the wall predicate instead (section 33), --padded the one-loop form on mixed-count batches (section 34)."""
+--rule RULE measures the wall predicate instead (section 33), --padded the one-loop form on mixed-count batches (section 34), --repair
+collision repair against the redraw loop (section 35)."""
 import argparse
 import json
 import os
@@ -155,6 +156,61 @@ def padded_main(args, weights):
     return out
 
 
+def repair_main(args, weights):
+    """--repair: what collision repair costs per ``predict_ret_best()`` against the redraw loop (docs/NOTEBOOK.md section 35), on the frames
+    of the default mode.  Three forecasters in ONE process on the same frames, seeds and draw numbers, alternating call by call:
+      (a) the staged route without a flag          (b) collision_free_rounds=3          (c) constraint_type="opt_softplus" alone
+    (b) and (c) at ``--threshold``.  Next to the medians and their p10 - p90: what (b) fixed of what collided, and the share of the samples
+    that (c) repaired and reverted, with its largest iteration count.  No gate: (c) is read against (a) and (b) of the same run."""
+    out = {"threshold": args.threshold}
+    for point, (N, K, k, H, step) in POINTS.items():
+        sim = EP.simulate_circle_crossing(args.episodes, N, 6 + args.warmup + args.calls, seed=11)
+        with tempfile.TemporaryDirectory() as td:
+            env, yp = write_configs(td, joint=True, ctx_dim=256, N=N, K=K, k_ret=k, H=H, step=step, time_step=0.25)
+            common = dict(weights=weights, precision=args.precision, self_check=False, rng_compat="device", seed=7, collision_threshold=args.threshold)
+            variants = {"a_staged": Staged(env, yp, **common),
+                        "b_rounds_3": HumanTrajectoryForecasterSim(env, yp, collision_free_rounds=3, **common),
+                        "c_opt_softplus": HumanTrajectoryForecasterSim(env, yp, constraint_type="opt_softplus", **common)}
+        ms = {name: [] for name in variants}
+        redraw, fix, most = np.zeros(2, dtype=np.int64), np.zeros(3, dtype=np.int64), 0
+        for e in range(args.episodes):
+            for f in variants.values():
+                f.prev_states, f.prev_robot_states = [[] for _ in range(N)], []
+            for i in range(6 + args.warmup + args.calls):
+                for f in variants.values():
+                    f.update_state_hists(St(sim["robot_xy"][e, i]), [St(p) for p in sim["human_xy"][e, i]], float(sim["stamps"][i]))
+                if i < 5:
+                    continue
+                order = list(variants.items())
+                order = order[i % 3:] + order[:i % 3]                       # alternate who goes first
+                for name, f in order:
+                    t0 = time.perf_counter()
+                    f.predict_ret_best()
+                    dt = 1e3 * (time.perf_counter() - t0)
+                    if i < 5 + args.warmup:
+                        continue
+                    ms[name].append(dt)
+                    if name.startswith("b"):
+                        redraw += np.array(f.rejection[1:3])
+                    if name.startswith("c"):
+                        fix += np.array(f.repair[:3])
+                        most = max(most, f.repair[3])
+        n = len(ms["a_staged"])
+        res = {name: {"median_ms": round(float(np.median(v)), 3), "p10_ms": round(float(np.percentile(v, 10)), 3),
+                      "p90_ms": round(float(np.percentile(v, 90)), 3)} for name, v in ms.items()}
+        res["calls"] = n
+        res["b_minus_a_ms"] = round(res["b_rounds_3"]["median_ms"] - res["a_staged"]["median_ms"], 3)
+        res["c_minus_a_ms"] = round(res["c_opt_softplus"]["median_ms"] - res["a_staged"]["median_ms"], 3)
+        res["b"] = {"samples_colliding": int(redraw[0]), "samples_fixed": int(redraw[1]), "share_colliding": round(float(redraw[0]) / (n * K), 5)}
+        res["c"] = {"samples_colliding": int(fix[0]), "share_repaired": round(float(fix[1]) / (n * K), 5),
+                    "share_reverted": round(float(fix[2]) / (n * K), 5), "max_iterations": int(most)}
+        res["erange_fallbacks"] = sum(f.erange_fallbacks for f in variants.values())
+        res["workload"] = f"N={N}, K={K} -> {k}, H={H}, {step} steps, {args.precision}, ORCA circle crossing, {args.episodes} episodes, threshold {args.threshold}"
+        out[point] = res
+        print(point, json.dumps(res), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16mx")
@@ -164,13 +220,14 @@ def main():
     ap.add_argument("--rule", default=None, help="a hallway rule of crowd_env (hallway_static, rectangle, ...): measure the wall predicate instead")
     ap.add_argument("--radius", type=float, default=0.3, help="with --rule: the wall radius in metres")
     ap.add_argument("--padded", action="store_true", help="predict_batch on mixed-count scenes: one loop per count against collision_free_padded")
-    ap.add_argument("--threshold", type=float, default=0.2, help="with --padded: the collision threshold in metres")
+    ap.add_argument("--repair", action="store_true", help="collision repair (constraint_type='opt_softplus') against collision_free_rounds=3 and no flag")
+    ap.add_argument("--threshold", type=float, default=0.2, help="with --padded / --repair: the collision threshold in metres")
     args = ap.parse_args()
     weights = JMIDWeights.from_seed(NetDims(ctx_dim=256), 5)
-    if args.rule or args.padded:
+    if args.rule or args.padded or args.repair:
         if args.padded and "--episodes" not in sys.argv:
             args.episodes = 8
-        out = padded_main(args, weights) if args.padded else walls_main(args, weights)
+        out = repair_main(args, weights) if args.repair else padded_main(args, weights) if args.padded else walls_main(args, weights)
         try:
             import bench
             out["sustained_mfma"] = bench.sustained_mfma_tflops()
