@@ -960,9 +960,41 @@ int jmid_dbg_qkv0(jmid_handle_t h, int E, int A, int K, int T, const float* x, c
 /* The tail of one denoise step alone (concat3 -> concat4 -> output layer) in a split-fp16 mode: X [M, d_model] fp32 stands for the
  * last LayerNorm's output and is split into the planes the mode's concat3 reads (X_hi; X_hi + X_lo in JMID_PREC_F16X3), hyp and step
  * as for jmid_dbg_qkv0; e [M, 2] receives e_theta.  The tail runs as a step of a one-chunk call runs it: as one 2 x d_model map per
- * (episode, agent) row from a one-step table, or as the two GEMMs + the output kernel with jmid_set_tuning "tail_fold" = 1. */
+ * (episode, agent) row from a one-step table, or as the two GEMMs + the output kernel with jmid_set_tuning "tail_fold" = 1.
+ * JMID_PREC_F32: the two fp32 GEMMs + the output kernel on X itself. */
 int jmid_dbg_tail(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* hyp, int hyp_width, int step, int precision,
                   float* e, float* thyp_row);
+/* The seam between e_theta of step-table entry `step` and the residual stream of entry `next_step`, as a step of a one-chunk call of
+ * that shape on an idle handle runs it after its last layer (all four precisions, JMID and iMID; the launches are that plan's: the
+ * folded tail or the two tail GEMMs + the output kernel by jmid_set_tuning "tail_fold", one wave per token or per trajectory piece by
+ * "out_traj"; DDIM or DDPM as the handle's step table is): the tail on X [M, d_model] fp32 (split as jmid_dbg_tail splits it), the
+ * sampler update of x [M, 2] with z [M, 2] (or NULL: no draw; a DDPM entry that takes none ignores it) and - next_step >= 0 - the
+ * embedding of the updated x with the time row of `next_step`; next_step = -1: the loop's last step, no embedding.  The hyper rows:
+ * exactly one of ctx [E A, ctx_dim] (the call's own hyper GEMM makes them) and hyp [E A, hyp_width] (given, as for jmid_dbg_qkv0).
+ * embed_only != 0: the embedding kernel of a call's first step alone on x at entry `step` (X, z and next_step are not read).
+ *   x_next [M, 2]     x after the update (embed_only: x)
+ *   hi, lo [M, d_model] each: the embedding's buffers after the launch as the mode stores them, as fp32 - blocked planes un-blocked,
+ *                     the bf8 byte plane decoded; JMID_PREC_F32: hi = X, lo = 0.  Before the launch every one of those buffers that is
+ *                     not an input of the tail is filled with the byte JMID_DBG_SEAM_FILL, the others hold X as split: with
+ *                     next_step = -1 they come back as that (fp16 planes of that byte: 0x3c3c = 1.05859375, a bf8 byte: 1.0)
+ *   hyp_out (or NULL) [E A, hyper width]: the hyper rows the kernels read
+ *   thyp_rows (or NULL) [2, hyper width]: the time rows of `step` and of `next_step` (next_step = -1: of `step` again)
+ *   coef (or NULL) [JMID_DBG_SEAM_COEF_WORDS]: the handle's coefficients of `step`: c_e, c_x, n_x, n_e (DDIM), c0, c1, sigma, and 1.0
+ *                     where the DDPM entry takes a draw
+ *   plan [JMID_DBG_SEAM_PLAN_WORDS]: the kernel that ran (JMID_DBG_SEAM_*), its tokens per wave (out_tpw; 0 = one wave per token), the
+ *                     representation (0 fp32, 1 fp16 hi + lo, 2 fp16 hi + bf8 lo), DDPM, embedded for next_step, folded tail, range flag.
+ * Returns as a denoise call does when the flag is set. */
+#define JMID_DBG_SEAM_FILL 0x3c
+#define JMID_DBG_SEAM_OUT 0        /* out_ddim_kernel */
+#define JMID_DBG_SEAM_OUT_TRAJ 1   /* out_ddim_traj_kernel */
+#define JMID_DBG_SEAM_FOLD 2       /* tail_fold_kernel */
+#define JMID_DBG_SEAM_FOLD_TRAJ 3  /* tail_fold_traj_kernel */
+#define JMID_DBG_SEAM_EMBED 4      /* embed_kernel */
+#define JMID_DBG_SEAM_COEF_WORDS 8
+#define JMID_DBG_SEAM_PLAN_WORDS 7
+int jmid_dbg_seam(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* x, const float* z, const float* ctx, const float* hyp,
+                  int hyp_width, int step, int next_step, int precision, int embed_only, float* x_next, float* hi, float* lo, float* hyp_out,
+                  float* thyp_rows, float* coef, int* plan);
 /* Encoder layer `layer` of one net evaluation, launch for launch as a step of a one-chunk call of that shape on an idle handle runs it
  * (all four precisions, JMID and iMID; the split-KV factor and the launch plans are that call's), with every stage copied out in
  * between.  X [M, d_model] fp32 (M = E K A T tokens) is split into the operand planes the mode's layer reads (fp16 hi + lo; hi + the

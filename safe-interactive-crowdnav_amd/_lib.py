@@ -146,6 +146,7 @@ DIAG_SIGNATURES = {
     "jmid_dbg_chain_layout": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int64)] * 3),
     "jmid_dbg_qkv0": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "jmid_dbg_tail": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "jmid_dbg_seam": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.POINTER(C.c_int)]),
     "jmid_dbg_layer": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "jmid_dbg_noise_words": (C.c_int, [Handle, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

@@ -439,7 +439,10 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
              float* out, float* thyp_row);      // jmid_dbg_qkv0 (tail = false) / jmid_dbg_tail: -DJMID_DIAGNOSTICS only
 int dbg_layer(jmid_ctx* h, int E, int A, int K, int T, int layer, int precision, const float* X, const int32_t* n_agents, int last,
               float* hi, float* lo, int* plan);      // jmid_dbg_layer: -DJMID_DIAGNOSTICS only
-int flagged_call(jmid_ctx* h, int flag);      // the status of a call whose range flag came back set (JMID_ETIMEOUT / JMID_ERANGE)
+int dbg_seam(jmid_ctx* h, int E, int A, int K, int T, const float* X, const float* x, const float* z, const float* ctx, const float* hyp,
+             int hyp_width, int step, int next_step, int precision, int embed_only, float* x_next, float* hi, float* lo, float* hyp_out,
+             float* thyp_rows, float* coef, int* plan);      // jmid_dbg_seam: -DJMID_DIAGNOSTICS only
+int flagged_call(jmid_ctx* h, int flag);     // the status of a call whose range flag came back set (JMID_ETIMEOUT / JMID_ERANGE)
 int launch_episode_metrics(jmid_ctx* h, const float* pos, const float* gt, float* out, int E, int K, int A, int T);
 // jmid_abi.hip
 size_t chain_io(const jmid_ctx* h, const ChainCall& c, char* base, ChainIo* out, bool pinned);

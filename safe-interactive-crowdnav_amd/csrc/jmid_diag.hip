@@ -317,6 +317,14 @@ int jmid_dbg_tail(jmid_handle_t h, int E, int A, int K, int T, const float* X, c
     return h ? dbg_step(h, true, E, A, K, T, X, hyp, hyp_width, step, precision, e, thyp_row) : JMID_EINVAL;
 }
 
+int jmid_dbg_seam(jmid_handle_t h, int E, int A, int K, int T, const float* X, const float* x, const float* z, const float* ctx, const float* hyp,
+                  int hyp_width, int step, int next_step, int precision, int embed_only, float* x_next, float* hi, float* lo, float* hyp_out,
+                  float* thyp_rows, float* coef, int* plan) {
+    return h ? dbg_seam(h, E, A, K, T, X, x, z, ctx, hyp, hyp_width, step, next_step, precision, embed_only, x_next, hi, lo, hyp_out, thyp_rows,
+                        coef, plan)
+             : JMID_EINVAL;
+}
+
 int jmid_dbg_layer(jmid_handle_t h, int E, int A, int K, int T, int layer, int precision, const float* X, const int32_t* n_agents, int last,
                    float* hi, float* lo, int* plan) {
     return h ? dbg_layer(h, E, A, K, T, layer, precision, X, n_agents, last, hi, lo, plan) : JMID_EINVAL;

@@ -1067,10 +1067,25 @@ int flagged_call(jmid_ctx* h, int flag) {
 }
 
 #ifdef JMID_DIAGNOSTICS
+// The tail of a step in JMID_PREC_F32 on ln.X, launch for launch as net_step runs it: concat3, concat4 (ConcatSquash epilogues), then
+// the output stage
+int f32_tail(jmid_ctx* h, const StepPlan& p, const Lane& ln, int step_idx, float* x_chunk, const float* hyp_chunk, float* e_out,
+             const float* z_chunk, int next_step) {
+    const int M = p.M, d = h->d;
+    const float* thyp = p.thyp(step_idx);
+    GemmArgs g = gemm_args(p.rm, M, ln.X, h->wt.concat3, ln.Y3, h->dmid, d);
+    g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.goff = h->hl.g3; g.boff = h->hl.b3;
+    if (int rc = run_gemm<EPI_CSL>(h, ln.stream, KC_GEMM_TAIL, g)) return rc;
+    g = gemm_args(p.rm, M, ln.Y3, h->wt.concat4, ln.Y4, h->dlow, h->dmid);
+    g.hyp = hyp_chunk; g.thyp = thyp; g.hyp_ld = h->hl.total; g.goff = h->hl.g4; g.boff = h->hl.b4;
+    if (int rc = run_gemm<EPI_CSL>(h, ln.stream, KC_GEMM_TAIL, g)) return rc;
+    return output_stage(h, p, ln, step_idx, x_chunk, hyp_chunk, e_out, z_chunk, next_step);
+}
+
 // jmid_dbg_qkv0 and jmid_dbg_tail: one piece of step `step` as a step of a one-chunk call on an idle handle runs it, on host buffers.
 // tail = false: the embedding of x [M, 2] and layer 0's Q / K / V^T planes (the "qkv0" knob decides how), read back as fp32 [M, 3 d].
 // tail = true: the tail alone on X [M, d] (fp32, split here into the planes the mode's concat3 reads: X_hi, and X_lo in F16X3) - folded,
-// or the two GEMMs + the output kernel with "tail_fold" = 1 -> e [M, 2].
+// or the two GEMMs + the output kernel with "tail_fold" = 1 -> e [M, 2]; JMID_PREC_F32: the fp32 GEMMs + the output kernel on X itself.
 int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in, const float* hyp, int hyp_width, int step, int precision,
              float* out, float* thyp_row) {
     const std::string who = tail ? "jmid_dbg_tail" : "jmid_dbg_qkv0";
@@ -1078,8 +1093,8 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
     if (int rc = check_ready(h)) return rc;
     if (!in || !hyp || !out || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen) return fail(h, JMID_EINVAL, who + ": bad arguments");
     if (hyp_width != h->hl.total) return fail(h, JMID_EINVAL, who + ": hyp rows must be " + std::to_string(h->hl.total) + " wide");
-    if (!call_mode(precision, &mode) || !mode.split || (!tail && h->net_kind != JMID_NET_JMID))
-        return fail(h, JMID_EINVAL, who + (tail ? ": a split-fp16 mode only" : ": JMID in a split-fp16 mode only"));
+    if (!call_mode(precision, &mode) || (!tail && (!mode.split || h->net_kind != JMID_NET_JMID)))
+        return fail(h, JMID_EINVAL, who + (tail ? ": bad precision" : ": JMID in a split-fp16 mode only"));
     if (step < 0 || step >= (int)h->beta.size()) return fail(h, JMID_EINVAL, who + ": step outside the step table");
     HIPCHK(h, hipSetDevice(h->device));
     h->last_pos = nullptr;
@@ -1108,7 +1123,10 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
     }
     HIPCHK(h, hipMemcpyAsync(in_d, in, M * in_w * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(hyp_d, hyp, EA * h->hl.total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (tail) {
+    if (tail && !mode.split) {
+        HIPCHK(h, hipMemcpyAsync(ln.X, in_d, M * d * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        if (int rc = f32_tail(h, p, ln, step, nullptr, hyp_d, out_d, nullptr, -1)) return rc;
+    } else if (tail) {
         // (the planes' padding rows up to the next multiple of 128 only ever feed discarded output rows of the GEMM path, but must be finite)
         HIPCHK(h, hipMemsetAsync(ln.Xh, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
         HIPCHK(h, hipMemsetAsync(ln.Xl, 0, blk_plane_elems(M, d) * sizeof(half_t), h->stream));
@@ -1130,6 +1148,120 @@ int dbg_step(jmid_ctx* h, bool tail, int E, int A, int K, int T, const float* in
     if (thyp_row)
         HIPCHK(h, hipMemcpyAsync(thyp_row, p.thyp(step), h->hl.total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return flag ? flagged_call(h, flag) : 0;
+}
+
+// jmid_dbg_seam: what net_step runs after the last layer of step `step` - the tail, the sampler update of x and, with next_step >= 0,
+// the embedding of the updated x for step `next_step` - as the plan of a one-chunk call of that shape on an idle handle says, in the
+// launches that plan says (net_tail in the split-fp16 modes; the two EPI_CSL GEMMs + output_stage in F32), all four modes, JMID and
+// iMID, DDIM or DDPM as the handle's step table is.  X [M, d] is split as dbg_step splits it.  The hyper rows come from the call's own
+// hyper GEMM on ctx (fill_workspace's launch), or are given.  The embedding's buffers are read back as two fp32 arrays after the
+// launch; before it, every one of them that is not an input of the tail holds JMID_DBG_SEAM_FILL bytes (the others hold X as split).
+// embed_only: run_embed alone on x at `step` (a call's first step), read back the same way.
+int dbg_seam(jmid_ctx* h, int E, int A, int K, int T, const float* X, const float* x, const float* z, const float* ctx, const float* hyp,
+             int hyp_width, int step, int next_step, int precision, int embed_only, float* x_next, float* hi, float* lo, float* hyp_out,
+             float* thyp_rows, float* coef, int* plan) {
+    const std::string who = "jmid_dbg_seam";
+    CallMode mode;
+    if (int rc = check_ready(h)) return rc;
+    if ((!X && !embed_only) || !x || !x_next || !hi || !lo || !plan || (!ctx == !hyp) || E <= 0 || A <= 0 || K <= 0 || T <= 0 || T > kPeMaxLen)
+        return fail(h, JMID_EINVAL, who + ": bad arguments");
+    if (hyp && hyp_width != h->hl.total) return fail(h, JMID_EINVAL, who + ": hyp rows must be " + std::to_string(h->hl.total) + " wide");
+    if (!call_mode(precision, &mode)) return fail(h, JMID_EINVAL, who + ": bad precision");
+    if (mode.split && !h->weights_in_half_range) return fail(h, JMID_ERANGE, who + ": a weight exceeds the fp16 range");
+    const int n_steps = (int)h->beta.size();
+    if (step < 0 || step >= n_steps || next_step < -1 || next_step >= n_steps) return fail(h, JMID_EINVAL, who + ": step outside the step table");
+    HIPCHK(h, hipSetDevice(h->device));
+    h->last_pos = nullptr;
+    const size_t M = (size_t)E * K * A * T, EA = (size_t)E * A;
+    const int d = h->d, width = h->hl.total;
+    const StepPlan p = plan_step(h, E, A, K, T, mode, CallFacts{});      // (an idle handle: nothing else in flight, one launch, the table of one step)
+    const size_t tail_rows = !embed_only && p.tail_fold ? EA : 0;
+    float *X_d, *x_d, *z_d, *ctx_d, *hyp_d, *hi_d, *lo_d;
+    const auto io = [&](char* base) {      // base null: the size only
+        Carver c(base);
+        X_d = c.take(M * d);
+        x_d = c.take(M * 2);
+        z_d = c.take(M * 2);
+        ctx_d = c.take(EA * h->ctx_dim);
+        hyp_d = c.take(EA * width);
+        hi_d = c.take(M * d);
+        lo_d = c.take(M * d);
+        return c.off;
+    };
+    const size_t io_off = io(nullptr);
+    if (int rc = ensure_arena(h, io_off + step_ws_floats(h, M, mode, p.sg, 1, nullptr, nullptr, 0, tail_rows), who.c_str())) return rc;
+    io(h->arena.p);
+    Lane ln{};
+    ln.stream = h->stream;
+    step_ws_floats(h, M, mode, p.sg, 1, &ln, h->arena.p + io_off, 0, tail_rows);
+    hipStream_t st = h->stream;
+    const size_t plane_bytes = blk_plane_elems(M, d) * sizeof(half_t);
+    if (mode.split) HIPCHK(h, hipMemsetAsync(h->range_flag, 0, sizeof(int), st));
+    HIPCHK(h, hipMemcpyAsync(x_d, x, M * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+    if (z) HIPCHK(h, hipMemcpyAsync(z_d, z, M * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+    if (ctx) {      // the ctx part of the four hyper nets as a call makes it (fill_workspace)
+        HIPCHK(h, hipMemcpyAsync(ctx_d, ctx, EA * h->ctx_dim * sizeof(float), hipMemcpyHostToDevice, st));
+        GemmArgs g{};
+        g.A = ctx_d; g.lda = h->ctx_dim; g.W = h->Whyp; g.ldw = h->ctx_dim; g.bias = h->bhyp; g.C = hyp_d;
+        g.ldc = width; g.M = (int)EA; g.N = width; g.K = h->ctx_dim;
+        if (int rc = run_gemm<EPI_BIAS>(h, st, KC_HYPER, g)) return rc;
+    } else {
+        HIPCHK(h, hipMemcpyAsync(hyp_d, hyp, EA * width * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    int kernel;
+    if (embed_only) {
+        if (mode.split) {
+            HIPCHK(h, hipMemsetAsync(ln.Xh, JMID_DBG_SEAM_FILL, plane_bytes, st));
+            HIPCHK(h, hipMemsetAsync(ln.Xl, JMID_DBG_SEAM_FILL, plane_bytes, st));
+        } else {
+            HIPCHK(h, hipMemsetAsync(ln.X, JMID_DBG_SEAM_FILL, M * d * sizeof(float), st));
+        }
+        if (int rc = run_embed(h, p, ln, x_d, hyp_d, p.thyp(step))) return rc;
+        kernel = JMID_DBG_SEAM_EMBED;
+    } else if (mode.split) {
+        HIPCHK(h, hipMemcpyAsync(X_d, X, M * d * sizeof(float), hipMemcpyHostToDevice, st));
+        // (the planes' padding rows up to the next multiple of 128 only ever feed discarded output rows of the GEMM path, but must be finite)
+        HIPCHK(h, hipMemsetAsync(ln.Xh, 0, plane_bytes, st));
+        HIPCHK(h, hipMemsetAsync(ln.Xl, mode.x2 ? JMID_DBG_SEAM_FILL : 0, plane_bytes, st));      // F16X2 / F16MX: the tail reads X_hi only
+        hipLaunchKernelGGL(tail_split_rows_kernel, dim3(512), dim3(256), 0, st, X_d, ln.Xh, mode.x2 ? nullptr : ln.Xl, (int)M, d);
+        HIPCHK(h, hipGetLastError());
+        if (int rc = net_tail(h, p, ln, step, x_d, hyp_d, nullptr, z ? z_d : nullptr, next_step)) return rc;
+        kernel = p.tail_fold ? (p.out_tpw ? JMID_DBG_SEAM_FOLD_TRAJ : JMID_DBG_SEAM_FOLD) : (p.out_tpw ? JMID_DBG_SEAM_OUT_TRAJ : JMID_DBG_SEAM_OUT);
+    } else {
+        HIPCHK(h, hipMemcpyAsync(ln.X, X, M * d * sizeof(float), hipMemcpyHostToDevice, st));
+        if (int rc = f32_tail(h, p, ln, step, x_d, hyp_d, nullptr, z ? z_d : nullptr, next_step)) return rc;
+        kernel = p.out_tpw ? JMID_DBG_SEAM_OUT_TRAJ : JMID_DBG_SEAM_OUT;
+    }
+    // the embedding's buffers as the mode stores them -> hi / lo
+    if (!mode.split) {
+        HIPCHK(h, hipMemcpyAsync(hi_d, ln.X, M * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemsetAsync(lo_d, 0, M * d * sizeof(float), st));
+    } else {
+        if (p.mxv2) hipLaunchKernelGGL(merge_planes_lo8_kernel, dim3(512), dim3(256), 0, st, ln.Xh, reinterpret_cast<unsigned char*>(ln.Xl), hi_d, (int)M, lo_d);
+        else hipLaunchKernelGGL(merge_planes_kernel, dim3(512), dim3(256), 0, st, ln.Xh, ln.Xl, hi_d, (int)M, d, lo_d);
+        HIPCHK(h, hipGetLastError());
+    }
+    int flag = 0;
+    if (mode.split) HIPCHK(h, hipMemcpyAsync(&flag, h->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(x_next, x_d, M * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hi, hi_d, M * d * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(lo, lo_d, M * d * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (hyp_out) HIPCHK(h, hipMemcpyAsync(hyp_out, hyp_d, EA * width * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (thyp_rows) {
+        HIPCHK(h, hipMemcpyAsync(thyp_rows, p.thyp(step), width * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(thyp_rows + width, p.thyp(next_step >= 0 ? next_step : step), width * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (coef) {
+        const float v[JMID_DBG_SEAM_COEF_WORDS] = {h->c_e[step], h->c_x[step], h->n_x[step], h->n_e[step],
+                                                   h->ddpm ? h->p_c0[step] : 0.f, h->ddpm ? h->p_c1[step] : 0.f, h->ddpm ? h->p_sigma[step] : 0.f,
+                                                   h->ddpm && h->p_noise[step] ? 1.f : 0.f};
+        for (int i = 0; i < JMID_DBG_SEAM_COEF_WORDS; ++i) coef[i] = v[i];
+    }
+    const int words[JMID_DBG_SEAM_PLAN_WORDS] = {kernel, p.out_tpw, !mode.split ? 0 : p.mxv2 ? 2 : 1, h->ddpm ? 1 : 0,
+                                                 !embed_only && next_step >= 0, p.tail_fold, flag};
+    for (int i = 0; i < JMID_DBG_SEAM_PLAN_WORDS; ++i) plan[i] = words[i];
     return flag ? flagged_call(h, flag) : 0;
 }
 

@@ -1068,7 +1068,7 @@ class JmidEngine:
     def dbg_tail(self, X: np.ndarray, hyp: np.ndarray, step: int, dims: Tuple[int, int, int, int], precision: str = "f16mx"):
         """The tail of one denoise step alone (``jmid_dbg_tail``; the "tail_fold" knob decides how it runs): X [M, d] stands for the
         last LayerNorm's output, hyp [E * A, hyper width] -> (e [M, 2] float32, the time part of the hyper nets at step-table entry
-        ``step`` [hyper width])."""
+        ``step`` [hyper width]).  "f32": the two fp32 GEMMs + the output kernel."""
         E, A, K, T = (int(v) for v in dims)
         X = np.ascontiguousarray(X, np.float32)
         hyp = np.ascontiguousarray(hyp, np.float32)
@@ -1081,6 +1081,54 @@ class JmidEngine:
         self._check(self._lib.jmid_dbg_tail(self._h, E, A, K, T, C.c_void_p(X.ctypes.data), C.c_void_p(hyp.ctypes.data), width, int(step),
                                             _lib.PRECISIONS[precision], C.c_void_p(out.ctypes.data), C.c_void_p(thyp.ctypes.data)))
         return out, thyp
+
+    SEAM_PLAN_FIELDS = ("kernel", "out_tpw", "rep", "ddpm", "embedded", "tail_fold", "range_flag")
+    SEAM_KERNELS = ("out_ddim", "out_ddim_traj", "tail_fold", "tail_fold_traj", "embed")
+    SEAM_REPS = ("f32", "pair", "hi_bf8")
+    SEAM_COEF_FIELDS = ("c_e", "c_x", "n_x", "n_e", "c0", "c1", "sigma", "noise")
+
+    def dbg_seam(self, X, x: np.ndarray, dims: Tuple[int, int, int, int], step: int, next_step: int = -1, precision: str = "f16mx",
+                 z=None, ctx=None, hyp=None, embed_only: bool = False):
+        """The seam between e_theta of step-table entry ``step`` and the residual stream of entry ``next_step`` as a step of a
+        one-chunk call of shape ``dims`` = (E, A, K, T) runs it (``jmid_dbg_seam``; the "tail_fold" and "out_traj" knobs and
+        ``set_step``'s sampling decide how): the tail on X [M, d_model], the sampler update of x [M, 2] with the draw z [M, 2] (or None),
+        the embedding of the updated x for ``next_step`` (-1: the loop's last step, none).  Exactly one of ctx [E A, ctx_dim] (the
+        call's own hyper GEMM) and hyp [E A, hyper width].  ``embed_only``: the first step's embedding kernel alone on x at ``step``.
+        Returns a dict: x_next [M, 2]; hi, lo [M, d_model] (the embedding's buffers as the mode stores them, as float32; before the
+        launch they hold X as split where the tail reads them, else the fill byte 0x3c: 1.05859375 in an fp16 plane, 1.0 in the bf8
+        one); hyp [E A, width] as the kernels read it; thyp [2, width], the time rows of ``step`` and ``next_step``; coef, the
+        handle's float32 coefficients of ``step`` by name; plan by ``SEAM_PLAN_FIELDS`` (kernel and rep as names)."""
+        E, A, K, T = (int(v) for v in dims)
+        M, d, width = E * K * A * T, self.dims.d_model, self.hyper_width()
+        x = np.ascontiguousarray(x, np.float32)
+        if x.shape != (M, 2):
+            raise ValueError(f"expected x [{M}, 2]")
+        if (ctx is None) == (hyp is None):
+            raise ValueError("exactly one of ctx and hyp")
+
+        def arr(a, shape, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32)
+            if a.shape != shape:
+                raise ValueError(f"expected {what} {list(shape)}")
+            return a
+        X = arr(X, (M, d), "X")
+        if X is None and not embed_only:
+            raise ValueError("X is needed unless embed_only")
+        z = arr(z, (M, 2), "z")
+        ctx = arr(ctx, (E * A, self.dims.ctx_dim), "ctx")
+        hyp = arr(hyp, (E * A, width), "hyp")
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        x_next, hi, lo = np.empty((M, 2), np.float32), np.empty((M, d), np.float32), np.empty((M, d), np.float32)
+        hyp_out, thyp, coef = np.empty((E * A, width), np.float32), np.empty((2, width), np.float32), np.empty((len(self.SEAM_COEF_FIELDS),), np.float32)
+        plan = (C.c_int * len(self.SEAM_PLAN_FIELDS))()
+        self._check(self._lib.jmid_dbg_seam(self._h, E, A, K, T, ptr(X), ptr(x), ptr(z), ptr(ctx), ptr(hyp), width, int(step), int(next_step),
+                                            _lib.PRECISIONS[precision], int(bool(embed_only)), ptr(x_next), ptr(hi), ptr(lo), ptr(hyp_out),
+                                            ptr(thyp), ptr(coef), plan))
+        plan = dict(zip(self.SEAM_PLAN_FIELDS, (int(v) for v in plan)))
+        plan["kernel"], plan["rep"] = self.SEAM_KERNELS[plan["kernel"]], self.SEAM_REPS[plan["rep"]]
+        return dict(x_next=x_next, hi=hi, lo=lo, hyp=hyp_out, thyp=thyp, coef=dict(zip(self.SEAM_COEF_FIELDS, coef)), plan=plan)
 
     LAYER_PLAN_FIELDS = ("stages", "in_proj_mode", "in_proj_shape", "in_proj_flags", "linear1_mode", "linear1_shape", "linear1_flags",
                          "out_proj_path", "out_proj_ln_rows", "out_proj_gemm_shape", "linear2_path", "linear2_ln_rows", "linear2_gemm_shape",

@@ -1,0 +1,208 @@
+"""The seam between e_theta of denoise step i and the residual stream of step i + 1 on the device (jmid_dbg_seam: the plan's own
+launches) against float64, stage by stage and element by element, under the derived bounds of tests/seam_reference.py: the hyper
+rows a call makes from ctx, the sampler update of x (DDIM, DDPM with and without a draw), the next step's embedding as the mode
+stores it - fp32 X, fp16 hi + lo planes, hi + the bf8 byte plane.  Plus the equalities the kernels' comments promise: the fused
+next embedding is embed_kernel's, per token and per trajectory piece agree, "tail_fold" 0 and 2 agree, no z is z = 0.
+tests/test_seam_bounds_host.py shows on the CPU that these bounds hold for a correct fp32 twin and catch eleven wrong kernels."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import seam_reference as S  # noqa: E402
+from safe_interactive_crowdnav_amd.engine import JmidEngine
+from safe_interactive_crowdnav_amd.schedule import ddim_steps, ddpm_steps
+from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims
+
+FLEX = 0.5                    # DDPM sigma = the mean of the two variances: the entry of t = 1 keeps a sigma > 0 that it must not use
+# sampling, steps of the table, step, next step, with z
+SCENARIOS = [("ddim", 10, 3, 4, False), ("ddim", 10, 9, -1, False), ("ddpm", 100, 40, 41, True), ("ddpm", 100, 99, -1, False)]
+_ENG, _NET = {}, {}
+
+
+def get_engine(ctx_dim, joint=True):
+    key = (ctx_dim, joint)
+    if key not in _ENG:
+        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim), 5)
+        _ENG[key] = (JmidEngine(w, joint=joint), w)
+    return _ENG[key]
+
+
+def net(ctx_dim):
+    """the float64 side of a width, made once: hyper weights, concat1, the positional table"""
+    if ctx_dim not in _NET:
+        _, w = get_engine(ctx_dim)
+        d, dmid, dlow = S.dims_of(ctx_dim)
+        W, b, tw = S.hyper_weights(w.tensors, d, dmid, dlow)
+        g8 = lambda n: w.tensors[n].detach().cpu().numpy().astype(np.float64)
+        _NET[ctx_dim] = dict(W=W, b=b, tw=tw, W1=g8("concat1._layer.weight"), b1=g8("concat1._layer.bias"), pe=S.positional_table(d),
+                             L=S.hyper_layout(d, dmid, dlow))
+    return _NET[ctx_dim]
+
+
+class Worst:
+    """largest |err| / bound per stage"""
+
+    def __init__(self):
+        self.r = {}
+
+    def check(self, stage, dev, ref, bound, what):
+        err = np.abs(np.asarray(dev, np.float64) - ref)
+        assert np.isfinite(np.asarray(dev)).all(), (stage, what)
+        q = float((err / np.maximum(bound, 1e-300)).max())
+        self.r[stage] = max(self.r.get(stage, 0.0), q)
+        bad = err > bound
+        assert not bad.any(), f"{stage} {what}: {int(bad.sum())} elements outside, worst |err| / bound {q:.3f} at {np.argwhere(bad)[0]}"
+
+
+def expected_kernel(split, fold, traj):
+    base = "tail_fold" if (split and fold != 1) else "out_ddim"
+    return base + ("_traj" if traj else "")
+
+
+def run_case(eng, ctx_dim, shape, precision, trajs, out_tpw_of, hyp_direct=False):
+    """Every knob and sampler combination of one (shape, width, mode); returns the worst ratios."""
+    E, A, K, T = shape
+    d, _, _ = S.dims_of(ctx_dim)
+    n, rep, inp = net(ctx_dim), S.rep_of(precision, d), S.seam_inputs(ctx_dim, shape)
+    split = precision != "f32"
+    folds = (0, 1, 2) if split else (0,)
+    X, x, z = inp["X"], inp["x"], inp["z"]
+    src = dict(hyp=inp["hyp"]) if hyp_direct else dict(ctx=inp["ctx"])
+    ea, _ = S.row_of(shape)
+    w = Worst()
+    got = {}
+    try:
+        for kind in ("ddim", "ddpm"):
+            steps = 10 if kind == "ddim" else 100
+            eng.set_step(steps, kind, FLEX if kind == "ddpm" else 0.0)
+            tab = ddim_steps(eng.schedule, steps) if kind == "ddim" else ddpm_steps(eng.schedule, steps, FLEX)
+            for traj in trajs:
+                eng.set_tuning("out_traj", traj)
+                for fold in folds:
+                    eng.set_tuning("tail_fold", fold)
+                    for sc in (s for s in SCENARIOS if s[0] == kind):
+                        _, _, step, nxt, with_z = sc
+                        what = f"{kind} step {step} -> {nxt} out_traj {traj} tail_fold {fold}"
+                        r = eng.dbg_seam(X, x, shape, step, nxt, precision, z=z if with_z else None, **src)
+                        got[sc, traj, fold] = r
+                        plan = r["plan"]
+                        assert plan["kernel"] == expected_kernel(split, fold, out_tpw_of(traj)) and plan["out_tpw"] == out_tpw_of(traj), (what, plan)
+                        assert plan["rep"] == rep and plan["ddpm"] == (kind == "ddpm") and plan["embedded"] == (nxt >= 0) and not plan["range_flag"], (what, plan)
+                        # the handle's coefficients are the schedule's, and its time rows their definition
+                        for k in (("c_e", "c_x", "n_x", "n_e") if kind == "ddim" else ("c0", "c1", "sigma")):
+                            assert r["coef"][k] == getattr(tab[step], k), (what, k)
+                        assert bool(r["coef"]["noise"]) == (kind == "ddpm" and tab[step].noise)
+                        for row, i in ((0, step), (1, nxt if nxt >= 0 else step)):
+                            t_ref, t_tol = S.time_row_check(r["thyp"][row], n["tw"], tab[i].beta)
+                            assert (np.abs(r["thyp"][row] - t_ref) <= t_tol).all(), (what, "time row", i)
+                        # hyper rows
+                        if hyp_direct:
+                            np.testing.assert_array_equal(r["hyp"], inp["hyp"])
+                        else:
+                            w.check("hyper", r["hyp"], *S.hyper_stage(inp["ctx"], n["W"], n["b"]), what)
+                        # the update, on the e the tail alone gives with these knobs
+                        e, _ = eng.dbg_tail(X, r["hyp"], step, shape, precision)
+                        de = S.contraction_term(e, r["hyp"][ea], r["thyp"][0], n["L"], folded=split and fold != 1)
+                        w.check("update", r["x_next"], *S.update_stage(x, z if with_z else None, e, r["coef"], kind == "ddpm", de), what)
+                        if nxt >= 0:
+                            # the embedding, on the device's own x_next and hyper rows and the handle's time row
+                            ref, bound = S.embed_stage(r["x_next"], r["hyp"], r["thyp"][1], n["W1"], n["b1"], n["pe"], shape, rep)
+                            assert np.isfinite(r["hi"]).all() and np.isfinite(r["lo"]).all()
+                            w.check("embed", S.stored(r["hi"], r["lo"]), ref, bound, what)
+                            first = eng.dbg_seam(None, r["x_next"], shape, nxt, -1, precision, hyp=r["hyp"], embed_only=True)
+                            assert first["plan"]["kernel"] == "embed"
+                            np.testing.assert_array_equal(r["hi"], first["hi"], err_msg=what + ": fused embedding against embed_kernel, hi")
+                            np.testing.assert_array_equal(r["lo"], first["lo"], err_msg=what + ": fused embedding against embed_kernel, lo")
+                        else:
+                            hi0, lo0 = S.untouched_planes(X, precision, rep)
+                            np.testing.assert_array_equal(r["hi"], hi0, err_msg=what + ": no next step, the hi plane was written")
+                            np.testing.assert_array_equal(r["lo"], lo0, err_msg=what + ": no next step, the lo plane was written")
+            # ---- no draw is a draw of zeros; an entry that takes no draw does not read one (default knobs of the case)
+            if kind == "ddpm":
+                eng.set_tuning("out_traj", trajs[0])
+                eng.set_tuning("tail_fold", 0)
+                mid, last = SCENARIOS[2], SCENARIOS[3]
+                for zz, base, label in ((None, eng.dbg_seam(X, x, shape, mid[2], mid[3], precision, z=np.zeros_like(z), **src), "no z against z = 0"),
+                                        (z, got[last, trajs[0], 0], "z passed to the entry of t = 1")):
+                    sc = mid if zz is None else last
+                    r = eng.dbg_seam(X, x, shape, sc[2], sc[3], precision, z=zz, **src)
+                    for k in ("x_next", "hi", "lo"):
+                        np.testing.assert_array_equal(r[k], base[k], err_msg=f"{label}: {k}")
+    finally:
+        eng.set_tuning("tail_fold", 0)
+        eng.set_tuning("out_traj", 0)
+        eng.set_step(10, "ddim")
+    # ---- the kernel forms and the table forms give the same bits
+    for sc in SCENARIOS:
+        for fold in folds:
+            for traj in trajs[1:]:
+                for k in ("x_next", "hi", "lo"):
+                    np.testing.assert_array_equal(got[sc, traj, fold][k], got[sc, trajs[0], fold][k], err_msg=f"{sc} tail_fold {fold}: per trajectory against per token, {k}")
+        if split:
+            for traj in trajs:
+                for k in ("x_next", "hi", "lo"):
+                    np.testing.assert_array_equal(got[sc, traj, 2][k], got[sc, traj, 0][k], err_msg=f"{sc} out_traj {traj}: tail_fold 2 against 0, {k}")
+    # ---- the first step's embedding against float64 as well
+    first = eng.dbg_seam(None, x, shape, 0, -1, precision, embed_only=True, **src)
+    np.testing.assert_array_equal(first["x_next"], x)
+    w.check("embed0", S.stored(first["hi"], first["lo"]), *S.embed_stage(x, first["hyp"], first["thyp"][0], n["W1"], n["b1"], n["pe"], shape, rep), "first step")
+    return w.r
+
+
+def report(tag, shape, ctx_dim, precision, worst):
+    print(f"seam {tag}{shape} d={2 * ctx_dim} [{precision}] max |err| / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(worst.items())))
+
+
+@pytest.mark.parametrize("precision", S.MODES)
+@pytest.mark.parametrize("ctx_dim", S.WIDTHS)
+@pytest.mark.parametrize("shape", S.SHAPES)
+def test_seam_stages_are_inside_their_bounds_and_the_bit_promises_hold(shape, ctx_dim, precision):
+    eng, _ = get_engine(ctx_dim)
+    T = shape[3]
+    worst = run_case(eng, ctx_dim, shape, precision, (0, 1), lambda traj: T if traj else 0)
+    report("", shape, ctx_dim, precision, worst)
+
+
+@pytest.mark.parametrize("precision", ["f16mx", "f32"])
+def test_pieces_that_start_mid_trajectory(precision):
+    """49 152 tokens at d_model 64: plan_step itself picks 12 tokens per wave ("out_traj" = 0), so half the pieces start at t0 = 12 -
+    run_case asserts the reported out_tpw, the case cannot silently stop reaching that path."""
+    eng, _ = get_engine(32)
+    worst = run_case(eng, 32, S.BIG_SHAPE, precision, (0,), lambda traj: S.BIG_TPW)
+    report("", S.BIG_SHAPE, 32, precision, worst)
+
+
+def test_seam_on_hyper_rows_given_directly():
+    """hyp ~ N(0, 1) as the qkv0 and tail tests pass it: gates saturate more than on ctx-made rows"""
+    eng, _ = get_engine(256)
+    shape = (3, 3, 5, 7)
+    worst = run_case(eng, 256, shape, "f16mx", (0, 1), lambda traj: 7 if traj else 0, hyp_direct=True)
+    report("direct hyp ", shape, 256, "f16mx", worst)
+
+
+def test_seam_on_an_imid_handle():
+    eng, _ = get_engine(256, joint=False)
+    shape = (3, 3, 5, 7)
+    worst = run_case(eng, 256, shape, "f16mx", (0, 1), lambda traj: 7 if traj else 0)
+    report("iMID ", shape, 256, "f16mx", worst)
+
+
+@pytest.mark.parametrize("ctx_dim", S.WIDTHS)
+@pytest.mark.parametrize("EA", [(1, 1), (2, 2), (5, 5)])
+def test_hyper_rows_at_edge_tiles(EA, ctx_dim):
+    """E A = 1, 4 and 25 rows of the call's hyper GEMM (N = 228 / 1796, K = 32 / 256): edge tiles in M and N"""
+    eng, _ = get_engine(ctx_dim)
+    n = net(ctx_dim)
+    shape = (EA[0], EA[1], 1, 1)
+    rows = EA[0] * EA[1]
+    ctx = np.random.default_rng(rows + ctx_dim).standard_normal((rows, ctx_dim)).astype(np.float32)
+    x = np.zeros((rows, 2), np.float32)
+    r = eng.dbg_seam(None, x, shape, 0, -1, "f32", ctx=ctx, embed_only=True)
+    w = Worst()
+    w.check("hyper", r["hyp"], *S.hyper_stage(ctx, n["W"], n["b"]), f"{rows} rows")
+    report("hyper rows ", shape, ctx_dim, "f32", w.r)
