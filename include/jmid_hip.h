@@ -780,6 +780,55 @@ int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const in
                            double threshold, double margin, double tau, double step, int max_iter, float* pos_out, float* vel_out,
                            float* sample_out, int32_t* episode_out, int mem);
 
+/* Collision repair with walls: jmid_repair_collisions whose objective and whose two gates know the wall segments of
+ * jmid_wall_statistics.  The reference has no body for this either, so THE RULE is decided here; it is that entry's rule plus a second
+ * family of terms.  fp64 on the fp32 inputs, every sample independent of every other.  OFF unless this entry is called.
+ *   Paths       agent a walks q[0 .. NP-1]: its T forecast points, with p0[a] in front when p0 is given (NP = T + 1) - the segments
+ *               jmid_wall_statistics walks.  p0 is fixed: it takes no gradient and is never written.
+ *   Candidates  a sample is a candidate iff the pedestrian predicate flags it (n_agents_colliding > 0 at `threshold`) OR the wall predicate
+ *               flags it (jmid_wall_statistics' own kernel at (walls, wall_radius, p0) gives n_agents_hitting > 0).  A NaN in either
+ *               minimum is state 3, untouched.  A single real agent (A = 1 or n_agents[e] = 1) IS a candidate when it hits a wall.
+ *   Wall term   per (agent, step s = q[s] -> q[s+1], wall l) the objective gains tau * softplus((m_w - d) / tau), m_w = wall_radius + margin.
+ *               d, the unit normal n and the weights of the step's two ends come from a closest-point form of their own (NOT the
+ *               predicate's branchy function, which judges the result).  With b0 = q[s], b1 = q[s+1], the wall w0 -> w1 and the four
+ *               difference vectors p00 = b0 - w0, p01 = b0 - w1, p10 = b1 - w0, p11 = b1 - w1, four candidates in fixed order, each the
+ *               origin against a segment a -> b in jmid_repair_collisions' closed form (ab = b - a, den = ab . ab,
+ *               u = den > 0 ? clamp(-(a . ab) / den, 0, 1) : 0, c = a + u ab, s = c . c; c points from the wall to the path):
+ *                 0. b0 onto the wall:           (a, b) = (p00, p01), weights (1, 0) on (b0, b1)
+ *                 1. b1 onto the wall:           (a, b) = (p10, p11), weights (0, 1)
+ *                 2. the wall's start onto the step: (a, b) = (p00, p10), weights (1 - u, u)
+ *                 3. the wall's end onto the step:   (a, b) = (p01, p11), weights (1 - u, u)
+ *               The candidate with the smallest s wins, the first one on a tie; d = sqrt(s), n = d > 0 ? c / d : (1, 0).
+ *               A step that PROPERLY CROSSES the wall - with W = w1 - w0, B = b1 - b0, o1 = W x p00, o2 = W x p10, o3 = By p00x - Bx p00y,
+ *               o4 = By p01x - Bx p01y: o1 and o2 of strictly opposite signs AND o3 and o4 of strictly opposite signs - takes candidate 1
+ *               with d negated and the normal reversed, so the far end is pulled back to the near end's side.
+ *               sigma = sigmoid((m_w - d) / tau) in the overflow-free form; the step subtracts (sigma w_b0) n from g[b0] and
+ *               (sigma w_b1) n from g[b1].
+ *   Order       the summation order of g[a][t]: the pedestrian partners first, exactly as in jmid_repair_collisions; then the walls l
+ *               ascending, per wall the step that ENDS in the point first, then the step that STARTS there.  No atomics.
+ *   Stop        when the pedestrian minimum is >= threshold + margin / 2 AND the minimum of d over all (agent, step, wall) is
+ *               >= wall_radius + margin / 2.  With fewer than two real agents only the wall minimum counts.
+ *   End         x is rounded to fp32 and BOTH predicates' own device functions run on the rounded values (the p0 step included for the
+ *               walls; a NaN is kept).  Acceptable to both (no pair closer than threshold, no d(a, l) - wall_radius < 0): state 1.
+ *               Otherwise the sample reverts bit for bit, state 2.  The velocity rule is jmid_repair_collisions'.
+ * A step that crosses a wall is repaired only by walking its far point back, point after point: a path that stays behind a wall for many
+ * steps reverts within max_iter = 32.  That is a stated limit of the form.
+ *   walls       [L, 4] float64 {x1, y1, x2, y2}, a HOST array, 0 <= L <= 64, finite; wall_radius finite and >= 0
+ *   p0          [E, A, 2] or NULL: the first point of every path (and x32[-1] of the velocities).  NULL: T - 1 steps per agent
+ *   sample_out, episode_out   as jmid_repair_collisions ("colliding on entry" reads "a candidate for either cause"): the old entry's rows
+ *               are a prefix of this entry's outputs
+ *   wall_out    [E, K, 2] float = {min_clear before, min_clear after (of the sample that comes back)}; may be NULL.  L = 0: +inf twice
+ * Everything else - n_agents (with jmid_wall_statistics_padded's rules), pos = NULL and the resident set, pos_out, vel_out, the defaults -
+ * as jmid_repair_collisions.  L = 0 IS jmid_repair_collisions, bit for bit in the four outputs they share.  Four launches on the handle's
+ * stream: the collision kernel's lean form, the wall kernel's lean form, the repair kernel (the walls [L, 4] and the p0 rows staged in LDS
+ * next to the sample: 53.0 KB at A = 64, T = 24, L = 64 with p0, inside the 64 KB a workgroup gets by default), the episode rows.
+ * Limits: those of jmid_repair_collisions and jmid_wall_statistics.  JMID_EINVAL: those of jmid_repair_collisions, L outside 0..64, a
+ * wall_radius that is not finite or < 0, L > 0 with walls NULL, a non-finite wall coordinate. */
+int jmid_repair_collisions_walls(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, float dt,
+                                 double threshold, double margin, double tau, double step, int max_iter, int L, const double* walls,
+                                 double wall_radius, float* pos_out, float* vel_out, float* sample_out, int32_t* episode_out, float* wall_out,
+                                 int mem);
+
 /* Padded chains on the resident scene: jmid_predict_scene / jmid_forecast_scene (and their seeded forms) for a scene whose episodes have
  * DIFFERENT in-cluster counts - what jmid_build_scene leaves whenever it chooses the clusters itself - in one call, in the layout and
  * under the rules of "Padded scene batches" above.  The caller passes no n_agents: the counts are the resident scene's n_in, read on the

@@ -943,12 +943,13 @@ int jmid_wall_statistics_padded(jmid_handle_t h, int E, int A, int K, int T, con
 }
 
 // The repair of colliding samples (repair.hpp): the collision kernel's lean form for the flags, the repair kernel, the episode rows - three
-// launches on the handle's stream, nothing comes back to the host in between.  pos null: the resident set, in place
-int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, float dt,
-                           double threshold, double margin, double tau, double step, int max_iter, float* pos_out, float* vel_out,
-                           float* sample_out, int32_t* episode_out, int mem) {
+// launches on the handle's stream, nothing comes back to the host in between.  pos null: the resident set, in place.
+// jmid_repair_collisions (with_walls false: L = 0, no wall_out) and jmid_repair_collisions_walls: with L > 0 the wall kernel's lean form runs
+// next to the collision kernel's and the repair kernel is the instance with the wall terms - four launches
+static int repair_entry(jmid_handle_t h, const char* who, bool with_walls, int E, int A, int K, int T, const int32_t* n_agents, const float* pos,
+                        const float* p0, float dt, double threshold, double margin, double tau, double step, int max_iter, int L, const double* walls,
+                        double wall_radius, float* pos_out, float* vel_out, float* sample_out, int32_t* episode_out, float* wall_out, int mem) {
     if (!h || E <= 0) return fail(h, JMID_EINVAL, "bad argument");
-    const char* who = "jmid_repair_collisions";
     const std::string w(who);
     if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
         return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
@@ -959,21 +960,28 @@ int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const in
     if (max_iter < 0 || max_iter > RPR_MAX_ITER) return fail(h, JMID_EINVAL, w + ": max_iter must lie in 0..1024");
     if (vel_out && !p0) return fail(h, JMID_EINVAL, w + ": vel_out needs p0 (a velocity's first step starts at the present position)");
     if (p0 && !(dt > 0.0f && std::isfinite(dt))) return fail(h, JMID_EINVAL, w + ": p0 needs a finite dt > 0 (the velocities divide by it)");
-    if (pos && !pos_out && !vel_out && !sample_out && !episode_out) return fail(h, JMID_EINVAL, w + ": every output is NULL");
+    if (pos && !pos_out && !vel_out && !sample_out && !episode_out && !wall_out) return fail(h, JMID_EINVAL, w + ": every output is NULL");
     if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
+    if (with_walls && (!(wall_radius >= 0.0) || !std::isfinite(wall_radius))) return fail(h, JMID_EINVAL, w + ": the wall_radius must be finite and >= 0");
     if (n_agents)
         if (int rc = check_n_agents(h, who, n_agents, E, A)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
+    WallStatsArgs ws{};
+    if (with_walls)
+        if (int rc = upload_walls(h, L, walls, &ws.walls, w)) return rc;
     if (!pos && !resident_positions(h, E, A, K, T)) return JMID_EINVAL;
     const bool host = mem == JMID_MEM_HOST;
     const size_t M2 = (size_t)E * K * A * T * 2;
     CollisionStatsArgs cs{};
     cs.E = E; cs.A = A; cs.K = K; cs.T = T; cs.threshold = threshold;
-    RepairArgs g{};
+    RepairWallArgs g{};
     g.E = E; g.A = A; g.K = K; g.T = T; g.max_iter = max_iter;
     g.threshold = threshold; g.margin = margin; g.tau = tau; g.step = step; g.dt = (double)dt;
+    g.L = L; g.walls = ws.walls; g.wall_radius = wall_radius;
+    ws.E = E; ws.A = A; ws.K = K; ws.T = T; ws.L = L; ws.radius = wall_radius;
     Staging st(h, mem, h->kde_ws, who);
-    st.scratch(&cs.ws, (size_t)E * K * CLS_WS_COLS * 8);
+    const size_t lean = (size_t)E * K * CLS_WS_COLS;          // the collision kernel's lean form, and behind it the wall kernel's (one slot)
+    st.scratch(&cs.ws, (lean + (L > 0 ? (size_t)E * K * WLS_WS_COLS : 0)) * 8);
     if (pos) {
         st.in(&g.src, pos, M2);
         if (pos_out) st.out(&g.dst, pos_out, M2);
@@ -982,7 +990,7 @@ int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const in
         g.dst = const_cast<float*>(h->last_pos);
         if (p0 && h->last_vel && h->last_vel_pos == h->last_pos) g.vel2 = h->last_vel;
     }
-    if (p0 && (vel_out || g.vel2)) st.in(&g.p0, p0, (size_t)E * A * 2);
+    if (p0 && (vel_out || g.vel2 || L > 0)) st.in(&g.p0, p0, (size_t)E * A * 2);      // (with walls: the first point of every path)
     if (vel_out) {      // in and out: only the rows of repaired samples are rewritten
         g.vel = vel_out;
         if (host) st.add(&g.vel, vel_out, vel_out, M2 * sizeof(float));
@@ -990,20 +998,44 @@ int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const in
     if (sample_out) st.out(&g.sample, sample_out, (size_t)E * K * RPR_SAMPLE_COLS);
     else st.scratch(&g.sample, (size_t)E * K * RPR_SAMPLE_COLS * sizeof(float));
     if (episode_out) st.out(&g.episode, episode_out, (size_t)E * RPR_EPISODE_COLS);
+    if (wall_out) st.out(&g.wall_out, wall_out, (size_t)E * K * RPR_WALL_COLS);
     if (int rc = st.begin()) return rc;
     if (n_agents) {
         if (int rc = h->nag.upload(h, n_agents, E, who)) return rc;
-        cs.n_agents = g.n_agents = h->nag.get<int>();
+        cs.n_agents = ws.n_agents = g.n_agents = h->nag.get<int>();
     }
-    cs.pos = g.src;
+    cs.pos = ws.pos = g.src;
+    ws.p0 = g.p0;
+    ws.ws = L > 0 ? cs.ws + lean : nullptr;
     g.ws = cs.ws;
+    g.wws = ws.ws;
     {
         ProfScope ps(h, KC_EVAL_STATS, h->stream);
         HIPCHK(h, launch_collision_stats(cs, h->stream));
-        HIPCHK(h, launch_repair(g, h->stream));
+        if (!with_walls) {
+            HIPCHK(h, launch_repair(g, h->stream));
+        } else {
+            if (L > 0) HIPCHK(h, launch_wall_stats(ws, h->stream));
+            HIPCHK(h, launch_repair_walls(g, h->stream));
+        }
     }
     if (!pos && pos_out) HIPCHK(h, hipMemcpyAsync(pos_out, h->last_pos, M2 * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
     return st.end();
+}
+
+int jmid_repair_collisions(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, float dt,
+                           double threshold, double margin, double tau, double step, int max_iter, float* pos_out, float* vel_out,
+                           float* sample_out, int32_t* episode_out, int mem) {
+    return repair_entry(h, "jmid_repair_collisions", false, E, A, K, T, n_agents, pos, p0, dt, threshold, margin, tau, step, max_iter, 0, nullptr, 0.0,
+                        pos_out, vel_out, sample_out, episode_out, nullptr, mem);
+}
+
+int jmid_repair_collisions_walls(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* pos, const float* p0, float dt,
+                                 double threshold, double margin, double tau, double step, int max_iter, int L, const double* walls,
+                                 double wall_radius, float* pos_out, float* vel_out, float* sample_out, int32_t* episode_out, float* wall_out,
+                                 int mem) {
+    return repair_entry(h, "jmid_repair_collisions_walls", true, E, A, K, T, n_agents, pos, p0, dt, threshold, margin, tau, step, max_iter, L, walls,
+                        wall_radius, pos_out, vel_out, sample_out, episode_out, wall_out, mem);
 }
 
 // jmid_topk (n_agents null) and jmid_topk_padded

@@ -888,7 +888,8 @@ class JmidEngine:
 
     def repair_collisions(self, pos: Optional[ArrayLike], threshold: float = 0.2, margin: float = 0.02, tau: float = 0.005, step: float = 0.02,
                           max_iter: int = 32, p0: Optional[ArrayLike] = None, dt: float = 0.25, vel: Optional[ArrayLike] = None,
-                          dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None, want_pos: Optional[bool] = None):
+                          dims: Optional[Tuple[int, int, int, int]] = None, n_agents=None, want_pos: Optional[bool] = None, walls=None,
+                          wall_radius: Optional[float] = None):
         """Collision repair on the device (``jmid_repair_collisions``; the rule stands in include/jmid_hip.h, its host twin is
         ``metrics.repair_collisions_host``): every joint sample of pos [E, K, A, T, 2] in which ``collision_statistics`` counts a colliding
         agent at ``threshold`` is pushed apart under a softplus penalty until the predicate holds - a small fp64 optimisation on the
@@ -900,7 +901,16 @@ class JmidEngine:
         ``pos=None`` with ``dims=(E, A, K, T)``: the set the preceding ``denoise`` / ``denoise_reject`` call left in the engine's workspace is
         repaired IN PLACE (with ``p0``, the accepted block's velocities too where it holds them): ``topk(None, ...)`` and the statistics
         entries then see the repaired set; pos_out is None unless ``want_pos=True`` (``p0`` / ``vel`` decide where the outputs live; host
-        arrays without them).  ``n_agents`` [E]: a padded batch - padded agents take part in nothing and their rows pass through."""
+        arrays without them).  ``n_agents`` [E]: a padded batch - padded agents take part in nothing and their rows pass through.
+        ``walls`` [L, 4] or [L, 2, 2] (a host array, as for ``wall_statistics``) with ``wall_radius`` (``jmid_repair_collisions_walls``): the
+        wall terms join the objective and the wall predicate at (walls, wall_radius, p0) joins both gates - a sample that hits a wall is a
+        candidate too, a single agent included, and is kept only when both predicates accept it; ``p0`` is then the fixed first point of
+        every path.  A fifth value comes back: wall [E, K, 2] = ``metrics.REPAIR_WALL_COLUMNS``.  No walls (L = 0): the four values above,
+        bit for bit, and +inf in the fifth."""
+        if walls is None and wall_radius is not None:
+            raise ValueError("wall_radius is given without walls")
+        if walls is not None and wall_radius is None:
+            raise ValueError("walls need wall_radius (the repair knows no agent radius)")
         if pos is None:
             if dims is None:
                 raise ValueError("pos=None needs dims=(E, A, K, T) of the preceding denoise call")
@@ -928,6 +938,15 @@ class JmidEngine:
         pos_out = _out((E, K, A, T, 2), device=where) if want_pos else None
         sample, episode = _out((E, K, 4), device=where), _out((E, 3), np.int32, where)
         na = agent_counts(n_agents, E) if n_agents is not None else None
+        if walls is not None:
+            w = wall_segments(walls)
+            wall = _out((E, K, 2), device=where)
+            self._check(self._lib.jmid_repair_collisions_walls(self._h, E, A, K, T, _ptr(na), bp.ptr if bp is not None else None,
+                                                               b0.ptr if b0 is not None else None, float(dt), float(threshold), float(margin),
+                                                               float(tau), float(step), int(max_iter), int(w.shape[0]),
+                                                               _ptr(w) if w.shape[0] else None, float(wall_radius), _ptr(pos_out), _ptr(vel_out),
+                                                               _ptr(sample), _ptr(episode), _ptr(wall), self._mem(dev)))
+            return pos_out, vel_out, sample, episode, wall
         self._check(self._lib.jmid_repair_collisions(self._h, E, A, K, T, _ptr(na), bp.ptr if bp is not None else None,
                                                      b0.ptr if b0 is not None else None, float(dt), float(threshold), float(margin), float(tau),
                                                      float(step), int(max_iter), _ptr(pos_out), _ptr(vel_out), _ptr(sample), _ptr(episode),

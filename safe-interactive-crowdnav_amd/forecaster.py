@@ -52,6 +52,11 @@ download.  The route is staged (denoise -> repair -> ranking on the repaired set
 collisions, repaired, reverted, largest iteration count), and ``repair_options`` = {margin, tau, step, max_iter} overrides the defaults.
 Together with ``collision_free_rounds=R`` the redraw loop runs first and the repair takes whatever is still flagged.  Not with
 ``static_obstacles=``: walls are not in the objective.
+``constraint_type="opt_softplus_walls"`` (opt-in; needs ``static_obstacles=`` and ``wall_radius=``, with or without a redraw loop): the same
+stage with the walls in the objective and in both gates (``jmid_repair_collisions_walls``) - a sample whose paths, the step from the present
+position included, come closer than ``wall_radius`` to a wall is a candidate too, a single pedestrian included, and a repaired sample is
+kept only when both predicates accept it.  ``self.repair_causes`` holds the last call's candidates split by cause
+(``metrics.repair_causes``).
 
 Differences from the reference that a caller can observe:
   * the engine (weights on the GPU) is cached across instances: the reference rebuilds the model and reloads the
@@ -103,14 +108,17 @@ DEFAULTS = {"device_id": 0, "precision": "f16mx", "rng_compat": "auto", "self_ch
 _PHILOX_STEP: Dict[Tuple[int, Tuple[int, ...]], int] = {}     # (device, shape) -> what one randn_like of that shape adds to the Philox offset
 
 
-def wall_arguments(static_obstacles, wall_radius, rounds: int) -> dict:
+def wall_arguments(static_obstacles, wall_radius, rounds: int, repair_walls: bool = False) -> dict:
     """The ``static_obstacles`` / ``wall_radius`` keywords of the forecaster, ``predict_batch`` and ``offline.sample`` as the keywords of
     ``JmidEngine.denoise_reject``: {} without walls (the call, its route and its bits are then what they were), else
     {"walls": [L, 4] float64, "wall_radius": float}.  Walls need collision-free sampling (``rounds`` > 0) and a radius - the sampler
-    knows no agent radius, so there is no default."""
+    knows no agent radius, so there is no default.  ``repair_walls``: ``constraint_type="opt_softplus_walls"`` reads the walls too
+    (``repair_arguments`` holds its copy), so without a redraw loop there is nothing to hand to one: {}."""
     if static_obstacles is None:
         if wall_radius is not None:
             raise ValueError("wall_radius is given without static_obstacles")
+        return {}
+    if rounds <= 0 and repair_walls:
         return {}
     if rounds <= 0:
         raise ValueError("static_obstacles needs collision-free sampling (collision_free_rounds > 0 / with_constraints=True)")
@@ -129,20 +137,25 @@ def wall_arguments(static_obstacles, wall_radius, rounds: int) -> dict:
 REPAIR_OPTIONS = ("margin", "tau", "step", "max_iter")
 
 
-def repair_arguments(constraint_type, repair_options=None, static_obstacles=None) -> Optional[dict]:
+CONSTRAINT_TYPES = ("opt_softplus", "opt_softplus_walls")
+
+
+def repair_arguments(constraint_type, repair_options=None, static_obstacles=None, wall_radius=None) -> Optional[dict]:
     """The ``constraint_type`` / ``repair_options`` keywords of the forecaster, ``predict_batch`` and ``offline.sample`` as the keywords of
     ``JmidEngine.repair_collisions``: None without a constraint type (nothing changes), else the options that were given ({}: the
-    defaults).  The only type is the reference configs' ``"opt_softplus"``; walls are not in its objective, so ``static_obstacles`` is
-    refused with it."""
+    defaults).  ``"opt_softplus"`` is the reference configs' name; walls are not in its objective, so ``static_obstacles`` is refused with
+    it.  ``"opt_softplus_walls"`` (``jmid_repair_collisions_walls``) has them in the objective and in both gates: it NEEDS
+    ``static_obstacles`` and ``wall_radius`` (no default: the sampler knows no agent radius), which come back as the keys ``walls`` /
+    ``wall_radius``."""
     if constraint_type is None:
         if repair_options:
             raise ValueError("repair_options is given without constraint_type")
         return None
-    if constraint_type != "opt_softplus":
-        raise ValueError(f"unknown constraint_type {constraint_type!r} (the one there is: 'opt_softplus')")
-    if static_obstacles is not None:
+    if constraint_type not in CONSTRAINT_TYPES:
+        raise ValueError(f"unknown constraint_type {constraint_type!r} (known: {list(CONSTRAINT_TYPES)})")
+    if constraint_type == "opt_softplus" and static_obstacles is not None:
         raise ValueError("static_obstacles cannot be combined with constraint_type='opt_softplus': walls are not in the repair's objective "
-                         "(a repaired sample could be pushed into one)")
+                         "(a repaired sample could be pushed into one); constraint_type='opt_softplus_walls' has them")
     opts = dict(repair_options or {})
     unknown = sorted(set(opts) - set(REPAIR_OPTIONS))
     if unknown:
@@ -152,6 +165,10 @@ def repair_arguments(constraint_type, repair_options=None, static_obstacles=None
             raise ValueError(f"repair_options[{key!r}] must be finite and {'>= 0' if key == 'margin' else '> 0'}")
     if "max_iter" in opts and not 0 <= int(opts["max_iter"]) <= 1024:
         raise ValueError("repair_options['max_iter'] must lie in 0..1024")
+    if constraint_type == "opt_softplus_walls":
+        if static_obstacles is None:
+            raise ValueError("constraint_type='opt_softplus_walls' needs static_obstacles (and wall_radius)")
+        opts.update(wall_arguments(static_obstacles, wall_radius, 1))
     return opts
 
 
@@ -163,11 +180,27 @@ def repair_totals(episode) -> Tuple[int, int, int, int]:
     return int(ep[:, 0].sum()), int(ep[:, 1].sum()), int(ep[:, 0].sum() - ep[:, 1].sum()), int(ep[:, 2].max())
 
 
-def repair_stage(engine: JmidEngine, pos, dims: Tuple[int, int, int, int], threshold: float, options: dict, n_agents=None):
+def repair_stage(engine: JmidEngine, pos, dims: Tuple[int, int, int, int], threshold: float, options: dict, n_agents=None, p0=None,
+                 dt: Optional[float] = None, causes: Optional[list] = None):
     """The repair stage of a staged route behind a denoise (or rejection) call of ``dims`` = (E, A, K, H): ``pos`` [E, K, A, H, 2], or None
     when the samples stayed on the device - they are then repaired where they lie and the ranking reads them there.
-    -> (pos repaired, or None; episode [E, 3])."""
-    out, _, _, episode = engine.repair_collisions(pos, threshold=threshold, dims=dims if pos is None else None, n_agents=n_agents, **options)
+    -> (pos repaired, or None; episode [E, 3]).  With walls among the ``options`` (``"opt_softplus_walls"``) the call's ``p0`` [E, A, 2] and
+    ``dt`` go along - the step from the present position is part of the wall predicate, as in the redraw loop - and ``causes``, a list,
+    receives ``metrics.repair_causes`` of the call."""
+    if "walls" not in options:
+        out, _, _, episode = engine.repair_collisions(pos, threshold=threshold, dims=dims if pos is None else None, n_agents=n_agents, **options)
+        return out, episode
+    from .metrics import repair_causes
+    on_device = pos is not None and torch.is_tensor(pos) and pos.is_cuda
+    # p0 goes where pos lives (pos None: the resident set, host arrays out)
+    if on_device:
+        p0 = (p0 if torch.is_tensor(p0) else torch.from_numpy(np.ascontiguousarray(p0, dtype=np.float32))).to(pos.device, torch.float32).contiguous()
+    else:
+        p0 = np.ascontiguousarray(p0.detach().cpu().numpy() if torch.is_tensor(p0) else p0, dtype=np.float32)
+    out, _, sample, episode, wall = engine.repair_collisions(pos, threshold=threshold, dims=dims if pos is None else None, n_agents=n_agents,
+                                                             p0=p0, dt=float(dt), **options)
+    if causes is not None:
+        causes.append(repair_causes(sample, wall, threshold, options["wall_radius"]))
     return out, episode
 
 
@@ -337,9 +370,13 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # rejection holds five counts (the three, then the samples that fail the pedestrian predicate, the wall predicate)
         # constraint_type="opt_softplus" (opt-in, every RNG contract): collision repair behind the denoise stage (and behind the redraw
         # loop, when both are asked for); repair: the last call's (samples with collisions, repaired, reverted, largest iteration count)
-        self.constraint_type, self._repair_options = constraint_type, repair_arguments(constraint_type, repair_options, static_obstacles)
+        # constraint_type="opt_softplus_walls": the same stage with the walls in the objective and in both gates (needs static_obstacles +
+        # wall_radius, with or without a redraw loop); repair_causes: the last call's candidates split by cause (metrics.repair_causes)
+        self.constraint_type = constraint_type
+        self._repair_options = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
         self.repair: Optional[Tuple[int, int, int, int]] = None
-        self._walls = wall_arguments(static_obstacles, wall_radius, self.collision_free_rounds)
+        self.repair_causes: Optional[Dict[str, int]] = None
+        self._walls = wall_arguments(static_obstacles, wall_radius, self.collision_free_rounds, constraint_type == "opt_softplus_walls")
         self.rejection: Optional[Tuple[int, ...]] = None
         self._init_MID(mid_config_file, weights, device_id, lib_path)
 
@@ -631,8 +668,10 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                     if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
                         pos = self._self_check(x_np, ctx[None], p0[None], pos)
                 if self._repair_options is not None:      # on the set the stage above left: in place on the device, or on the host copy
-                    pos, episode = repair_stage(self.engine, pos, (1, A, K, H), self.collision_threshold, self._repair_options)
-                    self.repair = repair_totals(episode)
+                    causes = []
+                    pos, episode = repair_stage(self.engine, pos, (1, A, K, H), self.collision_threshold, self._repair_options, p0=p0[None],
+                                                dt=self.time_step, causes=causes)
+                    self.repair, self.repair_causes = repair_totals(episode), causes[0] if causes else None
                 t2 = time.perf_counter()
                 rows, logw = rank_samples(self.engine, route.rank, pos, k, (1, A, K, H))
         t3 = time.perf_counter()
@@ -827,14 +866,17 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     when ``collision_free_rounds`` is given too - and the ranking on the repaired set; every group is staged.  ``stats`` gets ``repair``
     [E, 3] int32 = (samples with collisions, repaired, largest iteration count), rows in input order (an empty cluster: zeros).  Not with
     ``static_obstacles=`` (walls are not in the objective); with ``padded=`` the batch takes the count groups.
+    ``constraint_type="opt_softplus_walls"`` (needs ``static_obstacles=`` and ``wall_radius=``): the repair with the walls in its objective and
+    in both gates, every call with its group's ``p0``; ``stats`` also gets ``repair_causes``, the sums of ``metrics.repair_causes``.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
     if padded not in (False, True, "resident"):
         raise ValueError("padded must be False, True or 'resident'")
     R = int(collision_free_rounds)
-    fix = repair_arguments(constraint_type, repair_options, static_obstacles)
-    walls = wall_arguments(static_obstacles, wall_radius, R)
+    fix = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
+    walls = wall_arguments(static_obstacles, wall_radius, R, constraint_type == "opt_softplus_walls")
+    causes = [] if fix is not None and "walls" in fix else None      # metrics.repair_causes of every repair call
     if R:
         if padded:
             raise ValueError("collision_free_rounds has no padded form (jmid_denoise_reject_seeded takes one agent count per call)")
@@ -925,9 +967,11 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                 ctx, p0, seed=int(seed), episode_ids=np.asarray(seeds), K=K, T=H, dt=time_step, precision=p, threshold=collision_threshold,
                 max_rounds=R, draw0=0, want_vel=False, want_pos=route.rank != "device_resident", n_agents=counts, **walls), precision)
             if fix is not None:
-                pos, fixed = repair_stage(engine, pos, (E, A, K, H), collision_threshold, fix, n_agents=counts)
+                pos, fixed = repair_stage(engine, pos, (E, A, K, H), collision_threshold, fix, n_agents=counts, p0=p0, dt=time_step, causes=causes)
                 if stats is not None:
                     stats["repair"] = fixed
+                    if causes:
+                        stats["repair_causes"] = causes[0]
             if route.rank == "host":        # (beyond the device top-k's limits: the host twin on every episode's real agents)
                 sel, lw = np.full((E, A, k, H, 2), np.nan, dtype=np.float32), np.full((E, A, k), np.nan, dtype=np.float32)
                 for e in range(E):
@@ -986,11 +1030,13 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             else:
                 pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
             if fix is not None and A:
-                pos, fixed = repair_stage(engine, pos, (len(eps), A, K, H), collision_threshold, fix)
+                pos, fixed = repair_stage(engine, pos, (len(eps), A, K, H), collision_threshold, fix, p0=p0, dt=time_step, causes=causes)
                 if stats is not None:
                     stats["repair"][eps] = fixed
             sel, lw = rank_samples(engine, route.rank, pos, k, (len(eps), A, K, H))
         forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], sel, lw, b["cv"][eps], pose_now[eps], k, K)
+    if causes and stats is not None:            # the groups' counts, summed
+        stats["repair_causes"] = {key: sum(c[key] for c in causes) for key in causes[0]}
     if absent:
         forecasts[left_out], logw[left_out] = np.nan, np.nan
     return forecasts, logw, inc

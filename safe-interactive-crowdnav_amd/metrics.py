@@ -439,6 +439,7 @@ def summarise_collisions(scene: np.ndarray) -> Dict[str, float]:
 
 REPAIR_SAMPLE_COLUMNS = ("min_dist_before", "min_dist_after", "iterations", "state")
 REPAIR_EPISODE_COLUMNS = ("colliding", "repaired", "max_iterations")
+REPAIR_WALL_COLUMNS = ("min_clear_before", "min_clear_after")
 REPAIR_UNTOUCHED, REPAIR_REPAIRED, REPAIR_REVERTED, REPAIR_NAN = 0, 1, 2, 3
 # the defaults of collision repair (include/jmid_hip.h, ``jmid_repair_collisions``): arguments of the entry, not constants of the rule
 REPAIR_DEFAULTS = {"margin": 0.02, "tau": 0.005, "step": 0.02, "max_iter": 32}
@@ -462,10 +463,55 @@ def _repair_segments(x: np.ndarray, lo: np.ndarray, hi: np.ndarray, m: float, ta
     return d, u, nx, ny, sigma
 
 
-def _repair_iterate(x: np.ndarray, threshold: float, margin: float, tau: float, step: float, max_iter: int, exp):
-    """The iteration of the rule on the candidates x [S, n, T, 2] float64 -> (x at the end, iterations used [S])."""
+def _repair_wall_segments(q: np.ndarray, wall, m: float, tau: float, exp):
+    """The wall term's closest-point form for the steps q[:, :, s] -> q[:, :, s + 1] of q [S, n, NP, 2] and ONE wall {x1, y1, x2, y2}:
+    -> (d, w0, w1, nx, ny, sigma), each [S, n, NP - 1]; w0 / w1 are the weights of the step's two ends.  The operations and their order are
+    the device function's (``csrc/repair.hpp::rpr_wall_segment``)."""
+    w0x, w0y, w1x, w1y = (float(v) for v in wall)
+    b0x, b0y, b1x, b1y = q[:, :, :-1, 0], q[:, :, :-1, 1], q[:, :, 1:, 0], q[:, :, 1:, 1]
+    p00x, p00y, p01x, p01y = b0x - w0x, b0y - w0y, b0x - w1x, b0y - w1y
+    p10x, p10y, p11x, p11y = b1x - w0x, b1y - w0y, b1x - w1x, b1y - w1y
+
+    def closest(ax, ay, bx, by):                             # the origin against the segment a -> b, rpr_segment's closed form
+        abx, aby = bx - ax, by - ay
+        den = abx * abx + aby * aby
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = np.where(den > 0.0, np.clip(-(ax * abx + ay * aby) / den, 0.0, 1.0), 0.0)
+        cx, cy = ax + u * abx, ay + u * aby
+        return u, cx, cy, cx * cx + cy * cy
+
+    _, cx, cy, best = closest(p00x, p00y, p01x, p01y)        # b0 onto the wall
+    wa, wb = np.ones_like(best), np.zeros_like(best)
+    _, c1x, c1y, s1 = closest(p10x, p10y, p11x, p11y)        # b1 onto the wall
+    # a step that properly crosses the wall: the four orientation products, strictly opposite signs twice
+    Wx, Wy, Bx, By = w1x - w0x, w1y - w0y, b1x - b0x, b1y - b0y
+    o1, o2 = Wx * p00y - Wy * p00x, Wx * p10y - Wy * p10x
+    o3, o4 = By * p00x - Bx * p00y, By * p01x - Bx * p01y
+    cross = (((o1 > 0.0) & (o2 < 0.0)) | ((o1 < 0.0) & (o2 > 0.0))) & (((o3 > 0.0) & (o4 < 0.0)) | ((o3 < 0.0) & (o4 > 0.0)))
+    take = s1 < best
+    cx, cy, best, wa, wb = np.where(take, c1x, cx), np.where(take, c1y, cy), np.where(take, s1, best), np.where(take, 0.0, wa), np.where(take, 1.0, wb)
+    for ax, ay, bx, by in ((p00x, p00y, p10x, p10y), (p01x, p01y, p11x, p11y)):      # the wall's start, then its end, onto the step
+        u, c2x, c2y, s2 = closest(ax, ay, bx, by)
+        take = s2 < best
+        cx, cy, best, wa, wb = np.where(take, c2x, cx), np.where(take, c2y, cy), np.where(take, s2, best), np.where(take, 1.0 - u, wa), np.where(take, u, wb)
+    cx, cy, best, wa, wb = np.where(cross, c1x, cx), np.where(cross, c1y, cy), np.where(cross, s1, best), np.where(cross, 0.0, wa), np.where(cross, 1.0, wb)
+    d = np.sqrt(best)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nx, ny = np.where(d > 0.0, cx / d, 1.0), np.where(d > 0.0, cy / d, 0.0)
+    d, nx, ny = np.where(cross, -d, d), np.where(cross, -nx, nx), np.where(cross, -ny, ny)
+    z = (m - d) / tau
+    e = exp(-np.abs(z))
+    sigma = np.where(z >= 0.0, 1.0 / (1.0 + e), e / (1.0 + e))
+    return d, wa, wb, nx, ny, sigma
+
+
+def _repair_iterate(x: np.ndarray, threshold: float, margin: float, tau: float, step: float, max_iter: int, exp, walls=None,
+                    wall_radius: float = 0.0, lead=None):
+    """The iteration of the rule on the candidates x [S, n, T, 2] float64 -> (x at the end, iterations used [S]).  ``walls`` [L, 4]: the
+    wall terms of ``jmid_repair_collisions_walls`` behind the pairs' (``lead`` [n, 2] or None: the fixed point p0 in front of every path)."""
     S, n, T, _ = x.shape
     m, stop = threshold + margin, threshold + margin * 0.5
+    mw, wstop = wall_radius + margin, wall_radius + margin * 0.5
     x, iters, active = x.copy(), np.zeros(S, dtype=np.int64), np.ones(S, dtype=bool)
     agents = np.arange(n)
     for _ in range(int(max_iter)):
@@ -487,6 +533,22 @@ def _repair_iterate(x: np.ndarray, threshold: float, margin: float, tau: float, 
                 g[:, :, :-1, c] = np.where(real, np.where(sign < 0, g[:, :, :-1, c] - near, g[:, :, :-1, c] + near), g[:, :, :-1, c])
             dmin = np.minimum(dmin, np.where(real, d, np.inf).min(axis=(1, 2)))
         go = dmin < stop
+        if walls is not None:                                # walls ascending; per wall the step that ends in the point, then the one that starts there
+            q = xa if lead is None else np.concatenate([np.broadcast_to(lead[None, :, None, :], (idx.size, n, 1, 2)), xa], axis=2)
+            wmin = np.full(idx.size, np.inf)
+            for wall in walls:
+                d, wa, wb, nx, ny, sigma = _repair_wall_segments(q, wall, mw, tau, exp)
+                we, ws = sigma * wb, sigma * wa
+                for c, nc in ((0, nx), (1, ny)):
+                    end, start = we * nc, ws * nc
+                    if lead is None:
+                        g[:, :, 1:, c] = g[:, :, 1:, c] - end
+                        g[:, :, :-1, c] = g[:, :, :-1, c] - start
+                    else:                                    # step s ends in x[s]; p0 takes no gradient
+                        g[:, :, :, c] = g[:, :, :, c] - end
+                        g[:, :, :-1, c] = g[:, :, :-1, c] - start[:, :, 1:]
+                wmin = np.minimum(wmin, d.min(axis=(1, 2)))
+            go = go | (wmin < wstop)
         active[idx[~go]] = False
         moved = idx[go]
         x[moved] = xa[go] - step * g[go]
@@ -497,7 +559,7 @@ def _repair_iterate(x: np.ndarray, threshold: float, margin: float, tau: float, 
 def repair_collisions_host(pos: np.ndarray, threshold: float = COLLISION_THRESHOLD, margin: float = REPAIR_DEFAULTS["margin"],
                            tau: float = REPAIR_DEFAULTS["tau"], step: float = REPAIR_DEFAULTS["step"],
                            max_iter: int = REPAIR_DEFAULTS["max_iter"], p0: Optional[np.ndarray] = None, dt: Optional[float] = None,
-                           vel: Optional[np.ndarray] = None, n_agents=None, exp=np.exp):
+                           vel: Optional[np.ndarray] = None, n_agents=None, exp=np.exp, walls=None, wall_radius: Optional[float] = None):
     """The NumPy twin of collision repair (``jmid_repair_collisions``; include/jmid_hip.h states the rule, ``csrc/repair.hpp`` is the
     kernel): the same candidates, the same operations in the same order, the same outputs.  pos [E, K, A, T, 2] float32 ->
     (pos_out float32 [E, K, A, T, 2], vel_out float32 or None, sample float64 [E, K, 4] = ``REPAIR_SAMPLE_COLUMNS``, episode int32 [E, 3] =
@@ -505,7 +567,12 @@ def repair_collisions_host(pos: np.ndarray, threshold: float = COLLISION_THRESHO
     ``threshold``; a NaN ``min_dist`` is state 3; everything that is not repaired comes back bit for bit.  ``vel`` [E, K, A, T, 2] with
     ``p0`` [E, A, 2] and ``dt``: the velocities, of which the rows of repaired samples are rewritten as
     float32((float64(x32[t]) - float64(x32[t - 1])) / dt), x32[-1] = p0.  ``n_agents`` [E]: a padded batch - the rule on every compacted
-    episode, the padded rows as they are.  ``exp``: the exponential (the tests perturb it)."""
+    episode, the padded rows as they are.  ``exp``: the exponential (the tests perturb it).
+    ``walls`` [L, 4] or [L, 2, 2] with ``wall_radius`` (``jmid_repair_collisions_walls``): the wall terms join the objective and
+    ``wall_statistics_host`` at (walls, wall_radius, p0) joins both gates - a sample that hits a wall is a candidate too (a single agent
+    included), a NaN in either minimum is state 3, and a sample is kept only when both predicates accept it.  ``p0``, when given, is the
+    fixed first point of every path.  A fifth value comes back: wall float64 [E, K, 2] = ``REPAIR_WALL_COLUMNS``.  L = 0: the first four
+    values are those without walls, bit for bit."""
     pos = np.asarray(pos)
     if pos.dtype != np.float32:
         raise ValueError("pos must be float32 (the rule is defined on the fp32 samples)")
@@ -517,10 +584,21 @@ def repair_collisions_host(pos: np.ndarray, threshold: float = COLLISION_THRESHO
         raise ValueError("max_iter must lie in 0..1024")
     if vel is not None and (p0 is None or dt is None):
         raise ValueError("vel needs p0 and dt")
+    if walls is None and wall_radius is not None:
+        raise ValueError("wall_radius is given without walls")
+    if walls is not None:
+        walls = np.asarray(walls, dtype=np.float64).reshape(-1, 4)
+        if wall_radius is None or not (np.isfinite(wall_radius) and wall_radius >= 0.0):
+            raise ValueError("walls need a wall_radius that is finite and >= 0")
+        if not np.isfinite(walls).all():
+            raise ValueError("a wall has a non-finite coordinate")
+        if p0 is not None and np.asarray(p0).shape != (E, A, 2):
+            raise ValueError("p0 must be [E, A, 2]")
     counts = _counts(n_agents, E, A) if n_agents is not None else np.full(E, A, dtype=np.int64)
     out = pos.copy()
     vel_out = None if vel is None else np.array(vel, dtype=np.float32, copy=True)
     sample, episode = np.zeros((E, K, 4)), np.zeros((E, 3), dtype=np.int32)
+    wall = np.full((E, K, 2), np.inf)
     for e in range(E):
         n = int(counts[e])
         x32 = pos[e, :, :n]
@@ -528,15 +606,29 @@ def repair_collisions_host(pos: np.ndarray, threshold: float = COLLISION_THRESHO
         before, hit = cs[0, :, 0], cs[0, :, 3]
         sample[e, :, 0] = sample[e, :, 1] = before
         is_nan = np.isnan(before)
+        flagged = (hit > 0) & (n >= 2)
+        lead = None
+        if walls is not None:
+            lead32 = None if p0 is None else np.asarray(p0, dtype=np.float32)[e:e + 1, :n]
+            lead = None if lead32 is None else lead32[0].astype(np.float64)
+            _, _, ws, _ = wall_statistics_host(x32[None], walls, wall_radius, lead32)
+            wall[e, :, 0] = wall[e, :, 1] = ws[0, :, 0]
+            is_nan = is_nan | np.isnan(ws[0, :, 0])
+            flagged = flagged | (ws[0, :, 1] > 0)
         sample[e, is_nan, 3] = REPAIR_NAN
-        cand = np.flatnonzero(~is_nan & (hit > 0)) if n >= 2 else np.zeros(0, dtype=np.int64)
+        cand = np.flatnonzero(~is_nan & flagged)
         if not cand.size:
             continue
-        x, iters = _repair_iterate(x32[cand].astype(np.float64), float(threshold), float(margin), float(tau), float(step), max_iter, exp)
+        x, iters = _repair_iterate(x32[cand].astype(np.float64), float(threshold), float(margin), float(tau), float(step), max_iter, exp,
+                                   walls, 0.0 if walls is None else float(wall_radius), lead)
         r32 = x.astype(np.float32)
         _, _, rs, _ = collision_statistics_host(r32[None], threshold)
         after = rs[0, :, 0]
         ok = ~np.isnan(after) & (rs[0, :, 3] == 0)
+        if walls is not None:
+            _, _, ws, _ = wall_statistics_host(r32[None], walls, wall_radius, lead32)
+            ok = ok & ~np.isnan(ws[0, :, 0]) & (ws[0, :, 1] == 0)
+            wall[e, cand[ok], 1] = ws[0, ok, 0]
         sample[e, cand, 2] = iters
         sample[e, cand, 3] = np.where(ok, REPAIR_REPAIRED, REPAIR_REVERTED)
         sample[e, cand[ok], 1] = after[ok]
@@ -547,7 +639,26 @@ def repair_collisions_host(pos: np.ndarray, threshold: float = COLLISION_THRESHO
                                    r[:, :, :-1]], axis=2)
             vel_out[e, cand[ok], :n] = ((r - prev) / float(np.float32(dt))).astype(np.float32)
         episode[e] = (cand.size, int(ok.sum()), int(iters.max()))
-    return out, vel_out, sample, episode
+    if walls is None:
+        return out, vel_out, sample, episode
+    return out, vel_out, sample, episode, wall
+
+
+def repair_causes(sample, wall, threshold: float, wall_radius: float) -> Dict[str, int]:
+    """The candidates of a repair with walls split by cause, from its ``sample`` [..., 4] and ``wall`` [..., 2] outputs: how many samples
+    failed the pedestrian predicate on entry (min_dist < threshold), how many the wall predicate (min_clear - wall_radius < 0), how many
+    both, and of each how many came back repaired.  -> {"pedestrians", "walls", "both", "pedestrians_repaired", "walls_repaired",
+    "both_repaired", "candidates", "repaired", "reverted"}.  (State 3 counts nowhere.)"""
+    to_np = lambda a: np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=np.float64)
+    sample, wall = to_np(sample).reshape(-1, 4), to_np(wall).reshape(-1, 2)
+    state = sample[:, 3]
+    tried, fixed = (state == REPAIR_REPAIRED) | (state == REPAIR_REVERTED), state == REPAIR_REPAIRED
+    with np.errstate(invalid="ignore"):
+        ped, hit = tried & (sample[:, 0] < threshold), tried & (wall[:, 0] - float(wall_radius) < 0)
+    n = lambda m: int(m.sum())
+    return {"pedestrians": n(ped), "walls": n(hit), "both": n(ped & hit), "pedestrians_repaired": n(ped & fixed),
+            "walls_repaired": n(hit & fixed), "both_repaired": n(ped & hit & fixed), "candidates": n(tried), "repaired": n(fixed),
+            "reverted": n(tried & ~fixed)}
 
 
 def _wall_step_distance(a0, a1, b0, b1):

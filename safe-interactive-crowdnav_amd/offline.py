@@ -49,9 +49,12 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     constraints, on either RNG contract and under either sampler, and a sample in which two agents come closer than
     ``collision_threshold`` is pushed apart until the predicate holds or comes back as it was.  Needs positions only; the last three
     values are (the largest iteration count, samples with collisions, samples repaired).  ``repair_options`` = {margin, tau, step,
-    max_iter}.  Not with ``static_obstacles=``: walls are not in the objective."""
+    max_iter}.  Not with ``static_obstacles=``: walls are not in the objective.
+    ``constraint_type="opt_softplus_walls"``: the same with the walls of ``static_obstacles=`` / ``wall_radius=`` (both needed) in the
+    objective and in both gates (``jmid_repair_collisions_walls``): a sample whose paths, the step from p0 included, come closer than
+    ``wall_radius`` to a wall is a candidate too; "with collisions" then reads "not acceptable for either cause"."""
     from .forecaster import repair_arguments, wall_arguments
-    fix = repair_arguments(constraint_type, repair_options, static_obstacles)
+    fix = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
     if fix is not None:
         if not with_constraints:
             raise ValueError("constraint_type needs with_constraints=True")
@@ -60,8 +63,11 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
         pos, number_of_steps, *_ = _sample(engine, num_points, context, sample, bestof, point_dim, flexibility, ret_traj, sampling, step,
                                            precision, _integrate, seed)      # (this function: its own name is taken by an argument)
         B = int(pos.shape[1])
-        out, _, _, episode = engine.repair_collisions(np.ascontiguousarray(pos, dtype=np.float32).reshape(sample, 1, B, num_points, 2),
-                                                      threshold=collision_threshold, **fix)
+        if "walls" in fix:      # every sample an episode: p0 repeats per sample, as in the redraw loop
+            fix = dict(fix, p0=np.ascontiguousarray(np.broadcast_to(np.asarray(_integrate[0], dtype=np.float32)[None], (sample, B, 2))),
+                       dt=float(_integrate[1]))
+        out, _, _, episode, *_ = engine.repair_collisions(np.ascontiguousarray(pos, dtype=np.float32).reshape(sample, 1, B, num_points, 2),
+                                                          threshold=collision_threshold, **fix)
         return (out.reshape(sample, B, num_points, 2), number_of_steps, int(episode[:, 2].max()), int(episode[:, 0].sum()),
                 int(episode[:, 1].sum()))
     walls = wall_arguments(static_obstacles, wall_radius, 1 if with_constraints else 0)
@@ -130,7 +136,8 @@ def generate(engine: JmidEngine, context, p0, dt: float, num_points: int, sample
     output (``JmidEngine.encode``), ``p0`` [B, 2] the current positions.  -> (pos [sample, B, T, 2], steps, 0, 0, 0); with
     ``with_constraints=True`` (see ``sample``) the zeros are (num_iter, samples with collisions, samples fixed); ``static_obstacles`` /
     ``wall_radius`` as there; with ``constraint_type="opt_softplus"`` they are (the largest iteration count, samples with collisions,
-    samples repaired) of the collision repair."""
+    samples repaired) of the collision repair; ``"opt_softplus_walls"`` needs ``static_obstacles`` / ``wall_radius`` and repairs for either
+    cause."""
     pos, nsteps, a, b, c = sample(engine, num_points, context, sample_n, bestof, flexibility=flexibility,
                                   sampling=sampling, step=step, precision=precision, _integrate=(p0, dt), seed=seed,
                                   with_constraints=with_constraints, collision_threshold=collision_threshold, max_rounds=max_rounds,

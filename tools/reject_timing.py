@@ -10,7 +10,7 @@ Every figure is the median over the measured calls after warm-up; the three vari
 interleaved call by call, so clock and thermal drift hit them alike.  Run on the GPU box:
     python tools/reject_timing.py [--precision f16mx] [--calls 40] [--episodes 4]
 --rule RULE measures the wall predicate instead (section 33), --padded the one-loop form on mixed-count batches (section 34), --repair
-collision repair against the redraw loop (section 35)."""
+collision repair against the redraw loop (section 35), --repair --rule RULE collision repair with walls on that rule's frames (section 37)."""
 import argparse
 import json
 import os
@@ -211,13 +211,87 @@ def repair_main(args, weights):
     return out
 
 
+def repair_walls_main(args, weights):
+    """--repair --rule RULE: what collision repair WITH WALLS costs per ``predict_ret_best()`` (docs/NOTEBOOK.md section 37), on the frames
+    of ``crowd_env.simulate_hallway`` under that rule, with the rule's walls at ``--radius``.  Four forecasters in ONE process on the same
+    frames, seeds and draw numbers, alternating call by call:
+      (a) the staged route without a flag                        (b) collision_free_rounds=3 with the walls
+      (c) constraint_type="opt_softplus" (it knows no wall)      (d) constraint_type="opt_softplus_walls"
+    Next to the medians and their p10 - p90: what (b) found and fixed by cause, what (c) repaired, and for (d) the shares repaired and
+    reverted split by cause (``metrics.repair_causes``).  No gate: (d) is read against (a), (b) and (c) of the same run."""
+    from safe_interactive_crowdnav_amd import crowd_env
+    walls = crowd_env.static_obstacles(args.rule)[0]
+    if not len(walls):
+        raise SystemExit(f"rule {args.rule!r} has no walls")
+    out = {"rule": args.rule, "radius": args.radius, "walls": int(len(walls)), "threshold": args.threshold}
+    for point, (N, K, k, H, step) in POINTS.items():
+        sim = crowd_env.simulate_hallway(args.episodes, N, 6 + args.warmup + args.calls, seed=11, cfg=crowd_env.HallwayConfig(rule=args.rule))
+        with tempfile.TemporaryDirectory() as td:
+            env, yp = write_configs(td, joint=True, ctx_dim=256, N=N, K=K, k_ret=k, H=H, step=step, time_step=0.25)
+            common = dict(weights=weights, precision=args.precision, self_check=False, rng_compat="device", seed=7, collision_threshold=args.threshold)
+            obstacles = dict(static_obstacles=walls, wall_radius=args.radius)
+            variants = {"a_staged": Staged(env, yp, **common),
+                        "b_rounds_3_walls": HumanTrajectoryForecasterSim(env, yp, collision_free_rounds=3, **obstacles, **common),
+                        "c_opt_softplus": HumanTrajectoryForecasterSim(env, yp, constraint_type="opt_softplus", **common),
+                        "d_opt_softplus_walls": HumanTrajectoryForecasterSim(env, yp, constraint_type="opt_softplus_walls", **obstacles, **common)}
+        ms = {name: [] for name in variants}
+        redraw, fix, causes, most = np.zeros(4, dtype=np.int64), np.zeros(3, dtype=np.int64), {}, 0
+        for e in range(args.episodes):
+            for f in variants.values():
+                f.prev_states, f.prev_robot_states = [[] for _ in range(N)], []
+            for i in range(6 + args.warmup + args.calls):
+                for f in variants.values():
+                    f.update_state_hists(St(sim["robot_xy"][e, i]), [St(p) for p in sim["human_xy"][e, i]], float(sim["stamps"][i]))
+                if i < 5:
+                    continue
+                order = list(variants.items())
+                order = order[i % 4:] + order[:i % 4]                       # alternate who goes first
+                for name, f in order:
+                    t0 = time.perf_counter()
+                    f.predict_ret_best()
+                    dt = 1e3 * (time.perf_counter() - t0)
+                    if i < 5 + args.warmup:
+                        continue
+                    ms[name].append(dt)
+                    if name.startswith("b"):
+                        redraw += np.array(f.rejection[1:5])
+                    if name.startswith("c"):
+                        fix += np.array(f.repair[:3])
+                    if name.startswith("d"):
+                        causes = {key: causes.get(key, 0) + v for key, v in f.repair_causes.items()}
+                        most = max(most, f.repair[3])
+        n = len(ms["a_staged"])
+        res = {name: {"median_ms": round(float(np.median(v)), 3), "p10_ms": round(float(np.percentile(v, 10)), 3),
+                      "p90_ms": round(float(np.percentile(v, 90)), 3)} for name, v in ms.items()}
+        res["calls"] = n
+        for name in ("b_rounds_3_walls", "c_opt_softplus", "d_opt_softplus_walls"):
+            res[name[0] + "_minus_a_ms"] = round(res[name]["median_ms"] - res["a_staged"]["median_ms"], 3)
+        res["d_minus_c_ms"] = round(res["d_opt_softplus_walls"]["median_ms"] - res["c_opt_softplus"]["median_ms"], 3)
+        share = lambda v: round(float(v) / (n * K), 5)
+        res["b"] = {"samples_flagged": int(redraw[0]), "samples_fixed": int(redraw[1]), "round0_pedestrians": int(redraw[2]), "round0_walls": int(redraw[3]),
+                    "share_flagged": share(redraw[0]), "share_left_flagged": share(redraw[0] - redraw[1])}
+        res["c"] = {"samples_colliding": int(fix[0]), "share_repaired": share(fix[1]), "share_reverted": share(fix[2])}
+        res["d"] = dict(causes, max_iterations=int(most), share_candidates=share(causes["candidates"]), share_repaired=share(causes["repaired"]),
+                        share_reverted=share(causes["reverted"]), share_walls_repaired=share(causes["walls_repaired"]),
+                        share_walls_reverted=share(causes["walls"] - causes["walls_repaired"]),
+                        share_pedestrians_repaired=share(causes["pedestrians_repaired"]),
+                        share_pedestrians_reverted=share(causes["pedestrians"] - causes["pedestrians_repaired"]))
+        res["erange_fallbacks"] = sum(f.erange_fallbacks for f in variants.values())
+        res["workload"] = (f"N={N}, K={K} -> {k}, H={H}, {step} steps, {args.precision}, {args.rule} frames, {args.episodes} episodes, threshold "
+                           f"{args.threshold}, wall radius {args.radius}")
+        out[point] = res
+        print(point, json.dumps(res), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16mx")
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--episodes", type=int, default=4)
-    ap.add_argument("--rule", default=None, help="a hallway rule of crowd_env (hallway_static, rectangle, ...): measure the wall predicate instead")
+    ap.add_argument("--rule", default=None, help="a hallway rule of crowd_env (hallway_static, rectangle, ...): measure the wall predicate instead; with --repair: "
+                    "collision repair with walls on that rule's frames")
     ap.add_argument("--radius", type=float, default=0.3, help="with --rule: the wall radius in metres")
     ap.add_argument("--padded", action="store_true", help="predict_batch on mixed-count scenes: one loop per count against collision_free_padded")
     ap.add_argument("--repair", action="store_true", help="collision repair (constraint_type='opt_softplus') against collision_free_rounds=3 and no flag")
@@ -227,7 +301,10 @@ def main():
     if args.rule or args.padded or args.repair:
         if args.padded and "--episodes" not in sys.argv:
             args.episodes = 8
-        out = repair_main(args, weights) if args.repair else padded_main(args, weights) if args.padded else walls_main(args, weights)
+        if args.repair and args.rule:
+            out = repair_walls_main(args, weights)
+        else:
+            out = repair_main(args, weights) if args.repair else padded_main(args, weights) if args.padded else walls_main(args, weights)
         try:
             import bench
             out["sustained_mfma"] = bench.sustained_mfma_tflops()
