@@ -81,6 +81,7 @@ import configparser
 import os
 import time
 import warnings
+from functools import partial
 from threading import Lock, RLock
 from typing import Dict, NamedTuple, Optional, Tuple
 
@@ -92,6 +93,7 @@ from . import scene as SC
 from ._lib import EINVAL, ERANGE
 from .engine import JmidEngine, JmidError, wall_segments
 from .kde import most_likely_samples
+from .metrics import rejection_totals, repair_causes
 from .weights import JMIDWeights, NetDims
 
 _ENGINE_CACHE: Dict[tuple, JmidEngine] = {}
@@ -180,28 +182,53 @@ def repair_totals(episode) -> Tuple[int, int, int, int]:
     return int(ep[:, 0].sum()), int(ep[:, 1].sum()), int(ep[:, 0].sum() - ep[:, 1].sum()), int(ep[:, 2].max())
 
 
+class Constraints(NamedTuple):
+    """The sampling constraints of one call as data: everything the constraint keywords of the forecaster, ``predict_batch`` and
+    ``offline.sample`` decide, decided once (``sampling_constraints``).  The callers read the fields and never the keywords."""
+    rounds: Optional[int] = None      # the redraw loop (JmidEngine.denoise_reject) and its max_rounds; None: no loop
+    threshold: float = 0.2            # the pedestrian predicate's distance, of the loop and of the repair
+    walls: dict = {}                  # the loop's {walls, wall_radius} keywords, or {}
+    repair: Optional[dict] = None     # the repair stage (JmidEngine.repair_collisions) and its keywords, the walls of "opt_softplus_walls" among them; None: no stage
+    padded: bool = False              # predict_batch: ONE loop for the whole padded batch instead of one per count group
+
+
+def sampling_constraints(rounds: Optional[int] = None, threshold: float = 0.2, static_obstacles=None, wall_radius=None,
+                         constraint_type: Optional[str] = None, repair_options: Optional[dict] = None, padded: bool = False) -> Constraints:
+    """``Constraints`` from the public keywords, with every refusal that is about them: ``rounds`` is ``collision_free_rounds`` where it is
+    > 0 (``offline.sample``: ``max_rounds`` under ``with_constraints=True``) and None otherwise, ``threshold`` is ``collision_threshold``,
+    ``padded`` is ``collision_free_padded``.  What a caller refuses itself is what only it knows: its RNG contract, ``padded=``, the
+    sampler's ``bestof`` / ``sampling``."""
+    if rounds is not None and not 0 <= int(rounds) <= 64:
+        raise ValueError("collision_free_rounds must lie in 0..64")
+    threshold = float(threshold)
+    if not (np.isfinite(threshold) and threshold >= 0.0):
+        raise ValueError("collision_threshold must be finite and >= 0")
+    repair = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
+    walls = wall_arguments(static_obstacles, wall_radius, int(rounds is not None), repair is not None and "walls" in repair)
+    if padded and rounds is None:
+        raise ValueError("collision_free_padded needs collision_free_rounds > 0")
+    return Constraints(None if rounds is None else int(rounds), threshold, walls, repair, bool(padded))
+
+
 def repair_stage(engine: JmidEngine, pos, dims: Tuple[int, int, int, int], threshold: float, options: dict, n_agents=None, p0=None,
-                 dt: Optional[float] = None, causes: Optional[list] = None):
+                 dt: Optional[float] = None):
     """The repair stage of a staged route behind a denoise (or rejection) call of ``dims`` = (E, A, K, H): ``pos`` [E, K, A, H, 2], or None
     when the samples stayed on the device - they are then repaired where they lie and the ranking reads them there.
-    -> (pos repaired, or None; episode [E, 3]).  With walls among the ``options`` (``"opt_softplus_walls"``) the call's ``p0`` [E, A, 2] and
-    ``dt`` go along - the step from the present position is part of the wall predicate, as in the redraw loop - and ``causes``, a list,
-    receives ``metrics.repair_causes`` of the call."""
+    -> (pos repaired, or None; episode [E, 3]; ``metrics.repair_causes`` of the call, or None without walls).  With walls among the
+    ``options`` (``"opt_softplus_walls"``) the call's ``p0`` [E, A, 2] and ``dt`` go along - the step from the present position is part of
+    the wall predicate, as in the redraw loop."""
+    where = dict(dims=dims if pos is None else None, n_agents=n_agents)
     if "walls" not in options:
-        out, _, _, episode = engine.repair_collisions(pos, threshold=threshold, dims=dims if pos is None else None, n_agents=n_agents, **options)
-        return out, episode
-    from .metrics import repair_causes
+        out = engine.repair_collisions(pos, threshold=threshold, **where, **options)
+        return out[0], out[3], None
     on_device = pos is not None and torch.is_tensor(pos) and pos.is_cuda
     # p0 goes where pos lives (pos None: the resident set, host arrays out)
     if on_device:
         p0 = (p0 if torch.is_tensor(p0) else torch.from_numpy(np.ascontiguousarray(p0, dtype=np.float32))).to(pos.device, torch.float32).contiguous()
     else:
         p0 = np.ascontiguousarray(p0.detach().cpu().numpy() if torch.is_tensor(p0) else p0, dtype=np.float32)
-    out, _, sample, episode, wall = engine.repair_collisions(pos, threshold=threshold, dims=dims if pos is None else None, n_agents=n_agents,
-                                                             p0=p0, dt=float(dt), **options)
-    if causes is not None:
-        causes.append(repair_causes(sample, wall, threshold, options["wall_radius"]))
-    return out, episode
+    out = engine.repair_collisions(pos, threshold=threshold, **where, p0=p0, dt=float(dt), **options)      # (a fifth value: wall)
+    return out[0], out[3], repair_causes(out[2], out[4], threshold, options["wall_radius"])
 
 
 def advance_cuda_generator(device_id: int, shape: Tuple[int, ...], n: int) -> None:
@@ -355,17 +382,17 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         if rng_compat not in ("auto", "cpu", "cuda", "device"):
             raise ValueError("rng_compat must be 'auto', 'cpu', 'cuda' or 'device'")
         # rng_compat="device": the address of this instance's noise (seed, episode id) and the draw number its next call starts at
-        self.noise_seed, self.episode_id, self._noise_draw = int(seed), int(episode_id), 0
+        # (_draw0: the draw number the last call's redraw loop started at)
+        self.noise_seed, self.episode_id, self._noise_draw, self._draw0 = int(seed), int(episode_id), 0, 0
         self.rng_compat = rng_compat if rng_compat != "auto" else ("cuda" if torch.cuda.is_available() else "cpu")
         # > 0 (opt-in, needs rng_compat="device": a redraw is a draw number of the counter generator): collision-free sampling, up to that
         # many reruns of a scene whose joint samples collide at collision_threshold metres; rejection: the last call's totals
         self.collision_free_rounds, self.collision_threshold = int(collision_free_rounds), float(collision_threshold)
-        if not 0 <= self.collision_free_rounds <= 64:
-            raise ValueError("collision_free_rounds must lie in 0..64")
-        if self.collision_free_rounds and self.rng_compat != "device":
+        self.constraints = sampling_constraints(self.collision_free_rounds or None, collision_threshold, static_obstacles, wall_radius,
+                                                constraint_type, repair_options)
+        self._walls, self._repair_options = self.constraints.walls, self.constraints.repair      # (read by tests/)
+        if self.constraints.rounds is not None and self.rng_compat != "device":
             raise ValueError("collision_free_rounds needs rng_compat='device' (a redraw is a draw number of the library's counter generator)")
-        if not (np.isfinite(self.collision_threshold) and self.collision_threshold >= 0.0):
-            raise ValueError("collision_threshold must be finite and >= 0")
         # static_obstacles + wall_radius (opt-in, with collision_free_rounds > 0): the wall predicate joins the pedestrian one, and
         # rejection holds five counts (the three, then the samples that fail the pedestrian predicate, the wall predicate)
         # constraint_type="opt_softplus" (opt-in, every RNG contract): collision repair behind the denoise stage (and behind the redraw
@@ -373,10 +400,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # constraint_type="opt_softplus_walls": the same stage with the walls in the objective and in both gates (needs static_obstacles +
         # wall_radius, with or without a redraw loop); repair_causes: the last call's candidates split by cause (metrics.repair_causes)
         self.constraint_type = constraint_type
-        self._repair_options = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
         self.repair: Optional[Tuple[int, int, int, int]] = None
         self.repair_causes: Optional[Dict[str, int]] = None
-        self._walls = wall_arguments(static_obstacles, wall_radius, self.collision_free_rounds, constraint_type == "opt_softplus_walls")
         self.rejection: Optional[Tuple[int, ...]] = None
         self._init_MID(mid_config_file, weights, device_id, lib_path)
 
@@ -416,73 +441,32 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         with self.prev_states_lock:           # mid_sim_wrapper.py:251-258
             return [list(map(list, h)) for h in self.prev_states], list(map(list, self.prev_robot_states))
 
-    def _denoise(self, x_T, ctx, p0, want_pos=True):
-        """One denoise call in ``self.precision``; JMID_ERANGE -> the same call in exact fp32 (counted, warned about once)."""
-        pos, fell_back = denoise_with_fallback(self.engine, x_T, ctx, p0, self.time_step, self.precision, want_pos)
-        if fell_back:
-            if not self.erange_fallbacks:
-                warnings.warn("JMID_ERANGE: an activation left the fp16 range; the call was repeated in the exact-fp32 mode "
-                              "(same result, ~5x the latency).  Construct the forecaster with precision='f32' if this "
-                              "checkpoint does it often.", RuntimeWarning, stacklevel=3)
-            self.erange_fallbacks += 1
-        return pos
+    def _first_call_check(self, key, nan_downgrades: bool, stage, pos, rejection):
+        """First call per shape (``key``) in an opt-in mode: the call's denoise stage (``denoise_stage``) once more in "f16x3" on the same
+        inputs - a redraw loop from the same draw0 - and the downgrade when the two disagree.  -> the (pos, rejection) to use: those of
+        the run that produced the positions.  ``nan_downgrades``: whether a NaN delta downgrades as well (behind a redraw loop it does,
+        behind a plain denoise call it does not: docs/NOTEBOOK.md)."""
+        global SELF_CHECK_DOWNGRADES
+        self._checked_shapes.add(key)
+        (ref, ref_rejection), _ = repeat_in_fp32(lambda p: stage(p, True), "f16x3")
+        with np.errstate(invalid="ignore"):
+            delta = float(np.linalg.norm(pos - ref, axis=-1).mean())
+        self.self_check_delta = delta
+        if delta > self.self_check_tol or (nan_downgrades and np.isnan(delta)):
+            warnings.warn(f"precision={self.precision!r} differs from 'f16x3' by {delta:.2e} m mean displacement on this "
+                          f"checkpoint (> {self.self_check_tol:.1e}): this forecaster now runs 'f16x3'", RuntimeWarning,
+                          stacklevel=4)
+            self.precision, self.self_check = "f16x3", False
+            SELF_CHECK_DOWNGRADES += 1
+            return ref, ref_rejection
+        return pos, rejection
 
     def _self_check(self, x_T, ctx, p0, pos):
-        """First call per shape in an opt-in mode: the same inputs once more in "f16x3"; downgrade when they disagree."""
-        global SELF_CHECK_DOWNGRADES
+        """``_first_call_check`` of a plain denoise call on given inputs and positions -> the positions to use."""
         key = tuple(x_T.shape)
         if key in self._checked_shapes:
             return pos
-        self._checked_shapes.add(key)
-        ref, _ = denoise_with_fallback(self.engine, x_T, ctx, p0, self.time_step, "f16x3")
-        delta = float(np.linalg.norm(pos - ref, axis=-1).mean())
-        self.self_check_delta = delta
-        if delta > self.self_check_tol:
-            warnings.warn(f"precision={self.precision!r} differs from 'f16x3' by {delta:.2e} m mean displacement on this "
-                          f"checkpoint (> {self.self_check_tol:.1e}): this forecaster now runs 'f16x3'", RuntimeWarning,
-                          stacklevel=3)
-            self.precision, self.self_check = "f16x3", False
-            SELF_CHECK_DOWNGRADES += 1
-            return ref
-        return pos
-
-    def _denoise_reject(self, ctx, p0, check, want_pos=True):
-        """The denoise stage with ``collision_free_rounds``: ``engine.denoise_reject`` from this call's draw0 in ``self.precision``
-        (JMID_ERANGE: the whole call again in exact fp32, counted and warned about like ``_denoise``); ``check``: the first-call self
-        check - the same call, the same draws, once more in "f16x3", and the downgrade when the two disagree.  ``self.rejection`` <- the
-        totals of the call whose positions are used.  -> pos [1, K, A, H, 2], or None when they stay on the device."""
-        from .metrics import rejection_totals
-        A, K, H = int(ctx.shape[1]), self.num_samples, self.predict_horizon
-
-        def run(precision, pos_back):
-            out, fell_back = repeat_in_fp32(lambda p: self.engine.denoise_reject(
-                ctx, p0, self.noise_seed, [self.episode_id], K, H, dt=self.time_step, precision=p, threshold=self.collision_threshold,
-                max_rounds=self.collision_free_rounds, draw0=self._draw0, want_vel=False, want_pos=pos_back, **self._walls), precision)
-            return out[1], out[3:], fell_back            # (out[3:]: episodes, and with walls the causes)
-
-        pos, episodes, fell_back = run(self.precision, want_pos or check)
-        if fell_back:
-            if not self.erange_fallbacks:
-                warnings.warn("JMID_ERANGE: an activation left the fp16 range; the call was repeated in the exact-fp32 mode "
-                              "(same result, ~5x the latency).  Construct the forecaster with precision='f32' if this "
-                              "checkpoint does it often.", RuntimeWarning, stacklevel=3)
-            self.erange_fallbacks += 1
-        if check:
-            global SELF_CHECK_DOWNGRADES
-            self._checked_shapes.add((1, K * A, H, 2))
-            ref, ref_episodes, _ = run("f16x3", True)      # (the accepted set now resident is this call's: route.rank is "device" under check)
-            with np.errstate(invalid="ignore"):
-                delta = float(np.linalg.norm(pos - ref, axis=-1).mean())
-            self.self_check_delta = delta
-            if not delta <= self.self_check_tol:
-                warnings.warn(f"precision={self.precision!r} differs from 'f16x3' by {delta:.2e} m mean displacement on this "
-                              f"checkpoint (> {self.self_check_tol:.1e}): this forecaster now runs 'f16x3'", RuntimeWarning,
-                              stacklevel=3)
-                self.precision, self.self_check = "f16x3", False
-                SELF_CHECK_DOWNGRADES += 1
-                pos, episodes = ref, ref_episodes
-        self.rejection = rejection_totals(*episodes)
-        return pos if want_pos or check else None
+        return self._first_call_check(key, False, denoise_stage(self.engine, ctx, p0, Constraints(), self.time_step, x_T), pos, None)[0]
 
     def get_most_likely_samples(self, forecasts):
         """mid_sim_wrapper.py:440-441: the ``num_ret_samples`` most likely of the sampled joint futures under the per-step
@@ -631,14 +615,13 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         """Snapshot -> scene -> noise -> route -> run (ONE chained library entry, or encode / denoise / rank) -> assembly -> timings."""
         t0 = time.perf_counter()
         source, ids_in, cv, pose_now, sb, ff, present = self._scene(*self._snapshot())
-        A, K, H, k = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples
+        A, K, H, k, limits = len(ids_in), self.num_samples, self.predict_horizon, self.num_ret_samples, self.constraints
         x_np = self._draw_x_T(A)             # after the scene: a call that raises HistoryTooShortError has drawn nothing
         t1 = time.perf_counter()
         check = self.self_check and (1, K * A, H, 2) not in self._checked_shapes
         route = plan_route(k=k, K=K, A=A, H=H, device_topk=self.device_topk, device_scene=self.device_scene,
                            device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped",
-                           tracks=present is not None, collision_free=self.collision_free_rounds > 0,
-                           repair=self._repair_options is not None)
+                           tracks=present is not None, collision_free=limits.rounds is not None, repair=limits.repair is not None)
         result, call = None, dict(dt=self.time_step, precision=self.precision)
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
@@ -661,19 +644,22 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                 if pose_now is None:
                     pose_now = self.engine.scene_frames()["pose_now"]
                 ctx = self.engine.encode(x_st, nbr_sum, edge_mask, first_index=first_index)
-                if self.collision_free_rounds:
-                    pos = self._denoise_reject(ctx[None], p0[None], check, want_pos=route.rank != "device_resident")
-                else:
-                    pos = self._denoise(x_np, ctx[None], p0[None], want_pos=route.rank != "device_resident")
-                    if check:        # first call of this shape in an opt-in mode: pos is the result to use (possibly f16x3's)
-                        pos = self._self_check(x_np, ctx[None], p0[None], pos)
-                if self._repair_options is not None:      # on the set the stage above left: in place on the device, or on the host copy
-                    causes = []
-                    pos, episode = repair_stage(self.engine, pos, (1, A, K, H), self.collision_threshold, self._repair_options, p0=p0[None],
-                                                dt=self.time_step, causes=causes)
-                    self.repair, self.repair_causes = repair_totals(episode), causes[0] if causes else None
-                t2 = time.perf_counter()
-                rows, logw = rank_samples(self.engine, route.rank, pos, k, (1, A, K, H))
+                # (x_np None: a redraw loop draws inside the entry, from the draw number _draw_x_T reserved)
+                seeded = dict(seed=self.noise_seed, episode_ids=[self.episode_id], K=K, T=H) if x_np is None else None
+                out = run_staged(self.engine, ctx[None], p0[None], (1, A, K, H), limits, route.rank, k, self.time_step, self.precision,
+                                 x_T=x_np, seeded=seeded, draw0=self._draw0,
+                                 self_check=partial(self._first_call_check, (1, K * A, H, 2), limits.rounds is not None) if check else None)
+                if out.fell_back:
+                    if not self.erange_fallbacks:
+                        warnings.warn("JMID_ERANGE: an activation left the fp16 range; the call was repeated in the exact-fp32 mode "
+                                      "(same result, ~5x the latency).  Construct the forecaster with precision='f32' if this "
+                                      "checkpoint does it often.", RuntimeWarning, stacklevel=2)
+                    self.erange_fallbacks += 1
+                if out.rejection is not None:
+                    self.rejection = rejection_totals(out.rejection.episodes, out.rejection.cause)
+                if out.repair is not None:
+                    self.repair, self.repair_causes = repair_totals(out.repair), out.repair_causes
+                rows, logw, t2 = out.rows, out.logw, out.rank_started
         t3 = time.perf_counter()
         if result is None:
             in_cluster = np.zeros(self.num_hums if present is None else int(present.sum()), dtype=bool)
@@ -774,22 +760,72 @@ def repeat_in_fp32(call, precision: str):
     return call("f32"), True
 
 
-def denoise_with_fallback(engine: JmidEngine, x_T, ctx, p0, dt: float, precision: str, want_pos: bool = True, **seeded):
-    """``engine.denoise`` -> positions under ``repeat_in_fp32``.  -> (pos, fell_back).
-    ``seeded``: the seed / episode_ids / K / T keywords of a seeded call (x_T None): the repeat draws the same noise."""
-    return repeat_in_fp32(lambda p: engine.denoise(x_T, ctx, p0, dt=dt, precision=p, want_vel=False, want_pos=want_pos, **seeded)[1],
-                          precision)
-
-
-def rank_samples(engine: JmidEngine, rank: str, pos, k: int, dims: Tuple[int, int, int, int]):
+def rank_samples(engine: JmidEngine, rank: str, pos, k: int, dims: Tuple[int, int, int, int], n_agents=None):
     """The ranking stage (``Route.rank``) after a denoise call of ``dims`` = (E, A, K, H), ``pos`` [E, K, A, H, 2] or None (left on the device)
-    -> what ``scene.assemble_forecasts`` takes: (kept [E, A, k, H, 2], log-weights [E, A, k]), or (pos, None) when all K are returned."""
+    -> what ``scene.assemble_forecasts`` takes: (kept [E, A, k, H, 2], log-weights [E, A, k]), or (pos, None) when all K are returned.
+    ``n_agents`` [E]: a padded batch - every episode is ranked over its real agents, the rows of the padded ones are NaN."""
     if rank == "none":
         return pos, None
     if rank == "host":
-        parts = [most_likely_samples(p, k) for p in pos]
-        return np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts])
-    return engine.topk(pos if rank == "device" else None, k, dims=dims)
+        E, A, _, H = dims
+        sel, lw = np.full((E, A, k, H, 2), np.nan, dtype=np.float32), np.full((E, A, k), np.nan, dtype=np.float32)
+        for e, n in enumerate([A] * E if n_agents is None else n_agents):
+            sel[e, :n], lw[e, :n] = most_likely_samples(np.ascontiguousarray(pos[e][:, :n]), k)
+        return sel, lw
+    padded = {} if n_agents is None else {"n_agents": n_agents}      # (the call without counts is the one it always was)
+    return engine.topk(pos if rank == "device" else None, k, dims=dims, **padded)
+
+
+class Rejection(NamedTuple):
+    """What a redraw loop (``JmidEngine.denoise_reject``) reports next to its samples."""
+    slots: np.ndarray                  # [E, K, 3] int32
+    episodes: np.ndarray               # [E, 3] int32
+    cause: Optional[np.ndarray]        # [E, 2] int32 of a loop with walls or with counts, else None
+
+
+class Staged(NamedTuple):
+    """What ``run_staged`` returns."""
+    rows: np.ndarray                   # what ``scene.assemble_forecasts`` takes (``rank_samples``)
+    logw: Optional[np.ndarray]
+    rejection: Optional[Rejection]     # of the loop whose samples were used; None: no loop
+    repair: Optional[np.ndarray]       # the repair's episode rows [E, 3] (``repair_totals``); None: no repair stage
+    repair_causes: Optional[dict]      # ``metrics.repair_causes`` of a repair with walls
+    fell_back: bool                    # JMID_ERANGE: the denoise stage was repeated in exact fp32
+    rank_started: float                # ``time.perf_counter()`` between the repair and the ranking (the forecaster's timings split there)
+
+
+def denoise_stage(engine: JmidEngine, ctx, p0, constraints: Constraints, dt: float, x_T=None, seeded: Optional[dict] = None, draw0: int = 0,
+                  n_agents=None):
+    """The denoise stage of a staged run as a callable (precision, want_pos) -> (pos [E, K, A, H, 2] or None when the samples stay on the
+    device, ``Rejection`` or None): the redraw loop from ``draw0`` when the constraints ask for one, else one denoise call.  Either
+    ``x_T`` or ``seeded``, the seed / episode_ids / K / T keywords of a seeded call (a repeat then draws the same noise)."""
+    seeded = seeded or {}
+
+    def stage(precision: str, want_pos: bool):
+        if constraints.rounds is None:
+            return engine.denoise(x_T, ctx, p0, dt=dt, precision=precision, want_vel=False, want_pos=want_pos, **seeded)[1], None
+        out = engine.denoise_reject(ctx, p0, dt=dt, precision=precision, threshold=constraints.threshold, max_rounds=constraints.rounds,
+                                    draw0=draw0, want_vel=False, want_pos=want_pos, n_agents=n_agents, **constraints.walls, **seeded)
+        return out[1], Rejection(out[2], out[3], out[4] if len(out) > 4 else None)      # (the engine gives four values, or five)
+    return stage
+
+
+def run_staged(engine: JmidEngine, ctx, p0, dims: Tuple[int, int, int, int], constraints: Constraints, rank: str, k: int, dt: float,
+               precision: str, x_T=None, seeded: Optional[dict] = None, draw0: int = 0, n_agents=None, self_check=None) -> Staged:
+    """The staged run behind ``encode``, for every caller: ctx [E, A, ctx_dim], p0 [E, A, 2], ``dims`` = (E, A, K, H) -> the denoise stage
+    (``denoise_stage``) under ``repeat_in_fp32``, the repair stage when the constraints hold one, the ranking (``Route.rank``; k of K).
+    The samples come back from the device only when the ranking needs them there.  ``n_agents`` [E]: a padded batch.
+    ``self_check`` (stage, pos, rejection) -> (pos, rejection): the forecaster's first-call check, given the stage to run again."""
+    stage = denoise_stage(engine, ctx, p0, constraints, dt, x_T, seeded, draw0, n_agents)
+    (pos, rejection), fell_back = repeat_in_fp32(lambda p: stage(p, rank != "device_resident"), precision)
+    if self_check is not None:
+        pos, rejection = self_check(stage, pos, rejection)
+    episode = causes = None
+    if constraints.repair is not None:      # on the set the stage above left: in place on the device, or on the host copy
+        pos, episode, causes = repair_stage(engine, pos, dims, constraints.threshold, constraints.repair, n_agents=n_agents, p0=p0, dt=dt)
+    rank_started = time.perf_counter()
+    rows, logw = rank_samples(engine, rank, pos, k, dims, n_agents)
+    return Staged(rows, logw, rejection, episode, causes, fell_back, rank_started)
 
 
 def _engine_lock_of(engine: JmidEngine) -> RLock:
@@ -873,20 +909,13 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         raise ValueError("noise must be 'torch' or 'device'")
     if padded not in (False, True, "resident"):
         raise ValueError("padded must be False, True or 'resident'")
-    R = int(collision_free_rounds)
-    fix = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
-    walls = wall_arguments(static_obstacles, wall_radius, R, constraint_type == "opt_softplus_walls")
-    causes = [] if fix is not None and "walls" in fix else None      # metrics.repair_causes of every repair call
-    if R:
+    limits = sampling_constraints(int(collision_free_rounds) or None, collision_threshold, static_obstacles, wall_radius, constraint_type,
+                                  repair_options, collision_free_padded)
+    if limits.rounds is not None:
         if padded:
             raise ValueError("collision_free_rounds has no padded form (jmid_denoise_reject_seeded takes one agent count per call)")
         if noise != "device":
             raise ValueError("collision_free_rounds needs noise='device' (a redraw is a draw number of the library's counter generator)")
-    if collision_free_padded:
-        if padded:
-            raise ValueError("collision_free_padded is the padded form of collision_free_rounds: not with padded=")
-        if not R:
-            raise ValueError("collision_free_padded needs collision_free_rounds > 0")
     resident = isinstance(padded, str)
     if resident:
         padded, device_frames = False, True       # (what it falls back to: the grouped device path)
@@ -914,7 +943,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
 
     def plan(A, padded=False, resident=False):
         return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
-                          short=ff is not None, batch=True, padded=padded, resident=resident, collision_free=R > 0, repair=fix is not None)
+                          short=ff is not None, batch=True, padded=padded, resident=resident, collision_free=limits.rounds is not None,
+                          repair=limits.repair is not None)
 
     def torch_x_T(e, A):
         return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
@@ -949,51 +979,39 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         with lock:
             (rows, lw), _ = repeat_in_fp32(lambda p: engine.predict_padded(*args, dt=time_step, precision=p), precision)
         return (*SC.assemble_forecasts(inc, rows, lw, b["cv"], pose_now, k, K, n_agents=n_in), inc)
-    if collision_free_padded and n_in.min() >= 1:
+    if limits.padded and n_in.min() >= 1:
         # the staged route on the whole batch: padded inputs, one encode, one rejection loop, one ranking of the accepted set
         A = int(n_in.max())
-        route = plan(A)
         if "p0" not in b:           # (device_frames built without reading the encoder inputs back)
             with lock:
                 engine.build_scene(human_xy, robot_xy, time_step, horizon=H, first_frame=ff, **ab)
                 b.update(engine.scene_arrays())
         counts = n_in.astype(np.int32)
-        p0 = SC.pad_agents(b["p0"], inc, A)
         with lock:
             ctx = engine.encode(SC.pad_agents(b["x_st"], inc, A).reshape(E * A, F, 6), SC.pad_agents(b["nbr_sum"], inc, A).reshape(E * A, 2, F, 6),
                                 SC.pad_agents(b["edge_mask"], inc, A).reshape(E * A, 2),
                                 first_index=None if ff is None else SC.pad_agents(b["first_index"], inc, A).reshape(-1)).reshape(E, A, -1)
-            (_, pos, slots, episodes, cause), _ = repeat_in_fp32(lambda p: engine.denoise_reject(
-                ctx, p0, seed=int(seed), episode_ids=np.asarray(seeds), K=K, T=H, dt=time_step, precision=p, threshold=collision_threshold,
-                max_rounds=R, draw0=0, want_vel=False, want_pos=route.rank != "device_resident", n_agents=counts, **walls), precision)
-            if fix is not None:
-                pos, fixed = repair_stage(engine, pos, (E, A, K, H), collision_threshold, fix, n_agents=counts, p0=p0, dt=time_step, causes=causes)
-                if stats is not None:
-                    stats["repair"] = fixed
-                    if causes:
-                        stats["repair_causes"] = causes[0]
-            if route.rank == "host":        # (beyond the device top-k's limits: the host twin on every episode's real agents)
-                sel, lw = np.full((E, A, k, H, 2), np.nan, dtype=np.float32), np.full((E, A, k), np.nan, dtype=np.float32)
-                for e in range(E):
-                    sel[e, :counts[e]], lw[e, :counts[e]] = most_likely_samples(np.ascontiguousarray(pos[e][:, :counts[e]]), k)
-            elif route.rank == "none":
-                sel, lw = pos, None
-            else:
-                sel, lw = engine.topk(pos if route.rank == "device" else None, k, dims=(E, A, K, H), n_agents=counts)
+            out = run_staged(engine, ctx, SC.pad_agents(b["p0"], inc, A), (E, A, K, H), limits, plan(A).rank, k, time_step, precision,
+                             seeded=dict(seed=int(seed), episode_ids=np.asarray(seeds), K=K, T=H), n_agents=counts)
         if stats is not None:
-            stats["episodes"], stats["slots"], stats["cause"] = episodes, slots, cause
-        forecasts, logw = SC.assemble_forecasts(inc, sel, lw, b["cv"], pose_now, k, K, n_agents=counts)
+            stats["episodes"], stats["slots"], stats["cause"] = out.rejection.episodes, out.rejection.slots, out.rejection.cause
+            if out.repair is not None:
+                stats["repair"] = out.repair
+            if out.repair_causes is not None:
+                stats["repair_causes"] = out.repair_causes
+        forecasts, logw = SC.assemble_forecasts(inc, out.rows, out.logw, b["cv"], pose_now, k, K, n_agents=counts)
         if absent:
             forecasts[left_out], logw[left_out] = np.nan, np.nan
         return forecasts, logw, inc
     forecasts = np.empty((E, N, k, H + 1, 2), dtype=np.float64)
     logw = np.empty((E, N, k), dtype=np.float64)
-    if fix is not None and stats is not None:
+    if limits.repair is not None and stats is not None:
         stats["repair"] = np.zeros((E, 3), dtype=np.int32)
-    if R and stats is not None:
+    if limits.rounds is not None and stats is not None:
         stats["episodes"], stats["slots"] = np.zeros((E, 3), dtype=np.int32), np.zeros((E, K, 3), dtype=np.int32)
-        if walls:
+        if limits.walls:
             stats["cause"] = np.zeros((E, 2), dtype=np.int32)
+    causes = []                                 # metrics.repair_causes of every group's repair with walls
     for A in np.unique(n_in):                   # episodes with the same count share their device calls
         eps = np.nonzero(n_in == A)[0]
         A = int(A)
@@ -1019,22 +1037,18 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             ctx = engine.encode(b["x_st"][ei, rows].reshape(n, F, 6), b["nbr_sum"][ei, rows].reshape(n, 2, F, 6),
                                 b["edge_mask"][ei, rows].reshape(n, 2),
                                 first_index=None if ff is None else b["first_index"][ei, rows].reshape(-1)).reshape(len(eps), A, -1)
-            if R and A:
-                (_, pos, slots, episodes, *cause), _ = repeat_in_fp32(lambda p: engine.denoise_reject(
-                    ctx, p0, dt=time_step, precision=p, threshold=collision_threshold, max_rounds=R, want_vel=False,
-                    want_pos=route.rank != "device_resident", **walls, **nz), precision)
-                if stats is not None:
-                    stats["episodes"][eps], stats["slots"][eps] = episodes, slots
-                    if cause:
-                        stats["cause"][eps] = cause[0]
-            else:
-                pos, _ = denoise_with_fallback(engine, x_T, ctx, p0, time_step, precision, want_pos=route.rank != "device_resident", **nz)
-            if fix is not None and A:
-                pos, fixed = repair_stage(engine, pos, (len(eps), A, K, H), collision_threshold, fix, p0=p0, dt=time_step, causes=causes)
-                if stats is not None:
-                    stats["repair"][eps] = fixed
-            sel, lw = rank_samples(engine, route.rank, pos, k, (len(eps), A, K, H))
-        forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], sel, lw, b["cv"][eps], pose_now[eps], k, K)
+            # (an empty cluster: no loop and no repair - its stats rows stay zero)
+            out = run_staged(engine, ctx, p0, (len(eps), A, K, H), limits if A else Constraints(), route.rank, k, time_step, precision,
+                             x_T=x_T, seeded=nz)
+        if out.rejection is not None and stats is not None:
+            stats["episodes"][eps], stats["slots"][eps] = out.rejection.episodes, out.rejection.slots
+            if out.rejection.cause is not None:
+                stats["cause"][eps] = out.rejection.cause
+        if out.repair is not None and stats is not None:
+            stats["repair"][eps] = out.repair
+        if out.repair_causes is not None:
+            causes.append(out.repair_causes)
+        forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], out.rows, out.logw, b["cv"][eps], pose_now[eps], k, K)
     if causes and stats is not None:            # the groups' counts, summed
         stats["repair_causes"] = {key: sum(c[key] for c in causes) for key in causes[0]}
     if absent:

@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from .engine import JmidEngine
+from .forecaster import denoise_stage, repair_stage, sampling_constraints
+from .metrics import rejection_totals
 
 
 def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bool, point_dim: int = 2,
@@ -53,25 +55,14 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     ``constraint_type="opt_softplus_walls"``: the same with the walls of ``static_obstacles=`` / ``wall_radius=`` (both needed) in the
     objective and in both gates (``jmid_repair_collisions_walls``): a sample whose paths, the step from p0 included, come closer than
     ``wall_radius`` to a wall is a candidate too; "with collisions" then reads "not acceptable for either cause"."""
-    from .forecaster import repair_arguments, wall_arguments
-    fix = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
-    if fix is not None:
-        if not with_constraints:
-            raise ValueError("constraint_type needs with_constraints=True")
-        if _integrate is None:
-            raise ValueError("with_constraints=True needs positions (generate, or _integrate)")
-        pos, number_of_steps, *_ = _sample(engine, num_points, context, sample, bestof, point_dim, flexibility, ret_traj, sampling, step,
-                                           precision, _integrate, seed)      # (this function: its own name is taken by an argument)
-        B = int(pos.shape[1])
-        if "walls" in fix:      # every sample an episode: p0 repeats per sample, as in the redraw loop
-            fix = dict(fix, p0=np.ascontiguousarray(np.broadcast_to(np.asarray(_integrate[0], dtype=np.float32)[None], (sample, B, 2))),
-                       dt=float(_integrate[1]))
-        out, _, _, episode, *_ = engine.repair_collisions(np.ascontiguousarray(pos, dtype=np.float32).reshape(sample, 1, B, num_points, 2),
-                                                          threshold=collision_threshold, **fix)
-        return (out.reshape(sample, B, num_points, 2), number_of_steps, int(episode[:, 2].max()), int(episode[:, 0].sum()),
-                int(episode[:, 1].sum()))
-    walls = wall_arguments(static_obstacles, wall_radius, 1 if with_constraints else 0)
-    if with_constraints:
+    limits = sampling_constraints(max_rounds if with_constraints else None, collision_threshold, static_obstacles, wall_radius, constraint_type,
+                                  repair_options)
+    redraw = with_constraints and limits.repair is None      # (here the repair stands in for the redraws; in the forecaster it follows them)
+    if limits.repair is not None and not with_constraints:
+        raise ValueError("constraint_type needs with_constraints=True")
+    if limits.repair is not None and _integrate is None:
+        raise ValueError("with_constraints=True needs positions (generate, or _integrate)")
+    if redraw:
         missing = [w for w, ok in (("seed=", seed is not None), ("bestof=True", bool(bestof)), ('sampling="ddim"', sampling == "ddim"),
                                    ("positions (generate, or _integrate)", _integrate is not None)) if not ok]
         if missing:
@@ -89,42 +80,34 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     if seed is not None:
         if not bestof:
             raise ValueError("seed= needs bestof=True: the seeded entry draws x_T (bestof=False starts from zeros)")
-        ctx_e = ctx.unsqueeze(0).expand(sample, B, ctx.shape[1]).contiguous().numpy()
-        nz = dict(seed=int(seed), episode_ids=np.arange(sample, dtype=np.uint32), K=1, T=int(num_points))
-        number_of_steps = sample * (engine.schedule.num_steps // stride + 1)
-        if _integrate is not None:
-            p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(_integrate[0], dtype=np.float32)[None], (sample, B, 2)))
-            if with_constraints:
-                from .metrics import rejection_totals
-                _, pos, _, episodes, *_ = engine.denoise_reject(ctx_e, p0, dt=float(_integrate[1]), precision=precision,
-                                                                threshold=collision_threshold, max_rounds=max_rounds, want_vel=False,
-                                                                **walls, **nz)
-                return (pos.reshape(sample, B, num_points, 2), number_of_steps, *rejection_totals(episodes))
-            _, pos = engine.denoise(None, ctx_e, p0, dt=float(_integrate[1]), precision=precision, want_vel=False, **nz)
-            return pos.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
-        vel, _ = engine.denoise(None, ctx_e, None, precision=precision, want_pos=False, **nz)
-        return vel.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
-    x_T = torch.zeros([sample, B, num_points, 2])
-    z = torch.zeros([n_steps, sample, B, num_points, 2])
-    for i in range(sample):
-        if bestof:
-            x_T[i] = torch.randn([B, num_points, point_dim])
-        for k, t in enumerate(range(engine.schedule.num_steps, 0, -stride)):
-            if t > 1:
-                z[k, i] = torch.randn([B, num_points, point_dim])
+        x_T, noise = None, dict(seed=int(seed), episode_ids=np.arange(sample, dtype=np.uint32), K=1, T=int(num_points))
+    else:
+        x_T = torch.zeros([sample, B, num_points, 2])
+        z = torch.zeros([n_steps, sample, B, num_points, 2])
+        for i in range(sample):
+            if bestof:
+                x_T[i] = torch.randn([B, num_points, point_dim])
+            for k, t in enumerate(range(engine.schedule.num_steps, 0, -stride)):
+                if t > 1:
+                    z[k, i] = torch.randn([B, num_points, point_dim])
+        x_T, noise = x_T.numpy(), dict(z=z.numpy() if sampling == "ddpm" else None)
     ctx_e = ctx.unsqueeze(0).expand(sample, B, ctx.shape[1]).contiguous().numpy()
     number_of_steps = sample * (engine.schedule.num_steps // stride + 1)
-    if _integrate is not None:      # every sample is an "episode" of B agents with K = 1: p0 repeats per sample
-        p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(_integrate[0], dtype=np.float32)[None], (sample, B, 2)))
-        _, pos = engine.denoise(x_T.numpy(), ctx_e, p0, dt=float(_integrate[1]), precision=precision, want_vel=False,
-                                z=z.numpy() if sampling == "ddpm" else None)
-        return pos.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
-    vel, _ = engine.denoise(x_T.numpy(), ctx_e, None, precision=precision, want_pos=False,
-                            z=z.numpy() if sampling == "ddpm" else None)
-    return vel.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
-
-
-_sample = sample
+    if _integrate is None:
+        vel, _ = engine.denoise(x_T, ctx_e, None, precision=precision, want_pos=False, **noise)
+        return vel.reshape(sample, B, num_points, 2), number_of_steps, 0, 0, 0
+    # every sample is an "episode" of B agents with K = 1: p0 repeats per sample
+    p0, dt = np.ascontiguousarray(np.broadcast_to(np.asarray(_integrate[0], dtype=np.float32)[None], (sample, B, 2))), float(_integrate[1])
+    totals = (0, 0, 0)
+    if redraw:
+        pos, rejection = denoise_stage(engine, ctx_e, p0, limits, dt, seeded=noise)(precision, True)
+        totals = rejection_totals(rejection.episodes)
+    else:
+        _, pos = engine.denoise(x_T, ctx_e, p0, dt=dt, precision=precision, want_vel=False, **noise)
+    if limits.repair is not None:
+        pos, episode, _ = repair_stage(engine, pos, (sample, B, 1, num_points), limits.threshold, limits.repair, p0=p0, dt=dt)
+        totals = rejection_totals(episode)      # (the same three columns: largest iteration count, samples with collisions, repaired)
+    return (pos.reshape(sample, B, num_points, 2), number_of_steps, *totals)
 
 
 def generate(engine: JmidEngine, context, p0, dt: float, num_points: int, sample_n: int, bestof: bool,

@@ -20,12 +20,15 @@ TIMING_KEYS = {"scene_ms", "device_ms", "topk_ms", "assemble_ms", "total_ms"}
 
 class FakeEngine:
     """``JmidEngine``'s call surface as far as forecaster.py uses it.  Every entry appends its name to ``trace`` - with the precision
-    where it takes one, ``(nopos)`` for want_pos=False, ``(resident)`` for topk(pos=None), ``(seeded)`` for the seed forms, ``(ff)`` /
-    ``(fi)`` for first_frame / first_index - and an entry named in ``erange`` raises JMID_ERANGE in every precision but "f32"."""
+    where it takes one, ``(nopos)`` for want_pos=False, ``(resident)`` for topk / repair_collisions(pos=None), ``(seeded)`` for the seed
+    forms, ``(ff)`` / ``(fi)`` for first_frame / first_index, ``(padded)`` for n_agents, ``(walls)`` for walls, ``(p0)`` for the repair's p0 -
+    and an entry named in ``erange`` raises JMID_ERANGE in every precision but "f32".  ``draws``: the draw0 of every ``denoise_reject``."""
 
     def __init__(self, weights, joint=True, device_id=0, hist_len=6, step=2, lib_path=None):
         self.dims, self.device_id, self.hist_len, self.step, self.sampling = weights.dims, device_id, hist_len, step, "ddim"
-        self.trace, self.erange = [], set()
+        self.trace, self.erange, self.draws = [], set(), []
+        self.schedule = types.SimpleNamespace(num_steps=100)
+        self.set_step(step)
 
     def _log(self, name, precision=None):
         self.trace.append(name if precision is None else f"{name}[{precision}]")
@@ -38,8 +41,8 @@ class FakeEngine:
             return np.zeros((E, A, k, T, 2), np.float32), np.zeros((E, A, k), np.float32)
         return np.zeros((E, K, A, T, 2), np.float32), None
 
-    def set_step(self, step, sampling="ddim"):
-        self.step, self.sampling = step, sampling
+    def set_step(self, step, sampling="ddim", flexibility=0.0):
+        self.step, self.sampling, self.n_steps = step, sampling, len(range(100, 0, -int(100 / step)))
 
     def noise(self, seed, episode_ids, rows, T, draw=0):
         self._log("noise")
@@ -49,14 +52,34 @@ class FakeEngine:
         self._log("encode" + ("(fi)" if first_index is not None else ""))
         return np.zeros((x_st.shape[0], self.dims.ctx_dim), np.float32)
 
-    def denoise(self, x_T, ctx, p0, dt=0.25, precision="f32", want_vel=True, want_pos=True, seed=None, episode_ids=None, K=None, T=None):
+    def denoise(self, x_T, ctx, p0, dt=0.25, precision="f32", want_vel=True, want_pos=True, z=None, seed=None, episode_ids=None, K=None,
+                T=None):
         self._log("denoise" + ("(seeded)" if seed is not None else "") + ("" if want_pos else "(nopos)"), precision)
         E, A = ctx.shape[:2]
         K, T = (K, T) if x_T is None else (x_T.shape[1] // A, x_T.shape[2])
         return None, (np.zeros((E, K, A, T, 2), np.float32) if want_pos else None)
 
-    def topk(self, pos, k, dims=None):
-        self._log("topk" + ("(resident)" if pos is None else ""))
+    def denoise_reject(self, ctx, p0, seed, episode_ids, K, T, dt=0.25, precision="f32", threshold=0.2, max_rounds=3, draw0=0, want_vel=True,
+                       want_pos=True, walls=None, wall_radius=None, n_agents=None):
+        self.draws.append(int(draw0))
+        self._log("denoise_reject" + ("(padded)" if n_agents is not None else "") + ("(walls)" if walls is not None else "")
+                  + ("" if want_pos else "(nopos)"), precision)
+        n, a = ctx.shape[:2]
+        if n_agents is not None:
+            assert len(n_agents) == n and max(n_agents) == a and min(n_agents) >= 1 and draw0 == 0
+        out = (None, np.zeros((n, K, a, T, 2), np.float32) if want_pos else None, np.zeros((n, K, 3), np.int32), np.zeros((n, 3), np.int32))
+        return out + ((np.zeros((n, 2), np.int32),) if walls is not None or n_agents is not None else ())
+
+    def repair_collisions(self, pos, threshold=0.2, margin=0.02, tau=0.005, step=0.02, max_iter=32, p0=None, dt=0.25, vel=None, dims=None,
+                          n_agents=None, want_pos=None, walls=None, wall_radius=None):
+        self._log("repair" + ("(resident)" if pos is None else "") + ("(padded)" if n_agents is not None else "")
+                  + ("(walls)" if walls is not None else "") + ("(p0)" if p0 is not None else ""))
+        E, A, K, T = dims if pos is None else (pos.shape[0], pos.shape[2], pos.shape[1], pos.shape[3])
+        out = (None if pos is None else np.zeros((E, K, A, T, 2), np.float32), None, np.zeros((E, K, 4), np.float32), np.zeros((E, 3), np.int32))
+        return out + ((np.zeros((E, K, 2), np.float32),) if walls is not None else ())
+
+    def topk(self, pos, k, dims=None, n_agents=None):
+        self._log("topk" + ("(resident)" if pos is None else "") + ("(padded)" if n_agents is not None else ""))
         E, A, K, T = dims if pos is None else (pos.shape[0], pos.shape[2], pos.shape[1], pos.shape[3])
         return self._ranked(E, A, K + 1, T, k)
 
@@ -218,10 +241,11 @@ def test_a_too_short_history_draws_nothing(make, flags, frames, trace):
 
 
 # ------------------------------------------------------------------------------------------------------------- predict_batch
-def batch_inputs():
-    """The histories of tests/test_gpu_forecaster.py::test_predict_batch_with_natural_clusters..., six episodes of them."""
+def batch_inputs(seed=17):
+    """The histories of tests/test_gpu_forecaster.py::test_predict_batch_with_natural_clusters..., six episodes of them: six pedestrians
+    around a robot at (0, -3).  Seed 17: two count groups; ``THREE_COUNTS_SEED``: three."""
     E, F, N, dt = 6, 6, 6, 0.25
-    rng = np.random.default_rng(17)
+    rng = np.random.default_rng(seed)
     pos0 = rng.uniform(-5.0, 5.0, (E, N, 2))
     vel = rng.uniform(-1.0, 1.0, (E, N, 2))
     t = np.arange(F) * dt
@@ -230,6 +254,7 @@ def batch_inputs():
     return hum, rob
 
 
+THREE_COUNTS_SEED = 0      # in-cluster counts (1, 2, 4, 2, 2, 2) on the host scene: asserted where it is used
 PLAIN, FULL = "encode denoise(nopos)[f16mx] topk(resident)", "encode denoise[f16mx]"
 BATCH = [     # (keywords, k, trace); K = 8, two count groups
     (dict(), 3, [PLAIN] * 2),
@@ -268,3 +293,125 @@ def test_predict_batch_routes(kw, k, trace):
     assert fc.shape == (E, N, k, H + 1, 2) and lw.shape == (E, N, k) and fc.dtype == lw.dtype == np.float64
     assert " ".join(eng.trace) == " ".join(trace)
     assert FC.ERANGE_FALLBACKS == before + (sum(t.count("[f32]") for t in trace) if erange else 0)
+
+
+# ------------------------------------------------------------------------------------------------------------- constraint routes
+# recorded at the commit in front of the constraints record and the one staged run: the entries, their order and the draw numbers of
+# every constraint keyword on the three callers (the GPU tests compare results against twins; these compare the calls)
+WALLS = np.array([[0.5, -3.0, 0.5, 3.0], [-2.0, 1.0, 2.0, 1.2]])
+WALLED = dict(static_obstacles=WALLS, wall_radius=0.3, constraint_type="opt_softplus_walls")
+SOFT, REDRAW = dict(constraint_type="opt_softplus"), dict(rng_compat="device", collision_free_rounds=2)
+REPAIR_4, REPAIR_K = "encode denoise(nopos)[f16mx] repair(resident) topk(resident)", "encode denoise[f16mx] repair"
+REDRAW_4, REDRAW_K = "encode denoise_reject(nopos)[f16mx] topk(resident)", "encode denoise_reject[f16mx]"
+REDRAW_CHECK = "encode denoise_reject[f16mx] denoise_reject[f16x3]"
+CONSTRAINED = [     # (flags, k, first call, second call, draw0 of the first call's loops, of the second call's)
+    (SOFT, 4, REPAIR_4, REPAIR_4, [], []),
+    (SOFT, 10, REPAIR_K, REPAIR_K, [], []),
+    (dict(SOFT, self_check=True), 4, STAGED_CHECK + " repair topk", REPAIR_4, [], []),
+    (dict(SOFT, self_check=True), 10, STAGED_CHECK + " repair", REPAIR_K, [], []),
+    (REDRAW, 4, REDRAW_4, REDRAW_4, [0], [3]),
+    (REDRAW, 10, REDRAW_K, REDRAW_K, [0], [3]),
+    (dict(REDRAW, self_check=True), 4, REDRAW_CHECK + " topk", REDRAW_4, [0, 0], [3]),      # (the check's loop starts from the same draw0)
+    (dict(REDRAW, self_check=True), 10, REDRAW_CHECK, REDRAW_K, [0, 0], [3]),
+    (dict(REDRAW, **WALLED), 4, "encode denoise_reject(walls)(nopos)[f16mx] repair(resident)(walls)(p0) topk(resident)", None, [0], [3]),
+    (dict(REDRAW, **WALLED), 10, "encode denoise_reject(walls)[f16mx] repair(walls)(p0)", None, [0], [3]),
+    (dict(WALLED, device_frames=True), 4,
+     "build_scene_stamped scene_arrays scene_frames encode denoise(nopos)[f16mx] repair(resident)(walls)(p0) topk(resident)", None, [], []),
+]
+REPAIR_CAUSE_KEYS = {"pedestrians", "walls", "both", "pedestrians_repaired", "walls_repaired", "both_repaired", "candidates", "repaired",
+                     "reverted"}
+
+
+@pytest.mark.parametrize("flags,k,first,second,draws_first,draws_second", CONSTRAINED)
+def test_constraint_routes(make, flags, k, first, second, draws_first, draws_second):
+    f = make(k, **{"self_check": False, **flags})
+    for trace, draws in ((first, draws_first), (first if second is None else second, draws_second)):
+        f.engine.draws.clear()
+        assert call(f) == trace
+        assert f.engine.draws == draws
+        walls, rounds, fix = "static_obstacles" in flags, "collision_free_rounds" in flags, "constraint_type" in flags
+        assert (f.rejection is None) if not rounds else len(f.rejection) == (5 if walls else 3)
+        assert (f.repair is None) if not fix else len(f.repair) == 4
+        assert (f.repair_causes is None) if not (fix and walls) else set(f.repair_causes) == REPAIR_CAUSE_KEYS
+    assert f.erange_fallbacks == 0 and f.precision == "f16mx"
+
+
+def test_erange_in_the_redraw_loop_repeats_the_whole_loop_in_fp32(make):
+    """JMID_ERANGE from ``denoise_reject``: the loop again in exact fp32 from the same draw0, counted once per call, warned about once
+    per instance."""
+    f = make(4, erange=("denoise_reject(nopos)",), self_check=False, **REDRAW)
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        for n, draw0 in ((1, 0), (2, 3)):
+            f.engine.trace.clear()
+            f.engine.draws.clear()
+            before = FC.ERANGE_FALLBACKS
+            f.predict_ret_best()
+            assert " ".join(f.engine.trace) == "encode denoise_reject(nopos)[f16mx] denoise_reject(nopos)[f32] topk(resident)"
+            assert f.engine.draws == [draw0, draw0]
+            assert f.erange_fallbacks == n and FC.ERANGE_FALLBACKS == before + 1 and len(f.rejection) == 3
+    assert [str(w.message).startswith("JMID_ERANGE") for w in caught if issubclass(w.category, RuntimeWarning)] == [True]
+
+
+GROUP_WALLED = "encode denoise_reject(walls)(nopos)[f16mx] repair(resident)(walls)(p0) topk(resident)"
+DEVICE_NOISE = dict(noise="device", seed=5, collision_free_rounds=2)
+BATCH_CONSTRAINED = [     # (keywords, k, trace, keys of stats); K = 8, three count groups
+    (SOFT, 3, [REPAIR_4] * 3, ["repair"]),
+    (dict(DEVICE_NOISE, **WALLED), 3, [GROUP_WALLED] * 3, ["cause", "episodes", "repair", "repair_causes", "slots"]),
+    (dict(DEVICE_NOISE, collision_free_padded=True, **SOFT), 3,
+     ["encode denoise_reject(padded)(nopos)[f16mx] repair(resident)(padded) topk(resident)(padded)"], ["cause", "episodes", "repair", "slots"]),
+    (dict(DEVICE_NOISE, erange=("denoise_reject(nopos)",)), 3,
+     ["encode denoise_reject(nopos)[f16mx] denoise_reject(nopos)[f32] topk(resident)"] * 3, ["episodes", "slots"]),
+    # the padded branch beyond the device top-k: ranked on the host over every episode's real agents, no topk entry
+    (dict(DEVICE_NOISE, collision_free_padded=True, device_topk=False, **SOFT), 3, ["encode denoise_reject(padded)[f16mx] repair(padded)"],
+     ["cause", "episodes", "repair", "slots"]),
+]
+
+
+@pytest.mark.parametrize("kw,k,trace,keys", BATCH_CONSTRAINED)
+def test_predict_batch_constraint_routes(kw, k, trace, keys):
+    kw = dict(kw)
+    erange = set(kw.pop("erange", ()))
+    hum, rob = batch_inputs(THREE_COUNTS_SEED)
+    E, N, K, H = 6, 6, 8, 6
+    eng, stats = FakeEngine(WEIGHTS), {}
+    eng.erange = erange
+    before = FC.ERANGE_FALLBACKS
+    fc, lw, inc = FC.predict_batch(eng, hum, rob, range(E), num_samples=K, num_ret_samples=k, horizon=H, time_step=0.25, precision="f16mx",
+                                   stats=stats, **kw)
+    assert inc.sum(axis=1).tolist() == [1, 2, 4, 2, 2, 2]          # three count groups, nobody's cluster empty
+    assert fc.shape == (E, N, k, H + 1, 2) and lw.shape == (E, N, k) and fc.dtype == lw.dtype == np.float64
+    assert " ".join(eng.trace) == " ".join(trace)
+    assert sorted(stats) == keys and not any(eng.draws)           # (every loop of a batch starts at draw 0)
+    assert FC.ERANGE_FALLBACKS == before + (sum(t.count("[f32]") for t in trace) if erange else 0)
+    if "repair" in stats:
+        assert stats["repair"].shape == (E, 3)
+    if "repair_causes" in stats:
+        assert set(stats["repair_causes"]) == REPAIR_CAUSE_KEYS
+    if "episodes" in stats:
+        assert stats["episodes"].shape == (E, 3) and stats["slots"].shape == (E, K, 3)
+    if "cause" in stats:
+        assert stats["cause"].shape == (E, 2)
+
+
+OFFLINE = [     # (keywords of offline.generate, trace): offline the repair REPLACES the redraws, in the forecaster it follows them
+    (dict(with_constraints=True, seed=3, sampling="ddim"), "denoise_reject[f32]"),
+    (dict(with_constraints=True, seed=3, sampling="ddim", static_obstacles=WALLS, wall_radius=0.3), "denoise_reject(walls)[f32]"),
+    (dict(with_constraints=True, **SOFT), "denoise[f32] repair"),
+    (dict(with_constraints=True, seed=3, sampling="ddim", **SOFT), "denoise(seeded)[f32] repair"),
+    (dict(with_constraints=True, **WALLED), "denoise[f32] repair(walls)(p0)"),
+    (dict(with_constraints=True, seed=3, sampling="ddim", **WALLED), "denoise(seeded)[f32] repair(walls)(p0)"),
+]
+
+
+@pytest.mark.parametrize("kw,trace", OFFLINE)
+def test_offline_generate_constraint_routes(kw, trace):
+    from safe_interactive_crowdnav_amd import offline
+    B, T, n = 3, 6, 5
+    eng = FakeEngine(WEIGHTS)
+    rng = torch.get_rng_state()
+    pos, steps, a, b, c = offline.generate(eng, np.zeros((B, 32), np.float32), np.zeros((B, 2), np.float32), 0.25, T, n, True, step=2, **kw)
+    assert " ".join(eng.trace) == trace
+    assert ("constraint_type" in kw) == ("repair" in trace) == ("denoise_reject" not in trace)
+    assert pos.shape == (n, B, T, 2) and pos.dtype == np.float32 and steps == n * 3 and (a, b, c) == (0, 0, 0)
+    assert torch.equal(torch.get_rng_state(), rng) == ("seed" in kw)      # a seeded call draws nothing on the host

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from safe_interactive_crowdnav_amd import forecaster as FC, metrics
-from tests.test_forecaster_routes import WEIGHTS, FakeEngine
+from tests.test_forecaster_routes import THREE_COUNTS_SEED, WEIGHTS, FakeEngine, batch_inputs
 
 E, A, K, T = 5, 4, 6, 3
 COUNTS = np.array([4, 1, 2, 3, 4])
@@ -98,40 +98,6 @@ def test_twins_refuse_bad_counts():
 
 
 # ------------------------------------------------------------------------------------------------------------- predict_batch
-def batch_inputs(seed):
-    """Six episodes of six pedestrians around a robot at (0, -3), as tests/test_forecaster_routes.py draws them."""
-    n, F, N, dt = 6, 6, 6, 0.25
-    rng = np.random.default_rng(seed)
-    pos0 = rng.uniform(-5.0, 5.0, (n, N, 2))
-    vel = rng.uniform(-1.0, 1.0, (n, N, 2))
-    t = np.arange(F) * dt
-    hum = pos0[:, None] + vel[:, None] * t[None, :, None, None] + 0.01 * rng.standard_normal((n, F, N, 2))
-    rob = np.array([0.0, -3.0])[None, None] + 0.02 * rng.standard_normal((n, F, 2))
-    return hum, rob
-
-
-THREE_COUNTS_SEED = 0      # in-cluster counts (1, 2, 4, 2, 2, 2) on the host scene: asserted below
-
-
-class RejectingEngine(FakeEngine):
-    """The stand-in with the entries collision-free sampling adds: ``denoise_reject`` and ``topk(n_agents=)``."""
-
-    def denoise_reject(self, ctx, p0, seed, episode_ids, K, T, dt=0.25, precision="f32", threshold=0.2, max_rounds=3, draw0=0, want_vel=True,
-                       want_pos=True, walls=None, wall_radius=None, n_agents=None):
-        self._log("denoise_reject" + ("(padded)" if n_agents is not None else "") + ("(walls)" if walls is not None else "")
-                  + ("" if want_pos else "(nopos)"), precision)
-        n, a = ctx.shape[:2]
-        if n_agents is not None:
-            assert len(n_agents) == n and max(n_agents) == a and min(n_agents) >= 1 and draw0 == 0
-        out = (None, np.zeros((n, K, a, T, 2), np.float32) if want_pos else None, np.zeros((n, K, 3), np.int32), np.zeros((n, 3), np.int32))
-        return out + ((np.zeros((n, 2), np.int32),) if walls is not None or n_agents is not None else ())
-
-    def topk(self, pos, k, dims=None, n_agents=None):
-        self._log("topk" + ("(resident)" if pos is None else "") + ("(padded)" if n_agents is not None else ""))
-        n, a, K, T = dims if pos is None else (pos.shape[0], pos.shape[2], pos.shape[1], pos.shape[3])
-        return self._ranked(n, a, K + 1, T, k)
-
-
 KW = dict(num_samples=8, num_ret_samples=3, horizon=6, time_step=0.25, precision="f16mx")
 
 
@@ -156,7 +122,7 @@ def test_predict_batch_refusals():
 ])
 def test_the_keyword_issues_one_encode_one_loop_one_ranking(kw, trace):
     hum, rob = batch_inputs(THREE_COUNTS_SEED)
-    eng = RejectingEngine(WEIGHTS)
+    eng = FakeEngine(WEIGHTS)
     stats = {}
     args = dict(KW, noise="device", seed=5, collision_free_rounds=2, collision_free_padded=True, stats=stats)
     args.update(kw)
@@ -168,7 +134,7 @@ def test_the_keyword_issues_one_encode_one_loop_one_ranking(kw, trace):
     assert " ".join(eng.trace) == trace
     assert stats["episodes"].shape == (6, 3) and stats["slots"].shape == (6, 8, 3) and stats["cause"].shape == (6, 2)
     # ... against one loop per count without it
-    grouped = RejectingEngine(WEIGHTS)
+    grouped = FakeEngine(WEIGHTS)
     FC.predict_batch(grouped, hum, rob, range(6), **dict(args, collision_free_padded=False))
     assert sum(t.startswith("denoise_reject") for t in grouped.trace) == 3 and not any("(padded)" in t for t in grouped.trace)
 
@@ -184,7 +150,7 @@ def test_an_empty_cluster_takes_the_count_groups():
     args = dict(KW, noise="device", seed=5, collision_free_rounds=2, first_frame=ff)
 
     def outcome(**kw):
-        eng = RejectingEngine(WEIGHTS)
+        eng = FakeEngine(WEIGHTS)
         try:
             out = FC.predict_batch(eng, hum, rob, range(6), **args, **kw)
         except ValueError as err:
