@@ -829,6 +829,60 @@ int jmid_repair_collisions_walls(jmid_handle_t h, int E, int A, int K, int T, co
                                  double wall_radius, float* pos_out, float* vel_out, float* sample_out, int32_t* episode_out, float* wall_out,
                                  int mem);
 
+/* Guided sampling: a guidance term INSIDE the denoise loop.  The repair above moves a finished sample - the net never sees the correction -
+ * and a redraw costs a whole denoise call; guidance nudges the intermediate sample after every denoise step, so the remaining steps of the
+ * net run on the corrected state.  Like the rejection rule and the repair rule, the reference names the mechanism
+ * (DiffusionTraj.sample(with_constraints, constraint_type)) and has no body for it, so THE RULE is decided here.  OFF unless these entries
+ * are called; no existing entry changes.
+ * State x [E, K*A, T, 2] fp32 is the loop's velocity state, row r = (e*K + s)*A + a: the A*T*2 floats of one joint sample (e, s) are
+ * contiguous.  After the sampler update of step-table entry i (every entry, the last included), when weights[i] > 0, each sample goes
+ * through three stages independently of every other sample; everything inside is fp64, without contraction into FMA:
+ *   Integrate   acc[a][t] = acc[a][t-1] + double(x[a][t]) (acc[a][-1] = 0), q[a][t] = double(p0[e][a]) + double(dt) * acc[a][t], ascending
+ *               t.  Only the a < n real agents take part (n = n_agents[e], or A).  A sample with a q that is not finite is untouched.
+ *   Iterate     at most n_inner times exactly the Iteration of jmid_repair_collisions on q with step := weights[i] (metres): the minimum,
+ *               the stop at threshold + margin / 2, the Jacobi step, the summation order.  With L > 0 the iteration of
+ *               jmid_repair_collisions_walls: p0 is the fixed first point of every path, the wall terms come behind the partners, and
+ *               the order and the stop rule (both minima clear) are that entry's.  The kernel calls the repair's own device functions.
+ *               There is NO "End" stage: no rounding of positions, no predicate, no revert.  A sample that stops before its first
+ *               iteration is NOT WRITTEN at all.  T = 1 has no pedestrian segment: untouched without walls, wall terms only (the step
+ *               from p0) with them.  With one real agent only the wall terms exist.
+ *   Write back  with D[a][t] = q_final[a][t] - q_initial[a][t], D[a][-1] = 0:
+ *                 x[a][t] <- float(double(x[a][t]) + (D[a][t] - D[a][t-1]) / double(dt))
+ *               for all real rows of a sample that took at least one iteration: one rounding per point, no cumsum / difference round
+ *               trip - a point whose difference is exactly 0 keeps its value.  Padded agents' rows are never read or written.
+ * weights[i] = 0: no launch behind entry i; an all-zero table makes the whole call the unguided call, bit for bit.  Because the samples of
+ * one JMID episode attend to each other, "unchanged" is a statement per episode: an episode none of whose samples ever took an iteration
+ * equals the unguided call in every bit.
+ *
+ * jmid_guide_step: ONE application of the rule to a given block x [E, K*A, T, 2] at `weight` -> x_out (may be x itself in
+ * JMID_MEM_DEVICE); weight = 0 copies.  guide_out [E, K, 2] float = {1 if the sample iterated, iterations used}; may be NULL.
+ *
+ * jmid_denoise_guided: jmid_denoise (n_agents NULL) or jmid_denoise_padded (a HOST array [E]) under the rule, DDIM.  Every step embeds at
+ * its head (the unfused seam, bit-identical to the fused one), the guide kernel runs behind each entry with weights[i] > 0 on the stream of
+ * the chunk it belongs to, and the integrator and everything behind the loop are unchanged: vel_out, pos_out and the resident positions
+ * are the guided ones.  The call equals, bit for bit, the chain of one-entry calls with jmid_guide_step between them.  Never captured
+ * into a graph.  Nothing of the guidance stays on the handle.
+ *   weights     double [n_steps], a HOST array (n_steps: the installed DDIM table), metres, finite and >= 0
+ *   walls       [L, 4] float64 {x1, y1, x2, y2}, a HOST array, 0 <= L <= 64 (L = 0: no walls), finite; wall_radius finite and >= 0
+ *   p0          [E, A, 2], required; dt finite and > 0
+ *   guide_out   [E, K, 2] float = {steps at which the sample iterated, iterations in total}; may be NULL
+ * jmid_denoise_guided_seeded: the same with (seed, episode_ids) in place of x_T - draw 0, by the padded rule when counts are given.
+ * The kernel holds a sample in LDS as the repair with walls does (53.0 KB at A = 64, T = 24, L = 64).
+ * Limits: 1 <= K <= 1024, 1 <= T <= 24, 1 <= A <= 64.  JMID_EINVAL: those; a threshold or margin that is not finite or < 0; tau <= 0;
+ * L outside 0..64, L > 0 with walls NULL, a non-finite wall coordinate, a wall_radius that is not finite or < 0; p0 NULL; dt not finite or
+ * <= 0; a weight that is negative or not finite; n_inner outside 1..64; a count outside 1..A; a handle with the DDPM table set (the
+ * denoise entries); and whatever jmid_denoise / jmid_denoise_padded refuse. */
+int jmid_guide_step(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* x, const float* p0, float dt,
+                    double threshold, double margin, double tau, double weight, int n_inner, int L, const double* walls, double wall_radius,
+                    float* x_out, float* guide_out, int mem);
+int jmid_denoise_guided(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* x_T, const float* ctx, const float* p0,
+                        float dt, int precision, double threshold, double margin, double tau, const double* weights, int n_inner, int L,
+                        const double* walls, double wall_radius, float* vel_out, float* pos_out, float* guide_out, int mem);
+int jmid_denoise_guided_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,
+                               const float* ctx, const float* p0, float dt, int precision, double threshold, double margin, double tau,
+                               const double* weights, int n_inner, int L, const double* walls, double wall_radius, float* vel_out,
+                               float* pos_out, float* guide_out, int mem);
+
 /* Padded chains on the resident scene: jmid_predict_scene / jmid_forecast_scene (and their seeded forms) for a scene whose episodes have
  * DIFFERENT in-cluster counts - what jmid_build_scene leaves whenever it chooses the clusters itself - in one call, in the layout and
  * under the rules of "Padded scene batches" above.  The caller passes no n_agents: the counts are the resident scene's n_in, read on the

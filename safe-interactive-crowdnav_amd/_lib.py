@@ -108,6 +108,14 @@ SIGNATURES = {
     "jmid_repair_collisions_walls": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double,
                                                C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_guide_step": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double,
+                                  C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_denoise_guided": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                      C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "jmid_denoise_guided_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_float, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "jmid_predict_scene_padded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_forecast_scene_padded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p,

@@ -1038,6 +1038,100 @@ int jmid_repair_collisions_walls(jmid_handle_t h, int E, int A, int K, int T, co
                         wall_radius, pos_out, vel_out, sample_out, episode_out, wall_out, mem);
 }
 
+// What jmid_guide_step and the guided denoise entries refuse alike: the repair entries' conditions on threshold, margin, tau and
+// wall_radius, n_inner, the shape limits (T = 1 is allowed: no pedestrian segment, the wall terms of the step from p0 only)
+static int guide_check(jmid_handle_t h, const std::string& w, int E, int A, int K, int T, const float* p0, float dt, double threshold, double margin,
+                       double tau, int n_inner, double wall_radius) {
+    if (E <= 0) return fail(h, JMID_EINVAL, w + ": bad argument");
+    if (K < 1 || K > CLS_MAX_K || T < 1 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
+        return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 1 <= T <= 24, 1 <= A <= 64");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(h, JMID_EINVAL, w + ": the threshold must be finite and >= 0");
+    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(h, JMID_EINVAL, w + ": the margin must be finite and >= 0");
+    if (!(tau > 0.0) || !std::isfinite(tau)) return fail(h, JMID_EINVAL, w + ": tau must be finite and > 0");
+    if (n_inner < 1 || n_inner > GDE_MAX_INNER) return fail(h, JMID_EINVAL, w + ": n_inner must lie in 1..64");
+    if (!(wall_radius >= 0.0) || !std::isfinite(wall_radius)) return fail(h, JMID_EINVAL, w + ": the wall_radius must be finite and >= 0");
+    if (!p0) return fail(h, JMID_EINVAL, w + ": null p0 (the guidance is defined on positions)");
+    if (!(dt > 0.0f) || !std::isfinite(dt)) return fail(h, JMID_EINVAL, w + ": dt must be finite and > 0");
+    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
+    return 0;
+}
+
+// One application of the guidance rule (guide.hpp) to a block of velocities: what a guided denoise call runs behind one step-table entry
+int jmid_guide_step(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* x, const float* p0, float dt,
+                    double threshold, double margin, double tau, double weight, int n_inner, int L, const double* walls, double wall_radius,
+                    float* x_out, float* guide_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    const char* who = "jmid_guide_step";
+    const std::string w(who);
+    if (int rc = guide_check(h, w, E, A, K, T, p0, dt, threshold, margin, tau, n_inner, wall_radius)) return rc;
+    if (!(weight >= 0.0) || !std::isfinite(weight)) return fail(h, JMID_EINVAL, w + ": the weight must be finite and >= 0");
+    if (!x || !x_out) return fail(h, JMID_EINVAL, w + ": null x / x_out");
+    if (n_agents)
+        if (int rc = check_n_agents(h, who, n_agents, E, A)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    GuideArgs g{};
+    if (int rc = upload_walls(h, L, walls, &g.walls, w)) return rc;
+    const bool host = mem == JMID_MEM_HOST;
+    const size_t M2 = (size_t)E * K * A * T * 2, rows = (size_t)E * K * GDE_COLS;
+    g.E = E; g.A = A; g.K = K; g.T = T; g.n_inner = n_inner; g.L = L;
+    g.threshold = threshold; g.margin = margin; g.tau = tau; g.weight = weight; g.dt = (double)dt; g.wall_radius = wall_radius;
+    if (host) h->last_pos = nullptr;      // (as in jmid_encode)
+    Staging st(h, mem, h->kde_ws, who);
+    g.x = x_out;
+    if (host) st.add(&g.x, x, x_out, M2 * sizeof(float));      // up from x, worked on in place, down to x_out
+    st.in(&g.p0, p0, (size_t)E * A * 2);
+    if (guide_out) st.out(&g.out, guide_out, rows);
+    if (int rc = st.begin()) return rc;
+    if (!host && x_out != x) HIPCHK(h, hipMemcpyAsync(x_out, x, M2 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (g.out) HIPCHK(h, hipMemsetAsync(g.out, 0, rows * sizeof(float), h->stream));
+    if (n_agents) {
+        if (int rc = h->nag.upload(h, n_agents, E, who)) return rc;
+        g.n_agents = h->nag.get<int>();
+    }
+    if (weight > 0.0) {
+        ProfScope ps(h, KC_GUIDE, h->stream);
+        HIPCHK(h, launch_guide(g, h->stream));
+    }
+    return st.end();
+}
+
+// jmid_denoise_guided (seeded null) and jmid_denoise_guided_seeded: a DDIM denoise call with the guide kernel behind every step-table entry
+// whose weight is > 0; n_agents null, or a padded call.  What is about the table (DDPM, the weights) is refused by check_call
+static int guided_entry(jmid_handle_t h, const char* who, int E, int A, int K, int T, const int32_t* n_agents, const float* x_T, const SeedArgs* seeded,
+                        const float* ctx, const float* p0, float dt, int precision, double threshold, double margin, double tau,
+                        const double* weights, int n_inner, int L, const double* walls, double wall_radius, float* vel_out, float* pos_out,
+                        float* guide_out, int mem) {
+    if (!h) return JMID_EINVAL;
+    const std::string w(who);
+    if (int rc = guide_check(h, w, E, A, K, T, p0, dt, threshold, margin, tau, n_inner, wall_radius)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    GuideCall gc;
+    gc.threshold = threshold; gc.margin = margin; gc.tau = tau; gc.weights = weights; gc.n_inner = n_inner; gc.L = L;
+    gc.wall_radius = wall_radius; gc.guide_out = guide_out;
+    if (int rc = upload_walls(h, L, walls, &gc.walls, w)) return rc;
+    DenoiseCall c{E, A, K, T, precision, mem};
+    c.x_in = x_T; c.seeded = seeded; c.ctx = ctx; c.p0 = p0; c.dt = dt; c.vel_out = vel_out; c.pos_out = pos_out; c.n_agents = n_agents;
+    c.guide = &gc; c.who = who;
+    return run_network(h, c);
+}
+
+int jmid_denoise_guided(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, const float* x_T, const float* ctx, const float* p0,
+                        float dt, int precision, double threshold, double margin, double tau, const double* weights, int n_inner, int L,
+                        const double* walls, double wall_radius, float* vel_out, float* pos_out, float* guide_out, int mem) {
+    if (h && !x_T) return fail(h, JMID_EINVAL, "jmid_denoise_guided: null x_T");
+    return guided_entry(h, "jmid_denoise_guided", E, A, K, T, n_agents, x_T, nullptr, ctx, p0, dt, precision, threshold, margin, tau, weights, n_inner,
+                        L, walls, wall_radius, vel_out, pos_out, guide_out, mem);
+}
+
+int jmid_denoise_guided_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,
+                               const float* ctx, const float* p0, float dt, int precision, double threshold, double margin, double tau,
+                               const double* weights, int n_inner, int L, const double* walls, double wall_radius, float* vel_out,
+                               float* pos_out, float* guide_out, int mem) {
+    const SeedArgs sa{seed, episode_ids};
+    return guided_entry(h, "jmid_denoise_guided_seeded", E, A, K, T, n_agents, nullptr, &sa, ctx, p0, dt, precision, threshold, margin, tau, weights,
+                        n_inner, L, walls, wall_radius, vel_out, pos_out, guide_out, mem);
+}
+
 // jmid_topk (n_agents null) and jmid_topk_padded
 static int topk_entry(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* pos, const float* bw, float* sel,
                       float* logw, int mem) {

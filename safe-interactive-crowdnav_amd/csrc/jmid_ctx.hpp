@@ -46,6 +46,7 @@
 #include "tail_fold.hpp"
 #include "scene.hpp"
 #include "frames.hpp"
+#include "guide.hpp"
 
 using namespace jmid;
 
@@ -66,6 +67,7 @@ enum KClass {
     KC_VTRANS,
     KC_LOSS_PREPARE,
     KC_LOSS_REDUCE,
+    KC_GUIDE,
     KC_TOPK,
     KC_EVAL_STATS,
     KC_COUNT
@@ -357,6 +359,17 @@ struct LossCall {
     const SeedArgs* seeded = nullptr;
     double *loss_out = nullptr, *row_out = nullptr;      // [2]; [E, A] or null
 };
+// What a guided call (jmid_denoise_guided*; guide.hpp) adds to a denoise call: the rule's arguments and the per-entry weights.  A value
+// of the call like everything else here: nothing of it stays on the handle
+struct GuideCall {
+    double threshold = 0.0, margin = 0.0, tau = 0.0;
+    const double* weights = nullptr;      // HOST [n_steps], metres; 0: no launch behind that entry
+    int n_inner = 0;
+    int L = 0;
+    const double* walls = nullptr;        // [L, 4] on the DEVICE (upload_walls), null at L = 0
+    double wall_radius = 0.0;
+    float* guide_out = nullptr;           // [E, K, 2] where `mem` says, or null
+};
 // One denoise call (or, with single_step >= 0, one net evaluation -> e_out) as its entry point states it
 struct DenoiseCall {
     int E, A, K, T, precision, mem;
@@ -374,6 +387,9 @@ struct DenoiseCall {
     // the checks read, and nothing is uploaded.  With `seeded`, x_T is the padded fill of noise.hpp (DDIM only).
     const int* n_agents_dev = nullptr;
     const LossCall* loss = nullptr;       // a loss call: per-row timesteps folded into hyp, a zero row as thyp, e_out may be null
+    // a guided call: every step embeds at its head (no fused seam), the guide kernel follows each entry whose weight is > 0 on the chunk's
+    // stream, never captured.  DDIM only, p0 required
+    const GuideCall* guide = nullptr;
     const char* who = "jmid_denoise";     // the entry point that was called (error texts)
 };
 // One chained call (jmid_predict*, jmid_predict_scene*, jmid_forecast_scene*) as its entry point states it: upload, encoder -> denoise

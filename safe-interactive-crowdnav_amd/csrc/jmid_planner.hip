@@ -756,6 +756,7 @@ struct CallIo {
     float* tbo;          // (StepPlan::loss_tbo; only off the folded tail)
     double *loss_rows, *loss;
     const float* e_dev;  // ... and the e the two loss kernels read (fill_workspace)
+    float* guide;        // a guided call: [E, K, 2] the rows the guide kernel accumulates over the steps, zeroed by fill_workspace
 };
 size_t call_io(const jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, char* base, CallIo* out) {
     const size_t M = (size_t)a.E * a.K * a.A * a.T, EA = (size_t)a.E * a.A;
@@ -775,6 +776,7 @@ size_t call_io(const jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, char
         io.loss_rows = c.take<double>(EA);
         io.loss = c.take<double>(2);
     }
+    if (a.guide) io.guide = c.take((size_t)a.E * a.K * GDE_COLS);
     if (out) *out = io;
     return c.off;
 }
@@ -809,6 +811,17 @@ int check_call(jmid_ctx* h, const DenoiseCall& a, CallMode* mode) {
             if (lc->t[r] < 1 || lc->t[r] >= n_t)
                 return fail(h, JMID_EINVAL, w + ": t[" + std::to_string(r / a.A) + ", " + std::to_string(r % a.A) + "] = " + std::to_string(lc->t[r]) +
                                                 " (row " + std::to_string(r) + ") is outside 1.." + std::to_string(n_t - 1));
+    }
+    if (const GuideCall* gc = a.guide) {
+        const std::string w(a.who);
+        if (a.single_step >= 0 || a.loss || a.z) return fail(h, JMID_EINVAL, w + ": a guided call is a DDIM denoise call");
+        if (h->ddpm) return fail(h, JMID_EINVAL, w + ": a guided call samples with DDIM only (a DDPM table is installed)");
+        if (!a.p0) return fail(h, JMID_EINVAL, w + ": null p0 (the guidance is defined on positions)");
+        if (!(a.dt > 0.0f) || !std::isfinite(a.dt)) return fail(h, JMID_EINVAL, w + ": dt must be finite and > 0");
+        if (!gc->weights) return fail(h, JMID_EINVAL, w + ": null weights");
+        for (size_t i = 0; i < h->beta.size(); ++i)
+            if (!(gc->weights[i] >= 0.0) || !std::isfinite(gc->weights[i]))
+                return fail(h, JMID_EINVAL, w + ": weights[" + std::to_string(i) + "] must be finite and >= 0");
     }
     h->last_pos = nullptr;     // (the staging buffer is about to be reused)
     if (a.single_step < 0 && h->ddpm && !a.z && !a.seeded) return fail(h, JMID_EINVAL, "DDPM table installed: use jmid_denoise_ddpm (needs z)");
@@ -898,10 +911,28 @@ int fill_workspace(jmid_ctx* h, DenoiseCall& a, CallPlan& cp, CallIo& io) {
         ProfScope ps(h, KC_LOSS_PREPARE, h->stream);
         HIPCHK(h, launch_loss_prepare(pa, h->stream));
     }
+    if (a.guide) HIPCHK(h, hipMemsetAsync(io.guide, 0, (size_t)a.E * a.K * GDE_COLS * sizeof(float), h->stream));
     if (cp.nlanes > 1) {   // everything enqueued so far (inputs, hyper nets, memsets) precedes the extra lanes as well
         HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
         for (int l = 1; l < cp.nlanes; ++l) HIPCHK(h, hipStreamWaitEvent(cp.lanes[l].stream, h->ev_fork, 0));
     }
+    return 0;
+}
+
+// The guide kernel (guide.hpp) on the episodes [el, el + ec) of a guided call, behind step-table entry i on the chunk's own stream
+int guide_chunk(jmid_ctx* h, const DenoiseCall& a, const CallIo& io, const Lane& ln, int i, size_t el, int ec) {
+    const GuideCall& gc = *a.guide;
+    GuideArgs g{};
+    g.x = io.x_cur + el * (size_t)a.K * a.A * a.T * 2;
+    g.p0 = a.p0 + el * (size_t)a.A * 2;
+    g.n_agents = io.nag ? io.nag + el : nullptr;
+    g.walls = gc.walls;
+    g.out = io.guide + el * (size_t)a.K * GDE_COLS;
+    g.threshold = gc.threshold; g.margin = gc.margin; g.tau = gc.tau; g.weight = gc.weights[i]; g.dt = (double)a.dt;
+    g.wall_radius = gc.wall_radius;
+    g.E = ec; g.A = a.A; g.K = a.K; g.T = a.T; g.n_inner = gc.n_inner; g.L = gc.L;
+    ProfScope ps(h, KC_GUIDE, ln.stream);
+    HIPCHK(h, launch_guide(g, ln.stream));
     return 0;
 }
 
@@ -922,7 +953,7 @@ int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallI
     jmid_ctx::LoopGraph* lg = nullptr;
     bool capturing = false;
     if (a.single_step < 0 && lanes == 1 && nchunks == 1 && !h->prof_mask && !a.z && !h->ddpm && h->tune.graph == 1 &&
-        h->tune.bystander_lds == 0) {
+        h->tune.bystander_lds == 0 && !a.guide) {      // (a guided call's launches depend on its weights: never captured)
         const std::string key = std::to_string(E) + "," + std::to_string(A) + "," + std::to_string(K) + "," + std::to_string(T) +
                                 "," + std::to_string(a.precision) + (cp.masked ? ",padded" : "");
         lg = &h->graphs[key];
@@ -957,9 +988,12 @@ int run_steps(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const CallI
                 const StepPlan& pl = cp.plans[cp.chunk_plan[c0 + l]];
                 if (!rc && i == 0 && pl.qkv0 && pl.cf.qkv0_steps > 1) rc = qkv0_build_table(h, pl, ln, hc, 0, n_steps);
                 if (!rc && i == 0 && pl.tail_fold && pl.cf.tail_steps > 1) rc = tail_build_table(h, pl, ln, hc, 0, n_steps);
-                if (!rc) rc = net_step(h, pl, ln, i, xc, hc, one ? io.stage + el * tok * 2 : nullptr, zc, h->tune.fuse_embed && i > i0,
-                                        h->tune.fuse_embed && i + 1 < i1 ? i + 1 : -1,
+                // a guided call: the guide kernel sits between this step's update and the next step's embedding, so no seam is fused
+                const bool fuse = h->tune.fuse_embed && !a.guide;
+                if (!rc) rc = net_step(h, pl, ln, i, xc, hc, one ? io.stage + el * tok * 2 : nullptr, zc, fuse && i > i0,
+                                        fuse && i + 1 < i1 ? i + 1 : -1,
                                         io.mask ? io.mask + el * mask_words_per_seq((int)tok) : nullptr);
+                if (!rc && a.guide && a.guide->weights[i] > 0.0) rc = guide_chunk(h, a, io, ln, i, el, cp.chunk_sizes[c0 + l]);
                 if (rc) {
                     if (capturing) {
                         hipGraph_t dead = nullptr;
@@ -1017,6 +1051,8 @@ int finish_call(jmid_ctx* h, const DenoiseCall& a, const CallPlan& cp, const Cal
         if (a.e_out) HIPCHK(h, hipMemcpyAsync(a.e_out, io.stage, M * 2 * sizeof(float), kout, h->stream));
     } else {
         if (a.vel_out) HIPCHK(h, hipMemcpyAsync(a.vel_out, io.x_cur, M * 2 * sizeof(float), kout, h->stream));
+        if (a.guide && a.guide->guide_out)
+            HIPCHK(h, hipMemcpyAsync(a.guide->guide_out, io.guide, (size_t)a.E * a.K * GDE_COLS * sizeof(float), kout, h->stream));
         if (a.p0) {      // integrated whenever p0 is given: the positions stay in the workspace for jmid_topk(pos = NULL)
             {
                 ProfScope ps(h, KC_INTEGRATE, h->stream);

@@ -3,7 +3,7 @@
 
 const char* const kClassNames[KC_COUNT] = {"gemm_qkv", "gemm_attn_out", "gemm_ff1", "gemm_ff2", "gemm_tail", "attention",
                                      "add_layernorm", "embed", "out_ddim", "hyper", "encoder", "integrate",
-                                     "episode_metrics", "v_transpose", "loss_prepare", "loss_reduce", "kde_topk", "eval_statistics"};
+                                     "episode_metrics", "v_transpose", "loss_prepare", "loss_reduce", "guide", "kde_topk", "eval_statistics"};
 
 
 namespace jmid_host {

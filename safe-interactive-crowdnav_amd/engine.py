@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional, Tuple, Union
+from typing import Any, Dict, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 
@@ -99,6 +99,20 @@ def seeded_noise_args(x_T, seed, episode_ids, E: Optional[int] = None):
     if np.any(ids.astype(np.int64) < 0) or np.any(ids.astype(np.int64) > 0xFFFFFFFF):
         raise ValueError("episode ids are uint32")
     return seed, np.ascontiguousarray(ids, dtype=np.uint32)
+
+
+class Guidance(NamedTuple):
+    """The guidance of a guided denoise call (``jmid_denoise_guided``; include/jmid_hip.h states the rule): after every step-table entry
+    i with ``weights[i] > 0`` each joint sample is integrated, pushed apart by at most ``n_inner`` iterations of the repair's iteration
+    with step ``weights[i]`` metres, and written back as velocities.  ``weights``: one per entry of the installed DDIM table
+    (``schedule.guidance_weights``).  ``walls`` [L, 4] or [L, 2, 2] with ``wall_radius``: the wall terms too."""
+    threshold: float
+    margin: float = 0.02
+    tau: float = 0.005
+    weights: Any = None
+    n_inner: int = 4
+    walls: Any = None
+    wall_radius: Optional[float] = None
 
 
 class LossResult:
@@ -296,8 +310,12 @@ class JmidEngine:
 
     def denoise(self, x_T: Optional[ArrayLike], ctx: ArrayLike, p0: Optional[ArrayLike] = None, dt: float = 0.25,
                 precision: str = "f32", want_vel: bool = True, want_pos: bool = True, z: Optional[ArrayLike] = None,
-                seed: Optional[int] = None, episode_ids=None, K: Optional[int] = None, T: Optional[int] = None, n_agents=None):
+                seed: Optional[int] = None, episode_ids=None, K: Optional[int] = None, T: Optional[int] = None, n_agents=None,
+                guidance: Optional[Guidance] = None, want_guide: bool = False):
         """Batched reverse-denoising loop.  x_T [E, K*A, T, 2], ctx [E, A, ctx_dim], p0 [E, A, 2].
+        ``guidance`` (a ``Guidance``; ``jmid_denoise_guided`` / ``_seeded``, DDIM, ``p0`` required): softplus collision steps between
+        the denoise steps - explicit, seeded or padded (``n_agents``, with ``seed`` too: the padded draw).  ``want_guide=True``: a third
+        value, guide [E, K, 2] = ``metrics.GUIDE_COLUMNS``.  Without it the call is the call it always was.
         ``n_agents`` [E] (``jmid_denoise_padded``, DDIM with an explicit x_T only): episode e has n_agents[e] <= A real agents, rows
         s*A + a with a >= n_agents[e] are padding - never read on the way in, NaN in vel and pos.
         ``z`` [n_steps, E, K*A, T, 2]: per-step normal draws, required when the DDPM table is installed.
@@ -306,7 +324,11 @@ class JmidEngine:
         explicit call fed ``noise(seed, episode_ids, K * A, T, draw)``, for every batch the episodes are part of.
         Returns (vel [E,K,A,T,2] or None, pos [E,K,A,T,2] or None)."""
         seeded = seeded_noise_args(x_T, seed, episode_ids)
-        if n_agents is not None and (seeded is not None or z is not None):
+        if guidance is None and want_guide:
+            raise ValueError("want_guide needs guidance")
+        if guidance is not None and z is not None:
+            raise ValueError("a guided call is DDIM: no z")
+        if n_agents is not None and ((seeded is not None and guidance is None) or z is not None):
             raise ValueError("a padded call (n_agents) is DDIM with an explicit x_T: no seed, no z")
         if seeded is not None:
             if z is not None:
@@ -330,6 +352,19 @@ class JmidEngine:
         vel = _out((E, K, A, T, 2), device=where) if want_vel else None
         pos = _out((E, K, A, T, 2), device=where) if want_pos else None
         tail = (bc.ptr, bp.ptr if bp else None, float(dt), _lib.PRECISIONS[precision], _ptr(vel), _ptr(pos), self._mem(dev))
+        if guidance is not None:
+            if p0 is None:
+                raise ValueError("a guided call needs p0 (the guidance is defined on positions)")
+            gargs, keep = self._guidance_args(guidance)
+            guide = _out((E, K, 2), device=where) if want_guide else None
+            na = agent_counts(n_agents, E) if n_agents is not None else None
+            head = (self._h, E, A, K, T, _ptr(na))
+            mid = (bc.ptr, bp.ptr, float(dt), _lib.PRECISIONS[precision]) + gargs + (_ptr(vel), _ptr(pos), _ptr(guide), self._mem(dev))
+            if seeded is not None:
+                self._compute(self._lib.jmid_denoise_guided_seeded, *head, seeded[0], _ptr(seeded[1]), *mid)
+            else:
+                self._compute(self._lib.jmid_denoise_guided, *head, bx.ptr, *mid)
+            return (vel, pos, guide) if want_guide else (vel, pos)
         if seeded is not None:
             self._compute(self._lib.jmid_denoise_seeded, self._h, E, A, K, T, seeded[0], _ptr(seeded[1]), *tail)
         elif z is not None:
@@ -341,6 +376,58 @@ class JmidEngine:
         else:
             self._compute(self._lib.jmid_denoise, self._h, E, A, K, T, bx.ptr, *tail)
         return vel, pos
+
+    def _guidance_args(self, g: Guidance):
+        """The arguments of a ``Guidance`` as the guided entries take them (threshold ... wall_radius) and the arrays they point into."""
+        if g.weights is None:
+            raise ValueError("guidance needs weights: one per step-table entry (schedule.guidance_weights)")
+        w = np.ascontiguousarray(np.asarray(g.weights, dtype=np.float64).reshape(-1))
+        if w.size != self.n_steps:
+            raise ValueError(f"guidance.weights must hold one weight per step-table entry ({self.n_steps}), got {w.size}")
+        if g.walls is None and g.wall_radius is not None:
+            raise ValueError("wall_radius is given without walls")
+        if g.walls is not None and g.wall_radius is None:
+            raise ValueError("walls need wall_radius (the guidance knows no agent radius)")
+        walls = wall_segments(g.walls)
+        L = int(walls.shape[0])
+        args = (float(g.threshold), float(g.margin), float(g.tau), _ptr(w), int(g.n_inner), L, _ptr(walls) if L else None,
+                float(g.wall_radius) if g.wall_radius is not None else 0.0)
+        return args, (w, walls)
+
+    def guide_step(self, x: ArrayLike, p0: ArrayLike, dt: float = 0.25, threshold: float = 0.2, margin: float = 0.02, tau: float = 0.005,
+                   weight: float = 0.02, n_inner: int = 4, n_agents=None, walls=None, wall_radius: Optional[float] = None, inplace: bool = False):
+        """One guidance step on the device (``jmid_guide_step``; the rule stands in include/jmid_hip.h, its host twin is
+        ``metrics.guide_step_host``): x [E, K*A, T, 2] velocities (row s*A + a), p0 [E, A, 2] -> (x_out, guide [E, K, 2] =
+        ``metrics.GUIDE_COLUMNS``).  What a guided ``denoise`` runs behind one step-table entry with ``weight`` metres.  NumPy in ->
+        NumPy out, CUDA tensors in -> CUDA tensors out; ``inplace=True`` (a contiguous float32 CUDA tensor): x itself is written and
+        returned.  ``n_agents`` [E]: a padded block.  ``walls`` [L, 4] or [L, 2, 2] with ``wall_radius``: the wall terms too."""
+        if walls is None and wall_radius is not None:
+            raise ValueError("wall_radius is given without walls")
+        if walls is not None and wall_radius is None:
+            raise ValueError("walls need wall_radius (the guidance knows no agent radius)")
+        if x.ndim != 4 or int(x.shape[-1]) != 2 or p0.ndim != 3 or int(p0.shape[0]) != int(x.shape[0]) or int(p0.shape[2]) != 2 \
+                or int(x.shape[1]) % int(p0.shape[1]):
+            raise ValueError("expected x [E, K*A, T, 2] and p0 [E, A, 2]")
+        dev = _is_cuda(x)
+        E, KA, T, _ = (int(v) for v in x.shape)
+        A = int(p0.shape[1])
+        K = KA // A
+        bx, b0 = _Buf(x, dev), _Buf(p0, dev)
+        where = x.device if dev else None
+        if inplace:
+            if not dev or bx.keep.data_ptr() != x.data_ptr():
+                raise ValueError("inplace needs a contiguous float32 CUDA tensor")
+            out = x
+        else:
+            out = _out((E, KA, T, 2), device=where)
+        guide = _out((E, K, 2), device=where)
+        na = agent_counts(n_agents, E) if n_agents is not None else None
+        w = wall_segments(walls)
+        L = int(w.shape[0])
+        self._check(self._lib.jmid_guide_step(self._h, E, A, K, T, _ptr(na), bx.ptr, b0.ptr, float(dt), float(threshold), float(margin), float(tau),
+                                              float(weight), int(n_inner), L, _ptr(w) if L else None,
+                                              float(wall_radius) if wall_radius is not None else 0.0, _ptr(out), _ptr(guide), self._mem(dev)))
+        return out, guide
 
     def denoise_padded_seeded(self, ctx: ArrayLike, p0: Optional[ArrayLike], n_agents, seed: int, episode_ids, K: int, T: int, dt: float = 0.25,
                               precision: str = "f32", want_vel: bool = True, want_pos: bool = True):

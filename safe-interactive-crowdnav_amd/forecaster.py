@@ -57,6 +57,12 @@ stage with the walls in the objective and in both gates (``jmid_repair_collision
 position included, come closer than ``wall_radius`` to a wall is a candidate too, a single pedestrian included, and a repaired sample is
 kept only when both predicates accept it.  ``self.repair_causes`` holds the last call's candidates split by cause
 (``metrics.repair_causes``).
+``guidance={scale, n_inner, margin, tau, weights, walls, table}`` (opt-in, under EVERY ``rng_compat``; ``{}``: the defaults): guided
+sampling - softplus collision steps at ``collision_threshold`` BETWEEN the denoise steps (``JmidEngine.denoise(guidance=)``,
+``jmid_denoise_guided``; include/jmid_hip.h states the rule), so the net's remaining steps run on the corrected state; the route is staged
+and ``self.guide`` [K, 2] holds the last call's rows (``metrics.GUIDE_COLUMNS``).  With ``constraint_type`` the repair follows on the guided
+set; ``walls=True`` takes ``static_obstacles=`` / ``wall_radius=`` into the objective.  Not with ``collision_free_rounds`` (a rerun would
+have to be guided too), ``device_scene`` or ``device_frames`` (the one-entry chains).
 
 Differences from the reference that a caller can observe:
   * the engine (weights on the GPU) is cached across instances: the reference rebuilds the model and reloads the
@@ -91,9 +97,10 @@ import yaml
 
 from . import scene as SC
 from ._lib import EINVAL, ERANGE
-from .engine import JmidEngine, JmidError, wall_segments
+from .engine import Guidance, JmidEngine, JmidError, wall_segments
 from .kde import most_likely_samples
-from .metrics import rejection_totals, repair_causes
+from .metrics import GUIDE_DEFAULTS, rejection_totals, repair_causes
+from .schedule import guidance_weights
 from .weights import JMIDWeights, NetDims
 
 _ENGINE_CACHE: Dict[tuple, JmidEngine] = {}
@@ -174,6 +181,52 @@ def repair_arguments(constraint_type, repair_options=None, static_obstacles=None
     return opts
 
 
+GUIDANCE_OPTIONS = ("scale", "n_inner", "margin", "tau", "weights", "walls", "table")
+
+
+def guidance_arguments(guidance, threshold: float, static_obstacles=None, wall_radius=None, step: Optional[int] = None,
+                       sampling: str = "ddim") -> Optional[Guidance]:
+    """The ``guidance=`` keyword of the forecaster, ``predict_batch`` and ``offline.sample`` - a dict {scale, n_inner, margin, tau, weights,
+    walls: bool, table} - as the ``engine.Guidance`` of ``JmidEngine.denoise``: None without the keyword (nothing changes).  ``step``: the
+    sampler's step count (one weight per entry of its DDIM table).  ``weights`` is the table itself; otherwise ``scale`` (0.02 m, the
+    repair's step) and ``table`` ("alpha_bar") make it (``schedule.guidance_weights``).  ``walls=True`` takes ``static_obstacles`` /
+    ``wall_radius`` into the objective and is refused without them.  The threshold is the call's ``collision_threshold``."""
+    if guidance is None:
+        return None
+    if sampling != "ddim":
+        raise ValueError("guidance needs the DDIM sampler (a DDPM step draws noise behind the correction)")
+    opts = dict(guidance)
+    unknown = sorted(set(opts) - set(GUIDANCE_OPTIONS))
+    if unknown:
+        raise ValueError(f"unknown guidance options {unknown} (known: {list(GUIDANCE_OPTIONS)})")
+    if step is None:
+        raise ValueError("guidance needs the sampler's step count")
+    margin, tau = float(opts.get("margin", GUIDE_DEFAULTS["margin"])), float(opts.get("tau", GUIDE_DEFAULTS["tau"]))
+    n_inner = int(opts.get("n_inner", GUIDE_DEFAULTS["n_inner"]))
+    if not (np.isfinite(margin) and margin >= 0.0):
+        raise ValueError("guidance['margin'] must be finite and >= 0")
+    if not (np.isfinite(tau) and tau > 0.0):
+        raise ValueError("guidance['tau'] must be finite and > 0")
+    if not 1 <= n_inner <= 64:
+        raise ValueError("guidance['n_inner'] must lie in 1..64")
+    if opts.get("weights") is not None:
+        if "scale" in opts or "table" in opts:
+            raise ValueError("guidance takes either weights or scale / table")
+        weights = np.asarray(opts["weights"], dtype=np.float64).reshape(-1)
+        if weights.size != len(range(100, 0, -int(100 / step))):
+            raise ValueError(f"guidance['weights'] must hold one weight per step-table entry ({len(range(100, 0, -int(100 / step)))})")
+        if not (np.isfinite(weights).all() and (weights >= 0.0).all()):
+            raise ValueError("guidance['weights'] must be finite and >= 0")
+    else:
+        weights = guidance_weights(float(opts.get("scale", GUIDE_DEFAULTS["scale"])), step, table=opts.get("table", "alpha_bar"))
+    walls = {}
+    if opts.get("walls"):
+        if static_obstacles is None or wall_radius is None:
+            raise ValueError("guidance with walls=True needs static_obstacles and wall_radius")
+        walls = wall_arguments(static_obstacles, wall_radius, 1)
+    return Guidance(float(threshold), margin, tau, weights, n_inner, walls.get("walls"), walls.get("wall_radius"))
+
+
 def repair_totals(episode) -> Tuple[int, int, int, int]:
     """``episode`` [..., 3] of ``JmidEngine.repair_collisions`` -> (samples with collisions, repaired, reverted, largest iteration count)."""
     ep = np.asarray(episode.detach().cpu() if hasattr(episode, "detach") else episode).reshape(-1, 3).astype(np.int64)
@@ -190,24 +243,31 @@ class Constraints(NamedTuple):
     walls: dict = {}                  # the loop's {walls, wall_radius} keywords, or {}
     repair: Optional[dict] = None     # the repair stage (JmidEngine.repair_collisions) and its keywords, the walls of "opt_softplus_walls" among them; None: no stage
     padded: bool = False              # predict_batch: ONE loop for the whole padded batch instead of one per count group
+    guidance: Optional[Guidance] = None      # guided sampling (JmidEngine.denoise(guidance=)): the collision steps between the denoise steps; None: none
 
 
 def sampling_constraints(rounds: Optional[int] = None, threshold: float = 0.2, static_obstacles=None, wall_radius=None,
-                         constraint_type: Optional[str] = None, repair_options: Optional[dict] = None, padded: bool = False) -> Constraints:
+                         constraint_type: Optional[str] = None, repair_options: Optional[dict] = None, padded: bool = False,
+                         guidance: Optional[dict] = None, step: Optional[int] = None, sampling: str = "ddim") -> Constraints:
     """``Constraints`` from the public keywords, with every refusal that is about them: ``rounds`` is ``collision_free_rounds`` where it is
     > 0 (``offline.sample``: ``max_rounds`` under ``with_constraints=True``) and None otherwise, ``threshold`` is ``collision_threshold``,
     ``padded`` is ``collision_free_padded``.  What a caller refuses itself is what only it knows: its RNG contract, ``padded=``, the
-    sampler's ``bestof`` / ``sampling``."""
+    sampler's ``bestof`` / ``sampling``.  ``guidance`` (with the sampler's ``step`` and ``sampling``): ``guidance_arguments``; not with a
+    redraw loop - a rerun would have to be guided too - and composed with the repair: guide, then repair what is left."""
     if rounds is not None and not 0 <= int(rounds) <= 64:
         raise ValueError("collision_free_rounds must lie in 0..64")
     threshold = float(threshold)
     if not (np.isfinite(threshold) and threshold >= 0.0):
         raise ValueError("collision_threshold must be finite and >= 0")
     repair = repair_arguments(constraint_type, repair_options, static_obstacles, wall_radius)
-    walls = wall_arguments(static_obstacles, wall_radius, int(rounds is not None), repair is not None and "walls" in repair)
+    guide = guidance_arguments(guidance, threshold, static_obstacles, wall_radius, step, sampling)
+    if guide is not None and rounds is not None:
+        raise ValueError("guidance cannot be combined with collision_free_rounds (a rerun would have to be guided too: not built)")
+    walls = wall_arguments(static_obstacles, wall_radius, int(rounds is not None),
+                           (repair is not None and "walls" in repair) or (guide is not None and guide.walls is not None))
     if padded and rounds is None:
         raise ValueError("collision_free_padded needs collision_free_rounds > 0")
-    return Constraints(None if rounds is None else int(rounds), threshold, walls, repair, bool(padded))
+    return Constraints(None if rounds is None else int(rounds), threshold, walls, repair, bool(padded), guide)
 
 
 def repair_stage(engine: JmidEngine, pos, dims: Tuple[int, int, int, int], threshold: float, options: dict, n_agents=None, p0=None,
@@ -328,7 +388,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  lib_path: Optional[str] = None, device_scene: Optional[bool] = None, device_frames: Optional[bool] = None,
                  seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False, coast_frames: int = 0,
                  collision_free_rounds: int = 0, collision_threshold: float = 0.2, static_obstacles=None,
-                 wall_radius: Optional[float] = None, constraint_type: Optional[str] = None, repair_options: Optional[dict] = None):
+                 wall_radius: Optional[float] = None, constraint_type: Optional[str] = None, repair_options: Optional[dict] = None,
+                 guidance: Optional[dict] = None):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -388,8 +449,18 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # > 0 (opt-in, needs rng_compat="device": a redraw is a draw number of the counter generator): collision-free sampling, up to that
         # many reruns of a scene whose joint samples collide at collision_threshold metres; rejection: the last call's totals
         self.collision_free_rounds, self.collision_threshold = int(collision_free_rounds), float(collision_threshold)
+        # guidance={scale, n_inner, margin, tau, weights, walls, table} (opt-in, every RNG contract): softplus collision steps between the
+        # denoise steps (JmidEngine.denoise(guidance=)) - the staged route, not with collision_free_rounds or the one-entry chains;
+        # composes with constraint_type: guide, then repair what is left.  guide: the last call's rows [K, 2] (metrics.GUIDE_COLUMNS)
+        step = None
+        if guidance is not None:
+            if device_scene or device_frames:
+                raise ValueError("guidance has no one-entry chain: not with device_scene or device_frames")
+            with open(mid_config_file) as f:
+                step = int(yaml.safe_load(f)["step_size"])
         self.constraints = sampling_constraints(self.collision_free_rounds or None, collision_threshold, static_obstacles, wall_radius,
-                                                constraint_type, repair_options)
+                                                constraint_type, repair_options, guidance=guidance, step=step)
+        self.guide: Optional[np.ndarray] = None
         self._walls, self._repair_options = self.constraints.walls, self.constraints.repair      # (read by tests/)
         if self.constraints.rounds is not None and self.rng_compat != "device":
             raise ValueError("collision_free_rounds needs rng_compat='device' (a redraw is a draw number of the library's counter generator)")
@@ -621,7 +692,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         check = self.self_check and (1, K * A, H, 2) not in self._checked_shapes
         route = plan_route(k=k, K=K, A=A, H=H, device_topk=self.device_topk, device_scene=self.device_scene,
                            device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped",
-                           tracks=present is not None, collision_free=limits.rounds is not None, repair=limits.repair is not None)
+                           tracks=present is not None, collision_free=limits.rounds is not None, repair=limits.repair is not None,
+                           guidance=limits.guidance is not None)
         result, call = None, dict(dt=self.time_step, precision=self.precision)
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
@@ -659,6 +731,8 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                     self.rejection = rejection_totals(out.rejection.episodes, out.rejection.cause)
                 if out.repair is not None:
                     self.repair, self.repair_causes = repair_totals(out.repair), out.repair_causes
+                if out.guide is not None:
+                    self.guide = np.asarray(out.guide)[0]
                 rows, logw, t2 = out.rows, out.logw, out.rank_started
         t3 = time.perf_counter()
         if result is None:
@@ -719,7 +793,8 @@ def scene_source(device_scene: bool, device_frames: bool, short: bool = False, f
 
 def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, device_scene: bool = False, device_frames: bool = False,
                check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False,
-               resident: bool = False, tracks: bool = False, collision_free: bool = False, repair: bool = False) -> Route:
+               resident: bool = False, tracks: bool = False, collision_free: bool = False, repair: bool = False,
+               guidance: bool = False) -> Route:
     """Every decision of a call that does not need an array: the flags, k of K samples, A in-cluster pedestrians, horizon H, whether the
     first-call self check is due (``check``), whether the window is short (``short``) and whether the histories are frames (``frames``).
     ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count, ``resident``: that form on the
@@ -727,7 +802,8 @@ def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, devi
     ``collision_free``: collision-free sampling (``collision_free_rounds`` > 0) - the rejection loop has no one-entry chain, so the run is
     staged (encode -> ``denoise_reject`` -> rank) and the ranking reads the accepted set where the loop left it.
     ``repair``: collision repair (``constraint_type="opt_softplus"``) - a stage between the denoise call and the ranking, so the run is
-    staged too (encode -> denoise -> ``repair_collisions`` -> rank); with neither of the two nothing changes."""
+    staged too (encode -> denoise -> ``repair_collisions`` -> rank).  ``guidance``: guided sampling - the guided denoise call has no
+    one-entry chain either, so the run is staged; with none of the three nothing changes."""
     scene = scene_source(device_scene, device_frames, short, frames, batch, resident, tracks)
     # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits - the reference
     # has none - the host twin ranks them
@@ -738,7 +814,7 @@ def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, devi
     else:           # a short window built on the host is staged: jmid_predict has no first_index (a resident one is predict_scene's)
         chain = not (short and scene == "host")
     chain = chain and (on_dev or k == K) and not check        # (the self check compares the staged denoise call's positions)
-    chain = chain and not collision_free and not repair
+    chain = chain and not collision_free and not repair and not guidance
     rank = "none" if k >= K else "host" if not on_dev else "device" if check else "device_resident"
     return Route(scene, "chain" if chain else "staged", rank)
 
@@ -792,21 +868,28 @@ class Staged(NamedTuple):
     repair_causes: Optional[dict]      # ``metrics.repair_causes`` of a repair with walls
     fell_back: bool                    # JMID_ERANGE: the denoise stage was repeated in exact fp32
     rank_started: float                # ``time.perf_counter()`` between the repair and the ranking (the forecaster's timings split there)
+    guide: Optional[np.ndarray] = None      # the guided denoise call's rows [E, K, 2] (``metrics.GUIDE_COLUMNS``); None: no guidance
 
 
 def denoise_stage(engine: JmidEngine, ctx, p0, constraints: Constraints, dt: float, x_T=None, seeded: Optional[dict] = None, draw0: int = 0,
                   n_agents=None):
     """The denoise stage of a staged run as a callable (precision, want_pos) -> (pos [E, K, A, H, 2] or None when the samples stay on the
     device, ``Rejection`` or None): the redraw loop from ``draw0`` when the constraints ask for one, else one denoise call.  Either
-    ``x_T`` or ``seeded``, the seed / episode_ids / K / T keywords of a seeded call (a repeat then draws the same noise)."""
+    ``x_T`` or ``seeded``, the seed / episode_ids / K / T keywords of a seeded call (a repeat then draws the same noise).  With guidance
+    among the constraints the call is the guided one, and ``stage.guide`` holds the rows [E, K, 2] of its last run."""
     seeded = seeded or {}
 
     def stage(precision: str, want_pos: bool):
+        if constraints.guidance is not None:
+            _, pos, stage.guide = engine.denoise(x_T, ctx, p0, dt=dt, precision=precision, want_vel=False, want_pos=want_pos,
+                                                 guidance=constraints.guidance, want_guide=True, **seeded)
+            return pos, None
         if constraints.rounds is None:
             return engine.denoise(x_T, ctx, p0, dt=dt, precision=precision, want_vel=False, want_pos=want_pos, **seeded)[1], None
         out = engine.denoise_reject(ctx, p0, dt=dt, precision=precision, threshold=constraints.threshold, max_rounds=constraints.rounds,
                                     draw0=draw0, want_vel=False, want_pos=want_pos, n_agents=n_agents, **constraints.walls, **seeded)
         return out[1], Rejection(out[2], out[3], out[4] if len(out) > 4 else None)      # (the engine gives four values, or five)
+    stage.guide = None
     return stage
 
 
@@ -825,7 +908,7 @@ def run_staged(engine: JmidEngine, ctx, p0, dims: Tuple[int, int, int, int], con
         pos, episode, causes = repair_stage(engine, pos, dims, constraints.threshold, constraints.repair, n_agents=n_agents, p0=p0, dt=dt)
     rank_started = time.perf_counter()
     rows, logw = rank_samples(engine, rank, pos, k, dims, n_agents)
-    return Staged(rows, logw, rejection, episode, causes, fell_back, rank_started)
+    return Staged(rows, logw, rejection, episode, causes, fell_back, rank_started, stage.guide)
 
 
 def _engine_lock_of(engine: JmidEngine) -> RLock:
@@ -840,7 +923,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   padded=False, short_history: bool = False, first_frame=None, collision_free_rounds: int = 0,
                   collision_threshold: float = 0.2, stats: Optional[dict] = None, static_obstacles=None,
                   wall_radius: Optional[float] = None, collision_free_padded: bool = False, constraint_type: Optional[str] = None,
-                  repair_options: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  repair_options: Optional[dict] = None, guidance: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -904,13 +987,21 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     ``static_obstacles=`` (walls are not in the objective); with ``padded=`` the batch takes the count groups.
     ``constraint_type="opt_softplus_walls"`` (needs ``static_obstacles=`` and ``wall_radius=``): the repair with the walls in its objective and
     in both gates, every call with its group's ``p0``; ``stats`` also gets ``repair_causes``, the sums of ``metrics.repair_causes``.
+    ``guidance=`` {scale, n_inner, margin, tau, weights, walls, table} (opt-in, with either ``noise``; ``guidance_arguments``): guided
+    sampling - every group's denoise call runs softplus collision steps at ``collision_threshold`` between its denoise steps
+    (``engine.denoise(guidance=)``), every group is staged, and ``stats`` gets ``guide`` [E, K, 2] = ``metrics.GUIDE_COLUMNS``, rows in
+    input order.  It composes with ``constraint_type``: guide, then repair what is left.  Not with ``collision_free_rounds`` (a rerun
+    would have to be guided too), a DDPM table, ``padded=``, ``device_scene`` or ``device_frames`` (the one-entry chains).
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
     if padded not in (False, True, "resident"):
         raise ValueError("padded must be False, True or 'resident'")
+    sampler = {} if guidance is None else dict(step=engine.step, sampling=engine.sampling)      # (one weight per entry of the engine's table)
     limits = sampling_constraints(int(collision_free_rounds) or None, collision_threshold, static_obstacles, wall_radius, constraint_type,
-                                  repair_options, collision_free_padded)
+                                  repair_options, collision_free_padded, guidance=guidance, **sampler)
+    if limits.guidance is not None and (padded or device_scene or device_frames):
+        raise ValueError("guidance has no one-entry chain: not with padded=, device_scene or device_frames")
     if limits.rounds is not None:
         if padded:
             raise ValueError("collision_free_rounds has no padded form (jmid_denoise_reject_seeded takes one agent count per call)")
@@ -944,7 +1035,7 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     def plan(A, padded=False, resident=False):
         return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
                           short=ff is not None, batch=True, padded=padded, resident=resident, collision_free=limits.rounds is not None,
-                          repair=limits.repair is not None)
+                          repair=limits.repair is not None, guidance=limits.guidance is not None)
 
     def torch_x_T(e, A):
         return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
@@ -1007,6 +1098,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     logw = np.empty((E, N, k), dtype=np.float64)
     if limits.repair is not None and stats is not None:
         stats["repair"] = np.zeros((E, 3), dtype=np.int32)
+    if limits.guidance is not None and stats is not None:
+        stats["guide"] = np.zeros((E, K, 2), dtype=np.float32)
     if limits.rounds is not None and stats is not None:
         stats["episodes"], stats["slots"] = np.zeros((E, 3), dtype=np.int32), np.zeros((E, K, 3), dtype=np.int32)
         if limits.walls:
@@ -1048,6 +1141,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
             stats["repair"][eps] = out.repair
         if out.repair_causes is not None:
             causes.append(out.repair_causes)
+        if out.guide is not None and stats is not None:
+            stats["guide"][eps] = out.guide
         forecasts[eps], logw[eps] = SC.assemble_forecasts(inc[eps], out.rows, out.logw, b["cv"][eps], pose_now[eps], k, K)
     if causes and stats is not None:            # the groups' counts, summed
         stats["repair_causes"] = {key: sum(c[key] for c in causes) for key in causes[0]}

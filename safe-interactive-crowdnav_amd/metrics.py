@@ -18,6 +18,9 @@ Collision repair (``repair_collisions_host``; ``csrc/repair.hpp``, ``jmid_repair
 states for the reference's ``constraint_type: opt_softplus``: colliding samples are pushed apart under a softplus penalty on that
 clearance until the predicate holds, or come back as they were.
 
+Guided sampling (``guide_step_host``; ``csrc/guide.hpp``, ``jmid_guide_step``) is the twin of one guidance step of the denoise loop: the
+velocity state integrated to positions, at most ``n_inner`` steps of the repair's own iteration, the displacement written back.
+
 The wall statistics (``wall_statistics_host``, ``summarise_walls``; ``csrc/wall_stats.hpp``, ``jmid_wall_statistics``) take the
 reference simulator's predicate: a step hits a wall when ``closest_distance_between_line_segments(wall, step) - radius < 0``
 (crowd_sim_plus/envs/crowd_sim_plus.py:885-893, crowd_sim_plus/envs/utils/utils_plus.py:205-338).
@@ -521,7 +524,7 @@ def _repair_iterate(x: np.ndarray, threshold: float, margin: float, tau: float, 
         xa = x[idx]
         g = np.zeros_like(xa)
         dmin = np.full(idx.size, np.inf)
-        for b in range(n):                                   # partners ascending; a partner's segment t - 1 before its segment t
+        for b in range(n if T > 1 else 0):                   # partners ascending; a partner's segment t - 1 before its segment t (T = 1: no segment)
             lo, hi = np.minimum(agents, b), np.maximum(agents, b)
             d, u, nx, ny, sigma = _repair_segments(xa, lo, hi, m, tau, exp)
             real = (agents != b)[None, :, None]
@@ -642,6 +645,83 @@ def repair_collisions_host(pos: np.ndarray, threshold: float = COLLISION_THRESHO
     if walls is None:
         return out, vel_out, sample, episode
     return out, vel_out, sample, episode, wall
+
+
+GUIDE_COLUMNS = ("steps", "iterations")
+# the defaults of guided sampling (include/jmid_hip.h, ``jmid_denoise_guided``): arguments of the entries, not constants of the rule
+GUIDE_DEFAULTS = {"margin": 0.02, "tau": 0.005, "scale": 0.02, "n_inner": 4}
+
+
+def guide_step_host(x: np.ndarray, p0: np.ndarray, dt: float, threshold: float = COLLISION_THRESHOLD, margin: float = GUIDE_DEFAULTS["margin"],
+                    tau: float = GUIDE_DEFAULTS["tau"], weight: float = GUIDE_DEFAULTS["scale"], n_inner: int = GUIDE_DEFAULTS["n_inner"],
+                    n_agents=None, walls=None, wall_radius: Optional[float] = None, exp=np.exp, return_positions: bool = False):
+    """The NumPy twin of one guidance step (``jmid_guide_step``; include/jmid_hip.h states the rule, ``csrc/guide.hpp`` is the kernel):
+    x [E, K*A, T, 2] float32 velocities (row s*A + a), p0 [E, A, 2] -> (x_out float32, rows float64 [E, K, 2] = ``GUIDE_COLUMNS``: 1 if the
+    sample iterated, the iterations it used).  Per joint sample, in float64: integrate from p0 (ascending t), run at most ``n_inner``
+    iterations of the repair's own iteration (``_repair_iterate``, the functions ``repair_collisions_host`` runs) with step := ``weight``
+    metres, and write the displacement back as velocity differences, one rounding per point.  A sample that stops before its first
+    iteration - or has a point that is not finite - keeps its bits; ``weight = 0`` returns the input.  ``n_agents`` [E]: a padded block -
+    the rule on every compacted episode, the padded rows as they are.  ``walls`` [L, 4] or [L, 2, 2] with ``wall_radius``: the wall terms
+    of ``jmid_repair_collisions_walls`` with p0 as the fixed first point of every path.  ``return_positions``: a third value, the pair
+    (q_initial, q_final) float64 [E, K, A, T, 2] (NaN in padded rows)."""
+    x = np.asarray(x)
+    if x.dtype != np.float32 or x.ndim != 4 or x.shape[-1] != 2:
+        raise ValueError("x must be float32 [E, K*A, T, 2] (the rule is defined on the fp32 state)")
+    if p0 is None:
+        raise ValueError("p0 is required (the guidance is defined on positions)")
+    p0 = np.asarray(p0, dtype=np.float32)
+    E, KA, T, _ = x.shape
+    if p0.ndim != 3 or p0.shape[0] != E or p0.shape[2] != 2 or KA % p0.shape[1]:
+        raise ValueError("p0 must be [E, A, 2] with K*A rows of x per episode")
+    A = int(p0.shape[1])
+    K = KA // A
+    for name, v, low in (("threshold", threshold, True), ("margin", margin, True), ("tau", tau, False), ("weight", weight, True)):
+        if not (np.isfinite(v) and (v >= 0.0 if low else v > 0.0)):
+            raise ValueError(f"{name} must be finite and {'>= 0' if low else '> 0'}")
+    if not (np.isfinite(dt) and dt > 0.0):
+        raise ValueError("dt must be finite and > 0")
+    if not 1 <= int(n_inner) <= 64:
+        raise ValueError("n_inner must lie in 1..64")
+    if walls is None and wall_radius is not None:
+        raise ValueError("wall_radius is given without walls")
+    if walls is not None:
+        walls = np.asarray(walls, dtype=np.float64).reshape(-1, 4)
+        if wall_radius is None or not (np.isfinite(wall_radius) and wall_radius >= 0.0):
+            raise ValueError("walls need a wall_radius that is finite and >= 0")
+        if not np.isfinite(walls).all():
+            raise ValueError("a wall has a non-finite coordinate")
+        if walls.shape[0] > 64:
+            raise ValueError("at most 64 walls")
+        if walls.shape[0] == 0:
+            walls = None
+    counts = _counts(n_agents, E, A) if n_agents is not None else np.full(E, A, dtype=np.int64)
+    dtd = float(np.float32(dt))
+    out = x.copy()
+    view = out.reshape(E, K, A, T, 2)
+    rows = np.zeros((E, K, 2))
+    q_init, q_fin = np.full((E, K, A, T, 2), np.nan), np.full((E, K, A, T, 2), np.nan)
+    for e in range(E):
+        n = int(counts[e])
+        v = x.reshape(E, K, A, T, 2)[e, :, :n].astype(np.float64)
+        lead = p0[e, :n].astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            q0 = lead[None, :, None, :] + dtd * np.cumsum(v, axis=2)      # (a sequential sum, ascending t)
+        q_init[e, :, :n] = q_fin[e, :, :n] = q0
+        ok = np.flatnonzero(np.isfinite(q0).all(axis=(1, 2, 3)))
+        if not (weight > 0.0) or not ok.size or (T == 1 and walls is None):
+            continue
+        q, iters = _repair_iterate(q0[ok], float(threshold), float(margin), float(tau), float(weight), int(n_inner), exp, walls,
+                                   0.0 if walls is None else float(wall_radius), lead if walls is not None else None)
+        moved = iters > 0
+        D = q[moved] - q0[ok[moved]]
+        dD = D - np.concatenate([np.zeros_like(D[:, :, :1]), D[:, :, :-1]], axis=2)
+        view[e, ok[moved], :n] = (v[ok[moved]] + dD / dtd).astype(np.float32)
+        q_fin[e, ok[moved], :n] = q[moved]
+        rows[e, ok, 0] = moved
+        rows[e, ok, 1] = iters
+    if return_positions:
+        return out, rows, (q_init, q_fin)
+    return out, rows
 
 
 def repair_causes(sample, wall, threshold: float, wall_radius: float) -> Dict[str, int]:

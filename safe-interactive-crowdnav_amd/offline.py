@@ -34,7 +34,7 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
            precision: str = "f32", _integrate=None, seed: Optional[int] = None, with_constraints: bool = False,
            collision_threshold: float = 0.2, max_rounds: int = 3, static_obstacles=None,
            wall_radius: Optional[float] = None, constraint_type: Optional[str] = None,
-           repair_options: Optional[dict] = None) -> Tuple[np.ndarray, int, int, int, int]:
+           repair_options: Optional[dict] = None, guidance: Optional[dict] = None) -> Tuple[np.ndarray, int, int, int, int]:
     """-> (vel [sample, B, num_points, 2] float32, number_of_steps, 0, 0, 0)   (diffusion.py:603-613).
     ``_integrate`` = (p0 [B, 2], dt): used by ``generate`` - the same call also integrates on the device (integrate_kernel) and
     the first element of the result is the positions instead.
@@ -54,10 +54,20 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     max_iter}.  Not with ``static_obstacles=``: walls are not in the objective.
     ``constraint_type="opt_softplus_walls"``: the same with the walls of ``static_obstacles=`` / ``wall_radius=`` (both needed) in the
     objective and in both gates (``jmid_repair_collisions_walls``): a sample whose paths, the step from p0 included, come closer than
-    ``wall_radius`` to a wall is a candidate too; "with collisions" then reads "not acceptable for either cause"."""
-    limits = sampling_constraints(max_rounds if with_constraints else None, collision_threshold, static_obstacles, wall_radius, constraint_type,
-                                  repair_options)
-    redraw = with_constraints and limits.repair is None      # (here the repair stands in for the redraws; in the forecaster it follows them)
+    ``wall_radius`` to a wall is a candidate too; "with collisions" then reads "not acceptable for either cause".
+    ``guidance=`` {scale, n_inner, margin, tau, weights, walls, table} (with ``with_constraints=True`` and ``sampling="ddim"``; needs
+    positions): guided sampling INSTEAD of redraws (``JmidEngine.denoise(guidance=)``, every sample an episode with K = 1) - softplus
+    collision steps at ``collision_threshold`` between the denoise steps, on either RNG contract; with ``constraint_type`` the repair
+    follows on what is left, and without one the last three values are (the largest iteration total of a sample, samples that were
+    guided, 0)."""
+    if guidance is not None and not with_constraints:
+        raise ValueError("guidance needs with_constraints=True")
+    if guidance is not None and _integrate is None:
+        raise ValueError("guidance needs positions (generate, or _integrate)")
+    limits = sampling_constraints(max_rounds if with_constraints and guidance is None else None, collision_threshold, static_obstacles, wall_radius,
+                                  constraint_type, repair_options, guidance=guidance, step=step, sampling=sampling)
+    # (here the repair, or the guidance, stands in for the redraws; in the forecaster the repair follows them)
+    redraw = with_constraints and limits.repair is None and limits.guidance is None
     if limits.repair is not None and not with_constraints:
         raise ValueError("constraint_type needs with_constraints=True")
     if limits.repair is not None and _integrate is None:
@@ -102,6 +112,10 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
     if redraw:
         pos, rejection = denoise_stage(engine, ctx_e, p0, limits, dt, seeded=noise)(precision, True)
         totals = rejection_totals(rejection.episodes)
+    elif limits.guidance is not None:
+        _, pos, guide = engine.denoise(x_T, ctx_e, p0, dt=dt, precision=precision, want_vel=False, guidance=limits.guidance, want_guide=True,
+                                       **{key: v for key, v in noise.items() if key != "z"})
+        totals = (int(guide[..., 1].max()), int((guide[..., 0] > 0).sum()), 0)
     else:
         _, pos = engine.denoise(x_T, ctx_e, p0, dt=dt, precision=precision, want_vel=False, **noise)
     if limits.repair is not None:
@@ -113,19 +127,20 @@ def sample(engine: JmidEngine, num_points: int, context, sample: int, bestof: bo
 def generate(engine: JmidEngine, context, p0, dt: float, num_points: int, sample_n: int, bestof: bool,
              flexibility: float = 0.0, sampling: str = "ddpm", step: int = 100, precision: str = "f32", seed: Optional[int] = None,
              with_constraints: bool = False, collision_threshold: float = 0.2, max_rounds: int = 3, static_obstacles=None,
-             wall_radius: Optional[float] = None, constraint_type: Optional[str] = None, repair_options: Optional[dict] = None):
+             wall_radius: Optional[float] = None, constraint_type: Optional[str] = None, repair_options: Optional[dict] = None,
+             guidance: Optional[dict] = None):
     """Tail of ``AutoEncoder.generate``: ``sample`` + ``SingleIntegrator.integrate_samples``
     (``single_integrator.py:290-321``): pos = cumsum(vel, T) * dt + p0[b].  ``context`` [B, ctx] is the encoder
     output (``JmidEngine.encode``), ``p0`` [B, 2] the current positions.  -> (pos [sample, B, T, 2], steps, 0, 0, 0); with
     ``with_constraints=True`` (see ``sample``) the zeros are (num_iter, samples with collisions, samples fixed); ``static_obstacles`` /
     ``wall_radius`` as there; with ``constraint_type="opt_softplus"`` they are (the largest iteration count, samples with collisions,
     samples repaired) of the collision repair; ``"opt_softplus_walls"`` needs ``static_obstacles`` / ``wall_radius`` and repairs for either
-    cause."""
+    cause; ``guidance=`` as there."""
     pos, nsteps, a, b, c = sample(engine, num_points, context, sample_n, bestof, flexibility=flexibility,
                                   sampling=sampling, step=step, precision=precision, _integrate=(p0, dt), seed=seed,
                                   with_constraints=with_constraints, collision_threshold=collision_threshold, max_rounds=max_rounds,
                                   static_obstacles=static_obstacles, wall_radius=wall_radius, constraint_type=constraint_type,
-                                  repair_options=repair_options)
+                                  repair_options=repair_options, guidance=guidance)
     return np.asarray(pos, dtype=np.float32), nsteps, a, b, c
 
 

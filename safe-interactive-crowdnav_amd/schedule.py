@@ -124,3 +124,26 @@ def ddpm_steps(sched: VarianceSchedule, step: int, flexibility: float = 0.0) -> 
                             c1=np.float32(((1 - al[t]) / torch.sqrt(1 - ab[t])).item()), sigma=np.float32(sg[t].item()),
                             noise=t > 1))
     return out
+
+
+def guidance_weights(scale: float = 0.02, step: int = 50, sched: VarianceSchedule = None, table: str = "alpha_bar") -> np.ndarray:
+    """The per-entry weights of guided sampling (``jmid_denoise_guided``: metres, one per entry of the DDIM table of ``step``) -> float64
+    [n_steps].  ``table="alpha_bar"`` (the default): ``weights[i] = scale * alpha_bar`` of the timestep the state is at AFTER entry i
+    (``t - stride``) - about 0 on pure noise, where integrated noise is not a path worth pushing, and ``scale`` behind the last entry
+    (alpha_bar[0] = 1).  ``table="last_half"``: 0 behind the first half of the entries, ``scale`` behind the rest.  ``table="flat"``:
+    ``scale`` everywhere.  ``scale`` defaults to the repair's step, 0.02 m."""
+    if not (np.isfinite(scale) and scale >= 0.0):
+        raise ValueError("scale must be finite and >= 0")
+    sched = sched or VarianceSchedule.linear()
+    tab = ddim_steps(sched, step)
+    stride = int(100 / step)
+    n = len(tab)
+    if table == "alpha_bar":
+        w = [float(scale) * float(sched.alpha_bars[s.t - stride]) for s in tab]
+    elif table == "last_half":
+        w = [0.0 if i < n // 2 else float(scale) for i in range(n)]
+    elif table == "flat":
+        w = [float(scale)] * n
+    else:
+        raise ValueError("table must be 'alpha_bar', 'last_half' or 'flat'")
+    return np.asarray(w, dtype=np.float64)

@@ -10,7 +10,8 @@ Every figure is the median over the measured calls after warm-up; the three vari
 interleaved call by call, so clock and thermal drift hit them alike.  Run on the GPU box:
     python tools/reject_timing.py [--precision f16mx] [--calls 40] [--episodes 4]
 --rule RULE measures the wall predicate instead (section 33), --padded the one-loop form on mixed-count batches (section 34), --repair
-collision repair against the redraw loop (section 35), --repair --rule RULE collision repair with walls on that rule's frames (section 37)."""
+collision repair against the redraw loop (section 35), --repair --rule RULE collision repair with walls on that rule's frames (section 37),
+--guide guided sampling against no flag, the repair, both and the redraw loop (section 38; with --rule RULE on that rule's frames, walls in)."""
 import argparse
 import json
 import os
@@ -284,6 +285,99 @@ def repair_walls_main(args, weights):
     return out
 
 
+def guide_main(args, weights):
+    """--guide: what guided sampling (``guidance=``) costs per ``predict_ret_best()`` and what it does to the share of colliding samples
+    (docs/NOTEBOOK.md section 38).  The forecasters of ONE process on the same frames, seeds and draw numbers, alternating call by call:
+      (a) the staged route without a flag      (b) constraint_type="opt_softplus"      (c) guidance (the defaults: scale 0.02 m x alpha_bar,
+      n_inner 4)      (d) guidance + opt_softplus      (e) collision_free_rounds=3      (f) guidance with the alternative table: the last
+      half of the steps at scale, nothing before.
+    With --rule RULE the frames are that rule's hallway frames and (b), (c), (d), (e), (f) take its walls at --radius ("opt_softplus_walls").
+    After every timed call the collision (and wall) statistics entries judge the set the call left resident: ``share_colliding`` is the
+    share of samples that still fail at --threshold (for either cause with walls); behind a repair stage it is the repair's reverted share.
+    No gate: everything is read against (a) of the same run."""
+    from safe_interactive_crowdnav_amd import scene as SC
+    walls = None
+    if args.rule:
+        from safe_interactive_crowdnav_amd import crowd_env
+        walls = crowd_env.static_obstacles(args.rule)[0]
+        if not len(walls):
+            raise SystemExit(f"rule {args.rule!r} has no walls")
+    out = {"threshold": args.threshold, "rule": args.rule, "radius": args.radius if walls is not None else None}
+    for point, (N, K, k, H, step) in POINTS.items():
+        frames = 6 + args.warmup + args.calls
+        if walls is None:
+            sim = EP.simulate_circle_crossing(args.episodes, N, frames, seed=11)
+        else:
+            sim = crowd_env.simulate_hallway(args.episodes, N, frames, seed=11, cfg=crowd_env.HallwayConfig(rule=args.rule))
+        obstacles = {} if walls is None else dict(static_obstacles=walls, wall_radius=args.radius)
+        repair = "opt_softplus" if walls is None else "opt_softplus_walls"
+        gopt = {} if walls is None else {"walls": True}
+        with tempfile.TemporaryDirectory() as td:
+            env, yp = write_configs(td, joint=True, ctx_dim=256, N=N, K=K, k_ret=k, H=H, step=step, time_step=0.25)
+            common = dict(weights=weights, precision=args.precision, self_check=False, rng_compat="device", seed=7, collision_threshold=args.threshold)
+            variants = {"a_staged": Staged(env, yp, **common),
+                        "b_" + repair: HumanTrajectoryForecasterSim(env, yp, constraint_type=repair, **obstacles, **common),
+                        "c_guidance": HumanTrajectoryForecasterSim(env, yp, guidance=dict(gopt), **obstacles, **common),
+                        "d_guidance_" + repair: HumanTrajectoryForecasterSim(env, yp, guidance=dict(gopt), constraint_type=repair, **obstacles, **common),
+                        "e_rounds_3": HumanTrajectoryForecasterSim(env, yp, collision_free_rounds=3, **obstacles, **common),
+                        "f_guidance_last_half": HumanTrajectoryForecasterSim(env, yp, guidance=dict(gopt, table="last_half"), **obstacles, **common)}
+        ms = {name: [] for name in variants}
+        bad = {name: 0 for name in variants}
+        fix = {name: np.zeros(3, dtype=np.int64) for name in variants}
+        guided = {name: np.zeros(2, dtype=np.int64) for name in variants}
+        samples = 0
+        for e in range(args.episodes):
+            for f in variants.values():
+                f.prev_states, f.prev_robot_states = [[] for _ in range(N)], []
+            for i in range(frames):
+                for f in variants.values():
+                    f.update_state_hists(St(sim["robot_xy"][e, i]), [St(p) for p in sim["human_xy"][e, i]], float(sim["stamps"][i]))
+                if i < 5:
+                    continue
+                a = variants["a_staged"]
+                sb = SC.build_scene(*SC.frame_table(*a._snapshot(), a.time_step, a.num_hist_frames)[:2], a.time_step, H, a.num_hist_frames)
+                dims = (1, len(sb.ids_in), K, H)
+                order = list(variants.items())
+                order = order[i % len(order):] + order[:i % len(order)]     # alternate who goes first
+                for name, f in order:
+                    t0 = time.perf_counter()
+                    f.predict_ret_best()
+                    dt = 1e3 * (time.perf_counter() - t0)
+                    if i < 5 + args.warmup:
+                        continue
+                    ms[name].append(dt)
+                    if dims[1] >= 1:      # the set the call left resident, judged by the statistics entries (not timed)
+                        flagged = f.engine.collision_statistics(None, args.threshold, dims=dims, agents=False)[2][0, :, 3] > 0
+                        if walls is not None:
+                            flagged = flagged | (f.engine.wall_statistics(None, walls, args.radius, p0=sb.p0[None], dims=dims)[2][0, :, 1] > 0)
+                        bad[name] += int(flagged.sum())
+                    if f.repair is not None:
+                        fix[name] += np.array(f.repair[:3])
+                    if f.guide is not None:
+                        guided[name] += np.array([int((f.guide[:, 0] > 0).sum()), int(f.guide[:, 1].sum())])
+                if i >= 5 + args.warmup:
+                    samples += K
+        res = {name: {"median_ms": round(float(np.median(v)), 3), "p10_ms": round(float(np.percentile(v, 10)), 3),
+                      "p90_ms": round(float(np.percentile(v, 90)), 3), "share_colliding": round(bad[name] / samples, 5)} for name, v in ms.items()}
+        base = res["a_staged"]["median_ms"]
+        for name, f in variants.items():
+            res[name]["minus_a_ms"] = round(res[name]["median_ms"] - base, 3)
+            if f.constraints.repair is not None:
+                # the repair's own rows say what still fails (its reverted samples): at k = K the ranking reads a host copy and the
+                # resident set stays as the denoise call left it
+                res[name].update(share_repaired=round(float(fix[name][1]) / samples, 5), share_reverted=round(float(fix[name][2]) / samples, 5),
+                                 share_colliding_before_repair=round(float(fix[name][0]) / samples, 5), share_colliding=round(float(fix[name][2]) / samples, 5))
+            if guided[name][0]:
+                res[name].update(share_guided=round(float(guided[name][0]) / samples, 5), iterations_per_guided_sample=round(float(guided[name][1]) / float(guided[name][0]), 3))
+        res["calls"], res["samples"] = len(ms["a_staged"]), samples
+        res["erange_fallbacks"] = sum(f.erange_fallbacks for f in variants.values())
+        res["workload"] = (f"N={N}, K={K} -> {k}, H={H}, {step} steps, {args.precision}, " + ("ORCA circle crossing" if walls is None else f"{args.rule} frames, wall radius {args.radius}") +
+                           f", {args.episodes} episodes, threshold {args.threshold}")
+        out[point] = res
+        print(point, json.dumps(res), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16mx")
@@ -295,13 +389,16 @@ def main():
     ap.add_argument("--radius", type=float, default=0.3, help="with --rule: the wall radius in metres")
     ap.add_argument("--padded", action="store_true", help="predict_batch on mixed-count scenes: one loop per count against collision_free_padded")
     ap.add_argument("--repair", action="store_true", help="collision repair (constraint_type='opt_softplus') against collision_free_rounds=3 and no flag")
-    ap.add_argument("--threshold", type=float, default=0.2, help="with --padded / --repair: the collision threshold in metres")
+    ap.add_argument("--guide", action="store_true", help="guided sampling (guidance=) against no flag, the repair, both and collision_free_rounds=3; with --rule: with its walls")
+    ap.add_argument("--threshold", type=float, default=0.2, help="with --padded / --repair / --guide: the collision threshold in metres")
     args = ap.parse_args()
     weights = JMIDWeights.from_seed(NetDims(ctx_dim=256), 5)
-    if args.rule or args.padded or args.repair:
+    if args.rule or args.padded or args.repair or args.guide:
         if args.padded and "--episodes" not in sys.argv:
             args.episodes = 8
-        if args.repair and args.rule:
+        if args.guide:
+            out = guide_main(args, weights)
+        elif args.repair and args.rule:
             out = repair_walls_main(args, weights)
         else:
             out = repair_main(args, weights) if args.repair else padded_main(args, weights) if args.padded else walls_main(args, weights)
