@@ -365,6 +365,11 @@ def main():
         # BASELINE cfg4 at its real step count: one 19 200-key sequence, 50 DDIM steps (split-KV rounding accumulates);
         # ~15 min of reference CPU time: `python tests/golden/make_golden.py net_jmid_w256_a25` regenerates only this one
         ("jmid_w256_a25k64t12_s50", 256, 25, 64, 12, 50, True, 27, 207),
+        # widths between the two above that the reference can build (its nhead is 4): d_model 128 / head 32 and d_model 256 / head 64
+        # (tests/width_cases.py), S = 105 with S % 4 != 0
+        ("jmid_w64_a3k5t7_s5", 64, 3, 5, 7, 5, True, 61, 701),
+        ("imid_w64_a3k5t7_s5", 64, 3, 5, 7, 5, False, 62, 702),
+        ("jmid_w128_a3k5t7_s5", 128, 3, 5, 7, 5, True, 63, 703),
     ]
     for c in net_cases:
         if not ONLY or f"net_{c[0]}.npz".startswith(ONLY):     # (the big case is minutes of CPU: skip it unless asked for)
@@ -378,9 +383,13 @@ def main():
         ("imid_together", "together", False, 256, 5, 20, 20, 12, 2, 32, 305),
         ("jmid_topk", "together", True, 256, 3, 100, 15, 8, 2, 33, 306),   # shipped: K=100 -> k=15, H=8
         ("jmid_w32_spread50", "spread", True, 32, 6, 10, 10, 12, 50, 34, 307),
+        # LSTM hidden 32 and 64: the encoder's generic loop, and predict_ret_best at those widths
+        ("jmid_w64_together", "together", True, 64, 4, 8, 8, 12, 2, 64, 315),
+        ("jmid_w128_together", "together", True, 128, 4, 8, 8, 12, 2, 65, 316),
     ]
     for c in wrapper_cases:
-        gen_wrapper_case(*c)
+        if not ONLY or f"wrapper_{c[0]}.npz".startswith(ONLY):
+            gen_wrapper_case(*c)
     gen_wrapper_case("jmid_singleton", "singleton", True, 256, 4, 8, 8, 12, 2, 36, 310)
     gen_wrapper_case("jmid_one_human", "together", True, 256, 1, 8, 8, 12, 2, 36, 311)
     gen_wrapper_case("jmid_far_ids", "far_ids", True, 256, 5, 8, 8, 12, 2, 36, 312)

@@ -14,6 +14,7 @@ import math
 
 import numpy as np
 
+import width_cases as WC
 from layer_reference import BF8, LAMBDA, PAIR, U32, abs_matmul, bf8, gemm_core, out_term, split16  # noqa: F401  (re-exported for the tests)
 
 G32 = U32 / (1.0 - 16 * U32)      # one fp32 rounding with the products of up to 16 of them folded in (Higham's gamma_n / n)
@@ -85,13 +86,18 @@ def row_of(shape):
 
 
 # ---- the cases (shared by the host and the GPU test) ----
-WIDTHS = [32, 256]                                   # ctx_dim: d_model 64 and 512
+NETS = WC.NETS                                       # (ctx_dim, nhead): every row of tests/width_cases.py
+WIDTHS = WC.CTX_DIMS                                 # their ctx_dim: nothing of the seam reads the head count (dims_of)
+OLD_WIDTHS = WC.OLD_CTX_DIMS                         # d_model 64 and 512: every shape below; the other rows: NEW_SHAPES
 MODES = ["f32", "f16x3", "f16x2", "f16mx"]
 # (E, A, K, T): M = 1; 48 tokens, several hyper rows in a wave's neighbourhood; T odd, 315 tokens across 128-row panels; with
 # "out_traj" = 1 a wave takes 12 tokens + 1; T at the positional table's limit, two full blocks
 SHAPES = [(1, 1, 1, 1), (2, 2, 3, 4), (3, 3, 5, 7), (1, 2, 3, 13), (2, 1, 2, 24)]
 # 49 152 tokens: plan_step picks 12 tokens per wave by itself, half the pieces start at t0 = 12 (d_model 64, "out_traj" = 0)
 BIG_SHAPE, BIG_TPW = (8, 4, 64, 24), 12
+# the rows beyond the two old widths: one token; T odd across 128-row panels; T at the positional table's limit
+NEW_SHAPES = [(1, 1, 1, 1), (3, 3, 5, 7), (2, 1, 2, 24)]
+tail_folds, per_trajectory = WC.tail_folds, WC.per_trajectory      # what the plan does beyond tail_fold.hpp's limits (d_model 1024)
 
 
 def rep_of(precision, d):
@@ -99,8 +105,10 @@ def rep_of(precision, d):
     return "f32" if precision == "f32" else "hi_bf8" if (precision == "f16mx" and d == 512) else "pair"
 
 
-def dims_of(ctx_dim):
-    return 2 * ctx_dim, ctx_dim, ctx_dim // 2        # d_model, d_mid, d_low (weights.NetDims)
+def dims_of(ctx_dim, nhead=None):
+    """d_model, d_mid, d_low (weights.NetDims); with nhead also the head size - which no stage of the seam reads"""
+    dims = (2 * ctx_dim, ctx_dim, ctx_dim // 2)
+    return dims if nhead is None else dims + (2 * ctx_dim // nhead,)
 
 
 def seam_inputs(ctx_dim, shape):

@@ -7,6 +7,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import tests.width_cases as WC
 from safe_interactive_crowdnav_amd.engine import JmidEngine
 from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims
 
@@ -16,9 +17,19 @@ PRECISIONS = ["f32", "f16x3", "f16x2", "f16mx"]
 TOL = {"f32": 2e-5, "f16x3": 4e-5, "f16x2": 2e-3, "f16mx": 2e-3, "f16": 2e-2}
 
 
-@pytest.fixture(scope="module", params=[32, 256])
+@pytest.fixture(scope="module", params=WC.OLD_CTX_DIMS)
 def engine(request):
     eng = JmidEngine(JMIDWeights.from_seed(NetDims(ctx_dim=request.param), 1), joint=True)
+    yield eng
+    eng.close()
+
+
+# head sizes 32 and 64 (attn_f16x3_kernel<32 | 64>, attn_f32_kernel<32 | 64>; 64 also at d_model 512): for the attention test only - the
+# GEMM tests do not depend on the handle's width
+@pytest.fixture(scope="module", params=[(64, 4), (128, 4), (256, 8)], ids=WC.net_id)
+def head_engine(request):
+    assert request.param in WC.NEW_NETS
+    eng = JmidEngine(JMIDWeights.from_seed(NetDims(ctx_dim=request.param[0], nhead=request.param[1]), 1), joint=True)
     yield eng
     eng.close()
 
@@ -44,7 +55,25 @@ def test_gemm_matches_float64(engine, M, N, K, relu, precision):
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
-@pytest.mark.parametrize("nseq,S", [(2, 1200), (7, 12), (3, 48), (2, 33), (1, 129), (5, 1), (2, 24)])
+@pytest.mark.parametrize("M,N,K,relu", [(16800, 576, 192, False), (16800, 192, 192, False), (16800, 384, 192, True), (16800, 192, 384, False)])
+def test_gemm_matches_float64_at_the_batch_shapes_of_d_model_192(engine, M, N, K, relu, precision):
+    """in_proj, out_proj, linear1 and linear2 of d_model 192 (tests/width_cases.py) at 16 800 rows = 131 row tiles of 128 + 32 rows: enough
+    tiles for the 128 x 128 shape (launch_plan.hpp large_gemm_shape), whose last column tile is cut at N = 576 and N = 192 - a shape the
+    net's GEMMs at d_model 64 and 512 never take (tests/test_host_logic.py pins the plan)."""
+    test_gemm_matches_float64(engine, M, N, K, relu, precision)
+
+
+ATTN_SHAPES = [(2, 1200), (7, 12), (3, 48), (2, 33), (1, 129), (5, 1), (2, 24)]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("nseq,S", ATTN_SHAPES)
+def test_attention_matches_float64_at_head_sizes_32_and_64(head_engine, nseq, S, precision):
+    test_attention_matches_float64(head_engine, nseq, S, precision)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("nseq,S", ATTN_SHAPES)
 def test_attention_matches_float64(engine, nseq, S, precision):
     d = 2 * engine.dims.ctx_dim
     nh = engine.dims.nhead

@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import layer_reference as R  # noqa: E402
+import width_cases as WC  # noqa: E402
 from safe_interactive_crowdnav_amd.engine import JmidEngine  # noqa: E402
 from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims  # noqa: E402
 
@@ -27,16 +28,17 @@ TOL = {"f32": 2e-5, "f16x3": 4e-5, "f16x2": 2e-3, "f16mx": 2e-3}      # tests/te
 TOL_MX_LN = 6e-3                                                      # ... its F16MX GEMM + LayerNorm tests
 # GemmShape (csrc/launch_plan.hpp) and ResidualPath (csrc/jmid_planner.hip) words of the plan
 GS_SMALL = (1, 2, 3, 4)
+GS_LARGE = tuple(range(5, 13))      # GS_64 ... GS_REG_128
 GS_SMALL_64x128_TWO, GS_SMALL_64x64_TWO, GS_256x256 = 3, 4, 8
 RB_GEMM_LN2, RB_GEMM_LN, RB_LNX_SMALL, RB_GEMM_ADD_LN = 0, 1, 2, 3
 
 _ENGINES = {}
 
 
-def get_engine(d, joint):
-    key = (d, joint)
+def get_engine(d, joint, nhead=4):
+    key = (d, nhead, joint)
     if key not in _ENGINES:
-        w = JMIDWeights.from_seed(NetDims(ctx_dim=d // 2), 5)
+        w = JMIDWeights.from_seed(NetDims(ctx_dim=d // 2, nhead=nhead), 5)
         _ENGINES[key] = (JmidEngine(w, joint=joint, step=5), w)
     return _ENGINES[key]
 
@@ -48,15 +50,16 @@ def worst(err, bound, rows):
     return float(r[i]), row, int(i[1])
 
 
-def check_layer(d, joint, shape, n_agents, precision, layer, last, expect=None):
+def check_layer(d, joint, shape, n_agents, precision, layer, last, expect=None, nhead=4):
     """One jmid_dbg_layer call, every stage present against its reference.  Returns the plan."""
-    eng, w = get_engine(d, joint)
+    eng, w = get_engine(d, joint, nhead)
+    assert eng.dims.nhead == nhead and eng.dims.d_model == d
     E, A, K, T = shape
     M = E * A * K * T
     nseq, S = (E, K * A * T) if joint else (E * K * A, T)
     X = R.layer_input(shape, n_agents, d)
     stages, plan = eng.dbg_layer(X, layer, shape, precision, n_agents=n_agents, last=last)
-    tag = f"{'jmid' if joint else 'imid'} {shape} n={n_agents} d={d} [{precision}] layer {layer}{' (last)' if last else ''}"
+    tag = f"{'jmid' if joint else 'imid'} {shape} n={n_agents} d={d}{'' if nhead == 4 else f' nhead={nhead}'} [{precision}] layer {layer}{' (last)' if last else ''}"
     print(f"{tag} plan: {plan}")
     assert plan["range_flag"] == 0
     spec = R.stage_specs(precision, joint, plan, last)
@@ -112,10 +115,10 @@ def check_layer(d, joint, shape, n_agents, precision, layer, last, expect=None):
     return plan
 
 
-def both_layers(d, joint, shape, n_agents, precision, expect=None):
-    eng, _ = get_engine(d, joint)
-    check_layer(d, joint, shape, n_agents, precision, 1, False, expect)
-    return check_layer(d, joint, shape, n_agents, precision, eng.dims.tf_layer - 1, True, expect)
+def both_layers(d, joint, shape, n_agents, precision, expect=None, nhead=4):
+    eng, _ = get_engine(d, joint, nhead)
+    check_layer(d, joint, shape, n_agents, precision, 1, False, expect, nhead)
+    return check_layer(d, joint, shape, n_agents, precision, eng.dims.tf_layer - 1, True, expect, nhead)
 
 
 # (E, A, K, T), n_agents, also at d_model 64
@@ -127,30 +130,52 @@ JMID_SHAPES = [((1, 1, 1, 1), None, True),             # M = S = 1
                ((3, 4, 8, 12), [4, 1, 3], True),       # S = 384: all-ones, all-zero and partial mask words
                ((3, 3, 5, 6), [2, 3, 1], True),        # S = 90: the last key tile cut by both S and the mask
                ((1, 4, 8, 12), [1], False)]            # one padded scene through OUT_LNX
-JMID_CASES = [(s, n, d) for s, n, small in JMID_SHAPES for d in ((512, 64) if small else (512,))]
+OLD_D = tuple(sorted((WC.d_model(c) for c, _ in WC.OLD_NETS), reverse=True))      # d_model of the suite's two nhead = 4 networks
+JMID_CASES = [(s, n, d) for s, n, small in JMID_SHAPES for d in (OLD_D if small else OLD_D[:1])]
 
 
-def expectation(shape, n_agents, d, precision):
-    """which kernel the case is there for"""
+GM_X3, GM_X2, GM_MX = 0, 1, 2      # GemmMode (csrc/launch_plan.hpp)
+
+
+def expectation(shape, n_agents, d, precision, nhead=4):
+    """which kernel the case is there for: the facts of csrc/launch_plan.hpp / csrc/jmid_planner.hip each row of tests/width_cases.py exists
+    for - a planner change that silently stops exercising a path fails the test"""
     if precision == "f32":
         return {}
     e = {}
     S = shape[1] * shape[2] * shape[3]
+    head = d // nhead
+    mx = precision == "f16mx"
     e["vt_direct"] = int(S % 4 == 0)
-    e["attn_dma"] = int(d == 512)
+    e["attn_dma"] = int(head == 128)                                    # plan_attn: the LDS-DMA kernel is head 128's
     if d == 512:
         if not (shape == (1, 3, 100, 8) and precision == "f16x3"):      # (F16X3 has no two-workgroups-per-CU small shape)
             e["in_proj_shape"] = GS_SMALL
-        if precision == "f16mx":
-            e.update(k8=1, q8l=1, byte_lo=1, out_proj_path=RB_LNX_SMALL, linear2_path=RB_LNX_SMALL)
+        if mx:
+            # byte_lo_plane and residual_path look at d_model alone: the byte plane and the one-launch GEMM + LayerNorm beside either
+            # attention kernel; the bf8 K images are the LDS-DMA kernel's (plan_step: k8 needs head 128)
+            e.update(k8=int(head == 128), q8l=int(head == 128), byte_lo=1, out_proj_path=RB_LNX_SMALL, linear2_path=RB_LNX_SMALL)
         else:
             e.update(out_proj_path=RB_GEMM_ADD_LN, linear2_path=RB_GEMM_ADD_LN)
+    else:
+        # residual_path: no row-complete kernel and no OUT_LNX launch off d_model 512 (GLN_BN); byte_lo_plane: none either
+        e.update(byte_lo=0, out_proj_path=RB_GEMM_ADD_LN, linear2_path=RB_GEMM_ADD_LN, merge=0)
+    if head != 128:
+        e.update(k8=0, q8l=0, attn_nsplit=1, merge=0)                   # plan_call: only head 128's launches split the key range
+    if d == 1024 and mx:
+        e.update(k8=1, q8l=1)                                           # head 128 through nhead 8: the bf8 images without the byte plane
+    if d == 192:
+        # plan_gemm: F16MX needs N % 128 == 0 (in_proj 576, out_proj / linear2 192: F16X2's kernels; linear1 384: its own) - one step
+        # mixes the two; small_gemm_shape refuses K % 128 != 0 for every GEMM of the layer
+        word = {"f16x3": GM_X3, "f16x2": GM_X2, "f16mx": GM_MX}[precision]
+        narrow = GM_X2 if mx else word
+        e.update(in_proj_mode=narrow, out_proj_mode=narrow, linear2_mode=narrow, linear1_mode=word, in_proj_shape=GS_LARGE, linear1_shape=GS_LARGE)
     if shape == (1, 3, 100, 8) and precision in ("f16x2", "f16mx"):
         e["in_proj_shape"] = GS_SMALL_64x128_TWO
         if precision == "f16mx":
             e["out_proj_gemm_shape"] = GS_SMALL_64x64_TWO
-    if shape == (1, 5, 20, 12) and precision == "f16mx":
-        e["merge"] = 1
+    if shape == (1, 5, 20, 12) and precision == "f16mx" and d == 512 and head == 128:
+        e["merge"] = 1                                                  # small_cmb_fits: the merge rides in the OUT_LNX launch behind the LDS-DMA kernel only
     return e
 
 
@@ -160,9 +185,39 @@ def test_jmid_layer_stages_stay_inside_their_bounds(shape, n_agents, d, precisio
     both_layers(d, True, shape, n_agents, precision, expectation(shape, n_agents, d, precision))
 
 
+# ---- the rows of tests/width_cases.py the suite did not run before: (E, A, K, T), n_agents, only at d_model >= 512
+NEW_SHAPES = [((1, 1, 1, 1), None, False),
+              ((3, 3, 5, 7), None, False),             # S = 105, S % 4 != 0; M = 315: more than one row tile, the last one partial
+              ((3, 4, 8, 12), [4, 1, 3], False),       # all-ones, all-zero and partial mask words
+              ((1, 5, 20, 12), None, True)]            # one scene: the small launches / OUT_LNX / the merge - or, at d_model 1024, none of them planned
+NEW_CASES = [(net, s, n) for net in WC.NEW_NETS for s, n, wide in NEW_SHAPES if not wide or WC.d_model(net[0]) >= 512]
+
+
+@pytest.mark.parametrize("precision", MODES)
+@pytest.mark.parametrize("net,shape,n_agents", NEW_CASES, ids=lambda v: WC.net_id(v) if isinstance(v, tuple) and len(v) == 2 else str(v).replace(" ", ""))
+def test_jmid_layer_stages_at_every_accepted_width_and_head_size(net, shape, n_agents, precision):
+    d, nhead = WC.d_model(net[0]), net[1]
+    both_layers(d, True, shape, n_agents, precision, expectation(shape, n_agents, d, precision, nhead), nhead)
+
+
 @pytest.mark.parametrize("precision", MODES)
 @pytest.mark.parametrize("pack", [1, 0])
-@pytest.mark.parametrize("d", [512, 64])
+@pytest.mark.parametrize("net", [(64, 4), (128, 4), (256, 8)], ids=WC.net_id)
+def test_imid_layer_stages_at_head_sizes_32_and_64(net, pack, precision):
+    """attn_f32_kernel / attn_f32_packed_kernel<32 | 64> on S = T = 6"""
+    assert net in WC.NEW_NETS
+    d, nhead = WC.d_model(net[0]), net[1]
+    eng, _ = get_engine(d, False, nhead)
+    try:
+        eng.set_tuning("attn_pack", pack)
+        both_layers(d, False, (2, 3, 4, 6), None, precision, {"masked": 0, "k8": 0, "attn_pack": pack}, nhead)
+    finally:
+        eng.set_tuning("attn_pack", 1)
+
+
+@pytest.mark.parametrize("precision", MODES)
+@pytest.mark.parametrize("pack", [1, 0])
+@pytest.mark.parametrize("d", list(OLD_D))
 def test_imid_layer_stages_stay_inside_their_bounds(d, pack, precision):
     """S = T = 6: the exact-fp32 attention kernel on short sequences, several per wave (attn_pack) or one"""
     eng, _ = get_engine(d, False)

@@ -12,6 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import tests.width_cases as WC
 from oracle import jmid_oracle as O
 from safe_interactive_crowdnav_amd.engine import JmidEngine
 from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims
@@ -33,12 +34,12 @@ def ade(a, b):
 _ENGINES = {}
 
 
-def get_engine(ctx_dim, wseed, joint, flavour="diag"):
+def get_engine(ctx_dim, wseed, joint, flavour="diag", nhead=4):
     """`flavour`: "diag" = the diagnostics build the test session loads (tests/conftest.py), "prod" = the PRODUCTION
     libjmid_hip.so (what the drop-in class, bench.py and smoke() load), side by side in this process."""
-    key = (ctx_dim, wseed, joint, flavour)
+    key = (ctx_dim, wseed, joint, flavour) if nhead == 4 else (ctx_dim, wseed, joint, flavour, nhead)
     if key not in _ENGINES:
-        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim), wseed)
+        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim, nhead=nhead), wseed)
         _ENGINES[key] = (JmidEngine(w, joint=joint, lib_path={"prod": PROD_LIB}.get(flavour)), w)
         assert _ENGINES[key][0]._lib.has_diagnostics == (flavour != "prod")
     return _ENGINES[key]
@@ -106,6 +107,90 @@ def test_multi_episode_batch_is_block_diagonal(joint, precision):
     eng.set_chunk_episodes(0)
     for o in outs[1:]:
         np.testing.assert_array_equal(o, outs[0])  # chunking must not change a single bit
+
+
+_ORACLE_ONLY = {}
+
+
+def oracle_only_reference(ctx_dim, nhead):
+    """inputs and the float32 oracle's e_theta / velocities of one row of the table, made once for the four modes"""
+    key = (ctx_dim, nhead)
+    if key not in _ORACLE_ONLY:
+        _, w = get_engine(ctx_dim, 5, True, nhead=nhead)
+        E, A, K, T, step = 2, 3, 5, 7, 5
+        g = torch.Generator().manual_seed(1000 * ctx_dim + nhead)
+        ctx = torch.randn([E, A, ctx_dim], generator=g)
+        x_T = torch.randn([E, K * A, T, 2], generator=g)
+        rows = E * K * A
+        with torch.no_grad():
+            beta = O.variance_schedule()["betas"][[100] * rows]      # entry 0 of the step table: t = 100
+            e = O.net_forward(w.tensors, x_T.reshape(rows, T, 2), ctx.repeat(1, K, 1).reshape(rows, ctx_dim), beta, joint=True, nhead=nhead,
+                              seq_groups=E).reshape(E, K * A, T, 2).numpy()
+            vel = O.denoise(w.tensors, ctx, x_T, sample=K, step=step, joint=True, nhead=nhead).numpy()
+        _ORACLE_ONLY[key] = (ctx.numpy(), x_T.numpy(), e, vel)
+    return _ORACLE_ONLY[key]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("net", WC.ORACLE_ONLY_NETS, ids=WC.net_id)
+def test_rows_the_reference_cannot_build_match_the_oracle(net, precision):
+    """The reference's nhead is 4: the rows of tests/width_cases.py with another head count have no reference capture.  One e_theta
+    evaluation and the 5-step DDIM loop at E, A, K, T = 2, 3, 5, 7 against the oracle with that nhead, under this file's gates; chunk
+    sizes 0 and 1 give the same bits (test_multi_episode_batch_is_block_diagonal)."""
+    ctx_dim, nhead = net
+    eng, w = get_engine(ctx_dim, 5, True, nhead=nhead)
+    assert eng.dims.nhead == nhead
+    ctx, x_T, e_ref, vel_ref = oracle_only_reference(ctx_dim, nhead)
+    eng.set_step(5)
+    e = eng.net_eval(x_T, ctx, step_idx=0, precision=precision)
+    d = ade(e, e_ref)
+    print(f"{WC.net_id(net)} [{precision}] e_theta vs oracle = {d:.3e}")
+    assert np.isfinite(e).all() and d <= E_THETA_TOL[precision], ("e_theta", d)
+    outs = []
+    try:
+        for chunk in (0, 1):
+            eng.set_chunk_episodes(chunk)
+            vel, _ = eng.denoise(x_T, ctx, precision=precision, want_pos=False)
+            a = ade(vel, vel_ref)
+            print(f"{WC.net_id(net)} [{precision}] chunk {chunk} mean ADE(vel) vs oracle = {a:.3e}")
+            assert np.isfinite(vel).all() and a <= ADE_GATE, a
+            outs.append(vel)
+    finally:
+        eng.set_chunk_episodes(0)
+    np.testing.assert_array_equal(outs[1], outs[0])
+
+
+_BATCH_192 = {}
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_a_batch_at_d_model_192_on_the_large_tiles_matches_the_oracle(precision):
+    """20 episodes of 840 tokens as ONE chunk at (ctx_dim, nhead) = (96, 6): 16 800 rows, where in_proj (N = 576), out_proj and linear2
+    (N = 192) take the 128 x 128 tile shape with a partial last column tile and a partial last row tile (tests/test_host_logic.py pins
+    that plan) - in the net's own epilogues (Q / K / V^T planes, fp32 Y).  Two DDIM steps; the first two episodes against the oracle
+    (attention is block-diagonal over episodes: test_multi_episode_batch_is_block_diagonal), every episode finite, and the one-chunk call
+    bit-identical to the default chunk plan."""
+    eng, w = get_engine(96, 5, True, nhead=6)
+    E, A, K, T, step = 20, 3, 20, 14, 2
+    if not _BATCH_192:
+        g = torch.Generator().manual_seed(192)
+        ctx = torch.randn([E, A, 96], generator=g)
+        x_T = torch.randn([E, K * A, T, 2], generator=g)
+        with torch.no_grad():
+            ref = O.denoise(w.tensors, ctx[:2], x_T[:2], sample=K, step=step, joint=True, nhead=6).numpy()
+        _BATCH_192.update(ctx=ctx.numpy(), x_T=x_T.numpy(), ref=ref)
+    ctx, x_T, ref = _BATCH_192["ctx"], _BATCH_192["x_T"], _BATCH_192["ref"]
+    eng.set_step(step)
+    try:
+        base, _ = eng.denoise(x_T, ctx, precision=precision, want_pos=False)
+        eng.set_chunk_episodes(E)
+        vel, _ = eng.denoise(x_T, ctx, precision=precision, want_pos=False)
+    finally:
+        eng.set_chunk_episodes(0)
+    a = ade(vel[:2], ref)
+    print(f"d_model 192, 16 800 rows in one chunk [{precision}] mean ADE(vel) vs oracle = {a:.3e}")
+    assert np.isfinite(vel).all() and a <= ADE_GATE, a
+    np.testing.assert_array_equal(vel, base)
 
 
 def test_device_pointers_match_host_path():

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import tests.width_cases as WC
 from oracle import jmid_oracle as O
 from safe_interactive_crowdnav_amd.engine import JmidEngine, JmidError
 from safe_interactive_crowdnav_amd.schedule import ddim_steps
@@ -22,10 +23,10 @@ GEMM_TOL = {"f16x3": 4e-5, "f16x2": 2e-3, "f16mx": 2e-3}      # TOL of tests/tes
 _ENGINES = {}
 
 
-def get_engine(ctx_dim, wseed):
-    key = (ctx_dim, wseed)
+def get_engine(ctx_dim, wseed, nhead=4):
+    key = (ctx_dim, wseed) if nhead == 4 else (ctx_dim, wseed, nhead)
     if key not in _ENGINES:
-        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim), wseed)
+        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim, nhead=nhead), wseed)
         _ENGINES[key] = (JmidEngine(w, joint=True), w)
     return _ENGINES[key]
 
@@ -38,12 +39,12 @@ def ade(a, b):
 _REF = {}
 
 
-def qkv0_case(ctx_dim, shape):
+def qkv0_case(ctx_dim, shape, nhead=4):
     """Inputs of one case and in_proj(embed(x)) of layer 0 in float64 from the same fp32 weights, hyper rows and time row; made once
     per (width, shape) and shared by the three modes."""
-    key = (ctx_dim, shape)
+    key = (ctx_dim, shape) if nhead == 4 else (ctx_dim, shape, nhead)
     if key not in _REF:
-        eng, w = get_engine(ctx_dim, 5)
+        eng, w = get_engine(ctx_dim, 5, nhead)
         eng.set_step(10)
         E, A, K, T = shape
         d = 2 * ctx_dim
@@ -77,16 +78,16 @@ def qkv0_case(ctx_dim, shape):
 
 
 @pytest.mark.parametrize("precision", SPLIT_MODES)
-@pytest.mark.parametrize("ctx_dim", [32, 256])
+@pytest.mark.parametrize("ctx_dim", WC.OLD_CTX_DIMS)
 @pytest.mark.parametrize("shape", [(2, 2, 3, 4), (3, 3, 5, 7), (1, 5, 20, 12)])
-def test_expanded_planes_are_no_further_from_float64_than_the_gemm(shape, ctx_dim, precision):
+def test_expanded_planes_are_no_further_from_float64_than_the_gemm(shape, ctx_dim, precision, nhead=4):
     """S = 24 (rows and samples vary inside a sequence), S = 105 (S % 4 != 0: the V^T layout that needed the transpose kernel) and
     S = 1200 (one scene: ragged 128-row tile, panel boundaries), at d_model 64 (head_dim 16: no bf8 images) and 512 (K / Q_lo images in
     f16mx).  The expansion drops the fp16 rounding of the embedding in front of the GEMM, so its max and mean absolute error against
     float64 are bounded by the GEMM path's on the same inputs, without a margin."""
-    eng, _ = get_engine(ctx_dim, 5)
+    eng, _ = get_engine(ctx_dim, 5, nhead)
     eng.set_step(10)
-    x, hyp, step, ref = qkv0_case(ctx_dim, shape)
+    x, hyp, step, ref = qkv0_case(ctx_dim, shape, nhead)
     err = {}
     try:
         for knob in (0, 1, 2):                # 2: the expansion with the table's GEMM as one running sum (printed, not bounded)
@@ -104,6 +105,15 @@ def test_expanded_planes_are_no_further_from_float64_than_the_gemm(shape, ctx_di
     assert err[0][1] <= err[1][1], err
     # ... and the yardstick itself cannot drift: the GEMM path holds the project's tolerance for a GEMM of its mode (test_gpu_kernels.py)
     assert err[1][0] <= GEMM_TOL[precision] * max(1.0, float(np.abs(ref).max())), err
+
+
+@pytest.mark.parametrize("precision", SPLIT_MODES)
+@pytest.mark.parametrize("net", WC.NEW_NETS, ids=WC.net_id)
+def test_expanded_planes_at_every_other_accepted_width_and_head_size(net, precision):
+    """The same comparison at the other rows of tests/width_cases.py, at S = 24: head sizes 32 and 64 (the planes' head-major V^T
+    layout), d_model 192 (in_proj's N = 576 and K = 192 are no multiples of 128: the GEMM path it is compared with runs F16X2's kernel in
+    an f16mx call), d_model 1024 with the bf8 images."""
+    test_expanded_planes_are_no_further_from_float64_than_the_gemm((2, 2, 3, 4), net[0], precision, net[1])
 
 
 # ---- 2. the whole loop ----

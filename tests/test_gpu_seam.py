@@ -24,18 +24,18 @@ SCENARIOS = [("ddim", 10, 3, 4, False), ("ddim", 10, 9, -1, False), ("ddpm", 100
 _ENG, _NET = {}, {}
 
 
-def get_engine(ctx_dim, joint=True):
-    key = (ctx_dim, joint)
+def get_engine(ctx_dim, joint=True, nhead=4):
+    key = (ctx_dim, joint) if nhead == 4 else (ctx_dim, joint, nhead)
     if key not in _ENG:
-        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim), 5)
+        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim, nhead=nhead), 5)
         _ENG[key] = (JmidEngine(w, joint=joint), w)
     return _ENG[key]
 
 
-def net(ctx_dim):
-    """the float64 side of a width, made once: hyper weights, concat1, the positional table"""
+def net(ctx_dim, nhead=4):
+    """the float64 side of a width, made once: hyper weights, concat1, the positional table (the seeded weights do not depend on nhead)"""
     if ctx_dim not in _NET:
-        _, w = get_engine(ctx_dim)
+        _, w = get_engine(ctx_dim, nhead=nhead)
         d, dmid, dlow = S.dims_of(ctx_dim)
         W, b, tw = S.hyper_weights(w.tensors, d, dmid, dlow)
         g8 = lambda n: w.tensors[n].detach().cpu().numpy().astype(np.float64)
@@ -59,16 +59,21 @@ class Worst:
         assert not bad.any(), f"{stage} {what}: {int(bad.sum())} elements outside, worst |err| / bound {q:.3f} at {np.argwhere(bad)[0]}"
 
 
-def expected_kernel(split, fold, traj):
-    base = "tail_fold" if (split and fold != 1) else "out_ddim"
+def expected_kernel(split, fold, traj, folds=True):
+    base = "tail_fold" if (split and fold != 1 and folds) else "out_ddim"
     return base + ("_traj" if traj else "")
 
 
 def run_case(eng, ctx_dim, shape, precision, trajs, out_tpw_of, hyp_direct=False):
-    """Every knob and sampler combination of one (shape, width, mode); returns the worst ratios."""
+    """Every knob and sampler combination of one (shape, width, mode); returns the worst ratios.  At a width beyond tail_fold.hpp's
+    limits (S.tail_folds: d_model 1024) the plan must say so - out_ddim under every value of "tail_fold", and no per-trajectory form
+    (S.per_trajectory) -, the tail is the two EPI_CSL GEMMs + the output kernel, and the same stages are judged by the same bounds."""
     E, A, K, T = shape
     d, _, _ = S.dims_of(ctx_dim)
-    n, rep, inp = net(ctx_dim), S.rep_of(precision, d), S.seam_inputs(ctx_dim, shape)
+    n, rep, inp = net(ctx_dim, eng.dims.nhead), S.rep_of(precision, d), S.seam_inputs(ctx_dim, shape)
+    can_fold = S.tail_folds(ctx_dim)
+    if not S.per_trajectory(ctx_dim):
+        out_tpw_of = lambda traj: 0
     split = precision != "f32"
     folds = (0, 1, 2) if split else (0,)
     X, x, z = inp["X"], inp["x"], inp["z"]
@@ -91,7 +96,8 @@ def run_case(eng, ctx_dim, shape, precision, trajs, out_tpw_of, hyp_direct=False
                         r = eng.dbg_seam(X, x, shape, step, nxt, precision, z=z if with_z else None, **src)
                         got[sc, traj, fold] = r
                         plan = r["plan"]
-                        assert plan["kernel"] == expected_kernel(split, fold, out_tpw_of(traj)) and plan["out_tpw"] == out_tpw_of(traj), (what, plan)
+                        assert plan["kernel"] == expected_kernel(split, fold, out_tpw_of(traj), can_fold) and plan["out_tpw"] == out_tpw_of(traj), (what, plan)
+                        assert plan["tail_fold"] == int(split and fold != 1 and can_fold), (what, plan)
                         assert plan["rep"] == rep and plan["ddpm"] == (kind == "ddpm") and plan["embedded"] == (nxt >= 0) and not plan["range_flag"], (what, plan)
                         # the handle's coefficients are the schedule's, and its time rows their definition
                         for k in (("c_e", "c_x", "n_x", "n_e") if kind == "ddim" else ("c0", "c1", "sigma")):
@@ -107,7 +113,7 @@ def run_case(eng, ctx_dim, shape, precision, trajs, out_tpw_of, hyp_direct=False
                             w.check("hyper", r["hyp"], *S.hyper_stage(inp["ctx"], n["W"], n["b"]), what)
                         # the update, on the e the tail alone gives with these knobs
                         e, _ = eng.dbg_tail(X, r["hyp"], step, shape, precision)
-                        de = S.contraction_term(e, r["hyp"][ea], r["thyp"][0], n["L"], folded=split and fold != 1)
+                        de = S.contraction_term(e, r["hyp"][ea], r["thyp"][0], n["L"], folded=split and fold != 1 and can_fold)
                         w.check("update", r["x_next"], *S.update_stage(x, z if with_z else None, e, r["coef"], kind == "ddpm", de), what)
                         if nxt >= 0:
                             # the embedding, on the device's own x_next and hyper rows and the handle's time row
@@ -159,13 +165,27 @@ def report(tag, shape, ctx_dim, precision, worst):
 
 
 @pytest.mark.parametrize("precision", S.MODES)
-@pytest.mark.parametrize("ctx_dim", S.WIDTHS)
+@pytest.mark.parametrize("ctx_dim", S.OLD_WIDTHS)
 @pytest.mark.parametrize("shape", S.SHAPES)
 def test_seam_stages_are_inside_their_bounds_and_the_bit_promises_hold(shape, ctx_dim, precision):
     eng, _ = get_engine(ctx_dim)
     T = shape[3]
     worst = run_case(eng, ctx_dim, shape, precision, (0, 1), lambda traj: T if traj else 0)
     report("", shape, ctx_dim, precision, worst)
+
+
+@pytest.mark.parametrize("precision", S.MODES)
+@pytest.mark.parametrize("net_row", [n for n in S.NETS if n[0] not in S.OLD_WIDTHS or n[1] != 4], ids=S.WC.net_id)
+@pytest.mark.parametrize("shape", S.NEW_SHAPES)
+def test_seam_at_every_other_accepted_width(shape, net_row, precision):
+    """d_model 128, 192 (eight-column chunks of a row that are no multiple of a 128-column panel), 256, 512 under eight heads and
+    1024, where the tail is not folded and no per-trajectory kernel exists: run_case asserts that the plan says so."""
+    ctx_dim, nhead = net_row
+    eng, _ = get_engine(ctx_dim, nhead=nhead)
+    assert eng.dims.nhead == nhead
+    T = shape[3]
+    worst = run_case(eng, ctx_dim, shape, precision, (0, 1), lambda traj: T if traj else 0)
+    report(f"nhead {nhead} ", shape, ctx_dim, precision, worst)
 
 
 @pytest.mark.parametrize("precision", ["f16mx", "f32"])
@@ -196,8 +216,8 @@ def test_seam_on_an_imid_handle():
 @pytest.mark.parametrize("EA", [(1, 1), (2, 2), (5, 5)])
 def test_hyper_rows_at_edge_tiles(EA, ctx_dim):
     """E A = 1, 4 and 25 rows of the call's hyper GEMM (N = 228 / 1796, K = 32 / 256): edge tiles in M and N"""
-    eng, _ = get_engine(ctx_dim)
-    n = net(ctx_dim)
+    eng, _ = get_engine(ctx_dim, nhead=S.WC.nhead_of(ctx_dim))
+    n = net(ctx_dim, S.WC.nhead_of(ctx_dim))
     shape = (EA[0], EA[1], 1, 1)
     rows = EA[0] * EA[1]
     ctx = np.random.default_rng(rows + ctx_dim).standard_normal((rows, ctx_dim)).astype(np.float32)

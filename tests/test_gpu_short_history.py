@@ -12,6 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import tests.test_gpu_parity as P      # its engines (one per width and seed), ade() and tolerances
+import tests.width_cases as WC
 from safe_interactive_crowdnav_amd import _lib, offline
 from safe_interactive_crowdnav_amd import scene as SC
 from safe_interactive_crowdnav_amd.engine import JmidEngine, JmidError
@@ -36,7 +37,7 @@ class State:
 
 
 # ------------------------------------------------------------------------------------------------ 1. the encoder
-@pytest.mark.parametrize("ctx_dim", [32, 256])
+@pytest.mark.parametrize("ctx_dim", WC.OLD_CTX_DIMS)      # (every hidden size against float64, first_index included: tests/test_gpu_encoder.py)
 def test_row_equals_the_slice_on_an_engine_of_that_history_length(ctx_dim):
     """Row r with first_index f is, bit for bit, the row of an engine created with hist_len = F - f fed frames f ..: the same LSTM steps
     from the same zero state.  What stands in front of f - NaN here, in x_st AND nbr_sum - reaches no output."""

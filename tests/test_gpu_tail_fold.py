@@ -10,6 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import tests.width_cases as WC
 from oracle import jmid_oracle as O
 from safe_interactive_crowdnav_amd.engine import JmidEngine, JmidError
 from safe_interactive_crowdnav_amd.schedule import ddim_steps
@@ -25,7 +26,7 @@ _ENGINES = {}
 def get_engine(ctx_dim, wseed, joint=True):
     key = (ctx_dim, wseed, joint)
     if key not in _ENGINES:
-        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim), wseed)
+        w = JMIDWeights.from_seed(NetDims(ctx_dim=ctx_dim, nhead=WC.nhead_of(ctx_dim)), wseed)      # (the tail does not read the head count)
         _ENGINES[key] = (JmidEngine(w, joint=joint), w)
     return _ENGINES[key]
 
@@ -92,12 +93,35 @@ def tail_case(ctx_dim, shape):
 
 
 @pytest.mark.parametrize("precision", SPLIT_MODES)
-@pytest.mark.parametrize("ctx_dim", [32, 256])
+@pytest.mark.parametrize("ctx_dim", WC.OLD_CTX_DIMS)
 @pytest.mark.parametrize("shape", [(2, 2, 3, 4), (3, 3, 5, 7), (1, 5, 20, 12)])
 def test_folded_tail_is_no_further_from_float64_than_the_gemms(shape, ctx_dim, precision):
     """48 tokens (several rows of the table in a wave's neighbourhood), T odd (trajectories straddle the 128-row panel boundaries) and
     one scene, at d_model 64 (eight lanes of a wave hold columns) and 512, per token ("out_traj" = 0 at these sizes) and per trajectory
     (= 1).  The table built per step ("tail_fold" = 2) and the two kernel forms give the bits of the default."""
+    folded_against_the_gemms(shape, ctx_dim, precision)
+
+
+GEMM_TOL = {"f16x3": 4e-5, "f16x2": 2e-3, "f16mx": 2e-3}      # TOL of tests/test_gpu_kernels.py: max |err| relative to max(1, max |ref|)
+
+
+@pytest.mark.parametrize("precision", SPLIT_MODES)
+@pytest.mark.parametrize("ctx_dim", [c for c in WC.CTX_DIMS if c not in WC.OLD_CTX_DIMS])
+def test_tail_at_every_other_accepted_width(ctx_dim, precision):
+    """d_model 128 (concat3's N = 64 on the GEMM path), 192, 256 - and 1024, beyond tail_fold.hpp's kTailMaxD: nothing is folded there,
+    the plan takes the two EPI_CSL GEMMs + the output kernel under every value of the knob, so the three runs must be the same bits (the
+    seam test asserts the plan's word; this one that the knob is inert).  At every width the GEMM path also holds the project's
+    tolerance for a GEMM of its mode against float64, so a width at which both paths are wrong together cannot pass."""
+    err, got = folded_against_the_gemms((2, 2, 3, 4), ctx_dim, precision)
+    ref_max = max(1.0, float(np.abs(tail_case(ctx_dim, (2, 2, 3, 4))[2]).max()))
+    for traj in (0, 1):
+        assert err[traj, 1][0] <= GEMM_TOL[precision] * ref_max, (traj, err)
+        if not WC.tail_folds(ctx_dim):
+            np.testing.assert_array_equal(got[traj, 0], got[traj, 1], err_msg="no fold is planned at this width: the knob selects nothing")
+
+
+def folded_against_the_gemms(shape, ctx_dim, precision):
+    """one (shape, width, mode): every value of "tail_fold" x "out_traj" against float64; returns ((max, mean) errors, outputs) by (out_traj, tail_fold)"""
     eng, _ = get_engine(ctx_dim, 5)
     eng.set_step(10)
     X, hyp, ref = tail_case(ctx_dim, shape)
@@ -122,6 +146,7 @@ def test_folded_tail_is_no_further_from_float64_than_the_gemms(shape, ctx_dim, p
         np.testing.assert_array_equal(got[traj, 2], got[traj, 0], err_msg=f"one-step table, out_traj {traj}")
         assert within_the_gemm_paths_error(precision, err[traj, 0], err[traj, 1]), (traj, err)
     np.testing.assert_array_equal(got[1, 0], got[0, 0], err_msg="per trajectory against per token")
+    return err, got
 
 
 # ---- 2. the whole loop ----

@@ -348,6 +348,38 @@ def gemm_plan_rows(lib):
     return lines, plans
 
 
+def test_gemm_plans_at_d_model_192_mix_the_modes_and_cut_the_last_column_tile():
+    """What the rows (96, 6) and (96, 12) of tests/width_cases.py are there for, read from csrc/launch_plan.hpp: in an F16MX call in_proj
+    (N = 576), out_proj and linear2 (N = 192) run F16X2's kernels and linear1 (N = 384) F16MX's own; no GEMM of the layer takes a small
+    launch (K % 128 != 0); and a batch of 16 800 rows takes the 128 x 128 shape with a partial last column tile at N = 576 and 192 - the
+    shapes tests/test_gpu_kernels.py and tests/test_gpu_parity.py run on the device."""
+    import ctypes as C
+
+    import __graft_entry__ as graft
+    from safe_interactive_crowdnav_amd import _lib
+    from safe_interactive_crowdnav_amd.build import LIB_DIAG
+    graft.build()
+    lib = _lib.load_library(LIB_DIAG)
+    kv = (C.c_int * len(GEMM_PLAN_KNOBS))(*[GEMM_PLAN_DEFAULTS[k] for k in GEMM_PLAN_KNOBS])
+    out8 = (C.c_int * 8)()
+    X3, X2, MX = 0, 1, 2
+    d = 192
+    layers = {"in_proj": (EPI_BIAS, OUT_QKV, 3 * d, d), "out_proj": (EPI_BIAS, OUT_F32, d, d), "linear1": (EPI_BIAS_RELU, OUT_SPLIT, 2 * d, d),
+              "linear2": (EPI_BIAS, OUT_F32, d, 2 * d)}
+    for mode in (X3, X2, MX):
+        for name, (epi, out, N, K) in layers.items():
+            for M in (1, 315, 384, 16800):
+                assert lib.jmid_dbg_gemm_plan(mode, epi, out, M, N, K, 1, 1, kv, out8) == 0
+                family, shape, _, _, bm, bn = out8[:6]
+                assert family == (mode if mode != MX or name == "linear1" else X2), (mode, name, M, family)
+                assert shape not in GS_SMALL and shape != GS_NONE, (mode, name, M, shape)
+                if M == 16800:
+                    assert (shape, bm, bn) == (GS_128, 128, 128), (mode, name, shape)
+                    assert (N % bn != 0) == (name != "linear1")
+    # the one-launch GEMM + LayerNorm is not asked for off d_model 512 (residual_path), and would not fit: K % 128 != 0
+    assert lib.jmid_dbg_gemm_plan(MX, EPI_BIAS, OUT_LNX, 315, d, d, 1, 1, kv, out8) == 0 and out8[1] == GS_NONE
+
+
 def test_gemm_launch_plans_are_the_ones_the_launchers_used_to_pick():
     """csrc/launch_plan.hpp::plan_gemm reproduces, on the whole grid, what the per-launch rules it replaced decided (tests/golden/
     gemm_plan_table.txt: dumped from those rules, cut unchanged out of the launchers into functions that return the shape, before

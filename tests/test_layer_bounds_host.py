@@ -14,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import layer_reference as R  # noqa: E402
+import width_cases as WC  # noqa: E402
 from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims
 
 MODES = ["f32", "f16x3", "f16x2", "f16mx"]
@@ -21,7 +22,13 @@ MODES = ["f32", "f16x3", "f16x2", "f16mx"]
 SHAPES = [((1, 1, 1, 1), None, True, True), ((2, 2, 3, 4), None, True, True), ((3, 3, 5, 7), None, True, True),
           ((1, 5, 20, 12), None, False, True), ((1, 3, 100, 8), None, False, True), ((3, 4, 8, 12), [4, 1, 3], True, True),
           ((3, 3, 5, 6), [2, 3, 1], True, True), ((1, 4, 8, 12), [1], False, True), ((2, 3, 4, 6), None, True, False)]
-CASES = [(s, n, j, d) for s, n, small, j in SHAPES for d in ((512, 64) if small else (512,))]
+OLD_D = tuple(sorted((WC.d_model(c) for c, _ in WC.OLD_NETS), reverse=True))      # d_model of the suite's two nhead = 4 networks
+CASES = [(s, n, j, d, 4) for s, n, small, j in SHAPES for d in (OLD_D if small else OLD_D[:1])]
+# rows of tests/width_cases.py with another head size (32, 64, and 64 at d_model 512), at the one shape with a partial row tile and S % 4 != 0
+HEAD_NETS = [(96, 6), (128, 4), (256, 8)]
+HEAD_CASES = [(((3, 3, 5, 7)), None, True, WC.d_model(c), h) for c, h in HEAD_NETS]
+HEAD64_CASES = [c for c in HEAD_CASES if c[3] // c[4] == 64]
+assert all(n in WC.NETS for n in HEAD_NETS) and len(HEAD64_CASES) == 2
 _W = {}
 
 
@@ -34,13 +41,13 @@ def weights(d):
 make_x = R.layer_input
 
 
-def host_plan(precision, joint, d, M, masked):
+def host_plan(precision, joint, d, M, masked, nhead=4):
     """What launch_plan.hpp decides for the arithmetic of the layer's GEMMs (plan_gemm: F16MX where K % 64 == 0 and N % 128 == 0) and
     jmid_planner.hip plan_step for the images and planes - the words of jmid_dbg_layer's plan that layer_reference.stage_specs reads."""
     ff = 2 * d
     code = {"f32": -1, "f16x3": 0, "f16x2": 1, "f16mx": 2}[precision]
     mode = lambda N, K: 1 if code == 2 and not (K % 64 == 0 and N % 128 == 0) else code
-    hd128 = d // 4 == 128
+    hd128 = d // nhead == 128
     k8 = int(joint and precision == "f16mx" and hd128)
     return dict(in_proj_mode=mode(3 * d, d), linear1_mode=mode(ff, d), out_proj_mode=mode(d, d), linear2_mode=mode(d, ff),
                 k8=k8, q8l=k8, byte_lo=int(precision == "f16mx" and d == 512), attn_dma=int(hd128), masked=int(masked and joint))
@@ -217,15 +224,15 @@ class Layer:
     """The emulated correct layer of one case and mode, every stage fed the emulated output of the stage before it, with the reference
     and bound of every stage - made once, shared by the correct-kernel test and the mutations."""
 
-    def __init__(self, shape, n_agents, joint, d, precision):
+    def __init__(self, shape, n_agents, joint, d, nhead, precision):
         E, A, K, T = shape
         self.shape, self.n_agents, self.joint, self.d, self.precision = shape, n_agents, joint, d, precision
-        self.M, self.nhead, self.hd = E * A * K * T, 4, d // 4
+        self.M, self.nhead, self.hd = E * A * K * T, nhead, d // nhead
         self.nseq, self.S = (E, K * A * T) if joint else (E * K * A, T)
         self.w = weights(d)
         self.real = R.real_rows(n_agents, E, A, K, T)
         self.valid = R.key_valid(n_agents, E, A, K, T) if joint else np.ones((self.nseq, self.S), bool)
-        self.plan = host_plan(precision, joint, d, self.M, n_agents is not None)
+        self.plan = host_plan(precision, joint, d, self.M, n_agents is not None, nhead)
         self.spec = R.stage_specs(precision, joint, self.plan, last=False)
         self.qscale = R.LOG2E / np.sqrt(self.hd)
         self.split_joint = joint and precision != "f32"
@@ -285,11 +292,11 @@ def layer(case, precision):
 
 
 def case_id(c):
-    (E, A, K, T), n, joint, d = c
-    return f"{'jmid' if joint else 'imid'}-{E}x{A}x{K}x{T}-{'pad' if n else 'full'}-d{d}"
+    (E, A, K, T), n, joint, d, nhead = c
+    return f"{'jmid' if joint else 'imid'}-{E}x{A}x{K}x{T}-{'pad' if n else 'full'}-d{d}" + ("" if nhead == 4 else f"-h{nhead}")
 
 
-@pytest.mark.parametrize("case,precision", [(c, p) for p in MODES for c in CASES], ids=lambda v: v if isinstance(v, str) else case_id(v))
+@pytest.mark.parametrize("case,precision", [(c, p) for p in MODES for c in CASES + HEAD_CASES], ids=lambda v: v if isinstance(v, str) else case_id(v))
 def test_an_emulated_correct_kernel_stays_inside_every_bound(case, precision):
     L = layer(case, precision)
     worst = {}
@@ -411,4 +418,28 @@ def test_an_emulated_wrong_kernel_leaves_its_bound(mutation, precision):
         assert r > 1.0, (mutation.__name__, case_id(case), precision, r)
     # (F32 has no pre-scaled Q planes, no lo plane and no split-KV launch)
     if not (precision == "f32" and mutation in (mut_double_scale, mut_zero_lo, mut_dropped_range)):
+        assert seen > 0, "the mutation was never expressible"
+
+
+# (no padded scene and no split-KV launch among the head-64 cases: head 64's launches never split - plan_call - and the masked shapes
+#  are the GPU test's)
+HEAD64_MUTATIONS = [m for m in MUTATIONS if m not in (mut_padded_key, mut_dropped_range)]
+
+
+@pytest.mark.parametrize("precision", MODES)
+@pytest.mark.parametrize("mutation", HEAD64_MUTATIONS, ids=lambda f: f.__name__[4:])
+def test_an_emulated_wrong_kernel_leaves_its_bound_at_head_size_64(mutation, precision):
+    """the same faults at head 64 (d_model 256 with four heads, d_model 512 with eight): the bounds bite there before a device result
+    is judged by them"""
+    seen = 0
+    for case in HEAD64_CASES:
+        r = mutation(layer(case, precision))
+        if r is None:
+            continue
+        print(f"{mutation.__name__[4:]} {case_id(case)} [{precision}]: worst err/bound {r:.3g}" + (" (not asserted)" if isinstance(r, NotDetectable) else ""))
+        if isinstance(r, NotDetectable):
+            continue
+        seen += 1
+        assert r > 1.0, (mutation.__name__, case_id(case), precision, r)
+    if not (precision == "f32" and mutation in (mut_double_scale, mut_zero_lo)):
         assert seen > 0, "the mutation was never expressible"

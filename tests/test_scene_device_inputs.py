@@ -96,7 +96,8 @@ def test_reference_fixtures_hold_the_cluster_margin(case):
 
 
 def test_there_are_the_fourteen_reference_fixtures():
-    assert len(WRAPPER_CASES) == 14 and "wrapper_jmid_entering.npz" in WRAPPER_CASES
+    other_widths = [c for c in WRAPPER_CASES if c.startswith(("wrapper_jmid_w64_", "wrapper_jmid_w128_"))]      # tests/width_cases.py: hidden 32 and 64
+    assert len(WRAPPER_CASES) - len(other_widths) == 14 and len(other_widths) == 2 and "wrapper_jmid_entering.npz" in WRAPPER_CASES
 
 
 def test_entering_fixture_is_the_threshold_case():

@@ -22,7 +22,9 @@ from safe_interactive_crowdnav_amd.schedule import VarianceSchedule, ddim_steps,
 from safe_interactive_crowdnav_amd.weights import JMIDWeights, NetDims
 
 f32, f64 = np.float32, np.float64
-CASES = [(s, c, m, 0) for s in S.SHAPES for c in S.WIDTHS for m in S.MODES] + [(S.BIG_SHAPE, 32, m, S.BIG_TPW) for m in ("f16mx", "f32")]
+CASES = [(s, c, m, 0) for s in S.SHAPES for c in S.OLD_WIDTHS for m in S.MODES] + [(S.BIG_SHAPE, 32, m, S.BIG_TPW) for m in ("f16mx", "f32")]
+# ... and the other widths of tests/width_cases.py at the shapes the GPU test runs them at
+CASES += [(s, c, m, 0) for s in S.NEW_SHAPES for c in S.WIDTHS if c not in S.OLD_WIDTHS for m in S.MODES]
 DDIM_STEP, DDPM_STEP, DDPM_LAST, FLEX = 3, 40, 99, 0.5
 _W = {}
 
