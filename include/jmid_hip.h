@@ -910,6 +910,52 @@ int jmid_predict_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T
 int jmid_forecast_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, int k, uint64_t seed, const uint32_t* episode_ids, float dt,
                                       int precision, const float* bw, double* forecasts_out, double* logw_out);
 
+/* Constrained chains: guidance and repair INSIDE the one-entry chains - one upload, the phases on the stream, one download that brings the
+ * reports with it.  OFF unless these entries are called; no existing entry, layout or refusal changes.
+ *   jmid_predict_constrained          n_agents NULL: jmid_predict; a HOST array [E]: jmid_predict_padded
+ *   jmid_predict_scene_constrained    x_T NULL: the seeded form from (seed, episode_ids) (draw 0, by the padded rule when `padded`), else x_T
+ *                                     and (seed, episode_ids) unread; `padded` != 0: the rules of jmid_predict_scene_padded
+ *   jmid_forecast_scene_constrained   the same for jmid_forecast_scene / _seeded / _padded / _padded_seeded
+ * THE RULE is a composition, not a restatement.  A constrained chain equals, bit for bit in every output and every report row, the staged
+ * calls: the gathered rows of the scene (jmid_scene_get; or the caller's arrays) -> jmid_encode / jmid_encode_var -> jmid_denoise_guided
+ * [_seeded] when guide_weights is given, else jmid_denoise[_padded][_seeded] -> when `repair`, jmid_repair_collisions (repair_walls = 0)
+ * or jmid_repair_collisions_walls on the resident set (pos = NULL, with p0 and dt) -> jmid_topk[_padded](pos = NULL) -> the assembly of
+ * jmid_forecast_scene.  The ranking and the assembly read the repaired set, and with pos_out so does the caller.
+ *   threshold      of both mechanisms (metres between two pedestrians' centres)
+ *   guide_weights  double [n_steps], a HOST array (the installed DDIM table), or NULL: no guidance.  n_inner, guide_margin, guide_tau: the
+ *                  n_inner, margin and tau of jmid_denoise_guided.  guide_walls != 0: the guidance takes the wall terms too
+ *   repair         0: no repair.  margin, tau, step, max_iter: those of jmid_repair_collisions.  repair_walls != 0: the repair with walls
+ *   L, walls, wall_radius   [L, 4] float64 {x1, y1, x2, y2}, a HOST array; sent once per call, for both mechanisms.  Read only when
+ *                  guide_walls or repair_walls asks for them
+ *   guide_out [E, K, 2], sample_out [E, K, 4], episode_out [E, 3] int32, wall_out [E, K, 2]: HOST arrays, each may be NULL - the rows of
+ *                  jmid_denoise_guided, jmid_repair_collisions and jmid_repair_collisions_walls, unchanged.  A mechanism that is off leaves
+ *                  zeros in its rows (no guided step; state 0); a repair without repair_walls leaves +inf in wall_out (that entry's L = 0)
+ * With guidance the denoise loop is never captured into a graph (as jmid_denoise_guided); a repair-only chain keeps whatever capture the
+ * unconstrained chain of its shape has.  The repair phase is the staged entries' launches on the handle's stream between the denoise stage
+ * and the ranking; the reports lie inside the chain's download block: still one device-to-host copy and one synchronisation per call.
+ * Not here: the redraw loop (jmid_denoise_reject_*), DDPM.
+ * JMID_EINVAL, before anything is enqueued: whatever the namesake chain refuses; whatever jmid_denoise_guided and
+ * jmid_repair_collisions_walls refuse for the same arguments (so T >= 2 with repair); guide_walls or repair_walls with L = 0; a DDPM table.
+ * JMID_ERANGE and JMID_ETIMEOUT as in the chains (the reports are then undefined too). */
+int jmid_predict_constrained(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
+                             const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, double threshold,
+                             const double* guide_weights, int n_inner, double guide_margin, double guide_tau, int guide_walls, int repair,
+                             double margin, double tau, double step, int max_iter, int repair_walls, int L, const double* walls,
+                             double wall_radius, float* sel, float* logw, float* pos_out, float* guide_out, float* sample_out,
+                             int32_t* episode_out, float* wall_out);
+int jmid_predict_scene_constrained(jmid_handle_t h, int E, int A, int K, int T, int k, int padded, const float* x_T, uint64_t seed,
+                                   const uint32_t* episode_ids, float dt, int precision, const float* bw, double threshold,
+                                   const double* guide_weights, int n_inner, double guide_margin, double guide_tau, int guide_walls, int repair,
+                                   double margin, double tau, double step, int max_iter, int repair_walls, int L, const double* walls,
+                                   double wall_radius, float* sel, float* logw, float* pos_out, float* guide_out, float* sample_out,
+                                   int32_t* episode_out, float* wall_out);
+int jmid_forecast_scene_constrained(jmid_handle_t h, int E, int A, int K, int T, int k, int padded, const float* x_T, uint64_t seed,
+                                    const uint32_t* episode_ids, float dt, int precision, const float* bw, double threshold,
+                                    const double* guide_weights, int n_inner, double guide_margin, double guide_tau, int guide_walls, int repair,
+                                    double margin, double tau, double step, int max_iter, int repair_walls, int L, const double* walls,
+                                    double wall_radius, double* forecasts_out, double* logw_out, float* guide_out, float* sample_out,
+                                    int32_t* episode_out, float* wall_out);
+
 /* ---- the denoising loss on data with known futures: DiffusionTraj.get_loss (MID/models/diffusion.py:448-476), reached through
  * AutoEncoder.get_loss (MID/models/autoencoder.py:105-122) from MID.validation() (MID/mid.py:252-296, its "Avg. Val Loss") - the
  * noise-prediction MSE of ONE net evaluation per scene, every agent row at a timestep of its own.

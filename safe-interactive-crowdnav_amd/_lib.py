@@ -19,6 +19,11 @@ EINVAL, ENOWEIGHT, EHIP, ENOMEM, ERANGE, ETIMEOUT, EHISTORY = -1, -2, -3, -4, -5
 ERR_NAMES = {EINVAL: "JMID_EINVAL", ENOWEIGHT: "JMID_ENOWEIGHT", EHIP: "JMID_EHIP", ENOMEM: "JMID_ENOMEM", ERANGE: "JMID_ERANGE",
              ETIMEOUT: "JMID_ETIMEOUT", EHISTORY: "JMID_EHISTORY"}
 
+# the <constraints> arguments the constrained chains share: threshold, guide_weights, n_inner, guide_margin, guide_tau, guide_walls, repair,
+# margin, tau, step, max_iter, repair_walls, L, walls, wall_radius
+_CONSTRAINTS = [C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                C.c_int, C.c_void_p, C.c_double]
+
 # name -> (restype, argtypes): every symbol declared in include/jmid_hip.h
 SIGNATURES = {
     "jmid_version": (C.c_char_p, []),
@@ -124,6 +129,12 @@ SIGNATURES = {
                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_forecast_scene_padded_seeded": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_float,
                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jmid_predict_constrained": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p] + _CONSTRAINTS + [C.c_void_p] * 7),
+    "jmid_predict_scene_constrained": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
+                                                 C.c_void_p, C.c_float, C.c_int, C.c_void_p] + _CONSTRAINTS + [C.c_void_p] * 7),
+    "jmid_forecast_scene_constrained": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
+                                                  C.c_void_p, C.c_float, C.c_int, C.c_void_p] + _CONSTRAINTS + [C.c_void_p] * 6),
     "jmid_set_loss_schedule": (C.c_int, [Handle, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jmid_loss": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

@@ -84,7 +84,9 @@ EncArgs encoder_args(const jmid_ctx* h, const float* x_st, const float* nbr_sum,
 // scene mode the copy starts at x_T and the gather overwrites the p0 slot after it, on the stream) | ctx | the download block (flag,
 // forecasts, their logw, sel, logw, pos: contiguous, one copy, ending behind the assembled arrays of a forecast) | the dense [E * A] copy of
 // a resident scene's first_index.  pinned: the handle's pinned block instead - upload + download and nothing else, with the same inner
-// offsets.  base null: the size only
+// offsets.  A constrained chain (c.cons) adds its four report arrays behind the forecasts' logw, inside the download block of either form,
+// and - with repair, on the device only - the predicates' lean values at the very end; without constraints both layouts are what they
+// always were.  base null: the size only
 size_t chain_io(const jmid_ctx* h, const ChainCall& c, char* base, ChainIo* out, bool pinned) {
     const size_t n = (size_t)c.E * c.A, Th = h->hist_len, n_xT = (size_t)c.E * c.K * c.A * c.T * 2, Np = c.forecast ? h->scene.N : 0;
     Carver cv(base);
@@ -95,10 +97,16 @@ size_t chain_io(const jmid_ctx* h, const ChainCall& c, char* base, ChainIo* out,
     if (!pinned) io.ctx = cv.arr(n * 2 * h->H);
     const size_t down = cv.off;
     io.flag = cv.arr<int>(1); io.forecasts = cv.arr<double>((size_t)c.E * Np * c.k * (c.T + 1) * 2); io.logw_d = cv.arr<double>((size_t)c.E * Np * c.k);
+    if (c.cons) {      // a constrained chain: the four reports, inside the download block of either form (nothing of this without constraints)
+        const size_t EK = (size_t)c.E * c.K;
+        io.guide = cv.arr(EK * GDE_COLS); io.rsample = cv.arr(EK * RPR_SAMPLE_COLS); io.repisode = cv.arr<int>((size_t)c.E * RPR_EPISODE_COLS);
+        io.rwall = cv.arr(EK * RPR_WALL_COLS);
+    }
     if (c.forecast) io.down_bytes = cv.off - down;
     if (!c.forecast || !pinned) io.sel = cv.arr(c.rank() ? n * c.k * c.T * 2 : 0), io.logw = cv.arr(c.rank() ? n * c.k : 0), io.pos = cv.arr(c.pos_out ? n_xT : 0);
     if (!c.forecast) io.down_bytes = cv.off - down;
     if (!pinned && c.scene && h->scene.has_first()) io.first_index = cv.arr<int>(n);
+    if (!pinned && c.cons && c.cons->repair) io.gate = cv.arr<double>((size_t)c.E * c.K * (CLS_WS_COLS + WLS_WS_COLS));
     if (out) *out = io;
     return cv.off;
 }
@@ -108,6 +116,7 @@ size_t chain_io(const jmid_ctx* h, const ChainCall& c, char* base, ChainIo* out,
 struct ChainRun {
     ChainIo dev, pin;
     const int* nag_dev = nullptr;
+    const double* walls = nullptr;      // a constrained chain with walls: where upload_walls put them, once, for the guidance and the repair
 };
 
 int reserve_chain_io(jmid_ctx* h, const ChainCall& c, Block& b, bool pinned, ChainIo* io) {
@@ -164,7 +173,51 @@ int denoise_stage(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
     DenoiseCall d{c.E, c.A, c.K, c.T, c.precision, JMID_MEM_DEVICE};
     d.x_in = r.dev.x_T; d.ctx = r.dev.ctx; d.p0 = r.dev.p0; d.dt = c.dt; d.pos_out = r.dev.pos; d.chained = true;
     d.n_agents = c.n_agents; d.n_agents_dev = r.nag_dev; d.who = c.who;
+    GuideCall gc;
+    if (const ChainConstraints* k = c.cons) {
+        if (k->repair) d.pos_out = nullptr;      // (the repair phase copies the set out once it has repaired it)
+        if (k->guided()) {      // the guide kernel reads the chain's own p0 slot and the counts the denoise call has anyway
+            gc.threshold = k->threshold; gc.margin = k->guide_margin; gc.tau = k->guide_tau; gc.weights = k->guide_weights; gc.n_inner = k->n_inner;
+            gc.L = k->guide_walls ? k->L : 0; gc.walls = gc.L ? r.walls : nullptr; gc.wall_radius = k->guide_walls ? k->wall_radius : 0.0;
+            gc.guide_out = r.dev.guide;
+            d.guide = &gc;
+        }
+    }
     return run_network(h, d);
+}
+
+// phase 3b (a constrained chain with repair): the launches of jmid_repair_collisions[_walls](pos = NULL) on the set the denoise stage left,
+// in place, on the handle's stream - the ranking and the assembly then read the repaired set, and with pos_out the block is copied out
+// here.  (A variant of the repair kernel that evaluates the candidate gate itself, one launch instead of three or four, was measured
+// inside this phase and did not pay: docs/NOTEBOOK.md section 41)
+int repair_samples(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
+    const ChainConstraints& k = *c.cons;
+    const int E = c.E, A = c.A, K = c.K, T = c.T, L = k.repair_walls ? k.L : 0;
+    const int* nag = r.nag_dev ? r.nag_dev : c.padded ? h->nag.get<int>() : nullptr;      // (host arrays: the denoise stage's upload)
+    const size_t lean = (size_t)E * K * CLS_WS_COLS;
+    CollisionStatsArgs cs{};
+    cs.E = E; cs.A = A; cs.K = K; cs.T = T; cs.threshold = k.threshold;
+    cs.pos = h->last_pos; cs.ws = r.dev.gate.p; cs.n_agents = nag;
+    WallStatsArgs ws{};
+    ws.E = E; ws.A = A; ws.K = K; ws.T = T; ws.L = L; ws.radius = k.wall_radius;
+    ws.walls = L > 0 ? r.walls : nullptr; ws.pos = h->last_pos; ws.n_agents = nag;
+    ws.p0 = L > 0 ? r.dev.p0.p : nullptr;      // (the first point of every path; without walls the repair reads no p0)
+    ws.ws = L > 0 ? r.dev.gate.p + lean : nullptr;
+    RepairWallArgs g{};
+    g.E = E; g.A = A; g.K = K; g.T = T; g.max_iter = k.max_iter;
+    g.threshold = k.threshold; g.margin = k.margin; g.tau = k.tau; g.step = k.step; g.dt = (double)c.dt;
+    g.L = L; g.walls = ws.walls; g.wall_radius = k.repair_walls ? k.wall_radius : 0.0;
+    g.src = h->last_pos; g.dst = const_cast<float*>(h->last_pos); g.p0 = ws.p0; g.n_agents = nag;
+    g.sample = r.dev.rsample; g.episode = r.dev.repisode; g.wall_out = r.dev.rwall;
+    g.ws = cs.ws; g.wws = ws.ws;
+    {
+        ProfScope ps(h, KC_EVAL_STATS, h->stream);
+        HIPCHK(h, launch_collision_stats(cs, h->stream));
+        if (L > 0) HIPCHK(h, launch_wall_stats(ws, h->stream));
+        HIPCHK(h, launch_repair_walls(g, h->stream));      // (L = 0: jmid_repair_collisions' launches, +inf in the wall rows)
+    }
+    if (r.dev.pos.n) HIPCHK(h, hipMemcpyAsync(r.dev.pos.p, h->last_pos, r.dev.pos.bytes(), hipMemcpyDeviceToDevice, h->stream));
+    return 0;
 }
 
 // phase 4 (k < K): the KDE ranks the positions the denoise stage left in the workspace -> sel, logw
@@ -202,6 +255,12 @@ int finish_chain(jmid_ctx* h, const ChainCall& c, const ChainRun& r) {
     HIPCHK(h, hipMemcpyAsync(pin.flag.p, dev.flag.p, dev.down_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (flagged && *pin.flag.p) return jmid_host::flagged_call(h, *pin.flag.p);
+    if (const ChainConstraints* k = c.cons) {      // the reports came with the same copy
+        if (k->guide_out) std::memcpy(k->guide_out, pin.guide.p, pin.guide.bytes());
+        if (k->sample_out) std::memcpy(k->sample_out, pin.rsample.p, pin.rsample.bytes());
+        if (k->episode_out) std::memcpy(k->episode_out, pin.repisode.p, pin.repisode.bytes());
+        if (k->wall_out) std::memcpy(k->wall_out, pin.rwall.p, pin.rwall.bytes());
+    }
     if (c.forecast) {
         std::memcpy(c.forecasts_out, pin.forecasts.p, pin.forecasts.bytes());
         std::memcpy(c.logw_out, pin.logw_d.p, pin.logw_d.bytes());
@@ -221,9 +280,18 @@ int predict_chain(jmid_ctx* h, const ChainCall& c) {
     if (c.scene && c.padded) r.nag_dev = h->scene.arr.n_in;
     if (int rc = reserve_chain_io(h, c, h->io_dev, false, &r.dev)) return rc;
     if (int rc = reserve_chain_io(h, c, h->pin, true, &r.pin)) return rc;
+    if (const ChainConstraints* k = c.cons) {
+        // the walls go up once and serve both mechanisms; the report rows of a mechanism that is off are zero (state 0, no guided step)
+        if (k->walled())
+            if (int rc = upload_walls(h, k->L, k->walls, &r.walls, c.who)) return rc;
+        char* const z0 = (char*)(k->guided() ? r.dev.rsample.p : r.dev.guide.p);
+        char* const z1 = k->repair ? (char*)r.dev.rsample.p : (char*)r.dev.rwall.p + align_up(r.dev.rwall.bytes());
+        if (z1 > z0) HIPCHK(h, hipMemsetAsync(z0, 0, (size_t)(z1 - z0), h->stream));
+    }
     int rc = stage_inputs(h, c, r);
     if (!rc) rc = gather_encode(h, c, r);
     if (!rc) rc = denoise_stage(h, c, r);
+    if (!rc && c.cons && c.cons->repair) rc = repair_samples(h, c, r);
     if (!rc && c.rank()) rc = rank_samples(h, c, r);
     if (!rc && c.forecast) rc = assemble_forecasts(h, c, r);
     return rc ? rc : finish_chain(h, c, r);
@@ -942,6 +1010,23 @@ int jmid_wall_statistics_padded(jmid_handle_t h, int E, int A, int K, int T, con
     return wall_entry(h, "jmid_wall_statistics_padded", E, A, K, T, n_agents, pos, p0, L, walls, radius, dist_out, agent_out, sample_out, scene_out, mem);
 }
 
+// What the repair entries and a constrained chain with repair refuse alike: the shape limits and the conditions on the rule's arguments
+// (with_p0: the call has a p0, so the velocities divide by dt)
+static int repair_check(jmid_handle_t h, const std::string& w, bool with_walls, int E, int A, int K, int T, bool with_p0, float dt, double threshold,
+                        double margin, double tau, double step, int max_iter, double wall_radius) {
+    if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
+        return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(h, JMID_EINVAL, w + ": the threshold must be finite and >= 0");
+    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(h, JMID_EINVAL, w + ": the margin must be finite and >= 0");
+    if (!(tau > 0.0) || !std::isfinite(tau)) return fail(h, JMID_EINVAL, w + ": tau must be finite and > 0");
+    if (!(step > 0.0) || !std::isfinite(step)) return fail(h, JMID_EINVAL, w + ": the step must be finite and > 0");
+    if (max_iter < 0 || max_iter > RPR_MAX_ITER) return fail(h, JMID_EINVAL, w + ": max_iter must lie in 0..1024");
+    if (with_p0 && !(dt > 0.0f && std::isfinite(dt))) return fail(h, JMID_EINVAL, w + ": p0 needs a finite dt > 0 (the velocities divide by it)");
+    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
+    if (with_walls && (!(wall_radius >= 0.0) || !std::isfinite(wall_radius))) return fail(h, JMID_EINVAL, w + ": the wall_radius must be finite and >= 0");
+    return 0;
+}
+
 // The repair of colliding samples (repair.hpp): the collision kernel's lean form for the flags, the repair kernel, the episode rows - three
 // launches on the handle's stream, nothing comes back to the host in between.  pos null: the resident set, in place.
 // jmid_repair_collisions (with_walls false: L = 0, no wall_out) and jmid_repair_collisions_walls: with L > 0 the wall kernel's lean form runs
@@ -951,18 +1036,9 @@ static int repair_entry(jmid_handle_t h, const char* who, bool with_walls, int E
                         double wall_radius, float* pos_out, float* vel_out, float* sample_out, int32_t* episode_out, float* wall_out, int mem) {
     if (!h || E <= 0) return fail(h, JMID_EINVAL, "bad argument");
     const std::string w(who);
-    if (K < 1 || K > CLS_MAX_K || T < 2 || T > CLS_MAX_T || A < 1 || A > CLS_MAX_A)
-        return fail(h, JMID_EINVAL, w + " supports 1 <= K <= 1024, 2 <= T <= 24, 1 <= A <= 64");
-    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(h, JMID_EINVAL, w + ": the threshold must be finite and >= 0");
-    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(h, JMID_EINVAL, w + ": the margin must be finite and >= 0");
-    if (!(tau > 0.0) || !std::isfinite(tau)) return fail(h, JMID_EINVAL, w + ": tau must be finite and > 0");
-    if (!(step > 0.0) || !std::isfinite(step)) return fail(h, JMID_EINVAL, w + ": the step must be finite and > 0");
-    if (max_iter < 0 || max_iter > RPR_MAX_ITER) return fail(h, JMID_EINVAL, w + ": max_iter must lie in 0..1024");
+    if (int rc = repair_check(h, w, with_walls, E, A, K, T, p0 != nullptr, dt, threshold, margin, tau, step, max_iter, wall_radius)) return rc;
     if (vel_out && !p0) return fail(h, JMID_EINVAL, w + ": vel_out needs p0 (a velocity's first step starts at the present position)");
-    if (p0 && !(dt > 0.0f && std::isfinite(dt))) return fail(h, JMID_EINVAL, w + ": p0 needs a finite dt > 0 (the velocities divide by it)");
     if (pos && !pos_out && !vel_out && !sample_out && !episode_out && !wall_out) return fail(h, JMID_EINVAL, w + ": every output is NULL");
-    if ((size_t)E * K > (size_t)0x7fffffff) return fail(h, JMID_EINVAL, w + ": E * K exceeds the launch grid");
-    if (with_walls && (!(wall_radius >= 0.0) || !std::isfinite(wall_radius))) return fail(h, JMID_EINVAL, w + ": the wall_radius must be finite and >= 0");
     if (n_agents)
         if (int rc = check_n_agents(h, who, n_agents, E, A)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1543,6 +1619,111 @@ int jmid_forecast_scene_padded_seeded(jmid_handle_t h, int E, int A, int K, int 
     ChainCall c = chain_call("jmid_forecast_scene_padded_seeded", E, A, K, T, k, dt, precision);
     c.forecast = c.padded = true; c.seeded = &sa; c.bw = bw; c.forecasts_out = forecasts_out; c.logw_out = logw_out;
     return predict_scene_entry(h, c);
+}
+
+// The constraints value of a constrained chain from the entries' common argument list
+static ChainConstraints chain_constraints(double threshold, const double* guide_weights, int n_inner, double guide_margin, double guide_tau,
+                                          int guide_walls, int repair, double margin, double tau, double step, int max_iter, int repair_walls, int L,
+                                          const double* walls, double wall_radius, float* guide_out, float* sample_out, int32_t* episode_out,
+                                          float* wall_out) {
+    ChainConstraints k;
+    k.threshold = threshold;
+    k.guide_weights = guide_weights; k.n_inner = n_inner; k.guide_margin = guide_margin; k.guide_tau = guide_tau; k.guide_walls = guide_walls != 0;
+    k.repair = repair != 0; k.margin = margin; k.tau = tau; k.step = step; k.max_iter = max_iter; k.repair_walls = repair_walls != 0;
+    k.L = L; k.walls = walls; k.wall_radius = wall_radius;
+    k.guide_out = guide_out; k.sample_out = sample_out; k.episode_out = episode_out; k.wall_out = wall_out;
+    return k;
+}
+
+// What a constrained chain refuses on top of its namesake, before anything is enqueued: what jmid_denoise_guided (guide_check, the weights)
+// and jmid_repair_collisions_walls (repair_check) refuse for the same arguments, walls asked for with L = 0, a DDPM table
+static int check_constraints(jmid_handle_t h, const ChainCall& c) {
+    if (!h) return JMID_EINVAL;
+    if (int rc = check_ready(h)) return rc;
+    const ChainConstraints& k = *c.cons;
+    const std::string w(c.who);
+    if (h->ddpm) return fail(h, JMID_EINVAL, w + ": a constrained chain samples with DDIM only (a DDPM table is installed)");
+    if (k.L < 0 || k.L > WLS_MAX_L) return fail(h, JMID_EINVAL, w + " supports 0 <= L <= 64 walls");
+    if (k.L == 0 && ((k.guided() && k.guide_walls) || (k.repair && k.repair_walls)))
+        return fail(h, JMID_EINVAL, w + ": guide_walls / repair_walls need L > 0 walls");
+    if (k.walled() && !k.walls) return fail(h, JMID_EINVAL, w + ": null walls with L > 0");
+    static const float present = 0.f;      // (a scene chain's p0 is the resident scene's: there is always one)
+    const float* p0 = c.scene ? &present : c.p0;
+    if (k.guided()) {
+        if (int rc = guide_check(h, w, c.E, c.A, c.K, c.T, p0, c.dt, k.threshold, k.guide_margin, k.guide_tau, k.n_inner, k.guide_walls ? k.wall_radius : 0.0))
+            return rc;
+        for (size_t i = 0; i < h->beta.size(); ++i)
+            if (!(k.guide_weights[i] >= 0.0) || !std::isfinite(k.guide_weights[i]))
+                return fail(h, JMID_EINVAL, w + ": weights[" + std::to_string(i) + "] must be finite and >= 0");
+    }
+    if (k.repair) {
+        if (c.E <= 0) return fail(h, JMID_EINVAL, w + ": bad argument");
+        if (int rc = repair_check(h, w, k.repair_walls, c.E, c.A, c.K, c.T, true, c.dt, k.threshold, k.margin, k.tau, k.step, k.max_iter, k.wall_radius)) return rc;
+    }
+    if (!k.guided() && !k.repair && (!(k.threshold >= 0.0) || !std::isfinite(k.threshold)))
+        return fail(h, JMID_EINVAL, w + ": the threshold must be finite and >= 0");
+    if (k.walled())
+        for (int i = 0; i < k.L * 4; ++i)
+            if (!std::isfinite(k.walls[i])) return fail(h, JMID_EINVAL, w + ": a wall has a non-finite coordinate");
+    return 0;
+}
+
+int jmid_predict_constrained(jmid_handle_t h, int E, int A, int K, int T, int k, const int32_t* n_agents, const float* x_st, const float* nbr_sum,
+                             const float* edge_mask, const float* x_T, const float* p0, float dt, int precision, const float* bw, double threshold,
+                             const double* guide_weights, int n_inner, double guide_margin, double guide_tau, int guide_walls, int repair,
+                             double margin, double tau, double step, int max_iter, int repair_walls, int L, const double* walls,
+                             double wall_radius, float* sel, float* logw, float* pos_out, float* guide_out, float* sample_out,
+                             int32_t* episode_out, float* wall_out) {
+    if (!h) return JMID_EINVAL;
+    const ChainConstraints cons = chain_constraints(threshold, guide_weights, n_inner, guide_margin, guide_tau, guide_walls, repair, margin, tau, step,
+                                                    max_iter, repair_walls, L, walls, wall_radius, guide_out, sample_out, episode_out, wall_out);
+    ChainCall c = chain_call("jmid_predict_constrained", E, A, K, T, k, dt, precision);
+    if (n_agents) {
+        if (int rc = check_n_agents(h, c.who, n_agents, E, A)) return rc;
+        c.padded = true; c.n_agents = n_agents;
+    }
+    c.x_st = x_st; c.nbr_sum = nbr_sum; c.edge_mask = edge_mask; c.x_T = x_T; c.p0 = p0; c.bw = bw;
+    c.sel = sel; c.logw = logw; c.pos_out = pos_out; c.cons = &cons;
+    if (int rc = check_constraints(h, c)) return rc;
+    return predict_entry(h, c);
+}
+
+// jmid_predict_scene_constrained and jmid_forecast_scene_constrained: the scene chain of (padded, x_T or seed) with the constraints value
+static int scene_constrained_entry(jmid_handle_t h, ChainCall c, int padded, const float* x_T, uint64_t seed, const uint32_t* episode_ids,
+                                   const ChainConstraints& cons) {
+    if (!h) return JMID_EINVAL;
+    const SeedArgs sa{seed, episode_ids};
+    c.padded = padded != 0; c.x_T = x_T; c.cons = &cons;
+    if (!x_T) c.seeded = &sa;
+    c.scene = true;      // (predict_scene_entry says so too: the check below reads it)
+    if (int rc = check_constraints(h, c)) return rc;
+    return predict_scene_entry(h, c);
+}
+
+int jmid_predict_scene_constrained(jmid_handle_t h, int E, int A, int K, int T, int k, int padded, const float* x_T, uint64_t seed,
+                                   const uint32_t* episode_ids, float dt, int precision, const float* bw, double threshold,
+                                   const double* guide_weights, int n_inner, double guide_margin, double guide_tau, int guide_walls, int repair,
+                                   double margin, double tau, double step, int max_iter, int repair_walls, int L, const double* walls,
+                                   double wall_radius, float* sel, float* logw, float* pos_out, float* guide_out, float* sample_out,
+                                   int32_t* episode_out, float* wall_out) {
+    const ChainConstraints cons = chain_constraints(threshold, guide_weights, n_inner, guide_margin, guide_tau, guide_walls, repair, margin, tau, step,
+                                                    max_iter, repair_walls, L, walls, wall_radius, guide_out, sample_out, episode_out, wall_out);
+    ChainCall c = chain_call("jmid_predict_scene_constrained", E, A, K, T, k, dt, precision);
+    c.bw = bw; c.sel = sel; c.logw = logw; c.pos_out = pos_out;
+    return scene_constrained_entry(h, c, padded, x_T, seed, episode_ids, cons);
+}
+
+int jmid_forecast_scene_constrained(jmid_handle_t h, int E, int A, int K, int T, int k, int padded, const float* x_T, uint64_t seed,
+                                    const uint32_t* episode_ids, float dt, int precision, const float* bw, double threshold,
+                                    const double* guide_weights, int n_inner, double guide_margin, double guide_tau, int guide_walls, int repair,
+                                    double margin, double tau, double step, int max_iter, int repair_walls, int L, const double* walls,
+                                    double wall_radius, double* forecasts_out, double* logw_out, float* guide_out, float* sample_out,
+                                    int32_t* episode_out, float* wall_out) {
+    const ChainConstraints cons = chain_constraints(threshold, guide_weights, n_inner, guide_margin, guide_tau, guide_walls, repair, margin, tau, step,
+                                                    max_iter, repair_walls, L, walls, wall_radius, guide_out, sample_out, episode_out, wall_out);
+    ChainCall c = chain_call("jmid_forecast_scene_constrained", E, A, K, T, k, dt, precision);
+    c.forecast = true; c.bw = bw; c.forecasts_out = forecasts_out; c.logw_out = logw_out;
+    return scene_constrained_entry(h, c, padded, x_T, seed, episode_ids, cons);
 }
 
 int jmid_denoise_padded_seeded(jmid_handle_t h, int E, int A, int K, int T, const int32_t* n_agents, uint64_t seed, const uint32_t* episode_ids,

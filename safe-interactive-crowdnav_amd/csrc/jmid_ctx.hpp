@@ -392,6 +392,27 @@ struct DenoiseCall {
     const GuideCall* guide = nullptr;
     const char* who = "jmid_denoise";     // the entry point that was called (error texts)
 };
+// What a constrained chain (jmid_predict_constrained, jmid_predict_scene_constrained, jmid_forecast_scene_constrained) carries through its
+// phases: the guidance of the denoise stage, the repair between the denoise stage and the ranking, the walls both may read, and the HOST
+// report arrays that come back with the one download.  A value of the call: nothing of it stays on the handle
+struct ChainConstraints {
+    double threshold = 0.0;
+    const double* guide_weights = nullptr;      // HOST [n_steps] or null: no guidance
+    int n_inner = 0;
+    double guide_margin = 0.0, guide_tau = 0.0;
+    bool guide_walls = false;                   // the guidance takes the wall terms (L > 0)
+    bool repair = false;
+    double margin = 0.0, tau = 0.0, step = 0.0;
+    int max_iter = 0;
+    bool repair_walls = false;                  // the repair is jmid_repair_collisions_walls' (L > 0)
+    int L = 0;
+    const double* walls = nullptr;              // HOST [L, 4]: sent once per call, for both mechanisms
+    double wall_radius = 0.0;
+    float *guide_out = nullptr, *sample_out = nullptr, *wall_out = nullptr;      // HOST [E, K, 2] | [E, K, 4] | [E, K, 2], each may be null
+    int32_t* episode_out = nullptr;                                             // HOST [E, 3] or null
+    bool guided() const { return guide_weights != nullptr; }
+    bool walled() const { return L > 0 && ((guided() && guide_walls) || (repair && repair_walls)); }
+};
 // One chained call (jmid_predict*, jmid_predict_scene*, jmid_forecast_scene*) as its entry point states it: upload, encoder -> denoise
 // loop -> integrator -> top-k (-> assembly) on the stream, one download.  The modes are members, not null pointers read at a distance.
 struct ChainCall {
@@ -412,6 +433,7 @@ struct ChainCall {
     // copy of the resident scene's counts; the stages read the device counts the build kernel wrote (nothing is uploaded for them),
     // the gather zeroes the padded rows and a seeded x_T is the padded fill
     const int32_t* n_agents = nullptr;
+    const ChainConstraints* cons = nullptr;      // the constrained entries only: null for every other chain
     bool rank() const { return k < K; }
 };
 // The I/O block of a chained call as chain_io lays it out, in device memory or (ctx and first_index absent, and after the assembled
@@ -422,9 +444,13 @@ struct ChainIo {
     Arr<float> ctx;                                        // [E A, 2 H]
     Arr<int> flag;                                         // the download block: the range flag's word |
     Arr<double> forecasts, logw_d;                         // forecast: [E, N, k, T+1, 2] | [E, N, k] |
+    Arr<float> guide, rsample;                             // constrained: the reports [E, K, 2] | [E, K, 4] |
+    Arr<int> repisode;                                     //   [E, 3] |
+    Arr<float> rwall;                                      //   [E, K, 2] |
     Arr<float> sel, logw, pos;                             // k < K: [E, A, k, T, 2] | [E, A, k] | pos_out given: [E, K, A, T, 2]
-    size_t down_bytes = 0;                                 // flag ... pos; forecast: flag ... logw_d
+    size_t down_bytes = 0;                                 // flag ... pos; forecast: flag ... logw_d (constrained: ... rwall)
     Arr<int> first_index;                                  // a scene with one: [E A]
+    Arr<double> gate;                                      // a chain with repair: the predicates' lean per-sample values [E, K, 2] (with walls: twice)
     size_t up_bytes_from(const Arr<float>& a) const { return up_bytes - (size_t)((const char*)a.p - (const char*)x_st.p); }      // the rest of the upload block from `a` on
 };
 // One scene build (jmid_build_scene*, and the second half of jmid_build_scene_stamped*) as its entry point states it

@@ -115,6 +115,79 @@ class Guidance(NamedTuple):
     wall_radius: Optional[float] = None
 
 
+REPAIR_DEFAULTS = {"margin": 0.02, "tau": 0.005, "step": 0.02, "max_iter": 32}      # those of ``JmidEngine.repair_collisions``
+
+
+class ChainConstraints(NamedTuple):
+    """The constraints of a one-entry chain (``predict(constraints=)`` ... ``forecast_scene_padded(constraints=)``; the
+    ``jmid_*_constrained`` entries of include/jmid_hip.h): guided sampling inside the chain's denoise stage and collision repair between
+    that stage and the ranking, at one ``threshold``.  ``guidance``: a ``Guidance`` (its threshold must be this one), or None.
+    ``repair``: the keywords of ``JmidEngine.repair_collisions`` - margin, tau, step, max_iter, and ``walls`` with ``wall_radius`` for the
+    repair with walls - ({}: the defaults), or None: no repair.  Where both mechanisms take walls they are the same walls."""
+    threshold: float = 0.2
+    guidance: Optional[Guidance] = None
+    repair: Optional[dict] = None
+
+
+class ChainReport(NamedTuple):
+    """What a constrained chain reports next to its results, with the one download: the rows of the staged entries, unchanged.  ``guide``
+    [E, K, 2] (``metrics.GUIDE_COLUMNS``) or None without guidance; ``sample`` [E, K, 4] and ``episode`` [E, 3] int32
+    (``metrics.REPAIR_SAMPLE_COLUMNS`` / ``REPAIR_EPISODE_COLUMNS``) or None without repair; ``wall`` [E, K, 2]
+    (``metrics.REPAIR_WALL_COLUMNS``) or None unless the repair takes walls.  The episode axis is always there."""
+    guide: Optional[np.ndarray] = None
+    sample: Optional[np.ndarray] = None
+    episode: Optional[np.ndarray] = None
+    wall: Optional[np.ndarray] = None
+
+
+def chain_constraint_arguments(constraints: ChainConstraints, n_steps: int):
+    """The ``<constraints>`` arguments of the constrained chains from a ``ChainConstraints`` (threshold, guide_weights, n_inner,
+    guide_margin, guide_tau, guide_walls, repair, margin, tau, step, max_iter, repair_walls, L, walls, wall_radius) as plain Python values
+    and arrays - ``guide_weights`` float64 [n_steps] or None, ``walls`` float64 [L, 4] - with every refusal that needs no device."""
+    c = constraints
+    if not isinstance(c, ChainConstraints):
+        raise TypeError("constraints must be an engine.ChainConstraints")
+    threshold = float(c.threshold)
+    if not (np.isfinite(threshold) and threshold >= 0.0):
+        raise ValueError("constraints.threshold must be finite and >= 0")
+    g, walls, radius = c.guidance, None, None
+    weights, n_inner, g_margin, g_tau, g_walls = None, 0, 0.0, 0.0, 0
+    if g is not None:
+        if float(g.threshold) != threshold:
+            raise ValueError("constraints.guidance.threshold differs from constraints.threshold (a chain has one threshold)")
+        if g.weights is None:
+            raise ValueError("guidance needs weights: one per step-table entry (schedule.guidance_weights)")
+        weights = np.ascontiguousarray(np.asarray(g.weights, dtype=np.float64).reshape(-1))
+        if weights.size != n_steps:
+            raise ValueError(f"guidance.weights must hold one weight per step-table entry ({n_steps}), got {weights.size}")
+        if (g.walls is None) != (g.wall_radius is None):
+            raise ValueError("guidance: walls and wall_radius go together (the guidance knows no agent radius)")
+        n_inner, g_margin, g_tau = int(g.n_inner), float(g.margin), float(g.tau)
+        if g.walls is not None:
+            walls, radius, g_walls = wall_segments(g.walls), float(g.wall_radius), 1
+    margin, tau, step, max_iter, r_walls = 0.0, 0.0, 0.0, 0, 0
+    if c.repair is not None:
+        opts = dict(c.repair)
+        unknown = sorted(set(opts) - set(REPAIR_DEFAULTS) - {"walls", "wall_radius"})
+        if unknown:
+            raise ValueError(f"unknown repair options {unknown} (known: {sorted(REPAIR_DEFAULTS) + ['wall_radius', 'walls']})")
+        if (opts.get("walls") is None) != (opts.get("wall_radius") is None):
+            raise ValueError("repair: walls and wall_radius go together (the repair knows no agent radius)")
+        margin, tau, step = (float(opts.get(key, REPAIR_DEFAULTS[key])) for key in ("margin", "tau", "step"))
+        max_iter = int(opts.get("max_iter", REPAIR_DEFAULTS["max_iter"]))
+        if opts.get("walls") is not None:
+            rw, rr = wall_segments(opts["walls"]), float(opts["wall_radius"])
+            if walls is not None and (rw.shape != walls.shape or not np.array_equal(rw, walls) or rr != radius):
+                raise ValueError("the guidance and the repair of one chain take the same walls and wall_radius")
+            walls, radius, r_walls = rw, rr, 1
+    if walls is None:
+        walls, radius = np.zeros((0, 4), dtype=np.float64), 0.0
+    if (g_walls or r_walls) and walls.shape[0] == 0:
+        raise ValueError("walls are asked for, and there are none (L = 0)")
+    return (threshold, weights, n_inner, g_margin, g_tau, g_walls, int(c.repair is not None), margin, tau, step, max_iter, r_walls,
+            int(walls.shape[0]), walls, radius)
+
+
 class LossResult:
     """What ``JmidEngine.loss`` returns: ``loss``, ``count``, and ``rows`` / ``e_theta`` where they were asked for (else None)."""
     __slots__ = ("loss", "count", "rows", "e_theta")
@@ -535,20 +608,33 @@ class JmidEngine:
         return sel, lw
 
     def predict_padded(self, x_st: np.ndarray, nbr_sum: np.ndarray, edge_mask: np.ndarray, x_T: np.ndarray, p0: np.ndarray, k: int,
-                       n_agents, dt: float = 0.25, precision: str = "f32"):
+                       n_agents, dt: float = 0.25, precision: str = "f32", constraints: Optional[ChainConstraints] = None):
         """``predict`` for episodes of different agent counts in one call (``jmid_predict_padded``): the same arrays with A = the
         largest count as the row stride (``scene.pad_rows`` / ``scene.pad_samples`` make them) and ``n_agents`` [E].  The padded
-        agents' rows of every output are NaN."""
-        return self._predict(n_agents, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision)
+        agents' rows of every output are NaN.  ``constraints``: as ``predict``."""
+        return self._predict(n_agents, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision, constraints)
 
     def predict(self, x_st: np.ndarray, nbr_sum: np.ndarray, edge_mask: np.ndarray, x_T: np.ndarray, p0: np.ndarray, k: int,
-                dt: float = 0.25, precision: str = "f32"):
+                dt: float = 0.25, precision: str = "f32", constraints: Optional[ChainConstraints] = None):
         """One predictor call end to end (``jmid_predict``): encoder -> denoise loop -> integrator -> joint-KDE top-k, host arrays in
         and out, one upload, one download, nothing in between.  x_st [E*A, hist, 6], nbr_sum [E*A, 2, hist, 6], edge_mask [E*A, 2],
-        x_T [E, K*A, T, 2], p0 [E, A, 2].  k < K -> (kept [E, A, k, T, 2], log-weights [E, A, k]); k == K -> (pos [E, K, A, T, 2], None)."""
-        return self._predict(None, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision)
+        x_T [E, K*A, T, 2], p0 [E, A, 2].  k < K -> (kept [E, A, k, T, 2], log-weights [E, A, k]); k == K -> (pos [E, K, A, T, 2], None).
+        ``constraints`` (a ``ChainConstraints``; ``jmid_predict_constrained``): guided sampling and / or collision repair inside the same
+        one call - the bits of the staged ``encode`` -> ``denoise(guidance=)`` -> ``repair_collisions(None, ...)`` -> ``topk(None, ...)`` -
+        and a third value, the ``ChainReport``.  Without it the call is the call it always was."""
+        return self._predict(None, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision, constraints)
 
-    def _predict(self, n_agents, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision):
+    def _constrained(self, constraints: ChainConstraints, E: int, K: int):
+        """The ``<constraints>`` arguments of a constrained chain as ctypes takes them, the four report arrays behind its outputs (None
+        where the mechanism is off), and what the pointers point into."""
+        a = chain_constraint_arguments(constraints, self.n_steps)
+        weights, L, walls, repair, r_walls = a[1], a[12], a[13], a[6], a[11]
+        args = a[:1] + (_ptr(weights),) + a[2:13] + (_ptr(walls) if L else None, a[14])
+        report = ChainReport(_out((E, K, 2)) if weights is not None else None, _out((E, K, 4)) if repair else None,
+                             _out((E, 3), np.int32) if repair else None, _out((E, K, 2)) if r_walls else None)
+        return args, report, (weights, walls)
+
+    def _predict(self, n_agents, x_st, nbr_sum, edge_mask, x_T, p0, k, dt, precision, constraints=None):
         E, KA, T, _ = (int(v) for v in x_T.shape)
         A = int(p0.shape[1])
         K = KA // A
@@ -556,23 +642,32 @@ class JmidEngine:
                 or tuple(edge_mask.shape) != (E * A, 2) or KA != K * A or tuple(p0.shape) != (E, A, 2):
             raise ValueError("bad predict() input shapes")
         b = [_Buf(a, False) for a in (x_st, nbr_sum, edge_mask, x_T, p0)]
-        if n_agents is not None:
-            na = agent_counts(n_agents, E)
+        na = agent_counts(n_agents, E) if n_agents is not None else None
+        if constraints is not None:
+            fn, head = self._lib.jmid_predict_constrained, (self._h, E, A, K, T, int(k), _ptr(na))
+        elif na is not None:
             fn, head = self._lib.jmid_predict_padded, (self._h, E, A, K, T, int(k), _ptr(na))
         else:
             fn, head = self._lib.jmid_predict, (self._h, E, A, K, T, int(k))
-        return self._ranked_or_all(fn, (*head, *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k)
+        return self._ranked_or_all(fn, (*head, *[x.ptr for x in b], float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k, constraints)
 
-    def _ranked_or_all(self, fn, args, E: int, A: int, K: int, T: int, k: int):
+    def _ranked_or_all(self, fn, args, E: int, A: int, K: int, T: int, k: int, constraints: Optional[ChainConstraints] = None):
         """The output half of a chained predictor entry (``args`` = everything in front of it): k < K -> the joint-KDE top-k, (kept
-        [E, A, k, T, 2], log-weights [E, A, k]); k == K -> every sample, (pos [E, K, A, T, 2], None)."""
+        [E, A, k, T, 2], log-weights [E, A, k]); k == K -> every sample, (pos [E, K, A, T, 2], None).  ``constraints`` (``fn`` is then the
+        constrained entry): its arguments go between bw and the outputs, its report arrays behind them, and the ``ChainReport`` is the
+        third value."""
+        mid, tail, report = (), (), None
+        if constraints is not None:
+            mid, report, _keep = self._constrained(constraints, E, K)
+            tail = tuple(_ptr(r) for r in report)
+        more = () if report is None else (report,)
         if k < K:
             bw, sel, lw = kde_bandwidths(T), _out((E, A, k, T, 2)), _out((E, A, k))
-            self._compute(fn, *args, _ptr(bw), _ptr(sel), _ptr(lw), None)
-            return sel, lw
+            self._compute(fn, *args, _ptr(bw), *mid, _ptr(sel), _ptr(lw), None, *tail)
+            return (sel, lw) + more
         pos = _out((E, K, A, T, 2))
-        self._compute(fn, *args, None, None, None, _ptr(pos))
-        return pos, None
+        self._compute(fn, *args, None, *mid, None, None, _ptr(pos), *tail)
+        return (pos, None) + more
 
     def build_scene(self, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float, horizon: Optional[int] = None,
                     force_all_in_cluster: bool = False, first_frame=None, allow_absent: bool = False) -> Dict[str, np.ndarray]:
@@ -655,35 +750,47 @@ class JmidEngine:
         bx = _Buf(x_T, False)
         return E, A, KA // A, T, "", (bx.ptr,), bx
 
+    @staticmethod
+    def _constrained_noise(sfx, nz):
+        """The noise arguments of a constrained scene chain (x_T, seed, episode_ids) from ``_scene_noise``'s: x_T NULL selects the seeded form."""
+        return (None, *nz) if sfx else (*nz, 0, None)
+
     def predict_scene(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
-                      episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+                      episode_ids=None, K: Optional[int] = None, T: Optional[int] = None, constraints: Optional[ChainConstraints] = None):
         """``predict`` on the scene the preceding ``build_scene`` left on the device (``jmid_predict_scene``): x_T [E, K*A, T, 2] with A the
         in-cluster count of EVERY episode (``n_in``) and ``k`` kept futures of the K.  k < K -> (kept [E, A, k, T, 2], log-weights
         [E, A, k]); k == K -> (pos [E, K, A, T, 2], None).  The same bits as ``predict`` fed the in-cluster rows of ``scene_arrays``.
-        ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is drawn on the device (``jmid_predict_scene_seeded``)."""
-        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T)
+        ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is drawn on the device (``jmid_predict_scene_seeded``).
+        ``constraints`` (``jmid_predict_scene_constrained``): as ``predict`` - guidance and repair inside the one call, a third value."""
+        return self._predict_scene(False, x_T, k, dt, precision, seed, episode_ids, K, T, constraints)
+
+    def _predict_scene(self, padded, x_T, k, dt, precision, seed, episode_ids, K, T, constraints):
+        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T, padded)
         k = int(k)
-        fn = getattr(self._lib, "jmid_predict_scene" + sfx)
+        if constraints is not None:
+            head = (self._h, E, A, K, T, k, int(padded), *self._constrained_noise(sfx, nz))
+            return self._ranked_or_all(self._lib.jmid_predict_scene_constrained, (*head, float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k,
+                                       constraints)
+        fn = getattr(self._lib, ("jmid_predict_scene_padded" if padded else "jmid_predict_scene") + sfx)
         return self._ranked_or_all(fn, (self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k)
 
     def predict_scene_padded(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
-                             episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+                             episode_ids=None, K: Optional[int] = None, T: Optional[int] = None,
+                             constraints: Optional[ChainConstraints] = None):
         """``predict_scene`` for a resident scene of MIXED in-cluster counts, in one call (``jmid_predict_scene_padded``): A = the largest
         ``n_in``, x_T [E, K*A, T, 2] in the padded layout (row s*A + a real iff a < n_in[e]; the others are never read), the results of
         ``predict_padded`` fed the gathered rows of ``scene_arrays`` - NaN in the padded rows.  Every ``n_in`` must be at least 1.
         ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T`` (``jmid_predict_scene_padded_seeded``): every episode draws what it
-        draws alone at its own count, ``noise(seed, episode_ids, K * A, T, n_agents=n_in)``."""
-        E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T, padded=True)
-        k = int(k)
-        fn = getattr(self._lib, "jmid_predict_scene_padded" + sfx)
-        return self._ranked_or_all(fn, (self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision]), E, A, K, T, k)
+        draws alone at its own count, ``noise(seed, episode_ids, K * A, T, n_agents=n_in)``.  ``constraints``: as ``predict_scene``."""
+        return self._predict_scene(True, x_T, k, dt, precision, seed, episode_ids, K, T, constraints)
 
     def forecast_scene_padded(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
-                              episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+                              episode_ids=None, K: Optional[int] = None, T: Optional[int] = None,
+                              constraints: Optional[ChainConstraints] = None):
         """``forecast_scene`` for a resident scene of mixed in-cluster counts (``jmid_forecast_scene_padded`` /
         ``jmid_forecast_scene_padded_seeded``): the arguments of ``predict_scene_padded``, the results of ``forecast_scene`` - no NaN: an
-        in-cluster pedestrian reads its own row, everybody else the constant-velocity row."""
-        return self._forecast_scene("jmid_forecast_scene_padded", True, x_T, k, dt, precision, seed, episode_ids, K, T)
+        in-cluster pedestrian reads its own row, everybody else the constant-velocity row.  ``constraints``: as ``forecast_scene``."""
+        return self._forecast_scene("jmid_forecast_scene_padded", True, x_T, k, dt, precision, seed, episode_ids, K, T, constraints)
 
     def build_scene_stamped(self, stamps: np.ndarray, human_xy: np.ndarray, robot_xy: np.ndarray, time_step: float,
                             horizon: Optional[int] = None, force_all_in_cluster: bool = False,
@@ -770,22 +877,28 @@ class JmidEngine:
         return {k: v[0] for k, v in out.items()} if single else out
 
     def forecast_scene(self, x_T: Optional[np.ndarray], k: int, dt: float = 0.25, precision: str = "f32", seed: Optional[int] = None,
-                       episode_ids=None, K: Optional[int] = None, T: Optional[int] = None):
+                       episode_ids=None, K: Optional[int] = None, T: Optional[int] = None, constraints: Optional[ChainConstraints] = None):
         """``predict_scene`` followed by the result assembly on the device (``jmid_forecast_scene``; the twin of
         ``scene.assemble_forecasts``): x_T [E, K*A, T, 2] -> (forecasts [E, N, k, T+1, 2], log-weights [E, N, k]) float64, per episode
         exactly what ``predict_ret_best()`` returns.  The resident scene must have been built with ``horizon`` = T.  After a one-scene
         build the episode axis of the results is absent.  ``seed`` + ``episode_ids`` [E] with ``x_T=None``, ``K`` and ``T``: x_T is
-        drawn on the device (``jmid_forecast_scene_seeded``)."""
-        return self._forecast_scene("jmid_forecast_scene", False, x_T, k, dt, precision, seed, episode_ids, K, T)
+        drawn on the device (``jmid_forecast_scene_seeded``).  ``constraints`` (``jmid_forecast_scene_constrained``): guidance and repair
+        inside the one call - the ranking and the assembly read the guided, repaired set - and a third value, the ``ChainReport``."""
+        return self._forecast_scene("jmid_forecast_scene", False, x_T, k, dt, precision, seed, episode_ids, K, T, constraints)
 
-    def _forecast_scene(self, entry, padded, x_T, k, dt, precision, seed, episode_ids, K, T):
+    def _forecast_scene(self, entry, padded, x_T, k, dt, precision, seed, episode_ids, K, T, constraints=None):
         E, A, K, T, sfx, nz, _keep = self._scene_noise(x_T, seed, episode_ids, K, T, padded)
         k = int(k)
-        fn = getattr(self._lib, entry + sfx)
         shape = getattr(self, "_scene_shape", None)
         N, single = (shape[1], shape[3]) if shape is not None else (1, False)
         bw = kde_bandwidths(T) if k < K else None
         fc, lw = _out((E, N, max(k, 0), T + 1, 2), np.float64), _out((E, N, max(k, 0)), np.float64)
+        if constraints is not None:
+            mid, report, _keep2 = self._constrained(constraints, E, K)
+            self._compute(self._lib.jmid_forecast_scene_constrained, self._h, E, A, K, T, k, int(padded), *self._constrained_noise(sfx, nz),
+                          float(dt), _lib.PRECISIONS[precision], _ptr(bw), *mid, _ptr(fc), _ptr(lw), *[_ptr(r) for r in report])
+            return (fc[0], lw[0], report) if single else (fc, lw, report)
+        fn = getattr(self._lib, entry + sfx)
         self._compute(fn, self._h, E, A, K, T, k, *nz, float(dt), _lib.PRECISIONS[precision], _ptr(bw), _ptr(fc), _ptr(lw))
         return (fc[0], lw[0]) if single else (fc, lw)
 

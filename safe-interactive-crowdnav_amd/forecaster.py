@@ -62,7 +62,12 @@ sampling - softplus collision steps at ``collision_threshold`` BETWEEN the denoi
 ``jmid_denoise_guided``; include/jmid_hip.h states the rule), so the net's remaining steps run on the corrected state; the route is staged
 and ``self.guide`` [K, 2] holds the last call's rows (``metrics.GUIDE_COLUMNS``).  With ``constraint_type`` the repair follows on the guided
 set; ``walls=True`` takes ``static_obstacles=`` / ``wall_radius=`` into the objective.  Not with ``collision_free_rounds`` (a rerun would
-have to be guided too), ``device_scene`` or ``device_frames`` (the one-entry chains).
+have to be guided too), ``device_scene`` or ``device_frames`` (the one-entry chains) - unless ``constraint_route="chain"``.
+``constraint_route="chain"`` (opt-in; ``"staged"`` is the default, with the refusals above): ``guidance=`` and ``constraint_type=`` ride INSIDE
+the one-entry chains (``JmidEngine.predict(constraints=)`` ... ``forecast_scene(constraints=)``; the ``jmid_*_constrained`` entries) - one
+call per ``predict_ret_best()``, with ``device_scene``, ``device_frames``, ``track_presence`` and ``coast_frames`` too, the bits of the staged
+route, and ``self.guide`` / ``self.repair`` / ``self.repair_causes`` filled from the chain's reports.  The first-call self check and a
+JMID_ERANGE repeat still take the staged route.  Not with ``collision_free_rounds`` (the redraw loop has no chain).
 
 Differences from the reference that a caller can observe:
   * the engine (weights on the GPU) is cached across instances: the reference rebuilds the model and reloads the
@@ -97,7 +102,7 @@ import yaml
 
 from . import scene as SC
 from ._lib import EINVAL, ERANGE
-from .engine import Guidance, JmidEngine, JmidError, wall_segments
+from .engine import ChainConstraints, Guidance, JmidEngine, JmidError, wall_segments
 from .kde import most_likely_samples
 from .metrics import GUIDE_DEFAULTS, rejection_totals, repair_causes
 from .schedule import guidance_weights
@@ -233,6 +238,33 @@ def repair_totals(episode) -> Tuple[int, int, int, int]:
     if not ep.shape[0]:
         return 0, 0, 0, 0
     return int(ep[:, 0].sum()), int(ep[:, 1].sum()), int(ep[:, 0].sum() - ep[:, 1].sum()), int(ep[:, 2].max())
+
+
+CONSTRAINT_ROUTES = ("staged", "chain")
+
+
+def constraint_route_arguments(constraint_route: str, rounds) -> bool:
+    """The ``constraint_route=`` keyword of the forecaster and ``predict_batch`` -> whether guidance and repair ride inside the one-entry
+    chains.  ``"chain"`` is refused with a redraw loop (``collision_free_rounds``: the loop has no chain)."""
+    if constraint_route not in CONSTRAINT_ROUTES:
+        raise ValueError(f"constraint_route must be one of {list(CONSTRAINT_ROUTES)}")
+    if constraint_route == "chain" and rounds:
+        raise ValueError("constraint_route='chain' cannot be combined with collision_free_rounds (the redraw loop has no one-entry chain)")
+    return constraint_route == "chain"
+
+
+def chain_constraints(limits: "Constraints") -> Optional[ChainConstraints]:
+    """The guidance and the repair of ``limits`` as the ``constraints=`` of the engine's chained methods; None with neither."""
+    if limits.guidance is None and limits.repair is None:
+        return None
+    return ChainConstraints(limits.threshold, limits.guidance, limits.repair)
+
+
+def chain_report_causes(report, limits: "Constraints") -> Optional[dict]:
+    """``metrics.repair_causes`` of a constrained chain's report, as ``repair_stage`` gives it: None unless the repair takes walls."""
+    if report.wall is None:
+        return None
+    return repair_causes(report.sample, report.wall, limits.threshold, limits.repair["wall_radius"])
 
 
 class Constraints(NamedTuple):
@@ -389,7 +421,7 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
                  seed: int = 0, episode_id: int = 0, short_history: bool = False, track_presence: bool = False, coast_frames: int = 0,
                  collision_free_rounds: int = 0, collision_threshold: float = 0.2, static_obstacles=None,
                  wall_radius: Optional[float] = None, constraint_type: Optional[str] = None, repair_options: Optional[dict] = None,
-                 guidance: Optional[dict] = None):
+                 guidance: Optional[dict] = None, constraint_route: str = "staged"):
         # (lib_path: another build of the library - tests run both flavours in one process; the product leaves it at None)
         # keyword arguments left at None take the process-wide defaults (``DEFAULTS``; ``install(**defaults)`` sets them for
         # a caller that constructs the class with the reference's two positional arguments only, sicnav_acados.py:998-1000)
@@ -452,9 +484,13 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         # guidance={scale, n_inner, margin, tau, weights, walls, table} (opt-in, every RNG contract): softplus collision steps between the
         # denoise steps (JmidEngine.denoise(guidance=)) - the staged route, not with collision_free_rounds or the one-entry chains;
         # composes with constraint_type: guide, then repair what is left.  guide: the last call's rows [K, 2] (metrics.GUIDE_COLUMNS)
+        # constraint_route="chain" (opt-in): guidance and repair inside the one-entry chains (the jmid_*_constrained entries) wherever the
+        # unconstrained call would take a chain - device_scene and device_frames included; "staged": today's route and refusals
+        self.constraint_route = constraint_route
+        self._chain_constraints = constraint_route_arguments(constraint_route, collision_free_rounds)
         step = None
         if guidance is not None:
-            if device_scene or device_frames:
+            if (device_scene or device_frames) and not self._chain_constraints:
                 raise ValueError("guidance has no one-entry chain: not with device_scene or device_frames")
             with open(mid_config_file) as f:
                 step = int(yaml.safe_load(f)["step_size"])
@@ -693,19 +729,27 @@ class HumanTrajectoryForecasterSim(ForecasterSimSuper):
         route = plan_route(k=k, K=K, A=A, H=H, device_topk=self.device_topk, device_scene=self.device_scene,
                            device_frames=self.device_frames, check=check, short=ff is not None, frames=source == "stamped",
                            tracks=present is not None, collision_free=limits.rounds is not None, repair=limits.repair is not None,
-                           guidance=limits.guidance is not None)
-        result, call = None, dict(dt=self.time_step, precision=self.precision)
+                           guidance=limits.guidance is not None, chain_constraints=self._chain_constraints)
+        result, call, report = None, dict(dt=self.time_step, precision=self.precision), None
+        cons = chain_constraints(limits) if route.run == "chain" else None
+        if cons is not None:      # (the chained methods then return a third value, the report)
+            call["constraints"] = cons
         with self._engine_lock:               # the engine is shared between forecaster instances and not re-entrant
             if self.engine.step != self.step_size or self.engine.sampling != "ddim":
                 self.engine.set_step(self.step_size, "ddim")   # eval_sicnav hard-codes sampling="ddim" (MID/mid.py:333)
             if route.run == "chain":
                 try:
                     if source == "stamped":      # from raw frames, the assembled result itself: nothing left to do on the host
-                        result = self.engine.forecast_scene(x_np, k, **call)
+                        result, report = _split_report(self.engine.forecast_scene(x_np, k, **call))
                     elif sb is None:
-                        rows, logw = self.engine.predict_scene(x_np, k, **call)
+                        (rows, logw), report = _split_report(self.engine.predict_scene(x_np, k, **call))
                     else:
-                        rows, logw = self.engine.predict(sb.x_st, sb.nbr_sum, sb.edge_mask, x_np, sb.p0[None], k, **call)
+                        (rows, logw), report = _split_report(self.engine.predict(sb.x_st, sb.nbr_sum, sb.edge_mask, x_np, sb.p0[None], k, **call))
+                    if report is not None:      # what the staged run fills from its stages' outputs, from the chain's one download
+                        if report.guide is not None:
+                            self.guide = np.asarray(report.guide)[0]
+                        if report.episode is not None:
+                            self.repair, self.repair_causes = repair_totals(report.episode), chain_report_causes(report, limits)
                 except JmidError as e:
                     if not _repeats_in_fp32(e, self.precision):
                         raise
@@ -794,7 +838,7 @@ def scene_source(device_scene: bool, device_frames: bool, short: bool = False, f
 def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, device_scene: bool = False, device_frames: bool = False,
                check: bool = False, short: bool = False, frames: bool = True, batch: bool = False, padded: bool = False,
                resident: bool = False, tracks: bool = False, collision_free: bool = False, repair: bool = False,
-               guidance: bool = False) -> Route:
+               guidance: bool = False, chain_constraints: bool = False) -> Route:
     """Every decision of a call that does not need an array: the flags, k of K samples, A in-cluster pedestrians, horizon H, whether the
     first-call self check is due (``check``), whether the window is short (``short``) and whether the histories are frames (``frames``).
     ``batch``: a count group of ``predict_batch``, ``padded``: its one-call form with A the largest count, ``resident``: that form on the
@@ -803,7 +847,9 @@ def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, devi
     staged (encode -> ``denoise_reject`` -> rank) and the ranking reads the accepted set where the loop left it.
     ``repair``: collision repair (``constraint_type="opt_softplus"``) - a stage between the denoise call and the ranking, so the run is
     staged too (encode -> denoise -> ``repair_collisions`` -> rank).  ``guidance``: guided sampling - the guided denoise call has no
-    one-entry chain either, so the run is staged; with none of the three nothing changes."""
+    one-entry chain either, so the run is staged; with none of the three nothing changes.
+    ``chain_constraints`` (``constraint_route="chain"``): ``repair`` and ``guidance`` ride inside the chain (the constrained entries) and no
+    longer force the staged run; ``collision_free`` and the first-call self check still do.  False: every answer is what it was."""
     scene = scene_source(device_scene, device_frames, short, frames, batch, resident, tracks)
     # the K samples stay on the GPU (only the k kept ones come back) while jmid_topk takes the shape; beyond its limits - the reference
     # has none - the host twin ranks them
@@ -814,9 +860,14 @@ def plan_route(*, k: int, K: int, A: int, H: int, device_topk: bool = True, devi
     else:           # a short window built on the host is staged: jmid_predict has no first_index (a resident one is predict_scene's)
         chain = not (short and scene == "host")
     chain = chain and (on_dev or k == K) and not check        # (the self check compares the staged denoise call's positions)
-    chain = chain and not collision_free and not repair and not guidance
+    chain = chain and not collision_free and (chain_constraints or not (repair or guidance))
     rank = "none" if k >= K else "host" if not on_dev else "device" if check else "device_resident"
     return Route(scene, "chain" if chain else "staged", rank)
+
+
+def _split_report(out):
+    """What a chained engine method returned -> (its two values, the ``ChainReport`` of a constrained call or None)."""
+    return (out[:2], out[2]) if len(out) == 3 else (out, None)
 
 
 def _repeats_in_fp32(err: JmidError, precision: str) -> bool:
@@ -923,7 +974,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                   padded=False, short_history: bool = False, first_frame=None, collision_free_rounds: int = 0,
                   collision_threshold: float = 0.2, stats: Optional[dict] = None, static_obstacles=None,
                   wall_radius: Optional[float] = None, collision_free_padded: bool = False, constraint_type: Optional[str] = None,
-                  repair_options: Optional[dict] = None, guidance: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  repair_options: Optional[dict] = None, guidance: Optional[dict] = None,
+                  constraint_route: str = "staged") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``predict_ret_best()`` for E independent episodes in as few device calls as their cluster sizes allow: the feed
     of the multi-episode evaluation sweeps.
 
@@ -992,6 +1044,11 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     (``engine.denoise(guidance=)``), every group is staged, and ``stats`` gets ``guide`` [E, K, 2] = ``metrics.GUIDE_COLUMNS``, rows in
     input order.  It composes with ``constraint_type``: guide, then repair what is left.  Not with ``collision_free_rounds`` (a rerun
     would have to be guided too), a DDPM table, ``padded=``, ``device_scene`` or ``device_frames`` (the one-entry chains).
+    ``constraint_route="chain"`` (opt-in; ``"staged"`` is everything above): ``guidance=`` and ``constraint_type=`` ride inside the one-entry
+    chains (``engine.forecast_scene(constraints=)``, ``predict_padded(constraints=)``, ``forecast_scene_padded(constraints=)``), so they
+    combine with ``device_frames``, ``padded=True`` and ``padded="resident"`` in one call per group or batch; ``stats`` gets the same keys,
+    filled from the chains' reports.  A group or batch that has no chain (its ranking does not fit the device top-k, an empty cluster) is
+    staged as before.  Not with ``collision_free_rounds``.
     """
     if noise not in ("torch", "device"):
         raise ValueError("noise must be 'torch' or 'device'")
@@ -1000,7 +1057,10 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     sampler = {} if guidance is None else dict(step=engine.step, sampling=engine.sampling)      # (one weight per entry of the engine's table)
     limits = sampling_constraints(int(collision_free_rounds) or None, collision_threshold, static_obstacles, wall_radius, constraint_type,
                                   repair_options, collision_free_padded, guidance=guidance, **sampler)
-    if limits.guidance is not None and (padded or device_scene or device_frames):
+    chained = constraint_route_arguments(constraint_route, collision_free_rounds)
+    cons = chain_constraints(limits) if chained else None
+    kw = {} if cons is None else {"constraints": cons}      # (a chained method then returns a third value, the report)
+    if limits.guidance is not None and (padded or device_scene or device_frames) and not chained:
         raise ValueError("guidance has no one-entry chain: not with padded=, device_scene or device_frames")
     if limits.rounds is not None:
         if padded:
@@ -1035,7 +1095,18 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
     def plan(A, padded=False, resident=False):
         return plan_route(k=k, K=K, A=A, H=H, device_topk=device_topk, device_scene=device_scene, device_frames=device_frames,
                           short=ff is not None, batch=True, padded=padded, resident=resident, collision_free=limits.rounds is not None,
-                          repair=limits.repair is not None, guidance=limits.guidance is not None)
+                          repair=limits.repair is not None, guidance=limits.guidance is not None, chain_constraints=chained)
+
+    def batch_stats(report):
+        """``stats`` of a one-call form from its chain's report: the keys and rows the count groups fill."""
+        if report is None or stats is None:
+            return
+        if report.guide is not None:
+            stats["guide"] = report.guide
+        if report.episode is not None:
+            stats["repair"] = report.episode
+        if report.wall is not None:
+            stats["repair_causes"] = chain_report_causes(report, limits)
 
     def torch_x_T(e, A):
         return torch.randn([K * A, H, 2], generator=torch.Generator().manual_seed(int(seeds[e])))
@@ -1050,7 +1121,9 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
                     x_T, nz = None, dict(seed=int(seed), episode_ids=np.asarray(seeds), K=K, T=H)
                 else:
                     x_T, nz = SC.pad_samples([torch_x_T(e, int(n_in[e])).numpy() for e in range(E)], n_in, int(n_in.max()), K), {}
-                (forecasts, logw), _ = repeat_in_fp32(lambda p: engine.forecast_scene_padded(x_T, k, dt=time_step, precision=p, **nz), precision)
+                ((forecasts, logw), report), _ = repeat_in_fp32(
+                    lambda p: _split_report(engine.forecast_scene_padded(x_T, k, dt=time_step, precision=p, **nz, **kw)), precision)
+                batch_stats(report)
                 return forecasts, logw, b["in_cluster"]
             if not device_frames:
                 b.update(engine.scene_arrays())
@@ -1068,7 +1141,8 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         args = (SC.pad_agents(b["x_st"], inc, A).reshape(E * A, F, 6), SC.pad_agents(b["nbr_sum"], inc, A).reshape(E * A, 2, F, 6),
                 SC.pad_agents(b["edge_mask"], inc, A).reshape(E * A, 2), x_T, SC.pad_agents(b["p0"], inc, A), k, n_in)
         with lock:
-            (rows, lw), _ = repeat_in_fp32(lambda p: engine.predict_padded(*args, dt=time_step, precision=p), precision)
+            ((rows, lw), report), _ = repeat_in_fp32(lambda p: _split_report(engine.predict_padded(*args, dt=time_step, precision=p, **kw)), precision)
+        batch_stats(report)
         return (*SC.assemble_forecasts(inc, rows, lw, b["cv"], pose_now, k, K, n_agents=n_in), inc)
     if limits.padded and n_in.min() >= 1:
         # the staged route on the whole batch: padded inputs, one encode, one rejection loop, one ranking of the accepted set
@@ -1116,8 +1190,15 @@ def predict_batch(engine: JmidEngine, human_xy: np.ndarray, robot_xy: np.ndarray
         if route.run == "chain":
             with lock:              # the group's scenes resident, then predictor + assembly in one entry
                 engine.build_scene(human_xy[eps], robot_xy[eps], time_step, horizon=H, first_frame=None if ff is None else ff[eps], **ab)
-                (forecasts[eps], logw[eps]), _ = repeat_in_fp32(
-                    lambda p: engine.forecast_scene(x_T, k, dt=time_step, precision=p, **nz), precision)
+                ((forecasts[eps], logw[eps]), report), _ = repeat_in_fp32(
+                    lambda p: _split_report(engine.forecast_scene(x_T, k, dt=time_step, precision=p, **nz, **(kw if A else {}))), precision)
+            if report is not None and stats is not None:
+                if report.guide is not None:
+                    stats["guide"][eps] = report.guide
+                if report.episode is not None:
+                    stats["repair"][eps] = report.episode
+            if report is not None and report.wall is not None:
+                causes.append(chain_report_causes(report, limits))
             continue
         if "p0" not in b:           # (device_frames built without reading the encoder inputs back)
             with lock:

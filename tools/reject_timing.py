@@ -11,7 +11,9 @@ interleaved call by call, so clock and thermal drift hit them alike.  Run on the
     python tools/reject_timing.py [--precision f16mx] [--calls 40] [--episodes 4]
 --rule RULE measures the wall predicate instead (section 33), --padded the one-loop form on mixed-count batches (section 34), --repair
 collision repair against the redraw loop (section 35), --repair --rule RULE collision repair with walls on that rule's frames (section 37),
---guide guided sampling against no flag, the repair, both and the redraw loop (section 38; with --rule RULE on that rule's frames, walls in)."""
+--guide guided sampling against no flag, the repair, both and the redraw loop (section 38; with --rule RULE on that rule's frames, walls in),
+--chain the constraints inside the one-entry chains (constraint_route="chain") against the staged route (section 41; with --rule RULE on that
+rule's frames, walls in)."""
 import argparse
 import json
 import os
@@ -378,6 +380,85 @@ def guide_main(args, weights):
     return out
 
 
+def chain_main(args, weights):
+    """--chain: the constraints inside the one-entry chains against the staged route (docs/NOTEBOOK.md section 41).  The forecasters of ONE
+    process on the same frames, seeds and draw numbers, alternating call by call:
+      (a) no flag: the plain chain, and the same held on the staged route
+      (b) constraint_type (the repair), (c) guidance, (d) both - each staged (the default route) and as constraint_route="chain"
+    With --rule RULE the frames are that rule's hallway frames and every constraint takes its walls at --radius.  No gate fixed in advance:
+    a chain is read against the staged forecaster of the same constraints of the same run.  (The logs of section 41 also hold
+    "*_chain_separate_launches" rows: the chain's repair phase was measured once with a repair kernel that evaluates the candidate gate
+    itself against the separate predicate launches, which are what the chain runs; that kernel variant did not pay and is not in the tree.)"""
+    walls = None
+    if args.rule:
+        from safe_interactive_crowdnav_amd import crowd_env
+        walls = crowd_env.static_obstacles(args.rule)[0]
+        if not len(walls):
+            raise SystemExit(f"rule {args.rule!r} has no walls")
+    out = {"threshold": args.threshold, "rule": args.rule, "radius": args.radius if walls is not None else None}
+    for point, (N, K, k, H, step) in POINTS.items():
+        frames = 6 + args.warmup + args.calls
+        if walls is None:
+            sim = EP.simulate_circle_crossing(args.episodes, N, frames, seed=11)
+        else:
+            sim = crowd_env.simulate_hallway(args.episodes, N, frames, seed=11, cfg=crowd_env.HallwayConfig(rule=args.rule))
+        obstacles = {} if walls is None else dict(static_obstacles=walls, wall_radius=args.radius)
+        repair = "opt_softplus" if walls is None else "opt_softplus_walls"
+        gopt = {} if walls is None else {"walls": True}
+        kinds = {"repair": dict(constraint_type=repair), "guidance": dict(guidance=dict(gopt)),
+                 "both": dict(guidance=dict(gopt), constraint_type=repair)}
+        with tempfile.TemporaryDirectory() as td:
+            env, yp = write_configs(td, joint=True, ctx_dim=256, N=N, K=K, k_ret=k, H=H, step=step, time_step=0.25)
+            common = dict(weights=weights, precision=args.precision, self_check=False, rng_compat="device", seed=7, collision_threshold=args.threshold)
+            variants = {"a_chain": HumanTrajectoryForecasterSim(env, yp, **common), "a_staged": Staged(env, yp, **common)}
+            for kind, kw in kinds.items():
+                variants[kind + "_staged"] = HumanTrajectoryForecasterSim(env, yp, **kw, **obstacles, **common)
+                variants[kind + "_chain"] = HumanTrajectoryForecasterSim(env, yp, constraint_route="chain", **kw, **obstacles, **common)
+        ms = {name: [] for name in variants}
+        fix = {name: np.zeros(3, dtype=np.int64) for name in variants}
+        guided = {name: 0 for name in variants}
+        for e in range(args.episodes):
+            for f in variants.values():
+                f.prev_states, f.prev_robot_states = [[] for _ in range(N)], []
+            for i in range(frames):
+                for f in variants.values():
+                    f.update_state_hists(St(sim["robot_xy"][e, i]), [St(p) for p in sim["human_xy"][e, i]], float(sim["stamps"][i]))
+                if i < 5:
+                    continue
+                order = list(variants.items())
+                order = order[i % len(order):] + order[:i % len(order)]     # alternate who goes first
+                for name, f in order:
+                    t0 = time.perf_counter()
+                    f.predict_ret_best()
+                    dt = 1e3 * (time.perf_counter() - t0)
+                    if i < 5 + args.warmup:
+                        continue
+                    ms[name].append(dt)
+                    if f.repair is not None:
+                        fix[name] += np.array(f.repair[:3])
+                    if f.guide is not None:
+                        guided[name] += int((f.guide[:, 0] > 0).sum())
+        n = len(ms["a_chain"])
+        res = {name: {"median_ms": round(float(np.median(v)), 3), "p10_ms": round(float(np.percentile(v, 10)), 3),
+                      "p90_ms": round(float(np.percentile(v, 90)), 3)} for name, v in ms.items()}
+        for name in variants:
+            if fix[name][0]:
+                res[name].update(share_candidates=round(float(fix[name][0]) / (n * K), 5), share_repaired=round(float(fix[name][1]) / (n * K), 5))
+            if guided[name]:
+                res[name]["share_guided"] = round(float(guided[name]) / (n * K), 5)
+        res["calls"] = n
+        res["a_staged_minus_chain_ms"] = round(res["a_staged"]["median_ms"] - res["a_chain"]["median_ms"], 3)
+        for kind in kinds:
+            res[kind + "_staged_minus_chain_ms"] = round(res[kind + "_staged"]["median_ms"] - res[kind + "_chain"]["median_ms"], 3)
+            res[kind + "_chain_minus_plain_chain_ms"] = round(res[kind + "_chain"]["median_ms"] - res["a_chain"]["median_ms"], 3)
+        res["erange_fallbacks"] = sum(f.erange_fallbacks for f in variants.values())
+        res["workload"] = (f"N={N}, K={K} -> {k}, H={H}, {step} steps, {args.precision}, " + ("ORCA circle crossing" if walls is None else f"{args.rule} frames, wall radius {args.radius}") +
+                           f", {args.episodes} episodes, threshold {args.threshold}")
+        out[point] = res
+        print(point, json.dumps(res), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16mx")
@@ -390,13 +471,17 @@ def main():
     ap.add_argument("--padded", action="store_true", help="predict_batch on mixed-count scenes: one loop per count against collision_free_padded")
     ap.add_argument("--repair", action="store_true", help="collision repair (constraint_type='opt_softplus') against collision_free_rounds=3 and no flag")
     ap.add_argument("--guide", action="store_true", help="guided sampling (guidance=) against no flag, the repair, both and collision_free_rounds=3; with --rule: with its walls")
-    ap.add_argument("--threshold", type=float, default=0.2, help="with --padded / --repair / --guide: the collision threshold in metres")
+    ap.add_argument("--chain", action="store_true", help="guidance and repair inside the one-entry chains (constraint_route='chain') against the staged route; "
+                    "with --rule: with its walls")
+    ap.add_argument("--threshold", type=float, default=0.2, help="with --padded / --repair / --guide / --chain: the collision threshold in metres")
     args = ap.parse_args()
     weights = JMIDWeights.from_seed(NetDims(ctx_dim=256), 5)
-    if args.rule or args.padded or args.repair or args.guide:
+    if args.rule or args.padded or args.repair or args.guide or args.chain:
         if args.padded and "--episodes" not in sys.argv:
             args.episodes = 8
-        if args.guide:
+        if args.chain:
+            out = chain_main(args, weights)
+        elif args.guide:
             out = guide_main(args, weights)
         elif args.repair and args.rule:
             out = repair_walls_main(args, weights)
