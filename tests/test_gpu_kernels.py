@@ -88,9 +88,17 @@ def test_attention_matches_float64(engine, nseq, S, precision):
     assert np.abs(out - ref).max() <= TOL[precision] * max(1.0, np.abs(ref).max())
 
 
-def test_attention_online_softmax_rescale_branch(engine):
-    """A key whose score dwarfs everything seen so far must rescale the running state correctly:
-    spike one key late in the sequence (cdna guide rule: force the rare branch)."""
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_attention_online_softmax_rescale_branch_at_head_sizes_32_and_64(head_engine, precision):
+    test_attention_online_softmax_rescale_branch(head_engine, precision)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_attention_online_softmax_rescale_branch(engine, precision):
+    """A key whose score dwarfs everything seen so far must rescale the running state correctly, in every mode's kernel (the default
+    precision of dbg_attention is the exact-fp32 kernel alone): spike one key late in the sequence (cdna guide rule: force the rare
+    branch), and a smaller one in an earlier tile that is not the first - query 17's reference maximum moves twice, by 3 sqrt(hd) and by
+    another 3 sqrt(hd) nats (17 log2 units at head 16: past the lazy rule's 8; 49 at head 128: past the threshold rule's 14)."""
     d = 2 * engine.dims.ctx_dim
     nh = engine.dims.nhead
     hd = d // nh
@@ -98,11 +106,14 @@ def test_attention_online_softmax_rescale_branch(engine):
     rng = np.random.default_rng(0)
     qkv = rng.standard_normal((S, 3 * d)).astype(np.float32)
     qkv[150, d:2 * d] = 6.0 * qkv[17, :d]  # key 150 aligned with query 17 -> huge score in a late tile
-    out = engine.dbg_attention(qkv, 1, S)
+    qkv[70, d:2 * d] = 3.0 * qkv[17, :d]   # ... and half of it in tile 2
+    out = engine.dbg_attention(qkv, 1, S, precision=precision)
     t = torch.from_numpy(qkv).double().view(1, S, 3, nh, hd)
     q, k, v = (t[:, :, i].permute(0, 2, 1, 3) for i in range(3))
     ref = torch.nn.functional.scaled_dot_product_attention(q, k, v).permute(0, 2, 1, 3).reshape(S, d).numpy()
-    assert np.abs(out - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max())
+    err = np.abs(out - ref).max()
+    print(f"rescale branch d={d} head {hd} [{precision}]: |err| {err:.3e} (allowed {TOL[precision] * max(1.0, np.abs(ref).max()):.3e})")
+    assert err <= TOL[precision] * max(1.0, np.abs(ref).max())
 
 
 @pytest.mark.parametrize("M", [1, 5, 1200])

@@ -50,14 +50,16 @@ def worst(err, bound, rows):
     return float(r[i]), row, int(i[1])
 
 
-def check_layer(d, joint, shape, n_agents, precision, layer, last, expect=None, nhead=4):
-    """One jmid_dbg_layer call, every stage present against its reference.  Returns the plan."""
+def check_layer(d, joint, shape, n_agents, precision, layer, last, expect=None, nhead=4, X=None, report=None):
+    """One jmid_dbg_layer call, every stage present against its reference.  Returns (plan, stages).  X: another input than the case's
+    layer_input; report: a dict that receives (ref, bound) of the attention stage ("attention") and of stage 3 ("norm1")."""
     eng, w = get_engine(d, joint, nhead)
     assert eng.dims.nhead == nhead and eng.dims.d_model == d
     E, A, K, T = shape
     M = E * A * K * T
     nseq, S = (E, K * A * T) if joint else (E * K * A, T)
-    X = R.layer_input(shape, n_agents, d)
+    if X is None:
+        X = R.layer_input(shape, n_agents, d)
     stages, plan = eng.dbg_layer(X, layer, shape, precision, n_agents=n_agents, last=last)
     tag = f"{'jmid' if joint else 'imid'} {shape} n={n_agents} d={d}{'' if nhead == 4 else f' nhead={nhead}'} [{precision}] layer {layer}{' (last)' if last else ''}"
     print(f"{tag} plan: {plan}")
@@ -105,6 +107,8 @@ def check_layer(d, joint, shape, n_agents, precision, layer, last, expect=None, 
         r3 = R.ln_stage(*stages[0], att[0], np.zeros_like(att[0]), lw["out_w"], lw["out_b"], lw["n1_g"], lw["n1_b"], spec["out_proj"],
                         spec["x_rep"], A_err=att[1], A_plain=att[2])
     judge(3, *r3, real)
+    if report is not None:
+        report.update(attention=att[:2], norm1=r3[:2])
     judge(4, *R.gemm_stage(*stages[3], lw["l1_w"], lw["l1_b"], spec["linear1"], True, spec["h1_rep"]), real)
     judge(5, *R.ln_stage(*stages[3], *stages[4], lw["l2_w"], lw["l2_b"], lw["n2_g"], lw["n2_b"], spec["linear2"], spec["x_last_rep"]), real)
     assert not failures, (tag, failures)
@@ -112,7 +116,7 @@ def check_layer(d, joint, shape, n_agents, precision, layer, last, expect=None, 
     for key, want in (expect or {}).items():
         ok = seen[key] in want if isinstance(want, (tuple, list)) else seen[key] == want
         assert ok, (tag, key, seen[key], want)
-    return plan
+    return plan, stages
 
 
 def both_layers(d, joint, shape, n_agents, precision, expect=None, nhead=4):

@@ -110,10 +110,88 @@ def emu_qkv(X, W, b, spec, qscale, joint_split, **mut):
     return (read_hi, read_lo), dict(Q=Q, K=Kp, V=V)
 
 
-def emu_attention(kern, read, nseq, S, nhead, valid, spec, nsplit=1, admit=None, drop_range=None, shift_last_v=False):
+def emu_lazy_tile(rule, spec, s, m, l, o, vh, vl, first, fault):
+    """One key tile under a lazy rule: s [S, keys] fp32 logits (thr14: already minus m - the accumulator started there), the state
+    m, l [S, 1], o [S, hd] -> (m, l, o, moved [S, 1]).  first: the range's first computed tile."""
+    f32 = np.float32
+
+    def form(x):
+        with np.errstate(over="ignore"):
+            p = np.exp2(x).astype(f32)
+            if spec["p_rep"] == "p1":      # the packed fp16 P, and the row sum of exactly those values (dot2_ones)
+                ph = R.f16(p)
+                return p, ph, None, ph.sum(1, keepdims=True, dtype=f32)
+            if spec["p_rep"] == "split":
+                ph = R.f16_rtz(p)
+                return p, ph, R.f16_rtz(p - ph), p.sum(1, keepdims=True, dtype=f32)
+            return p, p, None, p.sum(1, keepdims=True, dtype=f32)
+
+    def pv(o, ph, pl):
+        o = o + ph @ vh
+        if pl is not None:
+            o = o + pl @ vh
+        if spec["v_lo"] and spec["p_rep"] != "f32":
+            o = o + ph @ vl
+        return o
+
+    with np.errstate(all="ignore"):
+        tmax = s.max(1, keepdims=True)
+        if rule == "lazy8":
+            m_new = np.where(tmax > m + f32(8), tmax, m).astype(f32)
+            alpha = np.exp2(m - m_new).astype(f32)
+            moved = (m_new != m) & (not first)
+            p, ph, pl, _ = form(s - m_new)
+            psum = p.sum(1, keepdims=True, dtype=f32)      # (:209, :776-783: the fp32 row sum, also where P enters P . V as one fp16 plane)
+            l = (l if fault == "no_l_rescale" else l * alpha) + psum
+            o = pv(o if fault == "no_o_rescale" else o * alpha, ph, pl)
+            return m_new, l, o, moved
+        trip = np.ones_like(m, bool)
+        if not first:
+            p, ph, pl, psum = form(s)
+            tested = psum
+            if fault == "half_sum":        # lane half 0 holds keys frag_row(r, 0) = (r & 3) + 8 (r >> 2): its sum alone
+                mine = (np.arange(s.shape[1]) % 8) < 4
+                tested = (p if pl is not None or spec["p_rep"] == "f32" else ph)[:, mine].sum(1, keepdims=True, dtype=f32)
+            trip = ~(tested <= f32(16384.0))
+        if first or trip.any():
+            delta = np.where(trip, tmax, f32(0)).astype(f32)
+            if fault == "move_whole_wave" and not first:      # delta = tmax for every row of a wave (32 queries) one of whose rows tripped
+                for w0 in range(0, len(trip), 32):
+                    if trip[w0:w0 + 32].any():
+                        delta[w0:w0 + 32] = tmax[w0:w0 + 32]
+            if not first or fault == "first_rescale":
+                alpha = np.exp2(-delta).astype(f32)
+                if fault != "no_o_rescale":
+                    o = o * alpha
+                if fault != "no_l_rescale":
+                    l = l * alpha
+            m = (m + delta).astype(f32)
+            if first or fault != "stale_p":
+                _, ph, pl, psum = form(s - delta)
+        return m, l + psum, pv(o, ph, pl), trip & (not first)
+
+
+SLOW_PATH_FAULTS = ("no_o_rescale", "no_l_rescale", "move_whole_wave", "half_sum", "stale_p", "first_rescale", "merge_true_max",
+                    "masked_range_zero")
+
+
+def emu_attention(kern, read, nseq, S, nhead, valid, spec, nsplit=1, admit=None, drop_range=None, shift_last_v=False, rule="strict",
+                  ranges=None, record=None, fault=None):
     """stage 2 in fp32: 32-key tiles, online softmax in log2 units on the pre-scaled Q, P rounded as the mode stores it, O and l summed
     tile by tile, split-KV ranges merged.  admit = (first query, last query, seq, key): those queries see that masked key;
-    drop_range: the keys of one split-KV range never arrive; shift_last_v: V^T of the last key is read one column on."""
+    drop_range: the keys of one split-KV range never arrive; shift_last_v: V^T of the last key is read one column on.
+    rule: how the reference maximum moves (tests/softmax_cases.py) - "strict" m = max(m, tile maximum); "lazy8" attn_f16x3.hpp:203 only
+    past m + 8; "thr14" attn_f16x3.hpp:694-754: the logits accumulate onto -m, P is formed optimistically, the row sum of the P actually used
+    (the packed fp16 sum in "p1") says which rows move, O and l of those take 2^-delta, P is formed again; a range's first computed
+    tile sets m from the placeholder 0 without a rescale; a zero mask word is skipped.  ranges: [begin tile, end tile) per split-KV
+    range (default: the nsplit equal parts this file always used).  record: a dict that receives "moved" [nseq, nhead, S, tiles] and
+    "first".  fault: one of SLOW_PATH_FAULTS, a wrong slow path / merge."""
+    assert rule in ("strict", "lazy8", "thr14") and (fault is None or fault in SLOW_PATH_FAULTS)
+    lazy = rule != "strict"
+    ntile = (S + 31) // 32
+    if record is not None:
+        record["moved"] = np.zeros((nseq, nhead, S, ntile), bool)
+        record["first"] = np.zeros((nseq, nhead, S, ntile), bool)
     f32 = np.float32
     M = nseq * S
     if kern is None:           # fp32 Q, K, V (F32; iMID)
@@ -140,16 +218,21 @@ def emu_attention(kern, read, nseq, S, nhead, valid, spec, nsplit=1, admit=None,
             if admit is not None and admit[2] == n:
                 ok[admit[0]:admit[1], admit[3]] = True
             bounds = np.linspace(0, (S + 31) // 32, nsplit + 1).astype(int) * 32
-            parts = []
-            for sp in range(nsplit):
-                m = np.full((S, 1), -np.inf, f32)
+            spans = [(bounds[sp], bounds[sp + 1]) for sp in range(nsplit)] if ranges is None else [(32 * a, 32 * b) for a, b in ranges]
+            parts, tops = [], []
+            for sp, (k_lo, k_hi) in enumerate(spans):
+                m = np.full((S, 1), 0.0 if rule == "thr14" else -np.inf, f32)
                 l = np.zeros((S, 1), f32)
                 o = np.zeros((S, hd), f32)
-                for k0 in range(bounds[sp], min(bounds[sp + 1], S), 32):
+                seen = False
+                true_max = np.full((S, 1), -np.inf, f32)
+                for k0 in range(k_lo, min(k_hi, S), 32):
                     if drop_range is not None and drop_range == sp:
                         continue
                     ks = slice(k0, min(k0 + 32, S))
-                    s = np.zeros((S, ks.stop - k0), f32)
+                    if lazy and not ok[:, ks].any():          # a zero mask word: the tile is skipped whole
+                        continue
+                    s = np.zeros((S, ks.stop - k0), f32) if rule != "thr14" else np.repeat(-m, ks.stop - k0, 1)
                     for c0 in range(0, hd, 16):
                         cs = slice(c0, c0 + 16)
                         s = s + qh[:, cs] @ kh[ks, cs].T
@@ -162,7 +245,18 @@ def emu_attention(kern, read, nseq, S, nhead, valid, spec, nsplit=1, admit=None,
                             s = s + ql[:, cs] @ head(k8h, n, h)[ks, cs].T
                             s = s + head(q8h, n, h)[:, cs] @ kl[ks, cs].T
                     s = np.where(ok[:, ks], s, f32(-np.inf))
+                    if lazy:
+                        true_max = np.maximum(true_max, s.max(1, keepdims=True) + (m if rule == "thr14" else f32(0)))
+                        first = not seen
+                        m, l, o, moved = emu_lazy_tile(rule, spec, s, m, l, o, vh[ks], vl[ks], first, fault)
+                        seen = True
+                        if record is not None:
+                            record["moved"][n, h, :, k0 // 32] = moved[:, 0]
+                            record["first"][n, h, :, k0 // 32] = first
+                        continue
                     m_new = np.maximum(m, s.max(1, keepdims=True))
+                    if record is not None:
+                        record["moved"][n, h, :, k0 // 32] = (np.isfinite(m) & (m_new > m))[:, 0]
                     safe = np.where(np.isfinite(m_new), m_new, f32(0))
                     alpha = np.where(np.isfinite(m), np.exp2(m - safe), f32(0)).astype(f32)
                     p = np.exp2(s - safe).astype(f32)
@@ -184,12 +278,18 @@ def emu_attention(kern, read, nseq, S, nhead, valid, spec, nsplit=1, admit=None,
                     if spec["v_lo"] and spec["p_rep"] != "f32":
                         o = o + ph @ vl[ks]
                     m = m_new
+                if lazy and not seen:      # the range computed no tile: (-inf, 0) to the merge, attn_f16x3.hpp:893
+                    m = np.full((S, 1), 0.0 if fault == "masked_range_zero" else -np.inf, f32)
                 parts.append((m, l, o))
-            if nsplit == 1:
+                tops.append(true_max)
+            if len(parts) == 1:
                 m, l, o = parts[0]
             else:
                 mm = np.max([p_[0] for p_ in parts], 0)
                 ws = [np.where(np.isfinite(p_[0]), np.exp2(p_[0] - mm), f32(0)).astype(f32) for p_ in parts]
+                if fault == "merge_true_max":      # the weights from the ranges' true maxima: O_i and l_i stand on the lazy m_i
+                    with np.errstate(invalid="ignore"):
+                        ws = [np.where(np.isfinite(t_), np.exp2(t_ - np.max(tops, 0)), f32(0)).astype(f32) for t_ in tops]
                 l = sum(w * p_[1] for w, p_ in zip(ws, parts))
                 o = sum(w * p_[2] for w, p_ in zip(ws, parts))
             out[n * S:(n + 1) * S, h * hd:(h + 1) * hd] = o * (f32(1) / l)
@@ -224,7 +324,10 @@ class Layer:
     """The emulated correct layer of one case and mode, every stage fed the emulated output of the stage before it, with the reference
     and bound of every stage - made once, shared by the correct-kernel test and the mutations."""
 
-    def __init__(self, shape, n_agents, joint, d, nhead, precision):
+    def __init__(self, shape, n_agents, joint, d, nhead, precision, X=None, rule="strict", ranges=None, plan=None, upto=5, stage1=None):
+        """X: another input than the case's layer_input; rule, ranges: emu_attention's; plan: words of host_plan to replace (a knob);
+        upto = 2: the stages after attention are not made (tests/test_softmax_paths_host.py judges attention alone); stage1: (st[0],
+        st[1], kern) of another Layer with the same input, mode and Q / K / V representations - the in_proj emulation is not repeated"""
         E, A, K, T = shape
         self.shape, self.n_agents, self.joint, self.d, self.precision = shape, n_agents, joint, d, precision
         self.M, self.nhead, self.hd = E * A * K * T, nhead, d // nhead
@@ -232,15 +335,24 @@ class Layer:
         self.w = weights(d)
         self.real = R.real_rows(n_agents, E, A, K, T)
         self.valid = R.key_valid(n_agents, E, A, K, T) if joint else np.ones((self.nseq, self.S), bool)
-        self.plan = host_plan(precision, joint, d, self.M, n_agents is not None, nhead)
+        self.plan = dict(host_plan(precision, joint, d, self.M, n_agents is not None, nhead), **(plan or {}))
+        self.rule, self.ranges, self.record = rule, ranges, {}
         self.spec = R.stage_specs(precision, joint, self.plan, last=False)
         self.qscale = R.LOG2E / np.sqrt(self.hd)
         self.split_joint = joint and precision != "f32"
         self.nsplit = 3 if (joint and precision != "f32" and self.hd == 128 and self.S >= 192) else 1
+        if ranges is not None:
+            self.nsplit = len(ranges)
         w, sp = self.w, self.spec
-        self.st = {0: store(make_x(shape, n_agents, d), "f32" if precision == "f32" else sp["x_rep"])}
-        self.st[1], self.kern = self.qkv()
-        self.st[2] = self.attention()
+        self.st = {0: store(make_x(shape, n_agents, d) if X is None else X, "f32" if precision == "f32" else sp["x_rep"])}
+        if stage1 is not None:
+            self.st[0], self.st[1], self.kern = stage1
+        else:
+            self.st[1], self.kern = self.qkv()
+        self.st[2] = self.attention(record=self.record)
+        self.ref = {}
+        if upto <= 2:
+            return
         self.st[3] = emu_ln(self.st[0], self.st[2], w["out_w"], w["out_b"], w["n1_g"], w["n1_b"], sp["out_proj"], sp["x_rep"])
         self.st[4] = emu_linear1(self.st[3], w["l1_w"], w["l1_b"], sp["linear1"], sp["h1_rep"])
         self.st[5] = emu_ln(self.st[3], self.st[4], w["l2_w"], w["l2_b"], w["n2_g"], w["n2_b"], sp["linear2"], sp["x_last_rep"])
@@ -254,7 +366,7 @@ class Layer:
 
     def attention(self, kern=None, read=None, **mut):
         return emu_attention(self.kern if kern is None else kern, self.st[1] if read is None else read, self.nseq, self.S, self.nhead,
-                             self.valid, self.spec, nsplit=mut.pop("nsplit", self.nsplit), **mut)
+                             self.valid, self.spec, nsplit=mut.pop("nsplit", self.nsplit), rule=self.rule, ranges=self.ranges, **mut)
 
     def reference(self, s):
         """(ref, bound) of stage s from the emulated planes of the stage(s) before it"""
